@@ -444,6 +444,18 @@ def _cpu_model():
     return "unknown"
 
 
+def dump_tick_records(out_dir, records):
+    """--dump-outputs: the 96-byte TickResult records (csrc/reloc_internal.h) of one step's frames, one float64 .npy per
+    field, frame order.  pad[0] (the host record's sequence stamp) is bookkeeping, not a result, and is left out."""
+    rec = np.ascontiguousarray(records).reshape(len(records), 96)
+    f64, i32 = rec.view(np.float64), rec.view(np.int32)
+    fields = dict(anchor_pose=f64[:, 0:7], reproj=f64[:, 7], n_inliers=i32[:, 16], lm_idx=i32[:, 17], outcome=i32[:, 18],
+                  n_candidates=i32[:, 19], n_features=i32[:, 20], relocating=i32[:, 21])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in fields.items():
+        np.save(os.path.join(out_dir, f"tick_{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def launch_plan(args, argv, env):
     """What `python bench.py --gpus N` has to do before anything touches the GPU (BASELINE.json north_star: frames/s at 1, 2, 4
     and 8 GPUs; the driver's N > 1 line is `python -m torch.distributed.run ... bench.py --gpus N`, a bare `python bench.py
@@ -522,14 +534,24 @@ def main(argv=None):
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the torch.distributed group at world size 1 too and route barrier / all_reduce / both\n"
                          "all-gathers of --shard-db through it (RCCL with --backend nccl) instead of the single-rank shortcut")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the result records of the last timed step's frames as DIR/<field>.npy\n"
+                         "(float64), so that two builds can be compared output for output; default workload only")
     argv = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
+    if args.dump_outputs and (args.shard_db or args.matrix_only):
+        raise SystemExit("bench.py: --dump-outputs covers the default workload, not --shard-db / --matrix-only")
     plan = launch_plan(args, argv, os.environ)
     if plan[0] == "error":
         raise SystemExit("bench.py: " + plan[1])
     if plan[0] == "spawn":
         import subprocess
-        r = subprocess.run(plan[1], cwd=ROOT)          # the ranks print on this process's stdout / stderr
+        cmd = plan[1]
+        if args.dump_outputs:                          # the ranks run in ROOT: hand them the directory as the caller meant it
+            cmd = cmd + ["--dump-outputs", os.path.abspath(args.dump_outputs)]
+        r = subprocess.run(cmd, cwd=ROOT)              # the ranks print on this process's stdout / stderr
         raise SystemExit(r.returncode)
     global W, H
     if args.size == "720p":
@@ -636,6 +658,7 @@ def main(argv=None):
                                        last_inliers=int(rec[B - 1, 16]))
 
     elapsed, per_step, outcomes = timed(False)
+    last_records = np.array(results)                                      # the last timed step's records, before later runs overwrite them
     total_frames = world * B * args.steps
     ingest = None
     if not args.no_ingest:
@@ -817,6 +840,8 @@ def main(argv=None):
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
+        if args.dump_outputs:
+            dump_tick_records(args.dump_outputs, last_records)
         print(json.dumps(result))
 
 

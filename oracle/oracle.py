@@ -9,15 +9,18 @@ The C files cite the reference call sites they restate; parity with OpenCV itsel
 """
 from __future__ import annotations
 
+import atexit
 import ctypes as C
 import os
+import shutil
 import subprocess
+import tempfile
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "_build", "libreloc_oracle.so")
-_FAST_PATH = os.path.join(_HERE, "_build", "libreloc_oracle_fast.so")
+_fast_dir = None
 _lib = None
 _libs = {}
 
@@ -36,9 +39,15 @@ def build(force: bool = False) -> str:
 
 
 def build_fast() -> str:
-    """The timing-only -O3 -march=native build (bench.py cpu_baseline); compiled on the machine that runs it."""
-    subprocess.run(["make", "-C", _HERE, "-B", "fast"], check=True, stdout=subprocess.DEVNULL)
-    return _FAST_PATH
+    """The timing-only -O3 -march=native build (bench.py cpu_baseline); compiled on the machine that runs it, into a
+    directory of this process's own (removed at exit): the tree may belong to whoever built it and be read-only here."""
+    global _fast_dir
+    if _fast_dir is None:
+        _fast_dir = tempfile.mkdtemp(prefix="reloc_oracle_fast_")
+        atexit.register(shutil.rmtree, _fast_dir, True)
+    out = os.path.join(_fast_dir, "libreloc_oracle_fast.so")
+    subprocess.run(["make", "-C", _HERE, "-B", "fast", f"FAST={out}"], check=True, stdout=subprocess.DEVNULL)
+    return out
 
 
 def select(fast: bool):
@@ -46,9 +55,8 @@ def select(fast: bool):
     global _lib
     key = "fast" if fast else "strict"
     if key not in _libs:
-        if fast:
-            build_fast()      # always, once per process: -march=native is for THIS machine, and a copy that travelled here may be stale
-        _libs[key] = _load(_FAST_PATH if fast else build())
+        # fast: built always, once per process: -march=native is for THIS machine, and a copy that travelled here may be stale
+        _libs[key] = _load(build_fast() if fast else build())
     _lib = _libs[key]
 
 

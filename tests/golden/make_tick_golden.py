@@ -154,7 +154,7 @@ def drive(mt, module, scene, ticks, fixed_ts, before_tick=None):
 
 
 def run(cv2_obj):
-    """returns the golden dict; also used by tests/test_reference_dropin.py"""
+    """returns the golden dict"""
     from nclt_slam_project_amd import synth
     install_stubs(cv2_obj)
     R = load(os.path.join(REF_COMMON, "visual_landmark_recorder.py"), "ref_recorder")

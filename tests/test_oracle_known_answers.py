@@ -3,6 +3,7 @@ to, so it must itself be checked): closed forms, literal per-pixel restatements 
 Python on small inputs, and planted geometry.  Parity with OpenCV binaries is UNPINNED (OpenCV is not
 installable here and the reference holds no fixtures for this path)."""
 import math
+import os
 
 import numpy as np
 import pytest
@@ -375,3 +376,11 @@ def test_lm_stop_rule_leaves_less_than_1e5_on_noisy_problems(oracle):
         n_checked += 1
     assert n_checked >= 100
     assert worst_t < 1e-5 and worst_a < 1e-5, (worst_t, worst_a)
+
+
+def test_timing_build_is_made_outside_the_tree(oracle):
+    """bench.py's cpu_baseline compiles the -march=native build in the process that times it, which may not be allowed
+    to write into a tree someone else built: the library goes to a directory of that process's own."""
+    path = oracle.build_fast()
+    assert os.path.isfile(path)
+    assert not os.path.abspath(path).startswith(os.path.dirname(os.path.abspath(oracle.__file__)) + os.sep)
