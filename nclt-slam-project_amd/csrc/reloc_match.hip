@@ -12,8 +12,8 @@
 //   - the accumulate form  v_bcnt_u32_b32 D, S0, S1 (D = popcount(S0) + S1)  keeps a 256-bit pair
 //     at 8 xor + 8 bcnt (about 54 cycles per 64 pairs per SIMD: the floor of this problem);
 //   - the argmin bookkeeping uses ONE 16-bit key per pair for both directions
-//     (distance << 7 | row-in-chunk << 3 | column slot) with v_lshlrev_b16, v_or_b32 and two
-//     v_min_u16, all in the cheap class.
+//     (distance << 7 | row-in-chunk << 3 | column slot), built by one v_fmaak_f32 on the f32-denormal
+//     bit patterns (see key_fma) and reduced with two v_min_u16, all in the cheap class.
 // Hot kernel (k_db_scan): a wave keeps all 512 current-frame descriptors (8 per lane, 64 VGPRs);
 // a database record's teach rows are wave-uniform, arrive through the scalar cache
 // (s_load_dwordx8, the fetch of row t+1 issued as soon as row t has landed) and feed the VALU as
@@ -47,10 +47,16 @@ __device__ __forceinline__ u32 min_u16(u32 a, u32 b)
     asm("v_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
-__device__ __forceinline__ u32 shl7_u16(u32 a)
+// The scan's argmin key d << 7 | idx in ONE full-rate instruction: d < 2^9 and the key < 2^16, so read as f32 bit patterns
+// d, idx and the key are positive denormals (x * 2^-149) and d * 128.0f + idx is exact -- the result's bit pattern IS the
+// integer key.  Needs f32 denormals kept (.amdhsa_float_denorm_mode_32 3, the default without fast-math; guarded by
+// tests/test_scan_denormals.py): flushed, every key would be 0.  c128 = 128.0f in a VGPR (v_fmaak_f32's multiplicand must
+// be one); idx is the literal.
+template <u32 IDX>
+__device__ __forceinline__ u32 key_fma(u32 d, u32 c128)
 {
     u32 r;
-    asm("v_lshlrev_b16 %0, 7, %1" : "=v"(r) : "v"(a));
+    asm("v_fmaak_f32 %0, %1, %2, %3" : "=v"(r) : "v"(d), "v"(c128), "n"(IDX));
     return r;
 }
 __device__ __forceinline__ u32 ham8(const u32 q[8], const uint4 a, const uint4 b, u32 init)
@@ -190,15 +196,16 @@ __device__ __forceinline__ void static_for(F &&f) { static_for_impl(f, std::make
 // One 16-bit key per pair serves both directions: distance << 7 | row-in-chunk << 3 | column slot.
 // Among the rows of one column the slot bits are equal, so the minimum is (distance, row); among the
 // columns of one row the row bits are equal, so the minimum is (distance, slot).  Per pair that is
-// shift + or + 2 min on top of the 16 instructions of the distance.
+// one v_fmaak_f32 (key_fma) + 2 v_min_u16 on top of the 16 instructions of the distance (through round 4: v_lshlrev_b16 +
+// v_or_b32 for the key; the row's 8-way minimum with v_min3_f32 was measured and dropped, profiles/README.md
+// "Dropped experiments" #9).
 template <int NJ, int R, bool FLEX>
 __device__ __forceinline__ void scan_chunk(const uint4 *__restrict__ rec, int n, int tc, int nr, const u32 (&q)[NJ][8],
                                            u32 colbase, u32 *rowkey, u32 *colbest, bool single_cb, int lane)
 {
     // (column minima in LDS instead of registers: measured and dropped, profiles/README.md "Dropped experiments" #1)
-    u32 cb16[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) cb16[j] = 0xFFFFu;
+    u32 cb16[NJ];                                                      // seeded by row 0, which every chunk has (nr >= 1)
+    const u32 c128 = 0x43000000u;                                      // 128.0f, key_fma's multiplicand
     // The R row keys are reduced by a register-tile butterfly, but AS THEY COME: the rows of the chunk
     // are visited in bit-reversed order (0, R/2, R/4, 3R/4, ...), so the two operands of every butterfly node are
     // finished right after each other and at most log2(R) + 1 partial results are alive instead of R keys -- 11
@@ -220,17 +227,17 @@ __device__ __forceinline__ void scan_chunk(const uint4 *__restrict__ rec, int n,
         if (i + 1 < R) { na = rec[2 * row_of(i + 1)]; nb = rec[2 * row_of(i + 1) + 1]; }   // ... the next one on its way
         __builtin_amdgcn_sched_barrier(0);
         u32 best = 0x7FFFFFu;                                         // a row the chunk does not have: loses every minimum
-        if (!FLEX || t < nr) {                                           // wave-uniform
+        if (!FLEX || t == 0 || t < nr) {                                 // wave-uniform
             const u32 w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
             u32 h[NJ];
             ham8_cols<NJ>(q, w, h);                                    // NJ accumulator chains, order pinned
-#pragma unroll
-            for (int j = 0; j < NJ; j += 2) {
-                const u32 k0 = shl7_u16(h[j]) | (u32)(t * 8 + j), k1 = shl7_u16(h[j + 1]) | (u32)(t * 8 + j + 1);
-                cb16[j] = min_u16(cb16[j], k0);                        // best row of column j
-                cb16[j + 1] = min_u16(cb16[j + 1], k1);
+            static_for<NJ / 2>([&](auto jc_) {
+                constexpr int j = 2 * decltype(jc_)::value;
+                const u32 k0 = key_fma<t * 8 + j>(h[j], c128), k1 = key_fma<t * 8 + j + 1>(h[j + 1], c128);
+                cb16[j] = t == 0 ? k0 : min_u16(cb16[j], k0);          // best row of column j
+                cb16[j + 1] = t == 0 ? k1 : min_u16(cb16[j + 1], k1);
                 best = j == 0 ? min_u16(k0, k1) : min_u16(best, min_u16(k0, k1));   // best column of this row
-            }
+            });
         }
         u32 v = (best << 9) | (u32)lane;
         // Node of level k joins rows t and t + R / 2^(k+1).  The four levels split on lane bits 2, 3 (DPP minima, two instructions
