@@ -226,6 +226,27 @@ int reloc_pnp_ransac(reloc_ctx *ctx, const float *obj, const float *img, int m, 
 int reloc_set_camera(reloc_ctx *ctx, const double K4[4], const double base_to_cam_t[3],
                      const double base_to_cam_R[9]);
 
+/* ---- lens distortion (include/reloc_spec.h, RELOC_UNDISTORT_ITERS) ---------------------------- */
+/* OpenCV's default model, coeffs = k1 k2 p1 p2 [k3 [k4 k5 k6 [s1 s2 s3 s4 [tx ty]]]] with n in {0, 4, 5, 8, 12, 14}; every
+ * coefficient after the fifth must be exactly 0 (the rational, thin-prism and tilted models are not implemented) and all
+ * must be finite, else RELOC_E_ARG.  n = 0 or all zero: pinhole (the pinhole kernels run, results bit-identical).  A new
+ * context is pinhole.  Read by reloc_tick, reloc_tick_dev, reloc_tick_batch_dev, reloc_tick_solve_dev,
+ * reloc_shard_solve_batch_dev, reloc_record_frame and reloc_tick_accumulate_dev; never by the explicit-K4 entry points
+ * (reloc_pnp_score, reloc_pnp_ransac, reloc_depth_points). */
+int reloc_set_distortion(reloc_ctx *ctx, const double *coeffs, int n);
+int reloc_get_distortion(reloc_ctx *ctx, double coeffs[5]);
+/* cv2.undistortPoints(img, K, dist) without R / P: m pixels (x, y) -> m normalized points (x, y) in double, five
+ * fixed-point iterations.  dist = k1 k2 p1 p2 k3 (NULL: zeros). */
+int reloc_undistort_points(reloc_ctx *ctx, const float *img, int m, const double K4[4], const double dist[5],
+                           double *out_norm);
+/* reloc_pnp_score / reloc_pnp_ransac through the distortion model dist = k1 k2 p1 p2 k3 (NULL or all zero: the pinhole
+ * entry points' kernels, bit-identical results). */
+int reloc_pnp_score_dist(reloc_ctx *ctx, const float *obj, const float *img, int m, const double *Rt, int H,
+                         const double K4[4], const double dist[5], float thr_px, int32_t *inlier_count, uint8_t *mask);
+int reloc_pnp_ransac_dist(reloc_ctx *ctx, const float *obj, const float *img, int m, const double K4[4],
+                          const double dist[5], int iters, float thr_px, double conf, uint64_t seed, double rvec[3],
+                          double tvec[3], int32_t *inliers, int32_t *n_inl, int32_t *ok);
+
 /* ---- fused tick ----------------------------------------------------------------------------- */
 #define RELOC_TICK_LOCAL   0   /* candidates by VIO distance / heading only                          M:293-302 */
 #define RELOC_TICK_GLOBAL  1   /* whole-database search unconditionally (the benchmarked shape)       G:329-344 */

@@ -117,4 +117,18 @@
  * quartic itself afterwards, so the resolvent root needs no more. */
 #define RELOC_P3P_CUBIC_ITERS    16
 
+/* Lens distortion: OpenCV's default ("plumb_bob", Brown-Conrady) model with (k1, k2, p1, p2, k3), restated from OpenCV 4.x
+ * (cv::projectPoints, cv::undistortPoints; not pinned against a cv2 build).  All in double.
+ *   forward   x = X/Z, y = Y/Z, r2 = x^2 + y^2, rad = 1 + k1 r2 + k2 r2^2 + k3 r2^3
+ *             xd = x rad + 2 p1 x y + p2 (r2 + 2 x^2),  yd = y rad + p1 (r2 + 2 y^2) + 2 p2 x y,  u = fx xd + cx, v = fy yd + cy
+ *   inverse   x0 = (u - cx) * (1/fx), y0 = (v - cy) * (1/fy) (OpenCV multiplies by the reciprocal); x = x0, y = y0; then
+ *             UNDISTORT_ITERS times (cv::undistortPoints' default criteria, no epsilon test):
+ *               r2 = x^2 + y^2, icdist = 1 / (1 + ((k3 r2 + k2) r2 + k1) r2); icdist < 0: (x, y) = (x0, y0), stop
+ *               x = (x0 - (2 p1 x y + p2 (r2 + 2 x^2))) icdist,  y = (y0 - (p1 (r2 + 2 y^2) + 2 p2 x y)) icdist
+ * PnP-RANSAC: P3P on undistorted normalized points, the fourth point picks the root by the ideal pixel K undistort(img);
+ * scoring, inlier list, Levenberg-Marquardt and the mean error measure in distorted pixels through the forward model.
+ * Recording / accumulation: X = x_u z, Y = y_u z with (x_u, y_u) = undistort(rounded pixel).  All-zero coefficients select
+ * the pinhole kernels. */
+#define RELOC_UNDISTORT_ITERS    5
+
 #endif /* RELOC_SPEC_H */

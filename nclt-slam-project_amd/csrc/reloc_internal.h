@@ -226,6 +226,43 @@ __device__ __forceinline__ void cur_heading_q(const double q[4], double &cc, dou
     sc = n > 0 ? Rb[3] / n : 0.0;
 }
 
+// Lens distortion k1 k2 p1 p2 k3 (include/reloc_spec.h): passed by value to the DIST instantiations only, so the pinhole
+// kernels keep their signature and code.  Operation order as cv::projectPoints / cv::undistortPoints (no FMA: the library
+// builds with -ffp-contract=off), so tests/distortion_ref.py restates it bit for bit.
+struct DistCoef { double k1, k2, p1, p2, k3; };
+struct CamK4 { double v[4]; };         // fx fy cx cy by value
+// host side: n coefficients all finite (x - x is NaN for an infinity or a NaN)
+static inline bool dist_finite(const double *d, int n = 5)
+{
+    if (!d) return true;
+    for (int k = 0; k < n; ++k) if (!(d[k] - d[k] == 0.0)) return false;
+    return true;
+}
+// normalized (x, y) -> distorted normalized (xd, yd)
+__device__ __forceinline__ void distort_norm(const DistCoef &d, double x, double y, double &xd, double &yd)
+{
+    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
+    const double rad = 1.0 + d.k1 * r2 + d.k2 * r4 + d.k3 * r6;
+    const double a1 = 2.0 * x * y, a2 = r2 + 2.0 * x * x, a3 = r2 + 2.0 * y * y;
+    xd = x * rad + d.p1 * a1 + d.p2 * a2;
+    yd = y * rad + d.p1 * a3 + d.p2 * a1;
+}
+// pixel (u, v) -> undistorted normalized (x, y): RELOC_UNDISTORT_ITERS fixed-point steps
+__device__ __forceinline__ void undistort_norm(const DistCoef &d, const double K4[4], double u, double v, double &x, double &y)
+{
+    const double x0 = (u - K4[2]) * (1.0 / K4[0]), y0 = (v - K4[3]) * (1.0 / K4[1]);
+    x = x0; y = y0;
+    for (int it = 0; it < RELOC_UNDISTORT_ITERS; ++it) {
+        const double r2 = x * x + y * y;
+        const double icdist = 1.0 / (1.0 + ((d.k3 * r2 + d.k2) * r2 + d.k1) * r2);
+        if (icdist < 0) { x = x0; y = y0; break; }
+        const double dx = 2.0 * d.p1 * x * y + d.p2 * (r2 + 2.0 * x * x);
+        const double dy = d.p1 * (r2 + 2.0 * y * y) + 2.0 * d.p2 * x * y;
+        x = (x0 - dx) * icdist;
+        y = (y0 - dy) * icdist;
+    }
+}
+
 // Optional heading mask of the whole-database scan: records whose teach heading is incompatible with the
 // robot's are not scored (count 0), exactly the records the reference skips at G:329-330.  xyh == NULL: no mask.
 struct ScanMask {
@@ -288,6 +325,8 @@ struct reloc_ctx {
     double K4[4] = {RELOC_FX, RELOC_FY, RELOC_CX, RELOC_CY};
     double b2c_t[3] = {0.35, 0.0, 0.18};
     double b2c_R[9] = {0, -1, 0, 0, 0, -1, 1, 0, 0};
+    double dist[5] = {0, 0, 0, 0, 0};   // k1 k2 p1 p2 k3 (reloc_set_distortion); zeros normalised to +0
+    bool has_dist = false;               // a coefficient is non-zero: the DIST kernels run
 
     // ---- matcher parameters (reloc_set_params) ----
     reloc_params prm;
@@ -372,5 +411,7 @@ int orb_run_batch_dev(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs_
 int orb_run_dev(reloc_ctx *ctx, const uint8_t *src_dev, int w, int h, int stride, int channels, int order,
                 int nfeatures);
 int pnp_run_candidates_batch(reloc_ctx *const *ctxs, int n, int n_cand_max, const uint64_t *seeds);
+// dist: k1 k2 p1 p2 k3, or NULL for the pinhole kernels (the caller passes NULL when every coefficient is zero)
 int pnp_run_candidates(reloc_ctx *ctx, int n_cand_max, const int32_t *n_cand_dev, const double K4[4], int iters,
-                       float thr_px, double conf, uint64_t seed, int min_m, const int32_t *relocating_dev, int gate_local, int gate_global);
+                       float thr_px, double conf, uint64_t seed, int min_m, const int32_t *relocating_dev, int gate_local, int gate_global,
+                       const double *dist = nullptr);

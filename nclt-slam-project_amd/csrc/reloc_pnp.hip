@@ -15,6 +15,11 @@
 //   k_pnp_finish  one wave per candidate: sequential adaptive-cap scan over the counts (lane 0),
 //                 inlier list by ballot compaction, LM refinement with the 6x6 normal equations
 //                 summed across the wave in fp64, Rodrigues log, mean inlier error.
+// Each body is a template on DIST (lens distortion, include/reloc_spec.h).  The pinhole kernels (DIST = false) keep their
+// signature and code; the k_pnp_*_dist kernels take the coefficients as one extra DistCoef argument.  With distortion
+// P3P gets undistorted normalized points, the fourth point picks the root by the ideal pixel K undistort(img), and the
+// scoring, the inlier list, the refinement and the mean error measure in distorted pixels (as OpenCV's PnPRansacCallback
+// and SOLVEPNP_ITERATIVE refinement do).
 #include "reloc_internal.h"
 
 // Developer build (-DRELOC_PNP_TIMING, tools/exp_pnp_phases.py): the first wave of each PnP kernel stamps the 100 MHz
@@ -284,6 +289,29 @@ __device__ __forceinline__ double reproj_err2(const double *Rt, const double K4[
     return du * du + dv * dv;
 }
 
+// cam = fx fy cx cy, and for DIST k1 k2 p1 p2 k3 behind them (one pointer for both instantiations)
+__device__ __forceinline__ DistCoef cam_dist(const double *cam) { return DistCoef{cam[4], cam[5], cam[6], cam[7], cam[8]}; }
+// squared reprojection error in distorted pixels (forward model)
+__device__ __forceinline__ double reproj_err2_dist(const double *Rt, const double *cam, const float *obj, const float *img)
+{
+    const double X = obj[0], Y = obj[1], Z = obj[2];
+    const double x = ((Rt[0] * X + Rt[1] * Y) + Rt[2] * Z) + Rt[9];
+    const double y = ((Rt[3] * X + Rt[4] * Y) + Rt[5] * Z) + Rt[10];
+    const double z = ((Rt[6] * X + Rt[7] * Y) + Rt[8] * Z) + Rt[11];
+    double xd, yd;
+    distort_norm(cam_dist(cam), x / z, y / z, xd, yd);
+    const double u = cam[0] * xd + cam[2];
+    const double v = cam[1] * yd + cam[3];
+    const double du = u - (double)img[0], dv = v - (double)img[1];
+    return du * du + dv * dv;
+}
+template <bool DIST>
+__device__ __forceinline__ double reproj_err2_t(const double *Rt, const double *cam, const float *obj, const float *img)
+{
+    if constexpr (DIST) return reproj_err2_dist(Rt, cam, obj, img);
+    else return reproj_err2(Rt, cam, obj, img);
+}
+
 struct PnpParams {
     double K4[4];
     double conf;
@@ -318,10 +346,11 @@ __device__ __forceinline__ int pnp_gate(const PnpParams &prm, const int32_t *rel
     return relocating_p ? (*relocating_p ? prm.gate_global : prm.gate_local) : 0;
 }
 
+template <bool DIST>
 __device__ __forceinline__ void pnp_hyp_body(const float *__restrict__ obj, const float *__restrict__ img,
                                              const int32_t *__restrict__ m_arr, const int32_t *__restrict__ n_cand_p,
                                              const PnpParams &prm, double *__restrict__ Rt_out, int32_t *__restrict__ cnt,
-                                             const int32_t *__restrict__ relocating_p)
+                                             const int32_t *__restrict__ relocating_p, const DistCoef &dc)
 {
     const int c = blockIdx.y;
     if (n_cand_p && c >= *n_cand_p) return;
@@ -340,8 +369,12 @@ __device__ __forceinline__ void pnp_hyp_body(const float *__restrict__ obj, cons
     double P[9], xn[6], Rt[12];
     for (int k = 0; k < 3; ++k) {
         for (int e = 0; e < 3; ++e) P[3 * k + e] = o[3 * idx[k] + e];
-        xn[2 * k] = ((double)im[2 * idx[k]] - prm.K4[2]) / prm.K4[0];
-        xn[2 * k + 1] = ((double)im[2 * idx[k] + 1] - prm.K4[3]) / prm.K4[1];
+        if constexpr (DIST) {
+            undistort_norm(dc, prm.K4, (double)im[2 * idx[k]], (double)im[2 * idx[k] + 1], xn[2 * k], xn[2 * k + 1]);
+        } else {
+            xn[2 * k] = ((double)im[2 * idx[k]] - prm.K4[2]) / prm.K4[0];
+            xn[2 * k + 1] = ((double)im[2 * idx[k] + 1] - prm.K4[3]) / prm.K4[1];
+        }
     }
     PNP_T(2);
     P3pSetup S;
@@ -349,7 +382,21 @@ __device__ __forceinline__ void pnp_hyp_body(const float *__restrict__ obj, cons
     double e = 0;
     bool valid = p3p_solution(S, P, sol, Rt);
     if (valid) {
-        e = reproj_err2(Rt, prm.K4, o + 3 * idx[3], im + 2 * idx[3]);
+        if constexpr (DIST) {
+            // the fourth point picks the root by its ideal pixel K undistort(img): the pinhole arithmetic on other inputs
+            double xu, yu;
+            undistort_norm(dc, prm.K4, (double)im[2 * idx[3]], (double)im[2 * idx[3] + 1], xu, yu);
+            const double iu = prm.K4[0] * xu + prm.K4[2], iv = prm.K4[1] * yu + prm.K4[3];
+            const float *q = o + 3 * idx[3];
+            const double X = q[0], Y = q[1], Z = q[2];
+            const double x = ((Rt[0] * X + Rt[1] * Y) + Rt[2] * Z) + Rt[9];
+            const double y = ((Rt[3] * X + Rt[4] * Y) + Rt[5] * Z) + Rt[10];
+            const double z = ((Rt[6] * X + Rt[7] * Y) + Rt[8] * Z) + Rt[11];
+            const double du = (prm.K4[0] * (x / z) + prm.K4[2]) - iu, dv = (prm.K4[1] * (y / z) + prm.K4[3]) - iv;
+            e = du * du + dv * dv;
+        } else {
+            e = reproj_err2(Rt, prm.K4, o + 3 * idx[3], im + 2 * idx[3]);
+        }
         valid = e == e;
     }
     PNP_T(6);
@@ -376,7 +423,15 @@ __global__ __launch_bounds__(HYP_BLOCK) void k_pnp_hyp(const float *__restrict__
                                                 const int32_t *__restrict__ relocating_p)
 {
     RELOC_SMALL_KERNEL_PRIO();
-    pnp_hyp_body(obj, img, m_arr, n_cand_p, prm, Rt_out, cnt, relocating_p);
+    pnp_hyp_body<false>(obj, img, m_arr, n_cand_p, prm, Rt_out, cnt, relocating_p, DistCoef{});
+}
+__global__ __launch_bounds__(HYP_BLOCK) void k_pnp_hyp_dist(const float *__restrict__ obj, const float *__restrict__ img,
+                                                     const int32_t *__restrict__ m_arr, const int32_t *__restrict__ n_cand_p,
+                                                     PnpParams prm, double *__restrict__ Rt_out, int32_t *__restrict__ cnt,
+                                                     const int32_t *__restrict__ relocating_p, DistCoef dc)
+{
+    RELOC_SMALL_KERNEL_PRIO();
+    pnp_hyp_body<true>(obj, img, m_arr, n_cand_p, prm, Rt_out, cnt, relocating_p, dc);
 }
 // grid (ceil(iters/64), n_cand_max, frames)
 __global__ __launch_bounds__(HYP_BLOCK) void k_pnp_hyp_batch(PnpBatch b, PnpParams prm)
@@ -384,15 +439,24 @@ __global__ __launch_bounds__(HYP_BLOCK) void k_pnp_hyp_batch(PnpBatch b, PnpPara
     RELOC_SMALL_KERNEL_PRIO();
     const PnpFrame &F = b.f[blockIdx.z];
     prm.seed = F.seed;
-    pnp_hyp_body(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, F.relocating);
+    pnp_hyp_body<false>(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, F.relocating, DistCoef{});
+}
+__global__ __launch_bounds__(HYP_BLOCK) void k_pnp_hyp_batch_dist(PnpBatch b, PnpParams prm, DistCoef dc)
+{
+    RELOC_SMALL_KERNEL_PRIO();
+    const PnpFrame &F = b.f[blockIdx.z];
+    prm.seed = F.seed;
+    pnp_hyp_body<true>(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, F.relocating, dc);
 }
 
 
 // grid (iters, n_cand_max), block 64: one wave scores one hypothesis
+template <bool DIST>
 __device__ __forceinline__ void pnp_score_body(const float *__restrict__ obj, const float *__restrict__ img,
                                                const int32_t *__restrict__ m_arr, const int32_t *__restrict__ n_cand_p,
                                                const PnpParams &prm, const double *__restrict__ Rt_in,
-                                               int32_t *__restrict__ cnt, uint8_t *__restrict__ mask, int hyp_stride)
+                                               int32_t *__restrict__ cnt, uint8_t *__restrict__ mask, int hyp_stride,
+                                               const DistCoef &dc)
 {
     const int c = blockIdx.y;
     if (n_cand_p && c >= *n_cand_p) return;
@@ -404,11 +468,16 @@ __device__ __forceinline__ void pnp_score_body(const float *__restrict__ obj, co
     const float *im = img + (size_t)c * prm.stride * 2;
     double Rt[12];
     for (int k = 0; k < 12; ++k) Rt[k] = Rt_in[((size_t)c * hyp_stride + h) * 12 + k];
+    double cam[DIST ? 9 : 1];
+    if constexpr (DIST) {
+        for (int k = 0; k < 4; ++k) cam[k] = prm.K4[k];
+        cam[4] = dc.k1; cam[5] = dc.k2; cam[6] = dc.p1; cam[7] = dc.p2; cam[8] = dc.k3;
+    }
     int count = 0;
     for (int i0 = 0; i0 < m; i0 += 64) {
         const int i = i0 + threadIdx.x;
         bool in = false;
-        if (i < m) in = reproj_err2(Rt, prm.K4, o + 3 * i, im + 2 * i) <= prm.thr2;
+        if (i < m) in = reproj_err2_t<DIST>(Rt, DIST ? cam : prm.K4, o + 3 * i, im + 2 * i) <= prm.thr2;
         if (mask && i < m) mask[((size_t)c * hyp_stride + h) * m + i] = (uint8_t)in;
         count += __popcll(__ballot(in));
     }
@@ -420,14 +489,29 @@ __global__ __launch_bounds__(64) void k_pnp_score(const float *__restrict__ obj,
                                                   int32_t *__restrict__ cnt, uint8_t *__restrict__ mask, int hyp_stride)
 {
     RELOC_SMALL_KERNEL_PRIO();
-    pnp_score_body(obj, img, m_arr, n_cand_p, prm, Rt_in, cnt, mask, hyp_stride);
+    pnp_score_body<false>(obj, img, m_arr, n_cand_p, prm, Rt_in, cnt, mask, hyp_stride, DistCoef{});
+}
+__global__ __launch_bounds__(64) void k_pnp_score_dist(const float *__restrict__ obj, const float *__restrict__ img,
+                                                       const int32_t *__restrict__ m_arr, const int32_t *__restrict__ n_cand_p,
+                                                       PnpParams prm, const double *__restrict__ Rt_in,
+                                                       int32_t *__restrict__ cnt, uint8_t *__restrict__ mask, int hyp_stride,
+                                                       DistCoef dc)
+{
+    RELOC_SMALL_KERNEL_PRIO();
+    pnp_score_body<true>(obj, img, m_arr, n_cand_p, prm, Rt_in, cnt, mask, hyp_stride, dc);
 }
 // grid (iters, n_cand_max, frames)
 __global__ __launch_bounds__(64) void k_pnp_score_batch(PnpBatch b, PnpParams prm, int hyp_stride)
 {
     RELOC_SMALL_KERNEL_PRIO();
     const PnpFrame &F = b.f[blockIdx.z];
-    pnp_score_body(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, nullptr, hyp_stride);
+    pnp_score_body<false>(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, nullptr, hyp_stride, DistCoef{});
+}
+__global__ __launch_bounds__(64) void k_pnp_score_batch_dist(PnpBatch b, PnpParams prm, int hyp_stride, DistCoef dc)
+{
+    RELOC_SMALL_KERNEL_PRIO();
+    const PnpFrame &F = b.f[blockIdx.z];
+    pnp_score_body<true>(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, nullptr, hyp_stride, dc);
 }
 
 
@@ -556,8 +640,11 @@ __device__ __forceinline__ void wave_sum28(double (&v)[32], double (&tot)[28])
 
 // Normal equations of the reprojection cost over the selected points, summed across the wave.
 // H: upper triangle (21 values, row-major a<=b), g: 6, returns the cost; every lane gets the sums.
+// DIST: K4 points at fx fy cx cy k1 k2 p1 p2 k3; the residual is forward(R X + t) - img and the Jacobian the pinhole one
+// with d(xd, yd) / d(x, y) chained in.
+template <bool DIST>
 __device__ double lm_normal_wave(const float *obj, const float *img, const int32_t *sel, int n, const double *Rt,
-                                 const double K4[4], double H[21], double g[6])
+                                 const double *K4, double H[21], double g[6])
 {
     double cost = 0;
     for (int k = 0; k < 21; ++k) H[k] = 0;
@@ -570,23 +657,49 @@ __device__ double lm_normal_wave(const float *obj, const float *img, const int32
         const double zr = Rt[6] * X + Rt[7] * Y + Rt[8] * Z;
         const double x = xr + Rt[9], y = yr + Rt[10], z = zr + Rt[11];
         const double iz = 1.0 / z;
-        const double ru = K4[0] * x * iz + K4[2] - (double)img[2 * i];
-        const double rv = K4[1] * y * iz + K4[3] - (double)img[2 * i + 1];
-        const double ux = K4[0] * iz, uz = -K4[0] * x * iz * iz;
-        const double vy = K4[1] * iz, vz = -K4[1] * y * iz * iz;
-        double Ju[6], Jv[6];
-        Ju[0] = uz * yr;            Ju[1] = ux * zr - uz * xr; Ju[2] = -ux * yr;
-        Jv[0] = -vy * zr + vz * yr; Jv[1] = -vz * xr;          Jv[2] = vy * xr;
-        Ju[3] = ux; Ju[4] = 0;  Ju[5] = uz;
-        Jv[3] = 0;  Jv[4] = vy; Jv[5] = vz;
-        int o = 0;
+        // accumulates one residual pair and its two Jacobian rows
+        auto acc = [&](const double ru, const double rv, const double (&Ju)[6], const double (&Jv)[6]) {
+            int o = 0;
 #pragma unroll
-        for (int a = 0; a < 6; ++a) {
-            g[a] += Ju[a] * ru + Jv[a] * rv;
+            for (int a = 0; a < 6; ++a) {
+                g[a] += Ju[a] * ru + Jv[a] * rv;
 #pragma unroll
-            for (int b = a; b < 6; ++b) H[o++] += Ju[a] * Ju[b] + Jv[a] * Jv[b];
+                for (int b = a; b < 6; ++b) H[o++] += Ju[a] * Ju[b] + Jv[a] * Jv[b];
+            }
+            cost += ru * ru + rv * rv;
+        };
+        if constexpr (DIST) {
+            const DistCoef d = cam_dist(K4);
+            const double xn = x * iz, yn = y * iz;
+            double xd, yd;
+            distort_norm(d, xn, yn, xd, yd);
+            const double ru = K4[0] * xd + K4[2] - (double)img[2 * i];
+            const double rv = K4[1] * yd + K4[3] - (double)img[2 * i + 1];
+            // d(xd, yd) / d(xn, yn)
+            const double r2 = xn * xn + yn * yn;
+            const double rad = 1.0 + d.k1 * r2 + d.k2 * r2 * r2 + d.k3 * r2 * r2 * r2;
+            const double drad = d.k1 + 2.0 * d.k2 * r2 + 3.0 * d.k3 * r2 * r2;
+            const double dxx = rad + 2.0 * xn * xn * drad + 2.0 * d.p1 * yn + 6.0 * d.p2 * xn;
+            const double dxy = 2.0 * xn * yn * drad + 2.0 * d.p1 * xn + 2.0 * d.p2 * yn;     // = d yd / d xn
+            const double dyy = rad + 2.0 * yn * yn * drad + 6.0 * d.p1 * yn + 2.0 * d.p2 * xn;
+            // d(u, v) / d(x, y, z) of the camera-frame point
+            const double Ux = K4[0] * dxx * iz, Uy = K4[0] * dxy * iz, Uz = -K4[0] * (dxx * xn + dxy * yn) * iz;
+            const double Vx = K4[1] * dxy * iz, Vy = K4[1] * dyy * iz, Vz = -K4[1] * (dxy * xn + dyy * yn) * iz;
+            const double Ju[6] = {-Uy * zr + Uz * yr, Ux * zr - Uz * xr, -Ux * yr + Uy * xr, Ux, Uy, Uz};
+            const double Jv[6] = {-Vy * zr + Vz * yr, Vx * zr - Vz * xr, -Vx * yr + Vy * xr, Vx, Vy, Vz};
+            acc(ru, rv, Ju, Jv);
+        } else {
+            const double ru = K4[0] * x * iz + K4[2] - (double)img[2 * i];
+            const double rv = K4[1] * y * iz + K4[3] - (double)img[2 * i + 1];
+            const double ux = K4[0] * iz, uz = -K4[0] * x * iz * iz;
+            const double vy = K4[1] * iz, vz = -K4[1] * y * iz * iz;
+            double Ju[6], Jv[6];
+            Ju[0] = uz * yr;            Ju[1] = ux * zr - uz * xr; Ju[2] = -ux * yr;
+            Jv[0] = -vy * zr + vz * yr; Jv[1] = -vz * xr;          Jv[2] = vy * xr;
+            Ju[3] = ux; Ju[4] = 0;  Ju[5] = uz;
+            Jv[3] = 0;  Jv[4] = vy; Jv[5] = vz;
+            acc(ru, rv, Ju, Jv);
         }
-        cost += ru * ru + rv * rv;
     }
 #if defined(RELOC_PNP_SUM28) && RELOC_PNP_SUM28 == 0          // developer switch: the r1 form, one butterfly per value
     for (int k = 0; k < 21; ++k) H[k] = wave_sum(H[k]);
@@ -635,11 +748,13 @@ __device__ bool chol_solve6(const double Ain[36], const double b[6], double x[6]
 // 4-stream run 5940 -> 6020 frames/s, synchronous tick +1.7 us.  80 registers: no further gain, tick +16 us.
 // (The same limit on k_pnp_hyp (108 -> 80) and k_pyramid (81 -> 64) changes nothing.)  Ticks that run no whole-database scan
 // and the single-call entry point use the unconstrained instantiation (ctx->latency_shapes).
+template <bool DIST>
 __device__ __forceinline__ void pnp_finish_body(const float *__restrict__ obj, const float *__restrict__ img,
                                                 const int32_t *__restrict__ m_arr, const int32_t *__restrict__ n_cand_p,
                                                 const PnpParams &prm, const double *__restrict__ Rt_all,
                                                 const int32_t *__restrict__ cnt, int32_t *__restrict__ inl_out,
-                                                PnpOut *__restrict__ out, const int32_t *__restrict__ relocating_p)
+                                                PnpOut *__restrict__ out, const int32_t *__restrict__ relocating_p,
+                                                const DistCoef &dc)
 {
     const int c = blockIdx.x;
     if (n_cand_p && c >= *n_cand_p) return;
@@ -718,12 +833,18 @@ __device__ __forceinline__ void pnp_finish_body(const float *__restrict__ obj, c
             return;
         }
     }
+    double camd[DIST ? 9 : 1];
+    if constexpr (DIST) {
+        for (int k = 0; k < 4; ++k) camd[k] = prm.K4[k];
+        camd[4] = dc.k1; camd[5] = dc.k2; camd[6] = dc.p1; camd[7] = dc.p2; camd[8] = dc.k3;
+    }
+    const double *cam = DIST ? camd : prm.K4;
     // inlier list (ascending) by ballot compaction
     int n = 0;
     for (int i0 = 0; i0 < m; i0 += 64) {
         const int i = i0 + lane;
         bool in = false;
-        if (i < m) in = reproj_err2(Rt, prm.K4, o + 3 * i, im + 2 * i) <= prm.thr2;
+        if (i < m) in = reproj_err2_t<DIST>(Rt, cam, o + 3 * i, im + 2 * i) <= prm.thr2;
         const unsigned long long bal = __ballot(in);
         if (in) inl[n + __popcll(bal & ((1ull << lane) - 1ull))] = i;
         n += __popcll(bal);
@@ -732,7 +853,7 @@ __device__ __forceinline__ void pnp_finish_body(const float *__restrict__ obj, c
     PNP_T(10);
     // Levenberg-Marquardt on the inliers, left-multiplied rotation increment
     double H[21], g[6], Hn[21], gn[6];
-    double cost = lm_normal_wave(o, im, inl, n, Rt, prm.K4, H, g);
+    double cost = lm_normal_wave<DIST>(o, im, inl, n, Rt, cam, H, g);
     double lambda = RELOC_LM_LAMBDA0;
     PNP_T(11);
     for (int trial = 0; trial < RELOC_LM_MAX_TRIALS; ++trial) {
@@ -758,7 +879,7 @@ __device__ __forceinline__ void pnp_finish_body(const float *__restrict__ obj, c
                 Rn[3 * r + cc] = dR[3 * r] * Rt[cc] + dR[3 * r + 1] * Rt[3 + cc] + dR[3 * r + 2] * Rt[6 + cc];
         for (int k = 0; k < 3; ++k) Rn[9 + k] = Rt[9 + k] + dx[3 + k];
         if (trial == 0) PNP_T(19);
-        const double cn = lm_normal_wave(o, im, inl, n, Rn, prm.K4, Hn, gn);
+        const double cn = lm_normal_wave<DIST>(o, im, inl, n, Rn, cam, Hn, gn);
         if (trial == 0) PNP_T(20);
         double step = 0;
         for (int a = 0; a < 6; ++a) if (fabs(dx[a]) > step) step = fabs(dx[a]);
@@ -780,7 +901,7 @@ __device__ __forceinline__ void pnp_finish_body(const float *__restrict__ obj, c
     double esum = 0;
     for (int kk = lane; kk < n; kk += 64) {
         const int i = inl[kk];
-        esum += sqrt(reproj_err2(Rt, prm.K4, o + 3 * i, im + 2 * i));
+        esum += sqrt(reproj_err2_t<DIST>(Rt, cam, o + 3 * i, im + 2 * i));
     }
     esum = wave_sum(esum);
     if (lane == 0) {
@@ -803,7 +924,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) 
                                                    PnpOut *__restrict__ out, const int32_t *__restrict__ relocating_p)
 {
     RELOC_SMALL_KERNEL_PRIO();
-    pnp_finish_body(obj, img, m_arr, n_cand_p, prm, Rt_all, cnt, inl_out, out, relocating_p);
+    pnp_finish_body<false>(obj, img, m_arr, n_cand_p, prm, Rt_all, cnt, inl_out, out, relocating_p, DistCoef{});
 }
 // grid (n_cand_max, frames)
 template <int WAVES>
@@ -812,7 +933,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) 
     RELOC_SMALL_KERNEL_PRIO();
     const PnpFrame &F = b.f[blockIdx.y];
     prm.seed = F.seed;
-    pnp_finish_body(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, F.inl, F.out, F.relocating);
+    pnp_finish_body<false>(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, F.inl, F.out, F.relocating, DistCoef{});
+}
+// DIST: one instantiation for every shape, budget PNP_DIST_WAVES (see pnp_run_candidates)
+constexpr int PNP_DIST_WAVES = 2;
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PNP_DIST_WAVES, 8))) void k_pnp_finish_dist(
+    const float *__restrict__ obj, const float *__restrict__ img, const int32_t *__restrict__ m_arr,
+    const int32_t *__restrict__ n_cand_p, PnpParams prm, const double *__restrict__ Rt_all, const int32_t *__restrict__ cnt,
+    int32_t *__restrict__ inl_out, PnpOut *__restrict__ out, const int32_t *__restrict__ relocating_p, DistCoef dc)
+{
+    RELOC_SMALL_KERNEL_PRIO();
+    pnp_finish_body<true>(obj, img, m_arr, n_cand_p, prm, Rt_all, cnt, inl_out, out, relocating_p, dc);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PNP_DIST_WAVES, 8))) void k_pnp_finish_batch_dist(
+    PnpBatch b, PnpParams prm, DistCoef dc)
+{
+    RELOC_SMALL_KERNEL_PRIO();
+    const PnpFrame &F = b.f[blockIdx.y];
+    prm.seed = F.seed;
+    pnp_finish_body<true>(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, F.inl, F.out, F.relocating, dc);
 }
 
 
@@ -831,8 +970,19 @@ static PnpParams make_params(const double K4[4], int iters, float thr_px, double
     return p;
 }
 
+static DistCoef make_dist(const double *d) { return DistCoef{d[0], d[1], d[2], d[3], d[4]}; }
+static bool dist_nonzero(const double *d)
+{
+    if (!d) return false;
+    for (int k = 0; k < 5; ++k) if (d[k] != 0.0) return true;
+    return false;
+}
+
+// The DIST kernels run when dist is non-NULL.  Their k_pnp_finish has ONE register budget, PNP_DIST_WAVES = 2 waves per SIMD
+// (256 VGPRs): the forward model and its Jacobian do not fit the pinhole kernel's 128 without scratch.
 int pnp_run_candidates(reloc_ctx *ctx, int n_cand_max, const int32_t *n_cand_dev, const double K4[4], int iters,
-                       float thr_px, double conf, uint64_t seed, int min_m, const int32_t *relocating_dev, int gate_local, int gate_global)
+                       float thr_px, double conf, uint64_t seed, int min_m, const int32_t *relocating_dev, int gate_local, int gate_global,
+                       const double *dist)
 {
     if (n_cand_max <= 0) return RELOC_OK;
     if (n_cand_max > MAX_CAND || iters < 1 || iters > MAX_HYP) {
@@ -841,6 +991,19 @@ int pnp_run_candidates(reloc_ctx *ctx, int n_cand_max, const int32_t *n_cand_dev
     }
     PnpParams prm = make_params(K4, iters, thr_px, conf, seed, MAX_REC_ROWS, min_m);
     prm.gate_local = gate_local; prm.gate_global = gate_global;
+    if (dist) {
+        const DistCoef dc = make_dist(dist);
+        reloc_prof_begin(ctx, RELOC_PROF_PNP);
+        hipLaunchKernelGGL(k_pnp_hyp_dist, dim3((iters + 63) / 64, n_cand_max), dim3(HYP_BLOCK), 0, ctx->stream, ctx->p_obj,
+                           ctx->p_img, ctx->m_n, n_cand_dev, prm, ctx->p_Rt, ctx->p_cnt, relocating_dev, dc);
+        hipLaunchKernelGGL(k_pnp_score_dist, dim3(iters, n_cand_max), dim3(64), 0, ctx->stream, ctx->p_obj, ctx->p_img, ctx->m_n,
+                           n_cand_dev, prm, ctx->p_Rt, ctx->p_cnt, (uint8_t *)nullptr, MAX_HYP, dc);
+        hipLaunchKernelGGL(k_pnp_finish_dist, dim3(n_cand_max), dim3(64), 0, ctx->stream, ctx->p_obj, ctx->p_img, ctx->m_n,
+                           n_cand_dev, prm, ctx->p_Rt, ctx->p_cnt, ctx->p_inl, ctx->p_out, relocating_dev, dc);
+        reloc_prof_end(ctx, RELOC_PROF_PNP);
+        HIP_TRY(hipGetLastError());
+        return RELOC_OK;
+    }
     reloc_prof_begin(ctx, RELOC_PROF_PNP);
     hipLaunchKernelGGL(k_pnp_hyp, dim3((iters + 63) / 64, n_cand_max), dim3(HYP_BLOCK), 0, ctx->stream, ctx->p_obj, ctx->p_img,
                        ctx->m_n, n_cand_dev, prm, ctx->p_Rt, ctx->p_cnt, relocating_dev);
@@ -876,6 +1039,16 @@ int pnp_run_candidates_batch(reloc_ctx *const *ctxs, int n, int n_cand_max, cons
         F.obj = c->p_obj; F.img = c->p_img; F.m_arr = c->m_n; F.n_cand_p = c->cand_n; F.Rt = c->p_Rt; F.cnt = c->p_cnt; F.inl = c->p_inl;
         F.out = c->p_out; F.seed = seeds ? seeds[f < n ? f : 0] : 0; F.relocating = c->tick_flags;
     }
+    if (c0->has_dist) {            // the contexts of a batch carry equal coefficients (checked by the callers)
+        const DistCoef dc = make_dist(c0->dist);
+        reloc_prof_begin(c0, RELOC_PROF_PNP);
+        hipLaunchKernelGGL(k_pnp_hyp_batch_dist, dim3((iters + 63) / 64, n_cand_max, n), dim3(HYP_BLOCK), 0, c0->stream, b, prm, dc);
+        hipLaunchKernelGGL(k_pnp_score_batch_dist, dim3(iters, n_cand_max, n), dim3(64), 0, c0->stream, b, prm, MAX_HYP, dc);
+        hipLaunchKernelGGL(k_pnp_finish_batch_dist, dim3(n_cand_max, n), dim3(64), 0, c0->stream, b, prm, dc);
+        reloc_prof_end(c0, RELOC_PROF_PNP);
+        HIP_TRY(hipGetLastError());
+        return RELOC_OK;
+    }
     reloc_prof_begin(c0, RELOC_PROF_PNP);
     hipLaunchKernelGGL(k_pnp_hyp_batch, dim3((iters + 63) / 64, n_cand_max, n), dim3(HYP_BLOCK), 0, c0->stream, b, prm);
     hipLaunchKernelGGL(k_pnp_score_batch, dim3(iters, n_cand_max, n), dim3(64), 0, c0->stream, b, prm, MAX_HYP);
@@ -887,11 +1060,10 @@ int pnp_run_candidates_batch(reloc_ctx *const *ctxs, int n, int n_cand_max, cons
 
 
 // ------------------------------------------------------------------------------------------------
-RELOC_API int reloc_pnp_score(reloc_ctx *ctx, const float *obj, const float *img, int m, const double *Rt, int H,
-                              const double K4[4], float thr_px, int32_t *inlier_count, uint8_t *mask)
+// dist: NULL = pinhole kernels
+static int pnp_score_impl(reloc_ctx *ctx, const float *obj, const float *img, int m, const double *Rt, int H,
+                          const double K4[4], const double *dist, float thr_px, int32_t *inlier_count, uint8_t *mask)
 {
-    ARG_CHECK_CTX(ctx, m >= 0 && H >= 0 && K4 && (H == 0 || (Rt && inlier_count)) && (m == 0 || (obj && img)),
-              "reloc_pnp_score");
     if (H == 0) return RELOC_OK;
     if (m == 0) { for (int h = 0; h < H; ++h) inlier_count[h] = 0; return RELOC_OK; }
     if (H > 65535) { reloc_set_error("pnp_score: more than 65535 hypotheses"); return RELOC_E_CAPACITY; }
@@ -909,9 +1081,14 @@ RELOC_API int reloc_pnp_score(reloc_ctx *ctx, const float *obj, const float *img
     HIP_TRY(hipMemsetAsync(dcnt, 0, (size_t)H * 4, ctx->stream));
     HIP_TRY(hipMemcpyAsync(dm, &m, 4, hipMemcpyHostToDevice, ctx->stream));
     const PnpParams prm = make_params(K4, H, thr_px, 0.99, 0, m, 0);
-    hipLaunchKernelGGL(k_pnp_score, dim3(H, 1), dim3(64), 0, ctx->stream, (const float *)dobj, (const float *)dimg,
-                       (const int32_t *)dm, (const int32_t *)nullptr, prm, (const double *)drt, (int32_t *)dcnt,
-                       (uint8_t *)dmask, H);
+    if (dist)
+        hipLaunchKernelGGL(k_pnp_score_dist, dim3(H, 1), dim3(64), 0, ctx->stream, (const float *)dobj, (const float *)dimg,
+                           (const int32_t *)dm, (const int32_t *)nullptr, prm, (const double *)drt, (int32_t *)dcnt,
+                           (uint8_t *)dmask, H, make_dist(dist));
+    else
+        hipLaunchKernelGGL(k_pnp_score, dim3(H, 1), dim3(64), 0, ctx->stream, (const float *)dobj, (const float *)dimg,
+                           (const int32_t *)dm, (const int32_t *)nullptr, prm, (const double *)drt, (int32_t *)dcnt,
+                           (uint8_t *)dmask, H);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(inlier_count, dcnt, (size_t)H * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (mask) HIP_TRY(hipMemcpyAsync(mask, dmask, (size_t)H * m, hipMemcpyDeviceToHost, ctx->stream));
@@ -919,12 +1096,27 @@ RELOC_API int reloc_pnp_score(reloc_ctx *ctx, const float *obj, const float *img
     return RELOC_OK;
 }
 
-RELOC_API int reloc_pnp_ransac(reloc_ctx *ctx, const float *obj, const float *img, int m, const double K4[4], int iters,
-                               float thr_px, double conf, uint64_t seed, double rvec[3], double tvec[3],
-                               int32_t *inliers, int32_t *n_inl, int32_t *ok)
+RELOC_API int reloc_pnp_score(reloc_ctx *ctx, const float *obj, const float *img, int m, const double *Rt, int H,
+                              const double K4[4], float thr_px, int32_t *inlier_count, uint8_t *mask)
 {
-    ARG_CHECK_CTX(ctx, m >= 0 && K4 && rvec && tvec && n_inl && ok && (m == 0 || (obj && img && inliers)),
-              "reloc_pnp_ransac");
+    ARG_CHECK_CTX(ctx, m >= 0 && H >= 0 && K4 && (H == 0 || (Rt && inlier_count)) && (m == 0 || (obj && img)),
+              "reloc_pnp_score");
+    return pnp_score_impl(ctx, obj, img, m, Rt, H, K4, nullptr, thr_px, inlier_count, mask);
+}
+
+RELOC_API int reloc_pnp_score_dist(reloc_ctx *ctx, const float *obj, const float *img, int m, const double *Rt, int H,
+                                   const double K4[4], const double dist[5], float thr_px, int32_t *inlier_count, uint8_t *mask)
+{
+    ARG_CHECK_CTX(ctx, m >= 0 && H >= 0 && K4 && (H == 0 || (Rt && inlier_count)) && (m == 0 || (obj && img)),
+              "reloc_pnp_score_dist");
+    ARG_CHECK(dist_finite(dist), "reloc_pnp_score_dist: non-finite distortion coefficient");
+    return pnp_score_impl(ctx, obj, img, m, Rt, H, K4, dist_nonzero(dist) ? dist : nullptr, thr_px, inlier_count, mask);
+}
+
+static int pnp_ransac_impl(reloc_ctx *ctx, const float *obj, const float *img, int m, const double K4[4], const double *dist,
+                           int iters, float thr_px, double conf, uint64_t seed, double rvec[3], double tvec[3],
+                           int32_t *inliers, int32_t *n_inl, int32_t *ok)
+{
     ARG_CHECK(iters >= 1 && iters <= MAX_HYP, "iterationsCount must be in [1, 256]");
     *ok = 0;
     *n_inl = 0;
@@ -936,7 +1128,7 @@ RELOC_API int reloc_pnp_ransac(reloc_ctx *ctx, const float *obj, const float *im
     // the single-call path has no MIN_MATCHES gate (that gate belongs to the matcher, M:330)
     int rc;
     ctx->latency_shapes = true;
-    rc = pnp_run_candidates(ctx, 1, nullptr, K4, iters, thr_px, conf, seed, RELOC_PNP_SAMPLE, nullptr, 0, 0);
+    rc = pnp_run_candidates(ctx, 1, nullptr, K4, iters, thr_px, conf, seed, RELOC_PNP_SAMPLE, nullptr, 0, 0, dist);
     ctx->latency_shapes = false;
     if (rc) return rc;
     PnpOut po;
@@ -949,5 +1141,61 @@ RELOC_API int reloc_pnp_ransac(reloc_ctx *ctx, const float *obj, const float *im
         *n_inl = po.n_inl;
         *ok = 1;
     }
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_pnp_ransac(reloc_ctx *ctx, const float *obj, const float *img, int m, const double K4[4], int iters,
+                               float thr_px, double conf, uint64_t seed, double rvec[3], double tvec[3],
+                               int32_t *inliers, int32_t *n_inl, int32_t *ok)
+{
+    ARG_CHECK_CTX(ctx, m >= 0 && K4 && rvec && tvec && n_inl && ok && (m == 0 || (obj && img && inliers)),
+              "reloc_pnp_ransac");
+    return pnp_ransac_impl(ctx, obj, img, m, K4, nullptr, iters, thr_px, conf, seed, rvec, tvec, inliers, n_inl, ok);
+}
+
+RELOC_API int reloc_pnp_ransac_dist(reloc_ctx *ctx, const float *obj, const float *img, int m, const double K4[4],
+                                    const double dist[5], int iters, float thr_px, double conf, uint64_t seed, double rvec[3],
+                                    double tvec[3], int32_t *inliers, int32_t *n_inl, int32_t *ok)
+{
+    ARG_CHECK_CTX(ctx, m >= 0 && K4 && rvec && tvec && n_inl && ok && (m == 0 || (obj && img && inliers)),
+              "reloc_pnp_ransac_dist");
+    ARG_CHECK(dist_finite(dist), "reloc_pnp_ransac_dist: non-finite distortion coefficient");
+    return pnp_ransac_impl(ctx, obj, img, m, K4, dist_nonzero(dist) ? dist : nullptr, iters, thr_px, conf, seed, rvec, tvec,
+                           inliers, n_inl, ok);
+}
+
+// ------------------------------------------------------------------------------------------------
+// cv2.undistortPoints without R / P: one point per lane, grid-stride, double (include/reloc_spec.h)
+__global__ __launch_bounds__(256) void k_undistort_points(const float *__restrict__ img, int m, CamK4 k, DistCoef dc,
+                                                          double *__restrict__ out)
+{
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x) {
+        double x, y;
+        undistort_norm(dc, k.v, (double)img[2 * i], (double)img[2 * i + 1], x, y);
+        out[2 * i] = x;
+        out[2 * i + 1] = y;
+    }
+}
+
+RELOC_API int reloc_undistort_points(reloc_ctx *ctx, const float *img, int m, const double K4[4], const double dist[5],
+                                     double *out_norm)
+{
+    ARG_CHECK_CTX(ctx, m >= 0 && K4 && (m == 0 || (img && out_norm)), "reloc_undistort_points");
+    ARG_CHECK(dist_finite(dist), "reloc_undistort_points: non-finite distortion coefficient");
+    if (m == 0) return RELOC_OK;
+    void *dimg, *dout;
+    int rc;
+    if ((rc = reloc_scratch(ctx, 0, (int64_t)m * 8, &dimg))) return rc;
+    if ((rc = reloc_scratch(ctx, 1, (int64_t)m * 16, &dout))) return rc;
+    HIP_TRY(hipMemcpyAsync(dimg, img, (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream));
+    CamK4 k;
+    for (int c = 0; c < 4; ++c) k.v[c] = K4[c];
+    const double zero[5] = {0, 0, 0, 0, 0};
+    const int blocks = (int)((m + 255) / 256 < 1024 ? (m + 255) / 256 : 1024);
+    hipLaunchKernelGGL(k_undistort_points, dim3(blocks), dim3(256), 0, ctx->stream, (const float *)dimg, m, k,
+                       make_dist(dist ? dist : zero), (double *)dout);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out_norm, dout, (size_t)m * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return RELOC_OK;
 }

@@ -635,7 +635,7 @@ static int tick_solve(reloc_ctx *ctx, const TickParams &prm, uint64_t seed)
     if (!rc)
         rc = pnp_run_candidates(ctx, MAX_CAND, ctx->cand_n, ctx->K4, ctx->prm.ransac_iterations, (float)ctx->prm.ransac_reproj_px,
                                 ctx->prm.ransac_confidence, seed, ctx->prm.min_matches, ctx->tick_flags, ctx->prm.min_inliers,
-                                ctx->prm.global_min_inliers);
+                                ctx->prm.global_min_inliers, ctx->has_dist ? ctx->dist : nullptr);
     ctx->latency_shapes = false;
     if (rc) return rc;
     TickParams fin = prm;
@@ -653,6 +653,32 @@ RELOC_API int reloc_set_camera(reloc_ctx *ctx, const double K4[4], const double 
     if (base_to_cam_t) for (int k = 0; k < 3; ++k) ctx->b2c_t[k] = base_to_cam_t[k];
     if (base_to_cam_R) for (int k = 0; k < 9; ++k) ctx->b2c_R[k] = base_to_cam_R[k];
     return db_reindex(ctx);
+}
+
+RELOC_API int reloc_set_distortion(reloc_ctx *ctx, const double *coeffs, int n)
+{
+    ARG_CHECK_CTX(ctx, n == 0 || coeffs, "reloc_set_distortion: coeffs is NULL");
+    ARG_CHECK(n == 0 || n == 4 || n == 5 || n == 8 || n == 12 || n == 14,
+              "reloc_set_distortion: n must be 0, 4, 5, 8, 12 or 14 (OpenCV's distortion vector lengths)");
+    ARG_CHECK(dist_finite(coeffs, n), "reloc_set_distortion: non-finite coefficient");
+    for (int k = 5; k < n; ++k)
+        ARG_CHECK(coeffs[k] == 0.0, "reloc_set_distortion: only k1 k2 p1 p2 k3 are implemented (the rational, thin-prism and "
+                                    "tilted coefficients must be 0)");
+    bool any = false;
+    for (int k = 0; k < 5; ++k) {
+        const double c = k < n ? coeffs[k] : 0.0;
+        ctx->dist[k] = c == 0.0 ? 0.0 : c;      // -0 -> +0: contexts with equal models compare equal byte for byte
+        any |= c != 0.0;
+    }
+    ctx->has_dist = any;
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_get_distortion(reloc_ctx *ctx, double coeffs[5])
+{
+    ARG_CHECK_CTX(ctx, coeffs, "reloc_get_distortion");
+    for (int k = 0; k < 5; ++k) coeffs[k] = ctx->dist[k];
+    return RELOC_OK;
 }
 
 // The tick in three parts, so that several contexts on one stream can share ONE scan launch (reloc_tick_batch_dev):
@@ -764,9 +790,11 @@ RELOC_API int reloc_tick_batch_dev(reloc_ctx *const *ctxs, int n, const uint8_t 
         if (c->stream != ctxs[0]->stream || c->device != ctxs[0]->device || c->db_desc != ctxs[0]->db_desc ||
             c->db_records != ctxs[0]->db_records || c->max_feat != ctxs[0]->max_feat ||
             memcmp(&c->prm, &ctxs[0]->prm, sizeof(reloc_params)) != 0 || memcmp(c->K4, ctxs[0]->K4, sizeof(c->K4)) != 0 ||
-            memcmp(c->b2c_t, ctxs[0]->b2c_t, sizeof(c->b2c_t)) != 0 || memcmp(c->b2c_R, ctxs[0]->b2c_R, sizeof(c->b2c_R)) != 0) {
+            memcmp(c->b2c_t, ctxs[0]->b2c_t, sizeof(c->b2c_t)) != 0 || memcmp(c->b2c_R, ctxs[0]->b2c_R, sizeof(c->b2c_R)) != 0 ||
+            memcmp(c->dist, ctxs[0]->dist, sizeof(c->dist)) != 0) {
             reloc_set_error("tick batch: the contexts must share one stream (reloc_set_stream), one device and one database "
-                            "(reloc_db_share) and have equal feature capacity, matcher parameters (reloc_set_params) and camera (reloc_set_camera)");
+                            "(reloc_db_share) and have equal feature capacity, matcher parameters (reloc_set_params), camera "
+                            "(reloc_set_camera) and lens distortion (reloc_set_distortion)");
             return RELOC_E_STATE;
         }
         for (int g = 0; g < f; ++g) ARG_CHECK(ctxs[g] != c, "reloc_tick_batch_dev: a context appears twice");
@@ -953,9 +981,10 @@ static int shard_batch_check(reloc_ctx *const *ctxs, int n, const char *what)
         if (c->stream != ctxs[0]->stream || c->device != ctxs[0]->device || c->db_desc != ctxs[0]->db_desc ||
             c->db_records != ctxs[0]->db_records || c->max_feat != ctxs[0]->max_feat ||
             memcmp(&c->prm, &ctxs[0]->prm, sizeof(reloc_params)) != 0 || memcmp(c->K4, ctxs[0]->K4, sizeof(c->K4)) != 0 ||
-            memcmp(c->b2c_t, ctxs[0]->b2c_t, sizeof(c->b2c_t)) != 0 || memcmp(c->b2c_R, ctxs[0]->b2c_R, sizeof(c->b2c_R)) != 0) {
+            memcmp(c->b2c_t, ctxs[0]->b2c_t, sizeof(c->b2c_t)) != 0 || memcmp(c->b2c_R, ctxs[0]->b2c_R, sizeof(c->b2c_R)) != 0 ||
+            memcmp(c->dist, ctxs[0]->dist, sizeof(c->dist)) != 0) {
             reloc_set_error("shard batch: the contexts must share one stream (reloc_set_stream), one device and one database "
-                            "(reloc_db_share) and have equal feature capacity, matcher parameters and camera");
+                            "(reloc_db_share) and have equal feature capacity, matcher parameters, camera and lens distortion");
             return RELOC_E_STATE;
         }
         for (int g = 0; g < f; ++g) ARG_CHECK(ctxs[g] != c, "shard batch: a context appears twice");

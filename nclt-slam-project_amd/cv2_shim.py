@@ -2,12 +2,15 @@
 
 Exposes exactly the OpenCV symbols the reference's teach/repeat nodes call:
     cvtColor, ORB_create(...).detectAndCompute / .detect, BFMatcher(...).match / .knnMatch,
-    solvePnPRansac, projectPoints, Rodrigues, KeyPoint, DMatch, error and the constants,
+    solvePnPRansac, projectPoints, undistortPoints, Rodrigues, KeyPoint, DMatch, error and the constants,
 with the same argument meaning, return shapes and error behaviour, so that
     import nclt_slam_project_amd.cv2_shim as cv2
 drops into simulation/isaac/scripts/common/visual_landmark_matcher.py and
 visual_landmark_recorder.py unchanged.  All arithmetic that is data-parallel runs in the HIP
 library through `Engine`; there is no CPU fallback (a missing library or GPU raises `error`).
+
+Lens distortion is OpenCV's default model (k1, k2, p1, p2[, k3]; include/reloc_spec.h) in any of OpenCV's shapes; longer
+vectors (rational, thin-prism, tilted) are accepted only when every coefficient after k3 is zero, anything else raises.
 
 `Cv2Shim(backend)` takes any object with the Engine's method names; the module-level functions
 bind to one lazily created HIP Engine.
@@ -34,6 +37,49 @@ SOLVEPNP_AP3P = 5
 
 class error(Exception):
     """Stands in for cv2.error: raised for malformed input (the reference catches it, M:328)."""
+
+
+def _dist_coeffs(distCoeffs, what):
+    """OpenCV distortion vector -> (5,) float64 k1 k2 p1 p2 k3, or None when it is absent or all zero (pinhole)."""
+    if distCoeffs is None:
+        return None
+    d = np.asarray(distCoeffs, np.float64).ravel()
+    if d.size == 0:
+        return None
+    if d.size not in (4, 5, 8, 12, 14):
+        raise error(f"{what}: distCoeffs must have 4, 5, 8, 12 or 14 elements, got {d.size}")
+    if not np.all(np.isfinite(d)):
+        raise error(f"{what}: distCoeffs must be finite")
+    if d.size > 5 and np.any(d[5:] != 0):
+        raise error(f"{what}: only the (k1, k2, p1, p2, k3) model is implemented; the rational, thin-prism and tilted "
+                    "coefficients must be 0")
+    d5 = np.zeros(5)
+    d5[:min(d.size, 5)] = d[:5]
+    return d5 if np.any(d5 != 0) else None
+
+
+def _takes_dist(fn):
+    """a backend method that accepts dist= (the HIP Engine's do; a backend without a distortion model must not be handed
+    distorted points silently)"""
+    import inspect
+    try:
+        ps = inspect.signature(fn).parameters
+    except (TypeError, ValueError):
+        return False
+    return "dist" in ps or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in ps.values())
+
+
+def _distort(x, y, d):
+    """forward model on normalized coordinates (float64, operation order of include/reloc_spec.h)"""
+    k1, k2, p1, p2, k3 = (float(v) for v in d)
+    r2 = x * x + y * y
+    r4 = r2 * r2
+    r6 = r4 * r2
+    rad = 1.0 + k1 * r2 + k2 * r4 + k3 * r6
+    a1 = 2.0 * x * y
+    a2 = r2 + 2.0 * x * x
+    a3 = r2 + 2.0 * y * y
+    return x * rad + p1 * a1 + p2 * a2, y * rad + p1 * a3 + p2 * a1
 
 
 class KeyPoint:
@@ -142,8 +188,25 @@ class _BFMatcher:
         return out
 
 
+class _Fisheye:
+    """cv2.fisheye stands in only to say that the fisheye model is not implemented: every function raises `error`."""
+
+    def __getattr__(self, name):
+        if name.startswith("__"):
+            raise AttributeError(name)
+
+        def _unsupported(*_a, **_kw):
+            raise error(f"fisheye.{name}: the fisheye camera model is not implemented (only k1, k2, p1, p2, k3)")
+        return _unsupported
+
+
+fisheye = _Fisheye()
+
+
 class Cv2Shim:
     """The cv2 surface over one backend (an Engine, or a test double with the same methods)."""
+
+    fisheye = fisheye
 
     NORM_HAMMING = NORM_HAMMING
     COLOR_BGR2GRAY = COLOR_BGR2GRAY
@@ -188,7 +251,8 @@ class Cv2Shim:
         """All accepted `flags` (ITERATIVE, EPNP, P3P, AP3P -- the reference's history switches between ITERATIVE and EPNP,
         M:342-348) select the SAME solver: P3P + 1 hypotheses scored by reprojection, Levenberg-Marquardt refinement on the
         inliers.  Anything this solver would silently ignore raises `error` instead: another flag, an
-        extrinsic guess, lens distortion."""
+        extrinsic guess, a distortion model other than (k1, k2, p1, p2[, k3]).  Non-zero distCoeffs select the distorted
+        solver (scoring and refinement in distorted pixels); zeros or None the pinhole one."""
         if flags not in (SOLVEPNP_ITERATIVE, SOLVEPNP_EPNP, SOLVEPNP_P3P, SOLVEPNP_AP3P):
             raise error(f"solvePnPRansac: flags={flags!r} is not implemented (ITERATIVE, EPNP, P3P and AP3P map to one solver)")
         if useExtrinsicGuess:
@@ -197,16 +261,18 @@ class Cv2Shim:
         img = np.asarray(imagePoints, np.float32).reshape(-1, 2)
         if len(obj) != len(img):
             raise error("solvePnPRansac: object/image point counts differ")
-        if distCoeffs is not None and np.any(np.asarray(distCoeffs) != 0):
-            raise error("solvePnPRansac: lens distortion is not implemented (the reference passes zeros)")
+        dist = _dist_coeffs(distCoeffs, "solvePnPRansac")
+        if dist is not None and not _takes_dist(self.backend.pnp_ransac):
+            raise error("solvePnPRansac: lens distortion is not implemented by this backend (its pnp_ransac takes no dist)")
         K = np.asarray(cameraMatrix, np.float64).reshape(3, 3)
         K4 = np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
         if len(obj) < 4:
             return False, np.zeros((3, 1)), np.zeros((3, 1)), None
         try:
+            kw = {} if dist is None else {"dist": dist}
             ok, r, t, inl = self.backend.pnp_ransac(obj, img, K4=K4, iters=int(iterationsCount),
                                                     thr_px=float(reprojectionError), conf=float(confidence),
-                                                    seed=self.ransac_seed)
+                                                    seed=self.ransac_seed, **kw)
         except RelocError as e:
             raise error(str(e)) from e
         if not ok:
@@ -214,12 +280,45 @@ class Cv2Shim:
         return True, r.reshape(3, 1).copy(), t.reshape(3, 1).copy(), inl.astype(np.int32).reshape(-1, 1)
 
     def projectPoints(self, objectPoints, rvec, tvec, cameraMatrix, distCoeffs=None, **_):
+        """float64 NumPy; with non-zero distCoeffs through the forward model (include/reloc_spec.h), otherwise pinhole"""
+        dist = _dist_coeffs(distCoeffs, "projectPoints")
         obj = np.asarray(objectPoints, np.float64).reshape(-1, 3)
         K = np.asarray(cameraMatrix, np.float64).reshape(3, 3)
         R = _rodrigues_matrix(rvec)
         pc = obj @ R.T + np.asarray(tvec, np.float64).reshape(1, 3)
+        if dist is not None:
+            xd, yd = _distort(pc[:, 0] / pc[:, 2], pc[:, 1] / pc[:, 2], dist)
+            uv = np.stack([K[0, 0] * xd + K[0, 2], K[1, 1] * yd + K[1, 2]], axis=1)
+            return uv.reshape(-1, 1, 2), None
         uv = np.stack([K[0, 0] * pc[:, 0] / pc[:, 2] + K[0, 2], K[1, 1] * pc[:, 1] / pc[:, 2] + K[1, 2]], axis=1)
         return uv.reshape(-1, 1, 2), None
+
+    def undistortPoints(self, src, cameraMatrix, distCoeffs, R=None, P=None):
+        """(N, 1, 2) normalized points (five fixed-point iterations, on the GPU), or projected by P (3x3 or 3x4, its first
+        three columns) when given.  The dtype follows src (float32 or float64); the pixels are read as float32, as every pixel
+        input of the library is.  A non-identity R raises."""
+        a = np.asarray(src)
+        if a.dtype not in (np.float32, np.float64) or a.size % 2:
+            raise error("undistortPoints: src must be float32 or float64 points of 2 coordinates")
+        if R is not None and not np.array_equal(np.asarray(R, np.float64).reshape(3, 3), np.eye(3)):
+            raise error("undistortPoints: a rectification R other than the identity is not implemented")
+        dist = _dist_coeffs(distCoeffs, "undistortPoints")
+        K = np.asarray(cameraMatrix, np.float64).reshape(3, 3)
+        K4 = np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
+        if not hasattr(self.backend, "undistort_points"):
+            raise error("undistortPoints: not implemented by this backend (it has no undistort_points)")
+        try:
+            xy = self.backend.undistort_points(a.reshape(-1, 2), K4=K4, dist=dist)
+        except RelocError as e:
+            raise error(str(e)) from e
+        if P is not None:
+            Pm = np.asarray(P, np.float64)
+            if Pm.shape not in ((3, 3), (3, 4)):
+                raise error("undistortPoints: P must be 3x3 or 3x4")
+            x, y = xy[:, 0], xy[:, 1]
+            w = 1.0 / (Pm[2, 0] * x + Pm[2, 1] * y + Pm[2, 2])
+            xy = np.stack([(Pm[0, 0] * x + Pm[0, 1] * y + Pm[0, 2]) * w, (Pm[1, 0] * x + Pm[1, 1] * y + Pm[1, 2]) * w], axis=1)
+        return xy.reshape(-1, 1, 2).astype(a.dtype)
 
     def Rodrigues(self, src, **_):
         a = np.asarray(src, np.float64)
@@ -274,6 +373,10 @@ def solvePnPRansac(*a, **kw):
 
 def projectPoints(*a, **kw):
     return default_shim().projectPoints(*a, **kw)
+
+
+def undistortPoints(*a, **kw):
+    return default_shim().undistortPoints(*a, **kw)
 
 
 def Rodrigues(*a, **kw):

@@ -332,18 +332,43 @@ class Engine:
                                                    C.c_void_p(out_dev)), "reloc_hamming_matrix_dev")
 
     # ------------------------------------------------------------------ PnP
-    def pnp_score(self, obj, img, Rt, K4=K4_DEFAULT, thr_px=3.0, want_mask=False):
+    @staticmethod
+    def _dist5(dist):
+        """k1 k2 p1 p2 [k3] -> (5,) float64 (missing k3 = 0)"""
+        d = np.asarray(dist, np.float64).ravel()
+        if d.size not in (4, 5):
+            raise N.RelocError("distortion: expected 4 or 5 coefficients (k1, k2, p1, p2[, k3])")
+        return np.ascontiguousarray(np.concatenate([d, np.zeros(5 - d.size)]))
+
+    def pnp_score(self, obj, img, Rt, K4=K4_DEFAULT, thr_px=3.0, want_mask=False, dist=None):
+        """dist=None: the pinhole entry point; otherwise k1 k2 p1 p2 [k3] (reloc_pnp_score_dist)"""
         obj = np.ascontiguousarray(obj, np.float32).reshape(-1, 3)
         img = np.ascontiguousarray(img, np.float32).reshape(-1, 2)
         Rt = np.ascontiguousarray(Rt, np.float64).reshape(-1, 12)
         K4 = np.ascontiguousarray(K4, np.float64)
         cnt = np.empty(len(Rt), np.int32)
         mask = np.empty((len(Rt), len(obj)), np.uint8) if want_mask else None
-        N.check(self._lib.reloc_pnp_score(self._ctx, N.ptr(obj), N.ptr(img), len(obj), N.ptr(Rt), len(Rt), N.ptr(K4),
-                                          float(thr_px), N.ptr(cnt), N.ptr(mask)), "reloc_pnp_score")
+        if dist is None:
+            N.check(self._lib.reloc_pnp_score(self._ctx, N.ptr(obj), N.ptr(img), len(obj), N.ptr(Rt), len(Rt), N.ptr(K4),
+                                              float(thr_px), N.ptr(cnt), N.ptr(mask)), "reloc_pnp_score")
+        else:
+            d = self._dist5(dist)
+            N.check(self._lib.reloc_pnp_score_dist(self._ctx, N.ptr(obj), N.ptr(img), len(obj), N.ptr(Rt), len(Rt), N.ptr(K4),
+                                                   N.ptr(d), float(thr_px), N.ptr(cnt), N.ptr(mask)), "reloc_pnp_score_dist")
         return (cnt, mask) if want_mask else cnt
 
-    def pnp_ransac(self, obj, img, K4=K4_DEFAULT, iters=200, thr_px=3.0, conf=0.99, seed=0):
+    def undistort_points(self, img, K4=K4_DEFAULT, dist=None):
+        """cv2.undistortPoints(img, K, dist) without R / P: (m, 2) pixels -> (m, 2) float64 normalized points"""
+        img = np.ascontiguousarray(img, np.float32).reshape(-1, 2)
+        K4 = np.ascontiguousarray(K4, np.float64).reshape(4)
+        d = np.zeros(5) if dist is None else self._dist5(dist)
+        out = np.empty((len(img), 2), np.float64)
+        N.check(self._lib.reloc_undistort_points(self._ctx, N.ptr(img), len(img), N.ptr(K4), N.ptr(d), N.ptr(out)),
+                "reloc_undistort_points")
+        return out
+
+    def pnp_ransac(self, obj, img, K4=K4_DEFAULT, iters=200, thr_px=3.0, conf=0.99, seed=0, dist=None):
+        """dist=None: the pinhole entry point; otherwise k1 k2 p1 p2 [k3] (reloc_pnp_ransac_dist)"""
         obj = np.ascontiguousarray(obj, np.float32).reshape(-1, 3)
         img = np.ascontiguousarray(img, np.float32).reshape(-1, 2)
         if len(obj) != len(img):
@@ -352,9 +377,15 @@ class Engine:
         rvec = np.zeros(3); tvec = np.zeros(3)
         inl = np.empty(max(len(obj), 1), np.int32)
         n = C.c_int32(); ok = C.c_int32()
-        N.check(self._lib.reloc_pnp_ransac(self._ctx, N.ptr(obj), N.ptr(img), len(obj), N.ptr(K4), int(iters),
-                                           float(thr_px), float(conf), int(seed), N.ptr(rvec), N.ptr(tvec), N.ptr(inl),
-                                           C.byref(n), C.byref(ok)), "reloc_pnp_ransac")
+        if dist is None:
+            N.check(self._lib.reloc_pnp_ransac(self._ctx, N.ptr(obj), N.ptr(img), len(obj), N.ptr(K4), int(iters),
+                                               float(thr_px), float(conf), int(seed), N.ptr(rvec), N.ptr(tvec), N.ptr(inl),
+                                               C.byref(n), C.byref(ok)), "reloc_pnp_ransac")
+        else:
+            d = self._dist5(dist)
+            N.check(self._lib.reloc_pnp_ransac_dist(self._ctx, N.ptr(obj), N.ptr(img), len(obj), N.ptr(K4), N.ptr(d),
+                                                    int(iters), float(thr_px), float(conf), int(seed), N.ptr(rvec),
+                                                    N.ptr(tvec), N.ptr(inl), C.byref(n), C.byref(ok)), "reloc_pnp_ransac_dist")
         return bool(ok.value), rvec, tvec, inl[: n.value].copy()
 
     # ------------------------------------------------------------------ fused tick
@@ -392,6 +423,17 @@ class Engine:
         b = None if base_to_cam_t is None else np.ascontiguousarray(base_to_cam_t, np.float64).reshape(3)
         c = None if base_to_cam_R is None else np.ascontiguousarray(base_to_cam_R, np.float64).reshape(9)
         N.check(self._lib.reloc_set_camera(self._ctx, N.ptr(a), N.ptr(b), N.ptr(c)), "reloc_set_camera")
+
+    def set_distortion(self, dist=()):
+        """lens distortion of the fused tick, recording and accumulation: OpenCV's k1 k2 p1 p2 [k3 ...] (4, 5, 8, 12 or 14
+        values, everything after k3 zero), () / None / all zero = pinhole"""
+        d = np.ascontiguousarray(np.zeros(0) if dist is None else np.asarray(dist, np.float64).ravel())
+        N.check(self._lib.reloc_set_distortion(self._ctx, N.ptr(d) if d.size else None, int(d.size)), "reloc_set_distortion")
+
+    def get_distortion(self) -> np.ndarray:
+        d = np.zeros(5)
+        N.check(self._lib.reloc_get_distortion(self._ctx, N.ptr(d)), "reloc_get_distortion")
+        return d
 
     def tick_debug(self):
         ids = np.zeros(32, np.int32); n = C.c_int32(); nm = np.zeros(32, np.int32); ni = np.zeros(32, np.int32)

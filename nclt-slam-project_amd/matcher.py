@@ -32,6 +32,9 @@ class MatcherConfig:
     fy: float = 320.0
     cx: float = 320.0
     cy: float = 240.0
+    # lens distortion, OpenCV's (k1, k2, p1, p2[, k3]) -- e.g. sensor_msgs/CameraInfo.d of a plumb_bob camera; () = pinhole
+    # (the reference's DIST = zeros, M:52).  Longer OpenCV vectors are accepted when everything after k3 is zero.
+    dist: tuple = ()
     candidate_radius_m: float = 8.0
     max_candidates: int = 5
     heading_tol_deg: float = 90.0
@@ -96,7 +99,7 @@ class LandmarkMatcherCore:
         self._adopt(load_landmarks(landmarks) if isinstance(landmarks, str) else landmarks)
         self.orb = cv2.ORB_create(nfeatures=self.cfg.nfeatures)
         self.matcher = cv2.BFMatcher(cv2.NORM_HAMMING, crossCheck=True)
-        self.dist = np.zeros((4, 1), dtype=np.float32)
+        self.dist = np.zeros((4, 1), dtype=np.float32) if len(self.cfg.dist) == 0 else np.asarray(self.cfg.dist, np.float64).reshape(-1, 1)
         self.last_anchor_ts = 0.0
         self.n_attempts = 0
         self.n_published = 0
@@ -298,7 +301,13 @@ class LandmarkMatcherCore:
         if ok.sum() < cfg.accum_min_kpts:
             return False
         uu, vv, z = uu[ok], vv[ok], z[ok]
-        pts3 = np.stack([(uu - cfg.cx) * z / cfg.fx, (vv - cfg.cy) * z / cfg.fy, z], axis=-1).astype(np.float32)
+        if np.any(self.dist != 0):
+            # a distorted camera: the rounded pixels through the inverse model (as k_accumulate_dist, include/reloc_spec.h)
+            xu = self.cv2.undistortPoints(np.stack([uu, vv], 1).astype(np.float64).reshape(-1, 1, 2), cfg.K.astype(np.float64),
+                                          self.dist).reshape(-1, 2)
+            pts3 = np.stack([xu[:, 0] * z, xu[:, 1] * z, z], axis=-1).astype(np.float32)
+        else:
+            pts3 = np.stack([(uu - cfg.cx) * z / cfg.fx, (vv - cfg.cy) * z / cfg.fy, z], axis=-1).astype(np.float32)
         R_wb = P.quat_to_rot(*base_pose[3:7])
         c = np.array(base_pose[:3], dtype=np.float64) + R_wb @ self.base_to_cam_t
         q = P.rot_to_quat_scipy(R_wb @ self.base_to_cam_R)          # the reference converts with scipy here (M:478-479)
@@ -342,6 +351,7 @@ class FusedLandmarkMatcher:
                      gray_coeff_bits=cfg.gray_coeff_bits)
         e.set_camera([cfg.fx, cfg.fy, cfg.cx, cfg.cy], data.get("base_to_cam_translation", P.BASE_TO_CAM_TRANSLATION),
                      data.get("base_to_cam_rot", P.BASE_TO_CAM_ROT))
+        e.set_distortion(cfg.dist)
         self._return_src = return_landmarks
         self.swap_flag = swap_flag
         self._swapped = False

@@ -39,10 +39,16 @@ def local_depth_std(depth_mm, uu, vv):
 
 
 class LandmarkRecorderCore:
-    def __init__(self, out_pkl=None, min_disp_m: float = 2.0, cv2=None, nfeatures: int = 500, logger=None, engine=None):
+    def __init__(self, out_pkl=None, min_disp_m: float = 2.0, cv2=None, nfeatures: int = 500, logger=None, engine=None,
+                 dist=()):
         """engine: when given, ORB + all per-keypoint gates + back-projection run in ONE device call
-        (reloc_record_frame); otherwise the gates run in NumPy on the cv2-shaped module's features."""
+        (reloc_record_frame); otherwise the gates run in NumPy on the cv2-shaped module's features.
+        dist: lens distortion as MatcherConfig.dist (OpenCV's k1 k2 p1 p2 [k3], () = pinhole): the kept keypoints are
+        back-projected through the inverse model (engine: reloc_set_distortion; cv2 path: cv2.undistortPoints)."""
         self.engine = engine
+        self.dist = tuple(np.asarray(dist, np.float64).ravel()) if dist is not None else ()
+        if engine is not None:
+            engine.set_distortion(self.dist)
         self.nfeatures = nfeatures
         if cv2 is None and engine is None:
             from . import cv2_shim as cv2
@@ -89,7 +95,13 @@ class LandmarkRecorderCore:
         if ok.sum() < MIN_RECORD_KPTS:
             return None
         uu, vv, z = uu[ok], vv[ok], z[ok]
-        pts3 = np.stack([(uu - CX) * z / FX, (vv - CY) * z / FY, z], axis=-1).astype(np.float32)
+        if any(self.dist):
+            K = np.array([[FX, 0, CX], [0, FY, CY], [0, 0, 1]])
+            xu = cv2.undistortPoints(np.stack([uu, vv], 1).astype(np.float64).reshape(-1, 1, 2), K,
+                                     np.asarray(self.dist)).reshape(-1, 2)
+            pts3 = np.stack([xu[:, 0] * z, xu[:, 1] * z, z], axis=-1).astype(np.float32)
+        else:
+            pts3 = np.stack([(uu - CX) * z / FX, (vv - CY) * z / FY, z], axis=-1).astype(np.float32)
         rec = {"pose": cam_pose, "descriptors": desc[ok], "keypoints_2d": xy[ok], "keypoints_3d_cam": pts3,
                "ts": rgb_ts, "n_features": int(len(pts3))}
         self.landmarks.append(rec)

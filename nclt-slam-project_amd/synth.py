@@ -67,9 +67,43 @@ def rodrigues(rvec):
     return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
 
 
-def pnp_problem(rng, m=200, outlier_ratio=0.4, noise_px=0.0, rvec=None, tvec=None):
+def distort_normalized(x, y, dist):
+    """OpenCV's forward distortion model on normalized coordinates, dist = k1 k2 p1 p2 [k3] (include/reloc_spec.h)"""
+    d = np.zeros(5)
+    dd = np.asarray(dist, np.float64).ravel()
+    d[:dd.size] = dd
+    k1, k2, p1, p2, k3 = d
+    r2 = x * x + y * y
+    rad = 1.0 + k1 * r2 + k2 * r2 * r2 + k3 * r2 * r2 * r2
+    return (x * rad + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x), y * rad + p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y)
+
+
+def undistort_converged(u, v, dist, fx=FX, fy=FY, cx=CX, cy=CY, tol=1e-12, max_iter=500):
+    """pixels -> normalized coordinates by the fixed-point inverse of OpenCV's model, iterated until no coordinate moves by
+    more than tol (not OpenCV's five steps: the physical ray of the pixel)"""
+    d = np.zeros(5)
+    dd = np.asarray(dist, np.float64).ravel()
+    d[:dd.size] = dd
+    k1, k2, p1, p2, k3 = d
+    x0 = (np.asarray(u, np.float64) - cx) / fx
+    y0 = (np.asarray(v, np.float64) - cy) / fy
+    x, y = x0.copy(), y0.copy()
+    for _ in range(max_iter):
+        r2 = x * x + y * y
+        ic = 1.0 / (1.0 + ((k3 * r2 + k2) * r2 + k1) * r2)
+        xn = (x0 - (2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x))) * ic
+        yn = (y0 - (p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y)) * ic
+        step = max(float(np.max(np.abs(xn - x), initial=0.0)), float(np.max(np.abs(yn - y), initial=0.0)))
+        x, y = xn, yn
+        if step <= tol:
+            return x, y
+    raise ValueError("undistort_converged: the fixed-point iteration did not converge (distortion too strong)")
+
+
+def pnp_problem(rng, m=200, outlier_ratio=0.4, noise_px=0.0, rvec=None, tvec=None, dist=None):
     """3-D points in the frustum z in [0.5, 15], a pose with |t| < 2 m and angle < 20 deg, pixel noise
-    and gross outliers.  Returns obj(m,3) f32, img(m,2) f32, rvec, tvec, inlier mask."""
+    and gross outliers.  Returns obj(m,3) f32, img(m,2) f32, rvec, tvec, inlier mask.
+    dist: k1 k2 p1 p2 [k3] -- image points through OpenCV's forward distortion model (None: pinhole, today's arrays)."""
     if rvec is None:
         ax = rng.normal(size=3); ax /= np.linalg.norm(ax)
         rvec = ax * np.deg2rad(rng.uniform(0, 20))
@@ -88,7 +122,11 @@ def pnp_problem(rng, m=200, outlier_ratio=0.4, noise_px=0.0, rvec=None, tvec=Non
                 obj.append(p)
     obj = np.array(obj, np.float32)
     pc = (R @ obj.astype(np.float64).T).T + tvec
-    uv = np.stack([FX * pc[:, 0] / pc[:, 2] + CX, FY * pc[:, 1] / pc[:, 2] + CY], 1)
+    if dist is None:
+        uv = np.stack([FX * pc[:, 0] / pc[:, 2] + CX, FY * pc[:, 1] / pc[:, 2] + CY], 1)
+    else:
+        xd, yd = distort_normalized(pc[:, 0] / pc[:, 2], pc[:, 1] / pc[:, 2], dist)
+        uv = np.stack([FX * xd + CX, FY * yd + CY], 1)
     if noise_px > 0:
         uv += rng.normal(0, noise_px, uv.shape)
     out = rng.random(m) < outlier_ratio
@@ -129,19 +167,25 @@ def descriptor_db(rng, n_records, rows="fixed64", cur=None, planted_records=(), 
 # on base_link (0.35 m forward, 0.18 m up, optical frame right-down-forward).
 class WallScene:
     """world: x forward, y left, z up.  The wall is the plane x = wall_x; its texture is metric
-    (`m_per_px` metres per texel).  render(base_pose) -> (bgr (H,W,3) u8, depth_mm (H,W) u16)."""
+    (`m_per_px` metres per texel).  render(base_pose) -> (bgr (H,W,3) u8, depth_mm (H,W) u16).
+    dist: k1 k2 p1 p2 [k3] -- a camera with OpenCV's lens distortion: every pixel's ray comes from the converged inverse
+    model (None: pinhole, today's rays)."""
 
     # optical axes expressed in base_link coordinates (columns): x_cam = -y, y_cam = -z, z_cam = +x
     R_BASE_CAM = np.array([[0.0, 0.0, 1.0], [-1.0, 0.0, 0.0], [0.0, -1.0, 0.0]])
     T_BASE_CAM = np.array([0.35, 0.0, 0.18])
 
-    def __init__(self, seed=20260501, wall_x=16.0, m_per_px=0.02, tex_w=2400, tex_h=1200, w=640, h=480, noise=2.0):
+    def __init__(self, seed=20260501, wall_x=16.0, m_per_px=0.02, tex_w=2400, tex_h=1200, w=640, h=480, noise=2.0, dist=None):
         rng = np.random.default_rng(seed)
         self.seed = seed
         self.tex = textured_frame(rng, tex_w, tex_h, n_shapes=2600, noise=0.0).astype(np.float32)
         self.wall_x, self.m_per_px, self.w, self.h, self.noise = wall_x, m_per_px, w, h, noise
         v, u = np.mgrid[0:h, 0:w]
-        self.rays = np.stack([(u - CX) / FX, (v - CY) / FY, np.ones_like(u, dtype=np.float64)], axis=-1)  # camera frame
+        if dist is None:
+            self.rays = np.stack([(u - CX) / FX, (v - CY) / FY, np.ones_like(u, dtype=np.float64)], axis=-1)  # camera frame
+        else:
+            xu, yu = undistort_converged(u, v, dist)
+            self.rays = np.stack([xu, yu, np.ones_like(u, dtype=np.float64)], axis=-1)
 
     @staticmethod
     def _quat_to_rot(q):

@@ -1,0 +1,226 @@
+"""Lens distortion on the host side (no GPU): known answers of the model restated in tests/distortion_ref.py, and the cv2
+shim's handling of distCoeffs (routing to the backend, errors, the pinhole path left bit-identical)."""
+import numpy as np
+import pytest
+
+import distortion_ref as DR
+from nclt_slam_project_amd import synth
+from nclt_slam_project_amd.cv2_shim import Cv2Shim, error
+
+K = np.array([[320.0, 0, 320.0], [0, 320.0, 240.0], [0, 0, 1]])
+K4 = (320.0, 320.0, 320.0, 240.0)
+D = np.array([-0.28, 0.07, 1e-3, -2e-3, 0.0])
+
+
+class RecordingBackend:
+    """Engine stand-in: records the keyword arguments of pnp_ransac, undistorts with the NumPy restatement."""
+
+    def __init__(self):
+        self.calls = []
+
+    def pnp_ransac(self, obj, img, **kw):
+        self.calls.append(kw)
+        return True, np.zeros(3), np.zeros(3), np.arange(len(obj), dtype=np.int32)
+
+    def undistort_points(self, img, K4, dist=None):
+        img = np.asarray(img, np.float32).reshape(-1, 2)
+        x, y = DR.undistort(img[:, 0], img[:, 1], K4, np.zeros(5) if dist is None else dist)
+        return np.stack([x, y], 1)
+
+
+@pytest.fixture
+def shim():
+    return Cv2Shim(RecordingBackend())
+
+
+def test_forward_model_known_answer(shim):
+    uv, _ = shim.projectPoints(np.array([[0.9, -0.6, 3.0]]), np.zeros(3), np.zeros(3), K, D)
+    assert uv.shape == (1, 1, 2)
+    assert np.abs(uv.reshape(2) - [412.382368, 178.397888]).max() < 1e-9
+    # the same number from the NumPy restatement
+    assert np.abs(DR.project([[0.9, -0.6, 3.0]], K4, D).reshape(2) - [412.382368, 178.397888]).max() < 1e-9
+
+
+def test_inverse_is_exactly_five_iterations():
+    x, y = DR.undistort(600.0, 40.0, K4, D)
+    assert abs(x[0] - 1.2246032820097574) < 1e-12 and abs(y[0] - (-0.8733659532374055)) < 1e-12
+    xc, yc = DR.undistort(600.0, 40.0, K4, D, iters=200)
+    assert abs(xc[0] - 1.22465481) < 1e-8 and abs(yc[0] - (-0.87340323)) < 1e-8
+    assert abs(x[0] - xc[0]) > 1e-5                              # five steps are not the converged value
+
+
+def test_inverse_negative_icdist_keeps_the_start():
+    d = (-2.0, 0.0, 0.0, 0.0, 0.0)                                # barrel so strong that 1 + k1 r2 < 0 at the corner
+    x, y = DR.undistort(0.0, 0.0, K4, d)
+    assert x[0] == (0.0 - 320.0) * (1.0 / 320.0) and y[0] == (0.0 - 240.0) * (1.0 / 320.0)
+
+
+@pytest.mark.parametrize("shape", [(4, 1), (1, 4), (5,), (1, 5), (5, 1), (8,), (14, 1)])
+def test_shim_routes_nonzero_distortion(shim, shape):
+    rng = np.random.default_rng(1)
+    obj = rng.normal(size=(20, 3)).astype(np.float32)
+    img = rng.normal(size=(20, 2)).astype(np.float32)
+    n = int(np.prod(shape))
+    d = np.zeros(n)
+    d[:min(n, 5)] = D[:min(n, 5)] if n >= 5 else D[:4]
+    ok, *_ = shim.solvePnPRansac(obj, img, K, d.reshape(shape))
+    assert ok
+    got = shim.backend.calls[-1]["dist"]
+    exp = np.zeros(5)
+    exp[:4] = D[:4]
+    if n >= 5:
+        exp[4] = D[4]
+    assert np.array_equal(got, exp)
+
+
+@pytest.mark.parametrize("d", [None, np.zeros((4, 1)), np.zeros((1, 5)), np.zeros(5), np.zeros(8), np.zeros(0)])
+def test_shim_zero_distortion_is_pinhole(shim, d):
+    obj = np.ones((10, 3), np.float32)
+    img = np.ones((10, 2), np.float32)
+    shim.solvePnPRansac(obj, img, K, d)
+    assert "dist" not in shim.backend.calls[-1]
+
+
+@pytest.mark.parametrize("d", [np.r_[D, 0.0, 0.0, 1e-3], np.r_[D, np.zeros(6), 0.0, 1e-4], np.r_[D[:4], np.nan],
+                               np.array([np.inf, 0, 0, 0]), np.zeros(6), np.zeros(3)])
+def test_shim_rejects_unsupported_models(shim, d):
+    obj = np.ones((10, 3), np.float32)
+    img = np.ones((10, 2), np.float32)
+    with pytest.raises(error):
+        shim.solvePnPRansac(obj, img, K, d)
+    with pytest.raises(error):
+        shim.projectPoints(obj, np.zeros(3), np.zeros(3), K, d)
+    assert not shim.backend.calls
+
+
+def test_project_points_zero_distortion_bit_identical(shim):
+    rng = np.random.default_rng(3)
+    obj = rng.uniform(-2, 2, (200, 3)) + [0, 0, 6]
+    rvec, tvec = rng.normal(size=3) * 0.1, rng.normal(size=3) * 0.2
+    base, _ = shim.projectPoints(obj, rvec, tvec, K, None)
+    for d in (np.zeros((4, 1)), np.zeros(5), np.zeros(14), np.zeros((1, 5))):
+        got, _ = shim.projectPoints(obj, rvec, tvec, K, d)
+        assert got.tobytes() == base.tobytes()
+    distorted, _ = shim.projectPoints(obj, rvec, tvec, K, D)
+    assert np.abs(distorted - base).max() > 1.0
+
+
+def test_undistort_points_shapes_dtypes_and_P(shim):
+    px = np.array([[600.0, 40.0], [320.0, 240.0], [10.0, 470.0]])
+    for dt in (np.float32, np.float64):
+        out = shim.undistortPoints(px.astype(dt).reshape(-1, 1, 2), K, D)
+        assert out.shape == (3, 1, 2) and out.dtype == dt
+    out = shim.undistortPoints(px.reshape(-1, 1, 2), K, D)
+    assert abs(out[0, 0, 0] - 1.2246032820097574) < 1e-12 and out[1, 0, 0] == 0.0
+    # P = K maps the normalized points back to ideal pixels; the 3x4 form reads the first three columns
+    p3 = shim.undistortPoints(px.reshape(-1, 1, 2), K, D, P=K)
+    p4 = shim.undistortPoints(px.reshape(-1, 1, 2), K, D, P=np.hstack([K, np.ones((3, 1))]))
+    assert np.array_equal(p3, p4)
+    assert np.abs(p3[:, 0, 0] - (320.0 * out[:, 0, 0] + 320.0)).max() < 1e-9
+    # forward(undistort(px)) returns px up to what five steps leave (moderate distortion: 6e-9 px here, 1.2e-3 px in the
+    # corners of a 640 x 480 frame)
+    dm = (-0.12, 0.03, 5e-4, -3e-4, 0.0)
+    xy = shim.undistortPoints(np.array([[400.0, 300.0]]).reshape(-1, 1, 2), K, dm).reshape(2)
+    uv, _ = shim.projectPoints(np.array([[xy[0], xy[1], 1.0]]), np.zeros(3), np.zeros(3), K, dm)
+    assert np.abs(uv.reshape(2) - [400.0, 300.0]).max() < 1e-7
+    assert shim.undistortPoints(px.reshape(-1, 1, 2), K, D, R=np.eye(3)).shape == (3, 1, 2)
+
+
+def test_undistort_points_rejects_rotation_and_bad_models(shim):
+    px = np.array([[600.0, 40.0]]).reshape(-1, 1, 2)
+    c, s = np.cos(0.1), np.sin(0.1)
+    with pytest.raises(error):
+        shim.undistortPoints(px, K, D, R=np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]]))
+    with pytest.raises(error):
+        shim.undistortPoints(px, K, np.r_[D, 0.0, 0.0, 0.5])
+    with pytest.raises(error):
+        shim.undistortPoints(px, K, np.array([np.nan, 0, 0, 0]))
+
+
+def test_synth_default_arrays_unchanged_and_distorted_problem():
+    a = synth.pnp_problem(np.random.default_rng(5), m=80, outlier_ratio=0.3, noise_px=0.2)
+    b = synth.pnp_problem(np.random.default_rng(5), m=80, outlier_ratio=0.3, noise_px=0.2, dist=None)
+    for x, y in zip(a, b):
+        assert np.array_equal(x, y)
+    obj, img, rvec, tvec, inl = synth.pnp_problem(np.random.default_rng(5), m=80, outlier_ratio=0.0, dist=D)
+    pc = obj.astype(np.float64) @ synth.rodrigues(rvec).T + tvec
+    assert np.abs(img - DR.project(pc, K4, D)).max() < 1e-3       # float32 pixels of the forward model
+    # converged rays: the forward model maps them back to their pixel
+    u = np.array([0.0, 639.0, 320.0]); v = np.array([0.0, 479.0, 240.0])
+    dm = (-0.12, 0.03, 5e-4, -3e-4, 0.0)
+    x, y = synth.undistort_converged(u, v, dm)
+    uv = DR.project(np.stack([x, y, np.ones(3)], 1), K4, dm)
+    assert np.abs(uv - np.stack([u, v], 1)).max() < 1e-9
+
+
+def test_fisheye_and_backends_without_undistortion_raise_cv2_error():
+    from nclt_slam_project_amd import cv2_shim
+    with pytest.raises(error):
+        cv2_shim.fisheye.undistortPoints(np.zeros((1, 1, 2)), K, np.zeros(4))
+    with pytest.raises(error):
+        Cv2Shim(object()).fisheye.projectPoints(np.zeros((1, 1, 3)), np.zeros(3), np.zeros(3), K, np.zeros(4))
+
+    class NoUndistortion:
+        pass
+    with pytest.raises(error):
+        Cv2Shim(NoUndistortion()).undistortPoints(np.zeros((1, 1, 2)), K, D)
+
+
+def _oracle_dist_cv2():
+    from oracle_backend import OracleBackend
+
+    class OracleWithUndistortion(OracleBackend):
+        """the CPU oracle's features, undistortion by the NumPy restatement"""
+
+        def undistort_points(self, img, K4, dist=None):
+            return RecordingBackend.undistort_points(self, img, K4, dist)
+    return Cv2Shim(OracleWithUndistortion())
+
+
+def _expected_points(kp2d, z, d):
+    uv = np.round(np.asarray(kp2d, np.float32)).astype(np.int32)
+    x, y = DR.undistort(uv[:, 0], uv[:, 1], K4, d)
+    z = np.asarray(z, np.float32).astype(np.float64)
+    return np.stack([x * z, y * z, z], 1).astype(np.float32)
+
+
+def test_recorder_cv2_path_back_projects_through_the_model(oracle):
+    from nclt_slam_project_amd.recorder import LandmarkRecorderCore
+    cv2 = _oracle_dist_cv2()
+    bp = synth.base_pose(4.5, 0.0, 0.0)
+    bgr, dep = synth.WallScene().render(bp)
+    a = LandmarkRecorderCore(cv2=cv2).tick(bgr, dep, bp, 1.0)
+    b = LandmarkRecorderCore(cv2=cv2, dist=D).tick(bgr, dep, bp, 1.0)
+    assert a["n_features"] == b["n_features"] > 30
+    np.testing.assert_array_equal(a["keypoints_2d"], b["keypoints_2d"])            # the gates are pixel-based
+    np.testing.assert_array_equal(a["descriptors"], b["descriptors"])
+    exp = _expected_points(b["keypoints_2d"], b["keypoints_3d_cam"][:, 2], D)
+    np.testing.assert_array_equal(b["keypoints_3d_cam"], exp)
+    assert np.abs(b["keypoints_3d_cam"] - a["keypoints_3d_cam"]).max() > 0.01
+
+
+def test_host_matcher_accumulation_back_projects_through_the_model(oracle):
+    """LandmarkMatcherCore's accumulation (M:435-500) with MatcherConfig.dist: the new record's 3-D points come from the
+    inverse model, like the recorder's and the fused k_accumulate_dist"""
+    from nclt_slam_project_amd.matcher import LandmarkMatcherCore, MatcherConfig
+    from nclt_slam_project_amd.recorder import LandmarkRecorderCore
+    cv2 = _oracle_dist_cv2()
+    scene = synth.WallScene()
+    rec = LandmarkRecorderCore(cv2=cv2)
+    for x in (2.0, 4.5):
+        bp = synth.base_pose(x, 0.0, 0.0)
+        rec.tick(*scene.render(bp), bp, x)
+    bp = synth.base_pose(9.5, -14.0, 0.0)                 # no candidate within 8 m: the frame is accumulated
+    bgr, dep = scene.render(bp)
+    recs = []
+    for d in ((), tuple(D)):
+        m = LandmarkMatcherCore(rec.database(), cv2=cv2, config=MatcherConfig(dist=d))
+        n0 = len(m.landmarks)
+        o = m.tick(bgr, dep, bp, ts=1000.0)
+        assert o.outcome == "no_candidates" and len(m.landmarks) == n0 + 1
+        recs.append(m.landmarks[-1])
+    a, b = recs
+    assert b["accumulated"] and a["n_features"] == b["n_features"] >= 30
+    np.testing.assert_array_equal(a["keypoints_2d"], b["keypoints_2d"])
+    np.testing.assert_array_equal(b["keypoints_3d_cam"], _expected_points(b["keypoints_2d"], b["keypoints_3d_cam"][:, 2], D))
+    assert np.abs(b["keypoints_3d_cam"] - a["keypoints_3d_cam"]).max() > 0.01
