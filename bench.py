@@ -12,16 +12,21 @@ mutual match lists -> PnP-RANSAC(200) -> gates -> anchor pose; every frame's 96-
 copied back to (pinned) host memory.  Nothing is skipped or cached between frames.
 
 `value` is measured with the frames already resident in HBM when the timed region starts (the contract of
-the judged line).  `host_ingest` repeats the same K steps with every frame crossing PCIe first -- uploaded
-from pinned host memory on the stream that processes it, SURVEY.md 3.1's "once per tick: upload one RGB
-frame (921.6 KB)" -- and reports that rate beside it.  Per-step times (median / p95) come from events on
-the streams, recorded inside the timed region without synchronising.
+the judged line).  Per-step times (median / p95) come from events on the streams, recorded inside the timed
+region without synchronising.
+
+A plain run does only what the headline needs: set-up, the pre-roll and W warm-up steps, the K timed steps,
+--dump-outputs if given, and the JSON line.  Everything else runs after the timed steps and only with --full
+(the --no-* options then skip single parts): `host_ingest` repeats the same K steps with every frame crossing
+PCIe first -- uploaded from pinned host memory on the stream that processes it, SURVEY.md 3.1's "once per tick:
+upload one RGB frame (921.6 KB)" -- and reports that rate beside it; then the figures listed below.  Without
+--full their keys are null, and so are `stage_us` and `hamming_match_GBps`, which come from the roofline launches.
 
 N > 1: frames are the independent units (a 10k-record database is 20 MB and fits every GPU), so each
 rank runs its own frame stream against its own replica and there is no data-path collective;
 per-GPU work is fixed ("weak").  value = frames of all ranks / max-over-ranks time.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+Rank 0 prints ONE JSON line with the contract fields plus, with --full,
   roofline      dominant kernel (k_db_scan): algorithmic bytes / average launch duration measured
                 with HIP events on the kernel's stream, against the 8 TB/s HBM peak; the kernel is
                 VALU-bound by construction, so the VALU issue roofline is reported
@@ -521,13 +526,16 @@ def main(argv=None):
                          "all-gather of the per-shard top-25 (not the judged default; reports its own JSON line)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend; gloo + --rehearse runs N ranks on one GPU")
     ap.add_argument("--rehearse", action="store_true", help="developer rehearsal: every rank uses device 0")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-matrix", action="store_true")
-    ap.add_argument("--no-ingest", action="store_true", help="skip the second timed run with frames uploaded from host memory")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure host_ingest, the rooflines, stage_us, the tick latency (2 Hz\n"
+                         "too) and the CPU baseline; a plain run reports the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-matrix", action="store_true", help="with --full: skip roofline_matrix")
+    ap.add_argument("--no-ingest", action="store_true", help="with --full: skip the second timed run with frames uploaded from host memory")
     ap.add_argument("--distinct-frames", type=int, default=32, help="distinct synthetic frames cycled through (each with its own planted record)")
-    ap.add_argument("--no-2hz", action="store_true", help="skip the tick latency at the reference's 2 Hz cadence (~50 s of mostly idle time)")
+    ap.add_argument("--no-2hz", action="store_true", help="with --full: skip the tick latency at the reference's 2 Hz cadence (~50 s of mostly idle time)")
     ap.add_argument("--ticks-2hz", type=int, default=24, help="ticks of EACH form (exclusive / not), interleaved, per mode")
-    ap.add_argument("--no-extra-scans", action="store_true", help="skip roofline_ragged / roofline_small_q")
+    ap.add_argument("--no-extra-scans", action="store_true", help="with --full: skip roofline_ragged / roofline_small_q")
     ap.add_argument("--matrix-only", action="store_true",
                     help="BASELINE config 5 shape: the 20000 x 20000 u16 Hamming matrix, row blocks split over the ranks, no\n"
                          "reduction (not the judged default; reports its own JSON line)")
@@ -592,12 +600,14 @@ def main(argv=None):
             e.set_stream(ts.cuda_stream)
     e0 = engines[0]
     frames_dev = [e0.to_device(f) for f in frames]                       # resident frames (judged mode)
-    frames_pin = []
-    for f in frames:                                                      # host frames in pinned memory (ingest mode)
-        p = e0.pinned(f.shape, np.uint8)
-        p[...] = f
-        frames_pin.append(p)
-    stage = {id(e): e.dev_alloc(W * H * 3) for e in engines}              # per-context upload target
+    run_ingest = args.full and not args.no_ingest
+    frames_pin, stage = [], {}
+    if run_ingest:
+        for f in frames:                                                  # host frames in pinned memory (ingest mode)
+            p = e0.pinned(f.shape, np.uint8)
+            p[...] = f
+            frames_pin.append(p)
+        stage = {id(e): e.dev_alloc(W * H * 3) for e in engines}          # per-context upload target
     B = args.frames_per_step // NB * NB
     results = e0.pinned((B, 96), np.uint8)                                # one result record per frame of a step
 
@@ -661,7 +671,7 @@ def main(argv=None):
     last_records = np.array(results)                                      # the last timed step's records, before later runs overwrite them
     total_frames = world * B * args.steps
     ingest = None
-    if not args.no_ingest:
+    if run_ingest:
         el_i, ps_i, oc_i = timed(True)
         ingest = dict(value=total_frames / el_i, unit="frames/s", ms_per_step=el_i / args.steps * 1e3,
                       step_ms=dict(median=float(np.median(ps_i)), p95=float(np.percentile(ps_i, 95))),
@@ -672,7 +682,7 @@ def main(argv=None):
     # ---- the same kernels INSIDE the timed configuration: HIP events around every context's scan / ORB / PnP launches while
     # all S streams run the step loop (16 further steps, untimed); the single-stream figures below are their unloaded times
     in_config = None
-    if rank == 0:
+    if rank == 0 and args.full:
         for w in range(3):
             step(w * B, False)
         sync_all()
@@ -701,121 +711,120 @@ def main(argv=None):
 
     result = None
     if rank == 0:
-        e = engines[0]
-        # ---- dominant kernel: HIP events around k_db_scan on its own stream, live
-        e.profile_enable(True)
-        n_prof = 40
-        for i in range(n_prof):
-            if NB == 1:
-                e.tick_dev(frames_dev[i % n_distinct], W, H, base_poses[i % n_distinct], False, True, i)
-            else:      # the launch the timed region ran: one scan for NB frames
-                fs = [(i * NB + j) % n_distinct for j in range(NB)]
-                Engine.tick_batch_dev(groups[0], [frames_dev[f] for f in fs], W, H, [base_poses[f] for f in fs], global_reloc=True,
-                                      seeds=[i * NB + j for j in range(NB)])
-        e.sync()
-        scan_ms, scan_n = e.profile_get(0)
-        orb_ms, orb_n = e.profile_get(2)
-        pnp_ms, pnp_n = e.profile_get(3)
-        e.profile_enable(False)
-        # single-stream synchronous tick latency (enqueue + kernels + result record in host memory, waited for with reloc_tick_wait), global and local candidate
-        # search, with the context told that it is alone on the GPU (reloc_set_exclusive; the timed 4-stream runs above are not)
-        lat = {}
-        for mode, name in ((1, "tick_global"), (0, "tick_local")):
-            ts_ = []
-            e.tick_result_to(results[0])
-            e.set_exclusive(True)                                         # a synchronous single-stream loop: the deployment this hint is for
-            for i in range(120):
-                results[0, 72:76] = 255                                    # outcome field: overwritten by the tick
-                t0 = time.perf_counter()
-                e.tick_dev(frames_dev[i % n_distinct], W, H, base_poses[i % n_distinct], False, mode, i)
-                e.tick_wait()                                             # the result record is in host memory now (reloc_tick_wait)
-                ts_.append(time.perf_counter() - t0)
-                assert results[0, 72] != 255, "tick result record did not arrive"
-            e.set_exclusive(False)
-            ts_ = np.array(ts_[20:]) * 1e6
-            lat[name + "_us"] = dict(median=float(np.median(ts_)), p95=float(np.percentile(ts_, 95)))
         desc, pts, off, poses = db
         T, L, Q = int(off[-1]), len(off) - 1, 500
-        alg_bytes = NB * (32 * T + 32 * Q + 4 * L)        # per frame: database once, queries once, one count per record; NB frames per launch
-        scan_s = scan_ms / max(scan_n, 1) * 1e-3
-        pairs = NB * T * Q
-        # VALU ceilings measured on MI355X (tools/ubench_valu2.hip, profiles/r2_ubench_valu2.log): the bare distance,
-        # 8 x (v_xor_b32 s,v ; accumulating v_bcnt_u32_b32), reaches 2.99 T pairs/s at 8 waves/SIMD (2.91 T at the
-        # kernel's 4); with the kernel's argmin bookkeeping in the stream (shl16 + or + 3 min16 per pair) 2.21 T at 4
-        valu_peak_pairs = 2.99e12
-        roofline = dict(kernel="k_db_scan" if NB == 1 else "k_db_scan_batch", frames_per_launch=NB, bound="hbm", achieved=alg_bytes / scan_s / 1e9, peak=8000.0, unit="GB/s",
-                        frac=alg_bytes / scan_s / 1e9 / 8000.0, traffic=(pmc_traffic("k_db_scan") or 0) * NB or None,
-                        avg_launch_us=scan_s * 1e6, launches=scan_n, algorithmic_bytes=alg_bytes,
-                        note="VALU-bound by construction: 250 int-op/B at Q=500 (SURVEY.md 8d); HBM fraction cannot exceed ~2 %",
-                        valu=dict(pairs_per_s=pairs / scan_s, peak_pairs_per_s=valu_peak_pairs,
-                                  frac=pairs / scan_s / valu_peak_pairs,
-                                  lane_ops_per_s=16.0 * pairs / scan_s, spec_lane_ops_per_s=78.6e12,
-                                  frac_of_spec_issue=16.0 * pairs / scan_s / 78.6e12,
-                                  basis="measured chip ceiling of the bare 256-bit distance, 8 v_xor_b32 (full rate) + 8 accumulating "
-                                        "v_bcnt_u32_b32 (half rate) per pair (tools/ubench_valu2.hip); spec issue = 256 CU x 4 SIMD-32 x "
-                                        "2.4 GHz counts every instruction at full rate"))
-        stage_us = dict(orb=orb_ms / max(orb_n, 1) * 1e3, db_scan_per_frame=scan_s * 1e6 / NB, pnp=pnp_ms / max(pnp_n, 1) * 1e3)
-        if in_config:
-            ic_s = in_config["scan_avg_launch_us"] * 1e-6
-            roofline["in_config"] = dict(in_config, achieved=alg_bytes / ic_s / 1e9, frac=alg_bytes / ic_s / 1e9 / 8000.0,
-                                         pairs_per_s_per_scan=pairs / ic_s,
-                                         scans_resident=in_config["frames_per_s_with_events"] / NB * ic_s,
-                                         aggregate_pairs_per_s=total_frames / elapsed * T * Q,
-                                         aggregate_valu_frac=total_frames / elapsed * T * Q / valu_peak_pairs)
-            roofline["note_single_stream"] = ("avg_launch_us / stage_us: one idle stream after the timed region (unloaded kernel times); "
-                                              "in_config: the same launches while the timed configuration runs")
-        # ---- 2 Hz cadence: a tick every 0.5 s, as the reference's timer fires (M:76), each on an idle chip
-        if not args.no_2hz:
-            for mode, name in ((1, "tick_global"), (0, "tick_local")):
-                lat[name + "_2hz_us"], lat[name + "_2hz_not_exclusive_us"] = tick_latency_2hz(
-                    e, frames_dev, base_poses, results[0], args.ticks_2hz, 0.5, mode)
-            lat["note_2hz"] = ("exclusive and non-exclusive ticks interleaved in one loop, alternating order, same sample size; a local tick "
-                               "launches the same kernel shapes in both forms (reloc_tick.hip: latency shapes for LOCAL ticks)")
-        # ---- the scan on the record sizes of real teach databases, and the few-query shape that IS HBM-bound
-        roofline_ragged = roofline_small_q = None
-        if not args.no_extra_scans:
-            ex = Engine(local_rank, W, H, 2048)
-            rag = scan_case(ex, args.records, "ragged", (500,), SEED + 10)
-            r45 = scan_case(ex, args.records, 45, (500,), SEED + 11)
-            pick = lambda rows, form: next(r for r in rows if r["scheduling"] == form)
-            roofline_ragged = dict(pick(rag, "shared"), workload=f"--rows ragged: {args.records} records of clip(round(N(60,25)),30,500) rows, Q = 500",
-                                   alone=pick(rag, "alone"), rows45=dict(shared=pick(r45, "shared"), alone=pick(r45, "alone")),
-                                   note="teach databases of the reference are ragged, ~45-100 rows per record (routes/01_road/teach/README.md:57,75); "
-                                        "VALU-bound like the headline kernel: compare valu.pairs_per_s")
-            sq = scan_case(ex, 100000, "fixed64", (1, 8, 32), SEED + 12)
-            for r_ in sq:
-                r_["traffic"] = pmc_traffic({1: "k_db_scan_rows_q1", 8: "k_db_scan_rows_q8", 32: "k_db_scan_rows_q32"}.get(r_["Q"], "-"))
-            roofline_small_q = dict(sq[0], workload="100000 records x 64 rows (205 MB), Q = 1: the variant-G scan shape with few current descriptors "
-                                                    "(G:329-344), the HBM-bound match shape", by_Q={str(r["Q"]): r for r in sq})
-            ex.close()
-        roofline_matrix = None
-        if not args.no_matrix:
-            F = K = 20000
-            rng = np.random.default_rng(SEED + 4)
-            a = e.to_device(rng.integers(0, 256, (F, 32), dtype=np.uint8))
-            b = e.to_device(rng.integers(0, 256, (K, 32), dtype=np.uint8))
-            out = e.dev_alloc(F * K * 2)
-            for _ in range(MATRIX_PREROLL):                               # clock governor settles after ~40 ms of load, see bench_matrix
-                e.hamming_matrix_dev(a, F, b, K, out)
-            e.sync()
+        roofline = stage_us = lat = roofline_ragged = roofline_small_q = roofline_matrix = cpu = None
+        if args.full:
+            e = engines[0]
+            # ---- dominant kernel: HIP events around k_db_scan on its own stream, live
             e.profile_enable(True)
-            for _ in range(100):
-                e.hamming_matrix_dev(a, F, b, K, out)
+            n_prof = 40
+            for i in range(n_prof):
+                if NB == 1:
+                    e.tick_dev(frames_dev[i % n_distinct], W, H, base_poses[i % n_distinct], False, True, i)
+                else:      # the launch the timed region ran: one scan for NB frames
+                    fs = [(i * NB + j) % n_distinct for j in range(NB)]
+                    Engine.tick_batch_dev(groups[0], [frames_dev[f] for f in fs], W, H, [base_poses[f] for f in fs], global_reloc=True,
+                                          seeds=[i * NB + j for j in range(NB)])
             e.sync()
-            m_ms, m_n = e.profile_get(1)
+            scan_ms, scan_n = e.profile_get(0)
+            orb_ms, orb_n = e.profile_get(2)
+            pnp_ms, pnp_n = e.profile_get(3)
             e.profile_enable(False)
-            mb = 32 * (F + K) + 2 * F * K
-            ms = m_ms / max(m_n, 1) * 1e-3
-            roofline_matrix = dict(kernel="k_hamming_matrix", shape=[F, K], bound="hbm", achieved=mb / ms / 1e9, peak=8000.0,
-                                   unit="GB/s", frac=mb / ms / 1e9 / 8000.0, traffic=pmc_traffic("k_hamming_matrix"), avg_launch_us=ms * 1e6,
-                                   launches=m_n, algorithmic_bytes=mb,
-                                   valu=dict(pairs_per_s=F * K / ms, peak_pairs_per_s=2.99e12, frac=F * K / ms / 2.99e12))
-            for p in (a, b, out):
-                e.dev_free(p)
-        cpu = None
-        if not args.no_cpu_baseline and world == 1:
-            cpu = cpu_baseline(frames, db)
-            cpu["opencv"] = opencv_baseline(frames, db)       # None unless OpenCV is importable on this host
+            # single-stream synchronous tick latency (enqueue + kernels + result record in host memory, waited for with reloc_tick_wait), global and local candidate
+            # search, with the context told that it is alone on the GPU (reloc_set_exclusive; the timed 4-stream runs above are not)
+            lat = {}
+            for mode, name in ((1, "tick_global"), (0, "tick_local")):
+                ts_ = []
+                e.tick_result_to(results[0])
+                e.set_exclusive(True)                                         # a synchronous single-stream loop: the deployment this hint is for
+                for i in range(120):
+                    results[0, 72:76] = 255                                    # outcome field: overwritten by the tick
+                    t0 = time.perf_counter()
+                    e.tick_dev(frames_dev[i % n_distinct], W, H, base_poses[i % n_distinct], False, mode, i)
+                    e.tick_wait()                                             # the result record is in host memory now (reloc_tick_wait)
+                    ts_.append(time.perf_counter() - t0)
+                    assert results[0, 72] != 255, "tick result record did not arrive"
+                e.set_exclusive(False)
+                ts_ = np.array(ts_[20:]) * 1e6
+                lat[name + "_us"] = dict(median=float(np.median(ts_)), p95=float(np.percentile(ts_, 95)))
+            alg_bytes = NB * (32 * T + 32 * Q + 4 * L)        # per frame: database once, queries once, one count per record; NB frames per launch
+            scan_s = scan_ms / max(scan_n, 1) * 1e-3
+            pairs = NB * T * Q
+            # VALU ceilings measured on MI355X (tools/ubench_valu2.hip, profiles/r2_ubench_valu2.log): the bare distance,
+            # 8 x (v_xor_b32 s,v ; accumulating v_bcnt_u32_b32), reaches 2.99 T pairs/s at 8 waves/SIMD (2.91 T at the
+            # kernel's 4); with the kernel's argmin bookkeeping in the stream (shl16 + or + 3 min16 per pair) 2.21 T at 4
+            valu_peak_pairs = 2.99e12
+            roofline = dict(kernel="k_db_scan" if NB == 1 else "k_db_scan_batch", frames_per_launch=NB, bound="hbm", achieved=alg_bytes / scan_s / 1e9, peak=8000.0, unit="GB/s",
+                            frac=alg_bytes / scan_s / 1e9 / 8000.0, traffic=(pmc_traffic("k_db_scan") or 0) * NB or None,
+                            avg_launch_us=scan_s * 1e6, launches=scan_n, algorithmic_bytes=alg_bytes,
+                            note="VALU-bound by construction: 250 int-op/B at Q=500 (SURVEY.md 8d); HBM fraction cannot exceed ~2 %",
+                            valu=dict(pairs_per_s=pairs / scan_s, peak_pairs_per_s=valu_peak_pairs,
+                                      frac=pairs / scan_s / valu_peak_pairs,
+                                      lane_ops_per_s=16.0 * pairs / scan_s, spec_lane_ops_per_s=78.6e12,
+                                      frac_of_spec_issue=16.0 * pairs / scan_s / 78.6e12,
+                                      basis="measured chip ceiling of the bare 256-bit distance, 8 v_xor_b32 (full rate) + 8 accumulating "
+                                            "v_bcnt_u32_b32 (half rate) per pair (tools/ubench_valu2.hip); spec issue = 256 CU x 4 SIMD-32 x "
+                                            "2.4 GHz counts every instruction at full rate"))
+            stage_us = dict(orb=orb_ms / max(orb_n, 1) * 1e3, db_scan_per_frame=scan_s * 1e6 / NB, pnp=pnp_ms / max(pnp_n, 1) * 1e3)
+            if in_config:
+                ic_s = in_config["scan_avg_launch_us"] * 1e-6
+                roofline["in_config"] = dict(in_config, achieved=alg_bytes / ic_s / 1e9, frac=alg_bytes / ic_s / 1e9 / 8000.0,
+                                             pairs_per_s_per_scan=pairs / ic_s,
+                                             scans_resident=in_config["frames_per_s_with_events"] / NB * ic_s,
+                                             aggregate_pairs_per_s=total_frames / elapsed * T * Q,
+                                             aggregate_valu_frac=total_frames / elapsed * T * Q / valu_peak_pairs)
+                roofline["note_single_stream"] = ("avg_launch_us / stage_us: one idle stream after the timed region (unloaded kernel times); "
+                                                  "in_config: the same launches while the timed configuration runs")
+            # ---- 2 Hz cadence: a tick every 0.5 s, as the reference's timer fires (M:76), each on an idle chip
+            if not args.no_2hz:
+                for mode, name in ((1, "tick_global"), (0, "tick_local")):
+                    lat[name + "_2hz_us"], lat[name + "_2hz_not_exclusive_us"] = tick_latency_2hz(
+                        e, frames_dev, base_poses, results[0], args.ticks_2hz, 0.5, mode)
+                lat["note_2hz"] = ("exclusive and non-exclusive ticks interleaved in one loop, alternating order, same sample size; a local tick "
+                                   "launches the same kernel shapes in both forms (reloc_tick.hip: latency shapes for LOCAL ticks)")
+            # ---- the scan on the record sizes of real teach databases, and the few-query shape that IS HBM-bound
+            if not args.no_extra_scans:
+                ex = Engine(local_rank, W, H, 2048)
+                rag = scan_case(ex, args.records, "ragged", (500,), SEED + 10)
+                r45 = scan_case(ex, args.records, 45, (500,), SEED + 11)
+                pick = lambda rows, form: next(r for r in rows if r["scheduling"] == form)
+                roofline_ragged = dict(pick(rag, "shared"), workload=f"--rows ragged: {args.records} records of clip(round(N(60,25)),30,500) rows, Q = 500",
+                                       alone=pick(rag, "alone"), rows45=dict(shared=pick(r45, "shared"), alone=pick(r45, "alone")),
+                                       note="teach databases of the reference are ragged, ~45-100 rows per record (routes/01_road/teach/README.md:57,75); "
+                                            "VALU-bound like the headline kernel: compare valu.pairs_per_s")
+                sq = scan_case(ex, 100000, "fixed64", (1, 8, 32), SEED + 12)
+                for r_ in sq:
+                    r_["traffic"] = pmc_traffic({1: "k_db_scan_rows_q1", 8: "k_db_scan_rows_q8", 32: "k_db_scan_rows_q32"}.get(r_["Q"], "-"))
+                roofline_small_q = dict(sq[0], workload="100000 records x 64 rows (205 MB), Q = 1: the variant-G scan shape with few current descriptors "
+                                                        "(G:329-344), the HBM-bound match shape", by_Q={str(r["Q"]): r for r in sq})
+                ex.close()
+            if not args.no_matrix:
+                F = K = 20000
+                rng = np.random.default_rng(SEED + 4)
+                a = e.to_device(rng.integers(0, 256, (F, 32), dtype=np.uint8))
+                b = e.to_device(rng.integers(0, 256, (K, 32), dtype=np.uint8))
+                out = e.dev_alloc(F * K * 2)
+                for _ in range(MATRIX_PREROLL):                               # clock governor settles after ~40 ms of load, see bench_matrix
+                    e.hamming_matrix_dev(a, F, b, K, out)
+                e.sync()
+                e.profile_enable(True)
+                for _ in range(100):
+                    e.hamming_matrix_dev(a, F, b, K, out)
+                e.sync()
+                m_ms, m_n = e.profile_get(1)
+                e.profile_enable(False)
+                mb = 32 * (F + K) + 2 * F * K
+                ms = m_ms / max(m_n, 1) * 1e-3
+                roofline_matrix = dict(kernel="k_hamming_matrix", shape=[F, K], bound="hbm", achieved=mb / ms / 1e9, peak=8000.0,
+                                       unit="GB/s", frac=mb / ms / 1e9 / 8000.0, traffic=pmc_traffic("k_hamming_matrix"), avg_launch_us=ms * 1e6,
+                                       launches=m_n, algorithmic_bytes=mb,
+                                       valu=dict(pairs_per_s=F * K / ms, peak_pairs_per_s=2.99e12, frac=F * K / ms / 2.99e12))
+                for p in (a, b, out):
+                    e.dev_free(p)
+            if not args.no_cpu_baseline and world == 1:
+                cpu = cpu_baseline(frames, db)
+                cpu["opencv"] = opencv_baseline(frames, db)       # None unless OpenCV is importable on this host
         result = {
             "metric": "relocalization frames/sec @640x480, 10k-landmark DB; Hamming-match HBM GB/s",
             "value": total_frames / elapsed, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -832,7 +841,7 @@ def main(argv=None):
             "host_ingest": ingest, "latency": lat,
             "roofline": roofline, "roofline_ragged": roofline_ragged, "roofline_small_q": roofline_small_q,
             "roofline_matrix": roofline_matrix, "cpu_baseline": cpu,
-            "stage_us": stage_us, "hamming_match_GBps": roofline["achieved"], **outcomes,
+            "stage_us": stage_us, "hamming_match_GBps": None if roofline is None else roofline["achieved"], **outcomes,
         }
     for e in engines:
         e.close()

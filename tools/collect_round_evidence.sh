@@ -5,7 +5,7 @@ set -e
 R=${1:-r4}; PART=${2:-all}
 cd $GRAFT_REPO_ROOT && export TMPDIR=/tmp
 O=gpurun_out/$R; mkdir -p $O
-NOX="--no-cpu-baseline --no-ingest --no-2hz --no-extra-scans"
+NOX="--full --no-cpu-baseline --no-ingest --no-2hz --no-extra-scans"
 if [ $PART = all ] || [ $PART = core ]; then
 timeout -k 10 600 python -m pytest tests -x -q -m gpu > $O/gputest.log 2>&1 || true
 tail -2 $O/gputest.log
@@ -17,7 +17,7 @@ timeout -k 10 200 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_SME
 python tools/pmc_summarize.py $P $P/summary.json > /dev/null || true
 mkdir -p profiles/pmc_$R && cp $P/summary.json profiles/pmc_$R/summary.json      # bench.py reads the round's own traffic figures
 echo pmc done
-timeout -k 10 600 python bench.py 2>$O/bench.err | tail -1 > $O/bench.json
+timeout -k 10 600 python bench.py --full 2>$O/bench.err | tail -1 > $O/bench.json
 echo bench done
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python3 bench.py --steps 10 --warmup 2 $NOX > $O/stats.log 2>&1
 # one stream: the scan in the scheduling form of the 4-stream line's `roofline` (one resident generation since round 4, in every

@@ -1,6 +1,6 @@
 # Developer harness: the frame benchmark (4 streams) and the synchronous tick latency for several builds of the library
 # (RELOC_LIB), interleaved on one box.   bash tools/exp_lib_bench.sh lib1.so lib2.so ...
-F="--no-cpu-baseline --no-matrix --no-ingest --no-2hz --no-extra-scans"
+F="--full --no-cpu-baseline --no-matrix --no-ingest --no-2hz --no-extra-scans"
 for rep in 1 2; do
   for lib in "$@"; do
     echo -n "$(basename $lib): "

@@ -1,6 +1,6 @@
 # Developer harness: the frame benchmark with the scan's workgroup budgets in ROWS (+ sweepers: 1 = one per CU, 2 = one per
 # XCD) against the record quota of rounds 2-3a (RELOC_SCAN_QUOTA_ROWS=0), interleaved on one box.
-F="--no-cpu-baseline --no-matrix --no-ingest --no-2hz --no-extra-scans"
+F="--full --no-cpu-baseline --no-matrix --no-ingest --no-2hz --no-extra-scans"
 for a in "" "--rows ragged"; do
   for rep in 1 2; do
     for m in ${1:-0 1 2}; do
