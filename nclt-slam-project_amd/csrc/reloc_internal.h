@@ -226,11 +226,17 @@ __device__ __forceinline__ void cur_heading_q(const double q[4], double &cc, dou
     sc = n > 0 ? Rb[3] / n : 0.0;
 }
 
-// Lens distortion k1 k2 p1 p2 k3 (include/reloc_spec.h): passed by value to the DIST instantiations only, so the pinhole
-// kernels keep their signature and code.  Operation order as cv::projectPoints / cv::undistortPoints (no FMA: the library
-// builds with -ffp-contract=off), so tests/distortion_ref.py restates it bit for bit.
+// Lens distortion k1 k2 p1 p2 k3 (include/reloc_spec.h): passed by value to both instantiations of a DIST-templated
+// kernel; the pinhole one (DIST = false) never reads it, so its code is that of a kernel without the argument.  Operation
+// order as cv::projectPoints / cv::undistortPoints (no FMA: the library builds with -ffp-contract=off), so
+// tests/distortion_ref.py restates it bit for bit.
 struct DistCoef { double k1, k2, p1, p2, k3; };
 struct CamK4 { double v[4]; };         // fx fy cx cy by value
+// host side: d = k1 k2 p1 p2 k3, or NULL for all zeros
+static inline DistCoef make_dist(const double *d)
+{
+    return d ? DistCoef{d[0], d[1], d[2], d[3], d[4]} : DistCoef{};
+}
 // host side: n coefficients all finite (x - x is NaN for an infinity or a NaN)
 static inline bool dist_finite(const double *d, int n = 5)
 {

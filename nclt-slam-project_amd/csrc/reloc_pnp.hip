@@ -15,8 +15,9 @@
 //   k_pnp_finish  one wave per candidate: sequential adaptive-cap scan over the counts (lane 0),
 //                 inlier list by ballot compaction, LM refinement with the 6x6 normal equations
 //                 summed across the wave in fp64, Rodrigues log, mean inlier error.
-// Each body is a template on DIST (lens distortion, include/reloc_spec.h).  The pinhole kernels (DIST = false) keep their
-// signature and code; the k_pnp_*_dist kernels take the coefficients as one extra DistCoef argument.  With distortion
+// Each kernel is a template on DIST (lens distortion, include/reloc_spec.h) and takes the coefficients as one DistCoef
+// argument, which the pinhole instantiations (DIST = false) never read: their code is that of the kernels before
+// distortion existed.  With distortion
 // P3P gets undistorted normalized points, the fourth point picks the root by the ideal pixel K undistort(img), and the
 // scoring, the inlier list, the refinement and the mean error measure in distorted pixels (as OpenCV's PnPRansacCallback
 // and SOLVEPNP_ITERATIVE refinement do).
@@ -417,36 +418,23 @@ __device__ __forceinline__ void pnp_hyp_body(const float *__restrict__ obj, cons
     }
     PNP_T(7);
 }
+template <bool DIST>
 __global__ __launch_bounds__(HYP_BLOCK) void k_pnp_hyp(const float *__restrict__ obj, const float *__restrict__ img,
                                                 const int32_t *__restrict__ m_arr, const int32_t *__restrict__ n_cand_p,
                                                 PnpParams prm, double *__restrict__ Rt_out, int32_t *__restrict__ cnt,
-                                                const int32_t *__restrict__ relocating_p)
+                                                const int32_t *__restrict__ relocating_p, DistCoef dc)
 {
     RELOC_SMALL_KERNEL_PRIO();
-    pnp_hyp_body<false>(obj, img, m_arr, n_cand_p, prm, Rt_out, cnt, relocating_p, DistCoef{});
-}
-__global__ __launch_bounds__(HYP_BLOCK) void k_pnp_hyp_dist(const float *__restrict__ obj, const float *__restrict__ img,
-                                                     const int32_t *__restrict__ m_arr, const int32_t *__restrict__ n_cand_p,
-                                                     PnpParams prm, double *__restrict__ Rt_out, int32_t *__restrict__ cnt,
-                                                     const int32_t *__restrict__ relocating_p, DistCoef dc)
-{
-    RELOC_SMALL_KERNEL_PRIO();
-    pnp_hyp_body<true>(obj, img, m_arr, n_cand_p, prm, Rt_out, cnt, relocating_p, dc);
+    pnp_hyp_body<DIST>(obj, img, m_arr, n_cand_p, prm, Rt_out, cnt, relocating_p, dc);
 }
 // grid (ceil(iters/64), n_cand_max, frames)
-__global__ __launch_bounds__(HYP_BLOCK) void k_pnp_hyp_batch(PnpBatch b, PnpParams prm)
+template <bool DIST>
+__global__ __launch_bounds__(HYP_BLOCK) void k_pnp_hyp_batch(PnpBatch b, PnpParams prm, DistCoef dc)
 {
     RELOC_SMALL_KERNEL_PRIO();
     const PnpFrame &F = b.f[blockIdx.z];
     prm.seed = F.seed;
-    pnp_hyp_body<false>(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, F.relocating, DistCoef{});
-}
-__global__ __launch_bounds__(HYP_BLOCK) void k_pnp_hyp_batch_dist(PnpBatch b, PnpParams prm, DistCoef dc)
-{
-    RELOC_SMALL_KERNEL_PRIO();
-    const PnpFrame &F = b.f[blockIdx.z];
-    prm.seed = F.seed;
-    pnp_hyp_body<true>(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, F.relocating, dc);
+    pnp_hyp_body<DIST>(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, F.relocating, dc);
 }
 
 
@@ -483,35 +471,23 @@ __device__ __forceinline__ void pnp_score_body(const float *__restrict__ obj, co
     }
     if (threadIdx.x == 0) *cn = count;
 }
+template <bool DIST>
 __global__ __launch_bounds__(64) void k_pnp_score(const float *__restrict__ obj, const float *__restrict__ img,
                                                   const int32_t *__restrict__ m_arr, const int32_t *__restrict__ n_cand_p,
                                                   PnpParams prm, const double *__restrict__ Rt_in,
-                                                  int32_t *__restrict__ cnt, uint8_t *__restrict__ mask, int hyp_stride)
+                                                  int32_t *__restrict__ cnt, uint8_t *__restrict__ mask, int hyp_stride,
+                                                  DistCoef dc)
 {
     RELOC_SMALL_KERNEL_PRIO();
-    pnp_score_body<false>(obj, img, m_arr, n_cand_p, prm, Rt_in, cnt, mask, hyp_stride, DistCoef{});
-}
-__global__ __launch_bounds__(64) void k_pnp_score_dist(const float *__restrict__ obj, const float *__restrict__ img,
-                                                       const int32_t *__restrict__ m_arr, const int32_t *__restrict__ n_cand_p,
-                                                       PnpParams prm, const double *__restrict__ Rt_in,
-                                                       int32_t *__restrict__ cnt, uint8_t *__restrict__ mask, int hyp_stride,
-                                                       DistCoef dc)
-{
-    RELOC_SMALL_KERNEL_PRIO();
-    pnp_score_body<true>(obj, img, m_arr, n_cand_p, prm, Rt_in, cnt, mask, hyp_stride, dc);
+    pnp_score_body<DIST>(obj, img, m_arr, n_cand_p, prm, Rt_in, cnt, mask, hyp_stride, dc);
 }
 // grid (iters, n_cand_max, frames)
-__global__ __launch_bounds__(64) void k_pnp_score_batch(PnpBatch b, PnpParams prm, int hyp_stride)
+template <bool DIST>
+__global__ __launch_bounds__(64) void k_pnp_score_batch(PnpBatch b, PnpParams prm, int hyp_stride, DistCoef dc)
 {
     RELOC_SMALL_KERNEL_PRIO();
     const PnpFrame &F = b.f[blockIdx.z];
-    pnp_score_body<false>(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, nullptr, hyp_stride, DistCoef{});
-}
-__global__ __launch_bounds__(64) void k_pnp_score_batch_dist(PnpBatch b, PnpParams prm, int hyp_stride, DistCoef dc)
-{
-    RELOC_SMALL_KERNEL_PRIO();
-    const PnpFrame &F = b.f[blockIdx.z];
-    pnp_score_body<true>(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, nullptr, hyp_stride, dc);
+    pnp_score_body<DIST>(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, nullptr, hyp_stride, dc);
 }
 
 
@@ -916,43 +892,28 @@ __device__ __forceinline__ void pnp_finish_body(const float *__restrict__ obj, c
     PNP_T(13);
     PNP_V(14, n);
 }
-template <int WAVES>
+template <bool DIST, int WAVES>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) void k_pnp_finish(const float *__restrict__ obj, const float *__restrict__ img,
                                                    const int32_t *__restrict__ m_arr, const int32_t *__restrict__ n_cand_p,
                                                    PnpParams prm, const double *__restrict__ Rt_all,
                                                    const int32_t *__restrict__ cnt, int32_t *__restrict__ inl_out,
-                                                   PnpOut *__restrict__ out, const int32_t *__restrict__ relocating_p)
+                                                   PnpOut *__restrict__ out, const int32_t *__restrict__ relocating_p,
+                                                   DistCoef dc)
 {
     RELOC_SMALL_KERNEL_PRIO();
-    pnp_finish_body<false>(obj, img, m_arr, n_cand_p, prm, Rt_all, cnt, inl_out, out, relocating_p, DistCoef{});
+    pnp_finish_body<DIST>(obj, img, m_arr, n_cand_p, prm, Rt_all, cnt, inl_out, out, relocating_p, dc);
 }
 // grid (n_cand_max, frames)
-template <int WAVES>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) void k_pnp_finish_batch(PnpBatch b, PnpParams prm)
+template <bool DIST, int WAVES>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) void k_pnp_finish_batch(PnpBatch b, PnpParams prm, DistCoef dc)
 {
     RELOC_SMALL_KERNEL_PRIO();
     const PnpFrame &F = b.f[blockIdx.y];
     prm.seed = F.seed;
-    pnp_finish_body<false>(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, F.inl, F.out, F.relocating, DistCoef{});
+    pnp_finish_body<DIST>(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, F.inl, F.out, F.relocating, dc);
 }
 // DIST: one instantiation for every shape, budget PNP_DIST_WAVES (see pnp_run_candidates)
 constexpr int PNP_DIST_WAVES = 2;
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PNP_DIST_WAVES, 8))) void k_pnp_finish_dist(
-    const float *__restrict__ obj, const float *__restrict__ img, const int32_t *__restrict__ m_arr,
-    const int32_t *__restrict__ n_cand_p, PnpParams prm, const double *__restrict__ Rt_all, const int32_t *__restrict__ cnt,
-    int32_t *__restrict__ inl_out, PnpOut *__restrict__ out, const int32_t *__restrict__ relocating_p, DistCoef dc)
-{
-    RELOC_SMALL_KERNEL_PRIO();
-    pnp_finish_body<true>(obj, img, m_arr, n_cand_p, prm, Rt_all, cnt, inl_out, out, relocating_p, dc);
-}
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PNP_DIST_WAVES, 8))) void k_pnp_finish_batch_dist(
-    PnpBatch b, PnpParams prm, DistCoef dc)
-{
-    RELOC_SMALL_KERNEL_PRIO();
-    const PnpFrame &F = b.f[blockIdx.y];
-    prm.seed = F.seed;
-    pnp_finish_body<true>(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, F.inl, F.out, F.relocating, dc);
-}
 
 
 static PnpParams make_params(const double K4[4], int iters, float thr_px, double conf, uint64_t seed, int stride,
@@ -970,7 +931,6 @@ static PnpParams make_params(const double K4[4], int iters, float thr_px, double
     return p;
 }
 
-static DistCoef make_dist(const double *d) { return DistCoef{d[0], d[1], d[2], d[3], d[4]}; }
 static bool dist_nonzero(const double *d)
 {
     if (!d) return false;
@@ -991,30 +951,18 @@ int pnp_run_candidates(reloc_ctx *ctx, int n_cand_max, const int32_t *n_cand_dev
     }
     PnpParams prm = make_params(K4, iters, thr_px, conf, seed, MAX_REC_ROWS, min_m);
     prm.gate_local = gate_local; prm.gate_global = gate_global;
-    if (dist) {
-        const DistCoef dc = make_dist(dist);
-        reloc_prof_begin(ctx, RELOC_PROF_PNP);
-        hipLaunchKernelGGL(k_pnp_hyp_dist, dim3((iters + 63) / 64, n_cand_max), dim3(HYP_BLOCK), 0, ctx->stream, ctx->p_obj,
-                           ctx->p_img, ctx->m_n, n_cand_dev, prm, ctx->p_Rt, ctx->p_cnt, relocating_dev, dc);
-        hipLaunchKernelGGL(k_pnp_score_dist, dim3(iters, n_cand_max), dim3(64), 0, ctx->stream, ctx->p_obj, ctx->p_img, ctx->m_n,
-                           n_cand_dev, prm, ctx->p_Rt, ctx->p_cnt, (uint8_t *)nullptr, MAX_HYP, dc);
-        hipLaunchKernelGGL(k_pnp_finish_dist, dim3(n_cand_max), dim3(64), 0, ctx->stream, ctx->p_obj, ctx->p_img, ctx->m_n,
-                           n_cand_dev, prm, ctx->p_Rt, ctx->p_cnt, ctx->p_inl, ctx->p_out, relocating_dev, dc);
-        reloc_prof_end(ctx, RELOC_PROF_PNP);
-        HIP_TRY(hipGetLastError());
-        return RELOC_OK;
-    }
+    auto hyp = dist ? k_pnp_hyp<true> : k_pnp_hyp<false>;
+    auto score = dist ? k_pnp_score<true> : k_pnp_score<false>;
+    auto finish = dist ? k_pnp_finish<true, PNP_DIST_WAVES>
+                       : ctx->latency_shapes ? k_pnp_finish<false, 1> : k_pnp_finish<false, 4>;
+    const DistCoef dc = make_dist(dist);
     reloc_prof_begin(ctx, RELOC_PROF_PNP);
-    hipLaunchKernelGGL(k_pnp_hyp, dim3((iters + 63) / 64, n_cand_max), dim3(HYP_BLOCK), 0, ctx->stream, ctx->p_obj, ctx->p_img,
-                       ctx->m_n, n_cand_dev, prm, ctx->p_Rt, ctx->p_cnt, relocating_dev);
-    hipLaunchKernelGGL(k_pnp_score, dim3(iters, n_cand_max), dim3(64), 0, ctx->stream, ctx->p_obj, ctx->p_img, ctx->m_n,
-                       n_cand_dev, prm, ctx->p_Rt, ctx->p_cnt, (uint8_t *)nullptr, MAX_HYP);
-    if (ctx->latency_shapes)
-        hipLaunchKernelGGL(k_pnp_finish<1>, dim3(n_cand_max), dim3(64), 0, ctx->stream, ctx->p_obj, ctx->p_img, ctx->m_n,
-                           n_cand_dev, prm, ctx->p_Rt, ctx->p_cnt, ctx->p_inl, ctx->p_out, relocating_dev);
-    else
-        hipLaunchKernelGGL(k_pnp_finish<4>, dim3(n_cand_max), dim3(64), 0, ctx->stream, ctx->p_obj, ctx->p_img, ctx->m_n,
-                           n_cand_dev, prm, ctx->p_Rt, ctx->p_cnt, ctx->p_inl, ctx->p_out, relocating_dev);
+    hipLaunchKernelGGL(hyp, dim3((iters + 63) / 64, n_cand_max), dim3(HYP_BLOCK), 0, ctx->stream, ctx->p_obj, ctx->p_img,
+                       ctx->m_n, n_cand_dev, prm, ctx->p_Rt, ctx->p_cnt, relocating_dev, dc);
+    hipLaunchKernelGGL(score, dim3(iters, n_cand_max), dim3(64), 0, ctx->stream, ctx->p_obj, ctx->p_img, ctx->m_n,
+                       n_cand_dev, prm, ctx->p_Rt, ctx->p_cnt, (uint8_t *)nullptr, MAX_HYP, dc);
+    hipLaunchKernelGGL(finish, dim3(n_cand_max), dim3(64), 0, ctx->stream, ctx->p_obj, ctx->p_img, ctx->m_n,
+                       n_cand_dev, prm, ctx->p_Rt, ctx->p_cnt, ctx->p_inl, ctx->p_out, relocating_dev, dc);
     reloc_prof_end(ctx, RELOC_PROF_PNP);
     HIP_TRY(hipGetLastError());
     return RELOC_OK;
@@ -1039,20 +987,16 @@ int pnp_run_candidates_batch(reloc_ctx *const *ctxs, int n, int n_cand_max, cons
         F.obj = c->p_obj; F.img = c->p_img; F.m_arr = c->m_n; F.n_cand_p = c->cand_n; F.Rt = c->p_Rt; F.cnt = c->p_cnt; F.inl = c->p_inl;
         F.out = c->p_out; F.seed = seeds ? seeds[f < n ? f : 0] : 0; F.relocating = c->tick_flags;
     }
-    if (c0->has_dist) {            // the contexts of a batch carry equal coefficients (checked by the callers)
-        const DistCoef dc = make_dist(c0->dist);
-        reloc_prof_begin(c0, RELOC_PROF_PNP);
-        hipLaunchKernelGGL(k_pnp_hyp_batch_dist, dim3((iters + 63) / 64, n_cand_max, n), dim3(HYP_BLOCK), 0, c0->stream, b, prm, dc);
-        hipLaunchKernelGGL(k_pnp_score_batch_dist, dim3(iters, n_cand_max, n), dim3(64), 0, c0->stream, b, prm, MAX_HYP, dc);
-        hipLaunchKernelGGL(k_pnp_finish_batch_dist, dim3(n_cand_max, n), dim3(64), 0, c0->stream, b, prm, dc);
-        reloc_prof_end(c0, RELOC_PROF_PNP);
-        HIP_TRY(hipGetLastError());
-        return RELOC_OK;
-    }
+    // the contexts of a batch carry equal coefficients (checked by the callers)
+    const bool dist = c0->has_dist;
+    auto hyp = dist ? k_pnp_hyp_batch<true> : k_pnp_hyp_batch<false>;
+    auto score = dist ? k_pnp_score_batch<true> : k_pnp_score_batch<false>;
+    auto finish = dist ? k_pnp_finish_batch<true, PNP_DIST_WAVES> : k_pnp_finish_batch<false, 4>;
+    const DistCoef dc = make_dist(c0->dist);
     reloc_prof_begin(c0, RELOC_PROF_PNP);
-    hipLaunchKernelGGL(k_pnp_hyp_batch, dim3((iters + 63) / 64, n_cand_max, n), dim3(HYP_BLOCK), 0, c0->stream, b, prm);
-    hipLaunchKernelGGL(k_pnp_score_batch, dim3(iters, n_cand_max, n), dim3(64), 0, c0->stream, b, prm, MAX_HYP);
-    hipLaunchKernelGGL(k_pnp_finish_batch<4>, dim3(n_cand_max, n), dim3(64), 0, c0->stream, b, prm);
+    hipLaunchKernelGGL(hyp, dim3((iters + 63) / 64, n_cand_max, n), dim3(HYP_BLOCK), 0, c0->stream, b, prm, dc);
+    hipLaunchKernelGGL(score, dim3(iters, n_cand_max, n), dim3(64), 0, c0->stream, b, prm, MAX_HYP, dc);
+    hipLaunchKernelGGL(finish, dim3(n_cand_max, n), dim3(64), 0, c0->stream, b, prm, dc);
     reloc_prof_end(c0, RELOC_PROF_PNP);
     HIP_TRY(hipGetLastError());
     return RELOC_OK;
@@ -1081,14 +1025,10 @@ static int pnp_score_impl(reloc_ctx *ctx, const float *obj, const float *img, in
     HIP_TRY(hipMemsetAsync(dcnt, 0, (size_t)H * 4, ctx->stream));
     HIP_TRY(hipMemcpyAsync(dm, &m, 4, hipMemcpyHostToDevice, ctx->stream));
     const PnpParams prm = make_params(K4, H, thr_px, 0.99, 0, m, 0);
-    if (dist)
-        hipLaunchKernelGGL(k_pnp_score_dist, dim3(H, 1), dim3(64), 0, ctx->stream, (const float *)dobj, (const float *)dimg,
-                           (const int32_t *)dm, (const int32_t *)nullptr, prm, (const double *)drt, (int32_t *)dcnt,
-                           (uint8_t *)dmask, H, make_dist(dist));
-    else
-        hipLaunchKernelGGL(k_pnp_score, dim3(H, 1), dim3(64), 0, ctx->stream, (const float *)dobj, (const float *)dimg,
-                           (const int32_t *)dm, (const int32_t *)nullptr, prm, (const double *)drt, (int32_t *)dcnt,
-                           (uint8_t *)dmask, H);
+    auto score = dist ? k_pnp_score<true> : k_pnp_score<false>;
+    hipLaunchKernelGGL(score, dim3(H, 1), dim3(64), 0, ctx->stream, (const float *)dobj, (const float *)dimg,
+                       (const int32_t *)dm, (const int32_t *)nullptr, prm, (const double *)drt, (int32_t *)dcnt,
+                       (uint8_t *)dmask, H, make_dist(dist));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(inlier_count, dcnt, (size_t)H * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (mask) HIP_TRY(hipMemcpyAsync(mask, dmask, (size_t)H * m, hipMemcpyDeviceToHost, ctx->stream));
@@ -1190,10 +1130,9 @@ RELOC_API int reloc_undistort_points(reloc_ctx *ctx, const float *img, int m, co
     HIP_TRY(hipMemcpyAsync(dimg, img, (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream));
     CamK4 k;
     for (int c = 0; c < 4; ++c) k.v[c] = K4[c];
-    const double zero[5] = {0, 0, 0, 0, 0};
     const int blocks = (int)((m + 255) / 256 < 1024 ? (m + 255) / 256 : 1024);
     hipLaunchKernelGGL(k_undistort_points, dim3(blocks), dim3(256), 0, ctx->stream, (const float *)dimg, m, k,
-                       make_dist(dist ? dist : zero), (double *)dout);
+                       make_dist(dist), (double *)dout);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out_norm, dout, (size_t)m * 16, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -12,11 +12,11 @@
 //   (uu - CX) * d_c / FX         -> int32 - python float = float64, * float32 = float64, / float64,
 //                                   stacked with float32 z and cast to float32
 // One lane per keypoint; survivors are compacted in keypoint order by a block-wide scan.
-// Lens distortion (include/reloc_spec.h): k_record_dist / k_accumulate_dist back-project through the inverse model,
+// Lens distortion (include/reloc_spec.h): k_record<true> / k_accumulate<true> back-project through the inverse model,
 //   (x_u, y_u) = undistort(u, v); X = x_u * z, Y = y_u * z in float64, cast to float32,
-// with the same pixel-based gates (the kept rows do not change).  They are copies of k_record / k_accumulate that differ in
-// the back-projection only: sharing one templated body changed the pinhole kernels' code (the compiler schedules the
-// inlined body differently), and the pinhole kernels are held to their listing.
+// with the same pixel-based gates (the kept rows do not change).  DIST is a template parameter of the __global__ kernels
+// themselves, not of a shared __device__ body: moving the body into a __forceinline__ function called from two kernels
+// changed the pinhole kernels' code, while templating the kernel keeps every instruction of <false> as it was.
 #include "reloc_internal.h"
 
 // camera-frame point of the rounded pixel (u, v) at depth dz through the inverse distortion model
@@ -52,76 +52,8 @@ __device__ float np_sum9(const float *a, int n)
     return r;
 }
 
-// k_record_dist below is a copy of this kernel with the back-projection through the distortion model: a change to the gates
-// here must be made there too.
+template <bool DIST>
 __global__ __launch_bounds__(1024) void k_record(const float *__restrict__ f_xy, const uint8_t *__restrict__ f_desc,
-                                                 const int32_t *__restrict__ f_count, int max_feat,
-                                                 const uint16_t *__restrict__ depth, int dstride, RecordParams p,
-                                                 float *__restrict__ o_xy, uint8_t *__restrict__ o_desc,
-                                                 float *__restrict__ o_pts, int32_t *__restrict__ o_idx,
-                                                 int32_t *__restrict__ o_n)
-{
-    RELOC_SMALL_KERNEL_PRIO();
-    __shared__ int s_wsum[16];
-    __shared__ int s_base;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = min(*f_count, max_feat);
-    if (tid == 0) s_base = 0;
-    __syncthreads();
-    for (int i0 = 0; i0 < n; i0 += 1024) {
-        const int i = i0 + tid;
-        bool keep = false;
-        float x = 0, y = 0, dz = 0;
-        int u = 0, v = 0;
-        if (i < n) {
-            x = f_xy[2 * i]; y = f_xy[2 * i + 1];
-            u = (int)rintf(x); v = (int)rintf(y);
-            if (u >= 1 && u < p.w - 1 && v >= 1 && v < p.h - 1 && v > p.ground_y) {
-                dz = __fdiv_rn((float)depth[(size_t)v * dstride + u], 1000.0f);
-                float vals[9];
-                int cnt = 0;
-                for (int dy = -1; dy <= 1; ++dy)
-                    for (int dx = -1; dx <= 1; ++dx) {
-                        const float m = __fdiv_rn((float)depth[(size_t)(v + dy) * dstride + (u + dx)], 1000.0f);
-                        if (m > 0.01f) vals[cnt++] = m;
-                    }
-                float sd = 999.0f;
-                if (cnt >= 3) {
-                    const float mean = __fdiv_rn(np_sum9(vals, cnt), (float)cnt);
-                    float sq[9];
-                    for (int k = 0; k < cnt; ++k) { const float d = __fsub_rn(vals[k], mean); sq[k] = __fmul_rn(d, d); }
-                    sd = __fsqrt_rn(__fdiv_rn(np_sum9(sq, cnt), (float)cnt));
-                }
-                keep = dz > p.depth_min && dz < p.depth_max && sd < p.var_max;
-            }
-        }
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) s_wsum[wave] = __popcll(bal);
-        __syncthreads();
-        int before = s_base;
-        for (int w = 0; w < wave; ++w) before += s_wsum[w];
-        int total = 0;
-        for (int w = 0; w < 16; ++w) total += s_wsum[w];
-        if (keep) {
-            const int pos = before + __popcll(bal & ((1ull << lane) - 1ull));
-            o_xy[2 * pos] = x; o_xy[2 * pos + 1] = y;
-            o_pts[3 * pos] = (float)__ddiv_rn(__dmul_rn(__dsub_rn((double)u, p.cx), (double)dz), p.fx);
-            o_pts[3 * pos + 1] = (float)__ddiv_rn(__dmul_rn(__dsub_rn((double)v, p.cy), (double)dz), p.fy);
-            o_pts[3 * pos + 2] = dz;
-            o_idx[pos] = i;
-            const uint4 *s = reinterpret_cast<const uint4 *>(f_desc + (size_t)i * 32);
-            uint4 *d = reinterpret_cast<uint4 *>(o_desc + (size_t)pos * 32);
-            d[0] = s[0]; d[1] = s[1];
-        }
-        __syncthreads();
-        if (tid == 0) s_base += total;
-        __syncthreads();
-    }
-    if (tid == 0) *o_n = s_base;
-}
-
-// k_record with the back-projection through the distortion model
-__global__ __launch_bounds__(1024) void k_record_dist(const float *__restrict__ f_xy, const uint8_t *__restrict__ f_desc,
                                                  const int32_t *__restrict__ f_count, int max_feat,
                                                  const uint16_t *__restrict__ depth, int dstride, RecordParams p,
                                                  float *__restrict__ o_xy, uint8_t *__restrict__ o_desc,
@@ -172,7 +104,13 @@ __global__ __launch_bounds__(1024) void k_record_dist(const float *__restrict__ 
         if (keep) {
             const int pos = before + __popcll(bal & ((1ull << lane) - 1ull));
             o_xy[2 * pos] = x; o_xy[2 * pos + 1] = y;
-            back_project_dist(p.fx, p.fy, p.cx, p.cy, dc, u, v, dz, o_pts + 3 * pos);
+            if constexpr (DIST) {
+                back_project_dist(p.fx, p.fy, p.cx, p.cy, dc, u, v, dz, o_pts + 3 * pos);
+            } else {
+                o_pts[3 * pos] = (float)__ddiv_rn(__dmul_rn(__dsub_rn((double)u, p.cx), (double)dz), p.fx);
+                o_pts[3 * pos + 1] = (float)__ddiv_rn(__dmul_rn(__dsub_rn((double)v, p.cy), (double)dz), p.fy);
+                o_pts[3 * pos + 2] = dz;
+            }
             o_idx[pos] = i;
             const uint4 *s = reinterpret_cast<const uint4 *>(f_desc + (size_t)i * 32);
             uint4 *d = reinterpret_cast<uint4 *>(o_desc + (size_t)pos * 32);
@@ -211,13 +149,9 @@ RELOC_API int reloc_record_frame(reloc_ctx *ctx, const uint8_t *img, const uint1
     p.fx = ctx->K4[0]; p.fy = ctx->K4[1]; p.cx = ctx->K4[2]; p.cy = ctx->K4[3];
     p.depth_min = RELOC_DEPTH_MIN_M; p.depth_max = RELOC_DEPTH_MAX_M; p.var_max = RELOC_DEPTH_VAR_MAX_M;
     p.ground_y = RELOC_GROUND_Y_THRESHOLD; p.w = w; p.h = h;
-    if (ctx->has_dist)
-        hipLaunchKernelGGL(k_record_dist, dim3(1), dim3(1024), 0, ctx->stream, ctx->f_xy, ctx->f_desc, ctx->f_count, ctx->max_feat,
-                           (const uint16_t *)ddepth, w, p, o_xy, o_desc, o_pts, o_idx, o_n,
-                           DistCoef{ctx->dist[0], ctx->dist[1], ctx->dist[2], ctx->dist[3], ctx->dist[4]});
-    else
-        hipLaunchKernelGGL(k_record, dim3(1), dim3(1024), 0, ctx->stream, ctx->f_xy, ctx->f_desc, ctx->f_count, ctx->max_feat,
-                           (const uint16_t *)ddepth, w, p, o_xy, o_desc, o_pts, o_idx, o_n);
+    auto kern = ctx->has_dist ? k_record<true> : k_record<false>;
+    hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, ctx->stream, ctx->f_xy, ctx->f_desc, ctx->f_count, ctx->max_feat,
+                       (const uint16_t *)ddepth, w, p, o_xy, o_desc, o_pts, o_idx, o_n, make_dist(ctx->dist));
     HIP_TRY(hipGetLastError());
     int32_t n = 0, nk = 0;
     HIP_TRY(hipMemcpyAsync(&n, o_n, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -278,119 +212,8 @@ __device__ void rot_to_quat_scipy(const double R[9], double q[4])
     for (int c = 0; c < 4; ++c) q[c] = q[c] / n;
 }
 
-// k_accumulate_dist below is a copy of this kernel with the back-projection through the distortion model: a change to the
-// gates here must be made there too.
+template <bool DIST>
 __global__ __launch_bounds__(1024) void k_accumulate(const float *__restrict__ f_xy, const uint8_t *__restrict__ f_desc,
-                                                     const int32_t *__restrict__ f_count, int max_feat,
-                                                     const uint16_t *__restrict__ depth, int dstride, AccumParams p,
-                                                     const TickResult *__restrict__ tick, double *__restrict__ xyh,
-                                                     uint8_t *__restrict__ db_desc, float *__restrict__ db_pts3d,
-                                                     float *__restrict__ db_kp2d, int64_t *__restrict__ db_off,
-                                                     double *__restrict__ db_pose, AccumResult *__restrict__ res)
-{
-    RELOC_SMALL_KERNEL_PRIO();
-    __shared__ int s_wsum[16];
-    __shared__ double s_wmin[16];
-    __shared__ int s_base;
-    __shared__ double s_near;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int oc = tick->outcome;
-    const bool wanted = p.silence_ok && (oc == RELOC_OUT_NO_CANDIDATES || oc == RELOC_OUT_NO_PNP_ACCEPT || oc == RELOC_OUT_CONSISTENCY_FAIL);
-    if (!wanted) {                                               // block-uniform
-        if (tid == 0) { res->appended = 0; res->n_kpts = 0; res->nearest_m = -1.0; }
-        return;
-    }
-    // nearest filed record (M:444-446)
-    double dmin = 1e300;
-    for (int64_t i = tid; i < p.L; i += 1024) {
-        const double dx = xyh[4 * i] - p.base_pose[0], dy = xyh[4 * i + 1] - p.base_pose[1];
-        dmin = fmin(dmin, sqrt(dx * dx + dy * dy));
-    }
-    for (int d = 32; d >= 1; d >>= 1) dmin = fmin(dmin, __shfl_xor(dmin, d));
-    if (lane == 0) s_wmin[wave] = dmin;
-    if (tid == 0) s_base = 0;
-    __syncthreads();
-    if (tid == 0) {
-        double m = s_wmin[0];
-        for (int w = 1; w < 16; ++w) m = fmin(m, s_wmin[w]);
-        s_near = m;
-    }
-    __syncthreads();
-    const double nearest = s_near;
-    if (nearest < p.min_dist) {
-        if (tid == 0) { res->appended = 0; res->n_kpts = 0; res->nearest_m = nearest; }
-        return;
-    }
-    const int n = min(*f_count, max_feat);
-    uint8_t *o_desc = db_desc + p.T * 32;
-    float *o_pts = db_pts3d + p.T * 3, *o_xy = db_kp2d + p.T * 2;
-    for (int i0 = 0; i0 < n; i0 += 1024) {
-        const int i = i0 + tid;
-        bool keep = false;
-        float x = 0, y = 0, dz = 0;
-        int u = 0, v = 0;
-        if (i < n) {
-            x = f_xy[2 * i]; y = f_xy[2 * i + 1];
-            u = (int)rintf(x); v = (int)rintf(y);
-            if (u >= 1 && u < p.w - 1 && v >= 1 && v < p.h - 1) {
-                dz = __fdiv_rn((float)depth[(size_t)v * dstride + u], 1000.0f);
-                keep = dz > p.zmin && dz < p.zmax;
-            }
-        }
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) s_wsum[wave] = __popcll(bal);
-        __syncthreads();
-        int before = s_base;
-        for (int w = 0; w < wave; ++w) before += s_wsum[w];
-        int total = 0;
-        for (int w = 0; w < 16; ++w) total += s_wsum[w];
-        if (keep) {
-            const int pos = before + __popcll(bal & ((1ull << lane) - 1ull));
-            o_xy[2 * pos] = x; o_xy[2 * pos + 1] = y;
-            o_pts[3 * pos] = (float)__ddiv_rn(__dmul_rn(__dsub_rn((double)u, p.cx), (double)dz), p.fx);
-            o_pts[3 * pos + 1] = (float)__ddiv_rn(__dmul_rn(__dsub_rn((double)v, p.cy), (double)dz), p.fy);
-            o_pts[3 * pos + 2] = dz;
-            const uint4 *sp = reinterpret_cast<const uint4 *>(f_desc + (size_t)i * 32);
-            uint4 *dp = reinterpret_cast<uint4 *>(o_desc + (size_t)pos * 32);
-            dp[0] = sp[0]; dp[1] = sp[1];
-        }
-        __syncthreads();
-        if (tid == 0) s_base += total;
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const int cnt = s_base;
-        res->n_kpts = cnt;
-        res->nearest_m = nearest;
-        if (cnt < p.min_kpts) { res->appended = 0; return; }
-        // camera pose from the base pose through the static mount (M:475-480)
-        double Rwb[9], Rwc[9], q[4];
-        quat_to_rot(p.base_pose[3], p.base_pose[4], p.base_pose[5], p.base_pose[6], Rwb);
-        double *pose = db_pose + 7 * p.L;
-        for (int r = 0; r < 3; ++r)
-            pose[r] = p.base_pose[r] + ((Rwb[3 * r] * p.b2c_t[0] + Rwb[3 * r + 1] * p.b2c_t[1]) + Rwb[3 * r + 2] * p.b2c_t[2]);
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c)
-                Rwc[3 * r + c] = (Rwb[3 * r] * p.b2c_R[c] + Rwb[3 * r + 1] * p.b2c_R[3 + c]) + Rwb[3 * r + 2] * p.b2c_R[6 + c];
-        rot_to_quat_scipy(Rwc, q);
-        for (int c = 0; c < 4; ++c) pose[3 + c] = q[c];
-        // filed under the VIO position (M:491); heading as for every record (M:233-245, k_db_index)
-        double Rq[9];
-        quat_to_rot(q[0], q[1], q[2], q[3], Rq);
-        const double fx = Rq[0] * p.b2c_R[0] + Rq[1] * p.b2c_R[1] + Rq[2] * p.b2c_R[2];
-        const double fy = Rq[3] * p.b2c_R[0] + Rq[4] * p.b2c_R[1] + Rq[5] * p.b2c_R[2];
-        const double fn = sqrt(fx * fx + fy * fy);
-        xyh[4 * p.L] = p.base_pose[0];
-        xyh[4 * p.L + 1] = p.base_pose[1];
-        xyh[4 * p.L + 2] = fn > 0 ? fx / fn : 1.0;
-        xyh[4 * p.L + 3] = fn > 0 ? fy / fn : 0.0;
-        db_off[p.L + 1] = p.T + cnt;
-        res->appended = 1;
-    }
-}
-
-// k_accumulate with the back-projection through the distortion model
-__global__ __launch_bounds__(1024) void k_accumulate_dist(const float *__restrict__ f_xy, const uint8_t *__restrict__ f_desc,
                                                      const int32_t *__restrict__ f_count, int max_feat,
                                                      const uint16_t *__restrict__ depth, int dstride, AccumParams p,
                                                      const TickResult *__restrict__ tick, double *__restrict__ xyh,
@@ -458,7 +281,13 @@ __global__ __launch_bounds__(1024) void k_accumulate_dist(const float *__restric
         if (keep) {
             const int pos = before + __popcll(bal & ((1ull << lane) - 1ull));
             o_xy[2 * pos] = x; o_xy[2 * pos + 1] = y;
-            back_project_dist(p.fx, p.fy, p.cx, p.cy, dc, u, v, dz, o_pts + 3 * pos);
+            if constexpr (DIST) {
+                back_project_dist(p.fx, p.fy, p.cx, p.cy, dc, u, v, dz, o_pts + 3 * pos);
+            } else {
+                o_pts[3 * pos] = (float)__ddiv_rn(__dmul_rn(__dsub_rn((double)u, p.cx), (double)dz), p.fx);
+                o_pts[3 * pos + 1] = (float)__ddiv_rn(__dmul_rn(__dsub_rn((double)v, p.cy), (double)dz), p.fy);
+                o_pts[3 * pos + 2] = dz;
+            }
             const uint4 *sp = reinterpret_cast<const uint4 *>(f_desc + (size_t)i * 32);
             uint4 *dp = reinterpret_cast<uint4 *>(o_desc + (size_t)pos * 32);
             dp[0] = sp[0]; dp[1] = sp[1];
@@ -519,15 +348,10 @@ RELOC_API int reloc_tick_accumulate_dev(reloc_ctx *ctx, const uint16_t *depth_mm
     p.zmin = (float)ctx->prm.accum_depth_min_m; p.zmax = (float)ctx->prm.accum_depth_max_m;
     p.w = w; p.h = h; p.min_kpts = ctx->prm.accum_min_kpts; p.silence_ok = silence_ok;
     p.L = ctx->db_records; p.T = ctx->db_rows;
-    if (ctx->has_dist)
-        hipLaunchKernelGGL(k_accumulate_dist, dim3(1), dim3(1024), 0, ctx->stream, ctx->f_xy, ctx->f_desc, ctx->f_count,
-                           ctx->max_feat, depth_mm_dev, w, p, ctx->tick_res, ctx->db_xy_heading, ctx->db_desc, ctx->db_pts3d,
-                           ctx->db_kp2d, ctx->db_off, ctx->db_pose, ctx->accum_res,
-                           DistCoef{ctx->dist[0], ctx->dist[1], ctx->dist[2], ctx->dist[3], ctx->dist[4]});
-    else
-        hipLaunchKernelGGL(k_accumulate, dim3(1), dim3(1024), 0, ctx->stream, ctx->f_xy, ctx->f_desc, ctx->f_count, ctx->max_feat,
-                           depth_mm_dev, w, p, ctx->tick_res, ctx->db_xy_heading, ctx->db_desc, ctx->db_pts3d, ctx->db_kp2d, ctx->db_off,
-                           ctx->db_pose, ctx->accum_res);
+    auto kern = ctx->has_dist ? k_accumulate<true> : k_accumulate<false>;
+    hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, ctx->stream, ctx->f_xy, ctx->f_desc, ctx->f_count, ctx->max_feat,
+                       depth_mm_dev, w, p, ctx->tick_res, ctx->db_xy_heading, ctx->db_desc, ctx->db_pts3d, ctx->db_kp2d, ctx->db_off,
+                       ctx->db_pose, ctx->accum_res, make_dist(ctx->dist));
     HIP_TRY(hipGetLastError());
     return RELOC_OK;
 }

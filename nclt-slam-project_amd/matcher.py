@@ -301,13 +301,7 @@ class LandmarkMatcherCore:
         if ok.sum() < cfg.accum_min_kpts:
             return False
         uu, vv, z = uu[ok], vv[ok], z[ok]
-        if np.any(self.dist != 0):
-            # a distorted camera: the rounded pixels through the inverse model (as k_accumulate_dist, include/reloc_spec.h)
-            xu = self.cv2.undistortPoints(np.stack([uu, vv], 1).astype(np.float64).reshape(-1, 1, 2), cfg.K.astype(np.float64),
-                                          self.dist).reshape(-1, 2)
-            pts3 = np.stack([xu[:, 0] * z, xu[:, 1] * z, z], axis=-1).astype(np.float32)
-        else:
-            pts3 = np.stack([(uu - cfg.cx) * z / cfg.fx, (vv - cfg.cy) * z / cfg.fy, z], axis=-1).astype(np.float32)
+        pts3 = P.back_project(self.cv2, uu, vv, z, cfg.fx, cfg.fy, cfg.cx, cfg.cy, self.dist, K=cfg.K.astype(np.float64))
         R_wb = P.quat_to_rot(*base_pose[3:7])
         c = np.array(base_pose[:3], dtype=np.float64) + R_wb @ self.base_to_cam_t
         q = P.rot_to_quat_scipy(R_wb @ self.base_to_cam_R)          # the reference converts with scipy here (M:478-479)

@@ -95,13 +95,7 @@ class LandmarkRecorderCore:
         if ok.sum() < MIN_RECORD_KPTS:
             return None
         uu, vv, z = uu[ok], vv[ok], z[ok]
-        if any(self.dist):
-            K = np.array([[FX, 0, CX], [0, FY, CY], [0, 0, 1]])
-            xu = cv2.undistortPoints(np.stack([uu, vv], 1).astype(np.float64).reshape(-1, 1, 2), K,
-                                     np.asarray(self.dist)).reshape(-1, 2)
-            pts3 = np.stack([xu[:, 0] * z, xu[:, 1] * z, z], axis=-1).astype(np.float32)
-        else:
-            pts3 = np.stack([(uu - CX) * z / FX, (vv - CY) * z / FY, z], axis=-1).astype(np.float32)
+        pts3 = P.back_project(cv2, uu, vv, z, FX, FY, CX, CY, self.dist)
         rec = {"pose": cam_pose, "descriptors": desc[ok], "keypoints_2d": xy[ok], "keypoints_3d_cam": pts3,
                "ts": rgb_ts, "n_features": int(len(pts3))}
         self.landmarks.append(rec)

@@ -57,7 +57,7 @@ def undistort(u, v, K4, d, iters=UNDISTORT_ITERS):
 
 
 def reproj_err2(Rt, K4, d, obj, img):
-    """squared error in distorted pixels of every correspondence under one pose (R row-major | t), as k_pnp_score_dist"""
+    """squared error in distorted pixels of every correspondence under one pose (R row-major | t), as k_pnp_score<true>"""
     Rt = np.asarray(Rt, np.float64).reshape(12)
     o = np.asarray(obj, np.float32).astype(np.float64)
     X, Y, Z = o[:, 0], o[:, 1], o[:, 2]

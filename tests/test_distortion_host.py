@@ -201,7 +201,7 @@ def test_recorder_cv2_path_back_projects_through_the_model(oracle):
 
 def test_host_matcher_accumulation_back_projects_through_the_model(oracle):
     """LandmarkMatcherCore's accumulation (M:435-500) with MatcherConfig.dist: the new record's 3-D points come from the
-    inverse model, like the recorder's and the fused k_accumulate_dist"""
+    inverse model, like the recorder's and the fused k_accumulate<true>"""
     from nclt_slam_project_amd.matcher import LandmarkMatcherCore, MatcherConfig
     from nclt_slam_project_amd.recorder import LandmarkRecorderCore
     cv2 = _oracle_dist_cv2()

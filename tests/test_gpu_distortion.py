@@ -252,8 +252,8 @@ def test_batch_refuses_contexts_with_different_distortion(eng):
 
 
 def test_batched_tick_with_distortion_equals_single_ticks():
-    """reloc_tick_batch_dev over two contexts with EQUAL distortion (k_pnp_*_batch_dist) gives each frame the record of
-    its own reloc_tick_dev (k_pnp_*_dist)"""
+    """reloc_tick_batch_dev over two contexts with EQUAL distortion (k_pnp_*_batch<true>) gives each frame the record of
+    its own reloc_tick_dev (k_pnp_*<true>)"""
     from nclt_slam_project_amd import landmarks as LM
     scene = synth.WallScene(dist=D_MODERATE)
     es = [Engine(0, 640, 480, 4096) for _ in range(2)]
@@ -287,7 +287,7 @@ def test_batched_tick_with_distortion_equals_single_ticks():
 
 
 def test_accumulation_with_distortion_host_and_fused_agree():
-    """Accumulation (M:435-500) with a distorted camera: the fused tick (k_accumulate_dist) and the host matcher
+    """Accumulation (M:435-500) with a distorted camera: the fused tick (k_accumulate<true>) and the host matcher
     (cv2.undistortPoints on the rounded pixels) append the same record, whose 3-D points are the NumPy back-projection
     through the five-step inverse"""
     from nclt_slam_project_amd.cv2_shim import Cv2Shim
