@@ -247,6 +247,21 @@ int reloc_pnp_ransac_dist(reloc_ctx *ctx, const float *obj, const float *img, in
                           const double dist[5], int iters, float thr_px, double conf, uint64_t seed, double rvec[3],
                           double tvec[3], int32_t *inliers, int32_t *n_inl, int32_t *ok);
 
+/* ---- CLAHE (include/reloc_spec.h, "CLAHE") ------------------------------------------------------- */
+/* cv2.createCLAHE(clipLimit, tileGridSize=(tiles_x, tiles_y)).apply(gray) in front of ORB on 3-channel frames.
+ * tiles_x == tiles_y == 0 turns it off (the default of a new context; the launch sequence is then that of a context that
+ * never had it).  Otherwise both are in 1..64 and clip_limit is finite (<= 0: no clipping), else RELOC_E_ARG.  The first
+ * enable allocates the context's CLAHE plane and LUTs.  Applied by reloc_tick, reloc_tick_dev, reloc_tick_batch_dev,
+ * reloc_tick_scan_dev, reloc_shard_scan_batch_dev, reloc_record_frame and reloc_orb_frame_dev (the accumulation uses the
+ * tick's features); never by reloc_orb_detect_compute or reloc_gray_u8.  Batched calls refuse contexts with unequal
+ * settings (RELOC_E_STATE).  reloc_get_clahe returns (0, 0, 0) when off. */
+int reloc_set_clahe(reloc_ctx *ctx, double clip_limit, int tiles_x, int tiles_y);
+int reloc_get_clahe(reloc_ctx *ctx, double *clip_limit, int32_t *tiles_x, int32_t *tiles_y);
+/* The same operation on a caller's gray image with explicit parameters (cv2 shim): any w, h >= 1 within the capacity,
+ * tiles in 1..64; out is w x h, dense.  Host pointers; synchronous. */
+int reloc_clahe_u8(reloc_ctx *ctx, const uint8_t *gray, int w, int h, int stride, double clip_limit, int tiles_x,
+                   int tiles_y, uint8_t *out);
+
 /* ---- fused tick ----------------------------------------------------------------------------- */
 #define RELOC_TICK_LOCAL   0   /* candidates by VIO distance / heading only                          M:293-302 */
 #define RELOC_TICK_GLOBAL  1   /* whole-database search unconditionally (the benchmarked shape)       G:329-344 */

@@ -131,4 +131,23 @@
  * the pinhole kernels. */
 #define RELOC_UNDISTORT_ITERS    5
 
+/* CLAHE: cv2.createCLAHE(clipLimit, tileGridSize=(tx, ty)).apply(gray) on 8-bit single-channel input, restated from OpenCV 4.x
+ * modules/imgproc/src/clahe.cpp (the reference: experiments/35_road_obstacle_avoidance/scripts/robust_anchor_localizer.py:50,103
+ * and the teach / repeat phases of run_husky_teach_then_repeat.py, clipLimit=2.0, tileGridSize=(8, 8); not pinned against a
+ * cv2 build).  w x h image, tx x ty tiles:
+ *   tiles      w % tx == 0 && h % ty == 0: tile = (w / tx) x (h / ty) of the source.  Otherwise BOTH axes are padded at the
+ *              right / bottom by tx - w % tx columns and ty - h % ty rows (a full extra tile on an axis that divides) with
+ *              BORDER_REFLECT_101 (repeated for pads larger than the image, a 1-pixel axis maps to 0) and tile = padded / grid.
+ *              Histograms read the padded image; the interpolation runs over the original w x h.
+ *   clip       area = tile_w * tile_h; clipLimit > 0: clip = max((int)(clipLimit * area / 256), 1) in double; else no clip.
+ *   redistribute  clipped = sum max(hist[i] - clip, 0), bins capped at clip; every bin += clipped / 256; then bins 0, step,
+ *              2 step, ... get +1 while residual = clipped % 256 lasts, step = max(256 / residual, 1).
+ *   LUT        lutScale = 255.0f / area (float division); lut[i] = saturate_cast<uchar>((float)sum_{j<=i} hist[j] * lutScale)
+ *              (cvRound: half to even).
+ *   interpolate   f32, no FMA: txf = x * (1.0f / tile_w) - 0.5f, tx1 = floor(txf), xa = txf - tx1, xa1 = 1.0f - xa,
+ *              tx2 = min(tx1 + 1, tx - 1), tx1 = max(tx1, 0); the same in y; out = saturate_cast<uchar>((L11[v] xa1 + L12[v] xa)
+ *              ya1 + (L21[v] xa1 + L22[v] xa) ya) with L<row><col> the LUTs of tiles (ty1|ty2, tx1|tx2), in this order. */
+#define RELOC_CLAHE_BINS         256
+#define RELOC_CLAHE_MAX_TILES    64   /* per grid dimension (reloc_set_clahe, reloc_clahe_u8) */
+
 #endif /* RELOC_SPEC_H */

@@ -62,6 +62,9 @@ SIGNATURES = {
     "reloc_undistort_points": (C.c_int, [c_ctx, P, C.c_int, P, P, P]),
     "reloc_pnp_score_dist": (C.c_int, [c_ctx, P, P, C.c_int, P, C.c_int, P, P, f32, P, P]),
     "reloc_pnp_ransac_dist": (C.c_int, [c_ctx, P, P, C.c_int, P, P, C.c_int, f32, f64, u64, P, P, P, P, P]),
+    "reloc_set_clahe": (C.c_int, [c_ctx, f64, C.c_int, C.c_int]),
+    "reloc_get_clahe": (C.c_int, [c_ctx, P, P, P]),
+    "reloc_clahe_u8": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, f64, C.c_int, C.c_int, P]),
     "reloc_tick_debug": (C.c_int, [c_ctx, P, P, P, P, P, P, P]),
     "reloc_tick": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, P, C.c_int, u64, P, P, P, P, P, P]),
     "reloc_get_params": (C.c_int, [c_ctx, P]),

@@ -334,6 +334,12 @@ struct reloc_ctx {
     double dist[5] = {0, 0, 0, 0, 0};   // k1 k2 p1 p2 k3 (reloc_set_distortion); zeros normalised to +0
     bool has_dist = false;               // a coefficient is non-zero: the DIST kernels run
 
+    // ---- CLAHE in front of ORB on 3-channel frames (reloc_set_clahe); tiles 0 x 0 = off, the default ----
+    double clahe_clip = 0.0;             // clipLimit (0 when off; -0 normalised to +0)
+    int clahe_tx = 0, clahe_ty = 0;      // tileGridSize
+    uint8_t *clahe_plane = nullptr;      // equalised gray plane, row stride (w + 63) & ~63 (allocated on first enable)
+    uint8_t *clahe_lut = nullptr;        // tiles_y x tiles_x x 256 LUTs (64 x 64 x 256 bytes, allocated with the plane)
+
     // ---- matcher parameters (reloc_set_params) ----
     reloc_params prm;
     int scan_grid = 0;               // RELOC_SCAN_GRID (developer switch), read once at creation: > 0 static grid of that

@@ -1076,7 +1076,190 @@ int orb_prepare(reloc_ctx *ctx, int w, int h, int nfeatures)
     return RELOC_OK;
 }
 
+// ---- CLAHE (include/reloc_spec.h) -------------------------------------------------------------------
+// cv2.createCLAHE(clipLimit, tileGridSize).apply(gray) on 8-bit input, in two launches:
+//   k_clahe_lut    one workgroup per tile: histogram of the tile's pixels of the padded frame (BORDER_REFLECT_101 on the
+//                  right / bottom) in per-wave LDS sub-histograms (integer atomics: order-independent), then wave 0 holds
+//                  4 bins per lane for the clip, the redistribution and the prefix sum and stores the tile's 256-byte LUT
+//   k_clahe_apply  4 pixels per lane: gray (CH = 3: fused conversion), four LUT lookups through the cache, bilinear blend
+// CH = 3 reads an interleaved frame (gray_fixed with the order / coefficient flags), CH = 1 a gray plane.  Both are
+// frame-batched (blockIdx.y = frame); a single frame is a batch of one.
+struct ClaheGeom {
+    int w, h;              // frame size (the interpolation runs over it)
+    int tx, ty;            // tile grid
+    int tw, th;            // tile size in the padded frame
+    int clip;              // clip count per bin, 0 = no clipping
+    float lut_scale;       // 255.0f / (tw * th)
+    float inv_tw, inv_th;  // 1.0f / tw, 1.0f / th
+};
+struct ClaheFrames { const uint8_t *src[RELOC_BATCH_MAX]; uint8_t *lut[RELOC_BATCH_MAX]; uint8_t *dst[RELOC_BATCH_MAX]; };
+#ifndef RELOC_CLAHE_LUT_BS
+#define RELOC_CLAHE_LUT_BS 1024
+#endif
+constexpr int CLAHE_LUT_BS = RELOC_CLAHE_LUT_BS;     // 16 waves, 16 sub-histograms (16 KB of LDS); see DESIGN.md for 256 / 512
+constexpr int CLAHE_MAX_TILES = RELOC_CLAHE_MAX_TILES;
+
+static ClaheGeom clahe_geom(int w, int h, double clip_limit, int tx, int ty)
+{
+    ClaheGeom g;
+    g.w = w; g.h = h; g.tx = tx; g.ty = ty;
+    // OpenCV pads BOTH axes unless both divide (a full extra tile on an axis that already divides)
+    const bool divides = w % tx == 0 && h % ty == 0;
+    g.tw = divides ? w / tx : (w + tx - w % tx) / tx;
+    g.th = divides ? h / ty : (h + ty - h % ty) / ty;
+    const int area = g.tw * g.th;
+    if (clip_limit > 0.0) {
+        const int c = (int)(clip_limit * area / 256);
+        g.clip = c > 1 ? c : 1;
+    } else {
+        g.clip = 0;
+    }
+    g.lut_scale = 255.0f / (float)area;
+    g.inv_tw = 1.0f / (float)g.tw;
+    g.inv_th = 1.0f / (float)g.th;
+    return g;
+}
+
+template <int CH>
+__global__ __launch_bounds__(CLAHE_LUT_BS) void k_clahe_lut(ClaheFrames F, ClaheGeom g, int sstride, int flags)
+{
+    constexpr int NWAVE = CLAHE_LUT_BS / 64;
+    __shared__ int s_hist[NWAVE][256];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    for (int i = tid; i < NWAVE * 256; i += CLAHE_LUT_BS) (&s_hist[0][0])[i] = 0;
+    __syncthreads();
+    const uint8_t *src = F.src[blockIdx.y];
+    const int ti = blockIdx.x % g.tx, tj = blockIdx.x / g.tx;
+    const int x0 = ti * g.tw, y0 = tj * g.th;
+    for (int py = wave; py < g.th; py += NWAVE) {
+        const int sy = y0 + py < g.h ? y0 + py : reflect101(y0 + py, g.h);
+        const uint8_t *row = src + (size_t)sy * sstride;
+        for (int px = lane; px < g.tw; px += 64) {
+            const int sx = x0 + px < g.w ? x0 + px : reflect101(x0 + px, g.w);
+            int v;
+            if (CH == 1) {
+                v = row[sx];
+            } else {
+                const uint8_t *p = row + 3 * sx;
+                const int c0 = p[0], c1 = p[1], c2 = p[2];
+                v = gray_fixed((flags & 1) ? c2 : c0, c1, (flags & 1) ? c0 : c2, flags);
+            }
+            atomicAdd(&s_hist[wave][v], 1);
+        }
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    int hb[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        int s = 0;
+#pragma unroll
+        for (int wv = 0; wv < NWAVE; ++wv) s += s_hist[wv][4 * lane + k];
+        hb[k] = s;
+    }
+    if (g.clip > 0) {
+        int clipped = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int ex = hb[k] > g.clip ? hb[k] - g.clip : 0;
+            clipped += ex;
+            hb[k] -= ex;
+        }
+        clipped = wave_sum_i32(clipped);
+        const int batch = clipped >> 8, residual = clipped & 255;
+        const int step = residual ? (256 / residual > 1 ? 256 / residual : 1) : 1;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int bin = 4 * lane + k;
+            hb[k] += batch + (residual && bin % step == 0 && bin / step < residual ? 1 : 0);
+        }
+    }
+    // inclusive prefix sum: 4 bins in the lane, then the lanes' totals across the wave
+    int loc[4];
+    loc[0] = hb[0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k) loc[k] = loc[k - 1] + hb[k];
+    int incl = loc[3];
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int t = __shfl_up(incl, off);
+        if (lane >= off) incl += t;
+    }
+    const int excl = incl - loc[3];
+    u32 out = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        int v = __float2int_rn((float)(excl + loc[k]) * g.lut_scale);     // saturate_cast<uchar>: cvRound, then clamp
+        v = v < 0 ? 0 : (v > 255 ? 255 : v);
+        out |= (u32)v << (8 * k);
+    }
+    reinterpret_cast<u32 *>(F.lut[blockIdx.y] + (size_t)blockIdx.x * 256)[lane] = out;
+}
+
+template <int CH, bool ALIGNED>
+__global__ __launch_bounds__(256) void k_clahe_apply(ClaheFrames F, ClaheGeom g, int sstride, int flags, int dstride)
+{
+    const int quads = (g.w + 3) >> 2;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= quads * g.h) return;
+    const int y = q / quads, x4 = 4 * (q - y * quads);
+    u32 d[3];
+    pyr_fetch<CH, ALIGNED>(F.src[blockIdx.y] + (size_t)y * sstride + CH * x4, x4, g.w, d);
+    const u32 gray4 = pyr_gray4<CH>(d, x4, g.w, flags);
+    const float tyf = (float)y * g.inv_th - 0.5f;
+    int ty1 = (int)floorf(tyf);
+    const float ya = tyf - (float)ty1, ya1 = 1.0f - ya;
+    const int ty2 = ty1 + 1 < g.ty - 1 ? ty1 + 1 : g.ty - 1;
+    ty1 = ty1 > 0 ? ty1 : 0;
+    const uint8_t *lut = F.lut[blockIdx.y];
+    const uint8_t *L1 = lut + (size_t)ty1 * g.tx * 256, *L2 = lut + (size_t)ty2 * g.tx * 256;
+    u32 out = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int x = x4 + k;
+        const float txf = (float)x * g.inv_tw - 0.5f;
+        int tx1 = (int)floorf(txf);
+        const float xa = txf - (float)tx1, xa1 = 1.0f - xa;
+        const int tx2 = tx1 + 1 < g.tx - 1 ? tx1 + 1 : g.tx - 1;
+        tx1 = tx1 > 0 ? tx1 : 0;
+        const int v = (gray4 >> (8 * k)) & 0xFF;
+        const float l11 = L1[tx1 * 256 + v], l12 = L1[tx2 * 256 + v], l21 = L2[tx1 * 256 + v], l22 = L2[tx2 * 256 + v];
+        const float res = (l11 * xa1 + l12 * xa) * ya1 + (l21 * xa1 + l22 * xa) * ya;
+        int r = __float2int_rn(res);
+        r = r < 0 ? 0 : (r > 255 ? 255 : r);
+        if (x < g.w) out |= (u32)r << (8 * k);
+    }
+    uint8_t *dst = F.dst[blockIdx.y] + (size_t)y * dstride + x4;
+    if ((dstride & 3) == 0) {
+        *reinterpret_cast<u32 *>(dst) = out;       // the row holds round4(w) bytes: dstride >= w and a multiple of 4
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (x4 + k < g.w) dst[k] = (uint8_t)(out >> (8 * k));
+    }
+}
+
+// the two CLAHE launches for n frames of equal geometry on stream st; srcs: channels-interleaved rows of sstride bytes
+static int clahe_launch(hipStream_t st, const ClaheFrames &F, int n, const ClaheGeom &g, int channels, int sstride, int flags,
+                        int dstride)
+{
+    bool aligned = g.w % 4 == 0 && sstride % 4 == 0;
+    for (int f = 0; f < n; ++f) aligned = aligned && ((uintptr_t)F.src[f]) % 4 == 0;
+    const int quads = (g.w + 3) / 4;
+    const dim3 glut(g.tx * g.ty, n), gapp((quads * g.h + 255) / 256, n);
+    auto lut = channels == 3 ? k_clahe_lut<3> : k_clahe_lut<1>;
+    auto app = channels == 3 ? (aligned ? k_clahe_apply<3, true> : k_clahe_apply<3, false>)
+                             : (aligned ? k_clahe_apply<1, true> : k_clahe_apply<1, false>);
+    hipLaunchKernelGGL(lut, glut, dim3(CLAHE_LUT_BS), 0, st, F, g, sstride, flags);
+    hipLaunchKernelGGL(app, gapp, dim3(256), 0, st, F, g, sstride, flags, dstride);
+    HIP_TRY(hipGetLastError());
+    return RELOC_OK;
+}
+
+static inline int clahe_stride(int w) { return (w + 63) & ~63; }
+
 // src_dev: channels == 3 -> interleaved frame (gray fused), channels == 1 -> gray plane.
+// A 3-channel frame of a context with CLAHE on (reloc_set_clahe) is equalised first; the pyramid then reads the CLAHE plane.
 int orb_run_dev(reloc_ctx *ctx, const uint8_t *src_dev, int w, int h, int stride, int channels, int order, int nfeatures)
 {
     int rc = orb_prepare(ctx, w, h, nfeatures);
@@ -1085,6 +1268,17 @@ int orb_run_dev(reloc_ctx *ctx, const uint8_t *src_dev, int w, int h, int stride
     const OrbTable *tab_d = (const OrbTable *)ctx->orb_const;
     hipStream_t st = ctx->stream;
     reloc_prof_begin(ctx, RELOC_PROF_ORB);
+    if (channels == 3 && ctx->clahe_tx > 0) {
+        ClaheFrames F = {};
+        F.src[0] = src_dev; F.lut[0] = ctx->clahe_lut; F.dst[0] = ctx->clahe_plane;
+        const int cs = clahe_stride(w);
+        if ((rc = clahe_launch(st, F, 1, clahe_geom(w, h, ctx->clahe_clip, ctx->clahe_tx, ctx->clahe_ty), 3, stride,
+                               gray_flags(ctx, order), cs))) {
+            reloc_prof_end(ctx, RELOC_PROF_ORB);
+            return rc;
+        }
+        src_dev = ctx->clahe_plane; stride = cs; channels = 1;
+    }
     {
         const bool aligned = (w % 4 == 0) && (stride % 4 == 0) && (((uintptr_t)src_dev) % 4 == 0);
         // 512-thread workgroups where nothing scans beside the tick (local-candidate ticks, exclusive contexts, single calls),
@@ -1128,6 +1322,10 @@ int orb_run_batch_dev(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs_
                 reloc_set_error("orb batch: contexts of unequal geometry");
                 return RELOC_E_STATE;
             }
+            if (c->clahe_tx != ctxs[0]->clahe_tx || c->clahe_ty != ctxs[0]->clahe_ty || c->clahe_clip != ctxs[0]->clahe_clip) {
+                reloc_set_error("orb batch: contexts of unequal CLAHE settings (reloc_set_clahe)");
+                return RELOC_E_STATE;
+            }
             aligned = aligned && (((uintptr_t)srcs_dev[f]) % 4 == 0);
         }
         OrbFrame &F = b.f[f];
@@ -1145,7 +1343,20 @@ int orb_run_batch_dev(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs_
     for (int l = 0; l < NLEV; ++l) lds.lev[l] = c0->pyr_lds[l];
     lds.tabs = c0->pyr_lds[NLEV];
     // 256-thread pyramid: a batch runs beside other streams' scans (see orb_run_dev)
-    if (aligned)
+    if (c0->clahe_tx > 0) {
+        // CLAHE of every frame into its context's plane, then the gray-plane pyramid over the planes
+        ClaheFrames F = {};
+        for (int f = 0; f < n; ++f) { F.src[f] = srcs_dev[f]; F.lut[f] = ctxs[f]->clahe_lut; F.dst[f] = ctxs[f]->clahe_plane; }
+        const int cs = clahe_stride(w);
+        const int rc = clahe_launch(st, F, n, clahe_geom(w, h, c0->clahe_clip, c0->clahe_tx, c0->clahe_ty), 3, stride,
+                                    gray_flags(c0, order), cs);
+        if (rc) { reloc_prof_end(c0, RELOC_PROF_ORB); return rc; }
+        for (int f = 0; f < RELOC_BATCH_MAX; ++f) b.f[f].src = ctxs[f < n ? f : 0]->clahe_plane;
+        if (w % 4 == 0)
+            hipLaunchKernelGGL((k_pyramid_batch<1, true, 256>), dim3(c0->pyr_ntiles, n), dim3(256), c0->pyr_lds_bytes, st, b, w, h, cs, 0, lds);
+        else
+            hipLaunchKernelGGL((k_pyramid_batch<1, false, 256>), dim3(c0->pyr_ntiles, n), dim3(256), c0->pyr_lds_bytes, st, b, w, h, cs, 0, lds);
+    } else if (aligned)
         hipLaunchKernelGGL((k_pyramid_batch<3, true, 256>), dim3(c0->pyr_ntiles, n), dim3(256), c0->pyr_lds_bytes, st, b, w, h, stride, gray_flags(c0, order), lds);
     else
         hipLaunchKernelGGL((k_pyramid_batch<3, false, 256>), dim3(c0->pyr_ntiles, n), dim3(256), c0->pyr_lds_bytes, st, b, w, h, stride, gray_flags(c0, order), lds);
@@ -1224,5 +1435,65 @@ RELOC_API int reloc_frame_debug_plane(reloc_ctx *ctx, int what, int level, uint8
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     *w = L.w;
     *h = L.h;
+    return RELOC_OK;
+}
+
+// ---- CLAHE entry points -------------------------------------------------------------------------------
+static bool clahe_args_ok(double clip_limit, int tiles_x, int tiles_y)
+{
+    return clip_limit - clip_limit == 0.0 && tiles_x >= 1 && tiles_x <= CLAHE_MAX_TILES && tiles_y >= 1 && tiles_y <= CLAHE_MAX_TILES;
+}
+
+RELOC_API int reloc_set_clahe(reloc_ctx *ctx, double clip_limit, int tiles_x, int tiles_y)
+{
+    ARG_CHECK_CTX(ctx, true, "ctx is NULL");
+    if (tiles_x == 0 && tiles_y == 0) {
+        ctx->clahe_clip = 0.0;
+        ctx->clahe_tx = ctx->clahe_ty = 0;
+        return RELOC_OK;
+    }
+    ARG_CHECK(clahe_args_ok(clip_limit, tiles_x, tiles_y),
+              "reloc_set_clahe: tiles_x and tiles_y must both be 0 (off) or both in 1..64, and clip_limit finite");
+    if (!ctx->clahe_plane) {
+        // first enable: the plane of the largest frame and the LUTs of the largest grid
+        HIP_TRY(hipMalloc((void **)&ctx->clahe_plane, (size_t)clahe_stride(ctx->max_w) * ctx->max_h));
+        const hipError_t e = hipMalloc((void **)&ctx->clahe_lut, (size_t)CLAHE_MAX_TILES * CLAHE_MAX_TILES * 256);
+        if (e != hipSuccess) {
+            (void)hipFree(ctx->clahe_plane);
+            ctx->clahe_plane = nullptr;
+            HIP_TRY(e);
+        }
+    }
+    ctx->clahe_clip = clip_limit == 0.0 ? 0.0 : clip_limit;     // -0 -> +0: equal settings compare equal
+    ctx->clahe_tx = tiles_x;
+    ctx->clahe_ty = tiles_y;
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_get_clahe(reloc_ctx *ctx, double *clip_limit, int32_t *tiles_x, int32_t *tiles_y)
+{
+    ARG_CHECK_CTX(ctx, clip_limit && tiles_x && tiles_y, "reloc_get_clahe");
+    *clip_limit = ctx->clahe_clip;
+    *tiles_x = ctx->clahe_tx;
+    *tiles_y = ctx->clahe_ty;
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_clahe_u8(reloc_ctx *ctx, const uint8_t *gray, int w, int h, int stride, double clip_limit, int tiles_x,
+                             int tiles_y, uint8_t *out)
+{
+    ARG_CHECK_CTX(ctx, gray && out && w >= 1 && h >= 1 && stride >= w, "reloc_clahe_u8");
+    ARG_CHECK(clahe_args_ok(clip_limit, tiles_x, tiles_y), "reloc_clahe_u8: tiles_x, tiles_y must be in 1..64 and clip_limit finite");
+    if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
+    void *dlut, *dout;
+    int rc;
+    if ((rc = reloc_scratch(ctx, 0, (int64_t)tiles_x * tiles_y * 256, &dlut))) return rc;
+    if ((rc = reloc_scratch(ctx, 1, (int64_t)w * h, &dout))) return rc;
+    HIP_TRY(hipMemcpy2DAsync(ctx->frame_img, w, gray, stride, w, h, hipMemcpyHostToDevice, ctx->stream));
+    ClaheFrames F = {};
+    F.src[0] = ctx->frame_img; F.lut[0] = (uint8_t *)dlut; F.dst[0] = (uint8_t *)dout;
+    if ((rc = clahe_launch(ctx->stream, F, 1, clahe_geom(w, h, clip_limit, tiles_x, tiles_y), 1, w, 0, w))) return rc;
+    HIP_TRY(hipMemcpyAsync(out, dout, (size_t)w * h, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return RELOC_OK;
 }

@@ -1,7 +1,7 @@
 """cv2-shaped front end of the MI355X relocalization library.
 
 Exposes exactly the OpenCV symbols the reference's teach/repeat nodes call:
-    cvtColor, ORB_create(...).detectAndCompute / .detect, BFMatcher(...).match / .knnMatch,
+    cvtColor, createCLAHE(...).apply, ORB_create(...).detectAndCompute / .detect, BFMatcher(...).match / .knnMatch,
     solvePnPRansac, projectPoints, undistortPoints, Rodrigues, KeyPoint, DMatch, error and the constants,
 with the same argument meaning, return shapes and error behaviour, so that
     import nclt_slam_project_amd.cv2_shim as cv2
@@ -11,6 +11,8 @@ library through `Engine`; there is no CPU fallback (a missing library or GPU rai
 
 Lens distortion is OpenCV's default model (k1, k2, p1, p2[, k3]; include/reloc_spec.h) in any of OpenCV's shapes; longer
 vectors (rational, thin-prism, tilted) are accepted only when every coefficient after k3 is zero, anything else raises.
+
+CLAHE is OpenCV's 8-bit algorithm (include/reloc_spec.h); 16-bit and colour input raise.
 
 `Cv2Shim(backend)` takes any object with the Engine's method names; the module-level functions
 bind to one lazily created HIP Engine.
@@ -146,6 +148,56 @@ class _ORB:
         return self._nfeatures
 
 
+class _CLAHE:
+    """cv2.CLAHE: 8-bit single-channel apply() on the backend (reloc_clahe_u8), OpenCV's getters and setters"""
+
+    def __init__(self, shim, clipLimit, tileGridSize):
+        self._shim = shim
+        self.setClipLimit(clipLimit)
+        self.setTilesGridSize(tileGridSize)
+
+    def apply(self, src, dst=None):
+        img = np.asarray(src)
+        if img.dtype == np.uint16:
+            raise error("CLAHE.apply: 16-bit input is not implemented (only 8-bit)")
+        if img.dtype != np.uint8 or img.ndim != 2:
+            raise error("CLAHE.apply: expected a single-channel uint8 image")
+        if not hasattr(self._shim.backend, "clahe"):
+            raise error("CLAHE.apply: not implemented by this backend (it has no clahe)")
+        try:
+            out = self._shim.backend.clahe(img, self._clip, self._tiles)
+        except RelocError as e:
+            raise error(str(e)) from e
+        if dst is not None:
+            dst[...] = out
+            return dst
+        return out
+
+    def getClipLimit(self):
+        return self._clip
+
+    def setClipLimit(self, clipLimit):
+        c = float(clipLimit)
+        if not math.isfinite(c):
+            raise error("CLAHE: clipLimit must be finite")
+        self._clip = c
+
+    def getTilesGridSize(self):
+        return self._tiles
+
+    def setTilesGridSize(self, tileGridSize):
+        try:
+            tx, ty = (int(v) for v in tileGridSize)
+        except (TypeError, ValueError) as e:
+            raise error("CLAHE: tileGridSize must be a (width, height) pair") from e
+        if not (1 <= tx <= 64 and 1 <= ty <= 64):
+            raise error(f"CLAHE: tileGridSize {tx}x{ty} is outside 1..64 per dimension")
+        self._tiles = (tx, ty)
+
+    def collectGarbage(self):
+        pass
+
+
 class _BFMatcher:
     def __init__(self, shim, normType, crossCheck):
         if normType not in (NORM_HAMMING,):
@@ -233,6 +285,9 @@ class Cv2Shim:
             return self.backend.gray(img, order_rgb=(code == COLOR_RGB2GRAY))
         except RelocError as e:
             raise error(str(e)) from e
+
+    def createCLAHE(self, clipLimit=40.0, tileGridSize=(8, 8)):
+        return _CLAHE(self, clipLimit, tileGridSize)
 
     def ORB_create(self, nfeatures=500, **kwargs):
         defaults = dict(scaleFactor=1.2, nlevels=8, edgeThreshold=31, firstLevel=0, WTA_K=2, scoreType=0,
@@ -357,6 +412,10 @@ def set_default_backend(backend, ransac_seed: int = 0):
 
 def cvtColor(src, code):
     return default_shim().cvtColor(src, code)
+
+
+def createCLAHE(clipLimit=40.0, tileGridSize=(8, 8)):
+    return default_shim().createCLAHE(clipLimit, tileGridSize)
 
 
 def ORB_create(nfeatures=500, **kw):

@@ -185,6 +185,32 @@ class Engine:
         return dict(xy=xy[:k].copy(), size=size[:k].copy(), angle=ang[:k].copy(), response=resp[:k].copy(),
                     octave=octv[:k].copy(), desc=desc[:k].copy(), n=k)
 
+    def clahe(self, gray: np.ndarray, clip: float = 40.0, tiles=(8, 8)) -> np.ndarray:
+        """cv2.createCLAHE(clip, tiles).apply(gray) on an (H, W) uint8 image (reloc_clahe_u8); tiles = (tiles_x, tiles_y)"""
+        gray = np.asarray(gray)
+        if gray.dtype != np.uint8 or gray.ndim != 2:
+            raise N.RelocError("clahe: expected an (H, W) uint8 image")
+        if gray.strides[1] != 1 or gray.strides[0] < gray.shape[1]:
+            gray = np.ascontiguousarray(gray)
+        h, w = gray.shape
+        tx, ty = (int(v) for v in tiles)
+        out = np.empty((h, w), np.uint8)
+        N.check(self._lib.reloc_clahe_u8(self._ctx, C.c_void_p(gray.ctypes.data), w, h, gray.strides[0], float(clip), tx, ty,
+                                         N.ptr(out)), "reloc_clahe_u8")
+        return out
+
+    def set_clahe(self, clip: float | None = 2.0, tiles=(8, 8)):
+        """CLAHE in front of ORB on the 3-channel frames of the fused tick, recording and reloc_orb_frame_dev (reloc_set_clahe);
+        clip=None or tiles=(0, 0) turns it off"""
+        tx, ty = (0, 0) if clip is None else (int(v) for v in tiles)
+        N.check(self._lib.reloc_set_clahe(self._ctx, 0.0 if clip is None else float(clip), tx, ty), "reloc_set_clahe")
+
+    def get_clahe(self):
+        """None when off, else (clip, (tiles_x, tiles_y))"""
+        clip = C.c_double(); tx = C.c_int32(); ty = C.c_int32()
+        N.check(self._lib.reloc_get_clahe(self._ctx, C.byref(clip), C.byref(tx), C.byref(ty)), "reloc_get_clahe")
+        return None if tx.value == 0 else (clip.value, (tx.value, ty.value))
+
     def record_frame(self, bgr: np.ndarray, depth_mm: np.ndarray, nfeatures: int = 500, order_rgb: bool = False):
         """teach-side record arrays of one frame: dict(xy (n,2), desc (n,32), pts3d (n,3), kp_index (n,), n, n_kp)"""
         bgr = N.u8(bgr)

@@ -35,6 +35,9 @@ class MatcherConfig:
     # lens distortion, OpenCV's (k1, k2, p1, p2[, k3]) -- e.g. sensor_msgs/CameraInfo.d of a plumb_bob camera; () = pinhole
     # (the reference's DIST = zeros, M:52).  Longer OpenCV vectors are accepted when everything after k3 is zero.
     dist: tuple = ()
+    # CLAHE between gray conversion and ORB: None = off (the reference matcher), or (clipLimit, (tiles_x, tiles_y)) as in
+    # cv2.createCLAHE(clipLimit=2.0, tileGridSize=(8, 8)) of the teach-and-repeat scripts.  Teach with the same setting.
+    clahe: tuple | None = None
     candidate_radius_m: float = 8.0
     max_candidates: int = 5
     heading_tol_deg: float = 90.0
@@ -99,6 +102,8 @@ class LandmarkMatcherCore:
         self._adopt(load_landmarks(landmarks) if isinstance(landmarks, str) else landmarks)
         self.orb = cv2.ORB_create(nfeatures=self.cfg.nfeatures)
         self.matcher = cv2.BFMatcher(cv2.NORM_HAMMING, crossCheck=True)
+        self.clahe = None if self.cfg.clahe is None else cv2.createCLAHE(clipLimit=self.cfg.clahe[0],
+                                                                         tileGridSize=tuple(self.cfg.clahe[1]))
         self.dist = np.zeros((4, 1), dtype=np.float32) if len(self.cfg.dist) == 0 else np.asarray(self.cfg.dist, np.float64).reshape(-1, 1)
         self.last_anchor_ts = 0.0
         self.n_attempts = 0
@@ -239,6 +244,8 @@ class LandmarkMatcherCore:
         vio_xy = (base_pose[0], base_pose[1])
         cand, d, herr = self.select_candidates(base_pose)
         gray = cv2.cvtColor(bgr, cv2.COLOR_BGR2GRAY)
+        if self.clahe is not None:
+            gray = self.clahe.apply(gray)
         kpts, desc = self.orb.detectAndCompute(gray, None)
         if desc is None or len(kpts) < cfg.min_matches:
             o = TickOutcome(ts, vio_xy, len(cand), 0, None, None, "curr_no_features")
@@ -346,6 +353,7 @@ class FusedLandmarkMatcher:
         e.set_camera([cfg.fx, cfg.fy, cfg.cx, cfg.cy], data.get("base_to_cam_translation", P.BASE_TO_CAM_TRANSLATION),
                      data.get("base_to_cam_rot", P.BASE_TO_CAM_ROT))
         e.set_distortion(cfg.dist)
+        e.set_clahe(*((None,) if cfg.clahe is None else (cfg.clahe[0], tuple(cfg.clahe[1]))))
         self._return_src = return_landmarks
         self.swap_flag = swap_flag
         self._swapped = False

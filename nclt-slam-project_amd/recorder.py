@@ -40,15 +40,18 @@ def local_depth_std(depth_mm, uu, vv):
 
 class LandmarkRecorderCore:
     def __init__(self, out_pkl=None, min_disp_m: float = 2.0, cv2=None, nfeatures: int = 500, logger=None, engine=None,
-                 dist=()):
+                 dist=(), clahe=None):
         """engine: when given, ORB + all per-keypoint gates + back-projection run in ONE device call
         (reloc_record_frame); otherwise the gates run in NumPy on the cv2-shaped module's features.
         dist: lens distortion as MatcherConfig.dist (OpenCV's k1 k2 p1 p2 [k3], () = pinhole): the kept keypoints are
-        back-projected through the inverse model (engine: reloc_set_distortion; cv2 path: cv2.undistortPoints)."""
+        back-projected through the inverse model (engine: reloc_set_distortion; cv2 path: cv2.undistortPoints).
+        clahe: None or (clipLimit, (tiles_x, tiles_y)) as MatcherConfig.clahe: CLAHE between gray conversion and ORB (engine:
+        reloc_set_clahe; cv2 path: cv2.createCLAHE(...).apply), so that the repeat run can equalise the same way."""
         self.engine = engine
         self.dist = tuple(np.asarray(dist, np.float64).ravel()) if dist is not None else ()
         if engine is not None:
             engine.set_distortion(self.dist)
+            engine.set_clahe(*((None,) if clahe is None else (clahe[0], tuple(clahe[1]))))
         self.nfeatures = nfeatures
         if cv2 is None and engine is None:
             from . import cv2_shim as cv2
@@ -56,6 +59,8 @@ class LandmarkRecorderCore:
         self.out_pkl = out_pkl
         self.min_disp_m = float(min_disp_m)
         self.orb = cv2.ORB_create(nfeatures=nfeatures) if cv2 is not None else None
+        self.clahe = (cv2.createCLAHE(clipLimit=clahe[0], tileGridSize=tuple(clahe[1]))
+                      if cv2 is not None and clahe is not None else None)
         self.landmarks = []
         self.last_landmark_pose_world = None
         self.log = logger or (lambda msg: None)
@@ -80,6 +85,8 @@ class LandmarkRecorderCore:
             return rec
         cv2 = self.cv2
         gray = cv2.cvtColor(bgr, cv2.COLOR_BGR2GRAY)
+        if self.clahe is not None:
+            gray = self.clahe.apply(gray)
         kpts, desc = self.orb.detectAndCompute(gray, None)
         if desc is None or len(kpts) == 0:
             return None
