@@ -71,16 +71,6 @@ constexpr int64_t MAX_DB_RECORDS = 0xFFFFF;   // the local-candidate key keeps t
 #else
 #define RELOC_SCAN_VGPR_ATTR
 #endif
-// Scheduling form of the whole-database scan in a context that shares the chip: n > 0 = n generations of workgroups, each with
-// a row budget, sweepers behind them; 0 = ONE resident generation that draws records until the counters are dry (what a lone
-// context has always run).  Rounds 2-3: three generations, so that other streams' small kernels found slots when a generation
-// retired.  Since the scan leaves them 96 registers they run BESIDE resident scans: 4 streams, interleaved on one box
-// (profiles/r4_scan_generations.log), 1 / 2 / 3 / 4 generations 6 853 / 6 759 / 6 752 / 6 604 frames/s, one generation without
-// budgets 6 826 -- and that form scans in 152 us on an idle chip where one generation WITH budgets takes 177 (static shares
-// leave a tail).  A batched launch (k_db_scan_batch) keeps one generation of budgets per frame.
-#ifndef RELOC_SCAN_GENS_SHARED
-#define RELOC_SCAN_GENS_SHARED 0
-#endif
 #ifndef RELOC_SMALL_PRIO
 #define RELOC_SMALL_PRIO 3
 #endif
@@ -272,8 +262,8 @@ __device__ __forceinline__ void undistort_norm(const DistCoef &d, const double K
 // Optional heading mask of the whole-database scan: records whose teach heading is incompatible with the
 // robot's are not scored (count 0), exactly the records the reference skips at G:329-330.  xyh == NULL: no mask.
 struct ScanMask {
-    const double *xyh;
-    double q[4];
+    const double *xyh = nullptr;
+    double q[4] = {0, 0, 0, 1};                  // base_link quaternion x y z w of the robot
     double cos_tol = 6.123233995736766e-17;      // cos(HEADING_TOL_DEG = 90 degrees) in double
     const int32_t *skip_if = nullptr;            // RELOC_TICK_AUTO: the whole launch stands down when *skip_if != 0
     // emit mode only (M:333-336): when g_obj is set, every mutual match also leaves its 3-D / 2-D pair
@@ -342,12 +332,8 @@ struct reloc_ctx {
 
     // ---- matcher parameters (reloc_set_params) ----
     reloc_params prm;
-    int scan_grid = 0;               // RELOC_SCAN_GRID (developer switch), read once at creation: > 0 static grid of that
-                                     // many workgroups, < 0 static default grid, 0 ticket scheduling
-    int scan_gens = 0;               // RELOC_SCAN_GENS (developer switch): generations of the ticket grid, < 0 = one, no quota
-    int scan_batch_gens = 0;         // RELOC_SCAN_BATCH_GENS (developer switch): generations of a batched scan launch
-    int scan_quota_rows = 1;         // RELOC_SCAN_QUOTA_ROWS (developer switch): 1 = workgroup budgets in rows + sweepers, 0 = a quota of records (rounds 2-3a)
-    int scan_nw = 0;                 // RELOC_SCAN_NW (developer switch): waves per record of the whole-database scan (1, 2, 4); 0 = by shape
+    int scan_gens = 0;               // RELOC_SCAN_GENS (developer switch), read once at creation: n > 0 = single whole-database
+                                     // scans in the form of batched ones (n generations of row budgets + sweepers, launch_db_count)
     uint32_t *scan_ticket = nullptr; // per frame of a batch (<= 8) 8 per-XCD record counters, then 1 exit counter, 128 bytes apart
 
     // ---- database: two arenas, the fields below are the SELECTED one's (reloc_db_select copies them) ----
@@ -397,9 +383,6 @@ int reloc_scratch(reloc_ctx *ctx, int slot, int64_t bytes, void **out);
 void reloc_prof_begin(reloc_ctx *ctx, int which);
 void reloc_prof_end(reloc_ctx *ctx, int which);
 
-// launchers shared between translation units
-// rec_ids == NULL: scan records 0..n_ids_max-1 and write counts[record]; otherwise scan the listed
-// records (count read from n_ids_dev when non-NULL) and write slot-indexed outputs.
 // lets go of one reference to an arena's six arrays; frees them when it was the last (reloc_match.hip)
 void db_arrays_drop(DbShare *&share, uint8_t *&desc, float *&pts3d, float *&kp2d, int64_t *&off, double *&pose, double *&xyh);
 extern int g_reloc_live_contexts;           // contexts created and not yet destroyed in this process (reloc_ctx.hip)
@@ -408,10 +391,16 @@ static inline bool ctx_alone(const reloc_ctx *c)
     return c->exclusive_hint > 0 || (c->exclusive_hint < 0 && __atomic_load_n(&g_reloc_live_contexts, __ATOMIC_RELAXED) == 1);
 }
 
-int launch_db_scan(reloc_ctx *ctx, const uint8_t *db_desc, const int64_t *db_off, int64_t n_rec,
-                   const int32_t *rec_ids, const int32_t *n_ids_dev, int n_ids_max, const uint8_t *cur,
-                   const int32_t *n_cur_dev, int n_cur_max, int max_rows, int32_t *counts, int32_t *m_qidx,
-                   int32_t *m_tidx, int32_t *m_dist, int32_t *m_n, int emit_stride, const ScanMask *mask = nullptr);
+// launchers shared between translation units (reloc_match.hip).  The whole-database scans count the mutual matches of the
+// current descriptors (cur, n_cur_max capacity, count on the device at n_cur_dev when non-NULL) with every record of the
+// context's database into counts[record]: one frame (launch_db_count) or one per context of a batch (launch_db_scan_batch).
+// launch_db_emit writes the match lists (emit_stride apart) of the listed records (n_ids_max capacity, count on the device
+// at n_ids_dev when non-NULL) or, with rec_ids == NULL, of records 0..n_ids_max-1 of db_desc / db_off.
+int launch_db_count(reloc_ctx *ctx, const uint8_t *cur, const int32_t *n_cur_dev, int n_cur_max, int32_t *counts,
+                    const ScanMask &mask = {});
+int launch_db_emit(reloc_ctx *ctx, const uint8_t *db_desc, const int64_t *db_off, int max_rows, const int32_t *rec_ids,
+                   const int32_t *n_ids_dev, int n_ids_max, const uint8_t *cur, const int32_t *n_cur_dev, int n_cur_max,
+                   int32_t *m_qidx, int32_t *m_tidx, int32_t *m_dist, int32_t *m_n, int emit_stride, const ScanMask &mask = {});
 int launch_db_emit_batch(reloc_ctx *const *ctxs, int n);
 int launch_db_scan_batch(reloc_ctx *const *ctxs, int n, const double *q, double cos_tol, bool auto_mode, bool heading_mask = true);
 int db_reindex(reloc_ctx *ctx);

@@ -500,8 +500,7 @@ __device__ __forceinline__ void db_count_body(
     // whatever waits: with several contexts on the chip another stream's ORB / PnP kernel); their budgets add up to the whole
     // database, so they normally serve every record.  The eight workgroups behind them (one per XCD, the last to start) draw
     // until the counters run dry: whatever the budgets left over is served (nothing, when the host knew the row total).
-    // (n_bounded < 0: the record quota of rounds 2-3a, RELOC_SCAN_QUOTA_ROWS=0; numbers and the variants dropped on the way:
-    // profiles/README.md "Dropped experiments" #4)
+    // (The variants dropped on the way, a quota of records among them: profiles/README.md "Dropped experiments" #4.)
     if (!ticket_pool) ticket_pool = ticket;
     if (block < 0) { block = blockIdx.x; n_blocks = gridDim.x; }
     constexpr int CB = 64 * NJ;
@@ -563,8 +562,7 @@ __device__ __forceinline__ void db_count_body(
         }
     };
     int it = stand_down ? n_ids : block;
-    const bool by_rows = n_bounded >= 0;                                      // n_bounded < 0: a quota of RECORDS for every workgroup
-    int left = (quota > 0 && (!by_rows || block < n_bounded)) ? quota : 0x7fffffff;   // rows (records) this workgroup may still take on
+    int left = (quota > 0 && block < n_bounded) ? quota : 0x7fffffff;        // rows this workgroup may still take on
     for (int i = tid; i < ncb * CB; i += 64 * NW) colbuf[i] = 0xFFFFFFFFu;
     if (tid == 0) wsum[0] = wsum[1] = 0;
     __syncthreads();
@@ -576,7 +574,7 @@ __device__ __forceinline__ void db_count_body(
         const int64_t row0 = off[r];
         const int n = scored ? (int)(off[r + 1] - row0) : 0;
         const uint4 *rec = db + 2 * row0;
-        left -= by_rows ? max(n, 1) : 1;
+        left -= max(n, 1);
         u32 next_ticket = 0;
         if (ticket && tid == 0 && left > 0) next_ticket = draw();        // no draw that this workgroup would not serve
         if (n > 0 && C > 0) {
@@ -641,7 +639,7 @@ __device__ __forceinline__ void db_count_body(
 // its feature capacity and always runs NJ = 8.  (One kernel branching on the device-side count was measured:
 // it costs the NJ = 8 path 3 %.)
 template <int NJ, bool EMIT, int NW>
-__global__ __launch_bounds__(64 * NW, NW >= 4 ? 16 / NW : 4) RELOC_SCAN_VGPR_ATTR void k_db_scan(
+__global__ __launch_bounds__(64 * NW, 16 / NW) RELOC_SCAN_VGPR_ATTR void k_db_scan(
     const uint4 *__restrict__ db, const int64_t *__restrict__ off, const int32_t *__restrict__ rec_ids,
     const int32_t *__restrict__ n_ids_p, int n_ids_max, const uint4 *__restrict__ cur,
     const int32_t *__restrict__ n_cur_p, int n_cur_max, int max_rows, int32_t *__restrict__ counts,
@@ -673,12 +671,18 @@ __global__ __launch_bounds__(256, 4) RELOC_SCAN_VGPR_ATTR void k_db_emit_batch(c
     RELOC_SMALL_KERNEL_PRIO();
     const EmitFrame &F = bt.f[blockIdx.y];
     ScanMask mask;
-    mask.xyh = nullptr;
-    mask.q[0] = mask.q[1] = mask.q[2] = 0; mask.q[3] = 1;
     mask.g_pts3d = g_pts3d; mask.g_xy = F.g_xy; mask.g_obj = F.g_obj; mask.g_img = F.g_img;
     const int C = F.n_cur_p ? min(*F.n_cur_p, n_cur_max) : n_cur_max;
     db_scan_body<8, true, 4>(lds, C, db, off, F.rec_ids, F.n_ids_p, n_ids_max, F.cur, max_rows, nullptr, F.m_qidx, F.m_tidx, F.m_dist, F.m_n,
                              emit_stride, mask, nullptr, 0);
+}
+
+// Dynamic LDS of a scan workgroup: col_words words of column minima, a row key per teach row, 16 words of counters
+static int scan_lds_bytes(const char *who, int col_words, int max_rows, size_t &lds)
+{
+    lds = (size_t)(col_words + max_rows + 16) * 4;
+    if (lds > 160 * 1024) { reloc_set_error("%s: LDS demand %zu bytes", who, lds); return RELOC_E_CAPACITY; }
+    return RELOC_OK;
 }
 
 int launch_db_emit_batch(reloc_ctx *const *ctxs, int n)
@@ -694,9 +698,8 @@ int launch_db_emit_batch(reloc_ctx *const *ctxs, int n)
         F.m_qidx = c->m_qidx; F.m_tidx = c->m_tidx; F.m_dist = c->m_dist; F.m_n = c->m_n; F.g_xy = c->f_xy; F.g_obj = c->p_obj; F.g_img = c->p_img;
     }
     const int max_rows = c0->db_max_rows < 1 ? 1 : c0->db_max_rows;
-    const int ncb = (c0->max_feat + 511) / 512;
-    const size_t lds = (size_t)(ncb * 512 + max_rows + 16) * 4;
-    if (lds > 160 * 1024) { reloc_set_error("emit batch: LDS demand %zu bytes", lds); return RELOC_E_CAPACITY; }
+    size_t lds;
+    if (int rc = scan_lds_bytes("emit batch", (c0->max_feat + 511) / 512 * 512, max_rows, lds)) return rc;
     hipLaunchKernelGGL(k_db_emit_batch, dim3(MAX_CAND, n), dim3(256), lds, c0->stream, (const uint4 *)c0->db_desc, c0->db_off, MAX_CAND,
                        c0->max_feat, max_rows, MAX_REC_ROWS, c0->db_pts3d, bt);
     HIP_TRY(hipGetLastError());
@@ -1066,30 +1069,67 @@ __global__ __launch_bounds__(64 * SQ_WAVES) __attribute__((amdgpu_waves_per_eu(8
     }
 }
 
-int launch_db_scan(reloc_ctx *ctx, const uint8_t *db_desc, const int64_t *db_off, int64_t n_rec,
-                   const int32_t *rec_ids, const int32_t *n_ids_dev, int n_ids_max, const uint8_t *cur,
-                   const int32_t *n_cur_dev, int n_cur_max, int max_rows, int32_t *counts, int32_t *m_qidx,
-                   int32_t *m_tidx, int32_t *m_dist, int32_t *m_n, int emit_stride, const ScanMask *mask_p)
+// Launch plan of a counting scan of the context's database (k_db_scan<NJ, false, 4>, k_db_scan_batch): 4-wave workgroups
+// over column blocks of 64 * nj current descriptors, n_cur_max of them at most.
+struct CountPlan {
+    int col_words = 0;            // column minima: one buffer for the capacity; the kernel double-buffers inside it when the
+                                  // run-time count leaves room (db_count_body), so at least two column blocks
+    size_t lds = 0;
+    int resident = 0;             // workgroups resident on the chip: 4 per CU (16 waves, 128-VGPR kernel) unless their LDS does not fit
+    int quota = 0, n_bounded = 0; // row budget of the first n_bounded workgroups of a scan (0, 0: none, see db_count_body)
+
+    int init(const reloc_ctx *ctx, const char *who, int nj, int n_cur_max, int max_rows)
+    {
+        const int cb = 64 * nj, ncb = (n_cur_max + cb - 1) / cb;
+        col_words = (ncb >= 2 ? ncb : 2) * cb;
+        if (int rc = scan_lds_bytes(who, col_words, max_rows, lds)) return rc;
+        const int wg_per_cu = (int)(160 * 1024 / lds);
+        resident = ctx->num_cu * (wg_per_cu < 4 ? wg_per_cu : 4);
+        return RELOC_OK;
+    }
+
+    // `workgroups` workgroups per scan with a budget of ROWS each, together the whole database (q_rec records' worth at the
+    // average record size); the caller adds the sweepers behind them, which draw until the counters are dry
+    void budget(const reloc_ctx *ctx, int workgroups)
+    {
+        const int n_ids = (int)ctx->db_records;
+        if (workgroups > n_ids) workgroups = n_ids;
+        if (workgroups < 1) workgroups = 1;
+        const int q_rec = (n_ids + workgroups - 1) / workgroups;
+        n_bounded = (n_ids + q_rec - 1) / q_rec;
+        quota = (int)((ctx->db_rows * q_rec + n_ids - 1) / n_ids);
+        if (quota < 1) quota = 1;
+    }
+};
+
+// The whole-database scan of one frame.  Records are DRAWN from per-XCD ticket counters instead of dealt round-robin, so the
+// work stays balanced to the last record, by ONE resident generation of workgroups that draws until the counters are dry:
+// the fastest form alone (152 us where one generation with row budgets takes 177: static shares leave a tail) and, since the
+// scan leaves 96 registers per lane to the kernels of other streams, beside them as well (4 streams: 6 826 frames/s against
+// 6 853 / 6 759 / 6 752 / 6 604 with 1 / 2 / 3 / 4 generations of budgets, profiles/r4_scan_generations.log; the other forms
+// dropped on the way: profiles/README.md "Dropped experiments" #4, #6).  RELOC_SCAN_GENS=n > 0 (developer switch) runs the
+// form of a batched launch instead: n generations of workgroups with row budgets and one sweeper per XCD.  The 128- and
+// 256-column kernels (their short records do not cover the draw latency) and databases that do not fill the chip are dealt
+// statically.
+int launch_db_count(reloc_ctx *ctx, const uint8_t *cur, const int32_t *n_cur_dev, int n_cur_max, int32_t *counts, const ScanMask &mask)
 {
-    if (n_ids_max <= 0) return RELOC_OK;
-    ScanMask mask;
-    mask.xyh = nullptr;
-    mask.q[0] = mask.q[1] = mask.q[2] = 0; mask.q[3] = 1;
-    if (mask_p) mask = *mask_p;
+    const int n_ids = (int)ctx->db_records;
+    if (n_ids <= 0) return RELOC_OK;
     if (n_cur_max > 65535) { reloc_set_error("db scan: more than 65535 current descriptors"); return RELOC_E_CAPACITY; }
-    if (max_rows > MAX_REC_ROWS) { reloc_set_error("db scan: record larger than %d rows", MAX_REC_ROWS); return RELOC_E_CAPACITY; }
-    if (max_rows < 1) max_rows = 1;
-    if (!m_qidx && !rec_ids && !n_ids_dev && !mask.xyh && counts && n_cur_max <= 64 && max_rows <= SQ_MAX_ROWS) {
+    if (ctx->db_max_rows > MAX_REC_ROWS) { reloc_set_error("db scan: record larger than %d rows", MAX_REC_ROWS); return RELOC_E_CAPACITY; }
+    const int max_rows = ctx->db_max_rows < 1 ? 1 : ctx->db_max_rows;
+    const uint4 *db = (const uint4 *)ctx->db_desc;
+    if (!mask.xyh && n_cur_max <= 64 && max_rows <= SQ_MAX_ROWS) {
         // few queries: lane = teach row (k_db_scan_rows)
         if (n_cur_max == 0) {                              // a capacity of zero descriptors: nothing may be read from `cur`
-            HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_ids_max * sizeof(int32_t), ctx->stream));
+            HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_ids * sizeof(int32_t), ctx->stream));
             return RELOC_OK;
         }
         int grid = ctx->num_cu * 8;                        // 8 workgroups of 4 waves per CU
-        const int need = (n_ids_max + SQ_WAVES - 1) / SQ_WAVES;
+        const int need = (n_ids + SQ_WAVES - 1) / SQ_WAVES;
         if (grid > need) grid = need;
 #define RELOC_LAUNCH_ROWS(G, HOIST)                                                                                           \
-    hipLaunchKernelGGL((k_db_scan_rows<G, HOIST>), dim3(grid), dim3(64 * SQ_WAVES), 0, ctx->stream, (const uint4 *)db_desc, db_off, n_ids_max, \
+    hipLaunchKernelGGL((k_db_scan_rows<G, HOIST>), dim3(grid), dim3(64 * SQ_WAVES), 0, ctx->stream, db, ctx->db_off, n_ids, \
                        (const uint4 *)cur, n_cur_dev, n_cur_max, counts)
         // G = queries per butterfly group: a call with 1-4 queries evaluates 4 distances per row, not 16; its query words stay in SGPRs
         if (n_cur_max <= 4) RELOC_LAUNCH_ROWS(4, true); else if (n_cur_max <= 8) RELOC_LAUNCH_ROWS(8, false); else RELOC_LAUNCH_ROWS(16, false);
@@ -1098,73 +1138,58 @@ int launch_db_scan(reloc_ctx *ctx, const uint8_t *db_desc, const int64_t *db_off
         return RELOC_OK;
     }
     const int nj = n_cur_max <= 128 ? 2 : (n_cur_max <= 256 ? 4 : 8);      // columns per lane, see k_db_scan
+    CountPlan p;
+    if (int rc = p.init(ctx, "db scan", nj, n_cur_max, max_rows)) return rc;
+    int grid = ctx->num_cu * 16;
+    u32 *ticket = nullptr;
+    if (nj == 8 && n_ids > p.resident && ctx->scan_ticket) {
+        ticket = ctx->scan_ticket;
+        grid = p.resident;
+        if (ctx->scan_gens > 0) {
+            p.budget(ctx, p.resident * ctx->scan_gens);
+            grid = p.n_bounded + 8;                                               // + one sweeper per XCD
+        }
+    }
+    if (grid > n_ids) grid = n_ids;
+#define RELOC_LAUNCH_COUNT(NJ)                                                                                               \
+    hipLaunchKernelGGL((k_db_scan<NJ, false, 4>), dim3(grid), dim3(256), p.lds, ctx->stream, db, ctx->db_off, nullptr, nullptr, n_ids, \
+                       (const uint4 *)cur, n_cur_dev, n_cur_max, max_rows, counts, nullptr, nullptr, nullptr, nullptr, 0, mask, ticket, \
+                       p.quota, p.n_bounded, p.col_words)
+    if (nj == 2) RELOC_LAUNCH_COUNT(2); else if (nj == 4) RELOC_LAUNCH_COUNT(4); else RELOC_LAUNCH_COUNT(8);
+#undef RELOC_LAUNCH_COUNT
+    HIP_TRY(hipGetLastError());
+    return RELOC_OK;
+}
+
+// Match lists of a few records, dealt statically.  One workgroup per record is alone on its CU and one wave per SIMD issues an
+// instruction only every ~7 cycles, so the record's rows are the kernel's run time.  8 waves per record take the synchronous
+// tick from 322 / 152 to 318 / 149 us (global / local) -- and the 4-stream whole-database run from 5940 to 5360 frames/s: a
+// 512-thread workgroup of this register size needs TWO scan workgroups of one CU to retire before it fits.  So: 8 waves where
+// no scan runs beside it (local-candidate ticks, single calls: ctx->latency_shapes), 4 waves in ticks that scan the database.
+int launch_db_emit(reloc_ctx *ctx, const uint8_t *db_desc, const int64_t *db_off, int max_rows, const int32_t *rec_ids,
+                   const int32_t *n_ids_dev, int n_ids_max, const uint8_t *cur, const int32_t *n_cur_dev, int n_cur_max,
+                   int32_t *m_qidx, int32_t *m_tidx, int32_t *m_dist, int32_t *m_n, int emit_stride, const ScanMask &mask)
+{
+    if (n_ids_max <= 0) return RELOC_OK;
+    if (n_cur_max > 65535) { reloc_set_error("db scan: more than 65535 current descriptors"); return RELOC_E_CAPACITY; }
+    if (max_rows > MAX_REC_ROWS) { reloc_set_error("db scan: record larger than %d rows", MAX_REC_ROWS); return RELOC_E_CAPACITY; }
+    if (max_rows < 1) max_rows = 1;
+    const int nj = n_cur_max <= 128 ? 2 : (n_cur_max <= 256 ? 4 : 8);      // columns per lane, see k_db_scan
     const int cb = 64 * nj;
     const int ncb = (n_cur_max + cb - 1) / cb > 0 ? (n_cur_max + cb - 1) / cb : 1;
-    // column minima: one buffer for the capacity; the counting scan double-buffers inside it when the run-time count leaves room
-    // (db_count_body), so at least two column blocks
-    const int col_words = (m_qidx || ncb >= 2 ? ncb : 2) * cb;
-    const size_t lds = (size_t)(col_words + max_rows + 16) * 4;
-    if (lds > 160 * 1024) { reloc_set_error("db scan: LDS demand %zu bytes", lds); return RELOC_E_CAPACITY; }
-    // Whole-database scans (host-known record count, more records than resident workgroups): workgroups DRAW their records
-    // from per-XCD ticket counters instead of a static round-robin deal, so the work stays balanced to the last record.  One
-    // resident generation that lives as long as the launch is the fastest form alone but starves the other streams of a
-    // multi-context run, so beside other streams a workgroup serves a budget and leaves: the grid holds THREE generations (the
-    // small kernels run at wave priority 3, RELOC_SMALL_KERNEL_PRIO, and need few free slots); reloc_set_exclusive / a process's
-    // only context selects the one-generation form.  Candidate lists, single records and the 128-column kernel (its short
-    // records do not cover the draw latency) are dealt statically.  Measurements behind each choice: profiles/README.md
-    // "Dropped experiments" #6.
-    // Waves per record of the counting scan (NW): 4 waves share a record's rows (finest grain: shortest tail of the launch),
-    // or 2, or ONE wave owns a record (no row left for a second chunk epilogue, no barrier that waits for anybody).
-    int nw = 4;
-    if (!m_qidx && nj == 8) {
-        nw = ctx->scan_nw == 1 || ctx->scan_nw == 2 || ctx->scan_nw == 4 ? ctx->scan_nw : 4;      // (8: 180 vs 152 us, profiles/r4_scan_intercept.log)
-        if (nw == 1 && lds * 16 > 150 * 1024) nw = 2;          // 16 one-wave workgroups per CU have to fit their LDS
-    }
-    int wg_per_cu = 16 / nw;                       // 16 waves per CU (128-VGPR kernel) ...
-    if ((size_t)wg_per_cu * lds > 160 * 1024) wg_per_cu = (int)(160 * 1024 / lds);     // ... unless their LDS does not fit
-    const int resident = ctx->num_cu * wg_per_cu;
-    int grid = ctx->scan_grid > 0 ? ctx->scan_grid : ctx->num_cu * 16;    // RELOC_SCAN_GRID: developer switch, read at creation
-    u32 *ticket = nullptr;
-    int quota = 0, n_bounded = 0;
-    if (!rec_ids && !n_ids_dev && n_ids_max > resident && ctx->scan_ticket && ctx->scan_grid >= 0 && nj == 8) {
-        ticket = ctx->scan_ticket;
-        const int gens = ctx->scan_gens > 0 ? ctx->scan_gens : (RELOC_SCAN_GENS_SHARED > 0 ? RELOC_SCAN_GENS_SHARED : 1);
-        // `gens` generations of workgroups: all but the last resident one leave after their share of the database's ROWS, the
-        // last generation draws until the counters are dry (see db_count_body); the row total is the host's when the
-        // context's own database is scanned, else 64 per record
-        const int q_rec = (n_ids_max + resident * gens - 1) / (resident * gens);          // records per workgroup at the average size
-        n_bounded = (n_ids_max + q_rec - 1) / q_rec;                                      // workgroups x q_rec >= records
-        grid = n_bounded + 8 < n_ids_max ? n_bounded + 8 : n_ids_max;                     // + one sweeper per XCD
-        const int64_t rows = db_desc == ctx->db_desc && ctx->db_rows > 0 ? ctx->db_rows : (int64_t)n_ids_max * 64;
-        quota = (int)((rows * q_rec + n_ids_max - 1) / n_ids_max);                        // that many records' worth of ROWS
-        if (quota < 1) quota = 1;
-        if (!ctx->scan_quota_rows) { quota = q_rec; grid = n_bounded; n_bounded = -1; }   // developer switch: the record quota of rounds 2-3a
-        // ONE resident generation that draws until the counters are dry: always for a context that is alone (reloc_set_exclusive:
-        // nobody to hand slots to), and since round 4 beside other streams as well (RELOC_SCAN_GENS_SHARED == 0, reloc_internal.h)
-        if ((ctx_alone(ctx) || RELOC_SCAN_GENS_SHARED == 0) && ctx->scan_gens == 0) { quota = 0; grid = resident; }
-        if (ctx->scan_gens < 0) { quota = 0; grid = ctx->scan_gens <= -2 ? ctx->num_cu * (-ctx->scan_gens - 1) : resident; }   // developer switch: one generation, no quota; -2 / -3 / -4: 1 / 2 / 3 workgroups per CU
-    }
-    if (grid > n_ids_max) grid = n_ids_max;
-    // Match lists of a few candidate records (the tick's emit pass, reloc_match_mutual): one workgroup per record is
-    // alone on its CU and one wave per SIMD issues an instruction only every ~7 cycles, so the record's rows are the
-    // kernel's run time.  8 waves per record take the synchronous tick from 322 / 152 to 318 / 149 us (global / local) --
-    // and the 4-stream whole-database run from 5940 to 5360 frames/s: a 512-thread workgroup of this register size needs
-    // TWO scan workgroups of one CU to retire before it fits.  So: 8 waves where no scan runs beside it (local-candidate
-    // ticks, single calls: ctx->latency_shapes), 4 waves in ticks that scan the database.
-#define RELOC_LAUNCH_SCAN(NJ, EMIT, NW)                                                                                      \
-    hipLaunchKernelGGL((k_db_scan<NJ, EMIT, NW>), dim3(grid), dim3(64 * NW), lds, ctx->stream, (const uint4 *)db_desc, db_off, rec_ids, \
-                       n_ids_dev, n_ids_max, (const uint4 *)cur, n_cur_dev, n_cur_max, max_rows, counts, m_qidx, m_tidx, m_dist, \
-                       m_n, emit_stride, mask, ticket, quota, n_bounded, col_words)
-    if (m_qidx && ctx->latency_shapes) {
-        if (nj == 2) RELOC_LAUNCH_SCAN(2, true, 8); else if (nj == 4) RELOC_LAUNCH_SCAN(4, true, 8); else RELOC_LAUNCH_SCAN(8, true, 8);
-    } else if (m_qidx) {
-        if (nj == 2) RELOC_LAUNCH_SCAN(2, true, 4); else if (nj == 4) RELOC_LAUNCH_SCAN(4, true, 4); else RELOC_LAUNCH_SCAN(8, true, 4);
-    } else if (nj == 8) {
-        if (nw == 1) RELOC_LAUNCH_SCAN(8, false, 1); else if (nw == 2) RELOC_LAUNCH_SCAN(8, false, 2); else RELOC_LAUNCH_SCAN(8, false, 4);
+    size_t lds;
+    if (int rc = scan_lds_bytes("db scan", ncb * cb, max_rows, lds)) return rc;
+    const int grid = n_ids_max < ctx->num_cu * 16 ? n_ids_max : ctx->num_cu * 16;
+#define RELOC_LAUNCH_EMIT(NJ, NW)                                                                                            \
+    hipLaunchKernelGGL((k_db_scan<NJ, true, NW>), dim3(grid), dim3(64 * NW), lds, ctx->stream, (const uint4 *)db_desc, db_off, rec_ids, \
+                       n_ids_dev, n_ids_max, (const uint4 *)cur, n_cur_dev, n_cur_max, max_rows, nullptr, m_qidx, m_tidx, m_dist, \
+                       m_n, emit_stride, mask, nullptr, 0, 0, ncb * cb)
+    if (ctx->latency_shapes) {
+        if (nj == 2) RELOC_LAUNCH_EMIT(2, 8); else if (nj == 4) RELOC_LAUNCH_EMIT(4, 8); else RELOC_LAUNCH_EMIT(8, 8);
     } else {
-        if (nj == 2) RELOC_LAUNCH_SCAN(2, false, 4); else RELOC_LAUNCH_SCAN(4, false, 4);
+        if (nj == 2) RELOC_LAUNCH_EMIT(2, 4); else if (nj == 4) RELOC_LAUNCH_EMIT(4, 4); else RELOC_LAUNCH_EMIT(8, 4);
     }
-#undef RELOC_LAUNCH_SCAN
+#undef RELOC_LAUNCH_EMIT
     HIP_TRY(hipGetLastError());
     return RELOC_OK;
 }
@@ -1177,6 +1202,10 @@ int launch_db_scan_batch(reloc_ctx *const *ctxs, int n, const double *q, double 
     reloc_ctx *c0 = ctxs[0];
     if (n < 1 || n > SCAN_BATCH_MAX) { reloc_set_error("scan batch: 1..%d frames", SCAN_BATCH_MAX); return RELOC_E_ARG; }
     if (c0->max_feat > 65535 || c0->db_max_rows > MAX_REC_ROWS) { reloc_set_error("scan batch: capacity"); return RELOC_E_CAPACITY; }
+    const int n_ids = (int)c0->db_records, max_rows = c0->db_max_rows < 1 ? 1 : c0->db_max_rows;
+    // n_cur_max = the feature capacity; the 8-column kernel walks column blocks of 512 (one block for nfeatures <= 512)
+    CountPlan p;
+    if (int rc = p.init(c0, "scan batch", 8, c0->max_feat, max_rows)) return rc;
     ScanBatch bt;
     bt.n = n;
     bt.xyh = heading_mask ? c0->db_xy_heading : nullptr;
@@ -1187,31 +1216,13 @@ int launch_db_scan_batch(reloc_ctx *const *ctxs, int n, const double *q, double 
         bt.skip_if[f] = auto_mode ? c->cand_n : nullptr;
         for (int k = 0; k < 4; ++k) bt.q[f][k] = q[4 * (f < n ? f : 0) + k];
     }
-    const int n_ids = (int)c0->db_records, max_rows = c0->db_max_rows < 1 ? 1 : c0->db_max_rows;
-    // n_cur_max = the feature capacity; the 8-column kernel walks column blocks of 512 (one block for nfeatures <= 512)
-    const int ncb = (c0->max_feat + 511) / 512;
-    const int col_words = (ncb >= 2 ? ncb : 2) * 512;         // see launch_db_scan
-    const size_t lds_all = (size_t)(col_words + max_rows + 16) * 4;
-    int gens = c0->scan_gens > 0 ? c0->scan_gens : (RELOC_SCAN_GENS_SHARED > 0 ? RELOC_SCAN_GENS_SHARED : 1);
-    if (c0->scan_batch_gens > 0) gens = c0->scan_batch_gens;
-    const int resident = c0->num_cu * 4;
-    // the grid holds `gens` generations in all (not per frame): a workgroup's quota grows with the batch, and with it
-    // the share of the launch that is not prologue
-    int per_frame = (resident * gens + n - 1) / n;
-    if (per_frame > n_ids) per_frame = n_ids;
-    if (per_frame < 1) per_frame = 1;
-    // per frame: per_frame workgroups with a row budget (together: the whole database) + one sweeper behind them that draws
-    // until the counters are dry (db_count_body)
-    const int q_rec = (n_ids + per_frame - 1) / per_frame;                           // records per workgroup at the average size
-    const int n_bounded = (n_ids + q_rec - 1) / q_rec;
-    int quota = (int)(((c0->db_rows > 0 ? c0->db_rows : (int64_t)n_ids * 64) * q_rec + n_ids - 1) / n_ids);   // in ROWS
-    if (quota < 1) quota = 1;
-    per_frame = n_bounded + 1;                                                       // + one sweeper per frame
-    if (per_frame > n_ids) per_frame = n_ids;
-    int nb_arg = n_bounded;
-    if (!c0->scan_quota_rows) { quota = q_rec; per_frame = n_bounded; nb_arg = -1; }
-    hipLaunchKernelGGL(k_db_scan_batch, dim3(per_frame * n), dim3(256), lds_all, c0->stream, (const uint4 *)c0->db_desc, c0->db_off,
-                       n_ids, c0->max_feat, max_rows, bt, c0->scan_ticket, quota, nb_arg, col_words);
+    // `gens` generations in all (not per frame): a workgroup's budget grows with the batch, and with it the share of the
+    // launch that is not prologue.  Per frame: the budgeted workgroups + one sweeper behind them
+    const int gens = c0->scan_gens > 0 ? c0->scan_gens : 1;
+    p.budget(c0, (p.resident * gens + n - 1) / n);
+    const int per_frame = p.n_bounded + 1 < n_ids ? p.n_bounded + 1 : n_ids;
+    hipLaunchKernelGGL(k_db_scan_batch, dim3(per_frame * n), dim3(256), p.lds, c0->stream, (const uint4 *)c0->db_desc, c0->db_off,
+                       n_ids, c0->max_feat, max_rows, bt, c0->scan_ticket, p.quota, p.n_bounded, p.col_words);
     HIP_TRY(hipGetLastError());
     return RELOC_OK;
 }
@@ -1495,8 +1506,7 @@ RELOC_API int reloc_match_mutual(reloc_ctx *ctx, const uint8_t *q, int nq, const
     HIP_TRY(hipMemcpyAsync(dq, q, (size_t)nq * 32, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(dt, t, (size_t)nt * 32, hipMemcpyHostToDevice, ctx->stream));
     ctx->latency_shapes = true;                               // a single record, nothing runs beside it: 8 waves
-    rc = launch_db_scan(ctx, (const uint8_t *)dq, doff, 1, nullptr, nullptr, 1, (const uint8_t *)dt, nullptr, nt,
-                        nq, nullptr, dqi, dti, ddi, dn, nq);
+    rc = launch_db_emit(ctx, (const uint8_t *)dq, doff, nq, nullptr, nullptr, 1, (const uint8_t *)dt, nullptr, nt, dqi, dti, ddi, dn, nq);
     ctx->latency_shapes = false;
     if (rc) return rc;
     int32_t n = 0;
@@ -1850,8 +1860,7 @@ RELOC_API int reloc_db_match_counts_dev(reloc_ctx *ctx, const uint8_t *cur_dev, 
     ARG_CHECK_CTX(ctx, cur_dev && counts_dev && n_cur_max >= 0, "reloc_db_match_counts_dev");
     if (!db_ready(ctx)) { reloc_set_error("no database uploaded"); return RELOC_E_STATE; }
     reloc_prof_begin(ctx, RELOC_PROF_DB_SCAN);
-    int rc = launch_db_scan(ctx, ctx->db_desc, ctx->db_off, ctx->db_records, nullptr, nullptr, (int)ctx->db_records, cur_dev,
-                            n_cur_dev, n_cur_max, ctx->db_max_rows, counts_dev, nullptr, nullptr, nullptr, nullptr, 0);
+    int rc = launch_db_count(ctx, cur_dev, n_cur_dev, n_cur_max, counts_dev);
     reloc_prof_end(ctx, RELOC_PROF_DB_SCAN);
 
     return rc;

@@ -624,14 +624,11 @@ static int tick_solve(reloc_ctx *ctx, const TickParams &prm, uint64_t seed)
     hipStream_t st = ctx->stream;
     // mutual matches of every candidate, in queryIdx order, with their 3-D / 2-D pairs (M:333-336)
     ScanMask emit;
-    emit.xyh = nullptr;
-    emit.q[0] = emit.q[1] = emit.q[2] = 0; emit.q[3] = 1;
     emit.g_pts3d = ctx->db_pts3d; emit.g_xy = ctx->f_xy; emit.g_obj = ctx->p_obj; emit.g_img = ctx->p_img;
     // a tick of local candidates runs no whole-database scan: its emit pass and refinement are sized for latency
     ctx->latency_shapes = prm.mode == RELOC_TICK_LOCAL || ctx_alone(ctx);
-    rc = launch_db_scan(ctx, ctx->db_desc, ctx->db_off, ctx->db_records, ctx->cand_ids, ctx->cand_n, MAX_CAND,
-                        ctx->f_desc, ctx->f_count, ctx->max_feat, ctx->db_max_rows, nullptr, ctx->m_qidx, ctx->m_tidx,
-                        ctx->m_dist, ctx->m_n, MAX_REC_ROWS, &emit);
+    rc = launch_db_emit(ctx, ctx->db_desc, ctx->db_off, ctx->db_max_rows, ctx->cand_ids, ctx->cand_n, MAX_CAND, ctx->f_desc,
+                        ctx->f_count, ctx->max_feat, ctx->m_qidx, ctx->m_tidx, ctx->m_dist, ctx->m_n, MAX_REC_ROWS, emit);
     if (!rc)
         rc = pnp_run_candidates(ctx, MAX_CAND, ctx->cand_n, ctx->K4, ctx->prm.ransac_iterations, (float)ctx->prm.ransac_reproj_px,
                                 ctx->prm.ransac_confidence, seed, ctx->prm.min_matches, ctx->tick_flags, ctx->prm.min_inliers,
@@ -703,9 +700,7 @@ static int tick_scan_single(reloc_ctx *ctx, const TickParams &prm)
     mask.cos_tol = prm.cos_tol;
     mask.skip_if = prm.mode == RELOC_TICK_AUTO ? ctx->cand_n : nullptr;
     reloc_prof_begin(ctx, RELOC_PROF_DB_SCAN);
-    const int rc = launch_db_scan(ctx, ctx->db_desc, ctx->db_off, ctx->db_records, nullptr, nullptr, (int)ctx->db_records, ctx->f_desc,
-                                  ctx->f_count, ctx->max_feat, ctx->db_max_rows, ctx->db_counts, nullptr, nullptr, nullptr, nullptr, 0,
-                                  &mask);
+    const int rc = launch_db_count(ctx, ctx->f_desc, ctx->f_count, ctx->max_feat, ctx->db_counts, mask);
     reloc_prof_end(ctx, RELOC_PROF_DB_SCAN);
     return rc;
 }
@@ -917,12 +912,13 @@ RELOC_API int reloc_tick_scan_dev(reloc_ctx *ctx, const uint8_t *img_dev, int w,
     ctx->orb_latency_shape = true;
     if (rc) return rc;
     ScanMask mask;
-    mask.xyh = base_pose ? ctx->db_xy_heading : nullptr;
-    for (int k = 0; k < 4; ++k) mask.q[k] = base_pose ? base_pose[3 + k] : (k == 3 ? 1.0 : 0.0);
+    if (base_pose) {
+        mask.xyh = ctx->db_xy_heading;
+        for (int k = 0; k < 4; ++k) mask.q[k] = base_pose[3 + k];
+    }
     mask.cos_tol = heading_cos_tol_host(ctx);
     reloc_prof_begin(ctx, RELOC_PROF_DB_SCAN);
-    rc = launch_db_scan(ctx, ctx->db_desc, ctx->db_off, ctx->db_records, nullptr, nullptr, (int)ctx->db_records, ctx->f_desc,
-                        ctx->f_count, ctx->max_feat, ctx->db_max_rows, ctx->db_counts, nullptr, nullptr, nullptr, nullptr, 0, &mask);
+    rc = launch_db_count(ctx, ctx->f_desc, ctx->f_count, ctx->max_feat, ctx->db_counts, mask);
     reloc_prof_end(ctx, RELOC_PROF_DB_SCAN);
     if (rc) return rc;
     launch_topk_counts(ctx, k, topk_ids_dev, topk_counts_dev, false);

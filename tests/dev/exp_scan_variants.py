@@ -61,7 +61,6 @@ if __name__ == "__main__":
         libs = sys.argv[1:] or [os.path.join(ROOT, "nclt-slam-project_amd", "csrc", "libreloc_hip.so")] + \
             sorted(glob.glob(os.path.join(ROOT, "build_variants", "*.so")))
         for lib in libs:
-            for grid in os.environ.get("EXP_GRIDS", "0").split(","):        # RELOC_SCAN_GRID values: 0 ticket, -1 static default
-                env = dict(os.environ, RELOC_DEV="1", RELOC_LIB=os.path.abspath(lib), RELOC_SCAN_GRID=grid)
-                print(json.dumps(dict(lib=os.path.basename(lib), RELOC_SCAN_GRID=grid)), flush=True)
-                subprocess.run([sys.executable, os.path.abspath(__file__), "--one", lib], env=env, timeout=600)
+            env = dict(os.environ, RELOC_DEV="1", RELOC_LIB=os.path.abspath(lib))
+            print(json.dumps(dict(lib=os.path.basename(lib))), flush=True)
+            subprocess.run([sys.executable, os.path.abspath(__file__), "--one", lib], env=env, timeout=600)
