@@ -367,9 +367,6 @@ struct reloc_ctx {
     PnpOut *p_out = nullptr;         // MAX_CAND
     int exclusive_hint = -1;         // reloc_set_exclusive: 1 = this ctx is the only stream of work on the GPU, 0 = it is not,
                                      // -1 (default) = it is while it is the only live context of this process (ctx_alone())
-    bool orb_latency_shape = true;   // k_pyramid with 512-thread workgroups; cleared by ticks that share the chip with scans
-    bool latency_shapes = false;     // set around the emit pass / PnP of a tick that runs NO whole-database scan (and by the
-                                     // single-call entry points): kernels sized for latency instead of for fitting beside a scan
     bool local_two_stage = false;    // developer switch RELOC_LOCAL_TWO_STAGE=1: local candidates by k_topk_part + k_candidates_local
     TickResult *tick_res = nullptr;  // 1
     TickResult *tick_res_host = nullptr;   // the same record in pinned host memory, written by k_tick_finalize
@@ -391,28 +388,36 @@ static inline bool ctx_alone(const reloc_ctx *c)
     return c->exclusive_hint > 0 || (c->exclusive_hint < 0 && __atomic_load_n(&g_reloc_live_contexts, __ATOMIC_RELAXED) == 1);
 }
 
-// launchers shared between translation units (reloc_match.hip).  The whole-database scans count the mutual matches of the
-// current descriptors (cur, n_cur_max capacity, count on the device at n_cur_dev when non-NULL) with every record of the
-// context's database into counts[record]: one frame (launch_db_count) or one per context of a batch (launch_db_scan_batch).
-// launch_db_emit writes the match lists (emit_stride apart) of the listed records (n_ids_max capacity, count on the device
-// at n_ids_dev when non-NULL) or, with rec_ids == NULL, of records 0..n_ids_max-1 of db_desc / db_off.
+// Stage launchers shared between translation units.  Each takes the n <= RELOC_BATCH_MAX contexts of one call (one stream,
+// equal geometry, parameters and database: ctx_batch_check in reloc_tick.hip) and makes ONE launch per kernel of its stage:
+// at n == 1 the pointer-argument kernel with frame 0's buffers, at n > 1 the frame-table kernel (*_batch, blockIdx = frame).
+// latency: kernels sized for latency instead of for fitting beside another stream's whole-database scan (512-thread
+// pyramid, 8-wave emit pass, unconstrained k_pnp_finish); only a single frame (n == 1) ever gets them.
+constexpr int RELOC_BATCH_MAX = 8;          // frames per batched launch (reloc_tick_batch_dev, reloc_shard_*_batch_dev)
+
+// Visits the RELOC_BATCH_MAX slots of a frame table: fn(slot, ctx, frame) with frame = slot for the n frames of the call and
+// frame 0 for the padding slots (never read: the grid holds n frames).
+template <typename Fn>
+static inline void frame_slots(reloc_ctx *const *ctxs, int n, Fn fn)
+{
+    for (int f = 0; f < RELOC_BATCH_MAX; ++f) fn(f, ctxs[f < n ? f : 0], f < n ? f : 0);
+}
+
+// The whole-database scans count the mutual matches of the current descriptors (cur, n_cur_max capacity, count on the
+// device at n_cur_dev when non-NULL) with every record of the context's database into counts[record]: one frame
+// (launch_db_count) or one per context of a batch (launch_db_scan_batch).
 int launch_db_count(reloc_ctx *ctx, const uint8_t *cur, const int32_t *n_cur_dev, int n_cur_max, int32_t *counts,
                     const ScanMask &mask = {});
-int launch_db_emit(reloc_ctx *ctx, const uint8_t *db_desc, const int64_t *db_off, int max_rows, const int32_t *rec_ids,
-                   const int32_t *n_ids_dev, int n_ids_max, const uint8_t *cur, const int32_t *n_cur_dev, int n_cur_max,
-                   int32_t *m_qidx, int32_t *m_tidx, int32_t *m_dist, int32_t *m_n, int emit_stride, const ScanMask &mask = {});
-int launch_db_emit_batch(reloc_ctx *const *ctxs, int n);
 int launch_db_scan_batch(reloc_ctx *const *ctxs, int n, const double *q, double cos_tol, bool auto_mode, bool heading_mask = true);
+// the emit pass of a tick: match lists, with their 3-D / 2-D pairs, of every context's candidate records (reloc_match.hip)
+int launch_tick_emit(reloc_ctx *const *ctxs, int n, bool latency);
 int db_reindex(reloc_ctx *ctx);
 int db_reserve(reloc_ctx *ctx, int64_t cap_records, int64_t cap_rows);
 inline bool db_ready(const reloc_ctx *ctx) { return ctx->db_desc && ctx->db_off && ctx->db_pose && ctx->db_xy_heading && ctx->db_counts && ctx->db_records > 0; }
 int orb_prepare(reloc_ctx *ctx, int w, int h, int nfeatures);
-constexpr int RELOC_BATCH_MAX = 8;          // frames per batched launch (reloc_tick_batch_dev, reloc_shard_*_batch_dev)
-int orb_run_batch_dev(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs_dev, int w, int h, int stride, int order, int nfeatures);
-int orb_run_dev(reloc_ctx *ctx, const uint8_t *src_dev, int w, int h, int stride, int channels, int order,
-                int nfeatures);
-int pnp_run_candidates_batch(reloc_ctx *const *ctxs, int n, int n_cand_max, const uint64_t *seeds);
-// dist: k1 k2 p1 p2 k3, or NULL for the pinhole kernels (the caller passes NULL when every coefficient is zero)
-int pnp_run_candidates(reloc_ctx *ctx, int n_cand_max, const int32_t *n_cand_dev, const double K4[4], int iters,
-                       float thr_px, double conf, uint64_t seed, int min_m, const int32_t *relocating_dev, int gate_local, int gate_global,
-                       const double *dist = nullptr);
+// ORB of frame f = srcs[f] into ctxs[f]'s feature buffers; channels == 3 -> interleaved frames (gray fused, CLAHE first when
+// the contexts have it on), channels == 1 -> gray planes (reloc_orb.hip)
+int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, int h, int stride, int channels, int order,
+            int nfeatures, bool latency);
+// PnP-RANSAC of every context's candidates with the matcher parameters of ctxs[0]; seeds: one per frame, or NULL (reloc_pnp.hip)
+int pnp_run_candidates(reloc_ctx *const *ctxs, int n, const uint64_t *seeds, bool latency);

@@ -662,6 +662,14 @@ struct EmitFrame {
     int32_t *m_qidx, *m_tidx, *m_dist, *m_n; const float *g_xy; float *g_obj, *g_img;
 };
 struct EmitBatch { EmitFrame f[RELOC_BATCH_MAX]; };
+// what the emit pass of a tick reads and writes of a context: its candidates against its features, match lists and pairs
+static EmitFrame emit_frame(const reloc_ctx *c)
+{
+    EmitFrame F;
+    F.rec_ids = c->cand_ids; F.n_ids_p = c->cand_n; F.cur = (const uint4 *)c->f_desc; F.n_cur_p = c->f_count;
+    F.m_qidx = c->m_qidx; F.m_tidx = c->m_tidx; F.m_dist = c->m_dist; F.m_n = c->m_n; F.g_xy = c->f_xy; F.g_obj = c->p_obj; F.g_img = c->p_img;
+    return F;
+}
 
 __global__ __launch_bounds__(256, 4) RELOC_SCAN_VGPR_ATTR void k_db_emit_batch(const uint4 *__restrict__ db, const int64_t *__restrict__ off, int n_ids_max,
                                                           int n_cur_max, int max_rows, int emit_stride, const float *__restrict__ g_pts3d,
@@ -685,39 +693,17 @@ static int scan_lds_bytes(const char *who, int col_words, int max_rows, size_t &
     return RELOC_OK;
 }
 
-int launch_db_emit_batch(reloc_ctx *const *ctxs, int n)
-{
-    reloc_ctx *c0 = ctxs[0];
-    if (n < 1 || n > RELOC_BATCH_MAX) { reloc_set_error("emit batch: 1..%d frames", RELOC_BATCH_MAX); return RELOC_E_ARG; }
-    if (c0->max_feat > 65535 || c0->db_max_rows > MAX_REC_ROWS) { reloc_set_error("emit batch: capacity"); return RELOC_E_CAPACITY; }
-    EmitBatch bt;
-    for (int f = 0; f < RELOC_BATCH_MAX; ++f) {
-        reloc_ctx *c = ctxs[f < n ? f : 0];
-        EmitFrame &F = bt.f[f];
-        F.rec_ids = c->cand_ids; F.n_ids_p = c->cand_n; F.cur = (const uint4 *)c->f_desc; F.n_cur_p = c->f_count;
-        F.m_qidx = c->m_qidx; F.m_tidx = c->m_tidx; F.m_dist = c->m_dist; F.m_n = c->m_n; F.g_xy = c->f_xy; F.g_obj = c->p_obj; F.g_img = c->p_img;
-    }
-    const int max_rows = c0->db_max_rows < 1 ? 1 : c0->db_max_rows;
-    size_t lds;
-    if (int rc = scan_lds_bytes("emit batch", (c0->max_feat + 511) / 512 * 512, max_rows, lds)) return rc;
-    hipLaunchKernelGGL(k_db_emit_batch, dim3(MAX_CAND, n), dim3(256), lds, c0->stream, (const uint4 *)c0->db_desc, c0->db_off, MAX_CAND,
-                       c0->max_feat, max_rows, MAX_REC_ROWS, c0->db_pts3d, bt);
-    HIP_TRY(hipGetLastError());
-    return RELOC_OK;
-}
-
 // Several frames in ONE launch (BASELINE.json config 4: batched relocalization): workgroup b scans frame b % B -- its
 // current descriptors, feature count, counts array, heading and ticket counters -- so B whole-database scans share one
 // launch: the launch-fixed cost (descriptor prologue per workgroup, last-record tail, kernel boundary) is paid once per
 // batch, and the deal stays dynamic per frame.  Frames whose local search found candidates (AUTO mode) stand down alone.
-constexpr int SCAN_BATCH_MAX = 8;
 struct ScanBatch {
     int n;
-    const uint4 *cur[SCAN_BATCH_MAX];
-    const int32_t *n_cur[SCAN_BATCH_MAX];
-    int32_t *counts[SCAN_BATCH_MAX];
-    const int32_t *skip_if[SCAN_BATCH_MAX];
-    double q[SCAN_BATCH_MAX][4];
+    const uint4 *cur[RELOC_BATCH_MAX];
+    const int32_t *n_cur[RELOC_BATCH_MAX];
+    int32_t *counts[RELOC_BATCH_MAX];
+    const int32_t *skip_if[RELOC_BATCH_MAX];
+    double q[RELOC_BATCH_MAX][4];
     const double *xyh;
     double cos_tol;
 };
@@ -1165,33 +1151,54 @@ int launch_db_count(reloc_ctx *ctx, const uint8_t *cur, const int32_t *n_cur_dev
 // instruction only every ~7 cycles, so the record's rows are the kernel's run time.  8 waves per record take the synchronous
 // tick from 322 / 152 to 318 / 149 us (global / local) -- and the 4-stream whole-database run from 5940 to 5360 frames/s: a
 // 512-thread workgroup of this register size needs TWO scan workgroups of one CU to retire before it fits.  So: 8 waves where
-// no scan runs beside it (local-candidate ticks, single calls: ctx->latency_shapes), 4 waves in ticks that scan the database.
-int launch_db_emit(reloc_ctx *ctx, const uint8_t *db_desc, const int64_t *db_off, int max_rows, const int32_t *rec_ids,
-                   const int32_t *n_ids_dev, int n_ids_max, const uint8_t *cur, const int32_t *n_cur_dev, int n_cur_max,
-                   int32_t *m_qidx, int32_t *m_tidx, int32_t *m_dist, int32_t *m_n, int emit_stride, const ScanMask &mask)
+// no scan runs beside it (latency: local-candidate ticks, single calls), 4 waves in ticks that scan the database.
+// Frame f lists the records rec_ids (n_ids_max capacity, count on the device at n_ids_p when non-NULL; rec_ids == NULL:
+// records 0..n_ids_max-1) of the database db_desc / db_off against its current descriptors (n_cur_max capacity), emit_stride
+// apart; with g_pts3d set every match also leaves its 3-D / 2-D pair (ScanMask).  A batch runs the 8-column kernel.
+static int launch_db_emit(reloc_ctx *const *ctxs, int n, const EmitBatch &bt, const uint8_t *db_desc, const int64_t *db_off,
+                          int max_rows, const float *g_pts3d, int n_ids_max, int n_cur_max, int emit_stride, bool latency)
 {
+    reloc_ctx *c0 = ctxs[0];
+    if (n < 1 || n > RELOC_BATCH_MAX) { reloc_set_error("emit: 1..%d frames", RELOC_BATCH_MAX); return RELOC_E_ARG; }
     if (n_ids_max <= 0) return RELOC_OK;
     if (n_cur_max > 65535) { reloc_set_error("db scan: more than 65535 current descriptors"); return RELOC_E_CAPACITY; }
     if (max_rows > MAX_REC_ROWS) { reloc_set_error("db scan: record larger than %d rows", MAX_REC_ROWS); return RELOC_E_CAPACITY; }
     if (max_rows < 1) max_rows = 1;
-    const int nj = n_cur_max <= 128 ? 2 : (n_cur_max <= 256 ? 4 : 8);      // columns per lane, see k_db_scan
+    const int nj = n > 1 || n_cur_max > 256 ? 8 : (n_cur_max <= 128 ? 2 : 4);      // columns per lane, see k_db_scan
     const int cb = 64 * nj;
     const int ncb = (n_cur_max + cb - 1) / cb > 0 ? (n_cur_max + cb - 1) / cb : 1;
     size_t lds;
     if (int rc = scan_lds_bytes("db scan", ncb * cb, max_rows, lds)) return rc;
-    const int grid = n_ids_max < ctx->num_cu * 16 ? n_ids_max : ctx->num_cu * 16;
+    const int grid = n_ids_max < c0->num_cu * 16 ? n_ids_max : c0->num_cu * 16;
+    if (n == 1) {
+        const EmitFrame &F = bt.f[0];
+        ScanMask mask;
+        mask.g_pts3d = g_pts3d; mask.g_xy = F.g_xy; mask.g_obj = F.g_obj; mask.g_img = F.g_img;
 #define RELOC_LAUNCH_EMIT(NJ, NW)                                                                                            \
-    hipLaunchKernelGGL((k_db_scan<NJ, true, NW>), dim3(grid), dim3(64 * NW), lds, ctx->stream, (const uint4 *)db_desc, db_off, rec_ids, \
-                       n_ids_dev, n_ids_max, (const uint4 *)cur, n_cur_dev, n_cur_max, max_rows, nullptr, m_qidx, m_tidx, m_dist, \
-                       m_n, emit_stride, mask, nullptr, 0, 0, ncb * cb)
-    if (ctx->latency_shapes) {
-        if (nj == 2) RELOC_LAUNCH_EMIT(2, 8); else if (nj == 4) RELOC_LAUNCH_EMIT(4, 8); else RELOC_LAUNCH_EMIT(8, 8);
-    } else {
-        if (nj == 2) RELOC_LAUNCH_EMIT(2, 4); else if (nj == 4) RELOC_LAUNCH_EMIT(4, 4); else RELOC_LAUNCH_EMIT(8, 4);
-    }
+    hipLaunchKernelGGL((k_db_scan<NJ, true, NW>), dim3(grid), dim3(64 * NW), lds, c0->stream, (const uint4 *)db_desc, db_off, F.rec_ids, \
+                       F.n_ids_p, n_ids_max, F.cur, F.n_cur_p, n_cur_max, max_rows, nullptr, F.m_qidx, F.m_tidx, F.m_dist, F.m_n,  \
+                       emit_stride, mask, nullptr, 0, 0, ncb * cb)
+        if (latency) {
+            if (nj == 2) RELOC_LAUNCH_EMIT(2, 8); else if (nj == 4) RELOC_LAUNCH_EMIT(4, 8); else RELOC_LAUNCH_EMIT(8, 8);
+        } else {
+            if (nj == 2) RELOC_LAUNCH_EMIT(2, 4); else if (nj == 4) RELOC_LAUNCH_EMIT(4, 4); else RELOC_LAUNCH_EMIT(8, 4);
+        }
 #undef RELOC_LAUNCH_EMIT
+    } else {
+        hipLaunchKernelGGL(k_db_emit_batch, dim3(grid, n), dim3(256), lds, c0->stream, (const uint4 *)db_desc, db_off, n_ids_max,
+                           n_cur_max, max_rows, emit_stride, g_pts3d, bt);
+    }
     HIP_TRY(hipGetLastError());
     return RELOC_OK;
+}
+
+int launch_tick_emit(reloc_ctx *const *ctxs, int n, bool latency)
+{
+    reloc_ctx *c0 = ctxs[0];
+    EmitBatch bt;
+    frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int) { bt.f[f] = emit_frame(c); });
+    return launch_db_emit(ctxs, n, bt, c0->db_desc, c0->db_off, c0->db_max_rows, c0->db_pts3d, MAX_CAND, c0->max_feat, MAX_REC_ROWS,
+                          latency);
 }
 
 // One launch for the whole-database scans of n contexts that share a stream and a database (ctxs[0]'s is scanned):
@@ -1200,7 +1207,7 @@ int launch_db_emit(reloc_ctx *ctx, const uint8_t *db_desc, const int64_t *db_off
 int launch_db_scan_batch(reloc_ctx *const *ctxs, int n, const double *q, double cos_tol, bool auto_mode, bool heading_mask)
 {
     reloc_ctx *c0 = ctxs[0];
-    if (n < 1 || n > SCAN_BATCH_MAX) { reloc_set_error("scan batch: 1..%d frames", SCAN_BATCH_MAX); return RELOC_E_ARG; }
+    if (n < 1 || n > RELOC_BATCH_MAX) { reloc_set_error("scan batch: 1..%d frames", RELOC_BATCH_MAX); return RELOC_E_ARG; }
     if (c0->max_feat > 65535 || c0->db_max_rows > MAX_REC_ROWS) { reloc_set_error("scan batch: capacity"); return RELOC_E_CAPACITY; }
     const int n_ids = (int)c0->db_records, max_rows = c0->db_max_rows < 1 ? 1 : c0->db_max_rows;
     // n_cur_max = the feature capacity; the 8-column kernel walks column blocks of 512 (one block for nfeatures <= 512)
@@ -1210,12 +1217,11 @@ int launch_db_scan_batch(reloc_ctx *const *ctxs, int n, const double *q, double 
     bt.n = n;
     bt.xyh = heading_mask ? c0->db_xy_heading : nullptr;
     bt.cos_tol = cos_tol;
-    for (int f = 0; f < SCAN_BATCH_MAX; ++f) {
-        reloc_ctx *c = ctxs[f < n ? f : 0];
+    frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int g) {
         bt.cur[f] = (const uint4 *)c->f_desc; bt.n_cur[f] = c->f_count; bt.counts[f] = c->db_counts;
         bt.skip_if[f] = auto_mode ? c->cand_n : nullptr;
-        for (int k = 0; k < 4; ++k) bt.q[f][k] = q[4 * (f < n ? f : 0) + k];
-    }
+        for (int k = 0; k < 4; ++k) bt.q[f][k] = q[4 * g + k];
+    });
     // `gens` generations in all (not per frame): a workgroup's budget grows with the batch, and with it the share of the
     // launch that is not prologue.  Per frame: the budgeted workgroups + one sweeper behind them
     const int gens = c0->scan_gens > 0 ? c0->scan_gens : 1;
@@ -1505,10 +1511,10 @@ RELOC_API int reloc_match_mutual(reloc_ctx *ctx, const uint8_t *q, int nq, const
     HIP_TRY(hipMemcpyAsync(doff, offs, sizeof(offs), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(dq, q, (size_t)nq * 32, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(dt, t, (size_t)nt * 32, hipMemcpyHostToDevice, ctx->stream));
-    ctx->latency_shapes = true;                               // a single record, nothing runs beside it: 8 waves
-    rc = launch_db_emit(ctx, (const uint8_t *)dq, doff, nq, nullptr, nullptr, 1, (const uint8_t *)dt, nullptr, nt, dqi, dti, ddi, dn, nq);
-    ctx->latency_shapes = false;
-    if (rc) return rc;
+    // the query set is the one record (rows nq) of a database of its own; nothing runs beside it: 8 waves
+    EmitBatch bt = {};
+    bt.f[0].cur = (const uint4 *)dt; bt.f[0].m_qidx = dqi; bt.f[0].m_tidx = dti; bt.f[0].m_dist = ddi; bt.f[0].m_n = dn;
+    if ((rc = launch_db_emit(&ctx, 1, bt, (const uint8_t *)dq, doff, nq, nullptr, 1, nt, nq, true))) return rc;
     int32_t n = 0;
     HIP_TRY(hipMemcpyAsync(&n, dn, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -186,7 +186,7 @@ __device__ __forceinline__ int pyr_div(int q, float inv) { return (int)(((float)
 
 // PYR_BS = threads per workgroup: 512 is the fastest alone (256 / 512 / 1024: ORB stage 73 / 68 / 66 us), 256 the best
 // neighbour of a scan (a 256-thread workgroup fits into the slot one retiring scan workgroup frees: 4-stream run 6550 ->
-// 6685 frames/s, synchronous tick +6 us), so both exist: see orb_run_dev.
+// 6685 frames/s, synchronous tick +6 us), so both exist: see orb_run.
 template <int CH, bool ALIGNED, int PYR_BS>
 __device__ __forceinline__ void pyramid_body(const OrbTable *__restrict__ tab, const PyrTile *__restrict__ tiles,
                                                  const int32_t *__restrict__ rz, const uint8_t *__restrict__ src, int w, int h,
@@ -1258,113 +1258,84 @@ static int clahe_launch(hipStream_t st, const ClaheFrames &F, int n, const Clahe
 
 static inline int clahe_stride(int w) { return (w + 63) & ~63; }
 
-// src_dev: channels == 3 -> interleaved frame (gray fused), channels == 1 -> gray plane.
-// A 3-channel frame of a context with CLAHE on (reloc_set_clahe) is equalised first; the pyramid then reads the CLAHE plane.
-int orb_run_dev(reloc_ctx *ctx, const uint8_t *src_dev, int w, int h, int stride, int channels, int order, int nfeatures)
+// what the five ORB kernels read and write of a context, for the source frame src
+static OrbFrame orb_frame(const reloc_ctx *c, const uint8_t *src)
 {
-    int rc = orb_prepare(ctx, w, h, nfeatures);
-    if (rc) return rc;
-    const OrbTable *tab_h = (const OrbTable *)ctx->orb_tab_host;
-    const OrbTable *tab_d = (const OrbTable *)ctx->orb_const;
-    hipStream_t st = ctx->stream;
-    reloc_prof_begin(ctx, RELOC_PROF_ORB);
-    if (channels == 3 && ctx->clahe_tx > 0) {
-        ClaheFrames F = {};
-        F.src[0] = src_dev; F.lut[0] = ctx->clahe_lut; F.dst[0] = ctx->clahe_plane;
-        const int cs = clahe_stride(w);
-        if ((rc = clahe_launch(st, F, 1, clahe_geom(w, h, ctx->clahe_clip, ctx->clahe_tx, ctx->clahe_ty), 3, stride,
-                               gray_flags(ctx, order), cs))) {
-            reloc_prof_end(ctx, RELOC_PROF_ORB);
-            return rc;
-        }
-        src_dev = ctx->clahe_plane; stride = cs; channels = 1;
-    }
-    {
-        const bool aligned = (w % 4 == 0) && (stride % 4 == 0) && (((uintptr_t)src_dev) % 4 == 0);
-        // 512-thread workgroups where nothing scans beside the tick (local-candidate ticks, exclusive contexts, single calls),
-        // 256 in ticks that share the chip with whole-database scans
-        const bool wide = ctx->orb_latency_shape;
-        auto kern512 = channels == 3 ? (aligned ? k_pyramid<3, true, 512> : k_pyramid<3, false, 512>) : (aligned ? k_pyramid<1, true, 512> : k_pyramid<1, false, 512>);
-        auto kern256 = channels == 3 ? (aligned ? k_pyramid<3, true, 256> : k_pyramid<3, false, 256>) : (aligned ? k_pyramid<1, true, 256> : k_pyramid<1, false, 256>);
-        PyrLds lds;
-        for (int l = 0; l < NLEV; ++l) lds.lev[l] = ctx->pyr_lds[l];
-        lds.tabs = ctx->pyr_lds[NLEV];
-        hipLaunchKernelGGL(wide ? kern512 : kern256, dim3(ctx->pyr_ntiles), dim3(wide ? 512 : 256), ctx->pyr_lds_bytes, st, tab_d,
-                           (const PyrTile *)ctx->pyr_tiles, ctx->rz_tab, src_dev, w, h, stride, gray_flags(ctx, order), ctx->pyr, lds, ctx->hist, ctx->cand_cnt);
-    }
-    hipLaunchKernelGGL(k_fast_blur, dim3(tab_h->fast_tile_base[NLEV] + tab_h->blur_tile_base[NLEV]), dim3(256), 0, st, tab_d, ctx->pyr,
-                       ctx->nms, ctx->hist, ctx->blur, tab_h->fast_tile_base[NLEV]);
-    hipLaunchKernelGGL(k_harris, dim3(tab_h->flat_base[NLEV]), dim3(256), 0, st, tab_d, ctx->pyr, ctx->nms, ctx->hist,
-                       ctx->cand_cnt, ctx->cand_key, ctx->cand_resp, ctx->dbg_cut);
-    hipLaunchKernelGGL(k_select, dim3(NLEV), dim3(1024), 0, st, tab_d, ctx->cand_cnt,
-                       ctx->cand_key, ctx->cand_resp, ctx->kp_cnt, ctx->kp_key, ctx->kp_resp);
-    hipLaunchKernelGGL(k_describe, dim3((ctx->max_feat + 3) / 4), dim3(256), 0, st, tab_d, ctx->pyr, ctx->blur, ctx->kp_cnt,
-                       ctx->kp_key, ctx->kp_resp, ctx->max_feat, ctx->f_xy, ctx->f_size, ctx->f_angle, ctx->f_resp,
-                       ctx->f_oct, ctx->f_desc, ctx->f_count);
-    reloc_prof_end(ctx, RELOC_PROF_ORB);
-    HIP_TRY(hipGetLastError());
-    return RELOC_OK;
+    OrbFrame F;
+    F.tab = (const OrbTable *)c->orb_const; F.tiles = (const PyrTile *)c->pyr_tiles; F.rz = c->rz_tab; F.src = src;
+    F.pyr = c->pyr; F.nms = c->nms; F.blur = c->blur; F.hist = c->hist; F.cand_cnt = c->cand_cnt; F.cand_key = c->cand_key;
+    F.cand_resp = c->cand_resp; F.dbg_cut = c->dbg_cut; F.kp_cnt = c->kp_cnt; F.kp_key = c->kp_key; F.kp_resp = c->kp_resp;
+    F.f_xy = c->f_xy; F.f_size = c->f_size; F.f_angle = c->f_angle; F.f_resp = c->f_resp; F.f_oct = c->f_oct; F.f_desc = c->f_desc;
+    F.f_count = c->f_count;
+    return F;
 }
 
-// The same five kernels for n contexts (one frame each, equal geometry) that share a stream: five launches, blockIdx.y = frame.
-int orb_run_batch_dev(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs_dev, int w, int h, int stride, int order, int nfeatures)
+// Five launches (six with CLAHE's two): the frames are of equal geometry.  3-channel frames of contexts with CLAHE on
+// (reloc_set_clahe) are equalised first; the pyramid then reads the CLAHE planes.  The pyramid runs 512-thread workgroups
+// for latency, 256 where it shares the chip with whole-database scans.
+int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, int h, int stride, int channels, int order,
+            int nfeatures, bool latency)
 {
-    if (n < 1 || n > RELOC_BATCH_MAX) { reloc_set_error("orb batch: 1..%d frames", RELOC_BATCH_MAX); return RELOC_E_ARG; }
-    OrbBatch b;
-    bool aligned = (w % 4 == 0) && (stride % 4 == 0);
-    for (int f = 0; f < RELOC_BATCH_MAX; ++f) {
-        reloc_ctx *c = ctxs[f < n ? f : 0];
-        if (f < n) {
-            const int rc = orb_prepare(c, w, h, nfeatures);
-            if (rc) return rc;
-            if (c->pyr_ntiles != ctxs[0]->pyr_ntiles || c->pyr_lds_bytes != ctxs[0]->pyr_lds_bytes || c->max_feat != ctxs[0]->max_feat ||
-                c->prm.gray_coeff_bits != ctxs[0]->prm.gray_coeff_bits) {
-                reloc_set_error("orb batch: contexts of unequal geometry");
-                return RELOC_E_STATE;
-            }
-            if (c->clahe_tx != ctxs[0]->clahe_tx || c->clahe_ty != ctxs[0]->clahe_ty || c->clahe_clip != ctxs[0]->clahe_clip) {
-                reloc_set_error("orb batch: contexts of unequal CLAHE settings (reloc_set_clahe)");
-                return RELOC_E_STATE;
-            }
-            aligned = aligned && (((uintptr_t)srcs_dev[f]) % 4 == 0);
-        }
-        OrbFrame &F = b.f[f];
-        F.tab = (const OrbTable *)c->orb_const; F.tiles = (const PyrTile *)c->pyr_tiles; F.rz = c->rz_tab; F.src = srcs_dev[f < n ? f : 0];
-        F.pyr = c->pyr; F.nms = c->nms; F.blur = c->blur; F.hist = c->hist; F.cand_cnt = c->cand_cnt; F.cand_key = c->cand_key;
-        F.cand_resp = c->cand_resp; F.dbg_cut = c->dbg_cut; F.kp_cnt = c->kp_cnt; F.kp_key = c->kp_key; F.kp_resp = c->kp_resp;
-        F.f_xy = c->f_xy; F.f_size = c->f_size; F.f_angle = c->f_angle; F.f_resp = c->f_resp; F.f_oct = c->f_oct; F.f_desc = c->f_desc;
-        F.f_count = c->f_count;
-    }
+    if (n < 1 || n > RELOC_BATCH_MAX) { reloc_set_error("orb: 1..%d frames", RELOC_BATCH_MAX); return RELOC_E_ARG; }
     reloc_ctx *c0 = ctxs[0];
+    for (int f = 0; f < n; ++f) {
+        reloc_ctx *c = ctxs[f];
+        if (int rc = orb_prepare(c, w, h, nfeatures)) return rc;
+        if (c->pyr_ntiles != c0->pyr_ntiles || c->pyr_lds_bytes != c0->pyr_lds_bytes || c->max_feat != c0->max_feat ||
+            c->prm.gray_coeff_bits != c0->prm.gray_coeff_bits) {
+            reloc_set_error("orb batch: contexts of unequal geometry");
+            return RELOC_E_STATE;
+        }
+        if (c->clahe_tx != c0->clahe_tx || c->clahe_ty != c0->clahe_ty || c->clahe_clip != c0->clahe_clip) {
+            reloc_set_error("orb batch: contexts of unequal CLAHE settings (reloc_set_clahe)");
+            return RELOC_E_STATE;
+        }
+    }
     const OrbTable *tab_h = (const OrbTable *)c0->orb_tab_host;
+    const int flags = gray_flags(c0, order);
     hipStream_t st = c0->stream;
     reloc_prof_begin(c0, RELOC_PROF_ORB);
+    const uint8_t *planes[RELOC_BATCH_MAX];
+    if (channels == 3 && c0->clahe_tx > 0) {
+        ClaheFrames F = {};
+        for (int f = 0; f < n; ++f) { F.src[f] = srcs[f]; F.lut[f] = ctxs[f]->clahe_lut; F.dst[f] = ctxs[f]->clahe_plane; planes[f] = F.dst[f]; }
+        const int cs = clahe_stride(w);
+        if (int rc = clahe_launch(st, F, n, clahe_geom(w, h, c0->clahe_clip, c0->clahe_tx, c0->clahe_ty), 3, stride, flags, cs)) {
+            reloc_prof_end(c0, RELOC_PROF_ORB);
+            return rc;
+        }
+        srcs = planes; stride = cs; channels = 1;
+    }
+    bool aligned = w % 4 == 0 && stride % 4 == 0;
+    for (int f = 0; f < n; ++f) aligned = aligned && ((uintptr_t)srcs[f]) % 4 == 0;
+    OrbBatch b;
+    frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int g) { b.f[f] = orb_frame(c, srcs[g]); });
     PyrLds lds;
     for (int l = 0; l < NLEV; ++l) lds.lev[l] = c0->pyr_lds[l];
     lds.tabs = c0->pyr_lds[NLEV];
-    // 256-thread pyramid: a batch runs beside other streams' scans (see orb_run_dev)
-    if (c0->clahe_tx > 0) {
-        // CLAHE of every frame into its context's plane, then the gray-plane pyramid over the planes
-        ClaheFrames F = {};
-        for (int f = 0; f < n; ++f) { F.src[f] = srcs_dev[f]; F.lut[f] = ctxs[f]->clahe_lut; F.dst[f] = ctxs[f]->clahe_plane; }
-        const int cs = clahe_stride(w);
-        const int rc = clahe_launch(st, F, n, clahe_geom(w, h, c0->clahe_clip, c0->clahe_tx, c0->clahe_ty), 3, stride,
-                                    gray_flags(c0, order), cs);
-        if (rc) { reloc_prof_end(c0, RELOC_PROF_ORB); return rc; }
-        for (int f = 0; f < RELOC_BATCH_MAX; ++f) b.f[f].src = ctxs[f < n ? f : 0]->clahe_plane;
-        if (w % 4 == 0)
-            hipLaunchKernelGGL((k_pyramid_batch<1, true, 256>), dim3(c0->pyr_ntiles, n), dim3(256), c0->pyr_lds_bytes, st, b, w, h, cs, 0, lds);
-        else
-            hipLaunchKernelGGL((k_pyramid_batch<1, false, 256>), dim3(c0->pyr_ntiles, n), dim3(256), c0->pyr_lds_bytes, st, b, w, h, cs, 0, lds);
-    } else if (aligned)
-        hipLaunchKernelGGL((k_pyramid_batch<3, true, 256>), dim3(c0->pyr_ntiles, n), dim3(256), c0->pyr_lds_bytes, st, b, w, h, stride, gray_flags(c0, order), lds);
-    else
-        hipLaunchKernelGGL((k_pyramid_batch<3, false, 256>), dim3(c0->pyr_ntiles, n), dim3(256), c0->pyr_lds_bytes, st, b, w, h, stride, gray_flags(c0, order), lds);
-    hipLaunchKernelGGL(k_fast_blur_batch, dim3(tab_h->fast_tile_base[NLEV] + tab_h->blur_tile_base[NLEV], n), dim3(256), 0, st, b,
-                       tab_h->fast_tile_base[NLEV]);
-    hipLaunchKernelGGL(k_harris_batch, dim3(tab_h->flat_base[NLEV], n), dim3(256), 0, st, b);
-    hipLaunchKernelGGL(k_select_batch, dim3(NLEV, n), dim3(1024), 0, st, b);
-    hipLaunchKernelGGL(k_describe_batch, dim3((c0->max_feat + 3) / 4, n), dim3(256), 0, st, b, c0->max_feat);
+    const int n_fast = tab_h->fast_tile_base[NLEV], n_blur = tab_h->blur_tile_base[NLEV];
+    if (n == 1) {
+        const OrbFrame &F = b.f[0];
+        auto kern512 = channels == 3 ? (aligned ? k_pyramid<3, true, 512> : k_pyramid<3, false, 512>) : (aligned ? k_pyramid<1, true, 512> : k_pyramid<1, false, 512>);
+        auto kern256 = channels == 3 ? (aligned ? k_pyramid<3, true, 256> : k_pyramid<3, false, 256>) : (aligned ? k_pyramid<1, true, 256> : k_pyramid<1, false, 256>);
+        hipLaunchKernelGGL(latency ? kern512 : kern256, dim3(c0->pyr_ntiles), dim3(latency ? 512 : 256), c0->pyr_lds_bytes, st, F.tab,
+                           F.tiles, F.rz, F.src, w, h, stride, flags, F.pyr, lds, F.hist, F.cand_cnt);
+        hipLaunchKernelGGL(k_fast_blur, dim3(n_fast + n_blur), dim3(256), 0, st, F.tab, F.pyr, F.nms, F.hist, F.blur, n_fast);
+        hipLaunchKernelGGL(k_harris, dim3(tab_h->flat_base[NLEV]), dim3(256), 0, st, F.tab, F.pyr, F.nms, F.hist, F.cand_cnt, F.cand_key,
+                           F.cand_resp, F.dbg_cut);
+        hipLaunchKernelGGL(k_select, dim3(NLEV), dim3(1024), 0, st, F.tab, F.cand_cnt, F.cand_key, F.cand_resp, F.kp_cnt, F.kp_key,
+                           F.kp_resp);
+        hipLaunchKernelGGL(k_describe, dim3((c0->max_feat + 3) / 4), dim3(256), 0, st, F.tab, F.pyr, F.blur, F.kp_cnt, F.kp_key,
+                           F.kp_resp, c0->max_feat, F.f_xy, F.f_size, F.f_angle, F.f_resp, F.f_oct, F.f_desc, F.f_count);
+    } else {
+        auto kern = channels == 3 ? (aligned ? k_pyramid_batch<3, true, 256> : k_pyramid_batch<3, false, 256>)
+                                  : (aligned ? k_pyramid_batch<1, true, 256> : k_pyramid_batch<1, false, 256>);
+        hipLaunchKernelGGL(kern, dim3(c0->pyr_ntiles, n), dim3(256), c0->pyr_lds_bytes, st, b, w, h, stride, flags, lds);
+        hipLaunchKernelGGL(k_fast_blur_batch, dim3(n_fast + n_blur, n), dim3(256), 0, st, b, n_fast);
+        hipLaunchKernelGGL(k_harris_batch, dim3(tab_h->flat_base[NLEV], n), dim3(256), 0, st, b);
+        hipLaunchKernelGGL(k_select_batch, dim3(NLEV, n), dim3(1024), 0, st, b);
+        hipLaunchKernelGGL(k_describe_batch, dim3((c0->max_feat + 3) / 4, n), dim3(256), 0, st, b, c0->max_feat);
+    }
     reloc_prof_end(c0, RELOC_PROF_ORB);
     HIP_TRY(hipGetLastError());
     return RELOC_OK;
@@ -1391,7 +1362,7 @@ RELOC_API int reloc_gray_u8(reloc_ctx *ctx, const uint8_t *img, int w, int h, in
 RELOC_API int reloc_orb_frame_dev(reloc_ctx *ctx, const uint8_t *img_dev, int w, int h, int stride, int order, int nfeatures)
 {
     ARG_CHECK_CTX(ctx, img_dev && w >= 64 && h >= 64 && stride >= 3 * w && nfeatures > 0, "reloc_orb_frame_dev");
-    return orb_run_dev(ctx, img_dev, w, h, stride, 3, order, nfeatures);
+    return orb_run(&ctx, 1, &img_dev, w, h, stride, 3, order, nfeatures, true);
 }
 
 RELOC_API const uint8_t *reloc_frame_desc_dev(reloc_ctx *ctx) { return ctx ? ctx->f_desc : nullptr; }
@@ -1407,7 +1378,8 @@ RELOC_API int reloc_orb_detect_compute(reloc_ctx *ctx, const uint8_t *gray, int 
     if (w < 63 || h < 63) return RELOC_OK;   // no level is wider than the 31-pixel edge margin on both sides
     if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
     HIP_TRY(hipMemcpy2DAsync(ctx->frame_img, w, gray, stride, w, h, hipMemcpyHostToDevice, ctx->stream));
-    int rc = orb_run_dev(ctx, ctx->frame_img, w, h, w, 1, 0, nfeatures);
+    const uint8_t *src = ctx->frame_img;
+    int rc = orb_run(&ctx, 1, &src, w, h, w, 1, 0, nfeatures, true);
     if (rc) return rc;
     int32_t n = 0;
     HIP_TRY(hipMemcpyAsync(&n, ctx->f_count, 4, hipMemcpyDeviceToHost, ctx->stream));

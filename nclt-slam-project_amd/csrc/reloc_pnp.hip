@@ -723,7 +723,7 @@ __device__ bool chol_solve6(const double Ain[36], const double b[6], double x[6]
 // SIMD from which TWO scan waves have retired; held to 128 (WAVES = 4 per SIMD, 144 bytes of scratch) it fits when one has:
 // 4-stream run 5940 -> 6020 frames/s, synchronous tick +1.7 us.  80 registers: no further gain, tick +16 us.
 // (The same limit on k_pnp_hyp (108 -> 80) and k_pyramid (81 -> 64) changes nothing.)  Ticks that run no whole-database scan
-// and the single-call entry point use the unconstrained instantiation (ctx->latency_shapes).
+// and the single-call entry point use the unconstrained instantiation (pnp_launch's latency flag).
 template <bool DIST>
 __device__ __forceinline__ void pnp_finish_body(const float *__restrict__ obj, const float *__restrict__ img,
                                                 const int32_t *__restrict__ m_arr, const int32_t *__restrict__ n_cand_p,
@@ -912,7 +912,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) 
     prm.seed = F.seed;
     pnp_finish_body<DIST>(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, F.inl, F.out, F.relocating, dc);
 }
-// DIST: one instantiation for every shape, budget PNP_DIST_WAVES (see pnp_run_candidates)
+// DIST: one instantiation for every shape, budget PNP_DIST_WAVES (see pnp_launch)
 constexpr int PNP_DIST_WAVES = 2;
 
 
@@ -938,68 +938,67 @@ static bool dist_nonzero(const double *d)
     return false;
 }
 
+// what PnP reads and writes of a context: the pairs of its emit pass, its hypotheses, inliers and per-candidate records
+static PnpFrame pnp_frame(const reloc_ctx *c, uint64_t seed)
+{
+    PnpFrame F;
+    F.obj = c->p_obj; F.img = c->p_img; F.m_arr = c->m_n; F.n_cand_p = c->cand_n; F.Rt = c->p_Rt; F.cnt = c->p_cnt; F.inl = c->p_inl;
+    F.out = c->p_out; F.seed = seed; F.relocating = c->tick_flags;
+    return F;
+}
+
+// Three launches for up to n_cand_max candidates of every frame (grid y / z = frame at n > 1); prm.seed is each frame's.
 // The DIST kernels run when dist is non-NULL.  Their k_pnp_finish has ONE register budget, PNP_DIST_WAVES = 2 waves per SIMD
 // (256 VGPRs): the forward model and its Jacobian do not fit the pinhole kernel's 128 without scratch.
-int pnp_run_candidates(reloc_ctx *ctx, int n_cand_max, const int32_t *n_cand_dev, const double K4[4], int iters,
-                       float thr_px, double conf, uint64_t seed, int min_m, const int32_t *relocating_dev, int gate_local, int gate_global,
-                       const double *dist)
+static int pnp_launch(reloc_ctx *const *ctxs, int n, const PnpBatch &b, int n_cand_max, PnpParams prm, const double *dist,
+                      bool latency)
 {
+    reloc_ctx *c0 = ctxs[0];
+    const int iters = prm.iters;
     if (n_cand_max <= 0) return RELOC_OK;
-    if (n_cand_max > MAX_CAND || iters < 1 || iters > MAX_HYP) {
-        reloc_set_error("pnp: n_cand %d (max %d) iters %d (max %d)", n_cand_max, MAX_CAND, iters, MAX_HYP);
+    if (n < 1 || n > RELOC_BATCH_MAX || n_cand_max > MAX_CAND || iters < 1 || iters > MAX_HYP) {
+        reloc_set_error("pnp: n %d n_cand %d (max %d) iters %d (max %d)", n, n_cand_max, MAX_CAND, iters, MAX_HYP);
         return RELOC_E_CAPACITY;
     }
-    PnpParams prm = make_params(K4, iters, thr_px, conf, seed, MAX_REC_ROWS, min_m);
-    prm.gate_local = gate_local; prm.gate_global = gate_global;
-    auto hyp = dist ? k_pnp_hyp<true> : k_pnp_hyp<false>;
-    auto score = dist ? k_pnp_score<true> : k_pnp_score<false>;
-    auto finish = dist ? k_pnp_finish<true, PNP_DIST_WAVES>
-                       : ctx->latency_shapes ? k_pnp_finish<false, 1> : k_pnp_finish<false, 4>;
     const DistCoef dc = make_dist(dist);
-    reloc_prof_begin(ctx, RELOC_PROF_PNP);
-    hipLaunchKernelGGL(hyp, dim3((iters + 63) / 64, n_cand_max), dim3(HYP_BLOCK), 0, ctx->stream, ctx->p_obj, ctx->p_img,
-                       ctx->m_n, n_cand_dev, prm, ctx->p_Rt, ctx->p_cnt, relocating_dev, dc);
-    hipLaunchKernelGGL(score, dim3(iters, n_cand_max), dim3(64), 0, ctx->stream, ctx->p_obj, ctx->p_img, ctx->m_n,
-                       n_cand_dev, prm, ctx->p_Rt, ctx->p_cnt, (uint8_t *)nullptr, MAX_HYP, dc);
-    hipLaunchKernelGGL(finish, dim3(n_cand_max), dim3(64), 0, ctx->stream, ctx->p_obj, ctx->p_img, ctx->m_n,
-                       n_cand_dev, prm, ctx->p_Rt, ctx->p_cnt, ctx->p_inl, ctx->p_out, relocating_dev, dc);
-    reloc_prof_end(ctx, RELOC_PROF_PNP);
+    hipStream_t st = c0->stream;
+    reloc_prof_begin(c0, RELOC_PROF_PNP);
+    if (n == 1) {
+        const PnpFrame &F = b.f[0];
+        prm.seed = F.seed;
+        auto hyp = dist ? k_pnp_hyp<true> : k_pnp_hyp<false>;
+        auto score = dist ? k_pnp_score<true> : k_pnp_score<false>;
+        auto finish = dist ? k_pnp_finish<true, PNP_DIST_WAVES> : latency ? k_pnp_finish<false, 1> : k_pnp_finish<false, 4>;
+        hipLaunchKernelGGL(hyp, dim3((iters + 63) / 64, n_cand_max), dim3(HYP_BLOCK), 0, st, F.obj, F.img, F.m_arr, F.n_cand_p, prm,
+                           F.Rt, F.cnt, F.relocating, dc);
+        hipLaunchKernelGGL(score, dim3(iters, n_cand_max), dim3(64), 0, st, F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt,
+                           (uint8_t *)nullptr, MAX_HYP, dc);
+        hipLaunchKernelGGL(finish, dim3(n_cand_max), dim3(64), 0, st, F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, F.inl,
+                           F.out, F.relocating, dc);
+    } else {
+        auto hyp = dist ? k_pnp_hyp_batch<true> : k_pnp_hyp_batch<false>;
+        auto score = dist ? k_pnp_score_batch<true> : k_pnp_score_batch<false>;
+        auto finish = dist ? k_pnp_finish_batch<true, PNP_DIST_WAVES> : k_pnp_finish_batch<false, 4>;
+        hipLaunchKernelGGL(hyp, dim3((iters + 63) / 64, n_cand_max, n), dim3(HYP_BLOCK), 0, st, b, prm, dc);
+        hipLaunchKernelGGL(score, dim3(iters, n_cand_max, n), dim3(64), 0, st, b, prm, MAX_HYP, dc);
+        hipLaunchKernelGGL(finish, dim3(n_cand_max, n), dim3(64), 0, st, b, prm, dc);
+    }
+    reloc_prof_end(c0, RELOC_PROF_PNP);
     HIP_TRY(hipGetLastError());
     return RELOC_OK;
 }
 
-// the candidates of n contexts (one shared stream, equal parameters) in three launches
-int pnp_run_candidates_batch(reloc_ctx *const *ctxs, int n, int n_cand_max, const uint64_t *seeds)
+int pnp_run_candidates(reloc_ctx *const *ctxs, int n, const uint64_t *seeds, bool latency)
 {
     reloc_ctx *c0 = ctxs[0];
-    const int iters = c0->prm.ransac_iterations;
-    if (n < 1 || n > RELOC_BATCH_MAX || n_cand_max <= 0 || n_cand_max > MAX_CAND || iters < 1 || iters > MAX_HYP) {
-        reloc_set_error("pnp batch: n %d n_cand %d (max %d) iters %d (max %d)", n, n_cand_max, MAX_CAND, iters, MAX_HYP);
-        return RELOC_E_CAPACITY;
-    }
-    PnpParams prm = make_params(c0->K4, iters, (float)c0->prm.ransac_reproj_px, c0->prm.ransac_confidence, 0, MAX_REC_ROWS,
-                                c0->prm.min_matches);
-    prm.gate_local = c0->prm.min_inliers; prm.gate_global = c0->prm.global_min_inliers;
+    const reloc_params &q = c0->prm;
+    PnpParams prm = make_params(c0->K4, q.ransac_iterations, (float)q.ransac_reproj_px, q.ransac_confidence, 0, MAX_REC_ROWS,
+                                q.min_matches);
+    prm.gate_local = q.min_inliers; prm.gate_global = q.global_min_inliers;
     PnpBatch b;
-    for (int f = 0; f < RELOC_BATCH_MAX; ++f) {
-        reloc_ctx *c = ctxs[f < n ? f : 0];
-        PnpFrame &F = b.f[f];
-        F.obj = c->p_obj; F.img = c->p_img; F.m_arr = c->m_n; F.n_cand_p = c->cand_n; F.Rt = c->p_Rt; F.cnt = c->p_cnt; F.inl = c->p_inl;
-        F.out = c->p_out; F.seed = seeds ? seeds[f < n ? f : 0] : 0; F.relocating = c->tick_flags;
-    }
-    // the contexts of a batch carry equal coefficients (checked by the callers)
-    const bool dist = c0->has_dist;
-    auto hyp = dist ? k_pnp_hyp_batch<true> : k_pnp_hyp_batch<false>;
-    auto score = dist ? k_pnp_score_batch<true> : k_pnp_score_batch<false>;
-    auto finish = dist ? k_pnp_finish_batch<true, PNP_DIST_WAVES> : k_pnp_finish_batch<false, 4>;
-    const DistCoef dc = make_dist(c0->dist);
-    reloc_prof_begin(c0, RELOC_PROF_PNP);
-    hipLaunchKernelGGL(hyp, dim3((iters + 63) / 64, n_cand_max, n), dim3(HYP_BLOCK), 0, c0->stream, b, prm, dc);
-    hipLaunchKernelGGL(score, dim3(iters, n_cand_max, n), dim3(64), 0, c0->stream, b, prm, MAX_HYP, dc);
-    hipLaunchKernelGGL(finish, dim3(n_cand_max, n), dim3(64), 0, c0->stream, b, prm, dc);
-    reloc_prof_end(c0, RELOC_PROF_PNP);
-    HIP_TRY(hipGetLastError());
-    return RELOC_OK;
+    frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int g) { b.f[f] = pnp_frame(c, seeds ? seeds[g] : 0); });
+    // the contexts of a call carry equal coefficients (ctx_batch_check)
+    return pnp_launch(ctxs, n, b, MAX_CAND, prm, c0->has_dist ? c0->dist : nullptr, latency);
 }
 
 
@@ -1066,11 +1065,11 @@ static int pnp_ransac_impl(reloc_ctx *ctx, const float *obj, const float *img, i
     HIP_TRY(hipMemcpyAsync(ctx->p_img, img, (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(ctx->m_n, &m, 4, hipMemcpyHostToDevice, ctx->stream));
     // the single-call path has no MIN_MATCHES gate (that gate belongs to the matcher, M:330)
-    int rc;
-    ctx->latency_shapes = true;
-    rc = pnp_run_candidates(ctx, 1, nullptr, K4, iters, thr_px, conf, seed, RELOC_PNP_SAMPLE, nullptr, 0, 0, dist);
-    ctx->latency_shapes = false;
-    if (rc) return rc;
+    PnpBatch b;
+    b.f[0] = pnp_frame(ctx, seed);
+    b.f[0].n_cand_p = nullptr; b.f[0].relocating = nullptr;       // one candidate of m pairs, no relocation flag
+    if (int rc = pnp_launch(&ctx, 1, b, 1, make_params(K4, iters, thr_px, conf, seed, MAX_REC_ROWS, RELOC_PNP_SAMPLE), dist, true))
+        return rc;
     PnpOut po;
     HIP_TRY(hipMemcpyAsync(&po, ctx->p_out, sizeof(po), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));

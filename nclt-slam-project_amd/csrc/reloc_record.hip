@@ -144,7 +144,8 @@ RELOC_API int reloc_record_frame(reloc_ctx *ctx, const uint8_t *img, const uint1
     int32_t *o_idx = (int32_t *)(o_pts + mf * 3), *o_n = o_idx + mf;
     HIP_TRY(hipMemcpyAsync(ctx->frame_img, img, (size_t)w * h * 3, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(ddepth, depth_mm, (size_t)w * h * 2, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = orb_run_dev(ctx, ctx->frame_img, w, h, w * 3, 3, order, nfeatures))) return rc;
+    const uint8_t *src = ctx->frame_img;
+    if ((rc = orb_run(&ctx, 1, &src, w, h, w * 3, 3, order, nfeatures, true))) return rc;
     RecordParams p;
     p.fx = ctx->K4[0]; p.fy = ctx->K4[1]; p.cx = ctx->K4[2]; p.cy = ctx->K4[3];
     p.depth_min = RELOC_DEPTH_MIN_M; p.depth_max = RELOC_DEPTH_MAX_M; p.var_max = RELOC_DEPTH_VAR_MAX_M;

@@ -452,19 +452,6 @@ static void launch_candidates_local(reloc_ctx *ctx, const TickParams &prm)
                        ctx->cand_ids, ctx->cand_n, ctx->tick_flags);
 }
 
-// auto_mode: the ranking only takes effect when the local search left no candidate (see k_topk_counts)
-static void launch_topk_counts(reloc_ctx *ctx, int k, int32_t *out_ids, int32_t *out_counts, bool auto_mode, int id_base = 0,
-                               int32_t *out_nfeat = nullptr)
-{
-    const int L = (int)ctx->db_records;
-    // a count cannot exceed the rows of the largest record nor the features of a frame
-    const int max_count = ctx->db_max_rows < ctx->max_feat ? ctx->db_max_rows : ctx->max_feat;
-    hipLaunchKernelGGL(k_topk_counts, dim3(1), dim3(TOPK_HIST_THREADS), (size_t)(max_count + 2) * sizeof(int), ctx->stream, ctx->db_counts,
-                       L, k, id_base, ctx->prm.min_matches, max_count, out_ids, out_counts, ctx->cand_n,
-                       auto_mode ? (const int32_t *)ctx->cand_n : (const int32_t *)nullptr, ctx->tick_flags,
-                       (const int32_t *)ctx->f_count, out_nfeat);
-}
-
 __device__ __forceinline__ void tick_stamp(TickResult *res_host, TickResult *res_ext, int seq)
 {
     if (!seq) return;
@@ -608,8 +595,6 @@ static TickParams make_tick_params(reloc_ctx *ctx, const double base_pose[7], in
     return p;
 }
 
-__global__ void k_set_flag(int32_t *flag, int v) { *flag = v; }
-
 // the stamp of the tick being enqueued: 1, 2, ... (never 0: 0 means "no stamp")
 static int tick_next_seq(reloc_ctx *ctx)
 {
@@ -618,29 +603,101 @@ static int tick_next_seq(reloc_ctx *ctx)
     return ctx->tick_seq;
 }
 
-static int tick_solve(reloc_ctx *ctx, const TickParams &prm, uint64_t seed)
+// candidate lists handed in by the caller (sharded solve): frame f's k entries at ids + f * k, -1 = none; flag: relocating
+struct SetCandBatch { int32_t *cand_ids[RELOC_BATCH_MAX], *cand_n[RELOC_BATCH_MAX], *flags[RELOC_BATCH_MAX]; };
+__global__ void k_set_candidates_batch(const int32_t *__restrict__ ids, int k, SetCandBatch b, int flag)
 {
-    int rc;
-    hipStream_t st = ctx->stream;
-    // mutual matches of every candidate, in queryIdx order, with their 3-D / 2-D pairs (M:333-336)
-    ScanMask emit;
-    emit.g_pts3d = ctx->db_pts3d; emit.g_xy = ctx->f_xy; emit.g_obj = ctx->p_obj; emit.g_img = ctx->p_img;
-    // a tick of local candidates runs no whole-database scan: its emit pass and refinement are sized for latency
-    ctx->latency_shapes = prm.mode == RELOC_TICK_LOCAL || ctx_alone(ctx);
-    rc = launch_db_emit(ctx, ctx->db_desc, ctx->db_off, ctx->db_max_rows, ctx->cand_ids, ctx->cand_n, MAX_CAND, ctx->f_desc,
-                        ctx->f_count, ctx->max_feat, ctx->m_qidx, ctx->m_tidx, ctx->m_dist, ctx->m_n, MAX_REC_ROWS, emit);
-    if (!rc)
-        rc = pnp_run_candidates(ctx, MAX_CAND, ctx->cand_n, ctx->K4, ctx->prm.ransac_iterations, (float)ctx->prm.ransac_reproj_px,
-                                ctx->prm.ransac_confidence, seed, ctx->prm.min_matches, ctx->tick_flags, ctx->prm.min_inliers,
-                                ctx->prm.global_min_inliers, ctx->has_dist ? ctx->dist : nullptr);
-    ctx->latency_shapes = false;
-    if (rc) return rc;
-    TickParams fin = prm;
-    fin.seq = tick_next_seq(ctx);
-    hipLaunchKernelGGL(k_tick_finalize, dim3(1), dim3(64), 0, st, ctx->cand_ids, ctx->cand_n, ctx->p_out, ctx->db_pose,
-                       ctx->f_count, fin, ctx->tick_flags, ctx->tick_res, ctx->tick_res_host, ctx->tick_res_ext);
+    const int f = blockIdx.x;
+    if (threadIdx.x == 0) {
+        int m = 0;
+        for (int i = 0; i < k; ++i)
+            if (ids[f * k + i] >= 0) b.cand_ids[f][m++] = ids[f * k + i];
+        *b.cand_n[f] = m;
+        *b.flags[f] = flag;
+    }
+}
+
+// ---- the stages of a tick for the n contexts of one call ------------------------------------------------------------------
+// Each stage is ONE launch per kernel whatever n is: the pointer-argument kernel with frame 0's buffers at n == 1, the
+// frame-table kernel (blockIdx = frame) at n > 1.  The frame builders state which buffers of a context a stage reads and writes.
+static TopkFrame topk_frame(const reloc_ctx *c, int32_t *out_ids, int32_t *out_counts, int32_t *out_nfeat, bool auto_mode)
+{
+    TopkFrame F;
+    F.counts = c->db_counts; F.out_ids = out_ids; F.out_counts = out_counts; F.out_n = c->cand_n;
+    F.skip_if = auto_mode ? (const int32_t *)c->cand_n : (const int32_t *)nullptr;   // AUTO: stands down when local candidates exist
+    F.relocating = c->tick_flags; F.f_count = c->f_count; F.out_nfeat = out_nfeat;
+    return F;
+}
+
+static FinalFrame final_frame(const reloc_ctx *c, const double base_pose[7], TickResult *res_ext, int seq)
+{
+    FinalFrame F;
+    F.cand_ids = c->cand_ids; F.cand_n = c->cand_n; F.pnp = c->p_out; F.f_count = c->f_count; F.relocating = c->tick_flags;
+    F.res = c->tick_res; F.res_host = c->tick_res_host; F.res_ext = res_ext;
+    for (int k = 0; k < 7; ++k) F.base_pose[k] = base_pose[k];
+    F.seq = seq;
+    return F;
+}
+
+// ranking of the counts: the k best (count, id + id_base) of every frame
+static void launch_topk_counts(reloc_ctx *const *ctxs, int n, const TopkBatch &b, int k, int id_base)
+{
+    reloc_ctx *c0 = ctxs[0];
+    const int L = (int)c0->db_records;
+    // a count cannot exceed the rows of the largest record nor the features of a frame
+    const int max_count = c0->db_max_rows < c0->max_feat ? c0->db_max_rows : c0->max_feat;
+    const size_t lds = (size_t)(max_count + 2) * sizeof(int);
+    if (n == 1) {
+        const TopkFrame &F = b.f[0];
+        hipLaunchKernelGGL(k_topk_counts, dim3(1), dim3(TOPK_HIST_THREADS), lds, c0->stream, F.counts, L, k, id_base, c0->prm.min_matches,
+                           max_count, F.out_ids, F.out_counts, F.out_n, F.skip_if, F.relocating, F.f_count, F.out_nfeat);
+    } else {
+        hipLaunchKernelGGL(k_topk_counts_batch, dim3(n), dim3(TOPK_HIST_THREADS), lds, c0->stream, b, L, k, id_base, c0->prm.min_matches,
+                           max_count);
+    }
+}
+
+// gates, pose composition and the result records; prm carries what the frames share (frame 0's base pose)
+static int launch_tick_finalize(reloc_ctx *const *ctxs, int n, const FinalBatch &b, TickParams prm)
+{
+    reloc_ctx *c0 = ctxs[0];
+    if (n == 1) {
+        const FinalFrame &F = b.f[0];
+        prm.seq = F.seq;
+        hipLaunchKernelGGL(k_tick_finalize, dim3(1), dim3(64), 0, c0->stream, F.cand_ids, F.cand_n, F.pnp, c0->db_pose, F.f_count, prm,
+                           F.relocating, F.res, F.res_host, F.res_ext);
+    } else {
+        hipLaunchKernelGGL(k_tick_finalize_batch, dim3(n), dim3(64), 0, c0->stream, b, c0->db_pose, prm);
+    }
     HIP_TRY(hipGetLastError());
     return RELOC_OK;
+}
+
+// The whole-database counting scan of every frame.  base_poses != NULL: only heading-compatible records are scored (G:329-344;
+// the scan leaves count 0 on the others).  auto_mode: a frame whose local search found candidates stands down on the device.
+static int scan_counts(reloc_ctx *const *ctxs, int n, const double *base_poses, bool auto_mode)
+{
+    reloc_ctx *c0 = ctxs[0];
+    const double cos_tol = heading_cos_tol_host(c0);
+    int rc;
+    reloc_prof_begin(c0, RELOC_PROF_DB_SCAN);
+    if (n == 1) {
+        ScanMask mask;
+        if (base_poses) {
+            mask.xyh = c0->db_xy_heading;
+            for (int k = 0; k < 4; ++k) mask.q[k] = base_poses[3 + k];
+        }
+        mask.cos_tol = cos_tol;
+        mask.skip_if = auto_mode ? c0->cand_n : nullptr;
+        rc = launch_db_count(c0, c0->f_desc, c0->f_count, c0->max_feat, c0->db_counts, mask);
+    } else {
+        double q[4 * RELOC_BATCH_MAX];
+        for (int f = 0; f < n; ++f)
+            for (int k = 0; k < 4; ++k) q[4 * f + k] = base_poses ? base_poses[7 * f + 3 + k] : (k == 3 ? 1.0 : 0.0);
+        rc = launch_db_scan_batch(ctxs, n, q, cos_tol, auto_mode, base_poses != nullptr);
+    }
+    reloc_prof_end(c0, RELOC_PROF_DB_SCAN);
+    return rc;
 }
 
 RELOC_API int reloc_set_camera(reloc_ctx *ctx, const double K4[4], const double base_to_cam_t[3], const double base_to_cam_R[9])
@@ -678,81 +735,105 @@ RELOC_API int reloc_get_distortion(reloc_ctx *ctx, double coeffs[5])
     return RELOC_OK;
 }
 
-// The tick in three parts, so that several contexts on one stream can share ONE scan launch (reloc_tick_batch_dev):
-//   begin: ORB, local candidates;  scan: whole-database scan (single or batched);  end: ranking, matches, PnP, gates.
-static int tick_begin(reloc_ctx *ctx, const uint8_t *img_dev, int w, int h, int order, const TickParams &prm)
+// ---- one host driver per tick half; a single-context call is a call of n = 1 ---------------------------------------------
+// The contexts of one call (<= RELOC_BATCH_MAX) share ONE stream, so their frames share every launch: ORB 5, local
+// candidates n (LOCAL / AUTO only), scan 1, ranking 1, emit 1, PnP 3, finalisation 1 -- 12 launches for 8 frames in
+// whole-database mode instead of the 100 of eight per-frame ticks (their serial chain of small kernels was what a batch
+// spent its time on).
+
+// until the finalisation has been enqueued (tick_next_seq), every context of a tick call reports its tick as failed
+static void tick_mark_failed(reloc_ctx *const *ctxs, int n)
 {
-    ctx->orb_latency_shape = prm.mode == RELOC_TICK_LOCAL || ctx_alone(ctx);
-    const int rc = orb_run_dev(ctx, img_dev, w, h, w * 3, 3, order, ctx->prm.nfeatures);
-    ctx->orb_latency_shape = true;
-    if (rc) return rc;
-    if (prm.mode != RELOC_TICK_GLOBAL) launch_candidates_local(ctx, prm);
+    if (ctxs && n >= 1 && n <= RELOC_BATCH_MAX)
+        for (int f = 0; f < n; ++f) if (ctxs[f]) ctxs[f]->tick_failed = true;
+}
+
+// the contexts of one call: one stream, device and database, equal feature capacity, matcher parameters, camera and lens
+// distortion, none twice; makes the device current
+static int ctx_batch_check(reloc_ctx *const *ctxs, int n, const char *who)
+{
+    ARG_CHECK(ctxs && n >= 1 && n <= RELOC_BATCH_MAX, who);
+    reloc_ctx *c0 = ctxs[0];
+    for (int f = 0; f < n; ++f) {
+        reloc_ctx *c = ctxs[f];
+        if (!c) { reloc_set_error("bad argument: %s: NULL context", who); return RELOC_E_ARG; }
+        if (!db_ready(c)) { reloc_set_error("no database uploaded"); return RELOC_E_STATE; }
+        if (c->stream != c0->stream || c->device != c0->device || c->db_desc != c0->db_desc || c->db_records != c0->db_records ||
+            c->max_feat != c0->max_feat || memcmp(&c->prm, &c0->prm, sizeof(reloc_params)) != 0 ||
+            memcmp(c->K4, c0->K4, sizeof(c->K4)) != 0 || memcmp(c->b2c_t, c0->b2c_t, sizeof(c->b2c_t)) != 0 ||
+            memcmp(c->b2c_R, c0->b2c_R, sizeof(c->b2c_R)) != 0 || memcmp(c->dist, c0->dist, sizeof(c->dist)) != 0) {
+            reloc_set_error("%s: the contexts must share one stream (reloc_set_stream), one device and one database "
+                            "(reloc_db_share) and have equal feature capacity, matcher parameters (reloc_set_params), camera "
+                            "(reloc_set_camera) and lens distortion (reloc_set_distortion)", who);
+            return RELOC_E_STATE;
+        }
+        for (int g = 0; g < f; ++g)
+            if (ctxs[g] == c) { reloc_set_error("bad argument: %s: a context appears twice", who); return RELOC_E_ARG; }
+    }
+    (void)hipSetDevice(c0->device);
     return RELOC_OK;
 }
 
-static int tick_scan_single(reloc_ctx *ctx, const TickParams &prm)
+// Kernels sized for latency (orb_run) where no whole-database scan runs beside them: a single frame of a tick of local
+// candidates, or of a context alone on the GPU (ctx_alone).  Never for several frames.
+static bool tick_latency(reloc_ctx *const *ctxs, int n, int mode)
 {
-    // G:329-344: only heading-compatible records are scored (the scan leaves count 0 on the others).  In AUTO
-    // mode the scan and the ranking stand down on the device when the local search has found candidates.
-    ScanMask mask;
-    mask.xyh = ctx->db_xy_heading;
-    for (int k = 0; k < 4; ++k) mask.q[k] = prm.base_pose[3 + k];
-    mask.cos_tol = prm.cos_tol;
-    mask.skip_if = prm.mode == RELOC_TICK_AUTO ? ctx->cand_n : nullptr;
-    reloc_prof_begin(ctx, RELOC_PROF_DB_SCAN);
-    const int rc = launch_db_count(ctx, ctx->f_desc, ctx->f_count, ctx->max_feat, ctx->db_counts, mask);
-    reloc_prof_end(ctx, RELOC_PROF_DB_SCAN);
-    return rc;
+    return n == 1 && (mode == RELOC_TICK_LOCAL || ctx_alone(ctxs[0]));
 }
 
-static int tick_end(reloc_ctx *ctx, const TickParams &prm, uint64_t seed)
-{
-    if (prm.mode != RELOC_TICK_LOCAL) launch_topk_counts(ctx, ctx->prm.global_max_candidates, ctx->cand_ids, nullptr, prm.mode == RELOC_TICK_AUTO);
-    return tick_solve(ctx, prm, seed);
-}
-
-// ---- frame-batched forms: n contexts on one stream, every stage ONE launch (blockIdx = frame) -----------------
-// scan_rows != NULL (sharded scan half): frame f's list goes to row f of scan_rows (2k + 2 int32: k ids, k counts, feature
-// count, 0) with id_base added; otherwise it becomes the frame's candidate list.
-static void launch_topk_counts_batch(reloc_ctx *const *ctxs, int n, int k, bool auto_mode, int id_base, int32_t *scan_rows)
+// Solve half: emit pass (mutual matches of every candidate in queryIdx order, with their 3-D / 2-D pairs, M:333-336), PnP,
+// finalisation.  cand_dev != NULL: the candidates are loaded from there first (k per frame, see k_set_candidates_batch),
+// with the relocation gates unless mode is RELOC_TICK_LOCAL.  res_ext_base != NULL: frame f's record also goes to
+// res_ext_base + f (device or pinned memory) instead of the context's reloc_tick_result_to target.
+static int solve_run(reloc_ctx *const *ctxs, int n, const int32_t *cand_dev, int k, const double *base_poses, int mode,
+                     int check_consistency, const uint64_t *seeds, TickResult *res_ext_base)
 {
     reloc_ctx *c0 = ctxs[0];
-    const int max_count = c0->db_max_rows < c0->max_feat ? c0->db_max_rows : c0->max_feat;
-    TopkBatch b;
-    for (int f = 0; f < RELOC_BATCH_MAX; ++f) {
-        reloc_ctx *c = ctxs[f < n ? f : 0];
-        TopkFrame &F = b.f[f];
-        int32_t *row = scan_rows ? scan_rows + (size_t)(f < n ? f : 0) * (2 * k + 2) : nullptr;
-        F.counts = c->db_counts;
-        F.out_ids = row ? row : c->cand_ids; F.out_counts = row ? row + k : nullptr; F.out_n = c->cand_n;
-        F.skip_if = auto_mode ? (const int32_t *)c->cand_n : (const int32_t *)nullptr;
-        F.relocating = c->tick_flags; F.f_count = c->f_count; F.out_nfeat = row ? row + 2 * k : nullptr;
+    const bool latency = tick_latency(ctxs, n, mode);
+    int rc;
+    if (cand_dev) {
+        SetCandBatch sb;
+        frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int) { sb.cand_ids[f] = c->cand_ids; sb.cand_n[f] = c->cand_n; sb.flags[f] = c->tick_flags; });
+        hipLaunchKernelGGL(k_set_candidates_batch, dim3(n), dim3(64), 0, c0->stream, cand_dev, k, sb, mode == RELOC_TICK_LOCAL ? 0 : 1);
     }
-    hipLaunchKernelGGL(k_topk_counts_batch, dim3(n), dim3(TOPK_HIST_THREADS), (size_t)(max_count + 2) * sizeof(int), c0->stream, b,
-                       (int)c0->db_records, k, id_base, c0->prm.min_matches, max_count);
+    if ((rc = launch_tick_emit(ctxs, n, latency))) return rc;
+    if ((rc = pnp_run_candidates(ctxs, n, seeds, latency))) return rc;
+    FinalBatch b;
+    frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int g) {
+        b.f[f] = final_frame(c, base_poses + 7 * g, res_ext_base ? res_ext_base + g : c->tick_res_ext, f < n ? tick_next_seq(c) : 0);
+    });
+    return launch_tick_finalize(ctxs, n, b, make_tick_params(c0, base_poses, mode, check_consistency));
 }
 
-// emit pass + PnP + finalisation of n frames: 1 + 3 + 1 launches.  res_ext_base != NULL: frame f's record also goes to
-// res_ext_base + f (device or pinned memory) instead of the context's reloc_tick_result_to target.
-static int tick_solve_batch(reloc_ctx *const *ctxs, int n, const double *base_poses, int mode, int check_consistency,
-                            const uint64_t *seeds, TickResult *res_ext_base)
+// The tick: ORB, local candidates (LOCAL / AUTO), whole-database scan and ranking (GLOBAL / AUTO), solve half.
+static int tick_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *imgs, int w, int h, int order, const double *base_poses,
+                    int mode, const uint64_t *seeds)
+{
+    reloc_ctx *c0 = ctxs[0];
+    if (c0->max_feat > 65535) { reloc_set_error("tick: max_feat must be <= 65535"); return RELOC_E_CAPACITY; }
+    const bool latency = tick_latency(ctxs, n, mode);
+    int rc;
+    if ((rc = orb_run(ctxs, n, imgs, w, h, w * 3, 3, order, c0->prm.nfeatures, latency))) return rc;
+    if (mode != RELOC_TICK_GLOBAL)
+        for (int f = 0; f < n; ++f) launch_candidates_local(ctxs[f], make_tick_params(ctxs[f], base_poses + 7 * f, mode, -1));
+    if (mode != RELOC_TICK_LOCAL) {
+        if ((rc = scan_counts(ctxs, n, base_poses, mode == RELOC_TICK_AUTO))) return rc;
+        TopkBatch b;
+        frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int) { b.f[f] = topk_frame(c, c->cand_ids, nullptr, nullptr, mode == RELOC_TICK_AUTO); });
+        launch_topk_counts(ctxs, n, b, c0->prm.global_max_candidates, 0);
+    }
+    return solve_run(ctxs, n, nullptr, 0, base_poses, mode, -1, seeds, nullptr);
+}
+
+// Scan half of the sharded tick: ORB, whole-database scan (heading mask when base_poses != NULL), ranking into out.
+static int scan_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *imgs, int w, int h, int order, const double *base_poses,
+                    const TopkBatch &out, int k, int id_base)
 {
     int rc;
-    if ((rc = launch_db_emit_batch(ctxs, n))) return rc;
-    if ((rc = pnp_run_candidates_batch(ctxs, n, MAX_CAND, seeds))) return rc;
-    reloc_ctx *c0 = ctxs[0];
-    const TickParams prm = make_tick_params(c0, base_poses, mode, check_consistency);
-    FinalBatch b;
-    for (int f = 0; f < RELOC_BATCH_MAX; ++f) {
-        const int g = f < n ? f : 0;
-        reloc_ctx *c = ctxs[g];
-        FinalFrame &F = b.f[f];
-        F.cand_ids = c->cand_ids; F.cand_n = c->cand_n; F.pnp = c->p_out; F.f_count = c->f_count; F.relocating = c->tick_flags;
-        F.res = c->tick_res; F.res_host = c->tick_res_host; F.res_ext = res_ext_base ? res_ext_base + g : c->tick_res_ext;
-        for (int k = 0; k < 7; ++k) F.base_pose[k] = base_poses[7 * g + k];
-        F.seq = f < n ? tick_next_seq(c) : 0;
-    }
-    hipLaunchKernelGGL(k_tick_finalize_batch, dim3(n), dim3(64), 0, c0->stream, b, c0->db_pose, prm);
+    if ((rc = orb_run(ctxs, n, imgs, w, h, w * 3, 3, order, ctxs[0]->prm.nfeatures, tick_latency(ctxs, n, RELOC_TICK_GLOBAL))))
+        return rc;
+    if ((rc = scan_counts(ctxs, n, base_poses, false))) return rc;
+    launch_topk_counts(ctxs, n, out, k, id_base);
     HIP_TRY(hipGetLastError());
     return RELOC_OK;
 }
@@ -760,60 +841,21 @@ static int tick_solve_batch(reloc_ctx *const *ctxs, int n, const double *base_po
 RELOC_API int reloc_tick_dev(reloc_ctx *ctx, const uint8_t *img_dev, int w, int h, int order, const double base_pose[7],
                              int global_reloc, uint64_t seed)
 {
-    if (ctx) ctx->tick_failed = true;         // until the finalisation has been enqueued (tick_next_seq)
+    tick_mark_failed(&ctx, 1);
     ARG_CHECK_CTX(ctx, img_dev && base_pose && w >= 64 && h >= 64 && global_reloc >= 0 && global_reloc <= 2, "reloc_tick_dev");
-    if (!db_ready(ctx)) { reloc_set_error("no database uploaded"); return RELOC_E_STATE; }
-    if (ctx->max_feat > 65535) { reloc_set_error("tick: max_feat must be <= 65535"); return RELOC_E_CAPACITY; }
-    int rc;
-    const TickParams prm = make_tick_params(ctx, base_pose, global_reloc, -1);
-    if ((rc = tick_begin(ctx, img_dev, w, h, order, prm))) return rc;
-    if (prm.mode != RELOC_TICK_LOCAL && (rc = tick_scan_single(ctx, prm))) return rc;
-    return tick_end(ctx, prm, seed);
+    if (int rc = ctx_batch_check(&ctx, 1, "reloc_tick_dev")) return rc;
+    return tick_run(&ctx, 1, &img_dev, w, h, order, base_pose, global_reloc, &seed);
 }
 
 RELOC_API int reloc_tick_batch_dev(reloc_ctx *const *ctxs, int n, const uint8_t *const *imgs_dev, int w, int h, int order,
                                    const double *base_poses, int global_reloc, const uint64_t *seeds)
 {
-    if (ctxs && n >= 1 && n <= 8)
-        for (int f = 0; f < n; ++f) if (ctxs[f]) ctxs[f]->tick_failed = true;
+    tick_mark_failed(ctxs, n);
     ARG_CHECK(ctxs && imgs_dev && base_poses && n >= 1 && n <= 8 && w >= 64 && h >= 64 && global_reloc >= 0 && global_reloc <= 2,
               "reloc_tick_batch_dev");
-    for (int f = 0; f < n; ++f) {
-        reloc_ctx *c = ctxs[f];
-        ARG_CHECK(c && imgs_dev[f], "reloc_tick_batch_dev: NULL context or frame");
-        if (!db_ready(c)) { reloc_set_error("no database uploaded"); return RELOC_E_STATE; }
-        if (c->stream != ctxs[0]->stream || c->device != ctxs[0]->device || c->db_desc != ctxs[0]->db_desc ||
-            c->db_records != ctxs[0]->db_records || c->max_feat != ctxs[0]->max_feat ||
-            memcmp(&c->prm, &ctxs[0]->prm, sizeof(reloc_params)) != 0 || memcmp(c->K4, ctxs[0]->K4, sizeof(c->K4)) != 0 ||
-            memcmp(c->b2c_t, ctxs[0]->b2c_t, sizeof(c->b2c_t)) != 0 || memcmp(c->b2c_R, ctxs[0]->b2c_R, sizeof(c->b2c_R)) != 0 ||
-            memcmp(c->dist, ctxs[0]->dist, sizeof(c->dist)) != 0) {
-            reloc_set_error("tick batch: the contexts must share one stream (reloc_set_stream), one device and one database "
-                            "(reloc_db_share) and have equal feature capacity, matcher parameters (reloc_set_params), camera "
-                            "(reloc_set_camera) and lens distortion (reloc_set_distortion)");
-            return RELOC_E_STATE;
-        }
-        for (int g = 0; g < f; ++g) ARG_CHECK(ctxs[g] != c, "reloc_tick_batch_dev: a context appears twice");
-    }
-    (void)hipSetDevice(ctxs[0]->device);
-    int rc;
-    double q[8 * 4];
-    for (int f = 0; f < n; ++f)
-        for (int k = 0; k < 4; ++k) q[4 * f + k] = base_poses[7 * f + 3 + k];
-    // every stage of the batch is ONE launch with the frame as a grid dimension: ORB 5, local candidates n (LOCAL / AUTO
-    // only), scan 1, ranking 1, emit 1, PnP 3, finalisation 1 -- 12 launches for 8 frames in whole-database mode instead
-    // of the 100 of eight per-frame ticks (their serial chain of small kernels was what a batch spent its time on)
-    if ((rc = orb_run_batch_dev(ctxs, n, imgs_dev, w, h, w * 3, order, ctxs[0]->prm.nfeatures))) return rc;
-    const TickParams prm0 = make_tick_params(ctxs[0], base_poses, global_reloc, -1);
-    if (global_reloc != RELOC_TICK_GLOBAL)
-        for (int f = 0; f < n; ++f) launch_candidates_local(ctxs[f], make_tick_params(ctxs[f], base_poses + 7 * f, global_reloc, -1));
-    if (global_reloc != RELOC_TICK_LOCAL) {
-        reloc_prof_begin(ctxs[0], RELOC_PROF_DB_SCAN);
-        rc = launch_db_scan_batch(ctxs, n, q, prm0.cos_tol, global_reloc == RELOC_TICK_AUTO);
-        reloc_prof_end(ctxs[0], RELOC_PROF_DB_SCAN);
-        if (rc) return rc;
-        launch_topk_counts_batch(ctxs, n, ctxs[0]->prm.global_max_candidates, global_reloc == RELOC_TICK_AUTO, 0, nullptr);
-    }
-    return tick_solve_batch(ctxs, n, base_poses, global_reloc, -1, seeds, nullptr);
+    for (int f = 0; f < n; ++f) ARG_CHECK(imgs_dev[f], "reloc_tick_batch_dev: NULL frame");
+    if (int rc = ctx_batch_check(ctxs, n, "reloc_tick_batch_dev")) return rc;
+    return tick_run(ctxs, n, imgs_dev, w, h, order, base_poses, global_reloc, seeds);
 }
 
 // Waits for the result record of the LAST tick enqueued on this context by polling its sequence stamp in pinned host memory
@@ -905,110 +947,43 @@ RELOC_API int reloc_tick_scan_dev(reloc_ctx *ctx, const uint8_t *img_dev, int w,
 {
     ARG_CHECK_CTX(ctx, img_dev && topk_ids_dev && topk_counts_dev && k > 0 && k <= MAX_CAND && w >= 64 && h >= 64,
               "reloc_tick_scan_dev");
-    if (!db_ready(ctx)) { reloc_set_error("no database uploaded"); return RELOC_E_STATE; }
-    int rc;
-    ctx->orb_latency_shape = ctx_alone(ctx);                // the sharded tick scans: a neighbour of scans unless the ctx is alone
-    rc = orb_run_dev(ctx, img_dev, w, h, w * 3, 3, order, ctx->prm.nfeatures);
-    ctx->orb_latency_shape = true;
-    if (rc) return rc;
-    ScanMask mask;
-    if (base_pose) {
-        mask.xyh = ctx->db_xy_heading;
-        for (int k = 0; k < 4; ++k) mask.q[k] = base_pose[3 + k];
-    }
-    mask.cos_tol = heading_cos_tol_host(ctx);
-    reloc_prof_begin(ctx, RELOC_PROF_DB_SCAN);
-    rc = launch_db_count(ctx, ctx->f_desc, ctx->f_count, ctx->max_feat, ctx->db_counts, mask);
-    reloc_prof_end(ctx, RELOC_PROF_DB_SCAN);
-    if (rc) return rc;
-    launch_topk_counts(ctx, k, topk_ids_dev, topk_counts_dev, false);
-    HIP_TRY(hipGetLastError());
-    return RELOC_OK;
-}
-
-__global__ void k_set_candidates(const int32_t *__restrict__ ids, int n, int32_t *__restrict__ cand_ids, int32_t *__restrict__ cand_n)
-{
-    if (threadIdx.x == 0) {
-        int m = 0;
-        for (int i = 0; i < n; ++i)
-            if (ids[i] >= 0) cand_ids[m++] = ids[i];
-        *cand_n = m;
-    }
-}
-
-struct SetCandBatch { int32_t *cand_ids[RELOC_BATCH_MAX], *cand_n[RELOC_BATCH_MAX], *flags[RELOC_BATCH_MAX]; };
-__global__ void k_set_candidates_batch(const int32_t *__restrict__ ids, int k, SetCandBatch b, int flag)
-{
-    const int f = blockIdx.x;
-    if (threadIdx.x == 0) {
-        int m = 0;
-        for (int i = 0; i < k; ++i)
-            if (ids[f * k + i] >= 0) b.cand_ids[f][m++] = ids[f * k + i];
-        *b.cand_n[f] = m;
-        *b.flags[f] = flag;
-    }
+    if (int rc = ctx_batch_check(&ctx, 1, "reloc_tick_scan_dev")) return rc;
+    TopkBatch out;
+    frame_slots(&ctx, 1, [&](int f, reloc_ctx *c, int) { out.f[f] = topk_frame(c, topk_ids_dev, topk_counts_dev, nullptr, false); });
+    return scan_run(&ctx, 1, &img_dev, w, h, order, base_pose, out, k, 0);
 }
 
 RELOC_API int reloc_tick_solve_dev(reloc_ctx *ctx, const int32_t *cand_ids_dev, int n_cand, const double base_pose[7],
                                    int check_consistency, uint64_t seed)
 {
-    if (ctx) ctx->tick_failed = true;
+    tick_mark_failed(&ctx, 1);
     ARG_CHECK_CTX(ctx, cand_ids_dev && base_pose && n_cand >= 0 && n_cand <= MAX_CAND, "reloc_tick_solve_dev");
-    if (!db_ready(ctx)) { reloc_set_error("no database uploaded"); return RELOC_E_STATE; }
-    hipLaunchKernelGGL(k_set_candidates, dim3(1), dim3(64), 0, ctx->stream, cand_ids_dev, n_cand, ctx->cand_ids, ctx->cand_n);
+    if (int rc = ctx_batch_check(&ctx, 1, "reloc_tick_solve_dev")) return rc;
     // candidates of a sharded whole-database search carry the relocation gates unless the caller asks for the
     // consistency check (= local candidates)
-    hipLaunchKernelGGL(k_set_flag, dim3(1), dim3(1), 0, ctx->stream, ctx->tick_flags, check_consistency ? 0 : 1);
-    const TickParams prm = make_tick_params(ctx, base_pose, check_consistency ? RELOC_TICK_LOCAL : RELOC_TICK_GLOBAL, check_consistency);
-    return tick_solve(ctx, prm, seed);
+    return solve_run(&ctx, 1, cand_ids_dev, n_cand, base_pose, check_consistency ? RELOC_TICK_LOCAL : RELOC_TICK_GLOBAL,
+                     check_consistency, &seed, nullptr);
 }
 
 // ---- sharded database, batched and device-resident (BASELINE.json config 4) ---------------------------------------
 // One call per half and batch, so a rank's host enqueues a batch of 8 frames with three calls instead of ~40: the
 // contexts of a batch share ONE stream and one shard (as for reloc_tick_batch_dev), and the exchange between the halves
 // (RCCL all-gather of the rows written here) is enqueued on that same stream by the caller.
-static int shard_batch_check(reloc_ctx *const *ctxs, int n, const char *what)
-{
-    ARG_CHECK(ctxs && n >= 1 && n <= 8, what);
-    for (int f = 0; f < n; ++f) {
-        reloc_ctx *c = ctxs[f];
-        ARG_CHECK(c, "shard batch: NULL context");
-        if (!db_ready(c)) { reloc_set_error("no database uploaded"); return RELOC_E_STATE; }
-        if (c->stream != ctxs[0]->stream || c->device != ctxs[0]->device || c->db_desc != ctxs[0]->db_desc ||
-            c->db_records != ctxs[0]->db_records || c->max_feat != ctxs[0]->max_feat ||
-            memcmp(&c->prm, &ctxs[0]->prm, sizeof(reloc_params)) != 0 || memcmp(c->K4, ctxs[0]->K4, sizeof(c->K4)) != 0 ||
-            memcmp(c->b2c_t, ctxs[0]->b2c_t, sizeof(c->b2c_t)) != 0 || memcmp(c->b2c_R, ctxs[0]->b2c_R, sizeof(c->b2c_R)) != 0 ||
-            memcmp(c->dist, ctxs[0]->dist, sizeof(c->dist)) != 0) {
-            reloc_set_error("shard batch: the contexts must share one stream (reloc_set_stream), one device and one database "
-                            "(reloc_db_share) and have equal feature capacity, matcher parameters, camera and lens distortion");
-            return RELOC_E_STATE;
-        }
-        for (int g = 0; g < f; ++g) ARG_CHECK(ctxs[g] != c, "shard batch: a context appears twice");
-    }
-    return RELOC_OK;
-}
-
 RELOC_API int reloc_shard_scan_batch_dev(reloc_ctx *const *ctxs, int n, const uint8_t *const *imgs_dev, int w, int h, int order,
                                          const double *base_poses, int k, int64_t id_base, int32_t *scan_out_dev)
 {
-    int rc = shard_batch_check(ctxs, n, "reloc_shard_scan_batch_dev");
+    int rc = ctx_batch_check(ctxs, n, "reloc_shard_scan_batch_dev");
     if (rc) return rc;
     ARG_CHECK(imgs_dev && scan_out_dev && k > 0 && k <= MAX_CAND && w >= 64 && h >= 64 && id_base >= 0 &&
               id_base + ctxs[0]->db_records <= 0x7fffffff, "reloc_shard_scan_batch_dev");
-    (void)hipSetDevice(ctxs[0]->device);
-    double q[8 * 4];
-    for (int f = 0; f < n; ++f) {
-        ARG_CHECK(imgs_dev[f], "reloc_shard_scan_batch_dev: NULL frame");
-        for (int j = 0; j < 4; ++j) q[4 * f + j] = base_poses ? base_poses[7 * f + 3 + j] : (j == 3 ? 1.0 : 0.0);
-    }
-    if ((rc = orb_run_batch_dev(ctxs, n, imgs_dev, w, h, w * 3, order, ctxs[0]->prm.nfeatures))) return rc;
-    reloc_prof_begin(ctxs[0], RELOC_PROF_DB_SCAN);
-    rc = launch_db_scan_batch(ctxs, n, q, heading_cos_tol_host(ctxs[0]), false, base_poses != nullptr);
-    reloc_prof_end(ctxs[0], RELOC_PROF_DB_SCAN);
-    if (rc) return rc;
-    launch_topk_counts_batch(ctxs, n, k, false, (int)id_base, scan_out_dev);
-    HIP_TRY(hipGetLastError());
-    return RELOC_OK;
+    for (int f = 0; f < n; ++f) ARG_CHECK(imgs_dev[f], "reloc_shard_scan_batch_dev: NULL frame");
+    // frame f's list goes to row f of scan_out_dev: 2k + 2 int32 (k ids + id_base, k counts, feature count, 0)
+    TopkBatch out;
+    frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int g) {
+        int32_t *row = scan_out_dev + (size_t)g * (2 * k + 2);
+        out.f[f] = topk_frame(c, row, row + k, row + 2 * k, false);
+    });
+    return scan_run(ctxs, n, imgs_dev, w, h, order, base_poses, out, k, (int)id_base);
 }
 
 // The merge every rank performs on the gathered lists (G:342-343 over the whole database): per frame the k best
@@ -1061,20 +1036,12 @@ RELOC_API int reloc_shard_merge_dev(reloc_ctx *ctx, const int32_t *all_scan_dev,
 RELOC_API int reloc_shard_solve_batch_dev(reloc_ctx *const *ctxs, int n, const int32_t *cand_local_dev, int k,
                                           const double *base_poses, const uint64_t *seeds, void *res_out)
 {
-    if (ctxs && n >= 1 && n <= 8)
-        for (int f = 0; f < n; ++f) if (ctxs[f]) ctxs[f]->tick_failed = true;
-    int rc = shard_batch_check(ctxs, n, "reloc_shard_solve_batch_dev");
+    tick_mark_failed(ctxs, n);
+    int rc = ctx_batch_check(ctxs, n, "reloc_shard_solve_batch_dev");
     if (rc) return rc;
     ARG_CHECK(cand_local_dev && base_poses && res_out && k > 0 && k <= MAX_CAND, "reloc_shard_solve_batch_dev");
-    (void)hipSetDevice(ctxs[0]->device);
-    SetCandBatch sb;
-    for (int f = 0; f < RELOC_BATCH_MAX; ++f) {
-        reloc_ctx *c = ctxs[f < n ? f : 0];
-        sb.cand_ids[f] = c->cand_ids; sb.cand_n[f] = c->cand_n; sb.flags[f] = c->tick_flags;
-    }
-    // candidates of a whole-database search: relocation gates (flag 1), no consistency check
-    hipLaunchKernelGGL(k_set_candidates_batch, dim3(n), dim3(64), 0, ctxs[0]->stream, cand_local_dev, k, sb, 1);
-    return tick_solve_batch(ctxs, n, base_poses, RELOC_TICK_GLOBAL, 0, seeds, (TickResult *)res_out);
+    // candidates of a whole-database search: relocation gates, no consistency check
+    return solve_run(ctxs, n, cand_local_dev, k, base_poses, RELOC_TICK_GLOBAL, 0, seeds, (TickResult *)res_out);
 }
 
 // read back the per-candidate PnP records of the last tick (parity taps for tests)

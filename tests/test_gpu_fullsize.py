@@ -249,7 +249,8 @@ def test_config4_through_rccl_at_world_size_1(order):
 def test_batched_tick_one_scan_launch_for_several_frames(engine, config4):
     """reloc_tick_batch_dev: 8 contexts on ONE stream sharing the 100k-record database, ORB per frame, one scan launch
     for the 8 frames (workgroup b scans frame b % 8 with its own ticket counters), ranking / PnP per frame == the
-    per-frame tick; twice, and once with 3 frames, so the ticket counters must have been put back"""
+    per-frame tick; twice, and once each with 3 frames and with 1 (the single-context launches), so the ticket counters
+    must have been put back"""
     from nclt_slam_project_amd.engine import Engine
     frames, db, base_poses, ref = config4
     es = [engine] + [Engine(0, 1280, 720, 8192) for _ in range(7)]
@@ -258,7 +259,7 @@ def test_batched_tick_one_scan_launch_for_several_frames(engine, config4):
         e.set_stream(engine.stream_ptr)
     fdev = [engine.to_device(f) for f in frames]
     recs = engine.pinned((8, 96), np.uint8)                    # one pinned result record per frame (reloc_tick_result_to)
-    for n in (8, 3, 8):
+    for n in (8, 3, 1, 8):
         recs[...] = 0xEE
         for f in range(n):
             es[f].tick_result_to(recs[f])
