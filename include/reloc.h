@@ -262,6 +262,34 @@ int reloc_get_clahe(reloc_ctx *ctx, double *clip_limit, int32_t *tiles_x, int32_
 int reloc_clahe_u8(reloc_ctx *ctx, const uint8_t *gray, int w, int h, int stride, double clip_limit, int tiles_x,
                    int tiles_y, uint8_t *out);
 
+/* ---- rectification (include/reloc_spec.h, "REMAP") ------------------------------------------------ */
+/* cv2.remap(gray, map1, map2, INTER_LINEAR) with BORDER_CONSTANT 0 in front of ORB (and of CLAHE) on 3-channel frames, with
+ * the map in OpenCV's fixed-point form: xy = int16[h][w][2] (CV_16SC2), alpha = uint16[h][w] (CV_16UC1), as
+ * cv2.convertMaps / cv2.initUndistortRectifyMap(..., CV_16SC2) hand them back.  Host pointers, copied into memory the context
+ * owns (allocated on the first enable).  xy == NULL turns it off (the default of a new context; the launch sequence is then
+ * that of a context that never had a map).  w, h within the context's capacity (RELOC_E_CAPACITY); every frame passed later
+ * must be exactly w x h, else RELOC_E_ARG.  Applied by the entry points that apply CLAHE, before it: frame -> gray + remap ->
+ * [CLAHE] -> ORB.  reloc_record_frame and reloc_tick_accumulate_dev also read the depth through the map
+ * (cv2.remap(depth, xy, alpha, INTER_NEAREST), border 0 = no depth).  Never applied by reloc_orb_detect_compute,
+ * reloc_gray_u8 or reloc_clahe_u8.  Batched calls refuse contexts that are not all on with one map size or all off
+ * (RELOC_E_STATE); the map contents may differ per context (a stereo pair).  Independent of reloc_set_camera and
+ * reloc_set_distortion: a rectified camera is normally a pinhole with the newCameraMatrix the map was built for, and it is
+ * the caller who sets that matrix and leaves the distortion empty.  reloc_get_rectify_map returns (0, 0) when off. */
+int reloc_set_rectify_map(reloc_ctx *ctx, const int16_t *xy, const uint16_t *alpha, int w, int h);
+int reloc_get_rectify_map(reloc_ctx *ctx, int32_t *w, int32_t *h);
+/* cv2.remap on a caller's image (cv2 shim): src is sw x sh with 1 or 3 interleaved channels, the map and out are dw x dh,
+ * dense; any sizes >= 1 within the capacity.  nearest = 0: INTER_LINEAR; nearest = 1: INTER_NEAREST (the pixel at xy; alpha
+ * may be NULL).  BORDER_CONSTANT with border_value in every channel.  reloc_remap_u16: single channel, nearest only (depth).
+ * sstride in bytes.  Host pointers; synchronous. */
+int reloc_remap_u8(reloc_ctx *ctx, const uint8_t *src, int sw, int sh, int sstride, int channels, const int16_t *xy,
+                   const uint16_t *alpha, int dw, int dh, int nearest, int border_value, uint8_t *out);
+int reloc_remap_u16(reloc_ctx *ctx, const uint16_t *src, int sw, int sh, int sstride, const int16_t *xy, int dw, int dh,
+                    int border_value, uint16_t *out);
+/* cv2.convertMaps(mapx, mapy, CV_16SC2, nninterpolation): float32 w x h maps to the fixed-point pair; with nninterpolation
+ * xy is the rounded coordinate and alpha is 0.  Host pointers; synchronous. */
+int reloc_convert_maps(reloc_ctx *ctx, const float *mapx, const float *mapy, int w, int h, int nninterpolation,
+                       int16_t *xy_out, uint16_t *alpha_out);
+
 /* ---- fused tick ----------------------------------------------------------------------------- */
 #define RELOC_TICK_LOCAL   0   /* candidates by VIO distance / heading only                          M:293-302 */
 #define RELOC_TICK_GLOBAL  1   /* whole-database search unconditionally (the benchmarked shape)       G:329-344 */

@@ -150,4 +150,30 @@
 #define RELOC_CLAHE_BINS         256
 #define RELOC_CLAHE_MAX_TILES    64   /* per grid dimension (reloc_set_clahe, reloc_clahe_u8) */
 
+/* REMAP: cv2.remap(src, map1, map2, INTER_LINEAR | INTER_NEAREST, BORDER_CONSTANT, borderValue) on 8-bit images (nearest also
+ * 16-bit), cv2.convertMaps and the map builders, restated from OpenCV 4.x modules/imgproc/src/imgwarp.cpp and
+ * modules/calib3d/src/undistort.dispatch.cpp / fisheye.cpp (the reference: datasets/nclt/scripts/run_all_visual_slam.py:182,217,
+ * datasets/rover/scripts/rectify_t265_stereo.py:113-156; not pinned against a cv2 build):
+ *   fixed-point map   sx = cvRound(mapx * 32), sy = cvRound(mapy * 32): f32 product (exact), half to even, saturating to int32,
+ *              NaN -> INT32_MIN (so NaN, +-inf and out-of-range values land outside every image);
+ *              xy = (saturate_cast<short>(sx >> 5), saturate_cast<short>(sy >> 5)), arithmetic shifts;
+ *              alpha = (sy & 31) * 32 + (sx & 31).  This is convertMaps(mapx, mapy, CV_16SC2) and what remap does with float
+ *              maps.  The library stores and takes only this form.
+ *   bilinear   taps p00 = src(y, x), p01 = src(y, x + 1), p10 = src(y + 1, x), p11 = src(y + 1, x + 1), (x, y) = xy,
+ *              fx = alpha & 31, fy = alpha >> 5, weights 32 * {(32 - fx)(32 - fy), fx (32 - fy), (32 - fx) fy, fx fy} (sum 32768),
+ *              dst = (p00 w0 + p01 w1 + p10 w2 + p11 w3 + (1 << 14)) >> 15, per channel.  OpenCV's weight table differs from the
+ *              closed form in one entry (alpha 0: {32767, 0, 0, 1} after its saturate-and-fix-up step); the byte is the same
+ *              for every alpha and every tap combination (|p11 - p00| < 2^14), tests/test_remap_host.py repeats the check.
+ *   border     BORDER_CONSTANT only: each tap outside the source is replaced by the border value on its own.
+ *   nearest    fixed-point map: the pixel at xy, the fraction ignored; float maps: (cvRound(mapx), cvRound(mapy)) saturated to
+ *              short (convertMaps with nninterpolation); outside: the border value.
+ *   builders   host, float64 (once per camera): initUndistortRectifyMap: (x, y, w) = (newK R)^-1 (u, v, 1), x' = x / w,
+ *              y' = y / w, r2 = x'^2 + y'^2, kr = (1 + ((k3 r2 + k2) r2 + k1) r2) / (1 + ((k6 r2 + k5) r2 + k4) r2),
+ *              xd = x' kr + 2 p1 x' y' + p2 (r2 + 2 x'^2) + s1 r2 + s2 r2^2, yd = y' kr + p1 (r2 + 2 y'^2) + 2 p2 x' y' + s3 r2 +
+ *              s4 r2^2, tilt(tauX, tauY) applied to (xd, yd, 1), map = (fx xd + cx, fy yd + cy); CV_32FC1: cast to f32;
+ *              CV_16SC2: iu = saturate_cast<int>(u * 32) on the double (half to even), then as above.
+ *              fisheye: theta = atan(r), theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8),
+ *              scale = r == 0 ? 1 : theta_d / r, map = (fx x' scale + cx, fy y' scale + cy) (K without skew). */
+#define RELOC_REMAP_INTER_BITS   5    /* 32 sub-pixel steps per axis, 1024 alphas */
+
 #endif /* RELOC_SPEC_H */

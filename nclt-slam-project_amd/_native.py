@@ -65,6 +65,11 @@ SIGNATURES = {
     "reloc_set_clahe": (C.c_int, [c_ctx, f64, C.c_int, C.c_int]),
     "reloc_get_clahe": (C.c_int, [c_ctx, P, P, P]),
     "reloc_clahe_u8": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, f64, C.c_int, C.c_int, P]),
+    "reloc_set_rectify_map": (C.c_int, [c_ctx, P, P, C.c_int, C.c_int]),
+    "reloc_get_rectify_map": (C.c_int, [c_ctx, P, P]),
+    "reloc_remap_u8": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, C.c_int, C.c_int, C.c_int, C.c_int, P]),
+    "reloc_remap_u16": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, P, C.c_int, C.c_int, C.c_int, P]),
+    "reloc_convert_maps": (C.c_int, [c_ctx, P, P, C.c_int, C.c_int, C.c_int, P, P]),
     "reloc_tick_debug": (C.c_int, [c_ctx, P, P, P, P, P, P, P]),
     "reloc_tick": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, P, C.c_int, u64, P, P, P, P, P, P]),
     "reloc_get_params": (C.c_int, [c_ctx, P]),

@@ -330,6 +330,13 @@ struct reloc_ctx {
     uint8_t *clahe_plane = nullptr;      // equalised gray plane, row stride (w + 63) & ~63 (allocated on first enable)
     uint8_t *clahe_lut = nullptr;        // tiles_y x tiles_x x 256 LUTs (64 x 64 x 256 bytes, allocated with the plane)
 
+    // ---- rectification in front of ORB and CLAHE on 3-channel frames (reloc_set_rectify_map); 0 x 0 = off, the default ----
+    int rect_w = 0, rect_h = 0;          // map = frame size
+    int16_t *rect_xy = nullptr;          // max_h x max_w x 2, dense rows of rect_w; allocated on first enable, one block with the three below
+    uint16_t *rect_alpha = nullptr;      // max_h x max_w
+    uint8_t *rect_plane = nullptr;       // rectified gray plane, row stride (w + 63) & ~63
+    uint16_t *rect_depth = nullptr;      // rectified depth (nearest), dense rows of rect_w
+
     // ---- matcher parameters (reloc_set_params) ----
     reloc_params prm;
     int scan_gens = 0;               // RELOC_SCAN_GENS (developer switch), read once at creation: n > 0 = single whole-database
@@ -415,9 +422,11 @@ int db_reindex(reloc_ctx *ctx);
 int db_reserve(reloc_ctx *ctx, int64_t cap_records, int64_t cap_rows);
 inline bool db_ready(const reloc_ctx *ctx) { return ctx->db_desc && ctx->db_off && ctx->db_pose && ctx->db_xy_heading && ctx->db_counts && ctx->db_records > 0; }
 int orb_prepare(reloc_ctx *ctx, int w, int h, int nfeatures);
-// ORB of frame f = srcs[f] into ctxs[f]'s feature buffers; channels == 3 -> interleaved frames (gray fused, CLAHE first when
-// the contexts have it on), channels == 1 -> gray planes (reloc_orb.hip)
+// ORB of frame f = srcs[f] into ctxs[f]'s feature buffers; channels == 3 -> interleaved frames (gray fused; rectification, then
+// CLAHE first when the contexts have them on), channels == 1 -> gray planes (reloc_orb.hip)
 int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, int h, int stride, int channels, int order,
             int nfeatures, bool latency);
+// the depth image of a context with a rectification map read through the map (nearest) into the context's depth plane
+int rectify_depth(reloc_ctx *ctx, const uint16_t *depth_dev, int w, int h, const uint16_t **out);
 // PnP-RANSAC of every context's candidates with the matcher parameters of ctxs[0]; seeds: one per frame, or NULL (reloc_pnp.hip)
 int pnp_run_candidates(reloc_ctx *const *ctxs, int n, const uint64_t *seeds, bool latency);

@@ -1258,6 +1258,176 @@ static int clahe_launch(hipStream_t st, const ClaheFrames &F, int n, const Clahe
 
 static inline int clahe_stride(int w) { return (w + 63) & ~63; }
 
+// ---- rectification: cv2.remap (include/reloc_spec.h, "REMAP") -----------------------------------------------
+// OpenCV's fixed-point bilinear remap of 8-bit images through a map in the CV_16SC2 + CV_16UC1 form, BORDER_CONSTANT:
+//   k_remap_u8<CH, GRAY>   4 output pixels per lane along x; the four taps of each pixel gathered through the cache (a
+//                          rectification map is locally coherent: neighbouring lanes share lines).  CH = 3, GRAY: the
+//                          stage in front of ORB -- gray of every tap on the fly (gray_fixed with the order / coefficient
+//                          flags), then the blend, one dword store.  CH = 3 (3-channel output) and CH = 1 serve the shim.
+//   k_remap_nearest<T, CH> the source pixel at xy (the fraction is ignored); T = uint16_t for the depth image
+//   k_convert_maps         float maps -> the fixed-point form (cv2.convertMaps)
+// All are frame-batched (blockIdx.y = frame) with per-frame map pointers; a single frame is a batch of one.
+struct RemapFrames {
+    const uint8_t *src[RELOC_BATCH_MAX]; const int16_t *xy[RELOC_BATCH_MAX]; const uint16_t *alpha[RELOC_BATCH_MAX];
+    uint8_t *dst[RELOC_BATCH_MAX];
+};
+struct RemapGeom {
+    int sw, sh, sstride;   // source size, row stride in bytes
+    int dw, dh, dstride;   // map = destination size (maps are dense), destination row stride in bytes
+    int border;            // BORDER_CONSTANT value
+};
+
+// one tap: the source pixel (x, y) or the border value; GRAY converts the 3 channels to one value
+template <int CH, bool GRAY>
+__device__ __forceinline__ void remap_tap(const uint8_t *__restrict__ src, const RemapGeom &g, int x, int y, int flags,
+                                          int (&v)[GRAY ? 1 : CH])
+{
+    const bool in = (unsigned)x < (unsigned)g.sw && (unsigned)y < (unsigned)g.sh;
+#pragma unroll
+    for (int c = 0; c < (GRAY ? 1 : CH); ++c) v[c] = g.border;
+    if (!in) return;
+    const uint8_t *p = src + (size_t)y * g.sstride + CH * x;
+    if (GRAY) {
+        const int c0 = p[0], c1 = p[1], c2 = p[2];
+        v[0] = gray_fixed((flags & 1) ? c2 : c0, c1, (flags & 1) ? c0 : c2, flags);
+    } else {
+#pragma unroll
+        for (int c = 0; c < CH; ++c) v[c] = p[c];
+    }
+}
+
+template <int CH, bool GRAY, bool ALIGNED>
+__global__ __launch_bounds__(256) void k_remap_u8(RemapFrames F, RemapGeom g, int flags)
+{
+    constexpr int OC = GRAY ? 1 : CH;       // output channels
+    const int quads = (g.dw + 3) >> 2;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= quads * g.dh) return;
+    const int y = q / quads, x4 = 4 * (q - y * quads);
+    const size_t m = (size_t)y * g.dw + x4;
+    const int16_t *xyp = F.xy[blockIdx.y] + 2 * m;
+    const uint16_t *ap = F.alpha[blockIdx.y] + m;
+    u32 xy[4], al[4];
+    if (ALIGNED) {      // dw % 4 == 0 and 16-byte aligned maps: 16 B of xy and 8 B of alpha per lane
+        const uint4 a = *reinterpret_cast<const uint4 *>(xyp);
+        const uint2 b = *reinterpret_cast<const uint2 *>(ap);
+        xy[0] = a.x; xy[1] = a.y; xy[2] = a.z; xy[3] = a.w;
+        al[0] = b.x & 0xFFFF; al[1] = b.x >> 16; al[2] = b.y & 0xFFFF; al[3] = b.y >> 16;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const bool ok = x4 + k < g.dw;
+            xy[k] = ok ? reinterpret_cast<const u32 *>(xyp)[k] : 0;
+            al[k] = ok ? ap[k] : 0;
+        }
+    }
+    const uint8_t *src = F.src[blockIdx.y];
+    int out[4][OC];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int sx = (int16_t)(xy[k] & 0xFFFF), sy = (int16_t)(xy[k] >> 16);
+        const int fx = al[k] & 31, fy = (al[k] >> 5) & 31;
+        int p00[OC], p01[OC], p10[OC], p11[OC];
+        remap_tap<CH, GRAY>(src, g, sx, sy, flags, p00);
+        remap_tap<CH, GRAY>(src, g, sx + 1, sy, flags, p01);
+        remap_tap<CH, GRAY>(src, g, sx, sy + 1, flags, p10);
+        remap_tap<CH, GRAY>(src, g, sx + 1, sy + 1, flags, p11);
+        const int w00 = 32 * (32 - fx) * (32 - fy), w01 = 32 * fx * (32 - fy), w10 = 32 * (32 - fx) * fy, w11 = 32 * fx * fy;
+#pragma unroll
+        for (int c = 0; c < OC; ++c) out[k][c] = (p00[c] * w00 + p01[c] * w01 + p10[c] * w10 + p11[c] * w11 + (1 << 14)) >> 15;
+    }
+    uint8_t *dst = F.dst[blockIdx.y] + (size_t)y * g.dstride + OC * x4;
+    if (OC == 1 && (g.dstride & 3) == 0) {
+        // the row holds round4(dw) bytes: dstride >= dw and a multiple of 4
+        *reinterpret_cast<u32 *>(dst) = (u32)out[0][0] | (u32)out[1][0] << 8 | (u32)out[2][0] << 16 | (u32)out[3][0] << 24;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (x4 + k < g.dw) {
+#pragma unroll
+                for (int c = 0; c < OC; ++c) dst[OC * k + c] = (uint8_t)out[k][c];
+            }
+    }
+}
+
+// nearest: one output pixel per lane; strides of src and dst in elements of T
+template <typename T, int CH>
+__global__ __launch_bounds__(256) void k_remap_nearest(RemapFrames F, RemapGeom g)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.z;
+    if (x >= g.dw) return;
+    const u32 xy = reinterpret_cast<const u32 *>(F.xy[blockIdx.y])[(size_t)y * g.dw + x];
+    const int sx = (int16_t)(xy & 0xFFFF), sy = (int16_t)(xy >> 16);
+    const bool in = (unsigned)sx < (unsigned)g.sw && (unsigned)sy < (unsigned)g.sh;
+    const T *s = reinterpret_cast<const T *>(F.src[blockIdx.y]) + (size_t)(in ? sy : 0) * g.sstride + CH * (in ? sx : 0);
+    T *d = reinterpret_cast<T *>(F.dst[blockIdx.y]) + (size_t)y * g.dstride + CH * x;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) d[c] = in ? s[c] : (T)g.border;
+}
+
+// cvRound of an f32 to int32: half to even, saturating; NaN -> INT32_MIN (both far outside every image)
+__device__ __forceinline__ int remap_round(float v)
+{
+    if (v != v) return INT32_MIN;
+    const float r = rintf(v);
+    if (r >= 2147483648.0f) return INT32_MAX;
+    if (r <= -2147483648.0f) return INT32_MIN;
+    return (int)r;
+}
+__device__ __forceinline__ int remap_sat16(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
+
+// cv2.convertMaps(mapx, mapy, CV_16SC2, nninterpolation = nn): one map entry per lane
+__global__ __launch_bounds__(256) void k_convert_maps(const float *__restrict__ mapx, const float *__restrict__ mapy, int n, int nn,
+                                                      u32 *__restrict__ xy, uint16_t *__restrict__ alpha)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    int x, y, a = 0;
+    if (nn) {
+        x = remap_sat16(remap_round(mapx[i]));
+        y = remap_sat16(remap_round(mapy[i]));
+    } else {
+        const int sx = remap_round(mapx[i] * 32.0f), sy = remap_round(mapy[i] * 32.0f);
+        x = remap_sat16(sx >> 5);
+        y = remap_sat16(sy >> 5);
+        a = (sy & 31) * 32 + (sx & 31);
+    }
+    xy[i] = (u32)(x & 0xFFFF) | (u32)(y & 0xFFFF) << 16;
+    alpha[i] = (uint16_t)a;
+}
+
+// one remap launch for n frames of equal geometry on stream st.  channels / gray: 1 -> gray plane, 3 + gray -> the stage
+// (gray output), 3 -> 3-channel output
+static int remap_launch(hipStream_t st, const RemapFrames &F, int n, const RemapGeom &g, int channels, bool gray, int flags)
+{
+    bool aligned = g.dw % 4 == 0;
+    for (int f = 0; f < n; ++f) aligned = aligned && ((uintptr_t)F.xy[f]) % 16 == 0 && ((uintptr_t)F.alpha[f]) % 8 == 0;
+    const int quads = (g.dw + 3) / 4;
+    auto kern = channels == 1 ? (aligned ? k_remap_u8<1, false, true> : k_remap_u8<1, false, false>)
+                : gray        ? (aligned ? k_remap_u8<3, true, true> : k_remap_u8<3, true, false>)
+                              : (aligned ? k_remap_u8<3, false, true> : k_remap_u8<3, false, false>);
+    hipLaunchKernelGGL(kern, dim3((quads * g.dh + 255) / 256, n), dim3(256), 0, st, F, g, flags);
+    HIP_TRY(hipGetLastError());
+    return RELOC_OK;
+}
+
+// depth (uint16 millimetres, dense rows of w) of a context with a rectification map through the map, nearest, border 0 =
+// "no depth", into the context's depth plane (reloc_record_frame, reloc_tick_accumulate_dev)
+int rectify_depth(reloc_ctx *ctx, const uint16_t *depth_dev, int w, int h, const uint16_t **out)
+{
+    if (w != ctx->rect_w || h != ctx->rect_h) {
+        reloc_set_error("frame %dx%d differs from the rectification map %dx%d (reloc_set_rectify_map)", w, h, ctx->rect_w, ctx->rect_h);
+        return RELOC_E_ARG;
+    }
+    RemapFrames F = {};
+    F.src[0] = (const uint8_t *)depth_dev; F.xy[0] = ctx->rect_xy; F.dst[0] = (uint8_t *)ctx->rect_depth;
+    const RemapGeom g = {w, h, w, w, h, w, 0};
+    hipLaunchKernelGGL((k_remap_nearest<uint16_t, 1>), dim3((w + 255) / 256, 1, h), dim3(256), 0, ctx->stream, F, g);
+    HIP_TRY(hipGetLastError());
+    *out = ctx->rect_depth;
+    return RELOC_OK;
+}
+
 // what the five ORB kernels read and write of a context, for the source frame src
 static OrbFrame orb_frame(const reloc_ctx *c, const uint8_t *src)
 {
@@ -1270,8 +1440,9 @@ static OrbFrame orb_frame(const reloc_ctx *c, const uint8_t *src)
     return F;
 }
 
-// Five launches (six with CLAHE's two): the frames are of equal geometry.  3-channel frames of contexts with CLAHE on
-// (reloc_set_clahe) are equalised first; the pyramid then reads the CLAHE planes.  The pyramid runs 512-thread workgroups
+// Five launches (plus one of the rectification and two of CLAHE): the frames are of equal geometry.  3-channel frames of
+// contexts with a rectification map (reloc_set_rectify_map) are converted to gray and remapped first, those of contexts
+// with CLAHE on (reloc_set_clahe) equalised next; the pyramid then reads the last plane written.  The pyramid runs 512-thread workgroups
 // for latency, 256 where it shares the chip with whole-database scans.
 int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, int h, int stride, int channels, int order,
             int nfeatures, bool latency)
@@ -1286,21 +1457,44 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
             reloc_set_error("orb batch: contexts of unequal geometry");
             return RELOC_E_STATE;
         }
+        if (c->rect_w != c0->rect_w || c->rect_h != c0->rect_h) {
+            reloc_set_error("orb batch: contexts with and without a rectification map, or with maps of unequal size (reloc_set_rectify_map)");
+            return RELOC_E_STATE;
+        }
         if (c->clahe_tx != c0->clahe_tx || c->clahe_ty != c0->clahe_ty || c->clahe_clip != c0->clahe_clip) {
             reloc_set_error("orb batch: contexts of unequal CLAHE settings (reloc_set_clahe)");
             return RELOC_E_STATE;
         }
     }
+    const bool frame = channels == 3;      // the image stages serve 3-channel frames only, never a caller's gray plane
+    if (frame && c0->rect_w > 0 && (w != c0->rect_w || h != c0->rect_h)) {
+        reloc_set_error("frame %dx%d differs from the rectification map %dx%d (reloc_set_rectify_map)", w, h, c0->rect_w, c0->rect_h);
+        return RELOC_E_ARG;
+    }
     const OrbTable *tab_h = (const OrbTable *)c0->orb_tab_host;
     const int flags = gray_flags(c0, order);
     hipStream_t st = c0->stream;
     reloc_prof_begin(c0, RELOC_PROF_ORB);
-    const uint8_t *planes[RELOC_BATCH_MAX];
-    if (channels == 3 && c0->clahe_tx > 0) {
+    const uint8_t *rplanes[RELOC_BATCH_MAX], *planes[RELOC_BATCH_MAX];
+    if (frame && c0->rect_w > 0) {
+        RemapFrames F = {};
+        for (int f = 0; f < n; ++f) {
+            F.src[f] = srcs[f]; F.xy[f] = ctxs[f]->rect_xy; F.alpha[f] = ctxs[f]->rect_alpha; F.dst[f] = ctxs[f]->rect_plane;
+            rplanes[f] = F.dst[f];
+        }
+        const int cs = clahe_stride(w);
+        const RemapGeom g = {w, h, stride, w, h, cs, 0};
+        if (int rc = remap_launch(st, F, n, g, 3, true, flags)) {
+            reloc_prof_end(c0, RELOC_PROF_ORB);
+            return rc;
+        }
+        srcs = rplanes; stride = cs; channels = 1;
+    }
+    if (frame && c0->clahe_tx > 0) {
         ClaheFrames F = {};
         for (int f = 0; f < n; ++f) { F.src[f] = srcs[f]; F.lut[f] = ctxs[f]->clahe_lut; F.dst[f] = ctxs[f]->clahe_plane; planes[f] = F.dst[f]; }
         const int cs = clahe_stride(w);
-        if (int rc = clahe_launch(st, F, n, clahe_geom(w, h, c0->clahe_clip, c0->clahe_tx, c0->clahe_ty), 3, stride, flags, cs)) {
+        if (int rc = clahe_launch(st, F, n, clahe_geom(w, h, c0->clahe_clip, c0->clahe_tx, c0->clahe_ty), channels, stride, flags, cs)) {
             reloc_prof_end(c0, RELOC_PROF_ORB);
             return rc;
         }
@@ -1466,6 +1660,125 @@ RELOC_API int reloc_clahe_u8(reloc_ctx *ctx, const uint8_t *gray, int w, int h, 
     F.src[0] = ctx->frame_img; F.lut[0] = (uint8_t *)dlut; F.dst[0] = (uint8_t *)dout;
     if ((rc = clahe_launch(ctx->stream, F, 1, clahe_geom(w, h, clip_limit, tiles_x, tiles_y), 1, w, 0, w))) return rc;
     HIP_TRY(hipMemcpyAsync(out, dout, (size_t)w * h, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return RELOC_OK;
+}
+
+// ---- rectification entry points ----------------------------------------------------------------------------
+RELOC_API int reloc_set_rectify_map(reloc_ctx *ctx, const int16_t *xy, const uint16_t *alpha, int w, int h)
+{
+    ARG_CHECK_CTX(ctx, true, "ctx is NULL");
+    if (!xy) {
+        ctx->rect_w = ctx->rect_h = 0;
+        return RELOC_OK;
+    }
+    ARG_CHECK(alpha && w >= 1 && h >= 1, "reloc_set_rectify_map: alpha is NULL or the size is not positive");
+    if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("rectification map exceeds ctx capacity"); return RELOC_E_CAPACITY; }
+    if (!ctx->rect_xy) {
+        // first enable: maps and planes of the largest frame, in one allocation (rect_xy owns it)
+        const size_t px = (size_t)ctx->max_w * ctx->max_h, plane = (size_t)clahe_stride(ctx->max_w) * ctx->max_h;
+        uint8_t *base;
+        HIP_TRY(hipMalloc((void **)&base, px * 4 + px * 2 + px * 2 + plane));
+        ctx->rect_xy = (int16_t *)base;
+        ctx->rect_alpha = (uint16_t *)(base + px * 4);
+        ctx->rect_depth = (uint16_t *)(base + px * 6);
+        ctx->rect_plane = base + px * 8;
+    }
+    // frames in flight may still read the previous map
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(ctx->rect_xy, xy, (size_t)w * h * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ctx->rect_alpha, alpha, (size_t)w * h * 2, hipMemcpyHostToDevice));
+    ctx->rect_w = w;
+    ctx->rect_h = h;
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_get_rectify_map(reloc_ctx *ctx, int32_t *w, int32_t *h)
+{
+    ARG_CHECK_CTX(ctx, w && h, "reloc_get_rectify_map");
+    *w = ctx->rect_w;
+    *h = ctx->rect_h;
+    return RELOC_OK;
+}
+
+// source, maps and destination of a host-pointer remap on the device: src into frame_img (dense rows), maps into scratch 0 / 1
+static int remap_stage(reloc_ctx *ctx, const void *src, int sw, int sh, int sstride, int row_bytes, const int16_t *xy,
+                       const uint16_t *alpha, int dw, int dh, int64_t out_bytes, RemapFrames &F)
+{
+    if (sw > ctx->max_w || sh > ctx->max_h || dw > ctx->max_w || dh > ctx->max_h) {
+        reloc_set_error("image or map exceeds ctx capacity");
+        return RELOC_E_CAPACITY;
+    }
+    void *dxy, *dal, *dout;
+    int rc;
+    if ((rc = reloc_scratch(ctx, 0, (int64_t)dw * dh * 4, &dxy))) return rc;
+    if ((rc = reloc_scratch(ctx, 1, (int64_t)dw * dh * 2, &dal))) return rc;
+    if ((rc = reloc_scratch(ctx, 2, out_bytes, &dout))) return rc;
+    HIP_TRY(hipMemcpy2DAsync(ctx->frame_img, row_bytes, src, sstride, row_bytes, sh, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dxy, xy, (size_t)dw * dh * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (alpha) HIP_TRY(hipMemcpyAsync(dal, alpha, (size_t)dw * dh * 2, hipMemcpyHostToDevice, ctx->stream));
+    F = {};
+    F.src[0] = ctx->frame_img; F.xy[0] = (const int16_t *)dxy; F.alpha[0] = (const uint16_t *)dal; F.dst[0] = (uint8_t *)dout;
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_remap_u8(reloc_ctx *ctx, const uint8_t *src, int sw, int sh, int sstride, int channels, const int16_t *xy,
+                             const uint16_t *alpha, int dw, int dh, int nearest, int border_value, uint8_t *out)
+{
+    ARG_CHECK_CTX(ctx, src && xy && out && (alpha || nearest) && sw >= 1 && sh >= 1 && dw >= 1 && dh >= 1 &&
+                  (channels == 1 || channels == 3) && sstride >= channels * sw && border_value >= 0 && border_value <= 255,
+                  "reloc_remap_u8");
+    RemapFrames F;
+    const int64_t out_bytes = (int64_t)dw * dh * channels;
+    if (int rc = remap_stage(ctx, src, sw, sh, sstride, sw * channels, xy, alpha, dw, dh, out_bytes, F)) return rc;
+    const RemapGeom g = {sw, sh, sw * channels, dw, dh, dw * channels, border_value};
+    if (nearest) {
+        auto kern = channels == 1 ? k_remap_nearest<uint8_t, 1> : k_remap_nearest<uint8_t, 3>;
+        hipLaunchKernelGGL(kern, dim3((dw + 255) / 256, 1, dh), dim3(256), 0, ctx->stream, F, g);
+        HIP_TRY(hipGetLastError());
+    } else if (int rc = remap_launch(ctx->stream, F, 1, g, channels, false, 0)) {
+        return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(out, F.dst[0], (size_t)out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_remap_u16(reloc_ctx *ctx, const uint16_t *src, int sw, int sh, int sstride, const int16_t *xy, int dw, int dh,
+                              int border_value, uint16_t *out)
+{
+    ARG_CHECK_CTX(ctx, src && xy && out && sw >= 1 && sh >= 1 && dw >= 1 && dh >= 1 && sstride >= 2 * sw && border_value >= 0 &&
+                  border_value <= 65535, "reloc_remap_u16");
+    RemapFrames F;
+    const int64_t out_bytes = (int64_t)dw * dh * 2;
+    if (int rc = remap_stage(ctx, src, sw, sh, sstride, sw * 2, xy, nullptr, dw, dh, out_bytes, F)) return rc;
+    const RemapGeom g = {sw, sh, sw, dw, dh, dw, border_value};        // strides in elements
+    hipLaunchKernelGGL((k_remap_nearest<uint16_t, 1>), dim3((dw + 255) / 256, 1, dh), dim3(256), 0, ctx->stream, F, g);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, F.dst[0], (size_t)out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_convert_maps(reloc_ctx *ctx, const float *mapx, const float *mapy, int w, int h, int nninterpolation,
+                                 int16_t *xy_out, uint16_t *alpha_out)
+{
+    ARG_CHECK_CTX(ctx, mapx && mapy && xy_out && alpha_out && w >= 1 && h >= 1, "reloc_convert_maps");
+    if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("map exceeds ctx capacity"); return RELOC_E_CAPACITY; }
+    const int64_t n = (int64_t)w * h;
+    void *dmx, *dmy, *dxy, *dal;
+    int rc;
+    if ((rc = reloc_scratch(ctx, 0, n * 4, &dxy))) return rc;
+    if ((rc = reloc_scratch(ctx, 1, n * 2, &dal))) return rc;
+    if ((rc = reloc_scratch(ctx, 2, n * 4, &dmx))) return rc;
+    if ((rc = reloc_scratch(ctx, 3, n * 4, &dmy))) return rc;
+    HIP_TRY(hipMemcpyAsync(dmx, mapx, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dmy, mapy, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_convert_maps, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float *)dmx,
+                       (const float *)dmy, (int)n, nninterpolation, (u32 *)dxy, (uint16_t *)dal);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(xy_out, dxy, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(alpha_out, dal, (size_t)n * 2, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return RELOC_OK;
 }

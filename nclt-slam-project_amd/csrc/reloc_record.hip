@@ -146,13 +146,15 @@ RELOC_API int reloc_record_frame(reloc_ctx *ctx, const uint8_t *img, const uint1
     HIP_TRY(hipMemcpyAsync(ddepth, depth_mm, (size_t)w * h * 2, hipMemcpyHostToDevice, ctx->stream));
     const uint8_t *src = ctx->frame_img;
     if ((rc = orb_run(&ctx, 1, &src, w, h, w * 3, 3, order, nfeatures, true))) return rc;
+    const uint16_t *depth = (const uint16_t *)ddepth;
+    if (ctx->rect_w > 0 && (rc = rectify_depth(ctx, depth, w, h, &depth))) return rc;
     RecordParams p;
     p.fx = ctx->K4[0]; p.fy = ctx->K4[1]; p.cx = ctx->K4[2]; p.cy = ctx->K4[3];
     p.depth_min = RELOC_DEPTH_MIN_M; p.depth_max = RELOC_DEPTH_MAX_M; p.var_max = RELOC_DEPTH_VAR_MAX_M;
     p.ground_y = RELOC_GROUND_Y_THRESHOLD; p.w = w; p.h = h;
     auto kern = ctx->has_dist ? k_record<true> : k_record<false>;
     hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, ctx->stream, ctx->f_xy, ctx->f_desc, ctx->f_count, ctx->max_feat,
-                       (const uint16_t *)ddepth, w, p, o_xy, o_desc, o_pts, o_idx, o_n, make_dist(ctx->dist));
+                       depth, w, p, o_xy, o_desc, o_pts, o_idx, o_n, make_dist(ctx->dist));
     HIP_TRY(hipGetLastError());
     int32_t n = 0, nk = 0;
     HIP_TRY(hipMemcpyAsync(&n, o_n, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -339,6 +341,9 @@ RELOC_API int reloc_tick_accumulate_dev(reloc_ctx *ctx, const uint16_t *depth_mm
         int rc = db_reserve(ctx, ctx->db_cap_records + ctx->db_cap_records / 2 + 64,
                             ctx->db_cap_rows + ctx->db_cap_rows / 2 + 64 * (int64_t)ctx->max_feat);
         if (rc) return rc;
+    }
+    if (ctx->rect_w > 0) {
+        if (int rc = rectify_depth(ctx, depth_mm_dev, w, h, &depth_mm_dev)) return rc;
     }
     AccumParams p;
     p.fx = ctx->K4[0]; p.fy = ctx->K4[1]; p.cx = ctx->K4[2]; p.cy = ctx->K4[3];

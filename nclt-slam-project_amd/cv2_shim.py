@@ -2,6 +2,7 @@
 
 Exposes exactly the OpenCV symbols the reference's teach/repeat nodes call:
     cvtColor, createCLAHE(...).apply, ORB_create(...).detectAndCompute / .detect, BFMatcher(...).match / .knnMatch,
+    remap, convertMaps, undistort, initUndistortRectifyMap, fisheye.initUndistortRectifyMap,
     solvePnPRansac, projectPoints, undistortPoints, Rodrigues, KeyPoint, DMatch, error and the constants,
 with the same argument meaning, return shapes and error behaviour, so that
     import nclt_slam_project_amd.cv2_shim as cv2
@@ -13,6 +14,10 @@ Lens distortion is OpenCV's default model (k1, k2, p1, p2[, k3]; include/reloc_s
 vectors (rational, thin-prism, tilted) are accepted only when every coefficient after k3 is zero, anything else raises.
 
 CLAHE is OpenCV's 8-bit algorithm (include/reloc_spec.h); 16-bit and colour input raise.
+
+remap is OpenCV's fixed-point bilinear / nearest remap with BORDER_CONSTANT (include/reloc_spec.h, "REMAP") on the backend;
+the map builders run in NumPy float64 on the host (once per camera) and honour all 14 coefficients of the default model and
+the four of the fisheye model.  Other interpolation or border modes, other dtypes and map types raise.
 
 `Cv2Shim(backend)` takes any object with the Engine's method names; the module-level functions
 bind to one lazily created HIP Engine.
@@ -35,6 +40,13 @@ SOLVEPNP_ITERATIVE = 0
 SOLVEPNP_EPNP = 1
 SOLVEPNP_P3P = 2
 SOLVEPNP_AP3P = 5
+INTER_NEAREST = 0
+INTER_LINEAR = 1
+BORDER_CONSTANT = 0
+CV_16UC1 = 2
+CV_32FC1 = 5
+CV_16SC2 = 11
+CV_32FC2 = 13
 
 
 class error(Exception):
@@ -240,8 +252,132 @@ class _BFMatcher:
         return out
 
 
+# ---- rectification maps (include/reloc_spec.h, "REMAP": builders) -----------------------------------------------
+def _round_i32(v):
+    """saturate_cast<int>(double): half to even, saturating, NaN -> INT32_MIN"""
+    with np.errstate(invalid="ignore"):
+        r = np.clip(np.rint(v), -2147483648.0, 2147483647.0)
+    return np.where(np.isnan(r), -2147483648.0, r).astype(np.int64)
+
+
+def _fixed_point_maps(u, v):
+    """float64 source coordinates -> (xy int16 (H, W, 2), alpha uint16 (H, W)), OpenCV's CV_16SC2 + CV_16UC1 pair"""
+    iu, iv = _round_i32(u * 32.0), _round_i32(v * 32.0)
+    xy = np.stack([np.clip(iu >> 5, -32768, 32767), np.clip(iv >> 5, -32768, 32767)], axis=-1).astype(np.int16)
+    return xy, ((iv & 31) * 32 + (iu & 31)).astype(np.uint16)
+
+
+def _mat33(m, what, allow34=False):
+    a = np.asarray(m, np.float64)
+    if allow34 and a.shape == (3, 4):
+        a = a[:, :3]
+    if a.shape != (3, 3) or not np.all(np.isfinite(a)):
+        raise error(f"{what} must be a finite 3x3 matrix")
+    return a
+
+
+def _rectify_args(what, K, R, newK, size, m1type):
+    K = _mat33(K, f"{what}: cameraMatrix")
+    try:
+        w, h = (int(t) for t in size)
+    except (TypeError, ValueError) as e:
+        raise error(f"{what}: size must be (width, height)") from e
+    if w < 1 or h < 1:
+        raise error(f"{what}: size must be positive")
+    if m1type not in (CV_32FC1, CV_16SC2):
+        raise error(f"{what}: m1type must be CV_32FC1 or CV_16SC2")
+    R = np.eye(3) if R is None or np.size(R) == 0 else _mat33(R, f"{what}: R")
+    return K, R, newK, w, h
+
+
+def _rays(newK, R, w, h, what):
+    """(x, y, w) = (newK R)^-1 (u, v, 1) over the w x h pixel grid"""
+    try:
+        ir = np.linalg.inv(newK @ R)
+    except np.linalg.LinAlgError as e:
+        raise error(f"{what}: newCameraMatrix * R is singular") from e
+    u, v = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
+    return (ir[0, 0] * u + ir[0, 1] * v + ir[0, 2], ir[1, 0] * u + ir[1, 1] * v + ir[1, 2],
+            ir[2, 0] * u + ir[2, 1] * v + ir[2, 2])
+
+
+def _maps_out(u, v, m1type):
+    if m1type == CV_16SC2:
+        return _fixed_point_maps(u, v)
+    return u.astype(np.float32), v.astype(np.float32)
+
+
+def _tilt_matrix(tx, ty):
+    cx, sx, cy, sy = math.cos(tx), math.sin(tx), math.cos(ty), math.sin(ty)
+    rx = np.array([[1, 0, 0], [0, cx, sx], [0, -sx, cx]], np.float64)
+    ry = np.array([[cy, 0, -sy], [0, 1, 0], [sy, 0, cy]], np.float64)
+    rxy = ry @ rx
+    return np.array([[rxy[2, 2], 0, -rxy[0, 2]], [0, rxy[2, 2], -rxy[1, 2]], [0, 0, 1]], np.float64) @ rxy
+
+
+def initUndistortRectifyMap(cameraMatrix, distCoeffs, R, newCameraMatrix, size, m1type):
+    """cv2.initUndistortRectifyMap for the default model with all 14 coefficients (k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4 tauX
+    tauY); m1type CV_32FC1 -> two float32 maps, CV_16SC2 -> the fixed-point pair.  Host, float64."""
+    what = "initUndistortRectifyMap"
+    K, R, newK, w, h = _rectify_args(what, cameraMatrix, R, newCameraMatrix, size, m1type)
+    if newK is None or np.size(newK) == 0:          # getDefaultNewCameraMatrix(K, size, centerPrincipalPoint=True)
+        newK = K.copy()
+        newK[0, 2], newK[1, 2] = (w - 1) * 0.5, (h - 1) * 0.5
+    else:
+        newK = _mat33(newK, f"{what}: newCameraMatrix", allow34=True)
+    d = np.zeros(14)
+    if distCoeffs is not None and np.size(distCoeffs):
+        dc = np.asarray(distCoeffs, np.float64).ravel()
+        if dc.size not in (4, 5, 8, 12, 14) or not np.all(np.isfinite(dc)):
+            raise error(f"{what}: distCoeffs must be 4, 5, 8, 12 or 14 finite elements")
+        d[:dc.size] = dc
+    k1, k2, p1, p2, k3, k4, k5, k6, s1, s2, s3, s4, tx, ty = d
+    xw, yw, ww = _rays(newK, R, w, h, what)
+    with np.errstate(all="ignore"):
+        x, y = xw / ww, yw / ww
+        x2, y2 = x * x, y * y
+        r2, xy2 = x2 + y2, 2 * x * y
+        kr = (1 + ((k3 * r2 + k2) * r2 + k1) * r2) / (1 + ((k6 * r2 + k5) * r2 + k4) * r2)
+        xd = x * kr + p1 * xy2 + p2 * (r2 + 2 * x2) + s1 * r2 + s2 * r2 * r2
+        yd = y * kr + p1 * (r2 + 2 * y2) + p2 * xy2 + s3 * r2 + s4 * r2 * r2
+        if tx != 0 or ty != 0:
+            t = _tilt_matrix(tx, ty)
+            tz = t[2, 0] * xd + t[2, 1] * yd + t[2, 2]
+            inv = np.where(tz != 0, 1.0 / tz, 1.0)
+            xd, yd = inv * (t[0, 0] * xd + t[0, 1] * yd + t[0, 2]), inv * (t[1, 0] * xd + t[1, 1] * yd + t[1, 2])
+        u, v = K[0, 0] * xd + K[0, 2], K[1, 1] * yd + K[1, 2]
+    return _maps_out(u, v, m1type)
+
+
+def _fisheye_init_undistort_rectify_map(K, D, R, P, size, m1type):
+    """cv2.fisheye.initUndistortRectifyMap: the equidistant model, theta_d = theta (1 + k1 theta^2 + ... + k4 theta^8); a ray
+    with w <= 0 (behind the camera) maps to -inf, outside every image.  Host, float64."""
+    what = "fisheye.initUndistortRectifyMap"
+    K, R, P, w, h = _rectify_args(what, K, R, P, size, m1type)
+    P = K if P is None or np.size(P) == 0 else _mat33(P, f"{what}: P", allow34=True)
+    dc = np.zeros(4) if D is None or np.size(D) == 0 else np.asarray(D, np.float64).ravel()
+    if dc.size != 4 or not np.all(np.isfinite(dc)):
+        raise error(f"{what}: D must be 4 finite elements")
+    xw, yw, ww = _rays(P, R, w, h, what)
+    with np.errstate(all="ignore"):
+        x, y = xw / ww, yw / ww
+        r = np.sqrt(x * x + y * y)
+        th = np.arctan(r)
+        t2 = th * th
+        t4, t6 = t2 * t2, t2 * t2 * t2
+        t8 = t4 * t4
+        thd = th * (1 + dc[0] * t2 + dc[1] * t4 + dc[2] * t6 + dc[3] * t8)
+        scale = np.where(r == 0, 1.0, thd / r)
+        u, v = K[0, 0] * x * scale + K[0, 2], K[1, 1] * y * scale + K[1, 2]
+        u, v = np.where(ww <= 0, -np.inf, u), np.where(ww <= 0, -np.inf, v)
+    return _maps_out(u, v, m1type)
+
+
 class _Fisheye:
-    """cv2.fisheye stands in only to say that the fisheye model is not implemented: every function raises `error`."""
+    """cv2.fisheye: initUndistortRectifyMap builds a rectification map on the host; the fisheye model itself (points, PnP)
+    is not implemented, and every other function raises `error`."""
+
+    initUndistortRectifyMap = staticmethod(_fisheye_init_undistort_rectify_map)
 
     def __getattr__(self, name):
         if name.startswith("__"):
@@ -267,6 +403,13 @@ class Cv2Shim:
     SOLVEPNP_EPNP = SOLVEPNP_EPNP
     SOLVEPNP_P3P = SOLVEPNP_P3P
     SOLVEPNP_AP3P = SOLVEPNP_AP3P
+    INTER_NEAREST = INTER_NEAREST
+    INTER_LINEAR = INTER_LINEAR
+    BORDER_CONSTANT = BORDER_CONSTANT
+    CV_16UC1 = CV_16UC1
+    CV_32FC1 = CV_32FC1
+    CV_16SC2 = CV_16SC2
+    CV_32FC2 = CV_32FC2
     error = error
     KeyPoint = KeyPoint
     DMatch = DMatch
@@ -288,6 +431,105 @@ class Cv2Shim:
 
     def createCLAHE(self, clipLimit=40.0, tileGridSize=(8, 8)):
         return _CLAHE(self, clipLimit, tileGridSize)
+
+    initUndistortRectifyMap = staticmethod(initUndistortRectifyMap)
+
+    def _backend(self, name, what):
+        fn = getattr(self.backend, name, None)
+        if fn is None:
+            raise error(f"{what}: not implemented by this backend (it has no {name})")
+        return fn
+
+    def convertMaps(self, map1, map2, dstmap1type, dstmap1=None, dstmap2=None, nninterpolation=False):
+        """two (H, W) float32 maps (or one (H, W, 2) float32 map) -> the CV_16SC2 + CV_16UC1 pair"""
+        if dstmap1type != CV_16SC2:
+            raise error("convertMaps: only the conversion to CV_16SC2 is implemented")
+        if dstmap1 is not None or dstmap2 is not None:
+            raise error("convertMaps: output arguments are not implemented; use the returned pair")
+        mx, my = self._float_maps(map1, map2, "convertMaps")
+        try:
+            return self._backend("convert_maps", "convertMaps")(mx, my, bool(nninterpolation))
+        except RelocError as e:
+            raise error(str(e)) from e
+
+    @staticmethod
+    def _float_maps(map1, map2, what):
+        m1 = np.asarray(map1)
+        if m1.dtype != np.float32:
+            raise error(f"{what}: the maps must be float32 (CV_32FC1 pair or CV_32FC2) or the CV_16SC2 + CV_16UC1 pair")
+        if m1.ndim == 3 and m1.shape[2] == 2 and (map2 is None or np.size(map2) == 0):
+            return np.ascontiguousarray(m1[..., 0]), np.ascontiguousarray(m1[..., 1])
+        m2 = None if map2 is None else np.asarray(map2)
+        if m1.ndim != 2 or m2 is None or m2.dtype != np.float32 or m2.shape != m1.shape or m1.size == 0:
+            raise error(f"{what}: map1 and map2 must be two (H, W) float32 arrays of one size")
+        return m1, m2
+
+    def remap(self, src, map1, map2, interpolation, dst=None, borderMode=BORDER_CONSTANT, borderValue=0):
+        """cv2.remap: INTER_LINEAR / INTER_NEAREST, BORDER_CONSTANT; src uint8 with 1 or 3 channels, or single-channel uint16
+        with INTER_NEAREST; the maps as a float32 pair (or CV_32FC2) or the fixed-point CV_16SC2 + CV_16UC1 pair"""
+        if interpolation not in (INTER_NEAREST, INTER_LINEAR):
+            raise error("remap: only INTER_NEAREST and INTER_LINEAR are implemented (no other interpolation or warp flag)")
+        if borderMode != BORDER_CONSTANT:
+            raise error("remap: only BORDER_CONSTANT is implemented")
+        nearest = interpolation == INTER_NEAREST
+        img = np.asarray(src)
+        if img.dtype == np.uint16:
+            if img.ndim != 2 or not nearest:
+                raise error("remap: 16-bit input is single-channel and INTER_NEAREST only")
+        elif img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)) or img.size == 0:
+            raise error("remap: expected an (H, W) or (H, W, 3) uint8 image or an (H, W) uint16 image")
+        if img.size == 0:
+            raise error("remap: empty image")
+        ch = 1 if img.ndim == 2 else 3
+        try:                                       # OpenCV's Scalar: missing components are 0
+            bv = [float(t) for t in np.atleast_1d(np.asarray(borderValue, np.float64)).ravel()]
+        except (TypeError, ValueError) as e:
+            raise error("remap: borderValue must be a number or up to four numbers") from e
+        if not 1 <= len(bv) <= 4 or not all(math.isfinite(t) for t in bv):
+            raise error("remap: borderValue must be one to four finite numbers")
+        bv = (bv + [0.0] * 4)[:ch]
+        if any(t != bv[0] for t in bv):
+            raise error("remap: a border value that differs between the channels is not implemented "
+                        "(a plain number means (v, 0, 0, 0) in OpenCV; pass (v, v, v) for a 3-channel image)")
+        border = int(min(max(np.rint(bv[0]), 0), 255 if img.dtype == np.uint8 else 65535))      # saturate_cast
+        m1 = np.asarray(map1)
+        fn = self._backend("remap", "remap")
+        try:
+            if m1.dtype == np.int16:
+                if m1.ndim != 3 or m1.shape[2] != 2 or m1.size == 0:
+                    raise error("remap: a fixed-point map1 is an (H, W, 2) int16 array (CV_16SC2)")
+                m2 = None if map2 is None or np.size(map2) == 0 else np.asarray(map2)
+                if m2 is None and not nearest:
+                    raise error("remap: INTER_LINEAR with a CV_16SC2 map needs the CV_16UC1 fraction map")
+                if m2 is not None and (m2.dtype != np.uint16 or m2.shape != m1.shape[:2]):
+                    raise error("remap: map2 must be an (H, W) uint16 array of map1's size (CV_16UC1)")
+                xy, alpha = m1, m2
+            else:
+                mx, my = self._float_maps(map1, map2, "remap")
+                xy, alpha = self._backend("convert_maps", "remap")(mx, my, nearest)
+            if dst is not None:
+                dst_a = np.asarray(dst)
+                if dst_a.dtype != img.dtype or dst_a.shape != xy.shape[:2] + img.shape[2:]:
+                    raise error("remap: dst must have the map's size and src's type")
+                if np.shares_memory(dst_a, img):
+                    raise error("remap: dst must not share memory with src (remap does not work in place)")
+            out = fn(img, xy, alpha, nearest, border)
+        except RelocError as e:
+            raise error(str(e)) from e
+        if dst is not None:
+            dst[...] = out
+            return dst
+        return out
+
+    def undistort(self, src, cameraMatrix, distCoeffs, dst=None, newCameraMatrix=None):
+        """cv2.undistort: initUndistortRectifyMap(K, dist, I, newCameraMatrix or K, size of src, CV_16SC2), then
+        remap(INTER_LINEAR, BORDER_CONSTANT)"""
+        img = np.asarray(src)
+        if img.ndim not in (2, 3) or img.size == 0:
+            raise error("undistort: expected an image")
+        newK = cameraMatrix if newCameraMatrix is None or np.size(newCameraMatrix) == 0 else newCameraMatrix
+        m1, m2 = initUndistortRectifyMap(cameraMatrix, distCoeffs, None, newK, (img.shape[1], img.shape[0]), CV_16SC2)
+        return self.remap(img, m1, m2, INTER_LINEAR, dst=dst)
 
     def ORB_create(self, nfeatures=500, **kwargs):
         defaults = dict(scaleFactor=1.2, nlevels=8, edgeThreshold=31, firstLevel=0, WTA_K=2, scoreType=0,
@@ -416,6 +658,18 @@ def cvtColor(src, code):
 
 def createCLAHE(clipLimit=40.0, tileGridSize=(8, 8)):
     return default_shim().createCLAHE(clipLimit, tileGridSize)
+
+
+def remap(*a, **kw):
+    return default_shim().remap(*a, **kw)
+
+
+def convertMaps(*a, **kw):
+    return default_shim().convertMaps(*a, **kw)
+
+
+def undistort(*a, **kw):
+    return default_shim().undistort(*a, **kw)
 
 
 def ORB_create(nfeatures=500, **kw):

@@ -211,6 +211,80 @@ class Engine:
         N.check(self._lib.reloc_get_clahe(self._ctx, C.byref(clip), C.byref(tx), C.byref(ty)), "reloc_get_clahe")
         return None if tx.value == 0 else (clip.value, (tx.value, ty.value))
 
+    @staticmethod
+    def _fixed_maps(xy, alpha, need_alpha=True):
+        """the fixed-point map pair as contiguous (H, W, 2) int16 + (H, W) uint16 (alpha may be None when not needed)"""
+        xy = np.asarray(xy)
+        if xy.dtype != np.int16 or xy.ndim != 3 or xy.shape[2] != 2 or xy.shape[0] < 1 or xy.shape[1] < 1:
+            raise N.RelocError("remap: the fixed-point map is an (H, W, 2) int16 array (CV_16SC2)")
+        if alpha is None:
+            if need_alpha:
+                raise N.RelocError("remap: bilinear interpolation needs the (H, W) uint16 fraction map")
+        else:
+            alpha = np.asarray(alpha)
+            if alpha.dtype != np.uint16 or alpha.shape != xy.shape[:2]:
+                raise N.RelocError("remap: the fraction map is an (H, W) uint16 array of the coordinate map's size (CV_16UC1)")
+            alpha = np.ascontiguousarray(alpha)
+        return np.ascontiguousarray(xy), alpha
+
+    def convert_maps(self, mapx: np.ndarray, mapy: np.ndarray, nearest: bool = False):
+        """cv2.convertMaps(mapx, mapy, CV_16SC2, nninterpolation=nearest) of two (H, W) float32 maps (reloc_convert_maps):
+        (xy (H, W, 2) int16, alpha (H, W) uint16)"""
+        mapx, mapy = np.asarray(mapx), np.asarray(mapy)
+        if mapx.dtype != np.float32 or mapy.dtype != np.float32 or mapx.ndim != 2 or mapx.shape != mapy.shape:
+            raise N.RelocError("convert_maps: expected two (H, W) float32 maps of one size")
+        mapx, mapy = np.ascontiguousarray(mapx), np.ascontiguousarray(mapy)
+        h, w = mapx.shape
+        xy = np.empty((h, w, 2), np.int16); alpha = np.empty((h, w), np.uint16)
+        N.check(self._lib.reloc_convert_maps(self._ctx, N.ptr(mapx), N.ptr(mapy), w, h, int(bool(nearest)), N.ptr(xy),
+                                             N.ptr(alpha)), "reloc_convert_maps")
+        return xy, alpha
+
+    def remap(self, src: np.ndarray, xy: np.ndarray, alpha: np.ndarray | None, nearest: bool = False, border: int = 0) -> np.ndarray:
+        """cv2.remap(src, xy, alpha, INTER_NEAREST if nearest else INTER_LINEAR, borderMode=BORDER_CONSTANT, borderValue=border)
+        with the fixed-point map pair: src (H, W) or (H, W, 3) uint8, or (H, W) uint16 with nearest (reloc_remap_u8 / _u16)"""
+        src = np.asarray(src)
+        xy, alpha = self._fixed_maps(xy, alpha, need_alpha=not nearest)
+        dh, dw = xy.shape[:2]
+        if src.dtype == np.uint16:
+            if src.ndim != 2 or not nearest:
+                raise N.RelocError("remap: uint16 input is single-channel and INTER_NEAREST only")
+            src = np.ascontiguousarray(src)
+            out = np.empty((dh, dw), np.uint16)
+            N.check(self._lib.reloc_remap_u16(self._ctx, N.ptr(src), src.shape[1], src.shape[0], src.strides[0], N.ptr(xy), dw, dh,
+                                              int(border), N.ptr(out)), "reloc_remap_u16")
+            return out
+        if src.dtype != np.uint8 or not (src.ndim == 2 or (src.ndim == 3 and src.shape[2] == 3)):
+            raise N.RelocError("remap: expected an (H, W) or (H, W, 3) uint8 image, or an (H, W) uint16 image")
+        ch = 1 if src.ndim == 2 else 3
+        if src.strides[-1] != 1 or (ch == 3 and src.strides[1] != 3) or src.strides[0] < src.shape[1] * ch:
+            src = np.ascontiguousarray(src)
+        out = np.empty((dh, dw) if ch == 1 else (dh, dw, 3), np.uint8)
+        N.check(self._lib.reloc_remap_u8(self._ctx, C.c_void_p(src.ctypes.data), src.shape[1], src.shape[0], src.strides[0], ch,
+                                         N.ptr(xy), N.ptr(alpha), dw, dh, int(bool(nearest)), int(border), N.ptr(out)),
+                "reloc_remap_u8")
+        return out
+
+    def set_rectify(self, maps=None):
+        """Rectification in front of ORB (and CLAHE) on the 3-channel frames of the fused tick, recording and
+        reloc_orb_frame_dev, and of the depth of recording and accumulation (reloc_set_rectify_map).  maps: None = off, or
+        (map1, map2) as cv2.remap takes them: two (H, W) float32 maps or the fixed-point (H, W, 2) int16 + (H, W) uint16 pair"""
+        if maps is None:
+            N.check(self._lib.reloc_set_rectify_map(self._ctx, None, None, 0, 0), "reloc_set_rectify_map")
+            return
+        m1, m2 = maps
+        if np.asarray(m1).dtype == np.float32:
+            m1, m2 = self.convert_maps(m1, m2)
+        xy, alpha = self._fixed_maps(m1, m2)
+        N.check(self._lib.reloc_set_rectify_map(self._ctx, N.ptr(xy), N.ptr(alpha), xy.shape[1], xy.shape[0]),
+                "reloc_set_rectify_map")
+
+    def get_rectify(self):
+        """None when off, else the map's (w, h)"""
+        w = C.c_int32(); h = C.c_int32()
+        N.check(self._lib.reloc_get_rectify_map(self._ctx, C.byref(w), C.byref(h)), "reloc_get_rectify_map")
+        return None if w.value == 0 else (w.value, h.value)
+
     def record_frame(self, bgr: np.ndarray, depth_mm: np.ndarray, nfeatures: int = 500, order_rgb: bool = False):
         """teach-side record arrays of one frame: dict(xy (n,2), desc (n,32), pts3d (n,3), kp_index (n,), n, n_kp)"""
         bgr = N.u8(bgr)

@@ -38,6 +38,11 @@ class MatcherConfig:
     # CLAHE between gray conversion and ORB: None = off (the reference matcher), or (clipLimit, (tiles_x, tiles_y)) as in
     # cv2.createCLAHE(clipLimit=2.0, tileGridSize=(8, 8)) of the teach-and-repeat scripts.  Teach with the same setting.
     clahe: tuple | None = None
+    # rectification of the frame between gray conversion and CLAHE / ORB (and of the depth, nearest, for accumulation):
+    # None = off, or (map1, map2) as cv2.remap takes them -- two float32 maps or the CV_16SC2 + CV_16UC1 pair, e.g. from
+    # cv2.initUndistortRectifyMap / cv2.fisheye.initUndistortRectifyMap.  fx, fy, cx, cy are then the newCameraMatrix the
+    # map was built for and dist stays empty.  Teach with the same map.
+    rectify: tuple | None = None
     candidate_radius_m: float = 8.0
     max_candidates: int = 5
     heading_tol_deg: float = 90.0
@@ -86,6 +91,16 @@ class TickOutcome:
     extra: dict = field(default_factory=dict)
 
 
+def fixed_rectify_maps(cv2, maps):
+    """MatcherConfig.rectify as the fixed-point pair cv2.remap reads for both interpolations (None stays None)"""
+    if maps is None:
+        return None
+    m1, m2 = maps
+    if np.asarray(m1).dtype == np.int16:
+        return np.asarray(m1), np.asarray(m2)
+    return cv2.convertMaps(m1, m2, cv2.CV_16SC2)
+
+
 class LandmarkMatcherCore:
     def __init__(self, landmarks, log_csv=None, cv2=None, config: MatcherConfig | None = None,
                  return_landmarks=None, swap_flag=None, logger=None):
@@ -104,6 +119,7 @@ class LandmarkMatcherCore:
         self.matcher = cv2.BFMatcher(cv2.NORM_HAMMING, crossCheck=True)
         self.clahe = None if self.cfg.clahe is None else cv2.createCLAHE(clipLimit=self.cfg.clahe[0],
                                                                          tileGridSize=tuple(self.cfg.clahe[1]))
+        self.rectify = fixed_rectify_maps(cv2, self.cfg.rectify)
         self.dist = np.zeros((4, 1), dtype=np.float32) if len(self.cfg.dist) == 0 else np.asarray(self.cfg.dist, np.float64).reshape(-1, 1)
         self.last_anchor_ts = 0.0
         self.n_attempts = 0
@@ -244,6 +260,10 @@ class LandmarkMatcherCore:
         vio_xy = (base_pose[0], base_pose[1])
         cand, d, herr = self.select_candidates(base_pose)
         gray = cv2.cvtColor(bgr, cv2.COLOR_BGR2GRAY)
+        if self.rectify is not None:
+            gray = cv2.remap(gray, *self.rectify, cv2.INTER_LINEAR)
+            if depth_mm is not None:
+                depth_mm = cv2.remap(depth_mm, *self.rectify, cv2.INTER_NEAREST)
         if self.clahe is not None:
             gray = self.clahe.apply(gray)
         kpts, desc = self.orb.detectAndCompute(gray, None)
@@ -354,6 +374,7 @@ class FusedLandmarkMatcher:
                      data.get("base_to_cam_rot", P.BASE_TO_CAM_ROT))
         e.set_distortion(cfg.dist)
         e.set_clahe(*((None,) if cfg.clahe is None else (cfg.clahe[0], tuple(cfg.clahe[1]))))
+        e.set_rectify(cfg.rectify)
         self._return_src = return_landmarks
         self.swap_flag = swap_flag
         self._swapped = False

@@ -14,6 +14,7 @@ import numpy as np
 
 from . import pose as P
 from .landmarks import new_database, save_landmarks
+from .matcher import fixed_rectify_maps
 
 FX = FY = 320.0
 CX, CY = 320.0, 240.0
@@ -40,18 +41,21 @@ def local_depth_std(depth_mm, uu, vv):
 
 class LandmarkRecorderCore:
     def __init__(self, out_pkl=None, min_disp_m: float = 2.0, cv2=None, nfeatures: int = 500, logger=None, engine=None,
-                 dist=(), clahe=None):
+                 dist=(), clahe=None, rectify=None):
         """engine: when given, ORB + all per-keypoint gates + back-projection run in ONE device call
         (reloc_record_frame); otherwise the gates run in NumPy on the cv2-shaped module's features.
         dist: lens distortion as MatcherConfig.dist (OpenCV's k1 k2 p1 p2 [k3], () = pinhole): the kept keypoints are
         back-projected through the inverse model (engine: reloc_set_distortion; cv2 path: cv2.undistortPoints).
         clahe: None or (clipLimit, (tiles_x, tiles_y)) as MatcherConfig.clahe: CLAHE between gray conversion and ORB (engine:
-        reloc_set_clahe; cv2 path: cv2.createCLAHE(...).apply), so that the repeat run can equalise the same way."""
+        reloc_set_clahe; cv2 path: cv2.createCLAHE(...).apply), so that the repeat run can equalise the same way.
+        rectify: None or (map1, map2) as MatcherConfig.rectify: the frame is rectified between gray conversion and CLAHE /
+        ORB and the depth read through the same map, nearest (engine: reloc_set_rectify_map; cv2 path: cv2.remap)."""
         self.engine = engine
         self.dist = tuple(np.asarray(dist, np.float64).ravel()) if dist is not None else ()
         if engine is not None:
             engine.set_distortion(self.dist)
             engine.set_clahe(*((None,) if clahe is None else (clahe[0], tuple(clahe[1]))))
+            engine.set_rectify(rectify)
         self.nfeatures = nfeatures
         if cv2 is None and engine is None:
             from . import cv2_shim as cv2
@@ -61,6 +65,7 @@ class LandmarkRecorderCore:
         self.orb = cv2.ORB_create(nfeatures=nfeatures) if cv2 is not None else None
         self.clahe = (cv2.createCLAHE(clipLimit=clahe[0], tileGridSize=tuple(clahe[1]))
                       if cv2 is not None and clahe is not None else None)
+        self.rectify = fixed_rectify_maps(cv2, rectify) if cv2 is not None else None
         self.landmarks = []
         self.last_landmark_pose_world = None
         self.log = logger or (lambda msg: None)
@@ -85,6 +90,9 @@ class LandmarkRecorderCore:
             return rec
         cv2 = self.cv2
         gray = cv2.cvtColor(bgr, cv2.COLOR_BGR2GRAY)
+        if self.rectify is not None:
+            gray = cv2.remap(gray, *self.rectify, cv2.INTER_LINEAR)
+            depth_mm = cv2.remap(depth_mm, *self.rectify, cv2.INTER_NEAREST)
         if self.clahe is not None:
             gray = self.clahe.apply(gray)
         kpts, desc = self.orb.detectAndCompute(gray, None)
