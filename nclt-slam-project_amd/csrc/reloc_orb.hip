@@ -13,10 +13,15 @@
 //   k_pyramid                            gray conversion (or a gray plane) and all 8 levels in one launch: a tile
 //                                        owns a rectangle of every level and derives level l from level l-1 in LDS
 //                                        (fixed-point INTER_LINEAR_EXACT), 4 px per lane, dword stores
-//   k_fast_blur                          one launch, two kinds of tiles over all levels:
-//                                        FAST 32x32 tiles + halo in LDS: segment test, scores of the compacted
+//   k_fast_blur                          one launch, two kinds of tiles over all levels, halos staged in LDS as aligned
+//                                        dwords (a lane owns a fixed (row, dword); border bytes only in border tiles):
+//                                        FAST 32x32 tiles: segment test of four adjacent pixels per lane on 7 x 3 LDS
+//                                        dwords (v_perm_b32 + 16-bit sign arithmetic, two pixels per instruction), the
+//                                        132 pixels of the ring around the tile one per lane; scores of the compacted
 //                                        corners, 3x3 NMS, per-level score histogram (LDS atomics, then global);
-//                                        blur 64x16 tiles staged in LDS (8.8 / 16.16 passes)
+//                                        blur 64x16 tiles: four horizontal sums per lane from three dwords
+//                                        (v_alignbyte_b32 + two v_dot4_u32_u8 per window), vertical pass on 16-bit
+//                                        pairs (8.8 / 16.16 passes)
 //   k_harris                             histogram -> cut score; survivors >= cut get a Harris
 //                                        response and enter the per-level candidate list
 //   k_select                             one workgroup per level: keep "fewer than quota strictly
@@ -332,12 +337,29 @@ __global__ __launch_bounds__(PYR_BS) void k_pyramid_batch(OrbBatch b, int w, int
 
 
 // ---- blur ---------------------------------------------------------------------------------------
+// Four bytes of one level row starting at the 4-aligned column gx, with the border rule applied per byte (BORDER_REFLECT_101
+// for the blur, clamp for FAST).  A dword that lies inside the image is one aligned load: rows start 64-byte aligned.
+template <bool REFLECT>
+__device__ __forceinline__ u32 halo_dword(const uint8_t *__restrict__ row, int gx, int w)
+{
+    if (gx >= 0 && gx + 4 <= w) return *reinterpret_cast<const u32 *>(row + gx);
+    u32 v = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int x = REFLECT ? reflect101(gx + k, w) : min(max(gx + k, 0), w - 1);
+        v |= (u32)row[x] << (8 * k);
+    }
+    return v;
+}
+
 constexpr int BT_W = 64, BT_H = 16;
+constexpr int BT_P = BT_W / 4 + 2;      // dwords per staged row: columns x0 - 4 .. x0 + BT_W + 3
+static_assert(BT_W == 64 && BT_H == 16, "blur7_tile maps 256 lanes to 16 rows x 16 dwords");
 __device__ __forceinline__ void blur7_tile(const OrbTable *__restrict__ tab, const uint8_t *__restrict__ pyr,
                                            uint8_t *__restrict__ blur, int bid)
 {
-    __shared__ uint8_t s_in[(BT_H + 6) * (BT_W + 8)];
-    __shared__ uint16_t s_h[(BT_H + 6) * BT_W];
+    __shared__ u32 s_in[(BT_H + 6) * BT_P];
+    __shared__ u32 s_h[(BT_H + 6) * BT_W / 2];      // horizontal sums, two 16-bit values per dword
     const int l = find_level(tab->blur_tile_base, bid);
     const OrbLevel L = tab->lev[l];
     const int tile = bid - tab->blur_tile_base[l];
@@ -345,31 +367,60 @@ __device__ __forceinline__ void blur7_tile(const OrbTable *__restrict__ tab, con
     const int x0 = (tile % tx) * BT_W, y0 = (tile / tx) * BT_H;
     const uint8_t *src = pyr + L.off;
     const int tid = threadIdx.x;
-    for (int i = tid; i < (BT_H + 6) * (BT_W + 6); i += 256) {
-        const int ry = i / (BT_W + 6), rx = i % (BT_W + 6);
-        const int gy = reflect101(y0 + ry - 3, L.h), gx = reflect101(x0 + rx - 3, L.w);
-        s_in[ry * (BT_W + 8) + rx] = src[(size_t)gy * L.stride + gx];
-    }
-    __syncthreads();
-    for (int i = tid; i < (BT_H + 6) * BT_W; i += 256) {
-        const int ry = i / BT_W, rx = i % BT_W;
-        const uint8_t *p = s_in + ry * (BT_W + 8) + rx;
-        const u32 s = RELOC_BLUR_K0 * (p[0] + p[6]) + RELOC_BLUR_K1 * (p[1] + p[5]) + RELOC_BLUR_K2 * (p[2] + p[4]) + RELOC_BLUR_K3 * p[3];
-        s_h[i] = (uint16_t)s;
-    }
-    __syncthreads();
-    // 4 output pixels per lane
+    const int r16 = tid >> 4, c16 = tid & 15;
+    // halo: a lane owns one dword of one row.  Trip A: rows 0..15, the 16 dwords of the tile's own columns.  Trip B: lanes
+    // 0..95 the same for rows 16..21, lanes 96..139 the dword left and right of the tile for all 22 rows.
     {
-        const int ry = tid / 16, rx4 = (tid % 16) * 4;
+        const int e = tid - 6 * 16;
+        const bool edge = e >= 0;
+        const int rb = edge ? e >> 1 : BT_H + r16, db = edge ? (e & 1) * (BT_P - 1) : 1 + c16;
+        const bool on = e < 2 * (BT_H + 6);
+        const int gya = reflect101(y0 + r16 - 3, L.h), gyb = reflect101(y0 + rb - 3, L.h);
+        const u32 va = halo_dword<true>(src + (size_t)gya * L.stride, x0 + 4 * c16, L.w);
+        u32 vb = 0;
+        if (on) vb = halo_dword<true>(src + (size_t)gyb * L.stride, x0 - 4 + 4 * db, L.w);
+        s_in[r16 * BT_P + 1 + c16] = va;
+        if (on) s_in[rb * BT_P + db] = vb;
+    }
+    __syncthreads();
+    // horizontal pass: four adjacent sums from three dwords; a 7-tap window is two byte dot products (the taps fit a byte,
+    // the sum 16 bits)
+    constexpr u32 W_LO = RELOC_BLUR_K0 | RELOC_BLUR_K1 << 8 | RELOC_BLUR_K2 << 16 | (u32)RELOC_BLUR_K3 << 24;
+    constexpr u32 W_HI = RELOC_BLUR_K2 | RELOC_BLUR_K1 << 8 | RELOC_BLUR_K0 << 16;
+    static_assert(RELOC_BLUR_K3 < 256 && 2 * (RELOC_BLUR_K0 + RELOC_BLUR_K1 + RELOC_BLUR_K2) + RELOC_BLUR_K3 <= 256, "blur taps");
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int ry = t * BT_H + r16;
+        if (ry < BT_H + 6) {
+            const u32 *p = s_in + ry * BT_P + c16;
+            const u32 d0 = p[0], d1 = p[1], d2 = p[2];      // columns x0 + 4 * c16 - 4 .. + 7
+            u32 s[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {                   // output k: bytes 1 + k .. 7 + k
+                const u32 lo = k < 3 ? __builtin_amdgcn_alignbyte(d1, d0, 1 + k) : d1;
+                const u32 hi = k < 3 ? __builtin_amdgcn_alignbyte(d2, d1, 1 + k) : d2;
+                s[k] = __builtin_amdgcn_udot4(lo, W_LO, __builtin_amdgcn_udot4(hi, W_HI, 0u, false), false);
+            }
+            *reinterpret_cast<uint2 *>(s_h + ry * (BT_W / 2) + 2 * c16) = make_uint2(s[0] | s[1] << 16, s[2] | s[3] << 16);
+        }
+    }
+    __syncthreads();
+    // vertical pass: 4 output pixels per lane, the seven rows read as 16-bit pairs
+    {
+        u32 c[7][4];
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            const uint2 d = *reinterpret_cast<const uint2 *>(s_h + (r16 + j) * (BT_W / 2) + 2 * c16);
+            c[j][0] = d.x & 0xFFFF; c[j][1] = d.x >> 16; c[j][2] = d.y & 0xFFFF; c[j][3] = d.y >> 16;
+        }
         u32 out = 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const uint16_t *p = s_h + ry * BT_W + rx4 + k;
-            const u32 s = RELOC_BLUR_K0 * ((u32)p[0] + p[6 * BT_W]) + RELOC_BLUR_K1 * ((u32)p[BT_W] + p[5 * BT_W]) +
-                          RELOC_BLUR_K2 * ((u32)p[2 * BT_W] + p[4 * BT_W]) + RELOC_BLUR_K3 * (u32)p[3 * BT_W];
+            const u32 s = RELOC_BLUR_K0 * (c[0][k] + c[6][k]) + RELOC_BLUR_K1 * (c[1][k] + c[5][k]) +
+                          RELOC_BLUR_K2 * (c[2][k] + c[4][k]) + RELOC_BLUR_K3 * c[3][k];
             out |= ((s + (1u << 15)) >> 16) << (8 * k);
         }
-        const int gy = y0 + ry, gx = x0 + rx4;
+        const int gy = y0 + r16, gx = x0 + 4 * c16;
         if (gy < L.h && gx < L.stride) *reinterpret_cast<u32 *>(blur + L.off + (size_t)gy * L.stride + gx) = out;
     }
 }
@@ -420,15 +471,96 @@ __device__ int fast_corner_score(const uint8_t *p, int stride, int thr, int sign
     return best > thr ? best - 1 : 0;
 }
 
+// 9 contiguous set bits on the 16-bit circle; x = the mask in both halves of a dword
+__device__ __forceinline__ bool fast_run9(u32 x)
+{
+    u32 y = x & (x >> 1);
+    y &= y >> 2;
+    y &= y >> 4;          // runs of 8
+    y &= x >> 8;          // runs of 9
+    return (y & 0xFFFFu) != 0;
+}
+
+// Segment test of four horizontally adjacent pixels by one lane.  w[r][0..2] = the 12 bytes of row r (dy = r - 3) that start
+// 4 columns left of pixel 0.  The ring byte (dx, dy) of the four pixels is four adjacent bytes of a row: one v_perm_b32 puts
+// those of pixels 0 / 2 and one those of pixels 1 / 3 into 16-bit halves, where "brighter than centre + t" and "darker than
+// centre - t" are the sign bits of one add / subtract for two pixels at a time.  The sign bits of the 16 ring positions are
+// shifted into one 16-bit mask per pixel and polarity (mb / md: [0] = pixels 0 | 2 << 16, [1] = pixels 1 | 3 << 16).
+struct FastQuad {
+    u32 nb[2], nd[2];
+    const u32 (*w)[3];
+    __device__ __forceinline__ FastQuad(const u32 (&rows)[7][3]) : w(rows)
+    {
+        const u32 c = rows[3][1];
+        const u32 ce = c & 0x00FF00FFu, co = (c >> 8) & 0x00FF00FFu;
+        // v > c + t  <=>  v + (0x7FFF - c - t) has bit 15;   v < c - t  <=>  (c - t - 1 + 0x8000) - v has bit 15
+        nb[0] = (0x7FFFu - RELOC_FAST_THRESHOLD) * 0x00010001u - ce; nb[1] = (0x7FFFu - RELOC_FAST_THRESHOLD) * 0x00010001u - co;
+        nd[0] = (0x7FFFu - RELOC_FAST_THRESHOLD) * 0x00010001u + ce; nd[1] = (0x7FFFu - RELOC_FAST_THRESHOLD) * 0x00010001u + co;
+    }
+    // sign words of ring position (dx, dy): bit 15 of each half = the flag, the other bits are to be ignored
+    template <int DX, int DY>
+    __device__ __forceinline__ void flags(u32 (&tb)[2], u32 (&td)[2]) const
+    {
+        constexpr int b = 4 + DX, q = b >> 2, o = b & 3;
+        constexpr u32 sel_e = (u32)o | 0x0C00u | (u32)(o + 2) << 16 | 0x0C000000u;
+        constexpr u32 sel_o = (u32)(o + 1) | 0x0C00u | (u32)(o + 3) << 16 | 0x0C000000u;
+        const u32 ve = __builtin_amdgcn_perm(w[DY + 3][q + 1], w[DY + 3][q], sel_e);
+        const u32 vo = __builtin_amdgcn_perm(w[DY + 3][q + 1], w[DY + 3][q], sel_o);
+        tb[0] = ve + nb[0]; tb[1] = vo + nb[1];
+        td[0] = nd[0] - ve; td[1] = nd[1] - vo;
+    }
+    template <int K>
+    __device__ __forceinline__ void ring(u32 (&tb)[2], u32 (&td)[2]) const
+    {
+        constexpr int dx[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
+        constexpr int dy[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3};
+        flags<dx[K], dy[K]>(tb, td);
+    }
+    // compass pretest: some pixel of the four has two brighter or two darker compass pixels
+    __device__ __forceinline__ bool candidate() const
+    {
+        u32 b0[2], d0[2], b4[2], d4[2], b8[2], d8[2], b12[2], d12[2];
+        ring<0>(b0, d0); ring<4>(b4, d4); ring<8>(b8, d8); ring<12>(b12, d12);
+        u32 any = 0;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            any |= (b0[j] & b4[j]) | (b8[j] & b12[j]) | ((b0[j] | b4[j]) & (b8[j] | b12[j]));
+            any |= (d0[j] & d4[j]) | (d8[j] & d12[j]) | ((d0[j] | d4[j]) & (d8[j] | d12[j]));
+        }
+        return (any & 0x80008000u) != 0;
+    }
+    template <int K>
+    __device__ __forceinline__ void shift_in(u32 (&mb)[2], u32 (&md)[2]) const
+    {
+        u32 tb[2], td[2];
+        ring<K>(tb, td);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {      // ring position K ends at bit K of its half; what crosses the halves is overwritten
+            mb[j] = (tb[j] & 0x80008000u) | ((mb[j] >> 1) & 0x7FFF7FFFu);
+            md[j] = (td[j] & 0x80008000u) | ((md[j] >> 1) & 0x7FFF7FFFu);
+        }
+        if constexpr (K < 15) shift_in<K + 1>(mb, md);
+    }
+    __device__ __forceinline__ void masks(u32 (&mb)[2], u32 (&md)[2]) const
+    {
+        mb[0] = mb[1] = md[0] = md[1] = 0;
+        shift_in<0>(mb, md);
+    }
+};
+
 constexpr int FT = 32;
+constexpr int FT_P = FT / 4 + 3;       // dwords per staged row: columns x0 - 4 .. x0 + FT + 3, one of padding
+static_assert(FT == 32, "fast_nms_tile maps 256 lanes to 32 rows x 8 dwords");
 __device__ __forceinline__ void fast_nms_tile(const OrbTable *__restrict__ tab, const uint8_t *__restrict__ pyr,
                                               uint8_t *__restrict__ nms, int32_t *__restrict__ hist, int bid)
 {
-    __shared__ uint8_t s_img[(FT + 8) * (FT + 12)];
-    __shared__ uint8_t s_sc[(FT + 2) * (FT + 4)];
+    __shared__ u32 s_img4[(FT + 8) * FT_P];
+    __shared__ u32 s_sc4[(FT + 2) * (FT + 4) / 4];
     __shared__ unsigned short s_corner[(FT + 2) * (FT + 2)];
     __shared__ int s_nc;
     __shared__ int s_hist[256];
+    const uint8_t *const s_img = reinterpret_cast<const uint8_t *>(s_img4);
+    uint8_t *const s_sc = reinterpret_cast<uint8_t *>(s_sc4);
     const int l = find_level(tab->fast_tile_base, bid);
     const OrbLevel L = tab->lev[l];
     const int tile = bid - tab->fast_tile_base[l];
@@ -446,31 +578,73 @@ __device__ __forceinline__ void fast_nms_tile(const OrbTable *__restrict__ tab, 
     }
     s_hist[tid] = 0;
     const uint8_t *src = pyr + L.off;
-    const int IS = FT + 12;
-    for (int i = tid; i < (FT + 8) * (FT + 8); i += 256) {
-        const int ry = i / (FT + 8), rx = i % (FT + 8);
-        const int gy = min(max(y0 + ry - 4, 0), L.h - 1), gx = min(max(x0 + rx - 4, 0), L.w - 1);
-        s_img[ry * IS + rx] = src[(size_t)gy * L.stride + gx];
+    const int IS = 4 * FT_P;
+    // halo, clamped at the image border: a lane owns one dword of a row, 16 rows per trip (10 of 16 lanes load)
+    {
+        const int r16 = tid >> 4, c16 = tid & 15;
+        u32 v[3];
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            const int ry = 16 * t + r16;
+            if (c16 < FT / 4 + 2 && ry < FT + 8) {
+                const int gy = min(max(y0 + ry - 4, 0), L.h - 1);
+                v[t] = halo_dword<false>(src + (size_t)gy * L.stride, x0 - 4 + 4 * c16, L.w);
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            const int ry = 16 * t + r16;
+            if (c16 < FT / 4 + 2 && ry < FT + 8) s_img4[ry * FT_P + c16] = v[t];
+        }
     }
+    for (int i = tid; i < (FT + 2) * (FT + 4) / 4; i += 256) s_sc4[i] = 0;
+    if (tid == 0) s_nc = 0;
     __syncthreads();
     // segment test for every pixel of the tile + 1-px ring; the few corners are compacted into a list so that
     // the score (as long as the test itself) runs on full waves of corners instead of on every wave that
     // happens to contain one.  (Compacting the pretest survivors as well, so that the segment test too runs on full waves:
     // 21 % fewer instructions and no faster -- profiles/README.md "Dropped experiments" #7.)
+    // The usual compass pretest, as a WAVE decision: an arc of 9 of the 16 ring pixels contains at least two of the four
+    // compass pixels (ring positions 0, 4, 8, 12), so a pixel with fewer than two brighter and fewer than two darker
+    // compass pixels is no corner.  Lanes cannot skip work on their own, but a wave whose pixels all fail (flat
+    // ground, sky, the inside of uniform shapes) skips the 16-pixel segment test altogether; the outcome is the same.
     const int SS = FT + 4;
-    if (tid == 0) s_nc = 0;
-    __syncthreads();
-    for (int i = tid; i < (FT + 2) * (FT + 2); i += 256) {
-        const int ry = i / (FT + 2), rx = i % (FT + 2);
+    // trip 1, the 32x32 pixels of the tile itself: a lane tests four adjacent pixels (row ry, columns rx .. rx + 3 of the
+    // 34x34 grid) on the 7 x 3 dwords around them
+    {
+        const int ry = 1 + (tid >> 3), g = tid & 7, rx = 1 + 4 * g;
+        u32 w[7][3];
+#pragma unroll
+        for (int r = 0; r < 7; ++r)
+#pragma unroll
+            for (int q = 0; q < 3; ++q) w[r][q] = s_img4[(ry + r) * FT_P + g + q];
+        const FastQuad Q(w);
+        if (__any(Q.candidate())) {
+            u32 mb[2], md[2];
+            Q.masks(mb, md);
+            const int gy = y0 + ry - 1;
+            const bool row_in = gy >= 3 && gy < L.h - 3;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const u32 sel = (k & 2) ? 0x03020302u : 0x01000100u;
+                const bool br = fast_run9(__builtin_amdgcn_perm(mb[k & 1], mb[k & 1], sel));
+                const bool dk = fast_run9(__builtin_amdgcn_perm(md[k & 1], md[k & 1], sel));
+                const int gx = x0 + rx - 1 + k;
+                if ((br || dk) && row_in && gx >= 3 && gx < L.w - 3)
+                    s_corner[atomicAdd(&s_nc, 1)] = (unsigned short)((ry << 6) | (rx + k) | (br ? 0 : 0x8000));
+            }
+        }
+    }
+    // trip 2, the 132 pixels of the ring around the tile, one per lane
+    {
+        const int i = tid;
+        const int ry = i < FT + 2 ? 0 : (i < 2 * (FT + 2) ? FT + 1 : (i < 3 * FT + 4 ? i - (2 * FT + 3) : i - (3 * FT + 3)));
+        const int rx = i < FT + 2 ? i : (i < 2 * (FT + 2) ? i - (FT + 2) : (i < 3 * FT + 4 ? 0 : FT + 1));
         const int gy = y0 + ry - 1, gx = x0 + rx - 1;
         int pol = 0;
-        // The usual compass pretest, as a WAVE decision: an arc of 9 of the 16 ring pixels contains at least two of the four
-        // compass pixels (ring positions 0, 4, 8, 12), so a pixel with fewer than two brighter and fewer than two darker
-        // compass pixels is no corner.  Lanes cannot skip work on their own, but a wave whose 64 pixels all fail (flat
-        // ground, sky, the inside of uniform shapes) skips the 16-pixel segment test altogether; the outcome is the same.
         bool cand = false;
         const uint8_t *pc = s_img + (ry + 3) * IS + (rx + 3);
-        const bool inside = i < (FT + 2) * (FT + 2) && gx >= 3 && gx < L.w - 3 && gy >= 3 && gy < L.h - 3;
+        const bool inside = i < 4 * FT + 4 && gx >= 3 && gx < L.w - 3 && gy >= 3 && gy < L.h - 3;
         if (inside) {
             const int c = pc[0];
             const int v0 = (int)pc[3 * IS] - c, v4 = (int)pc[3] - c, v8 = (int)pc[-3 * IS] - c, v12 = (int)pc[-3] - c;
@@ -478,10 +652,9 @@ __device__ __forceinline__ void fast_nms_tile(const OrbTable *__restrict__ tab, 
             const int nd = (v0 < -RELOC_FAST_THRESHOLD) + (v4 < -RELOC_FAST_THRESHOLD) + (v8 < -RELOC_FAST_THRESHOLD) + (v12 < -RELOC_FAST_THRESHOLD);
             cand = nb >= 2 || nd >= 2;
         }
-        if (__any(cand)) {
+        if (tid < 3 * 64 && __any(cand)) {
             if (cand) pol = fast_is_corner(pc, IS, RELOC_FAST_THRESHOLD);
         }
-        s_sc[ry * SS + rx] = 0;
         if (pol) s_corner[atomicAdd(&s_nc, 1)] = (unsigned short)((ry << 6) | rx | (pol < 0 ? 0x8000 : 0));
     }
     __syncthreads();
