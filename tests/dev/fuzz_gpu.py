@@ -138,13 +138,22 @@ while time.time() < t_end:
         if g[0] != x[0] or not np.array_equal(g[3], x[3]): fail(kind, (m, seed, "inliers"))
         if g[0] and (np.abs(g[2] - x[2]).max() > 1e-4 or np.abs(g[1] - x[1]).max() > 1e-4): fail(kind, (m, seed, "pose", np.abs(g[2] - x[2]).max()))
     elif kind == "record":
-        img = synth.textured_frame(rng, 640, 480)
-        dep = synth.ground_depth_mm(rng, zeros=float(rng.uniform(0, 0.3)))
-        from nclt_slam_project_amd.recorder import LandmarkRecorderCore
-        from nclt_slam_project_amd.cv2_shim import Cv2Shim
-        a = LandmarkRecorderCore(cv2=Cv2Shim(e)).tick(img, dep, synth.base_pose(0, 0, 0), 0.0)
-        b = LandmarkRecorderCore(engine=e).tick(img, dep, synth.base_pose(0, 0, 0), 0.0)
-        if (a is None) != (b is None): fail(kind, "none")
-        if a is not None and not (np.array_equal(a["descriptors"], b["descriptors"]) and
-                                  np.array_equal(a["keypoints_3d_cam"].view(np.uint32), b["keypoints_3d_cam"].view(np.uint32))): fail(kind, "arrays")
+        w, h = (640, 480) if rng.random() < 0.3 else (int(rng.integers(200, 1281)), int(rng.integers(200, 721)))
+        nf = int(rng.choice([500, 3000])); rgb = bool(rng.integers(0, 2))
+        img = synth.textured_frame(rng, w, h, n_shapes=max(40, w * h // 800))
+        dep = synth.ground_depth_mm(rng, w, h, zeros=float(rng.uniform(0, 0.3)))
+        sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+        import record_ref as RR
+        g = e.record_frame(img, dep, nf, order_rgb=rgb); f = e.orb_features()
+        x = RR.record_rows(f["xy"], f["desc"], dep, w, h, (320.0, 320.0, 320.0, 240.0))
+        if not (np.array_equal(g["kp_index"], x[0]) and np.array_equal(g["xy"].view(np.uint32), x[1].view(np.uint32)) and
+                np.array_equal(g["desc"], x[2]) and np.array_equal(g["pts3d"].view(np.uint32), x[3].view(np.uint32))): fail(kind, (w, h, nf, rgb, "ref"))
+        if (w, h, rgb) == (640, 480, False):      # the recorder cores are fixed to the 640x480 BGR camera
+            from nclt_slam_project_amd.recorder import LandmarkRecorderCore
+            from nclt_slam_project_amd.cv2_shim import Cv2Shim
+            a = LandmarkRecorderCore(cv2=Cv2Shim(e), nfeatures=nf).tick(img, dep, synth.base_pose(0, 0, 0), 0.0)
+            b = LandmarkRecorderCore(engine=e, nfeatures=nf).tick(img, dep, synth.base_pose(0, 0, 0), 0.0)
+            if (a is None) != (b is None): fail(kind, "none")
+            if a is not None and not (np.array_equal(a["descriptors"], b["descriptors"]) and
+                                      np.array_equal(a["keypoints_3d_cam"].view(np.uint32), b["keypoints_3d_cam"].view(np.uint32))): fail(kind, "arrays")
 print("fuzz ok", n_case, flush=True)

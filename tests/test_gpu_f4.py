@@ -43,3 +43,71 @@ def test_depth_points_equals_numpy(engine):
         got = engine.depth_points(depth, step=4)
         assert got.shape == exp.shape and len(got) > 5000
         np.testing.assert_array_equal(got.view(np.uint32), exp.view(np.uint32))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# k_depth_points over its arguments, against tests/record_ref.py (the reference's float32 expression), bit for bit
+K4_OTHER = (517.3, 516.5, 318.6, 255.3)
+
+
+def _special_f32(zmin, zmax):
+    f = np.float32
+    return {"zmin": f(zmin), "below_zmin": np.nextafter(f(zmin), f(0)), "above_zmin": np.nextafter(f(zmin), f(1)),
+            "zmax": f(zmax), "below_zmax": np.nextafter(f(zmax), f(0)), "above_zmax": np.nextafter(f(zmax), f(100)),
+            "negative": f(-2.5), "minus_zero": f(-0.0), "denormal": f(1e-40), "nan": f(np.nan), "inf": f(np.inf),
+            "minus_inf": f(-np.inf)}
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.uint16], ids=["f32", "u16"])
+@pytest.mark.parametrize("w,h", [(640, 480), (641, 479), (97, 65), (31, 17), (1280, 720)])
+@pytest.mark.parametrize("step", [1, 3, 4, 7])
+def test_depth_points_steps_sizes_dtypes(engine, step, w, h, dtype):
+    import record_ref as RR
+    rng = np.random.default_rng(step * 100003 + w * 7 + h + (dtype == np.uint16))
+    K4 = K4_OTHER if (step + w) % 2 else (320.0, 320.0, 320.0, 240.0)
+    zmin, zmax = (0.3, 10.0) if step != 3 else (0.45, 6.5)
+    gw, gh = -(-w // step), -(-h // step)
+    assert (w, h) != (31, 17) or gw * gh < 1024                       # fewer grid points than lanes of the one workgroup
+    if dtype == np.uint16:
+        depth = rng.integers(0, 13000, (h, w)).astype(np.uint16)
+        depth[rng.random((h, w)) < 0.1] = 0
+        special = {"zmin": round(zmin * 1000), "below_zmin": round(zmin * 1000) - 1, "above_zmin": round(zmin * 1000) + 1,
+                   "zmax": round(zmax * 1000), "below_zmax": round(zmax * 1000) - 1, "above_zmax": round(zmax * 1000) + 1,
+                   "zero": 0, "largest": 65535}
+    else:
+        depth = rng.uniform(-1.0, 13.0, (h, w)).astype(np.float32)
+        special = _special_f32(zmin, zmax)
+    cells = rng.permutation(gw * gh)[:len(special)]
+    assert len(cells) == len(special)
+    for cell, val in zip(cells, special.values()):
+        depth[(cell // gw) * step, (cell % gw) * step] = val
+    sampled = depth[::step, ::step]
+    assert sampled.shape == (gh, gw)
+    bits = sampled.view(np.uint32 if dtype == np.float32 else np.uint16)
+    for name, val in special.items():                                  # each kind is on the sampled grid
+        assert (bits == np.asarray(val, depth.dtype).view(bits.dtype)).any(), name
+    exp = RR.depth_points(depth, step, K4, zmin, zmax)
+    got = engine.depth_points(depth, step=step, K4=K4, zmin=zmin, zmax=zmax)
+    assert got.shape == exp.shape and 0 < len(exp) < gw * gh
+    np.testing.assert_array_equal(got.view(np.uint32), exp.view(np.uint32))
+    if dtype == np.float32:
+        zs = set(exp[:, 0].view(np.uint32).tolist())
+        kept = {k for k, v in special.items() if np.float32(v).view(np.uint32).item() in zs}
+        assert {"above_zmin", "below_zmax"} <= kept and not kept & {"zmin", "zmax", "below_zmin", "above_zmax", "inf"}
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.uint16], ids=["f32", "u16"])
+def test_depth_points_all_rejected_and_all_kept(engine, dtype):
+    import record_ref as RR
+    for w, h, step in ((640, 480, 4), (97, 65, 3), (31, 17, 7)):
+        gw, gh = -(-w // step), -(-h // step)
+        none = np.zeros((h, w), dtype)
+        none[1::2] = 20 if dtype == np.float32 else 20000
+        got = engine.depth_points(none, step=step)
+        assert got.shape == (0, 3) == RR.depth_points(none, step, (320.0, 320.0, 320.0, 240.0), 0.3, 10.0).shape
+        full = np.random.default_rng(w).integers(400, 9000, (h, w)).astype(np.uint16)
+        full = full if dtype == np.uint16 else full.astype(np.float32) / np.float32(1000.0)
+        exp = RR.depth_points(full, step, K4_OTHER, 0.3, 10.0)
+        got = engine.depth_points(full, step=step, K4=K4_OTHER)
+        assert got.shape == exp.shape == (gw * gh, 3)
+        np.testing.assert_array_equal(got.view(np.uint32), exp.view(np.uint32))
