@@ -54,7 +54,7 @@ constexpr int64_t MAX_DB_RECORDS = 0xFFFFF;   // the local-candidate key keeps t
 // phase stretches 2-3x (k_pyramid 49 vs 17 us, k_fast_blur 46 vs 16) and the scans of the streams overlap less.  With
 // priority the same instructions are issued, only sooner: 4-stream run 6060 -> 6250 frames/s, single-stream ticks unchanged.
 // -DRELOC_SMALL_PRIO=0 switches it off (A/B builds).
-// Register budget of the scan kernels (k_db_scan, k_db_scan_batch), capped with amdgpu_num_vgpr (0 = the compiler's choice: 112).
+// Register budget of the scan kernels (k_db_scan, k_db_scan_batch, k_db_scan_emit, k_db_scan_emit_batch), capped with amdgpu_num_vgpr (0 = the compiler's choice: 112).
 // Four scan waves per SIMD at 112 registers leave 64 of the 512 per lane to whatever else wants to run beside them -- and
 // k_pyramid (94), k_pnp_hyp (94), k_tick_finalize (80) do not fit into 64: they wait for a scan workgroup to retire.  At 104
 // (28 bytes of scratch) four scan waves leave 96 and a fifth still does not fit (5 x 104 > 512); at 96 a fifth does, and
@@ -259,17 +259,14 @@ __device__ __forceinline__ void undistort_norm(const DistCoef &d, const double K
     }
 }
 
-// Optional heading mask of the whole-database scan: records whose teach heading is incompatible with the
-// robot's are not scored (count 0), exactly the records the reference skips at G:329-330.  xyh == NULL: no mask.
+// What a whole-database counting scan (launch_db_count, k_db_scan_batch) may leave out.  The heading mask: records whose
+// teach heading is incompatible with the robot's are not scored (count 0), exactly the records the reference skips at
+// G:329-330; xyh == NULL: no mask.  skip_if: the scan of a frame that needs none.
 struct ScanMask {
     const double *xyh = nullptr;
     double q[4] = {0, 0, 0, 1};                  // base_link quaternion x y z w of the robot
     double cos_tol = 6.123233995736766e-17;      // cos(HEADING_TOL_DEG = 90 degrees) in double
     const int32_t *skip_if = nullptr;            // RELOC_TICK_AUTO: the whole launch stands down when *skip_if != 0
-    // emit mode only (M:333-336): when g_obj is set, every mutual match also leaves its 3-D / 2-D pair
-    // (keypoints_3d_cam[queryIdx], pts_curr_2d[trainIdx]) next to its index triplet, so no gather launch follows
-    const float *g_pts3d = nullptr, *g_xy = nullptr;
-    float *g_obj = nullptr, *g_img = nullptr;
 };
 
 struct reloc_ctx {

@@ -22,8 +22,8 @@
 // ranges, walked in 16-row chunks and finished with ONE flexible chunk of 1-15 rows.  Per chunk a wave produces (a) per lane and column the best row
 // (running 16-bit minimum), merged into LDS with ds_min_u32, and (b) per row the best column:
 // an in-lane 8-way 16-bit minimum, then a register-tile butterfly across lanes
-// (v_permlane16_swap / ds_bpermute).  Mutual nearest neighbours are resolved in LDS; the kernel
-// emits the per-record count and optionally the (queryIdx, trainIdx, distance) list in queryIdx
+// (v_permlane16_swap / ds_bpermute).  Mutual nearest neighbours are resolved in LDS; k_db_scan
+// leaves the per-record count, k_db_scan_emit the (queryIdx, trainIdx, distance) list in queryIdx
 // order.  Keys are (distance << k | index): the minimum of packed keys is the smallest distance
 // with the LOWEST index on ties, which is the tie rule of the specification.
 #include <stdlib.h>
@@ -188,10 +188,10 @@ __device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int
 template <int N, class F>
 __device__ __forceinline__ void static_for(F &&f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
-// One R-row chunk (R = 16 or 4) of a record against the wave's 64*NJ columns.
+// One 16-row chunk of a record against the wave's 64*NJ columns; nr = the rows it really has (1..16).
 //   q[j]    : descriptor of column colbase + j*64 + lane (padding columns repeat the last real column:
 //             a duplicate offers the same distance with a larger index, so it never wins a minimum)
-//   FLEX    : tail chunk of nr < R rows: the rows it does not have are skipped (wave-uniform branch) and enter the
+//   nr < 16 : the tail chunk of a wave's row range: the rows it does not have are skipped (wave-uniform branch) and enter the
 //             butterfly as "infinity"; their fetch addresses are clamped to the record's last row
 // One 16-bit key per pair serves both directions: distance << 7 | row-in-chunk << 3 | column slot.
 // Among the rows of one column the slot bits are equal, so the minimum is (distance, row); among the
@@ -199,23 +199,23 @@ __device__ __forceinline__ void static_for(F &&f) { static_for_impl(f, std::make
 // one v_fmaak_f32 (key_fma) + 2 v_min_u16 on top of the 16 instructions of the distance (through round 4: v_lshlrev_b16 +
 // v_or_b32 for the key; the row's 8-way minimum with v_min3_f32 was measured and dropped, profiles/README.md
 // "Dropped experiments" #9).
-template <int NJ, int R, bool FLEX>
+template <int NJ>
 __device__ __forceinline__ void scan_chunk(const uint4 *__restrict__ rec, int n, int tc, int nr, const u32 (&q)[NJ][8],
                                            u32 colbase, u32 *rowkey, u32 *colbest, bool single_cb, int lane)
 {
     // (column minima in LDS instead of registers: measured and dropped, profiles/README.md "Dropped experiments" #1)
     u32 cb16[NJ];                                                      // seeded by row 0, which every chunk has (nr >= 1)
     const u32 c128 = 0x43000000u;                                      // 128.0f, key_fma's multiplicand
-    // The R row keys are reduced by a register-tile butterfly, but AS THEY COME: the rows of the chunk
-    // are visited in bit-reversed order (0, R/2, R/4, 3R/4, ...), so the two operands of every butterfly node are
-    // finished right after each other and at most log2(R) + 1 partial results are alive instead of R keys -- 11
-    // VGPRs less at R = 16, which takes the kernel from 115 to <= 104 registers: four resident workgroups then leave
+    // The 16 row keys are reduced by a register-tile butterfly, but AS THEY COME: the rows of the chunk
+    // are visited in bit-reversed order (0, 8, 4, 12, ...), so the two operands of every butterfly node are
+    // finished right after each other and at most log2(16) + 1 partial results are alive instead of 16 keys -- 11
+    // VGPRs less, which takes the kernel from 115 to <= 104 registers: four resident workgroups then leave
     // 96 registers per SIMD lane free, enough for the small kernels of other streams to run BESIDE the scan.
-    constexpr int LOG_R = R == 16 ? 4 : (R == 8 ? 3 : 2);
+    constexpr int R = 16, LOG_R = 4;
     u32 stk[LOG_R + 1];
     // Teach rows come through the scalar cache, one fetch in flight (see srow_landed).
     auto bitrev = [](int i) { int r = 0; for (int b = 0; b < LOG_R; ++b) r |= ((i >> b) & 1) << (LOG_R - 1 - b); return r; };
-    auto row_of = [&](int i) { const int t = bitrev(i); return FLEX ? min(tc + t, n - 1) : tc + t; };   // wave-uniform
+    auto row_of = [&](int i) { return min(tc + bitrev(i), n - 1); };   // wave-uniform
     uint4 a = rec[2 * row_of(0)], b = rec[2 * row_of(0) + 1];
     // compile-time row and column indices: the key constants are immediates.
     // (bookkeeping software-pipelined into the next row's chains: measured and dropped, profiles/README.md "Dropped experiments" #2)
@@ -227,7 +227,7 @@ __device__ __forceinline__ void scan_chunk(const uint4 *__restrict__ rec, int n,
         if (i + 1 < R) { na = rec[2 * row_of(i + 1)]; nb = rec[2 * row_of(i + 1) + 1]; }   // ... the next one on its way
         __builtin_amdgcn_sched_barrier(0);
         u32 best = 0x7FFFFFu;                                         // a row the chunk does not have: loses every minimum
-        if (!FLEX || t == 0 || t < nr) {                                 // wave-uniform
+        if (t == 0 || t < nr) {                                          // wave-uniform
             const u32 w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
             u32 h[NJ];
             ham8_cols<NJ>(q, w, h);                                    // NJ accumulator chains, order pinned
@@ -240,35 +240,23 @@ __device__ __forceinline__ void scan_chunk(const uint4 *__restrict__ rec, int n,
             });
         }
         u32 v = (best << 9) | (u32)lane;
-        // Node of level k joins rows t and t + R / 2^(k+1).  The four levels split on lane bits 2, 3 (DPP minima, two instructions
+        // Node of level k joins rows t and t + 16 / 2^(k+1).  The four levels split on lane bits 2, 3 (DPP minima, two instructions
         // a node: the levels with 8 and 4 nodes), 4 and 5 (permlane swap + minimum), and the two lane bits left over are reduced
         // on the one value at the end: 32 instead of ~66 instructions per chunk and no select masks to keep (rounds 1-3: levels on
         // bits 3, 2, 1, 0 with select nodes -- two v_cndmask, a DPP move and a minimum each).  4-stream run +1.8 % (6 836 -> 6 958
         // frames/s, interleaved), and the kernel fits its 104 registers without scratch.  Lane l ends with row 8 b2 + 4 b3 + 2 b4 + b5.
-        static_assert(R == 16, "the level -> lane bit assignment below is for 16-row chunks");
-        auto node = [&](auto level, u32 lo, u32 hi_) -> u32 {
-            constexpr int k = decltype(level)::value;
-            if constexpr (k == 0) return bfly_dpp<4>(lo, hi_);
-            else if constexpr (k == 1) return bfly_dpp<8>(lo, hi_);
-            else if constexpr (k == 2) return bfly<16>(lo, hi_, lane);
-            else return bfly<32>(lo, hi_, lane);
-        };
         if constexpr ((i & 1) == 0) stk[0] = v;
         else {
-            v = node(std::integral_constant<int, 0>{}, stk[0], v);
-            if constexpr ((i & 2) == 0 || LOG_R < 2) stk[1] = v;
+            v = bfly_dpp<4>(stk[0], v);
+            if constexpr ((i & 2) == 0) stk[1] = v;
             else {
-                v = node(std::integral_constant<int, 1>{}, stk[1], v);
-                if constexpr (LOG_R >= 3) {
-                    if constexpr ((i & 4) == 0) stk[2] = v;
-                    else {
-                        v = node(std::integral_constant<int, 2>{}, stk[2], v);
-                        if constexpr (LOG_R >= 4) {
-                            if constexpr ((i & 8) == 0) stk[3] = v;
-                            else stk[4] = node(std::integral_constant<int, 3>{}, stk[3], v);
-                        } else stk[3] = v;
-                    }
-                } else stk[2] = v;
+                v = bfly_dpp<8>(stk[1], v);
+                if constexpr ((i & 4) == 0) stk[2] = v;
+                else {
+                    v = bfly<16>(stk[2], v, lane);
+                    if constexpr ((i & 8) == 0) stk[3] = v;
+                    else stk[4] = bfly<32>(stk[3], v, lane);
+                }
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -279,7 +267,7 @@ __device__ __forceinline__ void scan_chunk(const uint4 *__restrict__ rec, int n,
     const int row_in_chunk = ((lane >> 2) & 1) * 8 + ((lane >> 3) & 1) * 4 + ((lane >> 4) & 1) * 2 + (lane >> 5);
     const bool writer = (lane & 3) == 0;
     const int row = tc + row_in_chunk;
-    if (writer && row_in_chunk < (FLEX ? nr : R)) {
+    if (writer && row_in_chunk < nr) {
         const u32 key = (m & 0xFFFF0000u) | (colbase + ((m >> 9) & 7u) * 64u + (m & 63u));   // distance << 16 | column
         if (single_cb) rowkey[row] = key;
         else atomicMin(&rowkey[row], key);
@@ -292,29 +280,39 @@ __device__ __forceinline__ void scan_chunk(const uint4 *__restrict__ rec, int n,
     }
 }
 
-// grid: any; block: 256 (4 waves).  Dynamic LDS: (ncb*64*NJ + max_rows + 16) * 4 bytes.
-// NJ = columns per lane.  A wave covers a "column block" of 64*NJ current descriptors.  When the
-// number of column blocks ncb divides 4, wave w is bound to block w % ncb for the whole launch (its
-// descriptors stay in registers) and shares a record's rows with the other waves bound to that block;
-// otherwise every wave walks all column blocks and reloads its registers per block.
-// mask.xyh != NULL: heading-incompatible records are not scored (count 0), see ScanMask.
+// ---- what the counting scan and the emit pass share ---------------------------------------------
+// NJ = columns per lane.  A wave covers a "column block" of 64*NJ current descriptors, kept in registers (load_q).
 // NJ = 8 is the working point (500 descriptors are one block, 64 VGPRs of descriptors, 4 waves per SIMD);
 // NJ = 4 / 2 serve calls with at most 256 / 128 current descriptors, see k_db_scan.  (8 waves per SIMD -- NJ = 4 with two blocks,
 // or the descriptors in LDS -- measured slower: profiles/README.md "Dropped experiments" #3.)
-template <int NJ, bool EMIT, int NW = 4>
-__device__ __forceinline__ void db_scan_body(
+// When the number of column blocks ncb divides the NW waves of a workgroup, wave w is bound to block w % ncb for the whole
+// launch (its descriptors stay in registers) and shares a record's rows with the other waves bound to that block; otherwise
+// every wave walks all column blocks and reloads its registers per block.
+struct WaveBinding {
+    bool bound;               // static wave -> column block binding
+    int my_cb;                // the bound wave's column block
+    int chunk0, chunk_step;   // this wave's place among, and the number of, the waves that share a block's rows
+};
+template <int NW>
+__device__ __forceinline__ WaveBinding bind_wave(int wave, int ncb)
+{
+    const bool bound = (NW % ncb) == 0;
+    return {bound, bound ? wave % ncb : 0, bound ? wave / ncb : wave, bound ? NW / ncb : NW};
+}
+
+// The emit pass: the match lists (queryIdx, trainIdx, distance, in queryIdx order) of a few records, dealt statically
+// (record it = blockIdx.x, + gridDim.x, ...).  Dynamic LDS: (ncb*64*NJ + max_rows + 16) * 4 bytes.
+// Record it of the launch is rec_ids[it] (rec_ids == NULL: it) and lists emit_stride entries apart; with g_obj set every
+// mutual match also leaves its 3-D / 2-D pair (keypoints_3d_cam[queryIdx], pts_curr_2d[trainIdx], M:333-336) next to its
+// index triplet, so no gather launch follows.
+template <int NJ, int NW>
+__device__ __forceinline__ void db_emit_body(
     u32 *lds, int C, const uint4 *__restrict__ db, const int64_t *__restrict__ off, const int32_t *__restrict__ rec_ids,
     const int32_t *__restrict__ n_ids_p, int n_ids_max, const uint4 *__restrict__ cur, int max_rows,
-    int32_t *__restrict__ counts, int32_t *__restrict__ m_qidx, int32_t *__restrict__ m_tidx, int32_t *__restrict__ m_dist,
-    int32_t *__restrict__ m_n, int emit_stride, const ScanMask &mask, u32 *ticket, int quota, u32 *ticket_pool = nullptr,
-    int pool_frames = 1, int block = -1, int n_blocks = -1)
+    int32_t *__restrict__ m_qidx, int32_t *__restrict__ m_tidx, int32_t *__restrict__ m_dist, int32_t *__restrict__ m_n,
+    int emit_stride, const float *__restrict__ g_pts3d, const float *__restrict__ g_xy, float *__restrict__ g_obj,
+    float *__restrict__ g_img)
 {
-    // ticket: the 8 per-XCD record counters of THIS scan; ticket_pool / pool_frames: all counters of the launch (a batched
-    // launch scans pool_frames frames, frame f owning ticket_pool + f * 8 * TICKET_STRIDE; the word behind them counts
-    // the workgroups that have left).  block / n_blocks: this workgroup's index and the number of workgroups of ITS scan
-    // (static deal; default = the launch's).
-    if (!ticket_pool) ticket_pool = ticket;
-    if (block < 0) { block = blockIdx.x; n_blocks = gridDim.x; }
     constexpr int CB = 64 * NJ;           // columns per block
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: row fetches stay scalar
@@ -322,7 +320,8 @@ __device__ __forceinline__ void db_scan_body(
     const int ncb = max((C + CB - 1) / CB, 1);
     u32 *colbest = lds;                   // ncb * CB : best (distance << 16 | row) per column
     u32 *rowkey = colbest + ncb * CB;     // max_rows : best (distance << 16 | column) per row
-    u32 *wsum = rowkey + max_rows;        // 16
+    u32 *wsum = rowkey + max_rows;        // 16       : mutual pairs per wave
+    static_assert(NW == 1 || NW == 2 || NW == 4 || NW == 8, "wsum holds one word per wave");
 
     u32 q[NJ][8];
     auto load_q = [&](int colbase) {
@@ -334,77 +333,10 @@ __device__ __forceinline__ void db_scan_body(
             q[j][4] = b.x; q[j][5] = b.y; q[j][6] = b.z; q[j][7] = b.w;
         }
     };
-    static_assert(NW == 1 || NW == 2 || NW == 4 || NW == 8, "wsum[8] is the ticket slot");
-    const bool bound = (NW % ncb) == 0;           // ncb divides the wave count: static wave -> column block binding
-    const int my_cb = bound ? wave % ncb : 0;
-    const int chunk0 = bound ? wave / ncb : wave, chunk_step = bound ? NW / ncb : NW;
-    // RELOC_TICK_AUTO: this scan stands down (scan-uniform).  Its workgroups still check out at the end, so that the last
-    // workgroup of the launch can put the counters back
-    const bool stand_down = mask.skip_if && *mask.skip_if != 0;
-    if (bound && !stand_down) load_q(my_cb * CB);
-    double hc = 1.0, hs = 0.0, cos_tol = 0.0;
-    if (mask.xyh) {
-        cur_heading_q(mask.q, hc, hs);
-        cos_tol = mask.cos_tol;
-    }
-
-    // Work distribution.  ticket == NULL: record it = blockIdx.x, + gridDim.x, ... (static).  Otherwise the grid is one
-    // resident generation and every workgroup draws records from counters, so that all CUs stay full until the last
-    // record (with a static deal the workgroups of a CU finish one after the other and the CU's tail runs at 3, 2, 1
-    // waves per SIMD).  One counter serves ~88 draws per microsecond (measured: 10 000 draws on one word = 143 us), so
-    // there are 8, one per XCD (HW_REG_XCC_ID) on its own 128-byte line: counter x deals records x, x + 8, x + 16, ...;
-    // a workgroup whose counter has run dry moves on to the next one.  The draw for the next record is in flight
-    // while the current one is processed.  The last workgroup to leave (ticket[TICKET_DONE]) zeroes all words.
-    constexpr int TICKET_STRIDE = 32;
-    int shard = 0, dry = 0;
-    if (ticket) {
-        u32 x;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(x));
-        shard = (int)(x & 7u);
-    }
-    auto draw = [&]() -> u32 { return atomicAdd(&ticket[shard * TICKET_STRIDE], 1u); };
-    // thread 0: turn a drawn ticket into a record index, moving to the next counter while the current one is dry
-    auto settle = [&](u32 t) -> int {
-        for (;;) {
-            const long long rec_i = (long long)shard + 8ll * (long long)t;
-            if (rec_i < n_ids) return (int)rec_i;
-            if (++dry >= 8) return n_ids;
-            shard = (shard + 1) & 7;
-            t = draw();
-        }
-    };
-    int it = block;
-    if (stand_down) it = n_ids;
-    else if (ticket) {
-        if (tid == 0) wsum[8] = (u32)settle(draw());
-        __syncthreads();
-        it = __builtin_amdgcn_readfirstlane((int)wsum[8]);
-    }
-    // quota: a workgroup leaves after that many records although tickets remain (the grid then holds several
-    // generations): its slot goes to whatever waits -- with several contexts sharing the chip that is another stream's
-    // ORB / PnP kernel, which otherwise would not get a CU until this whole scan has drained
-    int left = quota > 0 ? quota : 0x7fffffff;
-    for (; it < n_ids;) {
-        --left;
-        u32 next_ticket = 0;
-        if (ticket && tid == 0 && left > 0) next_ticket = draw();        // no draw that this workgroup would not serve
-        auto advance = [&]() {
-            if (ticket) {
-                __syncthreads();
-                if (tid == 0) wsum[8] = left > 0 ? (u32)settle(next_ticket) : (u32)n_ids;
-                __syncthreads();
-                it = __builtin_amdgcn_readfirstlane((int)wsum[8]);
-            } else {
-                it += n_blocks;
-            }
-        };
+    const WaveBinding wb = bind_wave<NW>(wave, ncb);
+    if (wb.bound) load_q(wb.my_cb * CB);
+    for (int it = blockIdx.x; it < n_ids; it += gridDim.x) {
         const int r = rec_ids ? rec_ids[it] : it;
-        if (mask.xyh && !heading_ok(mask.xyh + 4 * (int64_t)r, hc, hs, cos_tol)) {      // workgroup-uniform
-            if (tid == 0 && counts) counts[EMIT ? it : r] = 0;
-            if (EMIT && tid == 0 && m_n) m_n[it] = 0;
-            advance();
-            continue;
-        }
         const int64_t row0 = off[r];
         const int n = (int)(off[r + 1] - row0);
         const uint4 *rec = db + 2 * row0;
@@ -412,21 +344,21 @@ __device__ __forceinline__ void db_scan_body(
         for (int i = tid; i < n; i += 64 * NW) rowkey[i] = 0xFFFFFFFFu;
         __syncthreads();
         if (n > 0 && C > 0) {
-            for (int cb = bound ? my_cb : 0; cb < (bound ? my_cb + 1 : ncb); ++cb) {
-                if (!bound) load_q(cb * CB);
+            for (int cb = wb.bound ? wb.my_cb : 0; cb < (wb.bound ? wb.my_cb + 1 : ncb); ++cb) {
+                if (!wb.bound) load_q(cb * CB);
                 // The record's rows are dealt to the waves bound to this column block as contiguous ranges, balanced to
                 // the single row; a wave walks its range in 16-row chunks and finishes it with ONE flexible chunk of
                 // 1-15 rows (n = 64, 4 waves: one 16-row chunk each; n = 45: 12/11/11/11 rows = one flexible chunk each
                 // -- round 2 walked tails in 4-row chunks and paid the chunk epilogue, butterfly + 9 LDS minima, every 4
                 // rows: 1.56 T pairs/s on 45-row records against 2.0 T on 64-row ones).
-                const int per = n / chunk_step, extra = n % chunk_step;
-                int tc = chunk0 * per + min(chunk0, extra);
-                const int tend = tc + per + (chunk0 < extra ? 1 : 0);
+                const int per = n / wb.chunk_step, extra = n % wb.chunk_step;
+                int tc = wb.chunk0 * per + min(wb.chunk0, extra);
+                const int tend = tc + per + (wb.chunk0 < extra ? 1 : 0);
                 // ONE instantiation serves full and partial chunks: the unrolled 16-row body is 45 KB of code, two of them
                 // would not share the 64 KB instruction cache
 #pragma nounroll
                 for (; tc < tend; tc += 16)
-                    scan_chunk<NJ, 16, true>(rec, n, tc, min(16, tend - tc), q, (u32)(cb * CB), rowkey, colbest, ncb == 1, lane);
+                    scan_chunk<NJ>(rec, n, tc, min(16, tend - tc), q, (u32)(cb * CB), rowkey, colbest, ncb == 1, lane);
             }
         }
         __syncthreads();
@@ -448,15 +380,15 @@ __device__ __forceinline__ void db_scan_body(
             for (int w = 0; w < wave; ++w) before += wsum[w];
             u32 total = 0;
             for (int w = 0; w < NW; ++w) total += wsum[w];
-            if (EMIT && mutual) {
+            if (mutual) {
                 const u32 pos = before + (u32)__popcll(bal & ((1ull << lane) - 1ull));
                 const int64_t o = (int64_t)it * emit_stride + pos;
                 m_qidx[o] = row;
                 m_tidx[o] = (int32_t)(key & 0xFFFFu);
                 m_dist[o] = (int32_t)(key >> 16);
-                if (mask.g_obj) {
-                    const float *p3 = mask.g_pts3d + 3 * (row0 + row), *p2 = mask.g_xy + 2 * (size_t)(key & 0xFFFFu);
-                    float *po = mask.g_obj + 3 * o, *pi = mask.g_img + 2 * o;
+                if (g_obj) {
+                    const float *p3 = g_pts3d + 3 * (row0 + row), *p2 = g_xy + 2 * (size_t)(key & 0xFFFFu);
+                    float *po = g_obj + 3 * o, *pi = g_img + 2 * o;
                     po[0] = p3[0]; po[1] = p3[1]; po[2] = p3[2];
                     pi[0] = p2[0]; pi[1] = p2[1];
                 }
@@ -464,22 +396,13 @@ __device__ __forceinline__ void db_scan_body(
             base += total;
             __syncthreads();
         }
-        if (tid == 0) {
-            if (counts) counts[EMIT ? it : r] = (int32_t)base;
-            if (EMIT && m_n) m_n[it] = (int32_t)base;
-        }
-        advance();
-    }
-    if (ticket && tid == 0) {
-        const int words = pool_frames * 8;
-        if (atomicAdd(&ticket_pool[words * TICKET_STRIDE], 1u) == gridDim.x - 1) {      // every other workgroup has made its last draw
-            for (int x = 0; x <= words; ++x)
-                __hip_atomic_store(&ticket_pool[x * TICKET_STRIDE], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        if (tid == 0 && m_n) m_n[it] = (int32_t)base;
     }
 }
 
-// The counting scan (no match lists): the per-record flow of db_scan_body reduced to TWO barriers per record.
+// The counting scan (no match lists) of the whole database.  grid: any; block: 256 (4 waves).  Dynamic LDS:
+// (col_words + max_rows + 16) * 4 bytes.  mask.xyh != NULL: heading-incompatible records are not scored (count 0), see ScanMask.
+// The per-record flow of db_emit_body reduced to TWO barriers per record:
 //   - colbest is double-buffered: the buffer of the NEXT record is cleared while this record's chunks run, so no
 //     clear / barrier pair stands in front of a record;
 //   - with one column block (<= 64 * NJ current descriptors: every fused tick) each row key is written by exactly one
@@ -489,7 +412,7 @@ __device__ __forceinline__ void db_scan_body(
 // A workgroup's FIRST record is dealt statically (record = workgroup index, no counter round trip in front of the first
 // row); the counters deal the records behind the grid.  Round 2's flow had six barriers per record and waited for an
 // atomic before the first row: 10 000 x 64 in three generations 162 -> [see DESIGN.md] us.
-template <int NJ, int NW>
+template <int NJ>
 __device__ __forceinline__ void db_count_body(
     u32 *lds, int C, const uint4 *__restrict__ db, const int64_t *__restrict__ off, const int32_t *__restrict__ rec_ids,
     const int32_t *__restrict__ n_ids_p, int n_ids_max, const uint4 *__restrict__ cur, int max_rows,
@@ -501,9 +424,13 @@ __device__ __forceinline__ void db_count_body(
     // database, so they normally serve every record.  The eight workgroups behind them (one per XCD, the last to start) draw
     // until the counters run dry: whatever the budgets left over is served (nothing, when the host knew the row total).
     // (The variants dropped on the way, a quota of records among them: profiles/README.md "Dropped experiments" #4.)
+    // ticket: the 8 per-XCD record counters of THIS scan; ticket_pool / pool_frames: all counters of the launch (a batched
+    // launch scans pool_frames frames, frame f owning ticket_pool + f * 8 * TICKET_STRIDE; the word behind them counts
+    // the workgroups that have left).  block / n_blocks: this workgroup's index and the number of workgroups of ITS scan
+    // (default = the launch's).
     if (!ticket_pool) ticket_pool = ticket;
     if (block < 0) { block = blockIdx.x; n_blocks = gridDim.x; }
-    constexpr int CB = 64 * NJ;
+    constexpr int CB = 64 * NJ, NW = 4;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n_ids = n_ids_p ? min(*n_ids_p, n_ids_max) : n_ids_max;
@@ -529,11 +456,11 @@ __device__ __forceinline__ void db_count_body(
             q[j][4] = b.x; q[j][5] = b.y; q[j][6] = b.z; q[j][7] = b.w;
         }
     };
-    const bool bound = (NW % ncb) == 0;
-    const int my_cb = bound ? wave % ncb : 0;
-    const int chunk0 = bound ? wave / ncb : wave, chunk_step = bound ? NW / ncb : NW;
+    const WaveBinding wb = bind_wave<NW>(wave, ncb);
+    // RELOC_TICK_AUTO: this scan stands down (scan-uniform).  Its workgroups still check out at the end, so that the last
+    // workgroup of the launch can put the counters back
     const bool stand_down = mask.skip_if && *mask.skip_if != 0;
-    if (bound && !stand_down) load_q(my_cb * CB);
+    if (wb.bound && !stand_down) load_q(wb.my_cb * CB);
     double hc = 1.0, hs = 0.0, cos_tol = 0.0;
     if (mask.xyh) {
         cur_heading_q(mask.q, hc, hs);
@@ -542,6 +469,13 @@ __device__ __forceinline__ void db_count_body(
         // the kernel is capped at 104 vector registers)
         hc = uniform_f64(hc); hs = uniform_f64(hs); cos_tol = uniform_f64(cos_tol);
     }
+    // Work distribution.  ticket == NULL: record it = block, + n_blocks, ... (static).  Otherwise the grid is one
+    // resident generation and every workgroup draws records from counters, so that all CUs stay full until the last
+    // record (with a static deal the workgroups of a CU finish one after the other and the CU's tail runs at 3, 2, 1
+    // waves per SIMD).  One counter serves ~88 draws per microsecond (measured: 10 000 draws on one word = 143 us), so
+    // there are 8, one per XCD (HW_REG_XCC_ID) on its own 128-byte line; a workgroup whose counter has run dry moves on to
+    // the next one.  The draw for the next record is in flight while the current one is processed.  The last workgroup to
+    // leave zeroes all words.
     constexpr int TICKET_STRIDE = 32;
     int shard = 0, dry = 0;
     if (ticket) {
@@ -582,16 +516,15 @@ __device__ __forceinline__ void db_count_body(
                 for (int i = tid; i < n; i += 64 * NW) rowkey[i] = 0xFFFFFFFFu;
                 __syncthreads();
             }
-            for (int cb = bound ? my_cb : 0; cb < (bound ? my_cb + 1 : ncb); ++cb) {
-                if (!bound) load_q(cb * CB);
-                // rows dealt to the waves of this column block as contiguous ranges balanced to the single row; 16-row
-                // chunks, the last one partial (see db_scan_body)
-                const int per = n / chunk_step, extra = n % chunk_step;
-                int tc = chunk0 * per + min(chunk0, extra);
-                const int tend = tc + per + (chunk0 < extra ? 1 : 0);
+            // the row walk and load_q are db_emit_body's, written out again: as shared functions they perturb this kernel's code
+            for (int cb = wb.bound ? wb.my_cb : 0; cb < (wb.bound ? wb.my_cb + 1 : ncb); ++cb) {
+                if (!wb.bound) load_q(cb * CB);
+                const int per = n / wb.chunk_step, extra = n % wb.chunk_step;
+                int tc = wb.chunk0 * per + min(wb.chunk0, extra);
+                const int tend = tc + per + (wb.chunk0 < extra ? 1 : 0);
 #pragma nounroll
                 for (; tc < tend; tc += 16)
-                    scan_chunk<NJ, 16, true>(rec, n, tc, min(16, tend - tc), q, (u32)(cb * CB), rowkey, colbest, ncb == 1, lane);
+                    scan_chunk<NJ>(rec, n, tc, min(16, tend - tc), q, (u32)(cb * CB), rowkey, colbest, ncb == 1, lane);
             }
         }
         if (dbl) {   // the other buffer, for the next record
@@ -633,27 +566,37 @@ __device__ __forceinline__ void db_count_body(
     }
 }
 
-// The kernel proper.  NJ is chosen by the host from the CAPACITY of the current-descriptor buffer: entry points
+// The kernels proper.  NJ is chosen by the host from the CAPACITY of the current-descriptor buffer: entry points
 // that know the query count (reloc_db_match_counts*, reloc_match_mutual) scan 128 or 256 columns per wave when
 // that is enough, so their cost follows the query count instead of being flat below 512; the fused tick passes
 // its feature capacity and always runs NJ = 8.  (One kernel branching on the device-side count was measured:
 // it costs the NJ = 8 path 3 %.)
-template <int NJ, bool EMIT, int NW>
-__global__ __launch_bounds__(64 * NW, 16 / NW) RELOC_SCAN_VGPR_ATTR void k_db_scan(
+template <int NJ>
+__global__ __launch_bounds__(256, 4) RELOC_SCAN_VGPR_ATTR void k_db_scan(
     const uint4 *__restrict__ db, const int64_t *__restrict__ off, const int32_t *__restrict__ rec_ids,
     const int32_t *__restrict__ n_ids_p, int n_ids_max, const uint4 *__restrict__ cur,
-    const int32_t *__restrict__ n_cur_p, int n_cur_max, int max_rows, int32_t *__restrict__ counts,
-    int32_t *__restrict__ m_qidx, int32_t *__restrict__ m_tidx, int32_t *__restrict__ m_dist,
-    int32_t *__restrict__ m_n, int emit_stride, ScanMask mask, u32 *ticket, int quota, int n_bounded, int col_words)
+    const int32_t *__restrict__ n_cur_p, int n_cur_max, int max_rows, int32_t *__restrict__ counts, ScanMask mask, u32 *ticket,
+    int quota, int n_bounded, int col_words)
 {
     extern __shared__ u32 lds[];
-    if constexpr (EMIT) RELOC_SMALL_KERNEL_PRIO();          // the emit pass of a few candidates is one of the tick's small kernels
     const int C = n_cur_p ? min(*n_cur_p, n_cur_max) : n_cur_max;
-    if constexpr (EMIT)
-        db_scan_body<NJ, true, NW>(lds, C, db, off, rec_ids, n_ids_p, n_ids_max, cur, max_rows, counts, m_qidx, m_tidx, m_dist, m_n,
-                                   emit_stride, mask, ticket, quota);
-    else
-        db_count_body<NJ, NW>(lds, C, db, off, rec_ids, n_ids_p, n_ids_max, cur, max_rows, counts, mask, ticket, quota, n_bounded, col_words);
+    db_count_body<NJ>(lds, C, db, off, rec_ids, n_ids_p, n_ids_max, cur, max_rows, counts, mask, ticket, quota, n_bounded, col_words);
+}
+
+// One frame's emit pass, NW waves per workgroup (see launch_db_emit).  Plain pointer arguments: a frame struct costs registers here.
+template <int NJ, int NW>
+__global__ __launch_bounds__(64 * NW, 16 / NW) RELOC_SCAN_VGPR_ATTR void k_db_scan_emit(
+    const uint4 *__restrict__ db, const int64_t *__restrict__ off, const int32_t *__restrict__ rec_ids,
+    const int32_t *__restrict__ n_ids_p, int n_ids_max, const uint4 *__restrict__ cur,
+    const int32_t *__restrict__ n_cur_p, int n_cur_max, int max_rows, int32_t *__restrict__ m_qidx,
+    int32_t *__restrict__ m_tidx, int32_t *__restrict__ m_dist, int32_t *__restrict__ m_n, int emit_stride,
+    const float *__restrict__ g_pts3d, const float *__restrict__ g_xy, float *__restrict__ g_obj, float *__restrict__ g_img)
+{
+    extern __shared__ u32 lds[];
+    RELOC_SMALL_KERNEL_PRIO();          // the emit pass of a few candidates is one of the tick's small kernels
+    const int C = n_cur_p ? min(*n_cur_p, n_cur_max) : n_cur_max;
+    db_emit_body<NJ, NW>(lds, C, db, off, rec_ids, n_ids_p, n_ids_max, cur, max_rows, m_qidx, m_tidx, m_dist, m_n, emit_stride, g_pts3d,
+                         g_xy, g_obj, g_img);
 }
 
 // The emit pass (match lists of the candidate records, M:327-336) of up to 8 frames in one launch: blockIdx.y = frame.
@@ -671,18 +614,16 @@ static EmitFrame emit_frame(const reloc_ctx *c)
     return F;
 }
 
-__global__ __launch_bounds__(256, 4) RELOC_SCAN_VGPR_ATTR void k_db_emit_batch(const uint4 *__restrict__ db, const int64_t *__restrict__ off, int n_ids_max,
+__global__ __launch_bounds__(256, 4) RELOC_SCAN_VGPR_ATTR void k_db_scan_emit_batch(const uint4 *__restrict__ db, const int64_t *__restrict__ off, int n_ids_max,
                                                           int n_cur_max, int max_rows, int emit_stride, const float *__restrict__ g_pts3d,
                                                           EmitBatch bt)
 {
     extern __shared__ u32 lds[];
     RELOC_SMALL_KERNEL_PRIO();
     const EmitFrame &F = bt.f[blockIdx.y];
-    ScanMask mask;
-    mask.g_pts3d = g_pts3d; mask.g_xy = F.g_xy; mask.g_obj = F.g_obj; mask.g_img = F.g_img;
     const int C = F.n_cur_p ? min(*F.n_cur_p, n_cur_max) : n_cur_max;
-    db_scan_body<8, true, 4>(lds, C, db, off, F.rec_ids, F.n_ids_p, n_ids_max, F.cur, max_rows, nullptr, F.m_qidx, F.m_tidx, F.m_dist, F.m_n,
-                             emit_stride, mask, nullptr, 0);
+    db_emit_body<8, 4>(lds, C, db, off, F.rec_ids, F.n_ids_p, n_ids_max, F.cur, max_rows, F.m_qidx, F.m_tidx, F.m_dist, F.m_n, emit_stride,
+                       g_pts3d, F.g_xy, F.g_obj, F.g_img);
 }
 
 // Dynamic LDS of a scan workgroup: col_words words of column minima, a row key per teach row, 16 words of counters
@@ -719,8 +660,8 @@ __global__ __launch_bounds__(256, 4) RELOC_SCAN_VGPR_ATTR void k_db_scan_batch(c
     mask.cos_tol = bt.cos_tol;
     mask.skip_if = bt.skip_if[f];
     const int C = bt.n_cur[f] ? min(*bt.n_cur[f], n_cur_max) : n_cur_max;
-    db_count_body<8, 4>(lds, C, db, off, nullptr, nullptr, n_ids, bt.cur[f], max_rows, bt.counts[f], mask, ticket_pool + f * 8 * 32, quota,
-                        n_bounded, col_words, ticket_pool, bt.n, (int)(blockIdx.x / bt.n), (int)((gridDim.x + bt.n - 1 - f) / bt.n));
+    db_count_body<8>(lds, C, db, off, nullptr, nullptr, n_ids, bt.cur[f], max_rows, bt.counts[f], mask, ticket_pool + f * 8 * 32, quota,
+                     n_bounded, col_words, ticket_pool, bt.n, (int)(blockIdx.x / bt.n), (int)((gridDim.x + bt.n - 1 - f) / bt.n));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1055,7 +996,7 @@ __global__ __launch_bounds__(64 * SQ_WAVES) __attribute__((amdgpu_waves_per_eu(8
     }
 }
 
-// Launch plan of a counting scan of the context's database (k_db_scan<NJ, false, 4>, k_db_scan_batch): 4-wave workgroups
+// Launch plan of a counting scan of the context's database (k_db_scan<NJ>, k_db_scan_batch): 4-wave workgroups
 // over column blocks of 64 * nj current descriptors, n_cur_max of them at most.
 struct CountPlan {
     int col_words = 0;            // column minima: one buffer for the capacity; the kernel double-buffers inside it when the
@@ -1138,9 +1079,8 @@ int launch_db_count(reloc_ctx *ctx, const uint8_t *cur, const int32_t *n_cur_dev
     }
     if (grid > n_ids) grid = n_ids;
 #define RELOC_LAUNCH_COUNT(NJ)                                                                                               \
-    hipLaunchKernelGGL((k_db_scan<NJ, false, 4>), dim3(grid), dim3(256), p.lds, ctx->stream, db, ctx->db_off, nullptr, nullptr, n_ids, \
-                       (const uint4 *)cur, n_cur_dev, n_cur_max, max_rows, counts, nullptr, nullptr, nullptr, nullptr, 0, mask, ticket, \
-                       p.quota, p.n_bounded, p.col_words)
+    hipLaunchKernelGGL((k_db_scan<NJ>), dim3(grid), dim3(256), p.lds, ctx->stream, db, ctx->db_off, nullptr, nullptr, n_ids,       \
+                       (const uint4 *)cur, n_cur_dev, n_cur_max, max_rows, counts, mask, ticket, p.quota, p.n_bounded, p.col_words)
     if (nj == 2) RELOC_LAUNCH_COUNT(2); else if (nj == 4) RELOC_LAUNCH_COUNT(4); else RELOC_LAUNCH_COUNT(8);
 #undef RELOC_LAUNCH_COUNT
     HIP_TRY(hipGetLastError());
@@ -1154,7 +1094,7 @@ int launch_db_count(reloc_ctx *ctx, const uint8_t *cur, const int32_t *n_cur_dev
 // no scan runs beside it (latency: local-candidate ticks, single calls), 4 waves in ticks that scan the database.
 // Frame f lists the records rec_ids (n_ids_max capacity, count on the device at n_ids_p when non-NULL; rec_ids == NULL:
 // records 0..n_ids_max-1) of the database db_desc / db_off against its current descriptors (n_cur_max capacity), emit_stride
-// apart; with g_pts3d set every match also leaves its 3-D / 2-D pair (ScanMask).  A batch runs the 8-column kernel.
+// apart; with g_obj set every match also leaves its 3-D / 2-D pair (db_emit_body).  A batch runs the 8-column kernel.
 static int launch_db_emit(reloc_ctx *const *ctxs, int n, const EmitBatch &bt, const uint8_t *db_desc, const int64_t *db_off,
                           int max_rows, const float *g_pts3d, int n_ids_max, int n_cur_max, int emit_stride, bool latency)
 {
@@ -1172,12 +1112,10 @@ static int launch_db_emit(reloc_ctx *const *ctxs, int n, const EmitBatch &bt, co
     const int grid = n_ids_max < c0->num_cu * 16 ? n_ids_max : c0->num_cu * 16;
     if (n == 1) {
         const EmitFrame &F = bt.f[0];
-        ScanMask mask;
-        mask.g_pts3d = g_pts3d; mask.g_xy = F.g_xy; mask.g_obj = F.g_obj; mask.g_img = F.g_img;
 #define RELOC_LAUNCH_EMIT(NJ, NW)                                                                                            \
-    hipLaunchKernelGGL((k_db_scan<NJ, true, NW>), dim3(grid), dim3(64 * NW), lds, c0->stream, (const uint4 *)db_desc, db_off, F.rec_ids, \
-                       F.n_ids_p, n_ids_max, F.cur, F.n_cur_p, n_cur_max, max_rows, nullptr, F.m_qidx, F.m_tidx, F.m_dist, F.m_n,  \
-                       emit_stride, mask, nullptr, 0, 0, ncb * cb)
+    hipLaunchKernelGGL((k_db_scan_emit<NJ, NW>), dim3(grid), dim3(64 * NW), lds, c0->stream, (const uint4 *)db_desc, db_off, F.rec_ids, \
+                       F.n_ids_p, n_ids_max, F.cur, F.n_cur_p, n_cur_max, max_rows, F.m_qidx, F.m_tidx, F.m_dist, F.m_n, emit_stride, \
+                       g_pts3d, F.g_xy, F.g_obj, F.g_img)
         if (latency) {
             if (nj == 2) RELOC_LAUNCH_EMIT(2, 8); else if (nj == 4) RELOC_LAUNCH_EMIT(4, 8); else RELOC_LAUNCH_EMIT(8, 8);
         } else {
@@ -1185,7 +1123,7 @@ static int launch_db_emit(reloc_ctx *const *ctxs, int n, const EmitBatch &bt, co
         }
 #undef RELOC_LAUNCH_EMIT
     } else {
-        hipLaunchKernelGGL(k_db_emit_batch, dim3(grid, n), dim3(256), lds, c0->stream, (const uint4 *)db_desc, db_off, n_ids_max,
+        hipLaunchKernelGGL(k_db_scan_emit_batch, dim3(grid, n), dim3(256), lds, c0->stream, (const uint4 *)db_desc, db_off, n_ids_max,
                            n_cur_max, max_rows, emit_stride, g_pts3d, bt);
     }
     HIP_TRY(hipGetLastError());

@@ -28,7 +28,13 @@ def test_scan_kernels_keep_f32_denormals(tmp_path):
     # one .amdhsa_kernel block per kernel: name, then its descriptor fields up to .end_amdhsa_kernel
     blocks = re.findall(r"^\s*\.amdhsa_kernel (\S+)\n(.*?)^\s*\.end_amdhsa_kernel", text, flags=re.M | re.S)
     scan = [(name, body) for name, body in blocks if re.match(r"_Z\d+k_db_scan", name)]
-    assert len(scan) >= 10, [name for name, _ in blocks]
+    assert len(scan) >= 14, [name for name, _ in blocks]
+    # by name: the count kernels, the six emit instantiations (NJ x waves) and both batch kernels
+    want = [f"_Z9k_db_scanILi{nj}EEv" for nj in (2, 4, 8)]
+    want += [f"_Z14k_db_scan_emitILi{nj}ELi{nw}EEv" for nj in (2, 4, 8) for nw in (4, 8)]
+    want += ["_Z15k_db_scan_batch", "_Z20k_db_scan_emit_batch"]
+    missing = [w for w in want if not any(name.startswith(w) for name, _ in scan)]
+    assert not missing, (missing, [name for name, _ in scan])
     for name, body in scan:
         m = re.search(r"\.amdhsa_float_denorm_mode_32\s+(\d+)", body)
         assert m and m.group(1) == "3", f"{name}: f32 denormals not preserved ({m.group(0) if m else 'no mode field'})"

@@ -11,7 +11,7 @@ doubled value ("upper") are kept; bench.py picks per kernel.
 import csv, glob, json, os, re, sys
 from collections import defaultdict
 
-KERNELS = {"k_db_scan": r"k_db_scan<(8, )?false(, 4)?>", "k_hamming_matrix": r"k_hamming_matrix\(",
+KERNELS = {"k_db_scan": r"k_db_scan<(8|(8, )?false(, 4)?)>", "k_hamming_matrix": r"k_hamming_matrix\(",
            "k_db_scan_rows_q1": r"k_db_scan_rows<4, ", "k_db_scan_rows_q8": r"k_db_scan_rows<8, ", "k_db_scan_rows_q32": r"k_db_scan_rows<16, "}
 NAMES = {"FETCH_SIZE": "fetch_size_raw_bytes", "WRITE_SIZE": "write_size_bytes", "SQ_INSTS_VALU": "valu_wave_insts",
          "GRBM_GUI_ACTIVE": "grbm_gui_active_sum", "SQ_WAVE_CYCLES": "sq_wave_cycles", "SQ_WAIT_ANY": "sq_wait_any",
