@@ -290,6 +290,32 @@ int reloc_remap_u16(reloc_ctx *ctx, const uint16_t *src, int sw, int sh, int sst
 int reloc_convert_maps(reloc_ctx *ctx, const float *mapx, const float *mapy, int w, int h, int nninterpolation,
                        int16_t *xy_out, uint16_t *alpha_out);
 
+/* ---- resize (include/reloc_spec.h, "RESIZE") ------------------------------------------------------- */
+/* cv2.resize on a caller's image (cv2 shim): src is sw x sh with 1 or 3 interleaved channels, out is dw x dh, dense; any sizes
+ * >= 1 within the capacity (RELOC_E_CAPACITY).  inv_scale_x / inv_scale_y are OpenCV's fx / fy of the call without dsize (the
+ * caller computes dw = cvRound(sw * fx) and passes fx on); 0 = dw / sw, the dsize form.  interpolation takes OpenCV's values:
+ * 0 INTER_NEAREST, 1 INTER_LINEAR (at exactly 2x on both axes computed as INTER_AREA, as OpenCV does), 3 INTER_AREA (downscale
+ * on both axes only); everything else is RELOC_E_ARG.  reloc_resize_u16: single channel, nearest only (depth).  sstride in
+ * bytes.  Host pointers; synchronous. */
+int reloc_resize_u8(reloc_ctx *ctx, const uint8_t *src, int sw, int sh, int sstride, int channels, uint8_t *out, int dw, int dh,
+                    double inv_scale_x, double inv_scale_y, int interpolation);
+int reloc_resize_u16(reloc_ctx *ctx, const uint16_t *src, int sw, int sh, int sstride, uint16_t *out, int dw, int dh,
+                     double inv_scale_x, double inv_scale_y);
+/* The downscale stage at the head of the image chain: cv2.resize(gray, (dw, dh), interpolation=INTER_AREA) of every
+ * 3-channel frame, so the chain is frame -> gray + resize -> [rectify] -> [CLAHE] -> ORB.  1 <= dw <= sw, 1 <= dh <= sh
+ * (RELOC_E_ARG) and sw x sh within the context's capacity (RELOC_E_CAPACITY): the context is created for the camera's size.
+ * (0, 0, 0, 0) turns it off (the default of a new context; the launch sequence is then that of a context that never had it).
+ * Applied by the entry points that apply the rectification map.  Every frame passed later must be exactly sw x sh, else
+ * RELOC_E_ARG; from the resize on, the working frame is dw x dh (at least 64 x 64 for ORB): it is the size of the rectification
+ * map, of CLAHE's grid and the pyramid, of the recorder's border gates, of keypoint and result coordinates, and of the camera
+ * (reloc_set_camera takes the intrinsics of the working image: fx' = fx / s, cx' = (cx + 0.5) / s - 0.5 for s = sw / dw).
+ * reloc_record_frame and reloc_tick_accumulate_dev take the depth at sw x sh and resize it with INTER_NEAREST before the
+ * rectification map's nearest read.  Never applied by reloc_orb_detect_compute, reloc_gray_u8, reloc_clahe_u8 or
+ * reloc_remap_*.  Batched calls refuse contexts that are not all off or all on with equal sizes (RELOC_E_STATE).
+ * reloc_get_resize returns zeros when off. */
+int reloc_set_resize(reloc_ctx *ctx, int sw, int sh, int dw, int dh);
+int reloc_get_resize(reloc_ctx *ctx, int32_t *sw, int32_t *sh, int32_t *dw, int32_t *dh);
+
 /* ---- fused tick ----------------------------------------------------------------------------- */
 #define RELOC_TICK_LOCAL   0   /* candidates by VIO distance / heading only                          M:293-302 */
 #define RELOC_TICK_GLOBAL  1   /* whole-database search unconditionally (the benchmarked shape)       G:329-344 */

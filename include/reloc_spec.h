@@ -176,4 +176,33 @@
  *              scale = r == 0 ? 1 : theta_d / r, map = (fx x' scale + cx, fy y' scale + cy) (K without skew). */
 #define RELOC_REMAP_INTER_BITS   5    /* 32 sub-pixel steps per axis, 1024 alphas */
 
+/* RESIZE: cv2.resize(src, dsize, fx, fy, INTER_NEAREST | INTER_LINEAR | INTER_AREA) on 8-bit images (nearest also 16-bit, one
+ * channel), restated from OpenCV 4.x modules/imgproc/src/resize.cpp (the reference: cv2.resize(img, (808, 616),
+ * interpolation=cv2.INTER_AREA) between undistort and CLAHE, datasets/nclt/scripts/run_orbslam3_tuning.py:209-211,
+ * run_all_visual_slam.py:182-183,217-218; not pinned against a cv2 build).  cvRound: half to even; cvFloor,
+ * cvCeil on doubles; ss / ds = source / destination extent of an axis.
+ *   sizes      dsize given: inv_scale = (double)ds / ss; dsize empty: ds = cvRound(ss * f) (saturating, >= 1 or an error),
+ *              inv_scale = f as the caller gave it; scale = 1.0 / inv_scale.
+ *   nearest    sx = min(cvFloor(dx * scale_x), sw - 1), the same in y.
+ *   area_fast  iscale = cvRound(scale); area_fast = |scale_x - iscale_x| < DBL_EPSILON && |scale_y - iscale_y| < DBL_EPSILON.
+ *              INTER_LINEAR with area_fast and iscale (2, 2) is computed as INTER_AREA.
+ *   area       downscale on both axes only (scale >= 1).  area_fast: box = iscale_x x iscale_y source pixels from
+ *              (dx iscale_x, dy iscale_y); wholly inside the source: (a + b + c + d + 2) >> 2 for (2, 2), otherwise
+ *              saturate_cast<uchar>(sum * (1.f / (iscale_x iscale_y))), int sum, one f32 multiply; sticking out (fx / fy sizes
+ *              only, (2, 2) included): saturate_cast<uchar>((float)sum / count) over the pixels inside; starting outside: 0.
+ *              General: per axis and destination index d a tap list in double with f32 alphas: f1 = d scale, f2 = f1 + scale,
+ *              cell = min(scale, ss - f1), s1 = cvCeil(f1), s2 = min(cvFloor(f2), ss - 1), s1 = min(s1, s2); taps
+ *              (s1 - 1, (s1 - f1) / cell) if s1 - f1 > 1e-3, (s, 1 / cell) for s in s1 .. s2 - 1,
+ *              (s2, min(min(f2 - s2, 1), cell) / cell) if f2 - s2 > 1e-3.  f32 without FMA: per y-tap (sy, beta) in order
+ *              buf = 0.f + sum over x-taps in order of S[sy][sx] * alpha; acc = beta * buf for the first, acc += beta * buf
+ *              after; dst = saturate_cast<uchar>(acc).  Channels independent.
+ *   linear     f = (float)((dx + 0.5) * scale_x - 0.5), sx = cvFloor(f), f -= sx; sx < 0: sx = 0, f = 0; sx >= sw - 1:
+ *              sx = sw - 1, f = 0; a0 = cvRound((1.f - f) * 2048), a1 = cvRound(f * 2048);
+ *              H = S[sx] * a0 + S[min(sx + 1, sw - 1)] * a1.  Vertically the same f and sy but not zeroed at the edges, rows
+ *              clip(sy, 0, sh - 1) and clip(sy + 1, 0, sh - 1), weights b0, b1;
+ *              dst = (((b0 * (H0 >> 4)) >> 16) + ((b1 * (H1 >> 4)) >> 16) + 2) >> 2.
+ *   The library builds the per-axis tables on the host in exactly these words; the kernels do integer or f32 arithmetic on
+ *   table entries only.  Everything else (other interpolations, dtypes, INTER_AREA upscaling) is refused. */
+#define RELOC_RESIZE_LINEAR_BITS 11   /* INTER_RESIZE_COEF_BITS: the two weights of an axis sum to 2048 */
+
 #endif /* RELOC_SPEC_H */

@@ -70,6 +70,10 @@ SIGNATURES = {
     "reloc_remap_u8": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, C.c_int, C.c_int, C.c_int, C.c_int, P]),
     "reloc_remap_u16": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, P, C.c_int, C.c_int, C.c_int, P]),
     "reloc_convert_maps": (C.c_int, [c_ctx, P, P, C.c_int, C.c_int, C.c_int, P, P]),
+    "reloc_resize_u8": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_int, C.c_int, f64, f64, C.c_int]),
+    "reloc_resize_u16": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, P, C.c_int, C.c_int, f64, f64]),
+    "reloc_set_resize": (C.c_int, [c_ctx, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "reloc_get_resize": (C.c_int, [c_ctx, P, P, P, P]),
     "reloc_tick_debug": (C.c_int, [c_ctx, P, P, P, P, P, P, P]),
     "reloc_tick": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, P, C.c_int, u64, P, P, P, P, P, P]),
     "reloc_get_params": (C.c_int, [c_ctx, P]),

@@ -30,7 +30,11 @@
 //                                        256 steered tests -> 4 ballots = 32 descriptor bytes
 // The per-frame HBM traffic is about 4 MB at 640x480; the stage is launch/latency-bound, not
 // bandwidth-bound.
+#include <float.h>
 #include <math.h>
+
+#include <algorithm>
+#include <vector>
 
 #include "../../include/reloc_orb_pattern.h"
 #include "reloc_internal.h"
@@ -1601,6 +1605,398 @@ int rectify_depth(reloc_ctx *ctx, const uint16_t *depth_dev, int w, int h, const
     return RELOC_OK;
 }
 
+// ---- resize: cv2.resize (include/reloc_spec.h, "RESIZE") ---------------------------------------------------
+// OpenCV's 8-bit resize.  The per-axis tables (offsets, coefficients, tap lists) are built on the host exactly as the spec
+// states them (resize_plan); the kernels do integer or f32 arithmetic on table entries only, so host and device cannot
+// disagree on a floor.
+//   k_resize_area<CH, GRAY, KIND>  INTER_AREA, downscale: 4 adjacent output pixels per lane.  KIND: exact 2x2 boxes, integer
+//                                  iscale_x x iscale_y boxes (partial boxes at the right / bottom edge included), or per-axis
+//                                  tap lists (first tap, count, f32 alphas).  GRAY (CH = 3): gray_fixed of every source pixel
+//                                  before the sum, one dword store -- the stage in front of ORB.
+//   k_resize_linear<CH>            INTER_LINEAR, 11 coefficient bits, one output pixel per lane
+//   k_resize_nearest<T, CH>        INTER_NEAREST, one output pixel per lane; T = uint16_t for the depth image
+// All are frame-batched (blockIdx.y = frame) with per-frame table pointers; a single frame is a batch of one.
+enum { RESIZE_AREA_2X2 = 0, RESIZE_AREA_INT = 1, RESIZE_AREA_TAB = 2, RESIZE_LINEAR = 3, RESIZE_NEAREST = 4 };
+struct ResizeFrames {
+    const uint8_t *src[RELOC_BATCH_MAX]; const int32_t *tab[RELOC_BATCH_MAX]; uint8_t *dst[RELOC_BATCH_MAX];
+};
+struct ResizeGeom {
+    int sw, sh, sstride;   // source size, row stride in bytes (k_resize_nearest: in elements of T)
+    int dw, dh, dstride;   // destination size and row stride, likewise
+    int isx, isy;          // integer kinds: the box
+    float inv_area;        // 1.f / (isx * isy)
+    int aligned;           // source rows start on dwords (base and stride multiples of 4; integer kind: isx % 4 == 0 as well)
+};
+
+// saturate_cast<uchar>(float): cvRound (half to even), then the clamp
+__device__ __forceinline__ int resize_sat_u8(float v)
+{
+    const int r = (int)rintf(v);
+    return r < 0 ? 0 : (r > 255 ? 255 : r);
+}
+
+// byte b of a row segment held as dwords (b is a constant after unrolling)
+#define RESIZE_BYTE(w, b) (int)(((w)[(b) >> 2] >> (8 * ((b) & 3))) & 255u)
+
+// NW dwords of a source row from p, of which `valid` bytes belong to the row; the rest reads as 0.  aligned: p is a
+// multiple of 4 and so is the row stride, so a dword that holds a valid byte ends within the row's stride
+template <int NW>
+__device__ __forceinline__ void resize_row_words(const uint8_t *__restrict__ p, int valid, bool aligned, u32 (&w)[NW])
+{
+    if (aligned) {
+#pragma unroll
+        for (int i = 0; i < NW; ++i) w[i] = 4 * i < valid ? reinterpret_cast<const u32 *>(p)[i] : 0u;
+    } else {
+#pragma unroll
+        for (int i = 0; i < NW; ++i) {
+            u32 v = 0;
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                if (4 * i + b < valid) v |= (u32)p[4 * i + b] << (8 * b);
+            w[i] = v;
+        }
+    }
+}
+
+// pixel j of a row segment held as dwords
+template <int CH, bool GRAY, int NW>
+__device__ __forceinline__ void resize_word_px(const u32 (&w)[NW], int j, int flags, int (&v)[GRAY ? 1 : CH])
+{
+    if (GRAY) {
+        const int c0 = RESIZE_BYTE(w, 3 * j), c1 = RESIZE_BYTE(w, 3 * j + 1), c2 = RESIZE_BYTE(w, 3 * j + 2);
+        v[0] = gray_fixed((flags & 1) ? c2 : c0, c1, (flags & 1) ? c0 : c2, flags);
+    } else {
+#pragma unroll
+        for (int c = 0; c < CH; ++c) v[c] = RESIZE_BYTE(w, CH * j + c);
+    }
+}
+
+// the pixel at p, byte by byte
+template <int CH, bool GRAY>
+__device__ __forceinline__ void resize_px(const uint8_t *__restrict__ p, int flags, int (&v)[GRAY ? 1 : CH])
+{
+    if (GRAY) {
+        const int c0 = p[0], c1 = p[1], c2 = p[2];
+        v[0] = gray_fixed((flags & 1) ? c2 : c0, c1, (flags & 1) ? c0 : c2, flags);
+    } else {
+#pragma unroll
+        for (int c = 0; c < CH; ++c) v[c] = p[c];
+    }
+}
+
+template <int CH, bool GRAY, int KIND>
+__global__ __launch_bounds__(256) void k_resize_area(ResizeFrames F, ResizeGeom g, int flags)
+{
+    constexpr int OC = GRAY ? 1 : CH;       // output channels
+    const int quads = (g.dw + 3) >> 2;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= quads * g.dh) return;
+    const int y = q / quads, x4 = 4 * (q - y * quads);
+    const uint8_t *src = F.src[blockIdx.y];
+    int out[4][OC];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int c = 0; c < OC; ++c) out[k][c] = 0;
+    if (KIND == RESIZE_AREA_2X2) {
+        // every box lies inside the source (2 dw <= sw, 2 dh <= sh): (a + b + c + d + 2) >> 2.  Eight source pixels per row
+        constexpr int NW = 2 * CH;
+        const int valid = (g.sw - 2 * x4) * CH;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            u32 w[NW];
+            resize_row_words<NW>(src + (size_t)(2 * y + r) * g.sstride + (size_t)2 * x4 * CH, valid, g.aligned, w);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                int v[OC];
+                resize_word_px<CH, GRAY, NW>(w, j, flags, v);
+#pragma unroll
+                for (int c = 0; c < OC; ++c) out[j >> 1][c] += v[c];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int c = 0; c < OC; ++c) out[k][c] = (out[k][c] + 2) >> 2;
+    } else if (KIND == RESIZE_AREA_INT) {
+        const int y0 = y * g.isy, ny = max(0, min(g.isy, g.sh - y0));
+        const bool is22 = g.isx == 2 && g.isy == 2;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int x0 = (x4 + k) * g.isx, nx = x4 + k < g.dw ? max(0, min(g.isx, g.sw - x0)) : 0;
+            const int count = nx * ny;
+            if (count == 0) continue;           // a box that starts outside the source: 0
+            int sum[OC];
+#pragma unroll
+            for (int c = 0; c < OC; ++c) sum[c] = 0;
+            for (int r = 0; r < ny; ++r) {
+                const uint8_t *row = src + (size_t)(y0 + r) * g.sstride + (size_t)x0 * CH;
+                if (g.aligned && nx == g.isx) {     // isx % 4 == 0: groups of four pixels = CH dwords
+                    for (int j = 0; j < nx; j += 4) {
+                        u32 w[CH];
+#pragma unroll
+                        for (int i = 0; i < CH; ++i) w[i] = reinterpret_cast<const u32 *>(row + (size_t)j * CH)[i];
+#pragma unroll
+                        for (int p = 0; p < 4; ++p) {
+                            int v[OC];
+                            resize_word_px<CH, GRAY, CH>(w, p, flags, v);
+#pragma unroll
+                            for (int c = 0; c < OC; ++c) sum[c] += v[c];
+                        }
+                    }
+                } else {
+                    for (int j = 0; j < nx; ++j) {
+                        int v[OC];
+                        resize_px<CH, GRAY>(row + (size_t)j * CH, flags, v);
+#pragma unroll
+                        for (int c = 0; c < OC; ++c) sum[c] += v[c];
+                    }
+                }
+            }
+            const bool inside = nx == g.isx && ny == g.isy;
+#pragma unroll
+            for (int c = 0; c < OC; ++c) {
+                if (inside) out[k][c] = is22 ? (sum[c] + 2) >> 2 : resize_sat_u8(__fmul_rn((float)sum[c], g.inv_area));
+                else        out[k][c] = resize_sat_u8(__fdiv_rn((float)sum[c], (float)count));
+            }
+        }
+    } else {
+        // tap lists: [x first dw][x count dw][x alpha offset dw][y first dh][y count dh][y alpha offset dh][f32 alphas]
+        const int32_t *tab = F.tab[blockIdx.y];
+        const float *al = reinterpret_cast<const float *>(tab);
+        const int32_t *ty = tab + 3 * g.dw;
+        const int yf = ty[y], yc = ty[g.dh + y], ya = ty[2 * g.dh + y];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (x4 + k >= g.dw) continue;
+            const int xf = tab[x4 + k], xc = tab[g.dw + x4 + k], xa = tab[2 * g.dw + x4 + k];
+            float acc[OC];
+#pragma unroll
+            for (int c = 0; c < OC; ++c) acc[c] = 0.f;
+            for (int t = 0; t < yc; ++t) {
+                const float beta = al[ya + t];
+                const uint8_t *row = src + (size_t)(yf + t) * g.sstride + (size_t)xf * CH;
+                float buf[OC];
+#pragma unroll
+                for (int c = 0; c < OC; ++c) buf[c] = 0.f;
+                for (int u = 0; u < xc; ++u) {
+                    const float a = al[xa + u];
+                    int v[OC];
+                    resize_px<CH, GRAY>(row + (size_t)u * CH, flags, v);
+#pragma unroll
+                    for (int c = 0; c < OC; ++c) buf[c] = __fadd_rn(buf[c], __fmul_rn((float)v[c], a));
+                }
+#pragma unroll
+                for (int c = 0; c < OC; ++c) acc[c] = t == 0 ? __fmul_rn(beta, buf[c]) : __fadd_rn(acc[c], __fmul_rn(beta, buf[c]));
+            }
+#pragma unroll
+            for (int c = 0; c < OC; ++c) out[k][c] = resize_sat_u8(acc[c]);
+        }
+    }
+    uint8_t *dst = F.dst[blockIdx.y] + (size_t)y * g.dstride + OC * x4;
+    if (OC == 1 && (g.dstride & 3) == 0) {
+        // the row holds round4(dw) bytes: dstride >= dw and a multiple of 4
+        *reinterpret_cast<u32 *>(dst) = (u32)out[0][0] | (u32)out[1][0] << 8 | (u32)out[2][0] << 16 | (u32)out[3][0] << 24;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (x4 + k < g.dw) {
+#pragma unroll
+                for (int c = 0; c < OC; ++c) dst[OC * k + c] = (uint8_t)out[k][c];
+            }
+    }
+}
+
+// table: [x offset dw][a0 | a1 << 16 dw][row 0 dh][row 1 dh][b0 | b1 << 16 dh], the rows already clipped to the source
+template <int CH>
+__global__ __launch_bounds__(256) void k_resize_linear(ResizeFrames F, ResizeGeom g)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.z;
+    if (x >= g.dw) return;
+    const int32_t *tab = F.tab[blockIdx.y], *ty = tab + 2 * g.dw;
+    const int sx = tab[x], sx1 = min(sx + 1, g.sw - 1);
+    const u32 ca = (u32)tab[g.dw + x], cb = (u32)ty[2 * g.dh + y];
+    const int a0 = ca & 0xFFFF, a1 = ca >> 16, b0 = cb & 0xFFFF, b1 = cb >> 16;
+    const uint8_t *r0 = F.src[blockIdx.y] + (size_t)ty[y] * g.sstride, *r1 = F.src[blockIdx.y] + (size_t)ty[g.dh + y] * g.sstride;
+    uint8_t *d = F.dst[blockIdx.y] + (size_t)y * g.dstride + CH * x;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        const int h0 = r0[CH * sx + c] * a0 + r0[CH * sx1 + c] * a1, h1 = r1[CH * sx + c] * a0 + r1[CH * sx1 + c] * a1;
+        d[c] = (uint8_t)((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2);
+    }
+}
+
+// table: [x offset dw][y offset dh]; strides of src and dst in elements of T
+template <typename T, int CH>
+__global__ __launch_bounds__(256) void k_resize_nearest(ResizeFrames F, ResizeGeom g)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.z;
+    if (x >= g.dw) return;
+    const int32_t *tab = F.tab[blockIdx.y];
+    const T *s = reinterpret_cast<const T *>(F.src[blockIdx.y]) + (size_t)tab[g.dw + y] * g.sstride + CH * tab[x];
+    T *d = reinterpret_cast<T *>(F.dst[blockIdx.y]) + (size_t)y * g.dstride + CH * x;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) d[c] = s[c];
+}
+
+// What one resize does: the kernel kind, the integer box and the table words (host).  Built from the spec's rules in double
+// with alphas stored as f32; every source index in a table lies inside the source.
+struct ResizePlan {
+    int kind = -1, isx = 1, isy = 1;
+    std::vector<int32_t> tab;
+};
+
+static inline int32_t resize_f32_bits(float v) { int32_t b; memcpy(&b, &v, 4); return b; }
+static inline int resize_clampi(double v, int lo, int hi) { return v < (double)lo ? lo : (v > (double)hi ? hi : (int)v); }
+
+// INTER_AREA tap list of one axis, appended to `first`, `count`, `alpha` (offsets into alpha are per axis)
+static void resize_area_axis(int ss, int ds, double scale, std::vector<int32_t> &first, std::vector<int32_t> &count,
+                             std::vector<int32_t> &aoff, std::vector<float> &alpha)
+{
+    for (int d = 0; d < ds; ++d) {
+        const double f1 = d * scale, f2 = f1 + scale, cell = std::min(scale, ss - f1);
+        int s1 = resize_clampi(ceil(f1), 0, ss - 1);
+        const int s2 = std::min(resize_clampi(floor(f2), 0, ss), ss - 1);
+        s1 = std::min(s1, s2);
+        const size_t a0 = alpha.size();
+        int f = s1;
+        if (s1 - f1 > 1e-3 && s1 >= 1) { f = s1 - 1; alpha.push_back((float)((s1 - f1) / cell)); }
+        for (int s = s1; s < s2; ++s) alpha.push_back((float)(1.0 / cell));
+        if (f2 - s2 > 1e-3) alpha.push_back((float)(std::min(std::min(f2 - s2, 1.0), cell) / cell));
+        first.push_back(f);
+        count.push_back((int32_t)(alpha.size() - a0));
+        aoff.push_back((int32_t)a0);
+    }
+}
+
+// INTER_LINEAR of one axis: source index (not clipped) and the 11-bit weights of it and of its successor
+static void resize_linear_axis(int ss, int ds, double scale, bool zero_at_edges, std::vector<int32_t> &ofs, std::vector<int32_t> &coef)
+{
+    for (int d = 0; d < ds; ++d) {
+        float f = (float)((d + 0.5) * scale - 0.5);
+        const float fl = floorf(f);
+        int s = resize_clampi((double)fl, -2, ss);      // an index outside [-1, ss - 1] behaves like the nearest edge
+        f -= fl;
+        if (zero_at_edges) {
+            if (s < 0) { s = 0; f = 0.f; }
+            if (s >= ss - 1) { s = ss - 1; f = 0.f; }
+        }
+        const int c0 = (int)lrintf((1.f - f) * 2048.f), c1 = (int)lrintf(f * 2048.f);
+        ofs.push_back(s);
+        coef.push_back((int32_t)((uint32_t)(c0 & 0xFFFF) | (uint32_t)(c1 & 0xFFFF) << 16));
+    }
+}
+
+static int resize_plan(int sw, int sh, int dw, int dh, double inv_x, double inv_y, int interpolation, ResizePlan &P)
+{
+    if (inv_x == 0.0) inv_x = (double)dw / sw;
+    if (inv_y == 0.0) inv_y = (double)dh / sh;
+    if (!(inv_x > 0.0 && inv_y > 0.0 && inv_x - inv_x == 0.0 && inv_y - inv_y == 0.0)) {
+        reloc_set_error("bad argument: resize: the scale factors must be positive and finite");
+        return RELOC_E_ARG;
+    }
+    const double scx = 1.0 / inv_x, scy = 1.0 / inv_y;
+    std::vector<int32_t> &T = P.tab;
+    T.clear();
+    if (interpolation == 0) {
+        P.kind = RESIZE_NEAREST;
+        for (int d = 0; d < dw; ++d) T.push_back(resize_clampi(floor(d * scx), 0, sw - 1));
+        for (int d = 0; d < dh; ++d) T.push_back(resize_clampi(floor(d * scy), 0, sh - 1));
+        return RELOC_OK;
+    }
+    const int isx = resize_clampi(rint(scx), 0, 1 << 30), isy = resize_clampi(rint(scy), 0, 1 << 30);
+    const bool area_fast = fabs(scx - isx) < DBL_EPSILON && fabs(scy - isy) < DBL_EPSILON;
+    if (interpolation == 1 && area_fast && isx == 2 && isy == 2) interpolation = 3;
+    if (interpolation == 3) {
+        if (!(scx >= 1.0 && scy >= 1.0)) {
+            reloc_set_error("bad argument: resize: INTER_AREA is implemented for downscaling on both axes only");
+            return RELOC_E_ARG;
+        }
+        if (scx > 2.0 * sw || scy > 2.0 * sh) {     // no destination size rounds to >= 1 from such a factor
+            reloc_set_error("bad argument: resize: INTER_AREA: a scale factor shrinks the source below half a pixel");
+            return RELOC_E_ARG;
+        }
+        if (area_fast) {
+            P.isx = isx; P.isy = isy;
+            P.kind = isx == 2 && isy == 2 && 2 * (int64_t)dw <= sw && 2 * (int64_t)dh <= sh ? RESIZE_AREA_2X2 : RESIZE_AREA_INT;
+            return RELOC_OK;
+        }
+        if ((dw - 1) * scx >= sw || (dh - 1) * scy >= sh) {
+            reloc_set_error("bad argument: resize: INTER_AREA: the destination reaches beyond the scaled source");
+            return RELOC_E_ARG;
+        }
+        P.kind = RESIZE_AREA_TAB;
+        std::vector<int32_t> xf, xc, xa, yf, yc, ya;
+        std::vector<float> ax, ay;
+        resize_area_axis(sw, dw, scx, xf, xc, xa, ax);
+        resize_area_axis(sh, dh, scy, yf, yc, ya, ay);
+        const int32_t base_x = 3 * (dw + dh), base_y = base_x + (int32_t)ax.size();
+        for (int d = 0; d < dw; ++d) { xa[d] += base_x; if (xf[d] + xc[d] > sw) xc[d] = sw - xf[d]; }
+        for (int d = 0; d < dh; ++d) { ya[d] += base_y; if (yf[d] + yc[d] > sh) yc[d] = sh - yf[d]; }
+        for (auto *v : {&xf, &xc, &xa, &yf, &yc, &ya}) T.insert(T.end(), v->begin(), v->end());
+        for (float a : ax) T.push_back(resize_f32_bits(a));
+        for (float a : ay) T.push_back(resize_f32_bits(a));
+        return RELOC_OK;
+    }
+    if (interpolation == 1) {
+        P.kind = RESIZE_LINEAR;
+        std::vector<int32_t> xo, xc, yo, yc;
+        resize_linear_axis(sw, dw, scx, true, xo, xc);
+        resize_linear_axis(sh, dh, scy, false, yo, yc);
+        T.insert(T.end(), xo.begin(), xo.end());
+        T.insert(T.end(), xc.begin(), xc.end());
+        for (int d = 0; d < dh; ++d) T.push_back(std::min(std::max(yo[d], 0), sh - 1));
+        for (int d = 0; d < dh; ++d) T.push_back(std::min(std::max(yo[d] + 1, 0), sh - 1));
+        T.insert(T.end(), yc.begin(), yc.end());
+        return RELOC_OK;
+    }
+    reloc_set_error("bad argument: resize: only INTER_NEAREST (0), INTER_LINEAR (1) and INTER_AREA (3) are implemented");
+    return RELOC_E_ARG;
+}
+
+// one resize launch for n frames of equal geometry on stream st.  elem: bytes per channel value (2 = the 16-bit nearest);
+// gray: 3-channel source, gray output (the stage, area kinds only)
+static int resize_launch(hipStream_t st, const ResizeFrames &F, int n, const ResizePlan &P, int sw, int sh, int sstride, int dw,
+                         int dh, int dstride, int channels, int elem, bool gray, int flags)
+{
+    ResizeGeom g = {sw, sh, sstride, dw, dh, dstride, P.isx, P.isy, 1.f / (float)(P.isx * P.isy), 0};
+    if (P.kind == RESIZE_NEAREST) {
+        auto kern = elem == 2 ? k_resize_nearest<uint16_t, 1> : channels == 1 ? k_resize_nearest<uint8_t, 1> : k_resize_nearest<uint8_t, 3>;
+        hipLaunchKernelGGL(kern, dim3((dw + 255) / 256, n, dh), dim3(256), 0, st, F, g);
+    } else if (P.kind == RESIZE_LINEAR) {
+        hipLaunchKernelGGL(channels == 1 ? k_resize_linear<1> : k_resize_linear<3>, dim3((dw + 255) / 256, n, dh), dim3(256), 0, st, F, g);
+    } else {
+        bool aligned = sstride % 4 == 0 && (P.kind != RESIZE_AREA_INT || P.isx % 4 == 0);
+        for (int f = 0; f < n; ++f) aligned = aligned && ((uintptr_t)F.src[f]) % 4 == 0;
+        g.aligned = aligned;
+        const dim3 grid((((dw + 3) / 4) * dh + 255) / 256, n);
+#define RESIZE_AREA_KERN(KIND) (channels == 1 ? k_resize_area<1, false, KIND> : gray ? k_resize_area<3, true, KIND> : k_resize_area<3, false, KIND>)
+        auto kern = P.kind == RESIZE_AREA_2X2 ? RESIZE_AREA_KERN(RESIZE_AREA_2X2)
+                    : P.kind == RESIZE_AREA_INT ? RESIZE_AREA_KERN(RESIZE_AREA_INT) : RESIZE_AREA_KERN(RESIZE_AREA_TAB);
+#undef RESIZE_AREA_KERN
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, F, g, flags);
+    }
+    HIP_TRY(hipGetLastError());
+    return RELOC_OK;
+}
+
+// depth (uint16 millimetres, dense rows of w) of a context with the downscale stage on, INTER_NEAREST to the working size,
+// into the context's depth plane (reloc_record_frame, reloc_tick_accumulate_dev)
+int resize_depth(reloc_ctx *ctx, const uint16_t *depth_dev, int w, int h, const uint16_t **out)
+{
+    if (w != ctx->rsz_sw || h != ctx->rsz_sh) {
+        reloc_set_error("frame %dx%d differs from the source size %dx%d of the downscale stage (reloc_set_resize)", w, h, ctx->rsz_sw, ctx->rsz_sh);
+        return RELOC_E_ARG;
+    }
+    ResizeFrames F = {};
+    F.src[0] = (const uint8_t *)depth_dev; F.tab[0] = ctx->rsz_ntab; F.dst[0] = (uint8_t *)ctx->rsz_depth;
+    ResizePlan P;
+    P.kind = RESIZE_NEAREST;
+    if (int rc = resize_launch(ctx->stream, F, 1, P, w, h, w, ctx->rsz_dw, ctx->rsz_dh, ctx->rsz_dw, 1, 2, false, 0)) return rc;
+    *out = ctx->rsz_depth;
+    return RELOC_OK;
+}
+
 // what the five ORB kernels read and write of a context, for the source frame src
 static OrbFrame orb_frame(const reloc_ctx *c, const uint8_t *src)
 {
@@ -1613,7 +2009,9 @@ static OrbFrame orb_frame(const reloc_ctx *c, const uint8_t *src)
     return F;
 }
 
-// Five launches (plus one of the rectification and two of CLAHE): the frames are of equal geometry.  3-channel frames of
+// Five launches (plus one of the downscale stage, one of the rectification and two of CLAHE): the frames are of equal
+// geometry.  3-channel frames of contexts with the downscale stage on (reloc_set_resize) are converted to gray and resized
+// (INTER_AREA) first, and everything downstream sees the working frame dw x dh; those of
 // contexts with a rectification map (reloc_set_rectify_map) are converted to gray and remapped first, those of contexts
 // with CLAHE on (reloc_set_clahe) equalised next; the pyramid then reads the last plane written.  The pyramid runs 512-thread workgroups
 // for latency, 256 where it shares the chip with whole-database scans.
@@ -1622,6 +2020,24 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
 {
     if (n < 1 || n > RELOC_BATCH_MAX) { reloc_set_error("orb: 1..%d frames", RELOC_BATCH_MAX); return RELOC_E_ARG; }
     reloc_ctx *c0 = ctxs[0];
+    const bool frame = channels == 3;      // the image stages serve 3-channel frames only, never a caller's gray plane
+    const bool resize = frame && c0->rsz_dw > 0;
+    const int sw = w, sh = h;               // the frame as handed in; w x h becomes the working frame
+    for (int f = 0; f < n; ++f) {
+        const reloc_ctx *c = ctxs[f];
+        if (c->rsz_sw != c0->rsz_sw || c->rsz_sh != c0->rsz_sh || c->rsz_dw != c0->rsz_dw || c->rsz_dh != c0->rsz_dh) {
+            reloc_set_error("orb batch: contexts with and without the downscale stage, or with unequal sizes (reloc_set_resize)");
+            return RELOC_E_STATE;
+        }
+    }
+    if (resize) {
+        if (w != c0->rsz_sw || h != c0->rsz_sh) {
+            reloc_set_error("frame %dx%d differs from the source size %dx%d of the downscale stage (reloc_set_resize)", w, h, c0->rsz_sw, c0->rsz_sh);
+            return RELOC_E_ARG;
+        }
+        w = c0->rsz_dw; h = c0->rsz_dh;
+        if (w < 64 || h < 64) { reloc_set_error("bad argument: the working frame %dx%d of the downscale stage is below 64x64", w, h); return RELOC_E_ARG; }
+    }
     for (int f = 0; f < n; ++f) {
         reloc_ctx *c = ctxs[f];
         if (int rc = orb_prepare(c, w, h, nfeatures)) return rc;
@@ -1639,7 +2055,6 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
             return RELOC_E_STATE;
         }
     }
-    const bool frame = channels == 3;      // the image stages serve 3-channel frames only, never a caller's gray plane
     if (frame && c0->rect_w > 0 && (w != c0->rect_w || h != c0->rect_h)) {
         reloc_set_error("frame %dx%d differs from the rectification map %dx%d (reloc_set_rectify_map)", w, h, c0->rect_w, c0->rect_h);
         return RELOC_E_ARG;
@@ -1648,7 +2063,19 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
     const int flags = gray_flags(c0, order);
     hipStream_t st = c0->stream;
     reloc_prof_begin(c0, RELOC_PROF_ORB);
-    const uint8_t *rplanes[RELOC_BATCH_MAX], *planes[RELOC_BATCH_MAX];
+    const uint8_t *zplanes[RELOC_BATCH_MAX], *rplanes[RELOC_BATCH_MAX], *planes[RELOC_BATCH_MAX];
+    if (resize) {
+        ResizeFrames F = {};
+        for (int f = 0; f < n; ++f) { F.src[f] = srcs[f]; F.tab[f] = ctxs[f]->rsz_tab; F.dst[f] = ctxs[f]->rsz_plane; zplanes[f] = F.dst[f]; }
+        ResizePlan P;
+        P.kind = c0->rsz_kind; P.isx = c0->rsz_isx; P.isy = c0->rsz_isy;
+        const int cs = clahe_stride(w);
+        if (int rc = resize_launch(st, F, n, P, sw, sh, stride, w, h, cs, 3, 1, true, flags)) {
+            reloc_prof_end(c0, RELOC_PROF_ORB);
+            return rc;
+        }
+        srcs = zplanes; stride = cs; channels = 1;
+    }
     if (frame && c0->rect_w > 0) {
         RemapFrames F = {};
         for (int f = 0; f < n; ++f) {
@@ -1657,7 +2084,7 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
         }
         const int cs = clahe_stride(w);
         const RemapGeom g = {w, h, stride, w, h, cs, 0};
-        if (int rc = remap_launch(st, F, n, g, 3, true, flags)) {
+        if (int rc = remap_launch(st, F, n, g, channels, channels == 3, flags)) {
             reloc_prof_end(c0, RELOC_PROF_ORB);
             return rc;
         }
@@ -1953,5 +2380,94 @@ RELOC_API int reloc_convert_maps(reloc_ctx *ctx, const float *mapx, const float 
     HIP_TRY(hipMemcpyAsync(xy_out, dxy, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(alpha_out, dal, (size_t)n * 2, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return RELOC_OK;
+}
+
+// ---- resize entry points -------------------------------------------------------------------------------------
+// source, table and destination of a host-pointer resize on the device: src into frame_img (dense rows), table into scratch 0
+static int resize_host(reloc_ctx *ctx, const void *src, int sw, int sh, int sstride, int channels, int elem, void *out, int dw, int dh,
+                       double inv_x, double inv_y, int interpolation)
+{
+    if (sw > ctx->max_w || sh > ctx->max_h || dw > ctx->max_w || dh > ctx->max_h) {
+        reloc_set_error("image exceeds ctx capacity");
+        return RELOC_E_CAPACITY;
+    }
+    ResizePlan P;
+    if (int rc = resize_plan(sw, sh, dw, dh, inv_x, inv_y, interpolation, P)) return rc;
+    const int row_bytes = sw * channels * elem;
+    const int64_t out_bytes = (int64_t)dw * dh * channels * elem;
+    void *dtab, *dout;
+    int rc;
+    if ((rc = reloc_scratch(ctx, 0, (int64_t)P.tab.size() * 4 + 4, &dtab))) return rc;
+    if ((rc = reloc_scratch(ctx, 1, out_bytes, &dout))) return rc;
+    HIP_TRY(hipMemcpy2DAsync(ctx->frame_img, row_bytes, src, sstride, row_bytes, sh, hipMemcpyHostToDevice, ctx->stream));
+    // the table is pageable host memory that dies with this call: the copy below is complete when the call returns
+    if (!P.tab.empty()) HIP_TRY(hipMemcpyAsync(dtab, P.tab.data(), P.tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    ResizeFrames F = {};
+    F.src[0] = ctx->frame_img; F.tab[0] = (const int32_t *)dtab; F.dst[0] = (uint8_t *)dout;
+    const bool by_elem = P.kind == RESIZE_NEAREST;      // k_resize_nearest counts strides in elements
+    if ((rc = resize_launch(ctx->stream, F, 1, P, sw, sh, by_elem ? sw * channels : row_bytes, dw, dh, dw * channels, channels, elem,
+                            false, 0)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(out, dout, (size_t)out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_resize_u8(reloc_ctx *ctx, const uint8_t *src, int sw, int sh, int sstride, int channels, uint8_t *out, int dw,
+                              int dh, double inv_scale_x, double inv_scale_y, int interpolation)
+{
+    ARG_CHECK_CTX(ctx, src && out && sw >= 1 && sh >= 1 && dw >= 1 && dh >= 1 && (channels == 1 || channels == 3) &&
+                  sstride >= channels * sw, "reloc_resize_u8");
+    return resize_host(ctx, src, sw, sh, sstride, channels, 1, out, dw, dh, inv_scale_x, inv_scale_y, interpolation);
+}
+
+RELOC_API int reloc_resize_u16(reloc_ctx *ctx, const uint16_t *src, int sw, int sh, int sstride, uint16_t *out, int dw, int dh,
+                               double inv_scale_x, double inv_scale_y)
+{
+    ARG_CHECK_CTX(ctx, src && out && sw >= 1 && sh >= 1 && dw >= 1 && dh >= 1 && sstride >= 2 * sw, "reloc_resize_u16");
+    return resize_host(ctx, src, sw, sh, sstride, 1, 2, out, dw, dh, inv_scale_x, inv_scale_y, 0);
+}
+
+RELOC_API int reloc_set_resize(reloc_ctx *ctx, int sw, int sh, int dw, int dh)
+{
+    ARG_CHECK_CTX(ctx, true, "ctx is NULL");
+    if (sw == 0 && sh == 0 && dw == 0 && dh == 0) {
+        ctx->rsz_sw = ctx->rsz_sh = ctx->rsz_dw = ctx->rsz_dh = 0;
+        return RELOC_OK;
+    }
+    ARG_CHECK(dw >= 1 && dh >= 1 && dw <= sw && dh <= sh,
+              "reloc_set_resize: sizes must be all 0 (off) or 1 <= dw <= sw and 1 <= dh <= sh");
+    if (sw > ctx->max_w || sh > ctx->max_h) { reloc_set_error("resize source exceeds ctx capacity"); return RELOC_E_CAPACITY; }
+    ResizePlan area, nearest;
+    if (int rc = resize_plan(sw, sh, dw, dh, 0.0, 0.0, 3, area)) return rc;
+    if (int rc = resize_plan(sw, sh, dw, dh, 0.0, 0.0, 0, nearest)) return rc;
+    // tables of the largest frame: 3 words and at most scale + 2 alphas per destination index and axis, one offset per index
+    // and axis for the depth; then the gray plane and the depth plane, in one allocation (rsz_tab owns it)
+    const size_t area_words = 6 * ((size_t)ctx->max_w + ctx->max_h), near_words = (size_t)ctx->max_w + ctx->max_h;
+    if (area.tab.size() > area_words || nearest.tab.size() > near_words) { reloc_set_error("resize tables exceed ctx capacity"); return RELOC_E_CAPACITY; }
+    if (!ctx->rsz_tab) {
+        const size_t px = (size_t)ctx->max_w * ctx->max_h, plane = (size_t)clahe_stride(ctx->max_w) * ctx->max_h;
+        const size_t tab_bytes = ((area_words + near_words) * 4 + 255) & ~(size_t)255;
+        uint8_t *base;
+        HIP_TRY(hipMalloc((void **)&base, tab_bytes + plane + px * 2));
+        ctx->rsz_tab = (int32_t *)base;
+        ctx->rsz_ntab = ctx->rsz_tab + area_words;
+        ctx->rsz_plane = base + tab_bytes;
+        ctx->rsz_depth = (uint16_t *)(base + tab_bytes + plane);
+    }
+    // frames in flight may still read the previous tables
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (!area.tab.empty()) HIP_TRY(hipMemcpy(ctx->rsz_tab, area.tab.data(), area.tab.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ctx->rsz_ntab, nearest.tab.data(), nearest.tab.size() * 4, hipMemcpyHostToDevice));
+    ctx->rsz_kind = area.kind; ctx->rsz_isx = area.isx; ctx->rsz_isy = area.isy;
+    ctx->rsz_sw = sw; ctx->rsz_sh = sh; ctx->rsz_dw = dw; ctx->rsz_dh = dh;
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_get_resize(reloc_ctx *ctx, int32_t *sw, int32_t *sh, int32_t *dw, int32_t *dh)
+{
+    ARG_CHECK_CTX(ctx, sw && sh && dw && dh, "reloc_get_resize");
+    *sw = ctx->rsz_sw; *sh = ctx->rsz_sh; *dw = ctx->rsz_dw; *dh = ctx->rsz_dh;
     return RELOC_OK;
 }

@@ -285,6 +285,63 @@ class Engine:
         N.check(self._lib.reloc_get_rectify_map(self._ctx, C.byref(w), C.byref(h)), "reloc_get_rectify_map")
         return None if w.value == 0 else (w.value, h.value)
 
+    def resize(self, src: np.ndarray, dsize=None, fx: float = 0.0, fy: float = 0.0, interpolation: int = 1) -> np.ndarray:
+        """cv2.resize(src, dsize, fx=fx, fy=fy, interpolation=interpolation): src (H, W) or (H, W, 3) uint8 with INTER_NEAREST
+        (0), INTER_LINEAR (1) or INTER_AREA (3, downscale only), or (H, W) uint16 with INTER_NEAREST; dsize = (width, height),
+        or None / (0, 0) for the fx / fy form (reloc_resize_u8 / _u16)"""
+        src = np.asarray(src)
+        if src.ndim not in (2, 3) or src.size == 0:
+            raise N.RelocError("resize: expected an (H, W) or (H, W, 3) uint8 image, or an (H, W) uint16 image")
+        sh, sw = src.shape[:2]
+        if dsize is None or tuple(dsize) == (0, 0):
+            fx, fy = float(fx), float(fy)
+            if not (fx > 0 and fy > 0 and np.isfinite(fx) and np.isfinite(fy)):
+                raise N.RelocError("resize: without dsize, fx and fy must be positive and finite")
+            dw, dh = (int(min(max(np.rint(s * f), -2147483648.0), 2147483647.0)) for s, f in ((sw, fx), (sh, fy)))
+            if dw < 1 or dh < 1:
+                raise N.RelocError("resize: fx / fy give an empty destination")
+        else:
+            dw, dh = (int(t) for t in dsize)
+            if dw < 1 or dh < 1:
+                raise N.RelocError("resize: dsize must be (width, height) with both positive")
+            fx = fy = 0.0
+        if src.dtype == np.uint16:
+            if src.ndim != 2 or interpolation != 0:
+                raise N.RelocError("resize: uint16 input is single-channel and INTER_NEAREST only")
+            src = np.ascontiguousarray(src)
+            out = np.empty((dh, dw), np.uint16)
+            N.check(self._lib.reloc_resize_u16(self._ctx, N.ptr(src), sw, sh, src.strides[0], N.ptr(out), dw, dh, fx, fy),
+                    "reloc_resize_u16")
+            return out
+        if src.dtype != np.uint8 or not (src.ndim == 2 or src.shape[2] == 3):
+            raise N.RelocError("resize: expected an (H, W) or (H, W, 3) uint8 image, or an (H, W) uint16 image")
+        ch = 1 if src.ndim == 2 else 3
+        if src.strides[-1] != 1 or (ch == 3 and src.strides[1] != 3) or src.strides[0] < sw * ch:
+            src = np.ascontiguousarray(src)
+        out = np.empty((dh, dw) if ch == 1 else (dh, dw, 3), np.uint8)
+        N.check(self._lib.reloc_resize_u8(self._ctx, C.c_void_p(src.ctypes.data), sw, sh, src.strides[0], ch, N.ptr(out), dw, dh,
+                                          fx, fy, int(interpolation)), "reloc_resize_u8")
+        return out
+
+    def set_resize(self, src_size=None, dst_size=None):
+        """The downscale stage at the head of the image chain (reloc_set_resize): every 3-channel frame of the fused tick,
+        recording and reloc_orb_frame_dev must be src_size = (w, h) and is converted to gray and resized to dst_size = (w, h)
+        with INTER_AREA before rectification, CLAHE and ORB; the depth of recording and accumulation with INTER_NEAREST.
+        Everything downstream, the camera included, is that of the working frame dst_size.  None = off."""
+        if src_size is None and dst_size is None:
+            N.check(self._lib.reloc_set_resize(self._ctx, 0, 0, 0, 0), "reloc_set_resize")
+            return
+        if src_size is None or dst_size is None:
+            raise N.RelocError("set_resize: give both sizes, or neither to turn the stage off")
+        (sw, sh), (dw, dh) = (int(t) for t in src_size), (int(t) for t in dst_size)
+        N.check(self._lib.reloc_set_resize(self._ctx, sw, sh, dw, dh), "reloc_set_resize")
+
+    def get_resize(self):
+        """None when off, else ((sw, sh), (dw, dh))"""
+        v = [C.c_int32() for _ in range(4)]
+        N.check(self._lib.reloc_get_resize(self._ctx, *(C.byref(t) for t in v)), "reloc_get_resize")
+        return None if v[2].value == 0 else ((v[0].value, v[1].value), (v[2].value, v[3].value))
+
     def record_frame(self, bgr: np.ndarray, depth_mm: np.ndarray, nfeatures: int = 500, order_rgb: bool = False):
         """teach-side record arrays of one frame: dict(xy (n,2), desc (n,32), pts3d (n,3), kp_index (n,), n, n_kp)"""
         bgr = N.u8(bgr)

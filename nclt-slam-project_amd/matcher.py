@@ -43,6 +43,11 @@ class MatcherConfig:
     # cv2.initUndistortRectifyMap / cv2.fisheye.initUndistortRectifyMap.  fx, fy, cx, cy are then the newCameraMatrix the
     # map was built for and dist stays empty.  Teach with the same map.
     rectify: tuple | None = None
+    # downscale of the frame at the head of the image chain, between gray conversion and rectification: None = off, or
+    # (width, height) as in cv2.resize(gray, (808, 616), interpolation=cv2.INTER_AREA) of the dataset runners (the depth with
+    # INTER_NEAREST).  fx, fy, cx, cy, the rectification map and every coordinate are then those of the resized image
+    # (scaled_camera).  The fused matcher's Engine must be created for the camera's full size.  Teach with the same size.
+    resize: tuple | None = None
     candidate_radius_m: float = 8.0
     max_candidates: int = 5
     heading_tol_deg: float = 90.0
@@ -91,6 +96,24 @@ class TickOutcome:
     extra: dict = field(default_factory=dict)
 
 
+def scaled_camera(K4, src_size, dst_size):
+    """(fx, fy, cx, cy) of an image resized from src_size = (w, h) to dst_size = (w, h) by cv2.resize: pixel centres map as
+    x' = (x + 0.5) / s - 0.5 with s = src / dst per axis, so fx' = fx / sx, cx' = (cx + 0.5) / sx - 0.5 (and likewise in y)"""
+    fx, fy, cx, cy = (float(t) for t in K4)
+    sx, sy = src_size[0] / dst_size[0], src_size[1] / dst_size[1]
+    return (fx / sx, fy / sy, (cx + 0.5) / sx - 0.5, (cy + 0.5) / sy - 0.5)
+
+
+def resize_setting(size):
+    """MatcherConfig.resize / the recorder's resize= as (width, height) ints (None stays None)"""
+    if size is None:
+        return None
+    w, h = (int(t) for t in size)
+    if w < 1 or h < 1:
+        raise ValueError("resize must be (width, height), both positive")
+    return (w, h)
+
+
 def fixed_rectify_maps(cv2, maps):
     """MatcherConfig.rectify as the fixed-point pair cv2.remap reads for both interpolations (None stays None)"""
     if maps is None:
@@ -120,6 +143,7 @@ class LandmarkMatcherCore:
         self.clahe = None if self.cfg.clahe is None else cv2.createCLAHE(clipLimit=self.cfg.clahe[0],
                                                                          tileGridSize=tuple(self.cfg.clahe[1]))
         self.rectify = fixed_rectify_maps(cv2, self.cfg.rectify)
+        self.resize = resize_setting(self.cfg.resize)
         self.dist = np.zeros((4, 1), dtype=np.float32) if len(self.cfg.dist) == 0 else np.asarray(self.cfg.dist, np.float64).reshape(-1, 1)
         self.last_anchor_ts = 0.0
         self.n_attempts = 0
@@ -260,6 +284,10 @@ class LandmarkMatcherCore:
         vio_xy = (base_pose[0], base_pose[1])
         cand, d, herr = self.select_candidates(base_pose)
         gray = cv2.cvtColor(bgr, cv2.COLOR_BGR2GRAY)
+        if self.resize is not None:
+            gray = cv2.resize(gray, self.resize, interpolation=cv2.INTER_AREA)
+            if depth_mm is not None:
+                depth_mm = cv2.resize(depth_mm, self.resize, interpolation=cv2.INTER_NEAREST)
         if self.rectify is not None:
             gray = cv2.remap(gray, *self.rectify, cv2.INTER_LINEAR)
             if depth_mm is not None:
@@ -374,6 +402,8 @@ class FusedLandmarkMatcher:
                      data.get("base_to_cam_rot", P.BASE_TO_CAM_ROT))
         e.set_distortion(cfg.dist)
         e.set_clahe(*((None,) if cfg.clahe is None else (cfg.clahe[0], tuple(cfg.clahe[1]))))
+        size = resize_setting(cfg.resize)
+        e.set_resize(*((None, None) if size is None else ((e.max_w, e.max_h), size)))   # the Engine is as large as the camera
         e.set_rectify(cfg.rectify)
         self._return_src = return_landmarks
         self.swap_flag = swap_flag

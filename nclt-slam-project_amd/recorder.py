@@ -14,7 +14,7 @@ import numpy as np
 
 from . import pose as P
 from .landmarks import new_database, save_landmarks
-from .matcher import fixed_rectify_maps
+from .matcher import fixed_rectify_maps, resize_setting
 
 FX = FY = 320.0
 CX, CY = 320.0, 240.0
@@ -41,7 +41,7 @@ def local_depth_std(depth_mm, uu, vv):
 
 class LandmarkRecorderCore:
     def __init__(self, out_pkl=None, min_disp_m: float = 2.0, cv2=None, nfeatures: int = 500, logger=None, engine=None,
-                 dist=(), clahe=None, rectify=None):
+                 dist=(), clahe=None, rectify=None, resize=None):
         """engine: when given, ORB + all per-keypoint gates + back-projection run in ONE device call
         (reloc_record_frame); otherwise the gates run in NumPy on the cv2-shaped module's features.
         dist: lens distortion as MatcherConfig.dist (OpenCV's k1 k2 p1 p2 [k3], () = pinhole): the kept keypoints are
@@ -49,12 +49,17 @@ class LandmarkRecorderCore:
         clahe: None or (clipLimit, (tiles_x, tiles_y)) as MatcherConfig.clahe: CLAHE between gray conversion and ORB (engine:
         reloc_set_clahe; cv2 path: cv2.createCLAHE(...).apply), so that the repeat run can equalise the same way.
         rectify: None or (map1, map2) as MatcherConfig.rectify: the frame is rectified between gray conversion and CLAHE /
-        ORB and the depth read through the same map, nearest (engine: reloc_set_rectify_map; cv2 path: cv2.remap)."""
+        ORB and the depth read through the same map, nearest (engine: reloc_set_rectify_map; cv2 path: cv2.remap).
+        resize: None or (width, height) as MatcherConfig.resize: the gray frame is resized with INTER_AREA and the depth with
+        INTER_NEAREST before the rectification; the camera and the map are those of the resized image (engine:
+        reloc_set_resize from the engine's full size, which must be the camera's; cv2 path: cv2.resize)."""
         self.engine = engine
         self.dist = tuple(np.asarray(dist, np.float64).ravel()) if dist is not None else ()
         if engine is not None:
             engine.set_distortion(self.dist)
             engine.set_clahe(*((None,) if clahe is None else (clahe[0], tuple(clahe[1]))))
+            size = resize_setting(resize)
+            engine.set_resize(*((None, None) if size is None else ((engine.max_w, engine.max_h), size)))
             engine.set_rectify(rectify)
         self.nfeatures = nfeatures
         if cv2 is None and engine is None:
@@ -66,6 +71,7 @@ class LandmarkRecorderCore:
         self.clahe = (cv2.createCLAHE(clipLimit=clahe[0], tileGridSize=tuple(clahe[1]))
                       if cv2 is not None and clahe is not None else None)
         self.rectify = fixed_rectify_maps(cv2, rectify) if cv2 is not None else None
+        self.resize = resize_setting(resize)
         self.landmarks = []
         self.last_landmark_pose_world = None
         self.log = logger or (lambda msg: None)
@@ -90,6 +96,9 @@ class LandmarkRecorderCore:
             return rec
         cv2 = self.cv2
         gray = cv2.cvtColor(bgr, cv2.COLOR_BGR2GRAY)
+        if self.resize is not None:
+            gray = cv2.resize(gray, self.resize, interpolation=cv2.INTER_AREA)
+            depth_mm = cv2.resize(depth_mm, self.resize, interpolation=cv2.INTER_NEAREST)
         if self.rectify is not None:
             gray = cv2.remap(gray, *self.rectify, cv2.INTER_LINEAR)
             depth_mm = cv2.remap(depth_mm, *self.rectify, cv2.INTER_NEAREST)
