@@ -337,7 +337,7 @@ struct reloc_ctx {
     // ---- downscale stage at the head of the image chain on 3-channel frames (reloc_set_resize); all 0 = off, the default ----
     int rsz_sw = 0, rsz_sh = 0;          // the size every frame must have
     int rsz_dw = 0, rsz_dh = 0;          // the working frame: what rectification, CLAHE, ORB, the recorder and the camera see
-    int rsz_kind = 0, rsz_isx = 1, rsz_isy = 1;   // kernel kind and integer box of the INTER_AREA resize (reloc_orb.hip)
+    int rsz_kind = 0, rsz_isx = 1, rsz_isy = 1;   // kernel kind and integer box of the INTER_AREA resize (reloc_image.hip)
     int32_t *rsz_tab = nullptr;          // INTER_AREA tap lists; allocated on first enable, one block with the three below
     int32_t *rsz_ntab = nullptr;         // INTER_NEAREST offsets of the depth image
     uint8_t *rsz_plane = nullptr;        // resized gray plane, row stride (dw + 63) & ~63
@@ -428,14 +428,19 @@ int db_reindex(reloc_ctx *ctx);
 int db_reserve(reloc_ctx *ctx, int64_t cap_records, int64_t cap_rows);
 inline bool db_ready(const reloc_ctx *ctx) { return ctx->db_desc && ctx->db_off && ctx->db_pose && ctx->db_xy_heading && ctx->db_counts && ctx->db_records > 0; }
 int orb_prepare(reloc_ctx *ctx, int w, int h, int nfeatures);
-// ORB of frame f = srcs[f] into ctxs[f]'s feature buffers; channels == 3 -> interleaved frames (gray fused; rectification, then
-// CLAHE first when the contexts have them on; with the downscale stage on, w x h is the source size and the features are those
+// ORB of frame f = srcs[f] into ctxs[f]'s feature buffers; channels == 3 -> interleaved frames (gray fused; the image chain
+// first when the contexts have stages on; with the downscale stage on, w x h is the source size and the features are those
 // of the working frame), channels == 1 -> gray planes (reloc_orb.hip)
 int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, int h, int stride, int channels, int order,
             int nfeatures, bool latency);
-// the depth image of a context with the downscale stage on, INTER_NEAREST to the working size, into the context's plane
-int resize_depth(reloc_ctx *ctx, const uint16_t *depth_dev, int w, int h, const uint16_t **out);
-// the depth image of a context with a rectification map read through the map (nearest) into the context's depth plane
-int rectify_depth(reloc_ctx *ctx, const uint16_t *depth_dev, int w, int h, const uint16_t **out);
+// The image chain of a context's stages, resize -> rectify -> CLAHE (reloc_image.hip).  The checks stand before orb_prepare
+// (the downscale stage; w x h becomes the working frame) and behind that of context f (rectification, CLAHE); _gray runs the
+// stages on 3-channel frames and leaves *srcs / *stride / *channels describing the last plane written; _depth takes a
+// depth image through resize and rectification (nearest), *w x *h becomes the working frame.
+int image_chain_check(reloc_ctx *const *ctxs, int n, int channels, int *w, int *h);
+int image_chain_check_prepared(reloc_ctx *const *ctxs, int f, int n, int channels, int w, int h);
+int image_chain_gray(reloc_ctx *const *ctxs, int n, const uint8_t *const **srcs, int sw, int sh, int w, int h, int *stride,
+                     int *channels, int flags, const uint8_t **planes);
+int image_chain_depth(reloc_ctx *ctx, const uint16_t *depth_dev, int *w, int *h, const uint16_t **out);
 // PnP-RANSAC of every context's candidates with the matcher parameters of ctxs[0]; seeds: one per frame, or NULL (reloc_pnp.hip)
 int pnp_run_candidates(reloc_ctx *const *ctxs, int n, const uint64_t *seeds, bool latency);

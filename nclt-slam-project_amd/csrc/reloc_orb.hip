@@ -1,7 +1,8 @@
-// reloc_orb.hip -- ORB front end on gfx950: gray -> 8-level pyramid -> FAST-9/16 + NMS ->
+// reloc_orb.hip -- ORB front end on gfx950: 8-level pyramid (gray conversion fused) -> FAST-9/16 + NMS ->
 // best-2n by FAST score -> Harris -> best-n -> intensity-centroid angle -> 7x7 blur -> steered
-// BRIEF-256.  Serves cv2.cvtColor(.., COLOR_BGR2GRAY) and
-// cv2.ORB_create(nfeatures).detectAndCompute(gray, None)        (reference M:305-306, R:240-241).
+// BRIEF-256.  Serves cv2.ORB_create(nfeatures).detectAndCompute(gray, None)        (reference M:306, R:241).
+// Holds the five ORB kernels with their batched twins, orb_prepare (tables and tiles of a frame size), orb_run and the ORB
+// entry points.  What happens to a frame before the pyramid is reloc_image.hip; the pixel helpers of both are reloc_pixels.h.
 //
 // Everything is integer or strictly-ordered IEEE float arithmetic (no fused multiply-add, own
 // sin/cos) so results are bit-identical to the specification; the algorithm constants live in
@@ -9,7 +10,10 @@
 // row stride inside one arena (ctx->pyr); the blurred pyramid (ctx->blur) and the NMS score maps
 // (ctx->nms) use the same geometry, so a level is addressed by one offset in all three.
 //
-// Launches per frame (all on the ctx stream):
+// The image chain feeds it through orb_run: image_chain_check, orb_prepare for the working frame, then image_chain_gray runs
+// the stages that are on and names the last plane written, which k_pyramid reads instead of the caller's frame.
+//
+// Five launches per frame (all on the ctx stream):
 //   k_pyramid                            gray conversion (or a gray plane) and all 8 levels in one launch: a tile
 //                                        owns a rectangle of every level and derives level l from level l-1 in LDS
 //                                        (fixed-point INTER_LINEAR_EXACT), 4 px per lane, dword stores
@@ -30,16 +34,11 @@
 //                                        256 steered tests -> 4 ballots = 32 descriptor bytes
 // The per-frame HBM traffic is about 4 MB at 640x480; the stage is launch/latency-bound, not
 // bandwidth-bound.
-#include <float.h>
 #include <math.h>
-
-#include <algorithm>
-#include <vector>
 
 #include "../../include/reloc_orb_pattern.h"
 #include "reloc_internal.h"
-
-typedef uint32_t u32;
+#include "reloc_pixels.h"
 
 constexpr int HARRIS_CHUNK = 1024;   // bytes of the NMS map per k_harris block (4 per thread)
 static_assert(HARRIS_CHUNK == 1024, "k_harris reads one dword per thread");
@@ -63,42 +62,6 @@ __device__ __forceinline__ int find_level(const int *base, int id)
 #pragma unroll
     for (int k = 1; k < NLEV; ++k) l += id >= base[k];
     return l;
-}
-
-__device__ __forceinline__ int reflect101(int p, int n)
-{
-    if (n == 1) return 0;
-    while (p < 0 || p >= n) {
-        if (p < 0) p = -p;
-        if (p >= n) p = 2 * n - 2 - p;
-    }
-    return p;
-}
-
-// ---- gray ---------------------------------------------------------------------------------------
-// `order_rgb` of the gray stages carries two flags: bit 0 = RELOC_ORDER_RGB, bit 1 = RELOC_GRAY_FLAG_15BIT (the 15-bit
-// coefficient set of reloc_params.gray_coeff_bits == 15).  Both are launch-uniform: the selects run on the scalar unit.
-__device__ __forceinline__ int gray_fixed(int b, int g, int r, int flags)
-{
-    const bool c15 = flags & RELOC_GRAY_FLAG_15BIT;
-    const int cb = c15 ? RELOC_GRAY15_CB : RELOC_GRAY_CB, cg = c15 ? RELOC_GRAY15_CG : RELOC_GRAY_CG, cr = c15 ? RELOC_GRAY15_CR : RELOC_GRAY_CR;
-    const int sh = c15 ? RELOC_GRAY15_SHIFT : RELOC_GRAY_SHIFT;
-    return (b * cb + g * cg + r * cr + (1 << (sh - 1))) >> sh;
-}
-static inline int gray_flags(const reloc_ctx *ctx, int order)
-{
-    return (order & 1) | (ctx->prm.gray_coeff_bits == RELOC_GRAY15_SHIFT ? RELOC_GRAY_FLAG_15BIT : 0);
-}
-// plain gray output for reloc_gray_u8 (dense rows)
-__global__ __launch_bounds__(256) void k_gray_plain(const uint8_t *__restrict__ src, int w, int h, int sstride, int order_rgb,
-                                                    uint8_t *__restrict__ dst)
-{
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-    if (x >= w) return;
-    const uint8_t *s = src + (size_t)y * sstride + 3 * x;
-    const int c0 = s[0], c1 = s[1], c2 = s[2];
-    const int b = (order_rgb & 1) ? c2 : c0, r = (order_rgb & 1) ? c0 : c2;
-    dst[(size_t)y * w + x] = (uint8_t)gray_fixed(b, c1, r, order_rgb);
 }
 
 // ---- fused pyramid ------------------------------------------------------------------------------
@@ -132,39 +95,6 @@ struct OrbFrame {
     int32_t *f_count;
 };
 struct OrbBatch { OrbFrame f[RELOC_BATCH_MAX]; };
-
-// gray value of 4 pixels from 12 interleaved bytes / a gray dword
-template <int CH, bool ALIGNED>
-__device__ __forceinline__ void pyr_fetch(const uint8_t *sp, int x4, int w, u32 (&d)[3])
-{
-    if (ALIGNED) {
-        const u32 *s4 = reinterpret_cast<const u32 *>(sp);
-        d[0] = s4[0];
-        if (CH == 3) { d[1] = s4[1]; d[2] = s4[2]; }
-    } else {
-        d[0] = d[1] = d[2] = 0;
-#pragma unroll
-        for (int k = 0; k < 4 * CH; ++k)
-            if (x4 + k / CH < w) d[k >> 2] |= (u32)sp[k] << (8 * (k & 3));
-    }
-}
-
-template <int CH>
-__device__ __forceinline__ u32 pyr_gray4(const u32 (&d)[3], int x4, int w, int order_rgb)
-{
-    if (CH == 1) return d[0];     // bytes beyond w are 0 (unaligned fetch) or do not exist (aligned: w % 4 == 0)
-    u32 out = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        int c[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) { const int bi = 3 * k + j; c[j] = (d[bi >> 2] >> (8 * (bi & 3))) & 0xFF; }
-        const int b = (order_rgb & 1) ? c[2] : c[0], r = (order_rgb & 1) ? c[0] : c[2];
-        const int g = gray_fixed(b, c[1], r, order_rgb);
-        if (x4 + k < w) out |= (u32)g << (8 * k);
-    }
-    return out;
-}
 
 // flat table index i -> positions of the (offset, coefficient) entries in the resize tables; the level is found
 // by selects over uniform values so that no load depends on it
@@ -338,7 +268,6 @@ __global__ __launch_bounds__(PYR_BS) void k_pyramid_batch(OrbBatch b, int w, int
     const OrbFrame &F = b.f[blockIdx.y];
     pyramid_body<CH, ALIGNED, PYR_BS>(F.tab, F.tiles, F.rz, F.src, w, h, sstride, order_rgb, F.pyr, lds, F.hist, F.cand_cnt);
 }
-
 
 // ---- blur ---------------------------------------------------------------------------------------
 // Four bytes of one level row starting at the 4-aligned column gx, with the border rule applied per byte (BORDER_REFLECT_101
@@ -689,29 +618,6 @@ __device__ __forceinline__ void fast_nms_tile(const OrbTable *__restrict__ tab, 
 }
 
 // ---- stage 1 cut + Harris -----------------------------------------------------------------------
-__device__ float harris_px(const uint8_t *p, int step)
-{
-    int a = 0, b = 0, c = 0;
-#pragma unroll
-    for (int dy = -3; dy <= 3; ++dy)
-#pragma unroll
-        for (int dx = -3; dx <= 3; ++dx) {
-            const uint8_t *q = p + dy * step + dx;
-            const int ix = (q[1] - q[-1]) * 2 + (q[-step + 1] - q[-step - 1]) + (q[step + 1] - q[step - 1]);
-            const int iy = (q[step] - q[-step]) * 2 + (q[step - 1] - q[-step - 1]) + (q[step + 1] - q[-step + 1]);
-            a += ix * ix;
-            b += iy * iy;
-            c += ix * iy;
-        }
-    const float scale = __fdiv_rn(1.f, (float)((1 << 2) * RELOC_HARRIS_BLOCK) * 255.f);
-    const float s2 = __fmul_rn(scale, scale), s3 = __fmul_rn(s2, scale), s4 = __fmul_rn(s3, scale);
-    const float fa = (float)a, fb = (float)b, fc = (float)c;
-    const float t1 = __fmul_rn(fa, fb), t2 = __fmul_rn(fc, fc), t3 = __fadd_rn(fa, fb);
-    const float t4 = __fmul_rn(RELOC_HARRIS_K, t3), t5 = __fmul_rn(t4, t3);
-    const float t6 = __fsub_rn(t1, t2), t7 = __fsub_rn(t6, t5);
-    return __fmul_rn(t7, s4);
-}
-
 // FAST + NMS tiles and 7x7 blur tiles of all levels in ONE launch, one workgroup per tile: both only read the pyramid, FAST
 // feeds Harris and the blur feeds the descriptors, so they need not run one after the other.  (A smaller grid whose workgroups
 // walk the tiles paid beside 112-register scans and pays nothing beside 104-register ones: profiles/README.md "Dropped
@@ -731,7 +637,6 @@ __global__ __launch_bounds__(256) void k_fast_blur_batch(OrbBatch b, int n_fast)
     if ((int)blockIdx.x < n_fast) fast_nms_tile(F.tab, F.pyr, F.nms, F.hist, (int)blockIdx.x);
     else blur7_tile(F.tab, F.pyr, F.blur, (int)blockIdx.x - n_fast);
 }
-
 
 // cut score from the level's histogram (KeyPointsFilter::retainBest(2*quota) with ties kept, raised
 // while the kept set exceeds RELOC_ORB_STAGE1_CAP), by ONE wave without block barriers: lane i owns the
@@ -903,7 +808,6 @@ __global__ __launch_bounds__(256) void k_harris_batch(OrbBatch b)
     harris_body(F.tab, F.pyr, F.nms, F.hist, F.cand_cnt, F.cand_key, F.cand_resp, F.dbg_cut);
 }
 
-
 // ---- stage 2: best quota by Harris (ties kept), raster order -----------------------------------
 // One workgroup per level.  Element i is kept iff fewer than `quota` responses are strictly greater
 // (= best quota plus every tie of the quota-th); the kept ones are then placed in raster order by
@@ -959,7 +863,6 @@ __global__ __launch_bounds__(1024) void k_select_batch(OrbBatch b)
     const OrbFrame &F = b.f[blockIdx.y];
     select_body(F.tab, F.cand_cnt, F.cand_key, F.cand_resp, F.kp_cnt, F.kp_key, F.kp_resp);
 }
-
 
 // ---- orientation + descriptor -------------------------------------------------------------------
 __device__ float fast_atan2_deg(float y, float x)
@@ -1114,7 +1017,6 @@ __global__ __launch_bounds__(256) void k_describe_batch(OrbBatch b, int max_feat
                   F.f_count);
 }
 
-
 // ------------------------------------------------------------------------------------------------
 static void resize_axis(int src_n, int dst_n, int32_t *ofs, int32_t *coef)
 {
@@ -1253,750 +1155,6 @@ int orb_prepare(reloc_ctx *ctx, int w, int h, int nfeatures)
     return RELOC_OK;
 }
 
-// ---- CLAHE (include/reloc_spec.h) -------------------------------------------------------------------
-// cv2.createCLAHE(clipLimit, tileGridSize).apply(gray) on 8-bit input, in two launches:
-//   k_clahe_lut    one workgroup per tile: histogram of the tile's pixels of the padded frame (BORDER_REFLECT_101 on the
-//                  right / bottom) in per-wave LDS sub-histograms (integer atomics: order-independent), then wave 0 holds
-//                  4 bins per lane for the clip, the redistribution and the prefix sum and stores the tile's 256-byte LUT
-//   k_clahe_apply  4 pixels per lane: gray (CH = 3: fused conversion), four LUT lookups through the cache, bilinear blend
-// CH = 3 reads an interleaved frame (gray_fixed with the order / coefficient flags), CH = 1 a gray plane.  Both are
-// frame-batched (blockIdx.y = frame); a single frame is a batch of one.
-struct ClaheGeom {
-    int w, h;              // frame size (the interpolation runs over it)
-    int tx, ty;            // tile grid
-    int tw, th;            // tile size in the padded frame
-    int clip;              // clip count per bin, 0 = no clipping
-    float lut_scale;       // 255.0f / (tw * th)
-    float inv_tw, inv_th;  // 1.0f / tw, 1.0f / th
-};
-struct ClaheFrames { const uint8_t *src[RELOC_BATCH_MAX]; uint8_t *lut[RELOC_BATCH_MAX]; uint8_t *dst[RELOC_BATCH_MAX]; };
-#ifndef RELOC_CLAHE_LUT_BS
-#define RELOC_CLAHE_LUT_BS 1024
-#endif
-constexpr int CLAHE_LUT_BS = RELOC_CLAHE_LUT_BS;     // 16 waves, 16 sub-histograms (16 KB of LDS); see DESIGN.md for 256 / 512
-constexpr int CLAHE_MAX_TILES = RELOC_CLAHE_MAX_TILES;
-
-static ClaheGeom clahe_geom(int w, int h, double clip_limit, int tx, int ty)
-{
-    ClaheGeom g;
-    g.w = w; g.h = h; g.tx = tx; g.ty = ty;
-    // OpenCV pads BOTH axes unless both divide (a full extra tile on an axis that already divides)
-    const bool divides = w % tx == 0 && h % ty == 0;
-    g.tw = divides ? w / tx : (w + tx - w % tx) / tx;
-    g.th = divides ? h / ty : (h + ty - h % ty) / ty;
-    const int area = g.tw * g.th;
-    if (clip_limit > 0.0) {
-        const int c = (int)(clip_limit * area / 256);
-        g.clip = c > 1 ? c : 1;
-    } else {
-        g.clip = 0;
-    }
-    g.lut_scale = 255.0f / (float)area;
-    g.inv_tw = 1.0f / (float)g.tw;
-    g.inv_th = 1.0f / (float)g.th;
-    return g;
-}
-
-template <int CH>
-__global__ __launch_bounds__(CLAHE_LUT_BS) void k_clahe_lut(ClaheFrames F, ClaheGeom g, int sstride, int flags)
-{
-    constexpr int NWAVE = CLAHE_LUT_BS / 64;
-    __shared__ int s_hist[NWAVE][256];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    for (int i = tid; i < NWAVE * 256; i += CLAHE_LUT_BS) (&s_hist[0][0])[i] = 0;
-    __syncthreads();
-    const uint8_t *src = F.src[blockIdx.y];
-    const int ti = blockIdx.x % g.tx, tj = blockIdx.x / g.tx;
-    const int x0 = ti * g.tw, y0 = tj * g.th;
-    for (int py = wave; py < g.th; py += NWAVE) {
-        const int sy = y0 + py < g.h ? y0 + py : reflect101(y0 + py, g.h);
-        const uint8_t *row = src + (size_t)sy * sstride;
-        for (int px = lane; px < g.tw; px += 64) {
-            const int sx = x0 + px < g.w ? x0 + px : reflect101(x0 + px, g.w);
-            int v;
-            if (CH == 1) {
-                v = row[sx];
-            } else {
-                const uint8_t *p = row + 3 * sx;
-                const int c0 = p[0], c1 = p[1], c2 = p[2];
-                v = gray_fixed((flags & 1) ? c2 : c0, c1, (flags & 1) ? c0 : c2, flags);
-            }
-            atomicAdd(&s_hist[wave][v], 1);
-        }
-    }
-    __syncthreads();
-    if (wave != 0) return;
-    int hb[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        int s = 0;
-#pragma unroll
-        for (int wv = 0; wv < NWAVE; ++wv) s += s_hist[wv][4 * lane + k];
-        hb[k] = s;
-    }
-    if (g.clip > 0) {
-        int clipped = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int ex = hb[k] > g.clip ? hb[k] - g.clip : 0;
-            clipped += ex;
-            hb[k] -= ex;
-        }
-        clipped = wave_sum_i32(clipped);
-        const int batch = clipped >> 8, residual = clipped & 255;
-        const int step = residual ? (256 / residual > 1 ? 256 / residual : 1) : 1;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int bin = 4 * lane + k;
-            hb[k] += batch + (residual && bin % step == 0 && bin / step < residual ? 1 : 0);
-        }
-    }
-    // inclusive prefix sum: 4 bins in the lane, then the lanes' totals across the wave
-    int loc[4];
-    loc[0] = hb[0];
-#pragma unroll
-    for (int k = 1; k < 4; ++k) loc[k] = loc[k - 1] + hb[k];
-    int incl = loc[3];
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off);
-        if (lane >= off) incl += t;
-    }
-    const int excl = incl - loc[3];
-    u32 out = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        int v = __float2int_rn((float)(excl + loc[k]) * g.lut_scale);     // saturate_cast<uchar>: cvRound, then clamp
-        v = v < 0 ? 0 : (v > 255 ? 255 : v);
-        out |= (u32)v << (8 * k);
-    }
-    reinterpret_cast<u32 *>(F.lut[blockIdx.y] + (size_t)blockIdx.x * 256)[lane] = out;
-}
-
-template <int CH, bool ALIGNED>
-__global__ __launch_bounds__(256) void k_clahe_apply(ClaheFrames F, ClaheGeom g, int sstride, int flags, int dstride)
-{
-    const int quads = (g.w + 3) >> 2;
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= quads * g.h) return;
-    const int y = q / quads, x4 = 4 * (q - y * quads);
-    u32 d[3];
-    pyr_fetch<CH, ALIGNED>(F.src[blockIdx.y] + (size_t)y * sstride + CH * x4, x4, g.w, d);
-    const u32 gray4 = pyr_gray4<CH>(d, x4, g.w, flags);
-    const float tyf = (float)y * g.inv_th - 0.5f;
-    int ty1 = (int)floorf(tyf);
-    const float ya = tyf - (float)ty1, ya1 = 1.0f - ya;
-    const int ty2 = ty1 + 1 < g.ty - 1 ? ty1 + 1 : g.ty - 1;
-    ty1 = ty1 > 0 ? ty1 : 0;
-    const uint8_t *lut = F.lut[blockIdx.y];
-    const uint8_t *L1 = lut + (size_t)ty1 * g.tx * 256, *L2 = lut + (size_t)ty2 * g.tx * 256;
-    u32 out = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int x = x4 + k;
-        const float txf = (float)x * g.inv_tw - 0.5f;
-        int tx1 = (int)floorf(txf);
-        const float xa = txf - (float)tx1, xa1 = 1.0f - xa;
-        const int tx2 = tx1 + 1 < g.tx - 1 ? tx1 + 1 : g.tx - 1;
-        tx1 = tx1 > 0 ? tx1 : 0;
-        const int v = (gray4 >> (8 * k)) & 0xFF;
-        const float l11 = L1[tx1 * 256 + v], l12 = L1[tx2 * 256 + v], l21 = L2[tx1 * 256 + v], l22 = L2[tx2 * 256 + v];
-        const float res = (l11 * xa1 + l12 * xa) * ya1 + (l21 * xa1 + l22 * xa) * ya;
-        int r = __float2int_rn(res);
-        r = r < 0 ? 0 : (r > 255 ? 255 : r);
-        if (x < g.w) out |= (u32)r << (8 * k);
-    }
-    uint8_t *dst = F.dst[blockIdx.y] + (size_t)y * dstride + x4;
-    if ((dstride & 3) == 0) {
-        *reinterpret_cast<u32 *>(dst) = out;       // the row holds round4(w) bytes: dstride >= w and a multiple of 4
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (x4 + k < g.w) dst[k] = (uint8_t)(out >> (8 * k));
-    }
-}
-
-// the two CLAHE launches for n frames of equal geometry on stream st; srcs: channels-interleaved rows of sstride bytes
-static int clahe_launch(hipStream_t st, const ClaheFrames &F, int n, const ClaheGeom &g, int channels, int sstride, int flags,
-                        int dstride)
-{
-    bool aligned = g.w % 4 == 0 && sstride % 4 == 0;
-    for (int f = 0; f < n; ++f) aligned = aligned && ((uintptr_t)F.src[f]) % 4 == 0;
-    const int quads = (g.w + 3) / 4;
-    const dim3 glut(g.tx * g.ty, n), gapp((quads * g.h + 255) / 256, n);
-    auto lut = channels == 3 ? k_clahe_lut<3> : k_clahe_lut<1>;
-    auto app = channels == 3 ? (aligned ? k_clahe_apply<3, true> : k_clahe_apply<3, false>)
-                             : (aligned ? k_clahe_apply<1, true> : k_clahe_apply<1, false>);
-    hipLaunchKernelGGL(lut, glut, dim3(CLAHE_LUT_BS), 0, st, F, g, sstride, flags);
-    hipLaunchKernelGGL(app, gapp, dim3(256), 0, st, F, g, sstride, flags, dstride);
-    HIP_TRY(hipGetLastError());
-    return RELOC_OK;
-}
-
-static inline int clahe_stride(int w) { return (w + 63) & ~63; }
-
-// ---- rectification: cv2.remap (include/reloc_spec.h, "REMAP") -----------------------------------------------
-// OpenCV's fixed-point bilinear remap of 8-bit images through a map in the CV_16SC2 + CV_16UC1 form, BORDER_CONSTANT:
-//   k_remap_u8<CH, GRAY>   4 output pixels per lane along x; the four taps of each pixel gathered through the cache (a
-//                          rectification map is locally coherent: neighbouring lanes share lines).  CH = 3, GRAY: the
-//                          stage in front of ORB -- gray of every tap on the fly (gray_fixed with the order / coefficient
-//                          flags), then the blend, one dword store.  CH = 3 (3-channel output) and CH = 1 serve the shim.
-//   k_remap_nearest<T, CH> the source pixel at xy (the fraction is ignored); T = uint16_t for the depth image
-//   k_convert_maps         float maps -> the fixed-point form (cv2.convertMaps)
-// All are frame-batched (blockIdx.y = frame) with per-frame map pointers; a single frame is a batch of one.
-struct RemapFrames {
-    const uint8_t *src[RELOC_BATCH_MAX]; const int16_t *xy[RELOC_BATCH_MAX]; const uint16_t *alpha[RELOC_BATCH_MAX];
-    uint8_t *dst[RELOC_BATCH_MAX];
-};
-struct RemapGeom {
-    int sw, sh, sstride;   // source size, row stride in bytes
-    int dw, dh, dstride;   // map = destination size (maps are dense), destination row stride in bytes
-    int border;            // BORDER_CONSTANT value
-};
-
-// one tap: the source pixel (x, y) or the border value; GRAY converts the 3 channels to one value
-template <int CH, bool GRAY>
-__device__ __forceinline__ void remap_tap(const uint8_t *__restrict__ src, const RemapGeom &g, int x, int y, int flags,
-                                          int (&v)[GRAY ? 1 : CH])
-{
-    const bool in = (unsigned)x < (unsigned)g.sw && (unsigned)y < (unsigned)g.sh;
-#pragma unroll
-    for (int c = 0; c < (GRAY ? 1 : CH); ++c) v[c] = g.border;
-    if (!in) return;
-    const uint8_t *p = src + (size_t)y * g.sstride + CH * x;
-    if (GRAY) {
-        const int c0 = p[0], c1 = p[1], c2 = p[2];
-        v[0] = gray_fixed((flags & 1) ? c2 : c0, c1, (flags & 1) ? c0 : c2, flags);
-    } else {
-#pragma unroll
-        for (int c = 0; c < CH; ++c) v[c] = p[c];
-    }
-}
-
-template <int CH, bool GRAY, bool ALIGNED>
-__global__ __launch_bounds__(256) void k_remap_u8(RemapFrames F, RemapGeom g, int flags)
-{
-    constexpr int OC = GRAY ? 1 : CH;       // output channels
-    const int quads = (g.dw + 3) >> 2;
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= quads * g.dh) return;
-    const int y = q / quads, x4 = 4 * (q - y * quads);
-    const size_t m = (size_t)y * g.dw + x4;
-    const int16_t *xyp = F.xy[blockIdx.y] + 2 * m;
-    const uint16_t *ap = F.alpha[blockIdx.y] + m;
-    u32 xy[4], al[4];
-    if (ALIGNED) {      // dw % 4 == 0 and 16-byte aligned maps: 16 B of xy and 8 B of alpha per lane
-        const uint4 a = *reinterpret_cast<const uint4 *>(xyp);
-        const uint2 b = *reinterpret_cast<const uint2 *>(ap);
-        xy[0] = a.x; xy[1] = a.y; xy[2] = a.z; xy[3] = a.w;
-        al[0] = b.x & 0xFFFF; al[1] = b.x >> 16; al[2] = b.y & 0xFFFF; al[3] = b.y >> 16;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const bool ok = x4 + k < g.dw;
-            xy[k] = ok ? reinterpret_cast<const u32 *>(xyp)[k] : 0;
-            al[k] = ok ? ap[k] : 0;
-        }
-    }
-    const uint8_t *src = F.src[blockIdx.y];
-    int out[4][OC];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int sx = (int16_t)(xy[k] & 0xFFFF), sy = (int16_t)(xy[k] >> 16);
-        const int fx = al[k] & 31, fy = (al[k] >> 5) & 31;
-        int p00[OC], p01[OC], p10[OC], p11[OC];
-        remap_tap<CH, GRAY>(src, g, sx, sy, flags, p00);
-        remap_tap<CH, GRAY>(src, g, sx + 1, sy, flags, p01);
-        remap_tap<CH, GRAY>(src, g, sx, sy + 1, flags, p10);
-        remap_tap<CH, GRAY>(src, g, sx + 1, sy + 1, flags, p11);
-        const int w00 = 32 * (32 - fx) * (32 - fy), w01 = 32 * fx * (32 - fy), w10 = 32 * (32 - fx) * fy, w11 = 32 * fx * fy;
-#pragma unroll
-        for (int c = 0; c < OC; ++c) out[k][c] = (p00[c] * w00 + p01[c] * w01 + p10[c] * w10 + p11[c] * w11 + (1 << 14)) >> 15;
-    }
-    uint8_t *dst = F.dst[blockIdx.y] + (size_t)y * g.dstride + OC * x4;
-    if (OC == 1 && (g.dstride & 3) == 0) {
-        // the row holds round4(dw) bytes: dstride >= dw and a multiple of 4
-        *reinterpret_cast<u32 *>(dst) = (u32)out[0][0] | (u32)out[1][0] << 8 | (u32)out[2][0] << 16 | (u32)out[3][0] << 24;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (x4 + k < g.dw) {
-#pragma unroll
-                for (int c = 0; c < OC; ++c) dst[OC * k + c] = (uint8_t)out[k][c];
-            }
-    }
-}
-
-// nearest: one output pixel per lane; strides of src and dst in elements of T
-template <typename T, int CH>
-__global__ __launch_bounds__(256) void k_remap_nearest(RemapFrames F, RemapGeom g)
-{
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.z;
-    if (x >= g.dw) return;
-    const u32 xy = reinterpret_cast<const u32 *>(F.xy[blockIdx.y])[(size_t)y * g.dw + x];
-    const int sx = (int16_t)(xy & 0xFFFF), sy = (int16_t)(xy >> 16);
-    const bool in = (unsigned)sx < (unsigned)g.sw && (unsigned)sy < (unsigned)g.sh;
-    const T *s = reinterpret_cast<const T *>(F.src[blockIdx.y]) + (size_t)(in ? sy : 0) * g.sstride + CH * (in ? sx : 0);
-    T *d = reinterpret_cast<T *>(F.dst[blockIdx.y]) + (size_t)y * g.dstride + CH * x;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) d[c] = in ? s[c] : (T)g.border;
-}
-
-// cvRound of an f32 to int32: half to even, saturating; NaN -> INT32_MIN (both far outside every image)
-__device__ __forceinline__ int remap_round(float v)
-{
-    if (v != v) return INT32_MIN;
-    const float r = rintf(v);
-    if (r >= 2147483648.0f) return INT32_MAX;
-    if (r <= -2147483648.0f) return INT32_MIN;
-    return (int)r;
-}
-__device__ __forceinline__ int remap_sat16(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
-
-// cv2.convertMaps(mapx, mapy, CV_16SC2, nninterpolation = nn): one map entry per lane
-__global__ __launch_bounds__(256) void k_convert_maps(const float *__restrict__ mapx, const float *__restrict__ mapy, int n, int nn,
-                                                      u32 *__restrict__ xy, uint16_t *__restrict__ alpha)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    int x, y, a = 0;
-    if (nn) {
-        x = remap_sat16(remap_round(mapx[i]));
-        y = remap_sat16(remap_round(mapy[i]));
-    } else {
-        const int sx = remap_round(mapx[i] * 32.0f), sy = remap_round(mapy[i] * 32.0f);
-        x = remap_sat16(sx >> 5);
-        y = remap_sat16(sy >> 5);
-        a = (sy & 31) * 32 + (sx & 31);
-    }
-    xy[i] = (u32)(x & 0xFFFF) | (u32)(y & 0xFFFF) << 16;
-    alpha[i] = (uint16_t)a;
-}
-
-// one remap launch for n frames of equal geometry on stream st.  channels / gray: 1 -> gray plane, 3 + gray -> the stage
-// (gray output), 3 -> 3-channel output
-static int remap_launch(hipStream_t st, const RemapFrames &F, int n, const RemapGeom &g, int channels, bool gray, int flags)
-{
-    bool aligned = g.dw % 4 == 0;
-    for (int f = 0; f < n; ++f) aligned = aligned && ((uintptr_t)F.xy[f]) % 16 == 0 && ((uintptr_t)F.alpha[f]) % 8 == 0;
-    const int quads = (g.dw + 3) / 4;
-    auto kern = channels == 1 ? (aligned ? k_remap_u8<1, false, true> : k_remap_u8<1, false, false>)
-                : gray        ? (aligned ? k_remap_u8<3, true, true> : k_remap_u8<3, true, false>)
-                              : (aligned ? k_remap_u8<3, false, true> : k_remap_u8<3, false, false>);
-    hipLaunchKernelGGL(kern, dim3((quads * g.dh + 255) / 256, n), dim3(256), 0, st, F, g, flags);
-    HIP_TRY(hipGetLastError());
-    return RELOC_OK;
-}
-
-// depth (uint16 millimetres, dense rows of w) of a context with a rectification map through the map, nearest, border 0 =
-// "no depth", into the context's depth plane (reloc_record_frame, reloc_tick_accumulate_dev)
-int rectify_depth(reloc_ctx *ctx, const uint16_t *depth_dev, int w, int h, const uint16_t **out)
-{
-    if (w != ctx->rect_w || h != ctx->rect_h) {
-        reloc_set_error("frame %dx%d differs from the rectification map %dx%d (reloc_set_rectify_map)", w, h, ctx->rect_w, ctx->rect_h);
-        return RELOC_E_ARG;
-    }
-    RemapFrames F = {};
-    F.src[0] = (const uint8_t *)depth_dev; F.xy[0] = ctx->rect_xy; F.dst[0] = (uint8_t *)ctx->rect_depth;
-    const RemapGeom g = {w, h, w, w, h, w, 0};
-    hipLaunchKernelGGL((k_remap_nearest<uint16_t, 1>), dim3((w + 255) / 256, 1, h), dim3(256), 0, ctx->stream, F, g);
-    HIP_TRY(hipGetLastError());
-    *out = ctx->rect_depth;
-    return RELOC_OK;
-}
-
-// ---- resize: cv2.resize (include/reloc_spec.h, "RESIZE") ---------------------------------------------------
-// OpenCV's 8-bit resize.  The per-axis tables (offsets, coefficients, tap lists) are built on the host exactly as the spec
-// states them (resize_plan); the kernels do integer or f32 arithmetic on table entries only, so host and device cannot
-// disagree on a floor.
-//   k_resize_area<CH, GRAY, KIND>  INTER_AREA, downscale: 4 adjacent output pixels per lane.  KIND: exact 2x2 boxes, integer
-//                                  iscale_x x iscale_y boxes (partial boxes at the right / bottom edge included), or per-axis
-//                                  tap lists (first tap, count, f32 alphas).  GRAY (CH = 3): gray_fixed of every source pixel
-//                                  before the sum, one dword store -- the stage in front of ORB.
-//   k_resize_linear<CH>            INTER_LINEAR, 11 coefficient bits, one output pixel per lane
-//   k_resize_nearest<T, CH>        INTER_NEAREST, one output pixel per lane; T = uint16_t for the depth image
-// All are frame-batched (blockIdx.y = frame) with per-frame table pointers; a single frame is a batch of one.
-enum { RESIZE_AREA_2X2 = 0, RESIZE_AREA_INT = 1, RESIZE_AREA_TAB = 2, RESIZE_LINEAR = 3, RESIZE_NEAREST = 4 };
-struct ResizeFrames {
-    const uint8_t *src[RELOC_BATCH_MAX]; const int32_t *tab[RELOC_BATCH_MAX]; uint8_t *dst[RELOC_BATCH_MAX];
-};
-struct ResizeGeom {
-    int sw, sh, sstride;   // source size, row stride in bytes (k_resize_nearest: in elements of T)
-    int dw, dh, dstride;   // destination size and row stride, likewise
-    int isx, isy;          // integer kinds: the box
-    float inv_area;        // 1.f / (isx * isy)
-    int aligned;           // source rows start on dwords (base and stride multiples of 4; integer kind: isx % 4 == 0 as well)
-};
-
-// saturate_cast<uchar>(float): cvRound (half to even), then the clamp
-__device__ __forceinline__ int resize_sat_u8(float v)
-{
-    const int r = (int)rintf(v);
-    return r < 0 ? 0 : (r > 255 ? 255 : r);
-}
-
-// byte b of a row segment held as dwords (b is a constant after unrolling)
-#define RESIZE_BYTE(w, b) (int)(((w)[(b) >> 2] >> (8 * ((b) & 3))) & 255u)
-
-// NW dwords of a source row from p, of which `valid` bytes belong to the row; the rest reads as 0.  aligned: p is a
-// multiple of 4 and so is the row stride, so a dword that holds a valid byte ends within the row's stride
-template <int NW>
-__device__ __forceinline__ void resize_row_words(const uint8_t *__restrict__ p, int valid, bool aligned, u32 (&w)[NW])
-{
-    if (aligned) {
-#pragma unroll
-        for (int i = 0; i < NW; ++i) w[i] = 4 * i < valid ? reinterpret_cast<const u32 *>(p)[i] : 0u;
-    } else {
-#pragma unroll
-        for (int i = 0; i < NW; ++i) {
-            u32 v = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-                if (4 * i + b < valid) v |= (u32)p[4 * i + b] << (8 * b);
-            w[i] = v;
-        }
-    }
-}
-
-// pixel j of a row segment held as dwords
-template <int CH, bool GRAY, int NW>
-__device__ __forceinline__ void resize_word_px(const u32 (&w)[NW], int j, int flags, int (&v)[GRAY ? 1 : CH])
-{
-    if (GRAY) {
-        const int c0 = RESIZE_BYTE(w, 3 * j), c1 = RESIZE_BYTE(w, 3 * j + 1), c2 = RESIZE_BYTE(w, 3 * j + 2);
-        v[0] = gray_fixed((flags & 1) ? c2 : c0, c1, (flags & 1) ? c0 : c2, flags);
-    } else {
-#pragma unroll
-        for (int c = 0; c < CH; ++c) v[c] = RESIZE_BYTE(w, CH * j + c);
-    }
-}
-
-// the pixel at p, byte by byte
-template <int CH, bool GRAY>
-__device__ __forceinline__ void resize_px(const uint8_t *__restrict__ p, int flags, int (&v)[GRAY ? 1 : CH])
-{
-    if (GRAY) {
-        const int c0 = p[0], c1 = p[1], c2 = p[2];
-        v[0] = gray_fixed((flags & 1) ? c2 : c0, c1, (flags & 1) ? c0 : c2, flags);
-    } else {
-#pragma unroll
-        for (int c = 0; c < CH; ++c) v[c] = p[c];
-    }
-}
-
-template <int CH, bool GRAY, int KIND>
-__global__ __launch_bounds__(256) void k_resize_area(ResizeFrames F, ResizeGeom g, int flags)
-{
-    constexpr int OC = GRAY ? 1 : CH;       // output channels
-    const int quads = (g.dw + 3) >> 2;
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= quads * g.dh) return;
-    const int y = q / quads, x4 = 4 * (q - y * quads);
-    const uint8_t *src = F.src[blockIdx.y];
-    int out[4][OC];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int c = 0; c < OC; ++c) out[k][c] = 0;
-    if (KIND == RESIZE_AREA_2X2) {
-        // every box lies inside the source (2 dw <= sw, 2 dh <= sh): (a + b + c + d + 2) >> 2.  Eight source pixels per row
-        constexpr int NW = 2 * CH;
-        const int valid = (g.sw - 2 * x4) * CH;
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            u32 w[NW];
-            resize_row_words<NW>(src + (size_t)(2 * y + r) * g.sstride + (size_t)2 * x4 * CH, valid, g.aligned, w);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                int v[OC];
-                resize_word_px<CH, GRAY, NW>(w, j, flags, v);
-#pragma unroll
-                for (int c = 0; c < OC; ++c) out[j >> 1][c] += v[c];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int c = 0; c < OC; ++c) out[k][c] = (out[k][c] + 2) >> 2;
-    } else if (KIND == RESIZE_AREA_INT) {
-        const int y0 = y * g.isy, ny = max(0, min(g.isy, g.sh - y0));
-        const bool is22 = g.isx == 2 && g.isy == 2;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int x0 = (x4 + k) * g.isx, nx = x4 + k < g.dw ? max(0, min(g.isx, g.sw - x0)) : 0;
-            const int count = nx * ny;
-            if (count == 0) continue;           // a box that starts outside the source: 0
-            int sum[OC];
-#pragma unroll
-            for (int c = 0; c < OC; ++c) sum[c] = 0;
-            for (int r = 0; r < ny; ++r) {
-                const uint8_t *row = src + (size_t)(y0 + r) * g.sstride + (size_t)x0 * CH;
-                if (g.aligned && nx == g.isx) {     // isx % 4 == 0: groups of four pixels = CH dwords
-                    for (int j = 0; j < nx; j += 4) {
-                        u32 w[CH];
-#pragma unroll
-                        for (int i = 0; i < CH; ++i) w[i] = reinterpret_cast<const u32 *>(row + (size_t)j * CH)[i];
-#pragma unroll
-                        for (int p = 0; p < 4; ++p) {
-                            int v[OC];
-                            resize_word_px<CH, GRAY, CH>(w, p, flags, v);
-#pragma unroll
-                            for (int c = 0; c < OC; ++c) sum[c] += v[c];
-                        }
-                    }
-                } else {
-                    for (int j = 0; j < nx; ++j) {
-                        int v[OC];
-                        resize_px<CH, GRAY>(row + (size_t)j * CH, flags, v);
-#pragma unroll
-                        for (int c = 0; c < OC; ++c) sum[c] += v[c];
-                    }
-                }
-            }
-            const bool inside = nx == g.isx && ny == g.isy;
-#pragma unroll
-            for (int c = 0; c < OC; ++c) {
-                if (inside) out[k][c] = is22 ? (sum[c] + 2) >> 2 : resize_sat_u8(__fmul_rn((float)sum[c], g.inv_area));
-                else        out[k][c] = resize_sat_u8(__fdiv_rn((float)sum[c], (float)count));
-            }
-        }
-    } else {
-        // tap lists: [x first dw][x count dw][x alpha offset dw][y first dh][y count dh][y alpha offset dh][f32 alphas]
-        const int32_t *tab = F.tab[blockIdx.y];
-        const float *al = reinterpret_cast<const float *>(tab);
-        const int32_t *ty = tab + 3 * g.dw;
-        const int yf = ty[y], yc = ty[g.dh + y], ya = ty[2 * g.dh + y];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (x4 + k >= g.dw) continue;
-            const int xf = tab[x4 + k], xc = tab[g.dw + x4 + k], xa = tab[2 * g.dw + x4 + k];
-            float acc[OC];
-#pragma unroll
-            for (int c = 0; c < OC; ++c) acc[c] = 0.f;
-            for (int t = 0; t < yc; ++t) {
-                const float beta = al[ya + t];
-                const uint8_t *row = src + (size_t)(yf + t) * g.sstride + (size_t)xf * CH;
-                float buf[OC];
-#pragma unroll
-                for (int c = 0; c < OC; ++c) buf[c] = 0.f;
-                for (int u = 0; u < xc; ++u) {
-                    const float a = al[xa + u];
-                    int v[OC];
-                    resize_px<CH, GRAY>(row + (size_t)u * CH, flags, v);
-#pragma unroll
-                    for (int c = 0; c < OC; ++c) buf[c] = __fadd_rn(buf[c], __fmul_rn((float)v[c], a));
-                }
-#pragma unroll
-                for (int c = 0; c < OC; ++c) acc[c] = t == 0 ? __fmul_rn(beta, buf[c]) : __fadd_rn(acc[c], __fmul_rn(beta, buf[c]));
-            }
-#pragma unroll
-            for (int c = 0; c < OC; ++c) out[k][c] = resize_sat_u8(acc[c]);
-        }
-    }
-    uint8_t *dst = F.dst[blockIdx.y] + (size_t)y * g.dstride + OC * x4;
-    if (OC == 1 && (g.dstride & 3) == 0) {
-        // the row holds round4(dw) bytes: dstride >= dw and a multiple of 4
-        *reinterpret_cast<u32 *>(dst) = (u32)out[0][0] | (u32)out[1][0] << 8 | (u32)out[2][0] << 16 | (u32)out[3][0] << 24;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (x4 + k < g.dw) {
-#pragma unroll
-                for (int c = 0; c < OC; ++c) dst[OC * k + c] = (uint8_t)out[k][c];
-            }
-    }
-}
-
-// table: [x offset dw][a0 | a1 << 16 dw][row 0 dh][row 1 dh][b0 | b1 << 16 dh], the rows already clipped to the source
-template <int CH>
-__global__ __launch_bounds__(256) void k_resize_linear(ResizeFrames F, ResizeGeom g)
-{
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.z;
-    if (x >= g.dw) return;
-    const int32_t *tab = F.tab[blockIdx.y], *ty = tab + 2 * g.dw;
-    const int sx = tab[x], sx1 = min(sx + 1, g.sw - 1);
-    const u32 ca = (u32)tab[g.dw + x], cb = (u32)ty[2 * g.dh + y];
-    const int a0 = ca & 0xFFFF, a1 = ca >> 16, b0 = cb & 0xFFFF, b1 = cb >> 16;
-    const uint8_t *r0 = F.src[blockIdx.y] + (size_t)ty[y] * g.sstride, *r1 = F.src[blockIdx.y] + (size_t)ty[g.dh + y] * g.sstride;
-    uint8_t *d = F.dst[blockIdx.y] + (size_t)y * g.dstride + CH * x;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-        const int h0 = r0[CH * sx + c] * a0 + r0[CH * sx1 + c] * a1, h1 = r1[CH * sx + c] * a0 + r1[CH * sx1 + c] * a1;
-        d[c] = (uint8_t)((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2);
-    }
-}
-
-// table: [x offset dw][y offset dh]; strides of src and dst in elements of T
-template <typename T, int CH>
-__global__ __launch_bounds__(256) void k_resize_nearest(ResizeFrames F, ResizeGeom g)
-{
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.z;
-    if (x >= g.dw) return;
-    const int32_t *tab = F.tab[blockIdx.y];
-    const T *s = reinterpret_cast<const T *>(F.src[blockIdx.y]) + (size_t)tab[g.dw + y] * g.sstride + CH * tab[x];
-    T *d = reinterpret_cast<T *>(F.dst[blockIdx.y]) + (size_t)y * g.dstride + CH * x;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) d[c] = s[c];
-}
-
-// What one resize does: the kernel kind, the integer box and the table words (host).  Built from the spec's rules in double
-// with alphas stored as f32; every source index in a table lies inside the source.
-struct ResizePlan {
-    int kind = -1, isx = 1, isy = 1;
-    std::vector<int32_t> tab;
-};
-
-static inline int32_t resize_f32_bits(float v) { int32_t b; memcpy(&b, &v, 4); return b; }
-static inline int resize_clampi(double v, int lo, int hi) { return v < (double)lo ? lo : (v > (double)hi ? hi : (int)v); }
-
-// INTER_AREA tap list of one axis, appended to `first`, `count`, `alpha` (offsets into alpha are per axis)
-static void resize_area_axis(int ss, int ds, double scale, std::vector<int32_t> &first, std::vector<int32_t> &count,
-                             std::vector<int32_t> &aoff, std::vector<float> &alpha)
-{
-    for (int d = 0; d < ds; ++d) {
-        const double f1 = d * scale, f2 = f1 + scale, cell = std::min(scale, ss - f1);
-        int s1 = resize_clampi(ceil(f1), 0, ss - 1);
-        const int s2 = std::min(resize_clampi(floor(f2), 0, ss), ss - 1);
-        s1 = std::min(s1, s2);
-        const size_t a0 = alpha.size();
-        int f = s1;
-        if (s1 - f1 > 1e-3 && s1 >= 1) { f = s1 - 1; alpha.push_back((float)((s1 - f1) / cell)); }
-        for (int s = s1; s < s2; ++s) alpha.push_back((float)(1.0 / cell));
-        if (f2 - s2 > 1e-3) alpha.push_back((float)(std::min(std::min(f2 - s2, 1.0), cell) / cell));
-        first.push_back(f);
-        count.push_back((int32_t)(alpha.size() - a0));
-        aoff.push_back((int32_t)a0);
-    }
-}
-
-// INTER_LINEAR of one axis: source index (not clipped) and the 11-bit weights of it and of its successor
-static void resize_linear_axis(int ss, int ds, double scale, bool zero_at_edges, std::vector<int32_t> &ofs, std::vector<int32_t> &coef)
-{
-    for (int d = 0; d < ds; ++d) {
-        float f = (float)((d + 0.5) * scale - 0.5);
-        const float fl = floorf(f);
-        int s = resize_clampi((double)fl, -2, ss);      // an index outside [-1, ss - 1] behaves like the nearest edge
-        f -= fl;
-        if (zero_at_edges) {
-            if (s < 0) { s = 0; f = 0.f; }
-            if (s >= ss - 1) { s = ss - 1; f = 0.f; }
-        }
-        const int c0 = (int)lrintf((1.f - f) * 2048.f), c1 = (int)lrintf(f * 2048.f);
-        ofs.push_back(s);
-        coef.push_back((int32_t)((uint32_t)(c0 & 0xFFFF) | (uint32_t)(c1 & 0xFFFF) << 16));
-    }
-}
-
-static int resize_plan(int sw, int sh, int dw, int dh, double inv_x, double inv_y, int interpolation, ResizePlan &P)
-{
-    if (inv_x == 0.0) inv_x = (double)dw / sw;
-    if (inv_y == 0.0) inv_y = (double)dh / sh;
-    if (!(inv_x > 0.0 && inv_y > 0.0 && inv_x - inv_x == 0.0 && inv_y - inv_y == 0.0)) {
-        reloc_set_error("bad argument: resize: the scale factors must be positive and finite");
-        return RELOC_E_ARG;
-    }
-    const double scx = 1.0 / inv_x, scy = 1.0 / inv_y;
-    std::vector<int32_t> &T = P.tab;
-    T.clear();
-    if (interpolation == 0) {
-        P.kind = RESIZE_NEAREST;
-        for (int d = 0; d < dw; ++d) T.push_back(resize_clampi(floor(d * scx), 0, sw - 1));
-        for (int d = 0; d < dh; ++d) T.push_back(resize_clampi(floor(d * scy), 0, sh - 1));
-        return RELOC_OK;
-    }
-    const int isx = resize_clampi(rint(scx), 0, 1 << 30), isy = resize_clampi(rint(scy), 0, 1 << 30);
-    const bool area_fast = fabs(scx - isx) < DBL_EPSILON && fabs(scy - isy) < DBL_EPSILON;
-    if (interpolation == 1 && area_fast && isx == 2 && isy == 2) interpolation = 3;
-    if (interpolation == 3) {
-        if (!(scx >= 1.0 && scy >= 1.0)) {
-            reloc_set_error("bad argument: resize: INTER_AREA is implemented for downscaling on both axes only");
-            return RELOC_E_ARG;
-        }
-        if (scx > 2.0 * sw || scy > 2.0 * sh) {     // no destination size rounds to >= 1 from such a factor
-            reloc_set_error("bad argument: resize: INTER_AREA: a scale factor shrinks the source below half a pixel");
-            return RELOC_E_ARG;
-        }
-        if (area_fast) {
-            P.isx = isx; P.isy = isy;
-            P.kind = isx == 2 && isy == 2 && 2 * (int64_t)dw <= sw && 2 * (int64_t)dh <= sh ? RESIZE_AREA_2X2 : RESIZE_AREA_INT;
-            return RELOC_OK;
-        }
-        if ((dw - 1) * scx >= sw || (dh - 1) * scy >= sh) {
-            reloc_set_error("bad argument: resize: INTER_AREA: the destination reaches beyond the scaled source");
-            return RELOC_E_ARG;
-        }
-        P.kind = RESIZE_AREA_TAB;
-        std::vector<int32_t> xf, xc, xa, yf, yc, ya;
-        std::vector<float> ax, ay;
-        resize_area_axis(sw, dw, scx, xf, xc, xa, ax);
-        resize_area_axis(sh, dh, scy, yf, yc, ya, ay);
-        const int32_t base_x = 3 * (dw + dh), base_y = base_x + (int32_t)ax.size();
-        for (int d = 0; d < dw; ++d) { xa[d] += base_x; if (xf[d] + xc[d] > sw) xc[d] = sw - xf[d]; }
-        for (int d = 0; d < dh; ++d) { ya[d] += base_y; if (yf[d] + yc[d] > sh) yc[d] = sh - yf[d]; }
-        for (auto *v : {&xf, &xc, &xa, &yf, &yc, &ya}) T.insert(T.end(), v->begin(), v->end());
-        for (float a : ax) T.push_back(resize_f32_bits(a));
-        for (float a : ay) T.push_back(resize_f32_bits(a));
-        return RELOC_OK;
-    }
-    if (interpolation == 1) {
-        P.kind = RESIZE_LINEAR;
-        std::vector<int32_t> xo, xc, yo, yc;
-        resize_linear_axis(sw, dw, scx, true, xo, xc);
-        resize_linear_axis(sh, dh, scy, false, yo, yc);
-        T.insert(T.end(), xo.begin(), xo.end());
-        T.insert(T.end(), xc.begin(), xc.end());
-        for (int d = 0; d < dh; ++d) T.push_back(std::min(std::max(yo[d], 0), sh - 1));
-        for (int d = 0; d < dh; ++d) T.push_back(std::min(std::max(yo[d] + 1, 0), sh - 1));
-        T.insert(T.end(), yc.begin(), yc.end());
-        return RELOC_OK;
-    }
-    reloc_set_error("bad argument: resize: only INTER_NEAREST (0), INTER_LINEAR (1) and INTER_AREA (3) are implemented");
-    return RELOC_E_ARG;
-}
-
-// one resize launch for n frames of equal geometry on stream st.  elem: bytes per channel value (2 = the 16-bit nearest);
-// gray: 3-channel source, gray output (the stage, area kinds only)
-static int resize_launch(hipStream_t st, const ResizeFrames &F, int n, const ResizePlan &P, int sw, int sh, int sstride, int dw,
-                         int dh, int dstride, int channels, int elem, bool gray, int flags)
-{
-    ResizeGeom g = {sw, sh, sstride, dw, dh, dstride, P.isx, P.isy, 1.f / (float)(P.isx * P.isy), 0};
-    if (P.kind == RESIZE_NEAREST) {
-        auto kern = elem == 2 ? k_resize_nearest<uint16_t, 1> : channels == 1 ? k_resize_nearest<uint8_t, 1> : k_resize_nearest<uint8_t, 3>;
-        hipLaunchKernelGGL(kern, dim3((dw + 255) / 256, n, dh), dim3(256), 0, st, F, g);
-    } else if (P.kind == RESIZE_LINEAR) {
-        hipLaunchKernelGGL(channels == 1 ? k_resize_linear<1> : k_resize_linear<3>, dim3((dw + 255) / 256, n, dh), dim3(256), 0, st, F, g);
-    } else {
-        bool aligned = sstride % 4 == 0 && (P.kind != RESIZE_AREA_INT || P.isx % 4 == 0);
-        for (int f = 0; f < n; ++f) aligned = aligned && ((uintptr_t)F.src[f]) % 4 == 0;
-        g.aligned = aligned;
-        const dim3 grid((((dw + 3) / 4) * dh + 255) / 256, n);
-#define RESIZE_AREA_KERN(KIND) (channels == 1 ? k_resize_area<1, false, KIND> : gray ? k_resize_area<3, true, KIND> : k_resize_area<3, false, KIND>)
-        auto kern = P.kind == RESIZE_AREA_2X2 ? RESIZE_AREA_KERN(RESIZE_AREA_2X2)
-                    : P.kind == RESIZE_AREA_INT ? RESIZE_AREA_KERN(RESIZE_AREA_INT) : RESIZE_AREA_KERN(RESIZE_AREA_TAB);
-#undef RESIZE_AREA_KERN
-        hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, F, g, flags);
-    }
-    HIP_TRY(hipGetLastError());
-    return RELOC_OK;
-}
-
-// depth (uint16 millimetres, dense rows of w) of a context with the downscale stage on, INTER_NEAREST to the working size,
-// into the context's depth plane (reloc_record_frame, reloc_tick_accumulate_dev)
-int resize_depth(reloc_ctx *ctx, const uint16_t *depth_dev, int w, int h, const uint16_t **out)
-{
-    if (w != ctx->rsz_sw || h != ctx->rsz_sh) {
-        reloc_set_error("frame %dx%d differs from the source size %dx%d of the downscale stage (reloc_set_resize)", w, h, ctx->rsz_sw, ctx->rsz_sh);
-        return RELOC_E_ARG;
-    }
-    ResizeFrames F = {};
-    F.src[0] = (const uint8_t *)depth_dev; F.tab[0] = ctx->rsz_ntab; F.dst[0] = (uint8_t *)ctx->rsz_depth;
-    ResizePlan P;
-    P.kind = RESIZE_NEAREST;
-    if (int rc = resize_launch(ctx->stream, F, 1, P, w, h, w, ctx->rsz_dw, ctx->rsz_dh, ctx->rsz_dw, 1, 2, false, 0)) return rc;
-    *out = ctx->rsz_depth;
-    return RELOC_OK;
-}
-
 // what the five ORB kernels read and write of a context, for the source frame src
 static OrbFrame orb_frame(const reloc_ctx *c, const uint8_t *src)
 {
@@ -2009,35 +1167,17 @@ static OrbFrame orb_frame(const reloc_ctx *c, const uint8_t *src)
     return F;
 }
 
-// Five launches (plus one of the downscale stage, one of the rectification and two of CLAHE): the frames are of equal
-// geometry.  3-channel frames of contexts with the downscale stage on (reloc_set_resize) are converted to gray and resized
-// (INTER_AREA) first, and everything downstream sees the working frame dw x dh; those of
-// contexts with a rectification map (reloc_set_rectify_map) are converted to gray and remapped first, those of contexts
-// with CLAHE on (reloc_set_clahe) equalised next; the pyramid then reads the last plane written.  The pyramid runs 512-thread workgroups
-// for latency, 256 where it shares the chip with whole-database scans.
+// Five launches behind the image chain (reloc_image.hip): the frames are of equal geometry.  The chain serves 3-channel
+// frames only, never a caller's gray plane; with the downscale stage on, w x h is the source size and everything from
+// orb_prepare on sees the working frame.  The pyramid reads the last plane the chain wrote, or the frame itself.  It runs
+// 512-thread workgroups for latency, 256 where it shares the chip with whole-database scans.
 int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, int h, int stride, int channels, int order,
             int nfeatures, bool latency)
 {
     if (n < 1 || n > RELOC_BATCH_MAX) { reloc_set_error("orb: 1..%d frames", RELOC_BATCH_MAX); return RELOC_E_ARG; }
     reloc_ctx *c0 = ctxs[0];
-    const bool frame = channels == 3;      // the image stages serve 3-channel frames only, never a caller's gray plane
-    const bool resize = frame && c0->rsz_dw > 0;
     const int sw = w, sh = h;               // the frame as handed in; w x h becomes the working frame
-    for (int f = 0; f < n; ++f) {
-        const reloc_ctx *c = ctxs[f];
-        if (c->rsz_sw != c0->rsz_sw || c->rsz_sh != c0->rsz_sh || c->rsz_dw != c0->rsz_dw || c->rsz_dh != c0->rsz_dh) {
-            reloc_set_error("orb batch: contexts with and without the downscale stage, or with unequal sizes (reloc_set_resize)");
-            return RELOC_E_STATE;
-        }
-    }
-    if (resize) {
-        if (w != c0->rsz_sw || h != c0->rsz_sh) {
-            reloc_set_error("frame %dx%d differs from the source size %dx%d of the downscale stage (reloc_set_resize)", w, h, c0->rsz_sw, c0->rsz_sh);
-            return RELOC_E_ARG;
-        }
-        w = c0->rsz_dw; h = c0->rsz_dh;
-        if (w < 64 || h < 64) { reloc_set_error("bad argument: the working frame %dx%d of the downscale stage is below 64x64", w, h); return RELOC_E_ARG; }
-    }
+    if (int rc = image_chain_check(ctxs, n, channels, &w, &h)) return rc;
     for (int f = 0; f < n; ++f) {
         reloc_ctx *c = ctxs[f];
         if (int rc = orb_prepare(c, w, h, nfeatures)) return rc;
@@ -2046,59 +1186,16 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
             reloc_set_error("orb batch: contexts of unequal geometry");
             return RELOC_E_STATE;
         }
-        if (c->rect_w != c0->rect_w || c->rect_h != c0->rect_h) {
-            reloc_set_error("orb batch: contexts with and without a rectification map, or with maps of unequal size (reloc_set_rectify_map)");
-            return RELOC_E_STATE;
-        }
-        if (c->clahe_tx != c0->clahe_tx || c->clahe_ty != c0->clahe_ty || c->clahe_clip != c0->clahe_clip) {
-            reloc_set_error("orb batch: contexts of unequal CLAHE settings (reloc_set_clahe)");
-            return RELOC_E_STATE;
-        }
-    }
-    if (frame && c0->rect_w > 0 && (w != c0->rect_w || h != c0->rect_h)) {
-        reloc_set_error("frame %dx%d differs from the rectification map %dx%d (reloc_set_rectify_map)", w, h, c0->rect_w, c0->rect_h);
-        return RELOC_E_ARG;
+        if (int rc = image_chain_check_prepared(ctxs, f, n, channels, w, h)) return rc;
     }
     const OrbTable *tab_h = (const OrbTable *)c0->orb_tab_host;
     const int flags = gray_flags(c0, order);
     hipStream_t st = c0->stream;
     reloc_prof_begin(c0, RELOC_PROF_ORB);
-    const uint8_t *zplanes[RELOC_BATCH_MAX], *rplanes[RELOC_BATCH_MAX], *planes[RELOC_BATCH_MAX];
-    if (resize) {
-        ResizeFrames F = {};
-        for (int f = 0; f < n; ++f) { F.src[f] = srcs[f]; F.tab[f] = ctxs[f]->rsz_tab; F.dst[f] = ctxs[f]->rsz_plane; zplanes[f] = F.dst[f]; }
-        ResizePlan P;
-        P.kind = c0->rsz_kind; P.isx = c0->rsz_isx; P.isy = c0->rsz_isy;
-        const int cs = clahe_stride(w);
-        if (int rc = resize_launch(st, F, n, P, sw, sh, stride, w, h, cs, 3, 1, true, flags)) {
-            reloc_prof_end(c0, RELOC_PROF_ORB);
-            return rc;
-        }
-        srcs = zplanes; stride = cs; channels = 1;
-    }
-    if (frame && c0->rect_w > 0) {
-        RemapFrames F = {};
-        for (int f = 0; f < n; ++f) {
-            F.src[f] = srcs[f]; F.xy[f] = ctxs[f]->rect_xy; F.alpha[f] = ctxs[f]->rect_alpha; F.dst[f] = ctxs[f]->rect_plane;
-            rplanes[f] = F.dst[f];
-        }
-        const int cs = clahe_stride(w);
-        const RemapGeom g = {w, h, stride, w, h, cs, 0};
-        if (int rc = remap_launch(st, F, n, g, channels, channels == 3, flags)) {
-            reloc_prof_end(c0, RELOC_PROF_ORB);
-            return rc;
-        }
-        srcs = rplanes; stride = cs; channels = 1;
-    }
-    if (frame && c0->clahe_tx > 0) {
-        ClaheFrames F = {};
-        for (int f = 0; f < n; ++f) { F.src[f] = srcs[f]; F.lut[f] = ctxs[f]->clahe_lut; F.dst[f] = ctxs[f]->clahe_plane; planes[f] = F.dst[f]; }
-        const int cs = clahe_stride(w);
-        if (int rc = clahe_launch(st, F, n, clahe_geom(w, h, c0->clahe_clip, c0->clahe_tx, c0->clahe_ty), channels, stride, flags, cs)) {
-            reloc_prof_end(c0, RELOC_PROF_ORB);
-            return rc;
-        }
-        srcs = planes; stride = cs; channels = 1;
+    const uint8_t *planes[RELOC_BATCH_MAX];
+    if (int rc = image_chain_gray(ctxs, n, &srcs, sw, sh, w, h, &stride, &channels, flags, planes)) {
+        reloc_prof_end(c0, RELOC_PROF_ORB);
+        return rc;
     }
     bool aligned = w % 4 == 0 && stride % 4 == 0;
     for (int f = 0; f < n; ++f) aligned = aligned && ((uintptr_t)srcs[f]) % 4 == 0;
@@ -2132,24 +1229,6 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
     }
     reloc_prof_end(c0, RELOC_PROF_ORB);
     HIP_TRY(hipGetLastError());
-    return RELOC_OK;
-}
-
-
-// ------------------------------------------------------------------------------------------------
-RELOC_API int reloc_gray_u8(reloc_ctx *ctx, const uint8_t *img, int w, int h, int stride, int order, uint8_t *gray)
-{
-    ARG_CHECK_CTX(ctx, img && gray && w > 0 && h > 0 && stride >= 3 * w, "reloc_gray_u8");
-    if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
-    void *dout;
-    int rc;
-    if ((rc = reloc_scratch(ctx, 0, (int64_t)w * h, &dout))) return rc;
-    HIP_TRY(hipMemcpy2DAsync(ctx->frame_img, (size_t)w * 3, img, stride, (size_t)w * 3, h, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_gray_plain, dim3((w + 255) / 256, h), dim3(256), 0, ctx->stream, ctx->frame_img, w, h, w * 3, gray_flags(ctx, order),
-                       (uint8_t *)dout);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(gray, dout, (size_t)w * h, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return RELOC_OK;
 }
 
@@ -2201,273 +1280,5 @@ RELOC_API int reloc_frame_debug_plane(reloc_ctx *ctx, int what, int level, uint8
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     *w = L.w;
     *h = L.h;
-    return RELOC_OK;
-}
-
-// ---- CLAHE entry points -------------------------------------------------------------------------------
-static bool clahe_args_ok(double clip_limit, int tiles_x, int tiles_y)
-{
-    return clip_limit - clip_limit == 0.0 && tiles_x >= 1 && tiles_x <= CLAHE_MAX_TILES && tiles_y >= 1 && tiles_y <= CLAHE_MAX_TILES;
-}
-
-RELOC_API int reloc_set_clahe(reloc_ctx *ctx, double clip_limit, int tiles_x, int tiles_y)
-{
-    ARG_CHECK_CTX(ctx, true, "ctx is NULL");
-    if (tiles_x == 0 && tiles_y == 0) {
-        ctx->clahe_clip = 0.0;
-        ctx->clahe_tx = ctx->clahe_ty = 0;
-        return RELOC_OK;
-    }
-    ARG_CHECK(clahe_args_ok(clip_limit, tiles_x, tiles_y),
-              "reloc_set_clahe: tiles_x and tiles_y must both be 0 (off) or both in 1..64, and clip_limit finite");
-    if (!ctx->clahe_plane) {
-        // first enable: the plane of the largest frame and the LUTs of the largest grid
-        HIP_TRY(hipMalloc((void **)&ctx->clahe_plane, (size_t)clahe_stride(ctx->max_w) * ctx->max_h));
-        const hipError_t e = hipMalloc((void **)&ctx->clahe_lut, (size_t)CLAHE_MAX_TILES * CLAHE_MAX_TILES * 256);
-        if (e != hipSuccess) {
-            (void)hipFree(ctx->clahe_plane);
-            ctx->clahe_plane = nullptr;
-            HIP_TRY(e);
-        }
-    }
-    ctx->clahe_clip = clip_limit == 0.0 ? 0.0 : clip_limit;     // -0 -> +0: equal settings compare equal
-    ctx->clahe_tx = tiles_x;
-    ctx->clahe_ty = tiles_y;
-    return RELOC_OK;
-}
-
-RELOC_API int reloc_get_clahe(reloc_ctx *ctx, double *clip_limit, int32_t *tiles_x, int32_t *tiles_y)
-{
-    ARG_CHECK_CTX(ctx, clip_limit && tiles_x && tiles_y, "reloc_get_clahe");
-    *clip_limit = ctx->clahe_clip;
-    *tiles_x = ctx->clahe_tx;
-    *tiles_y = ctx->clahe_ty;
-    return RELOC_OK;
-}
-
-RELOC_API int reloc_clahe_u8(reloc_ctx *ctx, const uint8_t *gray, int w, int h, int stride, double clip_limit, int tiles_x,
-                             int tiles_y, uint8_t *out)
-{
-    ARG_CHECK_CTX(ctx, gray && out && w >= 1 && h >= 1 && stride >= w, "reloc_clahe_u8");
-    ARG_CHECK(clahe_args_ok(clip_limit, tiles_x, tiles_y), "reloc_clahe_u8: tiles_x, tiles_y must be in 1..64 and clip_limit finite");
-    if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
-    void *dlut, *dout;
-    int rc;
-    if ((rc = reloc_scratch(ctx, 0, (int64_t)tiles_x * tiles_y * 256, &dlut))) return rc;
-    if ((rc = reloc_scratch(ctx, 1, (int64_t)w * h, &dout))) return rc;
-    HIP_TRY(hipMemcpy2DAsync(ctx->frame_img, w, gray, stride, w, h, hipMemcpyHostToDevice, ctx->stream));
-    ClaheFrames F = {};
-    F.src[0] = ctx->frame_img; F.lut[0] = (uint8_t *)dlut; F.dst[0] = (uint8_t *)dout;
-    if ((rc = clahe_launch(ctx->stream, F, 1, clahe_geom(w, h, clip_limit, tiles_x, tiles_y), 1, w, 0, w))) return rc;
-    HIP_TRY(hipMemcpyAsync(out, dout, (size_t)w * h, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return RELOC_OK;
-}
-
-// ---- rectification entry points ----------------------------------------------------------------------------
-RELOC_API int reloc_set_rectify_map(reloc_ctx *ctx, const int16_t *xy, const uint16_t *alpha, int w, int h)
-{
-    ARG_CHECK_CTX(ctx, true, "ctx is NULL");
-    if (!xy) {
-        ctx->rect_w = ctx->rect_h = 0;
-        return RELOC_OK;
-    }
-    ARG_CHECK(alpha && w >= 1 && h >= 1, "reloc_set_rectify_map: alpha is NULL or the size is not positive");
-    if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("rectification map exceeds ctx capacity"); return RELOC_E_CAPACITY; }
-    if (!ctx->rect_xy) {
-        // first enable: maps and planes of the largest frame, in one allocation (rect_xy owns it)
-        const size_t px = (size_t)ctx->max_w * ctx->max_h, plane = (size_t)clahe_stride(ctx->max_w) * ctx->max_h;
-        uint8_t *base;
-        HIP_TRY(hipMalloc((void **)&base, px * 4 + px * 2 + px * 2 + plane));
-        ctx->rect_xy = (int16_t *)base;
-        ctx->rect_alpha = (uint16_t *)(base + px * 4);
-        ctx->rect_depth = (uint16_t *)(base + px * 6);
-        ctx->rect_plane = base + px * 8;
-    }
-    // frames in flight may still read the previous map
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(ctx->rect_xy, xy, (size_t)w * h * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ctx->rect_alpha, alpha, (size_t)w * h * 2, hipMemcpyHostToDevice));
-    ctx->rect_w = w;
-    ctx->rect_h = h;
-    return RELOC_OK;
-}
-
-RELOC_API int reloc_get_rectify_map(reloc_ctx *ctx, int32_t *w, int32_t *h)
-{
-    ARG_CHECK_CTX(ctx, w && h, "reloc_get_rectify_map");
-    *w = ctx->rect_w;
-    *h = ctx->rect_h;
-    return RELOC_OK;
-}
-
-// source, maps and destination of a host-pointer remap on the device: src into frame_img (dense rows), maps into scratch 0 / 1
-static int remap_stage(reloc_ctx *ctx, const void *src, int sw, int sh, int sstride, int row_bytes, const int16_t *xy,
-                       const uint16_t *alpha, int dw, int dh, int64_t out_bytes, RemapFrames &F)
-{
-    if (sw > ctx->max_w || sh > ctx->max_h || dw > ctx->max_w || dh > ctx->max_h) {
-        reloc_set_error("image or map exceeds ctx capacity");
-        return RELOC_E_CAPACITY;
-    }
-    void *dxy, *dal, *dout;
-    int rc;
-    if ((rc = reloc_scratch(ctx, 0, (int64_t)dw * dh * 4, &dxy))) return rc;
-    if ((rc = reloc_scratch(ctx, 1, (int64_t)dw * dh * 2, &dal))) return rc;
-    if ((rc = reloc_scratch(ctx, 2, out_bytes, &dout))) return rc;
-    HIP_TRY(hipMemcpy2DAsync(ctx->frame_img, row_bytes, src, sstride, row_bytes, sh, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(dxy, xy, (size_t)dw * dh * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (alpha) HIP_TRY(hipMemcpyAsync(dal, alpha, (size_t)dw * dh * 2, hipMemcpyHostToDevice, ctx->stream));
-    F = {};
-    F.src[0] = ctx->frame_img; F.xy[0] = (const int16_t *)dxy; F.alpha[0] = (const uint16_t *)dal; F.dst[0] = (uint8_t *)dout;
-    return RELOC_OK;
-}
-
-RELOC_API int reloc_remap_u8(reloc_ctx *ctx, const uint8_t *src, int sw, int sh, int sstride, int channels, const int16_t *xy,
-                             const uint16_t *alpha, int dw, int dh, int nearest, int border_value, uint8_t *out)
-{
-    ARG_CHECK_CTX(ctx, src && xy && out && (alpha || nearest) && sw >= 1 && sh >= 1 && dw >= 1 && dh >= 1 &&
-                  (channels == 1 || channels == 3) && sstride >= channels * sw && border_value >= 0 && border_value <= 255,
-                  "reloc_remap_u8");
-    RemapFrames F;
-    const int64_t out_bytes = (int64_t)dw * dh * channels;
-    if (int rc = remap_stage(ctx, src, sw, sh, sstride, sw * channels, xy, alpha, dw, dh, out_bytes, F)) return rc;
-    const RemapGeom g = {sw, sh, sw * channels, dw, dh, dw * channels, border_value};
-    if (nearest) {
-        auto kern = channels == 1 ? k_remap_nearest<uint8_t, 1> : k_remap_nearest<uint8_t, 3>;
-        hipLaunchKernelGGL(kern, dim3((dw + 255) / 256, 1, dh), dim3(256), 0, ctx->stream, F, g);
-        HIP_TRY(hipGetLastError());
-    } else if (int rc = remap_launch(ctx->stream, F, 1, g, channels, false, 0)) {
-        return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(out, F.dst[0], (size_t)out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return RELOC_OK;
-}
-
-RELOC_API int reloc_remap_u16(reloc_ctx *ctx, const uint16_t *src, int sw, int sh, int sstride, const int16_t *xy, int dw, int dh,
-                              int border_value, uint16_t *out)
-{
-    ARG_CHECK_CTX(ctx, src && xy && out && sw >= 1 && sh >= 1 && dw >= 1 && dh >= 1 && sstride >= 2 * sw && border_value >= 0 &&
-                  border_value <= 65535, "reloc_remap_u16");
-    RemapFrames F;
-    const int64_t out_bytes = (int64_t)dw * dh * 2;
-    if (int rc = remap_stage(ctx, src, sw, sh, sstride, sw * 2, xy, nullptr, dw, dh, out_bytes, F)) return rc;
-    const RemapGeom g = {sw, sh, sw, dw, dh, dw, border_value};        // strides in elements
-    hipLaunchKernelGGL((k_remap_nearest<uint16_t, 1>), dim3((dw + 255) / 256, 1, dh), dim3(256), 0, ctx->stream, F, g);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, F.dst[0], (size_t)out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return RELOC_OK;
-}
-
-RELOC_API int reloc_convert_maps(reloc_ctx *ctx, const float *mapx, const float *mapy, int w, int h, int nninterpolation,
-                                 int16_t *xy_out, uint16_t *alpha_out)
-{
-    ARG_CHECK_CTX(ctx, mapx && mapy && xy_out && alpha_out && w >= 1 && h >= 1, "reloc_convert_maps");
-    if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("map exceeds ctx capacity"); return RELOC_E_CAPACITY; }
-    const int64_t n = (int64_t)w * h;
-    void *dmx, *dmy, *dxy, *dal;
-    int rc;
-    if ((rc = reloc_scratch(ctx, 0, n * 4, &dxy))) return rc;
-    if ((rc = reloc_scratch(ctx, 1, n * 2, &dal))) return rc;
-    if ((rc = reloc_scratch(ctx, 2, n * 4, &dmx))) return rc;
-    if ((rc = reloc_scratch(ctx, 3, n * 4, &dmy))) return rc;
-    HIP_TRY(hipMemcpyAsync(dmx, mapx, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(dmy, mapy, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_convert_maps, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float *)dmx,
-                       (const float *)dmy, (int)n, nninterpolation, (u32 *)dxy, (uint16_t *)dal);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(xy_out, dxy, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(alpha_out, dal, (size_t)n * 2, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return RELOC_OK;
-}
-
-// ---- resize entry points -------------------------------------------------------------------------------------
-// source, table and destination of a host-pointer resize on the device: src into frame_img (dense rows), table into scratch 0
-static int resize_host(reloc_ctx *ctx, const void *src, int sw, int sh, int sstride, int channels, int elem, void *out, int dw, int dh,
-                       double inv_x, double inv_y, int interpolation)
-{
-    if (sw > ctx->max_w || sh > ctx->max_h || dw > ctx->max_w || dh > ctx->max_h) {
-        reloc_set_error("image exceeds ctx capacity");
-        return RELOC_E_CAPACITY;
-    }
-    ResizePlan P;
-    if (int rc = resize_plan(sw, sh, dw, dh, inv_x, inv_y, interpolation, P)) return rc;
-    const int row_bytes = sw * channels * elem;
-    const int64_t out_bytes = (int64_t)dw * dh * channels * elem;
-    void *dtab, *dout;
-    int rc;
-    if ((rc = reloc_scratch(ctx, 0, (int64_t)P.tab.size() * 4 + 4, &dtab))) return rc;
-    if ((rc = reloc_scratch(ctx, 1, out_bytes, &dout))) return rc;
-    HIP_TRY(hipMemcpy2DAsync(ctx->frame_img, row_bytes, src, sstride, row_bytes, sh, hipMemcpyHostToDevice, ctx->stream));
-    // the table is pageable host memory that dies with this call: the copy below is complete when the call returns
-    if (!P.tab.empty()) HIP_TRY(hipMemcpyAsync(dtab, P.tab.data(), P.tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    ResizeFrames F = {};
-    F.src[0] = ctx->frame_img; F.tab[0] = (const int32_t *)dtab; F.dst[0] = (uint8_t *)dout;
-    const bool by_elem = P.kind == RESIZE_NEAREST;      // k_resize_nearest counts strides in elements
-    if ((rc = resize_launch(ctx->stream, F, 1, P, sw, sh, by_elem ? sw * channels : row_bytes, dw, dh, dw * channels, channels, elem,
-                            false, 0)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(out, dout, (size_t)out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return RELOC_OK;
-}
-
-RELOC_API int reloc_resize_u8(reloc_ctx *ctx, const uint8_t *src, int sw, int sh, int sstride, int channels, uint8_t *out, int dw,
-                              int dh, double inv_scale_x, double inv_scale_y, int interpolation)
-{
-    ARG_CHECK_CTX(ctx, src && out && sw >= 1 && sh >= 1 && dw >= 1 && dh >= 1 && (channels == 1 || channels == 3) &&
-                  sstride >= channels * sw, "reloc_resize_u8");
-    return resize_host(ctx, src, sw, sh, sstride, channels, 1, out, dw, dh, inv_scale_x, inv_scale_y, interpolation);
-}
-
-RELOC_API int reloc_resize_u16(reloc_ctx *ctx, const uint16_t *src, int sw, int sh, int sstride, uint16_t *out, int dw, int dh,
-                               double inv_scale_x, double inv_scale_y)
-{
-    ARG_CHECK_CTX(ctx, src && out && sw >= 1 && sh >= 1 && dw >= 1 && dh >= 1 && sstride >= 2 * sw, "reloc_resize_u16");
-    return resize_host(ctx, src, sw, sh, sstride, 1, 2, out, dw, dh, inv_scale_x, inv_scale_y, 0);
-}
-
-RELOC_API int reloc_set_resize(reloc_ctx *ctx, int sw, int sh, int dw, int dh)
-{
-    ARG_CHECK_CTX(ctx, true, "ctx is NULL");
-    if (sw == 0 && sh == 0 && dw == 0 && dh == 0) {
-        ctx->rsz_sw = ctx->rsz_sh = ctx->rsz_dw = ctx->rsz_dh = 0;
-        return RELOC_OK;
-    }
-    ARG_CHECK(dw >= 1 && dh >= 1 && dw <= sw && dh <= sh,
-              "reloc_set_resize: sizes must be all 0 (off) or 1 <= dw <= sw and 1 <= dh <= sh");
-    if (sw > ctx->max_w || sh > ctx->max_h) { reloc_set_error("resize source exceeds ctx capacity"); return RELOC_E_CAPACITY; }
-    ResizePlan area, nearest;
-    if (int rc = resize_plan(sw, sh, dw, dh, 0.0, 0.0, 3, area)) return rc;
-    if (int rc = resize_plan(sw, sh, dw, dh, 0.0, 0.0, 0, nearest)) return rc;
-    // tables of the largest frame: 3 words and at most scale + 2 alphas per destination index and axis, one offset per index
-    // and axis for the depth; then the gray plane and the depth plane, in one allocation (rsz_tab owns it)
-    const size_t area_words = 6 * ((size_t)ctx->max_w + ctx->max_h), near_words = (size_t)ctx->max_w + ctx->max_h;
-    if (area.tab.size() > area_words || nearest.tab.size() > near_words) { reloc_set_error("resize tables exceed ctx capacity"); return RELOC_E_CAPACITY; }
-    if (!ctx->rsz_tab) {
-        const size_t px = (size_t)ctx->max_w * ctx->max_h, plane = (size_t)clahe_stride(ctx->max_w) * ctx->max_h;
-        const size_t tab_bytes = ((area_words + near_words) * 4 + 255) & ~(size_t)255;
-        uint8_t *base;
-        HIP_TRY(hipMalloc((void **)&base, tab_bytes + plane + px * 2));
-        ctx->rsz_tab = (int32_t *)base;
-        ctx->rsz_ntab = ctx->rsz_tab + area_words;
-        ctx->rsz_plane = base + tab_bytes;
-        ctx->rsz_depth = (uint16_t *)(base + tab_bytes + plane);
-    }
-    // frames in flight may still read the previous tables
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (!area.tab.empty()) HIP_TRY(hipMemcpy(ctx->rsz_tab, area.tab.data(), area.tab.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ctx->rsz_ntab, nearest.tab.data(), nearest.tab.size() * 4, hipMemcpyHostToDevice));
-    ctx->rsz_kind = area.kind; ctx->rsz_isx = area.isx; ctx->rsz_isy = area.isy;
-    ctx->rsz_sw = sw; ctx->rsz_sh = sh; ctx->rsz_dw = dw; ctx->rsz_dh = dh;
-    return RELOC_OK;
-}
-
-RELOC_API int reloc_get_resize(reloc_ctx *ctx, int32_t *sw, int32_t *sh, int32_t *dw, int32_t *dh)
-{
-    ARG_CHECK_CTX(ctx, sw && sh && dw && dh, "reloc_get_resize");
-    *sw = ctx->rsz_sw; *sh = ctx->rsz_sh; *dw = ctx->rsz_dw; *dh = ctx->rsz_dh;
     return RELOC_OK;
 }

@@ -147,11 +147,7 @@ RELOC_API int reloc_record_frame(reloc_ctx *ctx, const uint8_t *img, const uint1
     const uint8_t *src = ctx->frame_img;
     if ((rc = orb_run(&ctx, 1, &src, w, h, w * 3, 3, order, nfeatures, true))) return rc;
     const uint16_t *depth = (const uint16_t *)ddepth;
-    if (ctx->rsz_dw > 0) {      // from here on the working frame
-        if ((rc = resize_depth(ctx, depth, w, h, &depth))) return rc;
-        w = ctx->rsz_dw; h = ctx->rsz_dh;
-    }
-    if (ctx->rect_w > 0 && (rc = rectify_depth(ctx, depth, w, h, &depth))) return rc;
+    if ((rc = image_chain_depth(ctx, depth, &w, &h, &depth))) return rc;      // from here on the working frame
     RecordParams p;
     p.fx = ctx->K4[0]; p.fy = ctx->K4[1]; p.cx = ctx->K4[2]; p.cy = ctx->K4[3];
     p.depth_min = RELOC_DEPTH_MIN_M; p.depth_max = RELOC_DEPTH_MAX_M; p.var_max = RELOC_DEPTH_VAR_MAX_M;
@@ -346,13 +342,7 @@ RELOC_API int reloc_tick_accumulate_dev(reloc_ctx *ctx, const uint16_t *depth_mm
                             ctx->db_cap_rows + ctx->db_cap_rows / 2 + 64 * (int64_t)ctx->max_feat);
         if (rc) return rc;
     }
-    if (ctx->rsz_dw > 0) {      // from here on the working frame
-        if (int rc = resize_depth(ctx, depth_mm_dev, w, h, &depth_mm_dev)) return rc;
-        w = ctx->rsz_dw; h = ctx->rsz_dh;
-    }
-    if (ctx->rect_w > 0) {
-        if (int rc = rectify_depth(ctx, depth_mm_dev, w, h, &depth_mm_dev)) return rc;
-    }
+    if (int rc = image_chain_depth(ctx, depth_mm_dev, &w, &h, &depth_mm_dev)) return rc;      // from here on the working frame
     AccumParams p;
     p.fx = ctx->K4[0]; p.fy = ctx->K4[1]; p.cx = ctx->K4[2]; p.cy = ctx->K4[3];
     for (int k = 0; k < 7; ++k) p.base_pose[k] = base_pose[k];

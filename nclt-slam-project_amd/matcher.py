@@ -124,6 +124,35 @@ def fixed_rectify_maps(cv2, maps):
     return cv2.convertMaps(m1, m2, cv2.CV_16SC2)
 
 
+class ImageChain:
+    """The image chain between gray conversion and ORB on the cv2-shaped path, stated here only: resize -> rectify -> CLAHE,
+    the depth following the first two with INTER_NEAREST.  clahe, rectify, resize: as MatcherConfig's; cv2 None: never applied."""
+    def __init__(self, cv2, clahe=None, rectify=None, resize=None):
+        self.cv2 = cv2
+        self.clahe = None if cv2 is None or clahe is None else cv2.createCLAHE(clipLimit=clahe[0], tileGridSize=tuple(clahe[1]))
+        self.rectify = fixed_rectify_maps(cv2, rectify) if cv2 is not None else None
+        self.resize = resize_setting(resize)
+
+    def apply(self, gray, depth_mm=None):
+        cv2 = self.cv2
+        if self.resize is not None:
+            gray = cv2.resize(gray, self.resize, interpolation=cv2.INTER_AREA)
+            depth_mm = None if depth_mm is None else cv2.resize(depth_mm, self.resize, interpolation=cv2.INTER_NEAREST)
+        if self.rectify is not None:
+            gray = cv2.remap(gray, *self.rectify, cv2.INTER_LINEAR)
+            depth_mm = None if depth_mm is None else cv2.remap(depth_mm, *self.rectify, cv2.INTER_NEAREST)
+        if self.clahe is not None:
+            gray = self.clahe.apply(gray)
+        return gray, depth_mm
+
+
+def configure_engine(engine, clahe=None, rectify=None, resize=None):
+    """the same three settings on an Engine, which is as large as the camera"""
+    engine.set_clahe(*((None,) if clahe is None else (clahe[0], tuple(clahe[1]))))
+    engine.set_resize(*((None, None) if resize is None else ((engine.max_w, engine.max_h), resize_setting(resize))))
+    engine.set_rectify(rectify)
+
+
 class LandmarkMatcherCore:
     def __init__(self, landmarks, log_csv=None, cv2=None, config: MatcherConfig | None = None,
                  return_landmarks=None, swap_flag=None, logger=None):
@@ -140,10 +169,8 @@ class LandmarkMatcherCore:
         self._adopt(load_landmarks(landmarks) if isinstance(landmarks, str) else landmarks)
         self.orb = cv2.ORB_create(nfeatures=self.cfg.nfeatures)
         self.matcher = cv2.BFMatcher(cv2.NORM_HAMMING, crossCheck=True)
-        self.clahe = None if self.cfg.clahe is None else cv2.createCLAHE(clipLimit=self.cfg.clahe[0],
-                                                                         tileGridSize=tuple(self.cfg.clahe[1]))
-        self.rectify = fixed_rectify_maps(cv2, self.cfg.rectify)
-        self.resize = resize_setting(self.cfg.resize)
+        self.chain = c = ImageChain(cv2, self.cfg.clahe, self.cfg.rectify, self.cfg.resize)
+        self.clahe, self.rectify, self.resize = c.clahe, c.rectify, c.resize
         self.dist = np.zeros((4, 1), dtype=np.float32) if len(self.cfg.dist) == 0 else np.asarray(self.cfg.dist, np.float64).reshape(-1, 1)
         self.last_anchor_ts = 0.0
         self.n_attempts = 0
@@ -283,17 +310,7 @@ class LandmarkMatcherCore:
         self.n_attempts += 1
         vio_xy = (base_pose[0], base_pose[1])
         cand, d, herr = self.select_candidates(base_pose)
-        gray = cv2.cvtColor(bgr, cv2.COLOR_BGR2GRAY)
-        if self.resize is not None:
-            gray = cv2.resize(gray, self.resize, interpolation=cv2.INTER_AREA)
-            if depth_mm is not None:
-                depth_mm = cv2.resize(depth_mm, self.resize, interpolation=cv2.INTER_NEAREST)
-        if self.rectify is not None:
-            gray = cv2.remap(gray, *self.rectify, cv2.INTER_LINEAR)
-            if depth_mm is not None:
-                depth_mm = cv2.remap(depth_mm, *self.rectify, cv2.INTER_NEAREST)
-        if self.clahe is not None:
-            gray = self.clahe.apply(gray)
+        gray, depth_mm = self.chain.apply(cv2.cvtColor(bgr, cv2.COLOR_BGR2GRAY), depth_mm)
         kpts, desc = self.orb.detectAndCompute(gray, None)
         if desc is None or len(kpts) < cfg.min_matches:
             o = TickOutcome(ts, vio_xy, len(cand), 0, None, None, "curr_no_features")
@@ -401,10 +418,7 @@ class FusedLandmarkMatcher:
         e.set_camera([cfg.fx, cfg.fy, cfg.cx, cfg.cy], data.get("base_to_cam_translation", P.BASE_TO_CAM_TRANSLATION),
                      data.get("base_to_cam_rot", P.BASE_TO_CAM_ROT))
         e.set_distortion(cfg.dist)
-        e.set_clahe(*((None,) if cfg.clahe is None else (cfg.clahe[0], tuple(cfg.clahe[1]))))
-        size = resize_setting(cfg.resize)
-        e.set_resize(*((None, None) if size is None else ((e.max_w, e.max_h), size)))   # the Engine is as large as the camera
-        e.set_rectify(cfg.rectify)
+        configure_engine(e, cfg.clahe, cfg.rectify, cfg.resize)
         self._return_src = return_landmarks
         self.swap_flag = swap_flag
         self._swapped = False

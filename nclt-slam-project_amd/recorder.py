@@ -14,7 +14,7 @@ import numpy as np
 
 from . import pose as P
 from .landmarks import new_database, save_landmarks
-from .matcher import fixed_rectify_maps, resize_setting
+from .matcher import ImageChain, configure_engine
 
 FX = FY = 320.0
 CX, CY = 320.0, 240.0
@@ -57,10 +57,7 @@ class LandmarkRecorderCore:
         self.dist = tuple(np.asarray(dist, np.float64).ravel()) if dist is not None else ()
         if engine is not None:
             engine.set_distortion(self.dist)
-            engine.set_clahe(*((None,) if clahe is None else (clahe[0], tuple(clahe[1]))))
-            size = resize_setting(resize)
-            engine.set_resize(*((None, None) if size is None else ((engine.max_w, engine.max_h), size)))
-            engine.set_rectify(rectify)
+            configure_engine(engine, clahe, rectify, resize)
         self.nfeatures = nfeatures
         if cv2 is None and engine is None:
             from . import cv2_shim as cv2
@@ -68,10 +65,8 @@ class LandmarkRecorderCore:
         self.out_pkl = out_pkl
         self.min_disp_m = float(min_disp_m)
         self.orb = cv2.ORB_create(nfeatures=nfeatures) if cv2 is not None else None
-        self.clahe = (cv2.createCLAHE(clipLimit=clahe[0], tileGridSize=tuple(clahe[1]))
-                      if cv2 is not None and clahe is not None else None)
-        self.rectify = fixed_rectify_maps(cv2, rectify) if cv2 is not None else None
-        self.resize = resize_setting(resize)
+        self.chain = c = ImageChain(cv2, clahe, rectify, resize)
+        self.clahe, self.rectify, self.resize = c.clahe, c.rectify, c.resize
         self.landmarks = []
         self.last_landmark_pose_world = None
         self.log = logger or (lambda msg: None)
@@ -94,16 +89,7 @@ class LandmarkRecorderCore:
             self.landmarks.append(rec)
             self.last_landmark_pose_world = cam_pose
             return rec
-        cv2 = self.cv2
-        gray = cv2.cvtColor(bgr, cv2.COLOR_BGR2GRAY)
-        if self.resize is not None:
-            gray = cv2.resize(gray, self.resize, interpolation=cv2.INTER_AREA)
-            depth_mm = cv2.resize(depth_mm, self.resize, interpolation=cv2.INTER_NEAREST)
-        if self.rectify is not None:
-            gray = cv2.remap(gray, *self.rectify, cv2.INTER_LINEAR)
-            depth_mm = cv2.remap(depth_mm, *self.rectify, cv2.INTER_NEAREST)
-        if self.clahe is not None:
-            gray = self.clahe.apply(gray)
+        gray, depth_mm = self.chain.apply(self.cv2.cvtColor(bgr, self.cv2.COLOR_BGR2GRAY), depth_mm)
         kpts, desc = self.orb.detectAndCompute(gray, None)
         if desc is None or len(kpts) == 0:
             return None
@@ -119,7 +105,7 @@ class LandmarkRecorderCore:
         if ok.sum() < MIN_RECORD_KPTS:
             return None
         uu, vv, z = uu[ok], vv[ok], z[ok]
-        pts3 = P.back_project(cv2, uu, vv, z, FX, FY, CX, CY, self.dist)
+        pts3 = P.back_project(self.cv2, uu, vv, z, FX, FY, CX, CY, self.dist)
         rec = {"pose": cam_pose, "descriptors": desc[ok], "keypoints_2d": xy[ok], "keypoints_3d_cam": pts3,
                "ts": rgb_ts, "n_features": int(len(pts3))}
         self.landmarks.append(rec)

@@ -225,6 +225,73 @@ def test_stage_order_with_rectify_and_clahe(oracle):
         e.close()
 
 
+@pytest.mark.parametrize("ssize,wsize,resize,rectify", [
+    ((128, 96), (64, 64), True, True), ((64, 64), (64, 64), False, True), ((128, 96), (64, 64), True, False),
+    ((512, 480), (256, 240), True, True)])      # the last one is large enough for rows below the recorder's ground line
+def test_record_and_accumulate_take_the_depth_through_one_chain(ssize, wsize, resize, rectify):
+    """reloc_record_frame and reloc_tick_accumulate_dev see the depth that Engine.resize (nearest), then Engine.remap (nearest)
+    make of it on the host side of the test: their 3-D points equal those of tests/record_ref.py on that depth, bit for bit"""
+    import record_ref as REC
+    from nclt_slam_project_amd import pose as P
+    (sw, sh), (ww, wh) = ssize, wsize
+    K4 = (320.0, 320.0, 320.0, 240.0)
+    img = synth.textured_frame(np.random.default_rng(sw + wh), sw, sh)
+    yy, xx = np.mgrid[0:sh, 0:sw]
+    dep = (1500 + 7 * xx + 13 * yy).astype(np.uint16)      # no two neighbours equal: a wrong tap is a wrong point
+    v, u = np.mgrid[0:wh, 0:ww]
+    maps = RR.convert_maps((u + 0.02 * (v - wh / 2) + 1.3).astype(np.float32), (v * 0.98 + 0.7).astype(np.float32))
+    poses = np.zeros((3, 7)); poses[:, 6] = 1.0; poses[:, 0] = 200.0 + np.arange(3)       # far away: no candidate, nothing near
+    e = Engine(0, sw, sh, 4096)
+    dep_dev = img_dev = 0
+    try:
+        if resize:
+            e.set_resize(ssize, wsize)
+        if rectify:
+            e.set_rectify(maps)
+        exp = e.resize(dep, wsize, interpolation=NEAREST) if resize else dep
+        exp = e.remap(exp, maps[0], None, nearest=True) if rectify else exp
+        assert exp.shape == (wh, ww) and exp.dtype == np.uint16
+        # recording
+        r = e.record_frame(img, dep)
+        f = e.orb_features()
+        idx, xy, desc, pts = REC.record_rows(f["xy"], f["desc"], exp, ww, wh, K4)
+        assert r["n"] == len(idx) and r["n_kp"] == f["n"]
+        np.testing.assert_array_equal(r["kp_index"], idx)
+        np.testing.assert_array_equal(r["pts3d"].view(np.uint32), pts.view(np.uint32))
+        # accumulation
+        e.set_params(accum_min_kpts=1, min_matches=4)
+        prm = e.get_params()
+        e.db_upload(np.zeros((6, 32), np.uint8), np.ones((6, 3), np.float32), 2 * np.arange(4, dtype=np.int64), poses)
+        bp = synth.base_pose(0.0, 0.0, 0.0)
+        img_dev, dep_dev = e.to_device(img), e.to_device(dep)
+        e.tick_dev(img_dev, sw, sh, bp)
+        e.tick_accumulate_dev(dep_dev, sw, sh, bp, True)
+        res, acc, f = e.tick_result(), e.accumulate_result(), e.orb_features()
+        ref = REC.accumulate_record(f["xy"], f["desc"], exp, ww, wh, K4, bp, P.BASE_TO_CAM_TRANSLATION, P.BASE_TO_CAM_ROT, poses[:, :2],
+                                    dict(accum_min_dist_m=prm.accum_min_dist_m, accum_min_kpts=prm.accum_min_kpts,
+                                         accum_depth_min_m=prm.accum_depth_min_m, accum_depth_max_m=prm.accum_depth_max_m,
+                                         wanted=res["outcome"] in (2, 3, 4)))
+        assert (acc["appended"], acc["n_kpts"]) == (ref[0], ref[1])
+        if ref[0]:
+            rec = e.db_fetch(3)
+            np.testing.assert_array_equal(rec["keypoints_2d"].view(np.uint32), ref[3][0].view(np.uint32))
+            np.testing.assert_array_equal(rec["keypoints_3d_cam"].view(np.uint32), ref[3][2].view(np.uint32))
+        if ww > 64:
+            assert r["n"] > 0 and ref[0] and ref[1] > 30
+        if resize:      # a depth image that is not the stage's source size: the stage's message, from both callers
+            msg = f"frame {sw - 2}x{sh} differs from the source size {sw}x{sh} of the downscale stage"
+            with pytest.raises(RelocError, match=msg):
+                e.tick_accumulate_dev(dep_dev, sw - 2, sh, bp, True)
+            with pytest.raises(RelocError, match=msg):
+                e.record_frame(np.ascontiguousarray(img[:, :-2]), np.ascontiguousarray(dep[:, :-2]))
+        e.sync()
+    finally:
+        for p in (img_dev, dep_dev):
+            if p:
+                e.dev_free(p)
+        e.close()
+
+
 def _rep(a, k):
     return np.ascontiguousarray(np.repeat(np.repeat(a, k, axis=0), k, axis=1))
 
