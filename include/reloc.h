@@ -316,6 +316,24 @@ int reloc_resize_u16(reloc_ctx *ctx, const uint16_t *src, int sw, int sh, int ss
 int reloc_set_resize(reloc_ctx *ctx, int sw, int sh, int dw, int dh);
 int reloc_get_resize(reloc_ctx *ctx, int32_t *sw, int32_t *sh, int32_t *dw, int32_t *dh);
 
+/* ---- Bayer demosaicing (include/reloc_spec.h, "BAYER") -------------------------------------------- */
+/* cv2.cvtColor(raw, code) on a caller's 8-bit mosaic (cv2 shim): raw is w x h, single channel, rows stride bytes apart;
+ * out_bgr is w x h x 3, interleaved B G R, dense.  code takes OpenCV's values: 46 COLOR_BayerBG2BGR, 47 COLOR_BayerGB2BGR,
+ * 48 COLOR_BayerRG2BGR, 49 COLOR_BayerGR2BGR (a 2RGB code is the aliased 2BGR one); anything else, w < 3 or h < 3 is
+ * RELOC_E_ARG, a mosaic beyond the context's capacity RELOC_E_CAPACITY.  Host pointers; synchronous. */
+int reloc_bayer_u8(reloc_ctx *ctx, const uint8_t *raw, int w, int h, int stride, int code, uint8_t *out_bgr);
+/* The raw-sensor stage in front of the whole image chain: with code = 46..49 every entry point that applies the downscale
+ * stage takes a SINGLE-CHANNEL w x h mosaic, rows dense (reloc_orb_frame_dev: stride in bytes of the mosaic, >= w), in place
+ * of the 3-channel frame, and the chain is raw -> demosaic + gray -> [resize] -> [rectify] -> [CLAHE] -> ORB: the bytes of
+ * cvtColor(cvtColor(raw, code), COLOR_BGR2GRAY) with the context's gray_coeff_bits.  The channel-order bit of `order` is
+ * ignored.  reloc_set_resize's source size is the mosaic's size.  Depth images are not mosaics and follow their chain
+ * unchanged.  0 turns the stage off (the default of a new context; the launch sequence is then that of a context that never
+ * had it, results bit-identical); any other code is RELOC_E_ARG.  The first enable allocates the context's plane.  Never
+ * applied by reloc_orb_detect_compute, reloc_gray_u8, reloc_clahe_u8, reloc_remap_* or reloc_resize_*.  Batched calls refuse
+ * contexts with unequal codes (RELOC_E_STATE).  reloc_get_bayer returns 0 when off. */
+int reloc_set_bayer(reloc_ctx *ctx, int code);
+int reloc_get_bayer(reloc_ctx *ctx, int32_t *code);
+
 /* ---- fused tick ----------------------------------------------------------------------------- */
 #define RELOC_TICK_LOCAL   0   /* candidates by VIO distance / heading only                          M:293-302 */
 #define RELOC_TICK_GLOBAL  1   /* whole-database search unconditionally (the benchmarked shape)       G:329-344 */

@@ -205,4 +205,28 @@
  *   table entries only.  Everything else (other interpolations, dtypes, INTER_AREA upscaling) is refused. */
 #define RELOC_RESIZE_LINEAR_BITS 11   /* INTER_RESIZE_COEF_BITS: the two weights of an axis sum to 2048 */
 
+/* BAYER: cv2.cvtColor(raw, COLOR_Bayer??2BGR | COLOR_Bayer??2RGB) on 8-bit single-channel mosaics of at least 3 x 3, restated
+ * from OpenCV 4.x modules/imgproc/src/demosaicing.cpp (bilinear Bayer2RGB_; the reference: cv2.cvtColor(raw,
+ * cv2.COLOR_BayerGR2BGR) in front of undistort and BGR2GRAY, datasets/robotcar/scripts/prepare_stereo_euroc.py:43-45,117-137;
+ * not pinned against a cv2 build).
+ *   pattern    the two letters of a code are the colours of pixels (row 1, col 1) and (row 1, col 2); the top-left 2 x 2 tile:
+ *              BG (46) = R G / G B (sensor name RGGB), GB (47) = G R / B G (GRBG), RG (48) = B G / G R (BGGR),
+ *              GR (49) = G B / R G (GBRG).  The tile repeats over the image.
+ *   interior   1 <= y <= h - 2, 1 <= x <= w - 2, integers on the raw bytes, N S W E NW NE SW SE the eight neighbours:
+ *              red or blue site: own colour = raw, green = (N + S + W + E + 2) >> 2, opposite = (NW + NE + SW + SE + 2) >> 2;
+ *              green site: green = raw, colour of the horizontal neighbours = (W + E + 1) >> 1, of the vertical ones
+ *              (N + S + 1) >> 1.
+ *   border     after the interior: column 0 copies column 1 and column w - 1 copies column w - 2 for rows 1 .. h - 2; then
+ *              row 0 copies row 1 and row h - 1 copies row h - 2 over the whole width (so a corner takes the nearest interior
+ *              pixel): dst(y, x) = interior(clamp(y, 1, h - 2), clamp(x, 1, w - 2)).
+ *   2RGB       the same arithmetic with the output channels swapped; OpenCV's enum aliases: BayerBG2RGB = BayerRG2BGR,
+ *              BayerGB2RGB = BayerGR2BGR, BayerRG2RGB = BayerBG2BGR, BayerGR2RGB = BayerGB2BGR.
+ *   gray       the stage in front of ORB: the gray conversion above on the demosaiced (B, G, R), i.e. the bytes of
+ *              cvtColor(cvtColor(raw, Bayer??2BGR), BGR2GRAY).  OpenCV's direct Bayer??2GRAY codes round differently (a 14-bit
+ *              path of their own) and are refused, as are 16-bit mosaics and the _VNG, _EA and 2BGRA codes. */
+#define RELOC_BAYER_BG2BGR       46
+#define RELOC_BAYER_GB2BGR       47
+#define RELOC_BAYER_RG2BGR       48
+#define RELOC_BAYER_GR2BGR       49
+
 #endif /* RELOC_SPEC_H */

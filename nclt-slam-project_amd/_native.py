@@ -74,6 +74,9 @@ SIGNATURES = {
     "reloc_resize_u16": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, P, C.c_int, C.c_int, f64, f64]),
     "reloc_set_resize": (C.c_int, [c_ctx, C.c_int, C.c_int, C.c_int, C.c_int]),
     "reloc_get_resize": (C.c_int, [c_ctx, P, P, P, P]),
+    "reloc_bayer_u8": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, C.c_int, P]),
+    "reloc_set_bayer": (C.c_int, [c_ctx, C.c_int]),
+    "reloc_get_bayer": (C.c_int, [c_ctx, P]),
     "reloc_tick_debug": (C.c_int, [c_ctx, P, P, P, P, P, P, P]),
     "reloc_tick": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, P, C.c_int, u64, P, P, P, P, P, P]),
     "reloc_get_params": (C.c_int, [c_ctx, P]),

@@ -170,7 +170,7 @@ RELOC_API void reloc_destroy(reloc_ctx *c)
                     c->m_tidx, c->m_dist, c->m_n, c->p_obj, c->p_img, c->p_Rt, c->p_cnt, c->p_inl,
                     c->p_out, c->tick_res, c->accum_res, c->tick_flags, c->scan_ticket, c->clahe_plane, c->clahe_lut,
                     c->rect_xy /* owns rect_alpha, rect_depth and rect_plane */,
-                    c->rsz_tab /* owns rsz_ntab, rsz_plane and rsz_depth */};
+                    c->rsz_tab /* owns rsz_ntab, rsz_plane and rsz_depth */, c->bayer_plane};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (c->tick_res_host) (void)hipHostFree(c->tick_res_host);

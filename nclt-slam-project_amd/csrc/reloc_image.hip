@@ -1,11 +1,13 @@
 // reloc_image.hip -- the image stages in front of ORB on gfx950, and the one place that orders them.
 // A section per stage (kernels, host planning, one *_launch for n frames of equal geometry on one stream):
 //   gray     cv2.cvtColor(.., COLOR_BGR2GRAY)   k_gray_plain; inside the chain the first kernel that reads the frame converts
+//   BAYER    cv2.cvtColor(.., COLOR_Bayer??2BGR) k_bayer: a raw mosaic -> BGR (the shim) or -> gray (the stage)
 //   CLAHE    cv2.createCLAHE(..).apply          k_clahe_lut, k_clahe_apply
 //   REMAP    cv2.remap, cv2.convertMaps         k_remap_u8, k_remap_nearest, k_convert_maps
 //   RESIZE   cv2.resize                         k_resize_area, k_resize_linear, k_resize_nearest
-// "image chain": resize -> rectify -> CLAHE on 3-channel frames in front of the pyramid (orb_run), resize -> rectify, both
-// nearest, on the depth image of the recorder and the accumulation.  No other code states this order.
+// "image chain": [demosaic] -> resize -> rectify -> CLAHE on the frames in front of the pyramid (orb_run; 3-channel frames, or
+// raw mosaics with the Bayer stage on), resize -> rectify, both nearest, on the depth image of the recorder and the
+// accumulation.  No other code states this order.
 // "entry points": the host-pointer form of every stage (the cv2 shim) and the reloc_set_* / reloc_get_* of a context.
 #include <float.h>
 #include <math.h>
@@ -30,6 +32,118 @@ __global__ __launch_bounds__(256) void k_gray_plain(const uint8_t *__restrict__ 
     const int c0 = s[0], c1 = s[1], c2 = s[2];
     const int b = (order_rgb & 1) ? c2 : c0, r = (order_rgb & 1) ? c0 : c2;
     dst[(size_t)y * w + x] = (uint8_t)gray_fixed(b, c1, r, order_rgb);
+}
+
+// ---- BAYER: cv2.cvtColor(raw, COLOR_Bayer??2BGR) (include/reloc_spec.h, "BAYER") ---------------------------------
+// OpenCV's bilinear 8-bit demosaic, interior and border rule in one launch: output pixel (y, x) is the interior value at
+// (clamp(y, 1, h - 2), clamp(x, 1, w - 2)) -- columns first, then rows, as the spec fills them.
+//   k_bayer<OC, ALIGNED>   4 output pixels per lane along x from three source rows.  ALIGNED (w % 4 == 0, rows on dwords):
+//                          per row the lane's dword and its two neighbours (one halo byte each); the border columns are then
+//                          pixels 0 and 3 of the first / last quad and take their neighbour's triple.  Otherwise (odd widths,
+//                          strided or odd sources): the nine bytes around every clamped pixel through the cache.
+//                          OC = 3: interleaved BGR (the shim).  OC = 1: gray_fixed of the triple with the coefficient flags --
+//                          the stage at the head of the image chain, byte for byte cvtColor(cvtColor(raw, Bayer2BGR), BGR2GRAY).
+// The pattern is two launch-uniform parity bits, not four instantiations: green_par = parity of x + y at the green sites,
+// blue_par = parity of the rows that hold blue sites; every site kind is computed by the same selects.  Frame-batched
+// (blockIdx.y = frame); a single frame is a batch of one.
+struct BayerFrames { const uint8_t *src[RELOC_BATCH_MAX]; uint8_t *dst[RELOC_BATCH_MAX]; };
+
+// the triple of one site from its 3 x 3 neighbourhood t (top), m (middle), b (bottom), columns 0..2
+__device__ __forceinline__ void bayer_site(const int (&t)[3], const int (&m)[3], const int (&b)[3], bool green, bool blue_row,
+                                           int &vb, int &vg, int &vr)
+{
+    const int c = m[1];
+    const int hor = (m[0] + m[2] + 1) >> 1, ver = (t[1] + b[1] + 1) >> 1;
+    const int cross = (t[1] + b[1] + m[0] + m[2] + 2) >> 2, diag = (t[0] + t[2] + b[0] + b[2] + 2) >> 2;
+    const int row_col = green ? hor : c;          // the colour of this row's red / blue sites
+    const int other = green ? ver : diag;         // the colour of the neighbouring rows' red / blue sites
+    vg = green ? c : cross;
+    vb = blue_row ? row_col : other;
+    vr = blue_row ? other : row_col;
+}
+
+template <int OC, bool ALIGNED>
+__global__ __launch_bounds__(256) void k_bayer(BayerFrames F, int w, int h, int sstride, int dstride, int green_par, int blue_par,
+                                               int flags)
+{
+    const int quads = (w + 3) >> 2;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= quads * h) return;
+    const int y = q / quads, x4 = 4 * (q - y * quads);
+    const int yc = min(max(y, 1), h - 2);
+    const bool blue_row = ((yc ^ blue_par) & 1) == 0;
+    const uint8_t *src = F.src[blockIdx.y];
+    int vb[4], vg[4], vr[4];
+    if (ALIGNED) {
+        // columns x4 - 1 .. x4 + 4 of rows yc - 1 .. yc + 1; a halo byte outside the image is 0 and feeds a border pixel only
+        int v[3][6];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const u32 *row = reinterpret_cast<const u32 *>(src + (size_t)(yc - 1 + r) * sstride + x4);
+            const u32 prev = x4 > 0 ? row[-1] : 0u, cur = row[0], next = x4 + 4 < w ? row[1] : 0u;
+            v[r][0] = prev >> 24;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[r][1 + k] = (cur >> (8 * k)) & 255u;
+            v[r][5] = next & 255u;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int t[3] = {v[0][k], v[0][k + 1], v[0][k + 2]}, m[3] = {v[1][k], v[1][k + 1], v[1][k + 2]};
+            const int b[3] = {v[2][k], v[2][k + 1], v[2][k + 2]};
+            bayer_site(t, m, b, (((x4 + k) ^ yc ^ green_par) & 1) == 0, blue_row, vb[k], vg[k], vr[k]);
+        }
+        if (x4 == 0) { vb[0] = vb[1]; vg[0] = vg[1]; vr[0] = vr[1]; }              // column 0 copies column 1
+        if (x4 + 4 == w) { vb[3] = vb[2]; vg[3] = vg[2]; vr[3] = vr[2]; }          // column w - 1 copies column w - 2
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int xc = min(max(x4 + k, 1), w - 2);          // also keeps the reads of a pixel beyond w inside the row
+            const uint8_t *p = src + (size_t)(yc - 1) * sstride + (xc - 1);
+            const int t[3] = {p[0], p[1], p[2]}, m[3] = {p[sstride], p[sstride + 1], p[sstride + 2]};
+            const int b[3] = {p[2 * (size_t)sstride], p[2 * (size_t)sstride + 1], p[2 * (size_t)sstride + 2]};
+            bayer_site(t, m, b, ((xc ^ yc ^ green_par) & 1) == 0, blue_row, vb[k], vg[k], vr[k]);
+        }
+    }
+    uint8_t *dst = F.dst[blockIdx.y] + (size_t)y * dstride + OC * x4;
+    if (OC == 1) {
+        u32 out = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (x4 + k < w) out |= (u32)gray_fixed(vb[k], vg[k], vr[k], flags) << (8 * k);
+        if ((dstride & 3) == 0) {
+            *reinterpret_cast<u32 *>(dst) = out;       // the row holds round4(w) bytes: dstride >= w and a multiple of 4
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x4 + k < w) dst[k] = (uint8_t)(out >> (8 * k));
+        }
+    } else if (ALIGNED && (dstride & 3) == 0) {
+        u32 *d4 = reinterpret_cast<u32 *>(dst);        // 12 bytes of 4 whole pixels (w % 4 == 0)
+        d4[0] = (u32)vb[0] | (u32)vg[0] << 8 | (u32)vr[0] << 16 | (u32)vb[1] << 24;
+        d4[1] = (u32)vg[1] | (u32)vr[1] << 8 | (u32)vb[2] << 16 | (u32)vg[2] << 24;
+        d4[2] = (u32)vr[2] | (u32)vb[3] << 8 | (u32)vg[3] << 16 | (u32)vr[3] << 24;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (x4 + k < w) { dst[3 * k] = (uint8_t)vb[k]; dst[3 * k + 1] = (uint8_t)vg[k]; dst[3 * k + 2] = (uint8_t)vr[k]; }
+    }
+}
+
+static inline bool bayer_code_ok(int code) { return code >= RELOC_BAYER_BG2BGR && code <= RELOC_BAYER_GR2BGR; }
+
+// one demosaic launch for n mosaics of w x h (>= 3 x 3) on stream st; oc: 3 -> interleaved BGR, 1 -> gray (flags: the
+// coefficient set; the channel-order bit has no meaning for a mosaic)
+static int bayer_launch(hipStream_t st, const BayerFrames &F, int n, int w, int h, int sstride, int dstride, int code, int oc, int flags)
+{
+    bool aligned = w % 4 == 0 && sstride % 4 == 0;
+    for (int f = 0; f < n; ++f) aligned = aligned && ((uintptr_t)F.src[f]) % 4 == 0 && ((uintptr_t)F.dst[f]) % 4 == 0;
+    // BG (46): R G / G B   GB (47): G R / B G   RG (48): B G / G R   GR (49): G B / R G
+    const int green_par = (code & 1) ^ 1, blue_par = ((code - RELOC_BAYER_BG2BGR) >> 1) ^ 1;
+    auto kern = oc == 3 ? (aligned ? k_bayer<3, true> : k_bayer<3, false>) : (aligned ? k_bayer<1, true> : k_bayer<1, false>);
+    hipLaunchKernelGGL(kern, dim3((((w + 3) / 4) * h + 255) / 256, n), dim3(256), 0, st, F, w, h, sstride, dstride, green_par, blue_par,
+                       flags & RELOC_GRAY_FLAG_15BIT);
+    HIP_TRY(hipGetLastError());
+    return RELOC_OK;
 }
 
 // ---- CLAHE (include/reloc_spec.h) -------------------------------------------------------------------
@@ -750,6 +864,9 @@ static int resize_launch(hipStream_t st, const ResizeFrames &F, int n, const Res
 }
 
 // ---- image chain ----------------------------------------------------------------------------------------------
+// bytes per pixel of the frames that enter the chain through orb_run: a raw mosaic with the Bayer stage on, else 3 channels
+int image_chain_frame_bpp(const reloc_ctx *c) { return c->bayer_code ? 1 : 3; }
+
 // a frame or depth image of *w x *h enters the downscale stage of c: *w x *h becomes the working frame
 static int resize_enter(const reloc_ctx *c, int *w, int *h)
 {
@@ -765,8 +882,8 @@ static int rectify_enter(const reloc_ctx *c, int w, int h)
     return RELOC_E_ARG;
 }
 
-// Before orb_prepare: the contexts agree on the downscale stage, a 3-channel frame has its source size; w x h becomes the
-// working frame, which orb_prepare and everything downstream see.
+// Before orb_prepare: the contexts agree on the Bayer and the downscale stage, a frame has the latter's source size; w x h
+// becomes the working frame, which orb_prepare and everything downstream see.
 int image_chain_check(reloc_ctx *const *ctxs, int n, int channels, int *w, int *h)
 {
     const reloc_ctx *c0 = ctxs[0];
@@ -774,6 +891,10 @@ int image_chain_check(reloc_ctx *const *ctxs, int n, int channels, int *w, int *
         const reloc_ctx *c = ctxs[f];
         if (c->rsz_sw != c0->rsz_sw || c->rsz_sh != c0->rsz_sh || c->rsz_dw != c0->rsz_dw || c->rsz_dh != c0->rsz_dh) {
             reloc_set_error("orb batch: contexts with and without the downscale stage, or with unequal sizes (reloc_set_resize)");
+            return RELOC_E_STATE;
+        }
+        if (c->bayer_code != c0->bayer_code) {
+            reloc_set_error("orb batch: contexts with and without the Bayer stage, or of unequal patterns (reloc_set_bayer)");
             return RELOC_E_STATE;
         }
     }
@@ -799,27 +920,32 @@ int image_chain_check_prepared(reloc_ctx *const *ctxs, int f, int n, int channel
     return f == n - 1 && channels == 3 && c0->rect_w > 0 ? rectify_enter(c0, w, h) : RELOC_OK;
 }
 
-// The gray half, on the stream of the (checked) contexts: 3-channel frames *srcs of sw x sh, rows of *stride bytes, go through
-// the stages that are on, each into its context's plane; the first one converts to gray.  Afterwards *srcs (= planes, the
-// caller's array) / *stride / *channels describe the last plane written.  A caller's gray plane passes untouched.
+// The gray half, on the stream of the (checked) contexts: frames *srcs of sw x sh, rows of *stride bytes (3 channels, or raw
+// mosaics with the Bayer stage on), go through the stages that are on, each into its context's plane; the first one converts
+// to gray.  Afterwards *srcs (= planes, the caller's array) / *stride / *channels describe the last plane written.  A
+// caller's gray plane passes untouched.
 int image_chain_gray(reloc_ctx *const *ctxs, int n, const uint8_t *const **srcs, int sw, int sh, int w, int h, int *stride,
                      int *channels, int flags, const uint8_t **planes)
 {
     if (*channels != 3) return RELOC_OK;
     const reloc_ctx *c0 = ctxs[0];
-    enum { STAGE_RESIZE, STAGE_RECTIFY, STAGE_CLAHE, N_STAGES };       // the order of the chain
-    const bool on[N_STAGES] = {c0->rsz_dw > 0, c0->rect_w > 0, c0->clahe_tx > 0};
-    const int cs = plane_stride(w);
+    enum { STAGE_BAYER, STAGE_RESIZE, STAGE_RECTIFY, STAGE_CLAHE, N_STAGES };       // the order of the chain
+    const bool on[N_STAGES] = {c0->bayer_code != 0, c0->rsz_dw > 0, c0->rect_w > 0, c0->clahe_tx > 0};
     for (int s = 0; s < N_STAGES; ++s) {
         if (!on[s]) continue;
         const uint8_t *const *in = *srcs;
+        const int cs = plane_stride(s == STAGE_BAYER ? sw : w);        // the mosaic's plane has the source size
         int rc;
-        if (s == STAGE_RESIZE) {
+        if (s == STAGE_BAYER) {
+            BayerFrames F = {};
+            for (int f = 0; f < n; ++f) { F.src[f] = in[f]; planes[f] = F.dst[f] = ctxs[f]->bayer_plane; }
+            rc = bayer_launch(c0->stream, F, n, sw, sh, *stride, cs, c0->bayer_code, 1, flags);
+        } else if (s == STAGE_RESIZE) {
             ResizeFrames F = {};
             for (int f = 0; f < n; ++f) { F.src[f] = in[f]; F.tab[f] = ctxs[f]->rsz_tab; planes[f] = F.dst[f] = ctxs[f]->rsz_plane; }
             ResizePlan P;
             P.kind = c0->rsz_kind; P.isx = c0->rsz_isx; P.isy = c0->rsz_isy;
-            rc = resize_launch(c0->stream, F, n, P, sw, sh, *stride, w, h, cs, 3, 1, true, flags);
+            rc = resize_launch(c0->stream, F, n, P, sw, sh, *stride, w, h, cs, *channels, 1, *channels == 3, flags);
         } else if (s == STAGE_RECTIFY) {
             RemapFrames F = {};
             for (int f = 0; f < n; ++f) { F.src[f] = in[f]; F.xy[f] = ctxs[f]->rect_xy; F.alpha[f] = ctxs[f]->rect_alpha; planes[f] = F.dst[f] = ctxs[f]->rect_plane; }
@@ -887,6 +1013,36 @@ RELOC_API int reloc_gray_u8(reloc_ctx *ctx, const uint8_t *img, int w, int h, in
         HIP_TRY(hipGetLastError());
         return RELOC_OK;
     });
+}
+
+// ---- Bayer entry points --------------------------------------------------------------------------------
+RELOC_API int reloc_bayer_u8(reloc_ctx *ctx, const uint8_t *raw, int w, int h, int stride, int code, uint8_t *out_bgr)
+{
+    ARG_CHECK_CTX(ctx, raw && out_bgr && w >= 3 && h >= 3 && stride >= w, "reloc_bayer_u8: NULL pointer, or a mosaic below 3 x 3");
+    ARG_CHECK(bayer_code_ok(code), "reloc_bayer_u8: code must be one of COLOR_BayerBG2BGR .. COLOR_BayerGR2BGR (46..49)");
+    if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
+    return host_round_trip(ctx, raw, w, h, stride, 0, out_bgr, (int64_t)w * h * 3, [&](uint8_t *dout) {
+        BayerFrames F = {};
+        F.src[0] = ctx->frame_img; F.dst[0] = dout;
+        return bayer_launch(ctx->stream, F, 1, w, h, w, 3 * w, code, 3, 0);
+    });
+}
+
+RELOC_API int reloc_set_bayer(reloc_ctx *ctx, int code)
+{
+    ARG_CHECK_CTX(ctx, true, "ctx is NULL");
+    ARG_CHECK(code == 0 || bayer_code_ok(code), "reloc_set_bayer: code must be 0 (off) or one of COLOR_BayerBG2BGR .. COLOR_BayerGR2BGR (46..49)");
+    // first enable: the gray plane of the largest mosaic
+    if (code && !ctx->bayer_plane) HIP_TRY(hipMalloc((void **)&ctx->bayer_plane, stage_plane_bytes(ctx)));
+    ctx->bayer_code = code;
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_get_bayer(reloc_ctx *ctx, int32_t *code)
+{
+    ARG_CHECK_CTX(ctx, code, "reloc_get_bayer");
+    *code = ctx->bayer_code;
+    return RELOC_OK;
 }
 
 // ---- CLAHE entry points -------------------------------------------------------------------------------

@@ -343,6 +343,10 @@ struct reloc_ctx {
     uint8_t *rsz_plane = nullptr;        // resized gray plane, row stride (dw + 63) & ~63
     uint16_t *rsz_depth = nullptr;       // resized depth (nearest), dense rows of rsz_dw
 
+    // ---- Bayer stage in front of the whole image chain (reloc_set_bayer); 0 = off, the default ----
+    int bayer_code = 0;                  // RELOC_BAYER_*2BGR: every frame of the chain's entry points is a raw 8-bit mosaic
+    uint8_t *bayer_plane = nullptr;      // demosaiced gray plane, row stride (w + 63) & ~63 (allocated on first enable)
+
     // ---- matcher parameters (reloc_set_params) ----
     reloc_params prm;
     int scan_gens = 0;               // RELOC_SCAN_GENS (developer switch), read once at creation: n > 0 = single whole-database
@@ -428,15 +432,18 @@ int db_reindex(reloc_ctx *ctx);
 int db_reserve(reloc_ctx *ctx, int64_t cap_records, int64_t cap_rows);
 inline bool db_ready(const reloc_ctx *ctx) { return ctx->db_desc && ctx->db_off && ctx->db_pose && ctx->db_xy_heading && ctx->db_counts && ctx->db_records > 0; }
 int orb_prepare(reloc_ctx *ctx, int w, int h, int nfeatures);
-// ORB of frame f = srcs[f] into ctxs[f]'s feature buffers; channels == 3 -> interleaved frames (gray fused; the image chain
-// first when the contexts have stages on; with the downscale stage on, w x h is the source size and the features are those
-// of the working frame), channels == 1 -> gray planes (reloc_orb.hip)
+// ORB of frame f = srcs[f] into ctxs[f]'s feature buffers; channels == 3 -> the frames of the image chain: interleaved
+// 3-channel frames (gray fused), or raw mosaics of image_chain_frame_bpp = 1 byte per pixel with the Bayer stage on; the
+// chain first when the contexts have stages on; with the downscale stage on, w x h is the source size and the features are
+// those of the working frame.  channels == 1 -> gray planes, never through the chain (reloc_orb.hip)
 int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, int h, int stride, int channels, int order,
             int nfeatures, bool latency);
-// The image chain of a context's stages, resize -> rectify -> CLAHE (reloc_image.hip).  The checks stand before orb_prepare
-// (the downscale stage; w x h becomes the working frame) and behind that of context f (rectification, CLAHE); _gray runs the
-// stages on 3-channel frames and leaves *srcs / *stride / *channels describing the last plane written; _depth takes a
-// depth image through resize and rectification (nearest), *w x *h becomes the working frame.
+// The image chain of a context's stages (reloc_image.hip states their order).  The checks stand before orb_prepare (the Bayer
+// and the downscale stage; w x h becomes the working frame) and behind that of context f (rectification, CLAHE); _gray runs
+// the stages on the frames and leaves *srcs / *stride / *channels describing the last plane written; _depth takes a
+// depth image through resize and rectification (nearest), *w x *h becomes the working frame; _frame_bpp: bytes per pixel of
+// the frames that the entry points take (3, or 1 for raw mosaics).
+int image_chain_frame_bpp(const reloc_ctx *c);
 int image_chain_check(reloc_ctx *const *ctxs, int n, int channels, int *w, int *h);
 int image_chain_check_prepared(reloc_ctx *const *ctxs, int f, int n, int channels, int w, int h);
 int image_chain_gray(reloc_ctx *const *ctxs, int n, const uint8_t *const **srcs, int sw, int sh, int w, int h, int *stride,

@@ -1167,10 +1167,11 @@ static OrbFrame orb_frame(const reloc_ctx *c, const uint8_t *src)
     return F;
 }
 
-// Five launches behind the image chain (reloc_image.hip): the frames are of equal geometry.  The chain serves 3-channel
-// frames only, never a caller's gray plane; with the downscale stage on, w x h is the source size and everything from
-// orb_prepare on sees the working frame.  The pyramid reads the last plane the chain wrote, or the frame itself.  It runs
-// 512-thread workgroups for latency, 256 where it shares the chip with whole-database scans.
+// Five launches behind the image chain (reloc_image.hip): the frames are of equal geometry.  The chain serves the frames
+// of channels == 3 (3-channel, or raw mosaics with the Bayer stage on), never a caller's gray plane; with the downscale
+// stage on, w x h is the source size and everything from orb_prepare on sees the working frame.  The pyramid reads the last
+// plane the chain wrote, or the frame itself.  It runs 512-thread workgroups for latency, 256 where it shares the chip with
+// whole-database scans.
 int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, int h, int stride, int channels, int order,
             int nfeatures, bool latency)
 {
@@ -1234,7 +1235,8 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
 
 RELOC_API int reloc_orb_frame_dev(reloc_ctx *ctx, const uint8_t *img_dev, int w, int h, int stride, int order, int nfeatures)
 {
-    ARG_CHECK_CTX(ctx, img_dev && w >= 64 && h >= 64 && stride >= 3 * w && nfeatures > 0, "reloc_orb_frame_dev");
+    ARG_CHECK_CTX(ctx, img_dev && w >= 64 && h >= 64 && nfeatures > 0, "reloc_orb_frame_dev");
+    ARG_CHECK(stride >= w * image_chain_frame_bpp(ctx), "reloc_orb_frame_dev");
     return orb_run(&ctx, 1, &img_dev, w, h, stride, 3, order, nfeatures, true);
 }
 

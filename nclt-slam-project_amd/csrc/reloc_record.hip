@@ -142,10 +142,11 @@ RELOC_API int reloc_record_frame(reloc_ctx *ctx, const uint8_t *img, const uint1
     uint8_t *o_desc = (uint8_t *)dout;
     float *o_xy = (float *)(o_desc + mf * 32), *o_pts = o_xy + mf * 2;
     int32_t *o_idx = (int32_t *)(o_pts + mf * 3), *o_n = o_idx + mf;
-    HIP_TRY(hipMemcpyAsync(ctx->frame_img, img, (size_t)w * h * 3, hipMemcpyHostToDevice, ctx->stream));
+    const int bpp = image_chain_frame_bpp(ctx);
+    HIP_TRY(hipMemcpyAsync(ctx->frame_img, img, (size_t)w * h * bpp, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(ddepth, depth_mm, (size_t)w * h * 2, hipMemcpyHostToDevice, ctx->stream));
     const uint8_t *src = ctx->frame_img;
-    if ((rc = orb_run(&ctx, 1, &src, w, h, w * 3, 3, order, nfeatures, true))) return rc;
+    if ((rc = orb_run(&ctx, 1, &src, w, h, w * bpp, 3, order, nfeatures, true))) return rc;
     const uint16_t *depth = (const uint16_t *)ddepth;
     if ((rc = image_chain_depth(ctx, depth, &w, &h, &depth))) return rc;      // from here on the working frame
     RecordParams p;

@@ -813,7 +813,7 @@ static int tick_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *imgs, i
     if (c0->max_feat > 65535) { reloc_set_error("tick: max_feat must be <= 65535"); return RELOC_E_CAPACITY; }
     const bool latency = tick_latency(ctxs, n, mode);
     int rc;
-    if ((rc = orb_run(ctxs, n, imgs, w, h, w * 3, 3, order, c0->prm.nfeatures, latency))) return rc;
+    if ((rc = orb_run(ctxs, n, imgs, w, h, w * image_chain_frame_bpp(c0), 3, order, c0->prm.nfeatures, latency))) return rc;
     if (mode != RELOC_TICK_GLOBAL)
         for (int f = 0; f < n; ++f) launch_candidates_local(ctxs[f], make_tick_params(ctxs[f], base_poses + 7 * f, mode, -1));
     if (mode != RELOC_TICK_LOCAL) {
@@ -830,7 +830,8 @@ static int scan_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *imgs, i
                     const TopkBatch &out, int k, int id_base)
 {
     int rc;
-    if ((rc = orb_run(ctxs, n, imgs, w, h, w * 3, 3, order, ctxs[0]->prm.nfeatures, tick_latency(ctxs, n, RELOC_TICK_GLOBAL))))
+    if ((rc = orb_run(ctxs, n, imgs, w, h, w * image_chain_frame_bpp(ctxs[0]), 3, order, ctxs[0]->prm.nfeatures,
+                      tick_latency(ctxs, n, RELOC_TICK_GLOBAL))))
         return rc;
     if ((rc = scan_counts(ctxs, n, base_poses, false))) return rc;
     launch_topk_counts(ctxs, n, out, k, id_base);
@@ -935,7 +936,7 @@ RELOC_API int reloc_tick(reloc_ctx *ctx, const uint8_t *img, int w, int h, int o
 {
     ARG_CHECK_CTX(ctx, img && base_pose && w >= 64 && h >= 64, "reloc_tick");
     if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
-    HIP_TRY(hipMemcpyAsync(ctx->frame_img, img, (size_t)w * h * 3, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->frame_img, img, (size_t)w * h * image_chain_frame_bpp(ctx), hipMemcpyHostToDevice, ctx->stream));
     int rc = reloc_tick_dev(ctx, ctx->frame_img, w, h, order, base_pose, global_reloc, seed);
     if (rc) return rc;
     return reloc_tick_result(ctx, anchor_pose, n_inl, reproj, lm_idx, outcome, n_candidates);

@@ -15,6 +15,9 @@ vectors (rational, thin-prism, tilted) are accepted only when every coefficient 
 
 CLAHE is OpenCV's 8-bit algorithm (include/reloc_spec.h); 16-bit and colour input raise.
 
+cvtColor with a COLOR_Bayer??2BGR / 2RGB code is OpenCV's bilinear 8-bit demosaicing (include/reloc_spec.h, "BAYER") of an
+(H, W) mosaic of at least 3 x 3; 16-bit mosaics and the _VNG, _EA, 2BGRA and direct 2GRAY codes raise.
+
 remap is OpenCV's fixed-point bilinear / nearest remap with BORDER_CONSTANT (include/reloc_spec.h, "REMAP") on the backend;
 the map builders run in NumPy float64 on the host (once per camera) and honour all 14 coefficients of the default model and
 the four of the fisheye model.  Other interpolation or border modes, other dtypes and map types raise.
@@ -39,6 +42,25 @@ NORM_HAMMING2 = 7
 NORM_L2 = 4
 COLOR_BGR2GRAY = 6
 COLOR_RGB2GRAY = 7
+# Bayer demosaicing: the two letters are the colours of pixels (row 1, col 1) and (row 1, col 2); a 2RGB code is OpenCV's alias
+# of the 2BGR code with red and blue swapped, and the sensor-named spellings (the top-left 2 x 2 tile) alias both
+COLOR_BayerBG2BGR = COLOR_BayerRG2RGB = COLOR_BayerRGGB2BGR = COLOR_BayerBGGR2RGB = 46
+COLOR_BayerGB2BGR = COLOR_BayerGR2RGB = COLOR_BayerGRBG2BGR = COLOR_BayerGBRG2RGB = 47
+COLOR_BayerRG2BGR = COLOR_BayerBG2RGB = COLOR_BayerBGGR2BGR = COLOR_BayerRGGB2RGB = 48
+COLOR_BayerGR2BGR = COLOR_BayerGB2RGB = COLOR_BayerGBRG2BGR = COLOR_BayerGRBG2RGB = 49
+# known to OpenCV, refused here (cvtColor says why)
+COLOR_BayerBG2BGR_VNG, COLOR_BayerGB2BGR_VNG, COLOR_BayerRG2BGR_VNG, COLOR_BayerGR2BGR_VNG = 62, 63, 64, 65
+COLOR_BayerBG2GRAY, COLOR_BayerGB2GRAY, COLOR_BayerRG2GRAY, COLOR_BayerGR2GRAY = 86, 87, 88, 89
+COLOR_BayerBG2BGR_EA, COLOR_BayerGB2BGR_EA, COLOR_BayerRG2BGR_EA, COLOR_BayerGR2BGR_EA = 135, 136, 137, 138
+COLOR_BayerBG2BGRA, COLOR_BayerGB2BGRA, COLOR_BayerRG2BGRA, COLOR_BayerGR2BGRA = 139, 140, 141, 142
+_BAYER_CODES = (46, 47, 48, 49)
+_BAYER_REFUSED = {
+    **{c: "the _VNG (variable number of gradients) demosaicing is not implemented; use the bilinear COLOR_Bayer??2BGR" for c in range(62, 66)},
+    **{c: "the direct COLOR_Bayer??2GRAY codes are not implemented (OpenCV rounds them on a path of its own); use "
+          "cvtColor(cvtColor(raw, COLOR_Bayer??2BGR), COLOR_BGR2GRAY)" for c in range(86, 90)},
+    **{c: "the _EA (edge-aware) demosaicing is not implemented; use the bilinear COLOR_Bayer??2BGR" for c in range(135, 139)},
+    **{c: "the COLOR_Bayer??2BGRA codes are not implemented; use COLOR_Bayer??2BGR" for c in range(139, 143)},
+}
 SOLVEPNP_ITERATIVE = 0
 SOLVEPNP_EPNP = 1
 SOLVEPNP_P3P = 2
@@ -425,12 +447,30 @@ class Cv2Shim:
 
     def cvtColor(self, src, code):
         img = np.asarray(src)
+        if code in _BAYER_REFUSED:
+            raise error("cvtColor: " + _BAYER_REFUSED[code])
+        if code in _BAYER_CODES:
+            return self._demosaic(img, code)
         if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
             raise error("cvtColor: expected an (H, W, 3) uint8 image")
         if code not in (COLOR_BGR2GRAY, COLOR_RGB2GRAY):
             raise error("cvtColor: only COLOR_BGR2GRAY / COLOR_RGB2GRAY are implemented")
         try:
             return self.backend.gray(img, order_rgb=(code == COLOR_RGB2GRAY))
+        except RelocError as e:
+            raise error(str(e)) from e
+
+    def _demosaic(self, img, code):
+        """cvtColor(raw, COLOR_Bayer??2BGR | 2RGB): (H, W) uint8 mosaic -> (H, W, 3)"""
+        if img.dtype == np.uint16:
+            raise error("cvtColor: 16-bit Bayer mosaics are not implemented (8-bit only)")
+        if img.dtype != np.uint8 or img.ndim != 2:
+            raise error("cvtColor: a Bayer code expects an (H, W) uint8 single-channel mosaic")
+        if img.shape[0] < 3 or img.shape[1] < 3:
+            raise error("cvtColor: a Bayer mosaic must be at least 3 x 3")
+        fn = self._backend("bayer", "cvtColor(Bayer)")
+        try:
+            return fn(img, code)
         except RelocError as e:
             raise error(str(e)) from e
 
@@ -690,6 +730,11 @@ class Cv2Shim:
             r = np.zeros(3) if n < 1e-12 else ax / n * th
             return r.reshape(3, 1), None
         raise error("Rodrigues: expected a 3-vector or a 3x3 matrix")
+
+
+for _name, _value in list(globals().items()):       # the Bayer codes as attributes of a shim object too
+    if _name.startswith("COLOR_Bayer"):
+        setattr(Cv2Shim, _name, _value)
 
 
 # ---- module-level API bound to one lazily created HIP engine ---------------------------------------

@@ -41,6 +41,7 @@ class Engine:
             raise N.RelocError("reloc_create failed: " + N.last_error())
         self.device = device
         self.max_w, self.max_h, self.max_feat = max_w, max_h, max_feat
+        self._bayer = None          # set_bayer's code: the frames of tick / record_frame are then (H, W) mosaics
 
     # ------------------------------------------------------------------ lifetime / plumbing
     def close(self):
@@ -342,11 +343,50 @@ class Engine:
         N.check(self._lib.reloc_get_resize(self._ctx, *(C.byref(t) for t in v)), "reloc_get_resize")
         return None if v[2].value == 0 else ((v[0].value, v[1].value), (v[2].value, v[3].value))
 
+    def bayer(self, raw: np.ndarray, code: int) -> np.ndarray:
+        """cv2.cvtColor(raw, code) of an (H, W) uint8 Bayer mosaic of at least 3 x 3 with code = COLOR_BayerBG2BGR (46),
+        GB (47), RG (48) or GR (49), bilinear: (H, W, 3) uint8 BGR (reloc_bayer_u8)"""
+        raw = np.asarray(raw)
+        if raw.dtype != np.uint8 or raw.ndim != 2:
+            raise N.RelocError("bayer: expected an (H, W) uint8 mosaic")
+        h, w = raw.shape
+        if w < 3 or h < 3:
+            raise N.RelocError("bayer: the mosaic must be at least 3 x 3")
+        if raw.strides[1] != 1 or raw.strides[0] < w:
+            raw = np.ascontiguousarray(raw)
+        out = np.empty((h, w, 3), np.uint8)
+        N.check(self._lib.reloc_bayer_u8(self._ctx, C.c_void_p(raw.ctypes.data), w, h, raw.strides[0], int(code), N.ptr(out)),
+                "reloc_bayer_u8")
+        return out
+
+    def set_bayer(self, code: int | None = None):
+        """The raw-sensor stage in front of the whole image chain (reloc_set_bayer): with code = COLOR_BayerBG2BGR (46), GB (47),
+        RG (48) or GR (49) every frame of the fused tick, recording and reloc_orb_frame_dev is an (H, W) uint8 mosaic,
+        demosaiced and converted to gray before resize, rectification, CLAHE and ORB.  None / 0 = off."""
+        code = int(code or 0)
+        N.check(self._lib.reloc_set_bayer(self._ctx, code), "reloc_set_bayer")
+        self._bayer = code or None
+
+    def get_bayer(self):
+        """None when off, else the code"""
+        v = C.c_int32()
+        N.check(self._lib.reloc_get_bayer(self._ctx, C.byref(v)), "reloc_get_bayer")
+        return v.value or None
+
+    def _frame(self, img, what):
+        """the frame of a host-pointer entry point of the image chain: (H, W, 3), or (H, W) with the Bayer stage on"""
+        img = N.u8(img)
+        if img.ndim != (2 if self._bayer else 3) or (img.ndim == 3 and img.shape[2] != 3):
+            raise N.RelocError(f"{what}: expected an (H, W) uint8 mosaic (set_bayer is on)" if self._bayer
+                               else f"{what}: expected an (H, W, 3) uint8 frame")
+        return img
+
     def record_frame(self, bgr: np.ndarray, depth_mm: np.ndarray, nfeatures: int = 500, order_rgb: bool = False):
-        """teach-side record arrays of one frame: dict(xy (n,2), desc (n,32), pts3d (n,3), kp_index (n,), n, n_kp)"""
-        bgr = N.u8(bgr)
+        """teach-side record arrays of one frame: dict(xy (n,2), desc (n,32), pts3d (n,3), kp_index (n,), n, n_kp); bgr:
+        (H, W, 3), or the (H, W) mosaic with the Bayer stage on"""
+        bgr = self._frame(bgr, "record_frame")
         depth_mm = np.ascontiguousarray(depth_mm, np.uint16)
-        h, w, _ = bgr.shape
+        h, w = bgr.shape[:2]
         if depth_mm.shape != (h, w):
             raise N.RelocError("record_frame: depth and colour sizes differ")
         mf = self.max_feat
@@ -602,8 +642,9 @@ class Engine:
                     reproj=rep[:k].copy(), Rt=Rt[:k].copy())
 
     def tick(self, img, base_pose, order_rgb=False, global_reloc=False, seed=0):
-        img = N.u8(img)
-        h, w, _ = img.shape
+        """img: (H, W, 3), or the (H, W) mosaic with the Bayer stage on"""
+        img = self._frame(img, "tick")
+        h, w = img.shape[:2]
         bp = np.ascontiguousarray(base_pose, np.float64).reshape(7)
         anchor = np.zeros(7); n_inl = C.c_int32(); rep = C.c_float(); lm = C.c_int32(); oc = C.c_int32(); nc = C.c_int32()
         N.check(self._lib.reloc_tick(self._ctx, N.ptr(img), w, h, int(order_rgb), N.ptr(bp), int(global_reloc), int(seed),
@@ -672,9 +713,10 @@ class Engine:
                 "reloc_tick_scan_dev")
 
     def orb_frame_dev(self, img_dev: int, w: int, h: int, stride: int | None = None, order_rgb=False, nfeatures: int = 500) -> int:
-        """gray + ORB of an interleaved 3-channel frame resident in device memory (reloc_orb_frame_dev); returns the
-        number of keypoints (synchronises).  Descriptors / coordinates stay on the device; frame_debug_plane() reads planes."""
-        N.check(self._lib.reloc_orb_frame_dev(self._ctx, C.c_void_p(img_dev), int(w), int(h), int(stride or 3 * w),
+        """gray + ORB of an interleaved 3-channel frame (with the Bayer stage on: a single-channel mosaic, stride in its bytes)
+        resident in device memory (reloc_orb_frame_dev); returns the number of keypoints (synchronises).  Descriptors /
+        coordinates stay on the device; frame_debug_plane() reads planes."""
+        N.check(self._lib.reloc_orb_frame_dev(self._ctx, C.c_void_p(img_dev), int(w), int(h), int(stride or (1 if self._bayer else 3) * w),
                                               int(order_rgb), int(nfeatures)), "reloc_orb_frame_dev")
         nf = np.empty(1, np.int32)
         N.check(self._lib.reloc_d2h(self._ctx, N.ptr(nf), C.c_void_p(self._lib.reloc_frame_count_dev(self._ctx)), 4), "reloc_d2h")

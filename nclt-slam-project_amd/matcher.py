@@ -48,6 +48,12 @@ class MatcherConfig:
     # INTER_NEAREST).  fx, fy, cx, cy, the rectification map and every coordinate are then those of the resized image
     # (scaled_camera).  The fused matcher's Engine must be created for the camera's full size.  Teach with the same size.
     resize: tuple | None = None
+    # raw colour camera: None = the frames are 3-channel BGR (the reference matcher), or the Bayer pattern of the 8-bit
+    # single-channel mosaics the camera delivers, in OpenCV's letters as in cv2.cvtColor(raw, cv2.COLOR_BayerGR2BGR) of the
+    # RobotCar pipeline: "BG" (sensor name RGGB), "GB" (GRBG), "RG" (BGGR) or "GR" (GBRG, RobotCar's "gbrg").  Every frame is
+    # then an (H, W) uint8 mosaic, demosaiced (bilinear) and converted to gray at the head of the image chain; resize takes
+    # the mosaic's size as its source.  Teach with the same pattern.
+    bayer: str | None = None
     candidate_radius_m: float = 8.0
     max_candidates: int = 5
     heading_tol_deg: float = 90.0
@@ -114,6 +120,19 @@ def resize_setting(size):
     return (w, h)
 
 
+BAYER_CODES = {"BG": 46, "GB": 47, "RG": 48, "GR": 49}      # cv2.COLOR_Bayer??2BGR
+
+
+def bayer_setting(pattern):
+    """MatcherConfig.bayer / the recorder's bayer= as OpenCV's COLOR_Bayer??2BGR code (None stays None)"""
+    if pattern is None:
+        return None
+    code = BAYER_CODES.get(str(pattern).upper())
+    if code is None:
+        raise ValueError('bayer must be None or one of "BG", "GB", "RG", "GR" (OpenCV\'s letters: RGGB, GRBG, BGGR, GBRG sensors)')
+    return code
+
+
 def fixed_rectify_maps(cv2, maps):
     """MatcherConfig.rectify as the fixed-point pair cv2.remap reads for both interpolations (None stays None)"""
     if maps is None:
@@ -125,16 +144,26 @@ def fixed_rectify_maps(cv2, maps):
 
 
 class ImageChain:
-    """The image chain between gray conversion and ORB on the cv2-shaped path, stated here only: resize -> rectify -> CLAHE,
-    the depth following the first two with INTER_NEAREST.  clahe, rectify, resize: as MatcherConfig's; cv2 None: never applied."""
-    def __init__(self, cv2, clahe=None, rectify=None, resize=None):
+    """The image chain between the camera frame and ORB on the cv2-shaped path, stated here only: [demosaic] -> gray ->
+    resize -> rectify -> CLAHE, the depth following resize and rectify with INTER_NEAREST.  clahe, rectify, resize, bayer: as
+    MatcherConfig's; cv2 None: never applied."""
+    def __init__(self, cv2, clahe=None, rectify=None, resize=None, bayer=None):
         self.cv2 = cv2
+        self.bayer = bayer_setting(bayer)
         self.clahe = None if cv2 is None or clahe is None else cv2.createCLAHE(clipLimit=clahe[0], tileGridSize=tuple(clahe[1]))
         self.rectify = fixed_rectify_maps(cv2, rectify) if cv2 is not None else None
         self.resize = resize_setting(resize)
 
-    def apply(self, gray, depth_mm=None):
+    def gray(self, frame):
+        """the camera frame as gray: a BGR frame, or a raw mosaic through the two cvtColor calls of the reference"""
         cv2 = self.cv2
+        if self.bayer is not None:
+            frame = cv2.cvtColor(frame, self.bayer)
+        return cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY)
+
+    def apply(self, frame, depth_mm=None):
+        cv2 = self.cv2
+        gray = self.gray(frame)
         if self.resize is not None:
             gray = cv2.resize(gray, self.resize, interpolation=cv2.INTER_AREA)
             depth_mm = None if depth_mm is None else cv2.resize(depth_mm, self.resize, interpolation=cv2.INTER_NEAREST)
@@ -146,8 +175,9 @@ class ImageChain:
         return gray, depth_mm
 
 
-def configure_engine(engine, clahe=None, rectify=None, resize=None):
-    """the same three settings on an Engine, which is as large as the camera"""
+def configure_engine(engine, clahe=None, rectify=None, resize=None, bayer=None):
+    """the same four settings on an Engine, which is as large as the camera"""
+    engine.set_bayer(bayer_setting(bayer))
     engine.set_clahe(*((None,) if clahe is None else (clahe[0], tuple(clahe[1]))))
     engine.set_resize(*((None, None) if resize is None else ((engine.max_w, engine.max_h), resize_setting(resize))))
     engine.set_rectify(rectify)
@@ -169,7 +199,7 @@ class LandmarkMatcherCore:
         self._adopt(load_landmarks(landmarks) if isinstance(landmarks, str) else landmarks)
         self.orb = cv2.ORB_create(nfeatures=self.cfg.nfeatures)
         self.matcher = cv2.BFMatcher(cv2.NORM_HAMMING, crossCheck=True)
-        self.chain = c = ImageChain(cv2, self.cfg.clahe, self.cfg.rectify, self.cfg.resize)
+        self.chain = c = ImageChain(cv2, self.cfg.clahe, self.cfg.rectify, self.cfg.resize, self.cfg.bayer)
         self.clahe, self.rectify, self.resize = c.clahe, c.rectify, c.resize
         self.dist = np.zeros((4, 1), dtype=np.float32) if len(self.cfg.dist) == 0 else np.asarray(self.cfg.dist, np.float64).reshape(-1, 1)
         self.last_anchor_ts = 0.0
@@ -301,7 +331,8 @@ class LandmarkMatcherCore:
         return len(inliers), err, P.cam_world_to_base_world(cam_world, self.base_to_cam_t, self.base_to_cam_R)
 
     def tick(self, bgr, depth_mm, base_pose, ts=None, drift_est=0.0):
-        """One repeat attempt.  bgr: (H,W,3) u8; depth_mm: (H,W) u16 or None; base_pose: 7-tuple."""
+        """One repeat attempt.  bgr: (H,W,3) u8, or the (H,W) u8 mosaic of a raw camera (cfg.bayer); depth_mm: (H,W) u16 or
+        None; base_pose: 7-tuple."""
         cfg, cv2 = self.cfg, self.cv2
         self.maybe_swap_to_return()
         if bgr is None or base_pose is None:
@@ -310,7 +341,7 @@ class LandmarkMatcherCore:
         self.n_attempts += 1
         vio_xy = (base_pose[0], base_pose[1])
         cand, d, herr = self.select_candidates(base_pose)
-        gray, depth_mm = self.chain.apply(cv2.cvtColor(bgr, cv2.COLOR_BGR2GRAY), depth_mm)
+        gray, depth_mm = self.chain.apply(bgr, depth_mm)
         kpts, desc = self.orb.detectAndCompute(gray, None)
         if desc is None or len(kpts) < cfg.min_matches:
             o = TickOutcome(ts, vio_xy, len(cand), 0, None, None, "curr_no_features")
@@ -418,7 +449,7 @@ class FusedLandmarkMatcher:
         e.set_camera([cfg.fx, cfg.fy, cfg.cx, cfg.cy], data.get("base_to_cam_translation", P.BASE_TO_CAM_TRANSLATION),
                      data.get("base_to_cam_rot", P.BASE_TO_CAM_ROT))
         e.set_distortion(cfg.dist)
-        configure_engine(e, cfg.clahe, cfg.rectify, cfg.resize)
+        configure_engine(e, cfg.clahe, cfg.rectify, cfg.resize, cfg.bayer)
         self._return_src = return_landmarks
         self.swap_flag = swap_flag
         self._swapped = False
@@ -498,7 +529,8 @@ class FusedLandmarkMatcher:
     def tick(self, bgr, base_pose, ts=None, global_reloc=None, depth_mm=None, drift_est=0.0):
         """One repeat attempt.  global_reloc: None = decide as the reference does (local candidates; the whole-database
         search only under G's trigger, when cfg.global_reloc is set), True = whole-database search unconditionally
-        (benchmark shape), False = local only.  depth_mm enables accumulation (cfg.accum_enable)."""
+        (benchmark shape), False = local only.  depth_mm enables accumulation (cfg.accum_enable).  bgr: (H,W,3) u8, or with
+        cfg.bayer the (H,W) u8 mosaic of the raw camera: a third of the bytes to upload."""
         cfg, e = self.cfg, self.engine
         self.maybe_swap_to_return()
         if bgr is None or base_pose is None:
@@ -511,7 +543,9 @@ class FusedLandmarkMatcher:
         else:
             mode = 1 if global_reloc else 0
         bgr = np.ascontiguousarray(bgr, np.uint8)
-        h, w, _ = bgr.shape
+        if bgr.ndim != (3 if cfg.bayer is None else 2):
+            raise ValueError("tick: expected an (H, W) mosaic" if cfg.bayer else "tick: expected an (H, W, 3) frame")
+        h, w = bgr.shape[:2]
         e.tick_dev(self._stage("img", bgr), w, h, base_pose, order_rgb=False, global_reloc=mode, seed=self.seed)
         accumulate = cfg.accum_enable and depth_mm is not None
         if accumulate:

@@ -41,7 +41,7 @@ def local_depth_std(depth_mm, uu, vv):
 
 class LandmarkRecorderCore:
     def __init__(self, out_pkl=None, min_disp_m: float = 2.0, cv2=None, nfeatures: int = 500, logger=None, engine=None,
-                 dist=(), clahe=None, rectify=None, resize=None):
+                 dist=(), clahe=None, rectify=None, resize=None, bayer=None):
         """engine: when given, ORB + all per-keypoint gates + back-projection run in ONE device call
         (reloc_record_frame); otherwise the gates run in NumPy on the cv2-shaped module's features.
         dist: lens distortion as MatcherConfig.dist (OpenCV's k1 k2 p1 p2 [k3], () = pinhole): the kept keypoints are
@@ -52,12 +52,15 @@ class LandmarkRecorderCore:
         ORB and the depth read through the same map, nearest (engine: reloc_set_rectify_map; cv2 path: cv2.remap).
         resize: None or (width, height) as MatcherConfig.resize: the gray frame is resized with INTER_AREA and the depth with
         INTER_NEAREST before the rectification; the camera and the map are those of the resized image (engine:
-        reloc_set_resize from the engine's full size, which must be the camera's; cv2 path: cv2.resize)."""
+        reloc_set_resize from the engine's full size, which must be the camera's; cv2 path: cv2.resize).
+        bayer: None or "BG" / "GB" / "RG" / "GR" as MatcherConfig.bayer (OpenCV's letters; sensor names RGGB / GRBG / BGGR /
+        GBRG): every frame is the (H, W) uint8 mosaic of a raw camera, demosaiced and converted to gray in front of the
+        resize (engine: reloc_set_bayer; cv2 path: cv2.cvtColor(raw, COLOR_Bayer??2BGR), then COLOR_BGR2GRAY)."""
         self.engine = engine
         self.dist = tuple(np.asarray(dist, np.float64).ravel()) if dist is not None else ()
         if engine is not None:
             engine.set_distortion(self.dist)
-            configure_engine(engine, clahe, rectify, resize)
+            configure_engine(engine, clahe, rectify, resize, bayer)
         self.nfeatures = nfeatures
         if cv2 is None and engine is None:
             from . import cv2_shim as cv2
@@ -65,7 +68,7 @@ class LandmarkRecorderCore:
         self.out_pkl = out_pkl
         self.min_disp_m = float(min_disp_m)
         self.orb = cv2.ORB_create(nfeatures=nfeatures) if cv2 is not None else None
-        self.chain = c = ImageChain(cv2, clahe, rectify, resize)
+        self.chain = c = ImageChain(cv2, clahe, rectify, resize, bayer)
         self.clahe, self.rectify, self.resize = c.clahe, c.rectify, c.resize
         self.landmarks = []
         self.last_landmark_pose_world = None
@@ -89,7 +92,7 @@ class LandmarkRecorderCore:
             self.landmarks.append(rec)
             self.last_landmark_pose_world = cam_pose
             return rec
-        gray, depth_mm = self.chain.apply(self.cv2.cvtColor(bgr, self.cv2.COLOR_BGR2GRAY), depth_mm)
+        gray, depth_mm = self.chain.apply(bgr, depth_mm)
         kpts, desc = self.orb.detectAndCompute(gray, None)
         if desc is None or len(kpts) == 0:
             return None

@@ -33,6 +33,20 @@ def img_msg_to_bgr(msg):
     raise ValueError(f"unsupported rgb encoding {msg.encoding}")
 
 
+BAYER_ENCODINGS = {"bayer_rggb8": "BG", "bayer_grbg8": "GB", "bayer_bggr8": "RG", "bayer_gbrg8": "GR"}     # sensor_msgs -> OpenCV's letters
+
+
+def img_msg_to_frame(msg, bayer=None):
+    """the colour topic's frame as the cores take it: BGR, or with bayer = "BG" / "GB" / "RG" / "GR" (MatcherConfig.bayer) the
+    camera's raw 8-bit mosaic, undecoded: mono8 (the driver does not name the pattern) or the bayer_* encoding of that pattern"""
+    if bayer is None:
+        return img_msg_to_bgr(msg)
+    if msg.encoding != "mono8" and BAYER_ENCODINGS.get(msg.encoding) != bayer.upper():
+        raise ValueError(f"encoding {msg.encoding} is not a raw 8-bit mosaic of pattern {bayer}")
+    step = getattr(msg, "step", 0) or msg.width
+    return np.frombuffer(msg.data, dtype=np.uint8).reshape(msg.height, step)[:, :msg.width].copy()
+
+
 def img_msg_to_depth_mm(msg):
     if msg.encoding in ("16UC1", "mono16"):
         return np.frombuffer(msg.data, dtype=np.uint16).reshape(msg.height, msg.width).copy()
@@ -64,8 +78,9 @@ def _node_base():
     return Node
 
 
-def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global_reloc=False, fused=False, cv2=None):
-    """cv2: the cv2-shaped module the ROS-free core calls (default: the HIP shim); only the non-fused core uses it"""
+def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global_reloc=False, fused=False, cv2=None, bayer=None):
+    """cv2: the cv2-shaped module the ROS-free core calls (default: the HIP shim); only the non-fused core uses it.
+    bayer: MatcherConfig.bayer -- the colour topic carries raw mosaics, passed through undecoded"""
     from geometry_msgs.msg import PoseWithCovarianceStamped
     from sensor_msgs.msg import Image
     Node = _node_base()
@@ -73,7 +88,7 @@ def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global
     class VisualLandmarkMatcher(Node):
         def __init__(self):
             super().__init__("visual_landmark_matcher")
-            cfg = MatcherConfig(global_reloc=global_reloc)
+            cfg = MatcherConfig(global_reloc=global_reloc, bayer=bayer)
             if fused:
                 self.core = FusedLandmarkMatcher(pkl_path, log_csv, config=cfg, return_landmarks=return_pkl,
                                                  swap_flag=swap_flag, logger=lambda m: self.get_logger().info(m),
@@ -94,7 +109,7 @@ def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global
 
         def _rgb_cb(self, msg):
             try:
-                self.last_rgb = img_msg_to_bgr(msg)
+                self.last_rgb = img_msg_to_frame(msg, bayer)
             except Exception as e:
                 self.get_logger().warn(f"rgb: {e}")
 
@@ -128,14 +143,14 @@ def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global
     return VisualLandmarkMatcher()
 
 
-def make_recorder_node(out_pkl, min_disp_m=2.0, cv2=None):
+def make_recorder_node(out_pkl, min_disp_m=2.0, cv2=None, bayer=None):
     from sensor_msgs.msg import Image
     Node = _node_base()
 
     class VisualLandmarkRecorder(Node):
         def __init__(self):
             super().__init__("visual_landmark_recorder")
-            self.core = LandmarkRecorderCore(out_pkl, min_disp_m, cv2=cv2)
+            self.core = LandmarkRecorderCore(out_pkl, min_disp_m, cv2=cv2, bayer=bayer)
             self.last_rgb = self.last_depth = None
             self.last_rgb_ts = 0.0
             self.create_subscription(Image, "/camera/color/image_raw", self._rgb_cb, 10)
@@ -146,7 +161,7 @@ def make_recorder_node(out_pkl, min_disp_m=2.0, cv2=None):
 
         def _rgb_cb(self, msg):
             try:
-                self.last_rgb = img_msg_to_bgr(msg)
+                self.last_rgb = img_msg_to_frame(msg, bayer)
                 self.last_rgb_ts = msg.header.stamp.sec + msg.header.stamp.nanosec * 1e-9
             except Exception as e:
                 self.get_logger().warn(f"rgb cb: {e}")
@@ -175,10 +190,12 @@ def matcher_main(argv=None):
     ap.add_argument("--swap-flag", default="/tmp/matcher_swap_return.txt")
     ap.add_argument("--global-reloc", action="store_true")
     ap.add_argument("--fused", action="store_true", help="run the whole tick in one device call")
+    ap.add_argument("--bayer", default=None, choices=["BG", "GB", "RG", "GR"], help="the colour topic carries raw 8-bit mosaics of this pattern")
     args = ap.parse_args(argv)
     import rclpy
     rclpy.init()
-    node = make_matcher_node(args.landmarks, args.out_csv, args.landmarks_return, args.swap_flag, args.global_reloc, args.fused)
+    raw = () if args.bayer is None else (None, args.bayer)           # cv2 (the default shim), bayer
+    node = make_matcher_node(args.landmarks, args.out_csv, args.landmarks_return, args.swap_flag, args.global_reloc, args.fused, *raw)
     try:
         rclpy.spin(node)
     except KeyboardInterrupt:
@@ -196,10 +213,12 @@ def recorder_main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
     ap.add_argument("--min-disp", type=float, default=2.0)
+    ap.add_argument("--bayer", default=None, choices=["BG", "GB", "RG", "GR"], help="the colour topic carries raw 8-bit mosaics of this pattern")
     args = ap.parse_args(argv)
     import rclpy
     rclpy.init()
-    node = make_recorder_node(args.out, args.min_disp)
+    raw = () if args.bayer is None else (None, args.bayer)           # cv2 (the default shim), bayer
+    node = make_recorder_node(args.out, args.min_disp, *raw)
     try:
         rclpy.spin(node)
     except KeyboardInterrupt:

@@ -1,0 +1,324 @@
+"""cv2.cvtColor(raw, COLOR_Bayer??2BGR) on the GPU (reloc_bayer_u8) against the NumPy restatement tests/bayer_ref.py, bit for
+bit, and the raw-sensor stage at the head of the image chain: its plane and features, equivalence with the two-call form
+through tick, batch, recording and accumulation, its order with resize, rectification and CLAHE, refusals, off = never set."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import bayer_ref as BR
+import clahe_ref as CR
+import remap_ref as RR
+import resize_ref as ZR
+from nclt_slam_project_amd import RelocError, _native as N, synth
+from nclt_slam_project_amd.cv2_shim import Cv2Shim
+from nclt_slam_project_amd.engine import Engine
+
+pytestmark = pytest.mark.gpu
+W, H = 320, 240
+
+
+@pytest.fixture(scope="module")
+def eng():
+    e = Engine(0, W, H, 4096)
+    yield e
+    e.close()
+
+
+@pytest.fixture(scope="module")
+def frames():
+    """three textured BGR frames; their mosaics are made per pattern where needed"""
+    return [synth.textured_frame(np.random.default_rng(40 + i), W, H) for i in range(3)]
+
+
+def _raws(w, h):
+    """seeded noise (every neighbour matters) and a checkerboard of extremes (every rounding carries)"""
+    rng = np.random.default_rng(1000 * w + h)
+    y, x = np.mgrid[0:h, 0:w]
+    return [rng.integers(0, 256, (h, w)).astype(np.uint8), (255 * ((x + y) & 1)).astype(np.uint8), (255 * ((x >> 1) + y & 1)).astype(np.uint8)]
+
+
+def _abi_bayer(e, raw, code, ptr=None, stride=None, w=None, h=None):
+    """reloc_bayer_u8 as a C caller uses it; ptr / stride / w / h override where the source lies and what is said of it"""
+    rh, rw = raw.shape
+    w, h = rw if w is None else w, rh if h is None else h
+    out = np.full((max(h, 1), max(w, 1), 3), 0xA5, np.uint8)
+    rc = e._lib.reloc_bayer_u8(e._ctx, C.c_void_p(raw.ctypes.data if ptr is None else ptr), w, h,
+                               raw.strides[0] if stride is None else stride, code, N.ptr(out))
+    return rc, out
+
+
+@pytest.mark.parametrize("w,h", [(3, 3), (4, 3), (5, 4), (7, 5), (64, 64), (66, 65), (131, 67), (320, 240)])
+def test_bayer_u8_bit_exact(eng, w, h):
+    for code in BR.CODES:
+        for raw in _raws(w, h):
+            exp = BR.demosaic(raw, code)
+            rc, got = _abi_bayer(eng, raw, code)
+            assert rc == 0, (rc, code)
+            np.testing.assert_array_equal(got, exp)
+        np.testing.assert_array_equal(eng.bayer(raw, code), exp)
+
+
+def test_strided_and_odd_sources(eng):
+    rng = np.random.default_rng(3)
+    for w, h in ((64, 48), (61, 47)):
+        wide = rng.integers(0, 256, (h, w + 13)).astype(np.uint8)
+        for off in (0, 1, 3, 4):            # a row stride larger than w; base addresses that are odd, and no multiple of 4
+            exp = BR.demosaic(np.ascontiguousarray(wide[:, off:off + w]), BR.RG)
+            rc, got = _abi_bayer(eng, wide, BR.RG, ptr=wide.ctypes.data + off, stride=wide.strides[0], w=w)
+            assert rc == 0
+            np.testing.assert_array_equal(got, exp)
+            np.testing.assert_array_equal(eng.bayer(wide[:, off:off + w], BR.RG), exp)
+
+
+def test_shim_on_the_engine(eng):
+    cv2 = Cv2Shim(eng)
+    raw = _raws(131, 67)[0]
+    bgr = cv2.cvtColor(raw, cv2.COLOR_BayerGR2BGR)
+    np.testing.assert_array_equal(bgr, BR.demosaic(raw, BR.GR))
+    np.testing.assert_array_equal(cv2.cvtColor(raw, cv2.COLOR_BayerGR2RGB), bgr[..., ::-1])
+    np.testing.assert_array_equal(cv2.cvtColor(bgr, cv2.COLOR_BGR2GRAY), BR.demosaic_gray(raw, BR.GR, 15))
+    with pytest.raises(cv2.error, match="capacity"):
+        cv2.cvtColor(np.zeros((H + 1, 64), np.uint8), cv2.COLOR_BayerGR2BGR)
+
+
+def test_error_codes(eng):
+    raw = np.zeros((48, 64), np.uint8)
+    lib, ctx = eng._lib, eng._ctx
+    assert _abi_bayer(eng, raw, 46)[0] == 0 and _abi_bayer(eng, raw, 49)[0] == 0
+    for code in (45, 50, 0, -1, 86, 62):
+        assert _abi_bayer(eng, raw, code)[0] == -1, code
+    assert _abi_bayer(eng, raw, 46, w=2)[0] == -1 and _abi_bayer(eng, raw, 46, h=2)[0] == -1 and _abi_bayer(eng, raw, 46, w=0)[0] == -1
+    assert _abi_bayer(eng, raw, 46, stride=63)[0] == -1                 # stride below the row
+    assert _abi_bayer(eng, np.zeros((8, W + 1), np.uint8), 46)[0] == -4 and _abi_bayer(eng, np.zeros((H + 1, 8), np.uint8), 46)[0] == -4
+    out = np.empty((48, 64, 3), np.uint8)
+    assert lib.reloc_bayer_u8(ctx, None, 64, 48, 64, 46, N.ptr(out)) == -1
+    assert lib.reloc_bayer_u8(ctx, N.ptr(raw), 64, 48, 64, 46, None) == -1
+    assert lib.reloc_bayer_u8(None, N.ptr(raw), 64, 48, 64, 46, N.ptr(out)) == -1
+    # the stage's setting
+    assert eng.get_bayer() is None
+    for code in (7, 45, 50, -1, 86):
+        assert lib.reloc_set_bayer(ctx, code) == -1, code
+    assert eng.get_bayer() is None
+    assert lib.reloc_set_bayer(None, 46) == -1 and lib.reloc_get_bayer(ctx, None) == -1
+    for code in BR.CODES:
+        eng.set_bayer(code)
+        assert eng.get_bayer() == code
+    with pytest.raises(RelocError, match="mosaic"):                     # a BGR frame while the stage is on
+        eng.tick(np.zeros((H, W, 3), np.uint8), synth.base_pose(0.0, 0.0, 0.0))
+    eng.set_bayer(None)
+    assert eng.get_bayer() is None
+    with pytest.raises(RelocError, match="frame"):                      # and a mosaic while it is off
+        eng.tick(np.zeros((H, W), np.uint8), synth.base_pose(0.0, 0.0, 0.0))
+    eng.set_bayer(0)
+    assert eng.get_bayer() is None
+
+
+# ---- the stage ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("w,h,codes", [(320, 240, (BR.BG, BR.GB)), (131, 67, (BR.RG, BR.GR))])
+def test_orb_frame_dev_on_a_mosaic_gives_the_features_of_its_gray(frames, w, h, codes):
+    e = Engine(0, W, H, 4096)
+    devs = []
+    try:
+        for code in codes:
+            raw = BR.mosaic(frames[0][:h, :w], code)
+            devs.append(e.to_device(raw))
+            e.set_bayer(code)
+            for bits, order_rgb in ((15, False), (14, True)):           # the channel-order bit is ignored
+                e.set_params(gray_coeff_bits=bits)
+                n = e.orb_frame_dev(devs[-1], w, h, order_rgb=order_rgb)
+                exp = BR.demosaic_gray(raw, code, bits)
+                np.testing.assert_array_equal(e.frame_debug_plane(0, 0), exp)
+                feats = e.orb_features()
+                ref = e.orb_detect_compute(exp, 500)                    # a gray image: the stage never applies
+                assert n == feats["n"] == ref["n"] and (n > 50 or w < 320)
+                np.testing.assert_array_equal(feats["xy"], ref["xy"])
+                np.testing.assert_array_equal(feats["desc"], ref["desc"])
+        # a mosaic inside a wider buffer at an odd address: stride in bytes of the mosaic
+        wide = np.zeros((h, w + 7), np.uint8)
+        wide[:, 3:3 + w] = raw
+        devs.append(e.to_device(wide))
+        e.orb_frame_dev(devs[-1] + 3, w, h, stride=w + 7)
+        np.testing.assert_array_equal(e.frame_debug_plane(0, 0), exp)
+        with pytest.raises(RelocError, match="code -1"):                # a stride below the mosaic's row
+            e.orb_frame_dev(devs[-1], w, h, stride=w - 1)
+        e.sync()
+    finally:
+        for p in devs:
+            e.dev_free(p)
+        e.close()
+
+
+def _tick_record(e, img, bp, mode):
+    e.tick(img, bp, global_reloc=mode, seed=1)
+    rec = np.zeros(96, np.uint8)
+    e.d2h(rec, e.tick_result_dev)
+    return rec
+
+
+def _device_record(e):
+    e.tick_result()
+    rec = np.zeros(96, np.uint8)
+    e.d2h(rec, e.tick_result_dev)
+    return rec
+
+
+def _same_features(a, b):
+    fa, fb = a.orb_features(), b.orb_features()
+    assert fa["n"] == fb["n"] > 50
+    for k in ("xy", "desc"):
+        np.testing.assert_array_equal(fa[k], fb[k])
+
+
+def _database(e, rng, bgr):
+    feats = e.orb_detect_compute(e.gray(bgr), 500)
+    return synth.descriptor_db(rng, 64, "ragged", feats["desc"], planted_records=(5, 40))
+
+
+def test_tick_record_and_accumulate_equal_the_two_call_form(frames):
+    code = BR.GR
+    raw = BR.mosaic(frames[0], code)
+    yy, xx = np.mgrid[0:H, 0:W]
+    dep = (2000 + 2 * xx + yy).astype(np.uint16)                        # smooth: the depth gates keep the keypoints
+    on, off = Engine(0, W, H, 4096), Engine(0, W, H, 4096)
+    devs = []
+    try:
+        bgr = off.bayer(raw, code)
+        np.testing.assert_array_equal(bgr, BR.demosaic(raw, code))
+        db = _database(off, np.random.default_rng(7), bgr)
+        for e in (on, off):
+            e.db_upload(*db)
+        on.set_bayer(code)
+        bp = synth.base_pose(10.0, 0.3, 2.0)
+        for mode in (False, True):
+            a, b = _tick_record(on, raw, bp, mode), _tick_record(off, bgr, bp, mode)
+            assert a.tobytes() == b.tobytes()
+            _same_features(on, off)
+        assert on.tick_result()["n_candidates"] > 0                     # the whole-database search found the planted records
+        np.testing.assert_array_equal(on.frame_debug_plane(0, 0), off.frame_debug_plane(0, 0))
+        ra, rb = on.record_frame(raw, dep), off.record_frame(bgr, dep)
+        assert ra["n"] == rb["n"] > 0 and ra["n_kp"] == rb["n_kp"] > 0
+        for key in ("xy", "desc", "pts3d", "kp_index"):
+            np.testing.assert_array_equal(ra[key], rb[key])
+        # accumulation: a database far away, so the tick finds nothing and the frame is filed
+        poses = np.zeros((3, 7)); poses[:, 6] = 1.0; poses[:, 0] = 200.0 + np.arange(3)
+        bp0 = synth.base_pose(0.0, 0.0, 0.0)
+        recs = []
+        for e, frame in ((on, raw), (off, bgr)):
+            e.set_params(accum_min_kpts=1, min_matches=4)
+            e.db_upload(np.zeros((6, 32), np.uint8), np.ones((6, 3), np.float32), 2 * np.arange(4, dtype=np.int64), poses)
+            devs += [e.to_device(frame), e.to_device(dep)]
+            e.tick_dev(devs[-2], W, H, bp0)
+            e.tick_accumulate_dev(devs[-1], W, H, bp0, True)
+            recs.append((_device_record(e).tobytes(), e.accumulate_result(), e.db_records))
+        assert recs[0] == recs[1] and recs[0][1]["appended"] and recs[0][2] == 4
+        fa, fb = on.db_fetch(3), off.db_fetch(3)
+        assert fa["n_features"] == fb["n_features"] > 30
+        for key in ("descriptors", "keypoints_2d", "keypoints_3d_cam"):
+            np.testing.assert_array_equal(fa[key], fb[key])
+        on.sync(); off.sync()
+    finally:
+        for e, ps in ((on, devs[:2]), (off, devs[2:])):
+            for p in ps:
+                e.dev_free(p)
+            e.close()
+
+
+def test_batched_tick_of_three_mosaics_and_mixed_batches(frames):
+    code = BR.BG
+    ons = [Engine(0, W, H, 4096) for _ in range(3)]
+    offs = [Engine(0, W, H, 4096) for _ in range(3)]
+    odev, fdev = [], []
+    try:
+        raws = [BR.mosaic(f, code) for f in frames]
+        bgrs = [offs[0].bayer(r, code) for r in raws]
+        db = _database(offs[0], np.random.default_rng(8), bgrs[0])
+        for es in (ons, offs):
+            es[0].db_upload(*db)
+            for e in es[1:]:
+                e.db_share(es[0])
+                e.set_stream(es[0].stream_ptr)
+        for e in ons:
+            e.set_bayer(code)
+        odev = [ons[0].to_device(r) for r in raws]
+        fdev = [offs[0].to_device(b) for b in bgrs]
+        poses = [synth.base_pose(10.0 + i, 0.3, 2.0) for i in range(3)]
+        for mode in (True, False):
+            Engine.tick_batch_dev(ons, odev, W, H, poses, global_reloc=mode, seeds=[7, 8, 9])
+            Engine.tick_batch_dev(offs, fdev, W, H, poses, global_reloc=mode, seeds=[7, 8, 9])
+            for a, b in zip(ons, offs):
+                assert _device_record(a).tobytes() == _device_record(b).tobytes()
+                _same_features(a, b)
+        # one context on, the others off, and unequal patterns are refused; equal ones accepted again
+        ons[1].set_bayer(None)
+        refusal = r"(?s)code -5.*Bayer stage"
+        with pytest.raises(RelocError, match=refusal):
+            Engine.tick_batch_dev(ons, odev, W, H, poses, global_reloc=True, seeds=[7, 8, 9])
+        odev.append(ons[0].dev_alloc(256))
+        with pytest.raises(RelocError, match=refusal):
+            Engine.shard_scan_batch_dev(ons[:2], odev[:2], W, H, poses[:2], 4, 0, odev[-1])
+        ons[1].set_bayer(BR.GR)
+        with pytest.raises(RelocError, match=refusal):
+            Engine.tick_batch_dev(ons, odev[:3], W, H, poses, global_reloc=True, seeds=[7, 8, 9])
+        ons[1].set_bayer(code)
+        Engine.tick_batch_dev(ons, odev[:3], W, H, poses, global_reloc=True, seeds=[7, 8, 9])
+        Engine.tick_batch_dev(offs, fdev, W, H, poses, global_reloc=True, seeds=[7, 8, 9])      # the last one above was local
+        for a, b in zip(ons, offs):
+            assert _device_record(a).tobytes() == _device_record(b).tobytes()
+    finally:
+        for es, devs in ((ons, odev), (offs, fdev)):
+            es[0].sync()
+            for p in devs:
+                es[0].dev_free(p)
+            for e in es[::-1]:
+                e.close()
+
+
+def test_stage_order_with_resize_rectify_and_clahe(frames):
+    sw, sh, dw, dh = 300, 220, 160, 120
+    raw = BR.mosaic(frames[1][:sh, :sw], BR.GB)
+    v, u = np.mgrid[0:dh, 0:dw]
+    maps = RR.convert_maps((u + 0.02 * (v - 60) + 1.3).astype(np.float32), (v * 0.98 + 0.7).astype(np.float32))
+    e = Engine(0, sw, sh, 4096)
+    dev = 0
+    try:
+        dev = e.to_device(raw)
+        e.set_bayer(BR.GB)
+        e.set_resize((sw, sh), (dw, dh))                                 # the source size is the mosaic's
+        e.set_rectify(maps)
+        e.set_clahe(2.0, (4, 4))
+        e.orb_frame_dev(dev, sw, sh)
+        exp = CR.clahe(RR.remap_fixed(ZR.resize_ref(BR.demosaic_gray(raw, BR.GB, 15), (dw, dh), interpolation=3), *maps), 2.0, (4, 4))
+        np.testing.assert_array_equal(e.frame_debug_plane(0, 0), exp)
+        # each later stage alone behind the demosaic
+        e.set_rectify(None); e.set_clahe(None)
+        e.orb_frame_dev(dev, sw, sh)
+        np.testing.assert_array_equal(e.frame_debug_plane(0, 0), ZR.resize_ref(BR.demosaic_gray(raw, BR.GB, 15), (dw, dh), interpolation=3))
+        e.set_resize(None); e.set_clahe(2.0, (4, 4))
+        e.orb_frame_dev(dev, sw, sh)
+        np.testing.assert_array_equal(e.frame_debug_plane(0, 0), CR.clahe(BR.demosaic_gray(raw, BR.GB, 15), 2.0, (4, 4)))
+        e.sync()
+    finally:
+        if dev:
+            e.dev_free(dev)
+        e.close()
+
+
+def test_off_is_off(frames):
+    bgr = frames[2]
+    fresh, used = Engine(0, W, H, 4096), Engine(0, W, H, 4096)
+    try:
+        db = _database(fresh, np.random.default_rng(9), bgr)
+        for e in (fresh, used):
+            e.db_upload(*db)
+        bp = synth.base_pose(10.0, 0.3, 2.0)
+        used.set_bayer(BR.RG)
+        _tick_record(used, BR.mosaic(bgr, BR.RG), bp, True)
+        used.set_bayer(None)
+        assert used.get_bayer() is None
+        for mode in (True, False):
+            assert _tick_record(used, bgr, bp, mode).tobytes() == _tick_record(fresh, bgr, bp, mode).tobytes()
+            _same_features(used, fresh)
+    finally:
+        fresh.close()
+        used.close()
