@@ -408,6 +408,14 @@ int reloc_accumulate_result(reloc_ctx *ctx, int32_t *appended, int32_t *n_kpts, 
  * With the gate at 0 every candidate takes the first shape (tests/test_gpu_tick.py::test_inlier_gate_shapes_of_the_parity_tap). */
 int reloc_tick_debug(reloc_ctx *ctx, int32_t *cand_ids, int32_t *n_cand, int32_t *n_matches,
                      int32_t *n_inl, int32_t *ok, double *reproj, double *Rt);
+/* Parity tap (tests only): what the emit pass of the last solve on ctx left for candidate slot `slot` -- the slot's order
+ * in reloc_tick_debug's cand_ids -- and so exactly what its PnP was given.  *n: the number of mutual matches; the first *n
+ * entries of qidx (row within the record), tidx (current feature), dist (Hamming distance), in queryIdx order; obj (*n x 3,
+ * the record's keypoints_3d_cam[qidx]) and img (*n x 2, the current keypoint xy[tidx]).  Every output pointer may be NULL;
+ * arrays need room for the record's rows.  RELOC_E_ARG when slot is not in [0, n_cand) of that solve (read from the device
+ * as reloc_tick_debug does).  Synchronises the context's stream; copies only, launches nothing. */
+int reloc_tick_debug_matches(reloc_ctx *ctx, int slot, int32_t *n, int32_t *qidx, int32_t *tidx, int32_t *dist,
+                             float *obj, float *img);
 /* Sharded database (one rank per GPU): per-record mutual-match counts are local; the caller
  * exchanges the per-shard top-k (count, global id) lists and tells each rank which of ITS
  * records made the global top-k.  These two calls split reloc_tick_dev at that exchange. */

@@ -78,6 +78,7 @@ SIGNATURES = {
     "reloc_set_bayer": (C.c_int, [c_ctx, C.c_int]),
     "reloc_get_bayer": (C.c_int, [c_ctx, P]),
     "reloc_tick_debug": (C.c_int, [c_ctx, P, P, P, P, P, P, P]),
+    "reloc_tick_debug_matches": (C.c_int, [c_ctx, C.c_int, P, P, P, P, P, P]),
     "reloc_tick": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, P, C.c_int, u64, P, P, P, P, P, P]),
     "reloc_get_params": (C.c_int, [c_ctx, P]),
     "reloc_set_params": (C.c_int, [c_ctx, P]),

@@ -1064,3 +1064,29 @@ RELOC_API int reloc_tick_debug(reloc_ctx *ctx, int32_t *cand_ids, int32_t *n_can
     }
     return RELOC_OK;
 }
+
+// read back what the emit pass of the last solve left for candidate slot `slot`: its mutual match list and the 3-D / 2-D
+// pairs PnP was given (parity tap for tests; copies only, nothing is launched)
+RELOC_API int reloc_tick_debug_matches(reloc_ctx *ctx, int slot, int32_t *n, int32_t *qidx, int32_t *tidx, int32_t *dist,
+                                       float *obj, float *img)
+{
+    ARG_CHECK_CTX(ctx, true, "ctx is NULL");
+    int32_t n_cand = 0;
+    HIP_TRY(hipMemcpyAsync(&n_cand, ctx->cand_n, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ARG_CHECK(slot >= 0 && slot < n_cand && slot < MAX_CAND, "reloc_tick_debug_matches: slot is not a candidate of the last solve");
+    int32_t m = 0;
+    HIP_TRY(hipMemcpyAsync(&m, ctx->m_n + slot, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (n) *n = m;
+    if (m < 0 || m > MAX_REC_ROWS) { reloc_set_error("reloc_tick_debug_matches: slot %d holds %d matches", slot, m); return RELOC_E_STATE; }
+    if (m == 0) return RELOC_OK;
+    const size_t at = (size_t)slot * MAX_REC_ROWS, k = (size_t)m;
+    if (qidx) HIP_TRY(hipMemcpyAsync(qidx, ctx->m_qidx + at, k * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (tidx) HIP_TRY(hipMemcpyAsync(tidx, ctx->m_tidx + at, k * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (dist) HIP_TRY(hipMemcpyAsync(dist, ctx->m_dist + at, k * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (obj) HIP_TRY(hipMemcpyAsync(obj, ctx->p_obj + 3 * at, k * 12, hipMemcpyDeviceToHost, ctx->stream));
+    if (img) HIP_TRY(hipMemcpyAsync(img, ctx->p_img + 2 * at, k * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return RELOC_OK;
+}

@@ -641,6 +641,18 @@ class Engine:
         return dict(cand_ids=ids[:k].copy(), n_matches=nm[:k].copy(), n_inliers=ni[:k].copy(), ok=ok[:k].copy(),
                     reproj=rep[:k].copy(), Rt=Rt[:k].copy())
 
+    def tick_debug_matches(self, slot: int):
+        """parity tap: the mutual match list and the 3-D / 2-D pairs of candidate slot `slot` of the last solve, as its PnP
+        was given them (reloc_tick_debug_matches; synchronises)"""
+        cap = 4096                                             # MAX_REC_ROWS: the largest record a database may hold
+        n = C.c_int32()
+        qi = np.zeros(cap, np.int32); ti = np.zeros(cap, np.int32); dd = np.zeros(cap, np.int32)
+        obj = np.zeros((cap, 3), np.float32); img = np.zeros((cap, 2), np.float32)
+        N.check(self._lib.reloc_tick_debug_matches(self._ctx, int(slot), C.byref(n), N.ptr(qi), N.ptr(ti), N.ptr(dd), N.ptr(obj),
+                                                   N.ptr(img)), "reloc_tick_debug_matches")
+        k = n.value
+        return dict(n=k, qidx=qi[:k].copy(), tidx=ti[:k].copy(), dist=dd[:k].copy(), obj=obj[:k].copy(), img=img[:k].copy())
+
     def tick(self, img, base_pose, order_rgb=False, global_reloc=False, seed=0):
         """img: (H, W, 3), or the (H, W) mosaic with the Bayer stage on"""
         img = self._frame(img, "tick")
