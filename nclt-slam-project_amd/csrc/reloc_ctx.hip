@@ -162,11 +162,10 @@ RELOC_API void reloc_destroy(reloc_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    // database arrays: one reference each (owner or adopter alike); counts / topk_part are this context's own scratch
-    db_arrays_drop(c->db_share, c->db_desc, c->db_pts3d, c->db_kp2d, c->db_off, c->db_pose, c->db_xy_heading);
+    for (DbArena &db : c->db_slot) db_arena_release(db);      // owner or adopter alike: one reference each
     void *ptrs[] = {c->pyr, c->blur, c->nms, c->rz_tab, c->pyr_tiles, c->hist, c->cand_cnt, c->cand_key, c->cand_resp,
                     c->kp_cnt, c->kp_key, c->kp_resp, c->f_xy, c->f_size, c->f_angle, c->f_resp, c->f_oct,
-                    c->f_desc, c->f_count, c->frame_img, c->orb_const, c->dbg_cut, c->db_counts, c->topk_part, c->cand_ids, c->cand_n, c->m_qidx,
+                    c->f_desc, c->f_count, c->frame_img, c->orb_const, c->dbg_cut, c->cand_ids, c->cand_n, c->m_qidx,
                     c->m_tidx, c->m_dist, c->m_n, c->p_obj, c->p_img, c->p_Rt, c->p_cnt, c->p_inl,
                     c->p_out, c->tick_res, c->accum_res, c->tick_flags, c->scan_ticket, c->clahe_plane, c->clahe_lut,
                     c->rect_xy /* owns rect_alpha, rect_depth and rect_plane */,
@@ -174,12 +173,6 @@ RELOC_API void reloc_destroy(reloc_ctx *c)
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (c->tick_res_host) (void)hipHostFree(c->tick_res_host);
-    {   // the database that is not selected
-        DbArena &a = c->db_slot[1 - c->db_sel];
-        db_arrays_drop(a.share, a.desc, a.pts3d, a.kp2d, a.off, a.pose, a.xy_heading);
-        if (a.counts) (void)hipFree(a.counts);
-        if (a.topk_part) (void)hipFree(a.topk_part);
-    }
     for (int i = 0; i < 8; ++i)
         if (c->scratch[i]) (void)hipFree(c->scratch[i]);
     for (int k = 0; k < RELOC_PROF_N; ++k)

@@ -111,10 +111,13 @@ struct AccumResult {
 // arrays are freed by whoever lets go last.  An owner that re-allocates (growth past the reserve, a new upload) or is
 // destroyed therefore never frees memory an adopter still scans: the adopter keeps the arrays -- and the record count --
 // it adopted until it calls reloc_db_share / reloc_db_upload again.
+// The arena is the unit of ownership: everything a context knows about a database is in its DbArena, a finished arena
+// enters a slot by assignment and leaves it through db_arena_release (reloc_db.hip), nothing else frees database memory.
 struct DbShare { int refs = 1; };
 
 struct DbArena {
-    DbShare *share = nullptr;
+    DbShare *share = nullptr;         // reference count of the six shared arrays
+    bool shared = false;              // the arrays were adopted from another ctx (reloc_db_share): read-only here
     int64_t cap_records = 0, cap_rows = 0;
     int64_t records = 0, rows = 0;
     int max_rows = 0;
@@ -123,9 +126,9 @@ struct DbArena {
     float *kp2d = nullptr;            // cap_rows x 2 (keypoints_2d; only kept for reloc_db_fetch)
     int64_t *off = nullptr;           // cap_records + 1
     double *pose = nullptr;           // cap_records x 7
-    double *xy_heading = nullptr;     // cap_records x 4
-    int32_t *counts = nullptr;        // cap_records
-    unsigned long long *topk_part = nullptr;
+    double *xy_heading = nullptr;     // cap_records x 4 (x, y, cos heading, sin heading) for candidate selection
+    int32_t *counts = nullptr;        // cap_records per-record mutual counts; this holder's own, like topk_part
+    unsigned long long *topk_part = nullptr;   // per-block winners of the two-stage top-k (topk_blocks x 32)
     int topk_blocks = 0;
 };
 
@@ -353,23 +356,9 @@ struct reloc_ctx {
                                      // scans in the form of batched ones (n generations of row budgets + sweepers, launch_db_count)
     uint32_t *scan_ticket = nullptr; // per frame of a batch (<= 8) 8 per-XCD record counters, then 1 exit counter, 128 bytes apart
 
-    // ---- database: two arenas, the fields below are the SELECTED one's (reloc_db_select copies them) ----
+    // ---- database: two arenas; db_sel names the selected one (ctx_db below), reloc_db_select only changes db_sel ----
     DbArena db_slot[2];
     int db_sel = 0;
-    bool db_shared = false;          // the selected database's arrays were adopted from another ctx (reloc_db_share): read-only here
-    DbShare *db_share = nullptr;     // reference count of the selected arena's six shared arrays
-    int64_t db_records = 0, db_rows = 0;
-    int64_t db_cap_records = 0, db_cap_rows = 0;
-    int db_max_rows = 0;
-    uint8_t *db_desc = nullptr;
-    float *db_pts3d = nullptr;
-    float *db_kp2d = nullptr;
-    int64_t *db_off = nullptr;
-    double *db_pose = nullptr;
-    double *db_xy_heading = nullptr; // L x 4 (x, y, cos heading, sin heading) for candidate selection
-    int32_t *db_counts = nullptr;    // L per-record mutual counts
-    unsigned long long *topk_part = nullptr;   // per-block winners of the two-stage top-k (topk_blocks x 32)
-    int topk_blocks = 0;
     AccumResult *accum_res = nullptr;   // 1
     int32_t *tick_flags = nullptr;      // [0] relocating flag of the current tick
 
@@ -397,8 +386,12 @@ int reloc_scratch(reloc_ctx *ctx, int slot, int64_t bytes, void **out);
 void reloc_prof_begin(reloc_ctx *ctx, int which);
 void reloc_prof_end(reloc_ctx *ctx, int which);
 
-// lets go of one reference to an arena's six arrays; frees them when it was the last (reloc_match.hip)
-void db_arrays_drop(DbShare *&share, uint8_t *&desc, float *&pts3d, float *&kp2d, int64_t *&off, double *&pose, double *&xyh);
+// the selected database of a context
+static inline DbArena &ctx_db(reloc_ctx *ctx) { return ctx->db_slot[ctx->db_sel]; }
+static inline const DbArena &ctx_db(const reloc_ctx *ctx) { return ctx->db_slot[ctx->db_sel]; }
+// The one way out of a slot: lets go of this holder's reference to the six shared arrays (the last holder frees them),
+// frees the arena's own counts / topk_part and leaves the arena value-initialised (reloc_db.hip)
+void db_arena_release(DbArena &a);
 extern int g_reloc_live_contexts;           // contexts created and not yet destroyed in this process (reloc_ctx.hip)
 static inline bool ctx_alone(const reloc_ctx *c)
 {
@@ -428,9 +421,14 @@ int launch_db_count(reloc_ctx *ctx, const uint8_t *cur, const int32_t *n_cur_dev
 int launch_db_scan_batch(reloc_ctx *const *ctxs, int n, const double *q, double cos_tol, bool auto_mode, bool heading_mask = true);
 // the emit pass of a tick: match lists, with their 3-D / 2-D pairs, of every context's candidate records (reloc_match.hip)
 int launch_tick_emit(reloc_ctx *const *ctxs, int n, bool latency);
+// re-derives the headings of both slots' records from the camera mounting; grows the selected arena (reloc_db.hip)
 int db_reindex(reloc_ctx *ctx);
 int db_reserve(reloc_ctx *ctx, int64_t cap_records, int64_t cap_rows);
-inline bool db_ready(const reloc_ctx *ctx) { return ctx->db_desc && ctx->db_off && ctx->db_pose && ctx->db_xy_heading && ctx->db_counts && ctx->db_records > 0; }
+inline bool db_ready(const reloc_ctx *ctx)
+{
+    const DbArena &db = ctx_db(ctx);
+    return db.desc && db.off && db.pose && db.xy_heading && db.counts && db.records > 0;
+}
 int orb_prepare(reloc_ctx *ctx, int w, int h, int nfeatures);
 // ORB of frame f = srcs[f] into ctxs[f]'s feature buffers; channels == 3 -> the frames of the image chain: interleaved
 // 3-channel frames (gray fused), or raw mosaics of image_chain_frame_bpp = 1 byte per pixel with the Bayer stage on; the

@@ -4,6 +4,8 @@
 //        cv2.BFMatcher(NORM_HAMMING, crossCheck=False).knnMatch k=2 (reference S:46,68)
 //        the whole-database candidate scoring of variant G          (reference G:329-344)
 // and the all-pairs u16 distance matrix of BASELINE.json config 5.
+// The file holds the kernels, their launchers and the entry points that scan (reloc_match_*, reloc_hamming_matrix*,
+// reloc_db_match_counts*, reloc_db_ratio_counts); the database they scan is kept by reloc_db.hip.
 //
 // No MFMA: this is bitwise work.  Instruction costs measured on MI355X (tools/ubench_valu.hip,
 // profiles/ubench_valu_r1.log): v_xor/v_or/v_and/v_add_u32 and the 16-bit v_min_u16 /
@@ -27,7 +29,6 @@
 // order.  Keys are (distance << k | index): the minimum of packed keys is the smallest distance
 // with the LOWEST index on ties, which is the tie rule of the specification.
 #include <stdlib.h>
-#include <new>
 #include <type_traits>
 #include <utility>
 
@@ -1019,12 +1020,13 @@ struct CountPlan {
     // average record size); the caller adds the sweepers behind them, which draw until the counters are dry
     void budget(const reloc_ctx *ctx, int workgroups)
     {
-        const int n_ids = (int)ctx->db_records;
+        const DbArena &db = ctx_db(ctx);
+        const int n_ids = (int)db.records;
         if (workgroups > n_ids) workgroups = n_ids;
         if (workgroups < 1) workgroups = 1;
         const int q_rec = (n_ids + workgroups - 1) / workgroups;
         n_bounded = (n_ids + q_rec - 1) / q_rec;
-        quota = (int)((ctx->db_rows * q_rec + n_ids - 1) / n_ids);
+        quota = (int)((db.rows * q_rec + n_ids - 1) / n_ids);
         if (quota < 1) quota = 1;
     }
 };
@@ -1040,12 +1042,13 @@ struct CountPlan {
 // statically.
 int launch_db_count(reloc_ctx *ctx, const uint8_t *cur, const int32_t *n_cur_dev, int n_cur_max, int32_t *counts, const ScanMask &mask)
 {
-    const int n_ids = (int)ctx->db_records;
+    const DbArena &db = ctx_db(ctx);
+    const int n_ids = (int)db.records;
     if (n_ids <= 0) return RELOC_OK;
     if (n_cur_max > 65535) { reloc_set_error("db scan: more than 65535 current descriptors"); return RELOC_E_CAPACITY; }
-    if (ctx->db_max_rows > MAX_REC_ROWS) { reloc_set_error("db scan: record larger than %d rows", MAX_REC_ROWS); return RELOC_E_CAPACITY; }
-    const int max_rows = ctx->db_max_rows < 1 ? 1 : ctx->db_max_rows;
-    const uint4 *db = (const uint4 *)ctx->db_desc;
+    if (db.max_rows > MAX_REC_ROWS) { reloc_set_error("db scan: record larger than %d rows", MAX_REC_ROWS); return RELOC_E_CAPACITY; }
+    const int max_rows = db.max_rows < 1 ? 1 : db.max_rows;
+    const uint4 *desc = (const uint4 *)db.desc;
     if (!mask.xyh && n_cur_max <= 64 && max_rows <= SQ_MAX_ROWS) {
         // few queries: lane = teach row (k_db_scan_rows)
         if (n_cur_max == 0) {                              // a capacity of zero descriptors: nothing may be read from `cur`
@@ -1056,7 +1059,7 @@ int launch_db_count(reloc_ctx *ctx, const uint8_t *cur, const int32_t *n_cur_dev
         const int need = (n_ids + SQ_WAVES - 1) / SQ_WAVES;
         if (grid > need) grid = need;
 #define RELOC_LAUNCH_ROWS(G, HOIST)                                                                                           \
-    hipLaunchKernelGGL((k_db_scan_rows<G, HOIST>), dim3(grid), dim3(64 * SQ_WAVES), 0, ctx->stream, db, ctx->db_off, n_ids, \
+    hipLaunchKernelGGL((k_db_scan_rows<G, HOIST>), dim3(grid), dim3(64 * SQ_WAVES), 0, ctx->stream, desc, db.off, n_ids, \
                        (const uint4 *)cur, n_cur_dev, n_cur_max, counts)
         // G = queries per butterfly group: a call with 1-4 queries evaluates 4 distances per row, not 16; its query words stay in SGPRs
         if (n_cur_max <= 4) RELOC_LAUNCH_ROWS(4, true); else if (n_cur_max <= 8) RELOC_LAUNCH_ROWS(8, false); else RELOC_LAUNCH_ROWS(16, false);
@@ -1079,7 +1082,7 @@ int launch_db_count(reloc_ctx *ctx, const uint8_t *cur, const int32_t *n_cur_dev
     }
     if (grid > n_ids) grid = n_ids;
 #define RELOC_LAUNCH_COUNT(NJ)                                                                                               \
-    hipLaunchKernelGGL((k_db_scan<NJ>), dim3(grid), dim3(256), p.lds, ctx->stream, db, ctx->db_off, nullptr, nullptr, n_ids,       \
+    hipLaunchKernelGGL((k_db_scan<NJ>), dim3(grid), dim3(256), p.lds, ctx->stream, desc, db.off, nullptr, nullptr, n_ids,       \
                        (const uint4 *)cur, n_cur_dev, n_cur_max, max_rows, counts, mask, ticket, p.quota, p.n_bounded, p.col_words)
     if (nj == 2) RELOC_LAUNCH_COUNT(2); else if (nj == 4) RELOC_LAUNCH_COUNT(4); else RELOC_LAUNCH_COUNT(8);
 #undef RELOC_LAUNCH_COUNT
@@ -1133,30 +1136,31 @@ static int launch_db_emit(reloc_ctx *const *ctxs, int n, const EmitBatch &bt, co
 int launch_tick_emit(reloc_ctx *const *ctxs, int n, bool latency)
 {
     reloc_ctx *c0 = ctxs[0];
+    const DbArena &db = ctx_db(c0);
     EmitBatch bt;
     frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int) { bt.f[f] = emit_frame(c); });
-    return launch_db_emit(ctxs, n, bt, c0->db_desc, c0->db_off, c0->db_max_rows, c0->db_pts3d, MAX_CAND, c0->max_feat, MAX_REC_ROWS,
-                          latency);
+    return launch_db_emit(ctxs, n, bt, db.desc, db.off, db.max_rows, db.pts3d, MAX_CAND, c0->max_feat, MAX_REC_ROWS, latency);
 }
 
 // One launch for the whole-database scans of n contexts that share a stream and a database (ctxs[0]'s is scanned):
-// frame f = ctxs[f]'s current features, counts into ctxs[f]->db_counts.  q: n x 4 base_link quaternions (heading mask),
+// frame f = ctxs[f]'s current features, counts into the counts of ctxs[f]'s arena.  q: n x 4 base_link quaternions (heading mask),
 // auto_mode: frames whose local search found candidates stand down on the device.
 int launch_db_scan_batch(reloc_ctx *const *ctxs, int n, const double *q, double cos_tol, bool auto_mode, bool heading_mask)
 {
     reloc_ctx *c0 = ctxs[0];
     if (n < 1 || n > RELOC_BATCH_MAX) { reloc_set_error("scan batch: 1..%d frames", RELOC_BATCH_MAX); return RELOC_E_ARG; }
-    if (c0->max_feat > 65535 || c0->db_max_rows > MAX_REC_ROWS) { reloc_set_error("scan batch: capacity"); return RELOC_E_CAPACITY; }
-    const int n_ids = (int)c0->db_records, max_rows = c0->db_max_rows < 1 ? 1 : c0->db_max_rows;
+    const DbArena &db = ctx_db(c0);
+    if (c0->max_feat > 65535 || db.max_rows > MAX_REC_ROWS) { reloc_set_error("scan batch: capacity"); return RELOC_E_CAPACITY; }
+    const int n_ids = (int)db.records, max_rows = db.max_rows < 1 ? 1 : db.max_rows;
     // n_cur_max = the feature capacity; the 8-column kernel walks column blocks of 512 (one block for nfeatures <= 512)
     CountPlan p;
     if (int rc = p.init(c0, "scan batch", 8, c0->max_feat, max_rows)) return rc;
     ScanBatch bt;
     bt.n = n;
-    bt.xyh = heading_mask ? c0->db_xy_heading : nullptr;
+    bt.xyh = heading_mask ? db.xy_heading : nullptr;
     bt.cos_tol = cos_tol;
     frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int g) {
-        bt.cur[f] = (const uint4 *)c->f_desc; bt.n_cur[f] = c->f_count; bt.counts[f] = c->db_counts;
+        bt.cur[f] = (const uint4 *)c->f_desc; bt.n_cur[f] = c->f_count; bt.counts[f] = ctx_db(c).counts;
         bt.skip_if[f] = auto_mode ? c->cand_n : nullptr;
         for (int k = 0; k < 4; ++k) bt.q[f][k] = q[4 * g + k];
     });
@@ -1165,7 +1169,7 @@ int launch_db_scan_batch(reloc_ctx *const *ctxs, int n, const double *q, double 
     const int gens = c0->scan_gens > 0 ? c0->scan_gens : 1;
     p.budget(c0, (p.resident * gens + n - 1) / n);
     const int per_frame = p.n_bounded + 1 < n_ids ? p.n_bounded + 1 : n_ids;
-    hipLaunchKernelGGL(k_db_scan_batch, dim3(per_frame * n), dim3(256), p.lds, c0->stream, (const uint4 *)c0->db_desc, c0->db_off,
+    hipLaunchKernelGGL(k_db_scan_batch, dim3(per_frame * n), dim3(256), p.lds, c0->stream, (const uint4 *)db.desc, db.off,
                        n_ids, c0->max_feat, max_rows, bt, c0->scan_ticket, p.quota, p.n_bounded, p.col_words);
     HIP_TRY(hipGetLastError());
     return RELOC_OK;
@@ -1466,338 +1470,7 @@ RELOC_API int reloc_match_mutual(reloc_ctx *ctx, const uint8_t *q, int nq, const
     return RELOC_OK;
 }
 
-// ---- database ---------------------------------------------------------------------------------
-// The selected database is a capacity-reserved arena (DbArena in reloc_internal.h): upload fills it, append copies one
-// record behind the last row, reserve grows it.  Nothing is published in the ctx before every allocation and copy of
-// an operation has succeeded: a failed upload leaves "no database" (db_records == 0), a failed reserve / append leaves
-// the database as it was.
-__global__ void k_db_index(const double *__restrict__ pose, int64_t first, int64_t n, double b0, double b1, double b2,
-                           double *__restrict__ xyh)
-{
-    // heading of base_link +X in the world from the stored CAMERA pose, exactly as the reference
-    // composes it (M:233-245): R_wb = R_wc @ B.T, fwd = R_wb @ [1,0,0] = R_wc @ B[0,:]
-    const int64_t i = first + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= first + n) return;
-    const double qx = pose[7 * i + 3], qy = pose[7 * i + 4], qz = pose[7 * i + 5], qw = pose[7 * i + 6];
-    const double r00 = 1 - 2 * (qy * qy + qz * qz), r01 = 2 * (qx * qy - qz * qw), r02 = 2 * (qx * qz + qy * qw);
-    const double r10 = 2 * (qx * qy + qz * qw), r11 = 1 - 2 * (qx * qx + qz * qz), r12 = 2 * (qy * qz - qx * qw);
-    const double fx = r00 * b0 + r01 * b1 + r02 * b2, fy = r10 * b0 + r11 * b1 + r12 * b2;
-    const double fn = sqrt(fx * fx + fy * fy);
-    xyh[4 * i] = pose[7 * i];
-    xyh[4 * i + 1] = pose[7 * i + 1];
-    xyh[4 * i + 2] = fn > 0 ? fx / fn : 1.0;      // cos(heading)
-    xyh[4 * i + 3] = fn > 0 ? fy / fn : 0.0;      // sin(heading)
-}
-
-// headings follow the camera mounting (reloc_set_camera); the (x, y) a record is filed under is kept
-__global__ void k_db_reheading(const double *__restrict__ pose, int64_t n, double b0, double b1, double b2, double *__restrict__ xyh)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double qx = pose[7 * i + 3], qy = pose[7 * i + 4], qz = pose[7 * i + 5], qw = pose[7 * i + 6];
-    const double r00 = 1 - 2 * (qy * qy + qz * qz), r01 = 2 * (qx * qy - qz * qw), r02 = 2 * (qx * qz + qy * qw);
-    const double r10 = 2 * (qx * qy + qz * qw), r11 = 1 - 2 * (qx * qx + qz * qz), r12 = 2 * (qy * qz - qx * qw);
-    const double fx = r00 * b0 + r01 * b1 + r02 * b2, fy = r10 * b0 + r11 * b1 + r12 * b2;
-    const double fn = sqrt(fx * fx + fy * fy);
-    xyh[4 * i + 2] = fn > 0 ? fx / fn : 1.0;
-    xyh[4 * i + 3] = fn > 0 ? fy / fn : 0.0;
-}
-
-int db_reindex(reloc_ctx *ctx)
-{
-    // both resident databases follow a change of the camera mounting
-    for (int slot = 0; slot < 2; ++slot) {
-        const bool sel = slot == ctx->db_sel;
-        const double *pose = sel ? ctx->db_pose : ctx->db_slot[slot].pose;
-        double *xyh = sel ? ctx->db_xy_heading : ctx->db_slot[slot].xy_heading;
-        const int64_t n = sel ? ctx->db_records : ctx->db_slot[slot].records;
-        if (!pose || !xyh || n <= 0) continue;
-        hipLaunchKernelGGL(k_db_reheading, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, pose, n, ctx->b2c_R[0],
-                           ctx->b2c_R[1], ctx->b2c_R[2], xyh);
-    }
-    HIP_TRY(hipGetLastError());
-    return RELOC_OK;
-}
-
-namespace {
-struct DbBuffers {
-    uint8_t *desc = nullptr; float *pts3d = nullptr, *kp2d = nullptr; int64_t *off = nullptr; double *pose = nullptr, *xyh = nullptr;
-    int32_t *counts = nullptr; unsigned long long *topk = nullptr;
-    void release()
-    {
-        void *p[] = {desc, pts3d, kp2d, off, pose, xyh, counts, topk};
-        for (void *q : p) if (q) (void)hipFree(q);
-        *this = DbBuffers();
-    }
-};
-}   // namespace
-
-void db_arrays_drop(DbShare *&share, uint8_t *&desc, float *&pts3d, float *&kp2d, int64_t *&off, double *&pose, double *&xyh)
-{
-    if (share && __atomic_sub_fetch(&share->refs, 1, __ATOMIC_ACQ_REL) == 0) {
-        void *p[] = {desc, pts3d, kp2d, off, pose, xyh};
-        for (void *q : p) if (q) (void)hipFree(q);
-        delete share;
-    }
-    share = nullptr;
-    desc = nullptr; pts3d = nullptr; kp2d = nullptr; off = nullptr; pose = nullptr; xyh = nullptr;
-}
-
-// an adopted database is let go (not freed while anybody else holds it) before this ctx gets one of its own again
-static void db_unshare(reloc_ctx *ctx)
-{
-    if (!ctx->db_shared) return;
-    if (ctx->db_counts) (void)hipFree(ctx->db_counts);
-    if (ctx->topk_part) (void)hipFree(ctx->topk_part);
-    db_arrays_drop(ctx->db_share, ctx->db_desc, ctx->db_pts3d, ctx->db_kp2d, ctx->db_off, ctx->db_pose, ctx->db_xy_heading);
-    ctx->db_counts = nullptr; ctx->topk_part = nullptr;
-    ctx->db_records = ctx->db_rows = ctx->db_cap_records = ctx->db_cap_rows = 0;
-    ctx->db_max_rows = 0; ctx->topk_blocks = 0;
-    ctx->db_shared = false;
-}
-
-// Grow the selected arena to at least (cap_records, cap_rows); contents are kept.  All-or-nothing.  The old arrays are
-// let go of, not necessarily freed: contexts that adopted them (reloc_db_share) keep scanning them.
-int db_reserve(reloc_ctx *ctx, int64_t cap_records, int64_t cap_rows)
-{
-    if (ctx->db_shared) { reloc_set_error("the selected database is shared from another context (read-only here)"); return RELOC_E_STATE; }
-    if (cap_records < 1) cap_records = 1;
-    if (cap_rows < 1) cap_rows = 1;
-    if (cap_records <= ctx->db_cap_records && cap_rows <= ctx->db_cap_rows && ctx->db_desc) return RELOC_OK;
-    if (cap_records < ctx->db_cap_records) cap_records = ctx->db_cap_records;
-    if (cap_rows < ctx->db_cap_rows) cap_rows = ctx->db_cap_rows;
-    if (cap_records > MAX_DB_RECORDS) { reloc_set_error("database: more than %lld records", (long long)MAX_DB_RECORDS); return RELOC_E_CAPACITY; }
-    DbBuffers nb;
-    const int blocks = (int)((cap_records + 1023) / 1024);
-    hipError_t e = hipSuccess;
-    auto grab = [&](void **p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
-    grab((void **)&nb.desc, (size_t)cap_rows * 32);
-    grab((void **)&nb.pts3d, (size_t)cap_rows * 12);
-    grab((void **)&nb.kp2d, (size_t)cap_rows * 8);
-    grab((void **)&nb.off, (size_t)(cap_records + 1) * 8);
-    grab((void **)&nb.pose, (size_t)cap_records * 56);
-    grab((void **)&nb.xyh, (size_t)cap_records * 32);
-    grab((void **)&nb.counts, (size_t)cap_records * 4);
-    grab((void **)&nb.topk, (size_t)blocks * 32 * sizeof(unsigned long long));
-    const int64_t L = ctx->db_desc ? ctx->db_records : 0, T = ctx->db_desc ? ctx->db_rows : 0;
-    auto copy = [&](void *d, const void *s_, size_t bytes) {
-        if (e == hipSuccess && bytes) e = hipMemcpyAsync(d, s_, bytes, hipMemcpyDeviceToDevice, ctx->stream);
-    };
-    if (L > 0) {
-        copy(nb.desc, ctx->db_desc, (size_t)T * 32);
-        copy(nb.pts3d, ctx->db_pts3d, (size_t)T * 12);
-        copy(nb.kp2d, ctx->db_kp2d, (size_t)T * 8);
-        copy(nb.off, ctx->db_off, (size_t)(L + 1) * 8);
-        copy(nb.pose, ctx->db_pose, (size_t)L * 56);
-        copy(nb.xyh, ctx->db_xy_heading, (size_t)L * 32);
-    } else if (e == hipSuccess) {
-        e = hipMemsetAsync(nb.off, 0, 8, ctx->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        nb.release();
-        (void)hipGetLastError();          // a failed hipMalloc leaves a sticky error that the next launch check would report
-        reloc_set_error("database reserve (%lld records, %lld rows) failed: %s", (long long)cap_records, (long long)cap_rows,
-                        hipGetErrorString(e));
-        return RELOC_E_HIP;
-    }
-    DbShare *fresh = new (std::nothrow) DbShare();
-    if (!fresh) { nb.release(); reloc_set_error("database reserve: out of host memory"); return RELOC_E_HIP; }
-    if (ctx->db_counts) (void)hipFree(ctx->db_counts);
-    if (ctx->topk_part) (void)hipFree(ctx->topk_part);
-    db_arrays_drop(ctx->db_share, ctx->db_desc, ctx->db_pts3d, ctx->db_kp2d, ctx->db_off, ctx->db_pose, ctx->db_xy_heading);
-    ctx->db_share = fresh;
-    ctx->db_desc = nb.desc; ctx->db_pts3d = nb.pts3d; ctx->db_kp2d = nb.kp2d; ctx->db_off = nb.off; ctx->db_pose = nb.pose;
-    ctx->db_xy_heading = nb.xyh; ctx->db_counts = nb.counts; ctx->topk_part = nb.topk;
-    ctx->topk_blocks = blocks;
-    ctx->db_cap_records = cap_records;
-    ctx->db_cap_rows = cap_rows;
-    ctx->db_records = L;
-    ctx->db_rows = T;
-    return RELOC_OK;
-}
-
-RELOC_API int reloc_db_reserve(reloc_ctx *ctx, int64_t cap_records, int64_t cap_rows)
-{
-    ARG_CHECK_CTX(ctx, cap_records >= 0 && cap_rows >= 0, "reloc_db_reserve");
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return db_reserve(ctx, cap_records, cap_rows);
-}
-
-RELOC_API int reloc_db_upload(reloc_ctx *ctx, const uint8_t *desc, const float *pts3d, const int64_t *offsets,
-                              const double *poses, int64_t n_records)
-{
-    ARG_CHECK_CTX(ctx, offsets && n_records >= 0, "reloc_db_upload");
-    const int64_t T = offsets[n_records];
-    ARG_CHECK(offsets[0] == 0 && T >= 0, "offsets must start at 0 and be non-decreasing");
-    int maxrows = 0;
-    for (int64_t r = 0; r < n_records; ++r) {
-        const int64_t n = offsets[r + 1] - offsets[r];
-        ARG_CHECK(n >= 0, "offsets must be non-decreasing");
-        if (n > MAX_REC_ROWS) { reloc_set_error("record %lld has %lld rows (max %d)", (long long)r, (long long)n, MAX_REC_ROWS); return RELOC_E_CAPACITY; }
-        if (n > maxrows) maxrows = (int)n;
-    }
-    ARG_CHECK(T == 0 || (desc && pts3d), "desc / pts3d missing");
-    ARG_CHECK(n_records == 0 || poses, "poses missing");
-    if (n_records > MAX_DB_RECORDS) { reloc_set_error("database: %lld records (max %lld)", (long long)n_records, (long long)MAX_DB_RECORDS); return RELOC_E_CAPACITY; }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    db_unshare(ctx);
-    if (ctx->db_share && __atomic_load_n(&ctx->db_share->refs, __ATOMIC_ACQUIRE) > 1) {
-        // other contexts adopted these arrays: they keep them as they are, this upload goes into fresh ones
-        db_arrays_drop(ctx->db_share, ctx->db_desc, ctx->db_pts3d, ctx->db_kp2d, ctx->db_off, ctx->db_pose, ctx->db_xy_heading);
-        ctx->db_cap_records = ctx->db_cap_rows = 0;
-    }
-    // from here on the ctx holds no database until everything below has succeeded
-    ctx->db_records = 0;
-    ctx->db_rows = 0;
-    ctx->db_max_rows = 0;
-    int rc = db_reserve(ctx, n_records, T);
-    if (rc) return rc;
-    if (T > 0) {
-        HIP_TRY(hipMemcpyAsync(ctx->db_desc, desc, (size_t)T * 32, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(ctx->db_pts3d, pts3d, (size_t)T * 12, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemsetAsync(ctx->db_kp2d, 0, (size_t)T * 8, ctx->stream));
-    }
-    HIP_TRY(hipMemcpyAsync(ctx->db_off, offsets, (size_t)(n_records + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (n_records > 0) {
-        HIP_TRY(hipMemcpyAsync(ctx->db_pose, poses, (size_t)n_records * 56, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_db_index, dim3((unsigned)((n_records + 255) / 256)), dim3(256), 0, ctx->stream, ctx->db_pose, (int64_t)0,
-                           n_records, ctx->b2c_R[0], ctx->b2c_R[1], ctx->b2c_R[2], ctx->db_xy_heading);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ctx->db_records = n_records;
-    ctx->db_rows = T;
-    ctx->db_max_rows = maxrows;
-    return RELOC_OK;
-}
-
-// room for one more record of n rows; geometric growth when the reserve is exhausted
-static int db_make_room(reloc_ctx *ctx, int64_t n)
-{
-    if (ctx->db_desc && ctx->db_records + 1 <= ctx->db_cap_records && ctx->db_rows + n <= ctx->db_cap_rows) return RELOC_OK;
-    const int64_t need_r = ctx->db_records + 1, need_t = ctx->db_rows + n;
-    int64_t cr = ctx->db_cap_records + ctx->db_cap_records / 2 + 64, ct = ctx->db_cap_rows + ctx->db_cap_rows / 2 + 64 * 512;
-    if (cr < need_r) cr = need_r;
-    if (ct < need_t) ct = need_t;
-    if (cr > MAX_DB_RECORDS) cr = MAX_DB_RECORDS;
-    if (need_r > MAX_DB_RECORDS) { reloc_set_error("database: more than %lld records", (long long)MAX_DB_RECORDS); return RELOC_E_CAPACITY; }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return db_reserve(ctx, cr, ct);
-}
-
-RELOC_API int reloc_db_append(reloc_ctx *ctx, const uint8_t *desc, const float *pts3d, const float *kp2d, int n,
-                              const double pose[7], const double index_xy[2])
-{
-    ARG_CHECK_CTX(ctx, n >= 0 && pose && (n == 0 || (desc && pts3d)), "reloc_db_append");
-    if (ctx->db_shared) { reloc_set_error("the selected database is shared from another context (read-only here)"); return RELOC_E_STATE; }
-    if (n > MAX_REC_ROWS) { reloc_set_error("record has %d rows (max %d)", n, MAX_REC_ROWS); return RELOC_E_CAPACITY; }
-    int rc = db_make_room(ctx, n);
-    if (rc) return rc;
-    const int64_t L = ctx->db_records, T = ctx->db_rows;
-    if (n > 0) {
-        HIP_TRY(hipMemcpyAsync(ctx->db_desc + T * 32, desc, (size_t)n * 32, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(ctx->db_pts3d + T * 3, pts3d, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream));
-        if (kp2d) HIP_TRY(hipMemcpyAsync(ctx->db_kp2d + T * 2, kp2d, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        else HIP_TRY(hipMemsetAsync(ctx->db_kp2d + T * 2, 0, (size_t)n * 8, ctx->stream));
-    }
-    const int64_t end = T + n;
-    HIP_TRY(hipMemcpyAsync(ctx->db_off + L + 1, &end, 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->db_pose + 7 * L, pose, 56, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_db_index, dim3(1), dim3(64), 0, ctx->stream, ctx->db_pose, L, (int64_t)1, ctx->b2c_R[0], ctx->b2c_R[1],
-                       ctx->b2c_R[2], ctx->db_xy_heading);
-    HIP_TRY(hipGetLastError());
-    if (index_xy) HIP_TRY(hipMemcpyAsync(ctx->db_xy_heading + 4 * L, index_xy, 16, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));     // the host sources may go away; the record is visible from here on
-    ctx->db_records = L + 1;
-    ctx->db_rows = end;
-    if (n > ctx->db_max_rows) ctx->db_max_rows = n;
-    return RELOC_OK;
-}
-
-static void db_store_slot(reloc_ctx *ctx)
-{
-    DbArena &a = ctx->db_slot[ctx->db_sel];
-    a.cap_records = ctx->db_cap_records; a.cap_rows = ctx->db_cap_rows; a.records = ctx->db_records; a.rows = ctx->db_rows;
-    a.max_rows = ctx->db_max_rows; a.desc = ctx->db_desc; a.pts3d = ctx->db_pts3d; a.kp2d = ctx->db_kp2d; a.off = ctx->db_off;
-    a.pose = ctx->db_pose; a.xy_heading = ctx->db_xy_heading; a.counts = ctx->db_counts; a.topk_part = ctx->topk_part;
-    a.topk_blocks = ctx->topk_blocks;
-    a.share = ctx->db_share;
-}
-
-RELOC_API int reloc_db_share(reloc_ctx *dst, reloc_ctx *src)
-{
-    ARG_CHECK_CTX(dst, src && src != dst, "reloc_db_share");
-    if (src->device != dst->device) { reloc_set_error("reloc_db_share: contexts live on different devices"); return RELOC_E_ARG; }
-    if (!db_ready(src)) { reloc_set_error("reloc_db_share: the source context has no database"); return RELOC_E_STATE; }
-    HIP_TRY(hipStreamSynchronize(dst->stream));
-    HIP_TRY(hipStreamSynchronize(src->stream));
-    int32_t *counts = nullptr;
-    unsigned long long *topk = nullptr;
-    const int blocks = (int)((src->db_cap_records + 1023) / 1024);
-    if (hipMalloc((void **)&counts, (size_t)src->db_cap_records * 4) != hipSuccess ||
-        hipMalloc((void **)&topk, (size_t)blocks * 32 * sizeof(unsigned long long)) != hipSuccess) {
-        if (counts) (void)hipFree(counts);
-        reloc_set_error("reloc_db_share: scratch allocation failed");
-        return RELOC_E_HIP;
-    }
-    if (dst->db_shared) db_unshare(dst);
-    else {
-        if (dst->db_counts) (void)hipFree(dst->db_counts);
-        if (dst->topk_part) (void)hipFree(dst->topk_part);
-        db_arrays_drop(dst->db_share, dst->db_desc, dst->db_pts3d, dst->db_kp2d, dst->db_off, dst->db_pose, dst->db_xy_heading);
-    }
-    __atomic_add_fetch(&src->db_share->refs, 1, __ATOMIC_ACQ_REL);
-    dst->db_share = src->db_share;
-    dst->db_desc = src->db_desc; dst->db_pts3d = src->db_pts3d; dst->db_kp2d = src->db_kp2d; dst->db_off = src->db_off;
-    dst->db_pose = src->db_pose; dst->db_xy_heading = src->db_xy_heading;
-    dst->db_counts = counts; dst->topk_part = topk; dst->topk_blocks = blocks;
-    dst->db_records = src->db_records; dst->db_rows = src->db_rows; dst->db_max_rows = src->db_max_rows;
-    dst->db_cap_records = src->db_cap_records; dst->db_cap_rows = src->db_cap_rows;
-    dst->db_shared = true;
-    return RELOC_OK;
-}
-
-RELOC_API int reloc_db_select(reloc_ctx *ctx, int slot)
-{
-    ARG_CHECK_CTX(ctx, slot == 0 || slot == 1, "reloc_db_select: slot must be 0 or 1");
-    if (slot == ctx->db_sel) return RELOC_OK;
-    if (ctx->db_shared) { reloc_set_error("reloc_db_select: the selected database is shared; upload or share per slot instead"); return RELOC_E_STATE; }
-    db_store_slot(ctx);
-    const DbArena &a = ctx->db_slot[slot];
-    ctx->db_sel = slot;
-    ctx->db_cap_records = a.cap_records; ctx->db_cap_rows = a.cap_rows; ctx->db_records = a.records; ctx->db_rows = a.rows;
-    ctx->db_max_rows = a.max_rows; ctx->db_desc = a.desc; ctx->db_pts3d = a.pts3d; ctx->db_kp2d = a.kp2d; ctx->db_off = a.off;
-    ctx->db_pose = a.pose; ctx->db_xy_heading = a.xy_heading; ctx->db_counts = a.counts; ctx->topk_part = a.topk_part;
-    ctx->topk_blocks = a.topk_blocks;
-    ctx->db_share = a.share;
-    return RELOC_OK;
-}
-
-RELOC_API int reloc_db_fetch(reloc_ctx *ctx, int64_t record, uint8_t *desc, float *pts3d, float *kp2d, double pose[7],
-                             double index_xyh[4], int32_t *n)
-{
-    ARG_CHECK_CTX(ctx, record >= 0, "reloc_db_fetch");
-    if (!db_ready(ctx) || record >= ctx->db_records) { reloc_set_error("db fetch: record %lld of %lld", (long long)record, (long long)ctx->db_records); return RELOC_E_STATE; }
-    int64_t o[2];
-    HIP_TRY(hipMemcpyAsync(o, ctx->db_off + record, 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    const int64_t cnt = o[1] - o[0];
-    if (n) *n = (int32_t)cnt;
-    if (cnt > 0) {
-        if (desc) HIP_TRY(hipMemcpyAsync(desc, ctx->db_desc + o[0] * 32, (size_t)cnt * 32, hipMemcpyDeviceToHost, ctx->stream));
-        if (pts3d) HIP_TRY(hipMemcpyAsync(pts3d, ctx->db_pts3d + o[0] * 3, (size_t)cnt * 12, hipMemcpyDeviceToHost, ctx->stream));
-        if (kp2d) HIP_TRY(hipMemcpyAsync(kp2d, ctx->db_kp2d + o[0] * 2, (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (pose) HIP_TRY(hipMemcpyAsync(pose, ctx->db_pose + 7 * record, 56, hipMemcpyDeviceToHost, ctx->stream));
-    if (index_xyh) HIP_TRY(hipMemcpyAsync(index_xyh, ctx->db_xy_heading + 4 * record, 32, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return RELOC_OK;
-}
-
-RELOC_API int64_t reloc_db_records(reloc_ctx *ctx) { return ctx ? ctx->db_records : -1; }
-RELOC_API int64_t reloc_db_rows(reloc_ctx *ctx) { return ctx ? ctx->db_rows : -1; }
-
+// ---- scans of the selected database (the database itself: reloc_db.hip) -----------------------
 RELOC_API int reloc_db_match_counts_dev(reloc_ctx *ctx, const uint8_t *cur_dev, const int32_t *n_cur_dev, int n_cur_max,
                                         int32_t *counts_dev)
 {
@@ -1814,18 +1487,19 @@ RELOC_API int reloc_db_ratio_counts(reloc_ctx *ctx, const uint8_t *cur, int n_cu
 {
     ARG_CHECK_CTX(ctx, counts && n_cur >= 0 && (n_cur == 0 || cur) && ratio > 0, "reloc_db_ratio_counts");
     if (!db_ready(ctx)) { reloc_set_error("no database uploaded"); return RELOC_E_STATE; }
-    if (n_cur == 0) { memset(counts, 0, (size_t)ctx->db_records * 4); return RELOC_OK; }
+    const DbArena &db = ctx_db(ctx);
+    if (n_cur == 0) { memset(counts, 0, (size_t)db.records * 4); return RELOC_OK; }
     if (n_cur > 65535) { reloc_set_error("ratio scan: more than 65535 current descriptors"); return RELOC_E_CAPACITY; }
     void *dc;
     int rc;
     if ((rc = reloc_scratch(ctx, 0, (int64_t)n_cur * 32, &dc))) return rc;
     HIP_TRY(hipMemcpyAsync(dc, cur, (size_t)n_cur * 32, hipMemcpyHostToDevice, ctx->stream));
     int grid = ctx->num_cu * 4;
-    if (grid > ctx->db_records) grid = (int)ctx->db_records;
-    hipLaunchKernelGGL(k_db_ratio, dim3(grid), dim3(256), 0, ctx->stream, (const uint4 *)ctx->db_desc, ctx->db_off,
-                       (int)ctx->db_records, (const uint4 *)dc, (const int32_t *)nullptr, n_cur, ratio, ctx->db_counts);
+    if (grid > db.records) grid = (int)db.records;
+    hipLaunchKernelGGL(k_db_ratio, dim3(grid), dim3(256), 0, ctx->stream, (const uint4 *)db.desc, db.off,
+                       (int)db.records, (const uint4 *)dc, (const int32_t *)nullptr, n_cur, ratio, db.counts);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(counts, ctx->db_counts, (size_t)ctx->db_records * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(counts, db.counts, (size_t)db.records * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return RELOC_OK;
 }
@@ -1834,13 +1508,14 @@ RELOC_API int reloc_db_match_counts(reloc_ctx *ctx, const uint8_t *cur, int n_cu
 {
     ARG_CHECK_CTX(ctx, counts && n_cur >= 0 && (n_cur == 0 || cur), "reloc_db_match_counts");
     if (!db_ready(ctx)) { reloc_set_error("no database uploaded"); return RELOC_E_STATE; }
-    if (n_cur == 0) { memset(counts, 0, (size_t)ctx->db_records * 4); return RELOC_OK; }
+    const DbArena &db = ctx_db(ctx);
+    if (n_cur == 0) { memset(counts, 0, (size_t)db.records * 4); return RELOC_OK; }
     void *dc;
     int rc;
     if ((rc = reloc_scratch(ctx, 0, (int64_t)n_cur * 32, &dc))) return rc;
     HIP_TRY(hipMemcpyAsync(dc, cur, (size_t)n_cur * 32, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = reloc_db_match_counts_dev(ctx, (const uint8_t *)dc, nullptr, n_cur, ctx->db_counts))) return rc;
-    HIP_TRY(hipMemcpyAsync(counts, ctx->db_counts, (size_t)ctx->db_records * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = reloc_db_match_counts_dev(ctx, (const uint8_t *)dc, nullptr, n_cur, db.counts))) return rc;
+    HIP_TRY(hipMemcpyAsync(counts, db.counts, (size_t)db.records * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return RELOC_OK;
 }

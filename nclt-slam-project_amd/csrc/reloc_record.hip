@@ -336,11 +336,11 @@ RELOC_API int reloc_tick_accumulate_dev(reloc_ctx *ctx, const uint16_t *depth_mm
 {
     ARG_CHECK_CTX(ctx, depth_mm_dev && base_pose && w >= 64 && h >= 64, "reloc_tick_accumulate_dev");
     if (!db_ready(ctx)) { reloc_set_error("no database uploaded"); return RELOC_E_STATE; }
-    if (ctx->db_shared) { reloc_set_error("the selected database is shared from another context (read-only here)"); return RELOC_E_STATE; }
-    if (ctx->db_records + 1 > ctx->db_cap_records || ctx->db_rows + ctx->max_feat > ctx->db_cap_rows) {
+    const DbArena &db = ctx_db(ctx);
+    if (db.shared) { reloc_set_error("the selected database is shared from another context (read-only here)"); return RELOC_E_STATE; }
+    if (db.records + 1 > db.cap_records || db.rows + ctx->max_feat > db.cap_rows) {
         // grow first (drains the stream): the kernel writes behind the last row without asking
-        int rc = db_reserve(ctx, ctx->db_cap_records + ctx->db_cap_records / 2 + 64,
-                            ctx->db_cap_rows + ctx->db_cap_rows / 2 + 64 * (int64_t)ctx->max_feat);
+        int rc = db_reserve(ctx, db.cap_records + db.cap_records / 2 + 64, db.cap_rows + db.cap_rows / 2 + 64 * (int64_t)ctx->max_feat);
         if (rc) return rc;
     }
     if (int rc = image_chain_depth(ctx, depth_mm_dev, &w, &h, &depth_mm_dev)) return rc;      // from here on the working frame
@@ -352,11 +352,11 @@ RELOC_API int reloc_tick_accumulate_dev(reloc_ctx *ctx, const uint16_t *depth_mm
     p.min_dist = ctx->prm.accum_min_dist_m;
     p.zmin = (float)ctx->prm.accum_depth_min_m; p.zmax = (float)ctx->prm.accum_depth_max_m;
     p.w = w; p.h = h; p.min_kpts = ctx->prm.accum_min_kpts; p.silence_ok = silence_ok;
-    p.L = ctx->db_records; p.T = ctx->db_rows;
+    p.L = db.records; p.T = db.rows;
     auto kern = ctx->has_dist ? k_accumulate<true> : k_accumulate<false>;
     hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, ctx->stream, ctx->f_xy, ctx->f_desc, ctx->f_count, ctx->max_feat,
-                       depth_mm_dev, w, p, ctx->tick_res, ctx->db_xy_heading, ctx->db_desc, ctx->db_pts3d, ctx->db_kp2d, ctx->db_off,
-                       ctx->db_pose, ctx->accum_res, make_dist(ctx->dist));
+                       depth_mm_dev, w, p, ctx->tick_res, db.xy_heading, db.desc, db.pts3d, db.kp2d, db.off, db.pose, ctx->accum_res,
+                       make_dist(ctx->dist));
     HIP_TRY(hipGetLastError());
     return RELOC_OK;
 }
@@ -369,9 +369,10 @@ RELOC_API int reloc_accumulate_result(reloc_ctx *ctx, int32_t *appended, int32_t
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (r.appended == 1) {
         // adopt the record the kernel wrote behind the last row; exactly once per accumulate call
-        ctx->db_records += 1;
-        ctx->db_rows += r.n_kpts;
-        if (r.n_kpts > ctx->db_max_rows) ctx->db_max_rows = r.n_kpts;
+        DbArena &db = ctx_db(ctx);
+        db.records += 1;
+        db.rows += r.n_kpts;
+        if (r.n_kpts > db.max_rows) db.max_rows = r.n_kpts;
         const int32_t zero = 0;
         HIP_TRY(hipMemcpyAsync(&ctx->accum_res->appended, &zero, 4, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -438,8 +438,9 @@ __global__ __launch_bounds__(TICK_BLOCK) void k_candidates_near(const double *__
 // host side: one launch (k_candidates_near), or the two stages for very large databases / RELOC_LOCAL_TWO_STAGE=1
 static void launch_candidates_local(reloc_ctx *ctx, const TickParams &prm)
 {
+    const DbArena &db = ctx_db(ctx);
     if (prm.n_records <= NEAR_MAX_RECORDS && !ctx->local_two_stage) {
-        hipLaunchKernelGGL(k_candidates_near, dim3(1), dim3(TICK_BLOCK), 0, ctx->stream, ctx->db_xy_heading, prm, ctx->cand_ids,
+        hipLaunchKernelGGL(k_candidates_near, dim3(1), dim3(TICK_BLOCK), 0, ctx->stream, db.xy_heading, prm, ctx->cand_ids,
                            ctx->cand_n, ctx->tick_flags);
         return;
     }
@@ -447,8 +448,8 @@ static void launch_candidates_local(reloc_ctx *ctx, const TickParams &prm)
     const int nb = L > TOPK_SLICE ? (L + TOPK_SLICE - 1) / TOPK_SLICE : 0;
     if (nb)
         hipLaunchKernelGGL(k_topk_part<LocalKey>, dim3(nb), dim3(TICK_BLOCK), 0, ctx->stream,
-                           LocalKey{ctx->db_xy_heading, prm.base_pose[0], prm.base_pose[1]}, L, k, ctx->topk_part);
-    hipLaunchKernelGGL(k_candidates_local, dim3(1), dim3(TICK_BLOCK), 0, ctx->stream, ctx->db_xy_heading, prm, ctx->topk_part, nb,
+                           LocalKey{db.xy_heading, prm.base_pose[0], prm.base_pose[1]}, L, k, db.topk_part);
+    hipLaunchKernelGGL(k_candidates_local, dim3(1), dim3(TICK_BLOCK), 0, ctx->stream, db.xy_heading, prm, db.topk_part, nb,
                        ctx->cand_ids, ctx->cand_n, ctx->tick_flags);
 }
 
@@ -585,7 +586,7 @@ static TickParams make_tick_params(reloc_ctx *ctx, const double base_pose[7], in
     for (int k = 0; k < 9; ++k) p.b2c_R[k] = ctx->b2c_R[k];
     p.mode = mode;
     p.check_consistency = check_consistency;
-    p.n_records = (int)ctx->db_records;
+    p.n_records = (int)ctx_db(ctx).records;
     const reloc_params &q = ctx->prm;
     p.max_candidates = q.max_candidates; p.min_matches = q.min_matches; p.min_inliers = q.min_inliers;
     p.global_min_inliers = q.global_min_inliers;
@@ -623,7 +624,7 @@ __global__ void k_set_candidates_batch(const int32_t *__restrict__ ids, int k, S
 static TopkFrame topk_frame(const reloc_ctx *c, int32_t *out_ids, int32_t *out_counts, int32_t *out_nfeat, bool auto_mode)
 {
     TopkFrame F;
-    F.counts = c->db_counts; F.out_ids = out_ids; F.out_counts = out_counts; F.out_n = c->cand_n;
+    F.counts = ctx_db(c).counts; F.out_ids = out_ids; F.out_counts = out_counts; F.out_n = c->cand_n;
     F.skip_if = auto_mode ? (const int32_t *)c->cand_n : (const int32_t *)nullptr;   // AUTO: stands down when local candidates exist
     F.relocating = c->tick_flags; F.f_count = c->f_count; F.out_nfeat = out_nfeat;
     return F;
@@ -643,9 +644,10 @@ static FinalFrame final_frame(const reloc_ctx *c, const double base_pose[7], Tic
 static void launch_topk_counts(reloc_ctx *const *ctxs, int n, const TopkBatch &b, int k, int id_base)
 {
     reloc_ctx *c0 = ctxs[0];
-    const int L = (int)c0->db_records;
+    const DbArena &db = ctx_db(c0);
+    const int L = (int)db.records;
     // a count cannot exceed the rows of the largest record nor the features of a frame
-    const int max_count = c0->db_max_rows < c0->max_feat ? c0->db_max_rows : c0->max_feat;
+    const int max_count = db.max_rows < c0->max_feat ? db.max_rows : c0->max_feat;
     const size_t lds = (size_t)(max_count + 2) * sizeof(int);
     if (n == 1) {
         const TopkFrame &F = b.f[0];
@@ -664,10 +666,10 @@ static int launch_tick_finalize(reloc_ctx *const *ctxs, int n, const FinalBatch 
     if (n == 1) {
         const FinalFrame &F = b.f[0];
         prm.seq = F.seq;
-        hipLaunchKernelGGL(k_tick_finalize, dim3(1), dim3(64), 0, c0->stream, F.cand_ids, F.cand_n, F.pnp, c0->db_pose, F.f_count, prm,
+        hipLaunchKernelGGL(k_tick_finalize, dim3(1), dim3(64), 0, c0->stream, F.cand_ids, F.cand_n, F.pnp, ctx_db(c0).pose, F.f_count, prm,
                            F.relocating, F.res, F.res_host, F.res_ext);
     } else {
-        hipLaunchKernelGGL(k_tick_finalize_batch, dim3(n), dim3(64), 0, c0->stream, b, c0->db_pose, prm);
+        hipLaunchKernelGGL(k_tick_finalize_batch, dim3(n), dim3(64), 0, c0->stream, b, ctx_db(c0).pose, prm);
     }
     HIP_TRY(hipGetLastError());
     return RELOC_OK;
@@ -684,12 +686,12 @@ static int scan_counts(reloc_ctx *const *ctxs, int n, const double *base_poses, 
     if (n == 1) {
         ScanMask mask;
         if (base_poses) {
-            mask.xyh = c0->db_xy_heading;
+            mask.xyh = ctx_db(c0).xy_heading;
             for (int k = 0; k < 4; ++k) mask.q[k] = base_poses[3 + k];
         }
         mask.cos_tol = cos_tol;
         mask.skip_if = auto_mode ? c0->cand_n : nullptr;
-        rc = launch_db_count(c0, c0->f_desc, c0->f_count, c0->max_feat, c0->db_counts, mask);
+        rc = launch_db_count(c0, c0->f_desc, c0->f_count, c0->max_feat, ctx_db(c0).counts, mask);
     } else {
         double q[4 * RELOC_BATCH_MAX];
         for (int f = 0; f < n; ++f)
@@ -758,7 +760,7 @@ static int ctx_batch_check(reloc_ctx *const *ctxs, int n, const char *who)
         reloc_ctx *c = ctxs[f];
         if (!c) { reloc_set_error("bad argument: %s: NULL context", who); return RELOC_E_ARG; }
         if (!db_ready(c)) { reloc_set_error("no database uploaded"); return RELOC_E_STATE; }
-        if (c->stream != c0->stream || c->device != c0->device || c->db_desc != c0->db_desc || c->db_records != c0->db_records ||
+        if (c->stream != c0->stream || c->device != c0->device || ctx_db(c).desc != ctx_db(c0).desc || ctx_db(c).records != ctx_db(c0).records ||
             c->max_feat != c0->max_feat || memcmp(&c->prm, &c0->prm, sizeof(reloc_params)) != 0 ||
             memcmp(c->K4, c0->K4, sizeof(c->K4)) != 0 || memcmp(c->b2c_t, c0->b2c_t, sizeof(c->b2c_t)) != 0 ||
             memcmp(c->b2c_R, c0->b2c_R, sizeof(c->b2c_R)) != 0 || memcmp(c->dist, c0->dist, sizeof(c->dist)) != 0) {
@@ -976,7 +978,7 @@ RELOC_API int reloc_shard_scan_batch_dev(reloc_ctx *const *ctxs, int n, const ui
     int rc = ctx_batch_check(ctxs, n, "reloc_shard_scan_batch_dev");
     if (rc) return rc;
     ARG_CHECK(imgs_dev && scan_out_dev && k > 0 && k <= MAX_CAND && w >= 64 && h >= 64 && id_base >= 0 &&
-              id_base + ctxs[0]->db_records <= 0x7fffffff, "reloc_shard_scan_batch_dev");
+              id_base + ctx_db(ctxs[0]).records <= 0x7fffffff, "reloc_shard_scan_batch_dev");
     for (int f = 0; f < n; ++f) ARG_CHECK(imgs_dev[f], "reloc_shard_scan_batch_dev: NULL frame");
     // frame f's list goes to row f of scan_out_dev: 2k + 2 int32 (k ids + id_base, k counts, feature count, 0)
     TopkBatch out;
