@@ -23,13 +23,6 @@ RELOC_API int reloc_device_count(void)
     return n;
 }
 
-template <typename T>
-static int dalloc(T **p, int64_t count)
-{
-    HIP_TRY(hipMalloc((void **)p, (size_t)(count > 0 ? count : 1) * sizeof(T)));
-    return 0;
-}
-
 static int ctx_alloc(reloc_ctx *c)
 {
     int rc = 0;
@@ -42,49 +35,38 @@ static int ctx_alloc(reloc_ctx *c)
         pyr += ((w + 63) / 64 * 64) * h + 256;
     }
     c->pyr_bytes = pyr;
-    rc |= dalloc(&c->pyr, pyr);
-    rc |= dalloc(&c->blur, pyr);
-    rc |= dalloc(&c->nms, pyr);
-    rc |= dalloc(&c->rz_tab, (int64_t)NLEV * 2 * 2 * (c->max_w > c->max_h ? c->max_w : c->max_h));
-    rc |= dalloc((char **)&c->pyr_tiles, (int64_t)((c->max_w + 15) / 16) * ((c->max_h + 15) / 16) * 128);   // >= any k_pyramid tiling
-    rc |= dalloc(&c->hist, NLEV * 256);
-    rc |= dalloc(&c->cand_cnt, NLEV);
-    rc |= dalloc(&c->cand_key, (int64_t)NLEV * RELOC_ORB_STAGE1_CAP);
-    rc |= dalloc(&c->cand_resp, (int64_t)NLEV * RELOC_ORB_STAGE1_CAP);
-    rc |= dalloc(&c->kp_cnt, NLEV);
-    rc |= dalloc(&c->kp_key, (int64_t)NLEV * RELOC_ORB_STAGE1_CAP);
-    rc |= dalloc(&c->kp_resp, (int64_t)NLEV * RELOC_ORB_STAGE1_CAP);
-    rc |= dalloc(&c->f_xy, mf * 2);
-    rc |= dalloc(&c->f_size, mf);
-    rc |= dalloc(&c->f_angle, mf);
-    rc |= dalloc(&c->f_resp, mf);
-    rc |= dalloc(&c->f_oct, mf);
-    rc |= dalloc(&c->f_desc, mf * 32);
-    rc |= dalloc(&c->f_count, 1);
-    rc |= dalloc(&c->frame_img, (int64_t)c->max_w * c->max_h * 3);
-    rc |= dalloc((char **)&c->orb_const, 1024);
-    rc |= dalloc(&c->dbg_cut, NLEV);
-    rc |= dalloc(&c->cand_ids, MAX_CAND);
-    rc |= dalloc(&c->cand_n, 1);
-    rc |= dalloc(&c->m_qidx, (int64_t)MAX_CAND * MAX_REC_ROWS);
-    rc |= dalloc(&c->m_tidx, (int64_t)MAX_CAND * MAX_REC_ROWS);
-    rc |= dalloc(&c->m_dist, (int64_t)MAX_CAND * MAX_REC_ROWS);
-    rc |= dalloc(&c->m_n, MAX_CAND);
-    rc |= dalloc(&c->p_obj, (int64_t)MAX_CAND * MAX_REC_ROWS * 3);
-    rc |= dalloc(&c->p_img, (int64_t)MAX_CAND * MAX_REC_ROWS * 2);
-    rc |= dalloc(&c->p_Rt, (int64_t)MAX_CAND * MAX_HYP * 12);
-    rc |= dalloc(&c->p_cnt, (int64_t)MAX_CAND * MAX_HYP);
-    rc |= dalloc(&c->p_inl, (int64_t)MAX_CAND * MAX_REC_ROWS);
-    rc |= dalloc(&c->p_out, MAX_CAND);
-    rc |= dalloc(&c->tick_res, 1);
+    for (uint8_t **p : {&c->pyr, &c->blur, &c->nms}) rc |= ctx_dev_alloc(c, p, pyr);
+    rc |= ctx_dev_alloc(c, &c->rz_tab, (int64_t)NLEV * 2 * 2 * (c->max_w > c->max_h ? c->max_w : c->max_h));
+    rc |= ctx_dev_alloc(c, (char **)&c->pyr_tiles, (int64_t)((c->max_w + 15) / 16) * ((c->max_h + 15) / 16) * 128);   // >= any k_pyramid tiling
+    rc |= ctx_dev_alloc(c, &c->hist, NLEV * 256);
+    for (int32_t **p : {&c->cand_cnt, &c->kp_cnt, &c->dbg_cut}) rc |= ctx_dev_alloc(c, p, NLEV);
+    for (uint32_t **p : {&c->cand_key, &c->kp_key}) rc |= ctx_dev_alloc(c, p, (int64_t)NLEV * RELOC_ORB_STAGE1_CAP);
+    for (float **p : {&c->cand_resp, &c->kp_resp}) rc |= ctx_dev_alloc(c, p, (int64_t)NLEV * RELOC_ORB_STAGE1_CAP);
+    rc |= ctx_dev_alloc(c, &c->f_xy, mf * 2);
+    for (float **p : {&c->f_size, &c->f_angle, &c->f_resp}) rc |= ctx_dev_alloc(c, p, mf);
+    rc |= ctx_dev_alloc(c, &c->f_oct, mf);
+    rc |= ctx_dev_alloc(c, &c->f_desc, mf * 32);
+    rc |= ctx_dev_alloc(c, &c->f_count, 1);
+    rc |= ctx_dev_alloc(c, &c->frame_img, (int64_t)c->max_w * c->max_h * 3);
+    rc |= ctx_dev_alloc(c, (char **)&c->orb_const, 1024);
+    rc |= ctx_dev_alloc(c, &c->cand_ids, MAX_CAND);
+    rc |= ctx_dev_alloc(c, &c->cand_n, 1);
+    for (int32_t **p : {&c->m_qidx, &c->m_tidx, &c->m_dist, &c->p_inl}) rc |= ctx_dev_alloc(c, p, (int64_t)MAX_CAND * MAX_REC_ROWS);
+    rc |= ctx_dev_alloc(c, &c->m_n, MAX_CAND);
+    rc |= ctx_dev_alloc(c, &c->p_obj, (int64_t)MAX_CAND * MAX_REC_ROWS * 3);
+    rc |= ctx_dev_alloc(c, &c->p_img, (int64_t)MAX_CAND * MAX_REC_ROWS * 2);
+    rc |= ctx_dev_alloc(c, &c->p_Rt, (int64_t)MAX_CAND * MAX_HYP * 12);
+    rc |= ctx_dev_alloc(c, &c->p_cnt, (int64_t)MAX_CAND * MAX_HYP);
+    rc |= ctx_dev_alloc(c, &c->p_out, MAX_CAND);
+    rc |= ctx_dev_alloc(c, &c->tick_res, 1);
     if (hipHostMalloc((void **)&c->tick_res_host, sizeof(TickResult), hipHostMallocDefault) != hipSuccess) {
         reloc_set_error("hipHostMalloc(result record) failed");
         c->tick_res_host = nullptr;
         rc |= RELOC_E_HIP;
     } else memset(c->tick_res_host, 0, sizeof(TickResult));
-    rc |= dalloc(&c->accum_res, 1);
-    rc |= dalloc(&c->tick_flags, 4);
-    rc |= dalloc(&c->scan_ticket, (8 * 8 + 1) * 32);
+    rc |= ctx_dev_alloc(c, &c->accum_res, 1);
+    rc |= ctx_dev_alloc(c, &c->tick_flags, 4);
+    rc |= ctx_dev_alloc(c, &c->scan_ticket, (8 * 8 + 1) * 32);
     if (rc == 0 && hipMemset(c->scan_ticket, 0, (8 * 8 + 1) * 32 * 4) != hipSuccess) rc = RELOC_E_HIP;
     return rc;
 }
@@ -163,18 +145,9 @@ RELOC_API void reloc_destroy(reloc_ctx *c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (DbArena &db : c->db_slot) db_arena_release(db);      // owner or adopter alike: one reference each
-    void *ptrs[] = {c->pyr, c->blur, c->nms, c->rz_tab, c->pyr_tiles, c->hist, c->cand_cnt, c->cand_key, c->cand_resp,
-                    c->kp_cnt, c->kp_key, c->kp_resp, c->f_xy, c->f_size, c->f_angle, c->f_resp, c->f_oct,
-                    c->f_desc, c->f_count, c->frame_img, c->orb_const, c->dbg_cut, c->cand_ids, c->cand_n, c->m_qidx,
-                    c->m_tidx, c->m_dist, c->m_n, c->p_obj, c->p_img, c->p_Rt, c->p_cnt, c->p_inl,
-                    c->p_out, c->tick_res, c->accum_res, c->tick_flags, c->scan_ticket, c->clahe_plane, c->clahe_lut,
-                    c->rect_xy /* owns rect_alpha, rect_depth and rect_plane */,
-                    c->rsz_tab /* owns rsz_ntab, rsz_plane and rsz_depth */, c->bayer_plane};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
+    for (void *p : c->dev_blocks) (void)hipFree(p);
+    for (void *p : c->scratch) if (p) (void)hipFree(p);
     if (c->tick_res_host) (void)hipHostFree(c->tick_res_host);
-    for (int i = 0; i < 8; ++i)
-        if (c->scratch[i]) (void)hipFree(c->scratch[i]);
     for (int k = 0; k < RELOC_PROF_N; ++k)
         if (c->prof[k].init)
             for (int i = 0; i < RELOC_PROF_RING; ++i) {
@@ -308,21 +281,28 @@ RELOC_API int reloc_timer_end(reloc_ctx *c, float *ms)
     return RELOC_OK;
 }
 
-int reloc_scratch(reloc_ctx *c, int slot, int64_t bytes, void **out)
+// ---- staging of the host-pointer entry points (HostStaging, reloc_internal.h) -----------------------------------
+void *HostStaging::slot_bytes(int s, int64_t bytes)
 {
-    if (c->scratch_bytes[slot] < bytes) {
-        if (c->scratch[slot]) {
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            HIP_TRY(hipFree(c->scratch[slot]));
-            c->scratch[slot] = nullptr;
-            c->scratch_bytes[slot] = 0;
+    void *&p = ctx->scratch[s];
+    int64_t &cap = ctx->scratch_bytes[s];
+    if (!rc && cap < bytes) {
+        if (p) hip(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");      // work in flight may still use the slot
+        if (p && !rc) hip(hipFree(p), "hipFree(scratch)");
+        if (!rc) {
+            p = nullptr; cap = 0;
+            hip(hipMalloc(&p, (size_t)(bytes + bytes / 4 + 4096)), "hipMalloc(scratch)");
+            if (!rc) cap = bytes + bytes / 4 + 4096;
         }
-        int64_t cap = bytes + bytes / 4 + 4096;
-        HIP_TRY(hipMalloc(&c->scratch[slot], (size_t)cap));
-        c->scratch_bytes[slot] = cap;
     }
-    *out = c->scratch[slot];
-    return RELOC_OK;
+    return rc ? nullptr : p;
+}
+
+void HostStaging::hip(hipError_t e, const char *what)
+{
+    if (rc || e == hipSuccess) return;
+    reloc_set_error("%s failed: %s", what, hipGetErrorString(e));
+    rc = RELOC_E_HIP;
 }
 
 // ---- per-kernel HIP-event stopwatch ----------------------------------------------------------

@@ -55,7 +55,7 @@ int db_reindex(reloc_ctx *ctx)
     for (const DbArena &db : ctx->db_slot) {
         if (!db.pose || !db.xy_heading || db.records <= 0) continue;
         hipLaunchKernelGGL(k_db_reheading, dim3((unsigned)((db.records + 255) / 256)), dim3(256), 0, ctx->stream, db.pose, db.records,
-                           ctx->b2c_R[0], ctx->b2c_R[1], ctx->b2c_R[2], db.xy_heading);
+                           ctx->cam.b2c_R[0], ctx->cam.b2c_R[1], ctx->cam.b2c_R[2], db.xy_heading);
     }
     HIP_TRY(hipGetLastError());
     return RELOC_OK;
@@ -175,7 +175,7 @@ RELOC_API int reloc_db_upload(reloc_ctx *ctx, const uint8_t *desc, const float *
     if (n_records > 0) {
         HIP_TRY(hipMemcpyAsync(db.pose, poses, (size_t)n_records * 56, hipMemcpyHostToDevice, ctx->stream));
         hipLaunchKernelGGL(k_db_index, dim3((unsigned)((n_records + 255) / 256)), dim3(256), 0, ctx->stream, db.pose, (int64_t)0,
-                           n_records, ctx->b2c_R[0], ctx->b2c_R[1], ctx->b2c_R[2], db.xy_heading);
+                           n_records, ctx->cam.b2c_R[0], ctx->cam.b2c_R[1], ctx->cam.b2c_R[2], db.xy_heading);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -219,8 +219,8 @@ RELOC_API int reloc_db_append(reloc_ctx *ctx, const uint8_t *desc, const float *
     const int64_t end = T + n;
     HIP_TRY(hipMemcpyAsync(db.off + L + 1, &end, 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(db.pose + 7 * L, pose, 56, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_db_index, dim3(1), dim3(64), 0, ctx->stream, db.pose, L, (int64_t)1, ctx->b2c_R[0], ctx->b2c_R[1],
-                       ctx->b2c_R[2], db.xy_heading);
+    hipLaunchKernelGGL(k_db_index, dim3(1), dim3(64), 0, ctx->stream, db.pose, L, (int64_t)1, ctx->cam.b2c_R[0], ctx->cam.b2c_R[1],
+                       ctx->cam.b2c_R[2], db.xy_heading);
     HIP_TRY(hipGetLastError());
     if (index_xy) HIP_TRY(hipMemcpyAsync(db.xy_heading + 4 * L, index_xy, 16, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));     // the host sources may go away; the record is visible from here on

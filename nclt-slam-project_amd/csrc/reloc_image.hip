@@ -865,41 +865,36 @@ static int resize_launch(hipStream_t st, const ResizeFrames &F, int n, const Res
 
 // ---- image chain ----------------------------------------------------------------------------------------------
 // bytes per pixel of the frames that enter the chain through orb_run: a raw mosaic with the Bayer stage on, else 3 channels
-int image_chain_frame_bpp(const reloc_ctx *c) { return c->bayer_code ? 1 : 3; }
+int image_chain_frame_bpp(const reloc_ctx *c) { return c->img.bayer.on() ? 1 : 3; }
 
-// a frame or depth image of *w x *h enters the downscale stage of c: *w x *h becomes the working frame
-static int resize_enter(const reloc_ctx *c, int *w, int *h)
+// a frame or depth image of *w x *h enters the downscale stage r: *w x *h becomes the working frame
+static int resize_enter(const ResizeStage &r, int *w, int *h)
 {
-    if (*w == c->rsz_sw && *h == c->rsz_sh) { *w = c->rsz_dw; *h = c->rsz_dh; return RELOC_OK; }
-    reloc_set_error("frame %dx%d differs from the source size %dx%d of the downscale stage (reloc_set_resize)", *w, *h, c->rsz_sw, c->rsz_sh);
+    if (*w == r.sw && *h == r.sh) { *w = r.dw; *h = r.dh; return RELOC_OK; }
+    reloc_set_error("frame %dx%d differs from the source size %dx%d of the downscale stage (reloc_set_resize)", *w, *h, r.sw, r.sh);
     return RELOC_E_ARG;
 }
-// ... and the rectification of c
-static int rectify_enter(const reloc_ctx *c, int w, int h)
+// ... and the rectification r
+static int rectify_enter(const RectifyStage &r, int w, int h)
 {
-    if (w == c->rect_w && h == c->rect_h) return RELOC_OK;
-    reloc_set_error("frame %dx%d differs from the rectification map %dx%d (reloc_set_rectify_map)", w, h, c->rect_w, c->rect_h);
+    if (w == r.w && h == r.h) return RELOC_OK;
+    reloc_set_error("frame %dx%d differs from the rectification map %dx%d (reloc_set_rectify_map)", w, h, r.w, r.h);
     return RELOC_E_ARG;
 }
+
+static int batch_unequal(const char *what) { reloc_set_error("orb batch: contexts %s", what); return RELOC_E_STATE; }
 
 // Before orb_prepare: the contexts agree on the Bayer and the downscale stage, a frame has the latter's source size; w x h
 // becomes the working frame, which orb_prepare and everything downstream see.
 int image_chain_check(reloc_ctx *const *ctxs, int n, int channels, int *w, int *h)
 {
-    const reloc_ctx *c0 = ctxs[0];
+    const auto &s0 = ctxs[0]->img;
     for (int f = 0; f < n; ++f) {
-        const reloc_ctx *c = ctxs[f];
-        if (c->rsz_sw != c0->rsz_sw || c->rsz_sh != c0->rsz_sh || c->rsz_dw != c0->rsz_dw || c->rsz_dh != c0->rsz_dh) {
-            reloc_set_error("orb batch: contexts with and without the downscale stage, or with unequal sizes (reloc_set_resize)");
-            return RELOC_E_STATE;
-        }
-        if (c->bayer_code != c0->bayer_code) {
-            reloc_set_error("orb batch: contexts with and without the Bayer stage, or of unequal patterns (reloc_set_bayer)");
-            return RELOC_E_STATE;
-        }
+        if (!ctxs[f]->img.resize.same(s0.resize)) return batch_unequal("with and without the downscale stage, or with unequal sizes (reloc_set_resize)");
+        if (!ctxs[f]->img.bayer.same(s0.bayer)) return batch_unequal("with and without the Bayer stage, or of unequal patterns (reloc_set_bayer)");
     }
-    if (channels != 3 || c0->rsz_dw <= 0) return RELOC_OK;
-    if (int rc = resize_enter(c0, w, h)) return rc;
+    if (channels != 3 || !s0.resize.on()) return RELOC_OK;
+    if (int rc = resize_enter(s0.resize, w, h)) return rc;
     if (*w < 64 || *h < 64) { reloc_set_error("bad argument: the working frame %dx%d of the downscale stage is below 64x64", *w, *h); return RELOC_E_ARG; }
     return RELOC_OK;
 }
@@ -908,16 +903,10 @@ int image_chain_check(reloc_ctx *const *ctxs, int n, int channels, int *w, int *
 // context 0 on rectification and CLAHE; behind the last context, a 3-channel working frame has the size of the map.
 int image_chain_check_prepared(reloc_ctx *const *ctxs, int f, int n, int channels, int w, int h)
 {
-    const reloc_ctx *c0 = ctxs[0], *c = ctxs[f];
-    if (c->rect_w != c0->rect_w || c->rect_h != c0->rect_h) {
-        reloc_set_error("orb batch: contexts with and without a rectification map, or with maps of unequal size (reloc_set_rectify_map)");
-        return RELOC_E_STATE;
-    }
-    if (c->clahe_tx != c0->clahe_tx || c->clahe_ty != c0->clahe_ty || c->clahe_clip != c0->clahe_clip) {
-        reloc_set_error("orb batch: contexts of unequal CLAHE settings (reloc_set_clahe)");
-        return RELOC_E_STATE;
-    }
-    return f == n - 1 && channels == 3 && c0->rect_w > 0 ? rectify_enter(c0, w, h) : RELOC_OK;
+    const auto &s0 = ctxs[0]->img, &s = ctxs[f]->img;
+    if (!s.rectify.same(s0.rectify)) return batch_unequal("with and without a rectification map, or with maps of unequal size (reloc_set_rectify_map)");
+    if (!s.clahe.same(s0.clahe)) return batch_unequal("of unequal CLAHE settings (reloc_set_clahe)");
+    return f == n - 1 && channels == 3 && s0.rectify.on() ? rectify_enter(s0.rectify, w, h) : RELOC_OK;
 }
 
 // The gray half, on the stream of the (checked) contexts: frames *srcs of sw x sh, rows of *stride bytes (3 channels, or raw
@@ -929,8 +918,9 @@ int image_chain_gray(reloc_ctx *const *ctxs, int n, const uint8_t *const **srcs,
 {
     if (*channels != 3) return RELOC_OK;
     const reloc_ctx *c0 = ctxs[0];
+    const auto &s0 = c0->img;
     enum { STAGE_BAYER, STAGE_RESIZE, STAGE_RECTIFY, STAGE_CLAHE, N_STAGES };       // the order of the chain
-    const bool on[N_STAGES] = {c0->bayer_code != 0, c0->rsz_dw > 0, c0->rect_w > 0, c0->clahe_tx > 0};
+    const bool on[N_STAGES] = {s0.bayer.on(), s0.resize.on(), s0.rectify.on(), s0.clahe.on()};
     for (int s = 0; s < N_STAGES; ++s) {
         if (!on[s]) continue;
         const uint8_t *const *in = *srcs;
@@ -938,22 +928,25 @@ int image_chain_gray(reloc_ctx *const *ctxs, int n, const uint8_t *const **srcs,
         int rc;
         if (s == STAGE_BAYER) {
             BayerFrames F = {};
-            for (int f = 0; f < n; ++f) { F.src[f] = in[f]; planes[f] = F.dst[f] = ctxs[f]->bayer_plane; }
-            rc = bayer_launch(c0->stream, F, n, sw, sh, *stride, cs, c0->bayer_code, 1, flags);
+            for (int f = 0; f < n; ++f) { F.src[f] = in[f]; planes[f] = F.dst[f] = ctxs[f]->img.bayer.plane; }
+            rc = bayer_launch(c0->stream, F, n, sw, sh, *stride, cs, s0.bayer.code, 1, flags);
         } else if (s == STAGE_RESIZE) {
             ResizeFrames F = {};
-            for (int f = 0; f < n; ++f) { F.src[f] = in[f]; F.tab[f] = ctxs[f]->rsz_tab; planes[f] = F.dst[f] = ctxs[f]->rsz_plane; }
+            for (int f = 0; f < n; ++f) { F.src[f] = in[f]; F.tab[f] = ctxs[f]->img.resize.tab; planes[f] = F.dst[f] = ctxs[f]->img.resize.plane; }
             ResizePlan P;
-            P.kind = c0->rsz_kind; P.isx = c0->rsz_isx; P.isy = c0->rsz_isy;
+            P.kind = s0.resize.kind; P.isx = s0.resize.isx; P.isy = s0.resize.isy;
             rc = resize_launch(c0->stream, F, n, P, sw, sh, *stride, w, h, cs, *channels, 1, *channels == 3, flags);
         } else if (s == STAGE_RECTIFY) {
             RemapFrames F = {};
-            for (int f = 0; f < n; ++f) { F.src[f] = in[f]; F.xy[f] = ctxs[f]->rect_xy; F.alpha[f] = ctxs[f]->rect_alpha; planes[f] = F.dst[f] = ctxs[f]->rect_plane; }
+            for (int f = 0; f < n; ++f) {
+                const RectifyStage &r = ctxs[f]->img.rectify;
+                F.src[f] = in[f]; F.xy[f] = r.xy; F.alpha[f] = r.alpha; planes[f] = F.dst[f] = r.plane;
+            }
             rc = remap_launch(c0->stream, F, n, RemapGeom{w, h, *stride, w, h, cs, 0}, *channels, *channels == 3, flags);
         } else {
             ClaheFrames F = {};
-            for (int f = 0; f < n; ++f) { F.src[f] = in[f]; F.lut[f] = ctxs[f]->clahe_lut; planes[f] = F.dst[f] = ctxs[f]->clahe_plane; }
-            rc = clahe_launch(c0->stream, F, n, clahe_geom(w, h, c0->clahe_clip, c0->clahe_tx, c0->clahe_ty), *channels, *stride, flags, cs);
+            for (int f = 0; f < n; ++f) { F.src[f] = in[f]; F.lut[f] = ctxs[f]->img.clahe.lut; planes[f] = F.dst[f] = ctxs[f]->img.clahe.plane; }
+            rc = clahe_launch(c0->stream, F, n, clahe_geom(w, h, s0.clahe.clip, s0.clahe.tx, s0.clahe.ty), *channels, *stride, flags, cs);
         }
         if (rc) return rc;
         *srcs = planes; *stride = cs; *channels = 1;
@@ -966,53 +959,39 @@ int image_chain_gray(reloc_ctx *const *ctxs, int n, const uint8_t *const **srcs,
 int image_chain_depth(reloc_ctx *ctx, const uint16_t *depth_dev, int *w, int *h, const uint16_t **out)
 {
     *out = depth_dev;
-    if (ctx->rsz_dw > 0) {
+    if (const ResizeStage &r = ctx->img.resize; r.on()) {
         const int sw = *w, sh = *h;
-        if (int rc = resize_enter(ctx, w, h)) return rc;
+        if (int rc = resize_enter(r, w, h)) return rc;
         ResizeFrames F = {};
-        F.src[0] = (const uint8_t *)*out; F.tab[0] = ctx->rsz_ntab; F.dst[0] = (uint8_t *)ctx->rsz_depth;
+        F.src[0] = (const uint8_t *)*out; F.tab[0] = r.ntab; F.dst[0] = (uint8_t *)r.depth;
         ResizePlan P;
         P.kind = RESIZE_NEAREST;
         if (int rc = resize_launch(ctx->stream, F, 1, P, sw, sh, sw, *w, *h, *w, 1, 2, false, 0)) return rc;
-        *out = ctx->rsz_depth;
+        *out = r.depth;
     }
-    if (ctx->rect_w > 0) {
-        if (int rc = rectify_enter(ctx, *w, *h)) return rc;
+    if (const RectifyStage &r = ctx->img.rectify; r.on()) {
+        if (int rc = rectify_enter(r, *w, *h)) return rc;
         RemapFrames F = {};
-        F.src[0] = (const uint8_t *)*out; F.xy[0] = ctx->rect_xy; F.dst[0] = (uint8_t *)ctx->rect_depth;
+        F.src[0] = (const uint8_t *)*out; F.xy[0] = r.xy; F.dst[0] = (uint8_t *)r.depth;
         if (int rc = remap_nearest_launch(ctx->stream, F, RemapGeom{*w, *h, *w, *w, *h, *w, 0}, 1, 2)) return rc;      // strides in elements
-        *out = ctx->rect_depth;
+        *out = r.depth;
     }
     return RELOC_OK;
 }
 
 // ---- entry points ---------------------------------------------------------------------------------------------
-// The round trip of a host-pointer entry point on the context's stream: src (rows of row_bytes, sstride apart) into
-// ctx->frame_img with dense rows, launch(dout) enqueues the work that writes scratch slot out_slot, out_bytes of it back to
-// out, synchronise.  Capacity checks and slot numbers stay with the entry point: the slots say who may overlap with whom.
-template <typename Launch>
-static int host_round_trip(reloc_ctx *ctx, const void *src, int row_bytes, int rows, int sstride, int out_slot, void *out,
-                           int64_t out_bytes, Launch launch)
-{
-    void *dout;
-    if (int rc = reloc_scratch(ctx, out_slot, out_bytes, &dout)) return rc;
-    HIP_TRY(hipMemcpy2DAsync(ctx->frame_img, row_bytes, src, sstride, row_bytes, rows, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = launch((uint8_t *)dout)) return rc;
-    HIP_TRY(hipMemcpyAsync(out, dout, (size_t)out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return RELOC_OK;
-}
-
+// A host-pointer entry point stages through HostStaging: the source into ctx->frame_img with dense rows, tables and the
+// destination in scratch slots.  Capacity checks and slot numbers stay with the entry point.
 RELOC_API int reloc_gray_u8(reloc_ctx *ctx, const uint8_t *img, int w, int h, int stride, int order, uint8_t *gray)
 {
     ARG_CHECK_CTX(ctx, img && gray && w > 0 && h > 0 && stride >= 3 * w, "reloc_gray_u8");
     if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
-    return host_round_trip(ctx, img, w * 3, h, stride, 0, gray, (int64_t)w * h, [&](uint8_t *dout) {
-        hipLaunchKernelGGL(k_gray_plain, dim3((w + 255) / 256, h), dim3(256), 0, ctx->stream, ctx->frame_img, w, h, w * 3, gray_flags(ctx, order),
-                           dout);
-        HIP_TRY(hipGetLastError());
-        return RELOC_OK;
-    });
+    HostStaging st{ctx};
+    uint8_t *dout = st.slot<uint8_t>(0, (int64_t)w * h);
+    st.upload_rows(ctx->frame_img, img, w * 3, h, stride);
+    st.launch(k_gray_plain, dim3((w + 255) / 256, h), dim3(256), ctx->frame_img, w, h, w * 3, gray_flags(ctx, order), dout);
+    st.download(gray, dout, (int64_t)w * h);
+    return st.finish();
 }
 
 // ---- Bayer entry points --------------------------------------------------------------------------------
@@ -1021,27 +1000,31 @@ RELOC_API int reloc_bayer_u8(reloc_ctx *ctx, const uint8_t *raw, int w, int h, i
     ARG_CHECK_CTX(ctx, raw && out_bgr && w >= 3 && h >= 3 && stride >= w, "reloc_bayer_u8: NULL pointer, or a mosaic below 3 x 3");
     ARG_CHECK(bayer_code_ok(code), "reloc_bayer_u8: code must be one of COLOR_BayerBG2BGR .. COLOR_BayerGR2BGR (46..49)");
     if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
-    return host_round_trip(ctx, raw, w, h, stride, 0, out_bgr, (int64_t)w * h * 3, [&](uint8_t *dout) {
-        BayerFrames F = {};
-        F.src[0] = ctx->frame_img; F.dst[0] = dout;
-        return bayer_launch(ctx->stream, F, 1, w, h, w, 3 * w, code, 3, 0);
-    });
+    HostStaging st{ctx};
+    uint8_t *dout = st.slot<uint8_t>(0, (int64_t)w * h * 3);
+    st.upload_rows(ctx->frame_img, raw, w, h, stride);
+    BayerFrames F = {};
+    F.src[0] = ctx->frame_img; F.dst[0] = dout;
+    st.run([&] { return bayer_launch(ctx->stream, F, 1, w, h, w, 3 * w, code, 3, 0); });
+    st.download(out_bgr, dout, (int64_t)w * h * 3);
+    return st.finish();
 }
 
 RELOC_API int reloc_set_bayer(reloc_ctx *ctx, int code)
 {
     ARG_CHECK_CTX(ctx, true, "ctx is NULL");
     ARG_CHECK(code == 0 || bayer_code_ok(code), "reloc_set_bayer: code must be 0 (off) or one of COLOR_BayerBG2BGR .. COLOR_BayerGR2BGR (46..49)");
-    // first enable: the gray plane of the largest mosaic
-    if (code && !ctx->bayer_plane) HIP_TRY(hipMalloc((void **)&ctx->bayer_plane, stage_plane_bytes(ctx)));
-    ctx->bayer_code = code;
+    BayerStage &b = ctx->img.bayer;
+    if (code && !b.plane)       // first enable: the gray plane of the largest mosaic
+        if (int rc = ctx_dev_alloc(ctx, &b.plane, stage_plane_bytes(ctx))) return rc;
+    b.code = code;
     return RELOC_OK;
 }
 
 RELOC_API int reloc_get_bayer(reloc_ctx *ctx, int32_t *code)
 {
     ARG_CHECK_CTX(ctx, code, "reloc_get_bayer");
-    *code = ctx->bayer_code;
+    *code = ctx->img.bayer.code;
     return RELOC_OK;
 }
 
@@ -1054,35 +1037,27 @@ static bool clahe_args_ok(double clip_limit, int tiles_x, int tiles_y)
 RELOC_API int reloc_set_clahe(reloc_ctx *ctx, double clip_limit, int tiles_x, int tiles_y)
 {
     ARG_CHECK_CTX(ctx, true, "ctx is NULL");
+    ClaheStage &c = ctx->img.clahe;
     if (tiles_x == 0 && tiles_y == 0) {
-        ctx->clahe_clip = 0.0;
-        ctx->clahe_tx = ctx->clahe_ty = 0;
+        c.clip = 0.0; c.tx = c.ty = 0;
         return RELOC_OK;
     }
     ARG_CHECK(clahe_args_ok(clip_limit, tiles_x, tiles_y),
               "reloc_set_clahe: tiles_x and tiles_y must both be 0 (off) or both in 1..64, and clip_limit finite");
-    if (!ctx->clahe_plane) {
-        // first enable: the plane of the largest frame and the LUTs of the largest grid
-        HIP_TRY(hipMalloc((void **)&ctx->clahe_plane, stage_plane_bytes(ctx)));
-        const hipError_t e = hipMalloc((void **)&ctx->clahe_lut, (size_t)CLAHE_MAX_TILES * CLAHE_MAX_TILES * 256);
-        if (e != hipSuccess) {
-            (void)hipFree(ctx->clahe_plane);
-            ctx->clahe_plane = nullptr;
-            HIP_TRY(e);
-        }
+    if (!c.plane) {
+        // first enable, one block: the plane of the largest frame, then the LUTs of the largest grid
+        if (int rc = ctx_dev_alloc(ctx, &c.plane, stage_plane_bytes(ctx) + (size_t)CLAHE_MAX_TILES * CLAHE_MAX_TILES * 256)) return rc;
+        c.lut = c.plane + stage_plane_bytes(ctx);
     }
-    ctx->clahe_clip = clip_limit == 0.0 ? 0.0 : clip_limit;     // -0 -> +0: equal settings compare equal
-    ctx->clahe_tx = tiles_x;
-    ctx->clahe_ty = tiles_y;
+    c.clip = clip_limit == 0.0 ? 0.0 : clip_limit;     // -0 -> +0: equal settings compare equal
+    c.tx = tiles_x; c.ty = tiles_y;
     return RELOC_OK;
 }
 
 RELOC_API int reloc_get_clahe(reloc_ctx *ctx, double *clip_limit, int32_t *tiles_x, int32_t *tiles_y)
 {
     ARG_CHECK_CTX(ctx, clip_limit && tiles_x && tiles_y, "reloc_get_clahe");
-    *clip_limit = ctx->clahe_clip;
-    *tiles_x = ctx->clahe_tx;
-    *tiles_y = ctx->clahe_ty;
+    *clip_limit = ctx->img.clahe.clip; *tiles_x = ctx->img.clahe.tx; *tiles_y = ctx->img.clahe.ty;
     return RELOC_OK;
 }
 
@@ -1092,49 +1067,47 @@ RELOC_API int reloc_clahe_u8(reloc_ctx *ctx, const uint8_t *gray, int w, int h, 
     ARG_CHECK_CTX(ctx, gray && out && w >= 1 && h >= 1 && stride >= w, "reloc_clahe_u8");
     ARG_CHECK(clahe_args_ok(clip_limit, tiles_x, tiles_y), "reloc_clahe_u8: tiles_x, tiles_y must be in 1..64 and clip_limit finite");
     if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
-    void *dlut;
-    if (int rc = reloc_scratch(ctx, 0, (int64_t)tiles_x * tiles_y * 256, &dlut)) return rc;
-    return host_round_trip(ctx, gray, w, h, stride, 1, out, (int64_t)w * h, [&](uint8_t *dout) {
-        ClaheFrames F = {};
-        F.src[0] = ctx->frame_img; F.lut[0] = (uint8_t *)dlut; F.dst[0] = dout;
-        return clahe_launch(ctx->stream, F, 1, clahe_geom(w, h, clip_limit, tiles_x, tiles_y), 1, w, 0, w);
-    });
+    HostStaging st{ctx};
+    uint8_t *dlut = st.slot<uint8_t>(0, (int64_t)tiles_x * tiles_y * 256), *dout = st.slot<uint8_t>(1, (int64_t)w * h);
+    st.upload_rows(ctx->frame_img, gray, w, h, stride);
+    ClaheFrames F = {};
+    F.src[0] = ctx->frame_img; F.lut[0] = dlut; F.dst[0] = dout;
+    st.run([&] { return clahe_launch(ctx->stream, F, 1, clahe_geom(w, h, clip_limit, tiles_x, tiles_y), 1, w, 0, w); });
+    st.download(out, dout, (int64_t)w * h);
+    return st.finish();
 }
 
 // ---- rectification entry points ----------------------------------------------------------------------------
 RELOC_API int reloc_set_rectify_map(reloc_ctx *ctx, const int16_t *xy, const uint16_t *alpha, int w, int h)
 {
     ARG_CHECK_CTX(ctx, true, "ctx is NULL");
+    RectifyStage &r = ctx->img.rectify;
     if (!xy) {
-        ctx->rect_w = ctx->rect_h = 0;
+        r.w = r.h = 0;
         return RELOC_OK;
     }
     ARG_CHECK(alpha && w >= 1 && h >= 1, "reloc_set_rectify_map: alpha is NULL or the size is not positive");
     if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("rectification map exceeds ctx capacity"); return RELOC_E_CAPACITY; }
-    if (!ctx->rect_xy) {
-        // first enable: maps and planes of the largest frame, in one allocation (rect_xy owns it)
-        const size_t px = (size_t)ctx->max_w * ctx->max_h, plane = stage_plane_bytes(ctx);
-        uint8_t *base;
-        HIP_TRY(hipMalloc((void **)&base, px * 4 + px * 2 + px * 2 + plane));
-        ctx->rect_xy = (int16_t *)base;
-        ctx->rect_alpha = (uint16_t *)(base + px * 4);
-        ctx->rect_depth = (uint16_t *)(base + px * 6);
-        ctx->rect_plane = base + px * 8;
+    if (!r.plane) {
+        // first enable, one block: the plane, then maps and depth of the largest frame
+        const size_t px = (size_t)ctx->max_w * ctx->max_h;
+        if (int rc = ctx_dev_alloc(ctx, &r.plane, stage_plane_bytes(ctx) + px * 4 + px * 2 + px * 2)) return rc;
+        r.xy = (int16_t *)(r.plane + stage_plane_bytes(ctx));
+        r.alpha = (uint16_t *)(r.xy + px * 2);
+        r.depth = r.alpha + px;
     }
     // frames in flight may still read the previous map
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(ctx->rect_xy, xy, (size_t)w * h * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ctx->rect_alpha, alpha, (size_t)w * h * 2, hipMemcpyHostToDevice));
-    ctx->rect_w = w;
-    ctx->rect_h = h;
+    HIP_TRY(hipMemcpy(r.xy, xy, (size_t)w * h * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(r.alpha, alpha, (size_t)w * h * 2, hipMemcpyHostToDevice));
+    r.w = w; r.h = h;
     return RELOC_OK;
 }
 
 RELOC_API int reloc_get_rectify_map(reloc_ctx *ctx, int32_t *w, int32_t *h)
 {
     ARG_CHECK_CTX(ctx, w && h, "reloc_get_rectify_map");
-    *w = ctx->rect_w;
-    *h = ctx->rect_h;
+    *w = ctx->img.rectify.w; *h = ctx->img.rectify.h;
     return RELOC_OK;
 }
 
@@ -1144,16 +1117,17 @@ static int remap_host(reloc_ctx *ctx, const void *src, int sstride, int channels
 {
     if (g.sw > ctx->max_w || g.sh > ctx->max_h || g.dw > ctx->max_w || g.dh > ctx->max_h) { reloc_set_error("image or map exceeds ctx capacity"); return RELOC_E_CAPACITY; }
     const int64_t px = (int64_t)g.dw * g.dh, out_bytes = px * channels * elem;
-    void *dxy, *dal;
-    if (int rc = reloc_scratch(ctx, 0, px * 4, &dxy)) return rc;
-    if (int rc = reloc_scratch(ctx, 1, px * 2, &dal)) return rc;
-    return host_round_trip(ctx, src, g.sw * channels * elem, g.sh, sstride, 2, out, out_bytes, [&](uint8_t *dout) {
-        HIP_TRY(hipMemcpyAsync(dxy, xy, (size_t)px * 4, hipMemcpyHostToDevice, ctx->stream));
-        if (alpha) HIP_TRY(hipMemcpyAsync(dal, alpha, (size_t)px * 2, hipMemcpyHostToDevice, ctx->stream));
-        RemapFrames F = {};
-        F.src[0] = ctx->frame_img; F.xy[0] = (const int16_t *)dxy; F.alpha[0] = (const uint16_t *)dal; F.dst[0] = dout;
-        return nearest ? remap_nearest_launch(ctx->stream, F, g, channels, elem) : remap_launch(ctx->stream, F, 1, g, channels, false, 0);
-    });
+    HostStaging st{ctx};
+    const int16_t *dxy = st.upload_slot(0, xy, px * 2);
+    uint16_t *dal = st.slot<uint16_t>(1, px);
+    uint8_t *dout = st.slot<uint8_t>(2, out_bytes);
+    st.upload_rows(ctx->frame_img, src, g.sw * channels * elem, g.sh, sstride);
+    if (alpha) st.upload(dal, alpha, px * 2);
+    RemapFrames F = {};
+    F.src[0] = ctx->frame_img; F.xy[0] = dxy; F.alpha[0] = dal; F.dst[0] = dout;
+    st.run([&] { return nearest ? remap_nearest_launch(ctx->stream, F, g, channels, elem) : remap_launch(ctx->stream, F, 1, g, channels, false, 0); });
+    st.download(out, dout, out_bytes);
+    return st.finish();
 }
 
 RELOC_API int reloc_remap_u8(reloc_ctx *ctx, const uint8_t *src, int sw, int sh, int sstride, int channels, const int16_t *xy,
@@ -1181,25 +1155,18 @@ RELOC_API int reloc_convert_maps(reloc_ctx *ctx, const float *mapx, const float 
     ARG_CHECK_CTX(ctx, mapx && mapy && xy_out && alpha_out && w >= 1 && h >= 1, "reloc_convert_maps");
     if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("map exceeds ctx capacity"); return RELOC_E_CAPACITY; }
     const int64_t n = (int64_t)w * h;
-    void *dmx, *dmy, *dxy, *dal;
-    int rc;
-    if ((rc = reloc_scratch(ctx, 0, n * 4, &dxy))) return rc;
-    if ((rc = reloc_scratch(ctx, 1, n * 2, &dal))) return rc;
-    if ((rc = reloc_scratch(ctx, 2, n * 4, &dmx))) return rc;
-    if ((rc = reloc_scratch(ctx, 3, n * 4, &dmy))) return rc;
-    HIP_TRY(hipMemcpyAsync(dmx, mapx, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(dmy, mapy, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_convert_maps, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float *)dmx,
-                       (const float *)dmy, (int)n, nninterpolation, (u32 *)dxy, (uint16_t *)dal);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(xy_out, dxy, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(alpha_out, dal, (size_t)n * 2, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return RELOC_OK;
+    HostStaging st{ctx};
+    u32 *dxy = st.slot<u32>(0, n);
+    uint16_t *dal = st.slot<uint16_t>(1, n);
+    const float *dmx = st.upload_slot(2, mapx, n), *dmy = st.upload_slot(3, mapy, n);
+    st.launch(k_convert_maps, dim3((unsigned)((n + 255) / 256)), dim3(256), dmx, dmy, (int)n, nninterpolation, dxy, dal);
+    st.download(xy_out, dxy, n * 4);
+    st.download(alpha_out, dal, n * 2);
+    return st.finish();
 }
 
 // ---- resize entry points -------------------------------------------------------------------------------------
-// a host-pointer resize: table into scratch 0, destination scratch 1, then the round trip
+// a host-pointer resize: table into scratch 0, destination scratch 1
 static int resize_host(reloc_ctx *ctx, const void *src, int sw, int sh, int sstride, int channels, int elem, void *out, int dw, int dh,
                        double inv_x, double inv_y, int interpolation)
 {
@@ -1208,17 +1175,18 @@ static int resize_host(reloc_ctx *ctx, const void *src, int sw, int sh, int sstr
     if (int rc = resize_plan(sw, sh, dw, dh, inv_x, inv_y, interpolation, P)) return rc;
     const int row_bytes = sw * channels * elem;
     const int64_t out_bytes = (int64_t)dw * dh * channels * elem;
-    void *dtab;
-    if (int rc = reloc_scratch(ctx, 0, (int64_t)P.tab.size() * 4 + 4, &dtab)) return rc;
-    return host_round_trip(ctx, src, row_bytes, sh, sstride, 1, out, out_bytes, [&](uint8_t *dout) {
-        // the table is pageable host memory that dies with this call: the copy below is complete when the call returns
-        if (!P.tab.empty()) HIP_TRY(hipMemcpyAsync(dtab, P.tab.data(), P.tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        ResizeFrames F = {};
-        F.src[0] = ctx->frame_img; F.tab[0] = (const int32_t *)dtab; F.dst[0] = dout;
-        const bool by_elem = P.kind == RESIZE_NEAREST;      // k_resize_nearest counts strides in elements
-        return resize_launch(ctx->stream, F, 1, P, sw, sh, by_elem ? sw * channels : row_bytes, dw, dh, dw * channels, channels, elem,
-                             false, 0);
-    });
+    HostStaging st{ctx};
+    int32_t *dtab = st.slot<int32_t>(0, (int64_t)P.tab.size() + 1);
+    uint8_t *dout = st.slot<uint8_t>(1, out_bytes);
+    st.upload_rows(ctx->frame_img, src, row_bytes, sh, sstride);
+    // the table is pageable host memory that dies with this call: finish() has waited for the copy by then
+    if (!P.tab.empty()) st.upload(dtab, P.tab.data(), (int64_t)P.tab.size() * 4);
+    ResizeFrames F = {};
+    F.src[0] = ctx->frame_img; F.tab[0] = dtab; F.dst[0] = dout;
+    const int stride = P.kind == RESIZE_NEAREST ? sw * channels : row_bytes;      // k_resize_nearest counts strides in elements
+    st.run([&] { return resize_launch(ctx->stream, F, 1, P, sw, sh, stride, dw, dh, dw * channels, channels, elem, false, 0); });
+    st.download(out, dout, out_bytes);
+    return st.finish();
 }
 
 RELOC_API int reloc_resize_u8(reloc_ctx *ctx, const uint8_t *src, int sw, int sh, int sstride, int channels, uint8_t *out, int dw,
@@ -1239,8 +1207,9 @@ RELOC_API int reloc_resize_u16(reloc_ctx *ctx, const uint16_t *src, int sw, int 
 RELOC_API int reloc_set_resize(reloc_ctx *ctx, int sw, int sh, int dw, int dh)
 {
     ARG_CHECK_CTX(ctx, true, "ctx is NULL");
+    ResizeStage &r = ctx->img.resize;
     if (sw == 0 && sh == 0 && dw == 0 && dh == 0) {
-        ctx->rsz_sw = ctx->rsz_sh = ctx->rsz_dw = ctx->rsz_dh = 0;
+        r.sw = r.sh = r.dw = r.dh = 0;
         return RELOC_OK;
     }
     ARG_CHECK(dw >= 1 && dh >= 1 && dw <= sw && dh <= sh,
@@ -1250,31 +1219,30 @@ RELOC_API int reloc_set_resize(reloc_ctx *ctx, int sw, int sh, int dw, int dh)
     if (int rc = resize_plan(sw, sh, dw, dh, 0.0, 0.0, 3, area)) return rc;
     if (int rc = resize_plan(sw, sh, dw, dh, 0.0, 0.0, 0, nearest)) return rc;
     // tables of the largest frame: 3 words and at most scale + 2 alphas per destination index and axis, one offset per index
-    // and axis for the depth; then the gray plane and the depth plane, in one allocation (rsz_tab owns it)
+    // and axis for the depth
     const size_t area_words = 6 * ((size_t)ctx->max_w + ctx->max_h), near_words = (size_t)ctx->max_w + ctx->max_h;
     if (area.tab.size() > area_words || nearest.tab.size() > near_words) { reloc_set_error("resize tables exceed ctx capacity"); return RELOC_E_CAPACITY; }
-    if (!ctx->rsz_tab) {
-        const size_t px = (size_t)ctx->max_w * ctx->max_h, plane = stage_plane_bytes(ctx);
-        const size_t tab_bytes = ((area_words + near_words) * 4 + 255) & ~(size_t)255;
-        uint8_t *base;
-        HIP_TRY(hipMalloc((void **)&base, tab_bytes + plane + px * 2));
-        ctx->rsz_tab = (int32_t *)base;
-        ctx->rsz_ntab = ctx->rsz_tab + area_words;
-        ctx->rsz_plane = base + tab_bytes;
-        ctx->rsz_depth = (uint16_t *)(base + tab_bytes + plane);
+    if (!r.plane) {
+        // first enable, one block: the plane, then the tables and the depth plane
+        const size_t bytes = stage_plane_bytes(ctx) + (area_words + near_words) * 4 + (size_t)ctx->max_w * ctx->max_h * 2;
+        if (int rc = ctx_dev_alloc(ctx, &r.plane, bytes)) return rc;
+        r.tab = (int32_t *)(r.plane + stage_plane_bytes(ctx));
+        r.ntab = r.tab + area_words;
+        r.depth = (uint16_t *)(r.ntab + near_words);
     }
     // frames in flight may still read the previous tables
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (!area.tab.empty()) HIP_TRY(hipMemcpy(ctx->rsz_tab, area.tab.data(), area.tab.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ctx->rsz_ntab, nearest.tab.data(), nearest.tab.size() * 4, hipMemcpyHostToDevice));
-    ctx->rsz_kind = area.kind; ctx->rsz_isx = area.isx; ctx->rsz_isy = area.isy;
-    ctx->rsz_sw = sw; ctx->rsz_sh = sh; ctx->rsz_dw = dw; ctx->rsz_dh = dh;
+    if (!area.tab.empty()) HIP_TRY(hipMemcpy(r.tab, area.tab.data(), area.tab.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(r.ntab, nearest.tab.data(), nearest.tab.size() * 4, hipMemcpyHostToDevice));
+    r.kind = area.kind; r.isx = area.isx; r.isy = area.isy;
+    r.sw = sw; r.sh = sh; r.dw = dw; r.dh = dh;
     return RELOC_OK;
 }
 
 RELOC_API int reloc_get_resize(reloc_ctx *ctx, int32_t *sw, int32_t *sh, int32_t *dw, int32_t *dh)
 {
     ARG_CHECK_CTX(ctx, sw && sh && dw && dh, "reloc_get_resize");
-    *sw = ctx->rsz_sw; *sh = ctx->rsz_sh; *dw = ctx->rsz_dw; *dh = ctx->rsz_dh;
+    const ResizeStage &r = ctx->img.resize;
+    *sw = r.sw; *sh = r.sh; *dw = r.dw; *dh = r.dh;
     return RELOC_OK;
 }

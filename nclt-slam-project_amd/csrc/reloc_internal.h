@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <vector>
+
 #include "../../include/reloc.h"
 #include "../../include/reloc_spec.h"
 
@@ -272,6 +274,70 @@ struct ScanMask {
     const int32_t *skip_if = nullptr;            // RELOC_TICK_AUTO: the whole launch stands down when *skip_if != 0
 };
 
+// ---- context state ("Context state") ------------------------------------------------------------------------
+// Device memory: every fixed block (ctx_alloc's buffers, the one block of a stage's first enable) comes from ctx_dev_alloc
+// and is freed by reloc_destroy from ctx->dev_blocks, the scratch slots of HostStaging in the same place; a DbArena owns its
+// database.  Settings: one struct per image stage and one for the camera, next to the buffers they fill.  on(): the stage
+// runs.  same(): two contexts may share a batched launch; it compares every setting of its struct and no buffer, and nothing
+// else decides that (ctx_batch_check, image_chain_check*): a new setting is compared because it is a member of its stage.
+
+// camera (reference M:49-52, M:107-112) and lens (reloc_set_camera, reloc_set_distortion)
+struct CameraModel {
+    double K4[4] = {RELOC_FX, RELOC_FY, RELOC_CX, RELOC_CY};
+    double b2c_t[3] = {0.35, 0.0, 0.18};
+    double b2c_R[9] = {0, -1, 0, 0, 0, -1, 1, 0, 0};
+    double dist[5] = {0, 0, 0, 0, 0};   // k1 k2 p1 p2 k3; zeros normalised to +0, so equal models compare equal byte for byte
+    bool has_dist = false;               // a coefficient is non-zero: the DIST kernels run
+    const double *lens() const { return has_dist ? dist : nullptr; }      // NULL = pinhole kernels (make_dist: all zeros)
+    bool same(const CameraModel &o) const
+    {
+        return memcmp(K4, o.K4, sizeof(K4)) == 0 && memcmp(b2c_t, o.b2c_t, sizeof(b2c_t)) == 0 &&
+               memcmp(b2c_R, o.b2c_R, sizeof(b2c_R)) == 0 && memcmp(dist, o.dist, sizeof(dist)) == 0;
+    }
+};
+
+// Bayer stage in front of the whole image chain (reloc_set_bayer): every frame of the chain's entry points is a raw 8-bit mosaic
+struct BayerStage {
+    int code = 0;                        // RELOC_BAYER_*2BGR; 0 = off, the default
+    uint8_t *plane = nullptr;            // demosaiced gray plane, row stride (w + 63) & ~63
+    bool on() const { return code != 0; }
+    bool same(const BayerStage &o) const { return code == o.code; }
+};
+
+// downscale stage at the head of the image chain on 3-channel frames (reloc_set_resize); all 0 = off, the default
+struct ResizeStage {
+    int sw = 0, sh = 0;                  // the size every frame must have
+    int dw = 0, dh = 0;                  // the working frame: what rectification, CLAHE, ORB, the recorder and the camera see
+    int kind = 0, isx = 1, isy = 1;      // kernel kind and integer box of the INTER_AREA resize (reloc_image.hip): derived from the sizes
+    int32_t *tab = nullptr;              // INTER_AREA tap lists
+    int32_t *ntab = nullptr;             // INTER_NEAREST offsets of the depth image
+    uint8_t *plane = nullptr;            // resized gray plane, row stride (dw + 63) & ~63
+    uint16_t *depth = nullptr;           // resized depth (nearest), dense rows of dw
+    bool on() const { return dw > 0; }
+    bool same(const ResizeStage &o) const { return sw == o.sw && sh == o.sh && dw == o.dw && dh == o.dh; }
+};
+
+// rectification in front of ORB and CLAHE on 3-channel frames (reloc_set_rectify_map); 0 x 0 = off, the default
+struct RectifyStage {
+    int w = 0, h = 0;                    // map = frame size
+    int16_t *xy = nullptr;               // max_h x max_w x 2, dense rows of w
+    uint16_t *alpha = nullptr;           // max_h x max_w
+    uint8_t *plane = nullptr;            // rectified gray plane, row stride (w + 63) & ~63
+    uint16_t *depth = nullptr;           // rectified depth (nearest), dense rows of w
+    bool on() const { return w > 0; }
+    bool same(const RectifyStage &o) const { return w == o.w && h == o.h; }      // the maps themselves may differ per context
+};
+
+// CLAHE in front of ORB on 3-channel frames (reloc_set_clahe); tiles 0 x 0 = off, the default
+struct ClaheStage {
+    double clip = 0.0;                   // clipLimit (0 when off; -0 normalised to +0)
+    int tx = 0, ty = 0;                  // tileGridSize
+    uint8_t *plane = nullptr;            // equalised gray plane, row stride (w + 63) & ~63
+    uint8_t *lut = nullptr;              // tiles_y x tiles_x x 256 LUTs (64 x 64 x 256 bytes)
+    bool on() const { return tx > 0; }
+    bool same(const ClaheStage &o) const { return tx == o.tx && ty == o.ty && clip == o.clip; }
+};
+
 struct reloc_ctx {
     int device = 0;
     int max_w = 0, max_h = 0, max_feat = 0;
@@ -286,7 +352,8 @@ struct reloc_ctx {
     // the device in the middle (prof_flush synchronises)
     struct ProfSlot { hipEvent_t a[RELOC_PROF_RING], b[RELOC_PROF_RING]; int n = 0; float total = 0.f; int launches = 0; bool init = false; } prof[RELOC_PROF_N];
 
-    // generic scratch (grown on demand by host-pointer entry points)
+    std::vector<void *> dev_blocks;      // every block ctx_dev_alloc handed out; reloc_destroy frees them
+    // generic scratch (grown on demand by host-pointer entry points: HostStaging)
     void *scratch[8] = {};
     int64_t scratch_bytes[8] = {};
 
@@ -317,38 +384,9 @@ struct reloc_ctx {
     char orb_tab_host[1024];       // host copy of the same table
     int32_t *dbg_cut = nullptr;    // NLEV stage-1 cut scores of the last frame
 
-    // ---- camera (reference M:49-52, M:107-112) ----
-    double K4[4] = {RELOC_FX, RELOC_FY, RELOC_CX, RELOC_CY};
-    double b2c_t[3] = {0.35, 0.0, 0.18};
-    double b2c_R[9] = {0, -1, 0, 0, 0, -1, 1, 0, 0};
-    double dist[5] = {0, 0, 0, 0, 0};   // k1 k2 p1 p2 k3 (reloc_set_distortion); zeros normalised to +0
-    bool has_dist = false;               // a coefficient is non-zero: the DIST kernels run
-
-    // ---- CLAHE in front of ORB on 3-channel frames (reloc_set_clahe); tiles 0 x 0 = off, the default ----
-    double clahe_clip = 0.0;             // clipLimit (0 when off; -0 normalised to +0)
-    int clahe_tx = 0, clahe_ty = 0;      // tileGridSize
-    uint8_t *clahe_plane = nullptr;      // equalised gray plane, row stride (w + 63) & ~63 (allocated on first enable)
-    uint8_t *clahe_lut = nullptr;        // tiles_y x tiles_x x 256 LUTs (64 x 64 x 256 bytes, allocated with the plane)
-
-    // ---- rectification in front of ORB and CLAHE on 3-channel frames (reloc_set_rectify_map); 0 x 0 = off, the default ----
-    int rect_w = 0, rect_h = 0;          // map = frame size
-    int16_t *rect_xy = nullptr;          // max_h x max_w x 2, dense rows of rect_w; allocated on first enable, one block with the three below
-    uint16_t *rect_alpha = nullptr;      // max_h x max_w
-    uint8_t *rect_plane = nullptr;       // rectified gray plane, row stride (w + 63) & ~63
-    uint16_t *rect_depth = nullptr;      // rectified depth (nearest), dense rows of rect_w
-
-    // ---- downscale stage at the head of the image chain on 3-channel frames (reloc_set_resize); all 0 = off, the default ----
-    int rsz_sw = 0, rsz_sh = 0;          // the size every frame must have
-    int rsz_dw = 0, rsz_dh = 0;          // the working frame: what rectification, CLAHE, ORB, the recorder and the camera see
-    int rsz_kind = 0, rsz_isx = 1, rsz_isy = 1;   // kernel kind and integer box of the INTER_AREA resize (reloc_image.hip)
-    int32_t *rsz_tab = nullptr;          // INTER_AREA tap lists; allocated on first enable, one block with the three below
-    int32_t *rsz_ntab = nullptr;         // INTER_NEAREST offsets of the depth image
-    uint8_t *rsz_plane = nullptr;        // resized gray plane, row stride (dw + 63) & ~63
-    uint16_t *rsz_depth = nullptr;       // resized depth (nearest), dense rows of rsz_dw
-
-    // ---- Bayer stage in front of the whole image chain (reloc_set_bayer); 0 = off, the default ----
-    int bayer_code = 0;                  // RELOC_BAYER_*2BGR: every frame of the chain's entry points is a raw 8-bit mosaic
-    uint8_t *bayer_plane = nullptr;      // demosaiced gray plane, row stride (w + 63) & ~63 (allocated on first enable)
+    CameraModel cam;
+    // the image chain's stages in its order (reloc_image.hip); a stage's buffers are one block, taken on its first enable
+    struct { BayerStage bayer; ResizeStage resize; RectifyStage rectify; ClaheStage clahe; } img;
 
     // ---- matcher parameters (reloc_set_params) ----
     reloc_params prm;
@@ -382,7 +420,56 @@ struct reloc_ctx {
     TickResult *tick_res_ext = nullptr;    // caller's pinned record for the next ticks (reloc_tick_result_to), or NULL
 };
 
-int reloc_scratch(reloc_ctx *ctx, int slot, int64_t bytes, void **out);
+// The one allocation of a context's fixed device blocks: count elements of T (at least one), recorded for reloc_destroy
+template <typename T>
+static inline int ctx_dev_alloc(reloc_ctx *ctx, T **p, int64_t count)
+{
+    void *q = nullptr;
+    HIP_TRY(hipMalloc(&q, (size_t)(count > 0 ? count : 1) * sizeof(T)));
+    ctx->dev_blocks.push_back(q);
+    *p = (T *)q;
+    return 0;
+}
+
+// The one staging path of the host-pointer entry points, on the context's stream: scratch slots, copies in, launches,
+// copies out, finish.  The first error sticks (rc) and turns everything behind it into a no-op, so an entry point reads as
+// the straight sequence; finish() synchronises whenever something was enqueued, also behind an error -- no copy from or to
+// the caller's memory is in flight when an entry point returns, failed or not.  Slot numbers stay with the entry point: they
+// say which calls may overlap.  A download whose size the device decides takes two phases: count(), then the rows.
+struct HostStaging {
+    reloc_ctx *ctx;
+    int rc = RELOC_OK;
+    bool pending = false;       // work enqueued since the last synchronisation
+    void hip(hipError_t e, const char *what);       // a HIP call's result: the first failure becomes rc and the error text
+    void *slot_bytes(int s, int64_t bytes);         // scratch slot s, re-allocated when too small (drains the stream first)
+    template <typename T>
+    T *slot(int s, int64_t count) { return (T *)slot_bytes(s, count * (int64_t)sizeof(T)); }       // NULL after an error
+    void copy(void *dst, const void *src, int64_t bytes, hipMemcpyKind kind)
+    {
+        run([&] { hip(hipMemcpyAsync(dst, src, (size_t)bytes, kind, ctx->stream), "hipMemcpyAsync"); return rc; });
+    }
+    void upload(void *dst, const void *src, int64_t bytes) { copy(dst, src, bytes, hipMemcpyHostToDevice); }
+    void download(void *dst, const void *src, int64_t bytes) { copy(dst, src, bytes, hipMemcpyDeviceToHost); }
+    // count elements of a host array into scratch slot s
+    template <typename T>
+    T *upload_slot(int s, const T *src, int64_t count) { T *d = slot<T>(s, count); upload(d, src, count * (int64_t)sizeof(T)); return d; }
+    // rows of row_bytes, sstride apart at the caller's, dense on the device
+    void upload_rows(void *dst, const void *src, int row_bytes, int rows, int sstride)
+    {
+        run([&] { hip(hipMemcpy2DAsync(dst, row_bytes, src, sstride, row_bytes, rows, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy2DAsync"); return rc; });
+    }
+    template <typename K, typename... A>
+    void launch(K kern, dim3 grid, dim3 block, A... args)
+    {
+        run([&] { hipLaunchKernelGGL(kern, grid, block, 0, ctx->stream, args...); hip(hipGetLastError(), "kernel launch"); return rc; });
+    }
+    // anything that enqueues on the stream and returns a RELOC_ code (the library's stage launchers)
+    template <typename Fn>
+    void run(Fn fn) { if (!rc) { pending = true; rc = fn(); } }
+    int finish() { if (pending) hip(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"); pending = false; return rc; }
+    // first phase of a two-phase download: the device's count, 0 after an error
+    int32_t count(const int32_t *dev) { int32_t n = 0; download(&n, dev, 4); return finish() ? 0 : n; }
+};
 void reloc_prof_begin(reloc_ctx *ctx, int which);
 void reloc_prof_end(reloc_ctx *ctx, int which);
 

@@ -1384,17 +1384,12 @@ RELOC_API int reloc_hamming_matrix(reloc_ctx *ctx, const uint8_t *a, int64_t na,
 {
     ARG_CHECK_CTX(ctx, a && b && out && na >= 0 && nb >= 0, "reloc_hamming_matrix");
     if (na == 0 || nb == 0) return RELOC_OK;
-    void *da, *db, *dout;
-    int rc;
-    if ((rc = reloc_scratch(ctx, 0, na * 32, &da))) return rc;
-    if ((rc = reloc_scratch(ctx, 1, nb * 32, &db))) return rc;
-    if ((rc = reloc_scratch(ctx, 2, na * nb * 2, &dout))) return rc;
-    HIP_TRY(hipMemcpyAsync(da, a, (size_t)na * 32, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(db, b, (size_t)nb * 32, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = launch_matrix(ctx, (const uint8_t *)da, na, (const uint8_t *)db, nb, (uint16_t *)dout))) return rc;
-    HIP_TRY(hipMemcpyAsync(out, dout, (size_t)na * nb * 2, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return RELOC_OK;
+    HostStaging st{ctx};
+    const uint8_t *da = st.upload_slot(0, a, na * 32), *db = st.upload_slot(1, b, nb * 32);
+    uint16_t *dout = st.slot<uint16_t>(2, na * nb);
+    st.run([&] { return launch_matrix(ctx, da, na, db, nb, dout); });
+    st.download(out, dout, na * nb * 2);
+    return st.finish();
 }
 
 RELOC_API int reloc_match_knn2(reloc_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t, int nt, int32_t *idx,
@@ -1412,24 +1407,17 @@ RELOC_API int reloc_match_knn2(reloc_ctx *ctx, const uint8_t *q, int nq, const u
     if (nsplit > (nt + 63) / 64) nsplit = (nt + 63) / 64;
     const int rows_per_split = (nt + nsplit - 1) / nsplit;
     nsplit = (nt + rows_per_split - 1) / rows_per_split;
-    void *dq, *dt, *dpart, *dout;
-    int rc;
-    if ((rc = reloc_scratch(ctx, 0, (int64_t)nq * 32, &dq))) return rc;
-    if ((rc = reloc_scratch(ctx, 1, (int64_t)nt * 32, &dt))) return rc;
-    if ((rc = reloc_scratch(ctx, 2, (int64_t)nsplit * nq * 8, &dpart))) return rc;
-    if ((rc = reloc_scratch(ctx, 3, (int64_t)nq * 16, &dout))) return rc;
-    HIP_TRY(hipMemcpyAsync(dq, q, (size_t)nq * 32, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(dt, t, (size_t)nt * 32, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_knn2, dim3((nq + 255) / 256, nsplit), dim3(256), 0, ctx->stream, (const uint4 *)dq, nq,
-                       (const uint4 *)dt, nt, rows_per_split, (u32 *)dpart);
-    int32_t *didx = (int32_t *)dout, *ddist = didx + 2 * (size_t)nq;
-    hipLaunchKernelGGL(k_knn2_merge, dim3((nq + 255) / 256), dim3(256), 0, ctx->stream, (const u32 *)dpart, nq, nsplit,
-                       didx, ddist);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(idx, didx, (size_t)nq * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(dist, ddist, (size_t)nq * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return RELOC_OK;
+    HostStaging st{ctx};
+    u32 *dpart = st.slot<u32>(2, (int64_t)nsplit * nq * 2);
+    int32_t *didx = st.slot<int32_t>(3, (int64_t)nq * 4);
+    if (st.rc) return st.rc;
+    int32_t *ddist = didx + 2 * (size_t)nq;
+    const uint8_t *dq = st.upload_slot(0, q, (int64_t)nq * 32), *dt = st.upload_slot(1, t, (int64_t)nt * 32);
+    st.launch(k_knn2, dim3((nq + 255) / 256, nsplit), dim3(256), (const uint4 *)dq, nq, (const uint4 *)dt, nt, rows_per_split, dpart);
+    st.launch(k_knn2_merge, dim3((nq + 255) / 256), dim3(256), dpart, nq, nsplit, didx, ddist);
+    st.download(idx, didx, (int64_t)nq * 8);
+    st.download(dist, ddist, (int64_t)nq * 8);
+    return st.finish();
 }
 
 RELOC_API int reloc_match_mutual(reloc_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t, int nt, int32_t *qidx,
@@ -1440,32 +1428,28 @@ RELOC_API int reloc_match_mutual(reloc_ctx *ctx, const uint8_t *q, int nq, const
     if (nq == 0 || nt == 0) return RELOC_OK;
     ARG_CHECK(q && t && qidx && tidx && dist, "reloc_match_mutual: NULL array");
     if (nq > MAX_REC_ROWS) { reloc_set_error("match: query set larger than %d rows", MAX_REC_ROWS); return RELOC_E_CAPACITY; }
-    void *dq, *dt, *dm;
-    int rc;
-    if ((rc = reloc_scratch(ctx, 0, (int64_t)nq * 32 + 64, &dq))) return rc;
-    if ((rc = reloc_scratch(ctx, 1, (int64_t)nt * 32, &dt))) return rc;
-    if ((rc = reloc_scratch(ctx, 2, (int64_t)nq * 12 + 64, &dm))) return rc;
+    HostStaging st{ctx};
+    uint8_t *dq = st.slot<uint8_t>(0, (int64_t)nq * 32 + 64), *dt = st.slot<uint8_t>(1, (int64_t)nt * 32);
+    int64_t *doff = (int64_t *)st.slot_bytes(2, (int64_t)nq * 12 + 64);
+    if (st.rc) return st.rc;
     // offsets {0, nq} live in front of the match arrays
-    int64_t offs[2] = {0, nq};
-    int64_t *doff = (int64_t *)dm;
+    const int64_t offs[2] = {0, nq};
     int32_t *dn = (int32_t *)(doff + 2);
     int32_t *dqi = dn + 4, *dti = dqi + nq, *ddi = dti + nq;
-    HIP_TRY(hipMemcpyAsync(doff, offs, sizeof(offs), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(dq, q, (size_t)nq * 32, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(dt, t, (size_t)nt * 32, hipMemcpyHostToDevice, ctx->stream));
+    st.upload(doff, offs, sizeof(offs));
+    st.upload(dq, q, (int64_t)nq * 32);
+    st.upload(dt, t, (int64_t)nt * 32);
     // the query set is the one record (rows nq) of a database of its own; nothing runs beside it: 8 waves
     EmitBatch bt = {};
     bt.f[0].cur = (const uint4 *)dt; bt.f[0].m_qidx = dqi; bt.f[0].m_tidx = dti; bt.f[0].m_dist = ddi; bt.f[0].m_n = dn;
-    if ((rc = launch_db_emit(&ctx, 1, bt, (const uint8_t *)dq, doff, nq, nullptr, 1, nt, nq, true))) return rc;
-    int32_t n = 0;
-    HIP_TRY(hipMemcpyAsync(&n, dn, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    st.run([&] { return launch_db_emit(&ctx, 1, bt, dq, doff, nq, nullptr, 1, nt, nq, true); });
+    const int32_t n = st.count(dn);
     if (n > 0) {
-        HIP_TRY(hipMemcpyAsync(qidx, dqi, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(tidx, dti, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(dist, ddi, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        st.download(qidx, dqi, (int64_t)n * 4);
+        st.download(tidx, dti, (int64_t)n * 4);
+        st.download(dist, ddi, (int64_t)n * 4);
     }
+    if (int rc = st.finish()) return rc;
     *n_out = n;
     return RELOC_OK;
 }
@@ -1490,18 +1474,14 @@ RELOC_API int reloc_db_ratio_counts(reloc_ctx *ctx, const uint8_t *cur, int n_cu
     const DbArena &db = ctx_db(ctx);
     if (n_cur == 0) { memset(counts, 0, (size_t)db.records * 4); return RELOC_OK; }
     if (n_cur > 65535) { reloc_set_error("ratio scan: more than 65535 current descriptors"); return RELOC_E_CAPACITY; }
-    void *dc;
-    int rc;
-    if ((rc = reloc_scratch(ctx, 0, (int64_t)n_cur * 32, &dc))) return rc;
-    HIP_TRY(hipMemcpyAsync(dc, cur, (size_t)n_cur * 32, hipMemcpyHostToDevice, ctx->stream));
+    HostStaging st{ctx};
+    const uint8_t *dc = st.upload_slot(0, cur, (int64_t)n_cur * 32);
     int grid = ctx->num_cu * 4;
     if (grid > db.records) grid = (int)db.records;
-    hipLaunchKernelGGL(k_db_ratio, dim3(grid), dim3(256), 0, ctx->stream, (const uint4 *)db.desc, db.off,
-                       (int)db.records, (const uint4 *)dc, (const int32_t *)nullptr, n_cur, ratio, db.counts);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(counts, db.counts, (size_t)db.records * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return RELOC_OK;
+    st.launch(k_db_ratio, dim3(grid), dim3(256), (const uint4 *)db.desc, db.off, (int)db.records, (const uint4 *)dc,
+              (const int32_t *)nullptr, n_cur, ratio, db.counts);
+    st.download(counts, db.counts, db.records * 4);
+    return st.finish();
 }
 
 RELOC_API int reloc_db_match_counts(reloc_ctx *ctx, const uint8_t *cur, int n_cur, int32_t *counts)
@@ -1510,12 +1490,9 @@ RELOC_API int reloc_db_match_counts(reloc_ctx *ctx, const uint8_t *cur, int n_cu
     if (!db_ready(ctx)) { reloc_set_error("no database uploaded"); return RELOC_E_STATE; }
     const DbArena &db = ctx_db(ctx);
     if (n_cur == 0) { memset(counts, 0, (size_t)db.records * 4); return RELOC_OK; }
-    void *dc;
-    int rc;
-    if ((rc = reloc_scratch(ctx, 0, (int64_t)n_cur * 32, &dc))) return rc;
-    HIP_TRY(hipMemcpyAsync(dc, cur, (size_t)n_cur * 32, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = reloc_db_match_counts_dev(ctx, (const uint8_t *)dc, nullptr, n_cur, db.counts))) return rc;
-    HIP_TRY(hipMemcpyAsync(counts, db.counts, (size_t)db.records * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return RELOC_OK;
+    HostStaging st{ctx};
+    const uint8_t *dc = st.upload_slot(0, cur, (int64_t)n_cur * 32);
+    st.run([&] { return reloc_db_match_counts_dev(ctx, dc, nullptr, n_cur, db.counts); });
+    st.download(counts, db.counts, db.records * 4);
+    return st.finish();
 }

@@ -1252,22 +1252,20 @@ RELOC_API int reloc_orb_detect_compute(reloc_ctx *ctx, const uint8_t *gray, int 
     *n_out = 0;
     if (w < 63 || h < 63) return RELOC_OK;   // no level is wider than the 31-pixel edge margin on both sides
     if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
-    HIP_TRY(hipMemcpy2DAsync(ctx->frame_img, w, gray, stride, w, h, hipMemcpyHostToDevice, ctx->stream));
+    HostStaging st{ctx};        // no scratch slot: the context's frame and feature buffers
+    st.upload_rows(ctx->frame_img, gray, w, h, stride);
     const uint8_t *src = ctx->frame_img;
-    int rc = orb_run(&ctx, 1, &src, w, h, w, 1, 0, nfeatures, true);
-    if (rc) return rc;
-    int32_t n = 0;
-    HIP_TRY(hipMemcpyAsync(&n, ctx->f_count, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    st.run([&] { return orb_run(&ctx, 1, &src, w, h, w, 1, 0, nfeatures, true); });
+    const int32_t n = st.count(ctx->f_count);
     if (n > 0) {
-        if (xy) HIP_TRY(hipMemcpyAsync(xy, ctx->f_xy, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (size) HIP_TRY(hipMemcpyAsync(size, ctx->f_size, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (angle) HIP_TRY(hipMemcpyAsync(angle, ctx->f_angle, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (response) HIP_TRY(hipMemcpyAsync(response, ctx->f_resp, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (octave) HIP_TRY(hipMemcpyAsync(octave, ctx->f_oct, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (desc) HIP_TRY(hipMemcpyAsync(desc, ctx->f_desc, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (xy) st.download(xy, ctx->f_xy, (int64_t)n * 8);
+        if (size) st.download(size, ctx->f_size, (int64_t)n * 4);
+        if (angle) st.download(angle, ctx->f_angle, (int64_t)n * 4);
+        if (response) st.download(response, ctx->f_resp, (int64_t)n * 4);
+        if (octave) st.download(octave, ctx->f_oct, (int64_t)n * 4);
+        if (desc) st.download(desc, ctx->f_desc, (int64_t)n * 32);
     }
+    if (int rc = st.finish()) return rc;
     *n_out = n;
     return RELOC_OK;
 }

@@ -992,13 +992,13 @@ int pnp_run_candidates(reloc_ctx *const *ctxs, int n, const uint64_t *seeds, boo
 {
     reloc_ctx *c0 = ctxs[0];
     const reloc_params &q = c0->prm;
-    PnpParams prm = make_params(c0->K4, q.ransac_iterations, (float)q.ransac_reproj_px, q.ransac_confidence, 0, MAX_REC_ROWS,
+    PnpParams prm = make_params(c0->cam.K4, q.ransac_iterations, (float)q.ransac_reproj_px, q.ransac_confidence, 0, MAX_REC_ROWS,
                                 q.min_matches);
     prm.gate_local = q.min_inliers; prm.gate_global = q.global_min_inliers;
     PnpBatch b;
     frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int g) { b.f[f] = pnp_frame(c, seeds ? seeds[g] : 0); });
     // the contexts of a call carry equal coefficients (ctx_batch_check)
-    return pnp_launch(ctxs, n, b, MAX_CAND, prm, c0->has_dist ? c0->dist : nullptr, latency);
+    return pnp_launch(ctxs, n, b, MAX_CAND, prm, c0->cam.lens(), latency);
 }
 
 
@@ -1010,29 +1010,20 @@ static int pnp_score_impl(reloc_ctx *ctx, const float *obj, const float *img, in
     if (H == 0) return RELOC_OK;
     if (m == 0) { for (int h = 0; h < H; ++h) inlier_count[h] = 0; return RELOC_OK; }
     if (H > 65535) { reloc_set_error("pnp_score: more than 65535 hypotheses"); return RELOC_E_CAPACITY; }
-    void *dobj, *dimg, *drt, *dcnt, *dmask = nullptr, *dm;
-    int rc;
-    if ((rc = reloc_scratch(ctx, 0, (int64_t)m * 12, &dobj))) return rc;
-    if ((rc = reloc_scratch(ctx, 1, (int64_t)m * 8, &dimg))) return rc;
-    if ((rc = reloc_scratch(ctx, 2, (int64_t)H * 96, &drt))) return rc;
-    if ((rc = reloc_scratch(ctx, 3, (int64_t)H * 4 + 16, &dcnt))) return rc;
-    if (mask && (rc = reloc_scratch(ctx, 4, (int64_t)H * m, &dmask))) return rc;
-    dm = (char *)dcnt + (int64_t)H * 4;
-    HIP_TRY(hipMemcpyAsync(dobj, obj, (size_t)m * 12, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(dimg, img, (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(drt, Rt, (size_t)H * 96, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemsetAsync(dcnt, 0, (size_t)H * 4, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(dm, &m, 4, hipMemcpyHostToDevice, ctx->stream));
-    const PnpParams prm = make_params(K4, H, thr_px, 0.99, 0, m, 0);
-    auto score = dist ? k_pnp_score<true> : k_pnp_score<false>;
-    hipLaunchKernelGGL(score, dim3(H, 1), dim3(64), 0, ctx->stream, (const float *)dobj, (const float *)dimg,
-                       (const int32_t *)dm, (const int32_t *)nullptr, prm, (const double *)drt, (int32_t *)dcnt,
-                       (uint8_t *)dmask, H, make_dist(dist));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(inlier_count, dcnt, (size_t)H * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (mask) HIP_TRY(hipMemcpyAsync(mask, dmask, (size_t)H * m, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return RELOC_OK;
+    HostStaging st{ctx};
+    int32_t *dcnt = st.slot<int32_t>(3, (int64_t)H + 4);
+    uint8_t *dmask = mask ? st.slot<uint8_t>(4, (int64_t)H * m) : nullptr;
+    if (st.rc) return st.rc;
+    int32_t *dm = dcnt + H;
+    const float *dobj = st.upload_slot(0, obj, (int64_t)m * 3), *dimg = st.upload_slot(1, img, (int64_t)m * 2);
+    const double *drt = st.upload_slot(2, Rt, (int64_t)H * 12);
+    st.upload(dm, &m, 4);
+    st.run([&] { HIP_TRY(hipMemsetAsync(dcnt, 0, (size_t)H * 4, ctx->stream)); return RELOC_OK; });
+    st.launch(dist ? k_pnp_score<true> : k_pnp_score<false>, dim3(H, 1), dim3(64), dobj, dimg, dm, (const int32_t *)nullptr,
+              make_params(K4, H, thr_px, 0.99, 0, m, 0), drt, dcnt, dmask, H, make_dist(dist));
+    st.download(inlier_count, dcnt, (int64_t)H * 4);
+    if (mask) st.download(mask, dmask, (int64_t)H * m);
+    return st.finish();
 }
 
 RELOC_API int reloc_pnp_score(reloc_ctx *ctx, const float *obj, const float *img, int m, const double *Rt, int H,
@@ -1061,21 +1052,21 @@ static int pnp_ransac_impl(reloc_ctx *ctx, const float *obj, const float *img, i
     *n_inl = 0;
     if (m < RELOC_PNP_SAMPLE) return RELOC_OK;
     if (m > MAX_REC_ROWS) { reloc_set_error("solvePnPRansac: more than %d correspondences", MAX_REC_ROWS); return RELOC_E_CAPACITY; }
-    HIP_TRY(hipMemcpyAsync(ctx->p_obj, obj, (size_t)m * 12, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->p_img, img, (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->m_n, &m, 4, hipMemcpyHostToDevice, ctx->stream));
+    HostStaging st{ctx};        // no scratch slot: the context's own PnP buffers
+    st.upload(ctx->p_obj, obj, (int64_t)m * 12);
+    st.upload(ctx->p_img, img, (int64_t)m * 8);
+    st.upload(ctx->m_n, &m, 4);
     // the single-call path has no MIN_MATCHES gate (that gate belongs to the matcher, M:330)
     PnpBatch b;
     b.f[0] = pnp_frame(ctx, seed);
     b.f[0].n_cand_p = nullptr; b.f[0].relocating = nullptr;       // one candidate of m pairs, no relocation flag
-    if (int rc = pnp_launch(&ctx, 1, b, 1, make_params(K4, iters, thr_px, conf, seed, MAX_REC_ROWS, RELOC_PNP_SAMPLE), dist, true))
-        return rc;
-    PnpOut po;
-    HIP_TRY(hipMemcpyAsync(&po, ctx->p_out, sizeof(po), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    st.run([&] { return pnp_launch(&ctx, 1, b, 1, make_params(K4, iters, thr_px, conf, seed, MAX_REC_ROWS, RELOC_PNP_SAMPLE), dist, true); });
+    PnpOut po = {};
+    st.download(&po, ctx->p_out, sizeof(po));
+    if (int rc = st.finish()) return rc;
     if (po.ok) {
-        HIP_TRY(hipMemcpyAsync(inliers, ctx->p_inl, (size_t)po.n_inl * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        st.download(inliers, ctx->p_inl, (int64_t)po.n_inl * 4);
+        if (int rc = st.finish()) return rc;
         for (int k = 0; k < 3; ++k) { rvec[k] = po.rvec[k]; tvec[k] = po.Rt[9 + k]; }
         *n_inl = po.n_inl;
         *ok = 1;
@@ -1122,18 +1113,13 @@ RELOC_API int reloc_undistort_points(reloc_ctx *ctx, const float *img, int m, co
     ARG_CHECK_CTX(ctx, m >= 0 && K4 && (m == 0 || (img && out_norm)), "reloc_undistort_points");
     ARG_CHECK(dist_finite(dist), "reloc_undistort_points: non-finite distortion coefficient");
     if (m == 0) return RELOC_OK;
-    void *dimg, *dout;
-    int rc;
-    if ((rc = reloc_scratch(ctx, 0, (int64_t)m * 8, &dimg))) return rc;
-    if ((rc = reloc_scratch(ctx, 1, (int64_t)m * 16, &dout))) return rc;
-    HIP_TRY(hipMemcpyAsync(dimg, img, (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream));
+    HostStaging st{ctx};
+    const float *dimg = st.upload_slot(0, img, (int64_t)m * 2);
+    double *dout = st.slot<double>(1, (int64_t)m * 2);
     CamK4 k;
     for (int c = 0; c < 4; ++c) k.v[c] = K4[c];
     const int blocks = (int)((m + 255) / 256 < 1024 ? (m + 255) / 256 : 1024);
-    hipLaunchKernelGGL(k_undistort_points, dim3(blocks), dim3(256), 0, ctx->stream, (const float *)dimg, m, k,
-                       make_dist(dist), (double *)dout);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out_norm, dout, (size_t)m * 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return RELOC_OK;
+    st.launch(k_undistort_points, dim3(blocks), dim3(256), dimg, m, k, make_dist(dist), dout);
+    st.download(out_norm, dout, (int64_t)m * 16);
+    return st.finish();
 }

@@ -134,40 +134,37 @@ RELOC_API int reloc_record_frame(reloc_ctx *ctx, const uint8_t *img, const uint1
     if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
     *n_out = 0;
     if (n_kp) *n_kp = 0;
-    int rc;
-    void *ddepth, *dout;
     const int64_t mf = ctx->max_feat;
-    if ((rc = reloc_scratch(ctx, 5, (int64_t)w * h * 2, &ddepth))) return rc;
-    if ((rc = reloc_scratch(ctx, 6, mf * (8 + 32 + 12 + 4) + 64, &dout))) return rc;
-    uint8_t *o_desc = (uint8_t *)dout;
+    HostStaging st{ctx};
+    uint8_t *o_desc = st.slot<uint8_t>(6, mf * (8 + 32 + 12 + 4) + 64);
+    if (st.rc) return st.rc;
     float *o_xy = (float *)(o_desc + mf * 32), *o_pts = o_xy + mf * 2;
     int32_t *o_idx = (int32_t *)(o_pts + mf * 3), *o_n = o_idx + mf;
     const int bpp = image_chain_frame_bpp(ctx);
-    HIP_TRY(hipMemcpyAsync(ctx->frame_img, img, (size_t)w * h * bpp, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ddepth, depth_mm, (size_t)w * h * 2, hipMemcpyHostToDevice, ctx->stream));
-    const uint8_t *src = ctx->frame_img;
-    if ((rc = orb_run(&ctx, 1, &src, w, h, w * bpp, 3, order, nfeatures, true))) return rc;
-    const uint16_t *depth = (const uint16_t *)ddepth;
-    if ((rc = image_chain_depth(ctx, depth, &w, &h, &depth))) return rc;      // from here on the working frame
+    st.upload(ctx->frame_img, img, (int64_t)w * h * bpp);
+    const uint16_t *depth = st.upload_slot(5, depth_mm, (int64_t)w * h);
+    st.run([&] {
+        const uint8_t *src = ctx->frame_img;
+        if (int rc = orb_run(&ctx, 1, &src, w, h, w * bpp, 3, order, nfeatures, true)) return rc;
+        return image_chain_depth(ctx, depth, &w, &h, &depth);      // from here on the working frame
+    });
     RecordParams p;
-    p.fx = ctx->K4[0]; p.fy = ctx->K4[1]; p.cx = ctx->K4[2]; p.cy = ctx->K4[3];
+    p.fx = ctx->cam.K4[0]; p.fy = ctx->cam.K4[1]; p.cx = ctx->cam.K4[2]; p.cy = ctx->cam.K4[3];
     p.depth_min = RELOC_DEPTH_MIN_M; p.depth_max = RELOC_DEPTH_MAX_M; p.var_max = RELOC_DEPTH_VAR_MAX_M;
     p.ground_y = RELOC_GROUND_Y_THRESHOLD; p.w = w; p.h = h;
-    auto kern = ctx->has_dist ? k_record<true> : k_record<false>;
-    hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, ctx->stream, ctx->f_xy, ctx->f_desc, ctx->f_count, ctx->max_feat,
-                       depth, w, p, o_xy, o_desc, o_pts, o_idx, o_n, make_dist(ctx->dist));
-    HIP_TRY(hipGetLastError());
-    int32_t n = 0, nk = 0;
-    HIP_TRY(hipMemcpyAsync(&n, o_n, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&nk, ctx->f_count, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const double *lens = ctx->cam.lens();
+    st.launch(lens ? k_record<true> : k_record<false>, dim3(1), dim3(1024), ctx->f_xy, ctx->f_desc, ctx->f_count, ctx->max_feat, depth,
+              w, p, o_xy, o_desc, o_pts, o_idx, o_n, make_dist(lens));
+    int32_t nk = 0;
+    st.download(&nk, ctx->f_count, 4);
+    const int32_t n = st.count(o_n);
     if (n > 0) {
-        if (xy) HIP_TRY(hipMemcpyAsync(xy, o_xy, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (desc) HIP_TRY(hipMemcpyAsync(desc, o_desc, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream));
-        if (pts3d) HIP_TRY(hipMemcpyAsync(pts3d, o_pts, (size_t)n * 12, hipMemcpyDeviceToHost, ctx->stream));
-        if (kp_index) HIP_TRY(hipMemcpyAsync(kp_index, o_idx, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (xy) st.download(xy, o_xy, (int64_t)n * 8);
+        if (desc) st.download(desc, o_desc, (int64_t)n * 32);
+        if (pts3d) st.download(pts3d, o_pts, (int64_t)n * 12);
+        if (kp_index) st.download(kp_index, o_idx, (int64_t)n * 4);
     }
+    if (int rc = st.finish()) return rc;
     *n_out = n;
     if (n_kp) *n_kp = nk;
     return RELOC_OK;
@@ -345,18 +342,19 @@ RELOC_API int reloc_tick_accumulate_dev(reloc_ctx *ctx, const uint16_t *depth_mm
     }
     if (int rc = image_chain_depth(ctx, depth_mm_dev, &w, &h, &depth_mm_dev)) return rc;      // from here on the working frame
     AccumParams p;
-    p.fx = ctx->K4[0]; p.fy = ctx->K4[1]; p.cx = ctx->K4[2]; p.cy = ctx->K4[3];
+    const CameraModel &cam = ctx->cam;
+    p.fx = cam.K4[0]; p.fy = cam.K4[1]; p.cx = cam.K4[2]; p.cy = cam.K4[3];
     for (int k = 0; k < 7; ++k) p.base_pose[k] = base_pose[k];
-    for (int k = 0; k < 3; ++k) p.b2c_t[k] = ctx->b2c_t[k];
-    for (int k = 0; k < 9; ++k) p.b2c_R[k] = ctx->b2c_R[k];
+    for (int k = 0; k < 3; ++k) p.b2c_t[k] = cam.b2c_t[k];
+    for (int k = 0; k < 9; ++k) p.b2c_R[k] = cam.b2c_R[k];
     p.min_dist = ctx->prm.accum_min_dist_m;
     p.zmin = (float)ctx->prm.accum_depth_min_m; p.zmax = (float)ctx->prm.accum_depth_max_m;
     p.w = w; p.h = h; p.min_kpts = ctx->prm.accum_min_kpts; p.silence_ok = silence_ok;
     p.L = db.records; p.T = db.rows;
-    auto kern = ctx->has_dist ? k_accumulate<true> : k_accumulate<false>;
+    auto kern = cam.lens() ? k_accumulate<true> : k_accumulate<false>;
     hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, ctx->stream, ctx->f_xy, ctx->f_desc, ctx->f_count, ctx->max_feat,
                        depth_mm_dev, w, p, ctx->tick_res, db.xy_heading, db.desc, db.pts3d, db.kp2d, db.off, db.pose, ctx->accum_res,
-                       make_dist(ctx->dist));
+                       make_dist(cam.lens()));
     HIP_TRY(hipGetLastError());
     return RELOC_OK;
 }
@@ -437,23 +435,17 @@ RELOC_API int reloc_depth_points(reloc_ctx *ctx, const void *depth, int is_f32, 
     ARG_CHECK_CTX(ctx, depth && points && n_out && w > 0 && h > 0 && step > 0 && K4, "reloc_depth_points");
     if ((int64_t)w * h > (int64_t)ctx->max_w * ctx->max_h) { reloc_set_error("depth image exceeds ctx capacity"); return RELOC_E_CAPACITY; }
     const int64_t npt = (int64_t)((w + step - 1) / step) * ((h + step - 1) / step);
-    void *ddepth, *dout;
-    int rc;
     const int esz = is_f32 ? 4 : 2;
-    if ((rc = reloc_scratch(ctx, 5, (int64_t)w * h * esz, &ddepth))) return rc;
-    if ((rc = reloc_scratch(ctx, 6, npt * 12 + 16, &dout))) return rc;
-    int32_t *o_n = (int32_t *)((char *)dout + npt * 12);
-    HIP_TRY(hipMemcpyAsync(ddepth, depth, (size_t)w * h * esz, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_depth_points, dim3(1), dim3(1024), 0, ctx->stream, (const void *)ddepth, is_f32, w, h, w, step,
-                       (float)K4[2], (float)K4[3], (float)K4[0], (float)K4[1], zmin, zmax, (float *)dout, o_n);
-    HIP_TRY(hipGetLastError());
-    int32_t n = 0;
-    HIP_TRY(hipMemcpyAsync(&n, o_n, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (n > 0) {
-        HIP_TRY(hipMemcpyAsync(points, dout, (size_t)n * 12, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-    }
+    HostStaging st{ctx};
+    float *dout = st.slot<float>(6, npt * 3 + 4);
+    if (st.rc) return st.rc;
+    int32_t *o_n = (int32_t *)(dout + npt * 3);
+    const void *ddepth = st.upload_slot(5, (const uint8_t *)depth, (int64_t)w * h * esz);
+    st.launch(k_depth_points, dim3(1), dim3(1024), ddepth, is_f32, w, h, w, step, (float)K4[2], (float)K4[3], (float)K4[0],
+              (float)K4[1], zmin, zmax, dout, o_n);
+    const int32_t n = st.count(o_n);
+    if (n > 0) st.download(points, dout, (int64_t)n * 12);
+    if (int rc = st.finish()) return rc;
     *n_out = n;
     return RELOC_OK;
 }

@@ -582,8 +582,8 @@ static TickParams make_tick_params(reloc_ctx *ctx, const double base_pose[7], in
 {
     TickParams p;
     for (int k = 0; k < 7; ++k) p.base_pose[k] = base_pose[k];
-    for (int k = 0; k < 3; ++k) p.b2c_t[k] = ctx->b2c_t[k];
-    for (int k = 0; k < 9; ++k) p.b2c_R[k] = ctx->b2c_R[k];
+    for (int k = 0; k < 3; ++k) p.b2c_t[k] = ctx->cam.b2c_t[k];
+    for (int k = 0; k < 9; ++k) p.b2c_R[k] = ctx->cam.b2c_R[k];
     p.mode = mode;
     p.check_consistency = check_consistency;
     p.n_records = (int)ctx_db(ctx).records;
@@ -705,9 +705,9 @@ static int scan_counts(reloc_ctx *const *ctxs, int n, const double *base_poses, 
 RELOC_API int reloc_set_camera(reloc_ctx *ctx, const double K4[4], const double base_to_cam_t[3], const double base_to_cam_R[9])
 {
     ARG_CHECK_CTX(ctx, true, "ctx is NULL");
-    if (K4) for (int k = 0; k < 4; ++k) ctx->K4[k] = K4[k];
-    if (base_to_cam_t) for (int k = 0; k < 3; ++k) ctx->b2c_t[k] = base_to_cam_t[k];
-    if (base_to_cam_R) for (int k = 0; k < 9; ++k) ctx->b2c_R[k] = base_to_cam_R[k];
+    if (K4) for (int k = 0; k < 4; ++k) ctx->cam.K4[k] = K4[k];
+    if (base_to_cam_t) for (int k = 0; k < 3; ++k) ctx->cam.b2c_t[k] = base_to_cam_t[k];
+    if (base_to_cam_R) for (int k = 0; k < 9; ++k) ctx->cam.b2c_R[k] = base_to_cam_R[k];
     return db_reindex(ctx);
 }
 
@@ -723,17 +723,17 @@ RELOC_API int reloc_set_distortion(reloc_ctx *ctx, const double *coeffs, int n)
     bool any = false;
     for (int k = 0; k < 5; ++k) {
         const double c = k < n ? coeffs[k] : 0.0;
-        ctx->dist[k] = c == 0.0 ? 0.0 : c;      // -0 -> +0: contexts with equal models compare equal byte for byte
+        ctx->cam.dist[k] = c == 0.0 ? 0.0 : c;      // -0 -> +0: contexts with equal models compare equal byte for byte
         any |= c != 0.0;
     }
-    ctx->has_dist = any;
+    ctx->cam.has_dist = any;
     return RELOC_OK;
 }
 
 RELOC_API int reloc_get_distortion(reloc_ctx *ctx, double coeffs[5])
 {
     ARG_CHECK_CTX(ctx, coeffs, "reloc_get_distortion");
-    for (int k = 0; k < 5; ++k) coeffs[k] = ctx->dist[k];
+    for (int k = 0; k < 5; ++k) coeffs[k] = ctx->cam.dist[k];
     return RELOC_OK;
 }
 
@@ -761,9 +761,7 @@ static int ctx_batch_check(reloc_ctx *const *ctxs, int n, const char *who)
         if (!c) { reloc_set_error("bad argument: %s: NULL context", who); return RELOC_E_ARG; }
         if (!db_ready(c)) { reloc_set_error("no database uploaded"); return RELOC_E_STATE; }
         if (c->stream != c0->stream || c->device != c0->device || ctx_db(c).desc != ctx_db(c0).desc || ctx_db(c).records != ctx_db(c0).records ||
-            c->max_feat != c0->max_feat || memcmp(&c->prm, &c0->prm, sizeof(reloc_params)) != 0 ||
-            memcmp(c->K4, c0->K4, sizeof(c->K4)) != 0 || memcmp(c->b2c_t, c0->b2c_t, sizeof(c->b2c_t)) != 0 ||
-            memcmp(c->b2c_R, c0->b2c_R, sizeof(c->b2c_R)) != 0 || memcmp(c->dist, c0->dist, sizeof(c->dist)) != 0) {
+            c->max_feat != c0->max_feat || memcmp(&c->prm, &c0->prm, sizeof(reloc_params)) != 0 || !c->cam.same(c0->cam)) {
             reloc_set_error("%s: the contexts must share one stream (reloc_set_stream), one device and one database "
                             "(reloc_db_share) and have equal feature capacity, matcher parameters (reloc_set_params), camera "
                             "(reloc_set_camera) and lens distortion (reloc_set_distortion)", who);

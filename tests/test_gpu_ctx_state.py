@@ -1,0 +1,222 @@
+"""The host-side state of a context, pinned from outside: which unequal settings make a batched tick refuse its contexts (and
+with which code and message), that an image stage switched on, off, to another setting and back leaves no trace, that a
+context with every stage enabled is destroyed cleanly, and that the host-pointer entry points survive their scratch slots
+growing and being reused."""
+import numpy as np
+import pytest
+
+from nclt_slam_project_amd import RelocError, synth
+from nclt_slam_project_amd.engine import Engine
+
+pytestmark = pytest.mark.gpu
+CAP_W, CAP_H, MAX_FEAT = 256, 192, 512          # capacity of every engine
+W, H = 128, 96                                  # the frames
+WORK = (120, 90)                                # the working frame of the downscale stage (at least 64 x 64)
+K4 = (110.0, 110.0, 64.0, 48.0)
+B2C_T = (0.35, 0.0, 0.18)
+B2C_R = (0.0, -1.0, 0.0, 0.0, 0.0, -1.0, 1.0, 0.0, 0.0)
+DIST = (-0.1, 0.02, 0.001, -0.0005, 0.003)
+BG, GB, RG = 46, 47, 48                         # COLOR_Bayer??2BGR
+
+
+def _maps(w, h, shift):
+    v, u = np.mgrid[0:h, 0:w]
+    return (u + 0.02 * (v - h / 2) + shift).astype(np.float32), (v * 0.98 + 0.7).astype(np.float32)
+
+
+@pytest.fixture(scope="module")
+def frame():
+    """2 x 2 blocks of random colour: corners everywhere, so that even these small frames give some 150 keypoints (the
+    31-pixel border of ORB leaves 66 x 34 pixels of level 0)"""
+    g = np.random.default_rng(11).integers(0, 256, (H // 2, W // 2, 3)).astype(np.uint8)
+    return np.ascontiguousarray(np.kron(g, np.ones((2, 2, 1), np.uint8)))
+
+
+def _database(e, frame):
+    """8 records, two of them planted with the frame's own descriptors"""
+    feats = e.orb_detect_compute(e.gray(frame), 500)
+    assert feats["n"] > 64
+    return synth.descriptor_db(np.random.default_rng(12), 8, "fixed64", feats["desc"], planted_records=(2, 5))
+
+
+# ---- 1. the batch refusal table ---------------------------------------------------------------------------------------
+GENERAL = "equal feature capacity, matcher parameters"      # ctx_batch_check's one message names everything it compares
+# (item, fragment of the message, the setting both contexts start from, the setting of the one that differs)
+REFUSALS = [
+    ("K4", GENERAL, lambda e: e.set_camera(K4=K4), lambda e: e.set_camera(K4=(110.0, 110.5, 64.0, 48.0))),
+    ("base_to_cam_t", GENERAL, lambda e: e.set_camera(base_to_cam_t=B2C_T), lambda e: e.set_camera(base_to_cam_t=(0.35, 0.0, 0.19))),
+    ("base_to_cam_R", GENERAL, lambda e: e.set_camera(base_to_cam_R=B2C_R),
+     lambda e: e.set_camera(base_to_cam_R=(0.0, -1.0, 0.0, 0.0, 0.0, 1.0, -1.0, 0.0, 0.0))),
+    ("distortion k3", "lens distortion", lambda e: e.set_distortion(DIST), lambda e: e.set_distortion(DIST[:4] + (0.004,))),
+    ("params.min_inliers", GENERAL, lambda e: e.set_params(min_inliers=10), lambda e: e.set_params(min_inliers=11)),
+    ("CLAHE on / off", "CLAHE", lambda e: e.set_clahe(None), lambda e: e.set_clahe(2.0, (4, 4))),
+    ("CLAHE clip", "CLAHE", lambda e: e.set_clahe(2.0, (4, 4)), lambda e: e.set_clahe(2.5, (4, 4))),
+    ("CLAHE tiles", "CLAHE", lambda e: e.set_clahe(2.0, (4, 4)), lambda e: e.set_clahe(2.0, (4, 2))),
+    ("rectify on / off", "rectification map", lambda e: e.set_rectify(None), lambda e: e.set_rectify(_maps(W, H, 1.3))),
+    ("rectify map size", "rectification map", lambda e: e.set_rectify(_maps(W, H, 1.3)), lambda e: e.set_rectify(_maps(W - 8, H, 1.3))),
+    ("resize on / off", "downscale stage", lambda e: e.set_resize(None), lambda e: e.set_resize((W, H), WORK)),
+    ("resize destination", "downscale stage", lambda e: e.set_resize((W, H), WORK), lambda e: e.set_resize((W, H), (WORK[0], WORK[1] - 6))),
+    ("Bayer on / off", "Bayer stage", lambda e: e.set_bayer(None), lambda e: e.set_bayer(BG)),
+    ("Bayer code", "Bayer stage", lambda e: e.set_bayer(BG), lambda e: e.set_bayer(GB)),
+]
+
+
+def _all_off(e):
+    e.set_bayer(None); e.set_resize(None); e.set_rectify(None); e.set_clahe(None); e.set_distortion(())
+
+
+@pytest.fixture(scope="module")
+def batch(frame):
+    """an owner, an adopter and an adopter of smaller feature capacity on one stream and one database; the frame on the device"""
+    owner, adopter, small = Engine(0, CAP_W, CAP_H, MAX_FEAT), Engine(0, CAP_W, CAP_H, MAX_FEAT), Engine(0, CAP_W, CAP_H, MAX_FEAT // 2)
+    owner.db_upload(*_database(owner, frame))
+    for e in (adopter, small):
+        e.db_share(owner)
+        e.set_stream(owner.stream_ptr)
+    dev = owner.to_device(frame)            # W x H x 3 bytes: also read as a W x H mosaic while the Bayer stage is on
+    yield owner, adopter, small, dev
+    owner.sync()
+    owner.dev_free(dev)
+    for e in (small, adopter, owner):
+        e.close()
+
+
+def _tick_pair(pair, dev):
+    poses = [synth.base_pose(10.0, 0.3, 2.0), synth.base_pose(11.0, 0.3, 2.0)]
+    Engine.tick_batch_dev(pair, [dev, dev], W, H, poses, global_reloc=True, seeds=[3, 4])
+
+
+@pytest.mark.parametrize("who", ["adopter", "owner"])
+@pytest.mark.parametrize("item,fragment,equal,differ", REFUSALS, ids=[r[0] for r in REFUSALS])
+def test_batch_refuses_one_unequal_setting(batch, who, item, fragment, equal, differ):
+    owner, adopter, _, dev = batch
+    pair = [owner, adopter]
+    odd = adopter if who == "adopter" else owner
+    try:
+        for e in pair:
+            equal(e)
+        _tick_pair(pair, dev)
+        owner.sync()
+        differ(odd)
+        with pytest.raises(RelocError, match=r"(?s)code -5.*" + fragment):
+            _tick_pair(pair, dev)
+        equal(odd)
+        _tick_pair(pair, dev)
+        owner.sync()
+        assert owner.tick_result()["n_features"] > 20 and adopter.tick_result()["n_features"] > 20
+    finally:
+        for e in pair:
+            _all_off(e)
+
+
+def test_batch_refuses_unequal_feature_capacity(batch):
+    owner, adopter, small, dev = batch
+    assert small.max_feat != owner.max_feat
+    with pytest.raises(RelocError, match=r"(?s)code -5.*" + GENERAL):
+        _tick_pair([owner, small], dev)
+    with pytest.raises(RelocError, match=r"(?s)code -5.*" + GENERAL):
+        _tick_pair([small, owner], dev)
+    _tick_pair([owner, adopter], dev)           # equal capacity: accepted
+    owner.sync()
+
+
+# ---- 2. stage lifecycle ------------------------------------------------------------------------------------------------
+# (stage, its setter, a first setting, another setting within capacity, off)
+STAGES = [
+    ("bayer", Engine.set_bayer, (BG,), (RG,), (None,)),
+    ("resize", Engine.set_resize, ((W, H), WORK), ((W, H), (112, 84)), (None, None)),
+    ("rectify", Engine.set_rectify, (_maps(W, H, 1.3),), (_maps(W, H, -2.1),), (None,)),
+    ("clahe", Engine.set_clahe, (2.0, (4, 4)), (3.0, (8, 2)), (None,)),
+]
+
+
+def _features(e, dev):
+    n = e.orb_frame_dev(dev, W, H)
+    f = e.orb_features()
+    assert f["n"] == n > 20
+    return f
+
+
+def _assert_same(a, b):
+    assert a["n"] == b["n"]
+    np.testing.assert_array_equal(a["xy"], b["xy"])
+    np.testing.assert_array_equal(a["desc"], b["desc"])
+
+
+def _enable_all(e):
+    e.set_bayer(BG)
+    e.set_resize((W, H), WORK)
+    e.set_rectify(_maps(*WORK, 1.3))
+    e.set_clahe(2.0, (4, 4))
+
+
+def test_stage_lifecycle(frame):
+    raw = np.ascontiguousarray(frame[..., 1])                   # any mosaic will do
+    e, never = Engine(0, CAP_W, CAP_H, MAX_FEAT), Engine(0, CAP_W, CAP_H, MAX_FEAT)
+    devs = []
+    try:
+        devs = [e.to_device(frame), e.to_device(raw), never.to_device(frame)]
+        plain = _features(never, devs[2])
+        for name, setter, first, other, off in STAGES:
+            src = devs[1] if name == "bayer" else devs[0]
+            setter(e, *first)
+            a = _features(e, src)
+            assert a["n"] != plain["n"] or not np.array_equal(a["desc"], plain["desc"]), name       # the stage did something
+            setter(e, *off)
+            _assert_same(_features(e, devs[0]), plain)
+            setter(e, *other)
+            _features(e, src)
+            setter(e, *first)
+            _assert_same(_features(e, src), a)
+            setter(e, *off)
+        # all four at once: one tick and one recording
+        e.db_upload(*_database(never, frame))
+        _enable_all(e)
+        e.tick(raw, synth.base_pose(10.0, 0.3, 2.0), global_reloc=True, seed=1)
+        assert e.tick_result()["n_features"] > 20
+        yy, xx = np.mgrid[0:H, 0:W]
+        rec = e.record_frame(raw, (2000 + 2 * xx + yy).astype(np.uint16))
+        assert 0 <= rec["n"] <= rec["n_kp"] and rec["n_kp"] > 20
+        e.sync()
+    finally:
+        for p, owner in zip(devs, (e, e, never)):
+            owner.dev_free(p)
+        e.close()
+        never.close()
+
+
+def test_three_fully_enabled_engines_in_sequence(frame):
+    raw = np.ascontiguousarray(frame[..., 1])
+    counts = []
+    for _ in range(3):                                          # the destroy path with every block present, three times
+        e = Engine(0, CAP_W, CAP_H, MAX_FEAT)
+        dev = e.to_device(raw)
+        _enable_all(e)
+        counts.append(e.orb_frame_dev(dev, W, H))
+        e.hamming_matrix(np.zeros((4, 32), np.uint8), np.ones((4, 32), np.uint8))      # a scratch slot to free as well
+        e.dev_free(dev)
+        e.close()
+    assert counts[0] > 20 and counts == [counts[0]] * 3
+
+
+# ---- 3. scratch regrowth through the staging helper --------------------------------------------------------------------
+def _hamming(a, b):
+    return np.unpackbits(a[:, None, :] ^ b[None, :, :], axis=2).sum(axis=2)
+
+
+def test_scratch_slots_regrow_and_are_reused():
+    rng = np.random.default_rng(5)
+    e = Engine(0, CAP_W, CAP_H, MAX_FEAT)
+    try:
+        for na, nb in ((8, 8), (64, 72), (8, 8)):               # the second call outgrows the first one's slots
+            a, b = synth.random_descriptors(rng, na), synth.random_descriptors(rng, nb)
+            np.testing.assert_array_equal(e.hamming_matrix(a, b), _hamming(a, b).astype(np.uint16))
+        for nq, nt in ((5, 7), (300, 520), (5, 7)):
+            q, t = synth.random_descriptors(rng, nq), synth.random_descriptors(rng, nt)
+            d = _hamming(q, t)
+            order = np.argsort(d, axis=1, kind="stable")[:, :2]         # the lower index wins a tie
+            idx, dist = e.match_knn2(q, t)
+            np.testing.assert_array_equal(idx, order)
+            np.testing.assert_array_equal(dist, np.take_along_axis(d, order, axis=1))
+    finally:
+        e.close()
