@@ -136,6 +136,27 @@ const int32_t *reloc_frame_count_dev(reloc_ctx *ctx);     /* 1 x i32: number of 
  * what: 0 = pyramid level, 1 = blurred level, 2 = NMS-kept FAST score map. */
 int reloc_frame_debug_plane(reloc_ctx *ctx, int what, int level, uint8_t *out, int32_t *w, int32_t *h);
 
+/* ---- ORB detection mask (include/reloc_spec.h, "ORB MASK") ---------------------------------------- */
+/* cv2.ORB.detectAndCompute(image, mask): mask is a host plane of h rows of w bytes, stride bytes apart; a corner is kept
+ * where its mask level is non-zero, before the per-level quota is spent.  reloc_set_orb_mask keeps a persistent mask on the
+ * context; mask == NULL or w == h == 0 turns it off (the default of a new context; the launch sequence is then that of a
+ * context that never had one).  The first use allocates the context's two mask pyramids.  The persistent mask has the size
+ * of the working frame (behind reloc_set_resize) and is applied by every entry point that goes through the image chain:
+ * reloc_orb_frame_dev, reloc_record_frame, reloc_tick, reloc_tick_dev, reloc_tick_batch_dev, reloc_tick_scan_dev,
+ * reloc_shard_scan_batch_dev (the accumulation uses the tick's features); a working frame of another size fails with
+ * RELOC_E_ARG before anything is launched.  Never applied to the caller's gray plane of reloc_orb_detect_compute.  The
+ * contexts of a batched call may hold different masks but agree on masked / unmasked and on the mask size, else
+ * RELOC_E_STATE.  reloc_get_orb_mask returns (0, 0) when off. */
+int reloc_set_orb_mask(reloc_ctx *ctx, const uint8_t *mask, int w, int h, int stride);
+int reloc_get_orb_mask(reloc_ctx *ctx, int32_t *w, int32_t *h);
+/* reloc_orb_detect_compute under a mask of the gray plane's size given with the call; the persistent mask and its pyramid
+ * stay as they were. */
+int reloc_orb_detect_compute_masked(reloc_ctx *ctx, const uint8_t *gray, int w, int h, int stride, const uint8_t *mask,
+                                    int mask_stride, int nfeatures, float *xy, float *size, float *angle,
+                                    float *response, int32_t *octave, uint8_t *desc, int32_t *n_out);
+/* Parity tap: level (in [0, 8)) of the mask pyramid that the last masked frame used, dense rows of *w bytes. */
+int reloc_orb_mask_level(reloc_ctx *ctx, int level, uint8_t *out, int32_t *w, int32_t *h);
+
 /* Teach-side record builder (R:240-288): ORB on the frame, then per keypoint the border / ground masks,
  * depth lookup (uint16 millimetres), 3x3 non-zero depth std, range and variance gates and pin-hole
  * back-projection.  Outputs (up to max_feat rows, keypoint order kept): xy = keypoints_2d, desc =

@@ -229,4 +229,19 @@
 #define RELOC_BAYER_RG2BGR       48
 #define RELOC_BAYER_GR2BGR       49
 
+/* ORB MASK: cv2.ORB.detectAndCompute(image, mask) with an 8-bit single-channel mask of the image's size, restated from OpenCV
+ * 4.x modules/features2d/src/orb.cpp (the mask pyramid of detectAndCompute, computeKeyPoints) and fast.cpp /
+ * KeyPointsFilter::runByPixelsMask (not pinned against a cv2 build).
+ *   pyramid    mask level 0 is the mask as given.  For l >= 1, mask level l = threshold(resize(mask level l - 1, size of
+ *              level l, INTER_LINEAR_EXACT), RELOC_ORB_MASK_THRESH, 0, THRESH_TOZERO): the resize tables and arithmetic of
+ *              the image pyramid above, then every value <= 254 becomes 0 -- a pixel survives only where the interpolation
+ *              gives 255.  Level l is resized from the THRESHOLDED level l - 1 and level 1 from the raw mask, so a mask of
+ *              values 0 / 1 keeps level 0 only (OpenCV's behaviour, kept).
+ *   per level  FAST and the 3x3 non-maximum suppression run unmasked: the mask does not change which pixel is a local
+ *              maximum.  A kept corner at the integer level pixel (x, y) is dropped iff mask level l at (y, x) is 0.  Then the
+ *              edge margin, the score histogram, retainBest(2 x quota) with ties, Harris, best-quota, orientation and the
+ *              descriptor exactly as without a mask (a dropped corner frees its place in the quota, which a filter behind
+ *              ORB cannot do).  A level whose mask is non-zero everywhere is that of the unmasked detector. */
+#define RELOC_ORB_MASK_THRESH    254  /* THRESH_TOZERO: values above it are kept */
+
 #endif /* RELOC_SPEC_H */

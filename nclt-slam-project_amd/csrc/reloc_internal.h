@@ -338,6 +338,18 @@ struct ClaheStage {
     bool same(const ClaheStage &o) const { return tx == o.tx && ty == o.ty && clip == o.clip; }
 };
 
+// ORB's detection mask on the working frame of the image chain (reloc_set_orb_mask); 0 x 0 = off, the default
+struct OrbMaskStage {
+    int w = 0, h = 0;                    // the persistent mask = working-frame size
+    uint8_t *pyr = nullptr;              // its mask pyramid, geometry of ctx->pyr; level 0 is the mask as given
+    uint8_t *call = nullptr;             // the same for the mask of one reloc_orb_detect_compute_masked call
+    bool built = false;                  // levels 1.. of pyr belong to the mask of level 0 (k_mask_level ran since it was set)
+    const uint8_t *last = nullptr;       // the pyramid the last masked frame used, of last_w x last_h (reloc_orb_mask_level)
+    int last_w = 0, last_h = 0;
+    bool on() const { return w > 0; }
+    bool same(const OrbMaskStage &o) const { return w == o.w && h == o.h; }      // the masks themselves may differ per context
+};
+
 struct reloc_ctx {
     int device = 0;
     int max_w = 0, max_h = 0, max_feat = 0;
@@ -383,6 +395,7 @@ struct reloc_ctx {
     void *orb_const = nullptr;     // device copy of the OrbTable (reloc_orb.hip)
     char orb_tab_host[1024];       // host copy of the same table
     int32_t *dbg_cut = nullptr;    // NLEV stage-1 cut scores of the last frame
+    OrbMaskStage mask;             // detection mask between NMS and the stage-1 cut; both pyramids are one block, taken on first use
 
     CameraModel cam;
     // the image chain's stages in its order (reloc_image.hip); a stage's buffers are one block, taken on its first enable
@@ -520,9 +533,10 @@ int orb_prepare(reloc_ctx *ctx, int w, int h, int nfeatures);
 // ORB of frame f = srcs[f] into ctxs[f]'s feature buffers; channels == 3 -> the frames of the image chain: interleaved
 // 3-channel frames (gray fused), or raw mosaics of image_chain_frame_bpp = 1 byte per pixel with the Bayer stage on; the
 // chain first when the contexts have stages on; with the downscale stage on, w x h is the source size and the features are
-// those of the working frame.  channels == 1 -> gray planes, never through the chain (reloc_orb.hip)
+// those of the working frame.  channels == 1 -> gray planes, never through the chain.  The chain's frames are detected
+// under the contexts' persistent mask; call_mask: under the mask whose level 0 the caller left in mask.call (reloc_orb.hip)
 int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, int h, int stride, int channels, int order,
-            int nfeatures, bool latency);
+            int nfeatures, bool latency, bool call_mask = false);
 // The image chain of a context's stages (reloc_image.hip states their order).  The checks stand before orb_prepare (the Bayer
 // and the downscale stage; w x h becomes the working frame) and behind that of context f (rectification, CLAHE); _gray runs
 // the stages on the frames and leaves *srcs / *stride / *channels describing the last plane written; _depth takes a

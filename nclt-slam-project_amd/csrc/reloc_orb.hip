@@ -32,6 +32,9 @@
 //                                        greater", order raster by rank counting
 //   k_describe                           one wave per keypoint: moments by wave reduction, angle,
 //                                        256 steered tests -> 4 ballots = 32 descriptor bytes
+// A detection mask (include/reloc_spec.h "ORB MASK"; reloc_set_orb_mask, reloc_orb_detect_compute_masked) adds no launch per
+// frame: k_fast_blur<true> reads the frame's mask pyramid (geometry of ctx->pyr) where it writes the NMS map; k_mask_level
+// builds that pyramid once per mask, seven dependent launches in front of the first frame that uses it.
 // The per-frame HBM traffic is about 4 MB at 640x480; the stage is launch/latency-bound, not
 // bandwidth-bound.
 #include <math.h>
@@ -93,6 +96,7 @@ struct OrbFrame {
     uint8_t *pyr, *nms, *blur; int32_t *hist, *cand_cnt; u32 *cand_key; float *cand_resp; int32_t *dbg_cut;
     int32_t *kp_cnt; u32 *kp_key; float *kp_resp; float *f_xy, *f_size, *f_angle, *f_resp; int32_t *f_oct; uint8_t *f_desc;
     int32_t *f_count;
+    const uint8_t *mask;    // mask pyramid of the frame (geometry of pyr), read by the MASKED kernels only
 };
 struct OrbBatch { OrbFrame f[RELOC_BATCH_MAX]; };
 
@@ -484,8 +488,12 @@ struct FastQuad {
 constexpr int FT = 32;
 constexpr int FT_P = FT / 4 + 3;       // dwords per staged row: columns x0 - 4 .. x0 + FT + 3, one of padding
 static_assert(FT == 32, "fast_nms_tile maps 256 lanes to 32 rows x 8 dwords");
+// MASKED: a kept corner whose byte of the mask pyramid (`mask`, geometry of pyr) is 0 enters neither the NMS map nor the
+// histogram (include/reloc_spec.h "ORB MASK"); the unmasked instantiation never reads `mask`.
+template <bool MASKED>
 __device__ __forceinline__ void fast_nms_tile(const OrbTable *__restrict__ tab, const uint8_t *__restrict__ pyr,
-                                              uint8_t *__restrict__ nms, int32_t *__restrict__ hist, int bid)
+                                              uint8_t *__restrict__ nms, int32_t *__restrict__ hist, int bid,
+                                              const uint8_t *__restrict__ mask)
 {
     __shared__ u32 s_img4[(FT + 8) * FT_P];
     __shared__ u32 s_sc4[(FT + 2) * (FT + 4) / 4];
@@ -599,11 +607,14 @@ __device__ __forceinline__ void fast_nms_tile(const OrbTable *__restrict__ tab, 
     {
         const int ry = tid / 8, rx4 = (tid % 8) * 4;
         u32 word = 0;
+        u32 keep = 0;       // MASKED: the mask bytes of the lane's four pixels, one aligned dword
+        if constexpr (MASKED)
+            if (y0 + ry < L.h) keep = *reinterpret_cast<const u32 *>(mask + L.off + (size_t)(y0 + ry) * L.stride + x0 + rx4);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int gx = x0 + rx4 + k, gy = y0 + ry;
             const uint8_t *s = s_sc + (ry + 1) * SS + (rx4 + k + 1);
-            const int c = s[0];
+            const int c = (!MASKED || ((keep >> (8 * k)) & 0xFF)) ? s[0] : 0;
             if (c && gx >= e && gx < L.w - e && gy >= e && gy < L.h - e && c > s[-1] && c > s[1] && c > s[-SS - 1] &&
                 c > s[-SS] && c > s[-SS + 1] && c > s[SS - 1] && c > s[SS] && c > s[SS + 1]) {
                 word |= (u32)c << (8 * k);
@@ -622,20 +633,52 @@ __device__ __forceinline__ void fast_nms_tile(const OrbTable *__restrict__ tab, 
 // feeds Harris and the blur feeds the descriptors, so they need not run one after the other.  (A smaller grid whose workgroups
 // walk the tiles paid beside 112-register scans and pays nothing beside 104-register ones: profiles/README.md "Dropped
 // experiments" #8.)
+// MASKED = true: the same with the detection mask applied behind NMS; `mask` is the last argument and unread otherwise.
+template <bool MASKED>
 __global__ __launch_bounds__(256) void k_fast_blur(const OrbTable *__restrict__ tab, const uint8_t *__restrict__ pyr,
                                                    uint8_t *__restrict__ nms, int32_t *__restrict__ hist,
-                                                   uint8_t *__restrict__ blur, int n_fast)
+                                                   uint8_t *__restrict__ blur, int n_fast, const uint8_t *__restrict__ mask)
 {
     RELOC_SMALL_KERNEL_PRIO();
-    if ((int)blockIdx.x < n_fast) fast_nms_tile(tab, pyr, nms, hist, (int)blockIdx.x);
+    if ((int)blockIdx.x < n_fast) fast_nms_tile<MASKED>(tab, pyr, nms, hist, (int)blockIdx.x, mask);
     else blur7_tile(tab, pyr, blur, (int)blockIdx.x - n_fast);
 }
+template <bool MASKED>
 __global__ __launch_bounds__(256) void k_fast_blur_batch(OrbBatch b, int n_fast)
 {
     RELOC_SMALL_KERNEL_PRIO();
     const OrbFrame &F = b.f[blockIdx.y];
-    if ((int)blockIdx.x < n_fast) fast_nms_tile(F.tab, F.pyr, F.nms, F.hist, (int)blockIdx.x);
+    if ((int)blockIdx.x < n_fast) fast_nms_tile<MASKED>(F.tab, F.pyr, F.nms, F.hist, (int)blockIdx.x, F.mask);
     else blur7_tile(F.tab, F.pyr, F.blur, (int)blockIdx.x - n_fast);
+}
+
+// ---- mask pyramid -------------------------------------------------------------------------------
+// Level l of a mask pyramid from its level l - 1 (include/reloc_spec.h "ORB MASK"): the image pyramid's resize (same table
+// slices, same arithmetic), then THRESH_TOZERO.  A lane writes the four pixels of one dword, the row padding as 0; one launch
+// per level, each reading what the one before wrote.  Runs when a mask is set, not per frame.
+__global__ __launch_bounds__(256) void k_mask_level(const OrbTable *__restrict__ tab, const int32_t *__restrict__ rz,
+                                                    uint8_t *__restrict__ mp, int l)
+{
+    const OrbLevel S = tab->lev[l - 1], D = tab->lev[l];
+    const int x4 = 4 * (int)(blockIdx.x * 256 + threadIdx.x), y = (int)blockIdx.y;
+    if (x4 >= D.stride || y >= D.h) return;
+    const int32_t *xo = rz + tab->rz_off[l][0], *xc = rz + tab->rz_off[l][1];
+    const int sy0 = rz[tab->rz_off[l][2] + y], sy1 = sy0 + 1 < S.h ? sy0 + 1 : S.h - 1;
+    const u32 b = (u32)rz[tab->rz_off[l][3] + y], one = 1u << RELOC_RESIZE_COEF_BITS;
+    const uint8_t *r0 = mp + S.off + (size_t)sy0 * S.stride, *r1 = mp + S.off + (size_t)sy1 * S.stride;
+    u32 out = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (x4 + k < D.w) {
+            const int k0 = xo[x4 + k], k1 = k0 + 1 < S.w ? k0 + 1 : S.w - 1;
+            const u32 a = (u32)xc[x4 + k];
+            const u32 h0 = (u32)r0[k0] * (one - a) + (u32)r0[k1] * a;
+            const u32 h1 = (u32)r1[k0] * (one - a) + (u32)r1[k1] * a;
+            const u32 v = (h0 * (one - b) + h1 * b + (1u << 15)) >> 16;
+            if (v > RELOC_ORB_MASK_THRESH) out |= v << (8 * k);
+        }
+    }
+    *reinterpret_cast<u32 *>(mp + D.off + (size_t)y * D.stride + x4) = out;
 }
 
 // cut score from the level's histogram (KeyPointsFilter::retainBest(2*quota) with ties kept, raised
@@ -1164,7 +1207,29 @@ static OrbFrame orb_frame(const reloc_ctx *c, const uint8_t *src)
     F.cand_resp = c->cand_resp; F.dbg_cut = c->dbg_cut; F.kp_cnt = c->kp_cnt; F.kp_key = c->kp_key; F.kp_resp = c->kp_resp;
     F.f_xy = c->f_xy; F.f_size = c->f_size; F.f_angle = c->f_angle; F.f_resp = c->f_resp; F.f_oct = c->f_oct; F.f_desc = c->f_desc;
     F.f_count = c->f_count;
+    F.mask = nullptr;
     return F;
+}
+
+// first use of a mask: both mask pyramids as one block
+static int mask_alloc(reloc_ctx *ctx)
+{
+    OrbMaskStage &m = ctx->mask;
+    if (m.pyr) return RELOC_OK;
+    if (int rc = ctx_dev_alloc(ctx, &m.pyr, 2 * ctx->pyr_bytes)) return rc;
+    m.call = m.pyr + ctx->pyr_bytes;
+    return RELOC_OK;
+}
+
+// levels 1.. of the mask pyramid mp of a prepared context from its level 0, on the context's stream
+static void mask_pyramid_launch(reloc_ctx *c, uint8_t *mp)
+{
+    for (int l = 1; l < NLEV; ++l) {
+        const OrbLevel &L = c->lev[l];
+        if (L.w < 1 || L.h < 1) break;
+        hipLaunchKernelGGL(k_mask_level, dim3((L.stride / 4 + 255) / 256, L.h), dim3(256), 0, c->stream, (const OrbTable *)c->orb_const,
+                           c->rz_tab, mp, l);
+    }
 }
 
 // Five launches behind the image chain (reloc_image.hip): the frames are of equal geometry.  The chain serves the frames
@@ -1173,7 +1238,7 @@ static OrbFrame orb_frame(const reloc_ctx *c, const uint8_t *src)
 // plane the chain wrote, or the frame itself.  It runs 512-thread workgroups for latency, 256 where it shares the chip with
 // whole-database scans.
 int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, int h, int stride, int channels, int order,
-            int nfeatures, bool latency)
+            int nfeatures, bool latency, bool call_mask)
 {
     if (n < 1 || n > RELOC_BATCH_MAX) { reloc_set_error("orb: 1..%d frames", RELOC_BATCH_MAX); return RELOC_E_ARG; }
     reloc_ctx *c0 = ctxs[0];
@@ -1188,7 +1253,24 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
             return RELOC_E_STATE;
         }
         if (int rc = image_chain_check_prepared(ctxs, f, n, channels, w, h)) return rc;
+        if (channels == 3 && !c->mask.same(c0->mask)) {
+            reloc_set_error("orb batch: contexts with and without a detection mask, or with masks of unequal size (reloc_set_orb_mask)");
+            return RELOC_E_STATE;
+        }
     }
+    // the persistent mask serves the frames of the chain and has the size of their working frame; nothing is launched otherwise
+    const bool masked = call_mask || (channels == 3 && c0->mask.on());
+    if (masked && !call_mask && (w != c0->mask.w || h != c0->mask.h)) {
+        reloc_set_error("working frame %dx%d differs from the detection mask %dx%d (reloc_set_orb_mask)", w, h, c0->mask.w, c0->mask.h);
+        return RELOC_E_ARG;
+    }
+    if (masked)
+        for (int f = 0; f < n; ++f) {
+            OrbMaskStage &m = ctxs[f]->mask;
+            if (call_mask) mask_pyramid_launch(ctxs[f], m.call);
+            else if (!m.built) { mask_pyramid_launch(ctxs[f], m.pyr); m.built = true; }
+            m.last = call_mask ? m.call : m.pyr; m.last_w = w; m.last_h = h;
+        }
     const OrbTable *tab_h = (const OrbTable *)c0->orb_tab_host;
     const int flags = gray_flags(c0, order);
     hipStream_t st = c0->stream;
@@ -1201,7 +1283,7 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
     bool aligned = w % 4 == 0 && stride % 4 == 0;
     for (int f = 0; f < n; ++f) aligned = aligned && ((uintptr_t)srcs[f]) % 4 == 0;
     OrbBatch b;
-    frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int g) { b.f[f] = orb_frame(c, srcs[g]); });
+    frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int g) { b.f[f] = orb_frame(c, srcs[g]); b.f[f].mask = masked ? c->mask.last : nullptr; });
     PyrLds lds;
     for (int l = 0; l < NLEV; ++l) lds.lev[l] = c0->pyr_lds[l];
     lds.tabs = c0->pyr_lds[NLEV];
@@ -1212,7 +1294,8 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
         auto kern256 = channels == 3 ? (aligned ? k_pyramid<3, true, 256> : k_pyramid<3, false, 256>) : (aligned ? k_pyramid<1, true, 256> : k_pyramid<1, false, 256>);
         hipLaunchKernelGGL(latency ? kern512 : kern256, dim3(c0->pyr_ntiles), dim3(latency ? 512 : 256), c0->pyr_lds_bytes, st, F.tab,
                            F.tiles, F.rz, F.src, w, h, stride, flags, F.pyr, lds, F.hist, F.cand_cnt);
-        hipLaunchKernelGGL(k_fast_blur, dim3(n_fast + n_blur), dim3(256), 0, st, F.tab, F.pyr, F.nms, F.hist, F.blur, n_fast);
+        hipLaunchKernelGGL(masked ? k_fast_blur<true> : k_fast_blur<false>, dim3(n_fast + n_blur), dim3(256), 0, st, F.tab, F.pyr, F.nms,
+                           F.hist, F.blur, n_fast, F.mask);
         hipLaunchKernelGGL(k_harris, dim3(tab_h->flat_base[NLEV]), dim3(256), 0, st, F.tab, F.pyr, F.nms, F.hist, F.cand_cnt, F.cand_key,
                            F.cand_resp, F.dbg_cut);
         hipLaunchKernelGGL(k_select, dim3(NLEV), dim3(1024), 0, st, F.tab, F.cand_cnt, F.cand_key, F.cand_resp, F.kp_cnt, F.kp_key,
@@ -1223,7 +1306,7 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
         auto kern = channels == 3 ? (aligned ? k_pyramid_batch<3, true, 256> : k_pyramid_batch<3, false, 256>)
                                   : (aligned ? k_pyramid_batch<1, true, 256> : k_pyramid_batch<1, false, 256>);
         hipLaunchKernelGGL(kern, dim3(c0->pyr_ntiles, n), dim3(256), c0->pyr_lds_bytes, st, b, w, h, stride, flags, lds);
-        hipLaunchKernelGGL(k_fast_blur_batch, dim3(n_fast + n_blur, n), dim3(256), 0, st, b, n_fast);
+        hipLaunchKernelGGL(masked ? k_fast_blur_batch<true> : k_fast_blur_batch<false>, dim3(n_fast + n_blur, n), dim3(256), 0, st, b, n_fast);
         hipLaunchKernelGGL(k_harris_batch, dim3(tab_h->flat_base[NLEV], n), dim3(256), 0, st, b);
         hipLaunchKernelGGL(k_select_batch, dim3(NLEV, n), dim3(1024), 0, st, b);
         hipLaunchKernelGGL(k_describe_batch, dim3((c0->max_feat + 3) / 4, n), dim3(256), 0, st, b, c0->max_feat);
@@ -1244,18 +1327,30 @@ RELOC_API const uint8_t *reloc_frame_desc_dev(reloc_ctx *ctx) { return ctx ? ctx
 RELOC_API const float *reloc_frame_xy_dev(reloc_ctx *ctx) { return ctx ? ctx->f_xy : nullptr; }
 RELOC_API const int32_t *reloc_frame_count_dev(reloc_ctx *ctx) { return ctx ? ctx->f_count : nullptr; }
 
-RELOC_API int reloc_orb_detect_compute(reloc_ctx *ctx, const uint8_t *gray, int w, int h, int stride, int nfeatures,
-                                       float *xy, float *size, float *angle, float *response, int32_t *octave,
-                                       uint8_t *desc, int32_t *n_out)
+// level 0 of the mask pyramid mp from a host mask of w x h (rows mask_stride apart): rows of the level's stride, padding 0
+static int mask_upload(reloc_ctx *ctx, uint8_t *mp, const uint8_t *mask, int w, int h, int mask_stride)
 {
-    ARG_CHECK_CTX(ctx, gray && n_out && w > 0 && h > 0 && stride >= w && nfeatures > 0, "reloc_orb_detect_compute");
+    const size_t ds = (size_t)((w + 63) / 64 * 64);
+    HIP_TRY(hipMemsetAsync(mp, 0, ds * h, ctx->stream));
+    HIP_TRY(hipMemcpy2DAsync(mp, ds, mask, mask_stride, w, h, hipMemcpyHostToDevice, ctx->stream));
+    return RELOC_OK;
+}
+
+// gray plane -> features on the host; mask != NULL: under that mask, through the context's per-call mask pyramid
+static int orb_detect_host(reloc_ctx *ctx, const uint8_t *gray, int w, int h, int stride, const uint8_t *mask, int mask_stride,
+                           int nfeatures, float *xy, float *size, float *angle, float *response, int32_t *octave, uint8_t *desc,
+                           int32_t *n_out)
+{
     *n_out = 0;
     if (w < 63 || h < 63) return RELOC_OK;   // no level is wider than the 31-pixel edge margin on both sides
     if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
+    if (mask)
+        if (int rc = mask_alloc(ctx)) return rc;
     HostStaging st{ctx};        // no scratch slot: the context's frame and feature buffers
     st.upload_rows(ctx->frame_img, gray, w, h, stride);
+    if (mask) st.run([&] { return mask_upload(ctx, ctx->mask.call, mask, w, h, mask_stride); });
     const uint8_t *src = ctx->frame_img;
-    st.run([&] { return orb_run(&ctx, 1, &src, w, h, w, 1, 0, nfeatures, true); });
+    st.run([&] { return orb_run(&ctx, 1, &src, w, h, w, 1, 0, nfeatures, true, mask != nullptr); });
     const int32_t n = st.count(ctx->f_count);
     if (n > 0) {
         if (xy) st.download(xy, ctx->f_xy, (int64_t)n * 8);
@@ -1267,6 +1362,67 @@ RELOC_API int reloc_orb_detect_compute(reloc_ctx *ctx, const uint8_t *gray, int 
     }
     if (int rc = st.finish()) return rc;
     *n_out = n;
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_orb_detect_compute(reloc_ctx *ctx, const uint8_t *gray, int w, int h, int stride, int nfeatures,
+                                       float *xy, float *size, float *angle, float *response, int32_t *octave,
+                                       uint8_t *desc, int32_t *n_out)
+{
+    ARG_CHECK_CTX(ctx, gray && n_out && w > 0 && h > 0 && stride >= w && nfeatures > 0, "reloc_orb_detect_compute");
+    return orb_detect_host(ctx, gray, w, h, stride, nullptr, 0, nfeatures, xy, size, angle, response, octave, desc, n_out);
+}
+
+RELOC_API int reloc_orb_detect_compute_masked(reloc_ctx *ctx, const uint8_t *gray, int w, int h, int stride, const uint8_t *mask,
+                                              int mask_stride, int nfeatures, float *xy, float *size, float *angle,
+                                              float *response, int32_t *octave, uint8_t *desc, int32_t *n_out)
+{
+    ARG_CHECK_CTX(ctx, gray && n_out && w > 0 && h > 0 && stride >= w && nfeatures > 0, "reloc_orb_detect_compute_masked");
+    ARG_CHECK(mask && mask_stride >= w, "reloc_orb_detect_compute_masked: mask is NULL or its stride is below the width");
+    return orb_detect_host(ctx, gray, w, h, stride, mask, mask_stride, nfeatures, xy, size, angle, response, octave, desc, n_out);
+}
+
+RELOC_API int reloc_set_orb_mask(reloc_ctx *ctx, const uint8_t *mask, int w, int h, int stride)
+{
+    ARG_CHECK_CTX(ctx, true, "ctx is NULL");
+    OrbMaskStage &m = ctx->mask;
+    if (!mask || (w == 0 && h == 0)) {
+        m.w = m.h = 0;
+        m.built = false;
+        return RELOC_OK;
+    }
+    ARG_CHECK(w >= 1 && h >= 1 && stride >= w, "reloc_set_orb_mask: the size is not positive or the stride is below the width");
+    if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("detection mask exceeds ctx capacity"); return RELOC_E_CAPACITY; }
+    if (int rc = mask_alloc(ctx)) return rc;
+    // frames in flight may still read the previous mask; its levels 1.. are built in front of the next frame, when the
+    // tables of the frame size exist
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    m.w = m.h = 0;
+    m.built = false;
+    if (m.last == m.pyr) m.last = nullptr;      // its levels no longer belong together: no tap until a frame used the new mask
+    if (int rc = mask_upload(ctx, m.pyr, mask, w, h, stride)) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    m.w = w; m.h = h;
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_get_orb_mask(reloc_ctx *ctx, int32_t *w, int32_t *h)
+{
+    ARG_CHECK_CTX(ctx, w && h, "reloc_get_orb_mask");
+    *w = ctx->mask.w; *h = ctx->mask.h;
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_orb_mask_level(reloc_ctx *ctx, int level, uint8_t *out, int32_t *w, int32_t *h)
+{
+    ARG_CHECK_CTX(ctx, out && w && h && level >= 0 && level < NLEV, "reloc_orb_mask_level");
+    const OrbMaskStage &m = ctx->mask;
+    if (!m.last || m.last_w != ctx->orb_w || m.last_h != ctx->orb_h) { reloc_set_error("no masked frame processed yet"); return RELOC_E_STATE; }
+    const OrbLevel &L = ctx->lev[level];
+    HIP_TRY(hipMemcpy2DAsync(out, L.w, m.last + L.off, L.stride, L.w, L.h, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *w = L.w;
+    *h = L.h;
     return RELOC_OK;
 }
 

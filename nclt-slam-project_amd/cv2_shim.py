@@ -98,15 +98,20 @@ def _dist_coeffs(distCoeffs, what):
     return d5 if np.any(d5 != 0) else None
 
 
-def _takes_dist(fn):
-    """a backend method that accepts dist= (the HIP Engine's do; a backend without a distortion model must not be handed
-    distorted points silently)"""
+def _takes(fn, name):
+    """a backend method that accepts the keyword `name`"""
     import inspect
     try:
         ps = inspect.signature(fn).parameters
     except (TypeError, ValueError):
         return False
-    return "dist" in ps or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in ps.values())
+    return name in ps or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in ps.values())
+
+
+def _takes_dist(fn):
+    """a backend method that accepts dist= (the HIP Engine's do; a backend without a distortion model must not be handed
+    distorted points silently)"""
+    return _takes(fn, "dist")
 
 
 def _distort(x, y, d):
@@ -166,13 +171,24 @@ class _ORB:
         self._nfeatures = int(nfeatures)
 
     def detectAndCompute(self, image, mask=None):
-        if mask is not None:
-            raise error("detectAndCompute: masks are not supported (the reference passes None)")
         img = np.asarray(image)
         if img.dtype != np.uint8 or img.ndim != 2:
             raise error("detectAndCompute: expected a single-channel uint8 image")
+        kw = {}
+        if mask is not None:
+            # OpenCV: CV_8UC1 of the image's size; zero pixels of a mask level take no keypoint (include/reloc_spec.h "ORB MASK")
+            m = np.asarray(mask)
+            if m.dtype != np.uint8 or m.ndim != 2:
+                raise error("detectAndCompute: the mask must be a single-channel uint8 array (CV_8UC1)")
+            if m.shape != img.shape:
+                raise error(f"detectAndCompute: the mask is {m.shape[1]}x{m.shape[0]}, the image {img.shape[1]}x{img.shape[0]}")
+            if not _takes(self._shim.backend.orb_detect_compute, "mask"):
+                raise error("detectAndCompute: masks are not implemented by this backend (its orb_detect_compute takes no mask)")
+            if m.strides[1] != 1 or m.strides[0] < m.shape[1]:
+                m = np.ascontiguousarray(m)
+            kw["mask"] = m
         try:
-            r = self._shim.backend.orb_detect_compute(img, self._nfeatures)
+            r = self._shim.backend.orb_detect_compute(img, self._nfeatures, **kw)
         except RelocError as e:
             raise error(str(e)) from e
         kps = tuple(KeyPoint(float(r["xy"][i, 0]), float(r["xy"][i, 1]), r["size"][i], r["angle"][i], r["response"][i],

@@ -170,7 +170,18 @@ class Engine:
         N.check(self._lib.reloc_gray_u8(self._ctx, N.ptr(img), w, h, w * 3, int(order_rgb), N.ptr(out)), "reloc_gray_u8")
         return out
 
-    def orb_detect_compute(self, gray: np.ndarray, nfeatures: int = 500):
+    @staticmethod
+    def _mask_plane(mask, what):
+        """an ORB mask as the library takes it: (H, W) uint8, unit column stride, rows strides[0] >= W apart (no copy)"""
+        if not isinstance(mask, np.ndarray) or mask.dtype != np.uint8 or mask.ndim != 2 or mask.size == 0:
+            raise N.RelocError(f"{what}: the mask is an (H, W) uint8 array")
+        if mask.strides[1] != 1 or mask.strides[0] < mask.shape[1]:
+            raise N.RelocError(f"{what}: the mask must be C-contiguous, or strided along rows only (strides[0] >= W)")
+        return mask
+
+    def orb_detect_compute(self, gray: np.ndarray, nfeatures: int = 500, mask: np.ndarray | None = None):
+        """cv2.ORB_create(nfeatures).detectAndCompute(gray, mask); mask: None, or an (H, W) uint8 array of gray's size that
+        applies to this call only (reloc_orb_detect_compute_masked; the persistent mask of set_orb_mask never applies here)"""
         gray = N.u8(gray)
         if gray.ndim != 2:
             raise N.RelocError("detectAndCompute: expected an (H, W) uint8 image")
@@ -179,12 +190,44 @@ class Engine:
         xy = np.empty((mf, 2), np.float32); size = np.empty(mf, np.float32); ang = np.empty(mf, np.float32)
         resp = np.empty(mf, np.float32); octv = np.empty(mf, np.int32); desc = np.empty((mf, 32), np.uint8)
         n = C.c_int32()
-        N.check(self._lib.reloc_orb_detect_compute(self._ctx, N.ptr(gray), w, h, w, int(nfeatures), N.ptr(xy), N.ptr(size),
-                                                   N.ptr(ang), N.ptr(resp), N.ptr(octv), N.ptr(desc), C.byref(n)),
-                "reloc_orb_detect_compute")
+        outs = (N.ptr(xy), N.ptr(size), N.ptr(ang), N.ptr(resp), N.ptr(octv), N.ptr(desc), C.byref(n))
+        if mask is None:
+            N.check(self._lib.reloc_orb_detect_compute(self._ctx, N.ptr(gray), w, h, w, int(nfeatures), *outs),
+                    "reloc_orb_detect_compute")
+        else:
+            mask = self._mask_plane(mask, "detectAndCompute")
+            if mask.shape != (h, w):
+                raise N.RelocError(f"detectAndCompute: the mask is {mask.shape[1]}x{mask.shape[0]}, the image {w}x{h}")
+            N.check(self._lib.reloc_orb_detect_compute_masked(self._ctx, N.ptr(gray), w, h, w, C.c_void_p(mask.ctypes.data),
+                                                              mask.strides[0], int(nfeatures), *outs),
+                    "reloc_orb_detect_compute_masked")
         k = n.value
         return dict(xy=xy[:k].copy(), size=size[:k].copy(), angle=ang[:k].copy(), response=resp[:k].copy(),
                     octave=octv[:k].copy(), desc=desc[:k].copy(), n=k)
+
+    def set_orb_mask(self, mask: np.ndarray | None = None):
+        """ORB's detection mask on the frames of the fused tick, recording and reloc_orb_frame_dev (reloc_set_orb_mask): an
+        (H, W) uint8 array of the size of the working frame (behind set_resize); corners on zero pixels of their mask level are
+        dropped before the per-level quota is spent.  None = off."""
+        if mask is None:
+            N.check(self._lib.reloc_set_orb_mask(self._ctx, None, 0, 0, 0), "reloc_set_orb_mask")
+            return
+        mask = self._mask_plane(mask, "set_orb_mask")
+        N.check(self._lib.reloc_set_orb_mask(self._ctx, C.c_void_p(mask.ctypes.data), mask.shape[1], mask.shape[0],
+                                             mask.strides[0]), "reloc_set_orb_mask")
+
+    def get_orb_mask(self):
+        """None when off, else the mask's (w, h)"""
+        w = C.c_int32(); h = C.c_int32()
+        N.check(self._lib.reloc_get_orb_mask(self._ctx, C.byref(w), C.byref(h)), "reloc_get_orb_mask")
+        return None if w.value == 0 else (w.value, h.value)
+
+    def orb_mask_level(self, level: int) -> np.ndarray:
+        """level of the mask pyramid that the last masked frame used (parity tap, reloc_orb_mask_level)"""
+        buf = np.empty(self.max_w * self.max_h, np.uint8)
+        w = C.c_int32(); h = C.c_int32()
+        N.check(self._lib.reloc_orb_mask_level(self._ctx, int(level), N.ptr(buf), C.byref(w), C.byref(h)), "reloc_orb_mask_level")
+        return buf[: w.value * h.value].reshape(h.value, w.value).copy()
 
     def clahe(self, gray: np.ndarray, clip: float = 40.0, tiles=(8, 8)) -> np.ndarray:
         """cv2.createCLAHE(clip, tiles).apply(gray) on an (H, W) uint8 image (reloc_clahe_u8); tiles = (tiles_x, tiles_y)"""

@@ -54,6 +54,12 @@ class MatcherConfig:
     # then an (H, W) uint8 mosaic, demosaiced (bilinear) and converted to gray at the head of the image chain; resize takes
     # the mosaic's size as its source.  Teach with the same pattern.
     bayer: str | None = None
+    # ORB's detection mask, the second argument of detectAndCompute: None = every pixel may carry a keypoint (the reference
+    # matcher), or an (H, W) uint8 array in which zero marks what must never become a landmark -- the robot's own hood, sky, the
+    # black wedges of a rectification, a fisheye's blind zone.  It has the size of the resized / rectified frame that ORB
+    # sees, and acts inside ORB, before the per-level quota is spent (include/reloc_spec.h "ORB MASK"; use 255 for "keep":
+    # pyramid levels above 0 keep a pixel only where the interpolated mask is 255).  Teach and repeat usually share it.
+    mask: np.ndarray | None = None
     candidate_radius_m: float = 8.0
     max_candidates: int = 5
     heading_tol_deg: float = 90.0
@@ -133,6 +139,16 @@ def bayer_setting(pattern):
     return code
 
 
+def mask_setting(mask):
+    """MatcherConfig.mask / the recorder's mask= as the (H, W) uint8 array detectAndCompute takes (None stays None)"""
+    if mask is None:
+        return None
+    m = np.asarray(mask)
+    if m.dtype != np.uint8 or m.ndim != 2 or m.size == 0:
+        raise ValueError("mask must be None or an (H, W) uint8 array of the size of the frame ORB sees")
+    return np.ascontiguousarray(m)
+
+
 def fixed_rectify_maps(cv2, maps):
     """MatcherConfig.rectify as the fixed-point pair cv2.remap reads for both interpolations (None stays None)"""
     if maps is None:
@@ -145,10 +161,12 @@ def fixed_rectify_maps(cv2, maps):
 
 class ImageChain:
     """The image chain between the camera frame and ORB on the cv2-shaped path, stated here only: [demosaic] -> gray ->
-    resize -> rectify -> CLAHE, the depth following resize and rectify with INTER_NEAREST.  clahe, rectify, resize, bayer: as
-    MatcherConfig's; cv2 None: never applied."""
-    def __init__(self, cv2, clahe=None, rectify=None, resize=None, bayer=None):
+    resize -> rectify -> CLAHE, the depth following resize and rectify with INTER_NEAREST; it carries ORB's detection mask, which
+    the cores hand to detectAndCompute with the chain's output.  clahe, rectify, resize, bayer, mask: as MatcherConfig's; cv2
+    None: never applied."""
+    def __init__(self, cv2, clahe=None, rectify=None, resize=None, bayer=None, mask=None):
         self.cv2 = cv2
+        self.mask = mask_setting(mask)
         self.bayer = bayer_setting(bayer)
         self.clahe = None if cv2 is None or clahe is None else cv2.createCLAHE(clipLimit=clahe[0], tileGridSize=tuple(clahe[1]))
         self.rectify = fixed_rectify_maps(cv2, rectify) if cv2 is not None else None
@@ -175,8 +193,9 @@ class ImageChain:
         return gray, depth_mm
 
 
-def configure_engine(engine, clahe=None, rectify=None, resize=None, bayer=None):
-    """the same four settings on an Engine, which is as large as the camera"""
+def configure_engine(engine, clahe=None, rectify=None, resize=None, bayer=None, mask=None):
+    """the same five settings on an Engine, which is as large as the camera"""
+    engine.set_orb_mask(mask_setting(mask))
     engine.set_bayer(bayer_setting(bayer))
     engine.set_clahe(*((None,) if clahe is None else (clahe[0], tuple(clahe[1]))))
     engine.set_resize(*((None, None) if resize is None else ((engine.max_w, engine.max_h), resize_setting(resize))))
@@ -199,7 +218,7 @@ class LandmarkMatcherCore:
         self._adopt(load_landmarks(landmarks) if isinstance(landmarks, str) else landmarks)
         self.orb = cv2.ORB_create(nfeatures=self.cfg.nfeatures)
         self.matcher = cv2.BFMatcher(cv2.NORM_HAMMING, crossCheck=True)
-        self.chain = c = ImageChain(cv2, self.cfg.clahe, self.cfg.rectify, self.cfg.resize, self.cfg.bayer)
+        self.chain = c = ImageChain(cv2, self.cfg.clahe, self.cfg.rectify, self.cfg.resize, self.cfg.bayer, self.cfg.mask)
         self.clahe, self.rectify, self.resize = c.clahe, c.rectify, c.resize
         self.dist = np.zeros((4, 1), dtype=np.float32) if len(self.cfg.dist) == 0 else np.asarray(self.cfg.dist, np.float64).reshape(-1, 1)
         self.last_anchor_ts = 0.0
@@ -342,7 +361,7 @@ class LandmarkMatcherCore:
         vio_xy = (base_pose[0], base_pose[1])
         cand, d, herr = self.select_candidates(base_pose)
         gray, depth_mm = self.chain.apply(bgr, depth_mm)
-        kpts, desc = self.orb.detectAndCompute(gray, None)
+        kpts, desc = self.orb.detectAndCompute(gray, self.chain.mask)
         if desc is None or len(kpts) < cfg.min_matches:
             o = TickOutcome(ts, vio_xy, len(cand), 0, None, None, "curr_no_features")
             self._csv(o)
@@ -449,7 +468,7 @@ class FusedLandmarkMatcher:
         e.set_camera([cfg.fx, cfg.fy, cfg.cx, cfg.cy], data.get("base_to_cam_translation", P.BASE_TO_CAM_TRANSLATION),
                      data.get("base_to_cam_rot", P.BASE_TO_CAM_ROT))
         e.set_distortion(cfg.dist)
-        configure_engine(e, cfg.clahe, cfg.rectify, cfg.resize, cfg.bayer)
+        configure_engine(e, cfg.clahe, cfg.rectify, cfg.resize, cfg.bayer, cfg.mask)
         self._return_src = return_landmarks
         self.swap_flag = swap_flag
         self._swapped = False

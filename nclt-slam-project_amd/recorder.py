@@ -41,7 +41,7 @@ def local_depth_std(depth_mm, uu, vv):
 
 class LandmarkRecorderCore:
     def __init__(self, out_pkl=None, min_disp_m: float = 2.0, cv2=None, nfeatures: int = 500, logger=None, engine=None,
-                 dist=(), clahe=None, rectify=None, resize=None, bayer=None):
+                 dist=(), clahe=None, rectify=None, resize=None, bayer=None, mask=None):
         """engine: when given, ORB + all per-keypoint gates + back-projection run in ONE device call
         (reloc_record_frame); otherwise the gates run in NumPy on the cv2-shaped module's features.
         dist: lens distortion as MatcherConfig.dist (OpenCV's k1 k2 p1 p2 [k3], () = pinhole): the kept keypoints are
@@ -55,12 +55,15 @@ class LandmarkRecorderCore:
         reloc_set_resize from the engine's full size, which must be the camera's; cv2 path: cv2.resize).
         bayer: None or "BG" / "GB" / "RG" / "GR" as MatcherConfig.bayer (OpenCV's letters; sensor names RGGB / GRBG / BGGR /
         GBRG): every frame is the (H, W) uint8 mosaic of a raw camera, demosaiced and converted to gray in front of the
-        resize (engine: reloc_set_bayer; cv2 path: cv2.cvtColor(raw, COLOR_Bayer??2BGR), then COLOR_BGR2GRAY)."""
+        resize (engine: reloc_set_bayer; cv2 path: cv2.cvtColor(raw, COLOR_Bayer??2BGR), then COLOR_BGR2GRAY).
+        mask: None or an (H, W) uint8 array as MatcherConfig.mask, of the size of the resized / rectified frame: ORB takes no
+        keypoint where it is zero (engine: reloc_set_orb_mask; cv2 path: the second argument of detectAndCompute).  Teach and
+        repeat usually share it."""
         self.engine = engine
         self.dist = tuple(np.asarray(dist, np.float64).ravel()) if dist is not None else ()
         if engine is not None:
             engine.set_distortion(self.dist)
-            configure_engine(engine, clahe, rectify, resize, bayer)
+            configure_engine(engine, clahe, rectify, resize, bayer, mask)
         self.nfeatures = nfeatures
         if cv2 is None and engine is None:
             from . import cv2_shim as cv2
@@ -68,7 +71,7 @@ class LandmarkRecorderCore:
         self.out_pkl = out_pkl
         self.min_disp_m = float(min_disp_m)
         self.orb = cv2.ORB_create(nfeatures=nfeatures) if cv2 is not None else None
-        self.chain = c = ImageChain(cv2, clahe, rectify, resize, bayer)
+        self.chain = c = ImageChain(cv2, clahe, rectify, resize, bayer, mask)
         self.clahe, self.rectify, self.resize = c.clahe, c.rectify, c.resize
         self.landmarks = []
         self.last_landmark_pose_world = None
@@ -93,7 +96,7 @@ class LandmarkRecorderCore:
             self.last_landmark_pose_world = cam_pose
             return rec
         gray, depth_mm = self.chain.apply(bgr, depth_mm)
-        kpts, desc = self.orb.detectAndCompute(gray, None)
+        kpts, desc = self.orb.detectAndCompute(gray, self.chain.mask)
         if desc is None or len(kpts) == 0:
             return None
         xy = np.array([k.pt for k in kpts], dtype=np.float32)

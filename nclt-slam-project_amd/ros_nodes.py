@@ -56,6 +56,17 @@ def img_msg_to_depth_mm(msg):
     raise ValueError(f"unexpected depth encoding {msg.encoding}")
 
 
+def load_mask(path):
+    """--mask FILE.npy: ORB's detection mask (MatcherConfig.mask) from a NumPy file holding an (H, W) uint8 array; no image
+    decoder is involved, a PNG mask is converted once with np.save.  None stays None."""
+    if path is None:
+        return None
+    m = np.load(path, allow_pickle=False)
+    if m.dtype != np.uint8 or m.ndim != 2 or m.size == 0:
+        raise ValueError(f"--mask {path}: expected an (H, W) uint8 array, got {m.dtype} {m.shape}")
+    return np.ascontiguousarray(m)
+
+
 def read_pose_file(path=POSE_FILE):
     try:
         with open(path) as f:
@@ -78,9 +89,10 @@ def _node_base():
     return Node
 
 
-def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global_reloc=False, fused=False, cv2=None, bayer=None):
+def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global_reloc=False, fused=False, cv2=None, bayer=None,
+                      mask=None):
     """cv2: the cv2-shaped module the ROS-free core calls (default: the HIP shim); only the non-fused core uses it.
-    bayer: MatcherConfig.bayer -- the colour topic carries raw mosaics, passed through undecoded"""
+    bayer: MatcherConfig.bayer -- the colour topic carries raw mosaics, passed through undecoded.  mask: MatcherConfig.mask"""
     from geometry_msgs.msg import PoseWithCovarianceStamped
     from sensor_msgs.msg import Image
     Node = _node_base()
@@ -88,7 +100,7 @@ def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global
     class VisualLandmarkMatcher(Node):
         def __init__(self):
             super().__init__("visual_landmark_matcher")
-            cfg = MatcherConfig(global_reloc=global_reloc, bayer=bayer)
+            cfg = MatcherConfig(global_reloc=global_reloc, bayer=bayer, mask=mask)
             if fused:
                 self.core = FusedLandmarkMatcher(pkl_path, log_csv, config=cfg, return_landmarks=return_pkl,
                                                  swap_flag=swap_flag, logger=lambda m: self.get_logger().info(m),
@@ -143,14 +155,14 @@ def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global
     return VisualLandmarkMatcher()
 
 
-def make_recorder_node(out_pkl, min_disp_m=2.0, cv2=None, bayer=None):
+def make_recorder_node(out_pkl, min_disp_m=2.0, cv2=None, bayer=None, mask=None):
     from sensor_msgs.msg import Image
     Node = _node_base()
 
     class VisualLandmarkRecorder(Node):
         def __init__(self):
             super().__init__("visual_landmark_recorder")
-            self.core = LandmarkRecorderCore(out_pkl, min_disp_m, cv2=cv2, bayer=bayer)
+            self.core = LandmarkRecorderCore(out_pkl, min_disp_m, cv2=cv2, bayer=bayer, mask=mask)
             self.last_rgb = self.last_depth = None
             self.last_rgb_ts = 0.0
             self.create_subscription(Image, "/camera/color/image_raw", self._rgb_cb, 10)
@@ -182,6 +194,15 @@ def make_recorder_node(out_pkl, min_disp_m=2.0, cv2=None, bayer=None):
     return VisualLandmarkRecorder()
 
 
+MASK_HELP = "ORB takes no keypoint where this (H, W) uint8 array (a .npy file, size of the frame ORB sees) is zero"
+
+
+def _chain_args(args):
+    """the trailing (cv2, bayer, mask) of the node factories; cv2 None = the default shim; nothing when all are defaults"""
+    mask = load_mask(args.mask)
+    return () if args.bayer is None and mask is None else (None, args.bayer) if mask is None else (None, args.bayer, mask)
+
+
 def matcher_main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--landmarks", required=True)
@@ -191,10 +212,11 @@ def matcher_main(argv=None):
     ap.add_argument("--global-reloc", action="store_true")
     ap.add_argument("--fused", action="store_true", help="run the whole tick in one device call")
     ap.add_argument("--bayer", default=None, choices=["BG", "GB", "RG", "GR"], help="the colour topic carries raw 8-bit mosaics of this pattern")
+    ap.add_argument("--mask", default=None, metavar="FILE.npy", help=MASK_HELP)
     args = ap.parse_args(argv)
+    raw = _chain_args(args)
     import rclpy
     rclpy.init()
-    raw = () if args.bayer is None else (None, args.bayer)           # cv2 (the default shim), bayer
     node = make_matcher_node(args.landmarks, args.out_csv, args.landmarks_return, args.swap_flag, args.global_reloc, args.fused, *raw)
     try:
         rclpy.spin(node)
@@ -214,10 +236,11 @@ def recorder_main(argv=None):
     ap.add_argument("--out", required=True)
     ap.add_argument("--min-disp", type=float, default=2.0)
     ap.add_argument("--bayer", default=None, choices=["BG", "GB", "RG", "GR"], help="the colour topic carries raw 8-bit mosaics of this pattern")
+    ap.add_argument("--mask", default=None, metavar="FILE.npy", help=MASK_HELP)
     args = ap.parse_args(argv)
+    raw = _chain_args(args)
     import rclpy
     rclpy.init()
-    raw = () if args.bayer is None else (None, args.bayer)           # cv2 (the default shim), bayer
     node = make_recorder_node(args.out, args.min_disp, *raw)
     try:
         rclpy.spin(node)

@@ -1,0 +1,370 @@
+"""GPU parity of ORB's detection mask (include/reloc_spec.h "ORB MASK"): the mask pyramid, the masked NMS pass behind the
+per-call and the persistent mask, and the fused entry points, bit for bit against tests/orb_mask_ref.py."""
+import numpy as np
+import pytest
+
+import orb_mask_ref as MR
+import record_ref as RR
+from nclt_slam_project_amd import synth
+from nclt_slam_project_amd._native import RelocError
+from nclt_slam_project_amd.engine import Engine
+
+pytestmark = pytest.mark.gpu
+
+# odd widths and row padding, levels below the 63-pixel limit, a single usable level
+SHAPES = [(4, 333, 251), (6, 100, 500), (2, 640, 480), (7, 130, 67)]
+_frames, _refs = {}, {}
+
+
+def _frame(seed, w, h):
+    """(bgr, gray) of the synthetic frame, computed once"""
+    if (seed, w, h) not in _frames:
+        from oracle import oracle as O
+        O.build()
+        img = synth.textured_frame(np.random.default_rng(seed), w, h, n_shapes=max(40, w * h // 800))
+        _frames[seed, w, h] = (img, O.gray_u8(img))
+    return _frames[seed, w, h]
+
+
+def _ref(oracle, seed, w, h, name, nfeatures=500):
+    """(mask, reference) of a named mask on the synthetic frame, computed once and left unchanged"""
+    key = (seed, w, h, name, nfeatures)
+    if key not in _refs:
+        mask = MR.named_mask(name, w, h)
+        _refs[key] = (mask, MR.detect_compute(oracle, _frame(seed, w, h)[1], mask, nfeatures))
+    return _refs[key]
+
+
+def _check_planes(e, ref, what):
+    for l in range(8):
+        np.testing.assert_array_equal(e.orb_mask_level(l), ref["mask_levels"][l], err_msg=f"{what}: mask level {l}")
+        np.testing.assert_array_equal(e.frame_debug_plane(2, l), ref["nms"][l], err_msg=f"{what}: nms level {l}")
+
+
+def _frame_dev(e, img, nfeatures=500):
+    h, w = img.shape[:2]
+    dev = e.to_device(img)
+    try:
+        n = e.orb_frame_dev(dev, w, h, nfeatures=nfeatures)
+    finally:
+        e.dev_free(dev)
+    return n
+
+
+def _check_device_features(e, n, ref, what):
+    """what the device keeps of a frame: count, coordinates (bit patterns) and descriptors, level-major raster order"""
+    f = e.orb_features()
+    assert n == f["n"] == ref["n"], f"{what}: n {n} != {ref['n']}"
+    np.testing.assert_array_equal(f["xy"].view(np.uint32), ref["xy"].view(np.uint32), err_msg=f"{what}: xy")
+    np.testing.assert_array_equal(f["desc"], ref["desc"], err_msg=f"{what}: desc")
+
+
+@pytest.mark.parametrize("name", MR.MASK_NAMES)
+@pytest.mark.parametrize("seed,w,h", SHAPES)
+def test_mask_pyramid(engine, oracle, seed, w, h, name):
+    mask, ref = _ref(oracle, seed, w, h, name)
+    engine.orb_detect_compute(_frame(seed, w, h)[1], 500, mask=mask)
+    for l in range(8):
+        got = engine.orb_mask_level(l)
+        assert got.shape == ref["mask_levels"][l].shape
+        np.testing.assert_array_equal(got, ref["mask_levels"][l], err_msg=f"mask level {l}")
+    if name in ("zero_one", "all0"):
+        assert all(engine.orb_mask_level(l).max() == 0 for l in range(1, 8))
+
+
+@pytest.mark.parametrize("name", MR.MASK_NAMES)
+@pytest.mark.parametrize("seed,w,h", SHAPES)
+def test_per_call_mask(engine, oracle, seed, w, h, name):
+    gray = _frame(seed, w, h)[1]
+    mask, ref = _ref(oracle, seed, w, h, name)
+    got = engine.orb_detect_compute(gray, 500, mask=mask)
+    MR.assert_features_equal(got, ref, f"{w}x{h} {name}")
+    _check_planes(engine, ref, f"{w}x{h} {name}")
+    assert engine.get_orb_mask() is None                     # a per-call mask is not a setting
+    if name == "all255":
+        MR.assert_features_equal(engine.orb_detect_compute(gray, 500), got, "all 255 vs unmasked")
+    if name == "all0":
+        assert got["n"] == 0
+    # a mask strided through strides[0] is read in place
+    wide = np.zeros((h, w + 37), np.uint8)
+    wide[:, :w] = mask
+    MR.assert_features_equal(engine.orb_detect_compute(gray, 500, mask=wide[:, :w]), ref, "strided mask")
+
+
+@pytest.mark.parametrize("name", MR.MASK_NAMES)
+@pytest.mark.parametrize("seed,w,h", SHAPES)
+def test_persistent_mask(engine, oracle, seed, w, h, name):
+    img = _frame(seed, w, h)[0]
+    mask, ref = _ref(oracle, seed, w, h, name)
+    try:
+        engine.set_orb_mask(mask)
+        assert engine.get_orb_mask() == (w, h)
+        _check_device_features(engine, _frame_dev(engine, img), ref, f"{w}x{h} {name}")
+        _check_planes(engine, ref, f"{w}x{h} {name}")
+        # never applied to a caller's gray plane
+        plain = engine.orb_detect_compute(_frame(seed, w, h)[1], 500)
+        assert plain["n"] == _ref(oracle, seed, w, h, "all255")[1]["n"]
+    finally:
+        engine.set_orb_mask(None)
+    assert engine.get_orb_mask() is None
+
+
+@pytest.mark.parametrize("nf", [300, 1000])
+def test_nfeatures(engine, oracle, nf):
+    seed, w, h = SHAPES[2]
+    img, gray = _frame(seed, w, h)
+    mask, ref = _ref(oracle, seed, w, h, "half_band", nf)
+    MR.assert_features_equal(engine.orb_detect_compute(gray, nf, mask=mask), ref, f"nfeatures {nf}")
+    _check_planes(engine, ref, f"nfeatures {nf}")
+    try:
+        engine.set_orb_mask(mask)
+        _check_device_features(engine, _frame_dev(engine, img, nf), ref, f"persistent, nfeatures {nf}")
+    finally:
+        engine.set_orb_mask(None)
+
+
+def test_single_pixel_holes(engine, oracle):
+    seed, w, h = SHAPES[2]
+    gray = _frame(seed, w, h)[1]
+    base = _ref(oracle, seed, w, h, "all255")[1]
+    l0 = np.nonzero(base["octave"] == 0)[0]
+    holes = base["xy_level"][l0[:: max(1, len(l0) // 10)][:10]]
+    assert len(holes) == 10
+    mask = np.full((h, w), 255, np.uint8)
+    mask[holes[:, 1], holes[:, 0]] = 0
+    ref = MR.detect_compute(oracle, gray, mask)
+    got = engine.orb_detect_compute(gray, 500, mask=mask)
+    MR.assert_features_equal(got, ref, "holes")              # the rest follow the reference
+    _check_planes(engine, ref, "holes")
+    lvl0 = {(int(x), int(y)) for (x, y), o in zip(got["xy"], got["octave"]) if o == 0}
+    before = {(int(x), int(y)) for x, y in base["xy_level"][l0]}
+    nms = engine.frame_debug_plane(2, 0)
+    for x, y in holes:
+        assert (int(x), int(y)) not in lvl0                  # they vanish
+        assert nms[y, x] == 0
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):                            # and no neighbour takes their place: NMS ran unmasked
+                assert nms[y + dy, x + dx] == 0 and ((int(x) + dx, int(y) + dy) in lvl0) == (((int(x) + dx, int(y) + dy) in before) and (dx, dy) != (0, 0))
+
+
+def test_per_call_mask_leaves_the_persistent_one_alone(engine, oracle):
+    seed, w, h = SHAPES[0]
+    img, gray = _frame(seed, w, h)
+    mask_a, ref_a = _ref(oracle, seed, w, h, "half_band")
+    mask_b, ref_b = _ref(oracle, seed, w, h, "blocks")
+    try:
+        engine.set_orb_mask(mask_a)
+        _check_device_features(engine, _frame_dev(engine, img), ref_a, "before")
+        MR.assert_features_equal(engine.orb_detect_compute(gray, 500, mask=mask_b), ref_b, "per call")
+        np.testing.assert_array_equal(engine.orb_mask_level(1), ref_b["mask_levels"][1])
+        # another size in between: the tables of 333x251 are rebuilt for the next frame, the persistent pyramid is not
+        s2, w2, h2 = SHAPES[1]
+        MR.assert_features_equal(engine.orb_detect_compute(_frame(s2, w2, h2)[1], 500, mask=_ref(oracle, s2, w2, h2, "ramp")[0]),
+                                 _ref(oracle, s2, w2, h2, "ramp")[1], "per call, other size")
+        assert engine.get_orb_mask() == (w, h)
+        _check_device_features(engine, _frame_dev(engine, img), ref_a, "after")
+        _check_planes(engine, ref_a, "after")
+    finally:
+        engine.set_orb_mask(None)
+
+
+def _tick_record(e, img, bp, mode=True):
+    e.tick(img, bp, global_reloc=mode, seed=1)
+    rec = np.zeros(96, np.uint8)
+    e.d2h(rec, e.tick_result_dev)
+    return rec
+
+
+def test_off_is_off():
+    """set_orb_mask(None) after use, and a fresh engine: features and tick record of an engine that never had a mask"""
+    rng = np.random.default_rng(7)
+    img = synth.textured_frame(rng, 640, 480)
+    es = [Engine(0, 640, 480, 4096) for _ in range(2)]
+    try:
+        feats = es[0].orb_detect_compute(es[0].gray(img), 500)
+        db = synth.descriptor_db(rng, 64, "ragged", feats["desc"], planted_records=(5, 40))
+        for e in es:
+            e.db_upload(*db)
+        bp = synth.base_pose(10.0, 0.3, 2.0)
+        es[1].set_orb_mask(MR.half_band(640, 480))
+        on = _tick_record(es[1], img, bp)
+        f_on = es[1].orb_features()
+        es[1].orb_detect_compute(es[1].gray(img), 500, mask=MR.blocks(640, 480))
+        es[1].set_orb_mask(None)
+        assert es[1].get_orb_mask() is None
+        a, b = _tick_record(es[0], img, bp), _tick_record(es[1], img, bp)
+        assert a.tobytes() == b.tobytes() and len(on) == 96
+        fa, fb = es[0].orb_features(), es[1].orb_features()
+        assert fa["n"] == fb["n"] == feats["n"]
+        np.testing.assert_array_equal(fa["desc"], fb["desc"])
+        np.testing.assert_array_equal(fa["xy"], fb["xy"])
+        np.testing.assert_array_equal(fa["desc"], feats["desc"])
+        for l in range(8):
+            np.testing.assert_array_equal(es[0].frame_debug_plane(2, l), es[1].frame_debug_plane(2, l))
+        assert f_on["n"] != fa["n"] or not np.array_equal(f_on["desc"], fa["desc"])
+        with pytest.raises(RelocError, match="code -5"):
+            es[0].orb_mask_level(0)                          # no masked frame yet
+    finally:
+        for e in es:
+            e.close()
+
+
+def test_wrong_size_is_refused_and_the_chain_in_front_of_the_mask(oracle):
+    seed, w, h = SHAPES[2]
+    img = _frame(seed, w, h)[0]
+    small = MR.half_band(320, 240)
+    dep = RR.keeping_depth(seed, w, h)
+    bp = synth.base_pose(10.0, 0.3, 2.0)
+    e = Engine(0, 640, 480, 4096)
+    dev = e.to_device(img)
+    try:
+        e.db_upload(*synth.descriptor_db(np.random.default_rng(1), 64, "ragged"))
+        n0 = e.orb_frame_dev(dev, w, h)
+        before = e.orb_features()
+        nms0 = e.frame_debug_plane(2, 0)
+        assert n0 > 0
+        for mask in (small, MR.half_band(640, 479), MR.half_band(639, 480)):
+            e.set_orb_mask(mask)
+            for call in (lambda: e.tick(img, bp, global_reloc=True, seed=1), lambda: e.record_frame(img, dep),
+                         lambda: e.orb_frame_dev(dev, w, h), lambda: e.tick_dev(dev, w, h, bp)):
+                with pytest.raises(RelocError, match=r"code -1\).*detection mask"):
+                    call()
+            after = e.orb_features()                         # nothing was launched: the previous frame's features stand
+            assert after["n"] == before["n"]
+            np.testing.assert_array_equal(after["desc"], before["desc"])
+            np.testing.assert_array_equal(after["xy"], before["xy"])
+            np.testing.assert_array_equal(e.frame_debug_plane(2, 0), nms0)
+        # bad arguments
+        for bad in (small.astype(np.float32), small[:, ::2], small[:, :, None]):
+            with pytest.raises(RelocError):
+                e.set_orb_mask(bad)
+        with pytest.raises(RelocError, match="code -4"):
+            e.set_orb_mask(np.zeros((481, 640), np.uint8))
+        with pytest.raises(RelocError):
+            e.orb_detect_compute(_frame(seed, w, h)[1], 500, mask=small)
+        # with the downscale stage on, the mask has the resized size
+        e.set_resize((640, 480), (320, 240))
+        e.set_orb_mask(MR.half_band(640, 480))
+        with pytest.raises(RelocError, match=r"code -1\).*detection mask"):
+            e.orb_frame_dev(dev, w, h)
+        e.set_orb_mask(small)
+        assert e.get_orb_mask() == (320, 240)
+        # resize + rectify + CLAHE, then the mask: the reference on the chain's output plane
+        v, u = np.mgrid[0:240, 0:320]
+        e.set_rectify((u.astype(np.float32) + 0.25, v.astype(np.float32)))
+        e.set_clahe(2.0, (8, 8))
+        n = e.orb_frame_dev(dev, w, h)
+        plane = e.frame_debug_plane(0, 0)
+        assert plane.shape == (240, 320)
+        ref = MR.detect_compute(oracle, plane, small)
+        assert ref["n"] > 50
+        _check_device_features(e, n, ref, "chain")
+        _check_planes(e, ref, "chain")
+    finally:
+        e.dev_free(dev)
+        e.close()
+
+
+def test_tick_record_and_accumulate_under_a_mask(oracle):
+    seed, w, h = SHAPES[2]
+    img = _frame(seed, w, h)[0]
+    mask, ref = _ref(oracle, seed, w, h, "half_band")
+    ref_xy = {tuple(r) for r in ref["xy"].view(np.uint32).tolist()}
+    rng = np.random.default_rng(3)
+    e = Engine(0, 640, 480, 4096)
+    try:
+        db = synth.descriptor_db(rng, 64, "ragged", ref["desc"], planted_records=(5, 40))
+        e.db_upload(*db)
+        e.set_orb_mask(mask)
+        bp = synth.base_pose(10.0, 0.3, 2.0)
+        res = e.tick(img, bp, global_reloc=True, seed=1)
+        _check_device_features(e, ref["n"], ref, "tick")
+        dbg = e.tick_debug()
+        assert {5, 40} <= set(int(i) for i in dbg["cand_ids"]) and res["n_candidates"] >= 2      # the planted records are found
+        for r in (5, 40):
+            assert dbg["n_matches"][list(dbg["cand_ids"]).index(r)] >= 20
+        # recording files only keypoints of the masked detector
+        dep = RR.keeping_depth(seed, w, h)
+        rec = e.record_frame(img, dep)
+        assert rec["n_kp"] == ref["n"] and 30 <= rec["n"] <= ref["n"]
+        np.testing.assert_array_equal(rec["xy"].view(np.uint32), ref["xy"][rec["kp_index"]].view(np.uint32))
+        np.testing.assert_array_equal(rec["desc"], ref["desc"][rec["kp_index"]])
+        # ... and so does the accumulation (far from every record, nothing published: a record is appended)
+        far = (500.0, 500.0) + tuple(bp[2:])
+        img_dev, dep_dev = e.to_device(img), e.to_device(np.ascontiguousarray(dep, np.uint16))
+        try:
+            e.tick_dev(img_dev, w, h, far)
+            e.tick_accumulate_dev(dep_dev, w, h, far, True)
+            e.tick_result()
+            acc = e.accumulate_result()
+        finally:
+            e.dev_free(img_dev); e.dev_free(dep_dev)
+        assert acc["appended"] and acc["n_kpts"] >= 30 and e.db_records == 65
+        new = e.db_fetch(64)
+        rows = [tuple(r) for r in np.ascontiguousarray(new["keypoints_2d"]).view(np.uint32).tolist()]
+        assert len(rows) == acc["n_kpts"] and all(r in ref_xy for r in rows)
+    finally:
+        e.close()
+
+
+def test_batched_tick_with_three_masks_and_mixed_batches(oracle):
+    seed, w, h = SHAPES[2]
+    img = _frame(seed, w, h)[0]
+    names = ("half_band", "blocks", "ramp")
+    refs = [_ref(oracle, seed, w, h, n) for n in names]
+    rng = np.random.default_rng(3)
+    es = [Engine(0, 640, 480, 4096) for _ in range(3)]
+    fdev = []
+    try:
+        db = synth.descriptor_db(rng, 64, "ragged", refs[0][1]["desc"], planted_records=(5, 40))
+        es[0].db_upload(*db)
+        for e in es[1:]:
+            e.db_share(es[0])
+            e.set_stream(es[0].stream_ptr)
+        for e, (mask, _) in zip(es, refs):
+            e.set_orb_mask(mask)
+        poses = [synth.base_pose(10.0, 0.3, 2.0), synth.base_pose(80.0, 0.2, 1.0), synth.base_pose(10.5, -0.3, -2.0)]
+        fdev = [es[0].to_device(img) for _ in es]
+        for mode in (True, False):
+            single = []
+            for f, e in enumerate(es):
+                e.tick_dev(fdev[f], w, h, poses[f], global_reloc=mode, seed=7 + f)
+                e.tick_result()
+                rec = np.zeros(96, np.uint8)
+                e.d2h(rec, e.tick_result_dev)
+                single.append(rec)
+                _check_device_features(e, refs[f][1]["n"], refs[f][1], f"single {names[f]}")
+            Engine.tick_batch_dev(es, fdev, w, h, poses, global_reloc=mode, seeds=[7, 8, 9])
+            for f, e in enumerate(es):
+                e.tick_result()
+                rec = np.zeros(96, np.uint8)
+                e.d2h(rec, e.tick_result_dev)
+                print(f"mode {mode} frame {f}: single {single[f].view(np.int32)[16:22]} batch {rec.view(np.int32)[16:22]}")
+                _check_device_features(e, refs[f][1]["n"], refs[f][1], f"batch {names[f]}")
+                np.testing.assert_array_equal(e.frame_debug_plane(2, 0), refs[f][1]["nms"][0])
+                assert rec.tobytes() == single[f].tobytes(), (mode, f)
+        # masked and unmasked contexts, or masks of unequal size, do not share a batch
+        es[1].set_orb_mask(None)
+        with pytest.raises(RelocError, match="code -5"):
+            Engine.tick_batch_dev(es, fdev, w, h, poses, global_reloc=True, seeds=[7, 8, 9])
+        es[1].set_orb_mask(MR.half_band(320, 240))
+        with pytest.raises(RelocError, match="code -5"):
+            Engine.tick_batch_dev(es, fdev, w, h, poses, global_reloc=True, seeds=[7, 8, 9])
+        es[1].set_orb_mask(refs[1][0])
+        Engine.tick_batch_dev(es, fdev, w, h, poses, global_reloc=True, seeds=[7, 8, 9])
+        es[0].sync()
+        _check_device_features(es[1], refs[1][1]["n"], refs[1][1], "batch again")
+        # all off: the unmasked batch
+        for e in es:
+            e.set_orb_mask(None)
+        Engine.tick_batch_dev(es, fdev, w, h, poses, global_reloc=True, seeds=[7, 8, 9])
+        es[0].sync()
+        base = _ref(oracle, seed, w, h, "all255")[1]
+        for e in es:
+            _check_device_features(e, base["n"], base, "unmasked batch")
+    finally:
+        es[0].sync()
+        for p in fdev:
+            es[0].dev_free(p)
+        for e in es[::-1]:
+            e.close()
