@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import chain_harness as CH
 import clahe_ref as CR
 from nclt_slam_project_amd import RelocError, synth
 from nclt_slam_project_amd.cv2_shim import Cv2Shim, error
@@ -65,9 +66,9 @@ def test_shim_clahe_on_the_engine(eng):
 def test_orb_frame_dev_reads_the_clahe_plane(oracle, w, h):
     rng = np.random.default_rng(w + h)
     img = synth.textured_frame(rng, w, h)
-    e = Engine(0, 700, 500, 4096)
-    try:
-        dev = e.to_device(img)
+    with CH.engines(1, 700, 500) as rig:
+        e, = rig.es
+        dev = rig.to_device(img)
         for bits in (15, 14):
             e.set_params(gray_coeff_bits=bits)
             for order_rgb in (False, True):
@@ -85,178 +86,62 @@ def test_orb_frame_dev_reads_the_clahe_plane(oracle, w, h):
                     oref = oracle.orb_detect_compute(exp, 500, max_out=4096)
                     for k in ("xy", "angle", "response", "octave", "desc"):
                         np.testing.assert_array_equal(ref[k], oref[k][: oref["n"]])
-        e.sync()
-        e.dev_free(dev)
-    finally:
-        e.close()
 
 
 def test_record_frame_with_clahe_equals_the_cv2_path():
-    from nclt_slam_project_amd.recorder import LandmarkRecorderCore
     scene = synth.WallScene()
-    es = [Engine(0, 640, 480, 4096) for _ in range(2)]
-    try:
-        dev = LandmarkRecorderCore(engine=es[0], clahe=SETTING)
-        assert es[0].get_clahe() == SETTING
-        host = LandmarkRecorderCore(cv2=Cv2Shim(es[1]), clahe=SETTING)
-        for x in (2.0, 4.5, 7.0):
-            bp = synth.base_pose(x, 0.0, 0.0)
-            bgr, dep = scene.render(bp)
-            a, b = dev.tick(bgr, dep, bp, x), host.tick(bgr, dep, bp, x)
-            assert a is not None and b is not None
-            assert a["n_features"] == b["n_features"] >= 30
-            for k in ("descriptors", "keypoints_2d", "keypoints_3d_cam"):
-                np.testing.assert_array_equal(a[k], b[k])
-        # and the equalisation changed what was recorded
-        plain = es[1].record_frame(*scene.render(synth.base_pose(2.0, 0.0, 0.0)))
-        assert plain["n"] != dev.landmarks[0]["n_features"] or not np.array_equal(plain["desc"], dev.landmarks[0]["descriptors"])
-    finally:
-        for e in es:
-            e.close()
+    with CH.engines(2) as rig:
+        CH.assert_record_equals_cv2_path(rig.es, scene.render, lambda e: e.get_clahe() == SETTING, clahe=SETTING)
 
 
 def _teach_clahe(cv2, scene, gold):
     from nclt_slam_project_amd.recorder import LandmarkRecorderCore
-    rec = LandmarkRecorderCore(cv2=cv2, clahe=SETTING)
-    for x in gold["teach_x"]:
-        bp = synth.base_pose(x, 0.0, 0.0)
-        bgr, dep = scene.render(bp)
-        rec.tick(bgr, dep, bp, rgb_ts=x)
+    rec = CH.teach_wall(LandmarkRecorderCore(cv2=cv2, clahe=SETTING), gold["teach_x"], scene.render)
     assert len(rec.landmarks) == len(gold["teach_x"])
     return rec.database()
 
 
 def test_session_shim_and_fused_agree_with_clahe(gold, tmp_path):
-    from nclt_slam_project_amd.matcher import FusedLandmarkMatcher, LandmarkMatcherCore, MatcherConfig
+    from nclt_slam_project_amd.matcher import MatcherConfig
     scene = synth.WallScene()
-    es = [Engine(0, 640, 480, 4096) for _ in range(2)]
-    try:
-        data = _teach_clahe(Cv2Shim(es[0]), scene, gold)
-        cfg = MatcherConfig(clahe=SETTING)
-        csv_a, csv_b = str(tmp_path / "a.csv"), str(tmp_path / "b.csv")
-        core = LandmarkMatcherCore(data, csv_a, cv2=Cv2Shim(es[0]), config=cfg)
-        fm = FusedLandmarkMatcher(data, csv_b, engine=es[1], config=cfg)
-        assert es[1].get_clahe() == SETTING
-        pubs = 0
-        for i, (x, y, yaw) in enumerate(gold["repeat"]):
-            bp = synth.base_pose(x, y, yaw)
-            bgr, dep = scene.render(bp)
-            a = core.tick(bgr, None, bp, ts=1000.0 + 0.5 * i)              # no depth: neither matcher accumulates
-            b = fm.tick(bgr, bp, ts=1000.0 + 0.5 * i)
-            assert a.outcome == b.outcome and a.n_inliers == b.n_inliers and a.n_candidates == b.n_candidates, i
-            if a.anchor_pose:
-                assert np.abs(np.array(a.anchor_pose) - np.array(b.anchor_pose)).max() < 1e-4
-            pubs += a.published
-        ra, rb = open(csv_a).read().splitlines(), open(csv_b).read().splitlines()
-        assert len(ra) == len(rb) == len(gold["repeat"]) + 1 and ra[0] == rb[0]
-        for g, e in zip(ra[1:], rb[1:]):
-            gf, ef = g.split(","), e.split(",")
-            assert gf[:6] == ef[:6] and gf[8] == ef[8], (g, e)
-            for u, v in zip(gf[6:8], ef[6:8]):
-                assert (u == v == "") or abs(float(u) - float(v)) < 1e-4
-        assert pubs >= 3
-        # whole-database search: the host core told to search unconditionally, the fused tick in global mode
-        gcore = LandmarkMatcherCore(data, cv2=Cv2Shim(es[0]),
-                                    config=MatcherConfig(clahe=SETTING, global_reloc=True, reloc_age_s=-1.0, reloc_drift_m=-1.0))
-        n_glob = 0
-        for (x, y, yaw) in gold["global_poses"] + [(4.0, 9.5, 0.0), (7.0, 10.0, -10.0)]:
-            bp = synth.base_pose(x, y, yaw)
-            bgr, dep = scene.render(bp)
-            exp = gcore.tick(bgr, dep, bp, ts=9000.0, drift_est=10.0)
-            if not exp.relocating:
-                continue
-            n_glob += 1
-            got = fm.tick(bgr, bp, ts=9000.0, global_reloc=True)
-            assert got.outcome == exp.outcome and got.n_inliers == exp.n_inliers and got.n_candidates == exp.n_candidates
-            if exp.anchor_pose:
-                assert np.abs(np.array(got.anchor_pose) - np.array(exp.anchor_pose)).max() < 1e-4
-        assert n_glob >= 1
-    finally:
-        for e in es:
-            e.close()
-
-
-def _tick_record(e, img, bp):
-    e.tick(img, bp, global_reloc=True, seed=1)
-    rec = np.zeros(96, np.uint8)
-    e.d2h(rec, e.tick_result_dev)
-    return rec
+    with CH.engines(2) as rig:
+        data = _teach_clahe(Cv2Shim(rig.es[0]), scene, gold)
+        CH.assert_sessions_agree(rig.es, data, tmp_path, gold["repeat"], scene.render, MatcherConfig(clahe=SETTING),
+                                 lambda e: e.get_clahe() == SETTING,
+                                 MatcherConfig(clahe=SETTING, global_reloc=True, reloc_age_s=-1.0, reloc_drift_m=-1.0),
+                                 gold["global_poses"] + [(4.0, 9.5, 0.0), (7.0, 10.0, -10.0)])
 
 
 def test_clahe_turned_off_is_byte_identical_to_never_enabled():
     rng = np.random.default_rng(7)
     img = synth.textured_frame(rng, 640, 480)
-    es = [Engine(0, 640, 480, 4096) for _ in range(2)]
-    try:
-        assert es[0].get_clahe() is None
-        feats = es[0].orb_detect_compute(es[0].gray(img), 500)
-        db = synth.descriptor_db(rng, 64, "ragged", feats["desc"], planted_records=(5, 40))
-        for e in es:
-            e.db_upload(*db)
-        bp = synth.base_pose(10.0, 0.3, 2.0)
-        es[1].set_clahe(*SETTING)
-        on = _tick_record(es[1], img, bp)
-        f_on = es[1].orb_features()
-        es[1].set_clahe(None)
-        assert es[1].get_clahe() is None
-        a, b = _tick_record(es[0], img, bp), _tick_record(es[1], img, bp)
-        assert a.tobytes() == b.tobytes()
-        fa, fb = es[0].orb_features(), es[1].orb_features()
-        assert fa["n"] == fb["n"]
-        np.testing.assert_array_equal(fa["desc"], fb["desc"])
-        np.testing.assert_array_equal(es[0].frame_debug_plane(0, 0), es[1].frame_debug_plane(0, 0))
-        assert f_on["n"] != fa["n"] or not np.array_equal(f_on["desc"], fa["desc"])
-        es[1].set_clahe(0.0, (0, 0))                                          # the other way of saying off
-        assert es[1].get_clahe() is None
-        assert _tick_record(es[1], img, bp).tobytes() == a.tobytes()
-    finally:
-        for e in es:
-            e.close()
+    bp = synth.base_pose(10.0, 0.3, 2.0)
+    with CH.engines(2) as rig:
+        fresh, used = rig.es
+        a, = CH.assert_off_is_off(fresh, used, CH.planted_db(fresh, rng, img), img, bp, lambda e: e.set_clahe(None),
+                                  lambda e: e.get_clahe() is None, on=lambda e: e.set_clahe(*SETTING))
+        used.set_clahe(0.0, (0, 0))                                           # the other way of saying off
+        assert used.get_clahe() is None
+        assert CH.tick_record(used, img, bp).tobytes() == a.tobytes()
 
 
 def test_batched_tick_with_clahe_equals_single_ticks(gold):
     from nclt_slam_project_amd import landmarks as LM
     scene = synth.WallScene()
-    es = [Engine(0, 640, 480, 4096) for _ in range(2)]
-    fdev = []
-    try:
+    with CH.engines(2) as rig:
+        es = rig.es
         data = _teach_clahe(Cv2Shim(es[0]), scene, gold)
         es[0].db_upload(*LM.pack_landmarks(data["landmarks"]))
-        es[1].db_share(es[0])
-        es[1].set_stream(es[0].stream_ptr)
+        rig.share()
         for e in es:
             e.set_clahe(*SETTING)
         poses = [synth.base_pose(2.3, -0.2, -2.0), synth.base_pose(7.4, 0.1, 1.0)]
-        fdev = [es[0].to_device(scene.render(bp)[0]) for bp in poses]
-        keys = ("outcome", "n_inliers", "lm_idx", "n_candidates", "relocating", "n_features")
-        for mode in (True, False):
-            ref = []
-            for f, bp in enumerate(poses):
-                es[0].tick_dev(fdev[f], 640, 480, bp, global_reloc=mode, seed=7 + f)
-                ref.append(es[0].tick_result())
-            if mode:
-                assert any(r["outcome"] == 0 for r in ref)                      # published: the whole chain ran
-            Engine.tick_batch_dev(es, fdev, 640, 480, poses, global_reloc=mode, seeds=[7, 8])
-            for f, e in enumerate(es):
-                got = e.tick_result()
-                assert {k: got[k] for k in keys if k in got} == {k: ref[f][k] for k in keys if k in ref[f]}, (mode, f)
-                np.testing.assert_allclose(got["anchor_pose"], ref[f]["anchor_pose"], atol=1e-9)
+        fdev = [rig.to_device(scene.render(bp)[0]) for bp in poses]
+        CH.assert_batch_equals_single(es, fdev, 640, 480, poses)
         # unequal settings are refused, equal ones accepted again
-        es[1].set_clahe(3.0, (8, 8))
-        with pytest.raises(RelocError, match="CLAHE"):
-            Engine.tick_batch_dev(es, fdev, 640, 480, poses, global_reloc=True, seeds=[7, 8])
-        es[1].set_clahe(None)
-        with pytest.raises(RelocError, match="code -5"):
-            Engine.tick_batch_dev(es, fdev, 640, 480, poses, global_reloc=True, seeds=[7, 8])
-        es[1].set_clahe(*SETTING)
-        Engine.tick_batch_dev(es, fdev, 640, 480, poses, global_reloc=True, seeds=[7, 8])
-        es[0].sync()
-    finally:
-        es[0].sync()
-        for p in fdev:
-            es[0].dev_free(p)
-        for e in es[::-1]:
-            e.close()
+        CH.assert_batch_refusals(es, lambda: Engine.tick_batch_dev(es, fdev, 640, 480, poses, global_reloc=True, seeds=[7, 8]),
+                                 [(lambda: es[1].set_clahe(3.0, (8, 8)), "CLAHE"), (lambda: es[1].set_clahe(None), "code -5")],
+                                 lambda: es[1].set_clahe(*SETTING))
 
 
 def test_low_contrast_session_gains_features_and_anchors(gold):
@@ -266,34 +151,28 @@ def test_low_contrast_session_gains_features_and_anchors(gold):
     from nclt_slam_project_amd.recorder import LandmarkRecorderCore
     scene = synth.WallScene()
 
-    def squash(bgr):
-        return (96 + (bgr.astype(np.int32) * 32) // 256).astype(np.uint8)
+    def squashed(bp):
+        bgr, dep = scene.render(bp)
+        return (96 + (bgr.astype(np.int32) * 32) // 256).astype(np.uint8), dep
 
     out = {}
     for setting in (None, SETTING):
-        e = Engine(0, 640, 480, 4096)
-        try:
-            rec = LandmarkRecorderCore(cv2=Cv2Shim(e), clahe=setting)
-            for x in gold["teach_x"]:
-                bp = synth.base_pose(x, 0.0, 0.0)
-                bgr, dep = scene.render(bp)
-                rec.tick(squash(bgr), dep, bp, rgb_ts=x)
+        with CH.engines(1) as rig:
+            e, = rig.es
+            rec = CH.teach_wall(LandmarkRecorderCore(cv2=Cv2Shim(e), clahe=setting), gold["teach_x"], squashed)
             feats = pubs = 0
             if rec.landmarks:
                 fm = FusedLandmarkMatcher(rec.database(), engine=e, config=MatcherConfig(clahe=setting))
                 for i, (x, y, yaw) in enumerate(gold["repeat"]):
                     bp = synth.base_pose(x, y, yaw)
-                    o = fm.tick(squash(scene.render(bp)[0]), bp, ts=1000.0 + 0.5 * i)
+                    o = fm.tick(squashed(bp)[0], bp, ts=1000.0 + 0.5 * i)
                     pubs += o.published
             e.set_clahe(*((None,) if setting is None else setting))
-            dev = e.to_device(np.zeros((480, 640, 3), np.uint8))
+            dev = rig.to_device(np.zeros((480, 640, 3), np.uint8))
             for (x, y, yaw) in gold["repeat"]:
-                e.h2d(dev, squash(scene.render(synth.base_pose(x, y, yaw))[0]))
+                e.h2d(dev, squashed(synth.base_pose(x, y, yaw))[0])
                 feats += e.orb_frame_dev(dev, 640, 480)
-            e.dev_free(dev)
             out[setting] = (len(rec.landmarks), feats, pubs)
-        finally:
-            e.close()
     print("\nlow contrast (records, features, published):", out)
     assert out[SETTING][1] > out[None][1] and out[SETTING][2] > out[None][2]
     assert out[SETTING][0] == len(gold["teach_x"])

@@ -5,6 +5,7 @@ contexts of its own, so the session engine's camera is never touched."""
 import numpy as np
 import pytest
 
+import chain_harness as CH
 import distortion_ref as DR
 from nclt_slam_project_amd import RelocError, synth
 from nclt_slam_project_amd.engine import Engine
@@ -101,30 +102,13 @@ def test_zero_distortion_is_the_pinhole_path(eng):
     np.testing.assert_array_equal(ma, mb)
 
 
-def _tick_record(e, img, bp):
-    e.tick(img, bp, global_reloc=True, seed=1)
-    rec = np.zeros(96, np.uint8)
-    e.d2h(rec, e.tick_result_dev)
-    return rec
-
-
 def test_tick_with_zero_distortion_is_byte_identical():
     rng = np.random.default_rng(7)
     img = synth.textured_frame(rng, 640, 480)
-    es = [Engine(0, 640, 480, 4096) for _ in range(2)]
-    try:
-        feats = es[0].orb_detect_compute(es[0].gray(img), 500)
-        db = synth.descriptor_db(rng, 64, "ragged", feats["desc"], planted_records=(5, 40))
-        for e in es:
-            e.db_upload(*db)
-        es[1].set_distortion(np.zeros(5))
-        assert not es[1].get_distortion().any()
-        bp = synth.base_pose(10.0, 0.3, 2.0)
-        a, b = _tick_record(es[0], img, bp), _tick_record(es[1], img, bp)
-        assert a.tobytes() == b.tobytes()
-    finally:
-        for e in es:
-            e.close()
+    with CH.engines(2) as rig:
+        fresh, used = rig.es
+        CH.assert_off_is_off(fresh, used, CH.planted_db(fresh, rng, img), img, synth.base_pose(10.0, 0.3, 2.0),
+                             lambda e: e.set_distortion(np.zeros(5)), lambda e: not e.get_distortion().any())
 
 
 def test_set_distortion_rejects_unsupported_models(eng):
@@ -165,11 +149,7 @@ def test_record_frame_with_distortion(eng):
 def _teach(e, scene, dist):
     """the four teach records of the wall route, recorded on the device through `e` with the given distortion"""
     from nclt_slam_project_amd.recorder import LandmarkRecorderCore
-    rec = LandmarkRecorderCore(engine=e, dist=dist)
-    for x in (2.0, 4.5, 7.0, 9.5):
-        bp = synth.base_pose(x, 0.0, 0.0)
-        bgr, dep = scene.render(bp)
-        rec.tick(bgr, dep, bp, rgb_ts=x)
+    rec = CH.teach_wall(LandmarkRecorderCore(engine=e, dist=dist), (2.0, 4.5, 7.0, 9.5), scene.render)
     assert len(rec.landmarks) == 4
     return rec.database()
 
@@ -178,8 +158,8 @@ def _session(dist_scene, dist_pipeline, poses):
     """teach with the recorder on the device, repeat with the fused matcher; the anchor poses of the repeat ticks"""
     from nclt_slam_project_amd.matcher import FusedLandmarkMatcher, MatcherConfig
     scene = synth.WallScene(dist=dist_scene)
-    e = Engine(0, 640, 480, 4096)
-    try:
+    with CH.engines(1) as rig:
+        e, = rig.es
         data = _teach(e, scene, dist_pipeline)
         fm = FusedLandmarkMatcher(data, engine=e, config=MatcherConfig(dist=dist_pipeline))
         out = []
@@ -188,8 +168,6 @@ def _session(dist_scene, dist_pipeline, poses):
             o = fm.tick(scene.render(bp)[0], bp, ts=1000.0 + 0.5 * i)
             out.append(o.anchor_pose)
         return out
-    finally:
-        e.close()
 
 
 def test_end_to_end_distorted_camera():
@@ -230,25 +208,15 @@ def test_end_to_end_distorted_camera():
 def test_batch_refuses_contexts_with_different_distortion(eng):
     rng = np.random.default_rng(4)
     img = synth.textured_frame(rng, 640, 480)
-    es = [Engine(0, 640, 480, 4096) for _ in range(2)]
-    try:
-        feats = es[0].orb_detect_compute(es[0].gray(img), 500)
-        es[0].db_upload(*synth.descriptor_db(rng, 32, "ragged", feats["desc"], planted_records=(3,)))
-        es[1].db_share(es[0])
-        es[1].set_stream(es[0].stream_ptr)
-        es[1].set_distortion(D_BARREL)
-        fdev = [es[0].to_device(img), es[0].to_device(img)]
+    with CH.engines(2) as rig:
+        es = rig.es
+        es[0].db_upload(*CH.planted_db(es[0], rng, img, 32, (3,)))
+        rig.share()
+        fdev = [rig.to_device(img), rig.to_device(img)]
         bps = [synth.base_pose(6.0, 0.0, 0.0)] * 2
-        with pytest.raises(RelocError, match="lens distortion"):
-            Engine.tick_batch_dev(es, fdev, 640, 480, bps, global_reloc=True, seeds=[1, 2])
-        es[1].set_distortion(())                                            # equal again: accepted
-        Engine.tick_batch_dev(es, fdev, 640, 480, bps, global_reloc=True, seeds=[1, 2])
-        es[0].sync()
-        for p in fdev:
-            es[0].dev_free(p)
-    finally:
-        for e in es[::-1]:
-            e.close()
+        CH.assert_batch_refusals(es, lambda: Engine.tick_batch_dev(es, fdev, 640, 480, bps, global_reloc=True, seeds=[1, 2]),
+                                 [(lambda: es[1].set_distortion(D_BARREL), "lens distortion")],
+                                 lambda: es[1].set_distortion(()))                  # equal again: accepted
 
 
 def test_batched_tick_with_distortion_equals_single_ticks():
@@ -256,34 +224,16 @@ def test_batched_tick_with_distortion_equals_single_ticks():
     its own reloc_tick_dev (k_pnp_*<true>)"""
     from nclt_slam_project_amd import landmarks as LM
     scene = synth.WallScene(dist=D_MODERATE)
-    es = [Engine(0, 640, 480, 4096) for _ in range(2)]
-    fdev = []
-    try:
+    with CH.engines(2) as rig:
+        es = rig.es
         data = _teach(es[0], scene, D_MODERATE)
         es[0].db_upload(*LM.pack_landmarks(data["landmarks"]))
-        es[1].db_share(es[0])
-        es[1].set_stream(es[0].stream_ptr)
+        rig.share()
         for e in es:
             e.set_distortion(D_MODERATE)
         poses = [synth.base_pose(2.3, -0.2, -2.0), synth.base_pose(7.4, 0.1, 1.0)]
-        fdev = [es[0].to_device(scene.render(bp)[0]) for bp in poses]
-        ref = []
-        for f, bp in enumerate(poses):
-            es[0].tick_dev(fdev[f], 640, 480, bp, global_reloc=True, seed=7 + f)
-            ref.append(es[0].tick_result())
-        assert all(r["outcome"] == 0 for r in ref)                          # published: the refinement ran
-        Engine.tick_batch_dev(es, fdev, 640, 480, poses, global_reloc=True, seeds=[7, 8])
-        keys = ("outcome", "n_inliers", "lm_idx", "n_candidates", "relocating")
-        for f, e in enumerate(es):
-            got = e.tick_result()
-            assert {k: got[k] for k in keys} == {k: ref[f][k] for k in keys}, f
-            np.testing.assert_allclose(got["anchor_pose"], ref[f]["anchor_pose"], atol=1e-9)
-    finally:
-        es[0].sync()
-        for p in fdev:
-            es[0].dev_free(p)
-        for e in es[::-1]:
-            e.close()
+        fdev = [rig.to_device(scene.render(bp)[0]) for bp in poses]
+        CH.assert_batch_equals_single(es, fdev, 640, 480, poses, modes=(True,), published=all)   # published: the refinement ran
 
 
 def test_accumulation_with_distortion_host_and_fused_agree():
@@ -293,8 +243,8 @@ def test_accumulation_with_distortion_host_and_fused_agree():
     from nclt_slam_project_amd.cv2_shim import Cv2Shim
     from nclt_slam_project_amd.matcher import FusedLandmarkMatcher, LandmarkMatcherCore, MatcherConfig
     scene = synth.WallScene(dist=D_MODERATE)
-    es = [Engine(0, 640, 480, 4096) for _ in range(2)]
-    try:
+    with CH.engines(2) as rig:
+        es = rig.es
         data = _teach(es[0], scene, D_MODERATE)
         bp = synth.base_pose(9.5, -14.0, 0.0)                               # no candidate within 8 m
         bgr, dep = scene.render(bp)
@@ -319,6 +269,3 @@ def test_accumulation_with_distortion_host_and_fused_agree():
         for got in (f, h):
             ulp = np.abs(got["keypoints_3d_cam"][:, :2].view(np.int32).astype(np.int64) - exp.view(np.int32).astype(np.int64))
             assert ulp.max() <= 1
-    finally:
-        for e in es:
-            e.close()

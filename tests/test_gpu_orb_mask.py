@@ -3,6 +3,7 @@ per-call and the persistent mask, and the fused entry points, bit for bit agains
 import numpy as np
 import pytest
 
+import chain_harness as CH
 import orb_mask_ref as MR
 import record_ref as RR
 from nclt_slam_project_amd import synth
@@ -168,45 +169,25 @@ def test_per_call_mask_leaves_the_persistent_one_alone(engine, oracle):
         engine.set_orb_mask(None)
 
 
-def _tick_record(e, img, bp, mode=True):
-    e.tick(img, bp, global_reloc=mode, seed=1)
-    rec = np.zeros(96, np.uint8)
-    e.d2h(rec, e.tick_result_dev)
-    return rec
-
-
 def test_off_is_off():
     """set_orb_mask(None) after use, and a fresh engine: features and tick record of an engine that never had a mask"""
     rng = np.random.default_rng(7)
     img = synth.textured_frame(rng, 640, 480)
-    es = [Engine(0, 640, 480, 4096) for _ in range(2)]
-    try:
-        feats = es[0].orb_detect_compute(es[0].gray(img), 500)
+
+    def off(e):
+        e.orb_detect_compute(e.gray(img), 500, mask=MR.blocks(640, 480))
+        e.set_orb_mask(None)
+
+    with CH.engines(2) as rig:
+        fresh, used = rig.es
+        feats = fresh.orb_detect_compute(fresh.gray(img), 500)
         db = synth.descriptor_db(rng, 64, "ragged", feats["desc"], planted_records=(5, 40))
-        for e in es:
-            e.db_upload(*db)
-        bp = synth.base_pose(10.0, 0.3, 2.0)
-        es[1].set_orb_mask(MR.half_band(640, 480))
-        on = _tick_record(es[1], img, bp)
-        f_on = es[1].orb_features()
-        es[1].orb_detect_compute(es[1].gray(img), 500, mask=MR.blocks(640, 480))
-        es[1].set_orb_mask(None)
-        assert es[1].get_orb_mask() is None
-        a, b = _tick_record(es[0], img, bp), _tick_record(es[1], img, bp)
-        assert a.tobytes() == b.tobytes() and len(on) == 96
-        fa, fb = es[0].orb_features(), es[1].orb_features()
-        assert fa["n"] == fb["n"] == feats["n"]
-        np.testing.assert_array_equal(fa["desc"], fb["desc"])
-        np.testing.assert_array_equal(fa["xy"], fb["xy"])
-        np.testing.assert_array_equal(fa["desc"], feats["desc"])
-        for l in range(8):
-            np.testing.assert_array_equal(es[0].frame_debug_plane(2, l), es[1].frame_debug_plane(2, l))
-        assert f_on["n"] != fa["n"] or not np.array_equal(f_on["desc"], fa["desc"])
+        CH.assert_off_is_off(fresh, used, db, img, synth.base_pose(10.0, 0.3, 2.0), off,
+                             lambda e: e.get_orb_mask() is None, on=lambda e: e.set_orb_mask(MR.half_band(640, 480)),
+                             planes=[(2, l) for l in range(8)])
+        CH.assert_same_features(fresh, feats, 1)            # the unmasked tick left what detect-and-compute gives
         with pytest.raises(RelocError, match="code -5"):
-            es[0].orb_mask_level(0)                          # no masked frame yet
-    finally:
-        for e in es:
-            e.close()
+            fresh.orb_mask_level(0)                          # no masked frame yet
 
 
 def test_wrong_size_is_refused_and_the_chain_in_front_of_the_mask(oracle):
@@ -215,9 +196,9 @@ def test_wrong_size_is_refused_and_the_chain_in_front_of_the_mask(oracle):
     small = MR.half_band(320, 240)
     dep = RR.keeping_depth(seed, w, h)
     bp = synth.base_pose(10.0, 0.3, 2.0)
-    e = Engine(0, 640, 480, 4096)
-    dev = e.to_device(img)
-    try:
+    with CH.engines(1) as rig:
+        e, = rig.es
+        dev = rig.to_device(img)
         e.db_upload(*synth.descriptor_db(np.random.default_rng(1), 64, "ragged"))
         n0 = e.orb_frame_dev(dev, w, h)
         before = e.orb_features()
@@ -260,9 +241,6 @@ def test_wrong_size_is_refused_and_the_chain_in_front_of_the_mask(oracle):
         assert ref["n"] > 50
         _check_device_features(e, n, ref, "chain")
         _check_planes(e, ref, "chain")
-    finally:
-        e.dev_free(dev)
-        e.close()
 
 
 def test_tick_record_and_accumulate_under_a_mask(oracle):
@@ -271,8 +249,8 @@ def test_tick_record_and_accumulate_under_a_mask(oracle):
     mask, ref = _ref(oracle, seed, w, h, "half_band")
     ref_xy = {tuple(r) for r in ref["xy"].view(np.uint32).tolist()}
     rng = np.random.default_rng(3)
-    e = Engine(0, 640, 480, 4096)
-    try:
+    with CH.engines(1) as rig:
+        e, = rig.es
         db = synth.descriptor_db(rng, 64, "ragged", ref["desc"], planted_records=(5, 40))
         e.db_upload(*db)
         e.set_orb_mask(mask)
@@ -291,20 +269,15 @@ def test_tick_record_and_accumulate_under_a_mask(oracle):
         np.testing.assert_array_equal(rec["desc"], ref["desc"][rec["kp_index"]])
         # ... and so does the accumulation (far from every record, nothing published: a record is appended)
         far = (500.0, 500.0) + tuple(bp[2:])
-        img_dev, dep_dev = e.to_device(img), e.to_device(np.ascontiguousarray(dep, np.uint16))
-        try:
-            e.tick_dev(img_dev, w, h, far)
-            e.tick_accumulate_dev(dep_dev, w, h, far, True)
-            e.tick_result()
-            acc = e.accumulate_result()
-        finally:
-            e.dev_free(img_dev); e.dev_free(dep_dev)
+        img_dev, dep_dev = rig.to_device(img), rig.to_device(np.ascontiguousarray(dep, np.uint16))
+        e.tick_dev(img_dev, w, h, far)
+        e.tick_accumulate_dev(dep_dev, w, h, far, True)
+        e.tick_result()
+        acc = e.accumulate_result()
         assert acc["appended"] and acc["n_kpts"] >= 30 and e.db_records == 65
         new = e.db_fetch(64)
         rows = [tuple(r) for r in np.ascontiguousarray(new["keypoints_2d"]).view(np.uint32).tolist()]
         assert len(rows) == acc["n_kpts"] and all(r in ref_xy for r in rows)
-    finally:
-        e.close()
 
 
 def test_batched_tick_with_three_masks_and_mixed_batches(oracle):
@@ -313,46 +286,32 @@ def test_batched_tick_with_three_masks_and_mixed_batches(oracle):
     names = ("half_band", "blocks", "ramp")
     refs = [_ref(oracle, seed, w, h, n) for n in names]
     rng = np.random.default_rng(3)
-    es = [Engine(0, 640, 480, 4096) for _ in range(3)]
-    fdev = []
-    try:
+    with CH.engines(3) as rig:
+        es = rig.es
         db = synth.descriptor_db(rng, 64, "ragged", refs[0][1]["desc"], planted_records=(5, 40))
         es[0].db_upload(*db)
-        for e in es[1:]:
-            e.db_share(es[0])
-            e.set_stream(es[0].stream_ptr)
+        rig.share()
         for e, (mask, _) in zip(es, refs):
             e.set_orb_mask(mask)
         poses = [synth.base_pose(10.0, 0.3, 2.0), synth.base_pose(80.0, 0.2, 1.0), synth.base_pose(10.5, -0.3, -2.0)]
-        fdev = [es[0].to_device(img) for _ in es]
+        fdev = [rig.to_device(img) for _ in es]
         for mode in (True, False):
             single = []
             for f, e in enumerate(es):
                 e.tick_dev(fdev[f], w, h, poses[f], global_reloc=mode, seed=7 + f)
-                e.tick_result()
-                rec = np.zeros(96, np.uint8)
-                e.d2h(rec, e.tick_result_dev)
-                single.append(rec)
+                single.append(CH.device_record(e))
                 _check_device_features(e, refs[f][1]["n"], refs[f][1], f"single {names[f]}")
             Engine.tick_batch_dev(es, fdev, w, h, poses, global_reloc=mode, seeds=[7, 8, 9])
             for f, e in enumerate(es):
-                e.tick_result()
-                rec = np.zeros(96, np.uint8)
-                e.d2h(rec, e.tick_result_dev)
+                rec = CH.device_record(e)
                 print(f"mode {mode} frame {f}: single {single[f].view(np.int32)[16:22]} batch {rec.view(np.int32)[16:22]}")
                 _check_device_features(e, refs[f][1]["n"], refs[f][1], f"batch {names[f]}")
                 np.testing.assert_array_equal(e.frame_debug_plane(2, 0), refs[f][1]["nms"][0])
                 assert rec.tobytes() == single[f].tobytes(), (mode, f)
         # masked and unmasked contexts, or masks of unequal size, do not share a batch
-        es[1].set_orb_mask(None)
-        with pytest.raises(RelocError, match="code -5"):
-            Engine.tick_batch_dev(es, fdev, w, h, poses, global_reloc=True, seeds=[7, 8, 9])
-        es[1].set_orb_mask(MR.half_band(320, 240))
-        with pytest.raises(RelocError, match="code -5"):
-            Engine.tick_batch_dev(es, fdev, w, h, poses, global_reloc=True, seeds=[7, 8, 9])
-        es[1].set_orb_mask(refs[1][0])
-        Engine.tick_batch_dev(es, fdev, w, h, poses, global_reloc=True, seeds=[7, 8, 9])
-        es[0].sync()
+        CH.assert_batch_refusals(es, lambda: Engine.tick_batch_dev(es, fdev, w, h, poses, global_reloc=True, seeds=[7, 8, 9]),
+                                 [(lambda: es[1].set_orb_mask(None), "code -5"), (lambda: es[1].set_orb_mask(MR.half_band(320, 240)), "code -5")],
+                                 lambda: es[1].set_orb_mask(refs[1][0]))
         _check_device_features(es[1], refs[1][1]["n"], refs[1][1], "batch again")
         # all off: the unmasked batch
         for e in es:
@@ -362,9 +321,3 @@ def test_batched_tick_with_three_masks_and_mixed_batches(oracle):
         base = _ref(oracle, seed, w, h, "all255")[1]
         for e in es:
             _check_device_features(e, base["n"], base, "unmasked batch")
-    finally:
-        es[0].sync()
-        for p in fdev:
-            es[0].dev_free(p)
-        for e in es[::-1]:
-            e.close()

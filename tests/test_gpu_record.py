@@ -3,6 +3,7 @@ reference's recorder uses (R:247-288), bit for bit: kept keypoints, descriptors,
 import numpy as np
 import pytest
 
+from chain_harness import teach_wall
 from nclt_slam_project_amd import synth
 from nclt_slam_project_amd.recorder import LandmarkRecorderCore
 
@@ -50,11 +51,7 @@ def test_wall_scene_teach_on_device_matches_golden(engine):
     import json, os, zlib
     gold = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "tick_scene.json")))
     scene = synth.WallScene()
-    rec = LandmarkRecorderCore(engine=engine)
-    for x in gold["teach_x"]:
-        bp = synth.base_pose(x, 0.0, 0.0)
-        bgr, dep = scene.render(bp)
-        rec.tick(bgr, dep, bp, rgb_ts=x)
+    rec = teach_wall(LandmarkRecorderCore(engine=engine), gold["teach_x"], scene.render)
     assert len(rec.landmarks) == len(gold["records"])
     for lm, g in zip(rec.landmarks, gold["records"]):          # what the reference's recorder produced
         assert lm["n_features"] == g["n"]

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import chain_harness as CH
 import clahe_ref as CR
 import remap_ref as RR
 from nclt_slam_project_amd import RelocError, cv2_shim, synth
@@ -137,9 +138,9 @@ def test_orb_frame_dev_reads_the_rectified_plane(oracle, w, h):
     img = synth.textured_frame(rng, w, h)
     kk = np.array([[0.5 * w, 0, 0.5 * w], [0, 0.5 * w, 0.5 * h], [0, 0, 1.0]])
     maps = cv2_shim.initUndistortRectifyMap(kk, (-0.15, 0.02, 0.001, 0.0, 0.0), None, kk, (w, h), cv2_shim.CV_16SC2)
-    e = Engine(0, 700, 500, 4096)
-    try:
-        dev = e.to_device(img)
+    with CH.engines(1, 700, 500) as rig:
+        e, = rig.es
+        dev = rig.to_device(img)
         assert e.get_rectify() is None
         e.set_rectify(maps)
         assert e.get_rectify() == (w, h)
@@ -169,85 +170,32 @@ def test_orb_frame_dev_reads_the_rectified_plane(oracle, w, h):
         # a frame of another size is refused, never passed through unrectified
         with pytest.raises(RelocError, match="code -1"):
             e.orb_frame_dev(dev, w - 2, h, stride=3 * w)
-        e.sync()
-        e.dev_free(dev)
-    finally:
-        e.close()
 
 
 def test_record_frame_with_the_map_equals_the_cv2_path(maps640):
-    from nclt_slam_project_amd.recorder import LandmarkRecorderCore
     warp, rect = maps640
     scene = synth.WallScene()
-    es = [Engine(0, 640, 480, 4096) for _ in range(2)]
-    try:
-        dev = LandmarkRecorderCore(engine=es[0], rectify=rect)
-        assert es[0].get_rectify() == (640, 480)
-        host = LandmarkRecorderCore(cv2=Cv2Shim(es[1]), rectify=rect)
-        for x in (2.0, 4.5, 7.0):
-            bp = synth.base_pose(x, 0.0, 0.0)
-            bgr, dep = warped(scene, bp, warp)
-            a, b = dev.tick(bgr, dep, bp, x), host.tick(bgr, dep, bp, x)
-            assert a is not None and b is not None
-            assert a["n_features"] == b["n_features"] >= 30
-            for k in ("descriptors", "keypoints_2d", "keypoints_3d_cam"):
-                np.testing.assert_array_equal(a[k], b[k])
-        # and the map changed what was recorded: the plain recorder on the same frame files something else
-        bp = synth.base_pose(2.0, 0.0, 0.0)
-        bgr, dep = warped(scene, bp, warp)
-        plain = es[1].record_frame(bgr, dep)
-        assert plain["n"] != dev.landmarks[0]["n_features"] or not np.array_equal(plain["desc"], dev.landmarks[0]["descriptors"])
+    with CH.engines(2) as rig:
+        CH.assert_record_equals_cv2_path(rig.es, lambda bp: warped(scene, bp, warp), lambda e: e.get_rectify() == (640, 480), rectify=rect)
+        bgr, dep = warped(scene, synth.base_pose(2.0, 0.0, 0.0), warp)
         with pytest.raises(RelocError, match="code -1"):
-            es[0].record_frame(bgr[:400], dep[:400])
-    finally:
-        for e in es:
-            e.close()
+            rig.es[0].record_frame(bgr[:400], dep[:400])
 
 
 def _teach(cv2, scene, gold, warp, rect):
     from nclt_slam_project_amd.recorder import LandmarkRecorderCore
-    rec = LandmarkRecorderCore(cv2=cv2, rectify=rect)
-    for x in gold["teach_x"]:
-        bp = synth.base_pose(x, 0.0, 0.0)
-        rec.tick(*warped(scene, bp, warp), bp, rgb_ts=x)
-    return rec
+    return CH.teach_wall(LandmarkRecorderCore(cv2=cv2, rectify=rect), gold["teach_x"], lambda bp: warped(scene, bp, warp))
 
 
 def test_session_shim_and_fused_agree_with_the_map(gold, tmp_path, maps640):
-    from nclt_slam_project_amd.matcher import FusedLandmarkMatcher, LandmarkMatcherCore, MatcherConfig
+    from nclt_slam_project_amd.matcher import MatcherConfig
     warp, rect = maps640
     scene = synth.WallScene()
-    es = [Engine(0, 640, 480, 4096) for _ in range(2)]
-    try:
-        rec = _teach(Cv2Shim(es[0]), scene, gold, warp, rect)
+    with CH.engines(2) as rig:
+        rec = _teach(Cv2Shim(rig.es[0]), scene, gold, warp, rect)
         assert len(rec.landmarks) == len(gold["teach_x"])
-        data = rec.database()
-        cfg = MatcherConfig(rectify=rect)
-        csv_a, csv_b = str(tmp_path / "a.csv"), str(tmp_path / "b.csv")
-        core = LandmarkMatcherCore(data, csv_a, cv2=Cv2Shim(es[0]), config=cfg)
-        fm = FusedLandmarkMatcher(data, csv_b, engine=es[1], config=cfg)
-        assert es[1].get_rectify() == (640, 480)
-        pubs = 0
-        for i, (x, y, yaw) in enumerate(gold["repeat"]):
-            bp = synth.base_pose(x, y, yaw)
-            bgr, _ = warped(scene, bp, warp)
-            a = core.tick(bgr, None, bp, ts=1000.0 + 0.5 * i)              # no depth: neither matcher accumulates
-            b = fm.tick(bgr, bp, ts=1000.0 + 0.5 * i)
-            assert a.outcome == b.outcome and a.n_inliers == b.n_inliers and a.n_candidates == b.n_candidates, i
-            if a.anchor_pose:
-                assert np.abs(np.array(a.anchor_pose) - np.array(b.anchor_pose)).max() < 1e-4
-            pubs += a.published
-        ra, rb = open(csv_a).read().splitlines(), open(csv_b).read().splitlines()
-        assert len(ra) == len(rb) == len(gold["repeat"]) + 1 and ra[0] == rb[0]
-        for g, e in zip(ra[1:], rb[1:]):
-            gf, ef = g.split(","), e.split(",")
-            assert gf[:6] == ef[:6] and gf[8] == ef[8], (g, e)
-            for u, v in zip(gf[6:8], ef[6:8]):
-                assert (u == v == "") or abs(float(u) - float(v)) < 1e-4
-        assert pubs >= 3
-    finally:
-        for e in es:
-            e.close()
+        CH.assert_sessions_agree(rig.es, rec.database(), tmp_path, gold["repeat"], lambda bp: warped(scene, bp, warp),
+                                 MatcherConfig(rectify=rect), lambda e: e.get_rectify() == (640, 480))
 
 
 def test_accumulation_files_the_record_of_the_cv2_path(gold, maps640):
@@ -255,10 +203,9 @@ def test_accumulation_files_the_record_of_the_cv2_path(gold, maps640):
     from nclt_slam_project_amd.matcher import FusedLandmarkMatcher, LandmarkMatcherCore, MatcherConfig
     warp, rect = maps640
     scene = synth.WallScene()
-    es = [Engine(0, 640, 480, 4096) for _ in range(2)]
-    try:
+    with CH.engines(2) as rig:
+        es = rig.es
         data = _teach(Cv2Shim(es[0]), scene, gold, warp, rect).database()
-        n0 = len(data["landmarks"])
         cfg = MatcherConfig(rectify=rect)
         core = LandmarkMatcherCore({**data, "landmarks": list(data["landmarks"])}, cv2=Cv2Shim(es[0]), config=cfg)
         fm = FusedLandmarkMatcher({**data, "landmarks": list(data["landmarks"])}, engine=es[1], config=cfg)
@@ -268,52 +215,16 @@ def test_accumulation_files_the_record_of_the_cv2_path(gold, maps640):
             a = core.tick(bgr, dep, bp, ts=ts)
             b = fm.tick(bgr, bp, ts=ts, depth_mm=dep)
             assert a.outcome == b.outcome and a.n_inliers == b.n_inliers, ts
-        acc_a = [lm for lm in core.landmarks if lm.get("accumulated")]
-        acc_b = [lm for lm in fm.landmarks if lm.get("accumulated")]
-        assert len(acc_a) == len(acc_b) >= 1 and es[1].db_records == n0 + len(acc_b)
-        for la, lb in zip(acc_a, acc_b):
-            assert la["n_features"] == lb["n_features"]
-            np.testing.assert_allclose(la["pose"], lb["pose"], rtol=0, atol=1e-9)
-            for k in ("descriptors", "keypoints_2d", "keypoints_3d_cam"):
-                np.testing.assert_array_equal(np.asarray(la[k]), np.asarray(lb[k]))
-    finally:
-        for e in es:
-            e.close()
-
-
-def _tick_record(e, img, bp):
-    e.tick(img, bp, global_reloc=True, seed=1)
-    rec = np.zeros(96, np.uint8)
-    e.d2h(rec, e.tick_result_dev)
-    return rec
+        CH.assert_accumulated_equal(core, fm, len(data["landmarks"]), (es[1],), 1e-9)
 
 
 def test_map_turned_off_is_byte_identical_to_never_enabled(maps640):
     rng = np.random.default_rng(7)
     img = synth.textured_frame(rng, 640, 480)
-    es = [Engine(0, 640, 480, 4096) for _ in range(2)]
-    try:
-        feats = es[0].orb_detect_compute(es[0].gray(img), 500)
-        db = synth.descriptor_db(rng, 64, "ragged", feats["desc"], planted_records=(5, 40))
-        for e in es:
-            e.db_upload(*db)
-        bp = synth.base_pose(10.0, 0.3, 2.0)
-        es[1].set_rectify(maps640[1])
-        _tick_record(es[1], img, bp)
-        f_on = es[1].orb_features()
-        es[1].set_rectify(None)
-        assert es[1].get_rectify() is None
-        a, b = _tick_record(es[0], img, bp), _tick_record(es[1], img, bp)
-        assert a.tobytes() == b.tobytes()
-        fa, fb = es[0].orb_features(), es[1].orb_features()
-        assert fa["n"] == fb["n"]
-        for k in ("xy", "desc"):
-            np.testing.assert_array_equal(fa[k], fb[k])
-        np.testing.assert_array_equal(es[0].frame_debug_plane(0, 0), es[1].frame_debug_plane(0, 0))
-        assert f_on["n"] != fa["n"] or not np.array_equal(f_on["desc"], fa["desc"])
-    finally:
-        for e in es:
-            e.close()
+    with CH.engines(2) as rig:
+        fresh, used = rig.es
+        CH.assert_off_is_off(fresh, used, CH.planted_db(fresh, rng, img), img, synth.base_pose(10.0, 0.3, 2.0),
+                             lambda e: e.set_rectify(None), lambda e: e.get_rectify() is None, on=lambda e: e.set_rectify(maps640[1]))
 
 
 def test_batched_tick_with_maps_equals_single_ticks(gold, maps640):
@@ -323,48 +234,23 @@ def test_batched_tick_with_maps_equals_single_ticks(gold, maps640):
     rect2 = cv2_shim.initUndistortRectifyMap(K, (BARREL[0] * 0.9, 0.0, 0.001, 0.0, 0.0), None, K, (640, 480), cv2_shim.CV_16SC2)
     small = cv2_shim.initUndistortRectifyMap(K, BARREL, None, K, (636, 480), cv2_shim.CV_16SC2)
     scene = synth.WallScene()
-    es = [Engine(0, 640, 480, 4096) for _ in range(2)]
-    fdev = []
-    try:
+    with CH.engines(2) as rig:
+        es = rig.es
         data = _teach(Cv2Shim(es[0]), scene, gold, warp, rect).database()
         es[0].db_upload(*LM.pack_landmarks(data["landmarks"]))
-        es[1].db_share(es[0])
-        es[1].set_stream(es[0].stream_ptr)
+        rig.share()
         poses = [synth.base_pose(2.3, -0.2, -2.0), synth.base_pose(7.4, 0.1, 1.0)]
-        fdev = [es[0].to_device(warped(scene, bp, warp)[0]) for bp in poses]
-        keys = ("outcome", "n_inliers", "lm_idx", "n_candidates", "relocating", "n_features")
+        fdev = [rig.to_device(warped(scene, bp, warp)[0]) for bp in poses]
         for second in (rect, rect2):
-            for mode in (True, False):
-                ref = []
-                for f, bp in enumerate(poses):
-                    es[0].set_rectify(second if f else rect)
-                    es[0].tick_dev(fdev[f], 640, 480, bp, global_reloc=mode, seed=7 + f)
-                    ref.append(es[0].tick_result())
-                if mode:
-                    assert any(r["outcome"] == 0 for r in ref)                      # published: the whole chain ran
+            def batch_maps():
                 es[0].set_rectify(rect)
                 es[1].set_rectify(second)
-                Engine.tick_batch_dev(es, fdev, 640, 480, poses, global_reloc=mode, seeds=[7, 8])
-                for f, e in enumerate(es):
-                    got = e.tick_result()
-                    assert {k: got[k] for k in keys if k in got} == {k: ref[f][k] for k in keys if k in ref[f]}, (mode, f)
-                    np.testing.assert_allclose(got["anchor_pose"], ref[f]["anchor_pose"], atol=1e-9)
+            CH.assert_batch_equals_single(es, fdev, 640, 480, poses, before_single=lambda f: es[0].set_rectify(second if f else rect),
+                                          before_batch=batch_maps)
         # mixed on / off and unequal sizes are refused, equal ones accepted again
-        es[1].set_rectify(None)
-        with pytest.raises(RelocError, match="code -5"):
-            Engine.tick_batch_dev(es, fdev, 640, 480, poses, global_reloc=True, seeds=[7, 8])
-        es[1].set_rectify(small)
-        with pytest.raises(RelocError, match="rectification"):
-            Engine.tick_batch_dev(es, fdev, 640, 480, poses, global_reloc=True, seeds=[7, 8])
-        es[1].set_rectify(rect2)
-        Engine.tick_batch_dev(es, fdev, 640, 480, poses, global_reloc=True, seeds=[7, 8])
-        es[0].sync()
-    finally:
-        es[0].sync()
-        for p in fdev:
-            es[0].dev_free(p)
-        for e in es[::-1]:
-            e.close()
+        CH.assert_batch_refusals(es, lambda: Engine.tick_batch_dev(es, fdev, 640, 480, poses, global_reloc=True, seeds=[7, 8]),
+                                 [(lambda: es[1].set_rectify(None), "code -5"), (lambda: es[1].set_rectify(small), "rectification")],
+                                 lambda: es[1].set_rectify(rect2))
 
 
 def test_sharded_batch_of_rectifying_contexts(gold, maps640):
@@ -372,45 +258,29 @@ def test_sharded_batch_of_rectifying_contexts(gold, maps640):
     scans what single rectified frames give; a mixed batch is refused"""
     warp, rect = maps640
     scene = synth.WallScene()
-    es = [Engine(0, 640, 480, 4096) for _ in range(2)]
-    fdev = []
-    out = 0
-    try:
+    with CH.engines(2) as rig:
+        es = rig.es
         from nclt_slam_project_amd import landmarks as LM
         data = _teach(Cv2Shim(es[0]), scene, gold, warp, rect).database()
         es[0].db_upload(*LM.pack_landmarks(data["landmarks"]))
-        es[1].db_share(es[0])
-        es[1].set_stream(es[0].stream_ptr)
+        rig.share()
         poses = [synth.base_pose(2.3, -0.2, -2.0), synth.base_pose(7.4, 0.1, 1.0)]
-        fdev = [es[0].to_device(warped(scene, bp, warp)[0]) for bp in poses]
+        fdev = [rig.to_device(warped(scene, bp, warp)[0]) for bp in poses]
         k = 4
-        out = es[0].dev_alloc(2 * (8 * k + 64))
+        out = rig.dev_alloc(2 * (8 * k + 64))
         for e in es:
             e.set_rectify(rect)
         Engine.shard_scan_batch_dev(es, fdev, 640, 480, poses, k, 0, out)
         es[0].sync()
         for f, e in enumerate(es):
-            n_batch = e.orb_features()
-            single = Engine(0, 640, 480, 4096)
-            try:
+            with CH.engines(1) as one:
+                single, = one.es
                 single.set_rectify(rect)
                 single.orb_frame_dev(fdev[f], 640, 480)
-                ref = single.orb_features()
-            finally:
-                single.close()
-            assert n_batch["n"] == ref["n"] > 100
-            np.testing.assert_array_equal(n_batch["desc"], ref["desc"])
+                CH.assert_same_features(e, single, min_n=101)
         es[1].set_rectify(None)
         with pytest.raises(RelocError, match="code -5"):
             Engine.shard_scan_batch_dev(es, fdev, 640, 480, poses, k, 0, out)
-    finally:
-        es[0].sync()
-        for p in fdev:
-            es[0].dev_free(p)
-        if out:
-            es[0].dev_free(out)
-        for e in es[::-1]:
-            e.close()
 
 
 def test_barrel_session_gains_anchors_with_the_map(gold, maps640):
@@ -422,8 +292,8 @@ def test_barrel_session_gains_anchors_with_the_map(gold, maps640):
     scene = synth.WallScene()
     out = {}
     for maps in (None, rect):
-        e = Engine(0, 640, 480, 4096)
-        try:
+        with CH.engines(1) as rig:
+            e, = rig.es
             rec = _teach(Cv2Shim(e), scene, gold, warp, maps)
             feats = pubs = 0
             if rec.landmarks:
@@ -434,8 +304,6 @@ def test_barrel_session_gains_anchors_with_the_map(gold, maps640):
                     pubs += o.published
                     feats += e.orb_features()["n"]
             out[maps is not None] = (len(rec.landmarks), feats, pubs)
-        finally:
-            e.close()
     print("\nbarrel session (records, features, published) without / with the map:", out[False], out[True])
     assert out[True][2] >= 1 and out[True][2] > out[False][2]
 

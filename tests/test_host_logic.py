@@ -8,6 +8,7 @@ import pickle
 import numpy as np
 import pytest
 
+from chain_harness import teach_wall
 from nclt_slam_project_amd import landmarks as LM
 from nclt_slam_project_amd import pose as P
 from nclt_slam_project_amd import synth
@@ -75,12 +76,7 @@ def scene():
 
 
 def _teach(cv2, scene, gold):
-    rec = LandmarkRecorderCore(cv2=cv2)
-    for x in gold["teach_x"]:
-        bp = synth.base_pose(x, 0.0, 0.0)
-        bgr, dep = scene.render(bp)
-        rec.tick(bgr, dep, bp, rgb_ts=x)
-    return rec
+    return teach_wall(LandmarkRecorderCore(cv2=cv2), gold["teach_x"], scene.render)
 
 
 def test_recorder_and_matcher_reproduce_reference_rows(oracle, gold, scene, tmp_path):

@@ -65,14 +65,10 @@ def _database():
     from nclt_slam_project_amd import synth
     from nclt_slam_project_amd.recorder import LandmarkRecorderCore
     from nclt_slam_project_amd import landmarks as LM
+    from chain_harness import teach_wall
     from oracle_backend import oracle_cv2
     scene = synth.WallScene()
-    rec = LandmarkRecorderCore(cv2=oracle_cv2())
-    for x in (2.0, 4.5, 7.0, 9.5):
-        bp = synth.base_pose(x, 0.0, 0.0)
-        bgr, dep = scene.render(bp)
-        rec.tick(bgr, dep, bp, x)
-    data = rec.database()
+    data = teach_wall(LandmarkRecorderCore(cv2=oracle_cv2()), (2.0, 4.5, 7.0, 9.5), scene.render).database()
     # pad with random records so the shards are not trivially small and the merge has to interleave
     rng = np.random.default_rng(3)
     desc, pts, off, poses = synth.descriptor_db(rng, 8, "ragged")
