@@ -25,49 +25,11 @@ RELOC_API int reloc_device_count(void)
 
 static int ctx_alloc(reloc_ctx *c)
 {
-    int rc = 0;
-    const int64_t mf = c->max_feat;
-    // pyramid geometry upper bound: sum over levels of stride*h with stride <= w+64 rounded
-    int64_t pyr = 0;
-    for (int l = 0; l < NLEV; ++l) {
-        double s = pow(RELOC_ORB_SCALE_FACTOR, (double)l);
-        int64_t w = (int64_t)(c->max_w / s) + 2, h = (int64_t)(c->max_h / s) + 2;
-        pyr += ((w + 63) / 64 * 64) * h + 256;
-    }
-    c->pyr_bytes = pyr;
-    for (uint8_t **p : {&c->pyr, &c->blur, &c->nms}) rc |= ctx_dev_alloc(c, p, pyr);
-    rc |= ctx_dev_alloc(c, &c->rz_tab, (int64_t)NLEV * 2 * 2 * (c->max_w > c->max_h ? c->max_w : c->max_h));
-    rc |= ctx_dev_alloc(c, (char **)&c->pyr_tiles, (int64_t)((c->max_w + 15) / 16) * ((c->max_h + 15) / 16) * 128);   // >= any k_pyramid tiling
-    rc |= ctx_dev_alloc(c, &c->hist, NLEV * 256);
-    for (int32_t **p : {&c->cand_cnt, &c->kp_cnt, &c->dbg_cut}) rc |= ctx_dev_alloc(c, p, NLEV);
-    for (uint32_t **p : {&c->cand_key, &c->kp_key}) rc |= ctx_dev_alloc(c, p, (int64_t)NLEV * RELOC_ORB_STAGE1_CAP);
-    for (float **p : {&c->cand_resp, &c->kp_resp}) rc |= ctx_dev_alloc(c, p, (int64_t)NLEV * RELOC_ORB_STAGE1_CAP);
-    rc |= ctx_dev_alloc(c, &c->f_xy, mf * 2);
-    for (float **p : {&c->f_size, &c->f_angle, &c->f_resp}) rc |= ctx_dev_alloc(c, p, mf);
-    rc |= ctx_dev_alloc(c, &c->f_oct, mf);
-    rc |= ctx_dev_alloc(c, &c->f_desc, mf * 32);
-    rc |= ctx_dev_alloc(c, &c->f_count, 1);
+    int rc = orb_alloc(c);
+    rc |= scan_alloc(c);
+    rc |= tick_alloc(c);
     rc |= ctx_dev_alloc(c, &c->frame_img, (int64_t)c->max_w * c->max_h * 3);
-    rc |= ctx_dev_alloc(c, (char **)&c->orb_const, 1024);
-    rc |= ctx_dev_alloc(c, &c->cand_ids, MAX_CAND);
-    rc |= ctx_dev_alloc(c, &c->cand_n, 1);
-    for (int32_t **p : {&c->m_qidx, &c->m_tidx, &c->m_dist, &c->p_inl}) rc |= ctx_dev_alloc(c, p, (int64_t)MAX_CAND * MAX_REC_ROWS);
-    rc |= ctx_dev_alloc(c, &c->m_n, MAX_CAND);
-    rc |= ctx_dev_alloc(c, &c->p_obj, (int64_t)MAX_CAND * MAX_REC_ROWS * 3);
-    rc |= ctx_dev_alloc(c, &c->p_img, (int64_t)MAX_CAND * MAX_REC_ROWS * 2);
-    rc |= ctx_dev_alloc(c, &c->p_Rt, (int64_t)MAX_CAND * MAX_HYP * 12);
-    rc |= ctx_dev_alloc(c, &c->p_cnt, (int64_t)MAX_CAND * MAX_HYP);
-    rc |= ctx_dev_alloc(c, &c->p_out, MAX_CAND);
-    rc |= ctx_dev_alloc(c, &c->tick_res, 1);
-    if (hipHostMalloc((void **)&c->tick_res_host, sizeof(TickResult), hipHostMallocDefault) != hipSuccess) {
-        reloc_set_error("hipHostMalloc(result record) failed");
-        c->tick_res_host = nullptr;
-        rc |= RELOC_E_HIP;
-    } else memset(c->tick_res_host, 0, sizeof(TickResult));
     rc |= ctx_dev_alloc(c, &c->accum_res, 1);
-    rc |= ctx_dev_alloc(c, &c->tick_flags, 4);
-    rc |= ctx_dev_alloc(c, &c->scan_ticket, (8 * 8 + 1) * 32);
-    if (rc == 0 && hipMemset(c->scan_ticket, 0, (8 * 8 + 1) * 32 * 4) != hipSuccess) rc = RELOC_E_HIP;
     return rc;
 }
 
@@ -147,7 +109,7 @@ RELOC_API void reloc_destroy(reloc_ctx *c)
     for (DbArena &db : c->db_slot) db_arena_release(db);      // owner or adopter alike: one reference each
     for (void *p : c->dev_blocks) (void)hipFree(p);
     for (void *p : c->scratch) if (p) (void)hipFree(p);
-    if (c->tick_res_host) (void)hipHostFree(c->tick_res_host);
+    tick_release(c);
     for (int k = 0; k < RELOC_PROF_N; ++k)
         if (c->prof[k].init)
             for (int i = 0; i < RELOC_PROF_RING; ++i) {

@@ -9,6 +9,7 @@
 
 #include "../../include/reloc.h"
 #include "../../include/reloc_spec.h"
+#include "reloc_orb_plan.h"
 
 #define RELOC_API extern "C" __attribute__((visibility("default")))
 #define RELOC_PROF_RING 256      /* event pairs per stopwatch before reloc_prof_begin has to wait for the device */
@@ -44,7 +45,6 @@ void reloc_set_error(const char *fmt, ...);
         (void)hipSetDevice((c)->device);                      \
     } while (0)
 
-constexpr int NLEV = RELOC_ORB_NLEVELS;
 constexpr int MAX_REC_ROWS = 4096;   // largest record (teach rows) the fused scan accepts
 constexpr int MAX_CAND = 32;         // PnP candidates per tick (5 local / 25 global)
 constexpr int MAX_HYP = 1024;        // RANSAC hypotheses per candidate (iterationsCount)
@@ -77,14 +77,6 @@ constexpr int64_t MAX_DB_RECORDS = 0xFFFFF;   // the local-candidate key keeps t
 #define RELOC_SMALL_PRIO 3
 #endif
 #define RELOC_SMALL_KERNEL_PRIO() __builtin_amdgcn_s_setprio(RELOC_SMALL_PRIO)
-
-struct OrbLevel {
-    int w, h;          // level size
-    int stride;        // row stride in bytes (multiple of 64)
-    int64_t off;       // byte offset of the level inside a pyramid buffer
-    float scale;
-    int quota;
-};
 
 // Result record of one tick (device resident, copied out by reloc_tick_result)
 struct TickResult {
@@ -341,13 +333,62 @@ struct ClaheStage {
 // ORB's detection mask on the working frame of the image chain (reloc_set_orb_mask); 0 x 0 = off, the default
 struct OrbMaskStage {
     int w = 0, h = 0;                    // the persistent mask = working-frame size
-    uint8_t *pyr = nullptr;              // its mask pyramid, geometry of ctx->pyr; level 0 is the mask as given
+    uint8_t *pyr = nullptr;              // its mask pyramid, geometry of orb.buf.pyr; level 0 is the mask as given
     uint8_t *call = nullptr;             // the same for the mask of one reloc_orb_detect_compute_masked call
     bool built = false;                  // levels 1.. of pyr belong to the mask of level 0 (k_mask_level ran since it was set)
     const uint8_t *last = nullptr;       // the pyramid the last masked frame used, of last_w x last_h (reloc_orb_mask_level)
     int last_w = 0, last_h = 0;
     bool on() const { return w > 0; }
     bool same(const OrbMaskStage &o) const { return w == o.w && h == o.h; }      // the masks themselves may differ per context
+};
+
+// What the five ORB kernels read and write of one frame, in the form they take it: a single-frame launch passes the members
+// as arguments, a batched one up to 8 of these in its kernel arguments (OrbBatch, blockIdx.y = frame).
+struct OrbFrame {
+    const OrbTable *tab; const PyrTile *tiles; const int32_t *rz; const uint8_t *src;
+    uint8_t *pyr, *nms, *blur; int32_t *hist, *cand_cnt; uint32_t *cand_key; float *cand_resp; int32_t *dbg_cut;
+    int32_t *kp_cnt; uint32_t *kp_key; float *kp_resp; float *f_xy, *f_size, *f_angle, *f_resp; int32_t *f_oct; uint8_t *f_desc;
+    int32_t *f_count;
+    const uint8_t *mask;    // mask pyramid of the frame (geometry of pyr), read by the MASKED kernels only
+};
+static_assert(sizeof(OrbFrame) == 184, "OrbFrame travels in the kernel arguments of the batched ORB launches (DESIGN.md)");
+
+// ORB front end of a context (reloc_orb.hip): the blocks orb_alloc sized for the context's capacity and the geometry of the
+// frame size orb_prepare last published.
+struct OrbState {
+    int w = 0, h = 0, nfeat = 0;   // the geometry tab, lds and the device tables were built for; w == 0: none
+    OrbTable tab = {};             // host copy of the device table buf.tab
+    PyrLds lds = {};               // LDS layout of k_pyramid, its workgroups and its dynamic LDS
+    int ntiles = 0, lds_bytes = 0;
+    OrbCaps caps = {};             // bytes of each of buf.pyr / nms / blur (and of a mask pyramid), entries of buf.rz and buf.tiles
+    // Device blocks, as the kernels take them; src and mask stay NULL here, a launch sets them in its copy.  tab, tiles, rz:
+    // the tables of the geometry above.  pyr, blur, nms: pyramid levels, blurred levels and NMS-kept FAST score maps
+    // (stage-1 source, parity tap), one geometry.  hist: NLEV x 256 score histograms.  cand_*: stage-1 lists (NLEV counters,
+    // NLEV x STAGE1_CAP keys y << 16 | x and Harris responses).  kp_*: the kept keypoints in raster order per level.  dbg_cut:
+    // NLEV stage-1 cut scores of the last frame.  f_*: the frame's features, max_feat rows, and their count.
+    OrbFrame buf = {};
+    OrbMaskStage mask;             // detection mask between NMS and the stage-1 cut; both pyramids are one block, taken on first use
+};
+
+// Tick, match and PnP scratch of a context (allocated and released by reloc_tick.hip); every pointer is device memory
+// except res_host / res_ext.
+struct TickState {
+    int32_t *cand_ids = nullptr;     // MAX_CAND candidate records of the current tick
+    int32_t *cand_n = nullptr;       // 1
+    int32_t *flags = nullptr;        // [0] relocating: the candidates came from the whole-database search
+    int32_t *m_qidx = nullptr, *m_tidx = nullptr, *m_dist = nullptr;    // MAX_CAND x MAX_REC_ROWS match lists of the emit pass
+    int32_t *m_n = nullptr;          // MAX_CAND list lengths
+    float *p_obj = nullptr, *p_img = nullptr;     // MAX_CAND x MAX_REC_ROWS x {3, 2}: the 3-D / 2-D pairs PnP is given
+    double *p_Rt = nullptr;          // MAX_CAND x MAX_HYP x 12
+    int32_t *p_cnt = nullptr;        // MAX_CAND x MAX_HYP
+    int32_t *p_inl = nullptr;        // MAX_CAND x MAX_REC_ROWS
+    PnpOut *p_out = nullptr;         // MAX_CAND
+    TickResult *res = nullptr;       // 1: the result record on the device
+    TickResult *res_host = nullptr;  // the same record in pinned host memory, written by k_tick_finalize
+    TickResult *res_ext = nullptr;   // caller's pinned record for the next ticks (reloc_tick_result_to), or NULL
+    bool failed = false;             // the last tick entry point on this context returned an error before its result record was
+                                     // enqueued: reloc_tick_wait / reloc_tick_result* report RELOC_E_STATE instead of the previous tick's record
+    int32_t seq = 0;                 // stamp of the last tick enqueued (TickResult.pad[0] of its host records); 0: none yet
 };
 
 struct reloc_ctx {
@@ -369,33 +410,9 @@ struct reloc_ctx {
     void *scratch[8] = {};
     int64_t scratch_bytes[8] = {};
 
-    // ---- ORB state ----
-    int orb_w = 0, orb_h = 0, orb_nfeat = 0;     // geometry the tables below were built for
-    OrbLevel lev[NLEV];
-    int64_t pyr_bytes = 0;
-    uint8_t *pyr = nullptr;        // pyramid levels
-    uint8_t *blur = nullptr;       // blurred levels
-    uint8_t *nms = nullptr;        // NMS-kept FAST score maps (stage-1 source, parity tap)
-    int32_t *rz_tab = nullptr;     // resize tables (device)
-    void *pyr_tiles = nullptr;     // PyrTile per workgroup of k_pyramid (device)
-    int pyr_ntiles = 0, pyr_lds[NLEV + 1] = {}, pyr_lds_bytes = 0;   // LDS offsets of the level buffers, then the tables
-    int32_t *hist = nullptr;       // NLEV x 256 score histograms
-    int32_t *cand_cnt = nullptr;   // NLEV counters (stage-1 list sizes)
-    uint32_t *cand_key = nullptr;  // NLEV x STAGE1_CAP packed (y<<16|x)
-    float *cand_resp = nullptr;    // NLEV x STAGE1_CAP Harris responses
-    int32_t *kp_cnt = nullptr;     // NLEV kept counts
-    uint32_t *kp_key = nullptr;    // NLEV x STAGE1_CAP kept keypoints (raster order per level)
-    float *kp_resp = nullptr;
-    // frame feature outputs (max_feat rows)
-    float *f_xy = nullptr, *f_size = nullptr, *f_angle = nullptr, *f_resp = nullptr;
-    int32_t *f_oct = nullptr;
-    uint8_t *f_desc = nullptr;
-    int32_t *f_count = nullptr;
-    uint8_t *frame_img = nullptr;  // staging for host frames (max_w*max_h*3)
-    void *orb_const = nullptr;     // device copy of the OrbTable (reloc_orb.hip)
-    char orb_tab_host[1024];       // host copy of the same table
-    int32_t *dbg_cut = nullptr;    // NLEV stage-1 cut scores of the last frame
-    OrbMaskStage mask;             // detection mask between NMS and the stage-1 cut; both pyramids are one block, taken on first use
+    OrbState orb;                  // reloc_orb.hip
+    uint8_t *frame_img = nullptr;  // staging plane of the host-pointer entry points (image stages, recording, tick, ORB): the
+                                   // caller's frame on the device, max_w * max_h * 3 bytes; no ORB state
 
     CameraModel cam;
     // the image chain's stages in its order (reloc_image.hip); a stage's buffers are one block, taken on its first enable
@@ -405,32 +422,17 @@ struct reloc_ctx {
     reloc_params prm;
     int scan_gens = 0;               // RELOC_SCAN_GENS (developer switch), read once at creation: n > 0 = single whole-database
                                      // scans in the form of batched ones (n generations of row budgets + sweepers, launch_db_count)
-    uint32_t *scan_ticket = nullptr; // per frame of a batch (<= 8) 8 per-XCD record counters, then 1 exit counter, 128 bytes apart
+    uint32_t *scan_ticket = nullptr; // SCAN_TICKET_WORDS counters of the whole-database scans (scan_alloc, reloc_match.hip)
 
     // ---- database: two arenas; db_sel names the selected one (ctx_db below), reloc_db_select only changes db_sel ----
     DbArena db_slot[2];
     int db_sel = 0;
     AccumResult *accum_res = nullptr;   // 1
-    int32_t *tick_flags = nullptr;      // [0] relocating flag of the current tick
 
-    // ---- tick state ----
-    int32_t *cand_ids = nullptr;     // MAX_CAND
-    int32_t *cand_n = nullptr;       // 1
-    int32_t *m_qidx = nullptr, *m_tidx = nullptr, *m_dist = nullptr, *m_n = nullptr; // MAX_CAND x MAX_REC_ROWS
-    float *p_obj = nullptr, *p_img = nullptr;     // MAX_CAND x MAX_REC_ROWS x {3,2}
-    double *p_Rt = nullptr;          // MAX_CAND x MAX_HYP x 12
-    int32_t *p_cnt = nullptr;        // MAX_CAND x MAX_HYP
-    int32_t *p_inl = nullptr;        // MAX_CAND x MAX_REC_ROWS
-    PnpOut *p_out = nullptr;         // MAX_CAND
+    TickState tick;                  // reloc_tick.hip
     int exclusive_hint = -1;         // reloc_set_exclusive: 1 = this ctx is the only stream of work on the GPU, 0 = it is not,
                                      // -1 (default) = it is while it is the only live context of this process (ctx_alone())
     bool local_two_stage = false;    // developer switch RELOC_LOCAL_TWO_STAGE=1: local candidates by k_topk_part + k_candidates_local
-    TickResult *tick_res = nullptr;  // 1
-    TickResult *tick_res_host = nullptr;   // the same record in pinned host memory, written by k_tick_finalize
-    bool tick_failed = false;              // the last tick entry point on this context returned an error before its result record was
-                                           // enqueued: reloc_tick_wait / reloc_tick_result* report RELOC_E_STATE instead of the previous tick's record
-    int32_t tick_seq = 0;                  // stamp of the last tick enqueued (TickResult.pad[0] of its host records); 0: none yet
-    TickResult *tick_res_ext = nullptr;    // caller's pinned record for the next ticks (reloc_tick_result_to), or NULL
 };
 
 // The one allocation of a context's fixed device blocks: count elements of T (at least one), recorded for reloc_destroy
@@ -529,6 +531,13 @@ inline bool db_ready(const reloc_ctx *ctx)
     const DbArena &db = ctx_db(ctx);
     return db.desc && db.off && db.pose && db.xy_heading && db.counts && db.records > 0;
 }
+// the fixed blocks of a new context, each stage's by its own file: ORB (reloc_orb.hip), scan counters (reloc_match.hip), tick /
+// match / PnP scratch with the pinned result record (reloc_tick.hip; tick_release lets go of that record)
+int orb_alloc(reloc_ctx *ctx);
+int scan_alloc(reloc_ctx *ctx);
+int tick_alloc(reloc_ctx *ctx);
+void tick_release(reloc_ctx *ctx);
+// tables and tiles of a frame size on the device (cached: one geometry per context); a failure leaves no geometry
 int orb_prepare(reloc_ctx *ctx, int w, int h, int nfeatures);
 // ORB of frame f = srcs[f] into ctxs[f]'s feature buffers; channels == 3 -> the frames of the image chain: interleaved
 // 3-channel frames (gray fused), or raw mosaics of image_chain_frame_bpp = 1 byte per pixel with the Bayer stage on; the

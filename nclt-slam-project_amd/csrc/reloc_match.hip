@@ -413,6 +413,10 @@ __device__ __forceinline__ void db_emit_body(
 // A workgroup's FIRST record is dealt statically (record = workgroup index, no counter round trip in front of the first
 // row); the counters deal the records behind the grid.  Round 2's flow had six barriers per record and waited for an
 // atomic before the first row: 10 000 x 64 in three generations 162 -> [see DESIGN.md] us.
+// The ticket counters of a launch, one per 128-byte line: per frame (<= RELOC_BATCH_MAX) the 8 per-XCD record counters, then
+// one exit counter behind the last frame's; scan_alloc takes the largest pool a launch can use.
+constexpr int TICKET_STRIDE = 32;
+constexpr int SCAN_TICKET_WORDS = (RELOC_BATCH_MAX * 8 + 1) * TICKET_STRIDE;
 template <int NJ>
 __device__ __forceinline__ void db_count_body(
     u32 *lds, int C, const uint4 *__restrict__ db, const int64_t *__restrict__ off, const int32_t *__restrict__ rec_ids,
@@ -477,7 +481,6 @@ __device__ __forceinline__ void db_count_body(
     // there are 8, one per XCD (HW_REG_XCC_ID) on its own 128-byte line; a workgroup whose counter has run dry moves on to
     // the next one.  The draw for the next record is in flight while the current one is processed.  The last workgroup to
     // leave zeroes all words.
-    constexpr int TICKET_STRIDE = 32;
     int shard = 0, dry = 0;
     if (ticket) {
         u32 x;
@@ -610,8 +613,10 @@ struct EmitBatch { EmitFrame f[RELOC_BATCH_MAX]; };
 static EmitFrame emit_frame(const reloc_ctx *c)
 {
     EmitFrame F;
-    F.rec_ids = c->cand_ids; F.n_ids_p = c->cand_n; F.cur = (const uint4 *)c->f_desc; F.n_cur_p = c->f_count;
-    F.m_qidx = c->m_qidx; F.m_tidx = c->m_tidx; F.m_dist = c->m_dist; F.m_n = c->m_n; F.g_xy = c->f_xy; F.g_obj = c->p_obj; F.g_img = c->p_img;
+    const TickState &t = c->tick;
+    const OrbFrame &o = c->orb.buf;
+    F.rec_ids = t.cand_ids; F.n_ids_p = t.cand_n; F.cur = (const uint4 *)o.f_desc; F.n_cur_p = o.f_count;
+    F.m_qidx = t.m_qidx; F.m_tidx = t.m_tidx; F.m_dist = t.m_dist; F.m_n = t.m_n; F.g_xy = o.f_xy; F.g_obj = t.p_obj; F.g_img = t.p_img;
     return F;
 }
 
@@ -661,7 +666,7 @@ __global__ __launch_bounds__(256, 4) RELOC_SCAN_VGPR_ATTR void k_db_scan_batch(c
     mask.cos_tol = bt.cos_tol;
     mask.skip_if = bt.skip_if[f];
     const int C = bt.n_cur[f] ? min(*bt.n_cur[f], n_cur_max) : n_cur_max;
-    db_count_body<8>(lds, C, db, off, nullptr, nullptr, n_ids, bt.cur[f], max_rows, bt.counts[f], mask, ticket_pool + f * 8 * 32, quota,
+    db_count_body<8>(lds, C, db, off, nullptr, nullptr, n_ids, bt.cur[f], max_rows, bt.counts[f], mask, ticket_pool + f * 8 * TICKET_STRIDE, quota,
                      n_bounded, col_words, ticket_pool, bt.n, (int)(blockIdx.x / bt.n), (int)((gridDim.x + bt.n - 1 - f) / bt.n));
 }
 
@@ -1031,6 +1036,15 @@ struct CountPlan {
     }
 };
 
+// The counters of a context's whole-database scans (ctx->scan_ticket), zero whenever no scan is running: the last workgroup to
+// leave zeroes them again.
+int scan_alloc(reloc_ctx *ctx)
+{
+    if (int rc = ctx_dev_alloc(ctx, &ctx->scan_ticket, SCAN_TICKET_WORDS)) return rc;
+    HIP_TRY(hipMemset(ctx->scan_ticket, 0, SCAN_TICKET_WORDS * sizeof(uint32_t)));
+    return RELOC_OK;
+}
+
 // The whole-database scan of one frame.  Records are DRAWN from per-XCD ticket counters instead of dealt round-robin, so the
 // work stays balanced to the last record, by ONE resident generation of workgroups that draws until the counters are dry:
 // the fastest form alone (152 us where one generation with row budgets takes 177: static shares leave a tail) and, since the
@@ -1160,8 +1174,8 @@ int launch_db_scan_batch(reloc_ctx *const *ctxs, int n, const double *q, double 
     bt.xyh = heading_mask ? db.xy_heading : nullptr;
     bt.cos_tol = cos_tol;
     frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int g) {
-        bt.cur[f] = (const uint4 *)c->f_desc; bt.n_cur[f] = c->f_count; bt.counts[f] = ctx_db(c).counts;
-        bt.skip_if[f] = auto_mode ? c->cand_n : nullptr;
+        bt.cur[f] = (const uint4 *)c->orb.buf.f_desc; bt.n_cur[f] = c->orb.buf.f_count; bt.counts[f] = ctx_db(c).counts;
+        bt.skip_if[f] = auto_mode ? c->tick.cand_n : nullptr;
         for (int k = 0; k < 4; ++k) bt.q[f][k] = q[4 * g + k];
     });
     // `gens` generations in all (not per frame): a workgroup's budget grows with the batch, and with it the share of the

@@ -1,14 +1,16 @@
 // reloc_orb.hip -- ORB front end on gfx950: 8-level pyramid (gray conversion fused) -> FAST-9/16 + NMS ->
 // best-2n by FAST score -> Harris -> best-n -> intensity-centroid angle -> 7x7 blur -> steered
 // BRIEF-256.  Serves cv2.ORB_create(nfeatures).detectAndCompute(gray, None)        (reference M:306, R:241).
-// Holds the five ORB kernels with their batched twins, orb_prepare (tables and tiles of a frame size), orb_run and the ORB
-// entry points.  What happens to a frame before the pyramid is reloc_image.hip; the pixel helpers of both are reloc_pixels.h.
+// Holds the five ORB kernels with their batched twins, orb_alloc (the blocks of a context's OrbState, ctx->orb), orb_prepare
+// (uploads the plan of a frame size: reloc_orb_plan.h holds the level, table and tile types and the host arithmetic), orb_run
+// and the ORB entry points.  What happens to a frame before the pyramid is reloc_image.hip; the pixel helpers of both are
+// reloc_pixels.h.
 //
 // Everything is integer or strictly-ordered IEEE float arithmetic (no fused multiply-add, own
 // sin/cos) so results are bit-identical to the specification; the algorithm constants live in
 // include/reloc_spec.h.  Data layout in HBM: every pyramid level is a plane with a 64-byte-aligned
-// row stride inside one arena (ctx->pyr); the blurred pyramid (ctx->blur) and the NMS score maps
-// (ctx->nms) use the same geometry, so a level is addressed by one offset in all three.
+// row stride inside one arena (ctx->orb.buf.pyr); the blurred pyramid (buf.blur) and the NMS score maps
+// (buf.nms) use the same geometry, so a level is addressed by one offset in all three.
 //
 // The image chain feeds it through orb_run: image_chain_check, orb_prepare for the working frame, then image_chain_gray runs
 // the stages that are on and names the last plane written, which k_pyramid reads instead of the caller's frame.
@@ -33,7 +35,7 @@
 //   k_describe                           one wave per keypoint: moments by wave reduction, angle,
 //                                        256 steered tests -> 4 ballots = 32 descriptor bytes
 // A detection mask (include/reloc_spec.h "ORB MASK"; reloc_set_orb_mask, reloc_orb_detect_compute_masked) adds no launch per
-// frame: k_fast_blur<true> reads the frame's mask pyramid (geometry of ctx->pyr) where it writes the NMS map; k_mask_level
+// frame: k_fast_blur<true> reads the frame's mask pyramid (geometry of buf.pyr) where it writes the NMS map; k_mask_level
 // builds that pyramid once per mask, seven dependent launches in front of the first frame that uses it.
 // The per-frame HBM traffic is about 4 MB at 640x480; the stage is launch/latency-bound, not
 // bandwidth-bound.
@@ -43,16 +45,7 @@
 #include "reloc_internal.h"
 #include "reloc_pixels.h"
 
-constexpr int HARRIS_CHUNK = 1024;   // bytes of the NMS map per k_harris block (4 per thread)
 static_assert(HARRIS_CHUNK == 1024, "k_harris reads one dword per thread");
-
-struct OrbTable {
-    OrbLevel lev[NLEV];
-    int fast_tile_base[NLEV + 1];   // 32x32 tiles over (stride x h)
-    int blur_tile_base[NLEV + 1];   // 64x16 tiles over (w x h)
-    int flat_base[NLEV + 1];        // HARRIS_CHUNK-byte chunks over stride*h
-    int rz_off[NLEV][4];            // offsets into the resize table: xofs, xcoef, yofs, ycoef
-};
 
 __constant__ signed char c_pattern[RELOC_ORB_NTESTS * 4];
 __constant__ int c_umax[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
@@ -75,29 +68,12 @@ __device__ __forceinline__ int find_level(const int *base, int id)
 // each level that its rectangles of the levels above need as bilinear taps -- at most one extra
 // row/column per level, so about 2x recomputation at level 0 and less above.  Per pixel the arithmetic
 // is that of a plain per-level resize (same tables, same order), so the planes are bit-identical.  The rectangles and the
-// table slices are worked out by the host once per frame size (orb_prepare).
-#ifndef PYR_TW
-#define PYR_TW 64
-#define PYR_TH 32
-#endif
-constexpr int PT_W = PYR_TW, PT_H = PYR_TH;     // level-0 footprint of a tile
-struct PyrTile {
-    uint16_t o[NLEV][4];    // stored rectangle x0, x1, y0, y1 (x0 multiple of 4; x1 may reach into the row padding)
-    uint16_t n[NLEV][4];    // computed rectangle (x0 multiple of 4, x1 <= level width)
-};
-static_assert(sizeof(PyrTile) == 128, "PyrTile is read as 8 dwordx4");
-
-struct PyrLds { int lev[NLEV]; int tabs; };    // byte offsets of the level buffers and of the table slices in LDS
+// table slices are worked out by the host once per frame size (orb_plan; PyrTile, PyrLds and the tile size PT_W x PT_H:
+// reloc_orb_plan.h).
 
 // Frame-batched launches (reloc_tick_batch_dev, the sharded halves): the five ORB kernels of up to 8 contexts as FIVE
-// launches, blockIdx.y = frame.  Everything a kernel needs of one context travels in the kernel arguments.
-struct OrbFrame {
-    const OrbTable *tab; const PyrTile *tiles; const int32_t *rz; const uint8_t *src;
-    uint8_t *pyr, *nms, *blur; int32_t *hist, *cand_cnt; u32 *cand_key; float *cand_resp; int32_t *dbg_cut;
-    int32_t *kp_cnt; u32 *kp_key; float *kp_resp; float *f_xy, *f_size, *f_angle, *f_resp; int32_t *f_oct; uint8_t *f_desc;
-    int32_t *f_count;
-    const uint8_t *mask;    // mask pyramid of the frame (geometry of pyr), read by the MASKED kernels only
-};
+// launches, blockIdx.y = frame.  Everything a kernel needs of one context travels in the kernel arguments (OrbFrame,
+// reloc_internal.h).
 struct OrbBatch { OrbFrame f[RELOC_BATCH_MAX]; };
 
 // flat table index i -> positions of the (offset, coefficient) entries in the resize tables; the level is found
@@ -289,7 +265,6 @@ __device__ __forceinline__ u32 halo_dword(const uint8_t *__restrict__ row, int g
     return v;
 }
 
-constexpr int BT_W = 64, BT_H = 16;
 constexpr int BT_P = BT_W / 4 + 2;      // dwords per staged row: columns x0 - 4 .. x0 + BT_W + 3
 static_assert(BT_W == 64 && BT_H == 16, "blur7_tile maps 256 lanes to 16 rows x 16 dwords");
 __device__ __forceinline__ void blur7_tile(const OrbTable *__restrict__ tab, const uint8_t *__restrict__ pyr,
@@ -485,7 +460,6 @@ struct FastQuad {
     }
 };
 
-constexpr int FT = 32;
 constexpr int FT_P = FT / 4 + 3;       // dwords per staged row: columns x0 - 4 .. x0 + FT + 3, one of padding
 static_assert(FT == 32, "fast_nms_tile maps 256 lanes to 32 rows x 8 dwords");
 // MASKED: a kept corner whose byte of the mask pyramid (`mask`, geometry of pyr) is 0 enters neither the NMS map nor the
@@ -1061,163 +1035,69 @@ __global__ __launch_bounds__(256) void k_describe_batch(OrbBatch b, int max_feat
 }
 
 // ------------------------------------------------------------------------------------------------
-static void resize_axis(int src_n, int dst_n, int32_t *ofs, int32_t *coef)
+// The fixed blocks of a context's ORB state, sized for its capacity (orb_caps) and its feature rows
+int orb_alloc(reloc_ctx *ctx)
 {
-    const double scale = (double)src_n / (double)dst_n;
-    for (int d = 0; d < dst_n; ++d) {
-        double f = ((double)d + 0.5) * scale - 0.5;
-        int s = (int)floor(f);
-        double a = f - (double)s;
-        if (s < 0) { s = 0; a = 0.0; }
-        if (s >= src_n - 1) { s = src_n - 1; a = 0.0; }
-        ofs[d] = s;
-        coef[d] = (int32_t)lrint(a * (double)(1 << RELOC_RESIZE_COEF_BITS));
-    }
+    OrbState &o = ctx->orb;
+    OrbFrame &b = o.buf;
+    const int64_t mf = ctx->max_feat, s1 = (int64_t)NLEV * RELOC_ORB_STAGE1_CAP;
+    o.caps = orb_caps(ctx->max_w, ctx->max_h);
+    int rc = 0;
+    for (uint8_t **p : {&b.pyr, &b.blur, &b.nms}) rc |= ctx_dev_alloc(ctx, p, o.caps.pyr_bytes);
+    rc |= ctx_dev_alloc(ctx, &b.tab, 1);
+    rc |= ctx_dev_alloc(ctx, &b.rz, o.caps.rz_entries);
+    rc |= ctx_dev_alloc(ctx, &b.tiles, o.caps.tiles);
+    rc |= ctx_dev_alloc(ctx, &b.hist, NLEV * 256);
+    for (int32_t **p : {&b.cand_cnt, &b.kp_cnt, &b.dbg_cut}) rc |= ctx_dev_alloc(ctx, p, NLEV);
+    for (uint32_t **p : {&b.cand_key, &b.kp_key}) rc |= ctx_dev_alloc(ctx, p, s1);
+    for (float **p : {&b.cand_resp, &b.kp_resp}) rc |= ctx_dev_alloc(ctx, p, s1);
+    rc |= ctx_dev_alloc(ctx, &b.f_xy, mf * 2);
+    for (float **p : {&b.f_size, &b.f_angle, &b.f_resp}) rc |= ctx_dev_alloc(ctx, p, mf);
+    rc |= ctx_dev_alloc(ctx, &b.f_oct, mf);
+    rc |= ctx_dev_alloc(ctx, &b.f_desc, mf * 32);
+    rc |= ctx_dev_alloc(ctx, &b.f_count, 1);
+    return rc;
 }
 
 static bool g_pattern_uploaded[64] = {};
 
+// Capacity check, cache hit, plan, then the three tables go to the device with the cache key taken down: a failed upload
+// leaves a context without geometry (the next frame plans again), never one whose key names tables that were half replaced.
 int orb_prepare(reloc_ctx *ctx, int w, int h, int nfeatures)
 {
+    OrbState &o = ctx->orb;
     if (w > ctx->max_w || h > ctx->max_h) {
         reloc_set_error("frame %dx%d exceeds the ctx capacity %dx%d", w, h, ctx->max_w, ctx->max_h);
         return RELOC_E_CAPACITY;
     }
-    if (ctx->orb_w == w && ctx->orb_h == h && ctx->orb_nfeat == nfeatures) return RELOC_OK;
+    if (o.w == w && o.h == h && o.nfeat == nfeatures) return RELOC_OK;
     if (!g_pattern_uploaded[ctx->device & 63]) {
         HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(c_pattern), RELOC_ORB_PATTERN, sizeof(RELOC_ORB_PATTERN)));
         g_pattern_uploaded[ctx->device & 63] = true;
     }
-    OrbTable tab;
-    memset(&tab, 0, sizeof(tab));
-    int64_t off = 0;
-    for (int l = 0; l < NLEV; ++l) {
-        const float s = (float)pow(RELOC_ORB_SCALE_FACTOR, (double)l);
-        OrbLevel &L = tab.lev[l];
-        L.scale = s;
-        L.w = (int)lrintf((float)w / s);
-        L.h = (int)lrintf((float)h / s);
-        L.stride = (L.w + 63) / 64 * 64;
-        L.off = off;
-        off += ((int64_t)L.stride * L.h + 255) / 256 * 256;
-    }
-    if (off > ctx->pyr_bytes) { reloc_set_error("pyramid arena too small"); return RELOC_E_CAPACITY; }
-    {
-        const float factor = (float)(1.0 / RELOC_ORB_SCALE_FACTOR);
-        float nper = (float)(nfeatures * (1 - factor) / (1 - (float)pow((double)factor, (double)NLEV)));
-        int sum = 0;
-        for (int l = 0; l < NLEV - 1; ++l) {
-            tab.lev[l].quota = (int)lrintf(nper);
-            sum += tab.lev[l].quota;
-            nper *= factor;
-        }
-        tab.lev[NLEV - 1].quota = nfeatures - sum > 0 ? nfeatures - sum : 0;
-    }
-    for (int l = 0; l < NLEV; ++l) {
-        const OrbLevel &L = tab.lev[l];
-        tab.fast_tile_base[l + 1] = tab.fast_tile_base[l] + (L.stride / FT) * ((L.h + FT - 1) / FT);
-        tab.blur_tile_base[l + 1] = tab.blur_tile_base[l] + ((L.w + BT_W - 1) / BT_W) * ((L.h + BT_H - 1) / BT_H);
-        tab.flat_base[l + 1] = tab.flat_base[l] + (int)(((int64_t)L.stride * L.h + HARRIS_CHUNK - 1) / HARRIS_CHUNK);
-    }
-    // resize tables
-    const int maxdim = ctx->max_w > ctx->max_h ? ctx->max_w : ctx->max_h;
-    int32_t *host = (int32_t *)malloc(sizeof(int32_t) * (size_t)NLEV * 4 * maxdim);
-    int pos = 0;
-    for (int l = 1; l < NLEV; ++l) {
-        const OrbLevel &S = tab.lev[l - 1], &D = tab.lev[l];
-        tab.rz_off[l][0] = pos; tab.rz_off[l][1] = pos + D.w;
-        resize_axis(S.w, D.w, host + pos, host + pos + D.w);
-        pos += 2 * D.w;
-        tab.rz_off[l][2] = pos; tab.rz_off[l][3] = pos + D.h;
-        resize_axis(S.h, D.h, host + pos, host + pos + D.h);
-        pos += 2 * D.h;
-    }
-    // fused-pyramid tiles: every tile owns a rectangle of every level (proportional split, x on 4-pixel
-    // boundaries, the last column of tiles takes the row padding of levels >= 1, which is stored as 0)
-    // and computes what the levels above need from it (k_pyramid).
-    const int ntx = (w + PT_W - 1) / PT_W, nty = (h + PT_H - 1) / PT_H;
-    PyrTile *tiles = (PyrTile *)calloc((size_t)ntx * nty, sizeof(PyrTile));
-    int lds_lev[NLEV] = {}, lds_t = 0;
-    for (int t = 0; t < ntx * nty; ++t) {
-        const int tx = t % ntx, ty = t / ntx;
-        PyrTile &T = tiles[t];
-        int nx0 = 0, nx1 = 0, ny0 = 0, ny1 = 0;    // needed rectangle of the level above (empty)
-        int tsum = 0;
-        for (int l = NLEV - 1; l >= 0; --l) {
-            const OrbLevel &L = tab.lev[l];
-            const int quads = (l == 0 ? (L.w + 3) / 4 : L.stride / 4);
-            const int ox0 = 4 * (int)((int64_t)tx * quads / ntx), ox1 = 4 * (int)((int64_t)(tx + 1) * quads / ntx);
-            const int oy0 = (int)((int64_t)ty * L.h / nty), oy1 = (int)((int64_t)(ty + 1) * L.h / nty);
-            T.o[l][0] = (uint16_t)ox0; T.o[l][1] = (uint16_t)ox1; T.o[l][2] = (uint16_t)oy0; T.o[l][3] = (uint16_t)oy1;
-            // computed rectangle = own pixels (inside the image) united with the taps of the level above
-            int cx0 = ox0, cx1 = ox1 < L.w ? ox1 : L.w, cy0 = oy0, cy1 = oy1;
-            const bool stores = ox0 < ox1 && oy0 < oy1;                     // may be row padding only
-            const bool own = cx0 < cx1 && cy0 < cy1, need = nx0 < nx1 && ny0 < ny1;
-            if (need) {
-                const int32_t *xo = host + tab.rz_off[l + 1][0], *yo = host + tab.rz_off[l + 1][2];
-                int sx0 = xo[nx0], sx1 = xo[nx1 - 1] + 2, sy0 = yo[ny0], sy1 = yo[ny1 - 1] + 2;
-                if (sx1 > L.w) sx1 = L.w;
-                if (sy1 > L.h) sy1 = L.h;
-                if (own) {
-                    cx0 = cx0 < sx0 ? cx0 : sx0; cx1 = cx1 > sx1 ? cx1 : sx1;
-                    cy0 = cy0 < sy0 ? cy0 : sy0; cy1 = cy1 > sy1 ? cy1 : sy1;
-                } else {
-                    cx0 = sx0; cx1 = sx1; cy0 = sy0; cy1 = sy1;
-                }
-            } else if (!own) {
-                cx0 = cx1 = cy0 = cy1 = 0;
-            }
-            cx0 &= ~3;
-            T.n[l][0] = (uint16_t)cx0; T.n[l][1] = (uint16_t)cx1; T.n[l][2] = (uint16_t)cy0; T.n[l][3] = (uint16_t)cy1;
-            if (!stores) T.o[l][0] = T.o[l][1] = T.o[l][2] = T.o[l][3] = 0;
-            nx0 = cx0; nx1 = cx1; ny0 = cy0; ny1 = cy1;
-            const int bytes = ((cx1 - cx0 + 3) / 4 * 4) * (cy1 - cy0);
-            lds_lev[l] = bytes > lds_lev[l] ? bytes : lds_lev[l];
-            if (l >= 1) tsum += (cx1 - cx0) + (cy1 - cy0);
-        }
-        lds_t = tsum > lds_t ? tsum : lds_t;
-    }
-    ctx->pyr_ntiles = ntx * nty;
-    {
-        int o = 0;
-        for (int l = 0; l < NLEV; ++l) { ctx->pyr_lds[l] = o; o += (lds_lev[l] + 15) / 16 * 16; }
-        ctx->pyr_lds[NLEV] = o;
-        ctx->pyr_lds_bytes = o + 4 * lds_t;
-    }
-    if (ctx->pyr_lds_bytes > 64 * 1024) { free(host); free(tiles); reloc_set_error("pyramid tile exceeds LDS"); return RELOC_E_CAPACITY; }
-    hipError_t e0 = hipMemcpyAsync(ctx->pyr_tiles, tiles, sizeof(PyrTile) * (size_t)ntx * nty, hipMemcpyHostToDevice, ctx->stream);
-    hipError_t e1 = hipMemcpyAsync(ctx->rz_tab, host, sizeof(int32_t) * (size_t)pos, hipMemcpyHostToDevice, ctx->stream);
-    hipError_t e2 = hipMemcpyAsync(ctx->orb_const, &tab, sizeof(tab), hipMemcpyHostToDevice, ctx->stream);
-    hipError_t e3 = hipStreamSynchronize(ctx->stream);
-    free(host);
-    free(tiles);
+    const OrbPlan plan = orb_plan(w, h, nfeatures, o.caps);
+    if (plan.rc) { reloc_set_error("%s", plan.err); return plan.rc; }
+    o.w = o.h = o.nfeat = 0;
+    const hipError_t e0 = hipMemcpyAsync(const_cast<PyrTile *>(o.buf.tiles), plan.tiles.data(), sizeof(PyrTile) * plan.tiles.size(),
+                                         hipMemcpyHostToDevice, ctx->stream);
+    const hipError_t e1 = hipMemcpyAsync(const_cast<int32_t *>(o.buf.rz), plan.rz.data(), sizeof(int32_t) * plan.rz.size(),
+                                         hipMemcpyHostToDevice, ctx->stream);
+    const hipError_t e2 = hipMemcpyAsync(const_cast<OrbTable *>(o.buf.tab), &plan.tab, sizeof(OrbTable), hipMemcpyHostToDevice, ctx->stream);
+    const hipError_t e3 = hipStreamSynchronize(ctx->stream);      // the plan's arrays leave with this function
     HIP_TRY(e0); HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
-    memcpy(ctx->lev, tab.lev, sizeof(tab.lev));
-    memcpy(ctx->orb_tab_host, &tab, sizeof(tab));
-    ctx->orb_w = w; ctx->orb_h = h; ctx->orb_nfeat = nfeatures;
+    memcpy(&o.tab, &plan.tab, sizeof(OrbTable));
+    o.lds = plan.lds; o.lds_bytes = plan.lds_bytes; o.ntiles = (int)plan.tiles.size();
+    o.w = w; o.h = h; o.nfeat = nfeatures;
     return RELOC_OK;
-}
-
-// what the five ORB kernels read and write of a context, for the source frame src
-static OrbFrame orb_frame(const reloc_ctx *c, const uint8_t *src)
-{
-    OrbFrame F;
-    F.tab = (const OrbTable *)c->orb_const; F.tiles = (const PyrTile *)c->pyr_tiles; F.rz = c->rz_tab; F.src = src;
-    F.pyr = c->pyr; F.nms = c->nms; F.blur = c->blur; F.hist = c->hist; F.cand_cnt = c->cand_cnt; F.cand_key = c->cand_key;
-    F.cand_resp = c->cand_resp; F.dbg_cut = c->dbg_cut; F.kp_cnt = c->kp_cnt; F.kp_key = c->kp_key; F.kp_resp = c->kp_resp;
-    F.f_xy = c->f_xy; F.f_size = c->f_size; F.f_angle = c->f_angle; F.f_resp = c->f_resp; F.f_oct = c->f_oct; F.f_desc = c->f_desc;
-    F.f_count = c->f_count;
-    F.mask = nullptr;
-    return F;
 }
 
 // first use of a mask: both mask pyramids as one block
 static int mask_alloc(reloc_ctx *ctx)
 {
-    OrbMaskStage &m = ctx->mask;
+    OrbMaskStage &m = ctx->orb.mask;
     if (m.pyr) return RELOC_OK;
-    if (int rc = ctx_dev_alloc(ctx, &m.pyr, 2 * ctx->pyr_bytes)) return rc;
-    m.call = m.pyr + ctx->pyr_bytes;
+    if (int rc = ctx_dev_alloc(ctx, &m.pyr, 2 * ctx->orb.caps.pyr_bytes)) return rc;
+    m.call = m.pyr + ctx->orb.caps.pyr_bytes;
     return RELOC_OK;
 }
 
@@ -1225,10 +1105,9 @@ static int mask_alloc(reloc_ctx *ctx)
 static void mask_pyramid_launch(reloc_ctx *c, uint8_t *mp)
 {
     for (int l = 1; l < NLEV; ++l) {
-        const OrbLevel &L = c->lev[l];
+        const OrbLevel &L = c->orb.tab.lev[l];
         if (L.w < 1 || L.h < 1) break;
-        hipLaunchKernelGGL(k_mask_level, dim3((L.stride / 4 + 255) / 256, L.h), dim3(256), 0, c->stream, (const OrbTable *)c->orb_const,
-                           c->rz_tab, mp, l);
+        hipLaunchKernelGGL(k_mask_level, dim3((L.stride / 4 + 255) / 256, L.h), dim3(256), 0, c->stream, c->orb.buf.tab, c->orb.buf.rz, mp, l);
     }
 }
 
@@ -1247,31 +1126,31 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
     for (int f = 0; f < n; ++f) {
         reloc_ctx *c = ctxs[f];
         if (int rc = orb_prepare(c, w, h, nfeatures)) return rc;
-        if (c->pyr_ntiles != c0->pyr_ntiles || c->pyr_lds_bytes != c0->pyr_lds_bytes || c->max_feat != c0->max_feat ||
+        if (c->orb.ntiles != c0->orb.ntiles || c->orb.lds_bytes != c0->orb.lds_bytes || c->max_feat != c0->max_feat ||
             c->prm.gray_coeff_bits != c0->prm.gray_coeff_bits) {
             reloc_set_error("orb batch: contexts of unequal geometry");
             return RELOC_E_STATE;
         }
         if (int rc = image_chain_check_prepared(ctxs, f, n, channels, w, h)) return rc;
-        if (channels == 3 && !c->mask.same(c0->mask)) {
+        if (channels == 3 && !c->orb.mask.same(c0->orb.mask)) {
             reloc_set_error("orb batch: contexts with and without a detection mask, or with masks of unequal size (reloc_set_orb_mask)");
             return RELOC_E_STATE;
         }
     }
     // the persistent mask serves the frames of the chain and has the size of their working frame; nothing is launched otherwise
-    const bool masked = call_mask || (channels == 3 && c0->mask.on());
-    if (masked && !call_mask && (w != c0->mask.w || h != c0->mask.h)) {
-        reloc_set_error("working frame %dx%d differs from the detection mask %dx%d (reloc_set_orb_mask)", w, h, c0->mask.w, c0->mask.h);
+    const bool masked = call_mask || (channels == 3 && c0->orb.mask.on());
+    if (masked && !call_mask && (w != c0->orb.mask.w || h != c0->orb.mask.h)) {
+        reloc_set_error("working frame %dx%d differs from the detection mask %dx%d (reloc_set_orb_mask)", w, h, c0->orb.mask.w, c0->orb.mask.h);
         return RELOC_E_ARG;
     }
     if (masked)
         for (int f = 0; f < n; ++f) {
-            OrbMaskStage &m = ctxs[f]->mask;
+            OrbMaskStage &m = ctxs[f]->orb.mask;
             if (call_mask) mask_pyramid_launch(ctxs[f], m.call);
             else if (!m.built) { mask_pyramid_launch(ctxs[f], m.pyr); m.built = true; }
             m.last = call_mask ? m.call : m.pyr; m.last_w = w; m.last_h = h;
         }
-    const OrbTable *tab_h = (const OrbTable *)c0->orb_tab_host;
+    const OrbTable *tab_h = &c0->orb.tab;
     const int flags = gray_flags(c0, order);
     hipStream_t st = c0->stream;
     reloc_prof_begin(c0, RELOC_PROF_ORB);
@@ -1283,16 +1162,14 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
     bool aligned = w % 4 == 0 && stride % 4 == 0;
     for (int f = 0; f < n; ++f) aligned = aligned && ((uintptr_t)srcs[f]) % 4 == 0;
     OrbBatch b;
-    frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int g) { b.f[f] = orb_frame(c, srcs[g]); b.f[f].mask = masked ? c->mask.last : nullptr; });
-    PyrLds lds;
-    for (int l = 0; l < NLEV; ++l) lds.lev[l] = c0->pyr_lds[l];
-    lds.tabs = c0->pyr_lds[NLEV];
+    frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int g) { b.f[f] = c->orb.buf; b.f[f].src = srcs[g]; b.f[f].mask = masked ? c->orb.mask.last : nullptr; });
+    const PyrLds lds = c0->orb.lds;
     const int n_fast = tab_h->fast_tile_base[NLEV], n_blur = tab_h->blur_tile_base[NLEV];
     if (n == 1) {
         const OrbFrame &F = b.f[0];
         auto kern512 = channels == 3 ? (aligned ? k_pyramid<3, true, 512> : k_pyramid<3, false, 512>) : (aligned ? k_pyramid<1, true, 512> : k_pyramid<1, false, 512>);
         auto kern256 = channels == 3 ? (aligned ? k_pyramid<3, true, 256> : k_pyramid<3, false, 256>) : (aligned ? k_pyramid<1, true, 256> : k_pyramid<1, false, 256>);
-        hipLaunchKernelGGL(latency ? kern512 : kern256, dim3(c0->pyr_ntiles), dim3(latency ? 512 : 256), c0->pyr_lds_bytes, st, F.tab,
+        hipLaunchKernelGGL(latency ? kern512 : kern256, dim3(c0->orb.ntiles), dim3(latency ? 512 : 256), c0->orb.lds_bytes, st, F.tab,
                            F.tiles, F.rz, F.src, w, h, stride, flags, F.pyr, lds, F.hist, F.cand_cnt);
         hipLaunchKernelGGL(masked ? k_fast_blur<true> : k_fast_blur<false>, dim3(n_fast + n_blur), dim3(256), 0, st, F.tab, F.pyr, F.nms,
                            F.hist, F.blur, n_fast, F.mask);
@@ -1305,7 +1182,7 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
     } else {
         auto kern = channels == 3 ? (aligned ? k_pyramid_batch<3, true, 256> : k_pyramid_batch<3, false, 256>)
                                   : (aligned ? k_pyramid_batch<1, true, 256> : k_pyramid_batch<1, false, 256>);
-        hipLaunchKernelGGL(kern, dim3(c0->pyr_ntiles, n), dim3(256), c0->pyr_lds_bytes, st, b, w, h, stride, flags, lds);
+        hipLaunchKernelGGL(kern, dim3(c0->orb.ntiles, n), dim3(256), c0->orb.lds_bytes, st, b, w, h, stride, flags, lds);
         hipLaunchKernelGGL(masked ? k_fast_blur_batch<true> : k_fast_blur_batch<false>, dim3(n_fast + n_blur, n), dim3(256), 0, st, b, n_fast);
         hipLaunchKernelGGL(k_harris_batch, dim3(tab_h->flat_base[NLEV], n), dim3(256), 0, st, b);
         hipLaunchKernelGGL(k_select_batch, dim3(NLEV, n), dim3(1024), 0, st, b);
@@ -1323,9 +1200,9 @@ RELOC_API int reloc_orb_frame_dev(reloc_ctx *ctx, const uint8_t *img_dev, int w,
     return orb_run(&ctx, 1, &img_dev, w, h, stride, 3, order, nfeatures, true);
 }
 
-RELOC_API const uint8_t *reloc_frame_desc_dev(reloc_ctx *ctx) { return ctx ? ctx->f_desc : nullptr; }
-RELOC_API const float *reloc_frame_xy_dev(reloc_ctx *ctx) { return ctx ? ctx->f_xy : nullptr; }
-RELOC_API const int32_t *reloc_frame_count_dev(reloc_ctx *ctx) { return ctx ? ctx->f_count : nullptr; }
+RELOC_API const uint8_t *reloc_frame_desc_dev(reloc_ctx *ctx) { return ctx ? ctx->orb.buf.f_desc : nullptr; }
+RELOC_API const float *reloc_frame_xy_dev(reloc_ctx *ctx) { return ctx ? ctx->orb.buf.f_xy : nullptr; }
+RELOC_API const int32_t *reloc_frame_count_dev(reloc_ctx *ctx) { return ctx ? ctx->orb.buf.f_count : nullptr; }
 
 // level 0 of the mask pyramid mp from a host mask of w x h (rows mask_stride apart): rows of the level's stride, padding 0
 static int mask_upload(reloc_ctx *ctx, uint8_t *mp, const uint8_t *mask, int w, int h, int mask_stride)
@@ -1348,17 +1225,17 @@ static int orb_detect_host(reloc_ctx *ctx, const uint8_t *gray, int w, int h, in
         if (int rc = mask_alloc(ctx)) return rc;
     HostStaging st{ctx};        // no scratch slot: the context's frame and feature buffers
     st.upload_rows(ctx->frame_img, gray, w, h, stride);
-    if (mask) st.run([&] { return mask_upload(ctx, ctx->mask.call, mask, w, h, mask_stride); });
+    if (mask) st.run([&] { return mask_upload(ctx, ctx->orb.mask.call, mask, w, h, mask_stride); });
     const uint8_t *src = ctx->frame_img;
     st.run([&] { return orb_run(&ctx, 1, &src, w, h, w, 1, 0, nfeatures, true, mask != nullptr); });
-    const int32_t n = st.count(ctx->f_count);
+    const int32_t n = st.count(ctx->orb.buf.f_count);
     if (n > 0) {
-        if (xy) st.download(xy, ctx->f_xy, (int64_t)n * 8);
-        if (size) st.download(size, ctx->f_size, (int64_t)n * 4);
-        if (angle) st.download(angle, ctx->f_angle, (int64_t)n * 4);
-        if (response) st.download(response, ctx->f_resp, (int64_t)n * 4);
-        if (octave) st.download(octave, ctx->f_oct, (int64_t)n * 4);
-        if (desc) st.download(desc, ctx->f_desc, (int64_t)n * 32);
+        if (xy) st.download(xy, ctx->orb.buf.f_xy, (int64_t)n * 8);
+        if (size) st.download(size, ctx->orb.buf.f_size, (int64_t)n * 4);
+        if (angle) st.download(angle, ctx->orb.buf.f_angle, (int64_t)n * 4);
+        if (response) st.download(response, ctx->orb.buf.f_resp, (int64_t)n * 4);
+        if (octave) st.download(octave, ctx->orb.buf.f_oct, (int64_t)n * 4);
+        if (desc) st.download(desc, ctx->orb.buf.f_desc, (int64_t)n * 32);
     }
     if (int rc = st.finish()) return rc;
     *n_out = n;
@@ -1385,7 +1262,7 @@ RELOC_API int reloc_orb_detect_compute_masked(reloc_ctx *ctx, const uint8_t *gra
 RELOC_API int reloc_set_orb_mask(reloc_ctx *ctx, const uint8_t *mask, int w, int h, int stride)
 {
     ARG_CHECK_CTX(ctx, true, "ctx is NULL");
-    OrbMaskStage &m = ctx->mask;
+    OrbMaskStage &m = ctx->orb.mask;
     if (!mask || (w == 0 && h == 0)) {
         m.w = m.h = 0;
         m.built = false;
@@ -1409,16 +1286,16 @@ RELOC_API int reloc_set_orb_mask(reloc_ctx *ctx, const uint8_t *mask, int w, int
 RELOC_API int reloc_get_orb_mask(reloc_ctx *ctx, int32_t *w, int32_t *h)
 {
     ARG_CHECK_CTX(ctx, w && h, "reloc_get_orb_mask");
-    *w = ctx->mask.w; *h = ctx->mask.h;
+    *w = ctx->orb.mask.w; *h = ctx->orb.mask.h;
     return RELOC_OK;
 }
 
 RELOC_API int reloc_orb_mask_level(reloc_ctx *ctx, int level, uint8_t *out, int32_t *w, int32_t *h)
 {
     ARG_CHECK_CTX(ctx, out && w && h && level >= 0 && level < NLEV, "reloc_orb_mask_level");
-    const OrbMaskStage &m = ctx->mask;
-    if (!m.last || m.last_w != ctx->orb_w || m.last_h != ctx->orb_h) { reloc_set_error("no masked frame processed yet"); return RELOC_E_STATE; }
-    const OrbLevel &L = ctx->lev[level];
+    const OrbMaskStage &m = ctx->orb.mask;
+    if (!m.last || m.last_w != ctx->orb.w || m.last_h != ctx->orb.h) { reloc_set_error("no masked frame processed yet"); return RELOC_E_STATE; }
+    const OrbLevel &L = ctx->orb.tab.lev[level];
     HIP_TRY(hipMemcpy2DAsync(out, L.w, m.last + L.off, L.stride, L.w, L.h, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     *w = L.w;
@@ -1429,9 +1306,9 @@ RELOC_API int reloc_orb_mask_level(reloc_ctx *ctx, int level, uint8_t *out, int3
 RELOC_API int reloc_frame_debug_plane(reloc_ctx *ctx, int what, int level, uint8_t *out, int32_t *w, int32_t *h)
 {
     ARG_CHECK_CTX(ctx, out && w && h && what >= 0 && what <= 2 && level >= 0 && level < NLEV, "reloc_frame_debug_plane");
-    if (!ctx->orb_w) { reloc_set_error("no frame processed yet"); return RELOC_E_STATE; }
-    const OrbLevel &L = ctx->lev[level];
-    const uint8_t *src = (what == 0 ? ctx->pyr : what == 1 ? ctx->blur : ctx->nms) + L.off;
+    if (!ctx->orb.w) { reloc_set_error("no frame processed yet"); return RELOC_E_STATE; }
+    const OrbLevel &L = ctx->orb.tab.lev[level];
+    const uint8_t *src = (what == 0 ? ctx->orb.buf.pyr : what == 1 ? ctx->orb.buf.blur : ctx->orb.buf.nms) + L.off;
     HIP_TRY(hipMemcpy2DAsync(out, L.w, src, L.stride, L.w, L.h, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     *w = L.w;

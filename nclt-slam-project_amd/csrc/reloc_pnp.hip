@@ -942,8 +942,9 @@ static bool dist_nonzero(const double *d)
 static PnpFrame pnp_frame(const reloc_ctx *c, uint64_t seed)
 {
     PnpFrame F;
-    F.obj = c->p_obj; F.img = c->p_img; F.m_arr = c->m_n; F.n_cand_p = c->cand_n; F.Rt = c->p_Rt; F.cnt = c->p_cnt; F.inl = c->p_inl;
-    F.out = c->p_out; F.seed = seed; F.relocating = c->tick_flags;
+    const TickState &t = c->tick;
+    F.obj = t.p_obj; F.img = t.p_img; F.m_arr = t.m_n; F.n_cand_p = t.cand_n; F.Rt = t.p_Rt; F.cnt = t.p_cnt; F.inl = t.p_inl;
+    F.out = t.p_out; F.seed = seed; F.relocating = t.flags;
     return F;
 }
 
@@ -1053,19 +1054,19 @@ static int pnp_ransac_impl(reloc_ctx *ctx, const float *obj, const float *img, i
     if (m < RELOC_PNP_SAMPLE) return RELOC_OK;
     if (m > MAX_REC_ROWS) { reloc_set_error("solvePnPRansac: more than %d correspondences", MAX_REC_ROWS); return RELOC_E_CAPACITY; }
     HostStaging st{ctx};        // no scratch slot: the context's own PnP buffers
-    st.upload(ctx->p_obj, obj, (int64_t)m * 12);
-    st.upload(ctx->p_img, img, (int64_t)m * 8);
-    st.upload(ctx->m_n, &m, 4);
+    st.upload(ctx->tick.p_obj, obj, (int64_t)m * 12);
+    st.upload(ctx->tick.p_img, img, (int64_t)m * 8);
+    st.upload(ctx->tick.m_n, &m, 4);
     // the single-call path has no MIN_MATCHES gate (that gate belongs to the matcher, M:330)
     PnpBatch b;
     b.f[0] = pnp_frame(ctx, seed);
     b.f[0].n_cand_p = nullptr; b.f[0].relocating = nullptr;       // one candidate of m pairs, no relocation flag
     st.run([&] { return pnp_launch(&ctx, 1, b, 1, make_params(K4, iters, thr_px, conf, seed, MAX_REC_ROWS, RELOC_PNP_SAMPLE), dist, true); });
     PnpOut po = {};
-    st.download(&po, ctx->p_out, sizeof(po));
+    st.download(&po, ctx->tick.p_out, sizeof(po));
     if (int rc = st.finish()) return rc;
     if (po.ok) {
-        st.download(inliers, ctx->p_inl, (int64_t)po.n_inl * 4);
+        st.download(inliers, ctx->tick.p_inl, (int64_t)po.n_inl * 4);
         if (int rc = st.finish()) return rc;
         for (int k = 0; k < 3; ++k) { rvec[k] = po.rvec[k]; tvec[k] = po.Rt[9 + k]; }
         *n_inl = po.n_inl;

@@ -153,10 +153,10 @@ RELOC_API int reloc_record_frame(reloc_ctx *ctx, const uint8_t *img, const uint1
     p.depth_min = RELOC_DEPTH_MIN_M; p.depth_max = RELOC_DEPTH_MAX_M; p.var_max = RELOC_DEPTH_VAR_MAX_M;
     p.ground_y = RELOC_GROUND_Y_THRESHOLD; p.w = w; p.h = h;
     const double *lens = ctx->cam.lens();
-    st.launch(lens ? k_record<true> : k_record<false>, dim3(1), dim3(1024), ctx->f_xy, ctx->f_desc, ctx->f_count, ctx->max_feat, depth,
+    st.launch(lens ? k_record<true> : k_record<false>, dim3(1), dim3(1024), ctx->orb.buf.f_xy, ctx->orb.buf.f_desc, ctx->orb.buf.f_count, ctx->max_feat, depth,
               w, p, o_xy, o_desc, o_pts, o_idx, o_n, make_dist(lens));
     int32_t nk = 0;
-    st.download(&nk, ctx->f_count, 4);
+    st.download(&nk, ctx->orb.buf.f_count, 4);
     const int32_t n = st.count(o_n);
     if (n > 0) {
         if (xy) st.download(xy, o_xy, (int64_t)n * 8);
@@ -352,8 +352,8 @@ RELOC_API int reloc_tick_accumulate_dev(reloc_ctx *ctx, const uint16_t *depth_mm
     p.w = w; p.h = h; p.min_kpts = ctx->prm.accum_min_kpts; p.silence_ok = silence_ok;
     p.L = db.records; p.T = db.rows;
     auto kern = cam.lens() ? k_accumulate<true> : k_accumulate<false>;
-    hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, ctx->stream, ctx->f_xy, ctx->f_desc, ctx->f_count, ctx->max_feat,
-                       depth_mm_dev, w, p, ctx->tick_res, db.xy_heading, db.desc, db.pts3d, db.kp2d, db.off, db.pose, ctx->accum_res,
+    hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, ctx->stream, ctx->orb.buf.f_xy, ctx->orb.buf.f_desc, ctx->orb.buf.f_count, ctx->max_feat,
+                       depth_mm_dev, w, p, ctx->tick.res, db.xy_heading, db.desc, db.pts3d, db.kp2d, db.off, db.pose, ctx->accum_res,
                        make_dist(cam.lens()));
     HIP_TRY(hipGetLastError());
     return RELOC_OK;

@@ -22,7 +22,7 @@ struct TickParams {
     // matcher parameters (reloc_params)
     int max_candidates, min_matches, min_inliers, global_min_inliers;
     double radius_m, cos_tol, reproj_max_px, global_reproj_max_px, consistency_m;
-    int seq;                  // sequence stamp of this tick (ctx->tick_seq), stored into the host records after their body
+    int seq;                  // sequence stamp of this tick (ctx->tick.seq), stored into the host records after their body
 };
 
 __device__ void rot_to_quat(const double R[9], double q[4])
@@ -440,8 +440,8 @@ static void launch_candidates_local(reloc_ctx *ctx, const TickParams &prm)
 {
     const DbArena &db = ctx_db(ctx);
     if (prm.n_records <= NEAR_MAX_RECORDS && !ctx->local_two_stage) {
-        hipLaunchKernelGGL(k_candidates_near, dim3(1), dim3(TICK_BLOCK), 0, ctx->stream, db.xy_heading, prm, ctx->cand_ids,
-                           ctx->cand_n, ctx->tick_flags);
+        hipLaunchKernelGGL(k_candidates_near, dim3(1), dim3(TICK_BLOCK), 0, ctx->stream, db.xy_heading, prm, ctx->tick.cand_ids,
+                           ctx->tick.cand_n, ctx->tick.flags);
         return;
     }
     const int L = prm.n_records, k = L < prm.max_candidates * 3 ? L : prm.max_candidates * 3;
@@ -450,7 +450,7 @@ static void launch_candidates_local(reloc_ctx *ctx, const TickParams &prm)
         hipLaunchKernelGGL(k_topk_part<LocalKey>, dim3(nb), dim3(TICK_BLOCK), 0, ctx->stream,
                            LocalKey{db.xy_heading, prm.base_pose[0], prm.base_pose[1]}, L, k, db.topk_part);
     hipLaunchKernelGGL(k_candidates_local, dim3(1), dim3(TICK_BLOCK), 0, ctx->stream, db.xy_heading, prm, db.topk_part, nb,
-                       ctx->cand_ids, ctx->cand_n, ctx->tick_flags);
+                       ctx->tick.cand_ids, ctx->tick.cand_n, ctx->tick.flags);
 }
 
 __device__ __forceinline__ void tick_stamp(TickResult *res_host, TickResult *res_ext, int seq)
@@ -596,12 +596,39 @@ static TickParams make_tick_params(reloc_ctx *ctx, const double base_pose[7], in
     return p;
 }
 
+// The tick, match and PnP scratch of a new context (TickState) and its result record in pinned host memory
+int tick_alloc(reloc_ctx *ctx)
+{
+    TickState &t = ctx->tick;
+    const int64_t rows = (int64_t)MAX_CAND * MAX_REC_ROWS, hyps = (int64_t)MAX_CAND * MAX_HYP;
+    int rc = ctx_dev_alloc(ctx, &t.cand_ids, MAX_CAND);
+    rc |= ctx_dev_alloc(ctx, &t.cand_n, 1);
+    rc |= ctx_dev_alloc(ctx, &t.flags, 4);
+    for (int32_t **p : {&t.m_qidx, &t.m_tidx, &t.m_dist, &t.p_inl}) rc |= ctx_dev_alloc(ctx, p, rows);
+    rc |= ctx_dev_alloc(ctx, &t.m_n, MAX_CAND);
+    rc |= ctx_dev_alloc(ctx, &t.p_obj, rows * 3);
+    rc |= ctx_dev_alloc(ctx, &t.p_img, rows * 2);
+    rc |= ctx_dev_alloc(ctx, &t.p_Rt, hyps * 12);
+    rc |= ctx_dev_alloc(ctx, &t.p_cnt, hyps);
+    rc |= ctx_dev_alloc(ctx, &t.p_out, MAX_CAND);
+    rc |= ctx_dev_alloc(ctx, &t.res, 1);
+    if (hipHostMalloc((void **)&t.res_host, sizeof(TickResult), hipHostMallocDefault) != hipSuccess) {
+        reloc_set_error("hipHostMalloc(result record) failed");
+        t.res_host = nullptr;
+        rc |= RELOC_E_HIP;
+    } else memset(t.res_host, 0, sizeof(TickResult));
+    return rc;
+}
+
+// reloc_destroy frees the device blocks with the context's others; the pinned record is let go of here
+void tick_release(reloc_ctx *ctx) { if (ctx->tick.res_host) (void)hipHostFree(ctx->tick.res_host); }
+
 // the stamp of the tick being enqueued: 1, 2, ... (never 0: 0 means "no stamp")
 static int tick_next_seq(reloc_ctx *ctx)
 {
-    ctx->tick_seq = ctx->tick_seq >= 0x7fffffff ? 1 : ctx->tick_seq + 1;
-    ctx->tick_failed = false;                 // called where the finalisation (which stores the record and this stamp) is launched
-    return ctx->tick_seq;
+    ctx->tick.seq = ctx->tick.seq >= 0x7fffffff ? 1 : ctx->tick.seq + 1;
+    ctx->tick.failed = false;                 // called where the finalisation (which stores the record and this stamp) is launched
+    return ctx->tick.seq;
 }
 
 // candidate lists handed in by the caller (sharded solve): frame f's k entries at ids + f * k, -1 = none; flag: relocating
@@ -624,17 +651,19 @@ __global__ void k_set_candidates_batch(const int32_t *__restrict__ ids, int k, S
 static TopkFrame topk_frame(const reloc_ctx *c, int32_t *out_ids, int32_t *out_counts, int32_t *out_nfeat, bool auto_mode)
 {
     TopkFrame F;
-    F.counts = ctx_db(c).counts; F.out_ids = out_ids; F.out_counts = out_counts; F.out_n = c->cand_n;
-    F.skip_if = auto_mode ? (const int32_t *)c->cand_n : (const int32_t *)nullptr;   // AUTO: stands down when local candidates exist
-    F.relocating = c->tick_flags; F.f_count = c->f_count; F.out_nfeat = out_nfeat;
+    const TickState &t = c->tick;
+    F.counts = ctx_db(c).counts; F.out_ids = out_ids; F.out_counts = out_counts; F.out_n = t.cand_n;
+    F.skip_if = auto_mode ? (const int32_t *)t.cand_n : (const int32_t *)nullptr;   // AUTO: stands down when local candidates exist
+    F.relocating = t.flags; F.f_count = c->orb.buf.f_count; F.out_nfeat = out_nfeat;
     return F;
 }
 
 static FinalFrame final_frame(const reloc_ctx *c, const double base_pose[7], TickResult *res_ext, int seq)
 {
     FinalFrame F;
-    F.cand_ids = c->cand_ids; F.cand_n = c->cand_n; F.pnp = c->p_out; F.f_count = c->f_count; F.relocating = c->tick_flags;
-    F.res = c->tick_res; F.res_host = c->tick_res_host; F.res_ext = res_ext;
+    const TickState &t = c->tick;
+    F.cand_ids = t.cand_ids; F.cand_n = t.cand_n; F.pnp = t.p_out; F.f_count = c->orb.buf.f_count; F.relocating = t.flags;
+    F.res = t.res; F.res_host = t.res_host; F.res_ext = res_ext;
     for (int k = 0; k < 7; ++k) F.base_pose[k] = base_pose[k];
     F.seq = seq;
     return F;
@@ -690,8 +719,8 @@ static int scan_counts(reloc_ctx *const *ctxs, int n, const double *base_poses, 
             for (int k = 0; k < 4; ++k) mask.q[k] = base_poses[3 + k];
         }
         mask.cos_tol = cos_tol;
-        mask.skip_if = auto_mode ? c0->cand_n : nullptr;
-        rc = launch_db_count(c0, c0->f_desc, c0->f_count, c0->max_feat, ctx_db(c0).counts, mask);
+        mask.skip_if = auto_mode ? c0->tick.cand_n : nullptr;
+        rc = launch_db_count(c0, c0->orb.buf.f_desc, c0->orb.buf.f_count, c0->max_feat, ctx_db(c0).counts, mask);
     } else {
         double q[4 * RELOC_BATCH_MAX];
         for (int f = 0; f < n; ++f)
@@ -747,7 +776,7 @@ RELOC_API int reloc_get_distortion(reloc_ctx *ctx, double coeffs[5])
 static void tick_mark_failed(reloc_ctx *const *ctxs, int n)
 {
     if (ctxs && n >= 1 && n <= RELOC_BATCH_MAX)
-        for (int f = 0; f < n; ++f) if (ctxs[f]) ctxs[f]->tick_failed = true;
+        for (int f = 0; f < n; ++f) if (ctxs[f]) ctxs[f]->tick.failed = true;
 }
 
 // the contexts of one call: one stream, device and database, equal feature capacity, matcher parameters, camera and lens
@@ -793,14 +822,14 @@ static int solve_run(reloc_ctx *const *ctxs, int n, const int32_t *cand_dev, int
     int rc;
     if (cand_dev) {
         SetCandBatch sb;
-        frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int) { sb.cand_ids[f] = c->cand_ids; sb.cand_n[f] = c->cand_n; sb.flags[f] = c->tick_flags; });
+        frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int) { sb.cand_ids[f] = c->tick.cand_ids; sb.cand_n[f] = c->tick.cand_n; sb.flags[f] = c->tick.flags; });
         hipLaunchKernelGGL(k_set_candidates_batch, dim3(n), dim3(64), 0, c0->stream, cand_dev, k, sb, mode == RELOC_TICK_LOCAL ? 0 : 1);
     }
     if ((rc = launch_tick_emit(ctxs, n, latency))) return rc;
     if ((rc = pnp_run_candidates(ctxs, n, seeds, latency))) return rc;
     FinalBatch b;
     frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int g) {
-        b.f[f] = final_frame(c, base_poses + 7 * g, res_ext_base ? res_ext_base + g : c->tick_res_ext, f < n ? tick_next_seq(c) : 0);
+        b.f[f] = final_frame(c, base_poses + 7 * g, res_ext_base ? res_ext_base + g : c->tick.res_ext, f < n ? tick_next_seq(c) : 0);
     });
     return launch_tick_finalize(ctxs, n, b, make_tick_params(c0, base_poses, mode, check_consistency));
 }
@@ -819,7 +848,7 @@ static int tick_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *imgs, i
     if (mode != RELOC_TICK_LOCAL) {
         if ((rc = scan_counts(ctxs, n, base_poses, mode == RELOC_TICK_AUTO))) return rc;
         TopkBatch b;
-        frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int) { b.f[f] = topk_frame(c, c->cand_ids, nullptr, nullptr, mode == RELOC_TICK_AUTO); });
+        frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int) { b.f[f] = topk_frame(c, c->tick.cand_ids, nullptr, nullptr, mode == RELOC_TICK_AUTO); });
         launch_topk_counts(ctxs, n, b, c0->prm.global_max_candidates, 0);
     }
     return solve_run(ctxs, n, nullptr, 0, base_poses, mode, -1, seeds, nullptr);
@@ -866,13 +895,13 @@ RELOC_API int reloc_tick_batch_dev(reloc_ctx *const *ctxs, int n, const uint8_t 
 RELOC_API int reloc_tick_wait(reloc_ctx *ctx)
 {
     ARG_CHECK_CTX(ctx, true, "ctx is NULL");
-    if (ctx->tick_failed) {
+    if (ctx->tick.failed) {
         reloc_set_error("reloc_tick_wait: the last tick on this context failed before its result record was enqueued");
         return RELOC_E_STATE;
     }
-    const int want = ctx->tick_seq;
-    if (want == 0 || !ctx->tick_res_host) { HIP_TRY(hipStreamSynchronize(ctx->stream)); return RELOC_OK; }
-    volatile int32_t *stamp = (volatile int32_t *)&ctx->tick_res_host->pad[0];
+    const int want = ctx->tick.seq;
+    if (want == 0 || !ctx->tick.res_host) { HIP_TRY(hipStreamSynchronize(ctx->stream)); return RELOC_OK; }
+    volatile int32_t *stamp = (volatile int32_t *)&ctx->tick.res_host->pad[0];
     struct timespec t0;
     clock_gettime(CLOCK_MONOTONIC, &t0);
     for (unsigned spin = 1;; ++spin) {
@@ -889,36 +918,13 @@ RELOC_API int reloc_tick_wait(reloc_ctx *ctx)
     return RELOC_OK;
 }
 
-RELOC_API int reloc_tick_result(reloc_ctx *ctx, double anchor_pose[7], int32_t *n_inl, float *reproj, int32_t *lm_idx,
-                                int32_t *outcome, int32_t *n_candidates)
-{
-    ARG_CHECK_CTX(ctx, true, "ctx is NULL");
-    { const int rc = reloc_tick_wait(ctx); if (rc) return rc; }
-    const TickResult r = *ctx->tick_res_host;          // written by k_tick_finalize itself (pinned, device-visible)
-    if (anchor_pose) for (int k = 0; k < 7; ++k) anchor_pose[k] = r.anchor_pose[k];
-    if (n_inl) *n_inl = r.n_inl;
-    if (reproj) *reproj = (float)r.reproj;
-    if (lm_idx) *lm_idx = r.lm_idx;
-    if (outcome) *outcome = r.outcome;
-    if (n_candidates) *n_candidates = r.n_candidates;
-    return RELOC_OK;
-}
-
-RELOC_API const void *reloc_tick_result_dev(reloc_ctx *ctx) { return ctx ? ctx->tick_res : nullptr; }
-
-RELOC_API int reloc_tick_result_to(reloc_ctx *ctx, void *pinned_record)
-{
-    ARG_CHECK_CTX(ctx, true, "ctx is NULL");
-    ctx->tick_res_ext = (TickResult *)pinned_record;
-    return RELOC_OK;
-}
-
+// The one reader of a context's result record: waits for the last tick's record and hands out the fields asked for
 RELOC_API int reloc_tick_result_ex(reloc_ctx *ctx, double anchor_pose[7], int32_t *n_inl, double *reproj, int32_t *lm_idx,
                                    int32_t *outcome, int32_t *n_candidates, int32_t *n_features, int32_t *relocating)
 {
     ARG_CHECK_CTX(ctx, true, "ctx is NULL");
-    { const int rc = reloc_tick_wait(ctx); if (rc) return rc; }
-    const TickResult r = *ctx->tick_res_host;          // written by k_tick_finalize itself (pinned, device-visible)
+    if (int rc = reloc_tick_wait(ctx)) return rc;
+    const TickResult r = *ctx->tick.res_host;          // written by k_tick_finalize itself (pinned, device-visible)
     if (anchor_pose) for (int k = 0; k < 7; ++k) anchor_pose[k] = r.anchor_pose[k];
     if (n_inl) *n_inl = r.n_inl;
     if (reproj) *reproj = r.reproj;
@@ -930,15 +936,39 @@ RELOC_API int reloc_tick_result_ex(reloc_ctx *ctx, double anchor_pose[7], int32_
     return RELOC_OK;
 }
 
+RELOC_API int reloc_tick_result(reloc_ctx *ctx, double anchor_pose[7], int32_t *n_inl, float *reproj, int32_t *lm_idx,
+                                int32_t *outcome, int32_t *n_candidates)
+{
+    double err = 0.0;
+    const int rc = reloc_tick_result_ex(ctx, anchor_pose, n_inl, &err, lm_idx, outcome, n_candidates, nullptr, nullptr);
+    if (!rc && reproj) *reproj = (float)err;
+    return rc;
+}
+
+RELOC_API const void *reloc_tick_result_dev(reloc_ctx *ctx) { return ctx ? ctx->tick.res : nullptr; }
+
+RELOC_API int reloc_tick_result_to(reloc_ctx *ctx, void *pinned_record)
+{
+    ARG_CHECK_CTX(ctx, true, "ctx is NULL");
+    ctx->tick.res_ext = (TickResult *)pinned_record;
+    return RELOC_OK;
+}
+
+// The tick of a frame in host memory, through the context's staging plane (frame_img).  Like every tick entry point it marks
+// the tick failed first, so no error below leaves the previous tick's record readable; an error behind the copy returns only
+// when the copy has left the caller's memory (as HostStaging::finish does).  The success path synchronises in the reader alone.
 RELOC_API int reloc_tick(reloc_ctx *ctx, const uint8_t *img, int w, int h, int order, const double base_pose[7],
                          int global_reloc, uint64_t seed, double anchor_pose[7], int32_t *n_inl, float *reproj,
                          int32_t *lm_idx, int32_t *outcome, int32_t *n_candidates)
 {
+    tick_mark_failed(&ctx, 1);
     ARG_CHECK_CTX(ctx, img && base_pose && w >= 64 && h >= 64, "reloc_tick");
     if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
     HIP_TRY(hipMemcpyAsync(ctx->frame_img, img, (size_t)w * h * image_chain_frame_bpp(ctx), hipMemcpyHostToDevice, ctx->stream));
-    int rc = reloc_tick_dev(ctx, ctx->frame_img, w, h, order, base_pose, global_reloc, seed);
-    if (rc) return rc;
+    if (int rc = reloc_tick_dev(ctx, ctx->frame_img, w, h, order, base_pose, global_reloc, seed)) {
+        (void)hipStreamSynchronize(ctx->stream);        // keeps the error text of the tick
+        return rc;
+    }
     return reloc_tick_result(ctx, anchor_pose, n_inl, reproj, lm_idx, outcome, n_candidates);
 }
 
@@ -1051,9 +1081,9 @@ RELOC_API int reloc_tick_debug(reloc_ctx *ctx, int32_t *cand_ids, int32_t *n_can
 {
     ARG_CHECK_CTX(ctx, cand_ids && n_cand, "reloc_tick_debug");
     PnpOut po[MAX_CAND];
-    HIP_TRY(hipMemcpyAsync(n_cand, ctx->cand_n, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(cand_ids, ctx->cand_ids, sizeof(int32_t) * MAX_CAND, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(po, ctx->p_out, sizeof(po), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(n_cand, ctx->tick.cand_n, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(cand_ids, ctx->tick.cand_ids, sizeof(int32_t) * MAX_CAND, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(po, ctx->tick.p_out, sizeof(po), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     for (int s = 0; s < *n_cand && s < MAX_CAND; ++s) {
         if (n_matches) n_matches[s] = po[s].n_matches;
@@ -1072,21 +1102,21 @@ RELOC_API int reloc_tick_debug_matches(reloc_ctx *ctx, int slot, int32_t *n, int
 {
     ARG_CHECK_CTX(ctx, true, "ctx is NULL");
     int32_t n_cand = 0;
-    HIP_TRY(hipMemcpyAsync(&n_cand, ctx->cand_n, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&n_cand, ctx->tick.cand_n, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ARG_CHECK(slot >= 0 && slot < n_cand && slot < MAX_CAND, "reloc_tick_debug_matches: slot is not a candidate of the last solve");
     int32_t m = 0;
-    HIP_TRY(hipMemcpyAsync(&m, ctx->m_n + slot, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&m, ctx->tick.m_n + slot, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (n) *n = m;
     if (m < 0 || m > MAX_REC_ROWS) { reloc_set_error("reloc_tick_debug_matches: slot %d holds %d matches", slot, m); return RELOC_E_STATE; }
     if (m == 0) return RELOC_OK;
     const size_t at = (size_t)slot * MAX_REC_ROWS, k = (size_t)m;
-    if (qidx) HIP_TRY(hipMemcpyAsync(qidx, ctx->m_qidx + at, k * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (tidx) HIP_TRY(hipMemcpyAsync(tidx, ctx->m_tidx + at, k * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (dist) HIP_TRY(hipMemcpyAsync(dist, ctx->m_dist + at, k * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (obj) HIP_TRY(hipMemcpyAsync(obj, ctx->p_obj + 3 * at, k * 12, hipMemcpyDeviceToHost, ctx->stream));
-    if (img) HIP_TRY(hipMemcpyAsync(img, ctx->p_img + 2 * at, k * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (qidx) HIP_TRY(hipMemcpyAsync(qidx, ctx->tick.m_qidx + at, k * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (tidx) HIP_TRY(hipMemcpyAsync(tidx, ctx->tick.m_tidx + at, k * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (dist) HIP_TRY(hipMemcpyAsync(dist, ctx->tick.m_dist + at, k * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (obj) HIP_TRY(hipMemcpyAsync(obj, ctx->tick.p_obj + 3 * at, k * 12, hipMemcpyDeviceToHost, ctx->stream));
+    if (img) HIP_TRY(hipMemcpyAsync(img, ctx->tick.p_img + 2 * at, k * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return RELOC_OK;
 }

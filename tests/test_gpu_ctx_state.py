@@ -1,7 +1,9 @@
 """The host-side state of a context, pinned from outside: which unequal settings make a batched tick refuse its contexts (and
 with which code and message), that an image stage switched on, off, to another setting and back leaves no trace, that a
 context with every stage enabled is destroyed cleanly, and that the host-pointer entry points survive their scratch slots
-growing and being reused."""
+growing and being reused; that the ORB geometry of a frame size is republished whole when the size or the feature count
+changes, that a refused frame leaves no trace, that a frame may fill the capacity exactly, and that a failed reloc_tick
+leaves no readable record."""
 import numpy as np
 import pytest
 
@@ -213,5 +215,128 @@ def test_scratch_slots_regrow_and_are_reused():
             idx, dist = e.match_knn2(q, t)
             np.testing.assert_array_equal(idx, order)
             np.testing.assert_array_equal(dist, np.take_along_axis(d, order, axis=1))
+    finally:
+        e.close()
+
+
+# ---- 4. ORB geometry: one cached plan per context, replaced whole ------------------------------------------------------
+def _orb_state(e, gray, nfeatures=500):
+    """features of a gray frame and the three debug planes (pyramid, blur, NMS map) of every level"""
+    f = e.orb_detect_compute(gray, nfeatures)
+    return f, [e.frame_debug_plane(what, l) for l in range(8) for what in range(3)]
+
+
+def _assert_same_state(got, want):
+    (fa, pa), (fb, pb) = got, want
+    assert fa["n"] == fb["n"] > 0                                 # 100 x 70 leaves ORB 38 x 8 pixels of level 0: a few keypoints
+    np.testing.assert_array_equal(fa["xy"].view(np.uint32), fb["xy"].view(np.uint32))
+    np.testing.assert_array_equal(fa["desc"], fb["desc"])
+    for i, (x, y) in enumerate(zip(pa, pb)):
+        np.testing.assert_array_equal(x, y, err_msg=f"level {i // 3} plane {i % 3}")
+
+
+def _fresh_state(gray, nfeatures=500):
+    """what an engine gives that never saw another geometry"""
+    e = Engine(0, CAP_W, CAP_H, MAX_FEAT)
+    try:
+        return _orb_state(e, gray, nfeatures)
+    finally:
+        e.close()
+
+
+@pytest.fixture(scope="module")
+def grays(frame):
+    e = Engine(0, CAP_W, CAP_H, MAX_FEAT)
+    try:
+        g = e.gray(frame)
+    finally:
+        e.close()
+    return g, np.ascontiguousarray(g[13:83, 9:109])            # 128 x 96 and 100 x 70
+
+
+def test_geometry_is_republished_whole(grays):
+    big, small = grays
+    assert big.shape == (H, W) and small.shape == (70, 100)
+    want_big, want_small, want_few = _fresh_state(big), _fresh_state(small), _fresh_state(big, 60)
+    assert want_few[0]["n"] < want_big[0]["n"]
+    e = Engine(0, CAP_W, CAP_H, MAX_FEAT)
+    try:
+        for gray, want in ((big, want_big), (small, want_small), (big, want_big)):          # the frame size changes and returns
+            _assert_same_state(_orb_state(e, gray), want)
+        for nfeatures, want in ((500, want_big), (60, want_few), (500, want_big)):          # the feature count does
+            _assert_same_state(_orb_state(e, big, nfeatures), want)
+    finally:
+        e.close()
+
+
+def test_refused_frame_leaves_no_trace(frame, grays):
+    big, _ = grays
+    e = Engine(0, CAP_W, CAP_H, MAX_FEAT)
+    dev = 0
+    try:
+        before = _orb_state(e, big)
+        with pytest.raises(RelocError, match="code -4"):
+            e.orb_detect_compute(np.zeros((H, 300), np.uint8), 500)
+        _assert_same_state(_orb_state(e, big), before)
+        dev = e.to_device(np.zeros((H, 300, 3), np.uint8))
+        with pytest.raises(RelocError, match="code -4"):                # the device-frame path: refused by orb_prepare itself
+            e.orb_frame_dev(dev, 300, H)
+        _assert_same_state(_orb_state(e, big), before)
+    finally:
+        if dev:
+            e.dev_free(dev)
+        e.close()
+
+
+@pytest.mark.parametrize("w,h", [(64, 64), (97, 65), (CAP_W, CAP_H)])
+def test_frame_equal_to_capacity(oracle, w, h):
+    """every block of the ORB state is sized from the capacity: a frame that fills it, bit-exact against the oracle"""
+    gray = oracle.gray_u8(synth.textured_frame(np.random.default_rng(w + h), w, h, n_shapes=max(40, w * h // 800)))
+    exp = oracle.orb_detect_compute(gray, 500, max_out=MAX_FEAT, debug=True)
+    pyr = oracle.pyramid(gray)
+    e = Engine(0, w, h, MAX_FEAT)
+    try:
+        got = e.orb_detect_compute(gray, 500)
+        for l in range(8):
+            np.testing.assert_array_equal(e.frame_debug_plane(0, l), pyr[l], err_msg=f"pyramid level {l}")
+            np.testing.assert_array_equal(e.frame_debug_plane(1, l), oracle.blur7(pyr[l]), err_msg=f"blur level {l}")
+            if pyr[l].shape[0] > 62 and pyr[l].shape[1] > 62:
+                nms = oracle.fast_nms_map(oracle.fast_score_map(pyr[l]))
+                np.testing.assert_array_equal(e.frame_debug_plane(2, l), nms, err_msg=f"nms level {l}")
+    finally:
+        e.close()
+    n = got["n"]
+    assert n == min(exp["n"], MAX_FEAT)
+    np.testing.assert_array_equal(got["octave"], exp["octave"][:n])
+    for k in ("xy", "response", "angle", "size"):
+        np.testing.assert_array_equal(got[k].view(np.uint32), exp[k][:n].view(np.uint32), err_msg=k)
+    np.testing.assert_array_equal(got["desc"], exp["desc"][:n])
+
+
+# ---- 5. the failed-tick contract of the host-image tick ---------------------------------------------------------------
+def _same_result(a, b):
+    assert a.keys() == b.keys()
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+
+
+def test_host_tick_that_fails_leaves_no_record(frame):
+    """reloc_tick marks the tick failed before its first check, like the device-frame entry points: after a refused frame
+    the result calls report RELOC_E_STATE and never the record of the tick before"""
+    pose = synth.base_pose(10.0, 0.3, 2.0)
+    e = Engine(0, CAP_W, CAP_H, MAX_FEAT)
+    try:
+        e.db_upload(*_database(e, frame))
+        first = e.tick(frame, pose, global_reloc=True, seed=1)
+        first_full = e.tick_result()
+        assert first_full["n_features"] > 64
+        with pytest.raises(RelocError, match="code -4"):
+            e.tick(np.zeros((H, 300, 3), np.uint8), pose, global_reloc=True, seed=1)
+        with pytest.raises(RelocError, match="failed before its result record"):
+            e.tick_result()
+        with pytest.raises(RelocError, match="failed before its result record"):
+            e.tick_wait()
+        _same_result(e.tick(frame, pose, global_reloc=True, seed=1), first)
+        _same_result(e.tick_result(), first_full)
     finally:
         e.close()
