@@ -157,6 +157,26 @@ int reloc_orb_detect_compute_masked(reloc_ctx *ctx, const uint8_t *gray, int w, 
 /* Parity tap: level (in [0, 8)) of the mask pyramid that the last masked frame used, dense rows of *w bytes. */
 int reloc_orb_mask_level(reloc_ctx *ctx, int level, uint8_t *out, int32_t *w, int32_t *h);
 
+/* ---- ORB parameters (include/reloc_spec.h, "ORB PARAMS") ------------------------------------------- */
+/* cv2.ORB_create(nfeatures, scaleFactor, nlevels, ..., scoreType, ..., fastThreshold): nlevels 1..8, scale_factor finite in
+ * [1.01, 2.0], fast_threshold 1..254, score_type 0 = HARRIS_SCORE | 1 = FAST_SCORE; anything else is RELOC_E_ARG with the
+ * range in the message.  A new context holds OpenCV's defaults (8, 1.2, 20, HARRIS_SCORE) and runs the kernels built for
+ * them.  reloc_set_orb_params is persistent and used by every entry point that runs ORB: reloc_orb_detect_compute,
+ * reloc_orb_detect_compute_masked, reloc_orb_frame_dev, reloc_record_frame, every reloc_tick*, the shard entry points (the
+ * accumulation uses the tick's features).  The next frame plans its geometry anew; blocks whose size depends on the scale
+ * grow when needed (the stream is drained) and never shrink, and a frame whose plan does not fit what the context holds
+ * fails with RELOC_E_CAPACITY before anything is launched.  Levels >= nlevels are empty: reloc_frame_debug_plane and
+ * reloc_orb_mask_level return RELOC_OK and 0 x 0 for them.  The contexts of a batched call agree on all four, else
+ * RELOC_E_STATE. */
+int reloc_set_orb_params(reloc_ctx *ctx, int nlevels, double scale_factor, int fast_threshold, int score_type);
+int reloc_get_orb_params(reloc_ctx *ctx, int32_t *nlevels, double *scale_factor, int32_t *fast_threshold, int32_t *score_type);
+/* reloc_orb_detect_compute with the four parameters, and under a mask when mask != NULL (as _masked), for this call only:
+ * the persistent parameters, the persistent mask and its pyramid stay as they were. */
+int reloc_orb_detect_compute_params(reloc_ctx *ctx, const uint8_t *gray, int w, int h, int stride, const uint8_t *mask,
+                                    int mask_stride, int nfeatures, int nlevels, double scale_factor, int fast_threshold,
+                                    int score_type, float *xy, float *size, float *angle, float *response,
+                                    int32_t *octave, uint8_t *desc, int32_t *n_out);
+
 /* Teach-side record builder (R:240-288): ORB on the frame, then per keypoint the border / ground masks,
  * depth lookup (uint16 millimetres), 3x3 non-zero depth std, range and variance gates and pin-hole
  * back-projection.  Outputs (up to max_feat rows, keypoint order kept): xy = keypoints_2d, desc =

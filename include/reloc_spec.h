@@ -244,4 +244,31 @@
  *              ORB cannot do).  A level whose mask is non-zero everywhere is that of the unmasked detector. */
 #define RELOC_ORB_MASK_THRESH    254  /* THRESH_TOZERO: values above it are kept */
 
+/* ORB PARAMS: cv2.ORB_create(nfeatures, scaleFactor, nlevels, ..., scoreType, ..., fastThreshold) as runtime settings, restated
+ * from OpenCV 4.x modules/features2d/src/orb.cpp (detectAndCompute, computeKeyPoints; not pinned against a cv2 build,
+ * DESIGN.md section 2).  The constants at the head of this file are the defaults and RELOC_ORB_NLEVELS stays the capacity of
+ * every per-level array.  edgeThreshold, patchSize, firstLevel and WTA_K are not settings.
+ *   levels     scale of level l = (float)pow(scale_factor, (double)l) with scale_factor a double (OpenCV's Python binding
+ *              rounds scaleFactor to float first; this restatement does not), level size = lrintf(w / scale) x lrintf(h / scale):
+ *              today's expressions, so (8, 1.2) is today's pyramid bit for bit.
+ *   quotas     factor = (float)(1.0 / scale_factor); n = (float)(nfeatures * (1 - factor) / (1 - (float)pow((double)factor,
+ *              (double)nlevels))); level l < nlevels - 1 gets lrintf(n), then n *= factor; level nlevels - 1 gets
+ *              max(nfeatures - sum, 0).
+ *   unused     levels l >= nlevels are empty: w = h = stride = 0, quota 0; so is a level one of whose sizes rounds to 0 (its
+ *              quota is spent on nothing).  A level takes keypoints iff w > 62 && h > 62 && quota > 0.
+ *   FAST       segment test and score with the given threshold t: score = best - 1 if best > t, else 0 (no corner).
+ *   stage 1    retainBest(n_keep) by FAST score with ties kept; n_keep = 2 * quota for HARRIS_SCORE, quota for FAST_SCORE.
+ *              A level with no more than n_keep corners keeps all: its cut is t.  The RELOC_ORB_STAGE1_CAP raise as before.
+ *   score      HARRIS_SCORE: Harris response of the stage-1 survivors, best quota with ties.  FAST_SCORE: no Harris pass, the
+ *              response is (float)score and every stage-1 survivor is a keypoint, so ties at the cut make a level exceed
+ *              its quota.  Output level-major, raster order inside a level; the excess over a context's rows is cut off.
+ *   mask       between NMS and the histogram as before, on the mask pyramid of the same level geometry. */
+#define RELOC_ORB_HARRIS_SCORE     0
+#define RELOC_ORB_FAST_SCORE       1
+#define RELOC_ORB_NLEVELS_MIN      1            /* .. RELOC_ORB_NLEVELS */
+#define RELOC_ORB_SCALE_MIN        1.01
+#define RELOC_ORB_SCALE_MAX        2.0
+#define RELOC_FAST_THRESHOLD_MIN   1            /* the score plane is 8-bit and 0 means "no corner" */
+#define RELOC_FAST_THRESHOLD_MAX   254
+
 #endif /* RELOC_SPEC_H */

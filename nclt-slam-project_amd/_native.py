@@ -46,6 +46,10 @@ SIGNATURES = {
     "reloc_get_orb_mask": (C.c_int, [c_ctx, P, P]),
     "reloc_orb_detect_compute_masked": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, P, C.c_int, C.c_int, P, P, P, P, P, P, P]),
     "reloc_orb_mask_level": (C.c_int, [c_ctx, C.c_int, P, P, P]),
+    "reloc_set_orb_params": (C.c_int, [c_ctx, C.c_int, f64, C.c_int, C.c_int]),
+    "reloc_get_orb_params": (C.c_int, [c_ctx, P, P, P, P]),
+    "reloc_orb_detect_compute_params": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, P, C.c_int, C.c_int, C.c_int, f64, C.c_int,
+                                                  C.c_int, P, P, P, P, P, P, P]),
     "reloc_record_frame": (C.c_int, [c_ctx, P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P]),
     "reloc_depth_points": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, C.c_int, P, f32, f32, P, P]),
     "reloc_db_ratio_counts": (C.c_int, [c_ctx, P, C.c_int, f64, P]),

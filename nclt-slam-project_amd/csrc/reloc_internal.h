@@ -336,6 +336,7 @@ struct OrbMaskStage {
     uint8_t *pyr = nullptr;              // its mask pyramid, geometry of orb.buf.pyr; level 0 is the mask as given
     uint8_t *call = nullptr;             // the same for the mask of one reloc_orb_detect_compute_masked call
     bool built = false;                  // levels 1.. of pyr belong to the mask of level 0 (k_mask_level ran since it was set)
+    OrbParams built_prm;                 // ... on the level geometry of these ORB parameters
     const uint8_t *last = nullptr;       // the pyramid the last masked frame used, of last_w x last_h (reloc_orb_mask_level)
     int last_w = 0, last_h = 0;
     bool on() const { return w > 0; }
@@ -357,6 +358,8 @@ static_assert(sizeof(OrbFrame) == 184, "OrbFrame travels in the kernel arguments
 // frame size orb_prepare last published.
 struct OrbState {
     int w = 0, h = 0, nfeat = 0;   // the geometry tab, lds and the device tables were built for; w == 0: none
+    OrbParams plan_prm;            // ... and the ORB parameters of that plan
+    OrbParams prm;                 // the context's persistent ORB parameters (reloc_set_orb_params); a per-call set never lands here
     OrbTable tab = {};             // host copy of the device table buf.tab
     PyrLds lds = {};               // LDS layout of k_pyramid, its workgroups and its dynamic LDS
     int ntiles = 0, lds_bytes = 0;
@@ -538,14 +541,16 @@ int scan_alloc(reloc_ctx *ctx);
 int tick_alloc(reloc_ctx *ctx);
 void tick_release(reloc_ctx *ctx);
 // tables and tiles of a frame size on the device (cached: one geometry per context); a failure leaves no geometry
-int orb_prepare(reloc_ctx *ctx, int w, int h, int nfeatures);
+int orb_prepare(reloc_ctx *ctx, int w, int h, int nfeatures, const OrbParams &prm);
 // ORB of frame f = srcs[f] into ctxs[f]'s feature buffers; channels == 3 -> the frames of the image chain: interleaved
 // 3-channel frames (gray fused), or raw mosaics of image_chain_frame_bpp = 1 byte per pixel with the Bayer stage on; the
 // chain first when the contexts have stages on; with the downscale stage on, w x h is the source size and the features are
 // those of the working frame.  channels == 1 -> gray planes, never through the chain.  The chain's frames are detected
-// under the contexts' persistent mask; call_mask: under the mask whose level 0 the caller left in mask.call (reloc_orb.hip)
+// under the contexts' persistent mask; call_mask: under the mask whose level 0 the caller left in mask.call (reloc_orb.hip).
+// Every frame runs with its context's persistent ORB parameters, which a batch must agree on; call_prm: one frame with
+// these instead, the blocks already grown for them (orb_grow).
 int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, int h, int stride, int channels, int order,
-            int nfeatures, bool latency, bool call_mask = false);
+            int nfeatures, bool latency, bool call_mask = false, const OrbParams *call_prm = nullptr);
 // The image chain of a context's stages (reloc_image.hip states their order).  The checks stand before orb_prepare (the Bayer
 // and the downscale stage; w x h becomes the working frame) and behind that of context f (rectification, CLAHE); _gray runs
 // the stages on the frames and leaves *srcs / *stride / *channels describing the last plane written; _depth takes a

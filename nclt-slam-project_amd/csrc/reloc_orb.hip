@@ -1,6 +1,9 @@
 // reloc_orb.hip -- ORB front end on gfx950: 8-level pyramid (gray conversion fused) -> FAST-9/16 + NMS ->
 // best-2n by FAST score -> Harris -> best-n -> intensity-centroid angle -> 7x7 blur -> steered
 // BRIEF-256.  Serves cv2.ORB_create(nfeatures).detectAndCompute(gray, None)        (reference M:306, R:241).
+// nlevels, scaleFactor, fastThreshold and scoreType are runtime parameters (include/reloc_spec.h "ORB PARAMS";
+// reloc_set_orb_params, reloc_orb_detect_compute_params): the plan of a frame carries them (OrbParams, reloc_orb_plan.h), levels
+// behind nlevels are empty, and the default set runs the kernels built for its constants (k_fast_blur<*, 20>, k_harris<0>).
 // Holds the five ORB kernels with their batched twins, orb_alloc (the blocks of a context's OrbState, ctx->orb), orb_prepare
 // (uploads the plan of a frame size: reloc_orb_plan.h holds the level, table and tile types and the host arithmetic), orb_run
 // and the ORB entry points.  What happens to a frame before the pyramid is reloc_image.hip; the pixel helpers of both are
@@ -401,13 +404,15 @@ __device__ __forceinline__ bool fast_run9(u32 x)
 struct FastQuad {
     u32 nb[2], nd[2];
     const u32 (*w)[3];
-    __device__ __forceinline__ FastQuad(const u32 (&rows)[7][3]) : w(rows)
+    __device__ __forceinline__ FastQuad(const u32 (&rows)[7][3], int thr) : w(rows)
     {
         const u32 c = rows[3][1];
         const u32 ce = c & 0x00FF00FFu, co = (c >> 8) & 0x00FF00FFu;
         // v > c + t  <=>  v + (0x7FFF - c - t) has bit 15;   v < c - t  <=>  (c - t - 1 + 0x8000) - v has bit 15
-        nb[0] = (0x7FFFu - RELOC_FAST_THRESHOLD) * 0x00010001u - ce; nb[1] = (0x7FFFu - RELOC_FAST_THRESHOLD) * 0x00010001u - co;
-        nd[0] = (0x7FFFu - RELOC_FAST_THRESHOLD) * 0x00010001u + ce; nd[1] = (0x7FFFu - RELOC_FAST_THRESHOLD) * 0x00010001u + co;
+        // (1 <= t <= 254: neither half borrows from or carries into the other)
+        const u32 t2 = (0x7FFFu - (u32)thr) * 0x00010001u;
+        nb[0] = t2 - ce; nb[1] = t2 - co;
+        nd[0] = t2 + ce; nd[1] = t2 + co;
     }
     // sign words of ring position (dx, dy): bit 15 of each half = the flag, the other bits are to be ignored
     template <int DX, int DY>
@@ -464,7 +469,9 @@ constexpr int FT_P = FT / 4 + 3;       // dwords per staged row: columns x0 - 4 
 static_assert(FT == 32, "fast_nms_tile maps 256 lanes to 32 rows x 8 dwords");
 // MASKED: a kept corner whose byte of the mask pyramid (`mask`, geometry of pyr) is 0 enters neither the NMS map nor the
 // histogram (include/reloc_spec.h "ORB MASK"); the unmasked instantiation never reads `mask`.
-template <bool MASKED>
+// THR: the FAST threshold as a compile-time constant (the default, RELOC_FAST_THRESHOLD), or 0: the wave-uniform value of the
+// table (include/reloc_spec.h "ORB PARAMS").  The host picks the instantiation (orb_run).
+template <bool MASKED, int THR>
 __device__ __forceinline__ void fast_nms_tile(const OrbTable *__restrict__ tab, const uint8_t *__restrict__ pyr,
                                               uint8_t *__restrict__ nms, int32_t *__restrict__ hist, int bid,
                                               const uint8_t *__restrict__ mask)
@@ -483,6 +490,7 @@ __device__ __forceinline__ void fast_nms_tile(const OrbTable *__restrict__ tab, 
     const int x0 = (tile % tx) * FT, y0 = (tile / tx) * FT;
     const int tid = threadIdx.x;
     const int e = RELOC_ORB_EDGE;
+    const int thr = THR ? THR : tab->fast_thr;
     uint8_t *out = nms + L.off;
     // tiles that cannot hold a kept corner only clear their part of the map
     const bool live = L.quota > 0 && x0 + FT > e && x0 < L.w - e && y0 + FT > e && y0 < L.h - e;
@@ -533,7 +541,7 @@ __device__ __forceinline__ void fast_nms_tile(const OrbTable *__restrict__ tab, 
         for (int r = 0; r < 7; ++r)
 #pragma unroll
             for (int q = 0; q < 3; ++q) w[r][q] = s_img4[(ry + r) * FT_P + g + q];
-        const FastQuad Q(w);
+        const FastQuad Q(w, thr);
         if (__any(Q.candidate())) {
             u32 mb[2], md[2];
             Q.masks(mb, md);
@@ -563,19 +571,19 @@ __device__ __forceinline__ void fast_nms_tile(const OrbTable *__restrict__ tab, 
         if (inside) {
             const int c = pc[0];
             const int v0 = (int)pc[3 * IS] - c, v4 = (int)pc[3] - c, v8 = (int)pc[-3 * IS] - c, v12 = (int)pc[-3] - c;
-            const int nb = (v0 > RELOC_FAST_THRESHOLD) + (v4 > RELOC_FAST_THRESHOLD) + (v8 > RELOC_FAST_THRESHOLD) + (v12 > RELOC_FAST_THRESHOLD);
-            const int nd = (v0 < -RELOC_FAST_THRESHOLD) + (v4 < -RELOC_FAST_THRESHOLD) + (v8 < -RELOC_FAST_THRESHOLD) + (v12 < -RELOC_FAST_THRESHOLD);
+            const int nb = (v0 > thr) + (v4 > thr) + (v8 > thr) + (v12 > thr);
+            const int nd = (v0 < -thr) + (v4 < -thr) + (v8 < -thr) + (v12 < -thr);
             cand = nb >= 2 || nd >= 2;
         }
         if (tid < 3 * 64 && __any(cand)) {
-            if (cand) pol = fast_is_corner(pc, IS, RELOC_FAST_THRESHOLD);
+            if (cand) pol = fast_is_corner(pc, IS, thr);
         }
         if (pol) s_corner[atomicAdd(&s_nc, 1)] = (unsigned short)((ry << 6) | rx | (pol < 0 ? 0x8000 : 0));
     }
     __syncthreads();
     for (int i = tid; i < s_nc; i += 256) {
         const int e16 = s_corner[i], ry = (e16 >> 6) & 63, rx = e16 & 63;
-        s_sc[ry * SS + rx] = (uint8_t)fast_corner_score(s_img + (ry + 3) * IS + (rx + 3), IS, RELOC_FAST_THRESHOLD, (e16 & 0x8000) ? -1 : 1);
+        s_sc[ry * SS + rx] = (uint8_t)fast_corner_score(s_img + (ry + 3) * IS + (rx + 3), IS, thr, (e16 & 0x8000) ? -1 : 1);
     }
     __syncthreads();
     {
@@ -608,21 +616,22 @@ __device__ __forceinline__ void fast_nms_tile(const OrbTable *__restrict__ tab, 
 // walk the tiles paid beside 112-register scans and pays nothing beside 104-register ones: profiles/README.md "Dropped
 // experiments" #8.)
 // MASKED = true: the same with the detection mask applied behind NMS; `mask` is the last argument and unread otherwise.
-template <bool MASKED>
+// THR: fast_nms_tile.
+template <bool MASKED, int THR>
 __global__ __launch_bounds__(256) void k_fast_blur(const OrbTable *__restrict__ tab, const uint8_t *__restrict__ pyr,
                                                    uint8_t *__restrict__ nms, int32_t *__restrict__ hist,
                                                    uint8_t *__restrict__ blur, int n_fast, const uint8_t *__restrict__ mask)
 {
     RELOC_SMALL_KERNEL_PRIO();
-    if ((int)blockIdx.x < n_fast) fast_nms_tile<MASKED>(tab, pyr, nms, hist, (int)blockIdx.x, mask);
+    if ((int)blockIdx.x < n_fast) fast_nms_tile<MASKED, THR>(tab, pyr, nms, hist, (int)blockIdx.x, mask);
     else blur7_tile(tab, pyr, blur, (int)blockIdx.x - n_fast);
 }
-template <bool MASKED>
+template <bool MASKED, int THR>
 __global__ __launch_bounds__(256) void k_fast_blur_batch(OrbBatch b, int n_fast)
 {
     RELOC_SMALL_KERNEL_PRIO();
     const OrbFrame &F = b.f[blockIdx.y];
-    if ((int)blockIdx.x < n_fast) fast_nms_tile<MASKED>(F.tab, F.pyr, F.nms, F.hist, (int)blockIdx.x, F.mask);
+    if ((int)blockIdx.x < n_fast) fast_nms_tile<MASKED, THR>(F.tab, F.pyr, F.nms, F.hist, (int)blockIdx.x, F.mask);
     else blur7_tile(F.tab, F.pyr, F.blur, (int)blockIdx.x - n_fast);
 }
 
@@ -655,13 +664,13 @@ __global__ __launch_bounds__(256) void k_mask_level(const OrbTable *__restrict__
     *reinterpret_cast<u32 *>(mp + D.off + (size_t)y * D.stride + x4) = out;
 }
 
-// cut score from the level's histogram (KeyPointsFilter::retainBest(2*quota) with ties kept, raised
+// cut score from the level's histogram (KeyPointsFilter::retainBest(n_keep) with ties kept, raised
 // while the kept set exceeds RELOC_ORB_STAGE1_CAP), by ONE wave without block barriers: lane i owns the
 // bins 4i .. 4i+3.  c(s) = sum_{k >= s} hist[k] is non-increasing in s;
-//   cut0 = max{s : c(s) >= n_keep} if c(0) > n_keep, else the FAST threshold (everything is kept);
+//   cut0 = max{s : c(s) >= n_keep} if c(0) > n_keep, else the FAST threshold in use, thr (everything is kept);
 //   cut  = min{s >= cut0 : c(s) <= CAP or s == 255}.
 // Every lane returns the cut.
-__device__ int stage1_cut_wave(const int32_t *__restrict__ hist_l, int n_keep, int lane)
+__device__ int stage1_cut_wave(const int32_t *__restrict__ hist_l, int n_keep, int lane, int thr)
 {
     const int4 h = *reinterpret_cast<const int4 *>(hist_l + 4 * lane);
     // exclusive suffix sum of the lane totals
@@ -675,7 +684,7 @@ __device__ int stage1_cut_wave(const int32_t *__restrict__ hist_l, int n_keep, i
     const int above = incl - mine;
     const int c3 = h.w + above, c2 = h.z + c3, c1 = h.y + c2, c0 = h.x + c1;     // c(4i+3) .. c(4i)
     const int total = __builtin_amdgcn_readlane(c0, 0);
-    int cut0 = RELOC_FAST_THRESHOLD;
+    int cut0 = thr;
     if (total > n_keep) {
         const int s = c3 >= n_keep ? 3 : (c2 >= n_keep ? 2 : (c1 >= n_keep ? 1 : (c0 >= n_keep ? 0 : -1)));
         cut0 = (int)wave_max_u32(s < 0 ? 0u : (unsigned)(4 * lane + s + 1)) - 1;
@@ -723,6 +732,11 @@ __device__ __forceinline__ float harris_finish(int a, int b, int c)
 // compute their Harris responses (one wave per survivor) and append them to the level's candidate list.
 // Corners cluster, and a block works through its survivors four at a time: small chunks keep the longest
 // block short (ORB stage 77.5 us with 4096-byte chunks, 75.7 us with 1024-byte chunks).
+// MODE (include/reloc_spec.h "ORB PARAMS"; the host picks, orb_run): ORB_MODE_DEFAULT = the default threshold as a constant,
+// Harris score; ORB_MODE_HARRIS = the table's threshold; ORB_MODE_FAST = the table's threshold, n_keep = quota, and the
+// survivors enter the candidate list with their FAST score as the response: no Harris sums.
+enum { ORB_MODE_DEFAULT = 0, ORB_MODE_HARRIS = 1, ORB_MODE_FAST = 2 };
+template <int MODE>
 __device__ __forceinline__ void harris_body(const OrbTable *__restrict__ tab, const uint8_t *__restrict__ pyr,
                                                 const uint8_t *__restrict__ nms, const int32_t *__restrict__ hist,
                                                 int32_t *__restrict__ cand_cnt, u32 *__restrict__ cand_key,
@@ -731,6 +745,7 @@ __device__ __forceinline__ void harris_body(const OrbTable *__restrict__ tab, co
     __shared__ int s_cut;
     __shared__ int s_n, s_base;
     __shared__ u32 s_list[HARRIS_CHUNK];
+    const int thr = MODE == ORB_MODE_DEFAULT ? RELOC_FAST_THRESHOLD : tab->fast_thr;
     const int l = find_level(tab->flat_base, blockIdx.x);
     const OrbLevel L = tab->lev[l];
     if (L.quota <= 0 || L.w <= 2 * RELOC_ORB_EDGE || L.h <= 2 * RELOC_ORB_EDGE) return;
@@ -742,7 +757,7 @@ __device__ __forceinline__ void harris_body(const OrbTable *__restrict__ tab, co
     if (threadIdx.x == 0) s_n = 0;
     if (!__syncthreads_or(any)) return;                      // nothing kept in this chunk: skip the cut computation
     if (threadIdx.x < 64) {
-        const int c = stage1_cut_wave(hist + l * 256, 2 * L.quota, threadIdx.x);
+        const int c = stage1_cut_wave(hist + l * 256, MODE == ORB_MODE_FAST ? L.quota : 2 * L.quota, threadIdx.x, thr);
         if (threadIdx.x == 0) {
             s_cut = c;
             if (dbg_cut) dbg_cut[l] = c;
@@ -750,6 +765,25 @@ __device__ __forceinline__ void harris_body(const OrbTable *__restrict__ tab, co
     }
     __syncthreads();
     const int cut = s_cut;
+    if constexpr (MODE == ORB_MODE_FAST) {
+        // every survivor is a candidate: the lane that found it files it, one slot reservation per survivor
+        if (any) {
+#pragma unroll
+            for (int k = 0; k < HARRIS_CHUNK / 256; ++k) {
+                const int sc = (v >> (8 * k)) & 0xFF;
+                if (sc && sc >= cut) {
+                    const int64_t idx = idx0 + k;
+                    const int y = (int)(idx / L.stride), x = (int)(idx % L.stride);
+                    const int pos = atomicAdd(&cand_cnt[l], 1);
+                    if (pos < RELOC_ORB_STAGE1_CAP) {
+                        cand_key[(size_t)l * RELOC_ORB_STAGE1_CAP + pos] = ((u32)y << 16) | (u32)x;
+                        cand_resp[(size_t)l * RELOC_ORB_STAGE1_CAP + pos] = (float)sc;
+                    }
+                }
+            }
+        }
+        return;
+    }
     if (any) {
 #pragma unroll
         for (int k = 0; k < HARRIS_CHUNK / 256; ++k) {
@@ -810,19 +844,21 @@ __device__ __forceinline__ void harris_body(const OrbTable *__restrict__ tab, co
         }
     }
 }
+template <int MODE>
 __global__ __launch_bounds__(256) void k_harris(const OrbTable *__restrict__ tab, const uint8_t *__restrict__ pyr,
                                                 const uint8_t *__restrict__ nms, const int32_t *__restrict__ hist,
                                                 int32_t *__restrict__ cand_cnt, u32 *__restrict__ cand_key,
                                                 float *__restrict__ cand_resp, int32_t *__restrict__ dbg_cut)
 {
     RELOC_SMALL_KERNEL_PRIO();
-    harris_body(tab, pyr, nms, hist, cand_cnt, cand_key, cand_resp, dbg_cut);
+    harris_body<MODE>(tab, pyr, nms, hist, cand_cnt, cand_key, cand_resp, dbg_cut);
 }
+template <int MODE>
 __global__ __launch_bounds__(256) void k_harris_batch(OrbBatch b)
 {
     RELOC_SMALL_KERNEL_PRIO();
     const OrbFrame &F = b.f[blockIdx.y];
-    harris_body(F.tab, F.pyr, F.nms, F.hist, F.cand_cnt, F.cand_key, F.cand_resp, F.dbg_cut);
+    harris_body<MODE>(F.tab, F.pyr, F.nms, F.hist, F.cand_cnt, F.cand_key, F.cand_resp, F.dbg_cut);
 }
 
 // ---- stage 2: best quota by Harris (ties kept), raster order -----------------------------------
@@ -1059,23 +1095,57 @@ int orb_alloc(reloc_ctx *ctx)
     return rc;
 }
 
+// The blocks whose size depends on the ORB parameters (the three pyramid arenas, both mask pyramids) grown for prm when the
+// context holds less; they never shrink, and a context that keeps the defaults keeps what orb_alloc took.  Drains the
+// stream first; the arenas hold nothing that outlives a frame except level 0 of the persistent mask, which moves.
+static int orb_grow(reloc_ctx *ctx, const OrbParams &prm)
+{
+    OrbState &o = ctx->orb;
+    const OrbCaps want = orb_caps(ctx->max_w, ctx->max_h, prm);
+    if (want.pyr_bytes <= o.caps.pyr_bytes) return RELOC_OK;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    auto swap_block = [ctx](uint8_t **p, int64_t bytes, int64_t keep) -> int {
+        void *q = nullptr;
+        HIP_TRY(hipMalloc(&q, (size_t)bytes));
+        if (keep > 0) HIP_TRY(hipMemcpy(q, *p, (size_t)keep, hipMemcpyDeviceToDevice));
+        for (void *&b : ctx->dev_blocks)
+            if (b == (void *)*p) b = q;
+        HIP_TRY(hipFree(*p));
+        *p = (uint8_t *)q;
+        return RELOC_OK;
+    };
+    for (uint8_t **p : {&o.buf.pyr, &o.buf.blur, &o.buf.nms})
+        if (int rc = swap_block(p, want.pyr_bytes, 0)) return rc;
+    OrbMaskStage &m = o.mask;
+    if (m.pyr) {
+        const int64_t level0 = m.on() ? (int64_t)((m.w + 63) / 64 * 64) * m.h : 0;
+        if (int rc = swap_block(&m.pyr, 2 * want.pyr_bytes, level0)) return rc;
+        m.call = m.pyr + want.pyr_bytes;
+        m.built = false;
+        m.last = nullptr;
+    }
+    o.caps.pyr_bytes = want.pyr_bytes;
+    o.w = o.h = o.nfeat = 0;      // the debug planes of the last frame went with the old arenas
+    return RELOC_OK;
+}
+
 static bool g_pattern_uploaded[64] = {};
 
 // Capacity check, cache hit, plan, then the three tables go to the device with the cache key taken down: a failed upload
 // leaves a context without geometry (the next frame plans again), never one whose key names tables that were half replaced.
-int orb_prepare(reloc_ctx *ctx, int w, int h, int nfeatures)
+int orb_prepare(reloc_ctx *ctx, int w, int h, int nfeatures, const OrbParams &prm)
 {
     OrbState &o = ctx->orb;
     if (w > ctx->max_w || h > ctx->max_h) {
         reloc_set_error("frame %dx%d exceeds the ctx capacity %dx%d", w, h, ctx->max_w, ctx->max_h);
         return RELOC_E_CAPACITY;
     }
-    if (o.w == w && o.h == h && o.nfeat == nfeatures) return RELOC_OK;
+    if (o.w == w && o.h == h && o.nfeat == nfeatures && o.plan_prm.same(prm)) return RELOC_OK;
     if (!g_pattern_uploaded[ctx->device & 63]) {
         HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(c_pattern), RELOC_ORB_PATTERN, sizeof(RELOC_ORB_PATTERN)));
         g_pattern_uploaded[ctx->device & 63] = true;
     }
-    const OrbPlan plan = orb_plan(w, h, nfeatures, o.caps);
+    const OrbPlan plan = orb_plan(w, h, nfeatures, o.caps, prm);
     if (plan.rc) { reloc_set_error("%s", plan.err); return plan.rc; }
     o.w = o.h = o.nfeat = 0;
     const hipError_t e0 = hipMemcpyAsync(const_cast<PyrTile *>(o.buf.tiles), plan.tiles.data(), sizeof(PyrTile) * plan.tiles.size(),
@@ -1087,7 +1157,7 @@ int orb_prepare(reloc_ctx *ctx, int w, int h, int nfeatures)
     HIP_TRY(e0); HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
     memcpy(&o.tab, &plan.tab, sizeof(OrbTable));
     o.lds = plan.lds; o.lds_bytes = plan.lds_bytes; o.ntiles = (int)plan.tiles.size();
-    o.w = w; o.h = h; o.nfeat = nfeatures;
+    o.w = w; o.h = h; o.nfeat = nfeatures; o.plan_prm = prm;
     return RELOC_OK;
 }
 
@@ -1117,15 +1187,20 @@ static void mask_pyramid_launch(reloc_ctx *c, uint8_t *mp)
 // plane the chain wrote, or the frame itself.  It runs 512-thread workgroups for latency, 256 where it shares the chip with
 // whole-database scans.
 int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, int h, int stride, int channels, int order,
-            int nfeatures, bool latency, bool call_mask)
+            int nfeatures, bool latency, bool call_mask, const OrbParams *call_prm)
 {
     if (n < 1 || n > RELOC_BATCH_MAX) { reloc_set_error("orb: 1..%d frames", RELOC_BATCH_MAX); return RELOC_E_ARG; }
     reloc_ctx *c0 = ctxs[0];
+    const OrbParams P = call_prm ? *call_prm : c0->orb.prm;
     const int sw = w, sh = h;               // the frame as handed in; w x h becomes the working frame
     if (int rc = image_chain_check(ctxs, n, channels, &w, &h)) return rc;
     for (int f = 0; f < n; ++f) {
         reloc_ctx *c = ctxs[f];
-        if (int rc = orb_prepare(c, w, h, nfeatures)) return rc;
+        if (!call_prm && !c->orb.prm.same(P)) {
+            reloc_set_error("orb batch: contexts with unequal ORB parameters (reloc_set_orb_params)");
+            return RELOC_E_STATE;
+        }
+        if (int rc = orb_prepare(c, w, h, nfeatures, P)) return rc;
         if (c->orb.ntiles != c0->orb.ntiles || c->orb.lds_bytes != c0->orb.lds_bytes || c->max_feat != c0->max_feat ||
             c->prm.gray_coeff_bits != c0->prm.gray_coeff_bits) {
             reloc_set_error("orb batch: contexts of unequal geometry");
@@ -1147,7 +1222,7 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
         for (int f = 0; f < n; ++f) {
             OrbMaskStage &m = ctxs[f]->orb.mask;
             if (call_mask) mask_pyramid_launch(ctxs[f], m.call);
-            else if (!m.built) { mask_pyramid_launch(ctxs[f], m.pyr); m.built = true; }
+            else if (!m.built || !m.built_prm.same(P)) { mask_pyramid_launch(ctxs[f], m.pyr); m.built = true; m.built_prm = P; }
             m.last = call_mask ? m.call : m.pyr; m.last_w = w; m.last_h = h;
         }
     const OrbTable *tab_h = &c0->orb.tab;
@@ -1165,15 +1240,20 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
     frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int g) { b.f[f] = c->orb.buf; b.f[f].src = srcs[g]; b.f[f].mask = masked ? c->orb.mask.last : nullptr; });
     const PyrLds lds = c0->orb.lds;
     const int n_fast = tab_h->fast_tile_base[NLEV], n_blur = tab_h->blur_tile_base[NLEV];
+    // the default detector runs the kernels built for it; any other threshold or score the ones that read the table
+    const bool thr_def = P.fast_thr == RELOC_FAST_THRESHOLD;
+    const int mode = P.score == RELOC_ORB_FAST_SCORE ? ORB_MODE_FAST : thr_def ? ORB_MODE_DEFAULT : ORB_MODE_HARRIS;
     if (n == 1) {
         const OrbFrame &F = b.f[0];
         auto kern512 = channels == 3 ? (aligned ? k_pyramid<3, true, 512> : k_pyramid<3, false, 512>) : (aligned ? k_pyramid<1, true, 512> : k_pyramid<1, false, 512>);
         auto kern256 = channels == 3 ? (aligned ? k_pyramid<3, true, 256> : k_pyramid<3, false, 256>) : (aligned ? k_pyramid<1, true, 256> : k_pyramid<1, false, 256>);
         hipLaunchKernelGGL(latency ? kern512 : kern256, dim3(c0->orb.ntiles), dim3(latency ? 512 : 256), c0->orb.lds_bytes, st, F.tab,
                            F.tiles, F.rz, F.src, w, h, stride, flags, F.pyr, lds, F.hist, F.cand_cnt);
-        hipLaunchKernelGGL(masked ? k_fast_blur<true> : k_fast_blur<false>, dim3(n_fast + n_blur), dim3(256), 0, st, F.tab, F.pyr, F.nms,
-                           F.hist, F.blur, n_fast, F.mask);
-        hipLaunchKernelGGL(k_harris, dim3(tab_h->flat_base[NLEV]), dim3(256), 0, st, F.tab, F.pyr, F.nms, F.hist, F.cand_cnt, F.cand_key,
+        auto fast = masked ? (thr_def ? k_fast_blur<true, RELOC_FAST_THRESHOLD> : k_fast_blur<true, 0>)
+                           : (thr_def ? k_fast_blur<false, RELOC_FAST_THRESHOLD> : k_fast_blur<false, 0>);
+        auto harris = mode == ORB_MODE_FAST ? k_harris<ORB_MODE_FAST> : mode == ORB_MODE_HARRIS ? k_harris<ORB_MODE_HARRIS> : k_harris<ORB_MODE_DEFAULT>;
+        hipLaunchKernelGGL(fast, dim3(n_fast + n_blur), dim3(256), 0, st, F.tab, F.pyr, F.nms, F.hist, F.blur, n_fast, F.mask);
+        hipLaunchKernelGGL(harris, dim3(tab_h->flat_base[NLEV]), dim3(256), 0, st, F.tab, F.pyr, F.nms, F.hist, F.cand_cnt, F.cand_key,
                            F.cand_resp, F.dbg_cut);
         hipLaunchKernelGGL(k_select, dim3(NLEV), dim3(1024), 0, st, F.tab, F.cand_cnt, F.cand_key, F.cand_resp, F.kp_cnt, F.kp_key,
                            F.kp_resp);
@@ -1183,8 +1263,12 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
         auto kern = channels == 3 ? (aligned ? k_pyramid_batch<3, true, 256> : k_pyramid_batch<3, false, 256>)
                                   : (aligned ? k_pyramid_batch<1, true, 256> : k_pyramid_batch<1, false, 256>);
         hipLaunchKernelGGL(kern, dim3(c0->orb.ntiles, n), dim3(256), c0->orb.lds_bytes, st, b, w, h, stride, flags, lds);
-        hipLaunchKernelGGL(masked ? k_fast_blur_batch<true> : k_fast_blur_batch<false>, dim3(n_fast + n_blur, n), dim3(256), 0, st, b, n_fast);
-        hipLaunchKernelGGL(k_harris_batch, dim3(tab_h->flat_base[NLEV], n), dim3(256), 0, st, b);
+        auto fast = masked ? (thr_def ? k_fast_blur_batch<true, RELOC_FAST_THRESHOLD> : k_fast_blur_batch<true, 0>)
+                           : (thr_def ? k_fast_blur_batch<false, RELOC_FAST_THRESHOLD> : k_fast_blur_batch<false, 0>);
+        auto harris = mode == ORB_MODE_FAST ? k_harris_batch<ORB_MODE_FAST>
+                                            : mode == ORB_MODE_HARRIS ? k_harris_batch<ORB_MODE_HARRIS> : k_harris_batch<ORB_MODE_DEFAULT>;
+        hipLaunchKernelGGL(fast, dim3(n_fast + n_blur, n), dim3(256), 0, st, b, n_fast);
+        hipLaunchKernelGGL(harris, dim3(tab_h->flat_base[NLEV], n), dim3(256), 0, st, b);
         hipLaunchKernelGGL(k_select_batch, dim3(NLEV, n), dim3(1024), 0, st, b);
         hipLaunchKernelGGL(k_describe_batch, dim3((c0->max_feat + 3) / 4, n), dim3(256), 0, st, b, c0->max_feat);
     }
@@ -1213,21 +1297,24 @@ static int mask_upload(reloc_ctx *ctx, uint8_t *mp, const uint8_t *mask, int w, 
     return RELOC_OK;
 }
 
-// gray plane -> features on the host; mask != NULL: under that mask, through the context's per-call mask pyramid
+// gray plane -> features on the host; mask != NULL: under that mask, through the context's per-call mask pyramid;
+// prm != NULL: with these ORB parameters for this call, the persistent ones untouched
 static int orb_detect_host(reloc_ctx *ctx, const uint8_t *gray, int w, int h, int stride, const uint8_t *mask, int mask_stride,
-                           int nfeatures, float *xy, float *size, float *angle, float *response, int32_t *octave, uint8_t *desc,
-                           int32_t *n_out)
+                           const OrbParams *prm, int nfeatures, float *xy, float *size, float *angle, float *response,
+                           int32_t *octave, uint8_t *desc, int32_t *n_out)
 {
     *n_out = 0;
     if (w < 63 || h < 63) return RELOC_OK;   // no level is wider than the 31-pixel edge margin on both sides
     if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
+    if (prm)
+        if (int rc = orb_grow(ctx, *prm)) return rc;
     if (mask)
         if (int rc = mask_alloc(ctx)) return rc;
     HostStaging st{ctx};        // no scratch slot: the context's frame and feature buffers
     st.upload_rows(ctx->frame_img, gray, w, h, stride);
     if (mask) st.run([&] { return mask_upload(ctx, ctx->orb.mask.call, mask, w, h, mask_stride); });
     const uint8_t *src = ctx->frame_img;
-    st.run([&] { return orb_run(&ctx, 1, &src, w, h, w, 1, 0, nfeatures, true, mask != nullptr); });
+    st.run([&] { return orb_run(&ctx, 1, &src, w, h, w, 1, 0, nfeatures, true, mask != nullptr, prm); });
     const int32_t n = st.count(ctx->orb.buf.f_count);
     if (n > 0) {
         if (xy) st.download(xy, ctx->orb.buf.f_xy, (int64_t)n * 8);
@@ -1247,7 +1334,7 @@ RELOC_API int reloc_orb_detect_compute(reloc_ctx *ctx, const uint8_t *gray, int 
                                        uint8_t *desc, int32_t *n_out)
 {
     ARG_CHECK_CTX(ctx, gray && n_out && w > 0 && h > 0 && stride >= w && nfeatures > 0, "reloc_orb_detect_compute");
-    return orb_detect_host(ctx, gray, w, h, stride, nullptr, 0, nfeatures, xy, size, angle, response, octave, desc, n_out);
+    return orb_detect_host(ctx, gray, w, h, stride, nullptr, 0, nullptr, nfeatures, xy, size, angle, response, octave, desc, n_out);
 }
 
 RELOC_API int reloc_orb_detect_compute_masked(reloc_ctx *ctx, const uint8_t *gray, int w, int h, int stride, const uint8_t *mask,
@@ -1256,7 +1343,43 @@ RELOC_API int reloc_orb_detect_compute_masked(reloc_ctx *ctx, const uint8_t *gra
 {
     ARG_CHECK_CTX(ctx, gray && n_out && w > 0 && h > 0 && stride >= w && nfeatures > 0, "reloc_orb_detect_compute_masked");
     ARG_CHECK(mask && mask_stride >= w, "reloc_orb_detect_compute_masked: mask is NULL or its stride is below the width");
-    return orb_detect_host(ctx, gray, w, h, stride, mask, mask_stride, nfeatures, xy, size, angle, response, octave, desc, n_out);
+    return orb_detect_host(ctx, gray, w, h, stride, mask, mask_stride, nullptr, nfeatures, xy, size, angle, response, octave, desc, n_out);
+}
+
+static int orb_params_check(const OrbParams &p, const char *who)
+{
+    if (const char *bad = p.check()) { reloc_set_error("bad argument: %s: %s", who, bad); return RELOC_E_ARG; }
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_orb_detect_compute_params(reloc_ctx *ctx, const uint8_t *gray, int w, int h, int stride, const uint8_t *mask,
+                                              int mask_stride, int nfeatures, int nlevels, double scale_factor, int fast_threshold,
+                                              int score_type, float *xy, float *size, float *angle, float *response,
+                                              int32_t *octave, uint8_t *desc, int32_t *n_out)
+{
+    ARG_CHECK_CTX(ctx, gray && n_out && w > 0 && h > 0 && stride >= w && nfeatures > 0, "reloc_orb_detect_compute_params");
+    ARG_CHECK(!mask || mask_stride >= w, "reloc_orb_detect_compute_params: the mask's stride is below the width");
+    const OrbParams prm{nlevels, scale_factor, fast_threshold, score_type};
+    if (int rc = orb_params_check(prm, "reloc_orb_detect_compute_params")) return rc;
+    return orb_detect_host(ctx, gray, w, h, stride, mask, mask_stride, &prm, nfeatures, xy, size, angle, response, octave, desc, n_out);
+}
+
+RELOC_API int reloc_set_orb_params(reloc_ctx *ctx, int nlevels, double scale_factor, int fast_threshold, int score_type)
+{
+    ARG_CHECK_CTX(ctx, true, "ctx is NULL");
+    const OrbParams prm{nlevels, scale_factor, fast_threshold, score_type};
+    if (int rc = orb_params_check(prm, "reloc_set_orb_params")) return rc;
+    if (int rc = orb_grow(ctx, prm)) return rc;
+    ctx->orb.prm = prm;
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_get_orb_params(reloc_ctx *ctx, int32_t *nlevels, double *scale_factor, int32_t *fast_threshold, int32_t *score_type)
+{
+    ARG_CHECK_CTX(ctx, nlevels && scale_factor && fast_threshold && score_type, "reloc_get_orb_params");
+    const OrbParams &p = ctx->orb.prm;
+    *nlevels = p.nlevels; *scale_factor = p.scale; *fast_threshold = p.fast_thr; *score_type = p.score;
+    return RELOC_OK;
 }
 
 RELOC_API int reloc_set_orb_mask(reloc_ctx *ctx, const uint8_t *mask, int w, int h, int stride)
@@ -1296,6 +1419,7 @@ RELOC_API int reloc_orb_mask_level(reloc_ctx *ctx, int level, uint8_t *out, int3
     const OrbMaskStage &m = ctx->orb.mask;
     if (!m.last || m.last_w != ctx->orb.w || m.last_h != ctx->orb.h) { reloc_set_error("no masked frame processed yet"); return RELOC_E_STATE; }
     const OrbLevel &L = ctx->orb.tab.lev[level];
+    if (L.w < 1 || L.h < 1) { *w = *h = 0; return RELOC_OK; }      // a level behind nlevels
     HIP_TRY(hipMemcpy2DAsync(out, L.w, m.last + L.off, L.stride, L.w, L.h, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     *w = L.w;
@@ -1308,6 +1432,7 @@ RELOC_API int reloc_frame_debug_plane(reloc_ctx *ctx, int what, int level, uint8
     ARG_CHECK_CTX(ctx, out && w && h && what >= 0 && what <= 2 && level >= 0 && level < NLEV, "reloc_frame_debug_plane");
     if (!ctx->orb.w) { reloc_set_error("no frame processed yet"); return RELOC_E_STATE; }
     const OrbLevel &L = ctx->orb.tab.lev[level];
+    if (L.w < 1 || L.h < 1) { *w = *h = 0; return RELOC_OK; }      // a level behind nlevels
     const uint8_t *src = (what == 0 ? ctx->orb.buf.pyr : what == 1 ? ctx->orb.buf.blur : ctx->orb.buf.nms) + L.off;
     HIP_TRY(hipMemcpy2DAsync(out, L.w, src, L.stride, L.w, L.h, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -33,14 +33,37 @@ struct OrbLevel {
     int quota;
 };
 
+// cv2.ORB_create's runtime parameters (include/reloc_spec.h "ORB PARAMS"); the defaults are the detector of a context that
+// never set any.  Levels >= nlevels of a plan are empty.
+struct OrbParams {
+    int nlevels = RELOC_ORB_NLEVELS;
+    double scale = RELOC_ORB_SCALE_FACTOR;
+    int fast_thr = RELOC_FAST_THRESHOLD;
+    int score = RELOC_ORB_HARRIS_SCORE;
+    bool same(const OrbParams &o) const { return nlevels == o.nlevels && scale == o.scale && fast_thr == o.fast_thr && score == o.score; }
+    // NULL, or the range that a value leaves
+    const char *check() const
+    {
+        if (nlevels < RELOC_ORB_NLEVELS_MIN || nlevels > RELOC_ORB_NLEVELS) return "nlevels outside 1..8";
+        if (!(scale >= RELOC_ORB_SCALE_MIN && scale <= RELOC_ORB_SCALE_MAX)) return "scaleFactor not finite or outside 1.01..2.0";
+        if (fast_thr < RELOC_FAST_THRESHOLD_MIN || fast_thr > RELOC_FAST_THRESHOLD_MAX) return "fastThreshold outside 1..254";
+        if (score != RELOC_ORB_HARRIS_SCORE && score != RELOC_ORB_FAST_SCORE) return "scoreType outside 0..1 (HARRIS_SCORE, FAST_SCORE)";
+        return nullptr;
+    }
+};
+
 struct OrbTable {
     OrbLevel lev[NLEV];
     int fast_tile_base[NLEV + 1];   // 32x32 tiles over (stride x h)
     int blur_tile_base[NLEV + 1];   // 64x16 tiles over (w x h)
     int flat_base[NLEV + 1];        // HARRIS_CHUNK-byte chunks over stride*h
     int rz_off[NLEV][4];            // offsets into the resize table: xofs, xcoef, yofs, ycoef
+    int nlevels;                    // levels in use; the ones behind them are empty
+    int fast_thr;                   // FAST threshold, read by the kernels that are not built for the default
+    int score;                      // RELOC_ORB_HARRIS_SCORE | RELOC_ORB_FAST_SCORE
+    int pad;
 };
-static_assert(sizeof(OrbLevel) == 32 && sizeof(OrbTable) == 496, "OrbTable is read by every ORB kernel");
+static_assert(sizeof(OrbLevel) == 32 && sizeof(OrbTable) == 512, "OrbTable is read by every ORB kernel");
 
 struct PyrTile {
     uint16_t o[NLEV][4];    // stored rectangle x0, x1, y0, y1 (x0 multiple of 4; x1 may reach into the row padding)
@@ -57,13 +80,13 @@ struct OrbCaps {
     int64_t tiles;          // PyrTile entries
 };
 
-static inline OrbCaps orb_caps(int max_w, int max_h)
+static inline OrbCaps orb_caps(int max_w, int max_h, const OrbParams &prm = OrbParams{})
 {
     OrbCaps c;
     // a level is at most 1 + dim / scale wide and high (lrintf), its stride the width rounded up to 64
     c.pyr_bytes = 0;
-    for (int l = 0; l < NLEV; ++l) {
-        const double s = pow(RELOC_ORB_SCALE_FACTOR, (double)l);
+    for (int l = 0; l < prm.nlevels; ++l) {
+        const double s = pow(prm.scale, (double)l);
         const int64_t w = (int64_t)(max_w / s) + 2, h = (int64_t)(max_h / s) + 2;
         c.pyr_bytes += ((w + 63) / 64 * 64) * h + 256;
     }
@@ -99,35 +122,44 @@ static inline void orb_resize_axis(int src_n, int dst_n, int32_t *ofs, int32_t *
 }
 
 // The plan of a w x h frame with nfeatures keypoints for blocks of the sizes in caps.
-static inline OrbPlan orb_plan(int w, int h, int nfeatures, const OrbCaps &caps)
+// Levels l >= prm.nlevels are empty (w = h = stride = 0, quota 0): they own no tile, no table entry and no byte of a tile's
+// rectangles, and the kernels' NLEV-long loops fall through them.  So is a level whose width or height rounds to 0 (a frame
+// below scale^l / 2: never with the default parameters from 64 x 64 on), whatever its quota.
+static inline OrbPlan orb_plan(int w, int h, int nfeatures, const OrbCaps &caps, const OrbParams &prm = OrbParams{})
 {
     OrbPlan p;
     OrbTable &tab = p.tab;
     memset(&tab, 0, sizeof(tab));
     memset(&p.lds, 0, sizeof(p.lds));
     auto refuse = [&p](const char *what) { p.rc = RELOC_E_CAPACITY; p.err = what; };
+    if (prm.check()) { p.rc = RELOC_E_ARG; p.err = prm.check(); return p; }
+    if (w > 0xFFFF || h > 0xFFFF) { refuse("frame exceeds the 16-bit rectangles of the pyramid tiles"); return p; }
+    const int nlev = prm.nlevels;
+    tab.nlevels = nlev; tab.fast_thr = prm.fast_thr; tab.score = prm.score;
     int64_t off = 0;
     for (int l = 0; l < NLEV; ++l) {
-        const float s = (float)pow(RELOC_ORB_SCALE_FACTOR, (double)l);
+        const float s = (float)pow(prm.scale, (double)l);
         OrbLevel &L = tab.lev[l];
         L.scale = s;
+        L.off = off;
+        if (l >= nlev) continue;
         L.w = (int)lrintf((float)w / s);
         L.h = (int)lrintf((float)h / s);
+        if (L.w < 1 || L.h < 1) L.w = L.h = 0;      // rounded away (scale^l beyond twice the frame): empty like the levels behind nlevels
         L.stride = (L.w + 63) / 64 * 64;
-        L.off = off;
         off += ((int64_t)L.stride * L.h + 255) / 256 * 256;
     }
     if (off > caps.pyr_bytes) { refuse("pyramid arena too small"); return p; }
     {
-        const float factor = (float)(1.0 / RELOC_ORB_SCALE_FACTOR);
-        float nper = (float)(nfeatures * (1 - factor) / (1 - (float)pow((double)factor, (double)NLEV)));
+        const float factor = (float)(1.0 / prm.scale);
+        float nper = (float)(nfeatures * (1 - factor) / (1 - (float)pow((double)factor, (double)nlev)));
         int sum = 0;
-        for (int l = 0; l < NLEV - 1; ++l) {
+        for (int l = 0; l < nlev - 1; ++l) {
             tab.lev[l].quota = (int)lrintf(nper);
             sum += tab.lev[l].quota;
             nper *= factor;
         }
-        tab.lev[NLEV - 1].quota = nfeatures - sum > 0 ? nfeatures - sum : 0;
+        tab.lev[nlev - 1].quota = nfeatures - sum > 0 ? nfeatures - sum : 0;
     }
     for (int l = 0; l < NLEV; ++l) {
         const OrbLevel &L = tab.lev[l];
@@ -147,8 +179,9 @@ static inline OrbPlan orb_plan(int w, int h, int nfeatures, const OrbCaps &caps)
     if (pos > caps.rz_entries) { refuse("resize tables exceed their block"); return p; }
     p.rz.resize((size_t)pos);
     int32_t *host = p.rz.data();
-    for (int l = 1; l < NLEV; ++l) {
+    for (int l = 1; l < nlev; ++l) {
         const OrbLevel &S = tab.lev[l - 1], &D = tab.lev[l];
+        if (D.w < 1) continue;
         orb_resize_axis(S.w, D.w, host + tab.rz_off[l][0], host + tab.rz_off[l][1]);
         orb_resize_axis(S.h, D.h, host + tab.rz_off[l][2], host + tab.rz_off[l][3]);
     }

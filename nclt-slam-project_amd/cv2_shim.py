@@ -69,6 +69,8 @@ INTER_NEAREST = 0
 INTER_LINEAR = 1
 INTER_AREA = 3
 BORDER_CONSTANT = 0
+ORB_HARRIS_SCORE = 0
+ORB_FAST_SCORE = 1
 CV_16UC1 = 2
 CV_32FC1 = 5
 CV_16SC2 = 11
@@ -165,16 +167,81 @@ def _rodrigues_matrix(rvec):
     return np.eye(3) + math.sin(th) * K + (1.0 - math.cos(th)) * (K @ K)
 
 
+ORB_DEFAULTS = (8, 1.2, 20, ORB_HARRIS_SCORE)      # (nlevels, scaleFactor, fastThreshold, scoreType) of cv2.ORB_create
+
+
+def orb_params(nlevels=8, scaleFactor=1.2, fastThreshold=20, scoreType=ORB_HARRIS_SCORE, what="ORB_create"):
+    """the four settable ORB_create parameters as the tuple the backends take (include/reloc_spec.h "ORB PARAMS"); a value
+    outside its range raises `error` with the range"""
+    def integer(v, name, lo, hi, note=""):
+        try:
+            ok = float(v) == int(v) and lo <= int(v) <= hi
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not ok:
+            raise error(f"{what}: {name} must be an integer in {lo}..{hi}{note}, got {v!r}")
+        return int(v)
+    n = integer(nlevels, "nlevels", 1, 8)
+    try:
+        sf = float(scaleFactor)
+    except (TypeError, ValueError) as e:
+        raise error(f"{what}: scaleFactor must be a finite number in 1.01..2.0, got {scaleFactor!r}") from e
+    if not (math.isfinite(sf) and 1.01 <= sf <= 2.0):
+        raise error(f"{what}: scaleFactor must be a finite number in 1.01..2.0, got {scaleFactor!r}")
+    t = integer(fastThreshold, "fastThreshold", 1, 254)
+    sc = integer(scoreType, "scoreType", 0, 1, " (ORB_HARRIS_SCORE, ORB_FAST_SCORE)")
+    return n, sf, t, sc
+
+
 class _ORB:
-    def __init__(self, shim, nfeatures):
+    """cv2.ORB: the parameters live in the object and travel with every call (orb=), so two objects on one backend never
+    see each other's settings"""
+
+    def __init__(self, shim, nfeatures, params=ORB_DEFAULTS):
         self._shim = shim
         self._nfeatures = int(nfeatures)
+        self._params = tuple(params)
+        self._check_backend(self._params)
+
+    def _check_backend(self, params):
+        if tuple(params) != ORB_DEFAULTS and not _takes(self._shim.backend.orb_detect_compute, "orb"):
+            raise error("ORB_create: only OpenCV's default nlevels, scaleFactor, fastThreshold and scoreType are implemented by "
+                        "this backend (its orb_detect_compute takes no orb)")
+
+    def _set(self, **kw):
+        n, sf, t, sc = self._params
+        cur = dict(nlevels=n, scaleFactor=sf, fastThreshold=t, scoreType=sc)
+        cur.update(kw)
+        params = orb_params(what="ORB", **cur)
+        self._check_backend(params)
+        self._params = params
+
+    def getMaxFeatures(self): return self._nfeatures
+    def getNLevels(self): return self._params[0]
+    def getScaleFactor(self): return self._params[1]
+    def getFastThreshold(self): return self._params[2]
+    def getScoreType(self): return self._params[3]
+    def setNLevels(self, nlevels): self._set(nlevels=nlevels)
+    def setScaleFactor(self, scaleFactor): self._set(scaleFactor=scaleFactor)
+    def setFastThreshold(self, fastThreshold): self._set(fastThreshold=fastThreshold)
+    def setScoreType(self, scoreType): self._set(scoreType=scoreType)
+
+    def setMaxFeatures(self, maxFeatures):
+        try:
+            ok = int(maxFeatures) == float(maxFeatures) and int(maxFeatures) > 0
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not ok:
+            raise error(f"ORB: maxFeatures must be a positive integer, got {maxFeatures!r}")
+        self._nfeatures = int(maxFeatures)
 
     def detectAndCompute(self, image, mask=None):
         img = np.asarray(image)
         if img.dtype != np.uint8 or img.ndim != 2:
             raise error("detectAndCompute: expected a single-channel uint8 image")
         kw = {}
+        if self._params != ORB_DEFAULTS:
+            kw["orb"] = self._params
         if mask is not None:
             # OpenCV: CV_8UC1 of the image's size; zero pixels of a mask level take no keypoint (include/reloc_spec.h "ORB MASK")
             m = np.asarray(mask)
@@ -448,6 +515,8 @@ class Cv2Shim:
     INTER_NEAREST = INTER_NEAREST
     INTER_LINEAR = INTER_LINEAR
     INTER_AREA = INTER_AREA
+    ORB_HARRIS_SCORE = ORB_HARRIS_SCORE
+    ORB_FAST_SCORE = ORB_FAST_SCORE
     BORDER_CONSTANT = BORDER_CONSTANT
     CV_16UC1 = CV_16UC1
     CV_32FC1 = CV_32FC1
@@ -649,12 +718,17 @@ class Cv2Shim:
         return self.remap(img, m1, m2, INTER_LINEAR, dst=dst)
 
     def ORB_create(self, nfeatures=500, **kwargs):
-        defaults = dict(scaleFactor=1.2, nlevels=8, edgeThreshold=31, firstLevel=0, WTA_K=2, scoreType=0,
-                        patchSize=31, fastThreshold=20)
+        """cv2.ORB_create: nlevels (1..8), scaleFactor (1.01..2.0), fastThreshold (1..254) and scoreType (ORB_HARRIS_SCORE,
+        ORB_FAST_SCORE) are settings (include/reloc_spec.h "ORB PARAMS") on a backend whose orb_detect_compute takes orb=;
+        edgeThreshold, firstLevel, WTA_K and patchSize only at OpenCV's defaults"""
+        fixed = dict(edgeThreshold=31, firstLevel=0, WTA_K=2, patchSize=31)
+        settable = ("nlevels", "scaleFactor", "fastThreshold", "scoreType")
         for k, v in kwargs.items():
-            if k not in defaults or abs(float(v) - float(defaults[k])) > 1e-6:
+            if k in settable:
+                continue
+            if k not in fixed or abs(float(v) - float(fixed[k])) > 1e-6:
                 raise error(f"ORB_create: only OpenCV's default {k} is implemented (the reference passes nfeatures only)")
-        return _ORB(self, nfeatures)
+        return _ORB(self, nfeatures, orb_params(**{k: kwargs[k] for k in settable if k in kwargs}))
 
     def BFMatcher(self, normType=NORM_L2, crossCheck=False):
         return _BFMatcher(self, normType, crossCheck)

@@ -179,9 +179,11 @@ class Engine:
             raise N.RelocError(f"{what}: the mask must be C-contiguous, or strided along rows only (strides[0] >= W)")
         return mask
 
-    def orb_detect_compute(self, gray: np.ndarray, nfeatures: int = 500, mask: np.ndarray | None = None):
+    def orb_detect_compute(self, gray: np.ndarray, nfeatures: int = 500, mask: np.ndarray | None = None, orb=None):
         """cv2.ORB_create(nfeatures).detectAndCompute(gray, mask); mask: None, or an (H, W) uint8 array of gray's size that
-        applies to this call only (reloc_orb_detect_compute_masked; the persistent mask of set_orb_mask never applies here)"""
+        applies to this call only (reloc_orb_detect_compute_masked; the persistent mask of set_orb_mask never applies here).
+        orb: None = the parameters of set_orb_params, or (nlevels, scaleFactor, fastThreshold, scoreType) for this call only
+        (reloc_orb_detect_compute_params; the persistent ones stay as they are)"""
         gray = N.u8(gray)
         if gray.ndim != 2:
             raise N.RelocError("detectAndCompute: expected an (H, W) uint8 image")
@@ -191,19 +193,49 @@ class Engine:
         resp = np.empty(mf, np.float32); octv = np.empty(mf, np.int32); desc = np.empty((mf, 32), np.uint8)
         n = C.c_int32()
         outs = (N.ptr(xy), N.ptr(size), N.ptr(ang), N.ptr(resp), N.ptr(octv), N.ptr(desc), C.byref(n))
-        if mask is None:
-            N.check(self._lib.reloc_orb_detect_compute(self._ctx, N.ptr(gray), w, h, w, int(nfeatures), *outs),
-                    "reloc_orb_detect_compute")
-        else:
+        if mask is not None:
             mask = self._mask_plane(mask, "detectAndCompute")
             if mask.shape != (h, w):
                 raise N.RelocError(f"detectAndCompute: the mask is {mask.shape[1]}x{mask.shape[0]}, the image {w}x{h}")
+        if orb is not None:
+            nlev, sf, thr, score = self._orb_params(orb, "detectAndCompute")
+            mp, ms = (None, 0) if mask is None else (C.c_void_p(mask.ctypes.data), mask.strides[0])
+            N.check(self._lib.reloc_orb_detect_compute_params(self._ctx, N.ptr(gray), w, h, w, mp, ms, int(nfeatures), nlev, sf,
+                                                              thr, score, *outs), "reloc_orb_detect_compute_params")
+        elif mask is None:
+            N.check(self._lib.reloc_orb_detect_compute(self._ctx, N.ptr(gray), w, h, w, int(nfeatures), *outs),
+                    "reloc_orb_detect_compute")
+        else:
             N.check(self._lib.reloc_orb_detect_compute_masked(self._ctx, N.ptr(gray), w, h, w, C.c_void_p(mask.ctypes.data),
                                                               mask.strides[0], int(nfeatures), *outs),
                     "reloc_orb_detect_compute_masked")
         k = n.value
         return dict(xy=xy[:k].copy(), size=size[:k].copy(), angle=ang[:k].copy(), response=resp[:k].copy(),
                     octave=octv[:k].copy(), desc=desc[:k].copy(), n=k)
+
+    @staticmethod
+    def _orb_params(orb, what):
+        """(nlevels, scaleFactor, fastThreshold, scoreType) as the library takes them; the library checks the ranges"""
+        try:
+            nlev, sf, thr, score = orb
+            if int(nlev) != nlev or int(thr) != thr or int(score) != score:
+                raise ValueError
+            return int(nlev), float(sf), int(thr), int(score)
+        except (TypeError, ValueError) as e:
+            raise N.RelocError(f"{what}: orb is (nlevels, scaleFactor, fastThreshold, scoreType): three integers and a number") from e
+
+    def set_orb_params(self, nlevels: int = 8, scale_factor: float = 1.2, fast_threshold: int = 20, score_type: int = 0):
+        """cv2.ORB_create's nlevels (1..8), scaleFactor (1.01..2.0), fastThreshold (1..254) and scoreType (0 = HARRIS_SCORE,
+        1 = FAST_SCORE) of every entry point that runs ORB (reloc_set_orb_params; include/reloc_spec.h "ORB PARAMS"); the
+        defaults are OpenCV's and those of a new engine"""
+        N.check(self._lib.reloc_set_orb_params(self._ctx, *self._orb_params((nlevels, scale_factor, fast_threshold, score_type),
+                                                                            "set_orb_params")), "reloc_set_orb_params")
+
+    def get_orb_params(self):
+        """(nlevels, scaleFactor, fastThreshold, scoreType)"""
+        n = C.c_int32(); s = C.c_double(); t = C.c_int32(); sc = C.c_int32()
+        N.check(self._lib.reloc_get_orb_params(self._ctx, C.byref(n), C.byref(s), C.byref(t), C.byref(sc)), "reloc_get_orb_params")
+        return n.value, s.value, t.value, sc.value
 
     def set_orb_mask(self, mask: np.ndarray | None = None):
         """ORB's detection mask on the frames of the fused tick, recording and reloc_orb_frame_dev (reloc_set_orb_mask): an
@@ -635,9 +667,10 @@ class Engine:
         return p
 
     def set_params_from(self, other: "Engine"):
-        """copy another engine's matcher parameters (the contexts of a batch must carry equal ones)"""
+        """copy another engine's matcher and ORB parameters (the contexts of a batch must carry equal ones)"""
         p = other.get_params()
         N.check(self._lib.reloc_set_params(self._ctx, C.byref(p)), "reloc_set_params")
+        self.set_orb_params(*other.get_orb_params())
 
     def set_params(self, **kw):
         """matcher parameters of the fused tick (reloc_params in include/reloc.h); unnamed fields keep their value"""

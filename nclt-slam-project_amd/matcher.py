@@ -60,6 +60,11 @@ class MatcherConfig:
     # sees, and acts inside ORB, before the per-level quota is spent (include/reloc_spec.h "ORB MASK"; use 255 for "keep":
     # pyramid levels above 0 keep a pixel only where the interpolated mask is 255).  Teach and repeat usually share it.
     mask: np.ndarray | None = None
+    # ORB_create's tunable parameters: None = OpenCV's defaults (the reference matcher), or (nlevels, scaleFactor,
+    # fastThreshold, scoreType) / a dict with those cv2 keyword names, e.g. dict(fastThreshold=7) for dim scenes, dict(nlevels=4,
+    # scaleFactor=1.5) for a small resized frame, dict(scoreType=1) for cv2.ORB_FAST_SCORE (include/reloc_spec.h "ORB PARAMS").
+    # Teach with the same setting.
+    orb: tuple | dict | None = None
     candidate_radius_m: float = 8.0
     max_candidates: int = 5
     heading_tol_deg: float = 90.0
@@ -149,6 +154,37 @@ def mask_setting(mask):
     return np.ascontiguousarray(m)
 
 
+ORB_KEYS = ("nlevels", "scaleFactor", "fastThreshold", "scoreType")
+
+
+def orb_setting(orb):
+    """MatcherConfig.orb / the recorder's orb= as the checked tuple (nlevels, scaleFactor, fastThreshold, scoreType); None
+    and OpenCV's defaults give None"""
+    from .cv2_shim import ORB_DEFAULTS, error, orb_params
+    if orb is None:
+        return None
+    if isinstance(orb, dict):
+        unknown = set(orb) - set(ORB_KEYS)
+        if unknown:
+            raise ValueError(f"orb: unknown key(s) {sorted(unknown)}; the settings are {ORB_KEYS}")
+        kw = dict(orb)
+    else:
+        if len(orb) != 4:
+            raise ValueError("orb must be None, (nlevels, scaleFactor, fastThreshold, scoreType) or a dict of those")
+        kw = dict(zip(ORB_KEYS, orb))
+    try:
+        p = orb_params(what="orb", **kw)
+    except error as e:
+        raise ValueError(str(e)) from e
+    return None if p == ORB_DEFAULTS else p
+
+
+def orb_create(cv2, nfeatures, orb=None):
+    """cv2.ORB_create for the cores: the reference's call when orb is None or the defaults"""
+    p = orb_setting(orb)
+    return cv2.ORB_create(nfeatures=nfeatures) if p is None else cv2.ORB_create(nfeatures=nfeatures, **dict(zip(ORB_KEYS, p)))
+
+
 def fixed_rectify_maps(cv2, maps):
     """MatcherConfig.rectify as the fixed-point pair cv2.remap reads for both interpolations (None stays None)"""
     if maps is None:
@@ -193,8 +229,10 @@ class ImageChain:
         return gray, depth_mm
 
 
-def configure_engine(engine, clahe=None, rectify=None, resize=None, bayer=None, mask=None):
-    """the same five settings on an Engine, which is as large as the camera"""
+def configure_engine(engine, clahe=None, rectify=None, resize=None, bayer=None, mask=None, orb=None):
+    """the same five settings and the ORB parameters on an Engine, which is as large as the camera"""
+    from .cv2_shim import ORB_DEFAULTS
+    engine.set_orb_params(*(orb_setting(orb) or ORB_DEFAULTS))
     engine.set_orb_mask(mask_setting(mask))
     engine.set_bayer(bayer_setting(bayer))
     engine.set_clahe(*((None,) if clahe is None else (clahe[0], tuple(clahe[1]))))
@@ -216,7 +254,7 @@ class LandmarkMatcherCore:
         self.swap_flag = swap_flag
         self._swapped = False
         self._adopt(load_landmarks(landmarks) if isinstance(landmarks, str) else landmarks)
-        self.orb = cv2.ORB_create(nfeatures=self.cfg.nfeatures)
+        self.orb = orb_create(cv2, self.cfg.nfeatures, self.cfg.orb)
         self.matcher = cv2.BFMatcher(cv2.NORM_HAMMING, crossCheck=True)
         self.chain = c = ImageChain(cv2, self.cfg.clahe, self.cfg.rectify, self.cfg.resize, self.cfg.bayer, self.cfg.mask)
         self.clahe, self.rectify, self.resize = c.clahe, c.rectify, c.resize
@@ -468,7 +506,7 @@ class FusedLandmarkMatcher:
         e.set_camera([cfg.fx, cfg.fy, cfg.cx, cfg.cy], data.get("base_to_cam_translation", P.BASE_TO_CAM_TRANSLATION),
                      data.get("base_to_cam_rot", P.BASE_TO_CAM_ROT))
         e.set_distortion(cfg.dist)
-        configure_engine(e, cfg.clahe, cfg.rectify, cfg.resize, cfg.bayer, cfg.mask)
+        configure_engine(e, cfg.clahe, cfg.rectify, cfg.resize, cfg.bayer, cfg.mask, cfg.orb)
         self._return_src = return_landmarks
         self.swap_flag = swap_flag
         self._swapped = False

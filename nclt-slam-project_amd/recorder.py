@@ -14,7 +14,7 @@ import numpy as np
 
 from . import pose as P
 from .landmarks import new_database, save_landmarks
-from .matcher import ImageChain, configure_engine
+from .matcher import ImageChain, configure_engine, orb_create
 
 FX = FY = 320.0
 CX, CY = 320.0, 240.0
@@ -41,7 +41,7 @@ def local_depth_std(depth_mm, uu, vv):
 
 class LandmarkRecorderCore:
     def __init__(self, out_pkl=None, min_disp_m: float = 2.0, cv2=None, nfeatures: int = 500, logger=None, engine=None,
-                 dist=(), clahe=None, rectify=None, resize=None, bayer=None, mask=None):
+                 dist=(), clahe=None, rectify=None, resize=None, bayer=None, mask=None, orb=None):
         """engine: when given, ORB + all per-keypoint gates + back-projection run in ONE device call
         (reloc_record_frame); otherwise the gates run in NumPy on the cv2-shaped module's features.
         dist: lens distortion as MatcherConfig.dist (OpenCV's k1 k2 p1 p2 [k3], () = pinhole): the kept keypoints are
@@ -58,19 +58,21 @@ class LandmarkRecorderCore:
         resize (engine: reloc_set_bayer; cv2 path: cv2.cvtColor(raw, COLOR_Bayer??2BGR), then COLOR_BGR2GRAY).
         mask: None or an (H, W) uint8 array as MatcherConfig.mask, of the size of the resized / rectified frame: ORB takes no
         keypoint where it is zero (engine: reloc_set_orb_mask; cv2 path: the second argument of detectAndCompute).  Teach and
-        repeat usually share it."""
+        repeat usually share it.
+        orb: None or (nlevels, scaleFactor, fastThreshold, scoreType) / a dict as MatcherConfig.orb (engine:
+        reloc_set_orb_params; cv2 path: the keywords of ORB_create).  Teach and repeat share it."""
         self.engine = engine
         self.dist = tuple(np.asarray(dist, np.float64).ravel()) if dist is not None else ()
         if engine is not None:
             engine.set_distortion(self.dist)
-            configure_engine(engine, clahe, rectify, resize, bayer, mask)
+            configure_engine(engine, clahe, rectify, resize, bayer, mask, orb)
         self.nfeatures = nfeatures
         if cv2 is None and engine is None:
             from . import cv2_shim as cv2
         self.cv2 = cv2
         self.out_pkl = out_pkl
         self.min_disp_m = float(min_disp_m)
-        self.orb = cv2.ORB_create(nfeatures=nfeatures) if cv2 is not None else None
+        self.orb = orb_create(cv2, nfeatures, orb) if cv2 is not None else None
         self.chain = c = ImageChain(cv2, clahe, rectify, resize, bayer, mask)
         self.clahe, self.rectify, self.resize = c.clahe, c.rectify, c.resize
         self.landmarks = []

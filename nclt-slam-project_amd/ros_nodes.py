@@ -90,9 +90,10 @@ def _node_base():
 
 
 def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global_reloc=False, fused=False, cv2=None, bayer=None,
-                      mask=None):
+                      mask=None, orb=None):
     """cv2: the cv2-shaped module the ROS-free core calls (default: the HIP shim); only the non-fused core uses it.
-    bayer: MatcherConfig.bayer -- the colour topic carries raw mosaics, passed through undecoded.  mask: MatcherConfig.mask"""
+    bayer: MatcherConfig.bayer -- the colour topic carries raw mosaics, passed through undecoded.  mask: MatcherConfig.mask.
+    orb: MatcherConfig.orb"""
     from geometry_msgs.msg import PoseWithCovarianceStamped
     from sensor_msgs.msg import Image
     Node = _node_base()
@@ -100,7 +101,7 @@ def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global
     class VisualLandmarkMatcher(Node):
         def __init__(self):
             super().__init__("visual_landmark_matcher")
-            cfg = MatcherConfig(global_reloc=global_reloc, bayer=bayer, mask=mask)
+            cfg = MatcherConfig(global_reloc=global_reloc, bayer=bayer, mask=mask, orb=orb)
             if fused:
                 self.core = FusedLandmarkMatcher(pkl_path, log_csv, config=cfg, return_landmarks=return_pkl,
                                                  swap_flag=swap_flag, logger=lambda m: self.get_logger().info(m),
@@ -155,14 +156,14 @@ def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global
     return VisualLandmarkMatcher()
 
 
-def make_recorder_node(out_pkl, min_disp_m=2.0, cv2=None, bayer=None, mask=None):
+def make_recorder_node(out_pkl, min_disp_m=2.0, cv2=None, bayer=None, mask=None, orb=None):
     from sensor_msgs.msg import Image
     Node = _node_base()
 
     class VisualLandmarkRecorder(Node):
         def __init__(self):
             super().__init__("visual_landmark_recorder")
-            self.core = LandmarkRecorderCore(out_pkl, min_disp_m, cv2=cv2, bayer=bayer, mask=mask)
+            self.core = LandmarkRecorderCore(out_pkl, min_disp_m, cv2=cv2, bayer=bayer, mask=mask, orb=orb)
             self.last_rgb = self.last_depth = None
             self.last_rgb_ts = 0.0
             self.create_subscription(Image, "/camera/color/image_raw", self._rgb_cb, 10)
@@ -197,10 +198,30 @@ def make_recorder_node(out_pkl, min_disp_m=2.0, cv2=None, bayer=None, mask=None)
 MASK_HELP = "ORB takes no keypoint where this (H, W) uint8 array (a .npy file, size of the frame ORB sees) is zero"
 
 
+def add_orb_flags(ap):
+    """--orb-nlevels, --orb-scale-factor, --orb-fast-threshold, --orb-score: MatcherConfig.orb (cv2.ORB_create's keywords)"""
+    ap.add_argument("--orb-nlevels", type=int, default=None, metavar="N", help="ORB pyramid levels, 1..8 (default 8)")
+    ap.add_argument("--orb-scale-factor", type=float, default=None, metavar="S", help="ORB pyramid scale factor, 1.01..2.0 (default 1.2)")
+    ap.add_argument("--orb-fast-threshold", type=int, default=None, metavar="T", help="ORB FAST threshold, 1..254 (default 20)")
+    ap.add_argument("--orb-score", default=None, choices=["harris", "fast"], help="ORB score type (default harris)")
+
+
+def orb_flags(args):
+    """MatcherConfig.orb of the --orb-* flags: None when none is given, else the checked tuple (a bad value: ValueError)"""
+    from .matcher import ORB_KEYS, orb_setting
+    given = dict(zip(ORB_KEYS, (args.orb_nlevels, args.orb_scale_factor, args.orb_fast_threshold,
+                                None if args.orb_score is None else int(args.orb_score == "fast"))))
+    given = {k: v for k, v in given.items() if v is not None}
+    return orb_setting(given) if given else None
+
+
 def _chain_args(args):
-    """the trailing (cv2, bayer, mask) of the node factories; cv2 None = the default shim; nothing when all are defaults"""
-    mask = load_mask(args.mask)
-    return () if args.bayer is None and mask is None else (None, args.bayer) if mask is None else (None, args.bayer, mask)
+    """the trailing (cv2, bayer, mask, orb) of the node factories; cv2 None = the default shim; only as far as the last one
+    that is not its default, nothing when all are defaults"""
+    tail = [None, args.bayer, load_mask(args.mask), orb_flags(args)]
+    while tail and tail[-1] is None:
+        tail.pop()
+    return tuple(tail)
 
 
 def matcher_main(argv=None):
@@ -213,6 +234,7 @@ def matcher_main(argv=None):
     ap.add_argument("--fused", action="store_true", help="run the whole tick in one device call")
     ap.add_argument("--bayer", default=None, choices=["BG", "GB", "RG", "GR"], help="the colour topic carries raw 8-bit mosaics of this pattern")
     ap.add_argument("--mask", default=None, metavar="FILE.npy", help=MASK_HELP)
+    add_orb_flags(ap)
     args = ap.parse_args(argv)
     raw = _chain_args(args)
     import rclpy
@@ -237,6 +259,7 @@ def recorder_main(argv=None):
     ap.add_argument("--min-disp", type=float, default=2.0)
     ap.add_argument("--bayer", default=None, choices=["BG", "GB", "RG", "GR"], help="the colour topic carries raw 8-bit mosaics of this pattern")
     ap.add_argument("--mask", default=None, metavar="FILE.npy", help=MASK_HELP)
+    add_orb_flags(ap)
     args = ap.parse_args(argv)
     raw = _chain_args(args)
     import rclpy

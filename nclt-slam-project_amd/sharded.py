@@ -148,12 +148,20 @@ class HipShard:
     """One rank's shard on its GPU.  `frame` is a device pointer to a (H, W, 3) uint8 BGR image.  n_slots > 1 keeps
     that many contexts (each with the shard uploaded and its own stream) so the frames of a batch overlap."""
 
-    def __init__(self, engine, desc, pts3d, offsets, poses, rank: int, world: int, w=640, h=480, n_slots: int = 1):
+    def __init__(self, engine, desc, pts3d, offsets, poses, rank: int, world: int, w=640, h=480, n_slots: int = 1, orb=None):
+        """orb: None = the engine's ORB parameters as they are, or MatcherConfig.orb: set on the engine; every slot (and every
+        context a pipeline makes with set_params_from) carries the engine's, as the contexts of a batch must"""
         from .engine import Engine
+        from .matcher import orb_setting
+        if orb is not None:
+            from .cv2_shim import ORB_DEFAULTS
+            engine.set_orb_params(*(orb_setting(orb) or ORB_DEFAULTS))
         bounds = shard_by_rows(offsets, world)
         a, b = int(bounds[rank]), int(bounds[rank + 1])
         off = np.asarray(offsets[a:b + 1], np.int64) - int(offsets[a])
         self.engines = [engine] + [Engine(engine.device, engine.max_w, engine.max_h, engine.max_feat) for _ in range(n_slots - 1)]
+        for e in self.engines[1:]:
+            e.set_orb_params(*engine.get_orb_params())
         if b > a:
             # one resident copy of the shard; the other slots (streams) scan it through reloc_db_share
             engine.db_upload(desc[offsets[a]:offsets[b]], pts3d[offsets[a]:offsets[b]], off, poses[a:b])
