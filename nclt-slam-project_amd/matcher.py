@@ -16,11 +16,12 @@ from __future__ import annotations
 import math
 import os
 import time
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, fields
 
 import numpy as np
 
 from . import pose as P
+from .front_end import FrontEnd, ImageChain, scaled_camera  # noqa: F401  (scaled_camera: INTEGRATION.md names it here)
 from .landmarks import load_landmarks, pack_landmarks, save_landmarks
 
 CSV_HEADER = "ts,vio_x,vio_y,candidates_tried,best_n_inliers,best_reproj_err,anchor_x,anchor_y,outcome\n"
@@ -32,38 +33,13 @@ class MatcherConfig:
     fy: float = 320.0
     cx: float = 320.0
     cy: float = 240.0
-    # lens distortion, OpenCV's (k1, k2, p1, p2[, k3]) -- e.g. sensor_msgs/CameraInfo.d of a plumb_bob camera; () = pinhole
-    # (the reference's DIST = zeros, M:52).  Longer OpenCV vectors are accepted when everything after k3 is zero.
+    # the camera front end, as front_end.FrontEnd describes the seven fields; front_end gives them as one checked object
     dist: tuple = ()
-    # CLAHE between gray conversion and ORB: None = off (the reference matcher), or (clipLimit, (tiles_x, tiles_y)) as in
-    # cv2.createCLAHE(clipLimit=2.0, tileGridSize=(8, 8)) of the teach-and-repeat scripts.  Teach with the same setting.
     clahe: tuple | None = None
-    # rectification of the frame between gray conversion and CLAHE / ORB (and of the depth, nearest, for accumulation):
-    # None = off, or (map1, map2) as cv2.remap takes them -- two float32 maps or the CV_16SC2 + CV_16UC1 pair, e.g. from
-    # cv2.initUndistortRectifyMap / cv2.fisheye.initUndistortRectifyMap.  fx, fy, cx, cy are then the newCameraMatrix the
-    # map was built for and dist stays empty.  Teach with the same map.
     rectify: tuple | None = None
-    # downscale of the frame at the head of the image chain, between gray conversion and rectification: None = off, or
-    # (width, height) as in cv2.resize(gray, (808, 616), interpolation=cv2.INTER_AREA) of the dataset runners (the depth with
-    # INTER_NEAREST).  fx, fy, cx, cy, the rectification map and every coordinate are then those of the resized image
-    # (scaled_camera).  The fused matcher's Engine must be created for the camera's full size.  Teach with the same size.
     resize: tuple | None = None
-    # raw colour camera: None = the frames are 3-channel BGR (the reference matcher), or the Bayer pattern of the 8-bit
-    # single-channel mosaics the camera delivers, in OpenCV's letters as in cv2.cvtColor(raw, cv2.COLOR_BayerGR2BGR) of the
-    # RobotCar pipeline: "BG" (sensor name RGGB), "GB" (GRBG), "RG" (BGGR) or "GR" (GBRG, RobotCar's "gbrg").  Every frame is
-    # then an (H, W) uint8 mosaic, demosaiced (bilinear) and converted to gray at the head of the image chain; resize takes
-    # the mosaic's size as its source.  Teach with the same pattern.
     bayer: str | None = None
-    # ORB's detection mask, the second argument of detectAndCompute: None = every pixel may carry a keypoint (the reference
-    # matcher), or an (H, W) uint8 array in which zero marks what must never become a landmark -- the robot's own hood, sky, the
-    # black wedges of a rectification, a fisheye's blind zone.  It has the size of the resized / rectified frame that ORB
-    # sees, and acts inside ORB, before the per-level quota is spent (include/reloc_spec.h "ORB MASK"; use 255 for "keep":
-    # pyramid levels above 0 keep a pixel only where the interpolated mask is 255).  Teach and repeat usually share it.
     mask: np.ndarray | None = None
-    # ORB_create's tunable parameters: None = OpenCV's defaults (the reference matcher), or (nlevels, scaleFactor,
-    # fastThreshold, scoreType) / a dict with those cv2 keyword names, e.g. dict(fastThreshold=7) for dim scenes, dict(nlevels=4,
-    # scaleFactor=1.5) for a small resized frame, dict(scoreType=1) for cv2.ORB_FAST_SCORE (include/reloc_spec.h "ORB PARAMS").
-    # Teach with the same setting.
     orb: tuple | dict | None = None
     candidate_radius_m: float = 8.0
     max_candidates: int = 5
@@ -92,6 +68,10 @@ class MatcherConfig:
     accum_min_kpts: int = 30
 
     @property
+    def front_end(self) -> FrontEnd:
+        return FrontEnd(**{f.name: getattr(self, f.name) for f in fields(FrontEnd)})
+
+    @property
     def K(self):
         return np.array([[self.fx, 0, self.cx], [0, self.fy, self.cy], [0, 0, 1]], dtype=np.float32)
 
@@ -113,155 +93,28 @@ class TickOutcome:
     extra: dict = field(default_factory=dict)
 
 
-def scaled_camera(K4, src_size, dst_size):
-    """(fx, fy, cx, cy) of an image resized from src_size = (w, h) to dst_size = (w, h) by cv2.resize: pixel centres map as
-    x' = (x + 0.5) / s - 0.5 with s = src / dst per axis, so fx' = fx / sx, cx' = (cx + 0.5) / sx - 0.5 (and likewise in y)"""
-    fx, fy, cx, cy = (float(t) for t in K4)
-    sx, sy = src_size[0] / dst_size[0], src_size[1] / dst_size[1]
-    return (fx / sx, fy / sy, (cx + 0.5) / sx - 0.5, (cy + 0.5) / sy - 0.5)
+def configure_engine(engine, **settings):
+    """FrontEnd(**settings).configure(engine), for callers that hold loose settings"""
+    FrontEnd(**settings).configure(engine)
 
 
-def resize_setting(size):
-    """MatcherConfig.resize / the recorder's resize= as (width, height) ints (None stays None)"""
-    if size is None:
-        return None
-    w, h = (int(t) for t in size)
-    if w < 1 or h < 1:
-        raise ValueError("resize must be (width, height), both positive")
-    return (w, h)
+class _MatcherSession:
+    """What a repeat session is, whichever way its ticks are computed: the landmark set and its return-leg swap, the
+    counters, the CSV log and the TickOutcome of each attempt.  LandmarkMatcherCore and FusedLandmarkMatcher add the tick, and
+    for the swap `_swap_in()`, which makes the return-leg set the current one and returns its dict, and the log's SWAP_WORD."""
 
-
-BAYER_CODES = {"BG": 46, "GB": 47, "RG": 48, "GR": 49}      # cv2.COLOR_Bayer??2BGR
-
-
-def bayer_setting(pattern):
-    """MatcherConfig.bayer / the recorder's bayer= as OpenCV's COLOR_Bayer??2BGR code (None stays None)"""
-    if pattern is None:
-        return None
-    code = BAYER_CODES.get(str(pattern).upper())
-    if code is None:
-        raise ValueError('bayer must be None or one of "BG", "GB", "RG", "GR" (OpenCV\'s letters: RGGB, GRBG, BGGR, GBRG sensors)')
-    return code
-
-
-def mask_setting(mask):
-    """MatcherConfig.mask / the recorder's mask= as the (H, W) uint8 array detectAndCompute takes (None stays None)"""
-    if mask is None:
-        return None
-    m = np.asarray(mask)
-    if m.dtype != np.uint8 or m.ndim != 2 or m.size == 0:
-        raise ValueError("mask must be None or an (H, W) uint8 array of the size of the frame ORB sees")
-    return np.ascontiguousarray(m)
-
-
-ORB_KEYS = ("nlevels", "scaleFactor", "fastThreshold", "scoreType")
-
-
-def orb_setting(orb):
-    """MatcherConfig.orb / the recorder's orb= as the checked tuple (nlevels, scaleFactor, fastThreshold, scoreType); None
-    and OpenCV's defaults give None"""
-    from .cv2_shim import ORB_DEFAULTS, error, orb_params
-    if orb is None:
-        return None
-    if isinstance(orb, dict):
-        unknown = set(orb) - set(ORB_KEYS)
-        if unknown:
-            raise ValueError(f"orb: unknown key(s) {sorted(unknown)}; the settings are {ORB_KEYS}")
-        kw = dict(orb)
-    else:
-        if len(orb) != 4:
-            raise ValueError("orb must be None, (nlevels, scaleFactor, fastThreshold, scoreType) or a dict of those")
-        kw = dict(zip(ORB_KEYS, orb))
-    try:
-        p = orb_params(what="orb", **kw)
-    except error as e:
-        raise ValueError(str(e)) from e
-    return None if p == ORB_DEFAULTS else p
-
-
-def orb_create(cv2, nfeatures, orb=None):
-    """cv2.ORB_create for the cores: the reference's call when orb is None or the defaults"""
-    p = orb_setting(orb)
-    return cv2.ORB_create(nfeatures=nfeatures) if p is None else cv2.ORB_create(nfeatures=nfeatures, **dict(zip(ORB_KEYS, p)))
-
-
-def fixed_rectify_maps(cv2, maps):
-    """MatcherConfig.rectify as the fixed-point pair cv2.remap reads for both interpolations (None stays None)"""
-    if maps is None:
-        return None
-    m1, m2 = maps
-    if np.asarray(m1).dtype == np.int16:
-        return np.asarray(m1), np.asarray(m2)
-    return cv2.convertMaps(m1, m2, cv2.CV_16SC2)
-
-
-class ImageChain:
-    """The image chain between the camera frame and ORB on the cv2-shaped path, stated here only: [demosaic] -> gray ->
-    resize -> rectify -> CLAHE, the depth following resize and rectify with INTER_NEAREST; it carries ORB's detection mask, which
-    the cores hand to detectAndCompute with the chain's output.  clahe, rectify, resize, bayer, mask: as MatcherConfig's; cv2
-    None: never applied."""
-    def __init__(self, cv2, clahe=None, rectify=None, resize=None, bayer=None, mask=None):
-        self.cv2 = cv2
-        self.mask = mask_setting(mask)
-        self.bayer = bayer_setting(bayer)
-        self.clahe = None if cv2 is None or clahe is None else cv2.createCLAHE(clipLimit=clahe[0], tileGridSize=tuple(clahe[1]))
-        self.rectify = fixed_rectify_maps(cv2, rectify) if cv2 is not None else None
-        self.resize = resize_setting(resize)
-
-    def gray(self, frame):
-        """the camera frame as gray: a BGR frame, or a raw mosaic through the two cvtColor calls of the reference"""
-        cv2 = self.cv2
-        if self.bayer is not None:
-            frame = cv2.cvtColor(frame, self.bayer)
-        return cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY)
-
-    def apply(self, frame, depth_mm=None):
-        cv2 = self.cv2
-        gray = self.gray(frame)
-        if self.resize is not None:
-            gray = cv2.resize(gray, self.resize, interpolation=cv2.INTER_AREA)
-            depth_mm = None if depth_mm is None else cv2.resize(depth_mm, self.resize, interpolation=cv2.INTER_NEAREST)
-        if self.rectify is not None:
-            gray = cv2.remap(gray, *self.rectify, cv2.INTER_LINEAR)
-            depth_mm = None if depth_mm is None else cv2.remap(depth_mm, *self.rectify, cv2.INTER_NEAREST)
-        if self.clahe is not None:
-            gray = self.clahe.apply(gray)
-        return gray, depth_mm
-
-
-def configure_engine(engine, clahe=None, rectify=None, resize=None, bayer=None, mask=None, orb=None):
-    """the same five settings and the ORB parameters on an Engine, which is as large as the camera"""
-    from .cv2_shim import ORB_DEFAULTS
-    engine.set_orb_params(*(orb_setting(orb) or ORB_DEFAULTS))
-    engine.set_orb_mask(mask_setting(mask))
-    engine.set_bayer(bayer_setting(bayer))
-    engine.set_clahe(*((None,) if clahe is None else (clahe[0], tuple(clahe[1]))))
-    engine.set_resize(*((None, None) if resize is None else ((engine.max_w, engine.max_h), resize_setting(resize))))
-    engine.set_rectify(rectify)
-
-
-class LandmarkMatcherCore:
-    def __init__(self, landmarks, log_csv=None, cv2=None, config: MatcherConfig | None = None,
-                 return_landmarks=None, swap_flag=None, logger=None):
-        """landmarks / return_landmarks: a landmarks.pkl path or an already loaded dict."""
+    def __init__(self, landmarks, config, return_landmarks, swap_flag, logger):
         self.cfg = config or MatcherConfig()
-        if cv2 is None:
-            from . import cv2_shim as cv2  # HIP-backed module-level shim
-        self.cv2 = cv2
         self.log = logger or (lambda msg: None)
         self.pkl_path = landmarks if isinstance(landmarks, str) else None
         self._return_src = return_landmarks
         self.swap_flag = swap_flag
         self._swapped = False
-        self._adopt(load_landmarks(landmarks) if isinstance(landmarks, str) else landmarks)
-        self.orb = orb_create(cv2, self.cfg.nfeatures, self.cfg.orb)
-        self.matcher = cv2.BFMatcher(cv2.NORM_HAMMING, crossCheck=True)
-        self.chain = c = ImageChain(cv2, self.cfg.clahe, self.cfg.rectify, self.cfg.resize, self.cfg.bayer, self.cfg.mask)
-        self.clahe, self.rectify, self.resize = c.clahe, c.rectify, c.resize
-        self.dist = np.zeros((4, 1), dtype=np.float32) if len(self.cfg.dist) == 0 else np.asarray(self.cfg.dist, np.float64).reshape(-1, 1)
         self.last_anchor_ts = 0.0
-        self.n_attempts = 0
-        self.n_published = 0
+        self.n_attempts = self.n_published = 0
+        self.log_csv = None
+
+    def _open_csv(self, log_csv):
         self.log_csv = log_csv
         if log_csv:
             d = os.path.dirname(log_csv)
@@ -271,26 +124,27 @@ class LandmarkMatcherCore:
                 f.write(CSV_HEADER)
 
     # ------------------------------------------------------------------ database
+    @staticmethod
+    def _load(src):
+        """a landmarks.pkl path or an already loaded dict"""
+        return load_landmarks(src) if isinstance(src, str) else src
+
     def _adopt(self, data):
         self.pkl_data = data
         self.landmarks = data["landmarks"]
-        self.base_to_cam_t = np.array(data.get("base_to_cam_translation", P.BASE_TO_CAM_TRANSLATION))
-        self.base_to_cam_R = np.array(data.get("base_to_cam_rot", P.BASE_TO_CAM_ROT))
-        self.xy = np.array([[lm["pose"][0], lm["pose"][1]] for lm in self.landmarks], dtype=np.float64).reshape(-1, 2)
-        self.heading = np.array([P.heading_of_camera_pose(lm["pose"], self.base_to_cam_R) for lm in self.landmarks])
         self.n_initial_landmarks = len(self.landmarks)
         self.n_accumulated = 0
 
     def maybe_swap_to_return(self):
-        """Variant X: once the flag file exists, replace the outbound set by the return-leg set."""
+        """Variant X (X:274-294): once the flag file exists the return-leg set replaces the outbound one."""
         if self._swapped or self._return_src is None or not self.swap_flag or not os.path.exists(self.swap_flag):
             return False
-        data = load_landmarks(self._return_src) if isinstance(self._return_src, str) else self._return_src
+        data = self._swap_in()
         if isinstance(self._return_src, str):
             self.pkl_path = self._return_src
         self._adopt(data)
         self._swapped = True
-        self.log(f"[SWAP] return-leg landmarks loaded ({len(self.landmarks)})")
+        self.log(f"[SWAP] return-leg landmarks {self.SWAP_WORD} ({len(self.landmarks)})")
         return True
 
     def save_augmented(self):
@@ -300,6 +154,66 @@ class LandmarkMatcherCore:
             save_landmarks(out, self.pkl_data)
             return out
         return None
+
+    # ------------------------------------------------------------------ one attempt's outcome
+    def _outcome(self, ts, vio_xy, code, n_candidates, n_inliers=0, reproj_err=None, anchor=None, lm_idx=None, relocating=False):
+        """The TickOutcome of an attempt, counted and logged as one CSV row.  code is the tick record's: 0 published, 1
+        curr_no_features, 2 no_candidates, 3 no_pnp_accept, 4 consistency_fail.  The three exits without a pose carry no inliers,
+        error, anchor or record; curr_no_features and consistency_fail carry no relocating, no_candidates reports 0
+        candidates; only published sets published, std and covariance."""
+        if code in (1, 2, 3):
+            o = TickOutcome(ts, vio_xy, 0 if code == 2 else n_candidates, 0, None, None,
+                            (None, "curr_no_features", "no_candidates", "no_pnp_accept")[code], relocating=relocating and code != 1)
+        else:
+            shift = math.hypot(anchor[0] - vio_xy[0], anchor[1] - vio_xy[1])
+            if code == 4:
+                o = TickOutcome(ts, vio_xy, n_candidates, n_inliers, reproj_err, anchor, f"consistency_fail_{shift:.1f}m", lm_idx=lm_idx)
+            else:
+                std = P.anchor_std(n_inliers)
+                self.n_published += 1
+                self.last_anchor_ts = ts
+                o = TickOutcome(ts, vio_xy, n_candidates, n_inliers, reproj_err, anchor, f"published_std{std:.2f}_shift{shift:.1f}",
+                                std=std, covariance=P.anchor_covariance(std), lm_idx=lm_idx, relocating=relocating, published=True)
+        self._csv(o)
+        return o
+
+    def _csv(self, o: TickOutcome):
+        if not self.log_csv:
+            return
+        err = "" if o.reproj_err is None else f"{o.reproj_err:.2f}"
+        ax = o.anchor_pose[0] if o.anchor_pose else ""
+        ay = o.anchor_pose[1] if o.anchor_pose else ""
+        with open(self.log_csv, "a") as f:
+            f.write(f"{o.ts:.3f},{o.vio_xy[0]:.3f},{o.vio_xy[1]:.3f},{o.n_candidates},{o.n_inliers},{err},{ax},{ay},"
+                    f"{o.outcome}\n")
+
+
+class LandmarkMatcherCore(_MatcherSession):
+    SWAP_WORD = "loaded"
+
+    def __init__(self, landmarks, log_csv=None, cv2=None, config: MatcherConfig | None = None,
+                 return_landmarks=None, swap_flag=None, logger=None):
+        """landmarks / return_landmarks: a landmarks.pkl path or an already loaded dict."""
+        super().__init__(landmarks, config, return_landmarks, swap_flag, logger)
+        if cv2 is None:
+            from . import cv2_shim as cv2  # HIP-backed module-level shim
+        self.cv2 = cv2
+        self._adopt(self._load(landmarks))
+        self.chain = c = ImageChain(cv2, self.cfg.front_end, self.cfg.nfeatures)
+        self.orb, self.dist, self.rectify = c.orb, c.dist, c.rectify
+        self.matcher = cv2.BFMatcher(cv2.NORM_HAMMING, crossCheck=True)
+        self._open_csv(log_csv)
+
+    # ------------------------------------------------------------------ database
+    def _adopt(self, data):
+        super()._adopt(data)
+        self.base_to_cam_t = np.array(data.get("base_to_cam_translation", P.BASE_TO_CAM_TRANSLATION))
+        self.base_to_cam_R = np.array(data.get("base_to_cam_rot", P.BASE_TO_CAM_ROT))
+        self.xy = np.array([[lm["pose"][0], lm["pose"][1]] for lm in self.landmarks], dtype=np.float64).reshape(-1, 2)
+        self.heading = np.array([P.heading_of_camera_pose(lm["pose"], self.base_to_cam_R) for lm in self.landmarks])
+
+    def _swap_in(self):
+        return self._load(self._return_src)
 
     # ------------------------------------------------------------------ candidates
     def heading_errors(self, base_pose):
@@ -337,16 +251,6 @@ class LandmarkMatcherCore:
         return [li for _, li in scored[: cfg.reloc_max_candidates]]
 
     # ------------------------------------------------------------------ one attempt
-    def _csv(self, o: TickOutcome):
-        if not self.log_csv:
-            return
-        err = "" if o.reproj_err is None else f"{o.reproj_err:.2f}"
-        ax = o.anchor_pose[0] if o.anchor_pose else ""
-        ay = o.anchor_pose[1] if o.anchor_pose else ""
-        with open(self.log_csv, "a") as f:
-            f.write(f"{o.ts:.3f},{o.vio_xy[0]:.3f},{o.vio_xy[1]:.3f},{o.n_candidates},{o.n_inliers},{err},{ax},{ay},"
-                    f"{o.outcome}\n")
-
     def solve_candidate(self, li, desc_curr, pts_curr_2d, relocating=False):
         """match + PnP + gates + pose composition for one record; returns (n_inl, err, base_pose) or None."""
         cfg, cv2 = self.cfg, self.cv2
@@ -390,7 +294,7 @@ class LandmarkMatcherCore:
     def tick(self, bgr, depth_mm, base_pose, ts=None, drift_est=0.0):
         """One repeat attempt.  bgr: (H,W,3) u8, or the (H,W) u8 mosaic of a raw camera (cfg.bayer); depth_mm: (H,W) u16 or
         None; base_pose: 7-tuple."""
-        cfg, cv2 = self.cfg, self.cv2
+        cfg = self.cfg
         self.maybe_swap_to_return()
         if bgr is None or base_pose is None:
             return None
@@ -398,46 +302,28 @@ class LandmarkMatcherCore:
         self.n_attempts += 1
         vio_xy = (base_pose[0], base_pose[1])
         cand, d, herr = self.select_candidates(base_pose)
-        gray, depth_mm = self.chain.apply(bgr, depth_mm)
-        kpts, desc = self.orb.detectAndCompute(gray, self.chain.mask)
+        kpts, desc, depth_mm = self.chain.features(bgr, depth_mm)
         if desc is None or len(kpts) < cfg.min_matches:
-            o = TickOutcome(ts, vio_xy, len(cand), 0, None, None, "curr_no_features")
-            self._csv(o)
-            return o
+            return self._outcome(ts, vio_xy, 1, len(cand))
         pts2d = np.array([k.pt for k in kpts], dtype=np.float32)
         relocating = False
         if (cfg.global_reloc and not cand and (ts - self.last_anchor_ts) > cfg.reloc_age_s
                 and drift_est > cfg.reloc_drift_m):
             cand = self.global_candidates(desc, herr)
             relocating = True
-        if not cand:
-            o = TickOutcome(ts, vio_xy, 0, 0, None, None, "no_candidates", relocating=relocating)
-            self._csv(o)
-            self.maybe_accumulate(base_pose, desc, pts2d, depth_mm, ts)
-            return o
         best = None
         for li in cand:
             r = self.solve_candidate(li, desc, pts2d, relocating)
             if r is not None and (best is None or r[0] > best[0]):
                 best = (*r, li)
         if best is None:
-            o = TickOutcome(ts, vio_xy, len(cand), 0, None, None, "no_pnp_accept", relocating=relocating)
-            self._csv(o)
+            o = self._outcome(ts, vio_xy, 3 if cand else 2, len(cand), relocating=relocating)
+        else:
+            n_inl, err, anchor, lm_idx = best
+            fail = not relocating and math.hypot(anchor[0] - vio_xy[0], anchor[1] - vio_xy[1]) > cfg.consistency_m
+            o = self._outcome(ts, vio_xy, 4 if fail else 0, len(cand), n_inl, err, anchor, lm_idx, relocating)
+        if not o.published:
             self.maybe_accumulate(base_pose, desc, pts2d, depth_mm, ts)
-            return o
-        n_inl, err, anchor, lm_idx = best
-        shift = math.hypot(anchor[0] - vio_xy[0], anchor[1] - vio_xy[1])
-        if not relocating and shift > cfg.consistency_m:
-            o = TickOutcome(ts, vio_xy, len(cand), n_inl, err, anchor, f"consistency_fail_{shift:.1f}m", lm_idx=lm_idx)
-            self._csv(o)
-            self.maybe_accumulate(base_pose, desc, pts2d, depth_mm, ts)
-            return o
-        std = P.anchor_std(n_inl)
-        self.n_published += 1
-        self.last_anchor_ts = ts
-        o = TickOutcome(ts, vio_xy, len(cand), n_inl, err, anchor, f"published_std{std:.2f}_shift{shift:.1f}", std=std,
-                        covariance=P.anchor_covariance(std), lm_idx=lm_idx, relocating=relocating, published=True)
-        self._csv(o)
         return o
 
     # ------------------------------------------------------------------ accumulation (M:435-500)
@@ -475,26 +361,26 @@ class LandmarkMatcherCore:
         return True
 
 
-class FusedLandmarkMatcher:
+class FusedLandmarkMatcher(_MatcherSession):
     """The whole repeat session through the fused device calls: both landmark databases live in HBM (outbound set and,
     for the split variant X, the return-leg set), a tick uploads one frame (and the depth image when accumulation may
     fire), the device runs candidate search -- local, and the whole-database search of variant G when that finds
     nothing and G's silence / drift conditions hold (G:324-326) -- matching, PnP, gates, pose composition and the
     accumulation of M:435-500, and the host reads back one result record.  Produces the same TickOutcome / CSV rows as
     LandmarkMatcherCore and the reference node."""
+    SWAP_WORD = "selected"
 
     def __init__(self, landmarks, log_csv=None, engine=None, config: MatcherConfig | None = None, seed: int = 0,
                  return_landmarks=None, swap_flag=None, logger=None, exclusive: bool = False):
         """exclusive: this matcher is the only stream of work on the GPU (the reference's deployment: one node, one camera) --
         Engine.set_exclusive, kernels sized for the latency of one tick; results do not depend on it."""
         from .engine import Engine
-        self.cfg = cfg = config or MatcherConfig()
+        super().__init__(landmarks, config, return_landmarks, swap_flag, logger)
+        cfg = self.cfg
         self.engine = e = engine or Engine()
         if exclusive:
             e.set_exclusive(True)
-        self.log = logger or (lambda msg: None)
-        self.pkl_path = landmarks if isinstance(landmarks, str) else None
-        data = load_landmarks(landmarks) if isinstance(landmarks, str) else landmarks
+        data = self._load(landmarks)
         e.set_params(nfeatures=cfg.nfeatures, max_candidates=cfg.max_candidates, min_matches=cfg.min_matches,
                      min_inliers=cfg.min_inliers, ransac_iterations=cfg.ransac_iterations,
                      global_max_candidates=cfg.reloc_max_candidates, global_min_inliers=cfg.reloc_min_inliers,
@@ -505,33 +391,21 @@ class FusedLandmarkMatcher:
                      gray_coeff_bits=cfg.gray_coeff_bits)
         e.set_camera([cfg.fx, cfg.fy, cfg.cx, cfg.cy], data.get("base_to_cam_translation", P.BASE_TO_CAM_TRANSLATION),
                      data.get("base_to_cam_rot", P.BASE_TO_CAM_ROT))
-        e.set_distortion(cfg.dist)
-        configure_engine(e, cfg.clahe, cfg.rectify, cfg.resize, cfg.bayer, cfg.mask, cfg.orb)
-        self._return_src = return_landmarks
-        self.swap_flag = swap_flag
-        self._swapped = False
+        cfg.front_end.configure(e)
         self._return_data = None
         e.db_select(0)
         if return_landmarks is not None:
             # the return-leg set is resident from the start (slot 1); the swap is a pointer flip
-            self._return_data = load_landmarks(return_landmarks) if isinstance(return_landmarks, str) else return_landmarks
+            self._return_data = self._load(return_landmarks)
             e.db_select(1)
             self._upload(self._return_data["landmarks"])
             e.db_select(0)
         self._adopt(data)
         self._upload(self.landmarks)
         self.seed = seed
-        self.last_anchor_ts = 0.0
-        self.n_attempts = self.n_published = 0
         self._img_dev = self._depth_dev = 0
         self._img_cap = self._depth_cap = 0
-        self.log_csv = log_csv
-        if log_csv:
-            d = os.path.dirname(log_csv)
-            if d:
-                os.makedirs(d, exist_ok=True)
-            with open(log_csv, "w") as f:
-                f.write(CSV_HEADER)
+        self._open_csv(log_csv)
 
     # ------------------------------------------------------------------ database
     def _upload(self, landmarks):
@@ -541,31 +415,9 @@ class FusedLandmarkMatcher:
         e.db_reserve(len(poses) + 256, int(off[-1]) + 256 * self.cfg.nfeatures)
         e.db_upload(desc, pts, off, poses)
 
-    def _adopt(self, data):
-        self.pkl_data = data
-        self.landmarks = data["landmarks"]
-        self.n_initial_landmarks = len(self.landmarks)
-        self.n_accumulated = 0
-
-    def maybe_swap_to_return(self):
-        """Variant X (X:274-294): once the flag file exists the return-leg set replaces the outbound one."""
-        if self._swapped or self._return_data is None or not self.swap_flag or not os.path.exists(self.swap_flag):
-            return False
+    def _swap_in(self):
         self.engine.db_select(1)
-        if isinstance(self._return_src, str):
-            self.pkl_path = self._return_src
-        self._adopt(self._return_data)
-        self._swapped = True
-        self.log(f"[SWAP] return-leg landmarks selected ({len(self.landmarks)})")
-        return True
-
-    def save_augmented(self):
-        if self.n_accumulated > 0 and self.pkl_path:
-            out = self.pkl_path.replace(".pkl", "_augmented.pkl")
-            self.pkl_data["landmarks"] = self.landmarks
-            save_landmarks(out, self.pkl_data)
-            return out
-        return None
+        return self._return_data
 
     # ------------------------------------------------------------------ one attempt
     def _stage(self, which, arr):
@@ -622,32 +474,5 @@ class FusedLandmarkMatcher:
                 self.n_accumulated += 1
                 self.log(f"[ACCUM #{self.n_accumulated}] new landmark at ({base_pose[0]:.1f},{base_pose[1]:.1f})  "
                          f"n_kpts={rec['n_features']}  nearest_existing={acc['nearest_m']:.1f}m")
-        vio_xy = (base_pose[0], base_pose[1])
-        oc, reloc = r["outcome"], r["relocating"]
-        if oc == 1:
-            o = TickOutcome(ts, vio_xy, r["n_candidates"], 0, None, None, "curr_no_features")
-        elif oc == 2:
-            o = TickOutcome(ts, vio_xy, 0, 0, None, None, "no_candidates", relocating=reloc)
-        elif oc == 3:
-            o = TickOutcome(ts, vio_xy, r["n_candidates"], 0, None, None, "no_pnp_accept", relocating=reloc)
-        else:
-            anchor = tuple(float(v) for v in r["anchor_pose"])
-            shift = math.hypot(anchor[0] - vio_xy[0], anchor[1] - vio_xy[1])
-            if oc == 4:
-                o = TickOutcome(ts, vio_xy, r["n_candidates"], r["n_inliers"], r["reproj"], anchor,
-                                f"consistency_fail_{shift:.1f}m", lm_idx=r["lm_idx"])
-            else:
-                std = P.anchor_std(r["n_inliers"])
-                self.n_published += 1
-                self.last_anchor_ts = ts
-                o = TickOutcome(ts, vio_xy, r["n_candidates"], r["n_inliers"], r["reproj"], anchor,
-                                f"published_std{std:.2f}_shift{shift:.1f}", std=std, covariance=P.anchor_covariance(std),
-                                lm_idx=r["lm_idx"], relocating=reloc, published=True)
-        if self.log_csv:
-            err = "" if o.reproj_err is None else f"{o.reproj_err:.2f}"
-            ax = o.anchor_pose[0] if o.anchor_pose else ""
-            ay = o.anchor_pose[1] if o.anchor_pose else ""
-            with open(self.log_csv, "a") as f:
-                f.write(f"{o.ts:.3f},{vio_xy[0]:.3f},{vio_xy[1]:.3f},{o.n_candidates},{o.n_inliers},{err},{ax},{ay},"
-                        f"{o.outcome}\n")
-        return o
+        return self._outcome(ts, (base_pose[0], base_pose[1]), r["outcome"], r["n_candidates"], r["n_inliers"], r["reproj"],
+                             tuple(float(v) for v in r["anchor_pose"]), r["lm_idx"], r["relocating"])

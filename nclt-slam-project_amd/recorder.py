@@ -13,8 +13,8 @@ import math
 import numpy as np
 
 from . import pose as P
+from .front_end import FrontEnd, ImageChain
 from .landmarks import new_database, save_landmarks
-from .matcher import ImageChain, configure_engine, orb_create
 
 FX = FY = 320.0
 CX, CY = 320.0, 240.0
@@ -44,37 +44,18 @@ class LandmarkRecorderCore:
                  dist=(), clahe=None, rectify=None, resize=None, bayer=None, mask=None, orb=None):
         """engine: when given, ORB + all per-keypoint gates + back-projection run in ONE device call
         (reloc_record_frame); otherwise the gates run in NumPy on the cv2-shaped module's features.
-        dist: lens distortion as MatcherConfig.dist (OpenCV's k1 k2 p1 p2 [k3], () = pinhole): the kept keypoints are
-        back-projected through the inverse model (engine: reloc_set_distortion; cv2 path: cv2.undistortPoints).
-        clahe: None or (clipLimit, (tiles_x, tiles_y)) as MatcherConfig.clahe: CLAHE between gray conversion and ORB (engine:
-        reloc_set_clahe; cv2 path: cv2.createCLAHE(...).apply), so that the repeat run can equalise the same way.
-        rectify: None or (map1, map2) as MatcherConfig.rectify: the frame is rectified between gray conversion and CLAHE /
-        ORB and the depth read through the same map, nearest (engine: reloc_set_rectify_map; cv2 path: cv2.remap).
-        resize: None or (width, height) as MatcherConfig.resize: the gray frame is resized with INTER_AREA and the depth with
-        INTER_NEAREST before the rectification; the camera and the map are those of the resized image (engine:
-        reloc_set_resize from the engine's full size, which must be the camera's; cv2 path: cv2.resize).
-        bayer: None or "BG" / "GB" / "RG" / "GR" as MatcherConfig.bayer (OpenCV's letters; sensor names RGGB / GRBG / BGGR /
-        GBRG): every frame is the (H, W) uint8 mosaic of a raw camera, demosaiced and converted to gray in front of the
-        resize (engine: reloc_set_bayer; cv2 path: cv2.cvtColor(raw, COLOR_Bayer??2BGR), then COLOR_BGR2GRAY).
-        mask: None or an (H, W) uint8 array as MatcherConfig.mask, of the size of the resized / rectified frame: ORB takes no
-        keypoint where it is zero (engine: reloc_set_orb_mask; cv2 path: the second argument of detectAndCompute).  Teach and
-        repeat usually share it.
-        orb: None or (nlevels, scaleFactor, fastThreshold, scoreType) / a dict as MatcherConfig.orb (engine:
-        reloc_set_orb_params; cv2 path: the keywords of ORB_create).  Teach and repeat share it."""
+        dist, clahe, rectify, resize, bayer, mask, orb: the camera front end, as front_end.FrontEnd describes them."""
         self.engine = engine
-        self.dist = tuple(np.asarray(dist, np.float64).ravel()) if dist is not None else ()
+        self.front_end = fe = FrontEnd(dist, clahe, rectify, resize, bayer, mask, orb)
         if engine is not None:
-            engine.set_distortion(self.dist)
-            configure_engine(engine, clahe, rectify, resize, bayer, mask, orb)
+            fe.configure(engine)
         self.nfeatures = nfeatures
         if cv2 is None and engine is None:
             from . import cv2_shim as cv2
         self.cv2 = cv2
         self.out_pkl = out_pkl
         self.min_disp_m = float(min_disp_m)
-        self.orb = orb_create(cv2, nfeatures, orb) if cv2 is not None else None
-        self.chain = c = ImageChain(cv2, clahe, rectify, resize, bayer, mask)
-        self.clahe, self.rectify, self.resize = c.clahe, c.rectify, c.resize
+        self.chain = None if engine is not None else ImageChain(cv2, fe, nfeatures)
         self.landmarks = []
         self.last_landmark_pose_world = None
         self.log = logger or (lambda msg: None)
@@ -97,8 +78,7 @@ class LandmarkRecorderCore:
             self.landmarks.append(rec)
             self.last_landmark_pose_world = cam_pose
             return rec
-        gray, depth_mm = self.chain.apply(bgr, depth_mm)
-        kpts, desc = self.orb.detectAndCompute(gray, self.chain.mask)
+        kpts, desc, depth_mm = self.chain.features(bgr, depth_mm)
         if desc is None or len(kpts) == 0:
             return None
         xy = np.array([k.pt for k in kpts], dtype=np.float32)
@@ -113,7 +93,7 @@ class LandmarkRecorderCore:
         if ok.sum() < MIN_RECORD_KPTS:
             return None
         uu, vv, z = uu[ok], vv[ok], z[ok]
-        pts3 = P.back_project(self.cv2, uu, vv, z, FX, FY, CX, CY, self.dist)
+        pts3 = P.back_project(self.cv2, uu, vv, z, FX, FY, CX, CY, self.chain.dist)
         rec = {"pose": cam_pose, "descriptors": desc[ok], "keypoints_2d": xy[ok], "keypoints_3d_cam": pts3,
                "ts": rgb_ts, "n_features": int(len(pts3))}
         self.landmarks.append(rec)

@@ -16,6 +16,7 @@ import sys
 
 import numpy as np
 
+from .front_end import add_front_end_flags, front_end_flags, load_mask  # noqa: F401  (load_mask: part of this module's interface)
 from .matcher import FusedLandmarkMatcher, LandmarkMatcherCore, MatcherConfig
 from .recorder import LandmarkRecorderCore
 
@@ -37,7 +38,7 @@ BAYER_ENCODINGS = {"bayer_rggb8": "BG", "bayer_grbg8": "GB", "bayer_bggr8": "RG"
 
 
 def img_msg_to_frame(msg, bayer=None):
-    """the colour topic's frame as the cores take it: BGR, or with bayer = "BG" / "GB" / "RG" / "GR" (MatcherConfig.bayer) the
+    """the colour topic's frame as the cores take it: BGR, or with bayer = "BG" / "GB" / "RG" / "GR" (FrontEnd.bayer) the
     camera's raw 8-bit mosaic, undecoded: mono8 (the driver does not name the pattern) or the bayer_* encoding of that pattern"""
     if bayer is None:
         return img_msg_to_bgr(msg)
@@ -54,17 +55,6 @@ def img_msg_to_depth_mm(msg):
         mm = np.frombuffer(msg.data, dtype=np.float32).reshape(msg.height, msg.width) * 1000.0
         return np.nan_to_num(mm, nan=0.0, posinf=0.0, neginf=0.0).astype(np.uint16)
     raise ValueError(f"unexpected depth encoding {msg.encoding}")
-
-
-def load_mask(path):
-    """--mask FILE.npy: ORB's detection mask (MatcherConfig.mask) from a NumPy file holding an (H, W) uint8 array; no image
-    decoder is involved, a PNG mask is converted once with np.save.  None stays None."""
-    if path is None:
-        return None
-    m = np.load(path, allow_pickle=False)
-    if m.dtype != np.uint8 or m.ndim != 2 or m.size == 0:
-        raise ValueError(f"--mask {path}: expected an (H, W) uint8 array, got {m.dtype} {m.shape}")
-    return np.ascontiguousarray(m)
 
 
 def read_pose_file(path=POSE_FILE):
@@ -92,8 +82,8 @@ def _node_base():
 def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global_reloc=False, fused=False, cv2=None, bayer=None,
                       mask=None, orb=None):
     """cv2: the cv2-shaped module the ROS-free core calls (default: the HIP shim); only the non-fused core uses it.
-    bayer: MatcherConfig.bayer -- the colour topic carries raw mosaics, passed through undecoded.  mask: MatcherConfig.mask.
-    orb: MatcherConfig.orb"""
+    bayer: FrontEnd.bayer -- the colour topic carries raw mosaics, passed through undecoded.  mask: FrontEnd.mask.
+    orb: FrontEnd.orb"""
     from geometry_msgs.msg import PoseWithCovarianceStamped
     from sensor_msgs.msg import Image
     Node = _node_base()
@@ -195,33 +185,31 @@ def make_recorder_node(out_pkl, min_disp_m=2.0, cv2=None, bayer=None, mask=None,
     return VisualLandmarkRecorder()
 
 
-MASK_HELP = "ORB takes no keypoint where this (H, W) uint8 array (a .npy file, size of the frame ORB sees) is zero"
-
-
-def add_orb_flags(ap):
-    """--orb-nlevels, --orb-scale-factor, --orb-fast-threshold, --orb-score: MatcherConfig.orb (cv2.ORB_create's keywords)"""
-    ap.add_argument("--orb-nlevels", type=int, default=None, metavar="N", help="ORB pyramid levels, 1..8 (default 8)")
-    ap.add_argument("--orb-scale-factor", type=float, default=None, metavar="S", help="ORB pyramid scale factor, 1.01..2.0 (default 1.2)")
-    ap.add_argument("--orb-fast-threshold", type=int, default=None, metavar="T", help="ORB FAST threshold, 1..254 (default 20)")
-    ap.add_argument("--orb-score", default=None, choices=["harris", "fast"], help="ORB score type (default harris)")
-
-
-def orb_flags(args):
-    """MatcherConfig.orb of the --orb-* flags: None when none is given, else the checked tuple (a bad value: ValueError)"""
-    from .matcher import ORB_KEYS, orb_setting
-    given = dict(zip(ORB_KEYS, (args.orb_nlevels, args.orb_scale_factor, args.orb_fast_threshold,
-                                None if args.orb_score is None else int(args.orb_score == "fast"))))
-    given = {k: v for k, v in given.items() if v is not None}
-    return orb_setting(given) if given else None
-
-
 def _chain_args(args):
     """the trailing (cv2, bayer, mask, orb) of the node factories; cv2 None = the default shim; only as far as the last one
     that is not its default, nothing when all are defaults"""
-    tail = [None, args.bayer, load_mask(args.mask), orb_flags(args)]
+    tail = [None, *front_end_flags(args)]
     while tail and tail[-1] is None:
         tail.pop()
     return tuple(tail)
+
+
+def _spin(make_node, save):
+    """one node's rclpy session: spin until interrupted, then call the core's `save` method and shut down"""
+    import rclpy
+    rclpy.init()
+    node = make_node()
+    try:
+        rclpy.spin(node)
+    except KeyboardInterrupt:
+        pass
+    finally:
+        getattr(node.core, save)()
+        node.destroy_node()
+        try:
+            rclpy.shutdown()
+        except Exception:
+            pass
 
 
 def matcher_main(argv=None):
@@ -232,47 +220,18 @@ def matcher_main(argv=None):
     ap.add_argument("--swap-flag", default="/tmp/matcher_swap_return.txt")
     ap.add_argument("--global-reloc", action="store_true")
     ap.add_argument("--fused", action="store_true", help="run the whole tick in one device call")
-    ap.add_argument("--bayer", default=None, choices=["BG", "GB", "RG", "GR"], help="the colour topic carries raw 8-bit mosaics of this pattern")
-    ap.add_argument("--mask", default=None, metavar="FILE.npy", help=MASK_HELP)
-    add_orb_flags(ap)
+    add_front_end_flags(ap)
     args = ap.parse_args(argv)
     raw = _chain_args(args)
-    import rclpy
-    rclpy.init()
-    node = make_matcher_node(args.landmarks, args.out_csv, args.landmarks_return, args.swap_flag, args.global_reloc, args.fused, *raw)
-    try:
-        rclpy.spin(node)
-    except KeyboardInterrupt:
-        pass
-    finally:
-        node.core.save_augmented()
-        node.destroy_node()
-        try:
-            rclpy.shutdown()
-        except Exception:
-            pass
+    _spin(lambda: make_matcher_node(args.landmarks, args.out_csv, args.landmarks_return, args.swap_flag, args.global_reloc, args.fused, *raw),
+          "save_augmented")
 
 
 def recorder_main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
     ap.add_argument("--min-disp", type=float, default=2.0)
-    ap.add_argument("--bayer", default=None, choices=["BG", "GB", "RG", "GR"], help="the colour topic carries raw 8-bit mosaics of this pattern")
-    ap.add_argument("--mask", default=None, metavar="FILE.npy", help=MASK_HELP)
-    add_orb_flags(ap)
+    add_front_end_flags(ap)
     args = ap.parse_args(argv)
     raw = _chain_args(args)
-    import rclpy
-    rclpy.init()
-    node = make_recorder_node(args.out, args.min_disp, *raw)
-    try:
-        rclpy.spin(node)
-    except KeyboardInterrupt:
-        pass
-    finally:
-        node.core.save()
-        node.destroy_node()
-        try:
-            rclpy.shutdown()
-        except Exception:
-            pass
+    _spin(lambda: make_recorder_node(args.out, args.min_disp, *raw), "save")

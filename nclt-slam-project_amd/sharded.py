@@ -149,12 +149,11 @@ class HipShard:
     that many contexts (each with the shard uploaded and its own stream) so the frames of a batch overlap."""
 
     def __init__(self, engine, desc, pts3d, offsets, poses, rank: int, world: int, w=640, h=480, n_slots: int = 1, orb=None):
-        """orb: None = the engine's ORB parameters as they are, or MatcherConfig.orb: set on the engine; every slot (and every
+        """orb: None = the engine's ORB parameters as they are, or FrontEnd.orb: set on the engine; every slot (and every
         context a pipeline makes with set_params_from) carries the engine's, as the contexts of a batch must"""
         from .engine import Engine
-        from .matcher import orb_setting
+        from .front_end import ORB_DEFAULTS, orb_setting
         if orb is not None:
-            from .cv2_shim import ORB_DEFAULTS
             engine.set_orb_params(*(orb_setting(orb) or ORB_DEFAULTS))
         bounds = shard_by_rows(offsets, world)
         a, b = int(bounds[rank]), int(bounds[rank + 1])

@@ -136,7 +136,8 @@ def test_shim_cvtcolor_bayer_and_its_refusals():
 
 
 def test_settings():
-    from nclt_slam_project_amd.matcher import MatcherConfig, bayer_setting
+    from nclt_slam_project_amd.front_end import bayer_setting
+    from nclt_slam_project_amd.matcher import MatcherConfig
     assert MatcherConfig().bayer is None and bayer_setting(None) is None
     assert [bayer_setting(p) for p in ("BG", "GB", "RG", "GR", "gr")] == [46, 47, 48, 49, 49]
     for bad in ("RGGB", "", "XX", 49):

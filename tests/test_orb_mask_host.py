@@ -147,11 +147,12 @@ def test_engine_mask_argument_checks():
 
 # ---- settings ----------------------------------------------------------------------------------------------------------------
 def test_settings():
-    from nclt_slam_project_amd.matcher import ImageChain, MatcherConfig, mask_setting
+    from nclt_slam_project_amd.front_end import FrontEnd, ImageChain, mask_setting
+    from nclt_slam_project_amd.matcher import MatcherConfig
     assert MatcherConfig().mask is None and mask_setting(None) is None and ImageChain(None).mask is None
     m = MR.half_band(64, 64)
     np.testing.assert_array_equal(mask_setting(m), m)
-    np.testing.assert_array_equal(ImageChain(None, mask=m).mask, m)
+    np.testing.assert_array_equal(ImageChain(None, FrontEnd(mask=m)).mask, m)
     for bad in (m.astype(np.float32), m[:, :, None], np.zeros((0, 0), np.uint8), "mask.npy"):
         with pytest.raises(ValueError):
             mask_setting(bad)

@@ -174,7 +174,8 @@ def test_getters_setters_and_two_objects_on_one_backend(oracle):
 
 def test_settings_reach_the_cores_and_configure_engine(oracle):
     from nclt_slam_project_amd import synth
-    from nclt_slam_project_amd.matcher import LandmarkMatcherCore, MatcherConfig, configure_engine, orb_setting
+    from nclt_slam_project_amd.front_end import orb_setting
+    from nclt_slam_project_amd.matcher import LandmarkMatcherCore, MatcherConfig, configure_engine
     from nclt_slam_project_amd.recorder import LandmarkRecorderCore
     assert MatcherConfig().orb is None and orb_setting(None) is None and orb_setting((8, 1.2, 20, 0)) is None
     assert orb_setting(dict(fastThreshold=7)) == (8, 1.2, 7, 0) and orb_setting([4, 1.5, 20, 1]) == (4, 1.5, 20, 1)
