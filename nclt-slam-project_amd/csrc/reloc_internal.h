@@ -91,6 +91,12 @@ struct TickResult {
     int32_t pad[2];       // 96 bytes; pad[0] of a record in HOST memory: the tick's sequence stamp, stored last (reloc_tick_wait)
 };
 static_assert(sizeof(TickResult) == 96, "TickResult is the 96-byte record documented in include/reloc.h");
+// the same offsets as the TICK_RESULT dtype of engine.py, which is how Python reads a record
+static_assert(offsetof(TickResult, anchor_pose) == 0 && offsetof(TickResult, reproj) == 56, "TickResult layout");
+static_assert(offsetof(TickResult, n_inl) == 64 && offsetof(TickResult, lm_idx) == 68 && offsetof(TickResult, outcome) == 72,
+              "TickResult layout");
+static_assert(offsetof(TickResult, n_candidates) == 76 && offsetof(TickResult, n_features) == 80 &&
+              offsetof(TickResult, relocating) == 84 && offsetof(TickResult, pad) == 88, "TickResult layout");
 
 // what reloc_tick_accumulate_dev left behind (device resident)
 struct AccumResult {

@@ -17,6 +17,21 @@ K4_DEFAULT = np.array([320.0, 320.0, 320.0, 240.0], dtype=np.float64)  # fx fy c
 OUTCOME_NAMES = {0: "published", 1: "curr_no_features", 2: "no_candidates", 3: "no_pnp_accept",
                  4: "consistency_fail"}
 
+MAX_CAND = 32           # candidates of one tick (MAX_CAND of csrc/reloc_internal.h): the longest top-k / candidate list
+
+# The 96-byte result record of a tick (include/reloc.h at reloc_tick_result_dev / reloc_tick_result_to; struct TickResult
+# of csrc/reloc_internal.h, whose static_asserts hold these offsets).  `seq`: the tick's stamp, in HOST records only.
+TICK_RESULT = np.dtype(dict(
+    names=["anchor_pose", "reproj", "n_inliers", "lm_idx", "outcome", "n_candidates", "n_features", "relocating", "seq", "pad"],
+    formats=[("<f8", 7), "<f8"] + ["<i4"] * 8, offsets=[0, 56, 64, 68, 72, 76, 80, 84, 88, 92], itemsize=96))
+
+
+def tick_result_dict(rec) -> dict:
+    """one TICK_RESULT record as the dict Engine.tick_result() returns"""
+    return dict(anchor_pose=rec["anchor_pose"].copy(), n_inliers=int(rec["n_inliers"]), reproj=float(np.float32(rec["reproj"])),
+                lm_idx=int(rec["lm_idx"]), outcome=int(rec["outcome"]), n_candidates=int(rec["n_candidates"]),
+                n_features=int(rec["n_features"]), relocating=bool(rec["relocating"]))
+
 
 class _PinnedBlock:
     """one hipHostMalloc allocation, freed with its last reference"""
@@ -42,6 +57,7 @@ class Engine:
         self.device = device
         self.max_w, self.max_h, self.max_feat = max_w, max_h, max_feat
         self._bayer = None          # set_bayer's code: the frames of tick / record_frame are then (H, W) mosaics
+        self._topk_dev = self._cand_dev = 0     # device scratch of the scan / solve halves (_halves_scratch)
 
     # ------------------------------------------------------------------ lifetime / plumbing
     def close(self):
@@ -709,8 +725,8 @@ class Engine:
         return d
 
     def tick_debug(self):
-        ids = np.zeros(32, np.int32); n = C.c_int32(); nm = np.zeros(32, np.int32); ni = np.zeros(32, np.int32)
-        ok = np.zeros(32, np.int32); rep = np.zeros(32); Rt = np.zeros((32, 12))
+        ids, nm, ni, ok = (np.zeros(MAX_CAND, np.int32) for _ in range(4))
+        n = C.c_int32(); rep = np.zeros(MAX_CAND); Rt = np.zeros((MAX_CAND, 12))
         N.check(self._lib.reloc_tick_debug(self._ctx, N.ptr(ids), C.byref(n), N.ptr(nm), N.ptr(ni), N.ptr(ok), N.ptr(rep),
                                            N.ptr(Rt)), "reloc_tick_debug")
         k = n.value
@@ -791,14 +807,18 @@ class Engine:
         N.check(engines[0]._lib.reloc_shard_solve_batch_dev(ctxs, n, C.c_void_p(cand_local_dev), int(k), N.ptr(bp), N.ptr(sd),
                                                             C.c_void_p(res_out)), "reloc_shard_solve_batch_dev")
 
+    def _halves_scratch(self):
+        """the engine's own buffers for the scan / solve halves, made on first use: MAX_CAND ids, MAX_CAND counts and the
+        feature count of the last scan (_topk_dev), MAX_CAND candidate ids for the solve (_cand_dev)"""
+        if not self._topk_dev:
+            self._topk_dev = self.dev_alloc((3 * MAX_CAND + 1) * 4)
+            self._cand_dev = self._topk_dev + (2 * MAX_CAND + 1) * 4
+
     def tick_scan_enqueue(self, img_dev: int, w: int, h: int, base_pose=None, k: int = 25, order_rgb=False):
         """ORB + whole-shard scan + local top-k, enqueued on the ctx stream; read with tick_scan_fetch(k)."""
-        if not hasattr(self, "_topk_dev"):
-            self._topk_dev = self.dev_alloc(2 * 32 * 4)
-        bp = None if base_pose is None else np.ascontiguousarray(base_pose, np.float64).reshape(7)
-        N.check(self._lib.reloc_tick_scan_dev(self._ctx, C.c_void_p(img_dev), w, h, int(order_rgb), N.ptr(bp),
-                                              C.c_void_p(self._topk_dev), C.c_void_p(self._topk_dev + 128), int(k)),
-                "reloc_tick_scan_dev")
+        self._halves_scratch()
+        t = self._topk_dev
+        self.tick_scan_into(img_dev, w, h, base_pose, k, t, t + 4 * MAX_CAND, t + 8 * MAX_CAND, order_rgb)
 
     def orb_frame_dev(self, img_dev: int, w: int, h: int, stride: int | None = None, order_rgb=False, nfeatures: int = 500) -> int:
         """gray + ORB of an interleaved 3-channel frame (with the Bayer stage on: a single-channel mosaic, stride in its bytes)
@@ -840,11 +860,9 @@ class Engine:
 
     def tick_scan_fetch(self, k: int = 25):
         """(local record ids (k,), counts (k,), n_features) of the last enqueued scan, -1 / 0 padded (synchronises the stream)."""
-        buf = np.empty(64, np.int32); nf = np.empty(1, np.int32)
-        N.check(self._lib.reloc_d2h(self._ctx, N.ptr(buf), C.c_void_p(self._topk_dev), buf.nbytes), "reloc_d2h")
-        N.check(self._lib.reloc_d2h(self._ctx, N.ptr(nf), C.c_void_p(self._lib.reloc_frame_count_dev(self._ctx)), 4), "reloc_d2h")
-        self.sync()
-        return buf[:k].copy(), buf[32:32 + k].copy(), int(nf[0])
+        buf = np.empty(2 * MAX_CAND + 1, np.int32)
+        self.d2h(buf, self._topk_dev)
+        return buf[:k].copy(), buf[MAX_CAND:MAX_CAND + k].copy(), int(buf[2 * MAX_CAND])
 
     def tick_scan(self, img_dev: int, w: int, h: int, base_pose=None, k: int = 25, order_rgb=False):
         self.tick_scan_enqueue(img_dev, w, h, base_pose, k, order_rgb)
@@ -853,14 +871,11 @@ class Engine:
     def tick_solve_enqueue(self, local_ids, base_pose, check_consistency: bool, seed: int = 0):
         """matches + PnP + gates for the listed LOCAL record ids against the features of the last scan; read with
         tick_result()."""
-        ids = np.full(32, -1, np.int32)
+        ids = np.full(MAX_CAND, -1, np.int32)
         ids[: len(local_ids)] = local_ids
-        if not hasattr(self, "_cand_dev"):
-            self._cand_dev = self.dev_alloc(32 * 4)
+        self._halves_scratch()
         self.h2d(self._cand_dev, ids)
-        bp = np.ascontiguousarray(base_pose, np.float64).reshape(7)
-        N.check(self._lib.reloc_tick_solve_dev(self._ctx, C.c_void_p(self._cand_dev), len(local_ids), N.ptr(bp),
-                                               int(check_consistency), int(seed)), "reloc_tick_solve_dev")
+        self.tick_solve_from(self._cand_dev, len(local_ids), base_pose, check_consistency, seed)
 
     def tick_solve(self, local_ids, base_pose, check_consistency: bool, seed: int = 0):
         self.tick_solve_enqueue(local_ids, base_pose, check_consistency, seed)

@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from .engine import TICK_RESULT, Engine, tick_result_dict
 from .landmarks import shard_by_rows
 
 K_GLOBAL = 25
@@ -45,7 +46,8 @@ def matrix_row_block(n_rows: int, rank: int, world: int):
 
 class ShardedRelocalizer:
     """backend: an object with
-         scan(frame, base_pose, k, slot) -> (local ids (k,), counts (k,)) padded with -1 / 0
+         scan(frame, base_pose, k, slot) -> (local ids (k,), counts (k,), n_features) padded with -1 / 0; n_features -1
+             from a rank that did not extract (an empty shard)
          solve(local_ids, base_pose, check_consistency, seed, slot)
              -> dict(outcome, n_inliers, reproj, anchor_pose, lm_idx)
        `slot` names which of the batch's frames the call is about (solve works on the features the scan of the same
@@ -57,6 +59,12 @@ class ShardedRelocalizer:
         # curr_no_features gate (M:307): the matcher parameter of the shard's engine when there is one
         eng = getattr(backend, "engine", None)
         self.min_features = int(eng.get_params().min_matches) if eng is not None and hasattr(eng, "get_params") else MIN_FEATURES
+        # the batch methods are optional: frame by frame for a backend without them
+        be = backend
+        self._scan_batch = getattr(be, "scan_batch", None) or (
+            lambda frames, bps, k: [be.scan(f, bps[i], k, i) for i, f in enumerate(frames)])
+        self._solve_batch = getattr(be, "solve_batch", None) or (
+            lambda jobs, bps, seeds: [be.solve(ids, bps[i], False, seeds[i], i) for i, ids in jobs])
 
     def _all_gather(self, arr: np.ndarray) -> np.ndarray:
         if self.world == 1:
@@ -80,68 +88,34 @@ class ShardedRelocalizer:
         top-k lists (B x 400 bytes per rank), one of the B result records (B x 96 bytes)."""
         B = len(frames)
         seeds = list(seeds) if seeds is not None else [0] * B
-        be = self.backend
-        if hasattr(be, "scan_batch"):
-            scans = be.scan_batch(frames, base_poses, k)
-        else:
-            scans = [be.scan(frames[i], base_poses[i], k, i) for i in range(B)]
-        # per frame: k global ids, k counts, and the frame's feature count (-1 from a rank that did not extract: an empty
-        # shard) -- the reference decides `curr_no_features` before any candidate work (M:307-309)
+        # per frame: k global ids, k counts, and the frame's feature count -- the reference decides `curr_no_features`
+        # before any candidate work (M:307-309)
         packed = np.zeros((B, 2 * k + 1), np.int64)
-        for i, scan in enumerate(scans):
-            lids, cnts = scan[0], scan[1]
+        for i, (lids, cnts, n_features) in enumerate(self._scan_batch(frames, base_poses, k)):
             packed[i, :k] = np.where(lids >= 0, lids + self.base, -1)
             packed[i, k:2 * k] = cnts
-            packed[i, 2 * k] = scan[2] if len(scan) > 2 else self.min_features
+            packed[i, 2 * k] = n_features
         allp = self._all_gather(packed)                                       # (world, B, 2k + 1)
         n_feat = allp[:, :, 2 * k].max(axis=0)
-        winners, jobs = [], []
+        win_gid, jobs = np.full((B, k), -1, np.int64), []
         for i in range(B):
-            if n_feat[i] < self.min_features:
-                winners.append((np.zeros(0, np.int64), []))
-                continue
-            win_ids, _ = merge_topk(allp[:, i, :k], allp[:, i, k:2 * k], k)
-            mine = [(pos, int(g - self.base)) for pos, g in enumerate(win_ids) if self._owns(int(g))]
-            winners.append((win_ids, mine))
-            if mine:
-                jobs.append((i, [l for _, l in mine]))
-        if hasattr(be, "solve_batch"):
-            solved = be.solve_batch(jobs, base_poses, seeds)
-        else:
-            solved = [be.solve(ids, base_poses[i], False, seeds[i], i) for i, ids in jobs]
-        res = np.zeros((B, 12), np.float64)                                   # [pos, n_inl, reproj, outcome, gid, pose7]
-        for i in range(B):
-            res[i, 0] = 1e9
-            res[i, 3] = 1 if n_feat[i] < self.min_features else (3 if len(winners[i][0]) else 2)
-        for (i, _), r in zip(jobs, solved):
-            mine = winners[i][1]
-            if r["outcome"] in (0, 4):
-                pos = next(p for p, l in mine if l == r["lm_idx"])
-                res[i, :5] = [pos, r["n_inliers"], r["reproj"], r["outcome"], r["lm_idx"] + self.base]
-                res[i, 5:] = r["anchor_pose"]
-            elif r["outcome"] == 1:
-                res[i, 3] = 1
-        allr = self._all_gather(res)                                          # (world, B, 12)
-        out = []
-        for i in range(B):
-            ar, n_cand = allr[:, i], len(winners[i][0])
-            none = dict(n_inliers=0, reproj=0.0, anchor_pose=np.zeros(7), lm_idx=-1, n_candidates=n_cand)
-            if (ar[:, 3] == 1).any():
-                out.append(dict(outcome=1, **none))
-                continue
-            ok = ar[:, 1] > 0
-            if not ok.any():
-                out.append(dict(outcome=int(res[i, 3]), **none))
-                continue
-            # most inliers, earliest in the global candidate order on ties (reference M:379)
-            best = min(np.nonzero(ok)[0], key=lambda j: (-ar[j, 1], ar[j, 0]))
-            b = ar[best]
-            out.append(dict(outcome=int(b[3]), n_inliers=int(b[1]), reproj=float(b[2]), anchor_pose=b[5:].copy(),
-                            lm_idx=int(b[4]), n_candidates=n_cand))
-        return out
-
-    def _owns(self, gid: int) -> bool:
-        return self.base <= gid < self.base + self.backend.n_records
+            if n_feat[i] >= self.min_features:
+                ids, _ = merge_topk(allp[:, i, :k], allp[:, i, k:2 * k], k)
+                win_gid[i, :len(ids)] = ids
+                mine = [int(g) - self.base for g in ids if self.base <= g < self.base + self.backend.n_records]
+                if mine:
+                    jobs.append((i, mine))
+        # this rank's result records, as the device path's solve half stores them but with GLOBAL lm_idx; a frame none of
+        # whose winners live here keeps no_candidates, which is never picked
+        rec = np.zeros(B, TICK_RESULT)
+        rec["outcome"], rec["lm_idx"] = 2, -1
+        for (i, _), r in zip(jobs, self._solve_batch(jobs, base_poses, seeds)):
+            o = rec[i]
+            o["outcome"], o["n_inliers"], o["reproj"], o["anchor_pose"] = r["outcome"], r["n_inliers"], r["reproj"], r["anchor_pose"]
+            o["lm_idx"] = r["lm_idx"] + self.base if r["lm_idx"] >= 0 else -1
+            o["relocating"] = r.get("relocating", False)
+        allr = self._all_gather(rec.view(np.uint8).reshape(B, TICK_RESULT.itemsize))     # (world, B, 96)
+        return pick_results(allr, win_gid, n_feat, None, self.min_features)
 
 
 class HipShard:
@@ -150,23 +124,31 @@ class HipShard:
 
     def __init__(self, engine, desc, pts3d, offsets, poses, rank: int, world: int, w=640, h=480, n_slots: int = 1, orb=None):
         """orb: None = the engine's ORB parameters as they are, or FrontEnd.orb: set on the engine; every slot (and every
-        context a pipeline makes with set_params_from) carries the engine's, as the contexts of a batch must"""
-        from .engine import Engine
+        context a pipeline makes with new_slot) carries the engine's, as the contexts of a batch must"""
         from .front_end import ORB_DEFAULTS, orb_setting
         if orb is not None:
             engine.set_orb_params(*(orb_setting(orb) or ORB_DEFAULTS))
         bounds = shard_by_rows(offsets, world)
         a, b = int(bounds[rank]), int(bounds[rank + 1])
-        off = np.asarray(offsets[a:b + 1], np.int64) - int(offsets[a])
-        self.engines = [engine] + [Engine(engine.device, engine.max_w, engine.max_h, engine.max_feat) for _ in range(n_slots - 1)]
-        for e in self.engines[1:]:
-            e.set_orb_params(*engine.get_orb_params())
+        self.engine, self.base, self.n_records, self.w, self.h = engine, a, b - a, w, h
         if b > a:
             # one resident copy of the shard; the other slots (streams) scan it through reloc_db_share
+            off = np.asarray(offsets[a:b + 1], np.int64) - int(offsets[a])
             engine.db_upload(desc[offsets[a]:offsets[b]], pts3d[offsets[a]:offsets[b]], off, poses[a:b])
-            for e in self.engines[1:]:
-                e.db_share(engine)
-        self.engine, self.base, self.n_records, self.w, self.h = engine, a, b - a, w, h
+        self.engines = [engine] + [self.new_slot() for _ in range(n_slots - 1)]
+
+    def new_slot(self, stream: int | None = None):
+        """a sibling context of the shard's engine: same device and capacities, the shard's records (reloc_db_share), the
+        engine's matcher and ORB parameters, its own stream or `stream`.  Camera, distortion and the FrontEnd stages are
+        not copied.  The caller closes it."""
+        e0 = self.engine
+        e = Engine(e0.device, e0.max_w, e0.max_h, e0.max_feat)
+        if self.n_records:
+            e.db_share(e0)
+        e.set_params_from(e0)
+        if stream is not None:
+            e.set_stream(stream)
+        return e
 
     def _empty(self, k):
         return np.full(k, -1, np.int32), np.zeros(k, np.int32), -1
@@ -222,34 +204,32 @@ def merge_topk_tensor(all_scan, k: int, base: int, n_local: int):
 
 
 def pick_results(res_all: np.ndarray, win_gid: np.ndarray, n_feat: np.ndarray, bases, min_features=MIN_FEATURES):
-    """res_all: (W, B, 96) uint8 TickResult records of every rank; win_gid (B, k); bases: first global id of every rank.
-    The anchor of a frame = most inliers, earliest position in the global candidate order on ties (M:379)."""
-    W, B, _ = res_all.shape
-    f64 = res_all.view(np.float64).reshape(W, B, 12)
-    i32 = res_all.view(np.int32).reshape(W, B, 24)
-    out = []
-    for i in range(B):
-        n_cand = int((win_gid[i] >= 0).sum())
-        none = dict(n_inliers=0, reproj=0.0, anchor_pose=np.zeros(7), lm_idx=-1, n_candidates=n_cand)
-        if n_feat[i] < min_features:
-            out.append(dict(outcome=1, **{**none, "n_candidates": 0}))
-            continue
-        best = None
-        for r in range(W):
-            oc, n_inl, lm = int(i32[r, i, 18]), int(i32[r, i, 16]), int(i32[r, i, 17])
-            if oc not in (0, 4) or lm < 0:
-                continue
-            g = lm + int(bases[r])
-            pos = int(np.nonzero(win_gid[i] == g)[0][0])
-            if best is None or (n_inl, -pos) > (best[0], -best[1]):
-                best = (n_inl, pos, r, g, oc)
-        if best is None:
-            out.append(dict(outcome=3 if n_cand else 2, **none))
-            continue
-        n_inl, pos, r, g, oc = best
-        out.append(dict(outcome=oc, n_inliers=n_inl, reproj=float(np.float32(f64[r, i, 7])), anchor_pose=f64[r, i, :7].copy(),
-                        lm_idx=g, n_candidates=n_cand))
-    return out
+    """res_all: (W, B, 96) uint8 TICK_RESULT records of every rank; win_gid (B, k) global ids of the winners, -1 padded;
+    bases: first global id of every rank (the records' lm_idx are local), or None: lm_idx are global already.
+    THE anchor rule of the sharded path, per frame:
+      fewer than min_features features              -> curr_no_features (1), no candidates
+      a rank whose solve reports curr_no_features   -> 1
+      the records with outcome 0 / 4                -> the one with most inliers, the earliest of the winners' order on
+                                                       ties (M:379), with global lm_idx
+      no such record                                -> no_pnp_accept (3) if there are winners, else no_candidates (2)
+    Returns one dict per frame with the keys of Engine.tick_result() (engine.tick_result_dict)."""
+    W, B = res_all.shape[:2]
+    rec = res_all.view(TICK_RESULT).reshape(W, B)
+    oc, n_inl, lm = rec["outcome"], rec["n_inliers"], rec["lm_idx"]
+    gid = lm if bases is None else lm + np.asarray(bases, lm.dtype)[:, None]
+    ok = ((oc == 0) | (oc == 4)) & (lm >= 0)
+    n_cand = (win_gid >= 0).sum(axis=1)
+    few = np.asarray(n_feat) < min_features
+    none = few | (oc == 1).any(axis=0)
+    out = np.zeros(B, TICK_RESULT)
+    out["lm_idx"], out["outcome"] = -1, np.where(none, 1, np.where(n_cand > 0, 3, 2))
+    for i in np.nonzero(ok.any(axis=0) & ~none)[0]:
+        rs = np.nonzero(ok[:, i])[0]
+        r = rs[0] if len(rs) == 1 else min(rs, key=lambda r: (-n_inl[r, i], np.nonzero(win_gid[i] == gid[r, i])[0][0]))
+        out[i] = rec[r, i]
+        out["lm_idx"][i] = gid[r, i]
+    out["n_features"], out["n_candidates"] = n_feat, np.where(few, 0, n_cand)
+    return [tick_result_dict(o) for o in out]
 
 
 class _Batch:
@@ -258,6 +238,34 @@ class _Batch:
 
     def __init__(self, group, n):
         self.group, self.n, self.done = group, n, False
+
+
+class _Group:
+    """`batch` contexts that share ONE stream and the rank's shard, plus the exchange buffers of the one batch the group
+    has in flight.  What the host reads of a batch -- every rank's result records, the winners, the feature counts -- is
+    ONE contiguous device buffer (`pack`; all_res, win_gid and n_feat are views of it) and ONE copy into pinned memory
+    (`h_pack`; h_res, h_win and h_nfeat are NumPy views of that)."""
+    __slots__ = ("stream", "engines", "scan", "all_scan", "cand_local", "pack", "all_res", "win_gid", "n_feat", "res",
+                 "h_pack", "h_res", "h_win", "h_nfeat", "event", "pending")
+
+    def __init__(self, torch, device, stream, engines, rank: int, world: int, B: int, k: int, collective: bool):
+        self.stream, self.engines, self.event, self.pending = stream, engines, torch.cuda.Event(), None
+        row, n_res, n_win = 2 * k + 2, world * B * TICK_RESULT.itemsize, B * k * 4
+        self.scan = torch.full((B, row), -1, dtype=torch.int32, device=device)
+        self.all_scan = torch.empty((world, B, row), dtype=torch.int32, device=device)
+        self.cand_local = torch.empty((B, k), dtype=torch.int32, device=device)
+        self.pack = torch.zeros(n_res + n_win + B * 4, dtype=torch.uint8, device=device)
+        self.all_res = self.pack[:n_res].view(world, B, TICK_RESULT.itemsize)
+        self.win_gid = self.pack[n_res:n_res + n_win].view(torch.int32).view(B, k)
+        self.n_feat = self.pack[n_res + n_win:].view(torch.int32)
+        # where the rank's own records are stored: its send buffer when a collective moves them (made once: no allocation
+        # on the group's stream per batch), straight into all_res[rank] without one
+        self.res = torch.zeros((B, TICK_RESULT.itemsize), dtype=torch.uint8, device=device) if collective else self.all_res[rank]
+        self.h_pack = torch.empty(n_res + n_win + B * 4, dtype=torch.uint8).pin_memory()
+        h = self.h_pack.numpy()
+        self.h_res = h[:n_res].reshape(world, B, TICK_RESULT.itemsize)
+        self.h_win = h[n_res:n_res + n_win].view(np.int32).reshape(B, k)
+        self.h_nfeat = h[n_res + n_win:].view(np.int32)
 
 
 class DeviceShardedRelocalizer:
@@ -284,51 +292,21 @@ class DeviceShardedRelocalizer:
         one rank, or an injected group) instead of the single-rank device copy -- the way to run the RCCL transport on a
         one-GPU box (tests, bench.py --shard-db --force-dist)."""
         import torch
-        from .engine import Engine
         self.torch, self.shard, self.rank, self.world, self.device, self.group, self.k = torch, shard, rank, world, device, group, k
         self.collective = world > 1 or bool(force_collective)
         B = batch if batch is not None else max(1, min(8, len(shard.engines)))
         self.B, self.depth = B, depth
-        e0 = shard.engine
-        self.min_features = int(e0.get_params().min_matches) if shard.n_records else MIN_FEATURES
-        row = 2 * k + 2
-        self.groups = []
+        self.min_features = int(shard.engine.get_params().min_matches) if shard.n_records else MIN_FEATURES
         # the groups' streams are made first and one after the other: the HIP runtime hands a new stream the least-used of
         # its (four) hardware queues, and two groups whose streams share a hardware queue run strictly one after the other
         # (four hardware queues: more than four streams only share them; further groups take turns on the four streams, which
         # is what lets the host run `depth` batches ahead of the device)
         streams = [torch.cuda.Stream(device=device) for _ in range(min(depth, n_streams))]
+        self.groups = []
         for g in range(depth):
             ts = streams[g % len(streams)]
-            engines = []
-            if shard.n_records:
-                for _ in range(B):
-                    e = Engine(e0.device, e0.max_w, e0.max_h, e0.max_feat)
-                    e.db_share(e0)
-                    e.set_params_from(e0)
-                    e.set_stream(ts.cuda_stream)
-                    engines.append(e)
-            # what the host reads of a batch -- every rank's result records, the winners, the feature counts -- is ONE
-            # contiguous device buffer (the tensors below are views of it) and ONE copy into pinned memory per batch
-            n_res, n_win, n_nf = world * B * 96, B * k * 4, B * 4
-            pack = torch.zeros(n_res + n_win + n_nf, dtype=torch.uint8, device=device)
-            h_pack = torch.empty(n_res + n_win + n_nf, dtype=torch.uint8).pin_memory()
-            all_res = pack[:n_res].view(world, B, 96)
-            self.groups.append(dict(
-                stream=ts, engines=engines,
-                scan=torch.full((B, row), -1, dtype=torch.int32, device=device),
-                all_scan=torch.empty((world, B, row), dtype=torch.int32, device=device),
-                win_gid=pack[n_res:n_res + n_win].view(torch.int32).view(B, k),
-                cand_local=torch.empty((B, k), dtype=torch.int32, device=device),
-                n_feat=pack[n_res + n_win:].view(torch.int32),
-                all_res=all_res, pack=pack, h_pack=h_pack,
-                # the rank's own result records when a collective moves them (its send buffer, made once: no allocation on the
-                # group's stream per batch); without a collective they are written straight into all_res[rank]
-                send_res=torch.zeros((B, 96), dtype=torch.uint8, device=device) if self.collective else None,
-                h_res=h_pack[:n_res].view(world, B, 96),
-                h_win=h_pack[n_res:n_res + n_win].view(torch.int32).view(B, k),
-                h_nfeat=h_pack[n_res + n_win:].view(torch.int32),
-                event=torch.cuda.Event(), pending=None))
+            engines = [shard.new_slot(ts.cuda_stream) for _ in range(B)] if shard.n_records else []
+            self.groups.append(_Group(torch, device, ts, engines, rank, world, B, k, self.collective))
         self._next = 0
         if bases is None:
             if not self.collective:
@@ -358,60 +336,53 @@ class DeviceShardedRelocalizer:
             raise ValueError(f"batch of {n} frames on groups of {self.B} slots")
         g = self.groups[self._next]
         self._next = (self._next + 1) % self.depth
-        if g["pending"] is not None and not g["pending"].done:
-            g["event"].synchronize()                              # its buffers are still in use
-            g["pending"].done = True
-        from .engine import Engine
+        if g.pending is not None and not g.pending.done:
+            g.event.synchronize()                                 # its buffers are still in use
+            g.pending.done = True
         seeds = list(seeds) if seeds is not None else [0] * n
         row = 2 * k + 2
-        with torch.cuda.stream(g["stream"]):
+        with torch.cuda.stream(g.stream):
             if sh.n_records:
-                Engine.shard_scan_batch_dev(g["engines"][:n], frames_dev, sh.w, sh.h, base_poses, k, sh.base, g["scan"].data_ptr())
+                Engine.shard_scan_batch_dev(g.engines[:n], frames_dev, sh.w, sh.h, base_poses, k, sh.base, g.scan.data_ptr())
             else:                                                 # more ranks than records: this rank only takes part in the exchange
-                g["scan"][:, :k] = -1; g["scan"][:, k:2 * k] = 0; g["scan"][:, 2 * k] = -1
+                g.scan[:, :k] = -1; g.scan[:, k:2 * k] = 0; g.scan[:, 2 * k] = -1
+            all_scan = g.scan
             if self.collective:
-                self._all_gather(g["all_scan"], g["scan"], g["stream"])
-                all_scan, stride = g["all_scan"], self.B * row
-            else:
-                all_scan, stride = g["scan"], self.B * row
-            eng = g["engines"][0] if sh.n_records else None
-            if eng is not None:
-                eng.shard_merge_dev(all_scan.data_ptr(), self.world, stride, n, k, sh.base, sh.n_records, g["win_gid"].data_ptr(),
-                                    g["cand_local"].data_ptr(), g["n_feat"].data_ptr())
-                res = g["send_res"] if self.collective else g["all_res"][self.rank]
-                Engine.shard_solve_batch_dev(g["engines"][:n], g["cand_local"].data_ptr(), k, base_poses, seeds, res.data_ptr())
+                self._all_gather(g.all_scan, g.scan, g.stream)
+                all_scan = g.all_scan
+            if sh.n_records:
+                g.engines[0].shard_merge_dev(all_scan.data_ptr(), self.world, self.B * row, n, k, sh.base, sh.n_records,
+                                             g.win_gid.data_ptr(), g.cand_local.data_ptr(), g.n_feat.data_ptr())
+                Engine.shard_solve_batch_dev(g.engines[:n], g.cand_local.data_ptr(), k, base_poses, seeds, g.res.data_ptr())
             else:
                 wg, _, nf = merge_topk_tensor(all_scan.view(self.world, self.B, row)[:, :n], k, sh.base, 0)
-                g["win_gid"][:n] = wg; g["n_feat"][:n] = nf
-                res = g["send_res"] if self.collective else g["all_res"][self.rank]
-                res.zero_()
-                res.view(torch.int32)[:, 18] = 2                  # outcome no_candidates, never picked
+                g.win_gid[:n] = wg; g.n_feat[:n] = nf
+                g.res.zero_()
+                g.res.view(torch.int32)[:, TICK_RESULT.fields["outcome"][1] // 4] = 2        # no_candidates, never picked
             if self.collective:
-                self._all_gather(g["all_res"], g["send_res"], g["stream"])
-            g["h_pack"].copy_(g["pack"], non_blocking=True)                      # the one trip to the host, not waited for here
-            g["event"].record(g["stream"])
-        b = _Batch(g, n)
-        g["pending"] = b
+                self._all_gather(g.all_res, g.res, g.stream)
+            g.h_pack.copy_(g.pack, non_blocking=True)                            # the one trip to the host, not waited for here
+            g.event.record(g.stream)
+        g.pending = b = _Batch(g, n)
         return b
 
     def result(self, b: _Batch):
         """wait for that batch (its event only) and pick every frame's anchor"""
-        g = b.group
-        if g["pending"] is not b:
+        g, n = b.group, b.n
+        if g.pending is not b:
             raise RuntimeError("this batch's buffers have been reused: collect a batch before `depth` more are submitted")
-        g["event"].synchronize()
+        g.event.synchronize()
         b.done = True
-        n = b.n
-        return pick_results(np.ascontiguousarray(g["h_res"].numpy()[:self.world, :n]), g["h_win"].numpy()[:n].copy(),
-                            g["h_nfeat"].numpy()[:n].copy(), self.bases, self.min_features)
+        return pick_results(g.h_res[:, :n], g.h_win[:n], g.h_nfeat[:n], self.bases, self.min_features)
 
     def tick_batch(self, frames_dev, base_poses, seeds=None):
         return self.result(self.submit(frames_dev, base_poses, seeds))
 
     def close(self):
         for g in self.groups:
-            g["event"].synchronize() if g["pending"] is not None else None
-            g["stream"].synchronize()
-            for e in g["engines"]:
+            if g.pending is not None:
+                g.event.synchronize()
+            g.stream.synchronize()
+            for e in g.engines:
                 e.close()
-            g["engines"] = []
+            g.engines = []

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from nclt_slam_project_amd import RelocError, synth
+from nclt_slam_project_amd.engine import TICK_RESULT
 
 RESULT_KEYS = ("outcome", "n_inliers", "lm_idx", "n_candidates", "relocating", "n_features")
 RECORD_KEYS = ("descriptors", "keypoints_2d", "keypoints_3d_cam")
@@ -67,14 +68,14 @@ def engines(n, max_w=640, max_h=480, max_feat=4096):
 def device_record(e):
     """the 96-byte result record of the last tick, as it lies on the device"""
     e.tick_result()
-    rec = np.zeros(96, np.uint8)
+    rec = np.zeros(TICK_RESULT.itemsize, np.uint8)
     e.d2h(rec, e.tick_result_dev)
     return rec
 
 
 def tick_record(e, img, bp, mode=True, seed=1):
     e.tick(img, bp, global_reloc=mode, seed=seed)
-    rec = np.zeros(96, np.uint8)
+    rec = np.zeros(TICK_RESULT.itemsize, np.uint8)
     e.d2h(rec, e.tick_result_dev)
     return rec
 

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 from nclt_slam_project_amd import synth
-from nclt_slam_project_amd.sharded import HipShard, ShardedRelocalizer
+from nclt_slam_project_amd.sharded import DeviceShardedRelocalizer, HipShard, ShardedRelocalizer
 
 pytestmark = pytest.mark.gpu
 
@@ -42,6 +42,88 @@ def test_scan_solve_equals_fused_tick(engine, oracle):
     if fused["outcome"] in (0, 4):
         assert r["n_inliers"] == fused["n_inliers"] and r["lm_idx"] == fused["lm_idx"]
         np.testing.assert_allclose(r["anchor_pose"], fused["anchor_pose"], atol=1e-9)
+
+
+@pytest.fixture(scope="module")
+def small(engine):
+    """the 300-record, 640x480 recipe of test_scan_solve_equals_fused_tick with record 120 made PnP-solvable the way the
+    benchmark's workload plants its records (its 3-D points reproject onto the keypoints its rows copy), and the fused
+    tick of that frame, made once"""
+    rng = np.random.default_rng(21)
+    img = synth.textured_frame(rng, 640, 480)
+    feat = engine.orb_detect_compute(engine.gray(img), 500)
+    desc, pts, off, poses = synth.descriptor_db(rng, 300, "ragged", feat["desc"], planted_records=(7, 120, 299))
+    a = int(off[120])
+    sel = rng.choice(feat["n"], min(int(off[121]) - a, feat["n"]), replace=False)
+    rvec = rng.normal(size=3); rvec *= np.deg2rad(4.0) / np.linalg.norm(rvec)
+    tvec, z, uv = rng.uniform(-0.5, 0.5, 3), rng.uniform(2.0, 12.0, len(sel)), feat["xy"][sel].astype(np.float64)
+    pc = np.stack([(uv[:, 0] - 320.0) / 320.0 * z, (uv[:, 1] - 240.0) / 320.0 * z, z], 1)
+    desc[a:a + len(sel)] = synth.perturb_descriptors(rng, feat["desc"][sel], 0.04)
+    pts[a:a + len(sel)] = ((pc - tvec) @ synth.rodrigues(rvec)).astype(np.float32)            # R^T (pc - t)
+    engine.db_upload(desc, pts, off, poses)
+    bp = synth.base_pose(float(poses[120, 0]) + 0.5, 0.2, 1.0)
+    return img, (desc, pts, off, poses), bp, engine.tick(img, bp, global_reloc=True, seed=5)
+
+
+class _World1Group:
+    """the all_gather_tensor seam with one rank in it: a copy on the stream the caller has made current"""
+    calls = 0
+
+    def all_gather_tensor(self, rank, out, inp, stream):
+        self.calls += 1
+        out[0].copy_(inp)
+
+
+def test_host_exchange_equals_device_exchange(engine, small):
+    """one batch of 3 on a 3-slot shard: ShardedRelocalizer (exchange through host memory) == DeviceShardedRelocalizer
+    (exchange in HBM), with the single-rank device copy and through an injected collective of world 1; both pick with
+    pick_results, from records with global and with local lm_idx"""
+    import torch
+    img, db, bp, fused = small
+    shard = HipShard(engine, *db, rank=0, world=1, n_slots=3)
+    frame_dev = engine.to_device(img)
+    frames, bps, seeds = [frame_dev] * 3, [bp] * 3, [5, 6, 7]
+    try:
+        host = ShardedRelocalizer(shard, shard.base, 0, 1).tick_batch(frames, bps, seeds=seeds)
+        print("fused", fused["outcome"], fused["n_inliers"], "host", [(h["outcome"], h["n_inliers"], h["lm_idx"]) for h in host])
+        for group in (None, _World1Group()):
+            sr = DeviceShardedRelocalizer(shard, 0, 1, torch.device("cuda", 0), group=group, bases=[shard.base], batch=3,
+                                          depth=2, force_collective=group is not None)
+            dev = sr.tick_batch(frames, bps, seeds)
+            sr.close()
+            assert group is None or group.calls == 2               # the scan rows, the result records
+            for h, d in zip(host, dev):
+                for key in ("outcome", "n_inliers", "lm_idx", "n_candidates"):
+                    assert h[key] == d[key], (key, group)
+                np.testing.assert_array_equal(h["anchor_pose"], d["anchor_pose"])
+                assert h["reproj"] == d["reproj"]
+    finally:
+        engine.dev_free(frame_dev)
+        shard.close()
+    assert fused["outcome"] in (0, 4) and fused["lm_idx"] == 120       # the planted record: poses and ids are really compared
+    assert host[0]["n_candidates"] == fused["n_candidates"] and host[0]["outcome"] in (0, 4)
+    assert host[0]["n_inliers"] == fused["n_inliers"] and host[0]["lm_idx"] == fused["lm_idx"]      # seed 5 is the fused tick's
+    np.testing.assert_allclose(host[0]["anchor_pose"], fused["anchor_pose"], atol=1e-9)
+
+
+def test_every_slot_carries_the_engines_parameters(engine, small):
+    """HipShard.new_slot: the extra slots of a shard and the contexts of a DeviceShardedRelocalizer group gate and extract
+    like the shard's engine (matcher and ORB parameters)"""
+    import torch
+    img, db, bp, _ = small
+    before = engine.get_params().min_matches
+    engine.set_params(min_matches=12)
+    try:
+        shard = HipShard(engine, *db, rank=0, world=1, n_slots=2)
+        sr = DeviceShardedRelocalizer(shard, 0, 1, torch.device("cuda", 0), batch=2, depth=2)
+        slots = shard.engines + [e for g in sr.groups for e in g.engines]
+        assert len(slots) == 2 + 2 * 2
+        for e in slots:
+            assert e.get_params().min_matches == 12 and e.get_orb_params() == engine.get_orb_params()
+        sr.close()
+        shard.close()
+    finally:
+        engine.set_params(min_matches=before)
 
 
 def test_topk_when_one_thread_owns_most_winners(engine, oracle):

@@ -47,7 +47,7 @@ class OracleShard:
         ids = np.full(k, -1, np.int32); cnt = np.zeros(k, np.int32)
         for i, (n, li) in enumerate(scored[:k]):
             ids[i] = li; cnt[i] = n
-        return ids, cnt
+        return ids, cnt, 10                      # MIN_FEATURES: what the relocalizer used to put in for a scan without a count
 
     def solve(self, local_ids, base_pose, check_consistency, seed, slot=0):
         best = None
@@ -160,6 +160,7 @@ def test_two_rank_gloo_equals_single_rank(oracle, tmp_path):
 def test_device_merge_equals_host_merge():
     """merge_topk_tensor (the device-resident exchange's merge, plain torch ops) == merge_topk (count desc, global id
     desc, -1 padding ignored), ties and short lists included; pick_results takes most inliers, earliest candidate on ties"""
+    from nclt_slam_project_amd.engine import TICK_RESULT
     from nclt_slam_project_amd.sharded import merge_topk, merge_topk_tensor, pick_results
     rng = np.random.default_rng(0)
     for trial in range(120):
@@ -185,12 +186,12 @@ def test_device_merge_equals_host_merge():
             assert nf[i].item() == all_scan[:, i, 2 * k].max()
     # result pick: two ranks report an anchor with equal inliers; the one earlier in the global candidate order wins
     res = np.zeros((2, 1, 96), np.uint8)
-    i32 = res.view(np.int32).reshape(2, 1, 24); f64 = res.view(np.float64).reshape(2, 1, 12)
-    i32[0, 0, 16:19] = (40, 7, 0); f64[0, 0, 0] = 1.5         # rank 0: local record 7 -> global 7
-    i32[1, 0, 16:19] = (40, 3, 0); f64[1, 0, 0] = 2.5         # rank 1: local record 3 -> global 1003
+    rec = res.view(TICK_RESULT).reshape(2, 1)
+    rec["n_inliers"], rec["outcome"] = 40, 0
+    rec["lm_idx"][:, 0], rec["anchor_pose"][:, 0, 0] = (7, 3), (1.5, 2.5)     # local records 7 and 3 -> global 7 and 1003
     win = np.array([[1003, 7, -1]], np.int32)
     out = pick_results(res, win, np.array([500]), [0, 1000])[0]
     assert out["lm_idx"] == 1003 and out["anchor_pose"][0] == 2.5 and out["n_candidates"] == 2
     assert pick_results(res, win, np.array([3]), [0, 1000])[0]["outcome"] == 1            # too few features
-    i32[:, 0, 18] = 3
+    rec["outcome"] = 3
     assert pick_results(res, win, np.array([500]), [0, 1000])[0]["outcome"] == 3
