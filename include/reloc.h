@@ -371,9 +371,36 @@ int reloc_bayer_u8(reloc_ctx *ctx, const uint8_t *raw, int w, int h, int stride,
  * unchanged.  0 turns the stage off (the default of a new context; the launch sequence is then that of a context that never
  * had it, results bit-identical); any other code is RELOC_E_ARG.  The first enable allocates the context's plane.  Never
  * applied by reloc_orb_detect_compute, reloc_gray_u8, reloc_clahe_u8, reloc_remap_* or reloc_resize_*.  Batched calls refuse
- * contexts with unequal codes (RELOC_E_STATE).  reloc_get_bayer returns 0 when off. */
+ * contexts with unequal codes (RELOC_E_STATE).  A code while a pixel format is set (reloc_set_pixel_format) is RELOC_E_STATE.
+ * reloc_get_bayer returns 0 when off. */
 int reloc_set_bayer(reloc_ctx *ctx, int code);
 int reloc_get_bayer(reloc_ctx *ctx, int32_t *code);
+
+/* ---- pixel formats (include/reloc_spec.h, "PIXEL FORMATS") -------------------------------------- */
+/* cv2.cvtColor(src, COLOR_BGRA2GRAY | COLOR_RGBA2GRAY | COLOR_YUV2GRAY_YUY2 | COLOR_YUV2GRAY_UYVY) on a caller's packed frame
+ * (cv2 shim): src is w x h pixels of fmt = RELOC_FMT_BGRA, _RGBA (4 bytes per pixel; the gray conversion with the context's
+ * gray_coeff_bits, alpha ignored), _YUYV or _UYVY (2 bytes per pixel, w even; the Y bytes), rows stride bytes apart; out is
+ * w x h, dense.  Any size >= 1 x 1 within the context's capacity (RELOC_E_CAPACITY); another fmt, an odd width in 4:2:2 or
+ * a stride below the row is RELOC_E_ARG.  Host pointers; synchronous. */
+int reloc_cvt_gray_u8(reloc_ctx *ctx, const uint8_t *src, int w, int h, int stride, int fmt, uint8_t *out);
+/* cv2.cvtColor(src, COLOR_YUV2BGR_YUY2 | COLOR_YUV2BGR_UYVY) (order 0) and the 2RGB twins (order RELOC_ORDER_RGB): fmt =
+ * RELOC_FMT_YUYV or _UYVY, w even; out is w x h x 3, interleaved, dense.  Errors as above.  Host pointers; synchronous. */
+int reloc_yuv422_bgr_u8(reloc_ctx *ctx, const uint8_t *src, int w, int h, int stride, int fmt, int order, uint8_t *out);
+/* The pixel format of the frames that enter the image chain: with fmt other than RELOC_FMT_BGR every entry point that applies
+ * the downscale stage takes w x h frames of that format, rows dense (reloc_orb_frame_dev: stride in bytes, >= w * bytes per
+ * pixel), in place of the 3-channel frame: RELOC_FMT_MONO8 1 byte per pixel, the gray itself (no kernel and no launch is
+ * added); _BGRA / _RGBA 4 bytes, _YUYV / _UYVY 2 bytes (w even, else RELOC_E_ARG from the entry point), through one unpack
+ * launch at the head of the chain, frame -> unpack -> [resize] -> [rectify] -> [CLAHE] -> ORB: the bytes of reloc_cvt_gray_u8.
+ * The channel-order bit of `order` is ignored.  reloc_set_resize's source size is the frame's size; the persistent detection
+ * mask applies as to any frame of the chain.  Depth images follow their chain unchanged.  RELOC_FMT_BGR (0) restores the
+ * default (the launch sequence is then that of a context that never had a format, results bit-identical); a value outside
+ * RELOC_FMT_BGR .. RELOC_FMT_UYVY is RELOC_E_ARG.  The format and the Bayer stage exclude each other: a format other than 0
+ * while reloc_set_bayer is on, and reloc_set_bayer with a code while a format is set, are RELOC_E_STATE.  The first enable
+ * of a packed format allocates the context's plane, and grows the staging plane of the host-pointer entry points for a
+ * 4-byte format.  Never applied by reloc_orb_detect_compute*, reloc_gray_u8, reloc_clahe_u8, reloc_remap_*, reloc_resize_*
+ * or reloc_bayer_u8.  Batched calls refuse contexts with unequal formats (RELOC_E_STATE). */
+int reloc_set_pixel_format(reloc_ctx *ctx, int fmt);
+int reloc_get_pixel_format(reloc_ctx *ctx, int32_t *fmt);
 
 /* ---- fused tick ----------------------------------------------------------------------------- */
 #define RELOC_TICK_LOCAL   0   /* candidates by VIO distance / heading only                          M:293-302 */

@@ -229,6 +229,35 @@
 #define RELOC_BAYER_RG2BGR       48
 #define RELOC_BAYER_GR2BGR       49
 
+/* PIXEL FORMATS: the packed 8-bit camera frames besides BGR / RGB, and cv2.cvtColor's conversions of them, restated from OpenCV
+ * 4.x modules/imgproc/src/color_rgb.simd.hpp (RGB2Gray) and color_yuv.simd.hpp (YUV422toRGB8Invoker; not pinned against a cv2
+ * build).  All integer.
+ *   mono8      (H, W): the bytes are the gray.
+ *   BGRA, RGBA (H, W, 4): COLOR_BGRA2GRAY (10) / COLOR_RGBA2GRAY (11) = the gray conversion at the head of this file on the
+ *              first three channels, in the given order; the fourth byte is ignored.
+ *   YUYV, UYVY (H, W, 2), W even: a pixel pair is the 4 bytes Y0 U Y1 V (YUYV = YUY2 = YUNV) or U Y0 V Y1 (UYVY = Y422 =
+ *              UYNV).  YVYU (Y0 V Y1 U) has its Y bytes where YUYV has them.
+ *     gray     COLOR_YUV2GRAY_YUY2 (124) / COLOR_YUV2GRAY_UYVY (123): the Y bytes, untouched (no range expansion).
+ *     colour   COLOR_YUV2BGR_YUY2 (116), COLOR_YUV2BGR_UYVY (108) and the 2RGB twins (115, 107), BT.601 limited range:
+ *              u = U - 128, v = V - 128, y = max(0, Y - 16) * CY, r = 1 << (SHIFT - 1);
+ *              B = sat8((y + r + CUB * u) >> SHIFT), G = sat8((y + r + CVG * v + CUG * u) >> SHIFT),
+ *              R = sat8((y + r + CVR * v) >> SHIFT); the shift is arithmetic (floor), sat8 clamps to 0..255, both pixels of a
+ *              pair take the pair's U and V.  2RGB: the same values, R first.
+ *   Planar 4:2:0 (NV12, I420), 16-bit mono, the 4-channel outputs and YVYU to colour are not implemented; the Y plane of a
+ *   4:2:0 buffer, frame[:H], is a mono8 frame. */
+#define RELOC_FMT_BGR            0    /* 3 interleaved bytes, BGR or RGB by the `order` argument: the default */
+#define RELOC_FMT_MONO8          1
+#define RELOC_FMT_BGRA           2
+#define RELOC_FMT_RGBA           3
+#define RELOC_FMT_YUYV           4
+#define RELOC_FMT_UYVY           5
+#define RELOC_YUV_SHIFT          20   /* ITUR_BT_601_SHIFT */
+#define RELOC_YUV_CY             1220542
+#define RELOC_YUV_CUB            2116026
+#define RELOC_YUV_CUG            (-409993)
+#define RELOC_YUV_CVG            (-852492)
+#define RELOC_YUV_CVR            1673527
+
 /* ORB MASK: cv2.ORB.detectAndCompute(image, mask) with an 8-bit single-channel mask of the image's size, restated from OpenCV
  * 4.x modules/features2d/src/orb.cpp (the mask pyramid of detectAndCompute, computeKeyPoints) and fast.cpp /
  * KeyPointsFilter::runByPixelsMask (not pinned against a cv2 build).

@@ -85,6 +85,10 @@ SIGNATURES = {
     "reloc_bayer_u8": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, C.c_int, P]),
     "reloc_set_bayer": (C.c_int, [c_ctx, C.c_int]),
     "reloc_get_bayer": (C.c_int, [c_ctx, P]),
+    "reloc_cvt_gray_u8": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, C.c_int, P]),
+    "reloc_yuv422_bgr_u8": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P]),
+    "reloc_set_pixel_format": (C.c_int, [c_ctx, C.c_int]),
+    "reloc_get_pixel_format": (C.c_int, [c_ctx, P]),
     "reloc_tick_debug": (C.c_int, [c_ctx, P, P, P, P, P, P, P]),
     "reloc_tick_debug_matches": (C.c_int, [c_ctx, C.c_int, P, P, P, P, P, P]),
     "reloc_tick": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, P, C.c_int, u64, P, P, P, P, P, P]),

@@ -2,12 +2,14 @@
 // A section per stage (kernels, host planning, one *_launch for n frames of equal geometry on one stream):
 //   gray     cv2.cvtColor(.., COLOR_BGR2GRAY)   k_gray_plain; inside the chain the first kernel that reads the frame converts
 //   BAYER    cv2.cvtColor(.., COLOR_Bayer??2BGR) k_bayer: a raw mosaic -> BGR (the shim) or -> gray (the stage)
+//   PIXFMT   cv2.cvtColor(.., COLOR_BGRA2GRAY, COLOR_YUV2GRAY_YUY2, COLOR_YUV2BGR_YUY2 ..)   k_unpack: a packed frame -> gray
+//            (the shim and the stage), k_yuv422_bgr: 4:2:2 -> BGR / RGB (the shim)
 //   CLAHE    cv2.createCLAHE(..).apply          k_clahe_lut, k_clahe_apply
 //   REMAP    cv2.remap, cv2.convertMaps         k_remap_u8, k_remap_nearest, k_convert_maps
 //   RESIZE   cv2.resize                         k_resize_area, k_resize_linear, k_resize_nearest
-// "image chain": [demosaic] -> resize -> rectify -> CLAHE on the frames in front of the pyramid (orb_run; 3-channel frames, or
-// raw mosaics with the Bayer stage on), resize -> rectify, both nearest, on the depth image of the recorder and the
-// accumulation.  No other code states this order.
+// "image chain": [demosaic | unpack] -> resize -> rectify -> CLAHE on the frames in front of the pyramid (orb_run; 3-channel
+// frames, raw mosaics with the Bayer stage on, or frames of the context's pixel format), resize -> rectify, both nearest, on
+// the depth image of the recorder and the accumulation.  No other code states this order.
 // "entry points": the host-pointer form of every stage (the cv2 shim) and the reloc_set_* / reloc_get_* of a context.
 #include <float.h>
 #include <math.h>
@@ -141,6 +143,107 @@ static int bayer_launch(hipStream_t st, const BayerFrames &F, int n, int w, int 
     const int green_par = (code & 1) ^ 1, blue_par = ((code - RELOC_BAYER_BG2BGR) >> 1) ^ 1;
     auto kern = oc == 3 ? (aligned ? k_bayer<3, true> : k_bayer<3, false>) : (aligned ? k_bayer<1, true> : k_bayer<1, false>);
     hipLaunchKernelGGL(kern, dim3((((w + 3) / 4) * h + 255) / 256, n), dim3(256), 0, st, F, w, h, sstride, dstride, green_par, blue_par,
+                       flags & RELOC_GRAY_FLAG_15BIT);
+    HIP_TRY(hipGetLastError());
+    return RELOC_OK;
+}
+
+// ---- PIXFMT: packed camera frames (include/reloc_spec.h, "PIXEL FORMATS") ---------------------------------------------
+//   k_unpack<FMT, ALIGNED>   the gray plane of a packed frame, 4 output pixels per lane, one dword store.  YUYV / UYVY: the Y
+//                            bytes (cvtColor(.., COLOR_YUV2GRAY_YUY2 / _UYVY)), 8 source bytes per lane.  BGRA / RGBA:
+//                            gray_fixed of the first three channels with the coefficient flag, alpha ignored
+//                            (COLOR_BGRA2GRAY / COLOR_RGBA2GRAY), 16 source bytes per lane.  ALIGNED (w % 4 == 0, rows on 8 /
+//                            16 bytes): one 64-bit / 128-bit load per lane, consecutive lanes consecutive addresses.
+//                            Otherwise the bytes of the pixels inside the row, through the cache (the guards of
+//                            pyr_fetch<CH, false>).  It is the stage at the head of the image chain, in the Bayer stage's place, and
+//                            reloc_cvt_gray_u8.  Grid (x, frame, row): no division; a single frame is a batch of one.
+//   k_yuv422_bgr             cvtColor(.., COLOR_YUV2BGR_YUY2 / _UYVY and the 2RGB twins): one pixel pair per lane, 4 bytes in,
+//                            6 out, OpenCV's fixed-point BT.601.  Serves reloc_yuv422_bgr_u8 only.
+// No LDS, no scratch.  mono8 frames need no kernel: they are gray planes.
+struct UnpackFrames { const uint8_t *src[RELOC_BATCH_MAX]; uint8_t *dst[RELOC_BATCH_MAX]; };
+constexpr int UNPACK_BS = 64;          // one wave = 256 pixels of a row: 640 and 1280 columns waste 17 % and 0 % of their lanes
+
+template <int FMT, bool ALIGNED>
+__global__ __launch_bounds__(UNPACK_BS) void k_unpack(UnpackFrames F, int w, int sstride, int dstride, int flags)
+{
+    constexpr int BPP = (FMT == RELOC_FMT_YUYV || FMT == RELOC_FMT_UYVY) ? 2 : 4;
+    const int x4 = 4 * (blockIdx.x * UNPACK_BS + threadIdx.x), y = blockIdx.z;
+    if (x4 >= w) return;
+    const uint8_t *sp = F.src[blockIdx.y] + (size_t)y * sstride + (size_t)BPP * x4;
+    u32 d[BPP];         // the 4 pixels' bytes; a pixel beyond w reads as 0
+    if (ALIGNED) {
+        if constexpr (BPP == 2) { const uint2 v = *reinterpret_cast<const uint2 *>(sp); d[0] = v.x; d[1] = v.y; }
+        else { const uint4 v = *reinterpret_cast<const uint4 *>(sp); d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w; }
+    } else {
+#pragma unroll
+        for (int i = 0; i < BPP; ++i) d[i] = 0;
+#pragma unroll
+        for (int k = 0; k < 4 * BPP; ++k)
+            if (x4 + k / BPP < w) d[k >> 2] |= (u32)sp[k] << (8 * (k & 3));
+    }
+    u32 out = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if constexpr (BPP == 2) {
+            const int bi = 2 * k + (FMT == RELOC_FMT_UYVY ? 1 : 0);
+            out |= ((d[bi >> 2] >> (8 * (bi & 3))) & 255u) << (8 * k);
+        } else {
+            const int c0 = d[k] & 255u, c1 = (d[k] >> 8) & 255u, c2 = (d[k] >> 16) & 255u;
+            const int g = FMT == RELOC_FMT_RGBA ? gray_fixed(c2, c1, c0, flags) : gray_fixed(c0, c1, c2, flags);
+            if (x4 + k < w) out |= (u32)g << (8 * k);
+        }
+    }
+    uint8_t *dst = F.dst[blockIdx.y] + (size_t)y * dstride + x4;
+    if ((dstride & 3) == 0) {
+        *reinterpret_cast<u32 *>(dst) = out;       // the row holds round4(w) bytes: dstride >= w and a multiple of 4
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (x4 + k < w) dst[k] = (uint8_t)(out >> (8 * k));
+    }
+}
+
+__device__ __forceinline__ int yuv_sat8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+// src: dense rows of 2 w bytes on a dword (w is even), dst: dense rows of 3 w bytes on a word -- the staging plane and a
+// scratch slot of reloc_yuv422_bgr_u8.  uyvy: the Y bytes are the odd ones; rgb: R first
+__global__ __launch_bounds__(256) void k_yuv422_bgr(const uint8_t *__restrict__ src, int w, int uyvy, int rgb, uint8_t *__restrict__ dst)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (2 * p >= w) return;
+    const u32 q = reinterpret_cast<const u32 *>(src + (size_t)y * 2 * w)[p];
+    const int b0 = q & 255u, b1 = (q >> 8) & 255u, b2 = (q >> 16) & 255u, b3 = q >> 24;
+    const int u = (uyvy ? b0 : b1) - 128, v = (uyvy ? b2 : b3) - 128;
+    const int ruv = (1 << (RELOC_YUV_SHIFT - 1)) + RELOC_YUV_CVR * v;
+    const int guv = (1 << (RELOC_YUV_SHIFT - 1)) + RELOC_YUV_CVG * v + RELOC_YUV_CUG * u;
+    const int buv = (1 << (RELOC_YUV_SHIFT - 1)) + RELOC_YUV_CUB * u;
+    int c[6];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int yy = max(0, (k ? (uyvy ? b3 : b2) : (uyvy ? b1 : b0)) - 16) * RELOC_YUV_CY;
+        const int B = yuv_sat8((yy + buv) >> RELOC_YUV_SHIFT), G = yuv_sat8((yy + guv) >> RELOC_YUV_SHIFT);
+        const int R = yuv_sat8((yy + ruv) >> RELOC_YUV_SHIFT);
+        c[3 * k] = rgb ? R : B; c[3 * k + 1] = G; c[3 * k + 2] = rgb ? B : R;
+    }
+    uint16_t *d = reinterpret_cast<uint16_t *>(dst + (size_t)y * 3 * w) + 3 * p;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) d[k] = (uint16_t)(c[2 * k] | c[2 * k + 1] << 8);
+}
+
+static inline bool pixfmt_packed(int fmt) { return fmt >= RELOC_FMT_BGRA && fmt <= RELOC_FMT_UYVY; }
+static inline bool pixfmt_422(int fmt) { return fmt == RELOC_FMT_YUYV || fmt == RELOC_FMT_UYVY; }
+
+// one unpack launch for n packed frames of w x h on stream st (w even for 4:2:2: the callers check); flags: the coefficient set
+static int unpack_launch(hipStream_t st, const UnpackFrames &F, int n, int w, int h, int sstride, int dstride, int fmt, int flags)
+{
+    const int vec = pixfmt_422(fmt) ? 8 : 16;           // bytes of 4 pixels
+    bool aligned = w % 4 == 0 && sstride % vec == 0;
+    for (int f = 0; f < n; ++f) aligned = aligned && ((uintptr_t)F.src[f]) % vec == 0 && ((uintptr_t)F.dst[f]) % 4 == 0;
+#define UNPACK_KERN(FMT) (aligned ? k_unpack<FMT, true> : k_unpack<FMT, false>)
+    auto kern = fmt == RELOC_FMT_BGRA ? UNPACK_KERN(RELOC_FMT_BGRA) : fmt == RELOC_FMT_RGBA ? UNPACK_KERN(RELOC_FMT_RGBA)
+                : fmt == RELOC_FMT_YUYV ? UNPACK_KERN(RELOC_FMT_YUYV) : UNPACK_KERN(RELOC_FMT_UYVY);
+#undef UNPACK_KERN
+    hipLaunchKernelGGL(kern, dim3(((w + 3) / 4 + UNPACK_BS - 1) / UNPACK_BS, n, h), dim3(UNPACK_BS), 0, st, F, w, sstride, dstride,
                        flags & RELOC_GRAY_FLAG_15BIT);
     HIP_TRY(hipGetLastError());
     return RELOC_OK;
@@ -864,8 +967,9 @@ static int resize_launch(hipStream_t st, const ResizeFrames &F, int n, const Res
 }
 
 // ---- image chain ----------------------------------------------------------------------------------------------
-// bytes per pixel of the frames that enter the chain through orb_run: a raw mosaic with the Bayer stage on, else 3 channels
-int image_chain_frame_bpp(const reloc_ctx *c) { return c->img.bayer.on() ? 1 : 3; }
+// bytes per pixel of the frames that enter the chain through orb_run: a raw mosaic with the Bayer stage on, else those of
+// the context's pixel format (3 channels by default)
+int image_chain_frame_bpp(const reloc_ctx *c) { return c->img.bayer.on() ? 1 : c->img.pixfmt.bpp(); }
 
 // a frame or depth image of *w x *h enters the downscale stage r: *w x *h becomes the working frame
 static int resize_enter(const ResizeStage &r, int *w, int *h)
@@ -884,52 +988,63 @@ static int rectify_enter(const RectifyStage &r, int w, int h)
 
 static int batch_unequal(const char *what) { reloc_set_error("orb batch: contexts %s", what); return RELOC_E_STATE; }
 
-// Before orb_prepare: the contexts agree on the Bayer and the downscale stage, a frame has the latter's source size; w x h
-// becomes the working frame, which orb_prepare and everything downstream see.
-int image_chain_check(reloc_ctx *const *ctxs, int n, int channels, int *w, int *h)
+// Before orb_prepare: the contexts agree on the Bayer stage, the pixel format and the downscale stage, a frame of the chain
+// has the latter's source size (and an even width in a 4:2:2 format); w x h becomes the working frame, which orb_prepare and
+// everything downstream see.
+int image_chain_check(reloc_ctx *const *ctxs, int n, bool chain, int *w, int *h)
 {
     const auto &s0 = ctxs[0]->img;
     for (int f = 0; f < n; ++f) {
         if (!ctxs[f]->img.resize.same(s0.resize)) return batch_unequal("with and without the downscale stage, or with unequal sizes (reloc_set_resize)");
         if (!ctxs[f]->img.bayer.same(s0.bayer)) return batch_unequal("with and without the Bayer stage, or of unequal patterns (reloc_set_bayer)");
+        if (!ctxs[f]->img.pixfmt.same(s0.pixfmt)) return batch_unequal("of unequal pixel formats (reloc_set_pixel_format)");
     }
-    if (channels != 3 || !s0.resize.on()) return RELOC_OK;
+    if (!chain) return RELOC_OK;
+    if (s0.pixfmt.yuv422() && (*w & 1)) { reloc_set_error("bad argument: a 4:2:2 frame (reloc_set_pixel_format) has an even width, not %d", *w); return RELOC_E_ARG; }
+    if (!s0.resize.on()) return RELOC_OK;
     if (int rc = resize_enter(s0.resize, w, h)) return rc;
     if (*w < 64 || *h < 64) { reloc_set_error("bad argument: the working frame %dx%d of the downscale stage is below 64x64", *w, *h); return RELOC_E_ARG; }
     return RELOC_OK;
 }
 
 // Behind orb_prepare of context f, where these checks have always stood (a call's errors keep their order): f agrees with
-// context 0 on rectification and CLAHE; behind the last context, a 3-channel working frame has the size of the map.
-int image_chain_check_prepared(reloc_ctx *const *ctxs, int f, int n, int channels, int w, int h)
+// context 0 on rectification and CLAHE; behind the last context, the working frame of the chain has the size of the map.
+int image_chain_check_prepared(reloc_ctx *const *ctxs, int f, int n, bool chain, int w, int h)
 {
     const auto &s0 = ctxs[0]->img, &s = ctxs[f]->img;
     if (!s.rectify.same(s0.rectify)) return batch_unequal("with and without a rectification map, or with maps of unequal size (reloc_set_rectify_map)");
     if (!s.clahe.same(s0.clahe)) return batch_unequal("of unequal CLAHE settings (reloc_set_clahe)");
-    return f == n - 1 && channels == 3 && s0.rectify.on() ? rectify_enter(s0.rectify, w, h) : RELOC_OK;
+    return f == n - 1 && chain && s0.rectify.on() ? rectify_enter(s0.rectify, w, h) : RELOC_OK;
 }
 
-// The gray half, on the stream of the (checked) contexts: frames *srcs of sw x sh, rows of *stride bytes (3 channels, or raw
-// mosaics with the Bayer stage on), go through the stages that are on, each into its context's plane; the first one converts
-// to gray.  Afterwards *srcs (= planes, the caller's array) / *stride / *channels describe the last plane written.  A
-// caller's gray plane passes untouched.
-int image_chain_gray(reloc_ctx *const *ctxs, int n, const uint8_t *const **srcs, int sw, int sh, int w, int h, int *stride,
-                     int *channels, int flags, const uint8_t **planes)
+// The gray half, on the stream of the (checked) contexts: frames *srcs of sw x sh, rows of *stride bytes (chain: 3 channels,
+// raw mosaics with the Bayer stage on, or the contexts' pixel format), go through the stages that are on, each into its
+// context's plane; the first one converts to gray (a mono8 frame is gray).  Afterwards *srcs (= planes, the caller's array) /
+// *stride / *channels describe the last plane written, or the frame itself where no stage ran.  A caller's gray plane
+// (!chain) passes untouched.
+int image_chain_gray(reloc_ctx *const *ctxs, int n, bool chain, const uint8_t *const **srcs, int sw, int sh, int w, int h,
+                     int *stride, int *channels, int flags, const uint8_t **planes)
 {
-    if (*channels != 3) return RELOC_OK;
+    *channels = 1;
+    if (!chain) return RELOC_OK;
     const reloc_ctx *c0 = ctxs[0];
     const auto &s0 = c0->img;
-    enum { STAGE_BAYER, STAGE_RESIZE, STAGE_RECTIFY, STAGE_CLAHE, N_STAGES };       // the order of the chain
-    const bool on[N_STAGES] = {s0.bayer.on(), s0.resize.on(), s0.rectify.on(), s0.clahe.on()};
+    if (s0.pixfmt.fmt != RELOC_FMT_MONO8) *channels = 3;       // a packed frame or a mosaic: its head stage never reads this
+    enum { STAGE_BAYER, STAGE_UNPACK, STAGE_RESIZE, STAGE_RECTIFY, STAGE_CLAHE, N_STAGES };       // the order of the chain
+    const bool on[N_STAGES] = {s0.bayer.on(), s0.pixfmt.on(), s0.resize.on(), s0.rectify.on(), s0.clahe.on()};
     for (int s = 0; s < N_STAGES; ++s) {
         if (!on[s]) continue;
         const uint8_t *const *in = *srcs;
-        const int cs = plane_stride(s == STAGE_BAYER ? sw : w);        // the mosaic's plane has the source size
+        const int cs = plane_stride(s <= STAGE_UNPACK ? sw : w);       // the plane of a head stage has the source size
         int rc;
         if (s == STAGE_BAYER) {
             BayerFrames F = {};
             for (int f = 0; f < n; ++f) { F.src[f] = in[f]; planes[f] = F.dst[f] = ctxs[f]->img.bayer.plane; }
             rc = bayer_launch(c0->stream, F, n, sw, sh, *stride, cs, s0.bayer.code, 1, flags);
+        } else if (s == STAGE_UNPACK) {
+            UnpackFrames F = {};
+            for (int f = 0; f < n; ++f) { F.src[f] = in[f]; planes[f] = F.dst[f] = ctxs[f]->img.pixfmt.plane; }
+            rc = unpack_launch(c0->stream, F, n, sw, sh, *stride, cs, s0.pixfmt.fmt, flags);
         } else if (s == STAGE_RESIZE) {
             ResizeFrames F = {};
             for (int f = 0; f < n; ++f) { F.src[f] = in[f]; F.tab[f] = ctxs[f]->img.resize.tab; planes[f] = F.dst[f] = ctxs[f]->img.resize.plane; }
@@ -1015,6 +1130,10 @@ RELOC_API int reloc_set_bayer(reloc_ctx *ctx, int code)
     ARG_CHECK_CTX(ctx, true, "ctx is NULL");
     ARG_CHECK(code == 0 || bayer_code_ok(code), "reloc_set_bayer: code must be 0 (off) or one of COLOR_BayerBG2BGR .. COLOR_BayerGR2BGR (46..49)");
     BayerStage &b = ctx->img.bayer;
+    if (code && ctx->img.pixfmt.fmt != RELOC_FMT_BGR) {
+        reloc_set_error("reloc_set_bayer: a pixel format is set (reloc_set_pixel_format); a frame is a mosaic or of a pixel format, not both");
+        return RELOC_E_STATE;
+    }
     if (code && !b.plane)       // first enable: the gray plane of the largest mosaic
         if (int rc = ctx_dev_alloc(ctx, &b.plane, stage_plane_bytes(ctx))) return rc;
     b.code = code;
@@ -1025,6 +1144,80 @@ RELOC_API int reloc_get_bayer(reloc_ctx *ctx, int32_t *code)
 {
     ARG_CHECK_CTX(ctx, code, "reloc_get_bayer");
     *code = ctx->img.bayer.code;
+    return RELOC_OK;
+}
+
+// ---- pixel format entry points ------------------------------------------------------------------------------
+// the staging plane holds frames of bpp bytes per pixel; grown once, to 4 (frames in flight may still read the old one)
+static int frame_img_reserve(reloc_ctx *ctx, int bpp)
+{
+    if (bpp <= ctx->frame_img_bpp) return RELOC_OK;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    uint8_t *old = ctx->frame_img, *grown = nullptr;
+    if (int rc = ctx_dev_alloc(ctx, &grown, (int64_t)ctx->max_w * ctx->max_h * bpp)) return rc;
+    ctx->dev_blocks.erase(std::find(ctx->dev_blocks.begin(), ctx->dev_blocks.end(), (void *)old));
+    (void)hipFree(old);
+    ctx->frame_img = grown;
+    ctx->frame_img_bpp = bpp;
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_cvt_gray_u8(reloc_ctx *ctx, const uint8_t *src, int w, int h, int stride, int fmt, uint8_t *out)
+{
+    ARG_CHECK_CTX(ctx, src && out && w >= 1 && h >= 1, "reloc_cvt_gray_u8");
+    ARG_CHECK(pixfmt_packed(fmt), "reloc_cvt_gray_u8: fmt must be RELOC_FMT_BGRA, RELOC_FMT_RGBA, RELOC_FMT_YUYV or RELOC_FMT_UYVY");
+    const int bpp = pixfmt_422(fmt) ? 2 : 4;
+    ARG_CHECK(!(pixfmt_422(fmt) && (w & 1)), "reloc_cvt_gray_u8: a 4:2:2 frame has an even width");
+    ARG_CHECK(stride >= w * bpp, "reloc_cvt_gray_u8: the stride is below the row");
+    if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
+    if (int rc = frame_img_reserve(ctx, bpp)) return rc;
+    HostStaging st{ctx};
+    uint8_t *dout = st.slot<uint8_t>(0, (int64_t)w * h);
+    st.upload_rows(ctx->frame_img, src, w * bpp, h, stride);
+    UnpackFrames F = {};
+    F.src[0] = ctx->frame_img; F.dst[0] = dout;
+    st.run([&] { return unpack_launch(ctx->stream, F, 1, w, h, w * bpp, w, fmt, gray_flags(ctx, 0)); });
+    st.download(out, dout, (int64_t)w * h);
+    return st.finish();
+}
+
+RELOC_API int reloc_yuv422_bgr_u8(reloc_ctx *ctx, const uint8_t *src, int w, int h, int stride, int fmt, int order, uint8_t *out)
+{
+    ARG_CHECK_CTX(ctx, src && out && w >= 1 && h >= 1, "reloc_yuv422_bgr_u8");
+    ARG_CHECK(pixfmt_422(fmt), "reloc_yuv422_bgr_u8: fmt must be RELOC_FMT_YUYV or RELOC_FMT_UYVY");
+    ARG_CHECK(!(w & 1), "reloc_yuv422_bgr_u8: a 4:2:2 frame has an even width");
+    ARG_CHECK(stride >= w * 2, "reloc_yuv422_bgr_u8: the stride is below the row");
+    if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
+    HostStaging st{ctx};
+    uint8_t *dout = st.slot<uint8_t>(0, (int64_t)w * h * 3);
+    st.upload_rows(ctx->frame_img, src, w * 2, h, stride);
+    st.launch(k_yuv422_bgr, dim3((w / 2 + 255) / 256, h), dim3(256), ctx->frame_img, w, fmt == RELOC_FMT_UYVY, order & 1, dout);
+    st.download(out, dout, (int64_t)w * h * 3);
+    return st.finish();
+}
+
+RELOC_API int reloc_set_pixel_format(reloc_ctx *ctx, int fmt)
+{
+    ARG_CHECK_CTX(ctx, true, "ctx is NULL");
+    ARG_CHECK(fmt >= RELOC_FMT_BGR && fmt <= RELOC_FMT_UYVY, "reloc_set_pixel_format: fmt must be one of RELOC_FMT_BGR (0, the default) .. RELOC_FMT_UYVY");
+    PixfmtStage &p = ctx->img.pixfmt;
+    if (fmt && ctx->img.bayer.on()) {
+        reloc_set_error("reloc_set_pixel_format: the Bayer stage is on (reloc_set_bayer); a frame is a mosaic or of a pixel format, not both");
+        return RELOC_E_STATE;
+    }
+    if (pixfmt_packed(fmt)) {
+        if (!p.plane)           // first enable of a packed format: the gray plane of the largest frame
+            if (int rc = ctx_dev_alloc(ctx, &p.plane, stage_plane_bytes(ctx))) return rc;
+        if (int rc = frame_img_reserve(ctx, pixfmt_422(fmt) ? 2 : 4)) return rc;
+    }
+    p.fmt = fmt;
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_get_pixel_format(reloc_ctx *ctx, int32_t *fmt)
+{
+    ARG_CHECK_CTX(ctx, fmt, "reloc_get_pixel_format");
+    *fmt = ctx->img.pixfmt.fmt;
     return RELOC_OK;
 }
 

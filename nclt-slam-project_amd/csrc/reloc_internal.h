@@ -302,6 +302,18 @@ struct BayerStage {
     bool same(const BayerStage &o) const { return code == o.code; }
 };
 
+// Pixel format of the frames of the chain's entry points (reloc_set_pixel_format); RELOC_FMT_BGR = the 3-channel frames, the
+// default.  MONO8 frames are gray planes and enter the chain as they are; the packed formats (BGRA, RGBA, YUYV, UYVY) take
+// the head-of-chain stage k_unpack, in the Bayer stage's place (the two exclude each other)
+struct PixfmtStage {
+    int fmt = RELOC_FMT_BGR;
+    uint8_t *plane = nullptr;            // unpacked gray plane of a packed format, row stride (w + 63) & ~63
+    bool on() const { return fmt >= RELOC_FMT_BGRA; }                    // the unpack stage runs
+    int bpp() const { return fmt == RELOC_FMT_BGR ? 3 : fmt == RELOC_FMT_MONO8 ? 1 : fmt <= RELOC_FMT_RGBA ? 4 : 2; }
+    bool yuv422() const { return fmt == RELOC_FMT_YUYV || fmt == RELOC_FMT_UYVY; }
+    bool same(const PixfmtStage &o) const { return fmt == o.fmt; }
+};
+
 // downscale stage at the head of the image chain on 3-channel frames (reloc_set_resize); all 0 = off, the default
 struct ResizeStage {
     int sw = 0, sh = 0;                  // the size every frame must have
@@ -421,11 +433,12 @@ struct reloc_ctx {
 
     OrbState orb;                  // reloc_orb.hip
     uint8_t *frame_img = nullptr;  // staging plane of the host-pointer entry points (image stages, recording, tick, ORB): the
-                                   // caller's frame on the device, max_w * max_h * 3 bytes; no ORB state
+                                   // caller's frame on the device, max_w * max_h * frame_img_bpp bytes; no ORB state
+    int frame_img_bpp = 3;         // 4 once a 4-byte pixel format was enabled or converted (frame_img_reserve)
 
     CameraModel cam;
     // the image chain's stages in its order (reloc_image.hip); a stage's buffers are one block, taken on its first enable
-    struct { BayerStage bayer; ResizeStage resize; RectifyStage rectify; ClaheStage clahe; } img;
+    struct { BayerStage bayer; PixfmtStage pixfmt; ResizeStage resize; RectifyStage rectify; ClaheStage clahe; } img;
 
     // ---- matcher parameters (reloc_set_params) ----
     reloc_params prm;
@@ -548,25 +561,27 @@ int tick_alloc(reloc_ctx *ctx);
 void tick_release(reloc_ctx *ctx);
 // tables and tiles of a frame size on the device (cached: one geometry per context); a failure leaves no geometry
 int orb_prepare(reloc_ctx *ctx, int w, int h, int nfeatures, const OrbParams &prm);
-// ORB of frame f = srcs[f] into ctxs[f]'s feature buffers; channels == 3 -> the frames of the image chain: interleaved
-// 3-channel frames (gray fused), or raw mosaics of image_chain_frame_bpp = 1 byte per pixel with the Bayer stage on; the
+// ORB of frame f = srcs[f] into ctxs[f]'s feature buffers; chain -> the frames of the image chain, of
+// image_chain_frame_bpp bytes per pixel: interleaved 3-channel frames (gray fused), raw mosaics with the Bayer stage on, or
+// frames of the contexts' pixel format (a mono8 frame is one channel and still a frame of the chain); the
 // chain first when the contexts have stages on; with the downscale stage on, w x h is the source size and the features are
-// those of the working frame.  channels == 1 -> gray planes, never through the chain.  The chain's frames are detected
+// those of the working frame.  !chain -> a caller's gray planes, never through the chain.  The chain's frames are detected
 // under the contexts' persistent mask; call_mask: under the mask whose level 0 the caller left in mask.call (reloc_orb.hip).
 // Every frame runs with its context's persistent ORB parameters, which a batch must agree on; call_prm: one frame with
 // these instead, the blocks already grown for them (orb_grow).
-int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, int h, int stride, int channels, int order,
+int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, int h, int stride, bool chain, int order,
             int nfeatures, bool latency, bool call_mask = false, const OrbParams *call_prm = nullptr);
-// The image chain of a context's stages (reloc_image.hip states their order).  The checks stand before orb_prepare (the Bayer
-// and the downscale stage; w x h becomes the working frame) and behind that of context f (rectification, CLAHE); _gray runs
-// the stages on the frames and leaves *srcs / *stride / *channels describing the last plane written; _depth takes a
+// The image chain of a context's stages (reloc_image.hip states their order).  chain: the frames are frames of the chain
+// (orb_run).  The checks stand before orb_prepare (the Bayer stage, the pixel format and the downscale stage; w x h becomes
+// the working frame) and behind that of context f (rectification, CLAHE); _gray runs the stages on the frames and leaves
+// *srcs / *stride / *channels describing the last plane written, or the frame itself; _depth takes a
 // depth image through resize and rectification (nearest), *w x *h becomes the working frame; _frame_bpp: bytes per pixel of
-// the frames that the entry points take (3, or 1 for raw mosaics).
+// the frames that the entry points take (3; 1 for raw mosaics and mono8; 2 for 4:2:2; 4 for BGRA / RGBA).
 int image_chain_frame_bpp(const reloc_ctx *c);
-int image_chain_check(reloc_ctx *const *ctxs, int n, int channels, int *w, int *h);
-int image_chain_check_prepared(reloc_ctx *const *ctxs, int f, int n, int channels, int w, int h);
-int image_chain_gray(reloc_ctx *const *ctxs, int n, const uint8_t *const **srcs, int sw, int sh, int w, int h, int *stride,
-                     int *channels, int flags, const uint8_t **planes);
+int image_chain_check(reloc_ctx *const *ctxs, int n, bool chain, int *w, int *h);
+int image_chain_check_prepared(reloc_ctx *const *ctxs, int f, int n, bool chain, int w, int h);
+int image_chain_gray(reloc_ctx *const *ctxs, int n, bool chain, const uint8_t *const **srcs, int sw, int sh, int w, int h,
+                     int *stride, int *channels, int flags, const uint8_t **planes);
 int image_chain_depth(reloc_ctx *ctx, const uint16_t *depth_dev, int *w, int *h, const uint16_t **out);
 // PnP-RANSAC of every context's candidates with the matcher parameters of ctxs[0]; seeds: one per frame, or NULL (reloc_pnp.hip)
 int pnp_run_candidates(reloc_ctx *const *ctxs, int n, const uint64_t *seeds, bool latency);

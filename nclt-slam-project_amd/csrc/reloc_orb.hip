@@ -1182,18 +1182,19 @@ static void mask_pyramid_launch(reloc_ctx *c, uint8_t *mp)
 }
 
 // Five launches behind the image chain (reloc_image.hip): the frames are of equal geometry.  The chain serves the frames
-// of channels == 3 (3-channel, or raw mosaics with the Bayer stage on), never a caller's gray plane; with the downscale
+// of the entry points (chain: 3-channel, raw mosaics with the Bayer stage on, or the contexts' pixel format), never a
+// caller's gray plane (!chain); with the downscale
 // stage on, w x h is the source size and everything from orb_prepare on sees the working frame.  The pyramid reads the last
 // plane the chain wrote, or the frame itself.  It runs 512-thread workgroups for latency, 256 where it shares the chip with
 // whole-database scans.
-int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, int h, int stride, int channels, int order,
+int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, int h, int stride, bool chain, int order,
             int nfeatures, bool latency, bool call_mask, const OrbParams *call_prm)
 {
     if (n < 1 || n > RELOC_BATCH_MAX) { reloc_set_error("orb: 1..%d frames", RELOC_BATCH_MAX); return RELOC_E_ARG; }
     reloc_ctx *c0 = ctxs[0];
     const OrbParams P = call_prm ? *call_prm : c0->orb.prm;
     const int sw = w, sh = h;               // the frame as handed in; w x h becomes the working frame
-    if (int rc = image_chain_check(ctxs, n, channels, &w, &h)) return rc;
+    if (int rc = image_chain_check(ctxs, n, chain, &w, &h)) return rc;
     for (int f = 0; f < n; ++f) {
         reloc_ctx *c = ctxs[f];
         if (!call_prm && !c->orb.prm.same(P)) {
@@ -1206,14 +1207,14 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
             reloc_set_error("orb batch: contexts of unequal geometry");
             return RELOC_E_STATE;
         }
-        if (int rc = image_chain_check_prepared(ctxs, f, n, channels, w, h)) return rc;
-        if (channels == 3 && !c->orb.mask.same(c0->orb.mask)) {
+        if (int rc = image_chain_check_prepared(ctxs, f, n, chain, w, h)) return rc;
+        if (chain && !c->orb.mask.same(c0->orb.mask)) {
             reloc_set_error("orb batch: contexts with and without a detection mask, or with masks of unequal size (reloc_set_orb_mask)");
             return RELOC_E_STATE;
         }
     }
     // the persistent mask serves the frames of the chain and has the size of their working frame; nothing is launched otherwise
-    const bool masked = call_mask || (channels == 3 && c0->orb.mask.on());
+    const bool masked = call_mask || (chain && c0->orb.mask.on());
     if (masked && !call_mask && (w != c0->orb.mask.w || h != c0->orb.mask.h)) {
         reloc_set_error("working frame %dx%d differs from the detection mask %dx%d (reloc_set_orb_mask)", w, h, c0->orb.mask.w, c0->orb.mask.h);
         return RELOC_E_ARG;
@@ -1230,7 +1231,8 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
     hipStream_t st = c0->stream;
     reloc_prof_begin(c0, RELOC_PROF_ORB);
     const uint8_t *planes[RELOC_BATCH_MAX];
-    if (int rc = image_chain_gray(ctxs, n, &srcs, sw, sh, w, h, &stride, &channels, flags, planes)) {
+    int channels = 1;       // of what the pyramid reads: the last plane the chain wrote, a gray plane, or a 3-channel frame
+    if (int rc = image_chain_gray(ctxs, n, chain, &srcs, sw, sh, w, h, &stride, &channels, flags, planes)) {
         reloc_prof_end(c0, RELOC_PROF_ORB);
         return rc;
     }
@@ -1281,7 +1283,7 @@ RELOC_API int reloc_orb_frame_dev(reloc_ctx *ctx, const uint8_t *img_dev, int w,
 {
     ARG_CHECK_CTX(ctx, img_dev && w >= 64 && h >= 64 && nfeatures > 0, "reloc_orb_frame_dev");
     ARG_CHECK(stride >= w * image_chain_frame_bpp(ctx), "reloc_orb_frame_dev");
-    return orb_run(&ctx, 1, &img_dev, w, h, stride, 3, order, nfeatures, true);
+    return orb_run(&ctx, 1, &img_dev, w, h, stride, true, order, nfeatures, true);
 }
 
 RELOC_API const uint8_t *reloc_frame_desc_dev(reloc_ctx *ctx) { return ctx ? ctx->orb.buf.f_desc : nullptr; }
@@ -1314,7 +1316,7 @@ static int orb_detect_host(reloc_ctx *ctx, const uint8_t *gray, int w, int h, in
     st.upload_rows(ctx->frame_img, gray, w, h, stride);
     if (mask) st.run([&] { return mask_upload(ctx, ctx->orb.mask.call, mask, w, h, mask_stride); });
     const uint8_t *src = ctx->frame_img;
-    st.run([&] { return orb_run(&ctx, 1, &src, w, h, w, 1, 0, nfeatures, true, mask != nullptr, prm); });
+    st.run([&] { return orb_run(&ctx, 1, &src, w, h, w, false, 0, nfeatures, true, mask != nullptr, prm); });
     const int32_t n = st.count(ctx->orb.buf.f_count);
     if (n > 0) {
         if (xy) st.download(xy, ctx->orb.buf.f_xy, (int64_t)n * 8);

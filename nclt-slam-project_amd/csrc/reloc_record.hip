@@ -145,7 +145,7 @@ RELOC_API int reloc_record_frame(reloc_ctx *ctx, const uint8_t *img, const uint1
     const uint16_t *depth = st.upload_slot(5, depth_mm, (int64_t)w * h);
     st.run([&] {
         const uint8_t *src = ctx->frame_img;
-        if (int rc = orb_run(&ctx, 1, &src, w, h, w * bpp, 3, order, nfeatures, true)) return rc;
+        if (int rc = orb_run(&ctx, 1, &src, w, h, w * bpp, true, order, nfeatures, true)) return rc;
         return image_chain_depth(ctx, depth, &w, &h, &depth);      // from here on the working frame
     });
     RecordParams p;

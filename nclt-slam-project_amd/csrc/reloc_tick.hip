@@ -842,7 +842,7 @@ static int tick_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *imgs, i
     if (c0->max_feat > 65535) { reloc_set_error("tick: max_feat must be <= 65535"); return RELOC_E_CAPACITY; }
     const bool latency = tick_latency(ctxs, n, mode);
     int rc;
-    if ((rc = orb_run(ctxs, n, imgs, w, h, w * image_chain_frame_bpp(c0), 3, order, c0->prm.nfeatures, latency))) return rc;
+    if ((rc = orb_run(ctxs, n, imgs, w, h, w * image_chain_frame_bpp(c0), true, order, c0->prm.nfeatures, latency))) return rc;
     if (mode != RELOC_TICK_GLOBAL)
         for (int f = 0; f < n; ++f) launch_candidates_local(ctxs[f], make_tick_params(ctxs[f], base_poses + 7 * f, mode, -1));
     if (mode != RELOC_TICK_LOCAL) {
@@ -859,7 +859,7 @@ static int scan_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *imgs, i
                     const TopkBatch &out, int k, int id_base)
 {
     int rc;
-    if ((rc = orb_run(ctxs, n, imgs, w, h, w * image_chain_frame_bpp(ctxs[0]), 3, order, ctxs[0]->prm.nfeatures,
+    if ((rc = orb_run(ctxs, n, imgs, w, h, w * image_chain_frame_bpp(ctxs[0]), true, order, ctxs[0]->prm.nfeatures,
                       tick_latency(ctxs, n, RELOC_TICK_GLOBAL))))
         return rc;
     if ((rc = scan_counts(ctxs, n, base_poses, false))) return rc;

@@ -18,6 +18,12 @@ CLAHE is OpenCV's 8-bit algorithm (include/reloc_spec.h); 16-bit and colour inpu
 cvtColor with a COLOR_Bayer??2BGR / 2RGB code is OpenCV's bilinear 8-bit demosaicing (include/reloc_spec.h, "BAYER") of an
 (H, W) mosaic of at least 3 x 3; 16-bit mosaics and the _VNG, _EA, 2BGRA and direct 2GRAY codes raise.
 
+cvtColor with COLOR_BGRA2GRAY / COLOR_RGBA2GRAY takes an (H, W, 4) frame (the BGR2GRAY coefficients, alpha ignored); with
+COLOR_YUV2GRAY_YUY2 / _UYVY an (H, W, 2) packed 4:2:2 frame of even width and returns its Y bytes; with COLOR_YUV2BGR_YUY2 /
+_UYVY and the 2RGB twins OpenCV's fixed-point BT.601 (include/reloc_spec.h, "PIXEL FORMATS").  YVYU has its Y bytes where
+YUYV has them: its gray is COLOR_YUV2GRAY_YUY2.  The 4-channel outputs, YVYU to colour and the planar 4:2:0 codes raise; the Y
+plane of an NV12 / I420 buffer is frame[:H] and needs no call.
+
 remap is OpenCV's fixed-point bilinear / nearest remap with BORDER_CONSTANT (include/reloc_spec.h, "REMAP") on the backend;
 the map builders run in NumPy float64 on the host (once per camera) and honour all 14 coefficients of the default model and
 the four of the fisheye model.  Other interpolation or border modes, other dtypes and map types raise.
@@ -60,6 +66,29 @@ _BAYER_REFUSED = {
           "cvtColor(cvtColor(raw, COLOR_Bayer??2BGR), COLOR_BGR2GRAY)" for c in range(86, 90)},
     **{c: "the _EA (edge-aware) demosaicing is not implemented; use the bilinear COLOR_Bayer??2BGR" for c in range(135, 139)},
     **{c: "the COLOR_Bayer??2BGRA codes are not implemented; use COLOR_Bayer??2BGR" for c in range(139, 143)},
+}
+# packed camera formats: gray of 4-byte pixels, gray and colour of packed 4:2:2 (the spellings are OpenCV's aliases)
+COLOR_BGRA2GRAY = 10
+COLOR_RGBA2GRAY = 11
+COLOR_YUV2RGB_UYVY = COLOR_YUV2RGB_Y422 = COLOR_YUV2RGB_UYNV = 107
+COLOR_YUV2BGR_UYVY = COLOR_YUV2BGR_Y422 = COLOR_YUV2BGR_UYNV = 108
+COLOR_YUV2RGB_YUY2 = COLOR_YUV2RGB_YUYV = COLOR_YUV2RGB_YUNV = 115
+COLOR_YUV2BGR_YUY2 = COLOR_YUV2BGR_YUYV = COLOR_YUV2BGR_YUNV = 116
+COLOR_YUV2GRAY_UYVY = COLOR_YUV2GRAY_Y422 = COLOR_YUV2GRAY_UYNV = 123
+COLOR_YUV2GRAY_YUY2 = COLOR_YUV2GRAY_YUYV = COLOR_YUV2GRAY_YUNV = 124
+# code -> (backend method, pixel format, channels of the frame, RGB output)
+_PIXFMT_CODES = {
+    10: ("cvt_gray", "bgra", 4, False), 11: ("cvt_gray", "rgba", 4, False),
+    123: ("cvt_gray", "uyvy", 2, False), 124: ("cvt_gray", "yuyv", 2, False),
+    107: ("yuv422_bgr", "uyvy", 2, True), 108: ("yuv422_bgr", "uyvy", 2, False),
+    115: ("yuv422_bgr", "yuyv", 2, True), 116: ("yuv422_bgr", "yuyv", 2, False),
+}
+_PIXFMT_REFUSED = {
+    **{c: "the planar 4:2:0 codes (NV12, NV21, YV12, IYUV / I420) are not implemented; the Y plane of such a buffer is "
+          "frame[:H], a gray image already" for c in range(90, 107)},
+    **{c: "the 4-channel outputs of packed 4:2:2 (2BGRA / 2RGBA) are not implemented; use COLOR_YUV2BGR_* / COLOR_YUV2RGB_*"
+       for c in (111, 112, 119, 120, 121, 122)},
+    **{c: "YVYU to colour is not implemented (only YUY2 and UYVY); its gray is COLOR_YUV2GRAY_YUY2" for c in (117, 118)},
 }
 SOLVEPNP_ITERATIVE = 0
 SOLVEPNP_EPNP = 1
@@ -536,6 +565,10 @@ class Cv2Shim:
             raise error("cvtColor: " + _BAYER_REFUSED[code])
         if code in _BAYER_CODES:
             return self._demosaic(img, code)
+        if code in _PIXFMT_REFUSED:
+            raise error("cvtColor: " + _PIXFMT_REFUSED[code])
+        if code in _PIXFMT_CODES:
+            return self._packed(img, code)
         if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
             raise error("cvtColor: expected an (H, W, 3) uint8 image")
         if code not in (COLOR_BGR2GRAY, COLOR_RGB2GRAY):
@@ -556,6 +589,19 @@ class Cv2Shim:
         fn = self._backend("bayer", "cvtColor(Bayer)")
         try:
             return fn(img, code)
+        except RelocError as e:
+            raise error(str(e)) from e
+
+    def _packed(self, img, code):
+        """cvtColor of a packed frame: (H, W, 4) -> gray, (H, W, 2) 4:2:2 -> gray or (H, W, 3)"""
+        name, fmt, ch, rgb = _PIXFMT_CODES[code]
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != ch or img.shape[0] < 1 or img.shape[1] < 1:
+            raise error(f"cvtColor: this code expects an (H, W, {ch}) uint8 frame")
+        if ch == 2 and img.shape[1] % 2:
+            raise error("cvtColor: a packed 4:2:2 frame must have an even width")
+        fn = self._backend(name, f"cvtColor({fmt})")
+        try:
+            return fn(img, fmt) if name == "cvt_gray" else fn(img, fmt, order_rgb=rgb)
         except RelocError as e:
             raise error(str(e)) from e
 
@@ -822,8 +868,8 @@ class Cv2Shim:
         raise error("Rodrigues: expected a 3-vector or a 3x3 matrix")
 
 
-for _name, _value in list(globals().items()):       # the Bayer codes as attributes of a shim object too
-    if _name.startswith("COLOR_Bayer"):
+for _name, _value in list(globals().items()):       # the Bayer and packed-format codes as attributes of a shim object too
+    if _name.startswith(("COLOR_Bayer", "COLOR_YUV2", "COLOR_BGRA2", "COLOR_RGBA2")):
         setattr(Cv2Shim, _name, _value)
 
 

@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
+from .front_end import PIXEL_FORMATS, frame_shape_ok, pixel_format_setting
 
 K4_DEFAULT = np.array([320.0, 320.0, 320.0, 240.0], dtype=np.float64)  # fx fy cx cy (reference M:49-52)
 
@@ -57,6 +58,7 @@ class Engine:
         self.device = device
         self.max_w, self.max_h, self.max_feat = max_w, max_h, max_feat
         self._bayer = None          # set_bayer's code: the frames of tick / record_frame are then (H, W) mosaics
+        self.pixel_format = None    # set_pixel_format's name: the frames are then (H, W), (H, W, 4) or (H, W, 2)
         self._topk_dev = self._cand_dev = 0     # device scratch of the scan / solve halves (_halves_scratch)
 
     # ------------------------------------------------------------------ lifetime / plumbing
@@ -464,17 +466,73 @@ class Engine:
         N.check(self._lib.reloc_get_bayer(self._ctx, C.byref(v)), "reloc_get_bayer")
         return v.value or None
 
+    @staticmethod
+    def _packed(img, fmt, what):
+        """a packed frame of the format named fmt for a host-pointer call: (array with byte-dense pixels, w, h, RELOC_FMT_*)"""
+        img = np.asarray(img)
+        code, tail = PIXEL_FORMATS.get(str(fmt).lower(), (None, None))[:2]
+        if not tail:
+            raise N.RelocError(f'{what}: the format must be "bgra", "rgba", "yuyv" or "uyvy"')
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != tail[0] or img.shape[0] < 1 or img.shape[1] < 1:
+            raise N.RelocError(f"{what}: expected an (H, W, {tail[0]}) uint8 frame")
+        h, w = img.shape[:2]
+        if tail[0] == 2 and w % 2:
+            raise N.RelocError(f"{what}: a packed 4:2:2 frame must have an even width")
+        if img.strides[2] != 1 or img.strides[1] != tail[0] or img.strides[0] < w * tail[0]:
+            img = np.ascontiguousarray(img)
+        return img, w, h, code
+
+    def cvt_gray(self, img: np.ndarray, fmt: str) -> np.ndarray:
+        """cv2.cvtColor(img, COLOR_BGRA2GRAY / COLOR_RGBA2GRAY) of an (H, W, 4) frame (fmt "bgra" / "rgba": the gray conversion
+        with gray_coeff_bits, alpha ignored) or cv2.cvtColor(img, COLOR_YUV2GRAY_YUY2 / _UYVY) of an (H, W, 2) packed 4:2:2
+        frame of even width (fmt "yuyv" / "uyvy": the Y bytes): (H, W) uint8 (reloc_cvt_gray_u8)"""
+        img, w, h, code = self._packed(img, fmt, "cvt_gray")
+        out = np.empty((h, w), np.uint8)
+        N.check(self._lib.reloc_cvt_gray_u8(self._ctx, C.c_void_p(img.ctypes.data), w, h, img.strides[0], code, N.ptr(out)),
+                "reloc_cvt_gray_u8")
+        return out
+
+    def yuv422_bgr(self, img: np.ndarray, fmt: str, order_rgb: bool = False) -> np.ndarray:
+        """cv2.cvtColor(img, COLOR_YUV2BGR_YUY2 / _UYVY) (order_rgb: the 2RGB twins) of an (H, W, 2) packed 4:2:2 frame of
+        even width, fmt "yuyv" / "uyvy": (H, W, 3) uint8, OpenCV's fixed-point BT.601 (reloc_yuv422_bgr_u8)"""
+        img, w, h, code = self._packed(img, fmt, "yuv422_bgr")
+        if img.shape[2] != 2:
+            raise N.RelocError('yuv422_bgr: the format must be "yuyv" or "uyvy"')
+        out = np.empty((h, w, 3), np.uint8)
+        N.check(self._lib.reloc_yuv422_bgr_u8(self._ctx, C.c_void_p(img.ctypes.data), w, h, img.strides[0], code, int(order_rgb),
+                                              N.ptr(out)), "reloc_yuv422_bgr_u8")
+        return out
+
+    def set_pixel_format(self, fmt: str | None = None):
+        """The pixel format of the frames of the fused tick, recording and reloc_orb_frame_dev (reloc_set_pixel_format):
+        "mono8" (H, W) frames, used as they are; "bgra" / "rgba" (H, W, 4) and "yuyv" / "uyvy" (H, W, 2, W even) frames,
+        unpacked to gray (cvt_gray) before resize, rectification, CLAHE and ORB.  None = 3-channel frames, the default.
+        Excludes set_bayer."""
+        name = pixel_format_setting(fmt)
+        N.check(self._lib.reloc_set_pixel_format(self._ctx, PIXEL_FORMATS[name][0] if name else 0), "reloc_set_pixel_format")
+        self.pixel_format = name
+
+    def get_pixel_format(self):
+        """None for the 3-channel default, else the name"""
+        v = C.c_int32()
+        N.check(self._lib.reloc_get_pixel_format(self._ctx, C.byref(v)), "reloc_get_pixel_format")
+        return {c[0]: k for k, c in PIXEL_FORMATS.items()}.get(v.value)
+
     def _frame(self, img, what):
-        """the frame of a host-pointer entry point of the image chain: (H, W, 3), or (H, W) with the Bayer stage on"""
+        """the frame of a host-pointer entry point of the image chain: (H, W, 3), (H, W) with the Bayer stage on, or the shape
+        of the pixel format"""
         img = N.u8(img)
-        if img.ndim != (2 if self._bayer else 3) or (img.ndim == 3 and img.shape[2] != 3):
+        if not frame_shape_ok(img.shape, self.pixel_format, self._bayer):
             raise N.RelocError(f"{what}: expected an (H, W) uint8 mosaic (set_bayer is on)" if self._bayer
+                               else f"{what}: expected a uint8 {self.pixel_format} frame (set_pixel_format)" if self.pixel_format
                                else f"{what}: expected an (H, W, 3) uint8 frame")
+        if self.pixel_format in ("yuyv", "uyvy") and img.shape[1] % 2:
+            raise N.RelocError(f"{what}: a packed 4:2:2 frame must have an even width")
         return img
 
     def record_frame(self, bgr: np.ndarray, depth_mm: np.ndarray, nfeatures: int = 500, order_rgb: bool = False):
         """teach-side record arrays of one frame: dict(xy (n,2), desc (n,32), pts3d (n,3), kp_index (n,), n, n_kp); bgr:
-        (H, W, 3), or the (H, W) mosaic with the Bayer stage on"""
+        (H, W, 3), the (H, W) mosaic with the Bayer stage on, or a frame of the pixel format"""
         bgr = self._frame(bgr, "record_frame")
         depth_mm = np.ascontiguousarray(depth_mm, np.uint16)
         h, w = bgr.shape[:2]
@@ -746,7 +804,7 @@ class Engine:
         return dict(n=k, qidx=qi[:k].copy(), tidx=ti[:k].copy(), dist=dd[:k].copy(), obj=obj[:k].copy(), img=img[:k].copy())
 
     def tick(self, img, base_pose, order_rgb=False, global_reloc=False, seed=0):
-        """img: (H, W, 3), or the (H, W) mosaic with the Bayer stage on"""
+        """img: (H, W, 3), the (H, W) mosaic with the Bayer stage on, or a frame of the pixel format"""
         img = self._frame(img, "tick")
         h, w = img.shape[:2]
         bp = np.ascontiguousarray(base_pose, np.float64).reshape(7)
@@ -821,15 +879,22 @@ class Engine:
         self.tick_scan_into(img_dev, w, h, base_pose, k, t, t + 4 * MAX_CAND, t + 8 * MAX_CAND, order_rgb)
 
     def orb_frame_dev(self, img_dev: int, w: int, h: int, stride: int | None = None, order_rgb=False, nfeatures: int = 500) -> int:
-        """gray + ORB of an interleaved 3-channel frame (with the Bayer stage on: a single-channel mosaic, stride in its bytes)
+        """gray + ORB of an interleaved 3-channel frame (with the Bayer stage on: a single-channel mosaic, stride in its bytes;
+        with a pixel format: a frame of 1, 2 or 4 bytes per pixel, stride in bytes)
         resident in device memory (reloc_orb_frame_dev); returns the number of keypoints (synchronises).  Descriptors /
         coordinates stay on the device; frame_debug_plane() reads planes."""
-        N.check(self._lib.reloc_orb_frame_dev(self._ctx, C.c_void_p(img_dev), int(w), int(h), int(stride or (1 if self._bayer else 3) * w),
+        N.check(self._lib.reloc_orb_frame_dev(self._ctx, C.c_void_p(img_dev), int(w), int(h), int(stride or self._frame_bpp() * w),
                                               int(order_rgb), int(nfeatures)), "reloc_orb_frame_dev")
         nf = np.empty(1, np.int32)
         N.check(self._lib.reloc_d2h(self._ctx, N.ptr(nf), C.c_void_p(self._lib.reloc_frame_count_dev(self._ctx)), 4), "reloc_d2h")
         self.sync()
         return int(nf[0])
+
+    def _frame_bpp(self):
+        """bytes per pixel of the frames of the image chain's entry points"""
+        if self._bayer:
+            return 1
+        return 3 if self.pixel_format is None else int(np.prod(PIXEL_FORMATS[self.pixel_format][1], dtype=int))
 
     def orb_features(self):
         """descriptors and coordinates of the frame last extracted on the device (orb_frame_dev / a tick), copied to the host"""

@@ -1,4 +1,4 @@
-"""The camera front end of the host layer, stated once: the seven settings a teach run and its repeat runs share (`FrontEnd`),
+"""The camera front end of the host layer, stated once: the eight settings a teach run and its repeat runs share (`FrontEnd`),
 their checks, and the two ways they reach ORB -- `FrontEnd.configure` on an Engine (the fused matcher, the recorder's device
 path) and `ImageChain` on a cv2-shaped module (`LandmarkMatcherCore`, the recorder's NumPy path) -- with the command-line
 flags of the ROS entry points.  None of the settings is stored in landmarks.pkl: teach and repeat are given the same ones.
@@ -41,6 +41,26 @@ def bayer_setting(pattern):
     if code is None:
         raise ValueError('bayer must be None or one of "BG", "GB", "RG", "GR" (OpenCV\'s letters: RGGB, GRBG, BGGR, GBRG sensors)')
     return code
+
+
+# FrontEnd.pixel_format -> (RELOC_FMT_* of reloc_set_pixel_format, trailing shape of a frame, the one cvtColor code of its gray)
+PIXEL_FORMATS = {"mono8": (1, (), None), "bgra": (2, (4,), 10), "rgba": (3, (4,), 11), "yuyv": (4, (2,), 124), "uyvy": (5, (2,), 123)}
+
+
+def pixel_format_setting(fmt):
+    """FrontEnd.pixel_format as its lower-case name (None stays None)"""
+    if fmt is None:
+        return None
+    name = str(fmt).lower()
+    if name not in PIXEL_FORMATS:
+        raise ValueError('pixel_format must be None (BGR / RGB) or one of "mono8", "bgra", "rgba", "yuyv", "uyvy"')
+    return name
+
+
+def frame_shape_ok(shape, pixel_format=None, bayer=None):
+    """a frame of this shape is what the front end takes: (H, W) mosaics and mono8, (H, W, 2) 4:2:2, (H, W, 3), (H, W, 4)"""
+    tail = () if bayer is not None else (3,) if pixel_format is None else PIXEL_FORMATS[pixel_format][1]
+    return len(shape) == 2 + len(tail) and tuple(shape[2:]) == tail
 
 
 def mask_setting(mask):
@@ -104,8 +124,9 @@ def _same(a, b):
 
 @dataclass(frozen=True, eq=False)
 class FrontEnd:
-    """What stands between the camera and ORB, and the camera's lens model: `MatcherConfig` carries the same seven fields,
-    `LandmarkRecorderCore` takes them as keywords.  resize, bayer, mask and orb are checked on construction (ValueError)."""
+    """What stands between the camera and ORB, and the camera's lens model: `MatcherConfig` carries the same eight fields,
+    `LandmarkRecorderCore` takes them as keywords.  resize, bayer, mask, orb and pixel_format are checked on construction
+    (ValueError)."""
     # lens distortion, OpenCV's (k1, k2, p1, p2[, k3]) -- e.g. sensor_msgs/CameraInfo.d of a plumb_bob camera; () = pinhole
     # (the reference's DIST = zeros, M:52).  Longer OpenCV vectors are accepted when everything after k3 is zero.  The kept
     # keypoints of a recording are back-projected through the inverse model.
@@ -139,11 +160,20 @@ class FrontEnd:
     # fastThreshold, scoreType) / a dict with those cv2 keyword names, e.g. dict(fastThreshold=7) for dim scenes, dict(nlevels=4,
     # scaleFactor=1.5) for a small resized frame, dict(scoreType=1) for cv2.ORB_FAST_SCORE (include/reloc_spec.h "ORB PARAMS").
     orb: tuple | dict | None = None
+    # pixel format of the camera's frames: None = 3-channel BGR (the reference matcher), or "mono8" -- (H, W) frames of a
+    # grayscale camera (a T265, most industrial global-shutter cameras; also the Y plane frame[:H] of an NV12 / I420 buffer),
+    # used as they are; "bgra" / "rgba" -- (H, W, 4) frames, gray as cv2.cvtColor(f, cv2.COLOR_BGRA2GRAY), alpha ignored;
+    # "yuyv" / "uyvy" -- (H, W, 2) packed 4:2:2 frames of a UVC camera, W even, gray as cv2.cvtColor(f, cv2.COLOR_YUV2GRAY_YUY2):
+    # the Y bytes (YVYU frames are "yuyv").  Excludes bayer; resize takes the frame's size as its source.
+    pixel_format: str | None = None
 
     def __post_init__(self):
         object.__setattr__(self, "dist", () if self.dist is None else tuple(float(v) for v in np.asarray(self.dist, np.float64).ravel()))
-        for check, value in ((resize_setting, self.resize), (bayer_setting, self.bayer), (mask_setting, self.mask), (orb_setting, self.orb)):
+        for check, value in ((resize_setting, self.resize), (bayer_setting, self.bayer), (mask_setting, self.mask), (orb_setting, self.orb),
+                             (pixel_format_setting, self.pixel_format)):
             check(value)
+        if self.bayer is not None and self.pixel_format is not None:
+            raise ValueError("bayer and pixel_format exclude each other: a frame is a raw mosaic or of a pixel format, not both")
 
     def __eq__(self, other):
         return isinstance(other, FrontEnd) and all(_same(getattr(self, f.name), getattr(other, f.name)) for f in fields(self))
@@ -153,7 +183,15 @@ class FrontEnd:
         engine.set_distortion(self.dist)
         engine.set_orb_params(*(orb_setting(self.orb) or ORB_DEFAULTS))
         engine.set_orb_mask(mask_setting(self.mask))
-        engine.set_bayer(bayer_setting(self.bayer))
+        # the pixel format and Bayer exclude each other on a context: the one that is off is set first.  A format is switched
+        # off where the engine has one (Engine.pixel_format), so the default front end makes the calls it always made
+        if self.pixel_format is None:
+            if isinstance(getattr(engine, "pixel_format", None), str):
+                engine.set_pixel_format(None)
+            engine.set_bayer(bayer_setting(self.bayer))
+        else:
+            engine.set_bayer(None)
+            engine.set_pixel_format(pixel_format_setting(self.pixel_format))
         engine.set_clahe(*((None,) if self.clahe is None else (self.clahe[0], tuple(self.clahe[1]))))
         engine.set_resize(*((None, None) if self.resize is None else ((engine.max_w, engine.max_h), resize_setting(self.resize))))
         engine.set_rectify(self.rectify)
@@ -168,6 +206,7 @@ class ImageChain:
         self.cv2 = cv2
         self.mask = mask_setting(fe.mask)
         self.bayer = bayer_setting(fe.bayer)
+        self.pixel_format = pixel_format_setting(fe.pixel_format)
         self.resize = resize_setting(fe.resize)
         self.dist = np.asarray(fe.dist, np.float64).reshape(-1, 1) if fe.dist else np.zeros((4, 1), dtype=np.float32)
         self.clahe = self.rectify = self.orb = None
@@ -177,8 +216,12 @@ class ImageChain:
             self.rectify = fixed_rectify_maps(cv2, fe.rectify)
 
     def gray(self, frame):
-        """the camera frame as gray: a BGR frame, or a raw mosaic through the two cvtColor calls of the reference"""
+        """the camera frame as gray: a BGR frame, a raw mosaic through the two cvtColor calls of the reference, or a frame
+        of the pixel format through its one call (a mono8 frame is gray)"""
         cv2 = self.cv2
+        if self.pixel_format is not None:
+            code = PIXEL_FORMATS[self.pixel_format][2]
+            return frame if code is None else cv2.cvtColor(frame, code)
         if self.bayer is not None:
             frame = cv2.cvtColor(frame, self.bayer)
         return cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY)
@@ -215,8 +258,10 @@ def load_mask(path):
 
 
 def add_front_end_flags(ap):
-    """--bayer, --mask and --orb-nlevels, --orb-scale-factor, --orb-fast-threshold, --orb-score (cv2.ORB_create's keywords)"""
+    """--bayer, --pixel-format, --mask and --orb-nlevels, --orb-scale-factor, --orb-fast-threshold, --orb-score (cv2.ORB_create's keywords)"""
     ap.add_argument("--bayer", default=None, choices=["BG", "GB", "RG", "GR"], help="the colour topic carries raw 8-bit mosaics of this pattern")
+    ap.add_argument("--pixel-format", default=None, choices=sorted(PIXEL_FORMATS),
+                    help="the colour topic carries frames of this format (mono8, bgra8 / rgba8, yuv422 = uyvy, yuv422_yuy2 = yuyv), passed through undecoded")
     ap.add_argument("--mask", default=None, metavar="FILE.npy",
                     help="ORB takes no keypoint where this (H, W) uint8 array (a .npy file, size of the frame ORB sees) is zero")
     ap.add_argument("--orb-nlevels", type=int, default=None, metavar="N", help="ORB pyramid levels, 1..8 (default 8)")
@@ -226,7 +271,7 @@ def add_front_end_flags(ap):
 
 
 def front_end_flags(args):
-    """(bayer, mask, orb) of those flags as FrontEnd takes them; orb is None when no --orb-* flag is given or they spell the
+    """(bayer, mask, orb) of those flags as FrontEnd takes them (--pixel-format is args.pixel_format as it stands); orb is None when no --orb-* flag is given or they spell the
     defaults, else the checked tuple (a bad value: ValueError)"""
     given = dict(zip(ORB_KEYS, (args.orb_nlevels, args.orb_scale_factor, args.orb_fast_threshold,
                                 None if args.orb_score is None else int(args.orb_score == "fast"))))

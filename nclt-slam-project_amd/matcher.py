@@ -21,7 +21,7 @@ from dataclasses import dataclass, field, fields
 import numpy as np
 
 from . import pose as P
-from .front_end import FrontEnd, ImageChain, scaled_camera  # noqa: F401  (scaled_camera: INTEGRATION.md names it here)
+from .front_end import FrontEnd, ImageChain, frame_shape_ok, scaled_camera  # noqa: F401  (scaled_camera: INTEGRATION.md names it here)
 from .landmarks import load_landmarks, pack_landmarks, save_landmarks
 
 CSV_HEADER = "ts,vio_x,vio_y,candidates_tried,best_n_inliers,best_reproj_err,anchor_x,anchor_y,outcome\n"
@@ -33,7 +33,7 @@ class MatcherConfig:
     fy: float = 320.0
     cx: float = 320.0
     cy: float = 240.0
-    # the camera front end, as front_end.FrontEnd describes the seven fields; front_end gives them as one checked object
+    # the camera front end, as front_end.FrontEnd describes the eight fields; front_end gives them as one checked object
     dist: tuple = ()
     clahe: tuple | None = None
     rectify: tuple | None = None
@@ -41,6 +41,7 @@ class MatcherConfig:
     bayer: str | None = None
     mask: np.ndarray | None = None
     orb: tuple | dict | None = None
+    pixel_format: str | None = None
     candidate_radius_m: float = 8.0
     max_candidates: int = 5
     heading_tol_deg: float = 90.0
@@ -292,8 +293,8 @@ class LandmarkMatcherCore(_MatcherSession):
         return len(inliers), err, P.cam_world_to_base_world(cam_world, self.base_to_cam_t, self.base_to_cam_R)
 
     def tick(self, bgr, depth_mm, base_pose, ts=None, drift_est=0.0):
-        """One repeat attempt.  bgr: (H,W,3) u8, or the (H,W) u8 mosaic of a raw camera (cfg.bayer); depth_mm: (H,W) u16 or
-        None; base_pose: 7-tuple."""
+        """One repeat attempt.  bgr: (H,W,3) u8, the (H,W) u8 mosaic of a raw camera (cfg.bayer), or a frame of
+        cfg.pixel_format; depth_mm: (H,W) u16 or None; base_pose: 7-tuple."""
         cfg = self.cfg
         self.maybe_swap_to_return()
         if bgr is None or base_pose is None:
@@ -439,7 +440,8 @@ class FusedLandmarkMatcher(_MatcherSession):
         """One repeat attempt.  global_reloc: None = decide as the reference does (local candidates; the whole-database
         search only under G's trigger, when cfg.global_reloc is set), True = whole-database search unconditionally
         (benchmark shape), False = local only.  depth_mm enables accumulation (cfg.accum_enable).  bgr: (H,W,3) u8, or with
-        cfg.bayer the (H,W) u8 mosaic of the raw camera: a third of the bytes to upload."""
+        cfg.bayer the (H,W) u8 mosaic of the raw camera: a third of the bytes to upload; with cfg.pixel_format an (H,W) mono8,
+        (H,W,4) BGRA / RGBA or (H,W,2) YUYV / UYVY frame."""
         cfg, e = self.cfg, self.engine
         self.maybe_swap_to_return()
         if bgr is None or base_pose is None:
@@ -452,8 +454,9 @@ class FusedLandmarkMatcher(_MatcherSession):
         else:
             mode = 1 if global_reloc else 0
         bgr = np.ascontiguousarray(bgr, np.uint8)
-        if bgr.ndim != (3 if cfg.bayer is None else 2):
-            raise ValueError("tick: expected an (H, W) mosaic" if cfg.bayer else "tick: expected an (H, W, 3) frame")
+        if not frame_shape_ok(bgr.shape, cfg.pixel_format, cfg.bayer):
+            raise ValueError("tick: expected an (H, W) mosaic" if cfg.bayer else f"tick: expected a {cfg.pixel_format} frame"
+                             if cfg.pixel_format else "tick: expected an (H, W, 3) frame")
         h, w = bgr.shape[:2]
         e.tick_dev(self._stage("img", bgr), w, h, base_pose, order_rgb=False, global_reloc=mode, seed=self.seed)
         accumulate = cfg.accum_enable and depth_mm is not None

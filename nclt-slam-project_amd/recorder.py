@@ -41,12 +41,12 @@ def local_depth_std(depth_mm, uu, vv):
 
 class LandmarkRecorderCore:
     def __init__(self, out_pkl=None, min_disp_m: float = 2.0, cv2=None, nfeatures: int = 500, logger=None, engine=None,
-                 dist=(), clahe=None, rectify=None, resize=None, bayer=None, mask=None, orb=None):
+                 dist=(), clahe=None, rectify=None, resize=None, bayer=None, mask=None, orb=None, pixel_format=None):
         """engine: when given, ORB + all per-keypoint gates + back-projection run in ONE device call
         (reloc_record_frame); otherwise the gates run in NumPy on the cv2-shaped module's features.
-        dist, clahe, rectify, resize, bayer, mask, orb: the camera front end, as front_end.FrontEnd describes them."""
+        dist, clahe, rectify, resize, bayer, mask, orb, pixel_format: the camera front end, as front_end.FrontEnd describes them."""
         self.engine = engine
-        self.front_end = fe = FrontEnd(dist, clahe, rectify, resize, bayer, mask, orb)
+        self.front_end = fe = FrontEnd(dist, clahe, rectify, resize, bayer, mask, orb, pixel_format)
         if engine is not None:
             fe.configure(engine)
         self.nfeatures = nfeatures

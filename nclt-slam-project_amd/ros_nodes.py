@@ -16,7 +16,7 @@ import sys
 
 import numpy as np
 
-from .front_end import add_front_end_flags, front_end_flags, load_mask  # noqa: F401  (load_mask: part of this module's interface)
+from .front_end import PIXEL_FORMATS, add_front_end_flags, front_end_flags, load_mask, pixel_format_setting  # noqa: F401  (load_mask: part of this module's interface)
 from .matcher import FusedLandmarkMatcher, LandmarkMatcherCore, MatcherConfig
 from .recorder import LandmarkRecorderCore
 
@@ -37,9 +37,23 @@ def img_msg_to_bgr(msg):
 BAYER_ENCODINGS = {"bayer_rggb8": "BG", "bayer_grbg8": "GB", "bayer_bggr8": "RG", "bayer_gbrg8": "GR"}     # sensor_msgs -> OpenCV's letters
 
 
-def img_msg_to_frame(msg, bayer=None):
+# sensor_msgs encodings of FrontEnd.pixel_format (yuv422 is UYVY, yuv422_yuy2 is YUYV; uyvy / yuyv are their newer names)
+PIXEL_FORMAT_ENCODINGS = {"mono8": "mono8", "bgra8": "bgra", "rgba8": "rgba", "yuv422": "uyvy", "uyvy": "uyvy",
+                          "yuv422_yuy2": "yuyv", "yuyv": "yuyv"}
+
+
+def img_msg_to_frame(msg, bayer=None, pixel_format=None):
     """the colour topic's frame as the cores take it: BGR, or with bayer = "BG" / "GB" / "RG" / "GR" (FrontEnd.bayer) the
-    camera's raw 8-bit mosaic, undecoded: mono8 (the driver does not name the pattern) or the bayer_* encoding of that pattern"""
+    camera's raw 8-bit mosaic, undecoded: mono8 (the driver does not name the pattern) or the bayer_* encoding of that pattern;
+    or with pixel_format (FrontEnd.pixel_format) the frame of that format, undecoded: (H, W), (H, W, 4) or (H, W, 2)"""
+    if pixel_format is not None:
+        fmt = pixel_format_setting(pixel_format)
+        if PIXEL_FORMAT_ENCODINGS.get(msg.encoding) != fmt:
+            raise ValueError(f"encoding {msg.encoding} is not a frame of pixel format {fmt}")
+        tail = PIXEL_FORMATS[fmt][1]
+        row = msg.width * (tail[0] if tail else 1)
+        step = getattr(msg, "step", 0) or row
+        return np.frombuffer(msg.data, dtype=np.uint8).reshape(msg.height, step)[:, :row].reshape(msg.height, msg.width, *tail).copy()
     if bayer is None:
         return img_msg_to_bgr(msg)
     if msg.encoding != "mono8" and BAYER_ENCODINGS.get(msg.encoding) != bayer.upper():
@@ -80,10 +94,11 @@ def _node_base():
 
 
 def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global_reloc=False, fused=False, cv2=None, bayer=None,
-                      mask=None, orb=None):
+                      mask=None, orb=None, pixel_format=None):
     """cv2: the cv2-shaped module the ROS-free core calls (default: the HIP shim); only the non-fused core uses it.
     bayer: FrontEnd.bayer -- the colour topic carries raw mosaics, passed through undecoded.  mask: FrontEnd.mask.
-    orb: FrontEnd.orb"""
+    orb: FrontEnd.orb.  pixel_format: FrontEnd.pixel_format -- the colour topic carries frames of that format, passed through
+    undecoded"""
     from geometry_msgs.msg import PoseWithCovarianceStamped
     from sensor_msgs.msg import Image
     Node = _node_base()
@@ -91,7 +106,7 @@ def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global
     class VisualLandmarkMatcher(Node):
         def __init__(self):
             super().__init__("visual_landmark_matcher")
-            cfg = MatcherConfig(global_reloc=global_reloc, bayer=bayer, mask=mask, orb=orb)
+            cfg = MatcherConfig(global_reloc=global_reloc, bayer=bayer, mask=mask, orb=orb, pixel_format=pixel_format)
             if fused:
                 self.core = FusedLandmarkMatcher(pkl_path, log_csv, config=cfg, return_landmarks=return_pkl,
                                                  swap_flag=swap_flag, logger=lambda m: self.get_logger().info(m),
@@ -112,7 +127,7 @@ def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global
 
         def _rgb_cb(self, msg):
             try:
-                self.last_rgb = img_msg_to_frame(msg, bayer)
+                self.last_rgb = img_msg_to_frame(msg, bayer, pixel_format)
             except Exception as e:
                 self.get_logger().warn(f"rgb: {e}")
 
@@ -146,14 +161,14 @@ def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global
     return VisualLandmarkMatcher()
 
 
-def make_recorder_node(out_pkl, min_disp_m=2.0, cv2=None, bayer=None, mask=None, orb=None):
+def make_recorder_node(out_pkl, min_disp_m=2.0, cv2=None, bayer=None, mask=None, orb=None, pixel_format=None):
     from sensor_msgs.msg import Image
     Node = _node_base()
 
     class VisualLandmarkRecorder(Node):
         def __init__(self):
             super().__init__("visual_landmark_recorder")
-            self.core = LandmarkRecorderCore(out_pkl, min_disp_m, cv2=cv2, bayer=bayer, mask=mask, orb=orb)
+            self.core = LandmarkRecorderCore(out_pkl, min_disp_m, cv2=cv2, bayer=bayer, mask=mask, orb=orb, pixel_format=pixel_format)
             self.last_rgb = self.last_depth = None
             self.last_rgb_ts = 0.0
             self.create_subscription(Image, "/camera/color/image_raw", self._rgb_cb, 10)
@@ -164,7 +179,7 @@ def make_recorder_node(out_pkl, min_disp_m=2.0, cv2=None, bayer=None, mask=None,
 
         def _rgb_cb(self, msg):
             try:
-                self.last_rgb = img_msg_to_frame(msg, bayer)
+                self.last_rgb = img_msg_to_frame(msg, bayer, pixel_format)
                 self.last_rgb_ts = msg.header.stamp.sec + msg.header.stamp.nanosec * 1e-9
             except Exception as e:
                 self.get_logger().warn(f"rgb cb: {e}")
@@ -186,9 +201,9 @@ def make_recorder_node(out_pkl, min_disp_m=2.0, cv2=None, bayer=None, mask=None,
 
 
 def _chain_args(args):
-    """the trailing (cv2, bayer, mask, orb) of the node factories; cv2 None = the default shim; only as far as the last one
-    that is not its default, nothing when all are defaults"""
-    tail = [None, *front_end_flags(args)]
+    """the trailing (cv2, bayer, mask, orb, pixel_format) of the node factories; cv2 None = the default shim; only as far as
+    the last one that is not its default, nothing when all are defaults"""
+    tail = [None, *front_end_flags(args), pixel_format_setting(getattr(args, "pixel_format", None))]
     while tail and tail[-1] is None:
         tail.pop()
     return tuple(tail)
