@@ -201,6 +201,22 @@ int reloc_match_mutual(reloc_ctx *ctx, const uint8_t *q, int nq, const uint8_t *
  * idx/dist are nq x 2; a missing second neighbour is (-1, -1). */
 int reloc_match_knn2(reloc_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t, int nt,
                      int32_t *idx, int32_t *dist);
+/* knnMatch(q, t, k=2) + Lowe test in one call: the lists of the MATCH POLICY block of reloc_spec.h (queryIdx = row of q in
+ * ascending order, trainIdx = its nearest row of t, distance), outputs sized nq.  ratio: finite, in (0, 1], else RELOC_E_ARG.
+ * nq <= 65535 (the capacity of a frame's features), nt < 2^22. */
+int reloc_match_ratio(reloc_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t, int nt, double ratio,
+                      int32_t *qidx, int32_t *tidx, int32_t *dist, int32_t *n_out);
+/* Match policy of the tick (reloc_spec.h, "MATCH POLICY"): how the candidate records are paired with the frame's features
+ * (the match lists and the 3-D / 2-D pairs PnP is given) and what the whole-database search counts per record.  Persists
+ * like the other reloc_set_* settings; a new context has (RELOC_MATCH_CROSS, 0.8).  Any other policy, a non-finite ratio or
+ * one outside (0, 1]: RELOC_E_ARG.  With RELOC_MATCH_CROSS the ratio is stored and ignored.  Read by every tick entry point
+ * (reloc_tick*, reloc_tick_scan_dev / _solve_dev, reloc_shard_scan_batch_dev / _solve_batch_dev); the contexts of a batch must
+ * agree (RELOC_E_STATE).  A ratio list holds up to max_feat entries, so under RELOC_MATCH_RATIO a context whose max_feat
+ * exceeds 4096 (the stride of the match lists) is refused by the tick entry points with RELOC_E_CAPACITY. */
+#define RELOC_MATCH_CROSS 0   /* BFMatcher(crossCheck=True).match(desc_t, desc_curr)          M:211,327 */
+#define RELOC_MATCH_RATIO 1   /* knnMatch(desc_curr, desc_t, k=2) + Lowe test                 S:68-71   */
+int reloc_set_match_policy(reloc_ctx *ctx, int policy, double ratio);
+int reloc_get_match_policy(reloc_ctx *ctx, int32_t *policy, double *ratio);
 /* landmarks.pkl -> packed device arena (R:290-297, M:179-187).  desc: T x 32; pts3d: T x 3
  * (keypoints_3d_cam); offsets: L+1 row offsets; poses: L x 7 camera pose (x y z qx qy qz qw).
  * Replaces any previously uploaded database. */
@@ -481,7 +497,11 @@ int reloc_tick_debug(reloc_ctx *ctx, int32_t *cand_ids, int32_t *n_cand, int32_t
  * entries of qidx (row within the record), tidx (current feature), dist (Hamming distance), in queryIdx order; obj (*n x 3,
  * the record's keypoints_3d_cam[qidx]) and img (*n x 2, the current keypoint xy[tidx]).  Every output pointer may be NULL;
  * arrays need room for the record's rows.  RELOC_E_ARG when slot is not in [0, n_cand) of that solve (read from the device
- * as reloc_tick_debug does).  Synchronises the context's stream; copies only, launches nothing. */
+ * as reloc_tick_debug does).  Synchronises the context's stream; copies only, launches nothing.
+ * The lists come in the orientation of the match policy in force at that solve (reloc_set_match_policy).  Under
+ * RELOC_MATCH_RATIO: *n Lowe survivors, qidx = current feature, tidx = row within the record, obj = keypoints_3d_cam[tidx],
+ * img = xy[qidx], arrays need room for max_feat entries; a record of fewer than min_matches rows keeps its list here and
+ * is given no PnP (reloc_tick_debug reports n_matches 0 for it). */
 int reloc_tick_debug_matches(reloc_ctx *ctx, int slot, int32_t *n, int32_t *qidx, int32_t *tidx, int32_t *dist,
                              float *obj, float *img);
 /* Sharded database (one rank per GPU): per-record mutual-match counts are local; the caller

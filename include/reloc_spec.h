@@ -300,4 +300,22 @@
 #define RELOC_FAST_THRESHOLD_MIN   1            /* the score plane is 8-bit and 0 means "no corner" */
 #define RELOC_FAST_THRESHOLD_MAX   254
 
+/* MATCH POLICY: how a record's descriptors are paired with the current frame's.  RELOC_MATCH_CROSS (the default) is
+ * BFMatcher(NORM_HAMMING, crossCheck=True).match(desc_t, desc_curr), the matcher of visual_landmark_matcher.py:211,327.
+ * RELOC_MATCH_RATIO restates experiments/62_tight_detour_anchor_sanity/scripts/checkpoint_a_selftest.py:68-77 (knnMatch(desc_curr,
+ * desc_t, k=2), Lowe test, gather, solvePnPRansac) and the score of simulation/isaac/scripts/_archive/anchor_localizer.py:82-90:
+ *   sets       query = the current frame's descriptors (column c, 0 <= c < C); train = the rows of ONE record (row r, 0 <= r < n).
+ *   neighbours per query c: nearest row = smallest Hamming distance, lowest row index on ties (d1); second nearest = the
+ *              smallest remaining (distance, index) (d2).  This is reloc_match_knn2(current, record), idx and dist alike.
+ *   test       c is a match iff n >= 2 and (double)d1 < ratio * (double)d2: strict, in double, one multiplication.  A record of
+ *              fewer than two rows yields no match; two identical rows nearest to c (d1 == d2) yield none at any ratio <= 1.
+ *   list       (queryIdx = c, trainIdx = nearest row, distance = d1), in queryIdx order.  Up to C entries.
+ *   pairs      keypoints_3d_cam[trainIdx], pts_curr_2d[queryIdx]: the opposite orientation to the crossCheck list, whose
+ *              queryIdx is the teach row.
+ *   score      of a record in the whole-database search: the length of its list.
+ *   ratio      a finite double in (0, 1].
+ *   gates      unchanged and in the reference's order: a record of len(desc_t) < min_matches rows is no candidate and is given
+ *              no PnP (S:64), a list shorter than min_matches neither (S:72); inliers, reprojection, consistency as before. */
+#define RELOC_LOWE_RATIO           0.80         /* LOWE_RATIO, visual_landmark_matcher.py:66 ("kept for docs"), S:71 */
+
 #endif /* RELOC_SPEC_H */

@@ -55,6 +55,9 @@ SIGNATURES = {
     "reloc_db_ratio_counts": (C.c_int, [c_ctx, P, C.c_int, f64, P]),
     "reloc_match_mutual": (C.c_int, [c_ctx, P, C.c_int, P, C.c_int, P, P, P, P]),
     "reloc_match_knn2": (C.c_int, [c_ctx, P, C.c_int, P, C.c_int, P, P]),
+    "reloc_match_ratio": (C.c_int, [c_ctx, P, C.c_int, P, C.c_int, f64, P, P, P, P]),
+    "reloc_set_match_policy": (C.c_int, [c_ctx, C.c_int, f64]),
+    "reloc_get_match_policy": (C.c_int, [c_ctx, P, P]),
     "reloc_db_upload": (C.c_int, [c_ctx, P, P, P, P, i64]),
     "reloc_db_records": (i64, [c_ctx]),
     "reloc_db_rows": (i64, [c_ctx]),

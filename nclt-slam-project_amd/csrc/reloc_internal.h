@@ -361,6 +361,15 @@ struct OrbMaskStage {
     bool same(const OrbMaskStage &o) const { return w == o.w && h == o.h; }      // the masks themselves may differ per context
 };
 
+// Match policy of the tick (reloc_set_match_policy; include/reloc_spec.h "MATCH POLICY"): the two places it decides are
+// scan_counts() and launch_tick_emit()
+struct MatchPolicy {
+    int policy = RELOC_MATCH_CROSS;
+    double ratio = RELOC_LOWE_RATIO;     // stored and ignored under RELOC_MATCH_CROSS
+    bool ratio_on() const { return policy == RELOC_MATCH_RATIO; }
+    bool same(const MatchPolicy &o) const { return policy == o.policy && ratio == o.ratio; }
+};
+
 // What the five ORB kernels read and write of one frame, in the form they take it: a single-frame launch passes the members
 // as arguments, a batched one up to 8 of these in its kernel arguments (OrbBatch, blockIdx.y = frame).
 struct OrbFrame {
@@ -398,7 +407,8 @@ struct TickState {
     int32_t *cand_n = nullptr;       // 1
     int32_t *flags = nullptr;        // [0] relocating: the candidates came from the whole-database search
     int32_t *m_qidx = nullptr, *m_tidx = nullptr, *m_dist = nullptr;    // MAX_CAND x MAX_REC_ROWS match lists of the emit pass
-    int32_t *m_n = nullptr;          // MAX_CAND list lengths
+    int32_t *m_n = nullptr;          // MAX_CAND list lengths; behind them MAX_CAND more, written under RELOC_MATCH_RATIO only:
+                                     // the lengths PnP reads there, 0 where the record-length gate closed (tick_pnp_lengths)
     float *p_obj = nullptr, *p_img = nullptr;     // MAX_CAND x MAX_REC_ROWS x {3, 2}: the 3-D / 2-D pairs PnP is given
     double *p_Rt = nullptr;          // MAX_CAND x MAX_HYP x 12
     int32_t *p_cnt = nullptr;        // MAX_CAND x MAX_HYP
@@ -440,8 +450,9 @@ struct reloc_ctx {
     // the image chain's stages in its order (reloc_image.hip); a stage's buffers are one block, taken on its first enable
     struct { BayerStage bayer; PixfmtStage pixfmt; ResizeStage resize; RectifyStage rectify; ClaheStage clahe; } img;
 
-    // ---- matcher parameters (reloc_set_params) ----
+    // ---- matcher parameters (reloc_set_params) and match policy (reloc_set_match_policy) ----
     reloc_params prm;
+    MatchPolicy match;
     int scan_gens = 0;               // RELOC_SCAN_GENS (developer switch), read once at creation: n > 0 = single whole-database
                                      // scans in the form of batched ones (n generations of row budgets + sweepers, launch_db_count)
     uint32_t *scan_ticket = nullptr; // SCAN_TICKET_WORDS counters of the whole-database scans (scan_alloc, reloc_match.hip)
@@ -543,8 +554,13 @@ static inline void frame_slots(reloc_ctx *const *ctxs, int n, Fn fn)
 int launch_db_count(reloc_ctx *ctx, const uint8_t *cur, const int32_t *n_cur_dev, int n_cur_max, int32_t *counts,
                     const ScanMask &mask = {});
 int launch_db_scan_batch(reloc_ctx *const *ctxs, int n, const double *q, double cos_tol, bool auto_mode, bool heading_mask = true);
+// The same scans under RELOC_MATCH_RATIO: counts[record] = Lowe survivors of every context's features against the record
+// (k_db_ratio), 0 for records of fewer than min_matches rows.  base_poses: n x 7 (heading mask) or NULL.
+int launch_db_ratio_scan(reloc_ctx *const *ctxs, int n, const double *base_poses, double cos_tol, bool auto_mode);
 // the emit pass of a tick: match lists, with their 3-D / 2-D pairs, of every context's candidate records (reloc_match.hip)
 int launch_tick_emit(reloc_ctx *const *ctxs, int n, bool latency);
+// the list lengths of a context's candidates as PnP takes them (see TickState::m_n)
+static inline const int32_t *tick_pnp_lengths(const reloc_ctx *c) { return c->tick.m_n + (c->match.ratio_on() ? MAX_CAND : 0); }
 // re-derives the headings of both slots' records from the camera mounting; grows the selected arena (reloc_db.hip)
 int db_reindex(reloc_ctx *ctx);
 int db_reserve(reloc_ctx *ctx, int64_t cap_records, int64_t cap_rows);

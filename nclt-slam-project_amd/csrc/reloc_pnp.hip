@@ -943,7 +943,7 @@ static PnpFrame pnp_frame(const reloc_ctx *c, uint64_t seed)
 {
     PnpFrame F;
     const TickState &t = c->tick;
-    F.obj = t.p_obj; F.img = t.p_img; F.m_arr = t.m_n; F.n_cand_p = t.cand_n; F.Rt = t.p_Rt; F.cnt = t.p_cnt; F.inl = t.p_inl;
+    F.obj = t.p_obj; F.img = t.p_img; F.m_arr = tick_pnp_lengths(c); F.n_cand_p = t.cand_n; F.Rt = t.p_Rt; F.cnt = t.p_cnt; F.inl = t.p_inl;
     F.out = t.p_out; F.seed = seed; F.relocating = t.flags;
     return F;
 }
@@ -1061,6 +1061,7 @@ static int pnp_ransac_impl(reloc_ctx *ctx, const float *obj, const float *img, i
     PnpBatch b;
     b.f[0] = pnp_frame(ctx, seed);
     b.f[0].n_cand_p = nullptr; b.f[0].relocating = nullptr;       // one candidate of m pairs, no relocation flag
+    b.f[0].m_arr = ctx->tick.m_n;                                 // ... its length uploaded above, whatever the match policy
     st.run([&] { return pnp_launch(&ctx, 1, b, 1, make_params(K4, iters, thr_px, conf, seed, MAX_REC_ROWS, RELOC_PNP_SAMPLE), dist, true); });
     PnpOut po = {};
     st.download(&po, ctx->tick.p_out, sizeof(po));

@@ -8,6 +8,8 @@
 //   first 5;  global: mutual-match count of every heading-compatible record, top 25) ->
 //   mutual matches of each candidate (reloc_match.hip, emit mode) -> gather 3-D/2-D pairs ->
 //   PnP-RANSAC batch (reloc_pnp.hip) -> gates, pose composition, best by inliers, consistency.
+// "Mutual" is the default match policy; under RELOC_MATCH_RATIO (reloc_set_match_policy, include/reloc_spec.h "MATCH POLICY")
+// the count and the lists are those of knnMatch(current, record, k=2) + Lowe test: scan_counts() and launch_tick_emit() branch.
 #include <time.h>
 
 #include "reloc_internal.h"
@@ -605,7 +607,7 @@ int tick_alloc(reloc_ctx *ctx)
     rc |= ctx_dev_alloc(ctx, &t.cand_n, 1);
     rc |= ctx_dev_alloc(ctx, &t.flags, 4);
     for (int32_t **p : {&t.m_qidx, &t.m_tidx, &t.m_dist, &t.p_inl}) rc |= ctx_dev_alloc(ctx, p, rows);
-    rc |= ctx_dev_alloc(ctx, &t.m_n, MAX_CAND);
+    rc |= ctx_dev_alloc(ctx, &t.m_n, 2 * MAX_CAND);        // list lengths, and the lengths PnP takes under RELOC_MATCH_RATIO
     rc |= ctx_dev_alloc(ctx, &t.p_obj, rows * 3);
     rc |= ctx_dev_alloc(ctx, &t.p_img, rows * 2);
     rc |= ctx_dev_alloc(ctx, &t.p_Rt, hyps * 12);
@@ -675,8 +677,8 @@ static void launch_topk_counts(reloc_ctx *const *ctxs, int n, const TopkBatch &b
     reloc_ctx *c0 = ctxs[0];
     const DbArena &db = ctx_db(c0);
     const int L = (int)db.records;
-    // a count cannot exceed the rows of the largest record nor the features of a frame
-    const int max_count = db.max_rows < c0->max_feat ? db.max_rows : c0->max_feat;
+    // a count cannot exceed the features of a frame nor, a count of mutual pairs, the rows of the largest record
+    const int max_count = !c0->match.ratio_on() && db.max_rows < c0->max_feat ? db.max_rows : c0->max_feat;
     const size_t lds = (size_t)(max_count + 2) * sizeof(int);
     if (n == 1) {
         const TopkFrame &F = b.f[0];
@@ -712,7 +714,9 @@ static int scan_counts(reloc_ctx *const *ctxs, int n, const double *base_poses, 
     const double cos_tol = heading_cos_tol_host(c0);
     int rc;
     reloc_prof_begin(c0, RELOC_PROF_DB_SCAN);
-    if (n == 1) {
+    if (c0->match.ratio_on()) {
+        rc = launch_db_ratio_scan(ctxs, n, base_poses, cos_tol, auto_mode);
+    } else if (n == 1) {
         ScanMask mask;
         if (base_poses) {
             mask.xyh = ctx_db(c0).xy_heading;
@@ -766,6 +770,25 @@ RELOC_API int reloc_get_distortion(reloc_ctx *ctx, double coeffs[5])
     return RELOC_OK;
 }
 
+RELOC_API int reloc_set_match_policy(reloc_ctx *ctx, int policy, double ratio)
+{
+    ARG_CHECK_CTX(ctx, true, "ctx is NULL");
+    ARG_CHECK(policy == RELOC_MATCH_CROSS || policy == RELOC_MATCH_RATIO,
+              "reloc_set_match_policy: policy must be RELOC_MATCH_CROSS (0) or RELOC_MATCH_RATIO (1)");
+    ARG_CHECK(ratio - ratio == 0.0 && ratio > 0.0 && ratio <= 1.0, "reloc_set_match_policy: ratio must be finite and in (0, 1]");
+    ctx->match.policy = policy;
+    ctx->match.ratio = ratio;
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_get_match_policy(reloc_ctx *ctx, int32_t *policy, double *ratio)
+{
+    ARG_CHECK_CTX(ctx, policy && ratio, "reloc_get_match_policy");
+    *policy = ctx->match.policy;
+    *ratio = ctx->match.ratio;
+    return RELOC_OK;
+}
+
 // ---- one host driver per tick half; a single-context call is a call of n = 1 ---------------------------------------------
 // The contexts of one call (<= RELOC_BATCH_MAX) share ONE stream, so their frames share every launch: ORB 5, local
 // candidates n (LOCAL / AUTO only), scan 1, ranking 1, emit 1, PnP 3, finalisation 1 -- 12 launches for 8 frames in
@@ -790,14 +813,21 @@ static int ctx_batch_check(reloc_ctx *const *ctxs, int n, const char *who)
         if (!c) { reloc_set_error("bad argument: %s: NULL context", who); return RELOC_E_ARG; }
         if (!db_ready(c)) { reloc_set_error("no database uploaded"); return RELOC_E_STATE; }
         if (c->stream != c0->stream || c->device != c0->device || ctx_db(c).desc != ctx_db(c0).desc || ctx_db(c).records != ctx_db(c0).records ||
-            c->max_feat != c0->max_feat || memcmp(&c->prm, &c0->prm, sizeof(reloc_params)) != 0 || !c->cam.same(c0->cam)) {
+            c->max_feat != c0->max_feat || memcmp(&c->prm, &c0->prm, sizeof(reloc_params)) != 0 || !c->cam.same(c0->cam) ||
+            !c->match.same(c0->match)) {
             reloc_set_error("%s: the contexts must share one stream (reloc_set_stream), one device and one database "
                             "(reloc_db_share) and have equal feature capacity, matcher parameters (reloc_set_params), camera "
-                            "(reloc_set_camera) and lens distortion (reloc_set_distortion)", who);
+                            "(reloc_set_camera), lens distortion (reloc_set_distortion) and match policy (reloc_set_match_policy)", who);
             return RELOC_E_STATE;
         }
         for (int g = 0; g < f; ++g)
             if (ctxs[g] == c) { reloc_set_error("bad argument: %s: a context appears twice", who); return RELOC_E_ARG; }
+    }
+    // a ratio list holds up to max_feat entries and the lists of a tick lie MAX_REC_ROWS apart: refused before any launch
+    if (c0->match.ratio_on() && c0->max_feat > MAX_REC_ROWS) {
+        reloc_set_error("%s: under RELOC_MATCH_RATIO a match list holds up to max_feat = %d entries, more than the list stride of %d "
+                        "(create the context with max_feat <= %d)", who, c0->max_feat, MAX_REC_ROWS, MAX_REC_ROWS);
+        return RELOC_E_CAPACITY;
     }
     (void)hipSetDevice(c0->device);
     return RELOC_OK;
@@ -1095,8 +1125,9 @@ RELOC_API int reloc_tick_debug(reloc_ctx *ctx, int32_t *cand_ids, int32_t *n_can
     return RELOC_OK;
 }
 
-// read back what the emit pass of the last solve left for candidate slot `slot`: its mutual match list and the 3-D / 2-D
-// pairs PnP was given (parity tap for tests; copies only, nothing is launched)
+// read back what the emit pass of the last solve left for candidate slot `slot`: its match list, in the orientation of the
+// match policy in force (crossCheck: queryIdx = teach row; ratio: queryIdx = current feature), and the 3-D / 2-D pairs PnP was
+// given (parity tap for tests; copies only, nothing is launched)
 RELOC_API int reloc_tick_debug_matches(reloc_ctx *ctx, int slot, int32_t *n, int32_t *qidx, int32_t *tidx, int32_t *dist,
                                        float *obj, float *img)
 {

@@ -362,7 +362,13 @@ class _BFMatcher:
             raise error("BFMatcher: descriptors must be (N, 32) uint8 (ORB)")
         return q, t
 
+    @staticmethod
+    def _no_mask(mask, who):
+        if mask is not None:
+            raise error(f"BFMatcher.{who}: a match mask is not implemented (it would be ignored)")
+
     def match(self, queryDescriptors, trainDescriptors, mask=None):
+        self._no_mask(mask, "match")
         q, t = self._check(queryDescriptors, trainDescriptors)
         try:
             if self._cross:
@@ -374,6 +380,7 @@ class _BFMatcher:
             raise error(str(e)) from e
 
     def knnMatch(self, queryDescriptors, trainDescriptors, k=2, mask=None):
+        self._no_mask(mask, "knnMatch")
         if self._cross and k != 1:
             raise error("BFMatcher: crossCheck=True requires k == 1")
         if k not in (1, 2):

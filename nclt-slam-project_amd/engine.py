@@ -18,6 +18,27 @@ K4_DEFAULT = np.array([320.0, 320.0, 320.0, 240.0], dtype=np.float64)  # fx fy c
 OUTCOME_NAMES = {0: "published", 1: "curr_no_features", 2: "no_candidates", 3: "no_pnp_accept",
                  4: "consistency_fail"}
 
+# match policies of the tick (RELOC_MATCH_* of include/reloc.h; the rule: include/reloc_spec.h, "MATCH POLICY")
+MATCH_POLICIES = {"cross": 0, "ratio": 1}
+MATCH_POLICY_RULE = "policy must be RELOC_MATCH_CROSS (0) or RELOC_MATCH_RATIO (1)"
+MATCH_RATIO_RULE = "ratio must be finite and in (0, 1]"
+
+
+def match_policy_setting(policy, ratio):
+    """(policy, ratio) as the checked (name, float): the one place the Python layer checks them, with the messages of
+    reloc_set_match_policy"""
+    name = policy.lower() if isinstance(policy, str) else {v: k for k, v in MATCH_POLICIES.items()}.get(policy)
+    if name not in MATCH_POLICIES:
+        raise ValueError(f'match_policy {policy!r}: {MATCH_POLICY_RULE}, "cross" or "ratio"')
+    try:
+        r = float(ratio)
+    except (TypeError, ValueError):
+        r = float("nan")
+    if not (np.isfinite(r) and 0.0 < r <= 1.0):
+        raise ValueError(f"lowe_ratio {ratio!r}: {MATCH_RATIO_RULE}")
+    return name, r
+
+
 MAX_CAND = 32           # candidates of one tick (MAX_CAND of csrc/reloc_internal.h): the longest top-k / candidate list
 
 # The 96-byte result record of a tick (include/reloc.h at reloc_tick_result_dev / reloc_tick_result_to; struct TickResult
@@ -578,6 +599,17 @@ class Engine:
                 "reloc_match_knn2")
         return idx, dist
 
+    def match_ratio(self, q, t, ratio: float = 0.8):
+        """knnMatch(q, t, k=2) + Lowe test (include/reloc_spec.h, MATCH POLICY): (queryIdx, trainIdx, distance) of the queries
+        whose nearest row of t passes d1 < ratio * d2, in queryIdx order"""
+        q = self._desc(q, "match_ratio"); t = self._desc(t, "match_ratio")
+        cap = max(len(q), 1)
+        qi = np.empty(cap, np.int32); ti = np.empty(cap, np.int32); dd = np.empty(cap, np.int32)
+        n = C.c_int32()
+        N.check(self._lib.reloc_match_ratio(self._ctx, N.ptr(q), len(q), N.ptr(t), len(t), float(ratio), N.ptr(qi), N.ptr(ti),
+                                            N.ptr(dd), C.byref(n)), "reloc_match_ratio")
+        return qi[: n.value].copy(), ti[: n.value].copy(), dd[: n.value].copy()
+
     def db_upload(self, desc, pts3d, offsets, poses):
         desc = self._desc(desc, "db_upload") if len(desc) else np.zeros((0, 32), np.uint8)
         pts3d = np.ascontiguousarray(pts3d, np.float32).reshape(-1, 3)
@@ -741,13 +773,33 @@ class Engine:
         return p
 
     def set_params_from(self, other: "Engine"):
-        """copy another engine's matcher and ORB parameters (the contexts of a batch must carry equal ones)"""
+        """copy another engine's matcher and ORB parameters and its match policy (the contexts of a batch must carry equal ones)"""
         p = other.get_params()
         N.check(self._lib.reloc_set_params(self._ctx, C.byref(p)), "reloc_set_params")
         self.set_orb_params(*other.get_orb_params())
+        self.set_match_policy(*other.match_policy)
+
+    def set_match_policy(self, policy="cross", ratio: float = 0.8):
+        """match policy of the fused tick (reloc_set_match_policy): "cross" = mutual nearest neighbours (the default), "ratio" =
+        knnMatch(current, record, k=2) + Lowe test with `ratio` in (0, 1]; also RELOC_MATCH_CROSS / RELOC_MATCH_RATIO.  Under
+        "ratio" the ticks need a context of max_feat <= 4096."""
+        code = MATCH_POLICIES.get(policy.lower(), -1) if isinstance(policy, str) else int(policy)
+        N.check(self._lib.reloc_set_match_policy(self._ctx, code, float(ratio)), "reloc_set_match_policy")
+
+    @property
+    def match_policy(self):
+        """(policy name, ratio) as the context holds them"""
+        code = C.c_int32(); ratio = C.c_double()
+        N.check(self._lib.reloc_get_match_policy(self._ctx, C.byref(code), C.byref(ratio)), "reloc_get_match_policy")
+        return {v: k for k, v in MATCH_POLICIES.items()}[code.value], ratio.value
 
     def set_params(self, **kw):
-        """matcher parameters of the fused tick (reloc_params in include/reloc.h); unnamed fields keep their value"""
+        """matcher parameters of the fused tick (reloc_params in include/reloc.h); unnamed fields keep their value.
+        match_policy / lowe_ratio: the match policy, which the context keeps beside them (set_match_policy)"""
+        policy, ratio = kw.pop("match_policy", None), kw.pop("lowe_ratio", None)
+        if policy is not None or ratio is not None:
+            now = self.match_policy
+            self.set_match_policy(now[0] if policy is None else policy, now[1] if ratio is None else ratio)
         p = self.get_params()
         for k, v in kw.items():
             if not hasattr(p, k):

@@ -21,6 +21,7 @@ from dataclasses import dataclass, field, fields
 import numpy as np
 
 from . import pose as P
+from .engine import match_policy_setting
 from .front_end import FrontEnd, ImageChain, frame_shape_ok, scaled_camera  # noqa: F401  (scaled_camera: INTEGRATION.md names it here)
 from .landmarks import load_landmarks, pack_landmarks, save_landmarks
 
@@ -55,6 +56,11 @@ class MatcherConfig:
     gray_coeff_bits: int = 15      # cvtColor fixed point: 15 = OpenCV 4.x (what M:305 computes on OpenCV >= 4.8), 14 = OpenCV <= 3.x / SURVEY.md A.1
                                    # (include/reloc_spec.h); fused path only --
                                    # the cv2-shaped path takes it from its backend (Engine.set_params)
+    # how a record is paired with the frame (include/reloc_spec.h, MATCH POLICY): "cross" = BFMatcher(crossCheck=True).match(
+    # desc_t, desc_curr), the reference matcher's; "ratio" = knnMatch(desc_curr, desc_t, k=2) + Lowe test with lowe_ratio
+    # (the reference's self-test harness, S:68-77); lowe_ratio is ignored under "cross"
+    match_policy: str = "cross"
+    lowe_ratio: float = 0.8
     # global relocalisation (variant G)
     global_reloc: bool = False
     reloc_age_s: float = 20.0
@@ -71,6 +77,11 @@ class MatcherConfig:
     @property
     def front_end(self) -> FrontEnd:
         return FrontEnd(**{f.name: getattr(self, f.name) for f in fields(FrontEnd)})
+
+    @property
+    def match(self):
+        """(match_policy, lowe_ratio), checked"""
+        return match_policy_setting(self.match_policy, self.lowe_ratio)
 
     @property
     def K(self):
@@ -106,6 +117,7 @@ class _MatcherSession:
 
     def __init__(self, landmarks, config, return_landmarks, swap_flag, logger):
         self.cfg = config or MatcherConfig()
+        self.match_policy, self.lowe_ratio = self.cfg.match
         self.log = logger or (lambda msg: None)
         self.pkl_path = landmarks if isinstance(landmarks, str) else None
         self._return_src = return_landmarks
@@ -156,6 +168,21 @@ class _MatcherSession:
             return out
         return None
 
+    # ------------------------------------------------------------------ matching
+    def _pairs(self, desc_t, desc_curr):
+        """(teach rows, current columns) of the matches of one record with the frame under the configured policy, through
+        self.matcher (a cv2-shaped BFMatcher); the 3-D / 2-D pairs are keypoints_3d_cam[teach rows], pts_curr_2d[current columns].
+        "cross": match(desc_t, desc_curr), queryIdx = teach (M:327).  "ratio": knnMatch(desc_curr, desc_t, k=2) and the Lowe
+        test, queryIdx = current (S:68-77)."""
+        if self.match_policy == "cross":
+            good = self.matcher.match(desc_t, desc_curr)
+            rows, cols = (m.queryIdx for m in good), (m.trainIdx for m in good)
+        else:
+            knn = self.matcher.knnMatch(desc_curr, desc_t, k=2)
+            good = [p[0] for p in knn if len(p) == 2 and p[0].distance < self.lowe_ratio * p[1].distance]
+            rows, cols = (m.trainIdx for m in good), (m.queryIdx for m in good)
+        return np.fromiter(rows, dtype=np.int64, count=len(good)), np.fromiter(cols, dtype=np.int64, count=len(good))
+
     # ------------------------------------------------------------------ one attempt's outcome
     def _outcome(self, ts, vio_xy, code, n_candidates, n_inliers=0, reproj_err=None, anchor=None, lm_idx=None, relocating=False):
         """The TickOutcome of an attempt, counted and logged as one CSV row.  code is the tick record's: 0 published, 1
@@ -202,7 +229,7 @@ class LandmarkMatcherCore(_MatcherSession):
         self._adopt(self._load(landmarks))
         self.chain = c = ImageChain(cv2, self.cfg.front_end, self.cfg.nfeatures)
         self.orb, self.dist, self.rectify = c.orb, c.dist, c.rectify
-        self.matcher = cv2.BFMatcher(cv2.NORM_HAMMING, crossCheck=True)
+        self.matcher = cv2.BFMatcher(cv2.NORM_HAMMING, crossCheck=self.match_policy == "cross")
         self._open_csv(log_csv)
 
     # ------------------------------------------------------------------ database
@@ -235,7 +262,7 @@ class LandmarkMatcherCore(_MatcherSession):
         return cand[: cfg.max_candidates], d, herr
 
     def global_candidates(self, desc_curr, herr):
-        """Variant G: mutual-match count of every heading-compatible record, top-N (G:329-344)."""
+        """Variant G: match count (the policy's list length) of every heading-compatible record, top-N (G:329-344)."""
         cfg = self.cfg
         scored = []
         for li in np.where(herr < math.radians(cfg.heading_tol_deg))[0]:
@@ -243,7 +270,7 @@ class LandmarkMatcherCore(_MatcherSession):
             if desc_t is None or len(desc_t) < cfg.min_matches:
                 continue
             try:
-                n = len(self.matcher.match(desc_t, desc_curr))
+                n = len(self._pairs(desc_t, desc_curr)[0])
             except self.cv2.error:
                 continue
             if n >= cfg.min_matches:
@@ -260,15 +287,13 @@ class LandmarkMatcherCore(_MatcherSession):
         if desc_t is None or len(desc_t) < cfg.min_matches:
             return None
         try:
-            good = self.matcher.match(desc_t, desc_curr)        # queryIdx = teach, trainIdx = current
+            rows, cols = self._pairs(desc_t, desc_curr)
         except cv2.error:
             return None
-        if len(good) < cfg.min_matches:
+        if len(rows) < cfg.min_matches:
             return None
-        qi = np.fromiter((m.queryIdx for m in good), dtype=np.int64, count=len(good))
-        ti = np.fromiter((m.trainIdx for m in good), dtype=np.int64, count=len(good))
-        obj_pts = np.asarray(lm["keypoints_3d_cam"], dtype=np.float32)[qi]
-        img_pts = np.asarray(pts_curr_2d, dtype=np.float32)[ti]
+        obj_pts = np.asarray(lm["keypoints_3d_cam"], dtype=np.float32)[rows]
+        img_pts = np.asarray(pts_curr_2d, dtype=np.float32)[cols]
         ok, rvec, tvec, inliers = cv2.solvePnPRansac(
             obj_pts, img_pts, cfg.K, self.dist, iterationsCount=cfg.ransac_iterations,
             reprojectionError=cfg.ransac_reproj_px, flags=cv2.SOLVEPNP_ITERATIVE)
@@ -378,7 +403,9 @@ class FusedLandmarkMatcher(_MatcherSession):
         from .engine import Engine
         super().__init__(landmarks, config, return_landmarks, swap_flag, logger)
         cfg = self.cfg
-        self.engine = e = engine or Engine()
+        # a ratio list holds up to max_feat entries, which must fit the tick's list stride (4096): a matcher that makes its own
+        # engine under "ratio" makes one of that capacity
+        self.engine = e = engine or (Engine(max_feat=4096) if self.match_policy == "ratio" else Engine())
         if exclusive:
             e.set_exclusive(True)
         data = self._load(landmarks)
@@ -389,7 +416,7 @@ class FusedLandmarkMatcher(_MatcherSession):
                      heading_tol_deg=cfg.heading_tol_deg, reproj_max_px=cfg.reproj_max_px,
                      ransac_reproj_px=cfg.ransac_reproj_px, consistency_m=cfg.consistency_m,
                      global_reproj_max_px=cfg.reloc_reproj_max_px, accum_min_dist_m=cfg.accum_min_dist_m,
-                     gray_coeff_bits=cfg.gray_coeff_bits)
+                     gray_coeff_bits=cfg.gray_coeff_bits, match_policy=self.match_policy, lowe_ratio=self.lowe_ratio)
         e.set_camera([cfg.fx, cfg.fy, cfg.cx, cfg.cy], data.get("base_to_cam_translation", P.BASE_TO_CAM_TRANSLATION),
                      data.get("base_to_cam_rot", P.BASE_TO_CAM_ROT))
         cfg.front_end.configure(e)

@@ -1,6 +1,7 @@
 """rclpy wrappers with the reference's node names, constructor signatures, topics and CLI flags:
 
     VisualLandmarkMatcher(pkl_path, log_csv)            --landmarks --out-csv [--landmarks-return --swap-flag]
+                                                        [--match-policy {cross,ratio} --lowe-ratio R]
     VisualLandmarkRecorder(out_pkl, min_disp_m=2.0)     --out --min-disp
 
 (reference simulation/isaac/scripts/common/visual_landmark_matcher.py:175-231,503-530,
@@ -94,11 +95,12 @@ def _node_base():
 
 
 def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global_reloc=False, fused=False, cv2=None, bayer=None,
-                      mask=None, orb=None, pixel_format=None):
+                      mask=None, orb=None, pixel_format=None, match_policy="cross", lowe_ratio=0.8):
     """cv2: the cv2-shaped module the ROS-free core calls (default: the HIP shim); only the non-fused core uses it.
     bayer: FrontEnd.bayer -- the colour topic carries raw mosaics, passed through undecoded.  mask: FrontEnd.mask.
     orb: FrontEnd.orb.  pixel_format: FrontEnd.pixel_format -- the colour topic carries frames of that format, passed through
-    undecoded"""
+    undecoded.  match_policy, lowe_ratio: MatcherConfig's -- "cross" (the reference matcher's crossCheck) or "ratio" (knnMatch
+    + Lowe test)"""
     from geometry_msgs.msg import PoseWithCovarianceStamped
     from sensor_msgs.msg import Image
     Node = _node_base()
@@ -106,7 +108,8 @@ def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global
     class VisualLandmarkMatcher(Node):
         def __init__(self):
             super().__init__("visual_landmark_matcher")
-            cfg = MatcherConfig(global_reloc=global_reloc, bayer=bayer, mask=mask, orb=orb, pixel_format=pixel_format)
+            cfg = MatcherConfig(global_reloc=global_reloc, bayer=bayer, mask=mask, orb=orb, pixel_format=pixel_format,
+                                match_policy=match_policy, lowe_ratio=lowe_ratio)
             if fused:
                 self.core = FusedLandmarkMatcher(pkl_path, log_csv, config=cfg, return_landmarks=return_pkl,
                                                  swap_flag=swap_flag, logger=lambda m: self.get_logger().info(m),
@@ -209,6 +212,15 @@ def _chain_args(args):
     return tuple(tail)
 
 
+def _match_args(args, raw):
+    """the (match_policy, lowe_ratio) of make_matcher_node behind its chain arguments `raw`, those padded to their full
+    length; nothing when both are defaults"""
+    policy, ratio = MatcherConfig(match_policy=args.match_policy, lowe_ratio=args.lowe_ratio).match
+    if (policy, ratio) == ("cross", 0.8):
+        return raw
+    return (*raw, *([None] * (5 - len(raw))), policy, ratio)
+
+
 def _spin(make_node, save):
     """one node's rclpy session: spin until interrupted, then call the core's `save` method and shut down"""
     import rclpy
@@ -235,9 +247,15 @@ def matcher_main(argv=None):
     ap.add_argument("--swap-flag", default="/tmp/matcher_swap_return.txt")
     ap.add_argument("--global-reloc", action="store_true")
     ap.add_argument("--fused", action="store_true", help="run the whole tick in one device call")
+    ap.add_argument("--match-policy", choices=("cross", "ratio"), default="cross",
+                    help="cross: mutual nearest neighbours (the reference matcher); ratio: knnMatch k=2 + Lowe test")
+    ap.add_argument("--lowe-ratio", type=float, default=0.8, help="ratio of the Lowe test, in (0, 1]; read under --match-policy ratio")
     add_front_end_flags(ap)
     args = ap.parse_args(argv)
-    raw = _chain_args(args)
+    try:
+        raw = _match_args(args, _chain_args(args))
+    except ValueError as e:
+        ap.error(str(e))
     _spin(lambda: make_matcher_node(args.landmarks, args.out_csv, args.landmarks_return, args.swap_flag, args.global_reloc, args.fused, *raw),
           "save_augmented")
 

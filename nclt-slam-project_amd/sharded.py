@@ -122,12 +122,18 @@ class HipShard:
     """One rank's shard on its GPU.  `frame` is a device pointer to a (H, W, 3) uint8 BGR image.  n_slots > 1 keeps
     that many contexts (each with the shard uploaded and its own stream) so the frames of a batch overlap."""
 
-    def __init__(self, engine, desc, pts3d, offsets, poses, rank: int, world: int, w=640, h=480, n_slots: int = 1, orb=None):
+    def __init__(self, engine, desc, pts3d, offsets, poses, rank: int, world: int, w=640, h=480, n_slots: int = 1, orb=None,
+                 match_policy=None, lowe_ratio=0.8):
         """orb: None = the engine's ORB parameters as they are, or FrontEnd.orb: set on the engine; every slot (and every
-        context a pipeline makes with new_slot) carries the engine's, as the contexts of a batch must"""
+        context a pipeline makes with new_slot) carries the engine's, as the contexts of a batch must.  match_policy: None =
+        the engine's match policy as it is, or MatcherConfig.match_policy with lowe_ratio: set on the engine and carried by
+        every slot in the same way (the scan half then counts, and the merge ranks, the policy's list lengths)"""
+        from .engine import match_policy_setting
         from .front_end import ORB_DEFAULTS, orb_setting
         if orb is not None:
             engine.set_orb_params(*(orb_setting(orb) or ORB_DEFAULTS))
+        if match_policy is not None:
+            engine.set_match_policy(*match_policy_setting(match_policy, lowe_ratio))
         bounds = shard_by_rows(offsets, world)
         a, b = int(bounds[rank]), int(bounds[rank + 1])
         self.engine, self.base, self.n_records, self.w, self.h = engine, a, b - a, w, h
@@ -139,7 +145,7 @@ class HipShard:
 
     def new_slot(self, stream: int | None = None):
         """a sibling context of the shard's engine: same device and capacities, the shard's records (reloc_db_share), the
-        engine's matcher and ORB parameters, its own stream or `stream`.  Camera, distortion and the FrontEnd stages are
+        engine's matcher and ORB parameters and match policy, its own stream or `stream`.  Camera, distortion and the FrontEnd stages are
         not copied.  The caller closes it."""
         e0 = self.engine
         e = Engine(e0.device, e0.max_w, e0.max_h, e0.max_feat)
