@@ -504,6 +504,13 @@ int reloc_tick_debug(reloc_ctx *ctx, int32_t *cand_ids, int32_t *n_cand, int32_t
  * is given no PnP (reloc_tick_debug reports n_matches 0 for it). */
 int reloc_tick_debug_matches(reloc_ctx *ctx, int slot, int32_t *n, int32_t *qidx, int32_t *tidx, int32_t *dist,
                              float *obj, float *img);
+/* Parity tap (tests only): the device address of THIS context's per-record counts array of its selected database --
+ * reloc_db_records entries of int32, the array the whole-database scans of this context's frames write (a single scan, its
+ * frame of a batched launch) and their ranking reads.  Every holder of a database has its own: an adopter made by
+ * reloc_db_share shares the records and counts into an array of its own.  NULL for a NULL context or while no database is
+ * ready.  Launches nothing and copies nothing; valid until the database is uploaded, reserved, appended to, shared or
+ * selected again. */
+int32_t *reloc_db_counts_dev(reloc_ctx *ctx);
 /* Sharded database (one rank per GPU): per-record mutual-match counts are local; the caller
  * exchanges the per-shard top-k (count, global id) lists and tells each rank which of ITS
  * records made the global top-k.  These two calls split reloc_tick_dev at that exchange. */
@@ -518,7 +525,7 @@ int reloc_tick_solve_dev(reloc_ctx *ctx, const int32_t *cand_ids_dev, int n_cand
  * below) can be enqueued on that same stream between them and the host never waits inside a batch.
  *   scan half:  ORB per frame, ONE scan launch for the n frames, per-frame ranking.  scan_out_dev: n rows of 2k + 2
  *               int32 = k GLOBAL record ids (id_base + local id, -1 padded), k mutual-match counts, the frame's feature
- *               count, 0.  base_poses: n x 7 (heading mask, G:329-330) or NULL.
+ *               count, one pad word the call never writes.  base_poses: n x 7 (heading mask, G:329-330) or NULL.
  *   merge:      what every rank computes from the gathered rows (all_scan_dev: `world` blocks `stride_rank` int32 apart,
  *               each n rows as above): per frame the k best (count desc, global id desc; G:342-343) -> win_gid (n x k,
  *               -1 padded), cand_local (n x k: local ids of the winners THIS rank owns, -1 elsewhere), n_feat (n: the

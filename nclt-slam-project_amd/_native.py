@@ -61,6 +61,7 @@ SIGNATURES = {
     "reloc_db_upload": (C.c_int, [c_ctx, P, P, P, P, i64]),
     "reloc_db_records": (i64, [c_ctx]),
     "reloc_db_rows": (i64, [c_ctx]),
+    "reloc_db_counts_dev": (P, [c_ctx]),
     "reloc_db_match_counts": (C.c_int, [c_ctx, P, C.c_int, P]),
     "reloc_db_match_counts_dev": (C.c_int, [c_ctx, P, P, C.c_int, P]),
     "reloc_hamming_matrix": (C.c_int, [c_ctx, P, i64, P, i64, P]),

@@ -288,3 +288,4 @@ RELOC_API int reloc_db_fetch(reloc_ctx *ctx, int64_t record, uint8_t *desc, floa
 
 RELOC_API int64_t reloc_db_records(reloc_ctx *ctx) { return ctx ? ctx_db(ctx).records : -1; }
 RELOC_API int64_t reloc_db_rows(reloc_ctx *ctx) { return ctx ? ctx_db(ctx).rows : -1; }
+RELOC_API int32_t *reloc_db_counts_dev(reloc_ctx *ctx) { return ctx && db_ready(ctx) ? ctx_db(ctx).counts : nullptr; }

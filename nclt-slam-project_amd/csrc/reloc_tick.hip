@@ -1038,7 +1038,7 @@ RELOC_API int reloc_shard_scan_batch_dev(reloc_ctx *const *ctxs, int n, const ui
     ARG_CHECK(imgs_dev && scan_out_dev && k > 0 && k <= MAX_CAND && w >= 64 && h >= 64 && id_base >= 0 &&
               id_base + ctx_db(ctxs[0]).records <= 0x7fffffff, "reloc_shard_scan_batch_dev");
     for (int f = 0; f < n; ++f) ARG_CHECK(imgs_dev[f], "reloc_shard_scan_batch_dev: NULL frame");
-    // frame f's list goes to row f of scan_out_dev: 2k + 2 int32 (k ids + id_base, k counts, feature count, 0)
+    // frame f's list goes to row f of scan_out_dev: 2k + 2 int32 (k ids + id_base, k counts, feature count, one pad word the call never writes)
     TopkBatch out;
     frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int g) {
         int32_t *row = scan_out_dev + (size_t)g * (2 * k + 2);

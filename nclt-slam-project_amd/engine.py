@@ -667,6 +667,11 @@ class Engine:
     def db_rows(self) -> int:
         return int(self._lib.reloc_db_rows(self._ctx))
 
+    def db_counts_dev(self) -> int:
+        """parity tap: device address of this engine's own per-record counts array (db_records int32), which the
+        whole-database scans of its frames write (reloc_db_counts_dev); 0 while no database is ready"""
+        return int(self._lib.reloc_db_counts_dev(self._ctx) or 0)
+
     def db_match_counts(self, cur):
         cur = self._desc(cur, "db_match_counts") if len(cur) else np.zeros((0, 32), np.uint8)
         counts = np.empty(self.db_records, np.int32)
@@ -890,7 +895,7 @@ class Engine:
     @staticmethod
     def shard_scan_batch_dev(engines, imgs_dev, w: int, h: int, base_poses, k: int, id_base: int, scan_out_dev: int, order_rgb=False):
         """ORB per frame + ONE scan launch + per-frame ranking for n <= 8 engines that share a stream and a shard; row f of
-        scan_out_dev (2k + 2 int32) = k global ids, k counts, feature count, 0.  Enqueue only."""
+        scan_out_dev (2k + 2 int32) = k global ids, k counts, feature count, one pad word (never written).  Enqueue only."""
         n = len(engines)
         ctxs = (C.c_void_p * n)(*[e._ctx for e in engines])
         imgs = (C.c_void_p * n)(*[int(p) for p in imgs_dev])

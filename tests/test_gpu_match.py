@@ -68,7 +68,11 @@ def test_knn2(engine, oracle, nq, nt):
 
 
 @pytest.mark.parametrize("L,nmode,Q", [(50, "fixed64", 500), (300, "ragged", 500), (40, "ragged", 37),
-                                       (20, "ragged", 1200), (1000, "fixed64", 500)])
+                                       (20, "ragged", 1200), (1000, "fixed64", 500),
+                                       # k_db_scan<2> / <4> on more than a handful of records; two bound column blocks
+                                       (300, "ragged", 100), (300, "ragged", 200), (300, "ragged", 700),
+                                       # few queries and a record above SQ_MAX_ROWS: the column kernel takes over from the rows kernel
+                                       (40, "ragged1100", 37)])
 def test_db_match_counts(engine, oracle, L, nmode, Q):
     rng = np.random.default_rng(L + Q)
     if nmode == "fixed64":
@@ -77,6 +81,8 @@ def test_db_match_counts(engine, oracle, L, nmode, Q):
         n = np.clip(np.rint(rng.normal(60, 25, L)), 30, 500).astype(int)
         n[0] = 0  # an empty record
         n[1] = 1
+        if nmode == "ragged1100":
+            n[L // 2] = 1100
     off = np.zeros(L + 1, np.int64); off[1:] = np.cumsum(n)
     cur = _desc(rng, Q)
     db = _desc(rng, int(off[-1]))
