@@ -456,7 +456,12 @@ int reloc_tick_result(reloc_ctx *ctx, double anchor_pose[7], int32_t *n_inl, flo
 int reloc_tick_wait(reloc_ctx *ctx);
 /* Device address of the 96-byte result record of the last tick (layout of reloc_tick_result_ex's outputs: double
  * anchor_pose[7], double reproj, int32 n_inl, lm_idx, outcome, n_candidates, n_features, relocating): lets a pipelined
- * host copy results with reloc_d2h into pinned memory without synchronising per frame. */
+ * host copy results with reloc_d2h into pinned memory without synchronising per frame.
+ * Every outcome writes all 96 bytes.  The three outcomes without a pose (NO_FEATURES, NO_CANDIDATES, NO_PNP_ACCEPT) leave
+ * anchor_pose all zero, reproj 0, n_inl 0 and lm_idx -1; CONSISTENCY_FAIL keeps anchor_pose, reproj, n_inl and lm_idx of the
+ * rejected anchor.  n_candidates (also under NO_FEATURES: the candidates were still found), n_features and relocating are
+ * reported by all five.  Word 22 is 0 in the device record (the sequence stamp goes to host records only), word 23 is 0
+ * (tests/test_gpu_finalize.py). */
 const void *reloc_tick_result_dev(reloc_ctx *ctx);
 /* Streaming without a copy: the ticks enqueued after this call ALSO write their 96-byte result record (same layout) to
  * `pinned_record`, memory from reloc_host_alloc() -- the last kernel of the tick stores it over PCIe itself, so the record
