@@ -107,7 +107,8 @@ int  reloc_timer_end(reloc_ctx *ctx, float *ms);
 #define RELOC_PROF_MATRIX   1
 #define RELOC_PROF_ORB      2
 #define RELOC_PROF_PNP      3
-#define RELOC_PROF_N        4
+#define RELOC_PROF_STEREO   4   /* k_stereo_depth (reloc_stereo_depth and the stereo recording / accumulation) */
+#define RELOC_PROF_N        5
 int  reloc_profile_enable(reloc_ctx *ctx, int on);
 int  reloc_profile_get(reloc_ctx *ctx, int which, float *total_ms, int32_t *launches);
 
@@ -417,6 +418,43 @@ int reloc_yuv422_bgr_u8(reloc_ctx *ctx, const uint8_t *src, int w, int h, int st
  * or reloc_bayer_u8.  Batched calls refuse contexts with unequal formats (RELOC_E_STATE). */
 int reloc_set_pixel_format(reloc_ctx *ctx, int fmt);
 int reloc_get_pixel_format(reloc_ctx *ctx, int32_t *fmt);
+
+/* ---- sparse stereo depth (include/reloc_spec.h, "STEREO") ----------------------------------------- */
+/* Depth at the ORB keypoints from the other eye of a rectified pair, for cameras without a depth sensor: an 11 x 11 SAD
+ * search along the row with edge, uniqueness and left-right gates, parabola sub-pixel step, depth = fx * baseline / disparity
+ * as uint16 millimetres (0 = no depth).  status per keypoint: 0 ok, 1 border, 2 range, 3 edge, 4 uniqueness, 5 left-right,
+ * 6 beyond 65535 mm.
+ * reloc_set_stereo keeps the setting on a context (the LEFT eye's); baseline_m == 0 switches it off (the default of a new
+ * context; no launch, allocation or event is then added to any entry point).  baseline_m finite and >= 0, min_disparity in
+ * 0..1024, num_disparities in 8..256, uniqueness in 0..50, lr_check 0 / 1, else RELOC_E_ARG.  The first enable allocates the
+ * context's stereo buffers.  reloc_get_stereo returns baseline_m 0 when off. */
+int reloc_set_stereo(reloc_ctx *ctx, double baseline_m, int min_disparity, int num_disparities, int uniqueness, int lr_check);
+int reloc_get_stereo(reloc_ctx *ctx, double *baseline_m, int32_t *min_disparity, int32_t *num_disparities, int32_t *uniqueness,
+                     int32_t *lr_check);
+/* Stateless probe with explicit parameters (like reloc_clahe_u8): two gray planes of w x h (w, h >= 11, within the capacity),
+ * rows stride bytes apart, n >= 0 keypoints xy (n x 2 f32), fx > 0, baseline_m > 0.
+ * depth_mm, disparity, status hold n entries.  Host pointers; synchronous.  Independent of reloc_set_stereo. */
+int reloc_stereo_depth(reloc_ctx *ctx, const uint8_t *left, const uint8_t *right, int w, int h, int stride,
+                       const float *xy, int n, double fx, double baseline_m, int min_disparity, int num_disparities,
+                       int uniqueness, int lr_check, uint16_t *depth_mm, float *disparity, uint8_t *status);
+/* reloc_record_frame with the right eye's frame in the depth image's place.  The right eye is a context of its own that
+ * carries that eye's image chain (pixel format or Bayer code, resize, its own rectification map, CLAHE): its frame runs
+ * through the gray half of the chain only, never ORB, on its own stream, ordered against ctx's stream by events.  right must
+ * agree with ctx in everything a batched call compares of the chain (and in capacity, device and gray_coeff_bits), else
+ * RELOC_E_STATE.  The left plane is level 0 of ctx's pyramid (the chain's output), fx is the context camera's.  The gates
+ * of reloc_record_frame apply to the per-keypoint depth except the 3 x 3 variance gate (reloc_spec.h).  *n_stereo = keypoints
+ * with status 0.  RELOC_E_STATE while stereo is off on ctx. */
+int reloc_record_frame_stereo(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img, const uint8_t *img_right, int w, int h,
+                              int order, int nfeatures, float *xy, uint8_t *desc, float *pts3d, int32_t *kp_index,
+                              int32_t *n_out, int32_t *n_kp, int32_t *n_stereo);
+/* reloc_tick_accumulate_dev with the right eye's frame (device pointer, a frame of right's chain, dense rows) in the depth
+ * image's place; right as above.  The frame is ordered on ctx's stream, like the depth image of reloc_tick_accumulate_dev (copy
+ * it with reloc_h2d on ctx).  Enqueues only: the two streams are ordered by events in both directions, the host never waits. */
+int reloc_tick_accumulate_stereo_dev(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img_right_dev, int w, int h, int order,
+                                     const double base_pose[7], int silence_ok);
+/* Parity tap: the last stereo pass of the context, per keypoint of the frame's ORB output (*n of them; arrays of max_feat
+ * entries, any may be NULL).  Synchronises the context's stream. */
+int reloc_stereo_debug(reloc_ctx *ctx, uint16_t *depth_mm, float *disparity, uint8_t *status, int32_t *n);
 
 /* ---- fused tick ----------------------------------------------------------------------------- */
 #define RELOC_TICK_LOCAL   0   /* candidates by VIO distance / heading only                          M:293-302 */

@@ -318,4 +318,45 @@
  *              no PnP (S:64), a list shorter than min_matches neither (S:72); inliers, reprojection, consistency as before. */
 #define RELOC_LOWE_RATIO           0.80         /* LOWE_RATIO, visual_landmark_matcher.py:66 ("kept for docs"), S:71 */
 
+/* STEREO: depth at the ORB keypoints from the other eye of a rectified pair.  The matcher is this project's own (nothing here
+ * is OpenCV's), stated in integers so that tests/stereo_ref.py restates it bit for bit.
+ *   inputs     two 8-bit gray planes L, R of the working-frame size w x h, rectified so that a scene point lies on the same row
+ *              in both at x_R = x_L - d, d >= 0; keypoints (x, y) in float32 level-0 coordinates; fx in pixels of the working
+ *              frame; baseline_m > 0; min_disparity in 0..1024; num_disparities in 8..256; uniqueness in 0..50; lr_check 0/1.
+ *              The window is fixed: R = RELOC_STEREO_R, a (2R + 1) x (2R + 1) patch.
+ *   per keypoint, in this order; the first failing step sets status, leaves depth_mm = 0 and disparity = 0 and ends it:
+ *   1 border   u = rint(x), v = rint(y), half to even in float32 (np.round, k_record).  status 1 unless R <= u < w - R and
+ *              R <= v < h - R.
+ *   2 range    D = { d : min_disparity <= d < min_disparity + num_disparities, u - d - R >= 0 }.  status 2 when |D| < 3.
+ *   3 cost     C(d) = sum over j, i in -R..R of |L[v + j, u + i] - R[v + j, u - d + i]|, int32.
+ *   4 edge     d* = argmin C, lowest d on ties.  status 3 when d* is the smallest or the largest member of D.
+ *   5 unique   C2 = min C(d) over d in D with |d - d*| >= 2.  status 4 when such a d exists and
+ *              C2 * (100 - uniqueness) <= C(d*) * 100.  A flat patch (all costs equal) fails at 4 or here and never passes.
+ *   6 LR       if lr_check: xr = u - d*; D' = { d' : min_disparity <= d' < min_disparity + num_disparities, xr + d' + R < w };
+ *              C'(d') = sum |R[v + j, xr + i] - L[v + j, xr + d' + i]|; d'* = argmin C', lowest on ties.  status 5 when
+ *              |d'* - d*| > 1.
+ *   7 subpixel a = C(d* - 1), b = C(d*), c = C(d* + 1), den = a + c - 2b in integers.  delta = 0 when den <= 0, else
+ *              (float)(a - c) / (float)(2 * den): one float32 division of exactly representable integers.
+ *              disparity = (float)d* + delta, one float32 addition.
+ *   8 depth    z = fx * baseline_m / (double)disparity in float64, mm = rint(z * 1000.0).  status 6 when mm > 65535, else
+ *              depth_mm = (uint16)mm and status 0.
+ * The result is what a depth camera would have delivered at that pixel: uint16 millimetres, 0 = no depth.  From there the
+ * recorder's and the accumulation's arithmetic applies unchanged ((float)mm / 1000.0f, range gates, back-projection, lens
+ * model).  The recorder's 3 x 3 depth-variance gate has no meaning for a per-keypoint depth and does not apply (sd = 0):
+ * uniqueness and the left-right check take its place as the guard against depth discontinuities. */
+#define RELOC_STEREO_R                 5
+#define RELOC_STEREO_MIN_DISPARITY_MAX 1024
+#define RELOC_STEREO_NUM_DISP_MIN      8
+#define RELOC_STEREO_NUM_DISP_MAX      256
+#define RELOC_STEREO_NUM_DISP_DEFAULT  128
+#define RELOC_STEREO_UNIQUENESS_MAX    50
+#define RELOC_STEREO_UNIQUENESS_DEFAULT 15
+#define RELOC_STEREO_OK          0
+#define RELOC_STEREO_BORDER      1
+#define RELOC_STEREO_RANGE       2
+#define RELOC_STEREO_EDGE        3
+#define RELOC_STEREO_UNIQUENESS  4
+#define RELOC_STEREO_LR          5
+#define RELOC_STEREO_FAR         6
+
 #endif /* RELOC_SPEC_H */

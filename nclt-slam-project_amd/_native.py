@@ -93,6 +93,13 @@ SIGNATURES = {
     "reloc_yuv422_bgr_u8": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P]),
     "reloc_set_pixel_format": (C.c_int, [c_ctx, C.c_int]),
     "reloc_get_pixel_format": (C.c_int, [c_ctx, P]),
+    "reloc_set_stereo": (C.c_int, [c_ctx, f64, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "reloc_get_stereo": (C.c_int, [c_ctx, P, P, P, P, P]),
+    "reloc_stereo_depth": (C.c_int, [c_ctx, P, P, C.c_int, C.c_int, C.c_int, P, C.c_int, f64, f64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     P, P, P]),
+    "reloc_record_frame_stereo": (C.c_int, [c_ctx, c_ctx, P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P]),
+    "reloc_tick_accumulate_stereo_dev": (C.c_int, [c_ctx, c_ctx, P, C.c_int, C.c_int, C.c_int, P, C.c_int]),
+    "reloc_stereo_debug": (C.c_int, [c_ctx, P, P, P, P]),
     "reloc_tick_debug": (C.c_int, [c_ctx, P, P, P, P, P, P, P]),
     "reloc_tick_debug_matches": (C.c_int, [c_ctx, C.c_int, P, P, P, P, P, P]),
     "reloc_tick": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, P, C.c_int, u64, P, P, P, P, P, P]),

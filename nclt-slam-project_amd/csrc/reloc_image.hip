@@ -36,6 +36,14 @@ __global__ __launch_bounds__(256) void k_gray_plain(const uint8_t *__restrict__ 
     dst[(size_t)y * w + x] = (uint8_t)gray_fixed(b, c1, r, order_rgb);
 }
 
+// the same on c's stream, device pointers: the right eye of a stereo pair whose chain has no stage on (reloc_stereo.hip)
+int image_gray_plain(reloc_ctx *c, const uint8_t *src, int w, int h, int sstride, int order, uint8_t *dst)
+{
+    hipLaunchKernelGGL(k_gray_plain, dim3((w + 255) / 256, h), dim3(256), 0, c->stream, src, w, h, sstride, gray_flags(c, order), dst);
+    HIP_TRY(hipGetLastError());
+    return RELOC_OK;
+}
+
 // ---- BAYER: cv2.cvtColor(raw, COLOR_Bayer??2BGR) (include/reloc_spec.h, "BAYER") ---------------------------------
 // OpenCV's bilinear 8-bit demosaic, interior and border rule in one launch: output pixel (y, x) is the interior value at
 // (clamp(y, 1, h - 2), clamp(x, 1, w - 2)) -- columns first, then rows, as the spec fills them.

@@ -370,6 +370,28 @@ struct MatchPolicy {
     bool same(const MatchPolicy &o) const { return policy == o.policy && ratio == o.ratio; }
 };
 
+// Sparse stereo depth of a context, the left eye's (reloc_set_stereo; include/reloc_spec.h "STEREO"); baseline 0 = off, the
+// default.  The buffers and the two events are taken on the first enable (reloc_stereo.hip).
+struct StereoState {
+    double baseline = 0.0;               // metres
+    int min_disp = 0, num_disp = RELOC_STEREO_NUM_DISP_DEFAULT, uniq = RELOC_STEREO_UNIQUENESS_DEFAULT, lr = 1;
+    uint8_t *block = nullptr;            // the one device block of the first enable; the four pointers below lie in it
+    uint8_t *plane = nullptr;            // right eye's gray plane where its chain has no stage on (dense rows)
+    uint16_t *mm = nullptr;              // max_feat: depth of the keypoints of the frame's ORB output
+    float *disp = nullptr;               // max_feat
+    uint8_t *status = nullptr;           // max_feat
+    hipEvent_t right_done = nullptr;     // the right eye's chain has written its plane (recorded on the right context's stream)
+    hipEvent_t left_ready = nullptr;     // this context's stream so far: the right frame's copy, the last stereo kernel (which
+                                         // reads the right chain's planes); the next right chain waits for it
+    bool ran = false;                    // a stereo pass was enqueued: mm / disp / status belong to a frame (reloc_stereo_debug)
+    bool on() const { return baseline > 0.0; }
+    // the settings, no buffer: reloc_set_stereo returns at once where nothing changes
+    bool same(const StereoState &o) const
+    {
+        return baseline == o.baseline && min_disp == o.min_disp && num_disp == o.num_disp && uniq == o.uniq && lr == o.lr;
+    }
+};
+
 // What the five ORB kernels read and write of one frame, in the form they take it: a single-frame launch passes the members
 // as arguments, a batched one up to 8 of these in its kernel arguments (OrbBatch, blockIdx.y = frame).
 struct OrbFrame {
@@ -453,6 +475,7 @@ struct reloc_ctx {
     // ---- matcher parameters (reloc_set_params) and match policy (reloc_set_match_policy) ----
     reloc_params prm;
     MatchPolicy match;
+    StereoState stereo;              // reloc_stereo.hip
     int scan_gens = 0;               // RELOC_SCAN_GENS (developer switch), read once at creation: n > 0 = single whole-database
                                      // scans in the form of batched ones (n generations of row budgets + sweepers, launch_db_count)
     uint32_t *scan_ticket = nullptr; // SCAN_TICKET_WORDS counters of the whole-database scans (scan_alloc, reloc_match.hip)
@@ -599,5 +622,13 @@ int image_chain_check_prepared(reloc_ctx *const *ctxs, int f, int n, bool chain,
 int image_chain_gray(reloc_ctx *const *ctxs, int n, bool chain, const uint8_t *const **srcs, int sw, int sh, int w, int h,
                      int *stride, int *channels, int flags, const uint8_t **planes);
 int image_chain_depth(reloc_ctx *ctx, const uint16_t *depth_dev, int *w, int *h, const uint16_t **out);
+// plain gray conversion of a 3-channel frame on c's stream into dense rows of w bytes (reloc_image.hip, k_gray_plain)
+int image_gray_plain(reloc_ctx *c, const uint8_t *src, int w, int h, int sstride, int order, uint8_t *dst);
+// Sparse stereo depth (reloc_stereo.hip).  stereo_frame: the right eye's frame (device memory, a frame of right's chain, w x h
+// as handed in) through right's chain on right's stream, then k_stereo_depth for the keypoints of ctx's last ORB frame on
+// ctx's stream into ctx->stereo.mm / disp / status; the streams are ordered by events in both directions.  *ww x *wh: the
+// working frame.  stereo_release: the events of a context that had stereo on.
+int stereo_frame(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img_right_dev, int w, int h, int order, int *ww, int *wh);
+void stereo_release(reloc_ctx *ctx);
 // PnP-RANSAC of every context's candidates with the matcher parameters of ctxs[0]; seeds: one per frame, or NULL (reloc_pnp.hip)
 int pnp_run_candidates(reloc_ctx *const *ctxs, int n, const uint64_t *seeds, bool latency);

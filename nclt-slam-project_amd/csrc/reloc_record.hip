@@ -17,6 +17,11 @@
 // with the same pixel-based gates (the kept rows do not change).  DIST is a template parameter of the __global__ kernels
 // themselves, not of a shared __device__ body: moving the body into a __forceinline__ function called from two kernels
 // changed the pinhole kernels' code, while templating the kernel keeps every instruction of <false> as it was.
+// Depth source: KPD, the second template parameter of the same two kernels and for the same reason.  false: the depth image
+// (the four instantiations there have always been, instruction for instruction).  true: a per-keypoint uint16 array indexed by
+// the keypoint's row in the frame's ORB output, the millimetres of k_stereo_depth (reloc_stereo.hip; include/reloc_spec.h
+// "STEREO"): dz = (float)kp_mm[i] / 1000.0f, k_record skips the 3x3 patch and takes sd = 0, everything else is the same
+// expression -- border, ground, range, back-projection, compaction, pose and index of an accumulated record.
 #include "reloc_internal.h"
 
 // camera-frame point of the rounded pixel (u, v) at depth dz through the inverse distortion model
@@ -52,7 +57,7 @@ __device__ float np_sum9(const float *a, int n)
     return r;
 }
 
-template <bool DIST>
+template <bool DIST, bool KPD = false>
 __global__ __launch_bounds__(1024) void k_record(const float *__restrict__ f_xy, const uint8_t *__restrict__ f_desc,
                                                  const int32_t *__restrict__ f_count, int max_feat,
                                                  const uint16_t *__restrict__ depth, int dstride, RecordParams p,
@@ -76,20 +81,25 @@ __global__ __launch_bounds__(1024) void k_record(const float *__restrict__ f_xy,
             x = f_xy[2 * i]; y = f_xy[2 * i + 1];
             u = (int)rintf(x); v = (int)rintf(y);
             if (u >= 1 && u < p.w - 1 && v >= 1 && v < p.h - 1 && v > p.ground_y) {
-                dz = __fdiv_rn((float)depth[(size_t)v * dstride + u], 1000.0f);
-                float vals[9];
-                int cnt = 0;
-                for (int dy = -1; dy <= 1; ++dy)
-                    for (int dx = -1; dx <= 1; ++dx) {
-                        const float m = __fdiv_rn((float)depth[(size_t)(v + dy) * dstride + (u + dx)], 1000.0f);
-                        if (m > 0.01f) vals[cnt++] = m;
+                float sd = 0.0f;
+                if constexpr (KPD) {
+                    dz = __fdiv_rn((float)depth[i], 1000.0f);      // depth: the per-keypoint millimetres; no patch, sd = 0
+                } else {
+                    dz = __fdiv_rn((float)depth[(size_t)v * dstride + u], 1000.0f);
+                    float vals[9];
+                    int cnt = 0;
+                    for (int dy = -1; dy <= 1; ++dy)
+                        for (int dx = -1; dx <= 1; ++dx) {
+                            const float m = __fdiv_rn((float)depth[(size_t)(v + dy) * dstride + (u + dx)], 1000.0f);
+                            if (m > 0.01f) vals[cnt++] = m;
+                        }
+                    sd = 999.0f;
+                    if (cnt >= 3) {
+                        const float mean = __fdiv_rn(np_sum9(vals, cnt), (float)cnt);
+                        float sq[9];
+                        for (int k = 0; k < cnt; ++k) { const float d = __fsub_rn(vals[k], mean); sq[k] = __fmul_rn(d, d); }
+                        sd = __fsqrt_rn(__fdiv_rn(np_sum9(sq, cnt), (float)cnt));
                     }
-                float sd = 999.0f;
-                if (cnt >= 3) {
-                    const float mean = __fdiv_rn(np_sum9(vals, cnt), (float)cnt);
-                    float sq[9];
-                    for (int k = 0; k < cnt; ++k) { const float d = __fsub_rn(vals[k], mean); sq[k] = __fmul_rn(d, d); }
-                    sd = __fsqrt_rn(__fdiv_rn(np_sum9(sq, cnt), (float)cnt));
                 }
                 keep = dz > p.depth_min && dz < p.depth_max && sd < p.var_max;
             }
@@ -123,6 +133,56 @@ __global__ __launch_bounds__(1024) void k_record(const float *__restrict__ f_xy,
     if (tid == 0) *o_n = s_base;
 }
 
+// the recorder's gates on the w x h working frame of ctx's camera
+static RecordParams record_params(const reloc_ctx *ctx, int w, int h)
+{
+    RecordParams p;
+    p.fx = ctx->cam.K4[0]; p.fy = ctx->cam.K4[1]; p.cx = ctx->cam.K4[2]; p.cy = ctx->cam.K4[3];
+    p.depth_min = RELOC_DEPTH_MIN_M; p.depth_max = RELOC_DEPTH_MAX_M; p.var_max = RELOC_DEPTH_VAR_MAX_M;
+    p.ground_y = RELOC_GROUND_Y_THRESHOLD; p.w = w; p.h = h;
+    return p;
+}
+
+// The rows of one recording on the device (scratch slot 6 of the context), the gates' launch on the frame's ORB output and the
+// rows' way to the caller: what reloc_record_frame and reloc_record_frame_stereo share behind their depth source.
+struct RecordRows {
+    uint8_t *desc = nullptr;
+    float *xy = nullptr, *pts = nullptr;
+    int32_t *idx = nullptr, *n = nullptr;
+    bool alloc(HostStaging &st)
+    {
+        const int64_t mf = st.ctx->max_feat;
+        desc = st.slot<uint8_t>(6, mf * (8 + 32 + 12 + 4) + 64);
+        if (st.rc) return false;
+        xy = (float *)(desc + mf * 32); pts = xy + mf * 2;
+        idx = (int32_t *)(pts + mf * 3); n = idx + mf;
+        return true;
+    }
+    // KPD: depth holds the millimetres per keypoint (dstride unused), else the depth image of the w x h working frame
+    template <bool KPD>
+    void launch(HostStaging &st, const uint16_t *depth, int w, int h)
+    {
+        reloc_ctx *ctx = st.ctx;
+        const RecordParams p = record_params(ctx, w, h);
+        const double *lens = ctx->cam.lens();
+        st.launch(lens ? k_record<true, KPD> : k_record<false, KPD>, dim3(1), dim3(1024), ctx->orb.buf.f_xy, ctx->orb.buf.f_desc,
+                  ctx->orb.buf.f_count, ctx->max_feat, depth, w, p, xy, desc, pts, idx, n, make_dist(lens));
+    }
+    // the rows written (0 after an error) into the caller's arrays, each of which may be NULL; *nk = the frame's ORB keypoints
+    int32_t download(HostStaging &st, float *h_xy, uint8_t *h_desc, float *h_pts, int32_t *h_idx, int32_t *nk)
+    {
+        st.download(nk, st.ctx->orb.buf.f_count, 4);
+        const int32_t rows = st.count(n);
+        if (rows > 0) {
+            if (h_xy) st.download(h_xy, xy, (int64_t)rows * 8);
+            if (h_desc) st.download(h_desc, desc, (int64_t)rows * 32);
+            if (h_pts) st.download(h_pts, pts, (int64_t)rows * 12);
+            if (h_idx) st.download(h_idx, idx, (int64_t)rows * 4);
+        }
+        return rows;
+    }
+};
+
 // Host-pointer entry point: ORB on the frame, then the gates.  Outputs hold up to the ctx's max_feat
 // rows: xy (n,2) f32 keypoints_2d, desc (n,32) u8, pts3d (n,3) f32 keypoints_3d_cam, kp_index (n) i32
 // (row of the surviving keypoint in the frame's ORB output); *n_out rows written, *n_kp = ORB keypoints.
@@ -134,12 +194,9 @@ RELOC_API int reloc_record_frame(reloc_ctx *ctx, const uint8_t *img, const uint1
     if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
     *n_out = 0;
     if (n_kp) *n_kp = 0;
-    const int64_t mf = ctx->max_feat;
     HostStaging st{ctx};
-    uint8_t *o_desc = st.slot<uint8_t>(6, mf * (8 + 32 + 12 + 4) + 64);
-    if (st.rc) return st.rc;
-    float *o_xy = (float *)(o_desc + mf * 32), *o_pts = o_xy + mf * 2;
-    int32_t *o_idx = (int32_t *)(o_pts + mf * 3), *o_n = o_idx + mf;
+    RecordRows rows;
+    if (!rows.alloc(st)) return st.rc;
     const int bpp = image_chain_frame_bpp(ctx);
     st.upload(ctx->frame_img, img, (int64_t)w * h * bpp);
     const uint16_t *depth = st.upload_slot(5, depth_mm, (int64_t)w * h);
@@ -148,25 +205,53 @@ RELOC_API int reloc_record_frame(reloc_ctx *ctx, const uint8_t *img, const uint1
         if (int rc = orb_run(&ctx, 1, &src, w, h, w * bpp, true, order, nfeatures, true)) return rc;
         return image_chain_depth(ctx, depth, &w, &h, &depth);      // from here on the working frame
     });
-    RecordParams p;
-    p.fx = ctx->cam.K4[0]; p.fy = ctx->cam.K4[1]; p.cx = ctx->cam.K4[2]; p.cy = ctx->cam.K4[3];
-    p.depth_min = RELOC_DEPTH_MIN_M; p.depth_max = RELOC_DEPTH_MAX_M; p.var_max = RELOC_DEPTH_VAR_MAX_M;
-    p.ground_y = RELOC_GROUND_Y_THRESHOLD; p.w = w; p.h = h;
-    const double *lens = ctx->cam.lens();
-    st.launch(lens ? k_record<true> : k_record<false>, dim3(1), dim3(1024), ctx->orb.buf.f_xy, ctx->orb.buf.f_desc, ctx->orb.buf.f_count, ctx->max_feat, depth,
-              w, p, o_xy, o_desc, o_pts, o_idx, o_n, make_dist(lens));
+    rows.launch<false>(st, depth, w, h);
     int32_t nk = 0;
-    st.download(&nk, ctx->orb.buf.f_count, 4);
-    const int32_t n = st.count(o_n);
-    if (n > 0) {
-        if (xy) st.download(xy, o_xy, (int64_t)n * 8);
-        if (desc) st.download(desc, o_desc, (int64_t)n * 32);
-        if (pts3d) st.download(pts3d, o_pts, (int64_t)n * 12);
-        if (kp_index) st.download(kp_index, o_idx, (int64_t)n * 4);
-    }
+    const int32_t n = rows.download(st, xy, desc, pts3d, kp_index, &nk);
     if (int rc = st.finish()) return rc;
     *n_out = n;
     if (n_kp) *n_kp = nk;
+    return RELOC_OK;
+}
+
+// The same with the right eye's frame in the depth image's place (include/reloc_spec.h "STEREO"): ORB on the left frame, the
+// right frame through its own context's chain, k_stereo_depth at the keypoints, then the gates on the per-keypoint depth.
+RELOC_API int reloc_record_frame_stereo(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img, const uint8_t *img_right, int w, int h,
+                                        int order, int nfeatures, float *xy, uint8_t *desc, float *pts3d, int32_t *kp_index,
+                                        int32_t *n_out, int32_t *n_kp, int32_t *n_stereo)
+{
+    ARG_CHECK_CTX(ctx, right && img && img_right && n_out && w >= 64 && h >= 64 && nfeatures > 0, "reloc_record_frame_stereo");
+    if (!ctx->stereo.on()) { reloc_set_error("stereo is off on this context (reloc_set_stereo)"); return RELOC_E_STATE; }
+    if (w > ctx->max_w || h > ctx->max_h || w > right->max_w || h > right->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
+    *n_out = 0;
+    if (n_kp) *n_kp = 0;
+    if (n_stereo) *n_stereo = 0;
+    HostStaging st{ctx};
+    RecordRows rows;
+    if (!rows.alloc(st)) return st.rc;
+    const int bpp = image_chain_frame_bpp(ctx);
+    st.upload(ctx->frame_img, img, (int64_t)w * h * bpp);
+    bool right_busy = false;       // the right context's stream holds a copy from the caller's memory
+    st.run([&] {
+        const uint8_t *src = ctx->frame_img;
+        if (int rc = orb_run(&ctx, 1, &src, w, h, w * bpp, true, order, nfeatures, true)) return rc;
+        right_busy = true;
+        HIP_TRY(hipMemcpyAsync(right->frame_img, img_right, (size_t)w * h * image_chain_frame_bpp(right), hipMemcpyHostToDevice, right->stream));
+        return stereo_frame(ctx, right, right->frame_img, w, h, order, &w, &h);      // from here on the working frame
+    });
+    rows.launch<true>(st, ctx->stereo.mm, w, h);
+    int32_t nk = 0;
+    const int32_t n = rows.download(st, xy, desc, pts3d, kp_index, &nk);
+    const int32_t ns = nk < ctx->max_feat ? nk : ctx->max_feat;
+    std::vector<uint8_t> status((size_t)(n_stereo && ns > 0 ? ns : 0));
+    if (!status.empty()) st.download(status.data(), ctx->stereo.status, ns);
+    const int rc = st.finish();
+    // after an error the two streams may not be ordered: nothing of the caller's right frame stays in flight
+    if (rc && right_busy) (void)hipStreamSynchronize(right->stream);
+    if (rc) return rc;
+    *n_out = n;
+    if (n_kp) *n_kp = nk;
+    for (uint8_t s : status) *n_stereo += s == RELOC_STEREO_OK;
     return RELOC_OK;
 }
 
@@ -213,7 +298,7 @@ __device__ void rot_to_quat_scipy(const double R[9], double q[4])
     for (int c = 0; c < 4; ++c) q[c] = q[c] / n;
 }
 
-template <bool DIST>
+template <bool DIST, bool KPD = false>
 __global__ __launch_bounds__(1024) void k_accumulate(const float *__restrict__ f_xy, const uint8_t *__restrict__ f_desc,
                                                      const int32_t *__restrict__ f_count, int max_feat,
                                                      const uint16_t *__restrict__ depth, int dstride, AccumParams p,
@@ -268,7 +353,8 @@ __global__ __launch_bounds__(1024) void k_accumulate(const float *__restrict__ f
             x = f_xy[2 * i]; y = f_xy[2 * i + 1];
             u = (int)rintf(x); v = (int)rintf(y);
             if (u >= 1 && u < p.w - 1 && v >= 1 && v < p.h - 1) {
-                dz = __fdiv_rn((float)depth[(size_t)v * dstride + u], 1000.0f);
+                if constexpr (KPD) dz = __fdiv_rn((float)depth[i], 1000.0f);       // depth: the per-keypoint millimetres
+                else dz = __fdiv_rn((float)depth[(size_t)v * dstride + u], 1000.0f);
                 keep = dz > p.zmin && dz < p.zmax;
             }
         }
@@ -328,10 +414,9 @@ __global__ __launch_bounds__(1024) void k_accumulate(const float *__restrict__ f
     }
 }
 
-RELOC_API int reloc_tick_accumulate_dev(reloc_ctx *ctx, const uint16_t *depth_mm_dev, int w, int h, const double base_pose[7],
-                                        int silence_ok)
+// room for one more record of max_feat rows in the selected database, which must be this context's own
+static int accum_reserve(reloc_ctx *ctx)
 {
-    ARG_CHECK_CTX(ctx, depth_mm_dev && base_pose && w >= 64 && h >= 64, "reloc_tick_accumulate_dev");
     if (!db_ready(ctx)) { reloc_set_error("no database uploaded"); return RELOC_E_STATE; }
     const DbArena &db = ctx_db(ctx);
     if (db.shared) { reloc_set_error("the selected database is shared from another context (read-only here)"); return RELOC_E_STATE; }
@@ -340,7 +425,14 @@ RELOC_API int reloc_tick_accumulate_dev(reloc_ctx *ctx, const uint16_t *depth_mm
         int rc = db_reserve(ctx, db.cap_records + db.cap_records / 2 + 64, db.cap_rows + db.cap_rows / 2 + 64 * (int64_t)ctx->max_feat);
         if (rc) return rc;
     }
-    if (int rc = image_chain_depth(ctx, depth_mm_dev, &w, &h, &depth_mm_dev)) return rc;      // from here on the working frame
+    return RELOC_OK;
+}
+
+// k_accumulate on the w x h working frame; KPD: depth = per-keypoint millimetres (reloc_tick_accumulate_stereo_dev)
+template <bool KPD>
+static int accum_launch(reloc_ctx *ctx, const uint16_t *depth_mm_dev, int w, int h, const double base_pose[7], int silence_ok)
+{
+    const DbArena &db = ctx_db(ctx);
     AccumParams p;
     const CameraModel &cam = ctx->cam;
     p.fx = cam.K4[0]; p.fy = cam.K4[1]; p.cx = cam.K4[2]; p.cy = cam.K4[3];
@@ -351,12 +443,32 @@ RELOC_API int reloc_tick_accumulate_dev(reloc_ctx *ctx, const uint16_t *depth_mm
     p.zmin = (float)ctx->prm.accum_depth_min_m; p.zmax = (float)ctx->prm.accum_depth_max_m;
     p.w = w; p.h = h; p.min_kpts = ctx->prm.accum_min_kpts; p.silence_ok = silence_ok;
     p.L = db.records; p.T = db.rows;
-    auto kern = cam.lens() ? k_accumulate<true> : k_accumulate<false>;
+    auto kern = cam.lens() ? k_accumulate<true, KPD> : k_accumulate<false, KPD>;
     hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, ctx->stream, ctx->orb.buf.f_xy, ctx->orb.buf.f_desc, ctx->orb.buf.f_count, ctx->max_feat,
                        depth_mm_dev, w, p, ctx->tick.res, db.xy_heading, db.desc, db.pts3d, db.kp2d, db.off, db.pose, ctx->accum_res,
                        make_dist(cam.lens()));
     HIP_TRY(hipGetLastError());
     return RELOC_OK;
+}
+
+RELOC_API int reloc_tick_accumulate_dev(reloc_ctx *ctx, const uint16_t *depth_mm_dev, int w, int h, const double base_pose[7],
+                                        int silence_ok)
+{
+    ARG_CHECK_CTX(ctx, depth_mm_dev && base_pose && w >= 64 && h >= 64, "reloc_tick_accumulate_dev");
+    if (int rc = accum_reserve(ctx)) return rc;
+    if (int rc = image_chain_depth(ctx, depth_mm_dev, &w, &h, &depth_mm_dev)) return rc;      // from here on the working frame
+    return accum_launch<false>(ctx, depth_mm_dev, w, h, base_pose, silence_ok);
+}
+
+// the same with the depth of the tick's keypoints from the right eye's frame (include/reloc_spec.h "STEREO"); enqueues only
+RELOC_API int reloc_tick_accumulate_stereo_dev(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img_right_dev, int w, int h, int order,
+                                               const double base_pose[7], int silence_ok)
+{
+    ARG_CHECK_CTX(ctx, right && img_right_dev && base_pose && w >= 64 && h >= 64, "reloc_tick_accumulate_stereo_dev");
+    if (!ctx->stereo.on()) { reloc_set_error("stereo is off on this context (reloc_set_stereo)"); return RELOC_E_STATE; }
+    if (int rc = accum_reserve(ctx)) return rc;
+    if (int rc = stereo_frame(ctx, right, img_right_dev, w, h, order, &w, &h)) return rc;      // from here on the working frame
+    return accum_launch<true>(ctx, ctx->stereo.mm, w, h, base_pose, silence_ok);
 }
 
 RELOC_API int reloc_accumulate_result(reloc_ctx *ctx, int32_t *appended, int32_t *n_kpts, double *nearest_m)

@@ -1,0 +1,365 @@
+// reloc_stereo.hip -- sparse stereo depth on gfx950: the depth of the ORB keypoints from the other eye of a rectified pair
+// (include/reloc_spec.h, "STEREO").  The matcher is this project's own; the spec states it in integers and
+// tests/stereo_ref.py restates it bit for bit.
+//   k_stereo_depth   one wave per keypoint, lanes over disparities, 64 per pass (num_disparities > 64: further passes of the
+//                    same wave).  Per pass the 11 rows of the searched eye that the 64 candidates cover (74 bytes each) and
+//                    the 11 x 11 patch of the other eye are staged in LDS, about 1 KB per wave.  A lane's patch row is three
+//                    dwords cut out of four aligned LDS dwords (v_alignbyte), the absolute differences are four per
+//                    instruction (v_sad_u8).  Four neighbouring lanes read the same dwords, 64 lanes span 17: no bank conflict.
+//                    (cost, disparity) travel as one integer key, cost << 11 | d, and are reduced with min in the DPP network,
+//                    so the lowest disparity wins a tie by the reduction itself.  The costs of a wave stay in registers (one
+//                    per pass); the parabola's neighbours are read back from the lanes that hold them.
+//                    Every branch on a status is wave-uniform; a workgroup is one wave, so its barriers cost nothing.
+// Each eye has its own row stride (a pyramid level or a stage's plane: (w + 63) & ~63; a dense gray plane or a caller's mono8
+// frame: w; reloc_stereo_depth: the caller's).  The bytes are staged one by one through the cache: rows start at any
+// alignment, and a byte outside 0 <= x < w, row padding included, is never fetched.
+#include "reloc_internal.h"
+#include "reloc_pixels.h"
+
+constexpr int SR = RELOC_STEREO_R, SP = 2 * RELOC_STEREO_R + 1;     // radius and side of the patch
+constexpr int STRIP_DW = 20;          // dwords per staged row: 63 + SP bytes, read as 4 dwords from dword (63 >> 2)
+constexpr int PATCH_DW = 3;           // dwords per patch row, the twelfth byte zero
+constexpr int STEREO_PASSES = RELOC_STEREO_NUM_DISP_MAX / 64;
+constexpr unsigned KEY_NONE = 0xFFFFFFFFu;
+static_assert(SP == 11 && SP * SP * 255 < (1 << 15) && RELOC_STEREO_MIN_DISPARITY_MAX + RELOC_STEREO_NUM_DISP_MAX < (1 << 11),
+              "cost << 11 | disparity is a 26-bit key");
+
+struct StereoParams {
+    double fx, baseline;
+    int w, h;
+    int min_disp, num_disp, uniq, lr;
+};
+
+// wave-wide minimum in the DPP network (wave_max_u32's steps); all 64 lanes active
+__device__ __forceinline__ unsigned wave_min_u32(unsigned v)
+{
+    int x = (int)v;
+#define RELOC_DPP_STEP(ctrl, rmask)                                                                     \
+    {                                                                                                   \
+        const unsigned o = (unsigned)__builtin_amdgcn_update_dpp(x, x, ctrl, rmask, 0xF, false);         \
+        x = (int)((unsigned)x < o ? (unsigned)x : o);                                                    \
+    }
+    RELOC_DPP_STEP(0xB1, 0xF)    // quad_perm [1,0,3,2]
+    RELOC_DPP_STEP(0x4E, 0xF)    // quad_perm [2,3,0,1]
+    RELOC_DPP_STEP(0x141, 0xF)   // row_half_mirror
+    RELOC_DPP_STEP(0x140, 0xF)   // row_mirror
+    RELOC_DPP_STEP(0x142, 0xA)   // row_bcast15 -> rows 1, 3
+    RELOC_DPP_STEP(0x143, 0xC)   // row_bcast31 -> rows 2, 3
+#undef RELOC_DPP_STEP
+    return (unsigned)__builtin_amdgcn_readlane(x, 63);
+}
+
+// rows v - R .. v + R of img, bytes x0 .. x0 + 4 ndw - 1, as dwords dst[row * ndw + k]; a byte outside 0 <= x < w is 0 and is
+// not fetched; patch: the bytes behind the eleventh are 0 as well
+__device__ __forceinline__ void stereo_stage(const uint8_t *__restrict__ img, int stride, int w, int v, int x0, int ndw, bool patch,
+                                             uint32_t *dst, int lane)
+{
+    for (int t = lane; t < SP * ndw; t += 64) {
+        const int j = t / ndw, k = t - j * ndw;
+        const uint8_t *row = img + (size_t)(v - SR + j) * stride;
+        uint32_t word = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int x = x0 + 4 * k + b;
+            if (x >= 0 && x < w && !(patch && 4 * k + b >= SP)) word |= (uint32_t)row[x] << (8 * b);
+        }
+        dst[t] = word;
+    }
+}
+
+// SAD of the staged patch and the SP x SP window whose first byte is byte `off` of the staged rows
+__device__ __forceinline__ int stereo_cost(const uint32_t *strip, const uint32_t *patch, int off)
+{
+    const int q = off >> 2;
+    const unsigned sh = (unsigned)off & 3u;
+    unsigned c = 0;
+#pragma unroll
+    for (int j = 0; j < SP; ++j) {
+        const uint32_t *s = strip + j * STRIP_DW + q;
+        const uint32_t w0 = s[0], w1 = s[1], w2 = s[2], w3 = s[3];
+        c = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w1, w0, sh), patch[PATCH_DW * j], c);
+        c = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w2, w1, sh), patch[PATCH_DW * j + 1], c);
+        c = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w3, w2, sh) & 0x00FFFFFFu, patch[PATCH_DW * j + 2], c);
+    }
+    return (int)c;
+}
+
+// pass-th register of a lane's costs (pass is wave-uniform)
+__device__ __forceinline__ int stereo_pick(const int (&cost)[STEREO_PASSES], int pass)
+{
+    int r = cost[0];
+#pragma unroll
+    for (int p = 1; p < STEREO_PASSES; ++p) r = pass == p ? cost[p] : r;
+    return r;
+}
+
+// keypoint blockIdx.x of xy; count: their number on the device (the frame's own keypoints, at most n_max) or NULL: n_max
+__global__ __launch_bounds__(64) void k_stereo_depth(const uint8_t *__restrict__ left, int lstride, const uint8_t *__restrict__ right,
+                                                     int rstride, const float *__restrict__ xy, const int32_t *__restrict__ count,
+                                                     int n_max, StereoParams p, uint16_t *__restrict__ o_mm,
+                                                     float *__restrict__ o_disp, uint8_t *__restrict__ o_status)
+{
+    RELOC_SMALL_KERNEL_PRIO();
+    __shared__ uint32_t s_strip[SP * STRIP_DW];
+    __shared__ uint32_t s_patch[SP * PATCH_DW];
+    const int lane = threadIdx.x, i = blockIdx.x;
+    const int n = count ? min(*count, n_max) : n_max;
+    if (i >= n) return;
+    int status = RELOC_STEREO_OK;
+    uint16_t mm_out = 0;
+    float disp_out = 0.f;
+    const int u = (int)rintf(xy[2 * i]), v = (int)rintf(xy[2 * i + 1]);
+    const int dmin = p.min_disp;
+    const int dhi = min(dmin + p.num_disp - 1, u - SR);          // largest member of D
+    int dstar = 0, a = 0, b = 0, c = 0;
+    if (!(u >= SR && u < p.w - SR && v >= SR && v < p.h - SR)) status = RELOC_STEREO_BORDER;
+    else if (dhi - dmin + 1 < 3) status = RELOC_STEREO_RANGE;
+    else {
+        // ---- steps 3-5: the costs of D, lane l of pass q holds d = dmin + 64 q + l ----
+        const int npass = (dhi - dmin + 64) >> 6;
+        int cost[STEREO_PASSES];
+        unsigned key = KEY_NONE;
+        stereo_stage(left, lstride, p.w, v, u - SR, PATCH_DW, true, s_patch, lane);
+#pragma unroll
+        for (int q = 0; q < STEREO_PASSES; ++q) {
+            cost[q] = 0;
+            if (q < npass) {
+                const int d0 = dmin + 64 * q, d = d0 + lane;
+                if (q) __syncthreads();                           // the previous pass has read the strip
+                stereo_stage(right, rstride, p.w, v, u - d0 - 63 - SR, STRIP_DW, false, s_strip, lane);
+                __syncthreads();
+                cost[q] = stereo_cost(s_strip, s_patch, 63 - lane);
+                if (d <= dhi) key = min(key, ((unsigned)cost[q] << 11) | (unsigned)d);
+            }
+        }
+        key = wave_min_u32(key);
+        dstar = (int)(key & 0x7FFu);
+        b = (int)(key >> 11);
+        if (dstar == dmin || dstar == dhi) status = RELOC_STEREO_EDGE;
+        else {
+            unsigned key2 = KEY_NONE;
+#pragma unroll
+            for (int q = 0; q < STEREO_PASSES; ++q) {
+                const int d = dmin + 64 * q + lane;
+                if (q < npass && d <= dhi && abs(d - dstar) >= 2) key2 = min(key2, ((unsigned)cost[q] << 11) | (unsigned)d);
+            }
+            key2 = wave_min_u32(key2);
+            if (key2 != KEY_NONE && (int)(key2 >> 11) * (100 - p.uniq) <= b * 100) status = RELOC_STEREO_UNIQUENESS;
+            else {
+                const int ia = dstar - 1 - dmin, ic = dstar + 1 - dmin;
+                a = __builtin_amdgcn_readlane(stereo_pick(cost, ia >> 6), ia & 63);
+                c = __builtin_amdgcn_readlane(stereo_pick(cost, ic >> 6), ic & 63);
+            }
+        }
+    }
+    if (status == RELOC_STEREO_OK && p.lr) {
+        // ---- step 6: the same search from the right eye's patch at xr over the left eye ----
+        const int xr = u - dstar;
+        const int dhi2 = min(dmin + p.num_disp - 1, p.w - SR - 1 - xr);      // >= dstar: D' is never empty
+        const int npass = (dhi2 - dmin + 64) >> 6;
+        unsigned key = KEY_NONE;
+        __syncthreads();
+        stereo_stage(right, rstride, p.w, v, xr - SR, PATCH_DW, true, s_patch, lane);
+        for (int q = 0; q < npass; ++q) {
+            const int d0 = dmin + 64 * q, d = d0 + lane;
+            if (q) __syncthreads();
+            stereo_stage(left, lstride, p.w, v, xr + d0 - SR, STRIP_DW, false, s_strip, lane);
+            __syncthreads();
+            const int cq = stereo_cost(s_strip, s_patch, lane);
+            if (d <= dhi2) key = min(key, ((unsigned)cq << 11) | (unsigned)d);
+        }
+        key = wave_min_u32(key);
+        if (abs((int)(key & 0x7FFu) - dstar) > 1) status = RELOC_STEREO_LR;
+    }
+    if (status == RELOC_STEREO_OK) {
+        // ---- steps 7, 8 ----
+        const int den = a + c - 2 * b;
+        const float delta = den <= 0 ? 0.f : __fdiv_rn((float)(a - c), (float)(2 * den));
+        const float disp = __fadd_rn((float)dstar, delta);
+        const double z = __ddiv_rn(__dmul_rn(p.fx, p.baseline), (double)disp);
+        const double mm = rint(__dmul_rn(z, 1000.0));
+        if (mm > 65535.0) status = RELOC_STEREO_FAR;
+        else { mm_out = (uint16_t)mm; disp_out = disp; }
+    }
+    if (lane == 0) {
+        o_mm[i] = mm_out;
+        o_disp[i] = disp_out;
+        o_status[i] = (uint8_t)status;
+    }
+}
+
+static int stereo_launch(reloc_ctx *ctx, const uint8_t *left, int lstride, const uint8_t *right, int rstride, const float *xy,
+                         const int32_t *count, int n_max, const StereoParams &p, uint16_t *mm, float *disp, uint8_t *status)
+{
+    reloc_prof_begin(ctx, RELOC_PROF_STEREO);
+    hipLaunchKernelGGL(k_stereo_depth, dim3(n_max), dim3(64), 0, ctx->stream, left, lstride, right, rstride, xy, count, n_max, p, mm, disp, status);
+    reloc_prof_end(ctx, RELOC_PROF_STEREO);
+    HIP_TRY(hipGetLastError());
+    return RELOC_OK;
+}
+
+static int stereo_args_check(double baseline_m, int min_disparity, int num_disparities, int uniqueness, int lr_check, bool may_be_off)
+{
+    if (!(baseline_m - baseline_m == 0.0) || baseline_m < 0.0 || (!may_be_off && baseline_m == 0.0)) {
+        reloc_set_error("bad argument: stereo baseline_m %g is not finite and %s 0", baseline_m, may_be_off ? ">=" : ">");
+        return RELOC_E_ARG;
+    }
+    if (min_disparity < 0 || min_disparity > RELOC_STEREO_MIN_DISPARITY_MAX) {
+        reloc_set_error("bad argument: stereo min_disparity %d outside 0..%d", min_disparity, RELOC_STEREO_MIN_DISPARITY_MAX);
+        return RELOC_E_ARG;
+    }
+    if (num_disparities < RELOC_STEREO_NUM_DISP_MIN || num_disparities > RELOC_STEREO_NUM_DISP_MAX) {
+        reloc_set_error("bad argument: stereo num_disparities %d outside %d..%d", num_disparities, RELOC_STEREO_NUM_DISP_MIN, RELOC_STEREO_NUM_DISP_MAX);
+        return RELOC_E_ARG;
+    }
+    if (uniqueness < 0 || uniqueness > RELOC_STEREO_UNIQUENESS_MAX) {
+        reloc_set_error("bad argument: stereo uniqueness %d outside 0..%d", uniqueness, RELOC_STEREO_UNIQUENESS_MAX);
+        return RELOC_E_ARG;
+    }
+    if (lr_check != 0 && lr_check != 1) { reloc_set_error("bad argument: stereo lr_check %d outside 0..1", lr_check); return RELOC_E_ARG; }
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_set_stereo(reloc_ctx *ctx, double baseline_m, int min_disparity, int num_disparities, int uniqueness, int lr_check)
+{
+    ARG_CHECK_CTX(ctx, true, "reloc_set_stereo");
+    StereoState &s = ctx->stereo;
+    if (baseline_m == 0.0) {       // off: the setting of a new context
+        s.baseline = 0.0; s.min_disp = 0; s.num_disp = RELOC_STEREO_NUM_DISP_DEFAULT; s.uniq = RELOC_STEREO_UNIQUENESS_DEFAULT; s.lr = 1;
+        return RELOC_OK;
+    }
+    if (int rc = stereo_args_check(baseline_m, min_disparity, num_disparities, uniqueness, lr_check, true)) return rc;
+    StereoState want = s;
+    want.baseline = baseline_m; want.min_disp = min_disparity; want.num_disp = num_disparities; want.uniq = uniqueness; want.lr = lr_check;
+    if (s.same(want)) return RELOC_OK;
+    if (!s.disp) {
+        // one block: disparities, millimetres, status of max_feat keypoints, then the right eye's plain gray plane.  The block
+        // belongs to the context from ctx_dev_alloc on (reloc_destroy frees it); the state is wired up only when the block is
+        // zeroed and both events exist, so a failure leaves the context as it was: stereo off, nothing of it alive.
+        const int64_t mf = ctx->max_feat, head = (mf * 7 + 255) / 256 * 256;
+        if (!s.block)
+            if (int rc = ctx_dev_alloc(ctx, &s.block, head + (int64_t)ctx->max_w * ctx->max_h)) return rc;
+        HIP_TRY(hipMemsetAsync(s.block, 0, (size_t)head, ctx->stream));
+        if ((!s.right_done && hipEventCreateWithFlags(&s.right_done, hipEventDisableTiming) != hipSuccess) ||
+            (!s.left_ready && hipEventCreateWithFlags(&s.left_ready, hipEventDisableTiming) != hipSuccess)) {
+            stereo_release(ctx);
+            reloc_set_error("stereo: event creation failed");
+            return RELOC_E_HIP;
+        }
+        s.disp = (float *)s.block; s.mm = (uint16_t *)(s.block + mf * 4); s.status = s.block + mf * 6; s.plane = s.block + head;
+    }
+    s.baseline = want.baseline; s.min_disp = want.min_disp; s.num_disp = want.num_disp; s.uniq = want.uniq; s.lr = want.lr;
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_get_stereo(reloc_ctx *ctx, double *baseline_m, int32_t *min_disparity, int32_t *num_disparities, int32_t *uniqueness,
+                               int32_t *lr_check)
+{
+    ARG_CHECK(ctx, "reloc_get_stereo");
+    const StereoState &s = ctx->stereo;
+    if (baseline_m) *baseline_m = s.baseline;
+    if (min_disparity) *min_disparity = s.min_disp;
+    if (num_disparities) *num_disparities = s.num_disp;
+    if (uniqueness) *uniqueness = s.uniq;
+    if (lr_check) *lr_check = s.lr;
+    return RELOC_OK;
+}
+
+void stereo_release(reloc_ctx *ctx)
+{
+    StereoState &s = ctx->stereo;
+    if (s.right_done) (void)hipEventDestroy(s.right_done);
+    if (s.left_ready) (void)hipEventDestroy(s.left_ready);
+    s.right_done = s.left_ready = nullptr;
+    s.ran = false;
+}
+
+RELOC_API int reloc_stereo_depth(reloc_ctx *ctx, const uint8_t *left, const uint8_t *right, int w, int h, int stride, const float *xy,
+                                 int n, double fx, double baseline_m, int min_disparity, int num_disparities, int uniqueness,
+                                 int lr_check, uint16_t *depth_mm, float *disparity, uint8_t *status)
+{
+    ARG_CHECK_CTX(ctx, left && right && w >= SP && h >= SP && stride >= w && n >= 0 && (n == 0 || (xy && depth_mm && disparity && status)),
+                  "reloc_stereo_depth");
+    if (!(fx - fx == 0.0) || fx <= 0.0) { reloc_set_error("bad argument: stereo fx %g is not finite and > 0", fx); return RELOC_E_ARG; }
+    if (int rc = stereo_args_check(baseline_m, min_disparity, num_disparities, uniqueness, lr_check, false)) return rc;
+    if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
+    if (n == 0) return RELOC_OK;
+    // the planes go to the device as they lie at the caller's, padding included, and the kernel walks the caller's stride
+    const int64_t bytes = (int64_t)(h - 1) * stride + w;
+    HostStaging st{ctx};
+    uint8_t *dl = st.slot<uint8_t>(0, bytes), *dr = st.slot<uint8_t>(1, bytes);
+    float *dxy = st.upload_slot(2, xy, (int64_t)n * 2);
+    uint8_t *out = st.slot<uint8_t>(3, (int64_t)n * 7);
+    if (st.rc) return st.finish();
+    float *o_disp = (float *)out;
+    uint16_t *o_mm = (uint16_t *)(out + (int64_t)n * 4);
+    uint8_t *o_st = out + (int64_t)n * 6;
+    st.upload(dl, left, bytes);
+    st.upload(dr, right, bytes);
+    const StereoParams p = {fx, baseline_m, w, h, min_disparity, num_disparities, uniqueness, lr_check};
+    st.run([&] { return stereo_launch(ctx, dl, stride, dr, stride, dxy, nullptr, n, p, o_mm, o_disp, o_st); });
+    st.download(disparity, o_disp, (int64_t)n * 4);
+    st.download(depth_mm, o_mm, (int64_t)n * 2);
+    st.download(status, o_st, n);
+    return st.finish();
+}
+
+int stereo_frame(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img_right_dev, int w, int h, int order, int *ww, int *wh)
+{
+    StereoState &s = ctx->stereo;
+    if (!s.on()) { reloc_set_error("stereo is off on this context (reloc_set_stereo)"); return RELOC_E_STATE; }
+    if (right == ctx) { reloc_set_error("bad argument: the right eye needs a context of its own"); return RELOC_E_ARG; }
+    if (right->device != ctx->device || right->prm.gray_coeff_bits != ctx->prm.gray_coeff_bits) {
+        reloc_set_error("stereo: the right eye's context is on another device or has another gray_coeff_bits");
+        return RELOC_E_STATE;
+    }
+    if (w > right->max_w || h > right->max_h || w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
+    reloc_ctx *pair[2] = {ctx, right};
+    *ww = w; *wh = h;
+    if (int rc = image_chain_check(pair, 2, true, ww, wh)) return rc;
+    if (int rc = image_chain_check_prepared(pair, 1, 2, true, *ww, *wh)) return rc;
+    if (ctx->orb.w != *ww || ctx->orb.h != *wh) {
+        reloc_set_error("stereo: the left eye's last ORB frame is %dx%d, the right eye's working frame %dx%d", ctx->orb.w, ctx->orb.h, *ww, *wh);
+        return RELOC_E_STATE;
+    }
+    // the right eye's chain on its own stream, behind what ctx's stream holds so far: the copy that brought the right frame
+    // (a _dev caller orders its frames on ctx's stream) and the last stereo kernel, which still reads the chain's planes
+    HIP_TRY(hipEventRecord(s.left_ready, ctx->stream));
+    HIP_TRY(hipStreamWaitEvent(right->stream, s.left_ready, 0));
+    const uint8_t *src = img_right_dev, *planes[RELOC_BATCH_MAX];
+    const uint8_t *const *srcs = &src;
+    int stride = w * image_chain_frame_bpp(right), channels = 1;
+    if (int rc = image_chain_gray(&right, 1, true, &srcs, w, h, *ww, *wh, &stride, &channels, gray_flags(right, order), planes)) return rc;
+    const uint8_t *rplane = srcs[0];
+    if (channels == 3) {       // no stage ran on a 3-channel frame
+        if (int rc = image_gray_plain(right, rplane, *ww, *wh, stride, order, s.plane)) return rc;
+        rplane = s.plane; stride = *ww;
+    }
+    HIP_TRY(hipEventRecord(s.right_done, right->stream));
+    HIP_TRY(hipStreamWaitEvent(ctx->stream, s.right_done, 0));
+    const OrbLevel &L0 = ctx->orb.tab.lev[0];       // level 0 of the pyramid is the chain's output (the blurred levels live in buf.blur)
+    const StereoParams p = {ctx->cam.K4[0], s.baseline, *ww, *wh, s.min_disp, s.num_disp, s.uniq, s.lr};
+    if (int rc = stereo_launch(ctx, ctx->orb.buf.pyr + L0.off, L0.stride, rplane, stride, ctx->orb.buf.f_xy, ctx->orb.buf.f_count,
+                               ctx->max_feat, p, s.mm, s.disp, s.status)) return rc;
+    s.ran = true;
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_stereo_debug(reloc_ctx *ctx, uint16_t *depth_mm, float *disparity, uint8_t *status, int32_t *n)
+{
+    ARG_CHECK_CTX(ctx, n, "reloc_stereo_debug");
+    const StereoState &s = ctx->stereo;
+    if (!s.disp || !s.ran) { reloc_set_error("no stereo pass on this context yet"); return RELOC_E_STATE; }
+    int32_t k = 0;
+    HIP_TRY(hipMemcpyAsync(&k, ctx->orb.buf.f_count, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    k = k < ctx->max_feat ? k : ctx->max_feat;
+    if (k > 0) {
+        if (depth_mm) HIP_TRY(hipMemcpyAsync(depth_mm, s.mm, (size_t)k * 2, hipMemcpyDeviceToHost, ctx->stream));
+        if (disparity) HIP_TRY(hipMemcpyAsync(disparity, s.disp, (size_t)k * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (status) HIP_TRY(hipMemcpyAsync(status, s.status, (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    *n = k;
+    return RELOC_OK;
+}

@@ -568,6 +568,74 @@ class Engine:
         k = n.value
         return dict(xy=xy[:k].copy(), desc=desc[:k].copy(), pts3d=pts[:k].copy(), kp_index=idx[:k].copy(), n=k, n_kp=nk.value)
 
+    # ------------------------------------------------------------------ sparse stereo depth (reloc_spec.h "STEREO")
+    def set_stereo(self, baseline_m: float | None = None, min_disparity: int = 0, num_disparities: int = 128, uniqueness: int = 15,
+                   lr_check: bool = True):
+        """sparse stereo depth of this (the left eye's) engine (reloc_set_stereo); baseline_m=None or 0 turns it off"""
+        N.check(self._lib.reloc_set_stereo(self._ctx, 0.0 if baseline_m is None else float(baseline_m), int(min_disparity),
+                                           int(num_disparities), int(uniqueness), int(bool(lr_check))), "reloc_set_stereo")
+
+    def get_stereo(self):
+        """None when off, else dict(baseline_m, min_disparity, num_disparities, uniqueness, lr_check)"""
+        b = C.c_double(); md = C.c_int32(); nd = C.c_int32(); un = C.c_int32(); lr = C.c_int32()
+        N.check(self._lib.reloc_get_stereo(self._ctx, C.byref(b), C.byref(md), C.byref(nd), C.byref(un), C.byref(lr)), "reloc_get_stereo")
+        if b.value == 0.0:
+            return None
+        return dict(baseline_m=b.value, min_disparity=md.value, num_disparities=nd.value, uniqueness=un.value, lr_check=bool(lr.value))
+
+    def stereo_depth(self, left: np.ndarray, right: np.ndarray, xy, fx: float, baseline_m: float, min_disparity: int = 0,
+                     num_disparities: int = 128, uniqueness: int = 15, lr_check: bool = True):
+        """(depth_mm (n,) uint16, disparity (n,) float32, status (n,) uint8) of the keypoints xy (n, 2) on two rectified (H, W)
+        uint8 planes with explicit parameters (reloc_stereo_depth); the planes may be row-strided views of one stride"""
+        left = np.asarray(left); right = np.asarray(right)
+        if left.dtype != np.uint8 or right.dtype != np.uint8 or left.ndim != 2 or left.shape != right.shape:
+            raise N.RelocError("stereo_depth: expected two (H, W) uint8 planes of one size")
+        if left.strides[1] != 1 or left.strides[0] < left.shape[1] or right.strides != left.strides:
+            left = np.ascontiguousarray(left); right = np.ascontiguousarray(right)
+        h, w = left.shape
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        n = len(xy)
+        mm = np.zeros(n, np.uint16); disp = np.zeros(n, np.float32); st = np.zeros(n, np.uint8)
+        N.check(self._lib.reloc_stereo_depth(self._ctx, C.c_void_p(left.ctypes.data), C.c_void_p(right.ctypes.data), w, h,
+                                             left.strides[0], N.ptr(xy), n, float(fx), float(baseline_m), int(min_disparity),
+                                             int(num_disparities), int(uniqueness), int(bool(lr_check)), N.ptr(mm), N.ptr(disp),
+                                             N.ptr(st)), "reloc_stereo_depth")
+        return mm, disp, st
+
+    def record_frame_stereo(self, bgr: np.ndarray, right_frame: np.ndarray, right_engine: "Engine", nfeatures: int = 500,
+                            order_rgb: bool = False):
+        """record_frame with the right eye's frame in the depth image's place (reloc_record_frame_stereo): right_engine
+        carries that eye's image chain.  The dict of record_frame plus n_stereo, the keypoints with a stereo depth."""
+        bgr = self._frame(bgr, "record_frame_stereo")
+        right_frame = right_engine._frame(right_frame, "record_frame_stereo (right)")
+        h, w = bgr.shape[:2]
+        if right_frame.shape[:2] != (h, w):
+            raise N.RelocError("record_frame_stereo: left and right sizes differ")
+        mf = self.max_feat
+        xy = np.empty((mf, 2), np.float32); desc = np.empty((mf, 32), np.uint8); pts = np.empty((mf, 3), np.float32)
+        idx = np.empty(mf, np.int32); n = C.c_int32(); nk = C.c_int32(); ns = C.c_int32()
+        N.check(self._lib.reloc_record_frame_stereo(self._ctx, right_engine._ctx, N.ptr(bgr), N.ptr(right_frame), w, h,
+                                                    int(order_rgb), int(nfeatures), N.ptr(xy), N.ptr(desc), N.ptr(pts),
+                                                    N.ptr(idx), C.byref(n), C.byref(nk), C.byref(ns)), "reloc_record_frame_stereo")
+        k = n.value
+        return dict(xy=xy[:k].copy(), desc=desc[:k].copy(), pts3d=pts[:k].copy(), kp_index=idx[:k].copy(), n=k, n_kp=nk.value,
+                    n_stereo=ns.value)
+
+    def tick_accumulate_stereo_dev(self, right_engine: "Engine", img_right_dev: int, w: int, h: int, base_pose, silence_ok: bool,
+                                   order_rgb: bool = False):
+        """tick_accumulate_dev with the right eye's frame (device memory) in the depth image's place; enqueues only"""
+        bp = np.ascontiguousarray(base_pose, np.float64).reshape(7)
+        N.check(self._lib.reloc_tick_accumulate_stereo_dev(self._ctx, right_engine._ctx, C.c_void_p(img_right_dev), w, h,
+                                                           int(order_rgb), N.ptr(bp), int(silence_ok)),
+                "reloc_tick_accumulate_stereo_dev")
+
+    def stereo_debug(self):
+        """(depth_mm, disparity, status) of the last stereo pass, per keypoint of the frame's ORB output"""
+        mf = self.max_feat
+        mm = np.zeros(mf, np.uint16); disp = np.zeros(mf, np.float32); st = np.zeros(mf, np.uint8); n = C.c_int32()
+        N.check(self._lib.reloc_stereo_debug(self._ctx, N.ptr(mm), N.ptr(disp), N.ptr(st), C.byref(n)), "reloc_stereo_debug")
+        return mm[:n.value].copy(), disp[:n.value].copy(), st[:n.value].copy()
+
     def frame_debug_plane(self, what: int, level: int) -> np.ndarray:
         buf = np.empty(self.max_w * self.max_h, np.uint8)
         w = C.c_int32(); h = C.c_int32()

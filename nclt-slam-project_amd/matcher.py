@@ -73,6 +73,9 @@ class MatcherConfig:
     accum_silence_s: float = 5.0
     accum_min_dist_m: float = 5.0
     accum_min_kpts: int = 30
+    # a stereo.StereoRig: tick(..., right=frame) then accumulates from the right eye's frame when no depth image is given
+    # (include/reloc_spec.h "STEREO"); None = accumulation needs a depth image, as in the reference
+    stereo: object | None = None
 
     @property
     def front_end(self) -> FrontEnd:
@@ -230,6 +233,8 @@ class LandmarkMatcherCore(_MatcherSession):
         self.chain = c = ImageChain(cv2, self.cfg.front_end, self.cfg.nfeatures)
         self.orb, self.dist, self.rectify = c.orb, c.dist, c.rectify
         self.matcher = cv2.BFMatcher(cv2.NORM_HAMMING, crossCheck=self.match_policy == "cross")
+        rig = self.cfg.stereo
+        self.right_chain = None if rig is None else ImageChain(cv2, rig.right_front_end(self.cfg.front_end), self.cfg.nfeatures)
         self._open_csv(log_csv)
 
     # ------------------------------------------------------------------ database
@@ -317,9 +322,10 @@ class LandmarkMatcherCore(_MatcherSession):
         cam_world = (float(t_wc[0]), float(t_wc[1]), float(t_wc[2]), *q)
         return len(inliers), err, P.cam_world_to_base_world(cam_world, self.base_to_cam_t, self.base_to_cam_R)
 
-    def tick(self, bgr, depth_mm, base_pose, ts=None, drift_est=0.0):
+    def tick(self, bgr, depth_mm, base_pose, ts=None, drift_est=0.0, right=None):
         """One repeat attempt.  bgr: (H,W,3) u8, the (H,W) u8 mosaic of a raw camera (cfg.bayer), or a frame of
-        cfg.pixel_format; depth_mm: (H,W) u16 or None; base_pose: 7-tuple."""
+        cfg.pixel_format; depth_mm: (H,W) u16 or None; base_pose: 7-tuple.  right: with cfg.stereo, the right eye's frame;
+        the accumulation then takes the depth of the keypoints from it when depth_mm is None."""
         cfg = self.cfg
         self.maybe_swap_to_return()
         if bgr is None or base_pose is None:
@@ -328,7 +334,12 @@ class LandmarkMatcherCore(_MatcherSession):
         self.n_attempts += 1
         vio_xy = (base_pose[0], base_pose[1])
         cand, d, herr = self.select_candidates(base_pose)
-        kpts, desc, depth_mm = self.chain.features(bgr, depth_mm)
+        stereo = cfg.stereo is not None and right is not None and depth_mm is None
+        if stereo:
+            gray, _ = self.chain.apply(bgr)
+            kpts, desc = self.chain.orb.detectAndCompute(gray, self.chain.mask)
+        else:
+            kpts, desc, depth_mm = self.chain.features(bgr, depth_mm)
         if desc is None or len(kpts) < cfg.min_matches:
             return self._outcome(ts, vio_xy, 1, len(cand))
         pts2d = np.array([k.pt for k in kpts], dtype=np.float32)
@@ -349,26 +360,39 @@ class LandmarkMatcherCore(_MatcherSession):
             fail = not relocating and math.hypot(anchor[0] - vio_xy[0], anchor[1] - vio_xy[1]) > cfg.consistency_m
             o = self._outcome(ts, vio_xy, 4 if fail else 0, len(cand), n_inl, err, anchor, lm_idx, relocating)
         if not o.published:
-            self.maybe_accumulate(base_pose, desc, pts2d, depth_mm, ts)
+            if stereo:
+                # the millimetres of the keypoints from the right eye, worked out only where the accumulation asks for them
+                def kp_mm():
+                    from .stereo import shim_backend
+                    gray_r, _ = self.right_chain.apply(right)
+                    return cfg.stereo.keypoint_depth_mm(shim_backend(self.cv2), gray, gray_r, pts2d, cfg.fx), gray.shape
+                self.maybe_accumulate(base_pose, desc, pts2d, None, ts, kp_mm)
+            else:
+                self.maybe_accumulate(base_pose, desc, pts2d, depth_mm, ts)
         return o
 
     # ------------------------------------------------------------------ accumulation (M:435-500)
-    def maybe_accumulate(self, base_pose, desc_curr, pts2d, depth_mm, ts):
+    def maybe_accumulate(self, base_pose, desc_curr, pts2d, depth_mm, ts, kp_mm=None):
+        """kp_mm: in place of the depth image, a callable giving (uint16 millimetres per keypoint, (H, W) of the working
+        frame): the stereo depth"""
         cfg = self.cfg
         if not cfg.accum_enable or ts - self.last_anchor_ts < cfg.accum_silence_s:
             return False
         if len(self.xy) and np.linalg.norm(self.xy - np.array([base_pose[0], base_pose[1]]), axis=1).min() < cfg.accum_min_dist_m:
             return False
-        if depth_mm is None or len(pts2d) == 0:
+        if (depth_mm is None and kp_mm is None) or len(pts2d) == 0:
             return False
-        H, W = depth_mm.shape
+        if depth_mm is None:
+            mm, (H, W) = kp_mm()
+        else:
+            H, W = depth_mm.shape
         uu = np.round(pts2d[:, 0]).astype(np.int32)
         vv = np.round(pts2d[:, 1]).astype(np.int32)
         inside = (uu >= 1) & (uu < W - 1) & (vv >= 1) & (vv < H - 1)
         uu, vv, p2, dsc = uu[inside], vv[inside], pts2d[inside], desc_curr[inside]
         if len(uu) == 0:
             return False
-        z = depth_mm[vv, uu].astype(np.float32) / 1000.0
+        z = (mm[inside] if depth_mm is None else depth_mm[vv, uu]).astype(np.float32) / 1000.0
         ok = (z > 0.5) & (z < 15.0)
         if ok.sum() < cfg.accum_min_kpts:
             return False
@@ -420,6 +444,11 @@ class FusedLandmarkMatcher(_MatcherSession):
         e.set_camera([cfg.fx, cfg.fy, cfg.cx, cfg.cy], data.get("base_to_cam_translation", P.BASE_TO_CAM_TRANSLATION),
                      data.get("base_to_cam_rot", P.BASE_TO_CAM_ROT))
         cfg.front_end.configure(e)
+        self.right_engine = None
+        if cfg.stereo is not None:
+            cfg.stereo.configure(e)
+            self.right_engine = cfg.stereo.right_engine(e, cfg.front_end)
+        self._right_dev = self._right_cap = 0
         self._return_data = None
         e.db_select(0)
         if return_landmarks is not None:
@@ -451,24 +480,43 @@ class FusedLandmarkMatcher(_MatcherSession):
     def _stage(self, which, arr):
         """device staging buffer of the frame / depth image, grown on demand; returns the device pointer"""
         e = self.engine
-        ptr, cap = (self._img_dev, self._img_cap) if which == "img" else (self._depth_dev, self._depth_cap)
+        ptr, cap = ((self._img_dev, self._img_cap) if which == "img" else (self._depth_dev, self._depth_cap) if which == "depth"
+                    else (self._right_dev, self._right_cap))
         if cap < arr.nbytes:
             if ptr:
                 e.dev_free(ptr)
             ptr, cap = e.dev_alloc(arr.nbytes), arr.nbytes
             if which == "img":
                 self._img_dev, self._img_cap = ptr, cap
-            else:
+            elif which == "depth":
                 self._depth_dev, self._depth_cap = ptr, cap
+            else:
+                self._right_dev, self._right_cap = ptr, cap
         e.h2d_async(ptr, arr)
         return ptr
 
-    def tick(self, bgr, base_pose, ts=None, global_reloc=None, depth_mm=None, drift_est=0.0):
+    def close(self):
+        """releases what this matcher made on the device: its staging buffers (frame, depth, right frame) and, with a stereo
+        rig, the right eye's Engine.  The Engine it ticks on stays open: it may be the caller's.  Without a call the buffers
+        live as long as that Engine, and the right eye's Engine until its own finaliser runs."""
+        e = self.engine
+        e.sync()
+        for name in ("_img", "_depth", "_right"):
+            if getattr(self, name + "_dev"):
+                e.dev_free(getattr(self, name + "_dev"))
+            setattr(self, name + "_dev", 0)
+            setattr(self, name + "_cap", 0)
+        if self.right_engine is not None:
+            self.right_engine.close()
+            self.right_engine = None
+
+    def tick(self, bgr, base_pose, ts=None, global_reloc=None, depth_mm=None, drift_est=0.0, right=None):
         """One repeat attempt.  global_reloc: None = decide as the reference does (local candidates; the whole-database
         search only under G's trigger, when cfg.global_reloc is set), True = whole-database search unconditionally
         (benchmark shape), False = local only.  depth_mm enables accumulation (cfg.accum_enable).  bgr: (H,W,3) u8, or with
         cfg.bayer the (H,W) u8 mosaic of the raw camera: a third of the bytes to upload; with cfg.pixel_format an (H,W) mono8,
-        (H,W,4) BGRA / RGBA or (H,W,2) YUYV / UYVY frame."""
+        (H,W,4) BGRA / RGBA or (H,W,2) YUYV / UYVY frame.  right: with cfg.stereo, the right eye's frame (same shape): it
+        enables accumulation when no depth_mm is given."""
         cfg, e = self.cfg, self.engine
         self.maybe_swap_to_return()
         if bgr is None or base_pose is None:
@@ -486,8 +534,15 @@ class FusedLandmarkMatcher(_MatcherSession):
                              if cfg.pixel_format else "tick: expected an (H, W, 3) frame")
         h, w = bgr.shape[:2]
         e.tick_dev(self._stage("img", bgr), w, h, base_pose, order_rgb=False, global_reloc=mode, seed=self.seed)
-        accumulate = cfg.accum_enable and depth_mm is not None
-        if accumulate:
+        stereo = cfg.stereo is not None and right is not None and depth_mm is None
+        accumulate = cfg.accum_enable and (depth_mm is not None or stereo)
+        if stereo and accumulate:
+            right = np.ascontiguousarray(right, np.uint8)
+            if right.shape != bgr.shape:
+                raise ValueError("left and right frames differ in shape")
+            e.tick_accumulate_stereo_dev(self.right_engine, self._stage("right", right), w, h, base_pose,
+                                         silence_ok=not (ts - self.last_anchor_ts < cfg.accum_silence_s))
+        elif accumulate:
             depth_mm = np.ascontiguousarray(depth_mm, np.uint16)
             if depth_mm.shape != (h, w):
                 raise ValueError("depth and colour sizes differ")

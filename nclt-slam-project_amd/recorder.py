@@ -41,10 +41,12 @@ def local_depth_std(depth_mm, uu, vv):
 
 class LandmarkRecorderCore:
     def __init__(self, out_pkl=None, min_disp_m: float = 2.0, cv2=None, nfeatures: int = 500, logger=None, engine=None,
-                 dist=(), clahe=None, rectify=None, resize=None, bayer=None, mask=None, orb=None, pixel_format=None):
+                 dist=(), clahe=None, rectify=None, resize=None, bayer=None, mask=None, orb=None, pixel_format=None, stereo=None):
         """engine: when given, ORB + all per-keypoint gates + back-projection run in ONE device call
         (reloc_record_frame); otherwise the gates run in NumPy on the cv2-shaped module's features.
-        dist, clahe, rectify, resize, bayer, mask, orb, pixel_format: the camera front end, as front_end.FrontEnd describes them."""
+        dist, clahe, rectify, resize, bayer, mask, orb, pixel_format: the camera front end, as front_end.FrontEnd describes them.
+        stereo: a stereo.StereoRig -- tick() then takes the right eye's frame in the depth image's place (a camera without a
+        depth sensor); both eyes share the front end, the right one with the rig's rectification."""
         self.engine = engine
         self.front_end = fe = FrontEnd(dist, clahe, rectify, resize, bayer, mask, orb, pixel_format)
         if engine is not None:
@@ -56,21 +58,33 @@ class LandmarkRecorderCore:
         self.out_pkl = out_pkl
         self.min_disp_m = float(min_disp_m)
         self.chain = None if engine is not None else ImageChain(cv2, fe, nfeatures)
+        self.stereo = stereo
+        self.right_engine = self.right_chain = None
+        if stereo is not None and engine is not None:
+            stereo.configure(engine)
+            self.right_engine = stereo.right_engine(engine, fe)
+        elif stereo is not None:
+            self.right_chain = ImageChain(cv2, stereo.right_front_end(fe), nfeatures)
         self.landmarks = []
         self.last_landmark_pose_world = None
         self.log = logger or (lambda msg: None)
 
-    def tick(self, bgr, depth_mm, base_pose, rgb_ts=0.0):
-        """Returns the appended record, or None when nothing was recorded this tick."""
-        if bgr is None or depth_mm is None or base_pose is None:
+    def tick(self, bgr, depth_mm, base_pose, rgb_ts=0.0, right=None):
+        """Returns the appended record, or None when nothing was recorded this tick.  right: with a stereo rig, the right
+        eye's frame; depth_mm may then be None (and is ignored)."""
+        use_stereo = self.stereo is not None and right is not None
+        if bgr is None or (depth_mm is None and not use_stereo) or base_pose is None:
             return None
         cam_pose = P.base_to_cam_world(*base_pose)
         if self.last_landmark_pose_world is not None:
             lx, ly = self.last_landmark_pose_world[0], self.last_landmark_pose_world[1]
             if math.hypot(cam_pose[0] - lx, cam_pose[1] - ly) < self.min_disp_m:
                 return None
+        if use_stereo and self.engine is None:
+            return self._tick_stereo_host(bgr, right, cam_pose, rgb_ts)
         if self.engine is not None:
-            r = self.engine.record_frame(bgr, depth_mm, self.nfeatures)
+            r = (self.engine.record_frame_stereo(bgr, right, self.right_engine, self.nfeatures) if use_stereo
+                 else self.engine.record_frame(bgr, depth_mm, self.nfeatures))
             if r["n"] < MIN_RECORD_KPTS:
                 return None
             rec = {"pose": cam_pose, "descriptors": r["desc"], "keypoints_2d": r["xy"], "keypoints_3d_cam": r["pts3d"],
@@ -99,6 +113,37 @@ class LandmarkRecorderCore:
         self.landmarks.append(rec)
         self.last_landmark_pose_world = cam_pose
         return rec
+
+    def _tick_stereo_host(self, bgr, right, cam_pose, rgb_ts):
+        """the cv2-shaped path of a stereo tick: both frames through their chains, keypoints on the left, their millimetres
+        from the backend's stereo kernel, the gates in NumPy (no 3x3 variance gate on a per-keypoint depth)"""
+        from .stereo import record_gates, shim_backend
+        gray, _ = self.chain.apply(bgr)
+        gray_r, _ = self.right_chain.apply(right)
+        kpts, desc = self.chain.orb.detectAndCompute(gray, self.chain.mask)
+        if desc is None or len(kpts) == 0:
+            return None
+        xy = np.array([k.pt for k in kpts], dtype=np.float32)
+        mm = self.stereo.keypoint_depth_mm(shim_backend(self.cv2), gray, gray_r, xy, FX)
+        uu = np.round(xy[:, 0]).astype(np.int32)
+        vv = np.round(xy[:, 1]).astype(np.int32)
+        hh, ww = gray.shape
+        ok, z = record_gates(uu, vv, mm, ww, hh, DEPTH_MIN_M, DEPTH_MAX_M, GROUND_Y_THRESHOLD)
+        if ok.sum() < MIN_RECORD_KPTS:
+            return None
+        pts3 = P.back_project(self.cv2, uu[ok], vv[ok], z[ok], FX, FY, CX, CY, self.chain.dist)
+        rec = {"pose": cam_pose, "descriptors": desc[ok], "keypoints_2d": xy[ok], "keypoints_3d_cam": pts3,
+               "ts": rgb_ts, "n_features": int(len(pts3))}
+        self.landmarks.append(rec)
+        self.last_landmark_pose_world = cam_pose
+        return rec
+
+    def close(self):
+        """closes the right eye's Engine, which this recorder made (a stereo rig on the device path); the left Engine stays
+        the caller's.  Without a call the Engine's own finaliser releases it."""
+        if self.right_engine is not None:
+            self.right_engine.close()
+            self.right_engine = None
 
     def database(self) -> dict:
         return new_database(self.landmarks, W, H, FX, FY, CX, CY)

@@ -3,6 +3,9 @@
     VisualLandmarkMatcher(pkl_path, log_csv)            --landmarks --out-csv [--landmarks-return --swap-flag]
                                                         [--match-policy {cross,ratio} --lowe-ratio R]
     VisualLandmarkRecorder(out_pkl, min_disp_m=2.0)     --out --min-disp
+    both, for a rectified stereo pair without a depth sensor:
+                                                        [--stereo-baseline M --stereo-num-disparities N
+                                                         --stereo-rectify-right FILE.npz --right-topic NAME]
 
 (reference simulation/isaac/scripts/common/visual_landmark_matcher.py:175-231,503-530,
  visual_landmark_recorder.py:154-179,375-392 and the exp-69 variant's extra flags).  They only move
@@ -20,7 +23,9 @@ import numpy as np
 from .front_end import PIXEL_FORMATS, add_front_end_flags, front_end_flags, load_mask, pixel_format_setting  # noqa: F401  (load_mask: part of this module's interface)
 from .matcher import FusedLandmarkMatcher, LandmarkMatcherCore, MatcherConfig
 from .recorder import LandmarkRecorderCore
+from .stereo import StereoRig
 
+RIGHT_TOPIC = "/camera/right/image_raw"      # --right-topic: the right eye of a stereo rig (--stereo-baseline)
 TICK_HZ = 2.0
 POSE_FILE = "/tmp/isaac_pose.txt"
 DRIFT_FILE = "/tmp/drift_est.txt"
@@ -95,12 +100,14 @@ def _node_base():
 
 
 def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global_reloc=False, fused=False, cv2=None, bayer=None,
-                      mask=None, orb=None, pixel_format=None, match_policy="cross", lowe_ratio=0.8):
+                      mask=None, orb=None, pixel_format=None, match_policy="cross", lowe_ratio=0.8, stereo=None,
+                      right_topic=RIGHT_TOPIC):
     """cv2: the cv2-shaped module the ROS-free core calls (default: the HIP shim); only the non-fused core uses it.
     bayer: FrontEnd.bayer -- the colour topic carries raw mosaics, passed through undecoded.  mask: FrontEnd.mask.
     orb: FrontEnd.orb.  pixel_format: FrontEnd.pixel_format -- the colour topic carries frames of that format, passed through
     undecoded.  match_policy, lowe_ratio: MatcherConfig's -- "cross" (the reference matcher's crossCheck) or "ratio" (knnMatch
-    + Lowe test)"""
+    + Lowe test).  stereo: MatcherConfig.stereo, a StereoRig -- the right eye's frames come from right_topic (same encoding as the
+    colour topic) and stand in for the depth image where none has arrived"""
     from geometry_msgs.msg import PoseWithCovarianceStamped
     from sensor_msgs.msg import Image
     Node = _node_base()
@@ -109,7 +116,7 @@ def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global
         def __init__(self):
             super().__init__("visual_landmark_matcher")
             cfg = MatcherConfig(global_reloc=global_reloc, bayer=bayer, mask=mask, orb=orb, pixel_format=pixel_format,
-                                match_policy=match_policy, lowe_ratio=lowe_ratio)
+                                match_policy=match_policy, lowe_ratio=lowe_ratio, stereo=stereo)
             if fused:
                 self.core = FusedLandmarkMatcher(pkl_path, log_csv, config=cfg, return_landmarks=return_pkl,
                                                  swap_flag=swap_flag, logger=lambda m: self.get_logger().info(m),
@@ -117,9 +124,11 @@ def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global
             else:
                 self.core = LandmarkMatcherCore(pkl_path, log_csv, cv2=cv2, config=cfg, return_landmarks=return_pkl,
                                                 swap_flag=swap_flag, logger=lambda m: self.get_logger().info(m))
-            self.last_rgb = self.last_depth = None
+            self.last_rgb = self.last_depth = self.last_right = None
             self.create_subscription(Image, "/camera/color/image_raw", self._rgb_cb, 10)
             self.create_subscription(Image, "/camera/depth/image_rect_raw", self._depth_cb, 10)
+            if stereo is not None:
+                self.create_subscription(Image, right_topic, self._right_cb, 10)
             self.anchor_pub = self.create_publisher(PoseWithCovarianceStamped, "/anchor_correction", 10)
             self.timer = self.create_timer(1.0 / TICK_HZ, self._tick)
             signal.signal(signal.SIGTERM, self._sigterm)
@@ -140,16 +149,23 @@ def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global
             except Exception as e:
                 self.get_logger().warn(f"depth: {e}")
 
+        def _right_cb(self, msg):
+            try:
+                self.last_right = img_msg_to_frame(msg, bayer, pixel_format)
+            except Exception as e:
+                self.get_logger().warn(f"right: {e}")
+
         def _tick(self):
-            if self.last_rgb is None or self.last_depth is None:
+            if self.last_rgb is None or (self.last_depth is None and self.last_right is None):
                 return
             pose = read_pose_file()
             if pose is None:
                 return
+            kw = {} if stereo is None else {"right": self.last_right}
             if fused:
-                o = self.core.tick(self.last_rgb, pose, depth_mm=self.last_depth, drift_est=read_drift())
+                o = self.core.tick(self.last_rgb, pose, depth_mm=self.last_depth, drift_est=read_drift(), **kw)
             else:
-                o = self.core.tick(self.last_rgb, self.last_depth, pose, drift_est=read_drift())
+                o = self.core.tick(self.last_rgb, self.last_depth, pose, drift_est=read_drift(), **kw)
             if o is None or not o.published:
                 return
             msg = PoseWithCovarianceStamped()
@@ -164,18 +180,23 @@ def make_matcher_node(pkl_path, log_csv, return_pkl=None, swap_flag=None, global
     return VisualLandmarkMatcher()
 
 
-def make_recorder_node(out_pkl, min_disp_m=2.0, cv2=None, bayer=None, mask=None, orb=None, pixel_format=None):
+def make_recorder_node(out_pkl, min_disp_m=2.0, cv2=None, bayer=None, mask=None, orb=None, pixel_format=None, stereo=None,
+                       right_topic=RIGHT_TOPIC):
+    """stereo: a StereoRig -- the recorder takes the right eye's frames from right_topic in the depth image's place"""
     from sensor_msgs.msg import Image
     Node = _node_base()
 
     class VisualLandmarkRecorder(Node):
         def __init__(self):
             super().__init__("visual_landmark_recorder")
-            self.core = LandmarkRecorderCore(out_pkl, min_disp_m, cv2=cv2, bayer=bayer, mask=mask, orb=orb, pixel_format=pixel_format)
-            self.last_rgb = self.last_depth = None
+            self.core = LandmarkRecorderCore(out_pkl, min_disp_m, cv2=cv2, bayer=bayer, mask=mask, orb=orb, pixel_format=pixel_format,
+                                             **({} if stereo is None else {"stereo": stereo}))
+            self.last_rgb = self.last_depth = self.last_right = None
             self.last_rgb_ts = 0.0
             self.create_subscription(Image, "/camera/color/image_raw", self._rgb_cb, 10)
             self.create_subscription(Image, "/camera/depth/image_rect_raw", self._depth_cb, 10)
+            if stereo is not None:
+                self.create_subscription(Image, right_topic, self._right_cb, 10)
             self.timer = self.create_timer(0.2, self._tick)
             signal.signal(signal.SIGTERM, self._save_and_exit)
             signal.signal(signal.SIGINT, self._save_and_exit)
@@ -193,8 +214,17 @@ def make_recorder_node(out_pkl, min_disp_m=2.0, cv2=None, bayer=None, mask=None,
             except Exception as e:
                 self.get_logger().warn(f"depth cb: {e}")
 
+        def _right_cb(self, msg):
+            try:
+                self.last_right = img_msg_to_frame(msg, bayer, pixel_format)
+            except Exception as e:
+                self.get_logger().warn(f"right cb: {e}")
+
         def _tick(self):
-            self.core.tick(self.last_rgb, self.last_depth, read_pose_file(), self.last_rgb_ts)
+            if stereo is None:
+                self.core.tick(self.last_rgb, self.last_depth, read_pose_file(), self.last_rgb_ts)
+            else:
+                self.core.tick(self.last_rgb, self.last_depth, read_pose_file(), self.last_rgb_ts, right=self.last_right)
 
         def _save_and_exit(self, *a):
             self.core.save()
@@ -210,6 +240,28 @@ def _chain_args(args):
     while tail and tail[-1] is None:
         tail.pop()
     return tuple(tail)
+
+
+def add_stereo_flags(ap):
+    """--stereo-baseline, --stereo-num-disparities, --stereo-rectify-right, --right-topic: a StereoRig beside the front end"""
+    ap.add_argument("--stereo-baseline", type=float, default=None, metavar="M",
+                    help="baseline of a rectified stereo pair in metres: the right eye's frames stand in for the depth image")
+    ap.add_argument("--stereo-num-disparities", type=int, default=128, metavar="N", help="searched disparities, 8..256 (default 128)")
+    ap.add_argument("--stereo-rectify-right", default=None, metavar="FILE.npz",
+                    help="the right eye's rectification maps: an .npz file holding map1 and map2 as cv2.remap takes them")
+    ap.add_argument("--right-topic", default=RIGHT_TOPIC, metavar="NAME", help="topic of the right eye's frames")
+
+
+def _stereo_kwargs(args):
+    """the stereo keywords of the node factories: nothing without --stereo-baseline (a bad value: ValueError)"""
+    if args.stereo_baseline is None:
+        return {}
+    maps = None
+    if args.stereo_rectify_right is not None:
+        with np.load(args.stereo_rectify_right, allow_pickle=False) as z:
+            maps = (z["map1"], z["map2"])
+    return dict(stereo=StereoRig(args.stereo_baseline, num_disparities=args.stereo_num_disparities, rectify_right=maps),
+                right_topic=args.right_topic)
 
 
 def _match_args(args, raw):
@@ -251,12 +303,14 @@ def matcher_main(argv=None):
                     help="cross: mutual nearest neighbours (the reference matcher); ratio: knnMatch k=2 + Lowe test")
     ap.add_argument("--lowe-ratio", type=float, default=0.8, help="ratio of the Lowe test, in (0, 1]; read under --match-policy ratio")
     add_front_end_flags(ap)
+    add_stereo_flags(ap)
     args = ap.parse_args(argv)
     try:
         raw = _match_args(args, _chain_args(args))
+        kw = _stereo_kwargs(args)
     except ValueError as e:
         ap.error(str(e))
-    _spin(lambda: make_matcher_node(args.landmarks, args.out_csv, args.landmarks_return, args.swap_flag, args.global_reloc, args.fused, *raw),
+    _spin(lambda: make_matcher_node(args.landmarks, args.out_csv, args.landmarks_return, args.swap_flag, args.global_reloc, args.fused, *raw, **kw),
           "save_augmented")
 
 
@@ -265,6 +319,11 @@ def recorder_main(argv=None):
     ap.add_argument("--out", required=True)
     ap.add_argument("--min-disp", type=float, default=2.0)
     add_front_end_flags(ap)
+    add_stereo_flags(ap)
     args = ap.parse_args(argv)
     raw = _chain_args(args)
-    _spin(lambda: make_recorder_node(args.out, args.min_disp, *raw), "save")
+    try:
+        kw = _stereo_kwargs(args)
+    except ValueError as e:
+        ap.error(str(e))
+    _spin(lambda: make_recorder_node(args.out, args.min_disp, *raw, **kw), "save")

@@ -1,0 +1,88 @@
+"""Sparse stereo depth of the host layer (include/reloc_spec.h "STEREO"): the rig -- baseline, search range and gates, the
+right eye's rectification -- as `LandmarkRecorderCore(stereo=...)` and `MatcherConfig.stereo` take it, the right eye's Engine
+made from the left eye's front end, and the NumPy side of the per-keypoint depth gates for the cv2-shaped cores.
+
+A rig stands beside the `FrontEnd`, not inside it: both eyes share one front end (the same pixel format or Bayer code, resize
+and CLAHE; `fx` and the maps are those of the rectified working frame), and a host without a rig makes exactly the engine
+calls it always made.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, replace
+
+import numpy as np
+
+MIN_DISPARITY_MAX = 1024                  # RELOC_STEREO_MIN_DISPARITY_MAX
+NUM_DISPARITIES = (8, 256)                # RELOC_STEREO_NUM_DISP_MIN .. _MAX
+UNIQUENESS_MAX = 50                       # RELOC_STEREO_UNIQUENESS_MAX
+STATUS = ("ok", "border", "range", "edge", "uniqueness", "left-right", "far")       # RELOC_STEREO_OK ..
+
+
+@dataclass(frozen=True, eq=False)
+class StereoRig:
+    """A rectified stereo pair: a scene point lies on the same row of both working frames, at x_right = x_left - disparity.
+    baseline_m: distance of the two optical centres in metres.  min_disparity, num_disparities: the searched disparities
+    min_disparity .. min_disparity + num_disparities - 1 (pixels of the working frame).  uniqueness: percent by which the
+    best cost must beat the best one two or more disparities away.  lr_check: the match must be found again from the right.
+    rectify_right: the right eye's map pair, as `FrontEnd.rectify` takes the left one (None: the right frames are rectified
+    already, or use the left eye's maps being None too)."""
+    baseline_m: float
+    min_disparity: int = 0
+    num_disparities: int = 128
+    uniqueness: int = 15
+    lr_check: bool = True
+    rectify_right: tuple | None = None
+
+    def __post_init__(self):
+        b = float(self.baseline_m)
+        if not (np.isfinite(b) and b > 0.0):
+            raise ValueError("stereo: baseline_m must be finite and > 0 (metres)")
+        for name, lo, hi in (("min_disparity", 0, MIN_DISPARITY_MAX), ("num_disparities", *NUM_DISPARITIES), ("uniqueness", 0, UNIQUENESS_MAX)):
+            v = getattr(self, name)
+            if int(v) != v or not lo <= int(v) <= hi:
+                raise ValueError(f"stereo: {name} must be an integer in {lo}..{hi}")
+            object.__setattr__(self, name, int(v))
+        object.__setattr__(self, "baseline_m", b)
+        object.__setattr__(self, "lr_check", bool(self.lr_check))
+
+    def settings(self) -> dict:
+        """the keywords of Engine.set_stereo and, behind fx and baseline_m, of Engine.stereo_depth"""
+        return dict(baseline_m=self.baseline_m, min_disparity=self.min_disparity, num_disparities=self.num_disparities,
+                    uniqueness=self.uniqueness, lr_check=self.lr_check)
+
+    def right_front_end(self, front_end):
+        """the right eye's FrontEnd: the left one with this rig's rectification"""
+        return replace(front_end, rectify=self.rectify_right)
+
+    def configure(self, engine):
+        """the rig's setting on the left eye's Engine"""
+        engine.set_stereo(**self.settings())
+
+    def right_engine(self, engine, front_end):
+        """an Engine for the right eye, as large as the left one, on the same device, configured with the right eye's front end"""
+        # it never runs ORB: the smallest feature capacity that holds a new context's nfeatures (500)
+        right = type(engine)(engine.device, engine.max_w, engine.max_h, 512)
+        self.right_front_end(front_end).configure(right)
+        right.set_params(gray_coeff_bits=engine.get_params().gray_coeff_bits)      # both eyes convert to gray alike
+        return right
+
+    def keypoint_depth_mm(self, backend, left_gray, right_gray, xy, fx):
+        """uint16 millimetres per keypoint (0 = no depth) from two planes of the chain's output through the backend's kernel"""
+        return backend.stereo_depth(left_gray, right_gray, xy, fx, **self.settings())[0]
+
+
+def shim_backend(cv2):
+    """the Engine behind a cv2-shaped module: a Cv2Shim's backend, or the one of the module-level shim"""
+    b = getattr(cv2, "backend", None)
+    return b if b is not None else cv2.default_shim().backend
+
+
+def record_gates(uu, vv, kp_mm, w, h, depth_min_m, depth_max_m, ground_y=None):
+    """the recorder's / the accumulation's gates on a per-keypoint depth: border, [v > ground_y,] depth range; no 3 x 3
+    variance gate (reloc_spec.h).  Returns (keep, z) with z float32 metres."""
+    z = np.asarray(kp_mm, np.uint16).astype(np.float32) / 1000.0
+    keep = (uu >= 1) & (uu < w - 1) & (vv >= 1) & (vv < h - 1)
+    if ground_y is not None:
+        keep &= vv > ground_y
+    keep &= (z > depth_min_m) & (z < depth_max_m)
+    return keep, z
