@@ -16,10 +16,38 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = (os.environ.get("RELOC_LIB") if os.environ.get("RELOC_DEV") == "1" else None) or os.path.join(_HERE, "csrc", "libreloc_hip.so")
 
 c_ctx = C.c_void_p
-P = C.c_void_p
 i32, i64, u64, f32, f64 = C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double
 
-# name -> (restype, argtypes); mirrors include/reloc.h one to one
+
+class RelocError(RuntimeError):
+    """Raised for every failure of the native library (the cv2 shim re-raises it as cv2.error)."""
+
+
+class P:
+    """A pointer argument (every pointer or array parameter of include/reloc.h but `reloc_ctx *`) that converts itself:
+    a C-contiguous numpy array passes its data pointer and an out-parameter of outs() its address; None, an int address,
+    byref(...), a c_void_p and a ctypes array pass as a plain c_void_p argument takes them.  A strided array raises
+    RelocError: from ptr() and the checked view as it is, from a call of the raw library inside ctypes.ArgumentError,
+    which is how ctypes reports whatever a from_param raises."""
+
+    @classmethod
+    def from_param(cls, a):
+        if isinstance(a, np.ndarray):
+            if not a.flags.c_contiguous:    # its base address with a dense byte count would read or write the wrong bytes
+                raise RelocError(f"a pointer argument must be a C-contiguous array, got strides {a.strides} for shape {a.shape}")
+            return C.c_void_p(a.ctypes.data)
+        if isinstance(a, (i32, i64, u64, f32, f64)):
+            return C.byref(a)
+        return C.c_void_p.from_param(a)
+
+
+def outs(*types):
+    """fresh ctypes objects for the out-parameters of one call: pass them as they are, read their .value afterwards"""
+    return tuple(t() for t in types)
+
+
+# name -> (restype, argtypes); mirrors include/reloc.h one to one (tests/test_abi.py compares the types with the header).
+# A pointer RETURN is a plain c_void_p.
 SIGNATURES = {
     "reloc_last_error": (C.c_char_p, []),
     "reloc_device_count": (C.c_int, []),
@@ -27,7 +55,7 @@ SIGNATURES = {
     "reloc_destroy": (None, [c_ctx]),
     "reloc_set_stream": (C.c_int, [c_ctx, P]),
     "reloc_sync": (C.c_int, [c_ctx]),
-    "reloc_dev_alloc": (P, [c_ctx, i64]),
+    "reloc_dev_alloc": (C.c_void_p, [c_ctx, i64]),
     "reloc_dev_free": (C.c_int, [c_ctx, P]),
     "reloc_h2d": (C.c_int, [c_ctx, P, P, i64]),
     "reloc_d2h": (C.c_int, [c_ctx, P, P, i64]),
@@ -38,9 +66,9 @@ SIGNATURES = {
     "reloc_gray_u8": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, C.c_int, P]),
     "reloc_orb_detect_compute": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P]),
     "reloc_orb_frame_dev": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "reloc_frame_desc_dev": (P, [c_ctx]),
-    "reloc_frame_xy_dev": (P, [c_ctx]),
-    "reloc_frame_count_dev": (P, [c_ctx]),
+    "reloc_frame_desc_dev": (C.c_void_p, [c_ctx]),
+    "reloc_frame_xy_dev": (C.c_void_p, [c_ctx]),
+    "reloc_frame_count_dev": (C.c_void_p, [c_ctx]),
     "reloc_frame_debug_plane": (C.c_int, [c_ctx, C.c_int, C.c_int, P, P, P]),
     "reloc_set_orb_mask": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int]),
     "reloc_get_orb_mask": (C.c_int, [c_ctx, P, P]),
@@ -61,7 +89,7 @@ SIGNATURES = {
     "reloc_db_upload": (C.c_int, [c_ctx, P, P, P, P, i64]),
     "reloc_db_records": (i64, [c_ctx]),
     "reloc_db_rows": (i64, [c_ctx]),
-    "reloc_db_counts_dev": (P, [c_ctx]),
+    "reloc_db_counts_dev": (C.c_void_p, [c_ctx]),
     "reloc_db_match_counts": (C.c_int, [c_ctx, P, C.c_int, P]),
     "reloc_db_match_counts_dev": (C.c_int, [c_ctx, P, P, C.c_int, P]),
     "reloc_hamming_matrix": (C.c_int, [c_ctx, P, i64, P, i64, P]),
@@ -110,10 +138,10 @@ SIGNATURES = {
     "reloc_db_select": (C.c_int, [c_ctx, C.c_int]),
     "reloc_db_share": (C.c_int, [c_ctx, c_ctx]),
     "reloc_d2d": (C.c_int, [c_ctx, P, P, i64]),
-    "reloc_host_alloc": (P, [i64]),
+    "reloc_host_alloc": (C.c_void_p, [i64]),
     "reloc_host_free": (C.c_int, [P]),
-    "reloc_get_stream": (P, [c_ctx]),
-    "reloc_tick_result_dev": (P, [c_ctx]),
+    "reloc_get_stream": (C.c_void_p, [c_ctx]),
+    "reloc_tick_result_dev": (C.c_void_p, [c_ctx]),
     "reloc_tick_result_to": (C.c_int, [c_ctx, P]),
     "reloc_set_exclusive": (C.c_int, [c_ctx, C.c_int]),
     "reloc_db_fetch": (C.c_int, [c_ctx, i64, P, P, P, P, P, P]),
@@ -131,6 +159,8 @@ SIGNATURES = {
     "reloc_tick_solve_dev": (C.c_int, [c_ctx, P, C.c_int, P, C.c_int, u64]),
 }
 
+# the entry points whose int is a status (0, or a RELOC_E_* code with reloc_last_error set): every int but the one count
+STATUS = frozenset(name for name, (res, _) in SIGNATURES.items() if res is C.c_int) - {"reloc_device_count"}
 
 
 class RelocParams(C.Structure):
@@ -143,11 +173,7 @@ class RelocParams(C.Structure):
                 ("accum_depth_max_m", f64), ("gray_coeff_bits", i32), ("reserved0", i32)]
 
 
-_lib = None
-
-
-class RelocError(RuntimeError):
-    """Raised for every failure of the native library (the cv2 shim re-raises it as cv2.error)."""
+_lib = _api = None
 
 
 def _one_hip_runtime():
@@ -200,6 +226,37 @@ def load(strict: bool = True):
     return lib
 
 
+class _Api:
+    """see api()"""
+
+    def __init__(self, lib):
+        for name in SIGNATURES:
+            fn = getattr(lib, name, None)
+            if fn is not None:
+                setattr(self, name, self._checked(fn, name) if name in STATUS else fn)
+
+    @staticmethod
+    def _checked(fn, name):
+        def call(*args):
+            try:
+                rc = fn(*args)
+            except C.ArgumentError as e:        # ctypes' wrapping of what a from_param raised: P's RelocError, a TypeError
+                raise RelocError(f"{name}: {e}") from e
+            if rc != 0:
+                check(rc, name)
+        return call
+
+
+def api():
+    """The checked view of the library load() returns: the same entry points as attributes, but one of STATUS raises
+    RelocError on a non-zero code -- with check()'s text -- or on an argument that does not convert, and returns nothing.
+    Those that return a pointer, a count, a string or nothing are load()'s own functions."""
+    global _api
+    if _api is None:
+        _api = _Api(load())
+    return _api
+
+
 def last_error() -> str:
     return load().reloc_last_error().decode("utf-8", "replace")
 
@@ -210,13 +267,8 @@ def check(rc: int, what: str = ""):
 
 
 def ptr(a):
-    """void* of a C-contiguous numpy array (or None)."""
-    if a is None:
-        return None
-    if isinstance(a, int):
-        return C.c_void_p(a)
-    assert a.flags["C_CONTIGUOUS"]
-    return a.ctypes.data_as(C.c_void_p)
+    """void* of a C-contiguous numpy array (or None), for calls of the raw library that spell the conversion out"""
+    return C.c_void_p(a) if isinstance(a, int) else P.from_param(a)
 
 
 def u8(a):

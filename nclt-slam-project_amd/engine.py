@@ -2,7 +2,8 @@
 methods.  This is the object the cv2-shaped shim, the matcher/recorder nodes and bench.py share.
 
 Every method calls the HIP library through the C-ABI of include/reloc.h; nothing falls back to
-a CPU implementation.
+a CPU implementation.  The calls go through the checked view of the library (_native.api()): a failing
+entry point raises RelocError, arrays, addresses and None are passed as they are.
 """
 from __future__ import annotations
 
@@ -11,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
+from ._native import f32, f64, i32
 from .front_end import PIXEL_FORMATS, frame_shape_ok, pixel_format_setting
 
 K4_DEFAULT = np.array([320.0, 320.0, 320.0, 240.0], dtype=np.float64)  # fx fy cx cy (reference M:49-52)
@@ -55,6 +57,22 @@ def tick_result_dict(rec) -> dict:
                 n_features=int(rec["n_features"]), relocating=bool(rec["relocating"]))
 
 
+def image_rows(img, channels, msg):
+    """img as the image entry points read it through a row stride: a uint8 array of shape (H, W) if 1 is in `channels`, or
+    (H, W, ch) for a ch > 1 in `channels`, with byte-dense pixels and rows at least W * ch bytes apart -- returned as it is
+    when it has that layout (a row-padded view is not copied), else as a C-contiguous copy.  Anything else: RelocError(msg)."""
+    img = np.asarray(img)
+    ch = 1 if img.ndim == 2 else img.shape[2] if img.ndim == 3 and img.shape[2] > 1 else 0
+    if img.dtype != np.uint8 or ch not in channels:
+        raise N.RelocError(msg)
+    if img.strides[-1] != 1 or img.strides[1] != ch or img.strides[0] < img.shape[1] * ch:
+        img = np.ascontiguousarray(img)
+    return img
+
+
+_FORMAT_NAMES = {c[0]: name for name, c in PIXEL_FORMATS.items()}       # RELOC_FMT_* -> name
+
+
 class _PinnedBlock:
     """one hipHostMalloc allocation, freed with its last reference"""
 
@@ -72,14 +90,13 @@ class _PinnedBlock:
 
 class Engine:
     def __init__(self, device: int = 0, max_w: int = 1280, max_h: int = 720, max_feat: int = 8192):
-        self._lib = N.load()
+        self._lib = N.load()        # the raw library: its entry points return their codes
+        self._api = N.api()         # the checked view every method calls through
         self._ctx = self._lib.reloc_create(device, max_w, max_h, max_feat)
         if not self._ctx:
             raise N.RelocError("reloc_create failed: " + N.last_error())
         self.device = device
         self.max_w, self.max_h, self.max_feat = max_w, max_h, max_feat
-        self._bayer = None          # set_bayer's code: the frames of tick / record_frame are then (H, W) mosaics
-        self.pixel_format = None    # set_pixel_format's name: the frames are then (H, W), (H, W, 4) or (H, W, 2)
         self._topk_dev = self._cand_dev = 0     # device scratch of the scan / solve halves (_halves_scratch)
 
     # ------------------------------------------------------------------ lifetime / plumbing
@@ -99,14 +116,14 @@ class Engine:
         return self._ctx
 
     def set_stream(self, hip_stream: int | None):
-        N.check(self._lib.reloc_set_stream(self._ctx, C.c_void_p(hip_stream or 0)), "reloc_set_stream")
+        self._api.reloc_set_stream(self._ctx, hip_stream or 0)
 
     def sync(self):
-        N.check(self._lib.reloc_sync(self._ctx), "reloc_sync")
+        self._api.reloc_sync(self._ctx)
 
     def tick_wait(self):
         """wait for the result record of the last tick enqueued (polls its sequence stamp in pinned memory: reloc_tick_wait)"""
-        N.check(self._lib.reloc_tick_wait(self._ctx), "reloc_tick_wait")
+        self._api.reloc_tick_wait(self._ctx)
 
     def dev_alloc(self, nbytes: int) -> int:
         p = self._lib.reloc_dev_alloc(self._ctx, int(nbytes))
@@ -115,25 +132,22 @@ class Engine:
         return int(p)
 
     def dev_free(self, p: int):
-        N.check(self._lib.reloc_dev_free(self._ctx, C.c_void_p(p)), "reloc_dev_free")
+        self._api.reloc_dev_free(self._ctx, p)
 
     def h2d(self, dst_dev: int, src: np.ndarray):
-        src = np.ascontiguousarray(src)
-        N.check(self._lib.reloc_h2d(self._ctx, C.c_void_p(dst_dev), N.ptr(src), src.nbytes), "reloc_h2d")
+        self.h2d_async(dst_dev, np.ascontiguousarray(src))
         self.sync()
 
     def h2d_async(self, dst_dev: int, src: np.ndarray):
-        """enqueue only; `src` must stay alive and unchanged until the stream has passed the copy"""
-        assert src.flags["C_CONTIGUOUS"]
-        N.check(self._lib.reloc_h2d(self._ctx, C.c_void_p(dst_dev), N.ptr(src), src.nbytes), "reloc_h2d")
+        """enqueue only; `src` must be C-contiguous, and stay alive and unchanged until the stream has passed the copy"""
+        self._api.reloc_h2d(self._ctx, dst_dev, src, src.nbytes)
 
     def d2d(self, dst_dev: int, src_dev: int, nbytes: int):
-        N.check(self._lib.reloc_d2d(self._ctx, C.c_void_p(dst_dev), C.c_void_p(src_dev), int(nbytes)), "reloc_d2d")
+        self._api.reloc_d2d(self._ctx, dst_dev, src_dev, int(nbytes))
 
     def d2h_async(self, dst: np.ndarray, src_dev: int):
-        """enqueue only; read `dst` after sync()"""
-        assert dst.flags["C_CONTIGUOUS"]
-        N.check(self._lib.reloc_d2h(self._ctx, N.ptr(dst), C.c_void_p(src_dev), dst.nbytes), "reloc_d2h")
+        """enqueue only; `dst` must be C-contiguous; read it after sync()"""
+        self._api.reloc_d2h(self._ctx, dst, src_dev, dst.nbytes)
 
     def pinned(self, shape, dtype=np.uint8) -> np.ndarray:
         """numpy array over page-locked host memory (hipHostMalloc): H2D / D2H copies from it are asynchronous DMA.
@@ -160,21 +174,17 @@ class Engine:
     def set_exclusive(self, on: bool | None):
         """deployment hint (no effect on results): this context is the only stream of work on the GPU -- kernels sized for
         the latency of one synchronous tick instead of for sharing the chip with other streams (reloc_set_exclusive)"""
-        N.check(self._lib.reloc_set_exclusive(self._ctx, -1 if on is None else int(bool(on))), "reloc_set_exclusive")
+        self._api.reloc_set_exclusive(self._ctx, -1 if on is None else int(bool(on)))
 
     def tick_result_to(self, record: np.ndarray | None):
         """the ticks enqueued from now on also write their 96-byte result record into `record` (a slice of a pinned() array;
         None stops it): no copy, complete once the stream has passed the tick (reloc_tick_result_to)"""
-        if record is None:
-            N.check(self._lib.reloc_tick_result_to(self._ctx, None), "reloc_tick_result_to")
-            return
-        if record.nbytes < 96 or not record.flags.c_contiguous:
+        if record is not None and (record.nbytes < 96 or not record.flags.c_contiguous):
             raise N.RelocError("tick_result_to: need a contiguous record of at least 96 bytes")
-        N.check(self._lib.reloc_tick_result_to(self._ctx, C.c_void_p(record.ctypes.data)), "reloc_tick_result_to")
+        self._api.reloc_tick_result_to(self._ctx, record)
 
     def d2h(self, dst: np.ndarray, src_dev: int):
-        assert dst.flags["C_CONTIGUOUS"]
-        N.check(self._lib.reloc_d2h(self._ctx, N.ptr(dst), C.c_void_p(src_dev), dst.nbytes), "reloc_d2h")
+        self.d2h_async(dst, src_dev)
         self.sync()
 
     def to_device(self, a: np.ndarray) -> int:
@@ -184,19 +194,19 @@ class Engine:
         return p
 
     def timer_begin(self):
-        N.check(self._lib.reloc_timer_begin(self._ctx), "reloc_timer_begin")
+        self._api.reloc_timer_begin(self._ctx)
 
     def timer_end(self) -> float:
-        ms = C.c_float()
-        N.check(self._lib.reloc_timer_end(self._ctx, C.byref(ms)), "reloc_timer_end")
+        ms = f32()
+        self._api.reloc_timer_end(self._ctx, ms)
         return ms.value
 
     def profile_enable(self, on: bool):
-        N.check(self._lib.reloc_profile_enable(self._ctx, int(on)), "reloc_profile_enable")
+        self._api.reloc_profile_enable(self._ctx, int(on))
 
     def profile_get(self, which: int):
-        ms = C.c_float(); n = C.c_int32()
-        N.check(self._lib.reloc_profile_get(self._ctx, which, C.byref(ms), C.byref(n)), "reloc_profile_get")
+        ms, n = N.outs(f32, i32)
+        self._api.reloc_profile_get(self._ctx, which, ms, n)
         return ms.value, n.value
 
     # ------------------------------------------------------------------ ORB front end
@@ -206,7 +216,7 @@ class Engine:
             raise N.RelocError("gray: expected an (H, W, 3) uint8 image")
         h, w, _ = img.shape
         out = np.empty((h, w), np.uint8)
-        N.check(self._lib.reloc_gray_u8(self._ctx, N.ptr(img), w, h, w * 3, int(order_rgb), N.ptr(out)), "reloc_gray_u8")
+        self._api.reloc_gray_u8(self._ctx, img, w, h, w * 3, int(order_rgb), out)
         return out
 
     @staticmethod
@@ -230,24 +240,21 @@ class Engine:
         mf = self.max_feat
         xy = np.empty((mf, 2), np.float32); size = np.empty(mf, np.float32); ang = np.empty(mf, np.float32)
         resp = np.empty(mf, np.float32); octv = np.empty(mf, np.int32); desc = np.empty((mf, 32), np.uint8)
-        n = C.c_int32()
-        outs = (N.ptr(xy), N.ptr(size), N.ptr(ang), N.ptr(resp), N.ptr(octv), N.ptr(desc), C.byref(n))
+        n = i32()
+        outs = (xy, size, ang, resp, octv, desc, n)
+        mp = ms = 0         # the mask's address (a row-strided view is no C-contiguous array) and row stride
         if mask is not None:
             mask = self._mask_plane(mask, "detectAndCompute")
             if mask.shape != (h, w):
                 raise N.RelocError(f"detectAndCompute: the mask is {mask.shape[1]}x{mask.shape[0]}, the image {w}x{h}")
+            mp, ms = mask.ctypes.data, mask.strides[0]
         if orb is not None:
             nlev, sf, thr, score = self._orb_params(orb, "detectAndCompute")
-            mp, ms = (None, 0) if mask is None else (C.c_void_p(mask.ctypes.data), mask.strides[0])
-            N.check(self._lib.reloc_orb_detect_compute_params(self._ctx, N.ptr(gray), w, h, w, mp, ms, int(nfeatures), nlev, sf,
-                                                              thr, score, *outs), "reloc_orb_detect_compute_params")
+            self._api.reloc_orb_detect_compute_params(self._ctx, gray, w, h, w, mp, ms, int(nfeatures), nlev, sf, thr, score, *outs)
         elif mask is None:
-            N.check(self._lib.reloc_orb_detect_compute(self._ctx, N.ptr(gray), w, h, w, int(nfeatures), *outs),
-                    "reloc_orb_detect_compute")
+            self._api.reloc_orb_detect_compute(self._ctx, gray, w, h, w, int(nfeatures), *outs)
         else:
-            N.check(self._lib.reloc_orb_detect_compute_masked(self._ctx, N.ptr(gray), w, h, w, C.c_void_p(mask.ctypes.data),
-                                                              mask.strides[0], int(nfeatures), *outs),
-                    "reloc_orb_detect_compute_masked")
+            self._api.reloc_orb_detect_compute_masked(self._ctx, gray, w, h, w, mp, ms, int(nfeatures), *outs)
         k = n.value
         return dict(xy=xy[:k].copy(), size=size[:k].copy(), angle=ang[:k].copy(), response=resp[:k].copy(),
                     octave=octv[:k].copy(), desc=desc[:k].copy(), n=k)
@@ -267,63 +274,56 @@ class Engine:
         """cv2.ORB_create's nlevels (1..8), scaleFactor (1.01..2.0), fastThreshold (1..254) and scoreType (0 = HARRIS_SCORE,
         1 = FAST_SCORE) of every entry point that runs ORB (reloc_set_orb_params; include/reloc_spec.h "ORB PARAMS"); the
         defaults are OpenCV's and those of a new engine"""
-        N.check(self._lib.reloc_set_orb_params(self._ctx, *self._orb_params((nlevels, scale_factor, fast_threshold, score_type),
-                                                                            "set_orb_params")), "reloc_set_orb_params")
+        self._api.reloc_set_orb_params(self._ctx, *self._orb_params((nlevels, scale_factor, fast_threshold, score_type), "set_orb_params"))
 
     def get_orb_params(self):
         """(nlevels, scaleFactor, fastThreshold, scoreType)"""
-        n = C.c_int32(); s = C.c_double(); t = C.c_int32(); sc = C.c_int32()
-        N.check(self._lib.reloc_get_orb_params(self._ctx, C.byref(n), C.byref(s), C.byref(t), C.byref(sc)), "reloc_get_orb_params")
-        return n.value, s.value, t.value, sc.value
+        v = N.outs(i32, f64, i32, i32)
+        self._api.reloc_get_orb_params(self._ctx, *v)
+        return tuple(t.value for t in v)
 
     def set_orb_mask(self, mask: np.ndarray | None = None):
         """ORB's detection mask on the frames of the fused tick, recording and reloc_orb_frame_dev (reloc_set_orb_mask): an
         (H, W) uint8 array of the size of the working frame (behind set_resize); corners on zero pixels of their mask level are
         dropped before the per-level quota is spent.  None = off."""
         if mask is None:
-            N.check(self._lib.reloc_set_orb_mask(self._ctx, None, 0, 0, 0), "reloc_set_orb_mask")
+            self._api.reloc_set_orb_mask(self._ctx, None, 0, 0, 0)
             return
         mask = self._mask_plane(mask, "set_orb_mask")
-        N.check(self._lib.reloc_set_orb_mask(self._ctx, C.c_void_p(mask.ctypes.data), mask.shape[1], mask.shape[0],
-                                             mask.strides[0]), "reloc_set_orb_mask")
+        self._api.reloc_set_orb_mask(self._ctx, mask.ctypes.data, mask.shape[1], mask.shape[0], mask.strides[0])
 
     def get_orb_mask(self):
         """None when off, else the mask's (w, h)"""
-        w = C.c_int32(); h = C.c_int32()
-        N.check(self._lib.reloc_get_orb_mask(self._ctx, C.byref(w), C.byref(h)), "reloc_get_orb_mask")
+        w, h = N.outs(i32, i32)
+        self._api.reloc_get_orb_mask(self._ctx, w, h)
         return None if w.value == 0 else (w.value, h.value)
 
     def orb_mask_level(self, level: int) -> np.ndarray:
         """level of the mask pyramid that the last masked frame used (parity tap, reloc_orb_mask_level)"""
         buf = np.empty(self.max_w * self.max_h, np.uint8)
-        w = C.c_int32(); h = C.c_int32()
-        N.check(self._lib.reloc_orb_mask_level(self._ctx, int(level), N.ptr(buf), C.byref(w), C.byref(h)), "reloc_orb_mask_level")
+        w, h = N.outs(i32, i32)
+        self._api.reloc_orb_mask_level(self._ctx, int(level), buf, w, h)
         return buf[: w.value * h.value].reshape(h.value, w.value).copy()
 
     def clahe(self, gray: np.ndarray, clip: float = 40.0, tiles=(8, 8)) -> np.ndarray:
         """cv2.createCLAHE(clip, tiles).apply(gray) on an (H, W) uint8 image (reloc_clahe_u8); tiles = (tiles_x, tiles_y)"""
-        gray = np.asarray(gray)
-        if gray.dtype != np.uint8 or gray.ndim != 2:
-            raise N.RelocError("clahe: expected an (H, W) uint8 image")
-        if gray.strides[1] != 1 or gray.strides[0] < gray.shape[1]:
-            gray = np.ascontiguousarray(gray)
+        gray = image_rows(gray, (1,), "clahe: expected an (H, W) uint8 image")
         h, w = gray.shape
         tx, ty = (int(v) for v in tiles)
         out = np.empty((h, w), np.uint8)
-        N.check(self._lib.reloc_clahe_u8(self._ctx, C.c_void_p(gray.ctypes.data), w, h, gray.strides[0], float(clip), tx, ty,
-                                         N.ptr(out)), "reloc_clahe_u8")
+        self._api.reloc_clahe_u8(self._ctx, gray.ctypes.data, w, h, gray.strides[0], float(clip), tx, ty, out)
         return out
 
     def set_clahe(self, clip: float | None = 2.0, tiles=(8, 8)):
         """CLAHE in front of ORB on the 3-channel frames of the fused tick, recording and reloc_orb_frame_dev (reloc_set_clahe);
         clip=None or tiles=(0, 0) turns it off"""
         tx, ty = (0, 0) if clip is None else (int(v) for v in tiles)
-        N.check(self._lib.reloc_set_clahe(self._ctx, 0.0 if clip is None else float(clip), tx, ty), "reloc_set_clahe")
+        self._api.reloc_set_clahe(self._ctx, 0.0 if clip is None else float(clip), tx, ty)
 
     def get_clahe(self):
         """None when off, else (clip, (tiles_x, tiles_y))"""
-        clip = C.c_double(); tx = C.c_int32(); ty = C.c_int32()
-        N.check(self._lib.reloc_get_clahe(self._ctx, C.byref(clip), C.byref(tx), C.byref(ty)), "reloc_get_clahe")
+        clip, tx, ty = N.outs(f64, i32, i32)
+        self._api.reloc_get_clahe(self._ctx, clip, tx, ty)
         return None if tx.value == 0 else (clip.value, (tx.value, ty.value))
 
     @staticmethod
@@ -351,8 +351,7 @@ class Engine:
         mapx, mapy = np.ascontiguousarray(mapx), np.ascontiguousarray(mapy)
         h, w = mapx.shape
         xy = np.empty((h, w, 2), np.int16); alpha = np.empty((h, w), np.uint16)
-        N.check(self._lib.reloc_convert_maps(self._ctx, N.ptr(mapx), N.ptr(mapy), w, h, int(bool(nearest)), N.ptr(xy),
-                                             N.ptr(alpha)), "reloc_convert_maps")
+        self._api.reloc_convert_maps(self._ctx, mapx, mapy, w, h, int(bool(nearest)), xy, alpha)
         return xy, alpha
 
     def remap(self, src: np.ndarray, xy: np.ndarray, alpha: np.ndarray | None, nearest: bool = False, border: int = 0) -> np.ndarray:
@@ -366,18 +365,13 @@ class Engine:
                 raise N.RelocError("remap: uint16 input is single-channel and INTER_NEAREST only")
             src = np.ascontiguousarray(src)
             out = np.empty((dh, dw), np.uint16)
-            N.check(self._lib.reloc_remap_u16(self._ctx, N.ptr(src), src.shape[1], src.shape[0], src.strides[0], N.ptr(xy), dw, dh,
-                                              int(border), N.ptr(out)), "reloc_remap_u16")
+            self._api.reloc_remap_u16(self._ctx, src, src.shape[1], src.shape[0], src.strides[0], xy, dw, dh, int(border), out)
             return out
-        if src.dtype != np.uint8 or not (src.ndim == 2 or (src.ndim == 3 and src.shape[2] == 3)):
-            raise N.RelocError("remap: expected an (H, W) or (H, W, 3) uint8 image, or an (H, W) uint16 image")
+        src = image_rows(src, (1, 3), "remap: expected an (H, W) or (H, W, 3) uint8 image, or an (H, W) uint16 image")
         ch = 1 if src.ndim == 2 else 3
-        if src.strides[-1] != 1 or (ch == 3 and src.strides[1] != 3) or src.strides[0] < src.shape[1] * ch:
-            src = np.ascontiguousarray(src)
         out = np.empty((dh, dw) if ch == 1 else (dh, dw, 3), np.uint8)
-        N.check(self._lib.reloc_remap_u8(self._ctx, C.c_void_p(src.ctypes.data), src.shape[1], src.shape[0], src.strides[0], ch,
-                                         N.ptr(xy), N.ptr(alpha), dw, dh, int(bool(nearest)), int(border), N.ptr(out)),
-                "reloc_remap_u8")
+        self._api.reloc_remap_u8(self._ctx, src.ctypes.data, src.shape[1], src.shape[0], src.strides[0], ch, xy, alpha, dw, dh,
+                                 int(bool(nearest)), int(border), out)
         return out
 
     def set_rectify(self, maps=None):
@@ -385,19 +379,18 @@ class Engine:
         reloc_orb_frame_dev, and of the depth of recording and accumulation (reloc_set_rectify_map).  maps: None = off, or
         (map1, map2) as cv2.remap takes them: two (H, W) float32 maps or the fixed-point (H, W, 2) int16 + (H, W) uint16 pair"""
         if maps is None:
-            N.check(self._lib.reloc_set_rectify_map(self._ctx, None, None, 0, 0), "reloc_set_rectify_map")
+            self._api.reloc_set_rectify_map(self._ctx, None, None, 0, 0)
             return
         m1, m2 = maps
         if np.asarray(m1).dtype == np.float32:
             m1, m2 = self.convert_maps(m1, m2)
         xy, alpha = self._fixed_maps(m1, m2)
-        N.check(self._lib.reloc_set_rectify_map(self._ctx, N.ptr(xy), N.ptr(alpha), xy.shape[1], xy.shape[0]),
-                "reloc_set_rectify_map")
+        self._api.reloc_set_rectify_map(self._ctx, xy, alpha, xy.shape[1], xy.shape[0])
 
     def get_rectify(self):
         """None when off, else the map's (w, h)"""
-        w = C.c_int32(); h = C.c_int32()
-        N.check(self._lib.reloc_get_rectify_map(self._ctx, C.byref(w), C.byref(h)), "reloc_get_rectify_map")
+        w, h = N.outs(i32, i32)
+        self._api.reloc_get_rectify_map(self._ctx, w, h)
         return None if w.value == 0 else (w.value, h.value)
 
     def resize(self, src: np.ndarray, dsize=None, fx: float = 0.0, fy: float = 0.0, interpolation: int = 1) -> np.ndarray:
@@ -425,17 +418,12 @@ class Engine:
                 raise N.RelocError("resize: uint16 input is single-channel and INTER_NEAREST only")
             src = np.ascontiguousarray(src)
             out = np.empty((dh, dw), np.uint16)
-            N.check(self._lib.reloc_resize_u16(self._ctx, N.ptr(src), sw, sh, src.strides[0], N.ptr(out), dw, dh, fx, fy),
-                    "reloc_resize_u16")
+            self._api.reloc_resize_u16(self._ctx, src, sw, sh, src.strides[0], out, dw, dh, fx, fy)
             return out
-        if src.dtype != np.uint8 or not (src.ndim == 2 or src.shape[2] == 3):
-            raise N.RelocError("resize: expected an (H, W) or (H, W, 3) uint8 image, or an (H, W) uint16 image")
+        src = image_rows(src, (1, 3), "resize: expected an (H, W) or (H, W, 3) uint8 image, or an (H, W) uint16 image")
         ch = 1 if src.ndim == 2 else 3
-        if src.strides[-1] != 1 or (ch == 3 and src.strides[1] != 3) or src.strides[0] < sw * ch:
-            src = np.ascontiguousarray(src)
         out = np.empty((dh, dw) if ch == 1 else (dh, dw, 3), np.uint8)
-        N.check(self._lib.reloc_resize_u8(self._ctx, C.c_void_p(src.ctypes.data), sw, sh, src.strides[0], ch, N.ptr(out), dw, dh,
-                                          fx, fy, int(interpolation)), "reloc_resize_u8")
+        self._api.reloc_resize_u8(self._ctx, src.ctypes.data, sw, sh, src.strides[0], ch, out, dw, dh, fx, fy, int(interpolation))
         return out
 
     def set_resize(self, src_size=None, dst_size=None):
@@ -444,63 +432,54 @@ class Engine:
         with INTER_AREA before rectification, CLAHE and ORB; the depth of recording and accumulation with INTER_NEAREST.
         Everything downstream, the camera included, is that of the working frame dst_size.  None = off."""
         if src_size is None and dst_size is None:
-            N.check(self._lib.reloc_set_resize(self._ctx, 0, 0, 0, 0), "reloc_set_resize")
+            self._api.reloc_set_resize(self._ctx, 0, 0, 0, 0)
             return
         if src_size is None or dst_size is None:
             raise N.RelocError("set_resize: give both sizes, or neither to turn the stage off")
         (sw, sh), (dw, dh) = (int(t) for t in src_size), (int(t) for t in dst_size)
-        N.check(self._lib.reloc_set_resize(self._ctx, sw, sh, dw, dh), "reloc_set_resize")
+        self._api.reloc_set_resize(self._ctx, sw, sh, dw, dh)
 
     def get_resize(self):
         """None when off, else ((sw, sh), (dw, dh))"""
-        v = [C.c_int32() for _ in range(4)]
-        N.check(self._lib.reloc_get_resize(self._ctx, *(C.byref(t) for t in v)), "reloc_get_resize")
-        return None if v[2].value == 0 else ((v[0].value, v[1].value), (v[2].value, v[3].value))
+        sw, sh, dw, dh = N.outs(i32, i32, i32, i32)
+        self._api.reloc_get_resize(self._ctx, sw, sh, dw, dh)
+        return None if dw.value == 0 else ((sw.value, sh.value), (dw.value, dh.value))
 
     def bayer(self, raw: np.ndarray, code: int) -> np.ndarray:
         """cv2.cvtColor(raw, code) of an (H, W) uint8 Bayer mosaic of at least 3 x 3 with code = COLOR_BayerBG2BGR (46),
         GB (47), RG (48) or GR (49), bilinear: (H, W, 3) uint8 BGR (reloc_bayer_u8)"""
-        raw = np.asarray(raw)
-        if raw.dtype != np.uint8 or raw.ndim != 2:
-            raise N.RelocError("bayer: expected an (H, W) uint8 mosaic")
+        raw = image_rows(raw, (1,), "bayer: expected an (H, W) uint8 mosaic")
         h, w = raw.shape
         if w < 3 or h < 3:
             raise N.RelocError("bayer: the mosaic must be at least 3 x 3")
-        if raw.strides[1] != 1 or raw.strides[0] < w:
-            raw = np.ascontiguousarray(raw)
         out = np.empty((h, w, 3), np.uint8)
-        N.check(self._lib.reloc_bayer_u8(self._ctx, C.c_void_p(raw.ctypes.data), w, h, raw.strides[0], int(code), N.ptr(out)),
-                "reloc_bayer_u8")
+        self._api.reloc_bayer_u8(self._ctx, raw.ctypes.data, w, h, raw.strides[0], int(code), out)
         return out
 
     def set_bayer(self, code: int | None = None):
         """The raw-sensor stage in front of the whole image chain (reloc_set_bayer): with code = COLOR_BayerBG2BGR (46), GB (47),
         RG (48) or GR (49) every frame of the fused tick, recording and reloc_orb_frame_dev is an (H, W) uint8 mosaic,
         demosaiced and converted to gray before resize, rectification, CLAHE and ORB.  None / 0 = off."""
-        code = int(code or 0)
-        N.check(self._lib.reloc_set_bayer(self._ctx, code), "reloc_set_bayer")
-        self._bayer = code or None
+        self._api.reloc_set_bayer(self._ctx, int(code or 0))
 
     def get_bayer(self):
         """None when off, else the code"""
-        v = C.c_int32()
-        N.check(self._lib.reloc_get_bayer(self._ctx, C.byref(v)), "reloc_get_bayer")
+        v = i32()
+        self._api.reloc_get_bayer(self._ctx, v)
         return v.value or None
 
     @staticmethod
     def _packed(img, fmt, what):
         """a packed frame of the format named fmt for a host-pointer call: (array with byte-dense pixels, w, h, RELOC_FMT_*)"""
-        img = np.asarray(img)
         code, tail = PIXEL_FORMATS.get(str(fmt).lower(), (None, None))[:2]
         if not tail:
             raise N.RelocError(f'{what}: the format must be "bgra", "rgba", "yuyv" or "uyvy"')
-        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != tail[0] or img.shape[0] < 1 or img.shape[1] < 1:
-            raise N.RelocError(f"{what}: expected an (H, W, {tail[0]}) uint8 frame")
+        img = image_rows(img, tail, f"{what}: expected an (H, W, {tail[0]}) uint8 frame")
         h, w = img.shape[:2]
+        if h < 1 or w < 1:
+            raise N.RelocError(f"{what}: expected an (H, W, {tail[0]}) uint8 frame")
         if tail[0] == 2 and w % 2:
             raise N.RelocError(f"{what}: a packed 4:2:2 frame must have an even width")
-        if img.strides[2] != 1 or img.strides[1] != tail[0] or img.strides[0] < w * tail[0]:
-            img = np.ascontiguousarray(img)
         return img, w, h, code
 
     def cvt_gray(self, img: np.ndarray, fmt: str) -> np.ndarray:
@@ -509,8 +488,7 @@ class Engine:
         frame of even width (fmt "yuyv" / "uyvy": the Y bytes): (H, W) uint8 (reloc_cvt_gray_u8)"""
         img, w, h, code = self._packed(img, fmt, "cvt_gray")
         out = np.empty((h, w), np.uint8)
-        N.check(self._lib.reloc_cvt_gray_u8(self._ctx, C.c_void_p(img.ctypes.data), w, h, img.strides[0], code, N.ptr(out)),
-                "reloc_cvt_gray_u8")
+        self._api.reloc_cvt_gray_u8(self._ctx, img.ctypes.data, w, h, img.strides[0], code, out)
         return out
 
     def yuv422_bgr(self, img: np.ndarray, fmt: str, order_rgb: bool = False) -> np.ndarray:
@@ -520,8 +498,7 @@ class Engine:
         if img.shape[2] != 2:
             raise N.RelocError('yuv422_bgr: the format must be "yuyv" or "uyvy"')
         out = np.empty((h, w, 3), np.uint8)
-        N.check(self._lib.reloc_yuv422_bgr_u8(self._ctx, C.c_void_p(img.ctypes.data), w, h, img.strides[0], code, int(order_rgb),
-                                              N.ptr(out)), "reloc_yuv422_bgr_u8")
+        self._api.reloc_yuv422_bgr_u8(self._ctx, img.ctypes.data, w, h, img.strides[0], code, int(order_rgb), out)
         return out
 
     def set_pixel_format(self, fmt: str | None = None):
@@ -530,24 +507,26 @@ class Engine:
         unpacked to gray (cvt_gray) before resize, rectification, CLAHE and ORB.  None = 3-channel frames, the default.
         Excludes set_bayer."""
         name = pixel_format_setting(fmt)
-        N.check(self._lib.reloc_set_pixel_format(self._ctx, PIXEL_FORMATS[name][0] if name else 0), "reloc_set_pixel_format")
-        self.pixel_format = name
+        self._api.reloc_set_pixel_format(self._ctx, PIXEL_FORMATS[name][0] if name else 0)
 
     def get_pixel_format(self):
         """None for the 3-channel default, else the name"""
-        v = C.c_int32()
-        N.check(self._lib.reloc_get_pixel_format(self._ctx, C.byref(v)), "reloc_get_pixel_format")
-        return {c[0]: k for k, c in PIXEL_FORMATS.items()}.get(v.value)
+        v = i32()
+        self._api.reloc_get_pixel_format(self._ctx, v)
+        return _FORMAT_NAMES.get(v.value)
+
+    pixel_format = property(get_pixel_format, doc="the context's pixel format: None for the 3-channel default, else the name")
 
     def _frame(self, img, what):
         """the frame of a host-pointer entry point of the image chain: (H, W, 3), (H, W) with the Bayer stage on, or the shape
-        of the pixel format"""
+        of the pixel format -- as the context holds the two settings, whoever set them"""
         img = N.u8(img)
-        if not frame_shape_ok(img.shape, self.pixel_format, self._bayer):
-            raise N.RelocError(f"{what}: expected an (H, W) uint8 mosaic (set_bayer is on)" if self._bayer
-                               else f"{what}: expected a uint8 {self.pixel_format} frame (set_pixel_format)" if self.pixel_format
+        bayer, fmt = self.get_bayer(), self.get_pixel_format()
+        if not frame_shape_ok(img.shape, fmt, bayer):
+            raise N.RelocError(f"{what}: expected an (H, W) uint8 mosaic (set_bayer is on)" if bayer
+                               else f"{what}: expected a uint8 {fmt} frame (set_pixel_format)" if fmt
                                else f"{what}: expected an (H, W, 3) uint8 frame")
-        if self.pixel_format in ("yuyv", "uyvy") and img.shape[1] % 2:
+        if fmt in ("yuyv", "uyvy") and img.shape[1] % 2:
             raise N.RelocError(f"{what}: a packed 4:2:2 frame must have an even width")
         return img
 
@@ -561,10 +540,9 @@ class Engine:
             raise N.RelocError("record_frame: depth and colour sizes differ")
         mf = self.max_feat
         xy = np.empty((mf, 2), np.float32); desc = np.empty((mf, 32), np.uint8); pts = np.empty((mf, 3), np.float32)
-        idx = np.empty(mf, np.int32); n = C.c_int32(); nk = C.c_int32()
-        N.check(self._lib.reloc_record_frame(self._ctx, N.ptr(bgr), N.ptr(depth_mm), w, h, int(order_rgb), int(nfeatures),
-                                             N.ptr(xy), N.ptr(desc), N.ptr(pts), N.ptr(idx), C.byref(n), C.byref(nk)),
-                "reloc_record_frame")
+        idx = np.empty(mf, np.int32)
+        n, nk = N.outs(i32, i32)
+        self._api.reloc_record_frame(self._ctx, bgr, depth_mm, w, h, int(order_rgb), int(nfeatures), xy, desc, pts, idx, n, nk)
         k = n.value
         return dict(xy=xy[:k].copy(), desc=desc[:k].copy(), pts3d=pts[:k].copy(), kp_index=idx[:k].copy(), n=k, n_kp=nk.value)
 
@@ -572,13 +550,13 @@ class Engine:
     def set_stereo(self, baseline_m: float | None = None, min_disparity: int = 0, num_disparities: int = 128, uniqueness: int = 15,
                    lr_check: bool = True):
         """sparse stereo depth of this (the left eye's) engine (reloc_set_stereo); baseline_m=None or 0 turns it off"""
-        N.check(self._lib.reloc_set_stereo(self._ctx, 0.0 if baseline_m is None else float(baseline_m), int(min_disparity),
-                                           int(num_disparities), int(uniqueness), int(bool(lr_check))), "reloc_set_stereo")
+        self._api.reloc_set_stereo(self._ctx, 0.0 if baseline_m is None else float(baseline_m), int(min_disparity),
+                                   int(num_disparities), int(uniqueness), int(bool(lr_check)))
 
     def get_stereo(self):
         """None when off, else dict(baseline_m, min_disparity, num_disparities, uniqueness, lr_check)"""
-        b = C.c_double(); md = C.c_int32(); nd = C.c_int32(); un = C.c_int32(); lr = C.c_int32()
-        N.check(self._lib.reloc_get_stereo(self._ctx, C.byref(b), C.byref(md), C.byref(nd), C.byref(un), C.byref(lr)), "reloc_get_stereo")
+        b, md, nd, un, lr = N.outs(f64, i32, i32, i32, i32)
+        self._api.reloc_get_stereo(self._ctx, b, md, nd, un, lr)
         if b.value == 0.0:
             return None
         return dict(baseline_m=b.value, min_disparity=md.value, num_disparities=nd.value, uniqueness=un.value, lr_check=bool(lr.value))
@@ -596,10 +574,9 @@ class Engine:
         xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
         n = len(xy)
         mm = np.zeros(n, np.uint16); disp = np.zeros(n, np.float32); st = np.zeros(n, np.uint8)
-        N.check(self._lib.reloc_stereo_depth(self._ctx, C.c_void_p(left.ctypes.data), C.c_void_p(right.ctypes.data), w, h,
-                                             left.strides[0], N.ptr(xy), n, float(fx), float(baseline_m), int(min_disparity),
-                                             int(num_disparities), int(uniqueness), int(bool(lr_check)), N.ptr(mm), N.ptr(disp),
-                                             N.ptr(st)), "reloc_stereo_depth")
+        self._api.reloc_stereo_depth(self._ctx, left.ctypes.data, right.ctypes.data, w, h, left.strides[0], xy, n, float(fx),
+                                     float(baseline_m), int(min_disparity), int(num_disparities), int(uniqueness),
+                                     int(bool(lr_check)), mm, disp, st)
         return mm, disp, st
 
     def record_frame_stereo(self, bgr: np.ndarray, right_frame: np.ndarray, right_engine: "Engine", nfeatures: int = 500,
@@ -613,10 +590,10 @@ class Engine:
             raise N.RelocError("record_frame_stereo: left and right sizes differ")
         mf = self.max_feat
         xy = np.empty((mf, 2), np.float32); desc = np.empty((mf, 32), np.uint8); pts = np.empty((mf, 3), np.float32)
-        idx = np.empty(mf, np.int32); n = C.c_int32(); nk = C.c_int32(); ns = C.c_int32()
-        N.check(self._lib.reloc_record_frame_stereo(self._ctx, right_engine._ctx, N.ptr(bgr), N.ptr(right_frame), w, h,
-                                                    int(order_rgb), int(nfeatures), N.ptr(xy), N.ptr(desc), N.ptr(pts),
-                                                    N.ptr(idx), C.byref(n), C.byref(nk), C.byref(ns)), "reloc_record_frame_stereo")
+        idx = np.empty(mf, np.int32)
+        n, nk, ns = N.outs(i32, i32, i32)
+        self._api.reloc_record_frame_stereo(self._ctx, right_engine._ctx, bgr, right_frame, w, h, int(order_rgb), int(nfeatures),
+                                            xy, desc, pts, idx, n, nk, ns)
         k = n.value
         return dict(xy=xy[:k].copy(), desc=desc[:k].copy(), pts3d=pts[:k].copy(), kp_index=idx[:k].copy(), n=k, n_kp=nk.value,
                     n_stereo=ns.value)
@@ -625,22 +602,20 @@ class Engine:
                                    order_rgb: bool = False):
         """tick_accumulate_dev with the right eye's frame (device memory) in the depth image's place; enqueues only"""
         bp = np.ascontiguousarray(base_pose, np.float64).reshape(7)
-        N.check(self._lib.reloc_tick_accumulate_stereo_dev(self._ctx, right_engine._ctx, C.c_void_p(img_right_dev), w, h,
-                                                           int(order_rgb), N.ptr(bp), int(silence_ok)),
-                "reloc_tick_accumulate_stereo_dev")
+        self._api.reloc_tick_accumulate_stereo_dev(self._ctx, right_engine._ctx, img_right_dev, w, h, int(order_rgb), bp,
+                                                   int(silence_ok))
 
     def stereo_debug(self):
         """(depth_mm, disparity, status) of the last stereo pass, per keypoint of the frame's ORB output"""
         mf = self.max_feat
-        mm = np.zeros(mf, np.uint16); disp = np.zeros(mf, np.float32); st = np.zeros(mf, np.uint8); n = C.c_int32()
-        N.check(self._lib.reloc_stereo_debug(self._ctx, N.ptr(mm), N.ptr(disp), N.ptr(st), C.byref(n)), "reloc_stereo_debug")
+        mm = np.zeros(mf, np.uint16); disp = np.zeros(mf, np.float32); st = np.zeros(mf, np.uint8); n = i32()
+        self._api.reloc_stereo_debug(self._ctx, mm, disp, st, n)
         return mm[:n.value].copy(), disp[:n.value].copy(), st[:n.value].copy()
 
     def frame_debug_plane(self, what: int, level: int) -> np.ndarray:
         buf = np.empty(self.max_w * self.max_h, np.uint8)
-        w = C.c_int32(); h = C.c_int32()
-        N.check(self._lib.reloc_frame_debug_plane(self._ctx, what, level, N.ptr(buf), C.byref(w), C.byref(h)),
-                "reloc_frame_debug_plane")
+        w, h = N.outs(i32, i32)
+        self._api.reloc_frame_debug_plane(self._ctx, what, level, buf, w, h)
         return buf[: w.value * h.value].reshape(h.value, w.value).copy()
 
     # ------------------------------------------------------------------ matching
@@ -655,16 +630,14 @@ class Engine:
         q = self._desc(q, "match"); t = self._desc(t, "match")
         cap = max(min(len(q), len(t)), 1)
         qi = np.empty(cap, np.int32); ti = np.empty(cap, np.int32); dd = np.empty(cap, np.int32)
-        n = C.c_int32()
-        N.check(self._lib.reloc_match_mutual(self._ctx, N.ptr(q), len(q), N.ptr(t), len(t), N.ptr(qi), N.ptr(ti),
-                                             N.ptr(dd), C.byref(n)), "reloc_match_mutual")
+        n = i32()
+        self._api.reloc_match_mutual(self._ctx, q, len(q), t, len(t), qi, ti, dd, n)
         return qi[: n.value].copy(), ti[: n.value].copy(), dd[: n.value].copy()
 
     def match_knn2(self, q, t):
         q = self._desc(q, "knnMatch"); t = self._desc(t, "knnMatch")
         idx = np.empty((len(q), 2), np.int32); dist = np.empty((len(q), 2), np.int32)
-        N.check(self._lib.reloc_match_knn2(self._ctx, N.ptr(q), len(q), N.ptr(t), len(t), N.ptr(idx), N.ptr(dist)),
-                "reloc_match_knn2")
+        self._api.reloc_match_knn2(self._ctx, q, len(q), t, len(t), idx, dist)
         return idx, dist
 
     def match_ratio(self, q, t, ratio: float = 0.8):
@@ -673,9 +646,8 @@ class Engine:
         q = self._desc(q, "match_ratio"); t = self._desc(t, "match_ratio")
         cap = max(len(q), 1)
         qi = np.empty(cap, np.int32); ti = np.empty(cap, np.int32); dd = np.empty(cap, np.int32)
-        n = C.c_int32()
-        N.check(self._lib.reloc_match_ratio(self._ctx, N.ptr(q), len(q), N.ptr(t), len(t), float(ratio), N.ptr(qi), N.ptr(ti),
-                                            N.ptr(dd), C.byref(n)), "reloc_match_ratio")
+        n = i32()
+        self._api.reloc_match_ratio(self._ctx, q, len(q), t, len(t), float(ratio), qi, ti, dd, n)
         return qi[: n.value].copy(), ti[: n.value].copy(), dd[: n.value].copy()
 
     def db_upload(self, desc, pts3d, offsets, poses):
@@ -685,12 +657,11 @@ class Engine:
         poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
         if len(offsets) != len(poses) + 1 or offsets[-1] != len(desc) or len(pts3d) != len(desc):
             raise N.RelocError("db_upload: inconsistent array sizes")
-        N.check(self._lib.reloc_db_upload(self._ctx, N.ptr(desc), N.ptr(pts3d), N.ptr(offsets), N.ptr(poses),
-                                          len(poses)), "reloc_db_upload")
+        self._api.reloc_db_upload(self._ctx, desc, pts3d, offsets, poses, len(poses))
 
     def db_reserve(self, cap_records: int, cap_rows: int):
         """room for that many records / descriptor rows in the selected database without re-allocation"""
-        N.check(self._lib.reloc_db_reserve(self._ctx, int(cap_records), int(cap_rows)), "reloc_db_reserve")
+        self._api.reloc_db_reserve(self._ctx, int(cap_records), int(cap_rows))
 
     def db_append(self, desc, pts3d, pose, keypoints_2d=None, index_xy=None):
         """one more record behind the last (self.landmarks.append + index update, M:489-493)"""
@@ -703,27 +674,25 @@ class Engine:
             raise N.RelocError("db_append: descriptor / keypoint counts differ")
         pose = np.ascontiguousarray(pose, np.float64).reshape(7)
         ixy = None if index_xy is None else np.ascontiguousarray(index_xy, np.float64).reshape(2)
-        N.check(self._lib.reloc_db_append(self._ctx, N.ptr(desc), N.ptr(pts3d), N.ptr(kp), len(desc), N.ptr(pose), N.ptr(ixy)),
-                "reloc_db_append")
+        self._api.reloc_db_append(self._ctx, desc, pts3d, kp, len(desc), pose, ixy)
 
     def db_share(self, src: "Engine"):
         """scan the database resident in `src` (same device) instead of holding a copy; read-only through this engine"""
-        N.check(self._lib.reloc_db_share(self._ctx, src._ctx), "reloc_db_share")
+        self._api.reloc_db_share(self._ctx, src._ctx)
         self._db_owner = src        # keeps the owner alive
 
     def db_select(self, slot: int):
         """switch between the two resident databases (outbound / return leg, X:274-294)"""
-        N.check(self._lib.reloc_db_select(self._ctx, int(slot)), "reloc_db_select")
+        self._api.reloc_db_select(self._ctx, int(slot))
 
     def db_fetch(self, record: int):
         """one record back from the device: dict(pose, descriptors, keypoints_2d, keypoints_3d_cam, index_xyh)"""
-        n = C.c_int32()
-        N.check(self._lib.reloc_db_fetch(self._ctx, int(record), None, None, None, None, None, C.byref(n)), "reloc_db_fetch")
+        n = i32()
+        self._api.reloc_db_fetch(self._ctx, int(record), None, None, None, None, None, n)
         k = n.value
         desc = np.empty((max(k, 1), 32), np.uint8); pts = np.empty((max(k, 1), 3), np.float32); kp = np.empty((max(k, 1), 2), np.float32)
         pose = np.empty(7); xyh = np.empty(4)
-        N.check(self._lib.reloc_db_fetch(self._ctx, int(record), N.ptr(desc), N.ptr(pts), N.ptr(kp), N.ptr(pose), N.ptr(xyh),
-                                         C.byref(n)), "reloc_db_fetch")
+        self._api.reloc_db_fetch(self._ctx, int(record), desc, pts, kp, pose, xyh, n)
         return dict(pose=tuple(float(v) for v in pose), descriptors=desc[:k].copy(), keypoints_2d=kp[:k].copy(),
                     keypoints_3d_cam=pts[:k].copy(), index_xyh=xyh, n_features=k)
 
@@ -743,19 +712,17 @@ class Engine:
     def db_match_counts(self, cur):
         cur = self._desc(cur, "db_match_counts") if len(cur) else np.zeros((0, 32), np.uint8)
         counts = np.empty(self.db_records, np.int32)
-        N.check(self._lib.reloc_db_match_counts(self._ctx, N.ptr(cur), len(cur), N.ptr(counts)), "reloc_db_match_counts")
+        self._api.reloc_db_match_counts(self._ctx, cur, len(cur), counts)
         return counts
 
     def db_match_counts_dev(self, cur_dev: int, n_cur: int, counts_dev: int, n_cur_dev: int = 0):
-        N.check(self._lib.reloc_db_match_counts_dev(self._ctx, C.c_void_p(cur_dev), C.c_void_p(n_cur_dev), int(n_cur),
-                                                    C.c_void_p(counts_dev)), "reloc_db_match_counts_dev")
+        self._api.reloc_db_match_counts_dev(self._ctx, cur_dev, n_cur_dev, int(n_cur), counts_dev)
 
     def db_ratio_counts(self, cur, ratio: float = 0.75):
         """per record: current descriptors passing the k=2 Lowe ratio test against the record's rows"""
         cur = self._desc(cur, "db_ratio_counts") if len(cur) else np.zeros((0, 32), np.uint8)
         counts = np.empty(self.db_records, np.int32)
-        N.check(self._lib.reloc_db_ratio_counts(self._ctx, N.ptr(cur), len(cur), float(ratio), N.ptr(counts)),
-                "reloc_db_ratio_counts")
+        self._api.reloc_db_ratio_counts(self._ctx, cur, len(cur), float(ratio), counts)
         return counts
 
     def depth_points(self, depth, step: int = 4, K4=K4_DEFAULT, zmin: float = 0.3, zmax: float = 10.0):
@@ -766,21 +733,19 @@ class Engine:
         h, w = depth.shape
         K4 = np.ascontiguousarray(K4, np.float64)
         pts = np.empty((-(-w // step) * -(-h // step), 3), np.float32)
-        n = C.c_int32()
-        N.check(self._lib.reloc_depth_points(self._ctx, N.ptr(depth), int(depth.dtype == np.float32), w, h, int(step), N.ptr(K4),
-                                             float(zmin), float(zmax), N.ptr(pts), C.byref(n)), "reloc_depth_points")
+        n = i32()
+        self._api.reloc_depth_points(self._ctx, depth, int(depth.dtype == np.float32), w, h, int(step), K4, float(zmin),
+                                     float(zmax), pts, n)
         return pts[: n.value].copy()
 
     def hamming_matrix(self, a, b):
         a = self._desc(a, "hamming_matrix"); b = self._desc(b, "hamming_matrix")
         out = np.empty((len(a), len(b)), np.uint16)
-        N.check(self._lib.reloc_hamming_matrix(self._ctx, N.ptr(a), len(a), N.ptr(b), len(b), N.ptr(out)),
-                "reloc_hamming_matrix")
+        self._api.reloc_hamming_matrix(self._ctx, a, len(a), b, len(b), out)
         return out
 
     def hamming_matrix_dev(self, a_dev: int, na: int, b_dev: int, nb: int, out_dev: int):
-        N.check(self._lib.reloc_hamming_matrix_dev(self._ctx, C.c_void_p(a_dev), na, C.c_void_p(b_dev), nb,
-                                                   C.c_void_p(out_dev)), "reloc_hamming_matrix_dev")
+        self._api.reloc_hamming_matrix_dev(self._ctx, a_dev, na, b_dev, nb, out_dev)
 
     # ------------------------------------------------------------------ PnP
     @staticmethod
@@ -800,12 +765,9 @@ class Engine:
         cnt = np.empty(len(Rt), np.int32)
         mask = np.empty((len(Rt), len(obj)), np.uint8) if want_mask else None
         if dist is None:
-            N.check(self._lib.reloc_pnp_score(self._ctx, N.ptr(obj), N.ptr(img), len(obj), N.ptr(Rt), len(Rt), N.ptr(K4),
-                                              float(thr_px), N.ptr(cnt), N.ptr(mask)), "reloc_pnp_score")
+            self._api.reloc_pnp_score(self._ctx, obj, img, len(obj), Rt, len(Rt), K4, float(thr_px), cnt, mask)
         else:
-            d = self._dist5(dist)
-            N.check(self._lib.reloc_pnp_score_dist(self._ctx, N.ptr(obj), N.ptr(img), len(obj), N.ptr(Rt), len(Rt), N.ptr(K4),
-                                                   N.ptr(d), float(thr_px), N.ptr(cnt), N.ptr(mask)), "reloc_pnp_score_dist")
+            self._api.reloc_pnp_score_dist(self._ctx, obj, img, len(obj), Rt, len(Rt), K4, self._dist5(dist), float(thr_px), cnt, mask)
         return (cnt, mask) if want_mask else cnt
 
     def undistort_points(self, img, K4=K4_DEFAULT, dist=None):
@@ -814,8 +776,7 @@ class Engine:
         K4 = np.ascontiguousarray(K4, np.float64).reshape(4)
         d = np.zeros(5) if dist is None else self._dist5(dist)
         out = np.empty((len(img), 2), np.float64)
-        N.check(self._lib.reloc_undistort_points(self._ctx, N.ptr(img), len(img), N.ptr(K4), N.ptr(d), N.ptr(out)),
-                "reloc_undistort_points")
+        self._api.reloc_undistort_points(self._ctx, img, len(img), K4, d, out)
         return out
 
     def pnp_ransac(self, obj, img, K4=K4_DEFAULT, iters=200, thr_px=3.0, conf=0.99, seed=0, dist=None):
@@ -827,28 +788,24 @@ class Engine:
         K4 = np.ascontiguousarray(K4, np.float64)
         rvec = np.zeros(3); tvec = np.zeros(3)
         inl = np.empty(max(len(obj), 1), np.int32)
-        n = C.c_int32(); ok = C.c_int32()
+        n, ok = N.outs(i32, i32)
+        tail = (int(iters), float(thr_px), float(conf), int(seed), rvec, tvec, inl, n, ok)
         if dist is None:
-            N.check(self._lib.reloc_pnp_ransac(self._ctx, N.ptr(obj), N.ptr(img), len(obj), N.ptr(K4), int(iters),
-                                               float(thr_px), float(conf), int(seed), N.ptr(rvec), N.ptr(tvec), N.ptr(inl),
-                                               C.byref(n), C.byref(ok)), "reloc_pnp_ransac")
+            self._api.reloc_pnp_ransac(self._ctx, obj, img, len(obj), K4, *tail)
         else:
-            d = self._dist5(dist)
-            N.check(self._lib.reloc_pnp_ransac_dist(self._ctx, N.ptr(obj), N.ptr(img), len(obj), N.ptr(K4), N.ptr(d),
-                                                    int(iters), float(thr_px), float(conf), int(seed), N.ptr(rvec),
-                                                    N.ptr(tvec), N.ptr(inl), C.byref(n), C.byref(ok)), "reloc_pnp_ransac_dist")
+            self._api.reloc_pnp_ransac_dist(self._ctx, obj, img, len(obj), K4, self._dist5(dist), *tail)
         return bool(ok.value), rvec, tvec, inl[: n.value].copy()
 
     # ------------------------------------------------------------------ fused tick
     def get_params(self) -> "N.RelocParams":
         p = N.RelocParams()
-        N.check(self._lib.reloc_get_params(self._ctx, C.byref(p)), "reloc_get_params")
+        self._api.reloc_get_params(self._ctx, C.byref(p))
         return p
 
     def set_params_from(self, other: "Engine"):
         """copy another engine's matcher and ORB parameters and its match policy (the contexts of a batch must carry equal ones)"""
         p = other.get_params()
-        N.check(self._lib.reloc_set_params(self._ctx, C.byref(p)), "reloc_set_params")
+        self._api.reloc_set_params(self._ctx, C.byref(p))
         self.set_orb_params(*other.get_orb_params())
         self.set_match_policy(*other.match_policy)
 
@@ -857,13 +814,13 @@ class Engine:
         knnMatch(current, record, k=2) + Lowe test with `ratio` in (0, 1]; also RELOC_MATCH_CROSS / RELOC_MATCH_RATIO.  Under
         "ratio" the ticks need a context of max_feat <= 4096."""
         code = MATCH_POLICIES.get(policy.lower(), -1) if isinstance(policy, str) else int(policy)
-        N.check(self._lib.reloc_set_match_policy(self._ctx, code, float(ratio)), "reloc_set_match_policy")
+        self._api.reloc_set_match_policy(self._ctx, code, float(ratio))
 
     @property
     def match_policy(self):
         """(policy name, ratio) as the context holds them"""
-        code = C.c_int32(); ratio = C.c_double()
-        N.check(self._lib.reloc_get_match_policy(self._ctx, C.byref(code), C.byref(ratio)), "reloc_get_match_policy")
+        code, ratio = N.outs(i32, f64)
+        self._api.reloc_get_match_policy(self._ctx, code, ratio)
         return {v: k for k, v in MATCH_POLICIES.items()}[code.value], ratio.value
 
     def set_params(self, **kw):
@@ -878,40 +835,38 @@ class Engine:
             if not hasattr(p, k):
                 raise N.RelocError(f"set_params: unknown parameter {k}")
             setattr(p, k, v)
-        N.check(self._lib.reloc_set_params(self._ctx, C.byref(p)), "reloc_set_params")
+        self._api.reloc_set_params(self._ctx, C.byref(p))
 
     def tick_accumulate_dev(self, depth_mm_dev: int, w: int, h: int, base_pose, silence_ok: bool):
         bp = np.ascontiguousarray(base_pose, np.float64).reshape(7)
-        N.check(self._lib.reloc_tick_accumulate_dev(self._ctx, C.c_void_p(depth_mm_dev), w, h, N.ptr(bp), int(silence_ok)),
-                "reloc_tick_accumulate_dev")
+        self._api.reloc_tick_accumulate_dev(self._ctx, depth_mm_dev, w, h, bp, int(silence_ok))
 
     def accumulate_result(self):
-        ap = C.c_int32(); n = C.c_int32(); d = C.c_double()
-        N.check(self._lib.reloc_accumulate_result(self._ctx, C.byref(ap), C.byref(n), C.byref(d)), "reloc_accumulate_result")
+        ap, n, d = N.outs(i32, i32, f64)
+        self._api.reloc_accumulate_result(self._ctx, ap, n, d)
         return dict(appended=bool(ap.value), n_kpts=n.value, nearest_m=d.value)
 
     def set_camera(self, K4=None, base_to_cam_t=None, base_to_cam_R=None):
         a = None if K4 is None else np.ascontiguousarray(K4, np.float64).reshape(4)
         b = None if base_to_cam_t is None else np.ascontiguousarray(base_to_cam_t, np.float64).reshape(3)
         c = None if base_to_cam_R is None else np.ascontiguousarray(base_to_cam_R, np.float64).reshape(9)
-        N.check(self._lib.reloc_set_camera(self._ctx, N.ptr(a), N.ptr(b), N.ptr(c)), "reloc_set_camera")
+        self._api.reloc_set_camera(self._ctx, a, b, c)
 
     def set_distortion(self, dist=()):
         """lens distortion of the fused tick, recording and accumulation: OpenCV's k1 k2 p1 p2 [k3 ...] (4, 5, 8, 12 or 14
         values, everything after k3 zero), () / None / all zero = pinhole"""
         d = np.ascontiguousarray(np.zeros(0) if dist is None else np.asarray(dist, np.float64).ravel())
-        N.check(self._lib.reloc_set_distortion(self._ctx, N.ptr(d) if d.size else None, int(d.size)), "reloc_set_distortion")
+        self._api.reloc_set_distortion(self._ctx, d if d.size else None, int(d.size))
 
     def get_distortion(self) -> np.ndarray:
         d = np.zeros(5)
-        N.check(self._lib.reloc_get_distortion(self._ctx, N.ptr(d)), "reloc_get_distortion")
+        self._api.reloc_get_distortion(self._ctx, d)
         return d
 
     def tick_debug(self):
         ids, nm, ni, ok = (np.zeros(MAX_CAND, np.int32) for _ in range(4))
-        n = C.c_int32(); rep = np.zeros(MAX_CAND); Rt = np.zeros((MAX_CAND, 12))
-        N.check(self._lib.reloc_tick_debug(self._ctx, N.ptr(ids), C.byref(n), N.ptr(nm), N.ptr(ni), N.ptr(ok), N.ptr(rep),
-                                           N.ptr(Rt)), "reloc_tick_debug")
+        n = i32(); rep = np.zeros(MAX_CAND); Rt = np.zeros((MAX_CAND, 12))
+        self._api.reloc_tick_debug(self._ctx, ids, n, nm, ni, ok, rep, Rt)
         k = n.value
         return dict(cand_ids=ids[:k].copy(), n_matches=nm[:k].copy(), n_inliers=ni[:k].copy(), ok=ok[:k].copy(),
                     reproj=rep[:k].copy(), Rt=Rt[:k].copy())
@@ -920,11 +875,10 @@ class Engine:
         """parity tap: the mutual match list and the 3-D / 2-D pairs of candidate slot `slot` of the last solve, as its PnP
         was given them (reloc_tick_debug_matches; synchronises)"""
         cap = 4096                                             # MAX_REC_ROWS: the largest record a database may hold
-        n = C.c_int32()
+        n = i32()
         qi = np.zeros(cap, np.int32); ti = np.zeros(cap, np.int32); dd = np.zeros(cap, np.int32)
         obj = np.zeros((cap, 3), np.float32); img = np.zeros((cap, 2), np.float32)
-        N.check(self._lib.reloc_tick_debug_matches(self._ctx, int(slot), C.byref(n), N.ptr(qi), N.ptr(ti), N.ptr(dd), N.ptr(obj),
-                                                   N.ptr(img)), "reloc_tick_debug_matches")
+        self._api.reloc_tick_debug_matches(self._ctx, int(slot), n, qi, ti, dd, obj, img)
         k = n.value
         return dict(n=k, qidx=qi[:k].copy(), tidx=ti[:k].copy(), dist=dd[:k].copy(), obj=obj[:k].copy(), img=img[:k].copy())
 
@@ -933,62 +887,55 @@ class Engine:
         img = self._frame(img, "tick")
         h, w = img.shape[:2]
         bp = np.ascontiguousarray(base_pose, np.float64).reshape(7)
-        anchor = np.zeros(7); n_inl = C.c_int32(); rep = C.c_float(); lm = C.c_int32(); oc = C.c_int32(); nc = C.c_int32()
-        N.check(self._lib.reloc_tick(self._ctx, N.ptr(img), w, h, int(order_rgb), N.ptr(bp), int(global_reloc), int(seed),
-                                     N.ptr(anchor), C.byref(n_inl), C.byref(rep), C.byref(lm), C.byref(oc), C.byref(nc)),
-                "reloc_tick")
+        anchor = np.zeros(7)
+        n_inl, rep, lm, oc, nc = N.outs(i32, f32, i32, i32, i32)
+        self._api.reloc_tick(self._ctx, img, w, h, int(order_rgb), bp, int(global_reloc), int(seed), anchor, n_inl, rep, lm, oc, nc)
         return dict(anchor_pose=anchor, n_inliers=n_inl.value, reproj=rep.value, lm_idx=lm.value, outcome=oc.value,
                     n_candidates=nc.value)
 
     def tick_dev(self, img_dev: int, w: int, h: int, base_pose, order_rgb=False, global_reloc=False, seed=0):
         """global_reloc: False / True or a RELOC_TICK_* mode (2 = local first, whole-database search if that finds nothing)"""
         bp = np.ascontiguousarray(base_pose, np.float64).reshape(7)
-        N.check(self._lib.reloc_tick_dev(self._ctx, C.c_void_p(img_dev), w, h, int(order_rgb), N.ptr(bp),
-                                         int(global_reloc), int(seed)), "reloc_tick_dev")
+        self._api.reloc_tick_dev(self._ctx, img_dev, w, h, int(order_rgb), bp, int(global_reloc), int(seed))
+
+    @staticmethod
+    def _batch(engines, imgs_dev=None, base_poses=None, seeds=None):
+        """the arguments the three batch entry points share: (checked view, n, context array, frame-address array or None,
+        base poses (n, 7) float64 or None, seeds (n,) uint64 or None)"""
+        n = len(engines)
+        ctxs = (C.c_void_p * n)(*[e._ctx for e in engines])
+        imgs = None if imgs_dev is None else (C.c_void_p * n)(*[int(p) for p in imgs_dev])
+        bp = None if base_poses is None else np.ascontiguousarray(base_poses, np.float64).reshape(n, 7)
+        sd = None if seeds is None else np.ascontiguousarray(seeds, np.uint64).reshape(n)
+        return engines[0]._api, n, ctxs, imgs, bp, sd
 
     @staticmethod
     def tick_batch_dev(engines, imgs_dev, w: int, h: int, base_poses, order_rgb=False, global_reloc=True, seeds=None):
         """n <= 8 frames through ONE whole-database scan launch: engines[i] processes imgs_dev[i]; the engines share a
         stream (set_stream) and a database (db_share).  Enqueue only; read engines[i].tick_result() afterwards."""
-        n = len(engines)
-        ctxs = (C.c_void_p * n)(*[e._ctx for e in engines])
-        imgs = (C.c_void_p * n)(*[int(p) for p in imgs_dev])
-        bp = np.ascontiguousarray(base_poses, np.float64).reshape(n, 7)
-        sd = None if seeds is None else np.ascontiguousarray(seeds, np.uint64).reshape(n)
-        lib = engines[0]._lib
-        N.check(lib.reloc_tick_batch_dev(ctxs, n, imgs, w, h, int(order_rgb), N.ptr(bp), int(global_reloc), N.ptr(sd)),
-                "reloc_tick_batch_dev")
+        api, n, ctxs, imgs, bp, sd = Engine._batch(engines, imgs_dev, base_poses, seeds)
+        api.reloc_tick_batch_dev(ctxs, n, imgs, w, h, int(order_rgb), bp, int(global_reloc), sd)
 
     # ---- sharded database, batched halves with the exchange in device memory (reloc_shard_*_dev) ----
     @staticmethod
     def shard_scan_batch_dev(engines, imgs_dev, w: int, h: int, base_poses, k: int, id_base: int, scan_out_dev: int, order_rgb=False):
         """ORB per frame + ONE scan launch + per-frame ranking for n <= 8 engines that share a stream and a shard; row f of
         scan_out_dev (2k + 2 int32) = k global ids, k counts, feature count, one pad word (never written).  Enqueue only."""
-        n = len(engines)
-        ctxs = (C.c_void_p * n)(*[e._ctx for e in engines])
-        imgs = (C.c_void_p * n)(*[int(p) for p in imgs_dev])
-        bp = None if base_poses is None else np.ascontiguousarray(base_poses, np.float64).reshape(n, 7)
-        lib = engines[0]._lib
-        N.check(lib.reloc_shard_scan_batch_dev(ctxs, n, imgs, int(w), int(h), int(order_rgb), N.ptr(bp), int(k), int(id_base),
-                                               C.c_void_p(scan_out_dev)), "reloc_shard_scan_batch_dev")
+        api, n, ctxs, imgs, bp, _ = Engine._batch(engines, imgs_dev, base_poses)
+        api.reloc_shard_scan_batch_dev(ctxs, n, imgs, int(w), int(h), int(order_rgb), bp, int(k), int(id_base), scan_out_dev)
 
     def shard_merge_dev(self, all_scan_dev: int, world: int, stride_rank: int, n: int, k: int, id_base: int, n_local: int,
                         win_gid_dev: int, cand_local_dev: int, n_feat_dev: int):
         """the merge every rank performs on the gathered rows, on this engine's stream (enqueue only)"""
-        N.check(self._lib.reloc_shard_merge_dev(self._ctx, C.c_void_p(all_scan_dev), int(world), int(stride_rank), int(n), int(k),
-                                                int(id_base), int(n_local), C.c_void_p(win_gid_dev), C.c_void_p(cand_local_dev),
-                                                C.c_void_p(n_feat_dev)), "reloc_shard_merge_dev")
+        self._api.reloc_shard_merge_dev(self._ctx, all_scan_dev, int(world), int(stride_rank), int(n), int(k), int(id_base),
+                                        int(n_local), win_gid_dev, cand_local_dev, n_feat_dev)
 
     @staticmethod
     def shard_solve_batch_dev(engines, cand_local_dev: int, k: int, base_poses, seeds, res_out: int):
         """matches + PnP + gates for the owned winners of every frame; result record f stored at res_out + 96 f (device
         or pinned host memory).  Enqueue only."""
-        n = len(engines)
-        ctxs = (C.c_void_p * n)(*[e._ctx for e in engines])
-        bp = np.ascontiguousarray(base_poses, np.float64).reshape(n, 7)
-        sd = None if seeds is None else np.ascontiguousarray(seeds, np.uint64).reshape(n)
-        N.check(engines[0]._lib.reloc_shard_solve_batch_dev(ctxs, n, C.c_void_p(cand_local_dev), int(k), N.ptr(bp), N.ptr(sd),
-                                                            C.c_void_p(res_out)), "reloc_shard_solve_batch_dev")
+        api, n, ctxs, _, bp, sd = Engine._batch(engines, None, base_poses, seeds)
+        api.reloc_shard_solve_batch_dev(ctxs, n, cand_local_dev, int(k), bp, sd, res_out)
 
     def _halves_scratch(self):
         """the engine's own buffers for the scan / solve halves, made on first use: MAX_CAND ids, MAX_CAND counts and the
@@ -1008,29 +955,29 @@ class Engine:
         with a pixel format: a frame of 1, 2 or 4 bytes per pixel, stride in bytes)
         resident in device memory (reloc_orb_frame_dev); returns the number of keypoints (synchronises).  Descriptors /
         coordinates stay on the device; frame_debug_plane() reads planes."""
-        N.check(self._lib.reloc_orb_frame_dev(self._ctx, C.c_void_p(img_dev), int(w), int(h), int(stride or self._frame_bpp() * w),
-                                              int(order_rgb), int(nfeatures)), "reloc_orb_frame_dev")
+        self._api.reloc_orb_frame_dev(self._ctx, img_dev, int(w), int(h), int(stride or self._frame_bpp() * w), int(order_rgb),
+                                      int(nfeatures))
         nf = np.empty(1, np.int32)
-        N.check(self._lib.reloc_d2h(self._ctx, N.ptr(nf), C.c_void_p(self._lib.reloc_frame_count_dev(self._ctx)), 4), "reloc_d2h")
-        self.sync()
+        self.d2h(nf, self._lib.reloc_frame_count_dev(self._ctx))
         return int(nf[0])
 
     def _frame_bpp(self):
-        """bytes per pixel of the frames of the image chain's entry points"""
-        if self._bayer:
+        """bytes per pixel of the frames of the image chain's entry points, as the context holds the two settings"""
+        if self.get_bayer():
             return 1
-        return 3 if self.pixel_format is None else int(np.prod(PIXEL_FORMATS[self.pixel_format][1], dtype=int))
+        fmt = self.get_pixel_format()
+        return 3 if fmt is None else int(np.prod(PIXEL_FORMATS[fmt][1], dtype=int))
 
     def orb_features(self):
         """descriptors and coordinates of the frame last extracted on the device (orb_frame_dev / a tick), copied to the host"""
         nf = np.empty(1, np.int32)
-        self.d2h(nf, int(self._lib.reloc_frame_count_dev(self._ctx)))
+        self.d2h(nf, self._lib.reloc_frame_count_dev(self._ctx))
         n = min(int(nf[0]), self.max_feat)
         desc = np.empty((n, 32), np.uint8)
         xy = np.empty((n, 2), np.float32)
         if n:
-            self.d2h(desc, int(self._lib.reloc_frame_desc_dev(self._ctx)))
-            self.d2h(xy, int(self._lib.reloc_frame_xy_dev(self._ctx)))
+            self.d2h(desc, self._lib.reloc_frame_desc_dev(self._ctx))
+            self.d2h(xy, self._lib.reloc_frame_xy_dev(self._ctx))
         return dict(n=n, desc=desc, xy=xy)
 
     def tick_scan_into(self, img_dev: int, w: int, h: int, base_pose, k: int, ids_dev: int, counts_dev: int, nfeat_dev: int,
@@ -1038,15 +985,13 @@ class Engine:
         """ORB + shard scan + local top-k, everything left in caller-owned device memory (k ids, k counts, 1 feature count);
         enqueue only"""
         bp = None if base_pose is None else np.ascontiguousarray(base_pose, np.float64).reshape(7)
-        N.check(self._lib.reloc_tick_scan_dev(self._ctx, C.c_void_p(img_dev), w, h, int(order_rgb), N.ptr(bp),
-                                              C.c_void_p(ids_dev), C.c_void_p(counts_dev), int(k)), "reloc_tick_scan_dev")
-        self.d2d(nfeat_dev, int(self._lib.reloc_frame_count_dev(self._ctx)), 4)
+        self._api.reloc_tick_scan_dev(self._ctx, img_dev, w, h, int(order_rgb), bp, ids_dev, counts_dev, int(k))
+        self.d2d(nfeat_dev, self._lib.reloc_frame_count_dev(self._ctx), 4)
 
     def tick_solve_from(self, cand_ids_dev: int, n: int, base_pose, check_consistency: bool, seed: int = 0):
         """matches + PnP + gates for the LOCAL record ids listed in device memory (-1 entries skipped); enqueue only"""
         bp = np.ascontiguousarray(base_pose, np.float64).reshape(7)
-        N.check(self._lib.reloc_tick_solve_dev(self._ctx, C.c_void_p(cand_ids_dev), int(n), N.ptr(bp), int(check_consistency),
-                                               int(seed)), "reloc_tick_solve_dev")
+        self._api.reloc_tick_solve_dev(self._ctx, cand_ids_dev, int(n), bp, int(check_consistency), int(seed))
 
     def tick_scan_fetch(self, k: int = 25):
         """(local record ids (k,), counts (k,), n_features) of the last enqueued scan, -1 / 0 padded (synchronises the stream)."""
@@ -1072,9 +1017,8 @@ class Engine:
         return self.tick_result()
 
     def tick_result(self):
-        anchor = np.zeros(7); n_inl = C.c_int32(); rep = C.c_double(); lm = C.c_int32(); oc = C.c_int32(); nc = C.c_int32()
-        nf = C.c_int32(); rl = C.c_int32()
-        N.check(self._lib.reloc_tick_result_ex(self._ctx, N.ptr(anchor), C.byref(n_inl), C.byref(rep), C.byref(lm),
-                                               C.byref(oc), C.byref(nc), C.byref(nf), C.byref(rl)), "reloc_tick_result_ex")
+        anchor = np.zeros(7)
+        n_inl, rep, lm, oc, nc, nf, rl = N.outs(i32, f64, i32, i32, i32, i32, i32)
+        self._api.reloc_tick_result_ex(self._ctx, anchor, n_inl, rep, lm, oc, nc, nf, rl)
         return dict(anchor_pose=anchor, n_inliers=n_inl.value, reproj=float(np.float32(rep.value)), lm_idx=lm.value,
                     outcome=oc.value, n_candidates=nc.value, n_features=nf.value, relocating=bool(rl.value))
