@@ -108,7 +108,8 @@ int  reloc_timer_end(reloc_ctx *ctx, float *ms);
 #define RELOC_PROF_ORB      2
 #define RELOC_PROF_PNP      3
 #define RELOC_PROF_STEREO   4   /* k_stereo_depth (reloc_stereo_depth and the stereo recording / accumulation) */
-#define RELOC_PROF_N        5
+#define RELOC_PROF_STEREO_DENSE 5 /* k_stereo_dense + k_stereo_dense_finish with the right map's reset (the dense stereo entry points) */
+#define RELOC_PROF_N        6
 int  reloc_profile_enable(reloc_ctx *ctx, int on);
 int  reloc_profile_get(reloc_ctx *ctx, int which, float *total_ms, int32_t *launches);
 
@@ -455,6 +456,35 @@ int reloc_tick_accumulate_stereo_dev(reloc_ctx *ctx, reloc_ctx *right, const uin
 /* Parity tap: the last stereo pass of the context, per keypoint of the frame's ORB output (*n of them; arrays of max_feat
  * entries, any may be NULL).  Synchronises the context's stream. */
 int reloc_stereo_debug(reloc_ctx *ctx, uint16_t *depth_mm, float *disparity, uint8_t *status, int32_t *n);
+
+/* ---- dense stereo depth (include/reloc_spec.h, "STEREO, dense") ----------------------------------- */
+/* The same matcher at every integer pixel of the working frame: a depth image for everything that takes one
+ * (reloc_depth_points, the depth-image form of reloc_record_frame, a log).  Three planes of the working-frame size with
+ * dense rows: depth_mm uint16 (0 = no depth), disparity float32 (0 where status != 0), status uint8 (the seven codes above).
+ * The plane at (rint x, rint y) is what reloc_stereo_depth returns for keypoint (x, y).  The buffers are taken on the first
+ * dense call of a context; a context that never makes one allocates and launches nothing of it.
+ * reloc_stereo_depth_image is the dense twin of reloc_stereo_depth: two gray planes of w x h (w, h >= 11, within the
+ * capacity, else RELOC_E_CAPACITY), rows stride bytes apart, explicit parameters with the same checks.  disparity and status
+ * may be NULL.  Host pointers; synchronous.  Independent of reloc_set_stereo. */
+int reloc_stereo_depth_image(reloc_ctx *ctx, const uint8_t *left, const uint8_t *right, int w, int h, int stride, double fx,
+                             double baseline_m, int min_disparity, int num_disparities, int uniqueness, int lr_check,
+                             uint16_t *depth_mm, float *disparity, uint8_t *status);
+/* A pair of host frames (w, h >= 64) through the gray half of both eyes' image chains, paired as reloc_record_frame_stereo pairs
+ * them (right: a context of its own with that eye's chain, its own stream, ordered by events; the same agreement checks), and
+ * no ORB; then the dense pass with ctx's reloc_set_stereo setting and the context camera's fx.  RELOC_E_STATE while stereo is
+ * off on ctx, RELOC_E_ARG for right == ctx.  The plane stays on the device (reloc_stereo_dense_debug, reloc_stereo_frame_points);
+ * depth_mm (working-frame size, may be NULL) receives a copy.  *out_w x *out_h (may be NULL): the working frame.  Synchronous. */
+int reloc_stereo_frame_depth(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img, const uint8_t *img_right, int w, int h,
+                             int order, uint16_t *depth_mm, int32_t *out_w, int32_t *out_h);
+/* The same pass, then the obstacle cloud of reloc_depth_points from the plane on the device with the context camera's K4:
+ * the depth makes no trip through the host.  step > 0; points holds ceil(W/step) * ceil(H/step) rows of 3 floats of the
+ * working frame W x H; the output contract is that of reloc_depth_points. */
+int reloc_stereo_frame_points(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img, const uint8_t *img_right, int w, int h,
+                              int order, int step, float zmin, float zmax, float *points, int32_t *n_out);
+/* Parity tap: the three planes of the context's last dense pass, *w x *h of them (arrays of the context's capacity
+ * max_w x max_h, or of the pass's size; any pointer may be NULL).  RELOC_E_STATE before the first pass.  Synchronises the
+ * context's stream. */
+int reloc_stereo_dense_debug(reloc_ctx *ctx, uint16_t *depth_mm, float *disparity, uint8_t *status, int32_t *w, int32_t *h);
 
 /* ---- fused tick ----------------------------------------------------------------------------- */
 #define RELOC_TICK_LOCAL   0   /* candidates by VIO distance / heading only                          M:293-302 */

@@ -343,7 +343,21 @@
  * The result is what a depth camera would have delivered at that pixel: uint16 millimetres, 0 = no depth.  From there the
  * recorder's and the accumulation's arithmetic applies unchanged ((float)mm / 1000.0f, range gates, back-projection, lens
  * model).  The recorder's 3 x 3 depth-variance gate has no meaning for a per-keypoint depth and does not apply (sd = 0):
- * uniqueness and the left-right check take its place as the guard against depth discontinuities. */
+ * uniqueness and the left-right check take its place as the guard against depth discontinuities.
+ *
+ * STEREO, dense: the depth image of the pair.  For every integer pixel (u, v) of the working frame, steps 1 to 8 with x = u,
+ * y = v (step 1 rounds nothing); no new parameter, no new status.  Three planes of the working-frame size w x h, w, h >= 2R + 1:
+ *   depth_mm   uint16, 0 = no depth;   disparity  float32, 0 where status is not 0;   status  uint8, the seven codes below.
+ * The plane at (rint x, rint y) is, by construction, what the per-keypoint form returns for keypoint (x, y).
+ *   cost volume  all seven statuses can be read off one left-referenced volume C(v, u, d) = sum over j, i in -R..R of
+ *              |L[v + j, u + i] - R[v + j, u - d + i]|, defined for R <= v < h - R, R <= u < w - R, d in D(u).  The search of
+ *              step 6 from pixel (u, v) with xr = u - d* is C'(d') = C(v, xr + d', d'): the same absolute differences, summed
+ *              over the same window.  So with the row's right disparity map dR(v, xr) = argmin over d' of C(v, xr + d', d'),
+ *              lowest d' on ties, over min_disparity <= d' < min_disparity + num_disparities with xr + d' + R < w, step 6
+ *              is |dR(v, u - d*) - d*| > 1.  The members of that search are exactly the defined entries of the volume on the
+ *              diagonal u - d = xr (xr >= R holds wherever step 6 is reached), those of pixels that fail step 2 included.
+ * A depth image made this way serves everything that takes one: the obstacle cloud (every step-th pixel, 0.3 to 10 m), the
+ * depth-image form of the recorder with its 3 x 3 variance gate, a log. */
 #define RELOC_STEREO_R                 5
 #define RELOC_STEREO_MIN_DISPARITY_MAX 1024
 #define RELOC_STEREO_NUM_DISP_MIN      8

@@ -128,6 +128,11 @@ SIGNATURES = {
     "reloc_record_frame_stereo": (C.c_int, [c_ctx, c_ctx, P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P]),
     "reloc_tick_accumulate_stereo_dev": (C.c_int, [c_ctx, c_ctx, P, C.c_int, C.c_int, C.c_int, P, C.c_int]),
     "reloc_stereo_debug": (C.c_int, [c_ctx, P, P, P, P]),
+    "reloc_stereo_depth_image": (C.c_int, [c_ctx, P, P, C.c_int, C.c_int, C.c_int, f64, f64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           P, P, P]),
+    "reloc_stereo_frame_depth": (C.c_int, [c_ctx, c_ctx, P, P, C.c_int, C.c_int, C.c_int, P, P, P]),
+    "reloc_stereo_frame_points": (C.c_int, [c_ctx, c_ctx, P, P, C.c_int, C.c_int, C.c_int, C.c_int, f32, f32, P, P]),
+    "reloc_stereo_dense_debug": (C.c_int, [c_ctx, P, P, P, P, P]),
     "reloc_tick_debug": (C.c_int, [c_ctx, P, P, P, P, P, P, P]),
     "reloc_tick_debug_matches": (C.c_int, [c_ctx, C.c_int, P, P, P, P, P, P]),
     "reloc_tick": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, P, C.c_int, u64, P, P, P, P, P, P]),

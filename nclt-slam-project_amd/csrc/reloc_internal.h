@@ -384,6 +384,18 @@ struct StereoState {
     hipEvent_t left_ready = nullptr;     // this context's stream so far: the right frame's copy, the last stereo kernel (which
                                          // reads the right chain's planes); the next right chain waits for it
     bool ran = false;                    // a stereo pass was enqueued: mm / disp / status belong to a frame (reloc_stereo_debug)
+    // Dense stereo depth ("STEREO, dense"): one block of max_w x max_h pixels, taken on the first dense call of the context
+    // (stereo_dense_alloc); a context that never asks for a dense plane has none of it.
+    struct Dense {
+        uint8_t *block = nullptr;        // the pointers below lie in it
+        uint32_t *rmap = nullptr;        // the right disparity map as cost << 11 | d' keys, KEY_NONE = no candidate
+        uint2 *best = nullptr;           // per pixel d* | C(d*) << 16, C(d* - 1) | C(d* + 1) << 16: k_stereo_dense to k_stereo_dense_finish
+        float *disp = nullptr;
+        uint16_t *mm = nullptr;
+        uint8_t *status = nullptr;
+        uint8_t *left = nullptr;         // left eye's gray plane where its chain has no stage on (dense rows)
+        int w = 0, h = 0;                // the last dense pass (reloc_stereo_dense_debug); 0 = none yet
+    } dense;
     bool on() const { return baseline > 0.0; }
     // the settings, no buffer: reloc_set_stereo returns at once where nothing changes
     bool same(const StereoState &o) const
@@ -630,5 +642,9 @@ int image_gray_plain(reloc_ctx *c, const uint8_t *src, int w, int h, int sstride
 // working frame.  stereo_release: the events of a context that had stereo on.
 int stereo_frame(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img_right_dev, int w, int h, int order, int *ww, int *wh);
 void stereo_release(reloc_ctx *ctx);
+// Dense stereo depth: both eyes' frames (ctx->frame_img, right->frame_img, w x h as handed in) through the gray half of their
+// chains, each on its own stream, no ORB; then k_stereo_dense and k_stereo_dense_finish on ctx's stream into ctx->stereo.dense
+// (mm: dense rows of *ww uint16).  Checks stereo on, right != ctx, capacity and the chains' agreement.
+int stereo_dense_frame(reloc_ctx *ctx, reloc_ctx *right, int w, int h, int order, int *ww, int *wh);
 // PnP-RANSAC of every context's candidates with the matcher parameters of ctxs[0]; seeds: one per frame, or NULL (reloc_pnp.hip)
 int pnp_run_candidates(reloc_ctx *const *ctxs, int n, const uint64_t *seeds, bool latency);

@@ -561,3 +561,37 @@ RELOC_API int reloc_depth_points(reloc_ctx *ctx, const void *depth, int is_f32, 
     *n_out = n;
     return RELOC_OK;
 }
+
+// The cloud of a stereo pair: the dense pass of reloc_stereo.hip, then k_depth_points on its plane where it lies.
+RELOC_API int reloc_stereo_frame_points(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img, const uint8_t *img_right, int w, int h,
+                                        int order, int step, float zmin, float zmax, float *points, int32_t *n_out)
+{
+    ARG_CHECK_CTX(ctx, right && img && img_right && points && n_out && w >= 64 && h >= 64 && step > 0, "reloc_stereo_frame_points");
+    if (!ctx->stereo.on()) { reloc_set_error("stereo is off on this context (reloc_set_stereo)"); return RELOC_E_STATE; }
+    if (right == ctx) { reloc_set_error("bad argument: the right eye needs a context of its own"); return RELOC_E_ARG; }
+    if (w > ctx->max_w || h > ctx->max_h || w > right->max_w || h > right->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
+    *n_out = 0;
+    HostStaging st{ctx};
+    // the working frame is no larger than the frame handed in: the slot holds either's grid
+    const int64_t cap = (int64_t)((w + step - 1) / step) * ((h + step - 1) / step);
+    float *dout = st.slot<float>(6, cap * 3 + 4);
+    if (st.rc) return st.rc;
+    int32_t *o_n = (int32_t *)(dout + cap * 3);
+    st.upload(ctx->frame_img, img, (int64_t)w * h * image_chain_frame_bpp(ctx));
+    bool right_busy = false;       // the right context's stream holds a copy from the caller's memory
+    st.run([&] {
+        right_busy = true;
+        HIP_TRY(hipMemcpyAsync(right->frame_img, img_right, (size_t)w * h * image_chain_frame_bpp(right), hipMemcpyHostToDevice, right->stream));
+        return stereo_dense_frame(ctx, right, w, h, order, &w, &h);      // from here on the working frame
+    });
+    const double *K4 = ctx->cam.K4;
+    st.launch(k_depth_points, dim3(1), dim3(1024), (const void *)ctx->stereo.dense.mm, 0, w, h, w, step, (float)K4[2], (float)K4[3],
+              (float)K4[0], (float)K4[1], zmin, zmax, dout, o_n);
+    const int32_t n = st.count(o_n);
+    if (n > 0) st.download(points, dout, (int64_t)n * 12);
+    const int rc = st.finish();
+    if (right_busy) (void)hipStreamSynchronize(right->stream);
+    if (rc) return rc;
+    *n_out = n;
+    return RELOC_OK;
+}

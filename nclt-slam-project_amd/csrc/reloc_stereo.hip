@@ -1,6 +1,6 @@
-// reloc_stereo.hip -- sparse stereo depth on gfx950: the depth of the ORB keypoints from the other eye of a rectified pair
-// (include/reloc_spec.h, "STEREO").  The matcher is this project's own; the spec states it in integers and
-// tests/stereo_ref.py restates it bit for bit.
+// reloc_stereo.hip -- stereo depth on gfx950: the depth of the ORB keypoints (sparse) or of every pixel (dense, second half of
+// this file) from the other eye of a rectified pair (include/reloc_spec.h, "STEREO", "STEREO, dense").  The matcher is this
+// project's own; the spec states it in integers and tests/stereo_ref.py restates it bit for bit.
 //   k_stereo_depth   one wave per keypoint, lanes over disparities, 64 per pass (num_disparities > 64: further passes of the
 //                    same wave).  Per pass the 11 rows of the searched eye that the 64 candidates cover (74 bytes each) and
 //                    the 11 x 11 patch of the other eye are staged in LDS, about 1 KB per wave.  A lane's patch row is three
@@ -304,10 +304,11 @@ RELOC_API int reloc_stereo_depth(reloc_ctx *ctx, const uint8_t *left, const uint
     return st.finish();
 }
 
-int stereo_frame(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img_right_dev, int w, int h, int order, int *ww, int *wh)
+// What a stereo pass checks of its pair of contexts before it enqueues anything: stereo on, two contexts of one device and one
+// gray conversion, the frame within both capacities, the two chains in agreement as in a batch; *ww x *wh: the working frame.
+static int stereo_pair_check(reloc_ctx *ctx, reloc_ctx *right, int w, int h, int *ww, int *wh)
 {
-    StereoState &s = ctx->stereo;
-    if (!s.on()) { reloc_set_error("stereo is off on this context (reloc_set_stereo)"); return RELOC_E_STATE; }
+    if (!ctx->stereo.on()) { reloc_set_error("stereo is off on this context (reloc_set_stereo)"); return RELOC_E_STATE; }
     if (right == ctx) { reloc_set_error("bad argument: the right eye needs a context of its own"); return RELOC_E_ARG; }
     if (right->device != ctx->device || right->prm.gray_coeff_bits != ctx->prm.gray_coeff_bits) {
         reloc_set_error("stereo: the right eye's context is on another device or has another gray_coeff_bits");
@@ -317,7 +318,13 @@ int stereo_frame(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img_right_dev,
     reloc_ctx *pair[2] = {ctx, right};
     *ww = w; *wh = h;
     if (int rc = image_chain_check(pair, 2, true, ww, wh)) return rc;
-    if (int rc = image_chain_check_prepared(pair, 1, 2, true, *ww, *wh)) return rc;
+    return image_chain_check_prepared(pair, 1, 2, true, *ww, *wh);
+}
+
+int stereo_frame(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img_right_dev, int w, int h, int order, int *ww, int *wh)
+{
+    StereoState &s = ctx->stereo;
+    if (int rc = stereo_pair_check(ctx, right, w, h, ww, wh)) return rc;
     if (ctx->orb.w != *ww || ctx->orb.h != *wh) {
         reloc_set_error("stereo: the left eye's last ORB frame is %dx%d, the right eye's working frame %dx%d", ctx->orb.w, ctx->orb.h, *ww, *wh);
         return RELOC_E_STATE;
@@ -361,5 +368,322 @@ RELOC_API int reloc_stereo_debug(reloc_ctx *ctx, uint16_t *depth_mm, float *disp
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
     *n = k;
+    return RELOC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Dense stereo depth (include/reloc_spec.h, "STEREO, dense"): the same specification at every integer pixel.
+//   k_stereo_dense<NP>     a workgroup of four waves takes DT_W output columns of one row, a wave 64 of them; lanes over
+//                          disparities, NP = ceil(num_disparities / 64) of them per lane.  The 11 rows that the row's windows
+//                          cover are staged in LDS column by column: the 11 bytes of a column in three dwords (16 bytes per
+//                          column), so that the SAD of one column of the window -- 11 absolute differences -- is three
+//                          v_sad_u8 on one broadcast LDS read of the left column x and one read of the right column
+//                          x - d (ds_read_b96), which neighbouring lanes take from neighbouring entries.  A wave walks along x: the
+//                          window's cost is the running sum of its last 11 column SADs (a ring in registers; the walk is
+//                          unrolled by 11 so that the ring's index is a constant), one addition and one subtraction per
+//                          (pixel, disparity) where k_stereo_depth spends 33 v_sad_u8 on 44 LDS dwords.  Per pixel the keys
+//                          cost << 11 | d of the lanes with d <= d_hi(u) = min(d_max, u - R) -- a per-pixel mask, the walk itself
+//                          never looks at the edge -- are reduced as in k_stereo_depth (two minima in the DPP network, the
+//                          parabola's neighbours by readlane); every branch on a status is wave-uniform.  The same keys
+//                          go, by ds_min_u32, into the workgroup's piece of the right disparity map at column u - d
+//                          (neighbouring lanes, neighbouring words) and from there with one global atomic minimum per
+//                          column into the row's map: C'(d') = C(v, xr + d', d'), so the left-right search needs no cost of
+//                          its own.  Writes the status of steps 1 to 5 and d*, C(d* - 1), C(d*), C(d* + 1) per pixel.
+//   k_stereo_dense_finish  lanes over pixels: step 6 from the right map, steps 7 and 8, the three planes.
+// The walk starts 10 columns before a wave's first pixel (16 % more column SADs at 64 columns per wave); a row is staged
+// once per output row (its bytes come from L2 eleven times), which costs about 200 of a lane's 2 000 to 8 000 instructions.
+constexpr int DT_W = 256;                                   // output columns of a workgroup
+constexpr int DT_L = DT_W + 2 * SR;                         // staged columns of the left eye
+constexpr int DT_R = DT_L + RELOC_STEREO_NUM_DISP_MAX;      // ... of the right eye, and words of the right map's piece
+static_assert(STEREO_PASSES * 64 == RELOC_STEREO_NUM_DISP_MAX, "a lane holds num_disparities / 64 disparities");
+
+// the bytes of column x, rows v - R .. v + R, in three dwords (row v - R in the low byte of .x)
+__device__ __forceinline__ uint4 stereo_pack_column(const uint8_t *__restrict__ img, int stride, int v, int x)
+{
+    const uint8_t *p = img + (size_t)(v - SR) * stride + x;
+    uint32_t r[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < SP; ++j) r[j >> 2] |= (uint32_t)p[(size_t)j * stride] << (8 * (j & 3));
+    return make_uint4(r[0], r[1], r[2], 0u);
+}
+
+// the cost of disparity dmin + i from the lane that holds it (i is wave-uniform): a readlane per register, then a choice
+// between scalars, which keeps the costs in registers
+template <int NP>
+__device__ __forceinline__ int stereo_cost_of(const int (&cost)[NP], int i)
+{
+    int r = __builtin_amdgcn_readlane(cost[0], i & 63);
+#pragma unroll
+    for (int q = 1; q < NP; ++q) {
+        const int t = __builtin_amdgcn_readlane(cost[q], i & 63);
+        r = (i >> 6) == q ? t : r;
+    }
+    return r;
+}
+
+template <int NP>
+__global__ __launch_bounds__(256) void k_stereo_dense(const uint8_t *__restrict__ left, int lstride, const uint8_t *__restrict__ right,
+                                                      int rstride, StereoParams p, uint32_t *__restrict__ rmap,
+                                                      uint2 *__restrict__ o_best, uint8_t *__restrict__ o_status)
+{
+    __shared__ uint4 s_l[DT_L];
+    __shared__ uint4 s_r[DT_R];
+    __shared__ unsigned s_dr[DT_R];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int w = p.w, v = blockIdx.y, U0 = blockIdx.x * DT_W, U1 = min(U0 + DT_W, w);
+    const int ulo = max(U0, SR), uhi = min(U1, w - SR);              // the workgroup's pixels that pass step 1: ulo <= u < uhi
+    const size_t row = (size_t)v * w;
+    if (v < SR || v >= p.h - SR || ulo >= uhi) {                      // workgroup-uniform
+        for (int u = U0 + tid; u < U1; u += 256) o_status[row + u] = RELOC_STEREO_BORDER;
+        return;
+    }
+    const int dmin = p.min_disp, dmax = dmin + p.num_disp - 1;
+    // staged columns: the left eye's xlo .. xlo + nl - 1 (all inside the row), the right eye's rb .. rb + nr - 1, which the
+    // lanes of the last disparities reach; a column left of the image is 0 and is not fetched
+    const int xlo = ulo - SR, nl = uhi - ulo + 2 * SR;
+    const int rb = xlo - dmin - 64 * NP + 1, nr = nl + 64 * NP - 1;
+    for (int e = tid; e < nl; e += 256) s_l[e] = stereo_pack_column(left, lstride, v, xlo + e);
+    for (int e = tid; e < nr; e += 256) {
+        const int x = rb + e;
+        s_r[e] = x >= 0 ? stereo_pack_column(right, rstride, v, x) : make_uint4(0u, 0u, 0u, 0u);
+        s_dr[e] = KEY_NONE;
+    }
+    __syncthreads();
+    const int S0 = U0 + 64 * wave;
+    const int wlo = max(S0, SR), whi = min(S0 + 64, uhi);             // the wave's pixels
+    if (S0 + lane < U1 && (S0 + lane < SR || S0 + lane >= w - SR)) o_status[row + S0 + lane] = RELOC_STEREO_BORDER;
+    if (wlo < whi) {                                                  // wave-uniform
+        int ring[NP][SP], cost[NP];
+#pragma unroll
+        for (int q = 0; q < NP; ++q) {
+            cost[q] = 0;
+#pragma unroll
+            for (int k = 0; k < SP; ++k) ring[q][k] = 0;
+        }
+        const int xend = whi + SR;
+        const int ebase = 64 * NP - 1 - lane - xlo;                  // entry of column x - d of chunk q: x + ebase - 64 q
+        for (int x0 = wlo - SR; x0 < xend; x0 += SP) {
+#pragma unroll
+            for (int k = 0; k < SP; ++k) {
+                const int x = x0 + k, u = x - SR;
+                if (x < xend) {
+                    const uint4 lc = s_l[x - xlo];
+#pragma unroll
+                    for (int q = 0; q < NP; ++q) {
+                        const uint4 rc = s_r[x + ebase - 64 * q];
+                        unsigned cs = __builtin_amdgcn_sad_u8(lc.x, rc.x, 0u);
+                        cs = __builtin_amdgcn_sad_u8(lc.y, rc.y, cs);
+                        cs = __builtin_amdgcn_sad_u8(lc.z, rc.z, cs);
+                        cost[q] += (int)cs - ring[q][k];
+                        ring[q][k] = (int)cs;
+                    }
+                    if (u >= wlo) {
+                        // ---- steps 2-5 of pixel (u, v); cost[q] = C(d) of d = dmin + 64 q + lane ----
+                        const int dhi = min(dmax, u - SR);
+                        unsigned key = KEY_NONE;
+#pragma unroll
+                        for (int q = 0; q < NP; ++q) {
+                            const int d = dmin + 64 * q + lane;
+                            if (d <= dhi) {
+                                const unsigned kq = ((unsigned)cost[q] << 11) | (unsigned)d;
+                                key = min(key, kq);
+                                if (p.lr) atomicMin(&s_dr[u - d - rb], kq);
+                            }
+                        }
+                        int status = RELOC_STEREO_OK, dstar = 0, a = 0, b = 0, c = 0;
+                        if (dhi - dmin + 1 < 3) status = RELOC_STEREO_RANGE;
+                        else {
+                            key = wave_min_u32(key);
+                            dstar = (int)(key & 0x7FFu);
+                            b = (int)(key >> 11);
+                            if (dstar == dmin || dstar == dhi) status = RELOC_STEREO_EDGE;
+                            else {
+                                unsigned key2 = KEY_NONE;
+#pragma unroll
+                                for (int q = 0; q < NP; ++q) {
+                                    const int d = dmin + 64 * q + lane;
+                                    if (d <= dhi && abs(d - dstar) >= 2) key2 = min(key2, ((unsigned)cost[q] << 11) | (unsigned)d);
+                                }
+                                key2 = wave_min_u32(key2);
+                                if (key2 != KEY_NONE && (int)(key2 >> 11) * (100 - p.uniq) <= b * 100) status = RELOC_STEREO_UNIQUENESS;
+                                else {
+                                    a = stereo_cost_of<NP>(cost, dstar - 1 - dmin);
+                                    c = stereo_cost_of<NP>(cost, dstar + 1 - dmin);
+                                }
+                            }
+                        }
+                        if (lane == 0) {
+                            o_status[row + u] = (uint8_t)status;
+                            o_best[row + u] = make_uint2((unsigned)dstar | ((unsigned)b << 16), (unsigned)a | ((unsigned)c << 16));
+                        }
+                    }
+                }
+            }
+        }
+    }
+    if (!p.lr) return;
+    __syncthreads();
+    // the workgroup's piece of the row's right map: column rb + e; a key exists only where 0 <= R <= rb + e < w
+    for (int e = tid; e < nr; e += 256) {
+        const unsigned k = s_dr[e];
+        if (k != KEY_NONE) atomicMin(&rmap[row + rb + e], k);
+    }
+}
+
+// pixel i of the w x h planes: step 6 from the right map, steps 7 and 8
+__global__ __launch_bounds__(256) void k_stereo_dense_finish(StereoParams p, const uint32_t *__restrict__ rmap,
+                                                             const uint2 *__restrict__ best, uint8_t *__restrict__ status,
+                                                             uint16_t *__restrict__ o_mm, float *__restrict__ o_disp)
+{
+    const int64_t n = (int64_t)p.w * p.h, i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    int st = status[i];
+    uint16_t mm_out = 0;
+    float disp_out = 0.f;
+    if (st == RELOC_STEREO_OK) {
+        const uint2 t = best[i];
+        const int dstar = (int)(t.x & 0xFFFFu), b = (int)(t.x >> 16), a = (int)(t.y & 0xFFFFu), c = (int)(t.y >> 16);
+        if (p.lr && abs((int)(rmap[i - dstar] & 0x7FFu) - dstar) > 1) st = RELOC_STEREO_LR;
+        else {
+            const int den = a + c - 2 * b;
+            const float delta = den <= 0 ? 0.f : __fdiv_rn((float)(a - c), (float)(2 * den));
+            const float disp = __fadd_rn((float)dstar, delta);
+            const double z = __ddiv_rn(__dmul_rn(p.fx, p.baseline), (double)disp);
+            const double mm = rint(__dmul_rn(z, 1000.0));
+            if (mm > 65535.0) st = RELOC_STEREO_FAR;
+            else { mm_out = (uint16_t)mm; disp_out = disp; }
+        }
+        if (st != RELOC_STEREO_OK) status[i] = (uint8_t)st;
+    }
+    o_mm[i] = mm_out;
+    o_disp[i] = disp_out;
+}
+
+// the context's dense block, on its first dense call; a failure leaves the context without one
+static int stereo_dense_alloc(reloc_ctx *ctx)
+{
+    StereoState::Dense &d = ctx->stereo.dense;
+    if (d.block) return RELOC_OK;
+    const int64_t px = (int64_t)ctx->max_w * ctx->max_h;
+    uint8_t *blk = nullptr;
+    if (int rc = ctx_dev_alloc(ctx, &blk, px * 20)) return rc;
+    d.block = blk;
+    d.best = (uint2 *)blk; d.rmap = (uint32_t *)(blk + px * 8); d.disp = (float *)(blk + px * 12);
+    d.mm = (uint16_t *)(blk + px * 16); d.status = blk + px * 18; d.left = blk + px * 19;
+    return RELOC_OK;
+}
+
+// both kernels on ctx's stream, into ctx's dense planes (dense rows of p.w); the planes of the eyes are device pointers
+static int stereo_dense_launch(reloc_ctx *ctx, const uint8_t *left, int lstride, const uint8_t *right, int rstride, const StereoParams &p)
+{
+    StereoState::Dense &d = ctx->stereo.dense;
+    const int64_t px = (int64_t)p.w * p.h;
+    const int np = (p.num_disp + 63) / 64;
+    auto kern = np == 1 ? k_stereo_dense<1> : np == 2 ? k_stereo_dense<2> : np == 3 ? k_stereo_dense<3> : k_stereo_dense<4>;
+    reloc_prof_begin(ctx, RELOC_PROF_STEREO_DENSE);
+    const hipError_t reset = p.lr ? hipMemsetAsync(d.rmap, 0xFF, (size_t)px * 4, ctx->stream) : hipSuccess;      // KEY_NONE
+    hipLaunchKernelGGL(kern, dim3((p.w + DT_W - 1) / DT_W, p.h), dim3(256), 0, ctx->stream, left, lstride, right, rstride, p, d.rmap,
+                       d.best, d.status);
+    hipLaunchKernelGGL(k_stereo_dense_finish, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, ctx->stream, p, d.rmap, d.best,
+                       d.status, d.mm, d.disp);
+    reloc_prof_end(ctx, RELOC_PROF_STEREO_DENSE);
+    HIP_TRY(reset);
+    HIP_TRY(hipGetLastError());
+    d.w = p.w; d.h = p.h;
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_stereo_depth_image(reloc_ctx *ctx, const uint8_t *left, const uint8_t *right, int w, int h, int stride, double fx,
+                                       double baseline_m, int min_disparity, int num_disparities, int uniqueness, int lr_check,
+                                       uint16_t *depth_mm, float *disparity, uint8_t *status)
+{
+    ARG_CHECK_CTX(ctx, left && right && depth_mm && w >= SP && h >= SP && stride >= w, "reloc_stereo_depth_image");
+    if (!(fx - fx == 0.0) || fx <= 0.0) { reloc_set_error("bad argument: stereo fx %g is not finite and > 0", fx); return RELOC_E_ARG; }
+    if (int rc = stereo_args_check(baseline_m, min_disparity, num_disparities, uniqueness, lr_check, false)) return rc;
+    if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
+    if (int rc = stereo_dense_alloc(ctx)) return rc;
+    const StereoState::Dense &d = ctx->stereo.dense;
+    const int64_t bytes = (int64_t)(h - 1) * stride + w, px = (int64_t)w * h;
+    HostStaging st{ctx};
+    uint8_t *dl = st.slot<uint8_t>(0, bytes), *dr = st.slot<uint8_t>(1, bytes);
+    if (st.rc) return st.finish();
+    st.upload(dl, left, bytes);
+    st.upload(dr, right, bytes);
+    const StereoParams p = {fx, baseline_m, w, h, min_disparity, num_disparities, uniqueness, lr_check};
+    st.run([&] { return stereo_dense_launch(ctx, dl, stride, dr, stride, p); });
+    st.download(depth_mm, d.mm, px * 2);
+    if (disparity) st.download(disparity, d.disp, px * 4);
+    if (status) st.download(status, d.status, px);
+    return st.finish();
+}
+
+int stereo_dense_frame(reloc_ctx *ctx, reloc_ctx *right, int w, int h, int order, int *ww, int *wh)
+{
+    StereoState &s = ctx->stereo;
+    if (int rc = stereo_pair_check(ctx, right, w, h, ww, wh)) return rc;
+    if (int rc = stereo_dense_alloc(ctx)) return rc;
+    // the right eye's chain on its own stream, behind what ctx's stream holds so far (stereo_frame); the left eye's on ctx's
+    HIP_TRY(hipEventRecord(s.left_ready, ctx->stream));
+    HIP_TRY(hipStreamWaitEvent(right->stream, s.left_ready, 0));
+    const uint8_t *plane[2];
+    int pstride[2];
+    for (int e = 0; e < 2; ++e) {
+        reloc_ctx *c = e ? right : ctx;
+        const uint8_t *src = c->frame_img, *planes[RELOC_BATCH_MAX];
+        const uint8_t *const *srcs = &src;
+        int stride = w * image_chain_frame_bpp(c), channels = 1;
+        if (int rc = image_chain_gray(&c, 1, true, &srcs, w, h, *ww, *wh, &stride, &channels, gray_flags(c, order), planes)) return rc;
+        plane[e] = srcs[0];
+        if (channels == 3) {       // no stage ran on a 3-channel frame
+            uint8_t *dst = e ? s.plane : s.dense.left;
+            if (int rc = image_gray_plain(c, plane[e], *ww, *wh, stride, order, dst)) return rc;
+            plane[e] = dst; stride = *ww;
+        }
+        pstride[e] = stride;
+    }
+    HIP_TRY(hipEventRecord(s.right_done, right->stream));
+    HIP_TRY(hipStreamWaitEvent(ctx->stream, s.right_done, 0));
+    const StereoParams p = {ctx->cam.K4[0], s.baseline, *ww, *wh, s.min_disp, s.num_disp, s.uniq, s.lr};
+    return stereo_dense_launch(ctx, plane[0], pstride[0], plane[1], pstride[1], p);
+}
+
+RELOC_API int reloc_stereo_frame_depth(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img, const uint8_t *img_right, int w, int h,
+                                       int order, uint16_t *depth_mm, int32_t *out_w, int32_t *out_h)
+{
+    ARG_CHECK_CTX(ctx, right && img && img_right && w >= 64 && h >= 64, "reloc_stereo_frame_depth");
+    if (!ctx->stereo.on()) { reloc_set_error("stereo is off on this context (reloc_set_stereo)"); return RELOC_E_STATE; }
+    if (right == ctx) { reloc_set_error("bad argument: the right eye needs a context of its own"); return RELOC_E_ARG; }
+    if (w > ctx->max_w || h > ctx->max_h || w > right->max_w || h > right->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
+    HostStaging st{ctx};
+    st.upload(ctx->frame_img, img, (int64_t)w * h * image_chain_frame_bpp(ctx));
+    bool right_busy = false;       // the right context's stream holds a copy from the caller's memory
+    int ww = 0, wh = 0;
+    st.run([&] {
+        right_busy = true;
+        HIP_TRY(hipMemcpyAsync(right->frame_img, img_right, (size_t)w * h * image_chain_frame_bpp(right), hipMemcpyHostToDevice, right->stream));
+        return stereo_dense_frame(ctx, right, w, h, order, &ww, &wh);
+    });
+    if (depth_mm) st.download(depth_mm, ctx->stereo.dense.mm, (int64_t)ww * wh * 2);
+    const int rc = st.finish();
+    // after an error the two streams may not be ordered: nothing of the caller's right frame stays in flight
+    if (right_busy) (void)hipStreamSynchronize(right->stream);
+    if (rc) return rc;
+    if (out_w) *out_w = ww;
+    if (out_h) *out_h = wh;
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_stereo_dense_debug(reloc_ctx *ctx, uint16_t *depth_mm, float *disparity, uint8_t *status, int32_t *w, int32_t *h)
+{
+    ARG_CHECK_CTX(ctx, true, "reloc_stereo_dense_debug");
+    const StereoState::Dense &d = ctx->stereo.dense;
+    if (!d.block || d.w == 0) { reloc_set_error("no dense stereo pass on this context yet"); return RELOC_E_STATE; }
+    const size_t px = (size_t)d.w * d.h;
+    if (depth_mm) HIP_TRY(hipMemcpyAsync(depth_mm, d.mm, px * 2, hipMemcpyDeviceToHost, ctx->stream));
+    if (disparity) HIP_TRY(hipMemcpyAsync(disparity, d.disp, px * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (status) HIP_TRY(hipMemcpyAsync(status, d.status, px, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (w) *w = d.w;
+    if (h) *h = d.h;
     return RELOC_OK;
 }

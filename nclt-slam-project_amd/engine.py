@@ -561,15 +561,21 @@ class Engine:
             return None
         return dict(baseline_m=b.value, min_disparity=md.value, num_disparities=nd.value, uniqueness=un.value, lr_check=bool(lr.value))
 
+    @staticmethod
+    def _stereo_planes(left, right, what):
+        """two rectified (H, W) uint8 planes as the stateless stereo entry points read them through one row stride"""
+        left = np.asarray(left); right = np.asarray(right)
+        if left.dtype != np.uint8 or right.dtype != np.uint8 or left.ndim != 2 or left.shape != right.shape:
+            raise N.RelocError(f"{what}: expected two (H, W) uint8 planes of one size")
+        if left.strides[1] != 1 or left.strides[0] < left.shape[1] or right.strides != left.strides:
+            left = np.ascontiguousarray(left); right = np.ascontiguousarray(right)
+        return left, right
+
     def stereo_depth(self, left: np.ndarray, right: np.ndarray, xy, fx: float, baseline_m: float, min_disparity: int = 0,
                      num_disparities: int = 128, uniqueness: int = 15, lr_check: bool = True):
         """(depth_mm (n,) uint16, disparity (n,) float32, status (n,) uint8) of the keypoints xy (n, 2) on two rectified (H, W)
         uint8 planes with explicit parameters (reloc_stereo_depth); the planes may be row-strided views of one stride"""
-        left = np.asarray(left); right = np.asarray(right)
-        if left.dtype != np.uint8 or right.dtype != np.uint8 or left.ndim != 2 or left.shape != right.shape:
-            raise N.RelocError("stereo_depth: expected two (H, W) uint8 planes of one size")
-        if left.strides[1] != 1 or left.strides[0] < left.shape[1] or right.strides != left.strides:
-            left = np.ascontiguousarray(left); right = np.ascontiguousarray(right)
+        left, right = self._stereo_planes(left, right, "stereo_depth")
         h, w = left.shape
         xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
         n = len(xy)
@@ -583,11 +589,7 @@ class Engine:
                             order_rgb: bool = False):
         """record_frame with the right eye's frame in the depth image's place (reloc_record_frame_stereo): right_engine
         carries that eye's image chain.  The dict of record_frame plus n_stereo, the keypoints with a stereo depth."""
-        bgr = self._frame(bgr, "record_frame_stereo")
-        right_frame = right_engine._frame(right_frame, "record_frame_stereo (right)")
-        h, w = bgr.shape[:2]
-        if right_frame.shape[:2] != (h, w):
-            raise N.RelocError("record_frame_stereo: left and right sizes differ")
+        bgr, right_frame, w, h = self._stereo_pair(bgr, right_frame, right_engine, "record_frame_stereo")
         mf = self.max_feat
         xy = np.empty((mf, 2), np.float32); desc = np.empty((mf, 32), np.uint8); pts = np.empty((mf, 3), np.float32)
         idx = np.empty(mf, np.int32)
@@ -611,6 +613,62 @@ class Engine:
         mm = np.zeros(mf, np.uint16); disp = np.zeros(mf, np.float32); st = np.zeros(mf, np.uint8); n = i32()
         self._api.reloc_stereo_debug(self._ctx, mm, disp, st, n)
         return mm[:n.value].copy(), disp[:n.value].copy(), st[:n.value].copy()
+
+    # ------------------------------------------------------------------ dense stereo depth (reloc_spec.h "STEREO, dense")
+    def stereo_depth_image(self, left: np.ndarray, right: np.ndarray, fx: float, baseline_m: float, min_disparity: int = 0,
+                           num_disparities: int = 128, uniqueness: int = 15, lr_check: bool = True):
+        """(depth_mm uint16, disparity float32, status uint8), each (H, W): the depth of every pixel of two rectified (H, W)
+        uint8 planes with explicit parameters (reloc_stereo_depth_image), what stereo_depth gives for a keypoint there; the
+        planes may be row-strided views of one stride"""
+        left, right = self._stereo_planes(left, right, "stereo_depth_image")
+        h, w = left.shape
+        mm = np.zeros((h, w), np.uint16); disp = np.zeros((h, w), np.float32); st = np.zeros((h, w), np.uint8)
+        self._api.reloc_stereo_depth_image(self._ctx, left.ctypes.data, right.ctypes.data, w, h, left.strides[0], float(fx),
+                                           float(baseline_m), int(min_disparity), int(num_disparities), int(uniqueness),
+                                           int(bool(lr_check)), mm, disp, st)
+        return mm, disp, st
+
+    def _stereo_pair(self, frame, right_frame, right_engine, what):
+        """both eyes' frames of a host-pointer stereo call, each checked against its own engine's chain, and their size"""
+        frame = self._frame(frame, what)
+        right_frame = right_engine._frame(right_frame, f"{what} (right)")
+        h, w = frame.shape[:2]
+        if right_frame.shape[:2] != (h, w):
+            raise N.RelocError(f"{what}: left and right sizes differ")
+        return frame, right_frame, w, h
+
+    def stereo_frame_depth(self, frame: np.ndarray, right_frame: np.ndarray, right_engine: "Engine", order_rgb: bool = False):
+        """the (H', W') uint16 depth image, millimetres, 0 = no depth, of a pair of camera frames (reloc_stereo_frame_depth):
+        both through the gray half of their engines' image chains, no ORB, then the dense pass with this engine's set_stereo
+        setting and camera; H' x W' is the working frame"""
+        frame, right_frame, w, h = self._stereo_pair(frame, right_frame, right_engine, "stereo_frame_depth")
+        mm = np.zeros(h * w, np.uint16)
+        ow, oh = N.outs(i32, i32)
+        self._api.reloc_stereo_frame_depth(self._ctx, right_engine._ctx, frame, right_frame, w, h, int(order_rgb), mm, ow, oh)
+        return mm[: ow.value * oh.value].reshape(oh.value, ow.value).copy()
+
+    def stereo_frame_points(self, frame: np.ndarray, right_frame: np.ndarray, right_engine: "Engine", step: int = 4,
+                            zmin: float = 0.3, zmax: float = 10.0, order_rgb: bool = False):
+        """(n, 3) float32 obstacle points of a pair of camera frames (reloc_stereo_frame_points): depth_points, with this
+        engine's camera, of the depth image of stereo_frame_depth, which stays on the device"""
+        frame, right_frame, w, h = self._stereo_pair(frame, right_frame, right_engine, "stereo_frame_points")
+        if int(step) != step or int(step) < 1:
+            raise N.RelocError("stereo_frame_points: step must be an integer >= 1")
+        step = int(step)
+        pts = np.empty((-(-w // step) * -(-h // step), 3), np.float32)
+        n = i32()
+        self._api.reloc_stereo_frame_points(self._ctx, right_engine._ctx, frame, right_frame, w, h, int(order_rgb), step,
+                                            float(zmin), float(zmax), pts, n)
+        return pts[: n.value].copy()
+
+    def stereo_dense_debug(self):
+        """(depth_mm, disparity, status) planes of the last dense stereo pass of this engine"""
+        px = self.max_w * self.max_h
+        mm = np.zeros(px, np.uint16); disp = np.zeros(px, np.float32); st = np.zeros(px, np.uint8)
+        w, h = N.outs(i32, i32)
+        self._api.reloc_stereo_dense_debug(self._ctx, mm, disp, st, w, h)
+        k, shape = w.value * h.value, (h.value, w.value)
+        return mm[:k].reshape(shape).copy(), disp[:k].reshape(shape).copy(), st[:k].reshape(shape).copy()
 
     def frame_debug_plane(self, what: int, level: int) -> np.ndarray:
         buf = np.empty(self.max_w * self.max_h, np.uint8)

@@ -1,6 +1,7 @@
-"""Sparse stereo depth of the host layer (include/reloc_spec.h "STEREO"): the rig -- baseline, search range and gates, the
+"""Stereo depth of the host layer (include/reloc_spec.h "STEREO", "STEREO, dense"): the rig -- baseline, search range and gates, the
 right eye's rectification -- as `LandmarkRecorderCore(stereo=...)` and `MatcherConfig.stereo` take it, the right eye's Engine
-made from the left eye's front end, and the NumPy side of the per-keypoint depth gates for the cv2-shaped cores.
+made from the left eye's front end, the NumPy side of the per-keypoint depth gates for the cv2-shaped cores, and
+`StereoDepthCore`: the depth image and the obstacle cloud of a stereo pair, for a robot without a depth sensor.
 
 A rig stands beside the `FrontEnd`, not inside it: both eyes share one front end (the same pixel format or Bayer code, resize
 and CLAHE; `fx` and the maps are those of the rectified working frame), and a host without a rig makes exactly the engine
@@ -70,6 +71,11 @@ class StereoRig:
         """uint16 millimetres per keypoint (0 = no depth) from two planes of the chain's output through the backend's kernel"""
         return backend.stereo_depth(left_gray, right_gray, xy, fx, **self.settings())[0]
 
+    def depth_image(self, backend, left_gray, right_gray, fx):
+        """the (H, W) uint16 depth image, millimetres, 0 = no depth, of two planes of the chain's output through the backend's
+        dense kernel"""
+        return backend.stereo_depth_image(left_gray, right_gray, fx, **self.settings())[0]
+
 
 def shim_backend(cv2):
     """the Engine behind a cv2-shaped module: a Cv2Shim's backend, or the one of the module-level shim"""
@@ -86,3 +92,58 @@ def record_gates(uu, vv, kp_mm, w, h, depth_min_m, depth_max_m, ground_y=None):
         keep &= vv > ground_y
     keep &= (z > depth_min_m) & (z < depth_max_m)
     return keep, z
+
+
+class StereoDepthCore:
+    """The depth image and the obstacle cloud of a rectified stereo pair, ROS-free: what a depth camera's driver and the
+    relay's depth callback (every `step`-th pixel, zmin .. zmax metres) deliver, from two camera frames.
+    front_end: the FrontEnd both eyes share (the right one with the rig's rectification); rig: a StereoRig; K4: fx, fy, cx, cy
+    of the rectified working frame.  engine: the left eye's Engine, as large as the camera -- both frames then run through
+    the engines' image chains and the dense kernel in one device call, the cloud without a trip of the depth through the
+    host; the core makes and owns the right eye's Engine (rig.right_engine).  engine=None: the cv2-shaped path, the chains of
+    both eyes through the cv2 module (default: the shim), the dense kernel and the cloud on the shim's backend."""
+
+    def __init__(self, front_end, rig, K4, engine=None, cv2=None):
+        from .front_end import FrontEnd, ImageChain
+        if not isinstance(rig, StereoRig):
+            raise ValueError("StereoDepthCore: rig must be a StereoRig")
+        K4 = np.asarray(K4, np.float64).ravel()
+        if K4.shape != (4,) or not np.isfinite(K4).all() or K4[0] <= 0.0 or K4[1] <= 0.0:
+            raise ValueError("StereoDepthCore: K4 must be four finite numbers fx, fy, cx, cy with fx, fy > 0")
+        self.front_end = fe = front_end if front_end is not None else FrontEnd()
+        self.rig, self.K4, self.engine = rig, K4, engine
+        self.right_engine = self.chain = self.right_chain = self.cv2 = None
+        if engine is not None:
+            fe.configure(engine)
+            engine.set_camera(K4)
+            rig.configure(engine)
+            self.right_engine = rig.right_engine(engine, fe)
+        else:
+            if cv2 is None:
+                from . import cv2_shim as cv2
+            self.cv2 = cv2
+            self.chain = ImageChain(cv2, fe)
+            self.right_chain = ImageChain(cv2, rig.right_front_end(fe))
+
+    def _gray_pair(self, left_frame, right_frame):
+        return self.chain.apply(left_frame)[0], self.right_chain.apply(right_frame)[0]
+
+    def depth(self, left_frame, right_frame):
+        """the (H', W') uint16 depth image of the working frame: millimetres, 0 = no depth"""
+        if self.engine is not None:
+            return self.engine.stereo_frame_depth(left_frame, right_frame, self.right_engine)
+        return self.rig.depth_image(shim_backend(self.cv2), *self._gray_pair(left_frame, right_frame), self.K4[0])
+
+    def cloud(self, left_frame, right_frame, step=4, zmin=0.3, zmax=10.0):
+        """(n, 3) float32 obstacle points (z, -x, -y) of every step-th pixel with zmin < z < zmax, raster order"""
+        if int(step) != step or int(step) < 1:
+            raise ValueError("StereoDepthCore: step must be an integer >= 1")
+        if self.engine is not None:
+            return self.engine.stereo_frame_points(left_frame, right_frame, self.right_engine, int(step), zmin, zmax)
+        return shim_backend(self.cv2).depth_points(self.depth(left_frame, right_frame), int(step), self.K4, zmin, zmax)
+
+    def close(self):
+        """closes the right eye's Engine, which this core made; the left Engine stays the caller's"""
+        if self.right_engine is not None:
+            self.right_engine.close()
+            self.right_engine = None

@@ -1,0 +1,327 @@
+"""GPU: dense stereo depth (include/reloc_spec.h "STEREO, dense").  k_stereo_dense / k_stereo_dense_finish, the frame path
+through both eyes' image chains and the cloud against tests/stereo_dense_ref.py (held to the per-keypoint reference at every
+pixel by tests/test_stereo_dense_host.py), against the sparse kernel and against reloc_depth_points.  Every comparison is
+exact: depth_mm and status equal, disparity as uint32 bit patterns."""
+import numpy as np
+import pytest
+
+import record_ref as RR
+import stereo_dense_ref as SD
+import stereo_ref as SR
+from chain_harness import engines
+from nclt_slam_project_amd import RelocError
+
+pytestmark = pytest.mark.gpu
+
+W, H = 192, 96
+FX, BASELINE = 320.0, 1.0
+RW, RH = 256, 240                  # the frames of the fused paths (at least 64 x 64)
+K4 = (320.0, 320.0, 320.0, 240.0)  # a new context's camera
+RIG = dict(baseline_m=0.12, min_disparity=0, num_disparities=128, uniqueness=15, lr_check=True)
+
+
+def _u32(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _same(got, ref):
+    np.testing.assert_array_equal(got[2], ref[2])                   # status first: it names the step that differs
+    np.testing.assert_array_equal(got[0], ref[0])
+    np.testing.assert_array_equal(_u32(got[1]), _u32(ref[1]))
+    assert got[0].dtype == np.uint16 and got[1].dtype == np.float32 and got[2].dtype == np.uint8
+
+
+def _probe(engine, left, right, fx=FX, baseline=BASELINE, **kw):
+    got = engine.stereo_depth_image(left, right, fx, baseline, **kw)
+    ref = SD.dense(np.ascontiguousarray(left), np.ascontiguousarray(right), fx, baseline, **kw)
+    _same(got, ref)
+    _same(engine.stereo_dense_debug(), ref)                         # the tap holds the same pass
+    return ref
+
+
+@pytest.fixture(scope="module")
+def scene1():
+    """two 64-disparity halves, every status"""
+    left, right, _ = SR.banded_scene(0, W, H, periodic=(30, 44, 16, 17), constant=(70, 84, 90))
+    return left, right, SD.dense(left, right, FX, BASELINE)
+
+
+@pytest.fixture(scope="module")
+def scene2():
+    h = 30
+    return SR.banded_scene(1, 120, h, disparities=(3, 17), periodic=(8, 16, 8, 5), constant=(h - 8, h - 2, 90))[:2]
+
+
+def _planted(seed, w, h, d=3):
+    rng = np.random.default_rng(seed)
+    left = SR.smooth_noise(rng, w, h)
+    return left, SR.shift_rows(left, d, SR.smooth_noise(rng, w, h))
+
+
+def _pair(seed, w=RW, h=RH):
+    return SR.banded_scene(seed, w, h, disparities=(9, 21), row0=h // 2, periodic=(20, 40, 16, 17), constant=(60, 80, 90))[:2]
+
+
+def _bgr(gray):
+    return np.ascontiguousarray(np.repeat(gray[:, :, None], 3, axis=2))
+
+
+def _settings(rig):
+    return {k: v for k, v in rig.items() if k != "baseline_m"}
+
+
+def _frame_ref(L, R, rig=RIG, fx=K4[0]):
+    return SD.dense(L, R, fx, rig["baseline_m"], **_settings(rig))
+
+
+# ---- 1: all statuses ------------------------------------------------------------------------------------------------
+def test_dense_all_statuses(engine, scene1):
+    left, right, ref = scene1
+    counts = np.bincount(ref[2][::3, ::3].ravel(), minlength=7)
+    print("statuses 0..6 of the reference on every third pixel:", counts.tolist())
+    assert tuple(counts) == (878, 279, 29, 154, 276, 60, 372)       # a condition on the inputs
+    assert set(np.unique(ref[2])) == set(range(7))
+    _same(engine.stereo_depth_image(left, right, FX, BASELINE), ref)
+
+
+# ---- 2: search range and gates --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kw", [dict(num_disparities=8), dict(num_disparities=63), dict(num_disparities=64), dict(num_disparities=65),
+                                dict(num_disparities=128), dict(num_disparities=256), dict(min_disparity=3, num_disparities=65),
+                                dict(min_disparity=40, num_disparities=65), dict(uniqueness=0), dict(uniqueness=50),
+                                dict(lr_check=False)], ids=lambda kw: "-".join(f"{k}={v}" for k, v in kw.items()))
+def test_dense_search_range_and_gates(engine, scene2, kw):
+    left, right = scene2
+    st = _probe(engine, left, right, **kw)[2]
+    assert (st == SR.OK).any()
+    if "lr_check" in kw:
+        assert not (st == SR.LR).any()
+
+
+# ---- 3: shapes, tile edges, strides ---------------------------------------------------------------------------------
+# the tile of k_stereo_dense is 256 columns by one row, 64 columns per wave: its width at -1, 0, +1 and twice that
+SHAPES = [(11, 11), (13, 11), (64, 11), (65, 12), (203, 61), (257, 33)] + [(w, 13) for w in (63, 64, 65, 127, 128, 129, 255, 256, 513)]
+
+
+@pytest.mark.parametrize("w,h", SHAPES, ids=[f"{w}x{h}" for w, h in SHAPES])
+def test_dense_shapes_and_strides(engine, w, h):
+    left, right = _planted(w * 1000 + h, w, h)
+    for nd in (8, 64):
+        refs = []
+        for stride in (w, w + 1, w + 37):
+            bl = np.full((h, stride), 0xFF, np.uint8); br = np.full((h, stride), 0xFF, np.uint8)
+            bl[:, :w] = left; br[:, :w] = right
+            refs.append(_probe(engine, bl[:, :w], br[:, :w], baseline=0.12, num_disparities=nd))
+        mm, disp, st = refs[0]
+        if (w, h) == (11, 11):
+            assert not mm.any() and not disp.any() and (st != SR.OK).all()
+        elif w >= 63:
+            assert (st == SR.OK).any() and np.abs(disp[st == SR.OK] - 3.0).max() <= 0.5
+
+
+# ---- 4: ties ----------------------------------------------------------------------------------------------------------
+def test_dense_ties(engine):
+    left, right, _ = SR.tie_scene()
+    mm, disp, st = _probe(engine, left, right, FX, 0.12)
+    assert st[40, 120] == SR.OK and disp[40, 120] == np.float32(20.5)
+    flat = np.full((H, W), 77, np.uint8)
+    assert (_probe(engine, flat, flat)[2] != SR.OK).all()
+
+
+# ---- 5: against the sparse kernel -----------------------------------------------------------------------------------
+def test_dense_equals_the_sparse_kernel_at_rounded_keypoints(engine, scene1):
+    left, right, _ = scene1
+    xy = SR.random_keypoints(21, 500, W, H)
+    uu, vv = RR.round_px(xy)
+    for kw in (dict(), dict(num_disparities=65, min_disparity=3, lr_check=False)):
+        mm, disp, st = engine.stereo_depth_image(left, right, FX, BASELINE, **kw)
+        smm, sdisp, sst = engine.stereo_depth(left, right, xy, FX, BASELINE, **kw)
+        np.testing.assert_array_equal(sst, st[vv, uu])
+        np.testing.assert_array_equal(smm, mm[vv, uu])
+        np.testing.assert_array_equal(_u32(sdisp), _u32(disp[vv, uu]))
+        assert len(set(sst.tolist())) >= 5
+
+
+# ---- 6: the frame path ----------------------------------------------------------------------------------------------
+def _shift_maps(w, h, dx):
+    x, y = np.meshgrid(np.arange(w, dtype=np.float32), np.arange(h, dtype=np.float32))
+    return np.ascontiguousarray(x + np.float32(dx)), np.ascontiguousarray(y)
+
+
+def _frame_vs_reference(es, lf, rf, L, R, rig=RIG):
+    """reloc_stereo_frame_depth against the reference on the planes L, R that the two chains deliver"""
+    ref = _frame_ref(L, R, rig)
+    mm = es[0].stereo_frame_depth(lf, rf, es[1])
+    assert mm.shape == L.shape and mm.dtype == np.uint16
+    np.testing.assert_array_equal(mm, ref[0])
+    _same(es[0].stereo_dense_debug(), ref)
+    return ref
+
+
+@pytest.mark.parametrize("variant", ["bgr", "mono8", "rectify", "resize", "clahe"])
+def test_stereo_frame_depth(variant):
+    L, R = _pair(0)
+    with engines(2, RW, RH) as rig:
+        es = rig.es
+        es[0].set_stereo(**RIG)
+        lf, rf, Lp, Rp = _bgr(L), _bgr(R), L, R
+        if variant == "mono8":
+            for e in es:
+                e.set_pixel_format("mono8")
+            lf, rf = L, R
+        if variant == "rectify":                               # the right eye's map reads 4 pixels further right
+            es[0].set_rectify(_shift_maps(RW, RH, 0)); es[1].set_rectify(_shift_maps(RW, RH, 4))
+            Rp = np.zeros_like(R); Rp[:, :RW - 4] = R[:, 4:]
+        if variant == "resize":                                # INTER_AREA at 2x gives the small planes back
+            up = lambda g: np.ascontiguousarray(np.repeat(np.repeat(g, 2, axis=0), 2, axis=1))
+            Lp, Rp = _pair(0, RW // 2, RH // 2)
+            for e in es:
+                e.set_resize((RW, RH), (RW // 2, RH // 2))
+            lf, rf = _bgr(up(Lp)), _bgr(up(Rp))
+        if variant == "clahe":
+            for e in es:
+                e.set_clahe(2.0, (4, 4))
+            Lp, Rp = es[0].clahe(L, 2.0, (4, 4)), es[0].clahe(R, 2.0, (4, 4))
+        ref = _frame_vs_reference(es, lf, rf, Lp, Rp)
+        assert ref[0].shape == ((RH // 2, RW // 2) if variant == "resize" else (RH, RW))
+        assert (ref[2] == SR.OK).sum() > 1000 and {0, 1, 3, 4, 5} <= set(np.unique(ref[2]).tolist())
+        if variant == "rectify":
+            es[1].set_rectify(None)                             # a map on one eye only
+            with pytest.raises(RelocError, match="rectification map"):
+                es[0].stereo_frame_depth(lf, rf, es[1])
+
+
+# ---- 7: the cloud ---------------------------------------------------------------------------------------------------
+def test_stereo_frame_points():
+    L, R = _pair(0)
+    with engines(2, RW, RH) as rig:
+        es = rig.es
+        es[0].set_stereo(**RIG)
+        mm = es[0].stereo_frame_depth(_bgr(L), _bgr(R), es[1])
+        np.testing.assert_array_equal(mm, _frame_ref(L, R)[0])
+        for step in (1, 4, 5):
+            got = es[0].stereo_frame_points(_bgr(L), _bgr(R), es[1], step=step)
+            via_host = es[0].depth_points(mm, step, K4)
+            assert got.dtype == np.float32 and got.shape == via_host.shape and len(got) > 20
+            np.testing.assert_array_equal(_u32(got), _u32(via_host))
+            np.testing.assert_array_equal(_u32(got), _u32(RR.depth_points(mm, step, K4, 0.3, 10.0)))
+        near = es[0].stereo_frame_points(_bgr(L), _bgr(R), es[1], step=1, zmin=1.0, zmax=2.0)
+        np.testing.assert_array_equal(_u32(near), _u32(RR.depth_points(mm, 1, K4, 1.0, 2.0)))
+        assert 0 < len(near) < len(es[0].stereo_frame_points(_bgr(L), _bgr(R), es[1], step=1))
+        # another camera: fx enters the depth, the whole K4 the cloud
+        K2 = (250.0, 251.0, 120.5, 118.25)
+        es[0].set_camera(K2)
+        mm2 = es[0].stereo_frame_depth(_bgr(L), _bgr(R), es[1])
+        np.testing.assert_array_equal(mm2, _frame_ref(L, R, fx=K2[0])[0])
+        got = es[0].stereo_frame_points(_bgr(L), _bgr(R), es[1], step=4)
+        np.testing.assert_array_equal(_u32(got), _u32(RR.depth_points(mm2, 4, K2, 0.3, 10.0)))
+
+
+# ---- 8: state -------------------------------------------------------------------------------------------------------
+def test_dense_state_and_errors():
+    L, R = _pair(0)
+    with engines(2, RW, RH) as rig:
+        es = rig.es
+        with pytest.raises(RelocError, match="no dense stereo pass on this context yet"):
+            es[0].stereo_dense_debug()
+        with pytest.raises(RelocError, match="stereo is off"):
+            es[0].stereo_frame_depth(_bgr(L), _bgr(R), es[1])
+        with pytest.raises(RelocError, match="stereo is off"):
+            es[0].stereo_frame_points(_bgr(L), _bgr(R), es[1])
+        es[0].set_stereo(**RIG)
+        with pytest.raises(RelocError, match="a context of its own"):
+            es[0].stereo_frame_depth(_bgr(L), _bgr(R), es[0])
+        with pytest.raises(RelocError, match="a context of its own"):
+            es[0].stereo_frame_points(_bgr(L), _bgr(R), es[0])
+        big = np.zeros((RH + 8, RW + 8), np.uint8)
+        for call in (lambda: es[0].stereo_frame_depth(_bgr(big), _bgr(big), es[1]), lambda: es[0].stereo_frame_points(_bgr(big), _bgr(big), es[1]),
+                     lambda: es[0].stereo_depth_image(big, big, FX, BASELINE)):
+            with pytest.raises(RelocError, match="exceeds ctx capacity"):
+                call()
+        flat = np.zeros((H, W), np.uint8)
+        for args, text in (((FX, 0.0), "baseline_m"), ((0.0, 0.1), "fx"), ((FX, 0.1, 1025), "min_disparity 1025"), ((FX, 0.1, 0, 7), "num_disparities 7"),
+                           ((FX, 0.1, 0, 257), "num_disparities 257"), ((FX, 0.1, 0, 64, 51), "uniqueness 51")):
+            with pytest.raises(RelocError, match=text):
+                es[0].stereo_depth_image(flat, flat, *args)
+        with pytest.raises(RelocError, match="reloc_stereo_depth_image"):
+            es[0].stereo_depth_image(flat[:10], flat[:10], FX, 0.1)
+        with pytest.raises(RelocError, match="no dense stereo pass on this context yet"):
+            es[0].stereo_dense_debug()                          # nothing above was a pass
+        # two different pairs in a row, a smaller frame, a changed setting: each equals its own reference
+        first = _frame_vs_reference(es, _bgr(L), _bgr(R), L, R)
+        L2, R2 = _pair(1)
+        second = _frame_vs_reference(es, _bgr(L2), _bgr(R2), L2, R2)
+        assert (first[0] != second[0]).any()
+        Ls, Rs = _pair(2, 200, 96)
+        _frame_vs_reference(es, _bgr(Ls), _bgr(Rs), Ls, Rs)
+        rig2 = dict(baseline_m=0.2, min_disparity=2, num_disparities=40, uniqueness=5, lr_check=False)
+        es[0].set_stereo(**rig2)
+        third = _frame_vs_reference(es, _bgr(L), _bgr(R), L, R, rig2)
+        assert (third[2] != first[2]).any() and not (third[2] == SR.LR).any()
+
+
+def test_dense_pass_leaves_sparse_records_and_ticks_alone():
+    from nclt_slam_project_amd import synth
+    L, R = _pair(0)
+    rng = np.random.default_rng(7)
+    img = synth.textured_frame(rng, RW, RH)
+    with engines(2, RW, RH) as rig:
+        es = rig.es
+        e = es[0]
+        e.set_stereo(**RIG)
+        feat = e.orb_detect_compute(e.gray(img), 500)
+        e.db_upload(*synth.descriptor_db(rng, 64, "ragged", feat["desc"], planted_records=(5, 40)))
+        bp = synth.base_pose(10.0, 0.3, 2.0)
+
+        def sparse_and_tick():
+            rec = e.record_frame_stereo(_bgr(L), _bgr(R), es[1], 1500)
+            return rec, e.stereo_debug(), e.tick(img, bp, global_reloc=True, seed=1)
+
+        rec0, dbg0, tick0 = sparse_and_tick()
+        assert rec0["n_stereo"] > 0 and tick0["n_candidates"] > 0
+        np.testing.assert_array_equal(e.stereo_frame_depth(_bgr(L), _bgr(R), es[1]), _frame_ref(L, R)[0])
+        e.stereo_frame_points(_bgr(L), _bgr(R), es[1])
+        e.stereo_depth_image(L, R, FX, BASELINE)
+        rec1, dbg1, tick1 = sparse_and_tick()
+        for a, b in ((rec0, rec1), (tick0, tick1)):
+            assert a.keys() == b.keys()
+            for k in a:
+                np.testing.assert_array_equal(np.asarray(a[k]), np.asarray(b[k]), err_msg=k)
+        for a, b in zip(dbg0, dbg1):
+            np.testing.assert_array_equal(a, b)
+
+
+# ---- 9: full size ---------------------------------------------------------------------------------------------------
+def test_dense_full_size(engine):
+    left, right, _ = SR.banded_scene(5, 640, 480)
+    st = _probe(engine, left, right, num_disparities=128, lr_check=True)[2]
+    assert (st == SR.OK).sum() > 100000 and {0, 1, 2, 3, 4, 5} <= set(np.unique(st).tolist())
+
+
+# ---- 10: the host core ----------------------------------------------------------------------------------------------
+def test_stereo_depth_core():
+    from nclt_slam_project_amd.cv2_shim import Cv2Shim
+    from nclt_slam_project_amd.front_end import FrontEnd
+    from nclt_slam_project_amd.stereo import StereoDepthCore, StereoRig
+    L, R = _pair(0)
+    srig = StereoRig(**RIG, rectify_right=_shift_maps(RW, RH, 4))
+    fe = FrontEnd(rectify=_shift_maps(RW, RH, 0), clahe=(2.0, (4, 4)))
+    K2 = (250.0, 251.0, 120.5, 118.25)
+    with engines(2, RW, RH) as rig:
+        es = rig.es
+        dev = StereoDepthCore(fe, srig, K2, engine=es[0])
+        host = StereoDepthCore(fe, srig, K2, cv2=Cv2Shim(es[1]))
+        try:
+            R4 = np.zeros_like(R); R4[:, :RW - 4] = R[:, 4:]
+            Lp, Rp = es[1].clahe(L, 2.0, (4, 4)), es[1].clahe(R4, 2.0, (4, 4))
+            ref = _frame_ref(Lp, Rp, fx=K2[0])
+            assert (ref[2] == SR.OK).sum() > 1000
+            for core in (dev, host):
+                mm = core.depth(_bgr(L), _bgr(R))
+                assert mm.dtype == np.uint16
+                np.testing.assert_array_equal(mm, ref[0])
+                for step in (4, 5):
+                    pts = core.cloud(_bgr(L), _bgr(R), step=step)
+                    assert pts.dtype == np.float32 and len(pts) > 20
+                    np.testing.assert_array_equal(_u32(pts), _u32(RR.depth_points(ref[0], step, K2, 0.3, 10.0)))
+        finally:
+            dev.close()
