@@ -184,6 +184,32 @@ __device__ __forceinline__ u32 allmin_quad(u32 x)
     return x;
 }
 
+// ---- the two keys a chunk leaves in LDS, and what reads them back ---------------------------------
+// A row's key enters the butterfly as best << 6 | lane, ONE v_lshl_or_b32 per row (the compiler splits the C form into a
+// shift and an or: 32 instead of 16 instructions per chunk).  best = distance << 7 | row << 3 | slot, so the low nine bits
+// of the result, slot << 6 | lane, ARE the column inside the wave's block and row_key() needs no field shuffle.
+__device__ __forceinline__ u32 row_entry(u32 best, u32 lane)
+{
+    u32 v;
+    asm("v_lshl_or_b32 %0, %1, 6, %2" : "=v"(v) : "v"(best), "v"(lane));
+    return v;
+}
+// reduced row entry (distance << 13 | row << 9 | column in block) -> LDS row key, distance << 16 | column
+__device__ __forceinline__ u32 row_key(u32 m, u32 colbase) { return ((m << 3) & 0xFFFF0000u) | ((m & 0x1FFu) | colbase); }
+// 16-bit column minimum (distance << 7 | row in chunk << 3 | slot) -> LDS column key, distance << 16 | (tc + row in chunk).
+// k16 << 9 has the distance in its upper half already; the lower half is REPLACED by tc + row in one SDWA add that writes
+// bits 0-15 and keeps bits 16-31 (tc is wave-uniform and rides in the scalar operand; tc + row < 2^16 because the LDS keys
+// hold a row in 16 bits): three instructions a column where shift, field, add and and-or took four.  The compiler does not
+// count wait states for an asm statement: scan_chunk keeps every key's first reader NJ instructions behind this partial write.
+__device__ __forceinline__ u32 col_key(u32 k16, int tc)
+{
+    u32 key = k16 << 9;
+    const u32 row = (k16 >> 3) & 15u;
+    asm("v_add_u32_sdwa %0, %1, %2 dst_sel:WORD_0 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD"
+        : "+v"(key) : "s"(tc), "v"(row));
+    return key;
+}
+
 // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), in order
 template <class F, int... I>
 __device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
@@ -228,8 +254,12 @@ __device__ __forceinline__ void scan_chunk(const uint4 *__restrict__ rec, int n,
         uint4 na, nb;
         if (i + 1 < R) { na = rec[2 * row_of(i + 1)]; nb = rec[2 * row_of(i + 1) + 1]; }   // ... the next one on its way
         __builtin_amdgcn_sched_barrier(0);
-        u32 best = 0x7FFFFFu;                                         // a row the chunk does not have: loses every minimum
+        // A row the chunk does not have loses every minimum.  The compiler sets this default in front of the row's branch, one
+        // v_mov on the way of every row that IS there; pinned to the far side of the branch instead (asm volatile in an else),
+        // the 15 instructions go and the 4-stream run LOSES 1 % (profiles/README.md "Dropped experiments" #10).
+        u32 v = 0xFFFFFFFFu;
         if (t == 0 || t < nr) {                                          // wave-uniform
+            u32 best = 0;
             const u32 w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
             u32 h[NJ];
             ham8_cols<NJ>(q, w, h);                                    // NJ accumulator chains, order pinned
@@ -240,8 +270,8 @@ __device__ __forceinline__ void scan_chunk(const uint4 *__restrict__ rec, int n,
                 cb16[j + 1] = t == 0 ? k1 : min_u16(cb16[j + 1], k1);
                 best = j == 0 ? min_u16(k0, k1) : min_u16(best, min_u16(k0, k1));   // best column of this row
             });
+            v = row_entry(best, (u32)lane);
         }
-        u32 v = (best << 9) | (u32)lane;
         // Node of level k joins rows t and t + 16 / 2^(k+1).  The four levels split on lane bits 2, 3 (DPP minima, two instructions
         // a node: the levels with 8 and 4 nodes), 4 and 5 (permlane swap + minimum), and the two lane bits left over are reduced
         // on the one value at the end: 32 instead of ~66 instructions per chunk and no select masks to keep (rounds 1-3: levels on
@@ -270,16 +300,16 @@ __device__ __forceinline__ void scan_chunk(const uint4 *__restrict__ rec, int n,
     const bool writer = (lane & 3) == 0;
     const int row = tc + row_in_chunk;
     if (writer && row_in_chunk < nr) {
-        const u32 key = (m & 0xFFFF0000u) | (colbase + ((m >> 9) & 7u) * 64u + (m & 63u));   // distance << 16 | column
-        if (single_cb) rowkey[row] = key;
-        else atomicMin(&rowkey[row], key);
+        if (single_cb) rowkey[row] = row_key(m, 0);                  // one column block: colbase == 0
+        else atomicMin(&rowkey[row], row_key(m, colbase));
     }
+    // all the column keys, then all the minima: a key's partial write is NJ instructions old before LDS reads the register
+    u32 ck[NJ];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const u32 k16 = cb16[j];
-        const u32 key = ((k16 >> 7) << 16) | (u32)(tc + (int)((k16 >> 3) & 15u));
-        atomicMin(&colbest[colbase + j * 64 + lane], key);
-    }
+    for (int j = 0; j < NJ; ++j) ck[j] = col_key(cb16[j], tc);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) atomicMin(&colbest[colbase + j * 64 + lane], ck[j]);
 }
 
 // ---- what the counting scan and the emit pass share ---------------------------------------------
@@ -489,7 +519,7 @@ __device__ __forceinline__ void db_count_body(
         shard = (int)(x & 7u);
     }
     auto draw = [&]() -> u32 { return atomicAdd(&ticket[shard * TICKET_STRIDE], 1u); };
-    // thread 0: ticket -> record index; counter x deals records n_blocks + x, n_blocks + x + 8, ... (the first n_blocks
+    // the dealing thread (`dealer` below): ticket -> record index; counter x deals records n_blocks + x, n_blocks + x + 8, ... (the first n_blocks
     // records are the workgroups' static first records)
     auto settle = [&](u32 t) -> int {
         for (;;) {
@@ -502,21 +532,27 @@ __device__ __forceinline__ void db_count_body(
     };
     int it = stand_down ? n_ids : block;
     int left = (quota > 0 && block < n_bounded) ? quota : 0x7fffffff;        // rows this workgroup may still take on
-    for (int i = tid; i < ncb * CB; i += 64 * NW) colbuf[i] = 0xFFFFFFFFu;
+    // Per-record work goes to the wave that owns it, behind wave-uniform branches, so that the other waves walk to the barrier
+    // and issue nothing: wave 0 counts the mutual pairs of rows 0-63 (wave w those of rows 64 w ...) and writes the count;
+    // the last wave, the one the row deal gives the fewest rows, draws and settles the tickets in its first lane.
+    const bool dealer = tid == 64 * (NW - 1);
+    const int buf_words = ncb * CB;                                          // one buffer of column minima, a multiple of 128
+    for (int i = tid; i < buf_words; i += 64 * NW) colbuf[i] = 0xFFFFFFFFu;
     if (tid == 0) wsum[0] = wsum[1] = 0;
     __syncthreads();
     int p = 0;
     while (it < n_ids) {
-        u32 *colbest = colbuf + (dbl ? p * ncb * CB : 0);
+        u32 *colbest = colbuf + (dbl ? p * buf_words : 0);
         const int r = rec_ids ? rec_ids[it] : it;
         const bool scored = !(mask.xyh && !heading_ok(mask.xyh + 4 * (int64_t)r, hc, hs, cos_tol));      // workgroup-uniform
         const int64_t row0 = off[r];
-        const int n = scored ? (int)(off[r + 1] - row0) : 0;
+        const int n_rec = scored ? (int)(off[r + 1] - row0) : 0;
+        const int n = C > 0 ? n_rec : 0;                                 // rows to scan and to resolve: none without a column
         const uint4 *rec = db + 2 * row0;
-        left -= max(n, 1);
+        left -= max(n_rec, 1);
         u32 next_ticket = 0;
-        if (ticket && tid == 0 && left > 0) next_ticket = draw();        // no draw that this workgroup would not serve
-        if (n > 0 && C > 0) {
+        if (ticket && dealer && left > 0) next_ticket = draw();          // no draw that this workgroup would not serve
+        if (n > 0) {
             if (ncb > 1) {                                               // several waves write one row's key: atomic minima
                 for (int i = tid; i < n; i += 64 * NW) rowkey[i] = 0xFFFFFFFFu;
                 __syncthreads();
@@ -532,24 +568,23 @@ __device__ __forceinline__ void db_count_body(
                     scan_chunk<NJ>(rec, n, tc, min(16, tend - tc), q, (u32)(cb * CB), rowkey, colbest, ncb == 1, lane);
             }
         }
-        if (dbl) {   // the other buffer, for the next record
-            u32 *other = colbuf + (p ^ 1) * ncb * CB;
-            for (int i = tid; i < ncb * CB; i += 64 * NW) other[i] = 0xFFFFFFFFu;
-        }
-        __syncthreads();                                                  // every minimum of this record is in LDS
-        if (C > 0) {
-            for (int rb = 0; rb < n; rb += 64 * NW) {                     // wave-uniform trip count
-                const int row = rb + tid;
-                bool mutual = false;
-                if (row < n) {
-                    const u32 col = rowkey[row] & 0xFFFFu;
-                    mutual = (colbest[col] & 0xFFFFu) == (u32)row;
-                }
-                const u32 c = (u32)__popcll(__ballot(mutual));
-                if (lane == 0 && c) atomicAdd(&wsum[p], c);
+        if (dbl) {   // the other buffer, for the next record: two words a lane, 128 a wave and step (512 words: one store each)
+            u32 *other = colbuf + (p ^ 1) * buf_words;
+            for (int base = 0; base + 128 * wave < buf_words; base += 128 * NW) {  // wave-uniform
+                other[base + 2 * tid] = 0xFFFFFFFFu;
+                other[base + 2 * tid + 1] = 0xFFFFFFFFu;
             }
         }
-        if (tid == 0) wsum[8] = ticket ? (left > 0 ? (u32)settle(next_ticket) : (u32)n_ids) : (u32)(it + n_blocks);
+        __syncthreads();                                                  // every minimum of this record is in LDS
+        for (int rb = 0; rb + 64 * wave < n; rb += 64 * NW) {             // wave-uniform: a wave without rows goes on to the barrier
+            const int row = rb + tid;
+            if (row < n) {                                                // the wave's first lane always is
+                const u32 col = rowkey[row] & 0xFFFFu;
+                const unsigned long long mutual = __builtin_amdgcn_ballot_w64((colbest[col] & 0xFFFFu) == (u32)row);
+                if (lane == 0 && mutual) atomicAdd(&wsum[p], (u32)__popcll(mutual));
+            }
+        }
+        if (dealer) wsum[8] = ticket ? (left > 0 ? (u32)settle(next_ticket) : (u32)n_ids) : (u32)(it + n_blocks);
         __syncthreads();
         if (tid == 0) {
             counts[r] = (int32_t)wsum[p];
