@@ -486,6 +486,30 @@ int reloc_stereo_frame_points(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *i
  * context's stream. */
 int reloc_stereo_dense_debug(reloc_ctx *ctx, uint16_t *depth_mm, float *disparity, uint8_t *status, int32_t *w, int32_t *h);
 
+/* ---- teach-time occupancy map (include/reloc_spec.h, "OCCUPANCY") ---------------------------------- */
+/* The log-odds grid of the reference's teach_run_depth_mapper.py: every frame's obstacle cloud is taken into the map frame,
+ * height-filtered, subsampled and ray-traced from the sensor's cell into a grid of int8 units of 0.2 (free -2, hit +7, bounds
+ * -25 / +25, one clamped update per cell per frame).  T12: the 3 x 4 sensor-to-map transform, row major, finite.  out_rays
+ * (may be NULL): the rays of the frame, what total_points_integrated grew by.
+ * reloc_occ_configure allocates and zeroes a grid of w_cells x h_cells cells of res metres with cell (0, 0) at (origin_x,
+ * origin_y), counters included; a second call resets it.  Non-positive sizes, res or subsample, anything not finite:
+ * RELOC_E_ARG; more than RELOC_OCC_MAX_CELLS cells or 32768 per side: RELOC_E_CAPACITY.  A context that never configures a
+ * map allocates and launches nothing of it.  Every integrate entry point and reloc_occ_read return RELOC_E_STATE before it. */
+int reloc_occ_configure(reloc_ctx *ctx, double origin_x, double origin_y, double res, int w_cells, int h_cells, double z_lo,
+                        double z_hi, int subsample);
+/* A host cloud of n >= 0 rows of 3 floats in any sensor frame (pts may be NULL when n == 0).  Synchronous. */
+int reloc_occ_integrate_points(reloc_ctx *ctx, const float *pts, int n, const double T12[12], int32_t *out_rays);
+/* A host depth image as reloc_depth_points takes it, through that cloud, which is never written.  Synchronous. */
+int reloc_occ_integrate_depth(reloc_ctx *ctx, const void *depth, int is_f32, int w, int h, int step, const double K4[4],
+                              float zmin, float zmax, const double T12[12], int32_t *out_rays);
+/* The depth plane of the context's last dense stereo pass where it lies on the device, with the context camera's K4: the
+ * cloud of reloc_stereo_frame_points.  RELOC_E_STATE before the first pass.  With out_rays == NULL it enqueues only. */
+int reloc_occ_integrate_stereo_dev(reloc_ctx *ctx, int step, float zmin, float zmax, const double T12[12], int32_t *out_rays);
+/* units: h_cells x w_cells int8, row 0 at origin_y.  pgm: the same size, 0 occupied (units >= 4) / 254 free (units <= -6) / 205
+ * unknown, rows flipped.  counters: frames_integrated, total_points_integrated, frames_skipped_empty.  Any pointer may be
+ * NULL.  Synchronous. */
+int reloc_occ_read(reloc_ctx *ctx, int8_t *units, uint8_t *pgm, int64_t counters[3]);
+
 /* ---- fused tick ----------------------------------------------------------------------------- */
 #define RELOC_TICK_LOCAL   0   /* candidates by VIO distance / heading only                          M:293-302 */
 #define RELOC_TICK_GLOBAL  1   /* whole-database search unconditionally (the benchmarked shape)       G:329-344 */

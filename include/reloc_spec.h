@@ -373,4 +373,43 @@
 #define RELOC_STEREO_LR          5
 #define RELOC_STEREO_FAR         6
 
+/* OCCUPANCY: the teach-time occupancy map of the reference's teach_run_depth_mapper.py (D below): a 2-D log-odds grid that
+ * the obstacle cloud of a frame is ray-traced into, written as .pgm + .yaml for the repeat run's static costmap layer.
+ * Restated in tests/occupancy_ref.py, which the library equals cell for cell.  D line by line except (g).
+ *   (a) cloud    (N, 3) float32 points in a sensor frame, in a fixed order; rows with a non-finite coordinate are dropped
+ *              (D:60).  The depth-image form produces exactly the cloud of reloc_depth_points: every step-th pixel,
+ *              zmin < z < zmax, finite, point = (z, -px, -py), raster order.
+ *   (b) map      T: the 3 x 4 sensor-to-map transform, float64, row major (D's _tf_to_matrix, computed by the host).
+ *              x = ((T00 * px + T01 * py) + T02 * pz) + T03, likewise y and z: float64, this order, no FMA contraction.
+ *   (c) filter   keep z_lo < z < z_hi in float64 (D: 0.2, 2.0).  Among the points kept by (a) and (c) together, in input order,
+ *              the rays are those of rank 0, s, 2s, ...; s = subsample (D: 4).
+ *   (d) cells    col = trunc((x - origin_x) / res), row = trunc((y - origin_y) / res) in float64, toward zero like Python's
+ *              int() (D:120-123): a coordinate in (origin - res, origin) lands in cell 0.  In-grid is decided on the double
+ *              (-1 < q < W), before any integer conversion.  The start cell comes from (T03, T13); if it is outside the
+ *              grid the frame marks nothing.
+ *   (e) rays     for every ray whose end cell is in the grid, D's Bresenham (D:172-195; err = dr - dc, both conditional
+ *              steps): every cell before the end cell gets a free update, the end cell a hit.  A ray whose end cell is
+ *              outside the grid marks nothing.  A zero-length ray is a hit on the start cell.
+ *   (f) units    D's log-odds are multiples of 0.2; the grid holds integers in units of 0.2: free -2, hit +7, bounds -25 and
+ *              +25.  Classes of the .pgm: occupied (0) iff units >= 4 (D: > ln(0.65 / 0.35) = 0.619), free (254) iff
+ *              units <= -6 (D: < ln(1 / 3) = -1.0986), unknown (205) otherwise; rows flipped (D's np.flipud).
+ *   (g) frame    THE DEVIATION.  D clamps after every single update, which makes a cell depend on the order of the updates
+ *              it receives within a frame.  Here a cell gets one update per frame:
+ *              v = clamp(v + 7 * hits - 2 * frees, -25, +25).  The two agree on every cell that receives only frees or only
+ *              hits within a frame; they can differ only where a cell receives both kinds in one frame and a bound engages.
+ *   (h) counters frames_skipped_empty: the cloud of (a) is empty.  Nothing moves when (c) leaves nothing or the start cell is
+ *              outside the grid.  Otherwise frames_integrated += 1 and total_points_integrated += number of rays, those
+ *              dropped in (e) included. */
+#define RELOC_OCC_L_FREE       (-2)
+#define RELOC_OCC_L_OCC        7
+#define RELOC_OCC_L_MIN        (-25)
+#define RELOC_OCC_L_MAX        25
+#define RELOC_OCC_UNITS_OCC    4      /* units >= this: occupied */
+#define RELOC_OCC_UNITS_FREE   (-6)   /* units <= this: free     */
+#define RELOC_OCC_PGM_OCC      0
+#define RELOC_OCC_PGM_FREE     254
+#define RELOC_OCC_PGM_UNKNOWN  205
+#define RELOC_OCC_MAX_CELLS    (1 << 24)   /* capacity of one grid: w_cells * h_cells */
+#define RELOC_OCC_SUBSAMPLE_DEFAULT 4
+
 #endif /* RELOC_SPEC_H */

@@ -404,6 +404,23 @@ struct StereoState {
     }
 };
 
+// Teach-time occupancy map of a context (reloc_occ_configure; include/reloc_spec.h "OCCUPANCY"; reloc_occupancy.hip); 0 x 0 = none,
+// the default: a context that never configures a map allocates and launches nothing of it.  One device block of its own,
+// taken by reloc_occ_configure and freed by occ_release.
+struct OccState {
+    int w = 0, h = 0;                    // cells
+    int sub = RELOC_OCC_SUBSAMPLE_DEFAULT;
+    double ox = 0, oy = 0, res = 0, z_lo = 0, z_hi = 0;
+    uint8_t *block = nullptr;            // the pointers below lie in it
+    int64_t block_cells = 0;             // the cells it was sized for
+    int32_t *acc = nullptr;              // w * h: sums of the cells beyond the on-chip window, zero between frames
+    int64_t *counters = nullptr;         // frames_integrated, total_points_integrated, frames_skipped_empty
+    int32_t *frame = nullptr;            // the last frame: rays, box of its far rays
+    int8_t *units = nullptr;             // w * h: the grid, log-odds in units of 0.2, row 0 at origin_y
+    uint8_t *pgm = nullptr;              // w * h: the classified plane of the last reloc_occ_read
+    bool on() const { return w > 0; }
+};
+
 // What the five ORB kernels read and write of one frame, in the form they take it: a single-frame launch passes the members
 // as arguments, a batched one up to 8 of these in its kernel arguments (OrbBatch, blockIdx.y = frame).
 struct OrbFrame {
@@ -488,6 +505,7 @@ struct reloc_ctx {
     reloc_params prm;
     MatchPolicy match;
     StereoState stereo;              // reloc_stereo.hip
+    OccState occ;                    // reloc_occupancy.hip
     int scan_gens = 0;               // RELOC_SCAN_GENS (developer switch), read once at creation: n > 0 = single whole-database
                                      // scans in the form of batched ones (n generations of row budgets + sweepers, launch_db_count)
     uint32_t *scan_ticket = nullptr; // SCAN_TICKET_WORDS counters of the whole-database scans (scan_alloc, reloc_match.hip)
@@ -642,6 +660,8 @@ int image_gray_plain(reloc_ctx *c, const uint8_t *src, int w, int h, int sstride
 // working frame.  stereo_release: the events of a context that had stereo on.
 int stereo_frame(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img_right_dev, int w, int h, int order, int *ww, int *wh);
 void stereo_release(reloc_ctx *ctx);
+// the occupancy map's block, if the context has one (reloc_occupancy.hip)
+void occ_release(reloc_ctx *ctx);
 // Dense stereo depth: both eyes' frames (ctx->frame_img, right->frame_img, w x h as handed in) through the gray half of their
 // chains, each on its own stream, no ORB; then k_stereo_dense and k_stereo_dense_finish on ctx's stream into ctx->stereo.dense
 // (mm: dense rows of *ww uint16).  Checks stereo on, right != ctx, capacity and the chains' agreement.

@@ -1,0 +1,326 @@
+// reloc_occupancy.hip -- teach-time occupancy map (include/reloc_spec.h "OCCUPANCY"; DESIGN.md "Occupancy map").
+// A frame is two launches on the context's stream:
+//   k_occ_integrate  one workgroup of 1024: depth pixel or cloud row -> sensor point -> map point -> filters -> ordered rank
+//                    (ballot + prefix, the form of k_depth_points; the cloud is never written), rays queued in LDS and
+//                    walked one per lane, 1024 at a time.  The cells of a OCC_WIN x OCC_WIN window around the start cell are
+//                    summed in LDS and applied to the grid once; the start cell itself, which every ray crosses, is summed in
+//                    registers and added once per wave.  Cells beyond the window take global int32 atomics into `acc`.
+//   k_occ_apply      v = clamp(v + acc) and acc = 0 over the box that the frame's far rays span (nothing when there are none).
+// Integer sums only: the grid is the same whatever order the adds arrive in.
+#include "reloc_internal.h"
+
+// Developer switch for A/B builds (build.build_variant, tools/exp_occupancy.py): 2 = the shipped form; 1 = only the start cell is
+// summed on chip, every other cell takes a global atomic; 0 = every update is a global atomic.  The grid is the same in all.
+#ifndef RELOC_OCC_FORM
+#define RELOC_OCC_FORM 2
+#endif
+constexpr int OCC_WIN = 112;          // side of the on-chip window, cells; the start cell is its cell (OCC_WIN / 2, OCC_WIN / 2)
+constexpr int OCC_QUEUE = 2048;       // rays waiting in LDS: drained when more than 1024 wait, so a chunk's 1024 always fit
+constexpr int OCC_MAX_SIDE = 32768;   // a queued end cell is row << 16 | col
+
+struct OccGeom { double ox, oy, res, z_lo, z_hi; int W, H, sub; };
+struct OccT { double v[12]; };
+// what a frame reads: a cloud (n rows of 3 floats) or a depth plane with the arguments of k_depth_points
+struct OccSrc { const void *data; int n; int w, h, stride, step; float cx, cy, fx, fy, zmin, zmax; };
+enum { OCC_SRC_POINTS = 0, OCC_SRC_DEPTH_F32 = 1, OCC_SRC_DEPTH_U16 = 2 };
+// frame record on the device: [0] rays of the frame, [1..4] box of the far rays (row lo, row hi, col lo, col hi; hi < lo: none)
+constexpr int OCC_FRAME_WORDS = 8;
+
+// (d): q = (x - origin) / res in double, in the grid iff -1 < q < n (trunc toward zero puts (-1, 0) into cell 0)
+__device__ __forceinline__ bool occ_cell(double x, double origin, double res, int n, int &cell)
+{
+    const double q = __ddiv_rn(__dsub_rn(x, origin), res);
+    const bool in = q > -1.0 && q < (double)n;
+    cell = in ? (int)q : 0;
+    return in;
+}
+
+template <int SRC>
+__global__ __launch_bounds__(1024) void k_occ_integrate(OccSrc src, OccT T, OccGeom g, int8_t *__restrict__ units,
+                                                        int32_t *__restrict__ acc, int64_t *__restrict__ counters,
+                                                        int32_t *__restrict__ frame)
+{
+    __shared__ int s_win[OCC_WIN * OCC_WIN];
+    __shared__ unsigned s_queue[OCC_QUEUE];
+    __shared__ int s_wfin[16], s_wkeep[16];
+    __shared__ int s_fin, s_keep, s_qn;
+    __shared__ int s_box[4];                      // row lo, row hi, col lo, col hi of the end cells beyond the window
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int i = tid; i < OCC_WIN * OCC_WIN; i += 1024) s_win[i] = 0;
+    if (tid == 0) { s_fin = 0; s_keep = 0; s_qn = 0; s_box[0] = g.H; s_box[1] = -1; s_box[2] = g.W; s_box[3] = -1; }
+    int r0, c0;
+    const bool start_in = occ_cell(T.v[3], g.ox, g.res, g.W, c0) & occ_cell(T.v[7], g.oy, g.res, g.H, r0);
+    const int wr0 = r0 - OCC_WIN / 2, wc0 = c0 - OCC_WIN / 2;
+    int gw = 0, n = src.n;
+    if (SRC != OCC_SRC_POINTS) {
+        gw = (src.w + src.step - 1) / src.step;
+        n = gw * ((src.h + src.step - 1) / src.step);
+    }
+    int at_start = 0;                             // this lane's share of the start cell's sum
+    __syncthreads();
+
+    // the rays waiting in the queue, one per lane
+    auto drain = [&]() {
+        const int qn = s_qn;
+        for (int q = tid; q < qn; q += 1024) {
+            const unsigned e = s_queue[q];
+            const int r1 = (int)(e >> 16), c1 = (int)(e & 0xFFFFu);
+            const int dr = abs(r1 - r0), dc = abs(c1 - c0);
+            const int sr = r0 < r1 ? 1 : -1, sc = c0 < c1 ? 1 : -1;
+            int err = dr - dc, r = r0, c = c0;
+            for (int it = 0; it <= dr + dc; ++it) {               // D:172-195; a walk takes max(dr, dc) steps
+                const bool end = r == r1 && c == c1;
+                const int d = end ? RELOC_OCC_L_OCC : RELOC_OCC_L_FREE;
+                const int wr = r - wr0, wc = c - wc0;
+                if (it == 0 && RELOC_OCC_FORM >= 1) at_start += d;
+                else if (RELOC_OCC_FORM >= 2 && (unsigned)wr < (unsigned)OCC_WIN && (unsigned)wc < (unsigned)OCC_WIN) atomicAdd(&s_win[wr * OCC_WIN + wc], d);
+                else if ((unsigned)r < (unsigned)g.H && (unsigned)c < (unsigned)g.W) atomicAdd(&acc[r * g.W + c], d);
+                if (end) break;
+                const int e2 = 2 * err;
+                if (e2 > -dc) { err -= dc; r += sr; }
+                if (e2 < dr) { err += dr; c += sc; }
+            }
+        }
+        __syncthreads();
+        if (tid == 0) s_qn = 0;
+        __syncthreads();
+    };
+
+    for (int i0 = 0; i0 < n; i0 += 1024) {
+        const int i = i0 + tid;
+        bool fin = false, keep = false;
+        double mx = 0, my = 0;
+        if (i < n) {
+            float px, py, pz;
+            if (SRC == OCC_SRC_POINTS) {
+                const float *p = reinterpret_cast<const float *>(src.data) + (size_t)3 * i;
+                px = p[0]; py = p[1]; pz = p[2];
+                fin = true;
+            } else {                                              // the pixel of k_depth_points, the same arithmetic
+                const int v = (i / gw) * src.step, u = (i % gw) * src.step;
+                float z;
+                if (SRC == OCC_SRC_DEPTH_F32) z = reinterpret_cast<const float *>(src.data)[(size_t)v * src.stride + u];
+                else z = __fdiv_rn((float)reinterpret_cast<const uint16_t *>(src.data)[(size_t)v * src.stride + u], 1000.0f);
+                fin = z > src.zmin && z < src.zmax && isfinite(z);
+                px = z;
+                py = -__fmul_rn(__fdiv_rn(__fsub_rn((float)u, src.cx), src.fx), z);
+                pz = -__fmul_rn(__fdiv_rn(__fsub_rn((float)v, src.cy), src.fy), z);
+            }
+            fin = fin && isfinite(px) && isfinite(py) && isfinite(pz);
+            if (fin) {
+                const double x = px, y = py, z = pz;
+                mx = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(T.v[0], x), __dmul_rn(T.v[1], y)), __dmul_rn(T.v[2], z)), T.v[3]);
+                my = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(T.v[4], x), __dmul_rn(T.v[5], y)), __dmul_rn(T.v[6], z)), T.v[7]);
+                const double mz = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(T.v[8], x), __dmul_rn(T.v[9], y)), __dmul_rn(T.v[10], z)), T.v[11]);
+                keep = mz > g.z_lo && mz < g.z_hi;
+            }
+        }
+        const unsigned long long balf = __ballot(fin), balk = __ballot(keep);
+        if (lane == 0) { s_wfin[wave] = __popcll(balf); s_wkeep[wave] = __popcll(balk); }
+        __syncthreads();
+        int before = s_keep, totk = 0, totf = 0;
+        for (int k = 0; k < 16; ++k) {
+            if (k < wave) before += s_wkeep[k];
+            totk += s_wkeep[k]; totf += s_wfin[k];
+        }
+        if (keep && start_in) {
+            const int rank = before + __popcll(balk & ((1ull << lane) - 1ull));
+            int r1, c1;
+            if (rank % g.sub == 0 && (occ_cell(mx, g.ox, g.res, g.W, c1) & occ_cell(my, g.oy, g.res, g.H, r1))) {
+                s_queue[atomicAdd(&s_qn, 1)] = (unsigned)r1 << 16 | (unsigned)c1;
+                if (RELOC_OCC_FORM < 2 || (unsigned)(r1 - wr0) >= (unsigned)OCC_WIN || (unsigned)(c1 - wc0) >= (unsigned)OCC_WIN) {
+                    atomicMin(&s_box[0], r1); atomicMax(&s_box[1], r1); atomicMin(&s_box[2], c1); atomicMax(&s_box[3], c1);
+                }
+            }
+        }
+        __syncthreads();
+        if (tid == 0) { s_keep += totk; s_fin += totf; }
+        __syncthreads();
+        if (s_qn > 1024) drain();
+    }
+    drain();
+
+    // the start cell: one add per wave
+    const int wave_start = wave_sum_i32(at_start);
+    if (lane == 0 && wave_start != 0) atomicAdd(&s_win[(OCC_WIN / 2) * OCC_WIN + OCC_WIN / 2], wave_start);
+    __syncthreads();
+    // the window: one clamped update per cell, straight into the grid (no far add ever lands on a window cell)
+    for (int i = tid; i < OCC_WIN * OCC_WIN; i += 1024) {
+        const int d = s_win[i];
+        const int r = wr0 + i / OCC_WIN, c = wc0 + i % OCC_WIN;
+        if (d != 0 && (unsigned)r < (unsigned)g.H && (unsigned)c < (unsigned)g.W) {
+            const int v = (int)units[r * g.W + c] + d;
+            units[r * g.W + c] = (int8_t)min(max(v, RELOC_OCC_L_MIN), RELOC_OCC_L_MAX);
+        }
+    }
+    if (tid == 0) {                               // (h)
+        int rays = 0;
+        if (s_fin == 0) counters[2] += 1;
+        else if (s_keep > 0 && start_in) {
+            rays = (s_keep + g.sub - 1) / g.sub;
+            counters[0] += 1;
+            counters[1] += rays;
+        }
+        frame[0] = rays;
+        const bool far = s_box[1] >= 0;            // the far cells of a ray lie in the box its two ends span
+        frame[1] = far ? min(s_box[0], r0) : 1; frame[2] = far ? max(s_box[1], r0) : 0;
+        frame[3] = far ? min(s_box[2], c0) : 1; frame[4] = far ? max(s_box[3], c0) : 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_occ_apply(int8_t *__restrict__ units, int32_t *__restrict__ acc, const int32_t *__restrict__ frame,
+                                                   int W, int H)
+{
+    const int r_lo = max(frame[1], 0), r_hi = min(frame[2], H - 1), c_lo = max(frame[3], 0), c_hi = min(frame[4], W - 1);
+    if (r_hi < r_lo || c_hi < c_lo) return;
+    const int bw = c_hi - c_lo + 1, n = bw * (r_hi - r_lo + 1);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int idx = (r_lo + i / bw) * W + c_lo + i % bw;
+        const int d = acc[idx];
+        if (d != 0) {
+            units[idx] = (int8_t)min(max((int)units[idx] + d, RELOC_OCC_L_MIN), RELOC_OCC_L_MAX);
+            acc[idx] = 0;
+        }
+    }
+}
+
+// (f): the .pgm's plane, rows flipped
+__global__ __launch_bounds__(256) void k_occ_classify(const int8_t *__restrict__ units, uint8_t *__restrict__ pgm, int W, int H)
+{
+    const int n = W * H;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int v = units[i], r = i / W, c = i % W;
+        pgm[(H - 1 - r) * W + c] = v >= RELOC_OCC_UNITS_OCC ? RELOC_OCC_PGM_OCC : v <= RELOC_OCC_UNITS_FREE ? RELOC_OCC_PGM_FREE : RELOC_OCC_PGM_UNKNOWN;
+    }
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------
+void occ_release(reloc_ctx *ctx)
+{
+    if (ctx->occ.block) (void)hipFree(ctx->occ.block);
+    ctx->occ = OccState{};
+}
+
+static inline bool occ_finite(double v) { return v - v == 0.0; }
+
+RELOC_API int reloc_occ_configure(reloc_ctx *ctx, double origin_x, double origin_y, double res, int w_cells, int h_cells, double z_lo,
+                                  double z_hi, int subsample)
+{
+    ARG_CHECK_CTX(ctx, w_cells > 0 && h_cells > 0 && subsample > 0 && occ_finite(origin_x) && occ_finite(origin_y) && occ_finite(res) &&
+                           res > 0 && occ_finite(z_lo) && occ_finite(z_hi),
+                  "reloc_occ_configure: sizes, res and subsample must be positive, everything finite");
+    if (w_cells > OCC_MAX_SIDE || h_cells > OCC_MAX_SIDE || (int64_t)w_cells * h_cells > RELOC_OCC_MAX_CELLS) {
+        reloc_set_error("occupancy grid %d x %d exceeds the capacity (%d cells, %d per side)", w_cells, h_cells, RELOC_OCC_MAX_CELLS, OCC_MAX_SIDE);
+        return RELOC_E_CAPACITY;
+    }
+    OccState &o = ctx->occ;
+    const int64_t cells = (int64_t)w_cells * h_cells;
+    const size_t acc_bytes = (size_t)((cells * 4 + 7) & ~(int64_t)7);
+    const size_t bytes = acc_bytes + 3 * 8 + OCC_FRAME_WORDS * 4 + (size_t)cells * 2;
+    if (!o.block || o.block_cells != cells) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        occ_release(ctx);
+        HIP_TRY(hipMalloc((void **)&o.block, bytes));
+        o.block_cells = cells;
+        o.acc = (int32_t *)o.block;
+        o.counters = (int64_t *)(o.block + acc_bytes);
+        o.frame = (int32_t *)(o.block + acc_bytes + 3 * 8);
+        o.units = (int8_t *)(o.block + acc_bytes + 3 * 8 + OCC_FRAME_WORDS * 4);
+        o.pgm = (uint8_t *)o.units + cells;
+    }
+    o.w = w_cells; o.h = h_cells; o.sub = subsample;
+    o.ox = origin_x; o.oy = origin_y; o.res = res; o.z_lo = z_lo; o.z_hi = z_hi;
+    HIP_TRY(hipMemsetAsync(o.block, 0, bytes, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return RELOC_OK;
+}
+
+static int occ_check(reloc_ctx *ctx, const double *T12, const char *who)
+{
+    if (!ctx->occ.on()) { reloc_set_error("%s: no occupancy map on this context (reloc_occ_configure)", who); return RELOC_E_STATE; }
+    for (int k = 0; k < 12; ++k)
+        if (!occ_finite(T12[k])) { reloc_set_error("bad argument: %s: the transform must be finite", who); return RELOC_E_ARG; }
+    return RELOC_OK;
+}
+
+// the two launches of a frame on the context's stream
+static int occ_launch(reloc_ctx *ctx, int kind, const OccSrc &src, const double *T12)
+{
+    const OccState &o = ctx->occ;
+    OccT T;
+    memcpy(T.v, T12, sizeof(T.v));
+    const OccGeom g{o.ox, o.oy, o.res, o.z_lo, o.z_hi, o.w, o.h, o.sub};
+    if (kind == OCC_SRC_POINTS) hipLaunchKernelGGL(k_occ_integrate<OCC_SRC_POINTS>, dim3(1), dim3(1024), 0, ctx->stream, src, T, g, o.units, o.acc, o.counters, o.frame);
+    else if (kind == OCC_SRC_DEPTH_F32) hipLaunchKernelGGL(k_occ_integrate<OCC_SRC_DEPTH_F32>, dim3(1), dim3(1024), 0, ctx->stream, src, T, g, o.units, o.acc, o.counters, o.frame);
+    else hipLaunchKernelGGL(k_occ_integrate<OCC_SRC_DEPTH_U16>, dim3(1), dim3(1024), 0, ctx->stream, src, T, g, o.units, o.acc, o.counters, o.frame);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_occ_apply, dim3(64), dim3(256), 0, ctx->stream, o.units, o.acc, (const int32_t *)o.frame, o.w, o.h);
+    HIP_TRY(hipGetLastError());
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_occ_integrate_points(reloc_ctx *ctx, const float *pts, int n, const double T12[12], int32_t *out_rays)
+{
+    ARG_CHECK_CTX(ctx, n >= 0 && (pts || n == 0) && T12, "reloc_occ_integrate_points");
+    if (int rc = occ_check(ctx, T12, "reloc_occ_integrate_points")) return rc;
+    HostStaging st{ctx};
+    OccSrc src{};
+    src.n = n;
+    src.data = n > 0 ? st.upload_slot(5, pts, (int64_t)n * 3) : nullptr;
+    st.run([&] { return occ_launch(ctx, OCC_SRC_POINTS, src, T12); });
+    const int32_t rays = st.count(ctx->occ.frame);
+    if (int rc = st.finish()) return rc;
+    if (out_rays) *out_rays = rays;
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_occ_integrate_depth(reloc_ctx *ctx, const void *depth, int is_f32, int w, int h, int step, const double K4[4],
+                                        float zmin, float zmax, const double T12[12], int32_t *out_rays)
+{
+    ARG_CHECK_CTX(ctx, depth && w > 0 && h > 0 && step > 0 && K4 && T12, "reloc_occ_integrate_depth");
+    if (int rc = occ_check(ctx, T12, "reloc_occ_integrate_depth")) return rc;
+    if ((int64_t)w * h > (int64_t)ctx->max_w * ctx->max_h) { reloc_set_error("depth image exceeds ctx capacity"); return RELOC_E_CAPACITY; }
+    HostStaging st{ctx};
+    OccSrc src{nullptr, 0, w, h, w, step, (float)K4[2], (float)K4[3], (float)K4[0], (float)K4[1], zmin, zmax};
+    src.data = st.upload_slot(5, (const uint8_t *)depth, (int64_t)w * h * (is_f32 ? 4 : 2));
+    st.run([&] { return occ_launch(ctx, is_f32 ? OCC_SRC_DEPTH_F32 : OCC_SRC_DEPTH_U16, src, T12); });
+    const int32_t rays = st.count(ctx->occ.frame);
+    if (int rc = st.finish()) return rc;
+    if (out_rays) *out_rays = rays;
+    return RELOC_OK;
+}
+
+// The plane of the last dense stereo pass where it lies.  out_rays == NULL: enqueues only, the host never waits.
+RELOC_API int reloc_occ_integrate_stereo_dev(reloc_ctx *ctx, int step, float zmin, float zmax, const double T12[12], int32_t *out_rays)
+{
+    ARG_CHECK_CTX(ctx, step > 0 && T12, "reloc_occ_integrate_stereo_dev");
+    if (int rc = occ_check(ctx, T12, "reloc_occ_integrate_stereo_dev")) return rc;
+    const StereoState::Dense &d = ctx->stereo.dense;
+    if (!d.block || d.w == 0) { reloc_set_error("no dense stereo pass on this context yet"); return RELOC_E_STATE; }
+    const double *K4 = ctx->cam.K4;
+    const OccSrc src{d.mm, 0, d.w, d.h, d.w, step, (float)K4[2], (float)K4[3], (float)K4[0], (float)K4[1], zmin, zmax};
+    if (int rc = occ_launch(ctx, OCC_SRC_DEPTH_U16, src, T12)) return rc;
+    if (out_rays) {
+        HIP_TRY(hipMemcpyAsync(out_rays, ctx->occ.frame, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_occ_read(reloc_ctx *ctx, int8_t *units, uint8_t *pgm, int64_t counters[3])
+{
+    ARG_CHECK_CTX(ctx, true, "reloc_occ_read");
+    const OccState &o = ctx->occ;
+    if (!o.on()) { reloc_set_error("reloc_occ_read: no occupancy map on this context (reloc_occ_configure)"); return RELOC_E_STATE; }
+    const size_t cells = (size_t)o.w * o.h;
+    if (units) HIP_TRY(hipMemcpyAsync(units, o.units, cells, hipMemcpyDeviceToHost, ctx->stream));
+    if (pgm) {
+        hipLaunchKernelGGL(k_occ_classify, dim3((unsigned)((cells + 255) / 256 < 1024 ? (cells + 255) / 256 : 1024)), dim3(256), 0, ctx->stream,
+                           (const int8_t *)o.units, o.pgm, o.w, o.h);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(pgm, o.pgm, cells, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (counters) HIP_TRY(hipMemcpyAsync(counters, o.counters, 3 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return RELOC_OK;
+}

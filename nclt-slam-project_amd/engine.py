@@ -637,14 +637,18 @@ class Engine:
             raise N.RelocError(f"{what}: left and right sizes differ")
         return frame, right_frame, w, h
 
-    def stereo_frame_depth(self, frame: np.ndarray, right_frame: np.ndarray, right_engine: "Engine", order_rgb: bool = False):
+    def stereo_frame_depth(self, frame: np.ndarray, right_frame: np.ndarray, right_engine: "Engine", order_rgb: bool = False,
+                           download: bool = True):
         """the (H', W') uint16 depth image, millimetres, 0 = no depth, of a pair of camera frames (reloc_stereo_frame_depth):
         both through the gray half of their engines' image chains, no ORB, then the dense pass with this engine's set_stereo
-        setting and camera; H' x W' is the working frame"""
+        setting and camera; H' x W' is the working frame.  download=False: the plane stays on the device (occ_integrate_stereo,
+        stereo_dense_debug) and (H', W') is returned"""
         frame, right_frame, w, h = self._stereo_pair(frame, right_frame, right_engine, "stereo_frame_depth")
-        mm = np.zeros(h * w, np.uint16)
+        mm = np.zeros(h * w, np.uint16) if download else None
         ow, oh = N.outs(i32, i32)
         self._api.reloc_stereo_frame_depth(self._ctx, right_engine._ctx, frame, right_frame, w, h, int(order_rgb), mm, ow, oh)
+        if not download:
+            return oh.value, ow.value
         return mm[: ow.value * oh.value].reshape(oh.value, ow.value).copy()
 
     def stereo_frame_points(self, frame: np.ndarray, right_frame: np.ndarray, right_engine: "Engine", step: int = 4,
@@ -795,6 +799,61 @@ class Engine:
         self._api.reloc_depth_points(self._ctx, depth, int(depth.dtype == np.float32), w, h, int(step), K4, float(zmin),
                                      float(zmax), pts, n)
         return pts[: n.value].copy()
+
+    # ------------------------------------------------------------------ teach-time occupancy map (reloc_spec.h "OCCUPANCY")
+    def occ_configure(self, origin_x: float, origin_y: float, res: float, w_cells: int, h_cells: int, z_lo: float = 0.2,
+                      z_hi: float = 2.0, subsample: int = 4):
+        """allocates and zeroes the context's log-odds grid of h_cells x w_cells cells; a second call resets it"""
+        self._api.reloc_occ_configure(self._ctx, float(origin_x), float(origin_y), float(res), int(w_cells), int(h_cells), float(z_lo),
+                                      float(z_hi), int(subsample))
+        self._occ_shape = (int(h_cells), int(w_cells))
+
+    @staticmethod
+    def _occ_T(T, what):
+        T = np.ascontiguousarray(T, np.float64)
+        if T.shape == (4, 4):
+            T = np.ascontiguousarray(T[:3])
+        if T.shape != (3, 4):
+            raise N.RelocError(f"{what}: expected a (3, 4) or (4, 4) sensor-to-map transform")
+        return T
+
+    def occ_integrate_points(self, points, T) -> int:
+        """one frame from an (n, 3) float32 cloud in the sensor frame; returns the number of rays"""
+        pts = np.ascontiguousarray(points, np.float32)
+        if pts.size and (pts.ndim != 2 or pts.shape[1] != 3):
+            raise N.RelocError("occ_integrate_points: expected an (n, 3) cloud")
+        rays = i32()
+        self._api.reloc_occ_integrate_points(self._ctx, pts if pts.size else None, pts.size // 3, self._occ_T(T, "occ_integrate_points"), rays)
+        return rays.value
+
+    def occ_integrate_depth(self, depth, T, step: int = 4, K4=K4_DEFAULT, zmin: float = 0.3, zmax: float = 10.0) -> int:
+        """one frame from a depth image as depth_points takes it; the cloud is never written"""
+        depth = np.ascontiguousarray(depth)
+        if depth.dtype not in (np.float32, np.uint16) or depth.ndim != 2:
+            raise N.RelocError("occ_integrate_depth: expected an (H, W) float32 (metres) or uint16 (millimetres) image")
+        h, w = depth.shape
+        rays = i32()
+        self._api.reloc_occ_integrate_depth(self._ctx, depth, int(depth.dtype == np.float32), w, h, int(step),
+                                            np.ascontiguousarray(K4, np.float64), float(zmin), float(zmax),
+                                            self._occ_T(T, "occ_integrate_depth"), rays)
+        return rays.value
+
+    def occ_integrate_stereo(self, T, step: int = 4, zmin: float = 0.3, zmax: float = 10.0, wait: bool = True):
+        """one frame from the depth plane of this engine's last dense stereo pass, on the device; wait=False enqueues only
+        and returns None"""
+        rays = i32() if wait else None
+        self._api.reloc_occ_integrate_stereo_dev(self._ctx, int(step), float(zmin), float(zmax), self._occ_T(T, "occ_integrate_stereo"), rays)
+        return rays.value if wait else None
+
+    def occ_read(self, units: bool = True, pgm: bool = True):
+        """dict(units (H, W) int8, pgm (H, W) uint8 with rows flipped, frames_integrated, total_points_integrated,
+        frames_skipped_empty) of the context's map; units / pgm only when asked for"""
+        shape = getattr(self, "_occ_shape", None) or (0, 0)
+        u = np.zeros(shape, np.int8) if units and shape[0] else None
+        p = np.zeros(shape, np.uint8) if pgm and shape[0] else None
+        c = np.zeros(3, np.int64)
+        self._api.reloc_occ_read(self._ctx, u, p, c)
+        return dict(units=u, pgm=p, frames_integrated=int(c[0]), total_points_integrated=int(c[1]), frames_skipped_empty=int(c[2]))
 
     def hamming_matrix(self, a, b):
         a = self._desc(a, "hamming_matrix"); b = self._desc(b, "hamming_matrix")

@@ -3,6 +3,9 @@
     VisualLandmarkMatcher(pkl_path, log_csv)            --landmarks --out-csv [--landmarks-return --swap-flag]
                                                         [--match-policy {cross,ratio} --lowe-ratio R]
     VisualLandmarkRecorder(out_pkl, min_disp_m=2.0)     --out --min-disp
+    TeachDepthMapper(out_prefix, origin_x, origin_y, width_m, height_m, res)
+                                                        --out-prefix --origin-x --origin-y --width-m --height-m --res
+                                                        [--depth-topic NAME --depth-k4 FX FY CX CY]
     both, for a rectified stereo pair without a depth sensor:
                                                         [--stereo-baseline M --stereo-num-disparities N
                                                          --stereo-rectify-right FILE.npz --right-topic NAME]
@@ -233,6 +236,103 @@ def make_recorder_node(out_pkl, min_disp_m=2.0, cv2=None, bayer=None, mask=None,
     return VisualLandmarkRecorder()
 
 
+def pc2_msg_to_points(msg):
+    """(n, 3) float32 x y z of a PointCloud2 with float32 fields, in the message's frame; an empty or field-less message gives
+    (0, 3), like the reference mapper's _parse_pc2 (D:40-61).  Non-finite rows stay: the library drops them."""
+    offsets = {f.name: f.offset for f in msg.fields}
+    n = msg.width * msg.height
+    if msg.point_step == 0 or n == 0 or "x" not in offsets:
+        return np.zeros((0, 3), np.float32)
+    rows = np.frombuffer(msg.data, dtype=np.uint8)[: n * msg.point_step].reshape(n, msg.point_step)
+    cols = [rows[:, offsets[k]:offsets[k] + 4].copy().view("<f4")[:, 0] for k in ("x", "y", "z")]
+    return np.stack(cols, axis=-1).astype(np.float32)
+
+
+def img_msg_to_depth(msg):
+    """the depth topic's image as the occupancy map takes it: float32 metres or uint16 millimetres, undecoded"""
+    if msg.encoding in ("16UC1", "mono16"):
+        return np.frombuffer(msg.data, dtype=np.uint16).reshape(msg.height, msg.width).copy()
+    if msg.encoding == "32FC1":
+        return np.frombuffer(msg.data, dtype=np.float32).reshape(msg.height, msg.width).copy()
+    raise ValueError(f"unexpected depth encoding {msg.encoding}")
+
+
+def make_depth_mapper_node(out_prefix, origin_x=-110.0, origin_y=-50.0, width_m=200.0, height_m=60.0, res=0.1, depth_topic=None,
+                           K4=None, engine=None):
+    """The reference's TeachDepthMapper(out_prefix, origin_x, origin_y, width_m, height_m, res) (teach_run_depth_mapper.py:83-111)
+    over mapper.OccupancyMapperCore: /depth_points clouds, or with depth_topic that depth image itself (camera K4 = fx, fy, cx,
+    cy; default the reference camera's), ray-traced on the device into the map frame of the message's frame_id.  engine: the
+    Engine that holds the grid (default: a new one)."""
+    import rclpy
+    import rclpy.time
+    import tf2_ros
+    from sensor_msgs.msg import Image, PointCloud2
+    from .engine import K4_DEFAULT, Engine
+    from .mapper import OccupancyMapperCore, tf_to_matrix
+    Node = _node_base()
+
+    class TeachDepthMapper(Node):
+        def __init__(self):
+            super().__init__("teach_depth_mapper")
+            self.core = OccupancyMapperCore(engine if engine is not None else Engine(), origin_x, origin_y, width_m, height_m, res,
+                                            out_prefix=out_prefix)
+            self.K4 = np.asarray(K4_DEFAULT if K4 is None else K4, np.float64)
+            self.tf_buf = tf2_ros.Buffer()
+            self.tf_listener = tf2_ros.TransformListener(self.tf_buf, self)
+            self.frames_skipped_tf = 0
+            if depth_topic is None:
+                self.create_subscription(PointCloud2, "/depth_points", self.cb, 10)
+            else:
+                self.create_subscription(Image, depth_topic, self.depth_cb, 10)
+            self.get_logger().info(f"Mapper grid {self.core.W}x{self.core.H} @ {res}m origin=({origin_x},{origin_y})")
+            signal.signal(signal.SIGTERM, self._save_and_exit)
+            signal.signal(signal.SIGINT, self._save_and_exit)
+            signal.signal(signal.SIGUSR1, self._save_partial)
+            self.log_timer = self.create_timer(10.0, self.log_progress)
+            self.periodic_save_timer = self.create_timer(60.0, self._save_partial)
+
+        def log_progress(self):
+            c = self.core.counters()
+            self.get_logger().info(f"frames: integrated={c['frames_integrated']} skipped_tf={self.frames_skipped_tf} "
+                                   f"skipped_empty={c['frames_skipped_empty']} pts_total={c['total_points_integrated']}")
+
+        def _transform(self, msg):
+            """map <- the message's frame as a 3 x 4 matrix, or None (counted) when tf has none"""
+            try:
+                tf = self.tf_buf.lookup_transform("map", msg.header.frame_id, rclpy.time.Time()).transform
+            except Exception:
+                self.frames_skipped_tf += 1
+                return None
+            t, q = tf.translation, tf.rotation
+            return tf_to_matrix((t.x, t.y, t.z), (q.x, q.y, q.z, q.w))
+
+        def cb(self, msg):
+            T = self._transform(msg)
+            if T is not None:
+                self.core.integrate_cloud(pc2_msg_to_points(msg), T)
+
+        def depth_cb(self, msg):
+            T = self._transform(msg)
+            if T is None:
+                return
+            try:
+                self.core.integrate_depth(img_msg_to_depth(msg), self.K4, T)
+            except ValueError as e:
+                self.get_logger().warn(f"depth: {e}")
+
+        def _save_and_exit(self, *a):
+            self.get_logger().warn(f"Saving map to {out_prefix}.pgm/.yaml and exiting")
+            self.core.save()
+            rclpy.shutdown()
+            sys.exit(0)
+
+        def _save_partial(self, *a):
+            self.get_logger().info(f"[PARTIAL] saving intermediate to {out_prefix}.pgm/.yaml")
+            self.core.save()
+
+    return TeachDepthMapper()
+
+
 def _chain_args(args):
     """the trailing (cv2, bayer, mask, orb, pixel_format) of the node factories; cv2 None = the default shim; only as far as
     the last one that is not its default, nothing when all are defaults"""
@@ -327,3 +427,20 @@ def recorder_main(argv=None):
     except ValueError as e:
         ap.error(str(e))
     _spin(lambda: make_recorder_node(args.out, args.min_disp, *raw, **kw), "save")
+
+
+def mapper_main(argv=None):
+    """the reference mapper's flags and defaults (teach_run_depth_mapper.py:242-250), plus --depth-topic / --depth-k4"""
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out-prefix", required=True)
+    ap.add_argument("--origin-x", type=float, default=-110.0)
+    ap.add_argument("--origin-y", type=float, default=-50.0)
+    ap.add_argument("--width-m", type=float, default=200.0)
+    ap.add_argument("--height-m", type=float, default=60.0)
+    ap.add_argument("--res", type=float, default=0.1)
+    ap.add_argument("--depth-topic", default=None, metavar="NAME",
+                    help="take this depth image topic instead of the /depth_points cloud")
+    ap.add_argument("--depth-k4", type=float, nargs=4, default=None, metavar=("FX", "FY", "CX", "CY"), help="camera of --depth-topic")
+    args = ap.parse_args(argv)
+    tail = () if args.depth_topic is None and args.depth_k4 is None else (args.depth_topic, args.depth_k4)
+    _spin(lambda: make_depth_mapper_node(args.out_prefix, args.origin_x, args.origin_y, args.width_m, args.height_m, args.res, *tail), "save")

@@ -142,6 +142,18 @@ class StereoDepthCore:
             return self.engine.stereo_frame_points(left_frame, right_frame, self.right_engine, int(step), zmin, zmax)
         return shim_backend(self.cv2).depth_points(self.depth(left_frame, right_frame), int(step), self.K4, zmin, zmax)
 
+    def integrate(self, mapper, left_frame, right_frame, T):
+        """one frame of a teach-time occupancy map (mapper.OccupancyMapperCore) from the pair: the dense pass, then the map's
+        integrate_stereo on the plane where it lies -- the depth never crosses to the host; the mapper must stand on this
+        core's left Engine.  On the cv2-shaped path the depth image goes through the mapper's integrate_depth.  T: the
+        camera-link-to-map transform.  Returns the number of rays."""
+        if self.engine is not None:
+            if mapper.engine is not self.engine:
+                raise ValueError("StereoDepthCore.integrate: the mapper must use this core's left engine")
+            self.engine.stereo_frame_depth(left_frame, right_frame, self.right_engine, download=False)
+            return mapper.integrate_stereo(T)
+        return mapper.integrate_depth(self.depth(left_frame, right_frame), self.K4, T)
+
     def close(self):
         """closes the right eye's Engine, which this core made; the left Engine stays the caller's"""
         if self.right_engine is not None:
