@@ -1,13 +1,13 @@
 // reloc_occupancy.hip -- teach-time occupancy map (include/reloc_spec.h "OCCUPANCY"; DESIGN.md "Occupancy map").
 // A frame is two launches on the context's stream:
-//   k_occ_integrate  one workgroup of 1024: depth pixel or cloud row -> sensor point -> map point -> filters -> ordered rank
-//                    (ballot + prefix, the form of k_depth_points; the cloud is never written), rays queued in LDS and
+//   k_occ_integrate  one workgroup of 1024: depth pixel (depth_grid_point) or cloud row -> sensor point -> map point -> filters
+//                    -> ordered rank (block_rank, as k_depth_points; the cloud is never written), rays queued in LDS and
 //                    walked one per lane, 1024 at a time.  The cells of a OCC_WIN x OCC_WIN window around the start cell are
 //                    summed in LDS and applied to the grid once; the start cell itself, which every ray crosses, is summed in
 //                    registers and added once per wave.  Cells beyond the window take global int32 atomics into `acc`.
 //   k_occ_apply      v = clamp(v + acc) and acc = 0 over the box that the frame's far rays span (nothing when there are none).
 // Integer sums only: the grid is the same whatever order the adds arrive in.
-#include "reloc_internal.h"
+#include "reloc_teach.h"
 
 // Developer switch for A/B builds (build.build_variant, tools/exp_occupancy.py): 2 = the shipped form; 1 = only the start cell is
 // summed on chip, every other cell takes a global atomic; 0 = every update is a global atomic.  The grid is the same in all.
@@ -20,8 +20,8 @@ constexpr int OCC_MAX_SIDE = 32768;   // a queued end cell is row << 16 | col
 
 struct OccGeom { double ox, oy, res, z_lo, z_hi; int W, H, sub; };
 struct OccT { double v[12]; };
-// what a frame reads: a cloud (n rows of 3 floats) or a depth plane with the arguments of k_depth_points
-struct OccSrc { const void *data; int n; int w, h, stride, step; float cx, cy, fx, fy, zmin, zmax; };
+// what a frame reads: a cloud (n rows of 3 floats at pts) or the grid of a depth plane, as k_depth_points takes it
+struct OccSrc { const float *pts; int n; DepthGrid grid; };
 enum { OCC_SRC_POINTS = 0, OCC_SRC_DEPTH_F32 = 1, OCC_SRC_DEPTH_U16 = 2 };
 // frame record on the device: [0] rays of the frame, [1..4] box of the far rays (row lo, row hi, col lo, col hi; hi < lo: none)
 constexpr int OCC_FRAME_WORDS = 8;
@@ -42,21 +42,18 @@ __global__ __launch_bounds__(1024) void k_occ_integrate(OccSrc src, OccT T, OccG
 {
     __shared__ int s_win[OCC_WIN * OCC_WIN];
     __shared__ unsigned s_queue[OCC_QUEUE];
-    __shared__ int s_wfin[16], s_wkeep[16];
-    __shared__ int s_fin, s_keep, s_qn;
+    __shared__ int s_wsum[16];
+    __shared__ int s_fin, s_qn;
     __shared__ int s_box[4];                      // row lo, row hi, col lo, col hi of the end cells beyond the window
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     for (int i = tid; i < OCC_WIN * OCC_WIN; i += 1024) s_win[i] = 0;
-    if (tid == 0) { s_fin = 0; s_keep = 0; s_qn = 0; s_box[0] = g.H; s_box[1] = -1; s_box[2] = g.W; s_box[3] = -1; }
+    if (tid == 0) { s_fin = 0; s_qn = 0; s_box[0] = g.H; s_box[1] = -1; s_box[2] = g.W; s_box[3] = -1; }
     int r0, c0;
     const bool start_in = occ_cell(T.v[3], g.ox, g.res, g.W, c0) & occ_cell(T.v[7], g.oy, g.res, g.H, r0);
     const int wr0 = r0 - OCC_WIN / 2, wc0 = c0 - OCC_WIN / 2;
-    int gw = 0, n = src.n;
-    if (SRC != OCC_SRC_POINTS) {
-        gw = (src.w + src.step - 1) / src.step;
-        n = gw * ((src.h + src.step - 1) / src.step);
-    }
+    const int n = SRC == OCC_SRC_POINTS ? src.n : src.grid.cols() * src.grid.rows();
     int at_start = 0;                             // this lane's share of the start cell's sum
+    int n_fin = 0, n_keep = 0;                    // this lane's finite points; the workgroup's kept points so far
     __syncthreads();
 
     // the rays waiting in the queue, one per lane
@@ -91,40 +88,25 @@ __global__ __launch_bounds__(1024) void k_occ_integrate(OccSrc src, OccT T, OccG
         bool fin = false, keep = false;
         double mx = 0, my = 0;
         if (i < n) {
-            float px, py, pz;
+            float p[3];
             if (SRC == OCC_SRC_POINTS) {
-                const float *p = reinterpret_cast<const float *>(src.data) + (size_t)3 * i;
-                px = p[0]; py = p[1]; pz = p[2];
+                for (int k = 0; k < 3; ++k) p[k] = src.pts[(size_t)3 * i + k];
                 fin = true;
-            } else {                                              // the pixel of k_depth_points, the same arithmetic
-                const int v = (i / gw) * src.step, u = (i % gw) * src.step;
-                float z;
-                if (SRC == OCC_SRC_DEPTH_F32) z = reinterpret_cast<const float *>(src.data)[(size_t)v * src.stride + u];
-                else z = __fdiv_rn((float)reinterpret_cast<const uint16_t *>(src.data)[(size_t)v * src.stride + u], 1000.0f);
-                fin = z > src.zmin && z < src.zmax && isfinite(z);
-                px = z;
-                py = -__fmul_rn(__fdiv_rn(__fsub_rn((float)u, src.cx), src.fx), z);
-                pz = -__fmul_rn(__fdiv_rn(__fsub_rn((float)v, src.cy), src.fy), z);
-            }
-            fin = fin && isfinite(px) && isfinite(py) && isfinite(pz);
+            } else fin = depth_grid_point(src.grid, SRC == OCC_SRC_DEPTH_F32, i, p);
+            fin = fin && isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]);
             if (fin) {
-                const double x = px, y = py, z = pz;
+                const double x = p[0], y = p[1], z = p[2];
                 mx = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(T.v[0], x), __dmul_rn(T.v[1], y)), __dmul_rn(T.v[2], z)), T.v[3]);
                 my = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(T.v[4], x), __dmul_rn(T.v[5], y)), __dmul_rn(T.v[6], z)), T.v[7]);
                 const double mz = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(T.v[8], x), __dmul_rn(T.v[9], y)), __dmul_rn(T.v[10], z)), T.v[11]);
                 keep = mz > g.z_lo && mz < g.z_hi;
             }
         }
-        const unsigned long long balf = __ballot(fin), balk = __ballot(keep);
-        if (lane == 0) { s_wfin[wave] = __popcll(balf); s_wkeep[wave] = __popcll(balk); }
-        __syncthreads();
-        int before = s_keep, totk = 0, totf = 0;
-        for (int k = 0; k < 16; ++k) {
-            if (k < wave) before += s_wkeep[k];
-            totk += s_wkeep[k]; totf += s_wfin[k];
-        }
+        n_fin += fin;
+        int total;
+        const int rank = block_rank(keep, s_wsum, n_keep, total);      // among the kept points, which is what sub counts
+        n_keep += total;
         if (keep && start_in) {
-            const int rank = before + __popcll(balk & ((1ull << lane) - 1ull));
             int r1, c1;
             if (rank % g.sub == 0 && (occ_cell(mx, g.ox, g.res, g.W, c1) & occ_cell(my, g.oy, g.res, g.H, r1))) {
                 s_queue[atomicAdd(&s_qn, 1)] = (unsigned)r1 << 16 | (unsigned)c1;
@@ -134,15 +116,14 @@ __global__ __launch_bounds__(1024) void k_occ_integrate(OccSrc src, OccT T, OccG
             }
         }
         __syncthreads();
-        if (tid == 0) { s_keep += totk; s_fin += totf; }
-        __syncthreads();
         if (s_qn > 1024) drain();
     }
     drain();
 
-    // the start cell: one add per wave
-    const int wave_start = wave_sum_i32(at_start);
+    // the start cell and the finite points: one add per wave
+    const int wave_start = wave_sum_i32(at_start), wave_fin = wave_sum_i32(n_fin);
     if (lane == 0 && wave_start != 0) atomicAdd(&s_win[(OCC_WIN / 2) * OCC_WIN + OCC_WIN / 2], wave_start);
+    if (lane == 0 && wave_fin != 0) atomicAdd(&s_fin, wave_fin);
     __syncthreads();
     // the window: one clamped update per cell, straight into the grid (no far add ever lands on a window cell)
     for (int i = tid; i < OCC_WIN * OCC_WIN; i += 1024) {
@@ -156,8 +137,8 @@ __global__ __launch_bounds__(1024) void k_occ_integrate(OccSrc src, OccT T, OccG
     if (tid == 0) {                               // (h)
         int rays = 0;
         if (s_fin == 0) counters[2] += 1;
-        else if (s_keep > 0 && start_in) {
-            rays = (s_keep + g.sub - 1) / g.sub;
+        else if (n_keep > 0 && start_in) {
+            rays = (n_keep + g.sub - 1) / g.sub;
             counters[0] += 1;
             counters[1] += rays;
         }
@@ -243,19 +224,21 @@ static int occ_check(reloc_ctx *ctx, const double *T12, const char *who)
     return RELOC_OK;
 }
 
-// the two launches of a frame on the context's stream
-static int occ_launch(reloc_ctx *ctx, int kind, const OccSrc &src, const double *T12)
+// A frame: the two launches on the context's stream, then the frame's rays into *out_rays (may be NULL); !wait: enqueues only.
+static int occ_frame(reloc_ctx *ctx, HostStaging &st, int kind, const OccSrc &src, const double *T12, int32_t *out_rays, bool wait)
 {
     const OccState &o = ctx->occ;
     OccT T;
     memcpy(T.v, T12, sizeof(T.v));
     const OccGeom g{o.ox, o.oy, o.res, o.z_lo, o.z_hi, o.w, o.h, o.sub};
-    if (kind == OCC_SRC_POINTS) hipLaunchKernelGGL(k_occ_integrate<OCC_SRC_POINTS>, dim3(1), dim3(1024), 0, ctx->stream, src, T, g, o.units, o.acc, o.counters, o.frame);
-    else if (kind == OCC_SRC_DEPTH_F32) hipLaunchKernelGGL(k_occ_integrate<OCC_SRC_DEPTH_F32>, dim3(1), dim3(1024), 0, ctx->stream, src, T, g, o.units, o.acc, o.counters, o.frame);
-    else hipLaunchKernelGGL(k_occ_integrate<OCC_SRC_DEPTH_U16>, dim3(1), dim3(1024), 0, ctx->stream, src, T, g, o.units, o.acc, o.counters, o.frame);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_occ_apply, dim3(64), dim3(256), 0, ctx->stream, o.units, o.acc, (const int32_t *)o.frame, o.w, o.h);
-    HIP_TRY(hipGetLastError());
+    st.launch(kind == OCC_SRC_POINTS ? k_occ_integrate<OCC_SRC_POINTS> : kind == OCC_SRC_DEPTH_F32 ? k_occ_integrate<OCC_SRC_DEPTH_F32>
+                                                                                                 : k_occ_integrate<OCC_SRC_DEPTH_U16>,
+              dim3(1), dim3(1024), src, T, g, o.units, o.acc, o.counters, o.frame);
+    st.launch(k_occ_apply, dim3(64), dim3(256), o.units, o.acc, (const int32_t *)o.frame, o.w, o.h);
+    if (!wait) return st.rc;
+    const int32_t rays = st.count(o.frame);
+    if (int rc = st.finish()) return rc;
+    if (out_rays) *out_rays = rays;
     return RELOC_OK;
 }
 
@@ -264,14 +247,8 @@ RELOC_API int reloc_occ_integrate_points(reloc_ctx *ctx, const float *pts, int n
     ARG_CHECK_CTX(ctx, n >= 0 && (pts || n == 0) && T12, "reloc_occ_integrate_points");
     if (int rc = occ_check(ctx, T12, "reloc_occ_integrate_points")) return rc;
     HostStaging st{ctx};
-    OccSrc src{};
-    src.n = n;
-    src.data = n > 0 ? st.upload_slot(5, pts, (int64_t)n * 3) : nullptr;
-    st.run([&] { return occ_launch(ctx, OCC_SRC_POINTS, src, T12); });
-    const int32_t rays = st.count(ctx->occ.frame);
-    if (int rc = st.finish()) return rc;
-    if (out_rays) *out_rays = rays;
-    return RELOC_OK;
+    const OccSrc src{n > 0 ? st.upload_slot(5, pts, (int64_t)n * 3) : nullptr, n, {}};
+    return occ_frame(ctx, st, OCC_SRC_POINTS, src, T12, out_rays, true);
 }
 
 RELOC_API int reloc_occ_integrate_depth(reloc_ctx *ctx, const void *depth, int is_f32, int w, int h, int step, const double K4[4],
@@ -281,13 +258,9 @@ RELOC_API int reloc_occ_integrate_depth(reloc_ctx *ctx, const void *depth, int i
     if (int rc = occ_check(ctx, T12, "reloc_occ_integrate_depth")) return rc;
     if ((int64_t)w * h > (int64_t)ctx->max_w * ctx->max_h) { reloc_set_error("depth image exceeds ctx capacity"); return RELOC_E_CAPACITY; }
     HostStaging st{ctx};
-    OccSrc src{nullptr, 0, w, h, w, step, (float)K4[2], (float)K4[3], (float)K4[0], (float)K4[1], zmin, zmax};
-    src.data = st.upload_slot(5, (const uint8_t *)depth, (int64_t)w * h * (is_f32 ? 4 : 2));
-    st.run([&] { return occ_launch(ctx, is_f32 ? OCC_SRC_DEPTH_F32 : OCC_SRC_DEPTH_U16, src, T12); });
-    const int32_t rays = st.count(ctx->occ.frame);
-    if (int rc = st.finish()) return rc;
-    if (out_rays) *out_rays = rays;
-    return RELOC_OK;
+    const void *ddepth = st.upload_slot(5, (const uint8_t *)depth, (int64_t)w * h * (is_f32 ? 4 : 2));
+    const OccSrc src{nullptr, 0, depth_grid(ddepth, is_f32, w, h, w, step, K4, zmin, zmax)};
+    return occ_frame(ctx, st, is_f32 ? OCC_SRC_DEPTH_F32 : OCC_SRC_DEPTH_U16, src, T12, out_rays, true);
 }
 
 // The plane of the last dense stereo pass where it lies.  out_rays == NULL: enqueues only, the host never waits.
@@ -297,14 +270,9 @@ RELOC_API int reloc_occ_integrate_stereo_dev(reloc_ctx *ctx, int step, float zmi
     if (int rc = occ_check(ctx, T12, "reloc_occ_integrate_stereo_dev")) return rc;
     const StereoState::Dense &d = ctx->stereo.dense;
     if (!d.block || d.w == 0) { reloc_set_error("no dense stereo pass on this context yet"); return RELOC_E_STATE; }
-    const double *K4 = ctx->cam.K4;
-    const OccSrc src{d.mm, 0, d.w, d.h, d.w, step, (float)K4[2], (float)K4[3], (float)K4[0], (float)K4[1], zmin, zmax};
-    if (int rc = occ_launch(ctx, OCC_SRC_DEPTH_U16, src, T12)) return rc;
-    if (out_rays) {
-        HIP_TRY(hipMemcpyAsync(out_rays, ctx->occ.frame, 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-    }
-    return RELOC_OK;
+    HostStaging st{ctx};
+    const OccSrc src{nullptr, 0, depth_grid(d.mm, 0, d.w, d.h, d.w, step, ctx->cam.K4, zmin, zmax)};
+    return occ_frame(ctx, st, OCC_SRC_DEPTH_U16, src, T12, out_rays, out_rays != nullptr);
 }
 
 RELOC_API int reloc_occ_read(reloc_ctx *ctx, int8_t *units, uint8_t *pgm, int64_t counters[3])
@@ -312,15 +280,14 @@ RELOC_API int reloc_occ_read(reloc_ctx *ctx, int8_t *units, uint8_t *pgm, int64_
     ARG_CHECK_CTX(ctx, true, "reloc_occ_read");
     const OccState &o = ctx->occ;
     if (!o.on()) { reloc_set_error("reloc_occ_read: no occupancy map on this context (reloc_occ_configure)"); return RELOC_E_STATE; }
-    const size_t cells = (size_t)o.w * o.h;
-    if (units) HIP_TRY(hipMemcpyAsync(units, o.units, cells, hipMemcpyDeviceToHost, ctx->stream));
+    const int64_t cells = (int64_t)o.w * o.h;
+    HostStaging st{ctx};
+    if (units) st.download(units, o.units, cells);
     if (pgm) {
-        hipLaunchKernelGGL(k_occ_classify, dim3((unsigned)((cells + 255) / 256 < 1024 ? (cells + 255) / 256 : 1024)), dim3(256), 0, ctx->stream,
-                           (const int8_t *)o.units, o.pgm, o.w, o.h);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(pgm, o.pgm, cells, hipMemcpyDeviceToHost, ctx->stream));
+        st.launch(k_occ_classify, dim3((unsigned)((cells + 255) / 256 < 1024 ? (cells + 255) / 256 : 1024)), dim3(256), (const int8_t *)o.units,
+                  o.pgm, o.w, o.h);
+        st.download(pgm, o.pgm, cells);
     }
-    if (counters) HIP_TRY(hipMemcpyAsync(counters, o.counters, 3 * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return RELOC_OK;
+    if (counters) st.download(counters, o.counters, 3 * 8);
+    return st.finish();
 }

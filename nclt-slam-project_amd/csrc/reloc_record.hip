@@ -14,26 +14,65 @@
 // One lane per keypoint; survivors are compacted in keypoint order by a block-wide scan.
 // Lens distortion (include/reloc_spec.h): k_record<true> / k_accumulate<true> back-project through the inverse model,
 //   (x_u, y_u) = undistort(u, v); X = x_u * z, Y = y_u * z in float64, cast to float32,
-// with the same pixel-based gates (the kept rows do not change).  DIST is a template parameter of the __global__ kernels
-// themselves, not of a shared __device__ body: moving the body into a __forceinline__ function called from two kernels
-// changed the pinhole kernels' code, while templating the kernel keeps every instruction of <false> as it was.
-// Depth source: KPD, the second template parameter of the same two kernels and for the same reason.  false: the depth image
-// (the four instantiations there have always been, instruction for instruction).  true: a per-keypoint uint16 array indexed by
-// the keypoint's row in the frame's ORB output, the millimetres of k_stereo_depth (reloc_stereo.hip; include/reloc_spec.h
-// "STEREO"): dz = (float)kp_mm[i] / 1000.0f, k_record skips the 3x3 patch and takes sd = 0, everything else is the same
-// expression -- border, ground, range, back-projection, compaction, pose and index of an accumulated record.
-#include "reloc_internal.h"
+// with the same pixel-based gates (the kept rows do not change).
+// Depth source: KPD.  false: the depth image.  true: a per-keypoint uint16 array indexed by the keypoint's row in the frame's ORB
+// output, the millimetres of k_stereo_depth (reloc_stereo.hip; include/reloc_spec.h "STEREO"): dz = (float)kp_mm[i] / 1000.0f,
+// k_record skips the 3x3 patch and takes sd = 0, everything else is the same expression -- border, ground, range,
+// back-projection, compaction, pose and index of an accumulated record.
+// DIST and KPD are template parameters of the two __global__ kernels, so each of the eight instantiations holds only its own
+// branch.  What the two kernels have in common -- the keypoint's pixel, its depth, the back-projection, the descriptor copy and
+// the compaction (block_rank, reloc_teach.h) -- are __forceinline__ functions templated the same way; the compiler schedules
+// their bodies with the caller's, so an instantiation's instructions are not those of a hand-inlined copy, only its results are
+// (DESIGN.md "Teach-side kernels" has the registers and instruction counts before and after the functions were shared).
+#include "reloc_teach.h"
 
-// camera-frame point of the rounded pixel (u, v) at depth dz through the inverse distortion model
-__device__ __forceinline__ void back_project_dist(double fx, double fy, double cx, double cy, const DistCoef &dc, int u, int v,
-                                                  float dz, float *o)
+// keypoint i of the frame's ORB output, its rounded pixel and (keypoint_depth) its depth in metres
+struct KeyPixel { float x, y, dz; int u, v; };
+
+// reads and rounds the keypoint; true iff the pixel has all eight neighbours in the w x h frame
+__device__ __forceinline__ bool keypoint_pixel(const float *__restrict__ f_xy, int i, int w, int h, KeyPixel &k)
 {
-    const double K4[4] = {fx, fy, cx, cy};
-    double xu, yu;
-    undistort_norm(dc, K4, (double)u, (double)v, xu, yu);
-    o[0] = (float)__dmul_rn(xu, (double)dz);
-    o[1] = (float)__dmul_rn(yu, (double)dz);
+    k.x = f_xy[2 * i]; k.y = f_xy[2 * i + 1];
+    k.u = (int)rintf(k.x); k.v = (int)rintf(k.y);
+    return k.u >= 1 && k.u < w - 1 && k.v >= 1 && k.v < h - 1;
+}
+
+// KPD: depth holds the millimetres per keypoint, else the depth image with rows of dstride pixels
+template <bool KPD>
+__device__ __forceinline__ float keypoint_depth(const uint16_t *__restrict__ depth, int dstride, int i, int u, int v)
+{
+    return __fdiv_rn((float)(KPD ? depth[i] : depth[(size_t)v * dstride + u]), 1000.0f);
+}
+
+// camera-frame point of the rounded pixel (u, v) at depth dz: pinhole, or through the inverse distortion model
+template <bool DIST>
+__device__ __forceinline__ void back_project(double fx, double fy, double cx, double cy, const DistCoef &dc, int u, int v, float dz,
+                                             float *o)
+{
+    if constexpr (DIST) {
+        const double K4[4] = {fx, fy, cx, cy};
+        double xu, yu;
+        undistort_norm(dc, K4, (double)u, (double)v, xu, yu);
+        o[0] = (float)__dmul_rn(xu, (double)dz);
+        o[1] = (float)__dmul_rn(yu, (double)dz);
+    } else {
+        o[0] = (float)__ddiv_rn(__dmul_rn(__dsub_rn((double)u, cx), (double)dz), fx);
+        o[1] = (float)__ddiv_rn(__dmul_rn(__dsub_rn((double)v, cy), (double)dz), fy);
+    }
     o[2] = dz;
+}
+
+// row pos of a record from keypoint i: position, camera-frame point, descriptor
+template <bool DIST>
+__device__ __forceinline__ void keypoint_row(const KeyPixel &k, int i, int pos, double fx, double fy, double cx, double cy,
+                                             const DistCoef &dc, const uint8_t *__restrict__ f_desc, float *__restrict__ o_xy,
+                                             float *__restrict__ o_pts, uint8_t *__restrict__ o_desc)
+{
+    o_xy[2 * pos] = k.x; o_xy[2 * pos + 1] = k.y;
+    back_project<DIST>(fx, fy, cx, cy, dc, k.u, k.v, k.dz, o_pts + 3 * pos);
+    const uint4 *s = reinterpret_cast<const uint4 *>(f_desc + (size_t)i * 32);
+    uint4 *d = reinterpret_cast<uint4 *>(o_desc + (size_t)pos * 32);
+    d[0] = s[0]; d[1] = s[1];
 }
 
 struct RecordParams {
@@ -67,70 +106,44 @@ __global__ __launch_bounds__(1024) void k_record(const float *__restrict__ f_xy,
 {
     RELOC_SMALL_KERNEL_PRIO();
     __shared__ int s_wsum[16];
-    __shared__ int s_base;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int n = min(*f_count, max_feat);
-    if (tid == 0) s_base = 0;
-    __syncthreads();
+    int base = 0;
     for (int i0 = 0; i0 < n; i0 += 1024) {
         const int i = i0 + tid;
         bool keep = false;
-        float x = 0, y = 0, dz = 0;
-        int u = 0, v = 0;
-        if (i < n) {
-            x = f_xy[2 * i]; y = f_xy[2 * i + 1];
-            u = (int)rintf(x); v = (int)rintf(y);
-            if (u >= 1 && u < p.w - 1 && v >= 1 && v < p.h - 1 && v > p.ground_y) {
-                float sd = 0.0f;
-                if constexpr (KPD) {
-                    dz = __fdiv_rn((float)depth[i], 1000.0f);      // depth: the per-keypoint millimetres; no patch, sd = 0
-                } else {
-                    dz = __fdiv_rn((float)depth[(size_t)v * dstride + u], 1000.0f);
-                    float vals[9];
-                    int cnt = 0;
-                    for (int dy = -1; dy <= 1; ++dy)
-                        for (int dx = -1; dx <= 1; ++dx) {
-                            const float m = __fdiv_rn((float)depth[(size_t)(v + dy) * dstride + (u + dx)], 1000.0f);
-                            if (m > 0.01f) vals[cnt++] = m;
-                        }
-                    sd = 999.0f;
-                    if (cnt >= 3) {
-                        const float mean = __fdiv_rn(np_sum9(vals, cnt), (float)cnt);
-                        float sq[9];
-                        for (int k = 0; k < cnt; ++k) { const float d = __fsub_rn(vals[k], mean); sq[k] = __fmul_rn(d, d); }
-                        sd = __fsqrt_rn(__fdiv_rn(np_sum9(sq, cnt), (float)cnt));
+        KeyPixel k = {};
+        if (i < n && keypoint_pixel(f_xy, i, p.w, p.h, k) && k.v > p.ground_y) {
+            const int u = k.u, v = k.v;
+            k.dz = keypoint_depth<KPD>(depth, dstride, i, u, v);
+            float sd = 0.0f;                                       // KPD: no patch
+            if constexpr (!KPD) {
+                float vals[9];
+                int cnt = 0;
+                for (int dy = -1; dy <= 1; ++dy)
+                    for (int dx = -1; dx <= 1; ++dx) {
+                        const float m = __fdiv_rn((float)depth[(size_t)(v + dy) * dstride + (u + dx)], 1000.0f);
+                        if (m > 0.01f) vals[cnt++] = m;
                     }
+                sd = 999.0f;
+                if (cnt >= 3) {
+                    const float mean = __fdiv_rn(np_sum9(vals, cnt), (float)cnt);
+                    float sq[9];
+                    for (int j = 0; j < cnt; ++j) { const float d = __fsub_rn(vals[j], mean); sq[j] = __fmul_rn(d, d); }
+                    sd = __fsqrt_rn(__fdiv_rn(np_sum9(sq, cnt), (float)cnt));
                 }
-                keep = dz > p.depth_min && dz < p.depth_max && sd < p.var_max;
             }
+            keep = k.dz > p.depth_min && k.dz < p.depth_max && sd < p.var_max;
         }
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) s_wsum[wave] = __popcll(bal);
-        __syncthreads();
-        int before = s_base;
-        for (int w = 0; w < wave; ++w) before += s_wsum[w];
-        int total = 0;
-        for (int w = 0; w < 16; ++w) total += s_wsum[w];
+        int total;
+        const int pos = block_rank(keep, s_wsum, base, total);
         if (keep) {
-            const int pos = before + __popcll(bal & ((1ull << lane) - 1ull));
-            o_xy[2 * pos] = x; o_xy[2 * pos + 1] = y;
-            if constexpr (DIST) {
-                back_project_dist(p.fx, p.fy, p.cx, p.cy, dc, u, v, dz, o_pts + 3 * pos);
-            } else {
-                o_pts[3 * pos] = (float)__ddiv_rn(__dmul_rn(__dsub_rn((double)u, p.cx), (double)dz), p.fx);
-                o_pts[3 * pos + 1] = (float)__ddiv_rn(__dmul_rn(__dsub_rn((double)v, p.cy), (double)dz), p.fy);
-                o_pts[3 * pos + 2] = dz;
-            }
+            keypoint_row<DIST>(k, i, pos, p.fx, p.fy, p.cx, p.cy, dc, f_desc, o_xy, o_pts, o_desc);
             o_idx[pos] = i;
-            const uint4 *s = reinterpret_cast<const uint4 *>(f_desc + (size_t)i * 32);
-            uint4 *d = reinterpret_cast<uint4 *>(o_desc + (size_t)pos * 32);
-            d[0] = s[0]; d[1] = s[1];
         }
-        __syncthreads();
-        if (tid == 0) s_base += total;
-        __syncthreads();
+        base += total;
     }
-    if (tid == 0) *o_n = s_base;
+    if (tid == 0) *o_n = base;
 }
 
 // the recorder's gates on the w x h working frame of ctx's camera
@@ -221,22 +234,17 @@ RELOC_API int reloc_record_frame_stereo(reloc_ctx *ctx, reloc_ctx *right, const 
                                         int32_t *n_out, int32_t *n_kp, int32_t *n_stereo)
 {
     ARG_CHECK_CTX(ctx, right && img && img_right && n_out && w >= 64 && h >= 64 && nfeatures > 0, "reloc_record_frame_stereo");
-    if (!ctx->stereo.on()) { reloc_set_error("stereo is off on this context (reloc_set_stereo)"); return RELOC_E_STATE; }
-    if (w > ctx->max_w || h > ctx->max_h || w > right->max_w || h > right->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
+    if (int rc = stereo_pair_entry(ctx, right, w, h)) return rc;
     *n_out = 0;
     if (n_kp) *n_kp = 0;
     if (n_stereo) *n_stereo = 0;
-    HostStaging st{ctx};
+    StereoPairStaging st(ctx, right);
     RecordRows rows;
     if (!rows.alloc(st)) return st.rc;
-    const int bpp = image_chain_frame_bpp(ctx);
-    st.upload(ctx->frame_img, img, (int64_t)w * h * bpp);
-    bool right_busy = false;       // the right context's stream holds a copy from the caller's memory
+    st.upload_pair(img, img_right, w, h);
     st.run([&] {
         const uint8_t *src = ctx->frame_img;
-        if (int rc = orb_run(&ctx, 1, &src, w, h, w * bpp, true, order, nfeatures, true)) return rc;
-        right_busy = true;
-        HIP_TRY(hipMemcpyAsync(right->frame_img, img_right, (size_t)w * h * image_chain_frame_bpp(right), hipMemcpyHostToDevice, right->stream));
+        if (int rc = orb_run(&ctx, 1, &src, w, h, w * image_chain_frame_bpp(ctx), true, order, nfeatures, true)) return rc;
         return stereo_frame(ctx, right, right->frame_img, w, h, order, &w, &h);      // from here on the working frame
     });
     rows.launch<true>(st, ctx->stereo.mm, w, h);
@@ -245,10 +253,7 @@ RELOC_API int reloc_record_frame_stereo(reloc_ctx *ctx, reloc_ctx *right, const 
     const int32_t ns = nk < ctx->max_feat ? nk : ctx->max_feat;
     std::vector<uint8_t> status((size_t)(n_stereo && ns > 0 ? ns : 0));
     if (!status.empty()) st.download(status.data(), ctx->stereo.status, ns);
-    const int rc = st.finish();
-    // after an error the two streams may not be ordered: nothing of the caller's right frame stays in flight
-    if (rc && right_busy) (void)hipStreamSynchronize(right->stream);
-    if (rc) return rc;
+    if (int rc = st.finish()) return rc;
     *n_out = n;
     if (n_kp) *n_kp = nk;
     for (uint8_t s : status) *n_stereo += s == RELOC_STEREO_OK;
@@ -311,7 +316,6 @@ __global__ __launch_bounds__(1024) void k_accumulate(const float *__restrict__ f
     RELOC_SMALL_KERNEL_PRIO();
     __shared__ int s_wsum[16];
     __shared__ double s_wmin[16];
-    __shared__ int s_base;
     __shared__ double s_near;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int oc = tick->outcome;
@@ -328,7 +332,6 @@ __global__ __launch_bounds__(1024) void k_accumulate(const float *__restrict__ f
     }
     for (int d = 32; d >= 1; d >>= 1) dmin = fmin(dmin, __shfl_xor(dmin, d));
     if (lane == 0) s_wmin[wave] = dmin;
-    if (tid == 0) s_base = 0;
     __syncthreads();
     if (tid == 0) {
         double m = s_wmin[0];
@@ -344,47 +347,22 @@ __global__ __launch_bounds__(1024) void k_accumulate(const float *__restrict__ f
     const int n = min(*f_count, max_feat);
     uint8_t *o_desc = db_desc + p.T * 32;
     float *o_pts = db_pts3d + p.T * 3, *o_xy = db_kp2d + p.T * 2;
+    int base = 0;
     for (int i0 = 0; i0 < n; i0 += 1024) {
         const int i = i0 + tid;
         bool keep = false;
-        float x = 0, y = 0, dz = 0;
-        int u = 0, v = 0;
-        if (i < n) {
-            x = f_xy[2 * i]; y = f_xy[2 * i + 1];
-            u = (int)rintf(x); v = (int)rintf(y);
-            if (u >= 1 && u < p.w - 1 && v >= 1 && v < p.h - 1) {
-                if constexpr (KPD) dz = __fdiv_rn((float)depth[i], 1000.0f);       // depth: the per-keypoint millimetres
-                else dz = __fdiv_rn((float)depth[(size_t)v * dstride + u], 1000.0f);
-                keep = dz > p.zmin && dz < p.zmax;
-            }
+        KeyPixel k = {};
+        if (i < n && keypoint_pixel(f_xy, i, p.w, p.h, k)) {
+            k.dz = keypoint_depth<KPD>(depth, dstride, i, k.u, k.v);
+            keep = k.dz > p.zmin && k.dz < p.zmax;
         }
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) s_wsum[wave] = __popcll(bal);
-        __syncthreads();
-        int before = s_base;
-        for (int w = 0; w < wave; ++w) before += s_wsum[w];
-        int total = 0;
-        for (int w = 0; w < 16; ++w) total += s_wsum[w];
-        if (keep) {
-            const int pos = before + __popcll(bal & ((1ull << lane) - 1ull));
-            o_xy[2 * pos] = x; o_xy[2 * pos + 1] = y;
-            if constexpr (DIST) {
-                back_project_dist(p.fx, p.fy, p.cx, p.cy, dc, u, v, dz, o_pts + 3 * pos);
-            } else {
-                o_pts[3 * pos] = (float)__ddiv_rn(__dmul_rn(__dsub_rn((double)u, p.cx), (double)dz), p.fx);
-                o_pts[3 * pos + 1] = (float)__ddiv_rn(__dmul_rn(__dsub_rn((double)v, p.cy), (double)dz), p.fy);
-                o_pts[3 * pos + 2] = dz;
-            }
-            const uint4 *sp = reinterpret_cast<const uint4 *>(f_desc + (size_t)i * 32);
-            uint4 *dp = reinterpret_cast<uint4 *>(o_desc + (size_t)pos * 32);
-            dp[0] = sp[0]; dp[1] = sp[1];
-        }
-        __syncthreads();
-        if (tid == 0) s_base += total;
-        __syncthreads();
+        int total;
+        const int pos = block_rank(keep, s_wsum, base, total);
+        if (keep) keypoint_row<DIST>(k, i, pos, p.fx, p.fy, p.cx, p.cy, dc, f_desc, o_xy, o_pts, o_desc);
+        base += total;
     }
     if (tid == 0) {
-        const int cnt = s_base;
+        const int cnt = base;
         res->n_kpts = cnt;
         res->nearest_m = nearest;
         if (cnt < p.min_kpts) { res->appended = 0; return; }
@@ -497,46 +475,36 @@ RELOC_API int reloc_accumulate_result(reloc_ctx *ctx, int32_t *appended, int32_t
 // Depth image -> obstacle point cloud (reference relay depth_cb,
 // tf_wall_clock_relay_v55.py:1020-1038): every `step`-th pixel, keep 0.3 < z < 10 and finite,
 // point = (z, -(u - cx) / fx * z, -(v - cy) / fy * z) in float32, raster order.
-__global__ __launch_bounds__(1024) void k_depth_points(const void *__restrict__ depth, int is_f32, int w, int h, int dstride_px,
-                                                       int step, float cx, float cy, float fx, float fy, float zmin, float zmax,
-                                                       float *__restrict__ out, int32_t *__restrict__ o_n)
+__global__ __launch_bounds__(1024) void k_depth_points(DepthGrid g, float *__restrict__ out, int32_t *__restrict__ o_n)
 {
     __shared__ int s_wsum[16];
-    __shared__ int s_base;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int gw = (w + step - 1) / step, gh = (h + step - 1) / step;
-    const int n = gw * gh;
-    if (tid == 0) s_base = 0;
-    __syncthreads();
+    const int tid = threadIdx.x;
+    const int n = g.cols() * g.rows();
+    int base = 0;
     for (int i0 = 0; i0 < n; i0 += 1024) {
         const int i = i0 + tid;
-        bool keep = false;
-        float z = 0;
-        int u = 0, v = 0;
-        if (i < n) {
-            v = (i / gw) * step; u = (i % gw) * step;
-            if (is_f32) z = reinterpret_cast<const float *>(depth)[(size_t)v * dstride_px + u];
-            else z = __fdiv_rn((float)reinterpret_cast<const uint16_t *>(depth)[(size_t)v * dstride_px + u], 1000.0f);
-            keep = z > zmin && z < zmax && isfinite(z);
-        }
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) s_wsum[wave] = __popcll(bal);
-        __syncthreads();
-        int before = s_base;
-        for (int k = 0; k < wave; ++k) before += s_wsum[k];
-        int total = 0;
-        for (int k = 0; k < 16; ++k) total += s_wsum[k];
-        if (keep) {
-            const int pos = before + __popcll(bal & ((1ull << lane) - 1ull));
-            const float px = __fmul_rn(__fdiv_rn(__fsub_rn((float)u, cx), fx), z);
-            const float py = __fmul_rn(__fdiv_rn(__fsub_rn((float)v, cy), fy), z);
-            out[3 * pos] = z; out[3 * pos + 1] = -px; out[3 * pos + 2] = -py;
-        }
-        __syncthreads();
-        if (tid == 0) s_base += total;
-        __syncthreads();
+        float p[3];
+        const bool keep = i < n && depth_grid_point(g, g.is_f32 != 0, i, p);
+        int total;
+        const int pos = block_rank(keep, s_wsum, base, total);
+        if (keep) { out[3 * pos] = p[0]; out[3 * pos + 1] = p[1]; out[3 * pos + 2] = p[2]; }
+        base += total;
     }
-    if (tid == 0) *o_n = s_base;
+    if (tid == 0) *o_n = base;
+}
+
+// The cloud of a depth plane on the device into the caller's points (room for cols x rows rows of 3 floats): scratch slot 6,
+// k_depth_points, the count, then the rows.  Returns the rows, 0 after an error.
+static int32_t depth_cloud(HostStaging &st, const DepthGrid &g, float *points)
+{
+    const int64_t cap = (int64_t)g.cols() * g.rows();
+    float *dout = st.slot<float>(6, cap * 3 + 4);
+    if (st.rc) return 0;
+    int32_t *o_n = (int32_t *)(dout + cap * 3);
+    st.launch(k_depth_points, dim3(1), dim3(1024), g, dout, o_n);
+    const int32_t n = st.count(o_n);
+    if (n > 0) st.download(points, dout, (int64_t)n * 12);
+    return n;
 }
 
 // depth: (h, w) float32 metres (is_f32 = 1) or uint16 millimetres (is_f32 = 0), dense rows.
@@ -546,17 +514,9 @@ RELOC_API int reloc_depth_points(reloc_ctx *ctx, const void *depth, int is_f32, 
 {
     ARG_CHECK_CTX(ctx, depth && points && n_out && w > 0 && h > 0 && step > 0 && K4, "reloc_depth_points");
     if ((int64_t)w * h > (int64_t)ctx->max_w * ctx->max_h) { reloc_set_error("depth image exceeds ctx capacity"); return RELOC_E_CAPACITY; }
-    const int64_t npt = (int64_t)((w + step - 1) / step) * ((h + step - 1) / step);
-    const int esz = is_f32 ? 4 : 2;
     HostStaging st{ctx};
-    float *dout = st.slot<float>(6, npt * 3 + 4);
-    if (st.rc) return st.rc;
-    int32_t *o_n = (int32_t *)(dout + npt * 3);
-    const void *ddepth = st.upload_slot(5, (const uint8_t *)depth, (int64_t)w * h * esz);
-    st.launch(k_depth_points, dim3(1), dim3(1024), ddepth, is_f32, w, h, w, step, (float)K4[2], (float)K4[3], (float)K4[0],
-              (float)K4[1], zmin, zmax, dout, o_n);
-    const int32_t n = st.count(o_n);
-    if (n > 0) st.download(points, dout, (int64_t)n * 12);
+    const void *ddepth = st.upload_slot(5, (const uint8_t *)depth, (int64_t)w * h * (is_f32 ? 4 : 2));
+    const int32_t n = depth_cloud(st, depth_grid(ddepth, is_f32, w, h, w, step, K4, zmin, zmax), points);
     if (int rc = st.finish()) return rc;
     *n_out = n;
     return RELOC_OK;
@@ -567,31 +527,13 @@ RELOC_API int reloc_stereo_frame_points(reloc_ctx *ctx, reloc_ctx *right, const 
                                         int order, int step, float zmin, float zmax, float *points, int32_t *n_out)
 {
     ARG_CHECK_CTX(ctx, right && img && img_right && points && n_out && w >= 64 && h >= 64 && step > 0, "reloc_stereo_frame_points");
-    if (!ctx->stereo.on()) { reloc_set_error("stereo is off on this context (reloc_set_stereo)"); return RELOC_E_STATE; }
-    if (right == ctx) { reloc_set_error("bad argument: the right eye needs a context of its own"); return RELOC_E_ARG; }
-    if (w > ctx->max_w || h > ctx->max_h || w > right->max_w || h > right->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
+    if (int rc = stereo_pair_entry(ctx, right, w, h)) return rc;
     *n_out = 0;
-    HostStaging st{ctx};
-    // the working frame is no larger than the frame handed in: the slot holds either's grid
-    const int64_t cap = (int64_t)((w + step - 1) / step) * ((h + step - 1) / step);
-    float *dout = st.slot<float>(6, cap * 3 + 4);
-    if (st.rc) return st.rc;
-    int32_t *o_n = (int32_t *)(dout + cap * 3);
-    st.upload(ctx->frame_img, img, (int64_t)w * h * image_chain_frame_bpp(ctx));
-    bool right_busy = false;       // the right context's stream holds a copy from the caller's memory
-    st.run([&] {
-        right_busy = true;
-        HIP_TRY(hipMemcpyAsync(right->frame_img, img_right, (size_t)w * h * image_chain_frame_bpp(right), hipMemcpyHostToDevice, right->stream));
-        return stereo_dense_frame(ctx, right, w, h, order, &w, &h);      // from here on the working frame
-    });
-    const double *K4 = ctx->cam.K4;
-    st.launch(k_depth_points, dim3(1), dim3(1024), (const void *)ctx->stereo.dense.mm, 0, w, h, w, step, (float)K4[2], (float)K4[3],
-              (float)K4[0], (float)K4[1], zmin, zmax, dout, o_n);
-    const int32_t n = st.count(o_n);
-    if (n > 0) st.download(points, dout, (int64_t)n * 12);
-    const int rc = st.finish();
-    if (right_busy) (void)hipStreamSynchronize(right->stream);
-    if (rc) return rc;
+    StereoPairStaging st(ctx, right);
+    st.upload_pair(img, img_right, w, h);
+    st.run([&] { return stereo_dense_frame(ctx, right, w, h, order, &w, &h); });      // from here on the working frame
+    const int32_t n = depth_cloud(st, depth_grid(ctx->stereo.dense.mm, 0, w, h, w, step, ctx->cam.K4, zmin, zmax), points);
+    if (int rc = st.finish()) return rc;
     *n_out = n;
     return RELOC_OK;
 }

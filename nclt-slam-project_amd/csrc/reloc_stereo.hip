@@ -13,7 +13,7 @@
 // Each eye has its own row stride (a pyramid level or a stage's plane: (w + 63) & ~63; a dense gray plane or a caller's mono8
 // frame: w; reloc_stereo_depth: the caller's).  The bytes are staged one by one through the cache: rows start at any
 // alignment, and a byte outside 0 <= x < w, row padding included, is never fetched.
-#include "reloc_internal.h"
+#include "reloc_teach.h"
 #include "reloc_pixels.h"
 
 constexpr int SR = RELOC_STEREO_R, SP = 2 * RELOC_STEREO_R + 1;     // radius and side of the patch
@@ -321,6 +321,38 @@ static int stereo_pair_check(reloc_ctx *ctx, reloc_ctx *right, int w, int h, int
     return image_chain_check_prepared(pair, 1, 2, true, *ww, *wh);
 }
 
+// The gray planes of a pass, plane[e] with rows of stride[e] bytes, e = 1 the right eye: the right eye's chain on right's stream,
+// the left eye's (lsrc == NULL: none, plane[0] is not written) on ctx's.  The streams are ordered by events in both directions:
+// right's goes on behind what ctx's holds so far -- the copy that brought the right frame (a _dev caller orders its frames on
+// ctx's stream) and the last stereo kernel, which still reads the right chain's planes -- and ctx's behind the right eye's chain.
+static int stereo_gray_planes(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *lsrc, const uint8_t *rsrc, int w, int h, int ww, int wh,
+                              int order, const uint8_t *plane[2], int stride[2])
+{
+    StereoState &s = ctx->stereo;
+    // eye e: c's frame (w x h as handed in) through the gray half of its chain; into dst when no stage ran on a 3-channel frame
+    auto eye = [&](int e, reloc_ctx *c, const uint8_t *src, uint8_t *dst) {
+        const uint8_t *planes[RELOC_BATCH_MAX];
+        const uint8_t *const *srcs = &src;
+        int channels = 1;
+        stride[e] = w * image_chain_frame_bpp(c);
+        if (int rc = image_chain_gray(&c, 1, true, &srcs, w, h, ww, wh, &stride[e], &channels, gray_flags(c, order), planes)) return rc;
+        plane[e] = srcs[0];
+        if (channels == 3) {
+            if (int rc = image_gray_plain(c, plane[e], ww, wh, stride[e], order, dst)) return rc;
+            plane[e] = dst; stride[e] = ww;
+        }
+        return (int)RELOC_OK;
+    };
+    HIP_TRY(hipEventRecord(s.left_ready, ctx->stream));
+    HIP_TRY(hipStreamWaitEvent(right->stream, s.left_ready, 0));
+    if (lsrc)
+        if (int rc = eye(0, ctx, lsrc, s.dense.left)) return rc;
+    if (int rc = eye(1, right, rsrc, s.plane)) return rc;
+    HIP_TRY(hipEventRecord(s.right_done, right->stream));
+    HIP_TRY(hipStreamWaitEvent(ctx->stream, s.right_done, 0));
+    return RELOC_OK;
+}
+
 int stereo_frame(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img_right_dev, int w, int h, int order, int *ww, int *wh)
 {
     StereoState &s = ctx->stereo;
@@ -329,24 +361,12 @@ int stereo_frame(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img_right_dev,
         reloc_set_error("stereo: the left eye's last ORB frame is %dx%d, the right eye's working frame %dx%d", ctx->orb.w, ctx->orb.h, *ww, *wh);
         return RELOC_E_STATE;
     }
-    // the right eye's chain on its own stream, behind what ctx's stream holds so far: the copy that brought the right frame
-    // (a _dev caller orders its frames on ctx's stream) and the last stereo kernel, which still reads the chain's planes
-    HIP_TRY(hipEventRecord(s.left_ready, ctx->stream));
-    HIP_TRY(hipStreamWaitEvent(right->stream, s.left_ready, 0));
-    const uint8_t *src = img_right_dev, *planes[RELOC_BATCH_MAX];
-    const uint8_t *const *srcs = &src;
-    int stride = w * image_chain_frame_bpp(right), channels = 1;
-    if (int rc = image_chain_gray(&right, 1, true, &srcs, w, h, *ww, *wh, &stride, &channels, gray_flags(right, order), planes)) return rc;
-    const uint8_t *rplane = srcs[0];
-    if (channels == 3) {       // no stage ran on a 3-channel frame
-        if (int rc = image_gray_plain(right, rplane, *ww, *wh, stride, order, s.plane)) return rc;
-        rplane = s.plane; stride = *ww;
-    }
-    HIP_TRY(hipEventRecord(s.right_done, right->stream));
-    HIP_TRY(hipStreamWaitEvent(ctx->stream, s.right_done, 0));
+    const uint8_t *plane[2];
+    int stride[2];
+    if (int rc = stereo_gray_planes(ctx, right, nullptr, img_right_dev, w, h, *ww, *wh, order, plane, stride)) return rc;
     const OrbLevel &L0 = ctx->orb.tab.lev[0];       // level 0 of the pyramid is the chain's output (the blurred levels live in buf.blur)
     const StereoParams p = {ctx->cam.K4[0], s.baseline, *ww, *wh, s.min_disp, s.num_disp, s.uniq, s.lr};
-    if (int rc = stereo_launch(ctx, ctx->orb.buf.pyr + L0.off, L0.stride, rplane, stride, ctx->orb.buf.f_xy, ctx->orb.buf.f_count,
+    if (int rc = stereo_launch(ctx, ctx->orb.buf.pyr + L0.off, L0.stride, plane[1], stride[1], ctx->orb.buf.f_xy, ctx->orb.buf.f_count,
                                ctx->max_feat, p, s.mm, s.disp, s.status)) return rc;
     s.ran = true;
     return RELOC_OK;
@@ -357,16 +377,15 @@ RELOC_API int reloc_stereo_debug(reloc_ctx *ctx, uint16_t *depth_mm, float *disp
     ARG_CHECK_CTX(ctx, n, "reloc_stereo_debug");
     const StereoState &s = ctx->stereo;
     if (!s.disp || !s.ran) { reloc_set_error("no stereo pass on this context yet"); return RELOC_E_STATE; }
-    int32_t k = 0;
-    HIP_TRY(hipMemcpyAsync(&k, ctx->orb.buf.f_count, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HostStaging st{ctx};
+    int32_t k = st.count(ctx->orb.buf.f_count);
     k = k < ctx->max_feat ? k : ctx->max_feat;
     if (k > 0) {
-        if (depth_mm) HIP_TRY(hipMemcpyAsync(depth_mm, s.mm, (size_t)k * 2, hipMemcpyDeviceToHost, ctx->stream));
-        if (disparity) HIP_TRY(hipMemcpyAsync(disparity, s.disp, (size_t)k * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (status) HIP_TRY(hipMemcpyAsync(status, s.status, (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (depth_mm) st.download(depth_mm, s.mm, (int64_t)k * 2);
+        if (disparity) st.download(disparity, s.disp, (int64_t)k * 4);
+        if (status) st.download(status, s.status, k);
     }
+    if (int rc = st.finish()) return rc;
     *n = k;
     return RELOC_OK;
 }
@@ -622,27 +641,9 @@ int stereo_dense_frame(reloc_ctx *ctx, reloc_ctx *right, int w, int h, int order
     StereoState &s = ctx->stereo;
     if (int rc = stereo_pair_check(ctx, right, w, h, ww, wh)) return rc;
     if (int rc = stereo_dense_alloc(ctx)) return rc;
-    // the right eye's chain on its own stream, behind what ctx's stream holds so far (stereo_frame); the left eye's on ctx's
-    HIP_TRY(hipEventRecord(s.left_ready, ctx->stream));
-    HIP_TRY(hipStreamWaitEvent(right->stream, s.left_ready, 0));
     const uint8_t *plane[2];
     int pstride[2];
-    for (int e = 0; e < 2; ++e) {
-        reloc_ctx *c = e ? right : ctx;
-        const uint8_t *src = c->frame_img, *planes[RELOC_BATCH_MAX];
-        const uint8_t *const *srcs = &src;
-        int stride = w * image_chain_frame_bpp(c), channels = 1;
-        if (int rc = image_chain_gray(&c, 1, true, &srcs, w, h, *ww, *wh, &stride, &channels, gray_flags(c, order), planes)) return rc;
-        plane[e] = srcs[0];
-        if (channels == 3) {       // no stage ran on a 3-channel frame
-            uint8_t *dst = e ? s.plane : s.dense.left;
-            if (int rc = image_gray_plain(c, plane[e], *ww, *wh, stride, order, dst)) return rc;
-            plane[e] = dst; stride = *ww;
-        }
-        pstride[e] = stride;
-    }
-    HIP_TRY(hipEventRecord(s.right_done, right->stream));
-    HIP_TRY(hipStreamWaitEvent(ctx->stream, s.right_done, 0));
+    if (int rc = stereo_gray_planes(ctx, right, ctx->frame_img, right->frame_img, w, h, *ww, *wh, order, plane, pstride)) return rc;
     const StereoParams p = {ctx->cam.K4[0], s.baseline, *ww, *wh, s.min_disp, s.num_disp, s.uniq, s.lr};
     return stereo_dense_launch(ctx, plane[0], pstride[0], plane[1], pstride[1], p);
 }
@@ -651,23 +652,13 @@ RELOC_API int reloc_stereo_frame_depth(reloc_ctx *ctx, reloc_ctx *right, const u
                                        int order, uint16_t *depth_mm, int32_t *out_w, int32_t *out_h)
 {
     ARG_CHECK_CTX(ctx, right && img && img_right && w >= 64 && h >= 64, "reloc_stereo_frame_depth");
-    if (!ctx->stereo.on()) { reloc_set_error("stereo is off on this context (reloc_set_stereo)"); return RELOC_E_STATE; }
-    if (right == ctx) { reloc_set_error("bad argument: the right eye needs a context of its own"); return RELOC_E_ARG; }
-    if (w > ctx->max_w || h > ctx->max_h || w > right->max_w || h > right->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
-    HostStaging st{ctx};
-    st.upload(ctx->frame_img, img, (int64_t)w * h * image_chain_frame_bpp(ctx));
-    bool right_busy = false;       // the right context's stream holds a copy from the caller's memory
+    if (int rc = stereo_pair_entry(ctx, right, w, h)) return rc;
+    StereoPairStaging st(ctx, right);
+    st.upload_pair(img, img_right, w, h);
     int ww = 0, wh = 0;
-    st.run([&] {
-        right_busy = true;
-        HIP_TRY(hipMemcpyAsync(right->frame_img, img_right, (size_t)w * h * image_chain_frame_bpp(right), hipMemcpyHostToDevice, right->stream));
-        return stereo_dense_frame(ctx, right, w, h, order, &ww, &wh);
-    });
+    st.run([&] { return stereo_dense_frame(ctx, right, w, h, order, &ww, &wh); });
     if (depth_mm) st.download(depth_mm, ctx->stereo.dense.mm, (int64_t)ww * wh * 2);
-    const int rc = st.finish();
-    // after an error the two streams may not be ordered: nothing of the caller's right frame stays in flight
-    if (right_busy) (void)hipStreamSynchronize(right->stream);
-    if (rc) return rc;
+    if (int rc = st.finish()) return rc;
     if (out_w) *out_w = ww;
     if (out_h) *out_h = wh;
     return RELOC_OK;
@@ -678,11 +669,12 @@ RELOC_API int reloc_stereo_dense_debug(reloc_ctx *ctx, uint16_t *depth_mm, float
     ARG_CHECK_CTX(ctx, true, "reloc_stereo_dense_debug");
     const StereoState::Dense &d = ctx->stereo.dense;
     if (!d.block || d.w == 0) { reloc_set_error("no dense stereo pass on this context yet"); return RELOC_E_STATE; }
-    const size_t px = (size_t)d.w * d.h;
-    if (depth_mm) HIP_TRY(hipMemcpyAsync(depth_mm, d.mm, px * 2, hipMemcpyDeviceToHost, ctx->stream));
-    if (disparity) HIP_TRY(hipMemcpyAsync(disparity, d.disp, px * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (status) HIP_TRY(hipMemcpyAsync(status, d.status, px, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const int64_t px = (int64_t)d.w * d.h;
+    HostStaging st{ctx};
+    if (depth_mm) st.download(depth_mm, d.mm, px * 2);
+    if (disparity) st.download(disparity, d.disp, px * 4);
+    if (status) st.download(status, d.status, px);
+    if (int rc = st.finish()) return rc;
     if (w) *w = d.w;
     if (h) *h = d.h;
     return RELOC_OK;

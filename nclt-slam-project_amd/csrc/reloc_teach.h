@@ -1,0 +1,90 @@
+// reloc_teach.h -- what the teach-side files (reloc_record.hip, reloc_stereo.hip, reloc_occupancy.hip) share and no other file
+// includes: the ordered compaction of a 1024-thread workgroup, the depth pixel of the obstacle cloud and of the occupancy map,
+// and the staging of a stereo pair that comes from the caller's memory.
+#pragma once
+#include "reloc_internal.h"
+
+// Ordered compaction, one chunk of a workgroup of 1024 threads (16 waves): the rank of this lane among the chunk's lanes with
+// `keep`, in thread order, counted from `base`; total: the chunk's kept lanes, the same in every thread, so the caller keeps its
+// running base in a register (base += total) and no thread has to publish it.  s_wsum: 16 ints of LDS, the helper's alone.
+// Reuse of s_wsum between chunks: a fast wave must not write its next count while a slow one still sums this chunk's, which
+// is what the first barrier is for; the second stands between the 16 writes and the sums.  Every thread of the workgroup calls.
+__device__ __forceinline__ int block_rank(bool keep, int *s_wsum, int base, int &total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long bal = __ballot(keep);
+    __syncthreads();
+    if (lane == 0) s_wsum[wave] = __popcll(bal);
+    __syncthreads();
+    total = 0;
+    for (int w = 0; w < 16; ++w) {
+        const int c = s_wsum[w];
+        if (w < wave) base += c;
+        total += c;
+    }
+    return base + __popcll(bal & ((1ull << lane) - 1ull));
+}
+
+// A depth plane on the device and the pixels a cloud takes of it: every step-th of w x h, rows `stride` pixels apart, float32
+// metres or uint16 millimetres (tf_wall_clock_relay_v55.py:1020-1038).
+struct DepthGrid {
+    const void *data;
+    int is_f32, w, h, stride, step;
+    float cx, cy, fx, fy, zmin, zmax;
+    __host__ __device__ int cols() const { return (w + step - 1) / step; }
+    __host__ __device__ int rows() const { return (h + step - 1) / step; }
+};
+static inline DepthGrid depth_grid(const void *data, int is_f32, int w, int h, int stride, int step, const double K4[4], float zmin,
+                                   float zmax)
+{
+    return DepthGrid{data, is_f32, w, h, stride, step, (float)K4[2], (float)K4[3], (float)K4[0], (float)K4[1], zmin, zmax};
+}
+
+// Pixel i of the grid in raster order: p = (z, -(u - cx) / fx * z, -(v - cy) / fy * z) in float32, true iff zmin < z < zmax and
+// z is finite.  f32 is the caller's to pass so that a kernel templated on the format folds the branch.
+__device__ __forceinline__ bool depth_grid_point(const DepthGrid &g, bool f32, int i, float p[3])
+{
+    const int gw = g.cols(), v = (i / gw) * g.step, u = (i % gw) * g.step;
+    const size_t at = (size_t)v * g.stride + u;
+    const float z = f32 ? reinterpret_cast<const float *>(g.data)[at]
+                        : __fdiv_rn((float)reinterpret_cast<const uint16_t *>(g.data)[at], 1000.0f);
+    p[0] = z;
+    p[1] = -__fmul_rn(__fdiv_rn(__fsub_rn((float)u, g.cx), g.fx), z);
+    p[2] = -__fmul_rn(__fdiv_rn(__fsub_rn((float)v, g.cy), g.fy), z);
+    return z > g.zmin && z < g.zmax && isfinite(z);
+}
+
+// What an entry point checks of a stereo pair before it enqueues anything.
+static inline int stereo_pair_entry(const reloc_ctx *ctx, const reloc_ctx *right, int w, int h)
+{
+    if (!ctx->stereo.on()) { reloc_set_error("stereo is off on this context (reloc_set_stereo)"); return RELOC_E_STATE; }
+    if (right == ctx) { reloc_set_error("bad argument: the right eye needs a context of its own"); return RELOC_E_ARG; }
+    if (w > ctx->max_w || h > ctx->max_h || w > right->max_w || h > right->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
+    return RELOC_OK;
+}
+
+// HostStaging for a stereo pair in the caller's memory: the left frame goes to ctx->frame_img on ctx's stream, the right one to
+// right->frame_img on right's stream, where its chain runs (stereo_frame, stereo_dense_frame).  After an error the two streams
+// may not be ordered, so finish() waits for the right stream as well whenever that copy was enqueued: nothing of the caller's
+// right frame stays in flight.
+struct StereoPairStaging : HostStaging {
+    reloc_ctx *right;
+    bool right_busy = false;
+    StereoPairStaging(reloc_ctx *c, reloc_ctx *r) : HostStaging{c}, right(r) {}
+    void upload_pair(const uint8_t *img, const uint8_t *img_right, int w, int h)
+    {
+        upload(ctx->frame_img, img, (int64_t)w * h * image_chain_frame_bpp(ctx));
+        run([&] {
+            right_busy = true;
+            HIP_TRY(hipMemcpyAsync(right->frame_img, img_right, (size_t)w * h * image_chain_frame_bpp(right), hipMemcpyHostToDevice, right->stream));
+            return (int)RELOC_OK;
+        });
+    }
+    int finish()
+    {
+        const int r = HostStaging::finish();
+        if (right_busy) (void)hipStreamSynchronize(right->stream);
+        right_busy = false;
+        return r;
+    }
+};

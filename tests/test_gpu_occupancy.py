@@ -222,6 +222,36 @@ def test_depth_images(engine, w, h, step, dtype):
     assert np.count_nonzero(p.check()["units"]) > 50
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.uint16], ids=["f32", "u16"])
+@pytest.mark.parametrize("fill", ["all", "none", "third"])
+@pytest.mark.parametrize("w", [1, 63, 64, 65, 1023, 1024, 1025, 2049])
+def test_compaction_at_its_chunk_edges(engine, w, fill, dtype):
+    """one row of w pixels at step 1 around the wave (64) and chunk (1024) sizes of the ordered compaction that k_depth_points
+    and k_occ_integrate share: every pixel valid, none, and every third one zero; the cloud bit for bit, the rays and the grid"""
+    rng = np.random.default_rng(w)
+    d = rng.uniform(0.5, 3.0, (1, w)).astype(np.float32)           # a fan of 90 degrees, 0.5 to 3 m, all of it inside the grid
+    if fill == "none":
+        d[:] = 0.0
+    if fill == "third":
+        d[0, 2::3] = 0.0
+    if dtype == np.uint16:
+        d = (d * 1000).astype(np.uint16)
+    K4 = (max(w, 2) / 2.0, 20.0, w / 2.0, 0.0)
+    T = pose(0.013, -0.021, 0.6, 33.0)
+    cloud = RR.depth_points(d, 1, K4, 0.3, 10.0)
+    assert len(cloud) == dict(all=w, none=0, third=w - w // 3)[fill]
+    got = engine.depth_points(d, 1, K4)
+    assert got.shape == cloud.shape and np.array_equal(got.view(np.uint32), cloud.view(np.uint32))
+    for sub in (1, 3):
+        p = Pair(engine, (-4.8, -4.8, 0.1, 96, 96), subsample=sub)
+        exp = p.ref.integrate_depth(d, K4, T, 1, 0.3, 10.0)
+        if fill != "none":                                         # no case passes empty
+            assert exp == -(-len(cloud) // sub) and p.ref.last_hits.sum() == exp
+        assert engine.occ_integrate_depth(d, T, 1, K4, 0.3, 10.0) == exp
+        r = p.check()
+        assert (fill == "none") == (r["frames_skipped_empty"] == 1) and (fill == "none") != bool(r["units"].any())
+
+
 @pytest.mark.parametrize("case", ["across", "beyond", "corner00", "cornerHW", "edge"])
 def test_depth_against_the_on_chip_window(engine, case):
     """rays that leave the window, a frame whose every end lies beyond it, and the start cell at a corner and an edge of the
@@ -344,8 +374,14 @@ def test_state_and_errors():
         r = q.check()
         assert not r["units"].any() and (r["pgm"] == 205).all() and r["frames_integrated"] == 0
         q.points(pts, T)
-        q.check()
-        s = Pair(e, GRID_B, subsample=2)                       # and another size takes a new block
+        before = q.check()
+        with pytest.raises(RelocError, match=r"code -1.*finite"):   # the reader after a refused call: the same arrays
+            e.occ_integrate_depth(d, T * np.nan, 1, K_SMALL)
+        with pytest.raises(RelocError, match=r"code -5.*no dense stereo pass"):
+            e.occ_integrate_stereo(T)
+        after = q.check()
+        assert all(np.array_equal(before[k], after[k]) for k in before)
+        s = Pair(e, GRID_B, subsample=2)                      # and another size takes a new block
         s.points(pts, T_at(*centre(GRID_B, 40, 5)))
         assert s.check()["units"].shape == (91, 37)
 

@@ -225,6 +225,20 @@ def test_record_frame_stereo(variant):
         assert r2["n"] != r["n"] or not np.array_equal(r2["desc"], r["desc"])
 
 
+def test_record_frame_stereo_refusals():
+    """an engine as its own right eye and a pair beyond the right engine's capacity are refused at the entry, with the codes
+    and texts of the other pair entry points; the next correct call on the same engines equals its reference"""
+    L, R = _pair(0)
+    with engines(2, RW, RH) as rig, engines(1, 128, 128) as small:
+        es = rig.es
+        es[0].set_stereo(**RIG)
+        for right, text in ((es[0], r"code -1.*a context of its own"), (small.es[0], r"code -4.*exceeds ctx capacity")):
+            with pytest.raises(RelocError, match=text):
+                es[0].record_frame_stereo(_bgr(L), _bgr(R), right, NF)
+            r = _record_vs_reference(es, _bgr(L), _bgr(R), L, R)[0]
+            assert r["n"] >= 30
+
+
 def test_stereo_argument_errors(engine):
     for kw, text in ((dict(baseline_m=-1.0), "baseline_m"), (dict(min_disparity=1025), r"min_disparity 1025 outside 0\.\.1024"),
                      (dict(num_disparities=7), r"num_disparities 7 outside 8\.\.256"), (dict(num_disparities=257), "num_disparities"),

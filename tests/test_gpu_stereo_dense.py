@@ -257,6 +257,12 @@ def test_dense_state_and_errors():
         es[0].set_stereo(**rig2)
         third = _frame_vs_reference(es, _bgr(L), _bgr(R), L, R, rig2)
         assert (third[2] != first[2]).any() and not (third[2] == SR.LR).any()
+        # the reader after refused calls on the same engine: the planes of the last pass, as before
+        with pytest.raises(RelocError, match="a context of its own"):
+            es[0].stereo_frame_depth(_bgr(L), _bgr(R), es[0])
+        with pytest.raises(RelocError, match="no dense stereo pass on this context yet"):
+            es[1].stereo_dense_debug()
+        _same(es[0].stereo_dense_debug(), third)
 
 
 def test_dense_pass_leaves_sparse_records_and_ticks_alone():
