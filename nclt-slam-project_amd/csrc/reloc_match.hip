@@ -220,16 +220,28 @@ __device__ __forceinline__ void static_for(F &&f) { static_for_impl(f, std::make
 //   q[j]    : descriptor of column colbase + j*64 + lane (padding columns repeat the last real column:
 //             a duplicate offers the same distance with a larger index, so it never wins a minimum)
 //   nr < 16 : the tail chunk of a wave's row range: the rows it does not have are skipped (wave-uniform branch) and enter the
-//             butterfly as "infinity"; their fetch addresses are clamped to the record's last row
+//             butterfly as don't-cares, which only the unwritten lanes of those rows receive; their fetch addresses are
+//             clamped to the record's last row
 // One 16-bit key per pair serves both directions: distance << 7 | row-in-chunk << 3 | column slot.
 // Among the rows of one column the slot bits are equal, so the minimum is (distance, row); among the
 // columns of one row the row bits are equal, so the minimum is (distance, slot).  Per pair that is
 // one v_fmaak_f32 (key_fma) + 2 v_min_u16 on top of the 16 instructions of the distance (through round 4: v_lshlrev_b16 +
 // v_or_b32 for the key; the row's 8-way minimum with v_min3_f32 was measured and dropped, profiles/README.md
 // "Dropped experiments" #9).
-template <int NJ>
+// The column minima leave the chunk in one of two forms (MERGE, a compile-time property of the CALLER):
+//   MERGE_SHARED : converted to distance << 16 | (tc + row) (col_key) and merged with ds_min_u32 into the buffer all waves of
+//                  the workgroup share -- the emit pass, and every record of the counting scan whose waves walk more than
+//                  one chunk or column block;
+//   MERGE_CHOICE : the counting scan.  n <= sliced_max (wave-uniform, per record) selects between the shared form and plain 16-bit
+//                  stores of the raw minima into the calling wave's own slice (slice[j * 64 + lane]), which db_count_body
+//                  resolves.  The choice is a scalar branch BEHIND the unrolled rows, never inside them, and not a second
+//                  instantiation: the 16-row body is 45 KB of code and two of them in one kernel would not share the 64 KB
+//                  instruction cache on a ragged database, where neighbouring workgroups take both paths.
+enum ScanMerge { MERGE_SHARED, MERGE_CHOICE };
+template <int NJ, ScanMerge MERGE = MERGE_SHARED>
 __device__ __forceinline__ void scan_chunk(const uint4 *__restrict__ rec, int n, int tc, int nr, const u32 (&q)[NJ][8],
-                                           u32 colbase, u32 *rowkey, u32 *colbest, bool single_cb, int lane)
+                                           u32 colbase, u32 *rowkey, u32 *colbest, bool single_cb, int lane,
+                                           unsigned short *slice = nullptr, int sliced_max = -1)
 {
     // (column minima in LDS instead of registers: measured and dropped, profiles/README.md "Dropped experiments" #1)
     u32 cb16[NJ];                                                      // seeded by row 0, which every chunk has (nr >= 1)
@@ -254,10 +266,13 @@ __device__ __forceinline__ void scan_chunk(const uint4 *__restrict__ rec, int n,
         uint4 na, nb;
         if (i + 1 < R) { na = rec[2 * row_of(i + 1)]; nb = rec[2 * row_of(i + 1) + 1]; }   // ... the next one on its way
         __builtin_amdgcn_sched_barrier(0);
-        // A row the chunk does not have loses every minimum.  The compiler sets this default in front of the row's branch, one
-        // v_mov on the way of every row that IS there; pinned to the far side of the branch instead (asm volatile in an else),
-        // the 15 instructions go and the 4-stream run LOSES 1 % (profiles/README.md "Dropped experiments" #10).
-        u32 v = 0xFFFFFFFFu;
+        // A row the chunk does not have needs no key at all: the butterfly transposes, a lane's result is the minimum over lanes
+        // of ITS row only, and the lanes of a missing row are not written below (row_in_chunk < nr).  So v is left undefined on
+        // the skipped side -- an empty asm output, no instruction and no block.  (An `= 0xFFFFFFFF` default is set by the compiler
+        // in front of the row's branch, one v_mov on the way of every row that IS there; pinned to the far side of the branch
+        // it costs fifteen out-of-line blocks and 1 %: profiles/README.md "Dropped experiments" #10.)
+        u32 v;
+        asm("" : "=v"(v));
         if (t == 0 || t < nr) {                                          // wave-uniform
             u32 best = 0;
             const u32 w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
@@ -302,6 +317,14 @@ __device__ __forceinline__ void scan_chunk(const uint4 *__restrict__ rec, int n,
     if (writer && row_in_chunk < nr) {
         if (single_cb) rowkey[row] = row_key(m, 0);                  // one column block: colbase == 0
         else atomicMin(&rowkey[row], row_key(m, colbase));
+    }
+    if constexpr (MERGE == MERGE_CHOICE) {
+        if (n <= sliced_max) {                                           // wave-uniform, one scalar compare
+            // eight ds_write_b16, no VALU: lanes l and l + 1 share a dword, a 2-way store conflict costs no LDS cycle
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) slice[j * 64 + lane] = (unsigned short)cb16[j];
+            return;
+        }
     }
     // all the column keys, then all the minima: a key's partial write is NJ instructions old before LDS reads the register
     u32 ck[NJ];
@@ -433,12 +456,14 @@ __device__ __forceinline__ void db_emit_body(
 }
 
 // The counting scan (no match lists) of the whole database.  grid: any; block: 256 (4 waves).  Dynamic LDS:
-// (col_words + max_rows + 16) * 4 bytes.  mask.xyh != NULL: heading-incompatible records are not scored (count 0), see ScanMask.
+// (col_words + max_rows + 16) * 4 + 4 * 64 * NJ * 2 bytes (CountPlan).  mask.xyh != NULL: heading-incompatible records are not scored (count 0), see ScanMask.
 // The per-record flow of db_emit_body reduced to TWO barriers per record:
 //   - colbest is double-buffered: the buffer of the NEXT record is cleared while this record's chunks run, so no
 //     clear / barrier pair stands in front of a record;
 //   - with one column block (<= 64 * NJ current descriptors: every fused tick) each row key is written by exactly one
 //     wave with a plain store and never needs clearing;
+//   - with one column block and records of at most 64 rows (one chunk per wave) the column minima take the same road: raw
+//     16-bit keys in a slice per wave, plain stores, resolved for the one column a row points at (`sliced` below);
 //   - the mutual pairs are only counted: per wave one ballot and one LDS add, no prefix sums;
 //   - the next record's ticket (drawn a record ahead) is settled between the same two barriers.
 // A workgroup's FIRST record is dealt statically (record = workgroup index, no counter round trip in front of the first
@@ -481,6 +506,14 @@ __device__ __forceinline__ void db_count_body(
     u32 *colbuf = lds;
     u32 *rowkey = colbuf + col_words;         // max_rows     : best (distance << 16 | column) per row
     u32 *wsum = rowkey + max_rows;            // [0], [1]: mutual-pair counters of the two buffers; [8]: next record
+    // Per-wave slices of raw column minima (NW x CB 16-bit keys, distance << 7 | row in chunk << 3 | slot), an LDS region of
+    // their own, for the records in which no wave walks more than one chunk of one column block (`sliced` below): one column
+    // block (every fused tick) and at most 16 rows per wave, i.e. records of up to 64 rows.  A wave then stores its minima
+    // with plain stores (scan_chunk, MERGE_CHOICE) and the resolving wave rebuilds distance << 16 | absolute row for the ONE
+    // column each row points at -- where the shared form converts all CB columns in every wave, merges them with ds_min_u32
+    // and clears a buffer per record.  No atomics, no second buffer, no clear: a wave with rows overwrites its whole slice
+    // in every such record, and the slice of a wave without rows is not read.
+    unsigned short *slices = (unsigned short *)(wsum + 16);
 
     u32 q[NJ][8];
     auto load_q = [&](int colbase) {
@@ -541,6 +574,7 @@ __device__ __forceinline__ void db_count_body(
     if (tid == 0) wsum[0] = wsum[1] = 0;
     __syncthreads();
     int p = 0;
+    const int sliced_max = ncb == 1 ? 16 * NW : -1;                          // most rows of a record that takes the slices
     while (it < n_ids) {
         u32 *colbest = colbuf + (dbl ? p * buf_words : 0);
         const int r = rec_ids ? rec_ids[it] : it;
@@ -552,6 +586,22 @@ __device__ __forceinline__ void db_count_body(
         left -= max(n_rec, 1);
         u32 next_ticket = 0;
         if (ticket && dealer && left > 0) next_ticket = draw();          // no draw that this workgroup would not serve
+        // Workgroup-uniform, per record: the column minima go through the per-wave slices (one column block, so the NW waves
+        // share the rows and chunk_step == NW; at most one chunk per wave).  Ragged databases mix both forms record by record.
+        // The shared buffer's invariant -- the buffer a record merges into (p when double-buffered, else the only one) holds
+        // 0xFFFFFFFF in all its ncb * CB words when the record starts -- holds whichever form the record before took:
+        //   - it holds for the first record (cleared in front of the loop);
+        //   - a record in the shared form dirties buffer p only and leaves the next record's buffer clear, as before: p ^ 1,
+        //     cleared beside its chunks and made current behind it, or the one buffer, cleared behind it;
+        //   - a sliced record neither reads nor writes the shared buffers and leaves p alone, so the buffer that was clear
+        //     when it started is the next record's buffer and still clear.  It therefore needs neither the clear nor the flip.
+        // (One column block always fits twice: col_words >= 2 * CB.  The single-buffer regime has no sliced records at all.)
+        // The counter wsum[p] of a sliced record is the one the record before may have used: thread 0 zeroes it behind that
+        // record's last barrier, and the first add of this record comes behind this record's first barrier.
+        // Tested where it is needed as ONE scalar compare of n against sliced_max (16 * NW with one column block, else -1; set
+        // in front of the loop), each time on a copy of n the compiler cannot see through: kept as one flag across the
+        // chunk it becomes a 64-bit lane mask that is spilled to and read back from VGPR lanes in every wave and record.
+        auto sliced = [&]() { int nn = n; asm volatile("" : "+s"(nn)); return nn <= sliced_max; };
         if (n > 0) {
             if (ncb > 1) {                                               // several waves write one row's key: atomic minima
                 for (int i = tid; i < n; i += 64 * NW) rowkey[i] = 0xFFFFFFFFu;
@@ -565,17 +615,46 @@ __device__ __forceinline__ void db_count_body(
                 const int tend = tc + per + (wb.chunk0 < extra ? 1 : 0);
 #pragma nounroll
                 for (; tc < tend; tc += 16)
-                    scan_chunk<NJ>(rec, n, tc, min(16, tend - tc), q, (u32)(cb * CB), rowkey, colbest, ncb == 1, lane);
+                    scan_chunk<NJ, MERGE_CHOICE>(rec, n, tc, min(16, tend - tc), q, (u32)(cb * CB), rowkey, colbest, ncb == 1, lane,
+                                                 slices + wave * CB, sliced_max);
             }
         }
-        if (dbl) {   // the other buffer, for the next record: two words a lane, 128 a wave and step (512 words: one store each)
-            u32 *other = colbuf + (p ^ 1) * buf_words;
-            for (int base = 0; base + 128 * wave < buf_words; base += 128 * NW) {  // wave-uniform
-                other[base + 2 * tid] = 0xFFFFFFFFu;
-                other[base + 2 * tid + 1] = 0xFFFFFFFFu;
+        if (!sliced()) {
+            asm volatile("");   // keeps the two tests apart: merged, every sliced record reads dbl's spilled lane mask back
+            if (dbl) {   // the other buffer, for the next record: two words a lane, 128 a wave and step (512 words: one store each)
+                u32 *other = colbuf + (p ^ 1) * buf_words;
+                for (int base = 0; base + 128 * wave < buf_words; base += 128 * NW) {  // wave-uniform
+                    other[base + 2 * tid] = 0xFFFFFFFFu;
+                    other[base + 2 * tid + 1] = 0xFFFFFFFFu;
+                }
             }
         }
         __syncthreads();                                                  // every minimum of this record is in LDS
+        if (sliced()) {
+            // At most 64 rows: wave 0 resolves them all (64 * wave < n, the shared form's own wave-uniform test).  Row `tid`
+            // points at column col; of that column every wave that had rows (wave w has some iff w < n: the deal gives
+            // n / NW rows and the first n % NW waves one more) left its best (distance, row in chunk).
+            // distance << 16 | (tc_w + row in chunk), tc_w from that deal, is the key the wave would have merged with
+            // ds_min_u32, and the minimum over the waves is what the shared buffer would hold: the smallest distance, on
+            // ties the lowest absolute row.
+            if (64 * wave < n) {
+                asm volatile("");   // a scalar branch for the waves without rows, not folded into the lane test below
+                if (tid < n) {
+                    const u32 col = rowkey[tid] & 0xFFFFu;
+                    const int per = n / NW, extra = n % NW;
+                    u32 best = 0xFFFFFFFFu;
+#pragma unroll
+                    for (int w = 0; w < NW; ++w)
+                        if (w < n) {                                      // wave-uniform
+                            const u32 k = slices[w * CB + col];
+                            const u32 tc_w = (u32)(w * per + min(w, extra));
+                            best = umin(best, ((k << 9) & 0xFFFF0000u) | (tc_w + ((k >> 3) & 15u)));
+                        }
+                    const unsigned long long mutual = __builtin_amdgcn_ballot_w64((best & 0xFFFFu) == (u32)tid);
+                    if (lane == 0 && mutual) atomicAdd(&wsum[p], (u32)__popcll(mutual));
+                }
+            }
+        } else
         for (int rb = 0; rb + 64 * wave < n; rb += 64 * NW) {             // wave-uniform: a wave without rows goes on to the barrier
             const int row = rb + tid;
             if (row < n) {                                                // the wave's first lane always is
@@ -591,6 +670,7 @@ __device__ __forceinline__ void db_count_body(
             wsum[p] = 0;
         }
         it = __builtin_amdgcn_readfirstlane((int)wsum[8]);
+        if (sliced()) continue;                                           // shared buffers untouched: nothing to flip or clear
         if (dbl) p ^= 1;
         else {       // one buffer: cleared between the records
             for (int i = tid; i < ncb * CB; i += 64 * NW) colbuf[i] = 0xFFFFFFFFu;
@@ -668,10 +748,11 @@ __global__ __launch_bounds__(256, 4) RELOC_SCAN_VGPR_ATTR void k_db_scan_emit_ba
                        g_pts3d, F.g_xy, F.g_obj, F.g_img);
 }
 
-// Dynamic LDS of a scan workgroup: col_words words of column minima, a row key per teach row, 16 words of counters
-static int scan_lds_bytes(const char *who, int col_words, int max_rows, size_t &lds)
+// Dynamic LDS of a scan workgroup: col_words words of column minima, a row key per teach row, 16 words of counters and, for
+// the counting scan, slice_keys 16-bit keys of per-wave column minima behind them (db_count_body)
+static int scan_lds_bytes(const char *who, int col_words, int max_rows, size_t &lds, int slice_keys = 0)
 {
-    lds = (size_t)(col_words + max_rows + 16) * 4;
+    lds = (size_t)(col_words + max_rows + 16) * 4 + (size_t)slice_keys * 2;
     if (lds > 160 * 1024) { reloc_set_error("%s: LDS demand %zu bytes", who, lds); return RELOC_E_CAPACITY; }
     return RELOC_OK;
 }
@@ -1235,7 +1316,9 @@ struct CountPlan {
     {
         const int cb = 64 * nj, ncb = (n_cur_max + cb - 1) / cb;
         col_words = (ncb >= 2 ? ncb : 2) * cb;
-        if (int rc = scan_lds_bytes(who, col_words, max_rows, lds)) return rc;
+        // + the four waves' slices of one column block, 4 KB at nj = 8: with the 32 KB of a context made for 8192 features
+        // four workgroups still fit a CU's 160 KB up to records of 1008 rows
+        if (int rc = scan_lds_bytes(who, col_words, max_rows, lds, 4 * cb)) return rc;
         const int wg_per_cu = (int)(160 * 1024 / lds);
         resident = ctx->num_cu * (wg_per_cu < 4 ? wg_per_cu : 4);
         return RELOC_OK;

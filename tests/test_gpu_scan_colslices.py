@@ -1,0 +1,430 @@
+"""GPU parity of the counting scan's two column-merge forms (db_count_body / scan_chunk of csrc/reloc_match.hip): records of at
+most 64 rows against one column block leave their column minima as raw 16-bit keys in a slice per wave and wave 0 resolves
+them ("sliced"); every other record merges into the shared buffer with ds_min_u32, double-buffered or cleared ("shared").
+Both forms live in one launch and a workgroup changes between them record by record.
+
+Expected counts: oracle.db_match_counts, 0 where tests/scan_ref.py's heading mask says so; all comparisons integer-exact.
+Counts are read from arrays poisoned before every call: the caller's for reloc_db_match_counts_dev, the context's own
+(reloc_db_counts_dev) for the tick's entry points.
+
+Databases.  `sizes`: the record sizes of SIZES, twice, fewer records than workgroups (static deal).  `ragged`: 12 records per
+CU, so a workgroup serves several by ticket; sizes follow the period-five pattern shared, sliced, shared, shared, sliced (a
+ticket counter deals every eighth record, so a workgroup walks the pattern 0 3 1 4 2: every transition between the forms),
+forty records hold noisy copies of a real frame's descriptors.  `ties`: low-entropy rows (every 32-bit word all zeros or all ones,
+so a distance is a multiple of 32) against low-entropy queries; test_tie_data_pins_the_rule shows on the CPU that these records
+have columns whose best distance is reached in several waves' row ranges, and that resolving such ties to the HIGHER row
+changes the count."""
+import numpy as np
+import pytest
+
+import chain_harness as CH
+import scan_ref as SR
+from nclt_slam_project_amd import pose as P
+from nclt_slam_project_amd import synth
+from nclt_slam_project_amd.engine import Engine
+
+gpu = pytest.mark.gpu
+
+W, H = 640, 480
+NFEAT, MAX_FEAT = 500, 2048                 # one column block through the ORB stage
+POISON = -7
+SLICED_SIZES = (1, 2, 3, 4, 5, 15, 16, 17, 31, 48, 63, 64)
+SHARED_SIZES = (65, 80, 130)
+SIZES = SLICED_SIZES + SHARED_SIZES
+FEATS = (0, 1, 63, 64, 65, 448, 500, 512)   # one column block of the 8-column kernel
+FEATS_SHARED = (513, 1100)                  # two / three blocks: the shared form whatever the record (1100 in a context of 2048: one buffer)
+PATTERN = ("shared", "sliced", "shared", "shared", "sliced")
+N_PLANTED = 40
+TIE_SIZES = (64, 64, 48, 33, 17, 5, 64, 130, 64, 80)
+YAWS = (0.0, 90.0, 180.0, 270.0)
+WINDOWS = (None, (36, 36), (96, 72), None)  # image 0: flat (no feature), 1 and 2: a textured window, 3: the whole texture
+
+
+def wave_ranges(n, nw=4):
+    """the contiguous row ranges db_count_body deals to the nw waves that share a column block"""
+    per, extra = divmod(n, nw)
+    lo = [w * per + min(w, extra) for w in range(nw)]
+    return [(lo[w], lo[w] + per + (1 if w < extra else 0)) for w in range(nw)]
+
+
+def distances(rec, cur):
+    a = np.unpackbits(rec, axis=1).astype(np.int32)
+    b = np.unpackbits(cur, axis=1).astype(np.int32)
+    return a @ (1 - b).T + (1 - a) @ b.T
+
+
+def mutual_count(D, high_row_on_ties=False):
+    """mutual nearest neighbours of a distance matrix (rows x columns), lowest column on ties; lowest row, or the mutant's"""
+    n = D.shape[0]
+    col_of_row = D.argmin(axis=1)
+    row_of_col = (n - 1 - D[::-1].argmin(axis=0)) if high_row_on_ties else D.argmin(axis=0)
+    return int((row_of_col[col_of_row] == np.arange(n)).sum())
+
+
+def low_entropy(rng, n):
+    """descriptors of eight 32-bit words, each all zeros or all ones: 256 values, distances multiples of 32"""
+    return np.repeat(np.where(rng.integers(0, 2, (n, 8)) == 1, 0xFF, 0).astype(np.uint8), 4, axis=1)
+
+
+def poses_of(L):
+    yaw = 7.0 + 13.0 * (np.arange(L) % 27)
+    return np.array([P.base_to_cam_world(*synth.base_pose(1000.0 + 40.0 * r, 0.0, yaw[r])) for r in range(L)])
+
+
+def make_db(name, rng, rows, desc):
+    rows = np.asarray(rows, np.int64)
+    off = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+    assert len(desc) == off[-1]
+    pts = rng.uniform(-2, 2, (int(off[-1]), 3)).astype(np.float32) + np.float32([0, 0, 6])
+    return dict(name=name, desc=desc, pts=pts, off=off, poses=poses_of(len(rows)), rows=rows, L=len(rows))
+
+
+def sizes_db(cur):
+    rng = np.random.default_rng(8101)
+    rows = list(SIZES) * 2
+    desc = np.concatenate([synth.perturb_descriptors(rng, cur[rng.choice(448, n, replace=False)]) for n in rows])
+    return make_db("sizes", rng, rows, desc)
+
+
+def planted_records(L):
+    """forty records spread over the database, their indices walking all residues of the period-five pattern"""
+    stride = L // (N_PLANTED + 2)
+    stride += (3 - stride) % 5
+    return 11 + stride * np.arange(N_PLANTED)
+
+
+def ragged_db(L, cur, rich):
+    rng = np.random.default_rng(8102)
+    rows = np.where(np.array([PATTERN[r % 5] == "sliced" for r in range(L)]), rng.integers(0, 21, L), rng.integers(65, 81, L))
+    edge = rng.choice(L, 60, replace=False)
+    for r, n in zip(edge, (63, 64, 16, 17, 48, 1) * 10):                   # the sliced form's edges among the ticket-dealt records
+        if PATTERN[r % 5] == "sliced":
+            rows[r] = n
+    planted = planted_records(L)
+    rows[planted] = np.where(np.array([PATTERN[r % 5] == "sliced" for r in planted]), rng.integers(32, 65, N_PLANTED),
+                             rng.integers(65, 131, N_PLANTED))
+    off = np.concatenate([[0], np.cumsum(rows)])
+    desc = synth.perturb_descriptors(rng, cur[rng.choice(500, int(off[-1]))], flip_p=0.2)
+    for r in planted:
+        desc[off[r]:off[r + 1]] = synth.perturb_descriptors(rng, rich[rng.choice(len(rich), int(rows[r]), replace=False)])
+    return make_db("ragged", rng, rows, desc)
+
+
+def ties_db():
+    rng = np.random.default_rng(8103)
+    return make_db("ties", rng, TIE_SIZES, low_entropy(rng, sum(TIE_SIZES)))
+
+
+def images():
+    tex = synth.textured_frame(np.random.default_rng(8110), W, H, n_shapes=1200)
+    out = []
+    for win in WINDOWS:
+        img = np.full((H, W, 3), 128, np.uint8)
+        if win:
+            x0, y0 = (W - win[0]) // 2, (H - win[1]) // 2
+            img[y0:y0 + win[1], x0:x0 + win[0]] = tex[y0:y0 + win[1], x0:x0 + win[0]]
+        out.append(img)
+    out[3] = tex
+    return out
+
+
+def frame_pose(f):
+    """far from every record (they lie at x >= 1000), yaw 90 * (f % 4)"""
+    return synth.base_pose(-500.0 - 10.0 * f, 3.0, YAWS[f % 4])
+
+
+_expected = {}
+
+
+def expected(oracle, db, cur, bp=None, tol=90.0):
+    key = (db["name"], cur.tobytes())
+    if key not in _expected:
+        c = oracle.db_match_counts(db["desc"], db["off"], cur) if len(cur) else np.zeros(db["L"], np.int32)
+        c.setflags(write=False)
+        _expected[key] = c
+    if bp is None:
+        return _expected[key].copy()
+    ok, margin = SR.heading_ok(db["poses"], bp, tol)
+    assert margin >= 1e-6
+    return SR.masked(_expected[key], ok)
+
+
+def assert_counts(got, exp, what):
+    assert (got != POISON).all(), f"{what}: records {np.nonzero(got == POISON)[0][:8]} kept the poison"
+    bad = np.nonzero(got != exp)[0]
+    assert len(bad) == 0, f"{what}: {len(bad)} records differ, first {bad[:8]}: got {got[bad[:8]]} expected {exp[bad[:8]]}"
+
+
+def poison(e):
+    e.h2d(e.db_counts_dev(), np.full(e.db_records, POISON, np.int32))
+
+
+def read_counts(e):
+    out = np.empty(e.db_records, np.int32)
+    e.d2h(out, e.db_counts_dev())
+    return out
+
+
+def queries():
+    rng = np.random.default_rng(8100)
+    cur = synth.random_descriptors(rng, 2048)
+    for j in (3, 17, 40, 63):
+        cur[j + 64] = cur[j]                 # another slot of the same lane
+    for j in (8, 130, 300):
+        cur[j + 1] = cur[j]                  # the neighbouring lane
+    return cur
+
+
+# ---- the tie data, on the CPU ---------------------------------------------------------------------------------------------
+def test_tie_data_pins_the_rule(oracle):
+    """what the `ties` cases rely on: in the sliced records the best distance of many columns is reached by rows of
+    DIFFERENT waves, the oracle resolves them to the lowest row, and the mutant rule (highest row) counts differently"""
+    db = ties_db()
+    cur = low_entropy(np.random.default_rng(8104), 512)
+    for Q in (448, 500):
+        exp = oracle.db_match_counts(db["desc"], db["off"], cur[:Q])
+        differs = 0
+        for r, n in enumerate(TIE_SIZES):
+            D = distances(db["desc"][db["off"][r]:db["off"][r + 1]], cur[:Q])
+            assert mutual_count(D) == exp[r], (Q, r)
+            if n <= 64:
+                best = D.min(axis=0)
+                reach = np.array([(D[lo:hi] == best).any(axis=0) if hi > lo else np.zeros(Q, bool) for lo, hi in wave_ranges(n)])
+                assert (reach.sum(axis=0) >= 2).sum() >= Q // 4, (Q, r)
+                differs += mutual_count(D, high_row_on_ties=True) != exp[r]
+        assert differs >= 4, (Q, differs)
+
+
+# ---- the GPU cases --------------------------------------------------------------------------------------------------------
+class World:
+    pass
+
+
+@pytest.fixture(scope="module")
+def world():
+    import torch
+    wd = World()
+    wd.cu = torch.cuda.get_device_properties(0).multi_processor_count
+    wd.L = 12 * wd.cu
+    assert SR.single_scan_draws_tickets(wd.L, wd.cu) and all(SR.batch_scan_draws_tickets(wd.L, wd.cu, n) for n in (2, 3))
+    wd.cur = queries()
+    wd.cur_lo = low_entropy(np.random.default_rng(8104), 512)
+    with CH.engines(3, W, H, MAX_FEAT) as rig:
+        wd.rig, wd.es = rig, rig.es
+        for e in wd.es:
+            e.set_params(nfeatures=NFEAT)
+        wd.prm = wd.es[0].get_params()
+        wd.imgs = images()
+        wd.imgs_dev = [rig.to_device(img) for img in wd.imgs]
+        assert wd.es[0].orb_frame_dev(wd.imgs_dev[3], W, H, nfeatures=NFEAT) == NFEAT
+        wd.rich = wd.es[0].orb_features()["desc"]
+        wd.dbs = {"sizes": sizes_db(wd.cur), "ragged": ragged_db(wd.L, wd.cur, wd.rich), "ties": ties_db()}
+        rows = wd.dbs["ragged"]["rows"]
+        assert int(rows.sum()) < 160000 and set(SLICED_SIZES) & set(rows.tolist()) >= {1, 16, 17, 48, 63, 64}
+        assert 0.3 < (rows <= 64).mean() < 0.5 and rows.max() <= 130
+        db = wd.dbs["ragged"]
+        wd.es[0].db_upload(db["desc"], db["pts"], db["off"], db["poses"])
+        rig.share()
+        wd.scan_out_dev = rig.dev_alloc(3 * (2 * 25 + 2) * 4)
+        # contexts of both capacities for the calls with chosen query sets
+        wd.direct, bufs = {}, []
+        try:
+            for cap in (2048, 8192):
+                for name, d in wd.dbs.items():
+                    e = Engine(0, 64, 64, cap)
+                    e.db_upload(d["desc"], d["pts"], d["off"], d["poses"])
+                    ps = (e.dev_alloc(cap * 32), e.dev_alloc(4), e.dev_alloc(d["L"] * 4))
+                    bufs.append((e, ps))
+                    wd.direct[cap, name] = (e,) + ps
+            yield wd
+        finally:
+            for e, ps in bufs:
+                e.sync()
+                for p in ps:
+                    e.dev_free(p)
+                e.close()
+
+
+def scan_dev(wd, cap, name, cur, Q):
+    """reloc_db_match_counts_dev with the capacity as n_cur_max and the count Q on the device: k_db_scan<8>"""
+    e, cur_dev, n_dev, counts_dev = wd.direct[cap, name]
+    L = wd.dbs[name]["L"]
+    e.h2d(cur_dev, np.ascontiguousarray(cur[:min(len(cur), cap)]))
+    e.h2d(n_dev, np.array([Q], np.int32))
+    e.h2d(counts_dev, np.full(L, POISON, np.int32))
+    e.db_match_counts_dev(cur_dev, cap, counts_dev, n_dev)
+    e.sync()
+    got = np.empty(L, np.int32)
+    e.d2h(got, counts_dev)
+    return got
+
+
+@gpu
+@pytest.mark.parametrize("cap", [2048, 8192])
+def test_record_sizes_every_feature_count(world, oracle, cap):
+    """every record size on both sides of the 64-row edge, one record per workgroup; feature counts of one column block
+    (sliced up to 64 rows) and of two and three (shared everywhere).  Each scan twice: the second finds the first one's LDS"""
+    wd = world
+    db = wd.dbs["sizes"]
+    for Q in FEATS + FEATS_SHARED:
+        exp = expected(oracle, db, wd.cur[:Q])
+        for rep in range(2):
+            assert_counts(scan_dev(wd, cap, "sizes", wd.cur, Q), exp, f"capacity {cap} Q {Q} scan {rep}")
+
+
+@gpu
+def test_record_sizes_narrow_kernels(world, oracle):
+    """reloc_db_match_counts picks k_db_scan<2> up to 128 queries and <4> up to 256: slices of 128 and 256 columns"""
+    wd = world
+    e = wd.direct[2048, "sizes"][0]
+    for Q in (65, 100, 128, 129, 200, 256, 257):
+        assert_counts(e.db_match_counts(wd.cur[:Q]), expected(oracle, wd.dbs["sizes"], wd.cur[:Q]), f"Q {Q}")
+
+
+@gpu
+@pytest.mark.parametrize("cap", [2048, 8192])
+def test_ragged_records_by_ticket(world, oracle, cap):
+    """12 records per CU: a workgroup serves several by ticket and changes form between them in every order.  Q = 500 and 64
+    mix the forms; Q = 1100 is the shared form alone, single-buffered in the context of 2048 and double-buffered in 8192"""
+    wd = world
+    db = wd.dbs["ragged"]
+    for Q in (500, 64, 1100, 500):
+        exp = expected(oracle, db, wd.cur[:Q])
+        assert_counts(scan_dev(wd, cap, "ragged", wd.cur, Q), exp, f"capacity {cap} Q {Q}")
+    assert expected(oracle, db, wd.cur[:500]).max() >= 10
+
+
+@gpu
+@pytest.mark.parametrize("cap", [2048, 8192])
+def test_cross_wave_ties(world, oracle, cap):
+    """low-entropy rows and queries: a column's best distance is reached in several waves' slices and the lowest absolute row
+    must win (test_tie_data_pins_the_rule); the 80- and 130-row records take the shared form beside them"""
+    wd = world
+    db = wd.dbs["ties"]
+    for Q in (448, 500, 512):
+        exp = expected(oracle, db, wd.cur_lo[:Q])
+        assert_counts(scan_dev(wd, cap, "ties", wd.cur_lo, Q), exp, f"capacity {cap} Q {Q}")
+    zero = np.zeros((500, 32), np.uint8)                                      # every pair of a record ties
+    assert_counts(scan_dev(wd, cap, "ties", zero, 500), expected(oracle, db, zero), f"capacity {cap} zero queries")
+
+
+@gpu
+@pytest.mark.parametrize("n", [2, 3])
+def test_batched_scan_frames_of_different_feature_counts(world, oracle, n):
+    """reloc_shard_scan_batch_dev on the ragged database: frame f = image (3, 1, 2)[f], i.e. 500 features, a few and some
+    dozens; with poses (heading mask: about half of the records unscored, count 0 and never resolved) and without"""
+    wd = world
+    es, db, k = wd.es[:n], wd.dbs["ragged"], 25
+    order = (3, 1, 2)[:n]
+    imgs = [wd.imgs_dev[i] for i in order]
+    bps = [frame_pose(f) for f in range(n)]
+    seen = set()
+    for posed in (True, False):
+        for x in es:
+            poison(x)
+        Engine.shard_scan_batch_dev(es, imgs, W, H, bps if posed else None, k, 0, wd.scan_out_dev)
+        es[0].sync()
+        for f, x in enumerate(es):
+            feat = x.orb_features()
+            seen.add(feat["n"])
+            exp = expected(oracle, db, feat["desc"], bps[f] if posed else None, wd.prm.heading_tol_deg)
+            assert_counts(read_counts(x), exp, f"batch of {n} posed {posed} frame {f} ({feat['n']} features)")
+            if posed:
+                assert 0.3 <= (exp == 0).mean()
+    assert len(seen) == n and max(seen) == NFEAT and min(seen) < NFEAT // 2
+
+
+@gpu
+def test_heading_mask_single_scan(world, oracle):
+    """reloc_tick_scan_dev with a pose: the unscored records change nothing in the LDS of the workgroup that skips them"""
+    wd = world
+    e, db, k = wd.es[0], wd.dbs["ragged"], 25
+    for f in range(2):
+        bp = frame_pose(f)
+        poison(e)
+        e.tick_scan_into(wd.imgs_dev[3], W, H, bp, k, wd.scan_out_dev, wd.scan_out_dev + 4 * k, wd.scan_out_dev + 8 * k)
+        e.sync()
+        feat = e.orb_features()
+        assert feat["n"] == NFEAT
+        ok, _ = SR.heading_ok(db["poses"], bp, wd.prm.heading_tol_deg)
+        exp = expected(oracle, db, feat["desc"], bp, wd.prm.heading_tol_deg)
+        assert_counts(read_counts(e), exp, f"heading mask, frame {f}")
+        assert 0.3 <= ok.mean() <= 0.7 and (exp[~ok] == 0).all() and exp[ok].max() >= 10
+
+
+def auto_poses(wd, n, stand_down):
+    """frame f in stand_down: 1 m beside a planted record of a compatible heading (local candidates: the scan stands down);
+    the others far from every record"""
+    yaw = 7.0 + 13.0 * (np.arange(wd.L) % 27)
+    planted = planted_records(wd.L)
+    out = []
+    for f in range(n):
+        if f in stand_down:
+            d = np.abs((yaw[planted] - YAWS[f % 4] + 180.0) % 360.0 - 180.0)
+            r = int(planted[np.nonzero(d < 60.0)[0][f]])
+            out.append(synth.base_pose(1000.0 + 40.0 * r + 1.0, 0.5, YAWS[f % 4]))
+        else:
+            out.append(frame_pose(f))
+    return out
+
+
+def assert_emit_lists(e, exp, what):
+    """the emit pass behind a scan: every candidate's match list is as long as the count the scan gave its record"""
+    dbg = e.tick_debug()
+    assert len(dbg["cand_ids"]) >= 2, what
+    for s, r in enumerate(dbg["cand_ids"]):
+        assert e.tick_debug_matches(s)["n"] == exp[r] == dbg["n_matches"][s], (what, s, int(r))
+
+
+@gpu
+def test_auto_stand_down_and_emit_single(world, oracle):
+    """reloc_tick_dev: in AUTO mode a frame with local candidates leaves the poisoned counts alone; a global tick scans, and
+    the emit pass lists as many matches per candidate as the scan counted"""
+    wd = world
+    e, db = wd.es[0], wd.dbs["ragged"]
+    bps = auto_poses(wd, 2, (0,))
+    for f in range(2):
+        poison(e)
+        e.tick_dev(wd.imgs_dev[3], W, H, bps[f], global_reloc=2, seed=11 + f)
+        e.tick_result()
+        got = read_counts(e)
+        if f == 0:
+            assert (got == POISON).all(), f"a frame with local candidates scanned {int((got != POISON).sum())} records"
+        else:
+            exp = expected(oracle, db, e.orb_features()["desc"], bps[f], wd.prm.heading_tol_deg)
+            assert_counts(got, exp, "AUTO tick without local candidates")
+            assert_emit_lists(e, exp, "AUTO tick")
+    poison(e)
+    e.tick_dev(wd.imgs_dev[3], W, H, bps[1], global_reloc=1, seed=5)
+    e.tick_result()
+    exp = expected(oracle, db, e.orb_features()["desc"], bps[1], wd.prm.heading_tol_deg)
+    assert_counts(read_counts(e), exp, "global tick")
+    assert_emit_lists(e, exp, "global tick")
+
+
+@gpu
+@pytest.mark.parametrize("n", [2, 3])
+def test_tick_batch_stand_down_and_emit(world, oracle, n):
+    """reloc_tick_batch_dev, frames of different feature counts: global mode, then AUTO with frame 0 standing down inside the
+    launch; the emit pass of every scanned frame that has candidates"""
+    wd = world
+    es, db = wd.es[:n], wd.dbs["ragged"]
+    imgs = [wd.imgs_dev[i] for i in (3, 3, 2)[:n]]
+    seeds = [11 + f for f in range(n)]
+    for mode, stand_down in ((1, ()), (2, (0,))):
+        bps = auto_poses(wd, n, stand_down)
+        for x in es:
+            poison(x)
+        Engine.tick_batch_dev(es, imgs, W, H, bps, global_reloc=mode, seeds=seeds)
+        for f, x in enumerate(es):
+            x.tick_result()
+            got = read_counts(x)
+            what = f"batch of {n} mode {mode} frame {f}"
+            if f in stand_down:
+                assert (got == POISON).all(), what
+                continue
+            feat = x.orb_features()
+            exp = expected(oracle, db, feat["desc"], bps[f], wd.prm.heading_tol_deg)
+            assert_counts(got, exp, what)
+            if feat["n"] == NFEAT:
+                assert_emit_lists(x, exp, what)
