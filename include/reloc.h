@@ -278,6 +278,14 @@ int reloc_pnp_score(reloc_ctx *ctx, const float *obj, const float *img, int m, c
 int reloc_pnp_ransac(reloc_ctx *ctx, const float *obj, const float *img, int m, const double K4[4],
                      int iters, float thr_px, double conf, uint64_t seed, double rvec[3],
                      double tvec[3], int32_t *inliers, int32_t *n_inl, int32_t *ok);
+/* Parity tap (tests only): the hypothesis stage of the last PnP launch on ctx, for candidate `slot` -- slot 0 after
+ * reloc_pnp_ransac[_dist] (a call with m < 4 launches nothing and leaves the previous launch in place), the slot's order in
+ * reloc_tick_debug's cand_ids after a tick solve.  Rt: the first n poses (n x 12 doubles, R row-major | t) as the
+ * hypothesis kernel wrote them; cnt: their n inlier counts; *best_h: the hypothesis the RANSAC decision chose (-1: none).
+ * A row whose count is -1 holds no pose (the sample was degenerate or no root gave one): its 12 doubles are whatever the
+ * buffer held before.  Rows at or beyond the launch's iterationsCount are stale as well.  RELOC_E_ARG for slot outside
+ * [0, 32), n outside [1, 1024] or a NULL pointer.  Synchronises the context's stream; copies only, launches nothing. */
+int reloc_pnp_debug_hypotheses(reloc_ctx *ctx, int slot, int n, double *Rt, int32_t *cnt, int32_t *best_h);
 
 /* Camera model used by the fused tick: K4 = fx fy cx cy (M:49-52) and the static base_link ->
  * camera transform stored in landmarks.pkl (M:183-184; R:81-88).  NULL keeps the current value;

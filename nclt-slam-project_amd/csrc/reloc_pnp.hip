@@ -1048,7 +1048,10 @@ static int pnp_ransac_impl(reloc_ctx *ctx, const float *obj, const float *img, i
                            int iters, float thr_px, double conf, uint64_t seed, double rvec[3], double tvec[3],
                            int32_t *inliers, int32_t *n_inl, int32_t *ok)
 {
-    ARG_CHECK(iters >= 1 && iters <= MAX_HYP, "iterationsCount must be in [1, 256]");
+    if (iters < 1 || iters > MAX_HYP) {
+        reloc_set_error("bad argument: iterationsCount must be in [1, %d]", MAX_HYP);
+        return RELOC_E_ARG;
+    }
     *ok = 0;
     *n_inl = 0;
     if (m < RELOC_PNP_SAMPLE) return RELOC_OK;
@@ -1094,6 +1097,23 @@ RELOC_API int reloc_pnp_ransac_dist(reloc_ctx *ctx, const float *obj, const floa
     ARG_CHECK(dist_finite(dist), "reloc_pnp_ransac_dist: non-finite distortion coefficient");
     return pnp_ransac_impl(ctx, obj, img, m, K4, dist_nonzero(dist) ? dist : nullptr, iters, thr_px, conf, seed, rvec, tvec,
                            inliers, n_inl, ok);
+}
+
+// Parity tap: the hypothesis stage of the context's last PnP launch, as k_pnp_hyp and k_pnp_score left it for candidate
+// `slot`.  Copies only, launches nothing.
+RELOC_API int reloc_pnp_debug_hypotheses(reloc_ctx *ctx, int slot, int n, double *Rt, int32_t *cnt, int32_t *best_h)
+{
+    ARG_CHECK_CTX(ctx, slot >= 0 && slot < MAX_CAND && n >= 1 && n <= MAX_HYP && Rt && cnt && best_h,
+                  "reloc_pnp_debug_hypotheses");
+    const size_t at = (size_t)slot * MAX_HYP;
+    PnpOut po = {};
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpyAsync(Rt, ctx->tick.p_Rt + at * 12, (size_t)n * 12 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(cnt, ctx->tick.p_cnt + at, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&po, ctx->tick.p_out + slot, sizeof(po), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *best_h = po.best_h;
+    return RELOC_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -913,6 +913,15 @@ class Engine:
             self._api.reloc_pnp_ransac_dist(self._ctx, obj, img, len(obj), K4, self._dist5(dist), *tail)
         return bool(ok.value), rvec, tvec, inl[: n.value].copy()
 
+    def pnp_debug_hypotheses(self, n: int, slot: int = 0):
+        """parity tap: (Rt (n, 12), cnt (n,), best_h) of candidate slot `slot` of the last PnP launch -- slot 0 after
+        pnp_ransac (reloc_pnp_debug_hypotheses; synchronises).  Rows with cnt == -1 hold no pose."""
+        n = int(n)
+        Rt = np.zeros((max(n, 1), 12), np.float64); cnt = np.zeros(max(n, 1), np.int32)
+        best = i32()
+        self._api.reloc_pnp_debug_hypotheses(self._ctx, int(slot), n, Rt, cnt, best)
+        return Rt, cnt, best.value
+
     # ------------------------------------------------------------------ fused tick
     def get_params(self) -> "N.RelocParams":
         p = N.RelocParams()
