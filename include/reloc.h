@@ -518,6 +518,39 @@ int reloc_occ_integrate_stereo_dev(reloc_ctx *ctx, int step, float zmin, float z
  * NULL.  Synchronous. */
 int reloc_occ_read(reloc_ctx *ctx, int8_t *units, uint8_t *pgm, int64_t counters[3]);
 
+/* ---- depth-correlation anchor (include/reloc_spec.h, "CORRELATION") ------------------------------- */
+/* The second anchor channel of the reference's depth_correlation_matcher.py: the cells of the current depth cloud slid over the
+ * dilated teach occupancy map, hits counted at every offset of a table, best and second best picked on the device.
+ * reloc_corr_set_map takes the occupied plane (h x w uint8, row 0 at origin_y, non-zero = occupied; cell (0, 0) at (origin_x,
+ * origin_y), res metres per cell), packs it to one bit per cell and dilates it `dilate` times by the 4-connected cross.  A
+ * second call replaces the map.  reloc_corr_set_map_from_occ takes the context's live occupancy grid (units >= 4, its
+ * geometry) where it lies: RELOC_E_STATE without one.  Non-positive sizes or res, dilate < 0, anything not finite: RELOC_E_ARG;
+ * more than RELOC_CORR_MAX_CELLS cells, RELOC_CORR_MAX_SIDE per side or RELOC_CORR_MAX_DILATE iterations, or a cell size under
+ * which the configured max_range no longer fits the window: RELOC_E_CAPACITY, the map before stays.  A context that never sets
+ * a map allocates and launches nothing of this.  Every other entry point here returns RELOC_E_STATE before a map is set. */
+int reloc_corr_set_map(reloc_ctx *ctx, const uint8_t *occupied, int w, int h, double origin_x, double origin_y, double res,
+                       int dilate);
+int reloc_corr_set_map_from_occ(reloc_ctx *ctx, int dilate);
+/* The search: cell_offsets, the n_side = 2 ns + 1 cell offsets of rule (g), index i for columns and j for rows; the height
+ * band, the range about the base position and the least number of points (rules (d), (e)).  n_side even or < 1, min_points
+ * < 0, max_range <= 0, anything not finite: RELOC_E_ARG.  n_side > RELOC_CORR_MAX_TABLE, an offset beyond
+ * RELOC_CORR_MAX_OFFSET cells, or 2 * (ceil(max_range / res) + 2) + 1 > RELOC_CORR_MAX_WINDOW: RELOC_E_CAPACITY. */
+int reloc_corr_configure(reloc_ctx *ctx, const int32_t *cell_offsets, int n_side, double z_lo, double z_hi, double max_range,
+                         int min_points);
+/* One tick from each of the occupancy map's three sources (reloc_occ_integrate_*): T12 the 3 x 4 sensor-to-map transform,
+ * (vio_x, vio_y) the base position, all finite (RELOC_E_ARG).  record: RELOC_CORR_RECORD_WORDS int32 -- status RELOC_CORR_*,
+ * kept points, points in the map, n_cells, best i, best j (in [-ns, ns]), best hits, second hits.  surface (may be NULL):
+ * n_side x n_side int32 hits, [i + ns][j + ns]; all zero behind a status other than RELOC_CORR_OK.  RELOC_E_STATE before
+ * reloc_corr_configure.  Synchronous. */
+int reloc_corr_match_points(reloc_ctx *ctx, const float *pts, int n, const double T12[12], double vio_x, double vio_y,
+                            int32_t *record, int32_t *surface);
+int reloc_corr_match_depth(reloc_ctx *ctx, const void *depth, int is_f32, int w, int h, int step, const double K4[4], float zmin,
+                           float zmax, const double T12[12], double vio_x, double vio_y, int32_t *record, int32_t *surface);
+int reloc_corr_match_stereo_dev(reloc_ctx *ctx, int step, float zmin, float zmax, const double T12[12], double vio_x, double vio_y,
+                                int32_t *record, int32_t *surface);
+/* The dilated map unpacked: h x w uint8 of 0 / 1, row 0 at origin_y (plane may be NULL); *w, *h: its size (may be NULL). */
+int reloc_corr_read_map(reloc_ctx *ctx, uint8_t *plane, int32_t *w, int32_t *h);
+
 /* ---- fused tick ----------------------------------------------------------------------------- */
 #define RELOC_TICK_LOCAL   0   /* candidates by VIO distance / heading only                          M:293-302 */
 #define RELOC_TICK_GLOBAL  1   /* whole-database search unconditionally (the benchmarked shape)       G:329-344 */

@@ -412,4 +412,54 @@
 #define RELOC_OCC_MAX_CELLS    (1 << 24)   /* capacity of one grid: w_cells * h_cells */
 #define RELOC_OCC_SUBSAMPLE_DEFAULT 4
 
+/* CORRELATION: the depth-correlation anchor of the reference's depth_correlation_matcher.py (C below): the cells of the current
+ * depth cloud are slid over the dilated teach occupancy map and the offset with the most hits becomes an anchor.  Restated in
+ * tests/correlation_ref.py, which the library equals in every integer it returns.  C line by line.
+ *   (a) map      the .pgm plane with rows flipped (C:84-85), occupied = (pixel == 0) (C:86), row 0 at origin_y.  Dilated n
+ *              times (C:89-90, iterations = dilate_cells, C's default 1) by SciPy's DEFAULT structuring element: the
+ *              4-connected cross, whatever C's comment says of a 3 x 3 square.  One iteration: a cell is occupied iff it or one
+ *              of its four edge neighbours was; cells beyond the border count as empty.  n = 0: the plane as it is.
+ *   (b) cloud    OCCUPANCY (a): rows with a non-finite coordinate are dropped first (C:108).  No row left: status
+ *              NO_DEPTH_POINTS (C:170-172).
+ *   (c) map pt   OCCUPANCY (b) with the 3 x 4 float64 sensor-to-map transform, same operations, same order (C:175-179; the
+ *              host composes the transform).
+ *   (d) filters  keep z_lo < z < z_hi, both strict (C:183; 0.2, 2.0), and dx * dx + dy * dy < R * R with dx = x - vio_x,
+ *              dy = y - vio_y: float64, each operation rounded, no contraction, R * R computed once (C:184-185's
+ *              hypot(dx, dy) < MAX_RANGE, 15.0).  (vio_x, vio_y) is the BASE position, not the sensor's.  Fewer than
+ *              min_points (C: 100) points kept: status TOO_FEW_POINTS, the record's kept count is what C logs (C:187-189).
+ *   (e) cells    OCCUPANCY (d) for col from x and row from y (C:192-194): truncation toward zero, in the map iff
+ *              0 <= cell < n after truncation.  Fewer than min_points POINTS (not cells) in the map: status OUT_OF_BOUNDS,
+ *              the in-map count is what C logs (C:196-198).
+ *   (f) scan     the set of distinct (row, col) of the points in the map; n_cells its size (C:200-201).
+ *   (g) search   offsets (i, j), i, j in [-ns, ns], ns = int(window / step) (C:135-139).  The cell offset of index k is
+ *              t[k + ns] = int(round(k * step / res)) with Python's round (C:210-211); the host computes this table of
+ *              2 ns + 1 entries and hands it over.  i shifts columns, j rows.  hits(i, j) = number of scan cells (r, c) with
+ *              (r + t[j], c + t[i]) inside the map and occupied there (C:212-219).  Entries may repeat.
+ *   (h) best     scores in i-major, j-minor order; best = the first strictly greater than every score before it, starting
+ *              from 0 hits at (i, j) = (0, 0) (C:204-223): an all-zero surface gives (0, 0) with 0 hits.  second = the second
+ *              element of the scores sorted descending (C:226-228): equal to best when the maximum is tied, 0 for a table of
+ *              one entry.
+ *   (i) host     float64, C's expressions: frac = hits / n_cells (0.0 when n_cells == 0), peak_ratio = hits / max(1, second)
+ *              (C:225-229); gates in this order: hits < min_hits -> low_hits, frac < min_fraction -> low_fraction, peak_ratio <
+ *              min_peak_ratio -> not_significant, hypot(dx, dy) > consistency_m -> consistency_fail_{:.1f} (C:231-248) with
+ *              dx = i * step, dy = j * step; anchor = (vio_x + dx, vio_y + dy, base z, base quaternion) (C:251-272);
+ *              std = min(0.10 + 0.15 / max(1.0, peak_ratio - 1.0), 0.25), covariance [0] = [7] = std * std, [14] = 0.25,
+ *              [21] = [28] = [35] = 0.05 (C:255-261); outcome published_std{:.2f}_shift{:.2f}; the CSV header and row of
+ *              C:132, 152-156.
+ * The record of a tick: RELOC_CORR_RECORD_WORDS int32: status, kept points (d), points in the map (e), n_cells, best i, best j,
+ * best hits, second hits; the two point counts are always the frame's, behind a status other than OK the last five words are 0
+ * and so is the whole surface. */
+#define RELOC_CORR_OK               0
+#define RELOC_CORR_NO_DEPTH_POINTS  1
+#define RELOC_CORR_TOO_FEW_POINTS   2
+#define RELOC_CORR_OUT_OF_BOUNDS    3
+#define RELOC_CORR_RECORD_WORDS     8
+#define RELOC_CORR_MAX_CELLS   (1 << 24)   /* capacity of one map: w * h ... */
+#define RELOC_CORR_MAX_SIDE    32768       /* ... and cells per side */
+#define RELOC_CORR_MAX_DILATE  64          /* iterations of (a) */
+#define RELOC_CORR_MAX_TABLE   255         /* entries of the offset table (g): 2 ns + 1 */
+#define RELOC_CORR_MAX_OFFSET  32768       /* magnitude of one entry, cells */
+#define RELOC_CORR_MAX_WINDOW  703         /* side of the scan's window, cells: 2 * (ceil(max_range / res) + 2) + 1 */
+#define RELOC_CORR_MIN_POINTS_DEFAULT 100
+
 #endif /* RELOC_SPEC_H */

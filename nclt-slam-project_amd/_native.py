@@ -139,6 +139,13 @@ SIGNATURES = {
     "reloc_occ_integrate_depth": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, C.c_int, P, f32, f32, P, P]),
     "reloc_occ_integrate_stereo_dev": (C.c_int, [c_ctx, C.c_int, f32, f32, P, P]),
     "reloc_occ_read": (C.c_int, [c_ctx, P, P, P]),
+    "reloc_corr_set_map": (C.c_int, [c_ctx, P, C.c_int, C.c_int, f64, f64, f64, C.c_int]),
+    "reloc_corr_set_map_from_occ": (C.c_int, [c_ctx, C.c_int]),
+    "reloc_corr_configure": (C.c_int, [c_ctx, P, C.c_int, f64, f64, f64, C.c_int]),
+    "reloc_corr_match_points": (C.c_int, [c_ctx, P, C.c_int, P, f64, f64, P, P]),
+    "reloc_corr_match_depth": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, C.c_int, P, f32, f32, P, f64, f64, P, P]),
+    "reloc_corr_match_stereo_dev": (C.c_int, [c_ctx, C.c_int, f32, f32, P, f64, f64, P, P]),
+    "reloc_corr_read_map": (C.c_int, [c_ctx, P, P, P]),
     "reloc_tick_debug": (C.c_int, [c_ctx, P, P, P, P, P, P, P]),
     "reloc_tick_debug_matches": (C.c_int, [c_ctx, C.c_int, P, P, P, P, P, P]),
     "reloc_tick": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, P, C.c_int, u64, P, P, P, P, P, P]),

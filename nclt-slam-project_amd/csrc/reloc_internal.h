@@ -421,6 +421,26 @@ struct OccState {
     bool on() const { return w > 0; }
 };
 
+// Depth-correlation anchor of a context (include/reloc_spec.h "CORRELATION"; reloc_correlation.hip); 0 x 0 = no map, the default: a
+// context that never sets a correlation map allocates and launches nothing of it.  Two device blocks of its own: the map's
+// (reloc_corr_set_map*) and the search's (reloc_corr_configure), both freed by corr_release.
+struct CorrState {
+    int w = 0, h = 0, mp = 0;            // the map: cells, words per packed row
+    double ox = 0, oy = 0, res = 0;
+    uint8_t *map_block = nullptr;        // two packed planes of map_words words: the dilation goes from one to the other
+    int64_t map_words = 0;
+    uint32_t *map = nullptr;             // the one that holds the dilated map
+    int n_side = 0, min_points = 0, half = 0;      // offsets per axis (0: not configured); the window is 2 * half + 1 cells a side
+    double z_lo = 0, z_hi = 0, max_range = 0;
+    uint8_t *cfg_block = nullptr;        // the pointers below lie in it, sized for the limits of reloc_spec.h
+    uint32_t *list = nullptr;            // the last tick's scan: the non-zero words of the window's bitmap (row << 5 | word, bits)
+    int32_t *surface = nullptr;          // n_side x n_side hits of the last tick
+    int32_t *table = nullptr;            // n_side cell offsets
+    int32_t *record = nullptr;           // the last tick's record
+    bool on() const { return w > 0; }
+    bool configured() const { return n_side > 0; }
+};
+
 // What the five ORB kernels read and write of one frame, in the form they take it: a single-frame launch passes the members
 // as arguments, a batched one up to 8 of these in its kernel arguments (OrbBatch, blockIdx.y = frame).
 struct OrbFrame {
@@ -506,6 +526,7 @@ struct reloc_ctx {
     MatchPolicy match;
     StereoState stereo;              // reloc_stereo.hip
     OccState occ;                    // reloc_occupancy.hip
+    CorrState corr;                  // reloc_correlation.hip
     int scan_gens = 0;               // RELOC_SCAN_GENS (developer switch), read once at creation: n > 0 = single whole-database
                                      // scans in the form of batched ones (n generations of row budgets + sweepers, launch_db_count)
     uint32_t *scan_ticket = nullptr; // SCAN_TICKET_WORDS counters of the whole-database scans (scan_alloc, reloc_match.hip)
@@ -662,6 +683,8 @@ int stereo_frame(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img_right_dev,
 void stereo_release(reloc_ctx *ctx);
 // the occupancy map's block, if the context has one (reloc_occupancy.hip)
 void occ_release(reloc_ctx *ctx);
+// the correlation anchor's blocks, if the context has any (reloc_correlation.hip)
+void corr_release(reloc_ctx *ctx);
 // Dense stereo depth: both eyes' frames (ctx->frame_img, right->frame_img, w x h as handed in) through the gray half of their
 // chains, each on its own stream, no ORB; then k_stereo_dense and k_stereo_dense_finish on ctx's stream into ctx->stereo.dense
 // (mm: dense rows of *ww uint16).  Checks stereo on, right != ctx, capacity and the chains' agreement.

@@ -19,21 +19,8 @@ constexpr int OCC_QUEUE = 2048;       // rays waiting in LDS: drained when more 
 constexpr int OCC_MAX_SIDE = 32768;   // a queued end cell is row << 16 | col
 
 struct OccGeom { double ox, oy, res, z_lo, z_hi; int W, H, sub; };
-struct OccT { double v[12]; };
-// what a frame reads: a cloud (n rows of 3 floats at pts) or the grid of a depth plane, as k_depth_points takes it
-struct OccSrc { const float *pts; int n; DepthGrid grid; };
-enum { OCC_SRC_POINTS = 0, OCC_SRC_DEPTH_F32 = 1, OCC_SRC_DEPTH_U16 = 2 };
 // frame record on the device: [0] rays of the frame, [1..4] box of the far rays (row lo, row hi, col lo, col hi; hi < lo: none)
 constexpr int OCC_FRAME_WORDS = 8;
-
-// (d): q = (x - origin) / res in double, in the grid iff -1 < q < n (trunc toward zero puts (-1, 0) into cell 0)
-__device__ __forceinline__ bool occ_cell(double x, double origin, double res, int n, int &cell)
-{
-    const double q = __ddiv_rn(__dsub_rn(x, origin), res);
-    const bool in = q > -1.0 && q < (double)n;
-    cell = in ? (int)q : 0;
-    return in;
-}
 
 template <int SRC>
 __global__ __launch_bounds__(1024) void k_occ_integrate(OccSrc src, OccT T, OccGeom g, int8_t *__restrict__ units,
@@ -51,7 +38,7 @@ __global__ __launch_bounds__(1024) void k_occ_integrate(OccSrc src, OccT T, OccG
     int r0, c0;
     const bool start_in = occ_cell(T.v[3], g.ox, g.res, g.W, c0) & occ_cell(T.v[7], g.oy, g.res, g.H, r0);
     const int wr0 = r0 - OCC_WIN / 2, wc0 = c0 - OCC_WIN / 2;
-    const int n = SRC == OCC_SRC_POINTS ? src.n : src.grid.cols() * src.grid.rows();
+    const int n = occ_src_count<SRC>(src);
     int at_start = 0;                             // this lane's share of the start cell's sum
     int n_fin = 0, n_keep = 0;                    // this lane's finite points; the workgroup's kept points so far
     __syncthreads();
@@ -89,16 +76,11 @@ __global__ __launch_bounds__(1024) void k_occ_integrate(OccSrc src, OccT T, OccG
         double mx = 0, my = 0;
         if (i < n) {
             float p[3];
-            if (SRC == OCC_SRC_POINTS) {
-                for (int k = 0; k < 3; ++k) p[k] = src.pts[(size_t)3 * i + k];
-                fin = true;
-            } else fin = depth_grid_point(src.grid, SRC == OCC_SRC_DEPTH_F32, i, p);
-            fin = fin && isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]);
+            fin = occ_src_point<SRC>(src, i, p);
             if (fin) {
-                const double x = p[0], y = p[1], z = p[2];
-                mx = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(T.v[0], x), __dmul_rn(T.v[1], y)), __dmul_rn(T.v[2], z)), T.v[3]);
-                my = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(T.v[4], x), __dmul_rn(T.v[5], y)), __dmul_rn(T.v[6], z)), T.v[7]);
-                const double mz = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(T.v[8], x), __dmul_rn(T.v[9], y)), __dmul_rn(T.v[10], z)), T.v[11]);
+                mx = occ_map_coord(T, 0, p);
+                my = occ_map_coord(T, 1, p);
+                const double mz = occ_map_coord(T, 2, p);
                 keep = mz > g.z_lo && mz < g.z_hi;
             }
         }
@@ -181,8 +163,6 @@ void occ_release(reloc_ctx *ctx)
     if (ctx->occ.block) (void)hipFree(ctx->occ.block);
     ctx->occ = OccState{};
 }
-
-static inline bool occ_finite(double v) { return v - v == 0.0; }
 
 RELOC_API int reloc_occ_configure(reloc_ctx *ctx, double origin_x, double origin_y, double res, int w_cells, int h_cells, double z_lo,
                                   double z_hi, int subsample)

@@ -1,6 +1,7 @@
-// reloc_teach.h -- what the teach-side files (reloc_record.hip, reloc_stereo.hip, reloc_occupancy.hip) share and no other file
-// includes: the ordered compaction of a 1024-thread workgroup, the depth pixel of the obstacle cloud and of the occupancy map,
-// and the staging of a stereo pair that comes from the caller's memory.
+// reloc_teach.h -- what the teach-side files (reloc_record.hip, reloc_stereo.hip, reloc_occupancy.hip, reloc_correlation.hip) share
+// and no other file includes: the ordered compaction of a 1024-thread workgroup, the depth pixel of the obstacle cloud and of the
+// occupancy map, the frame source and map point of the occupancy map and the correlation scan, and the staging of a stereo pair
+// that comes from the caller's memory.
 #pragma once
 #include "reloc_internal.h"
 
@@ -53,6 +54,45 @@ __device__ __forceinline__ bool depth_grid_point(const DepthGrid &g, bool f32, i
     p[2] = -__fmul_rn(__fdiv_rn(__fsub_rn((float)v, g.cy), g.fy), z);
     return z > g.zmin && z < g.zmax && isfinite(z);
 }
+
+// What a frame of the occupancy map and of the correlation scan reads: a cloud (n rows of 3 floats at pts) or the grid of a depth
+// plane, as k_depth_points takes it.  A kernel is templated on the kind.
+struct OccSrc { const float *pts; int n; DepthGrid grid; };
+enum { OCC_SRC_POINTS = 0, OCC_SRC_DEPTH_F32 = 1, OCC_SRC_DEPTH_U16 = 2 };
+struct OccT { double v[12]; };       // the 3 x 4 sensor-to-map transform, row major
+
+template <int SRC>
+__device__ __forceinline__ int occ_src_count(const OccSrc &src) { return SRC == OCC_SRC_POINTS ? src.n : src.grid.cols() * src.grid.rows(); }
+
+// OCCUPANCY (a): row or pixel i of the source; true iff it is a point of the cloud with three finite coordinates
+template <int SRC>
+__device__ __forceinline__ bool occ_src_point(const OccSrc &src, int i, float p[3])
+{
+    bool fin;
+    if (SRC == OCC_SRC_POINTS) {
+        for (int k = 0; k < 3; ++k) p[k] = src.pts[(size_t)3 * i + k];
+        fin = true;
+    } else fin = depth_grid_point(src.grid, SRC == OCC_SRC_DEPTH_F32, i, p);
+    return fin && isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]);
+}
+
+// OCCUPANCY (b): row k of the transform applied to p, float64, this order, no contraction
+__device__ __forceinline__ double occ_map_coord(const OccT &T, int k, const float p[3])
+{
+    const double x = p[0], y = p[1], z = p[2];
+    return __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(T.v[4 * k], x), __dmul_rn(T.v[4 * k + 1], y)), __dmul_rn(T.v[4 * k + 2], z)), T.v[4 * k + 3]);
+}
+
+// OCCUPANCY (d): q = (x - origin) / res in double, in the grid iff -1 < q < n (trunc toward zero puts (-1, 0) into cell 0)
+__device__ __forceinline__ bool occ_cell(double x, double origin, double res, int n, int &cell)
+{
+    const double q = __ddiv_rn(__dsub_rn(x, origin), res);
+    const bool in = q > -1.0 && q < (double)n;
+    cell = in ? (int)q : 0;
+    return in;
+}
+
+static inline bool occ_finite(double v) { return v - v == 0.0; }
 
 // What an entry point checks of a stereo pair before it enqueues anything.
 static inline int stereo_pair_entry(const reloc_ctx *ctx, const reloc_ctx *right, int w, int h)

@@ -855,6 +855,69 @@ class Engine:
         self._api.reloc_occ_read(self._ctx, u, p, c)
         return dict(units=u, pgm=p, frames_integrated=int(c[0]), total_points_integrated=int(c[1]), frames_skipped_empty=int(c[2]))
 
+    # ------------------------------------------------------------------ depth-correlation anchor (reloc_spec.h "CORRELATION")
+    def corr_set_map(self, occupied, origin_x: float, origin_y: float, res: float, dilate: int = 1):
+        """the teach map: an (H, W) plane, row 0 at origin_y, non-zero = occupied; dilated `dilate` times on the device"""
+        occ = np.ascontiguousarray(occupied)
+        if occ.ndim != 2 or occ.size == 0:
+            raise N.RelocError("corr_set_map: expected a non-empty (H, W) plane")
+        occ = np.ascontiguousarray(occ != 0, np.uint8)
+        h, w = occ.shape
+        self._api.reloc_corr_set_map(self._ctx, occ, w, h, float(origin_x), float(origin_y), float(res), int(dilate))
+
+    def corr_set_map_from_occ(self, dilate: int = 1):
+        """the context's live occupancy grid (occ_configure) as the teach map, without a trip through the host"""
+        self._api.reloc_corr_set_map_from_occ(self._ctx, int(dilate))
+
+    def corr_configure(self, cell_offsets, z_lo: float = 0.2, z_hi: float = 2.0, max_range: float = 15.0, min_points: int = 100):
+        """the search: the 2 ns + 1 cell offsets of both axes, the height band, the range about the base, the least points"""
+        t = np.ascontiguousarray(cell_offsets, np.int32)
+        if t.ndim != 1:
+            raise N.RelocError("corr_configure: expected a 1-D table of cell offsets")
+        self._api.reloc_corr_configure(self._ctx, t, len(t), float(z_lo), float(z_hi), float(max_range), int(min_points))
+        self._corr_side = len(t)
+
+    def _corr_out(self, surface):
+        n = getattr(self, "_corr_side", 0)
+        return np.zeros(8, np.int32), (np.zeros((n, n), np.int32) if surface and n else None)
+
+    def corr_match_points(self, points, T, vio_x: float, vio_y: float, surface: bool = False):
+        """one tick from an (n, 3) float32 cloud in the sensor frame: (record of 8 int32, surface [i][j] or None)"""
+        pts = np.ascontiguousarray(points, np.float32)
+        if pts.size and (pts.ndim != 2 or pts.shape[1] != 3):
+            raise N.RelocError("corr_match_points: expected an (n, 3) cloud")
+        rec, surf = self._corr_out(surface)
+        self._api.reloc_corr_match_points(self._ctx, pts if pts.size else None, pts.size // 3, self._occ_T(T, "corr_match_points"),
+                                          float(vio_x), float(vio_y), rec, surf)
+        return rec, surf
+
+    def corr_match_depth(self, depth, T, vio_x: float, vio_y: float, step: int = 4, K4=K4_DEFAULT, zmin: float = 0.3, zmax: float = 10.0,
+                         surface: bool = False):
+        """one tick from a depth image as depth_points takes it; the cloud is never written"""
+        depth = np.ascontiguousarray(depth)
+        if depth.dtype not in (np.float32, np.uint16) or depth.ndim != 2:
+            raise N.RelocError("corr_match_depth: expected an (H, W) float32 (metres) or uint16 (millimetres) image")
+        h, w = depth.shape
+        rec, surf = self._corr_out(surface)
+        self._api.reloc_corr_match_depth(self._ctx, depth, int(depth.dtype == np.float32), w, h, int(step), np.ascontiguousarray(K4, np.float64),
+                                         float(zmin), float(zmax), self._occ_T(T, "corr_match_depth"), float(vio_x), float(vio_y), rec, surf)
+        return rec, surf
+
+    def corr_match_stereo(self, T, vio_x: float, vio_y: float, step: int = 4, zmin: float = 0.3, zmax: float = 10.0, surface: bool = False):
+        """one tick from the depth plane of this engine's last dense stereo pass, on the device"""
+        rec, surf = self._corr_out(surface)
+        self._api.reloc_corr_match_stereo_dev(self._ctx, int(step), float(zmin), float(zmax), self._occ_T(T, "corr_match_stereo"),
+                                              float(vio_x), float(vio_y), rec, surf)
+        return rec, surf
+
+    def corr_read_map(self):
+        """the dilated teach map: (H, W) bool, row 0 at origin_y"""
+        w, h = i32(), i32()
+        self._api.reloc_corr_read_map(self._ctx, None, w, h)
+        plane = np.zeros((h.value, w.value), np.uint8)
+        self._api.reloc_corr_read_map(self._ctx, plane, None, None)
+        return plane.astype(bool)
+
     def hamming_matrix(self, a, b):
         a = self._desc(a, "hamming_matrix"); b = self._desc(b, "hamming_matrix")
         out = np.empty((len(a), len(b)), np.uint16)

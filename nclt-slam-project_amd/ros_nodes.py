@@ -6,7 +6,9 @@
     TeachDepthMapper(out_prefix, origin_x, origin_y, width_m, height_m, res)
                                                         --out-prefix --origin-x --origin-y --width-m --height-m --res
                                                         [--depth-topic NAME --depth-k4 FX FY CX CY]
-    both, for a rectified stereo pair without a depth sensor:
+    DepthCorrelationMatcher(teach_yaml, log_csv)        --teach-map --out-csv [--depth-topic NAME --depth-k4 FX FY CX CY]
+                                                        [one flag per threshold: CORRELATION_FLAGS]
+    the first two, for a rectified stereo pair without a depth sensor:
                                                         [--stereo-baseline M --stereo-num-disparities N
                                                          --stereo-rectify-right FILE.npz --right-topic NAME]
 
@@ -30,6 +32,7 @@ from .stereo import StereoRig
 
 RIGHT_TOPIC = "/camera/right/image_raw"      # --right-topic: the right eye of a stereo rig (--stereo-baseline)
 TICK_HZ = 2.0
+CORRELATION_TICK_HZ = 1.0                    # the depth-correlation node's own rate (depth_correlation_matcher.py:51,126)
 POSE_FILE = "/tmp/isaac_pose.txt"
 DRIFT_FILE = "/tmp/drift_est.txt"
 
@@ -333,6 +336,63 @@ def make_depth_mapper_node(out_prefix, origin_x=-110.0, origin_y=-50.0, width_m=
     return TeachDepthMapper()
 
 
+def make_depth_correlation_node(teach_yaml, log_csv, depth_topic=None, K4=None, engine=None, **thresholds):
+    """The reference's DepthCorrelationMatcher(teach_yaml, log_csv) (depth_correlation_matcher.py:111-285) over
+    depth_anchor.DepthCorrelationCore: the last /depth_points cloud, or with depth_topic that depth image itself (camera K4 =
+    fx, fy, cx, cy; default the reference camera's), correlated once a second against the teach map from the pose file's pose;
+    an anchor goes out on /anchor_correction, beside the matcher node's.  thresholds: DepthCorrelationCore's keywords.
+    engine: the Engine that holds the map (default: a new one)."""
+    import time
+    from geometry_msgs.msg import PoseWithCovarianceStamped
+    from sensor_msgs.msg import Image, PointCloud2
+    from .depth_anchor import DepthCorrelationCore
+    from .engine import K4_DEFAULT, Engine
+    Node = _node_base()
+
+    class DepthCorrelationMatcher(Node):
+        def __init__(self):
+            super().__init__("depth_correlation_matcher")
+            self.core = DepthCorrelationCore(engine if engine is not None else Engine(), teach_yaml=teach_yaml, out_csv=log_csv, **thresholds)
+            self.K4 = np.asarray(K4_DEFAULT if K4 is None else K4, np.float64)
+            self.last_depth = None
+            if depth_topic is None:
+                self.create_subscription(PointCloud2, "/depth_points", self._depth_cb, 10)
+            else:
+                self.create_subscription(Image, depth_topic, self._depth_cb, 10)
+            self.anchor_pub = self.create_publisher(PoseWithCovarianceStamped, "/anchor_correction", 10)
+            self.timer = self.create_timer(1.0 / CORRELATION_TICK_HZ, self._tick)
+
+        def _depth_cb(self, msg):
+            self.last_depth = msg
+
+        def _tick(self):
+            if self.last_depth is None:
+                return
+            pose = read_pose_file()
+            if pose is None:
+                return
+            try:
+                if depth_topic is None:
+                    o = self.core.tick_cloud(pc2_msg_to_points(self.last_depth), pose, time.time())
+                else:
+                    o = self.core.tick_depth(img_msg_to_depth(self.last_depth), self.K4, pose, time.time())
+            except ValueError as e:
+                self.get_logger().warn(f"depth: {e}")
+                return
+            if o.message is None:
+                return
+            msg = PoseWithCovarianceStamped()
+            msg.header.frame_id = o.message["frame_id"]
+            msg.header.stamp = self.get_clock().now().to_msg()
+            p, q = msg.pose.pose.position, msg.pose.pose.orientation
+            p.x, p.y, p.z = o.message["position"]
+            q.x, q.y, q.z, q.w = o.message["orientation"]
+            msg.pose.covariance = o.message["covariance"]
+            self.anchor_pub.publish(msg)
+
+    return DepthCorrelationMatcher()
+
+
 def _chain_args(args):
     """the trailing (cv2, bayer, mask, orb, pixel_format) of the node factories; cv2 None = the default shim; only as far as
     the last one that is not its default, nothing when all are defaults"""
@@ -373,8 +433,9 @@ def _match_args(args, raw):
     return (*raw, *([None] * (5 - len(raw))), policy, ratio)
 
 
-def _spin(make_node, save):
-    """one node's rclpy session: spin until interrupted, then call the core's `save` method and shut down"""
+def _spin(make_node, save, log_result=False):
+    """one node's rclpy session: spin until interrupted, then call the core's `save` method and shut down; log_result: what
+    that method returns is the node's last log line"""
     import rclpy
     rclpy.init()
     node = make_node()
@@ -383,7 +444,9 @@ def _spin(make_node, save):
     except KeyboardInterrupt:
         pass
     finally:
-        getattr(node.core, save)()
+        out = getattr(node.core, save)()
+        if log_result:
+            node.get_logger().info(out)
         node.destroy_node()
         try:
             rclpy.shutdown()
@@ -444,3 +507,35 @@ def mapper_main(argv=None):
     args = ap.parse_args(argv)
     tail = () if args.depth_topic is None and args.depth_k4 is None else (args.depth_topic, args.depth_k4)
     _spin(lambda: make_depth_mapper_node(args.out_prefix, args.origin_x, args.origin_y, args.width_m, args.height_m, args.res, *tail), "save")
+
+
+# the thresholds of depth_correlation_main: flag, DepthCorrelationCore keyword, type, the reference's value
+CORRELATION_FLAGS = (("--dilate", "dilate", int, 1), ("--window-m", "window_m", float, 5.0), ("--step-m", "step_m", float, 0.2),
+                     ("--min-hits", "min_hits", int, 5), ("--min-fraction", "min_fraction", float, 0.20),
+                     ("--min-peak-ratio", "min_peak_ratio", float, 1.4), ("--consistency-m", "consistency_m", float, 5.0),
+                     ("--z-lo", "z_lo", float, 0.2), ("--z-hi", "z_hi", float, 2.0), ("--max-range", "max_range", float, 15.0),
+                     ("--min-points", "min_points", int, 100))
+
+
+def depth_correlation_args(argv=None):
+    """(teach_map, out_csv, tail, thresholds) of depth_correlation_main's command line: the reference matcher's two flags
+    (depth_correlation_matcher.py:287-291), --depth-topic / --depth-k4 as mapper_main has them, one flag per threshold; tail and
+    thresholds hold only what differs from the defaults"""
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--teach-map", required=True)
+    ap.add_argument("--out-csv", required=True)
+    ap.add_argument("--depth-topic", default=None, metavar="NAME",
+                    help="take this depth image topic instead of the /depth_points cloud")
+    ap.add_argument("--depth-k4", type=float, nargs=4, default=None, metavar=("FX", "FY", "CX", "CY"), help="camera of --depth-topic")
+    for flag, key, ty, default in CORRELATION_FLAGS:
+        ap.add_argument(flag, dest=key, type=ty, default=default, help=f"default {default}")
+    args = ap.parse_args(argv)
+    tail = () if args.depth_topic is None and args.depth_k4 is None else (args.depth_topic, args.depth_k4)
+    thresholds = {key: getattr(args, key) for _, key, _, default in CORRELATION_FLAGS if getattr(args, key) != default}
+    return args.teach_map, args.out_csv, tail, thresholds
+
+
+def depth_correlation_main(argv=None):
+    """on shutdown the node logs the reference's `Final: N publishes / M attempts` (depth_correlation_matcher.py:300-301)"""
+    teach_map, out_csv, tail, thresholds = depth_correlation_args(argv)
+    _spin(lambda: make_depth_correlation_node(teach_map, out_csv, *tail, **thresholds), "summary", log_result=True)

@@ -154,6 +154,18 @@ class StereoDepthCore:
             return mapper.integrate_stereo(T)
         return mapper.integrate_depth(self.depth(left_frame, right_frame), self.K4, T)
 
+    def correlate(self, anchor, left_frame, right_frame, base_pose7, ts):
+        """one tick of a depth-correlation anchor (depth_anchor.DepthCorrelationCore) from the pair: the dense pass, then the
+        anchor's tick_stereo on the plane where it lies -- the depth never crosses to the host; the anchor must stand on this
+        core's left Engine.  On the cv2-shaped path the depth image goes through the anchor's tick_depth.  The cloud's
+        transform is the anchor's sensor_to_base of base_pose7.  Returns the anchor's CorrelationResult."""
+        if self.engine is not None:
+            if anchor.engine is not self.engine:
+                raise ValueError("StereoDepthCore.correlate: the anchor must use this core's left engine")
+            self.engine.stereo_frame_depth(left_frame, right_frame, self.right_engine, download=False)
+            return anchor.tick_stereo(base_pose7, ts)
+        return anchor.tick_depth(self.depth(left_frame, right_frame), self.K4, base_pose7, ts)
+
     def close(self):
         """closes the right eye's Engine, which this core made; the left Engine stays the caller's"""
         if self.right_engine is not None:
