@@ -642,6 +642,23 @@ int reloc_tick_debug(reloc_ctx *ctx, int32_t *cand_ids, int32_t *n_cand, int32_t
  * is given no PnP (reloc_tick_debug reports n_matches 0 for it). */
 int reloc_tick_debug_matches(reloc_ctx *ctx, int slot, int32_t *n, int32_t *qidx, int32_t *tidx, int32_t *dist,
                              float *obj, float *img);
+/* Parity tap (tests only): the local candidate selection of a tick (M:293-302) alone, on the selected database -- the same
+ * parameter block and the same launcher as a RELOC_TICK_LOCAL tick, no ORB, scan or PnP.  path: -1 = the kernels a tick of
+ * this context would launch, 0 = the one-launch kernel (RELOC_E_ARG above 131072 records), 1 = the two stages.  ids_out: 32
+ * entries, the first *n_out are the candidates in order.  Writes the context's candidate list, count and relocating flag, as
+ * a tick's selection does, and nothing else; synchronises the context's stream. */
+int reloc_debug_local_candidates(reloc_ctx *ctx, const double base_pose[7], int path, int32_t *ids_out, int32_t *n_out);
+/* Parity tap (tests only): the whole-database count ranking (G:342-343) on counts the caller gives -- n_frames (1..8) arrays
+ * of L int32, one launch through the launcher a tick uses (the single-frame kernel at n_frames 1, the batched one above).
+ * Needs no database; its device scratch is allocated and freed inside the call.  Every count must be <= max_count (the size
+ * of the ranking's histogram: in a tick the feature capacity or the rows of the largest record); 1 <= k <= 32, min_matches
+ * >= 4, max_count <= 16254.  ids_out / counts_out: n_frames x 32, n_out: n_frames; all three are set to 0xA5A5A5A5 on the
+ * device before the launch and copied back whole, so an entry the ranking did not write shows.  skip_in != NULL: the AUTO
+ * arrangement -- frame f's n_out starts as skip_in[f] and is also the ranking's stand-down flag (non-zero: the local search
+ * found candidates, the frame is not ranked and keeps every entry as it was).  Synchronises the context's stream. */
+int reloc_debug_rank_counts(reloc_ctx *ctx, const int32_t *counts_host, int n_frames, int64_t L, int k, int64_t id_base,
+                            int min_matches, int max_count, const int32_t *skip_in, int32_t *ids_out, int32_t *counts_out,
+                            int32_t *n_out);
 /* Parity tap (tests only): the device address of THIS context's per-record counts array of its selected database --
  * reloc_db_records entries of int32, the array the whole-database scans of this context's frames write (a single scan, its
  * frame of a batched launch) and their ranking reads.  Every holder of a database has its own: an adopter made by

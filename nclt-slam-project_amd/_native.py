@@ -148,6 +148,8 @@ SIGNATURES = {
     "reloc_corr_read_map": (C.c_int, [c_ctx, P, P, P]),
     "reloc_tick_debug": (C.c_int, [c_ctx, P, P, P, P, P, P, P]),
     "reloc_tick_debug_matches": (C.c_int, [c_ctx, C.c_int, P, P, P, P, P, P]),
+    "reloc_debug_local_candidates": (C.c_int, [c_ctx, P, C.c_int, P, P]),
+    "reloc_debug_rank_counts": (C.c_int, [c_ctx, P, C.c_int, i64, C.c_int, i64, C.c_int, C.c_int, P, P, P, P]),
     "reloc_tick": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, P, C.c_int, u64, P, P, P, P, P, P]),
     "reloc_get_params": (C.c_int, [c_ctx, P]),
     "reloc_set_params": (C.c_int, [c_ctx, P]),

@@ -438,10 +438,13 @@ __global__ __launch_bounds__(TICK_BLOCK) void k_candidates_near(const double *__
 }
 
 // host side: one launch (k_candidates_near), or the two stages for very large databases / RELOC_LOCAL_TWO_STAGE=1
-static void launch_candidates_local(reloc_ctx *ctx, const TickParams &prm)
+static bool local_two_stage(const reloc_ctx *ctx, int n_records) { return n_records > NEAR_MAX_RECORDS || ctx->local_two_stage; }
+
+// two_stage: what local_two_stage() says for a tick; the parity tap reloc_debug_local_candidates may force either path
+static void launch_candidates_local(reloc_ctx *ctx, const TickParams &prm, bool two_stage)
 {
     const DbArena &db = ctx_db(ctx);
-    if (prm.n_records <= NEAR_MAX_RECORDS && !ctx->local_two_stage) {
+    if (!two_stage) {
         hipLaunchKernelGGL(k_candidates_near, dim3(1), dim3(TICK_BLOCK), 0, ctx->stream, db.xy_heading, prm, ctx->tick.cand_ids,
                            ctx->tick.cand_n, ctx->tick.flags);
         return;
@@ -671,23 +674,37 @@ static FinalFrame final_frame(const reloc_ctx *c, const double base_pose[7], Tic
     return F;
 }
 
-// ranking of the counts: the k best (count, id + id_base) of every frame
-static void launch_topk_counts(reloc_ctx *const *ctxs, int n, const TopkBatch &b, int k, int id_base)
+// ranking of the counts: the k best (count, id + id_base) of every frame.  TopkShape: what the contexts of a call fix --
+// counts per frame, the largest count a record can hold (the histogram's size; a larger count is outside the contract) and
+// the eligibility gate.  launch_topk_shape: the LDS size and the launch, for the tick and for the parity tap
+// reloc_debug_rank_counts alike.
+struct TopkShape { int L, max_count, min_matches; };
+constexpr size_t TOPK_HIST_LDS_MAX = 64 * 1024 - 512;      // dynamic LDS of a launch without an opt-in, less the kernel's own
+
+static TopkShape topk_shape(const reloc_ctx *c0)
 {
-    reloc_ctx *c0 = ctxs[0];
     const DbArena &db = ctx_db(c0);
-    const int L = (int)db.records;
     // a count cannot exceed the features of a frame nor, a count of mutual pairs, the rows of the largest record
     const int max_count = !c0->match.ratio_on() && db.max_rows < c0->max_feat ? db.max_rows : c0->max_feat;
-    const size_t lds = (size_t)(max_count + 2) * sizeof(int);
+    return TopkShape{(int)db.records, max_count, c0->prm.min_matches};
+}
+
+static void launch_topk_shape(hipStream_t stream, int n, const TopkBatch &b, const TopkShape &s, int k, int id_base)
+{
+    const size_t lds = (size_t)(s.max_count + 2) * sizeof(int);
     if (n == 1) {
         const TopkFrame &F = b.f[0];
-        hipLaunchKernelGGL(k_topk_counts, dim3(1), dim3(TOPK_HIST_THREADS), lds, c0->stream, F.counts, L, k, id_base, c0->prm.min_matches,
-                           max_count, F.out_ids, F.out_counts, F.out_n, F.skip_if, F.relocating, F.f_count, F.out_nfeat);
+        hipLaunchKernelGGL(k_topk_counts, dim3(1), dim3(TOPK_HIST_THREADS), lds, stream, F.counts, s.L, k, id_base, s.min_matches,
+                           s.max_count, F.out_ids, F.out_counts, F.out_n, F.skip_if, F.relocating, F.f_count, F.out_nfeat);
     } else {
-        hipLaunchKernelGGL(k_topk_counts_batch, dim3(n), dim3(TOPK_HIST_THREADS), lds, c0->stream, b, L, k, id_base, c0->prm.min_matches,
-                           max_count);
+        hipLaunchKernelGGL(k_topk_counts_batch, dim3(n), dim3(TOPK_HIST_THREADS), lds, stream, b, s.L, k, id_base, s.min_matches,
+                           s.max_count);
     }
+}
+
+static void launch_topk_counts(reloc_ctx *const *ctxs, int n, const TopkBatch &b, int k, int id_base)
+{
+    launch_topk_shape(ctxs[0]->stream, n, b, topk_shape(ctxs[0]), k, id_base);
 }
 
 // gates, pose composition and the result records; prm carries what the frames share (frame 0's base pose)
@@ -874,7 +891,10 @@ static int tick_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *imgs, i
     int rc;
     if ((rc = orb_run(ctxs, n, imgs, w, h, w * image_chain_frame_bpp(c0), true, order, c0->prm.nfeatures, latency))) return rc;
     if (mode != RELOC_TICK_GLOBAL)
-        for (int f = 0; f < n; ++f) launch_candidates_local(ctxs[f], make_tick_params(ctxs[f], base_poses + 7 * f, mode, -1));
+        for (int f = 0; f < n; ++f) {
+            const TickParams prm = make_tick_params(ctxs[f], base_poses + 7 * f, mode, -1);
+            launch_candidates_local(ctxs[f], prm, local_two_stage(ctxs[f], prm.n_records));
+        }
     if (mode != RELOC_TICK_LOCAL) {
         if ((rc = scan_counts(ctxs, n, base_poses, mode == RELOC_TICK_AUTO))) return rc;
         TopkBatch b;
@@ -1148,6 +1168,70 @@ RELOC_API int reloc_tick_debug_matches(reloc_ctx *ctx, int slot, int32_t *n, int
     if (dist) HIP_TRY(hipMemcpyAsync(dist, ctx->tick.m_dist + at, k * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (obj) HIP_TRY(hipMemcpyAsync(obj, ctx->tick.p_obj + 3 * at, k * 12, hipMemcpyDeviceToHost, ctx->stream));
     if (img) HIP_TRY(hipMemcpyAsync(img, ctx->tick.p_img + 2 * at, k * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return RELOC_OK;
+}
+
+// ---- parity taps of the candidate selection (tests only) --------------------------------------------------------------
+RELOC_API int reloc_debug_local_candidates(reloc_ctx *ctx, const double base_pose[7], int path, int32_t *ids_out, int32_t *n_out)
+{
+    ARG_CHECK_CTX(ctx, base_pose && ids_out && n_out && path >= -1 && path <= 1, "reloc_debug_local_candidates");
+    if (!db_ready(ctx)) { reloc_set_error("no database uploaded"); return RELOC_E_STATE; }
+    const TickParams prm = make_tick_params(ctx, base_pose, RELOC_TICK_LOCAL, -1);
+    ARG_CHECK(path != 0 || prm.n_records <= NEAR_MAX_RECORDS,
+              "reloc_debug_local_candidates: the one-launch kernel takes at most 131072 records");
+    launch_candidates_local(ctx, prm, path < 0 ? local_two_stage(ctx, prm.n_records) : path == 1);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(n_out, ctx->tick.cand_n, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ids_out, ctx->tick.cand_ids, sizeof(int32_t) * MAX_CAND, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return RELOC_OK;
+}
+
+namespace {
+// the tap's own device scratch: freed on every way out of the call
+struct RankScratch {
+    int32_t *counts = nullptr, *ids = nullptr, *cnt = nullptr, *n = nullptr, *flags = nullptr;
+    ~RankScratch() { for (int32_t *p : {counts, ids, cnt, n, flags}) if (p) (void)hipFree(p); }
+};
+}
+
+RELOC_API int reloc_debug_rank_counts(reloc_ctx *ctx, const int32_t *counts_host, int n_frames, int64_t L, int k, int64_t id_base,
+                                      int min_matches, int max_count, const int32_t *skip_in, int32_t *ids_out, int32_t *counts_out,
+                                      int32_t *n_out)
+{
+    ARG_CHECK_CTX(ctx, counts_host && ids_out && counts_out && n_out && n_frames >= 1 && n_frames <= RELOC_BATCH_MAX,
+                  "reloc_debug_rank_counts");
+    ARG_CHECK(k >= 1 && k <= MAX_CAND && L >= 1 && L <= MAX_DB_RECORDS && id_base >= 0 && id_base + L <= 0x7fffffff &&
+              min_matches >= RELOC_PNP_SAMPLE && max_count >= 0 && ((size_t)max_count + 2) * sizeof(int) <= TOPK_HIST_LDS_MAX,
+              "reloc_debug_rank_counts: 1 <= k <= 32, 1 <= L <= 1048575, id_base + L < 2^31, min_matches >= 4, max_count <= 16254");
+    RankScratch s;
+    const size_t slots = (size_t)n_frames * MAX_CAND * sizeof(int32_t), cbytes = (size_t)n_frames * (size_t)L * sizeof(int32_t);
+    HIP_TRY(hipMalloc((void **)&s.counts, cbytes));
+    HIP_TRY(hipMalloc((void **)&s.ids, slots));
+    HIP_TRY(hipMalloc((void **)&s.cnt, slots));
+    HIP_TRY(hipMalloc((void **)&s.n, RELOC_BATCH_MAX * sizeof(int32_t)));
+    HIP_TRY(hipMalloc((void **)&s.flags, RELOC_BATCH_MAX * sizeof(int32_t)));
+    HIP_TRY(hipMemcpyAsync(s.counts, counts_host, cbytes, hipMemcpyHostToDevice, ctx->stream));
+    // poison: an entry the ranking does not write comes back as 0xA5A5A5A5
+    HIP_TRY(hipMemsetAsync(s.ids, 0xA5, slots, ctx->stream));
+    HIP_TRY(hipMemsetAsync(s.cnt, 0xA5, slots, ctx->stream));
+    HIP_TRY(hipMemsetAsync(s.n, 0xA5, RELOC_BATCH_MAX * sizeof(int32_t), ctx->stream));
+    HIP_TRY(hipMemsetAsync(s.flags, 0xA5, RELOC_BATCH_MAX * sizeof(int32_t), ctx->stream));
+    // skip_in given: the AUTO arrangement -- out_n holds what the local search left (0: nothing found) and is the skip_if too
+    if (skip_in) HIP_TRY(hipMemcpyAsync(s.n, skip_in, (size_t)n_frames * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    TopkBatch b;
+    for (int f = 0; f < RELOC_BATCH_MAX; ++f) {
+        const int g = f < n_frames ? f : 0;
+        TopkFrame &F = b.f[f];
+        F.counts = s.counts + (size_t)g * (size_t)L; F.out_ids = s.ids + g * MAX_CAND; F.out_counts = s.cnt + g * MAX_CAND;
+        F.out_n = s.n + g; F.skip_if = skip_in ? s.n + g : nullptr; F.relocating = s.flags + g; F.f_count = nullptr; F.out_nfeat = nullptr;
+    }
+    launch_topk_shape(ctx->stream, n_frames, b, TopkShape{(int)L, max_count, min_matches}, k, (int)id_base);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(ids_out, s.ids, slots, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(counts_out, s.cnt, slots, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(n_out, s.n, (size_t)n_frames * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return RELOC_OK;
 }

@@ -42,6 +42,7 @@ def match_policy_setting(policy, ratio):
 
 
 MAX_CAND = 32           # candidates of one tick (MAX_CAND of csrc/reloc_internal.h): the longest top-k / candidate list
+DEBUG_POISON = -1515870811      # int32 0xA5A5A5A5: what debug_rank_counts leaves where the ranking wrote nothing
 
 # The 96-byte result record of a tick (include/reloc.h at reloc_tick_result_dev / reloc_tick_result_to; struct TickResult
 # of csrc/reloc_internal.h, whose static_asserts hold these offsets).  `seq`: the tick's stamp, in HOST records only.
@@ -1070,6 +1071,29 @@ class Engine:
         self._api.reloc_tick_debug_matches(self._ctx, int(slot), n, qi, ti, dd, obj, img)
         k = n.value
         return dict(n=k, qidx=qi[:k].copy(), tidx=ti[:k].copy(), dist=dd[:k].copy(), obj=obj[:k].copy(), img=img[:k].copy())
+
+    def debug_local_candidates(self, base_pose, path: int = -1) -> np.ndarray:
+        """parity tap: the local candidate list a tick at base_pose would solve against, by the selection alone
+        (reloc_debug_local_candidates; synchronises).  path: -1 the context's choice, 0 the one-launch kernel, 1 two stages"""
+        bp = np.ascontiguousarray(base_pose, np.float64).reshape(7)
+        ids = np.zeros(MAX_CAND, np.int32)
+        n = i32()
+        self._api.reloc_debug_local_candidates(self._ctx, bp, int(path), ids, n)
+        return ids[: n.value].copy()
+
+    def debug_rank_counts(self, counts, k: int, id_base: int = 0, min_matches: int = 10, max_count: int = None, skip=None):
+        """parity tap: the whole-database ranking on given counts (reloc_debug_rank_counts; synchronises).  counts: (F, L) or
+        (L,) int32, F <= 8 frames ranked by one launch; max_count defaults to the largest count.  skip: F values, non-zero =
+        that frame stands down (AUTO).  Returns ids (F, 32), counts (F, 32), n (F,) as the device left them: entries the
+        ranking did not write hold DEBUG_POISON."""
+        c = np.ascontiguousarray(counts, np.int32)
+        c = c.reshape(1, -1) if c.ndim == 1 else c
+        F, L = c.shape
+        ids = np.zeros((F, MAX_CAND), np.int32); cnt = np.zeros((F, MAX_CAND), np.int32); n = np.zeros(F, np.int32)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.int32).reshape(F)
+        self._api.reloc_debug_rank_counts(self._ctx, c, F, L, int(k), int(id_base), int(min_matches),
+                                          int(c.max() if max_count is None else max_count), sk, ids, cnt, n)
+        return ids, cnt, n
 
     def tick(self, img, base_pose, order_rgb=False, global_reloc=False, seed=0):
         """img: (H, W, 3), the (H, W) mosaic with the Bayer stage on, or a frame of the pixel format"""

@@ -127,8 +127,11 @@ def test_every_slot_carries_the_engines_parameters(engine, small):
 
 
 def test_topk_when_one_thread_owns_most_winners(engine, oracle):
-    """k_topk_counts deals record i to thread i mod 256 and every thread keeps its four best in registers;
-    25 winners that all fall on ONE thread force the refill path (rescan below the last key taken)."""
+    """25 winners at stride 256 (record 7 + 256 i) among 6664 records, through the scan and k_topk_counts' histogram
+    selection: every thread of its block owns a contiguous id range, so the winners fall one to a thread, 25 threads
+    apart, and all lie above the threshold count.  (The name dates from a ranking kernel that dealt record i to thread
+    i mod 256 and kept four keys per thread; that scheme, block_topk with its refill, serves the local search only
+    and is tested in tests/test_gpu_candidates.py.)"""
     rng = np.random.default_rng(77)
     img = synth.textured_frame(rng, 640, 480)
     feat = engine.orb_detect_compute(engine.gray(img), 500)
