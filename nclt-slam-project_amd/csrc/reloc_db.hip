@@ -5,7 +5,7 @@
 // unit of ownership.  There is one way into a slot -- a complete arena, built aside, is assigned to it -- and one way out,
 // db_arena_release.  Nothing is published in the ctx before every allocation and copy of an operation has succeeded: a
 // failed upload leaves "no database" (records == 0), a failed reserve / append leaves the database as it was.
-// The scans of a database are in reloc_match.hip, the appending kernel of the fused tick in reloc_record.hip.
+// The scans of a database are in reloc_scan.hip, reloc_scan_rows.hip and reloc_ratio.hip, the appending kernel of the fused tick in reloc_record.hip.
 #include <new>
 
 #include "reloc_internal.h"

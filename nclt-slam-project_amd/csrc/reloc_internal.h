@@ -529,7 +529,7 @@ struct reloc_ctx {
     CorrState corr;                  // reloc_correlation.hip
     int scan_gens = 0;               // RELOC_SCAN_GENS (developer switch), read once at creation: n > 0 = single whole-database
                                      // scans in the form of batched ones (n generations of row budgets + sweepers, launch_db_count)
-    uint32_t *scan_ticket = nullptr; // SCAN_TICKET_WORDS counters of the whole-database scans (scan_alloc, reloc_match.hip)
+    uint32_t *scan_ticket = nullptr; // SCAN_TICKET_WORDS counters of the whole-database scans (scan_alloc, reloc_scan.hip)
 
     // ---- database: two arenas; db_sel names the selected one (ctx_db below), reloc_db_select only changes db_sel ----
     DbArena db_slot[2];
@@ -631,7 +631,7 @@ int launch_db_scan_batch(reloc_ctx *const *ctxs, int n, const double *q, double 
 // The same scans under RELOC_MATCH_RATIO: counts[record] = Lowe survivors of every context's features against the record
 // (k_db_ratio), 0 for records of fewer than min_matches rows.  base_poses: n x 7 (heading mask) or NULL.
 int launch_db_ratio_scan(reloc_ctx *const *ctxs, int n, const double *base_poses, double cos_tol, bool auto_mode);
-// the emit pass of a tick: match lists, with their 3-D / 2-D pairs, of every context's candidate records (reloc_match.hip)
+// the emit pass of a tick: match lists, with their 3-D / 2-D pairs, of every context's candidate records (reloc_scan.hip)
 int launch_tick_emit(reloc_ctx *const *ctxs, int n, bool latency);
 // the list lengths of a context's candidates as PnP takes them (see TickState::m_n)
 static inline const int32_t *tick_pnp_lengths(const reloc_ctx *c) { return c->tick.m_n + (c->match.ratio_on() ? MAX_CAND : 0); }
@@ -643,7 +643,7 @@ inline bool db_ready(const reloc_ctx *ctx)
     const DbArena &db = ctx_db(ctx);
     return db.desc && db.off && db.pose && db.xy_heading && db.counts && db.records > 0;
 }
-// the fixed blocks of a new context, each stage's by its own file: ORB (reloc_orb.hip), scan counters (reloc_match.hip), tick /
+// the fixed blocks of a new context, each stage's by its own file: ORB (reloc_orb.hip), scan counters (reloc_scan.hip), tick /
 // match / PnP scratch with the pinned result record (reloc_tick.hip; tick_release lets go of that record)
 int orb_alloc(reloc_ctx *ctx);
 int scan_alloc(reloc_ctx *ctx);

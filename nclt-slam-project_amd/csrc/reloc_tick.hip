@@ -6,7 +6,7 @@
 // G:424):
 //   ORB (reloc_orb.hip) -> candidates (local: nearest 15 by VIO distance, radius 8 m, heading 90 deg,
 //   first 5;  global: mutual-match count of every heading-compatible record, top 25) ->
-//   mutual matches of each candidate (reloc_match.hip, emit mode) -> gather 3-D/2-D pairs ->
+//   mutual matches of each candidate (reloc_scan.hip, emit mode) -> gather 3-D/2-D pairs ->
 //   PnP-RANSAC batch (reloc_pnp.hip) -> gates, pose composition, best by inliers, consistency.
 // "Mutual" is the default match policy; under RELOC_MATCH_RATIO (reloc_set_match_policy, include/reloc_spec.h "MATCH POLICY")
 // the count and the lists are those of knnMatch(current, record, k=2) + Lowe test: scan_counts() and launch_tick_emit() branch.

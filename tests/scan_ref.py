@@ -7,7 +7,7 @@ import numpy as np
 
 B2C_ROW0 = (0.0, -1.0, 0.0)              # first row of the default base_link -> camera rotation (CameraModel::b2c_R)
 MAX_REC_ROWS = 4096                      # csrc/reloc_internal.h
-SQ_MAX_ROWS = 1024                       # the lane-per-row kernel's largest record (csrc/reloc_match.hip)
+SQ_MAX_ROWS = 1024                       # the lane-per-row kernel's largest record (csrc/reloc_hamming.h)
 BATCH_MAX = 8                            # RELOC_BATCH_MAX
 WG_PER_CU = 4                            # resident scan workgroups per CU (CountPlan::init)
 

@@ -1,4 +1,4 @@
-"""GPU parity of the counting scan's two column-merge forms (db_count_body / scan_chunk of csrc/reloc_match.hip): records of at
+"""GPU parity of the counting scan's two column-merge forms (db_count_body / scan_chunk of csrc/reloc_scan.hip): records of at
 most 64 rows against one column block leave their column minima as raw 16-bit keys in a slice per wave and wave 0 resolves
 them ("sliced"); every other record merges into the shared buffer with ds_min_u32, double-buffered or cleared ("shared").
 Both forms live in one launch and a workgroup changes between them record by record.

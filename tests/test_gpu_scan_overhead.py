@@ -1,5 +1,5 @@
 """GPU parity of the counting scan's bookkeeping around the distance chains: the LDS key helpers (row_entry / row_key /
-col_key of csrc/reloc_match.hip), the wave-owned per-record work of db_count_body (the buffer clear, the mutual resolution of
+col_key of csrc/reloc_scan.hip), the wave-owned per-record work of db_count_body (the buffer clear, the mutual resolution of
 rows 64 w .. by wave w, the ticket deal in the last wave) and the emit pass that shares scan_chunk.
 
 Everything goes through the C-ABI and is compared integer-exact with the oracle: oracle.db_match_counts for the counts,
