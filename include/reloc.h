@@ -468,7 +468,8 @@ int reloc_stereo_debug(reloc_ctx *ctx, uint16_t *depth_mm, float *disparity, uin
 /* ---- dense stereo depth (include/reloc_spec.h, "STEREO, dense") ----------------------------------- */
 /* The same matcher at every integer pixel of the working frame: a depth image for everything that takes one
  * (reloc_depth_points, the depth-image form of reloc_record_frame, a log).  Three planes of the working-frame size with
- * dense rows: depth_mm uint16 (0 = no depth), disparity float32 (0 where status != 0), status uint8 (the seven codes above).
+ * dense rows: depth_mm uint16 (0 = no depth), disparity float32 (0 where status != 0), status uint8 (the seven codes above; an eighth,
+ * RELOC_STEREO_SPECKLE, only from a pass with the speckle stage on, below).
  * The plane at (rint x, rint y) is what reloc_stereo_depth returns for keypoint (x, y).  The buffers are taken on the first
  * dense call of a context; a context that never makes one allocates and launches nothing of it.
  * reloc_stereo_depth_image is the dense twin of reloc_stereo_depth: two gray planes of w x h (w, h >= 11, within the
@@ -493,6 +494,21 @@ int reloc_stereo_frame_points(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *i
  * max_w x max_h, or of the pass's size; any pointer may be NULL).  RELOC_E_STATE before the first pass.  Synchronises the
  * context's stream. */
 int reloc_stereo_dense_debug(reloc_ctx *ctx, uint16_t *depth_mm, float *disparity, uint8_t *status, int32_t *w, int32_t *h);
+
+/* ---- speckle filter (include/reloc_spec.h, "STEREO, speckle") -------------------------------------- */
+/* OpenCV's filterSpeckles on an int16 plane of w x h, rows stride ELEMENTS apart, in place: every pixel of a 4-connected
+ * component (valid = differs from new_val; joined = |a - b| <= max_diff) of at most max_speckle_size pixels becomes new_val;
+ * the padding of a row is neither read nor written.  Host pointer; synchronous.  RELOC_E_ARG for w or h < 1, stride < w, a
+ * negative limit or a new_val outside int16; RELOC_E_CAPACITY beyond the context's max_w x max_h. */
+int reloc_filter_speckles(reloc_ctx *ctx, int16_t *img, int w, int h, int stride, int new_val, int max_speckle_size, int max_diff);
+/* The speckle stage of the dense pass, a persistent setting of the LEFT context: window = the component size limit in pixels,
+ * 0 = off (a new context); range in whole disparities, 0..RELOC_STEREO_SPECKLE_RANGE_MAX.  Independent of reloc_set_stereo.
+ * It applies to every dense pass that runs with the context's settings (reloc_stereo_frame_depth, reloc_stereo_frame_points,
+ * and so to what reloc_occ_integrate_stereo_dev, reloc_corr_match_stereo_dev and reloc_stereo_dense_debug read): a removed
+ * pixel has status RELOC_STEREO_SPECKLE, depth_mm 0 and disparity 0.  reloc_stereo_depth_image takes its parameters
+ * explicitly and is never filtered.  With window 0 a pass launches what it always launched. */
+int reloc_set_stereo_speckle(reloc_ctx *ctx, int window, int range);
+int reloc_get_stereo_speckle(reloc_ctx *ctx, int32_t *window, int32_t *range);
 
 /* ---- teach-time occupancy map (include/reloc_spec.h, "OCCUPANCY") ---------------------------------- */
 /* The log-odds grid of the reference's teach_run_depth_mapper.py: every frame's obstacle cloud is taken into the map frame,

@@ -357,7 +357,21 @@
  *              is |dR(v, u - d*) - d*| > 1.  The members of that search are exactly the defined entries of the volume on the
  *              diagonal u - d = xr (xr >= R holds wherever step 6 is reached), those of pixels that fail step 2 included.
  * A depth image made this way serves everything that takes one: the obstacle cloud (every step-th pixel, 0.3 to 10 m), the
- * depth-image form of the recorder with its 3 x 3 variance gate, a log. */
+ * depth-image form of the recorder with its 3 x 3 variance gate, a log.
+ *
+ * STEREO, speckle: an optional stage behind steps 1 to 8 of the dense pass, OpenCV's filterSpeckles as StereoBM / StereoSGBM
+ * apply it (speckleWindowSize, speckleRange).  Two settings: speckle_window, the component size limit in pixels, 0 = off
+ * (the default); speckle_range in whole disparities, 0..RELOC_STEREO_SPECKLE_RANGE_MAX, default 1.
+ *   filter     filterSpeckles(img, newVal, maxSpeckleSize, maxDiff) on a 2-D int16 plane: a pixel is valid when it differs
+ *              from newVal; two 4-neighbours are joined when both are valid and |a - b| <= maxDiff, the difference taken in
+ *              int32; a component is a connected component of that relation (transitive through chains, never diagonal);
+ *              every pixel of a component of at most maxSpeckleSize pixels becomes newVal, nothing else changes.  OpenCV
+ *              states it as a raster-order flood fill; the result does not depend on the order.
+ *   quantise   q = (int16)rint(disparity * 16.0f) where status is 0 (the product is exact, rint rounds half to even; every
+ *              such q is positive), q = -16 elsewhere -- status 6 included.
+ *   stage      the filter with newVal = -16, maxSpeckleSize = speckle_window, maxDiff = 16 * speckle_range.  A pixel of
+ *              status 0 that it removes gets status 7, depth_mm 0 and disparity 0; no other pixel changes.
+ * tests/speckle_ref.py restates filter and stage. */
 #define RELOC_STEREO_R                 5
 #define RELOC_STEREO_MIN_DISPARITY_MAX 1024
 #define RELOC_STEREO_NUM_DISP_MIN      8
@@ -372,6 +386,8 @@
 #define RELOC_STEREO_UNIQUENESS  4
 #define RELOC_STEREO_LR          5
 #define RELOC_STEREO_FAR         6
+#define RELOC_STEREO_SPECKLE     7
+#define RELOC_STEREO_SPECKLE_RANGE_MAX 255
 
 /* OCCUPANCY: the teach-time occupancy map of the reference's teach_run_depth_mapper.py (D below): a 2-D log-odds grid that
  * the obstacle cloud of a frame is ray-traced into, written as .pgm + .yaml for the repeat run's static costmap layer.

@@ -134,6 +134,9 @@ SIGNATURES = {
     "reloc_stereo_frame_depth": (C.c_int, [c_ctx, c_ctx, P, P, C.c_int, C.c_int, C.c_int, P, P, P]),
     "reloc_stereo_frame_points": (C.c_int, [c_ctx, c_ctx, P, P, C.c_int, C.c_int, C.c_int, C.c_int, f32, f32, P, P]),
     "reloc_stereo_dense_debug": (C.c_int, [c_ctx, P, P, P, P, P]),
+    "reloc_filter_speckles": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "reloc_set_stereo_speckle": (C.c_int, [c_ctx, C.c_int, C.c_int]),
+    "reloc_get_stereo_speckle": (C.c_int, [c_ctx, P, P]),
     "reloc_occ_configure": (C.c_int, [c_ctx, f64, f64, f64, C.c_int, C.c_int, f64, f64, C.c_int]),
     "reloc_occ_integrate_points": (C.c_int, [c_ctx, P, C.c_int, P, P]),
     "reloc_occ_integrate_depth": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, C.c_int, P, f32, f32, P, P]),

@@ -396,6 +396,9 @@ struct StereoState {
         uint8_t *left = nullptr;         // left eye's gray plane where its chain has no stage on (dense rows)
         int w = 0, h = 0;                // the last dense pass (reloc_stereo_dense_debug); 0 = none yet
     } dense;
+    // The speckle stage behind the dense pass ("STEREO, speckle"; reloc_set_stereo_speckle, a setting of its own): window 0 = off,
+    // the default.  It labels in the dense block's best plane, which k_stereo_dense_finish has read by then: no memory of its own.
+    int speckle_window = 0, speckle_range = 1;
     bool on() const { return baseline > 0.0; }
     // the settings, no buffer: reloc_set_stereo returns at once where nothing changes
     bool same(const StereoState &o) const
@@ -689,5 +692,8 @@ void corr_release(reloc_ctx *ctx);
 // chains, each on its own stream, no ORB; then k_stereo_dense and k_stereo_dense_finish on ctx's stream into ctx->stereo.dense
 // (mm: dense rows of *ww uint16).  Checks stereo on, right != ctx, capacity and the chains' agreement.
 int stereo_dense_frame(reloc_ctx *ctx, reloc_ctx *right, int w, int h, int order, int *ww, int *wh);
+// the speckle stage on the w x h planes of ctx's dense pass with ctx's speckle setting (window > 0), on ctx's stream
+// (reloc_speckle.hip)
+int stereo_speckle_launch(reloc_ctx *ctx, int w, int h);
 // PnP-RANSAC of every context's candidates with the matcher parameters of ctxs[0]; seeds: one per frame, or NULL (reloc_pnp.hip)
 int pnp_run_candidates(reloc_ctx *const *ctxs, int n, const uint64_t *seeds, bool latency);

@@ -592,8 +592,10 @@ static int stereo_dense_alloc(reloc_ctx *ctx)
     return RELOC_OK;
 }
 
-// both kernels on ctx's stream, into ctx's dense planes (dense rows of p.w); the planes of the eyes are device pointers
-static int stereo_dense_launch(reloc_ctx *ctx, const uint8_t *left, int lstride, const uint8_t *right, int rstride, const StereoParams &p)
+// both kernels on ctx's stream, into ctx's dense planes (dense rows of p.w); the planes of the eyes are device pointers;
+// speckle: then the speckle stage with ctx's setting ("STEREO, speckle"), inside the same stopwatch bracket
+static int stereo_dense_launch(reloc_ctx *ctx, const uint8_t *left, int lstride, const uint8_t *right, int rstride, const StereoParams &p,
+                               bool speckle)
 {
     StereoState::Dense &d = ctx->stereo.dense;
     const int64_t px = (int64_t)p.w * p.h;
@@ -605,9 +607,11 @@ static int stereo_dense_launch(reloc_ctx *ctx, const uint8_t *left, int lstride,
                        d.best, d.status);
     hipLaunchKernelGGL(k_stereo_dense_finish, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, ctx->stream, p, d.rmap, d.best,
                        d.status, d.mm, d.disp);
+    const int filtered = speckle ? stereo_speckle_launch(ctx, p.w, p.h) : (int)RELOC_OK;
     reloc_prof_end(ctx, RELOC_PROF_STEREO_DENSE);
     HIP_TRY(reset);
     HIP_TRY(hipGetLastError());
+    if (filtered) return filtered;
     d.w = p.w; d.h = p.h;
     return RELOC_OK;
 }
@@ -629,7 +633,7 @@ RELOC_API int reloc_stereo_depth_image(reloc_ctx *ctx, const uint8_t *left, cons
     st.upload(dl, left, bytes);
     st.upload(dr, right, bytes);
     const StereoParams p = {fx, baseline_m, w, h, min_disparity, num_disparities, uniqueness, lr_check};
-    st.run([&] { return stereo_dense_launch(ctx, dl, stride, dr, stride, p); });
+    st.run([&] { return stereo_dense_launch(ctx, dl, stride, dr, stride, p, false); });
     st.download(depth_mm, d.mm, px * 2);
     if (disparity) st.download(disparity, d.disp, px * 4);
     if (status) st.download(status, d.status, px);
@@ -645,7 +649,7 @@ int stereo_dense_frame(reloc_ctx *ctx, reloc_ctx *right, int w, int h, int order
     int pstride[2];
     if (int rc = stereo_gray_planes(ctx, right, ctx->frame_img, right->frame_img, w, h, *ww, *wh, order, plane, pstride)) return rc;
     const StereoParams p = {ctx->cam.K4[0], s.baseline, *ww, *wh, s.min_disp, s.num_disp, s.uniq, s.lr};
-    return stereo_dense_launch(ctx, plane[0], pstride[0], plane[1], pstride[1], p);
+    return stereo_dense_launch(ctx, plane[0], pstride[0], plane[1], pstride[1], p, s.speckle_window > 0);
 }
 
 RELOC_API int reloc_stereo_frame_depth(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img, const uint8_t *img_right, int w, int h,

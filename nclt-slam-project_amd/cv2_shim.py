@@ -770,6 +770,37 @@ class Cv2Shim:
         m1, m2 = initUndistortRectifyMap(cameraMatrix, distCoeffs, None, newK, (img.shape[1], img.shape[0]), CV_16SC2)
         return self.remap(img, m1, m2, INTER_LINEAR, dst=dst)
 
+    def filterSpeckles(self, img, newVal, maxSpeckleSize, maxDiff, buf=None):
+        """cv2.filterSpeckles: a writable (H, W) int16 or uint8 array, filtered in place (rows may be strided); every pixel of
+        a 4-connected component (valid = differs from newVal, joined = |a - b| <= maxDiff) of at most maxSpeckleSize pixels
+        becomes newVal.  Returns (img, buf) with the same array; buf is OpenCV's scratch and passes through unused"""
+        if not isinstance(img, np.ndarray) or img.dtype not in (np.int16, np.uint8) or img.ndim != 2 or img.size == 0:
+            raise error("filterSpeckles: expected a non-empty (H, W) int16 or uint8 array (CV_16SC1, CV_8UC1)")
+        if not img.flags.writeable:
+            raise error("filterSpeckles: img is filtered in place and must be writable")
+        try:
+            if int(newVal) != newVal or int(maxSpeckleSize) != maxSpeckleSize:
+                raise ValueError
+            new_val, size, diff = int(newVal), int(maxSpeckleSize), int(float(maxDiff))       # maxDiff: a C cast, toward zero
+        except (TypeError, ValueError, OverflowError) as e:
+            raise error("filterSpeckles: newVal and maxSpeckleSize must be integers, maxDiff a finite number") from e
+        info = np.iinfo(img.dtype)
+        if not info.min <= new_val <= info.max:
+            raise error(f"filterSpeckles: newVal {new_val} does not fit the image's type ({img.dtype})")
+        if size < 0 or diff < 0:
+            raise error("filterSpeckles: maxSpeckleSize and maxDiff must be >= 0")
+        fn = self._backend("filter_speckles", "filterSpeckles")
+        try:
+            if img.dtype == np.int16:
+                fn(img, new_val, size, diff)
+            else:                                  # through int16 on the host: exact both ways
+                plane = img.astype(np.int16)
+                fn(plane, new_val, size, diff)
+                img[...] = plane.astype(np.uint8)
+        except RelocError as e:
+            raise error(str(e)) from e
+        return img, buf
+
     def ORB_create(self, nfeatures=500, **kwargs):
         """cv2.ORB_create: nlevels (1..8), scaleFactor (1.01..2.0), fastThreshold (1..254) and scoreType (ORB_HARRIS_SCORE,
         ORB_FAST_SCORE) are settings (include/reloc_spec.h "ORB PARAMS") on a backend whose orb_detect_compute takes orb=;
@@ -923,6 +954,10 @@ def undistort(*a, **kw):
 
 def resize(*a, **kw):
     return default_shim().resize(*a, **kw)
+
+
+def filterSpeckles(*a, **kw):
+    return default_shim().filterSpeckles(*a, **kw)
 
 
 def ORB_create(nfeatures=500, **kw):

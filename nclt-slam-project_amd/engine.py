@@ -675,6 +675,44 @@ class Engine:
         k, shape = w.value * h.value, (h.value, w.value)
         return mm[:k].reshape(shape).copy(), disp[:k].reshape(shape).copy(), st[:k].reshape(shape).copy()
 
+    # ------------------------------------------------------------------ speckle filter (reloc_spec.h "STEREO, speckle")
+    def filter_speckles(self, img: np.ndarray, new_val: int, max_speckle_size: int, max_diff: int) -> np.ndarray:
+        """OpenCV's filterSpeckles on a writable (H, W) int16 array, in place (reloc_filter_speckles): every pixel of a
+        4-connected component (valid = differs from new_val, joined = |a - b| <= max_diff) of at most max_speckle_size pixels
+        becomes new_val.  Rows may be strided (a view of a wider array, whose padding stays untouched); returns img"""
+        if not isinstance(img, np.ndarray) or img.dtype != np.int16 or img.ndim != 2 or img.size == 0 or not img.flags.writeable:
+            raise N.RelocError("filter_speckles: expected a writable, non-empty (H, W) int16 array")
+        for name, v in (("new_val", new_val), ("max_speckle_size", max_speckle_size), ("max_diff", max_diff)):
+            if int(v) != v:
+                raise N.RelocError(f"filter_speckles: {name} must be an integer")
+        if not -32768 <= int(new_val) <= 32767:
+            raise N.RelocError("filter_speckles: new_val must fit int16")
+        if int(max_speckle_size) < 0 or int(max_diff) < 0:
+            raise N.RelocError("filter_speckles: max_speckle_size and max_diff must be >= 0")
+        h, w = img.shape
+        limit, diff = min(int(max_speckle_size), 2 ** 31 - 1), min(int(max_diff), 65536)      # above every size / difference
+        if img.strides[1] == 2 and img.strides[0] % 2 == 0 and (h == 1 or img.strides[0] >= 2 * w):
+            self._api.reloc_filter_speckles(self._ctx, img.ctypes.data, w, h, w if h == 1 else img.strides[0] // 2, int(new_val), limit, diff)
+        else:
+            dense = np.ascontiguousarray(img)
+            self._api.reloc_filter_speckles(self._ctx, dense, w, h, w, int(new_val), limit, diff)
+            img[...] = dense
+        return img
+
+    def set_stereo_speckle(self, window: int = 0, range: int = 1):
+        """the speckle stage of this (the left eye's) engine's dense stereo passes (reloc_set_stereo_speckle): components of
+        at most `window` pixels, joined within `range` whole disparities, lose their depth (status 7); window 0 turns it off"""
+        for name, v in (("window", window), ("range", range)):
+            if int(v) != v:
+                raise N.RelocError(f"set_stereo_speckle: {name} must be an integer")
+        self._api.reloc_set_stereo_speckle(self._ctx, int(window), int(range))
+
+    def get_stereo_speckle(self):
+        """(window, range); window 0 = off"""
+        win, rng = N.outs(i32, i32)
+        self._api.reloc_get_stereo_speckle(self._ctx, win, rng)
+        return win.value, rng.value
+
     def frame_debug_plane(self, what: int, level: int) -> np.ndarray:
         buf = np.empty(self.max_w * self.max_h, np.uint8)
         w, h = N.outs(i32, i32)

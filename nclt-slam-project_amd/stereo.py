@@ -16,7 +16,9 @@ import numpy as np
 MIN_DISPARITY_MAX = 1024                  # RELOC_STEREO_MIN_DISPARITY_MAX
 NUM_DISPARITIES = (8, 256)                # RELOC_STEREO_NUM_DISP_MIN .. _MAX
 UNIQUENESS_MAX = 50                       # RELOC_STEREO_UNIQUENESS_MAX
-STATUS = ("ok", "border", "range", "edge", "uniqueness", "left-right", "far")       # RELOC_STEREO_OK ..
+STATUS = ("ok", "border", "range", "edge", "uniqueness", "left-right", "far", "speckle")       # RELOC_STEREO_OK ..
+SPECKLE_RANGE_MAX = 255                   # RELOC_STEREO_SPECKLE_RANGE_MAX
+SPECKLE_NONE = -16                        # the quantised disparity of a pixel without one ("STEREO, speckle")
 
 
 @dataclass(frozen=True, eq=False)
@@ -26,19 +28,25 @@ class StereoRig:
     min_disparity .. min_disparity + num_disparities - 1 (pixels of the working frame).  uniqueness: percent by which the
     best cost must beat the best one two or more disparities away.  lr_check: the match must be found again from the right.
     rectify_right: the right eye's map pair, as `FrontEnd.rectify` takes the left one (None: the right frames are rectified
-    already, or use the left eye's maps being None too)."""
+    already, or use the left eye's maps being None too).  speckle_window, speckle_range: the speckle stage behind the dense
+    pass ("STEREO, speckle"), OpenCV's speckleWindowSize and speckleRange -- components of at most speckle_window pixels whose
+    neighbours differ by at most speckle_range disparities lose their depth; 0 = off.  The sparse per-keypoint depth has no
+    neighbourhood and is not filtered."""
     baseline_m: float
     min_disparity: int = 0
     num_disparities: int = 128
     uniqueness: int = 15
     lr_check: bool = True
     rectify_right: tuple | None = None
+    speckle_window: int = 0
+    speckle_range: int = 1
 
     def __post_init__(self):
         b = float(self.baseline_m)
         if not (np.isfinite(b) and b > 0.0):
             raise ValueError("stereo: baseline_m must be finite and > 0 (metres)")
-        for name, lo, hi in (("min_disparity", 0, MIN_DISPARITY_MAX), ("num_disparities", *NUM_DISPARITIES), ("uniqueness", 0, UNIQUENESS_MAX)):
+        for name, lo, hi in (("min_disparity", 0, MIN_DISPARITY_MAX), ("num_disparities", *NUM_DISPARITIES), ("uniqueness", 0, UNIQUENESS_MAX),
+                             ("speckle_window", 0, 2 ** 31 - 1), ("speckle_range", 0, SPECKLE_RANGE_MAX)):
             v = getattr(self, name)
             if int(v) != v or not lo <= int(v) <= hi:
                 raise ValueError(f"stereo: {name} must be an integer in {lo}..{hi}")
@@ -47,7 +55,8 @@ class StereoRig:
         object.__setattr__(self, "lr_check", bool(self.lr_check))
 
     def settings(self) -> dict:
-        """the keywords of Engine.set_stereo and, behind fx and baseline_m, of Engine.stereo_depth"""
+        """the keywords of Engine.set_stereo and, behind fx and baseline_m, of Engine.stereo_depth; the speckle pair travels
+        separately (configure, depth_image)"""
         return dict(baseline_m=self.baseline_m, min_disparity=self.min_disparity, num_disparities=self.num_disparities,
                     uniqueness=self.uniqueness, lr_check=self.lr_check)
 
@@ -56,8 +65,10 @@ class StereoRig:
         return replace(front_end, rectify=self.rectify_right)
 
     def configure(self, engine):
-        """the rig's setting on the left eye's Engine"""
+        """the rig's setting on the left eye's Engine; the speckle stage only where the rig has one"""
         engine.set_stereo(**self.settings())
+        if self.speckle_window:
+            engine.set_stereo_speckle(self.speckle_window, self.speckle_range)
 
     def right_engine(self, engine, front_end):
         """an Engine for the right eye, as large as the left one, on the same device, configured with the right eye's front end"""
@@ -73,8 +84,16 @@ class StereoRig:
 
     def depth_image(self, backend, left_gray, right_gray, fx):
         """the (H, W) uint16 depth image, millimetres, 0 = no depth, of two planes of the chain's output through the backend's
-        dense kernel"""
-        return backend.stereo_depth_image(left_gray, right_gray, fx, **self.settings())[0]
+        dense kernel; with a speckle window, then the stage from public pieces: the quantised disparity in NumPy, the
+        backend's filter_speckles, the depth zeroed where the filter removed a pixel"""
+        mm, disp, status = backend.stereo_depth_image(left_gray, right_gray, fx, **self.settings())
+        if not self.speckle_window:
+            return mm
+        ok = np.asarray(status) == 0
+        q = np.where(ok, np.rint(np.asarray(disp, np.float32) * np.float32(16.0)), SPECKLE_NONE).astype(np.int16)
+        backend.filter_speckles(q, SPECKLE_NONE, self.speckle_window, 16 * self.speckle_range)
+        mm[ok & (q == SPECKLE_NONE)] = 0
+        return mm
 
 
 def shim_backend(cv2):
