@@ -567,6 +567,37 @@ int reloc_corr_match_stereo_dev(reloc_ctx *ctx, int step, float zmin, float zmax
 /* The dilated map unpacked: h x w uint8 of 0 / 1, row 0 at origin_y (plane may be NULL); *w, *h: its size (may be NULL). */
 int reloc_corr_read_map(reloc_ctx *ctx, uint8_t *plane, int32_t *w, int32_t *h);
 
+/* ---- route clearance (include/reloc_spec.h, "ROUTE") --------------------------------------------- */
+/* What the reference's sanitize_route.py and send_goals_hybrid.py walk a grid for: the distance from a cell to the nearest
+ * occupied one, and the first cell of the walk's order that satisfies a predicate.  All synchronous.
+ * reloc_route_set_map takes the occupied plane (h x w uint8, row 0 at origin_y, non-zero = occupied), ORs in n_stamps rectangles
+ * (n_stamps x 4 int32: r_lo, r_hi, c_lo, c_hi, half open, clipped to the plane) and computes the clearance plane of rule (d)
+ * with `cap`; row_remap (h int32) and col_remap (w int32) are the tables of rule (e), NULL = identity.  A second call replaces
+ * the map.  reloc_route_set_map_from_occ takes the context's live occupancy grid (units >= 4) where it lies: RELOC_E_STATE
+ * without one.  Non-positive sizes, cap outside [0, 254], a remap entry outside the plane, a stamp with lo > hi: RELOC_E_ARG;
+ * more than RELOC_OCC_MAX_CELLS cells or RELOC_ROUTE_MAX_SIDE per side: RELOC_E_CAPACITY; the map before stays in both cases.  A
+ * context that never sets a route map or a costmap allocates and launches nothing of this. */
+int reloc_route_set_map(reloc_ctx *ctx, const uint8_t *occupied, int w, int h, const int32_t *stamps, int n_stamps, int cap,
+                        const int32_t *row_remap, const int32_t *col_remap);
+int reloc_route_set_map_from_occ(reloc_ctx *ctx, const int32_t *stamps, int n_stamps, int cap, const int32_t *row_remap,
+                                 const int32_t *col_remap);
+/* The clearance plane: h x w uint8, row 0 at origin_y (plane may be NULL); *w, *h: its size (may be NULL).  RELOC_E_STATE
+ * before a map is set, as reloc_route_clearance_at. */
+int reloc_route_read_clearance(reloc_ctx *ctx, uint8_t *plane, int32_t *w, int32_t *h);
+/* out[i] = the clearance at cell (cells_rc[2 i], cells_rc[2 i + 1]) = (row, col), no remap; RELOC_ROUTE_FAR for a cell outside
+ * the plane.  n == 0 launches nothing. */
+int reloc_route_clearance_at(reloc_ctx *ctx, const int32_t *cells_rc, int n, uint8_t *out);
+/* The int8 costmap of the COST predicate (h x w, row 0 at its origin_y), a plane of its own beside the route map; a second call
+ * replaces it.  Capacity as the map's. */
+int reloc_route_set_costmap(reloc_ctx *ctx, const int8_t *cost, int w, int h);
+/* Rule (g): offsets_rc is the order table (n_offsets x 2 int32: dr, dc), cells_rc the n start cells (row, col; any int32);
+ * out_index[i] = the first table index whose cell is inside the plane and satisfies the predicate, -1 for none.
+ * RELOC_ROUTE_PRED_CLEARANCE: clearance at the remapped cell >= thresh, RELOC_E_STATE before a route map;
+ * RELOC_ROUTE_PRED_COST: 0 <= cost < thresh, RELOC_E_STATE before a costmap.  Another predicate: RELOC_E_ARG.  More than
+ * RELOC_ROUTE_MAX_OFFSETS entries, or one beyond RELOC_ROUTE_MAX_OFFSET cells: RELOC_E_CAPACITY.  n == 0 launches nothing. */
+int reloc_route_search(reloc_ctx *ctx, int predicate, int thresh, const int32_t *offsets_rc, int n_offsets, const int32_t *cells_rc,
+                       int n, int32_t *out_index);
+
 /* ---- fused tick ----------------------------------------------------------------------------- */
 #define RELOC_TICK_LOCAL   0   /* candidates by VIO distance / heading only                          M:293-302 */
 #define RELOC_TICK_GLOBAL  1   /* whole-database search unconditionally (the benchmarked shape)       G:329-344 */

@@ -478,4 +478,52 @@
 #define RELOC_CORR_MAX_WINDOW  703         /* side of the scan's window, cells: 2 * (ceil(max_range / res) + 2) + 1 */
 #define RELOC_CORR_MIN_POINTS_DEFAULT 100
 
+/* ROUTE: route clearance, what the reference does to keep a route's waypoints out of obstacles: offline sanitize_route.py (S
+ * below, the same file in experiments 58..64) on the teach map, live send_goals_hybrid.py (H below; _project_wp and costmap_cb,
+ * H:200-262) on every costmap update.  Both walk a grid breadth first; here the walk's depth is a distance plane and the walk's
+ * order a table.  Restated in tests/route_ref.py, which the library equals in every byte and index it returns.
+ *   (a) grid     a plane is h x w, row 0 at origin_y.  The cell of a point: col = int((x - origin_x) / res), row likewise from y,
+ *              float64, truncation toward zero as Python's int() (S:78-79, H:114-115): a point up to one cell left of the map
+ *              lands in column 0.  Not floor.  Always computed on the host.
+ *   (b) occupied two sources: a host uint8 plane, non-zero = occupied (S.load_teach_map: flipud(img) == 0), or the context's
+ *              occupancy grid where it lies, occupied iff units >= RELOC_OCC_UNITS_OCC: the cells reloc_occ_read's pgm paints 0.
+ *   (c) stamps   a list of cell rectangles [r_lo, r_hi) x [c_lo, c_hi), OR-ed into the occupied plane on the device before (d);
+ *              the part of a rectangle outside the plane is dropped.  The host computes them with S.stamp_obstacles'
+ *              arithmetic (S:55-72): a cone is the one cell of (a), dropped when off the map; the tent is clipped as S clips it.
+ *   (d) clearance uint8: the L1 (city-block) distance in cells to the nearest occupied cell where that is <= cap, else
+ *              RELOC_ROUTE_FAR; cap in [0, RELOC_ROUTE_MAX_CAP]; a plane with no occupied cell is all RELOC_ROUTE_FAR.  S's walk
+ *              (S:75-96) steps to 4-neighbours inside the rectangle and does not stop at obstacles, so its depth IS the L1
+ *              distance; its `d > max_cells` test lets distance max_cells itself count.
+ *   (e) re-entry S.find_safe_shift hands a candidate cell's corner origin_x + c * res back to dist_to_nearest_occupied
+ *              (S:118-121), which recomputes the cell as int(((origin_x + c * res) - origin_x) / res): in float64 sometimes
+ *              c - 1.  The same for rows.  The host computes both int32 tables once per map with exactly that expression; the
+ *              device reads the clearance of a candidate at [row_remap[r]][col_remap[c]].  The waypoint's own first test (S:164)
+ *              uses no remap.
+ *   (f) order    an order table: the (dr, dc) in the order the reference's walk dequeues them from a start cell, neighbours
+ *              up, down, left, right = (-1, 0), (1, 0), (0, -1), (0, 1), layer by layer through layer m.  H enqueues off-map
+ *              cells (H:227-232): its table is always the unclipped diamond, 2 m (m + 1) + 1 entries, 1861 at m = 30.  S enqueues
+ *              only in-map cells (S:125-129): its table is the walk clipped to min(r0, m), min(h - 1 - r0, m), min(c0, m),
+ *              min(w - 1 - c0, m) cells around the start.  The clipped table is the unclipped one without its off-map entries,
+ *              in the same order: every cell that enqueues an in-map cell lies between it and the start, hence in the map as
+ *              well, so layer by layer the in-map cells keep the order they have among all cells (tests/test_route_host.py
+ *              holds the two equal for every clip).  (g) skips off-map cells, so the unclipped table serves S and H alike,
+ *              and a whole route is one search.  The host runs the walk on an empty window and hands the table over: the
+ *              queue defines the order.
+ *   (g) search   one order table, n start cells: for each start the smallest table index k whose cell (r0 + dr_k, c0 + dc_k) is
+ *              inside the plane and satisfies the predicate; -1 when there is none.
+ *   (h) predicates CLEARANCE: clearance[row_remap[r]][col_remap[c]] >= d_min.  COST: 0 <= cost[r][c] < thresh on an int8
+ *              costmap; negative (unknown) and off-map cells are blocked (H:124-131).
+ *   (i) thresholds d_min: the smallest integer d with d * res >= safety_m in float64, found on the host by trying d = 0, 1, ...;
+ *              the comparison S itself makes (S:121, 165), not a quotient: 17 * 0.1 = 1.7000000000000002 >= 1.7 holds through
+ *              the product's rounding.  The plane's cap is
+ *              ceil(safety_m / res) + 2 (S:109, 121).  The host asserts d_min <= int(safety_m / res) + 2, the cap of S:164: one
+ *              plane then answers both of S's calls, since only `>= d_min` is ever asked of it. */
+#define RELOC_ROUTE_FAR             255       /* clearance: no occupied cell within cap */
+#define RELOC_ROUTE_MAX_CAP         254
+#define RELOC_ROUTE_MAX_SIDE        32768     /* cells per side of a map or costmap; cells in all: RELOC_OCC_MAX_CELLS */
+#define RELOC_ROUTE_MAX_OFFSETS     65536     /* entries of one order table: m = 180 layers unclipped */
+#define RELOC_ROUTE_MAX_OFFSET      32767     /* magnitude of one entry's dr or dc, cells */
+#define RELOC_ROUTE_PRED_CLEARANCE  0
+#define RELOC_ROUTE_PRED_COST       1
+
 #endif /* RELOC_SPEC_H */

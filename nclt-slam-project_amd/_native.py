@@ -149,6 +149,12 @@ SIGNATURES = {
     "reloc_corr_match_depth": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, C.c_int, P, f32, f32, P, f64, f64, P, P]),
     "reloc_corr_match_stereo_dev": (C.c_int, [c_ctx, C.c_int, f32, f32, P, f64, f64, P, P]),
     "reloc_corr_read_map": (C.c_int, [c_ctx, P, P, P]),
+    "reloc_route_set_map": (C.c_int, [c_ctx, P, C.c_int, C.c_int, P, C.c_int, C.c_int, P, P]),
+    "reloc_route_set_map_from_occ": (C.c_int, [c_ctx, P, C.c_int, C.c_int, P, P]),
+    "reloc_route_read_clearance": (C.c_int, [c_ctx, P, P, P]),
+    "reloc_route_clearance_at": (C.c_int, [c_ctx, P, C.c_int, P]),
+    "reloc_route_set_costmap": (C.c_int, [c_ctx, P, C.c_int, C.c_int]),
+    "reloc_route_search": (C.c_int, [c_ctx, C.c_int, C.c_int, P, C.c_int, P, C.c_int, P]),
     "reloc_tick_debug": (C.c_int, [c_ctx, P, P, P, P, P, P, P]),
     "reloc_tick_debug_matches": (C.c_int, [c_ctx, C.c_int, P, P, P, P, P, P]),
     "reloc_debug_local_candidates": (C.c_int, [c_ctx, P, C.c_int, P, P]),

@@ -256,14 +256,21 @@ static int corr_map_begin(reloc_ctx *ctx, int w, int h, double ox, double oy, do
     return RELOC_OK;
 }
 
+// `plane` (device memory: h x w uint8, or the occupancy map's int8 units) as h packed rows of mp = ceil(w / 32) words at `bits`
+void corr_pack_plane(HostStaging &st, const void *plane, bool from_units, uint32_t *bits, int w, int h, int mp)
+{
+    const int64_t words = (int64_t)mp * h;
+    if (from_units) st.launch(k_corr_pack<1>, dim3(corr_grid(words)), dim3(256), plane, bits, w, h, mp);
+    else st.launch(k_corr_pack<0>, dim3(corr_grid(words)), dim3(256), plane, bits, w, h, mp);
+}
+
 // packs `plane` (device memory) into the map and dilates it
 static void corr_map_build(reloc_ctx *ctx, HostStaging &st, const void *plane, bool from_units, int dilate)
 {
     CorrState &s = ctx->corr;
     const int64_t words = (int64_t)s.mp * s.h;
     uint32_t *a = (uint32_t *)s.map_block, *b = a + s.map_words;
-    if (from_units) st.launch(k_corr_pack<1>, dim3(corr_grid(words)), dim3(256), plane, a, s.w, s.h, s.mp);
-    else st.launch(k_corr_pack<0>, dim3(corr_grid(words)), dim3(256), plane, a, s.w, s.h, s.mp);
+    corr_pack_plane(st, plane, from_units, a, s.w, s.h, s.mp);
     for (int it = 0; it < dilate; ++it) {
         st.launch(k_corr_dilate, dim3(corr_grid(words)), dim3(256), (const uint32_t *)a, b, s.w, s.h, s.mp);
         uint32_t *t = a; a = b; b = t;

@@ -113,6 +113,7 @@ RELOC_API void reloc_destroy(reloc_ctx *c)
     stereo_release(c);
     occ_release(c);
     corr_release(c);
+    route_release(c);
     for (int k = 0; k < RELOC_PROF_N; ++k)
         if (c->prof[k].init)
             for (int i = 0; i < RELOC_PROF_RING; ++i) {

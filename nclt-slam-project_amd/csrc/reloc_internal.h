@@ -444,6 +444,25 @@ struct CorrState {
     bool configured() const { return n_side > 0; }
 };
 
+// Route clearance of a context (include/reloc_spec.h "ROUTE"; reloc_route.hip); 0 x 0 = no map, the default: a context that never
+// sets a route map or a costmap allocates and launches nothing of it.  Two device blocks of its own: the map's
+// (reloc_route_set_map*) and the costmap's (reloc_route_set_costmap), both freed by route_release.
+struct RouteState {
+    int w = 0, h = 0, mp = 0, ws = 0;    // the map: cells, words per packed row, bytes per row of the two byte planes (32 * mp)
+    int cap = 0;
+    uint8_t *block = nullptr;            // the pointers below lie in it
+    int64_t block_bytes = 0;
+    uint32_t *bits = nullptr;            // h x mp: the occupied plane with the stamps, one bit per cell
+    uint8_t *rowd = nullptr;             // h x ws: capped distance to the nearest occupied cell of the same row
+    uint8_t *clear = nullptr;            // h x ws: the clearance plane (d)
+    int32_t *row_remap = nullptr, *col_remap = nullptr;      // h and w entries (e)
+    int cw = 0, ch = 0;                  // the costmap: cells
+    int8_t *cost = nullptr;              // ch x cw, a block of its own
+    int64_t cost_bytes = 0;
+    bool on() const { return w > 0; }
+    bool has_cost() const { return cw > 0; }
+};
+
 // What the five ORB kernels read and write of one frame, in the form they take it: a single-frame launch passes the members
 // as arguments, a batched one up to 8 of these in its kernel arguments (OrbBatch, blockIdx.y = frame).
 struct OrbFrame {
@@ -530,6 +549,7 @@ struct reloc_ctx {
     StereoState stereo;              // reloc_stereo.hip
     OccState occ;                    // reloc_occupancy.hip
     CorrState corr;                  // reloc_correlation.hip
+    RouteState route;                // reloc_route.hip
     int scan_gens = 0;               // RELOC_SCAN_GENS (developer switch), read once at creation: n > 0 = single whole-database
                                      // scans in the form of batched ones (n generations of row budgets + sweepers, launch_db_count)
     uint32_t *scan_ticket = nullptr; // SCAN_TICKET_WORDS counters of the whole-database scans (scan_alloc, reloc_scan.hip)
@@ -582,6 +602,11 @@ struct HostStaging {
     void upload_rows(void *dst, const void *src, int row_bytes, int rows, int sstride)
     {
         run([&] { hip(hipMemcpy2DAsync(dst, row_bytes, src, sstride, row_bytes, rows, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy2DAsync"); return rc; });
+    }
+    // rows of row_bytes, sstride apart on the device, dense at the caller's
+    void download_rows(void *dst, const void *src, int row_bytes, int rows, int sstride)
+    {
+        run([&] { hip(hipMemcpy2DAsync(dst, row_bytes, src, sstride, row_bytes, rows, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy2DAsync"); return rc; });
     }
     template <typename K, typename... A>
     void launch(K kern, dim3 grid, dim3 block, A... args)
@@ -688,6 +713,11 @@ void stereo_release(reloc_ctx *ctx);
 void occ_release(reloc_ctx *ctx);
 // the correlation anchor's blocks, if the context has any (reloc_correlation.hip)
 void corr_release(reloc_ctx *ctx);
+// an occupied plane on the device (h x w uint8, non-zero = occupied; from_units: the occupancy map's int8 units, occupied from
+// RELOC_OCC_UNITS_OCC) as h packed rows of mp = ceil(w / 32) words, the bits beyond column w - 1 clear (reloc_correlation.hip)
+void corr_pack_plane(HostStaging &st, const void *plane, bool from_units, uint32_t *bits, int w, int h, int mp);
+// the route clearance's blocks, if the context has any (reloc_route.hip)
+void route_release(reloc_ctx *ctx);
 // Dense stereo depth: both eyes' frames (ctx->frame_img, right->frame_img, w x h as handed in) through the gray half of their
 // chains, each on its own stream, no ORB; then k_stereo_dense and k_stereo_dense_finish on ctx's stream into ctx->stereo.dense
 // (mm: dense rows of *ww uint16).  Checks stereo on, right != ctx, capacity and the chains' agreement.

@@ -41,6 +41,8 @@ def match_policy_setting(policy, ratio):
     return name, r
 
 
+ROUTE_PREDICATES = {"clearance": 0, "cost": 1}      # RELOC_ROUTE_PRED_* of include/reloc_spec.h
+
 MAX_CAND = 32           # candidates of one tick (MAX_CAND of csrc/reloc_internal.h): the longest top-k / candidate list
 DEBUG_POISON = -1515870811      # int32 0xA5A5A5A5: what debug_rank_counts leaves where the ranking wrote nothing
 
@@ -956,6 +958,74 @@ class Engine:
         plane = np.zeros((h.value, w.value), np.uint8)
         self._api.reloc_corr_read_map(self._ctx, plane, None, None)
         return plane.astype(bool)
+
+    # ------------------------------------------------------------------ route clearance (reloc_spec.h "ROUTE")
+    @staticmethod
+    def _route_map_args(stamps, row_remap, col_remap):
+        s = np.ascontiguousarray(stamps if stamps is not None else [], np.int32).reshape(-1, 4)
+        remap = lambda t: None if t is None else np.ascontiguousarray(t, np.int32)
+        return (s if len(s) else None), len(s), remap(row_remap), remap(col_remap)
+
+    def route_set_map(self, occupied, stamps=None, cap: int = 19, row_remap=None, col_remap=None):
+        """the occupied plane: (H, W), row 0 at origin_y, non-zero = occupied; stamps: (n, 4) cell rectangles r_lo, r_hi, c_lo,
+        c_hi OR-ed in on the device; the clearance plane is computed with `cap`; the remap tables of rule (e), None = identity"""
+        occ = np.ascontiguousarray(occupied)
+        if occ.ndim != 2 or occ.size == 0:
+            raise N.RelocError("route_set_map: expected a non-empty (H, W) plane")
+        occ = np.ascontiguousarray(occ != 0, np.uint8)
+        h, w = occ.shape
+        s, n, rr, cr = self._route_map_args(stamps, row_remap, col_remap)
+        if (rr is not None and rr.shape != (h,)) or (cr is not None and cr.shape != (w,)):
+            raise N.RelocError("route_set_map: row_remap needs H entries and col_remap W")
+        self._api.reloc_route_set_map(self._ctx, occ, w, h, s, n, int(cap), rr, cr)
+
+    def route_set_map_from_occ(self, stamps=None, cap: int = 19, row_remap=None, col_remap=None):
+        """the context's live occupancy grid (occ_configure) as the occupied plane, without a trip through the host"""
+        s, n, rr, cr = self._route_map_args(stamps, row_remap, col_remap)
+        shape = getattr(self, "_occ_shape", None)
+        if shape and ((rr is not None and rr.shape != (shape[0],)) or (cr is not None and cr.shape != (shape[1],))):
+            raise N.RelocError("route_set_map_from_occ: row_remap needs H entries and col_remap W")
+        self._api.reloc_route_set_map_from_occ(self._ctx, s, n, int(cap), rr, cr)
+
+    def route_read_clearance(self):
+        """the clearance plane: (H, W) uint8, row 0 at origin_y, 255 = no occupied cell within cap"""
+        w, h = i32(), i32()
+        self._api.reloc_route_read_clearance(self._ctx, None, w, h)
+        plane = np.zeros((h.value, w.value), np.uint8)
+        self._api.reloc_route_read_clearance(self._ctx, plane, None, None)
+        return plane
+
+    @staticmethod
+    def _route_cells(cells, what):
+        c = np.ascontiguousarray(cells, np.int32)
+        if c.size and (c.ndim != 2 or c.shape[1] != 2):
+            raise N.RelocError(f"{what}: expected (n, 2) cells (row, col)")
+        return c.reshape(-1, 2)
+
+    def route_clearance_at(self, cells):
+        """the clearance at (n, 2) cells (row, col), no remap; 255 for a cell off the map"""
+        c = self._route_cells(cells, "route_clearance_at")
+        out = np.zeros(len(c), np.uint8)
+        self._api.reloc_route_clearance_at(self._ctx, c if len(c) else None, len(c), out if len(c) else None)
+        return out
+
+    def route_set_costmap(self, cost):
+        """the (H, W) int8 costmap of the COST predicate, row 0 at its origin_y"""
+        cost = np.ascontiguousarray(cost, np.int8)
+        if cost.ndim != 2 or cost.size == 0:
+            raise N.RelocError("route_set_costmap: expected a non-empty (H, W) int8 plane")
+        self._api.reloc_route_set_costmap(self._ctx, cost, cost.shape[1], cost.shape[0])
+
+    def route_search(self, predicate, thresh: int, offsets, cells):
+        """rule (g): for each of the (n, 2) start cells the first index of the (m, 2) order table `offsets` whose cell satisfies
+        the predicate ("clearance": clearance at the remapped cell >= thresh; "cost": 0 <= cost < thresh), -1 for none"""
+        pred = ROUTE_PREDICATES.get(predicate, predicate)
+        t = self._route_cells(offsets, "route_search")
+        c = self._route_cells(cells, "route_search")
+        out = np.zeros(len(c), np.int32)
+        self._api.reloc_route_search(self._ctx, int(pred), int(thresh), t if len(t) else None, len(t), c if len(c) else None, len(c),
+                                     out if len(c) else None)
+        return out
 
     def hamming_matrix(self, a, b):
         a = self._desc(a, "hamming_matrix"); b = self._desc(b, "hamming_matrix")

@@ -539,3 +539,56 @@ def depth_correlation_main(argv=None):
     """on shutdown the node logs the reference's `Final: N publishes / M attempts` (depth_correlation_matcher.py:300-301)"""
     teach_map, out_csv, tail, thresholds = depth_correlation_args(argv)
     _spin(lambda: make_depth_correlation_node(teach_map, out_csv, *tail, **thresholds), "summary", log_result=True)
+
+
+def make_goal_projector(waypoints, engine=None, **thresholds):
+    """send_goals_hybrid.py's proactive projection (its costmap_cb, :235-262) without the planner client: a ROS-free holder whose
+    costmap_cb takes an OccupancyGrid-shaped message (info.width / height / resolution / origin.position, data) and re-projects
+    the waypoints from current_idx on through route.WaypointProjectorCore; projected_wps, skip_flags and the two counters are the
+    core's.  thresholds: WaypointProjectorCore's keywords.  engine: the Engine that holds the costmap (default: a new one)."""
+    from .route import WaypointProjectorCore
+    if engine is None:
+        from .engine import Engine
+        engine = Engine()
+
+    class GoalProjector:
+        def __init__(self):
+            self.core = WaypointProjectorCore(engine, waypoints, **thresholds)
+            self.current_idx = 0
+
+        def costmap_cb(self, msg):
+            info = msg.info
+            cost = np.array(msg.data, dtype=np.int8).reshape(info.height, info.width)
+            return self.core.costmap_update(cost, info.origin.position.x, info.origin.position.y, info.resolution, self.current_idx)
+
+    return GoalProjector()
+
+
+def sanitize_route_main(argv=None, engine=None):
+    """sanitize_route.py's flags (its main, :133-141) plus the obstacles it hard-codes as arguments: --cone X Y (repeatable) and
+    --tent CX CY HX HY; prints the reference's summary lines.  engine: the Engine to run on (default: a new one)."""
+    import csv
+    from .route import RouteSanitizerCore
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--trajectory", required=True, help="input CSV with gt_x, gt_y columns")
+    ap.add_argument("--teach-map", required=True)
+    ap.add_argument("--output", required=True)
+    ap.add_argument("--spacing", type=float, default=4.0, help="only sanitize WPs at this spacing")
+    ap.add_argument("--cone", type=float, nargs=2, action="append", default=[], metavar=("X", "Y"), help="a known cone, one cell; repeatable")
+    ap.add_argument("--tent", type=float, nargs=4, default=None, metavar=("CX", "CY", "HX", "HY"), help="a known tent: centre and half extents")
+    args = ap.parse_args(argv)
+    if engine is None:
+        from .engine import Engine
+        engine = Engine()
+    core = RouteSanitizerCore(engine, teach_yaml=args.teach_map, cones=[tuple(c) for c in args.cone], tent=args.tent)
+    with open(args.trajectory) as f:
+        pts = [(float(row["gt_x"]), float(row["gt_y"])) for row in csv.DictReader(f)]
+    wps = core.subsample(pts, args.spacing)
+    print(f"Loaded {len(wps)} WPs at {args.spacing}m spacing")
+    rows, counts = core.sanitize(wps)
+    core.write_csv(args.output, rows)
+    print(f"\nWrote {len(rows)} rows to {args.output}")
+    print(f"  safe unchanged:  {counts['unchanged']}")
+    print(f"  shifted:         {counts['shifted']}")
+    print(f"  skipped (unsafe):{counts['skipped']}")
+    return counts
