@@ -210,12 +210,10 @@ __global__ __launch_bounds__(1024) void k_corr_pick(const int32_t *__restrict__ 
 // ---- host ---------------------------------------------------------------------------------------------------------------
 void corr_release(reloc_ctx *ctx)
 {
-    if (ctx->corr.map_block) (void)hipFree(ctx->corr.map_block);
-    if (ctx->corr.cfg_block) (void)hipFree(ctx->corr.cfg_block);
+    ctx->corr.map_block.release();
+    ctx->corr.cfg_block.release();
     ctx->corr = CorrState{};
 }
-
-static inline unsigned corr_grid(int64_t n) { const int64_t b = (n + 255) / 256; return (unsigned)(b < 1 ? 1 : b < 1024 ? b : 1024); }
 
 // half the window's side for a range and a cell size; RELOC_E_CAPACITY beyond RELOC_CORR_MAX_WINDOW
 static int corr_window(double max_range, double res, int *half)
@@ -243,14 +241,11 @@ static int corr_map_begin(reloc_ctx *ctx, int w, int h, double ox, double oy, do
     if (s.configured())
         if (int rc = corr_window(s.max_range, res, &half)) return rc;
     const int mp = (w + 31) / 32;
-    const int64_t words = (int64_t)mp * h;
-    if (!s.map_block || s.map_words < words) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (s.map_block) (void)hipFree(s.map_block);
-        s.map_block = nullptr; s.map_words = 0; s.w = s.h = 0;
-        HIP_TRY(hipMalloc((void **)&s.map_block, (size_t)words * 8));
-        s.map_words = words;
-    }
+    if (int rc = s.map_block.layout(ctx, [&] {
+            size_t at = 0;
+            for (uint32_t *&plane : s.plane) plane = s.map_block.carve<uint32_t>(at, (int64_t)mp * h);
+            return at;
+        })) { s.w = s.h = 0; return rc; }
     s.w = w; s.h = h; s.mp = mp; s.ox = ox; s.oy = oy; s.res = res;
     if (s.configured()) s.half = half;
     return RELOC_OK;
@@ -259,23 +254,20 @@ static int corr_map_begin(reloc_ctx *ctx, int w, int h, double ox, double oy, do
 // `plane` (device memory: h x w uint8, or the occupancy map's int8 units) as h packed rows of mp = ceil(w / 32) words at `bits`
 void corr_pack_plane(HostStaging &st, const void *plane, bool from_units, uint32_t *bits, int w, int h, int mp)
 {
-    const int64_t words = (int64_t)mp * h;
-    if (from_units) st.launch(k_corr_pack<1>, dim3(corr_grid(words)), dim3(256), plane, bits, w, h, mp);
-    else st.launch(k_corr_pack<0>, dim3(corr_grid(words)), dim3(256), plane, bits, w, h, mp);
+    st.launch(from_units ? k_corr_pack<1> : k_corr_pack<0>, dim3(grid_1d((int64_t)mp * h, 1024)), dim3(256), plane, bits, w, h, mp);
 }
 
-// packs `plane` (device memory) into the map and dilates it
-static void corr_map_build(reloc_ctx *ctx, HostStaging &st, const void *plane, bool from_units, int dilate)
+// packs `plane` (device memory) into the map and dilates it; a failure leaves no map
+static int corr_map_build(reloc_ctx *ctx, HostStaging &st, const void *plane, bool from_units, int dilate)
 {
     CorrState &s = ctx->corr;
-    const int64_t words = (int64_t)s.mp * s.h;
-    uint32_t *a = (uint32_t *)s.map_block, *b = a + s.map_words;
-    corr_pack_plane(st, plane, from_units, a, s.w, s.h, s.mp);
-    for (int it = 0; it < dilate; ++it) {
-        st.launch(k_corr_dilate, dim3(corr_grid(words)), dim3(256), (const uint32_t *)a, b, s.w, s.h, s.mp);
-        uint32_t *t = a; a = b; b = t;
-    }
-    s.map = a;
+    corr_pack_plane(st, plane, from_units, s.plane[0], s.w, s.h, s.mp);
+    for (int it = 0; it < dilate; ++it)
+        st.launch(k_corr_dilate, dim3(grid_1d((int64_t)s.mp * s.h, 1024)), dim3(256), (const uint32_t *)s.plane[it & 1], s.plane[~it & 1], s.w, s.h, s.mp);
+    s.map = s.plane[dilate & 1];
+    const int rc = st.finish();
+    if (rc) s.w = s.h = 0;
+    return rc;
 }
 
 RELOC_API int reloc_corr_set_map(reloc_ctx *ctx, const uint8_t *occupied, int w, int h, double origin_x, double origin_y, double res, int dilate)
@@ -284,31 +276,21 @@ RELOC_API int reloc_corr_set_map(reloc_ctx *ctx, const uint8_t *occupied, int w,
                   "reloc_corr_set_map: a plane, positive sizes and res, dilate >= 0, everything finite");
     if (int rc = corr_map_begin(ctx, w, h, origin_x, origin_y, res, dilate, "reloc_corr_set_map")) return rc;
     HostStaging st{ctx};
-    corr_map_build(ctx, st, st.upload_slot(6, occupied, (int64_t)w * h), false, dilate);
-    const int rc = st.finish();
-    if (rc) ctx->corr.w = ctx->corr.h = 0;
-    return rc;
+    return corr_map_build(ctx, st, st.upload_slot(6, occupied, (int64_t)w * h), false, dilate);
 }
 
 RELOC_API int reloc_corr_set_map_from_occ(reloc_ctx *ctx, int dilate)
 {
     ARG_CHECK_CTX(ctx, dilate >= 0, "reloc_corr_set_map_from_occ: dilate >= 0");
+    if (int rc = occ_need_map(ctx, "reloc_corr_set_map_from_occ")) return rc;
     const OccState &o = ctx->occ;
-    if (!o.on()) { reloc_set_error("reloc_corr_set_map_from_occ: no occupancy map on this context (reloc_occ_configure)"); return RELOC_E_STATE; }
     if (int rc = corr_map_begin(ctx, o.w, o.h, o.ox, o.oy, o.res, dilate, "reloc_corr_set_map_from_occ")) return rc;
     HostStaging st{ctx};
-    corr_map_build(ctx, st, o.units, true, dilate);
-    const int rc = st.finish();
-    if (rc) ctx->corr.w = ctx->corr.h = 0;
-    return rc;
+    return corr_map_build(ctx, st, o.units, true, dilate);
 }
 
-static int corr_need_map(const reloc_ctx *ctx, const char *who)
-{
-    if (ctx->corr.on()) return RELOC_OK;
-    reloc_set_error("%s: no correlation map on this context (reloc_corr_set_map)", who);
-    return RELOC_E_STATE;
-}
+static int corr_need_map(const reloc_ctx *ctx, const char *who) { return need_map(ctx->corr.on(), who, "correlation", "reloc_corr_set_map"); }
+
 
 RELOC_API int reloc_corr_configure(reloc_ctx *ctx, const int32_t *cell_offsets, int n_side, double z_lo, double z_hi, double max_range, int min_points)
 {
@@ -325,14 +307,15 @@ RELOC_API int reloc_corr_configure(reloc_ctx *ctx, const int32_t *cell_offsets, 
     CorrState &s = ctx->corr;
     int half = 0;
     if (int rc = corr_window(max_range, s.res, &half)) return rc;
-    if (!s.cfg_block) {                           // sized for the limits, once
-        const size_t surf = (size_t)RELOC_CORR_MAX_TABLE * RELOC_CORR_MAX_TABLE;
-        HIP_TRY(hipMalloc((void **)&s.cfg_block, (CORR_LIST_WORDS + surf + 256 + CORR_REC_DEV) * 4));
-        s.list = (uint32_t *)s.cfg_block;
-        s.surface = (int32_t *)(s.list + CORR_LIST_WORDS);
-        s.table = s.surface + surf;
-        s.record = s.table + 256;
-    }
+    static_assert(RELOC_CORR_MAX_TABLE <= 256, "the table's room in the search's block");
+    if (int rc = s.cfg_block.layout(ctx, [&] {      // sized for the limits: taken once
+            size_t at = 0;
+            s.list = s.cfg_block.carve<uint32_t, 8>(at, CORR_LIST_WORDS);      // k_corr_correlate reads uint2
+            s.surface = s.cfg_block.carve<int32_t>(at, RELOC_CORR_MAX_TABLE * RELOC_CORR_MAX_TABLE);
+            s.table = s.cfg_block.carve<int32_t>(at, 256);
+            s.record = s.cfg_block.carve<int32_t>(at, CORR_REC_DEV);
+            return at;
+        })) { s.n_side = 0; return rc; }
     HostStaging st{ctx};
     st.upload(s.table, cell_offsets, (int64_t)n_side * 4);
     if (int rc = st.finish()) { s.n_side = 0; return rc; }
@@ -344,8 +327,7 @@ static int corr_check(reloc_ctx *ctx, const double *T12, double vio_x, double vi
 {
     if (int rc = corr_need_map(ctx, who)) return rc;
     if (!ctx->corr.configured()) { reloc_set_error("%s: the correlation search is not configured (reloc_corr_configure)", who); return RELOC_E_STATE; }
-    for (int k = 0; k < 12; ++k)
-        if (!occ_finite(T12[k])) { reloc_set_error("bad argument: %s: the transform must be finite", who); return RELOC_E_ARG; }
+    if (int rc = frame_transform_check(T12, who)) return rc;
     if (!occ_finite(vio_x) || !occ_finite(vio_y)) { reloc_set_error("bad argument: %s: the base position must be finite", who); return RELOC_E_ARG; }
     return RELOC_OK;
 }
@@ -357,7 +339,7 @@ static inline int corr_base_cell(double v, double origin, double res)
 }
 
 // A tick: the three launches on the context's stream, then the record and the surface (may be NULL) to the host
-static int corr_tick(reloc_ctx *ctx, HostStaging &st, int kind, const OccSrc &src, const double *T12, double vio_x, double vio_y, int32_t *record,
+static int corr_tick(reloc_ctx *ctx, HostStaging &st, const FrameSrc &f, const double *T12, double vio_x, double vio_y, int32_t *record,
                      int32_t *surface)
 {
     const CorrState &s = ctx->corr;
@@ -368,8 +350,7 @@ static int corr_tick(reloc_ctx *ctx, HostStaging &st, int kind, const OccSrc &sr
                      corr_base_cell(vio_y, s.oy, s.res) - s.half, corr_base_cell(vio_x, s.ox, s.res) - s.half, S, PW, s.min_points};
     const size_t lds = (size_t)S * PW * 4;
     st.run([&] {
-        auto kern = kind == OCC_SRC_POINTS ? k_corr_scan<OCC_SRC_POINTS> : kind == OCC_SRC_DEPTH_F32 ? k_corr_scan<OCC_SRC_DEPTH_F32> : k_corr_scan<OCC_SRC_DEPTH_U16>;
-        hipLaunchKernelGGL(kern, dim3(1), dim3(1024), lds, ctx->stream, src, T, g, s.list, s.record);
+        hipLaunchKernelGGL(FRAME_KERNEL(k_corr_scan, f.kind), dim3(1), dim3(1024), lds, ctx->stream, f.src, T, g, s.list, s.record);
         st.hip(hipGetLastError(), "kernel launch");
         return st.rc;
     });
@@ -391,8 +372,7 @@ RELOC_API int reloc_corr_match_points(reloc_ctx *ctx, const float *pts, int n, c
     ARG_CHECK_CTX(ctx, n >= 0 && (pts || n == 0) && T12 && record, "reloc_corr_match_points");
     if (int rc = corr_check(ctx, T12, vio_x, vio_y, "reloc_corr_match_points")) return rc;
     HostStaging st{ctx};
-    const OccSrc src{n > 0 ? st.upload_slot(5, pts, (int64_t)n * 3) : nullptr, n, {}};
-    return corr_tick(ctx, st, OCC_SRC_POINTS, src, T12, vio_x, vio_y, record, surface);
+    return corr_tick(ctx, st, frame_from_cloud(st, pts, n), T12, vio_x, vio_y, record, surface);
 }
 
 RELOC_API int reloc_corr_match_depth(reloc_ctx *ctx, const void *depth, int is_f32, int w, int h, int step, const double K4[4], float zmin, float zmax,
@@ -400,11 +380,8 @@ RELOC_API int reloc_corr_match_depth(reloc_ctx *ctx, const void *depth, int is_f
 {
     ARG_CHECK_CTX(ctx, depth && w > 0 && h > 0 && step > 0 && K4 && T12 && record, "reloc_corr_match_depth");
     if (int rc = corr_check(ctx, T12, vio_x, vio_y, "reloc_corr_match_depth")) return rc;
-    if ((int64_t)w * h > (int64_t)ctx->max_w * ctx->max_h) { reloc_set_error("depth image exceeds ctx capacity"); return RELOC_E_CAPACITY; }
     HostStaging st{ctx};
-    const void *ddepth = st.upload_slot(5, (const uint8_t *)depth, (int64_t)w * h * (is_f32 ? 4 : 2));
-    const OccSrc src{nullptr, 0, depth_grid(ddepth, is_f32, w, h, w, step, K4, zmin, zmax)};
-    return corr_tick(ctx, st, is_f32 ? OCC_SRC_DEPTH_F32 : OCC_SRC_DEPTH_U16, src, T12, vio_x, vio_y, record, surface);
+    return corr_tick(ctx, st, frame_from_depth(st, depth, is_f32, w, h, step, K4, zmin, zmax), T12, vio_x, vio_y, record, surface);
 }
 
 RELOC_API int reloc_corr_match_stereo_dev(reloc_ctx *ctx, int step, float zmin, float zmax, const double T12[12], double vio_x, double vio_y,
@@ -412,11 +389,8 @@ RELOC_API int reloc_corr_match_stereo_dev(reloc_ctx *ctx, int step, float zmin, 
 {
     ARG_CHECK_CTX(ctx, step > 0 && T12 && record, "reloc_corr_match_stereo_dev");
     if (int rc = corr_check(ctx, T12, vio_x, vio_y, "reloc_corr_match_stereo_dev")) return rc;
-    const StereoState::Dense &d = ctx->stereo.dense;
-    if (!d.block || d.w == 0) { reloc_set_error("no dense stereo pass on this context yet"); return RELOC_E_STATE; }
     HostStaging st{ctx};
-    const OccSrc src{nullptr, 0, depth_grid(d.mm, 0, d.w, d.h, d.w, step, ctx->cam.K4, zmin, zmax)};
-    return corr_tick(ctx, st, OCC_SRC_DEPTH_U16, src, T12, vio_x, vio_y, record, surface);
+    return corr_tick(ctx, st, frame_from_stereo(st, step, zmin, zmax), T12, vio_x, vio_y, record, surface);
 }
 
 RELOC_API int reloc_corr_read_map(reloc_ctx *ctx, uint8_t *plane, int32_t *w, int32_t *h)
@@ -430,7 +404,7 @@ RELOC_API int reloc_corr_read_map(reloc_ctx *ctx, uint8_t *plane, int32_t *w, in
     const int64_t cells = (int64_t)s.w * s.h;
     HostStaging st{ctx};
     uint8_t *d = st.slot<uint8_t>(6, cells);
-    st.launch(k_corr_unpack, dim3(corr_grid(cells)), dim3(256), (const uint32_t *)s.map, d, s.w, s.h, s.mp);
+    st.launch(k_corr_unpack, dim3(grid_1d(cells, 1024)), dim3(256), (const uint32_t *)s.map, d, s.w, s.h, s.mp);
     st.download(plane, d, cells);
     return st.finish();
 }

@@ -264,6 +264,16 @@ void *HostStaging::slot_bytes(int s, int64_t bytes)
     return rc ? nullptr : p;
 }
 
+int DevBlock::reserve(reloc_ctx *ctx, size_t need)
+{
+    if (p && bytes >= need) return RELOC_OK;
+    if (p) HIP_TRY(hipStreamSynchronize(ctx->stream));      // work in flight may still use the block
+    release();
+    HIP_TRY(hipMalloc((void **)&p, need));
+    bytes = need;
+    return RELOC_OK;
+}
+
 void HostStaging::hip(hipError_t e, const char *what)
 {
     if (rc || e == hipSuccess) return;

@@ -407,15 +407,33 @@ struct StereoState {
     }
 };
 
+// A device block that a map state owns: grown when too small, never shrunk.  Its layout is a list of carve() lines in block order
+// that layout() walks twice on every configure / set-map call: for the size, then behind reserve() for the pointers (those of the
+// first walk mean nothing; a caller turns its state off when layout() fails).
+struct DevBlock {
+    uint8_t *p = nullptr;
+    size_t bytes = 0;
+    int reserve(reloc_ctx *ctx, size_t need);      // replaces a missing or smaller block, a live one behind a drain of ctx's stream (reloc_ctx.hip)
+    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+    template <typename T, size_t ALIGN = alignof(T)>      // count elements of T at the next multiple of ALIGN from `at`, which moves behind them
+    T *carve(size_t &at, int64_t count) const
+    {
+        static_assert(ALIGN % alignof(T) == 0 && 256 % ALIGN == 0, "hipMalloc aligns a block to 256 bytes");
+        const size_t here = at = (at + ALIGN - 1) / ALIGN * ALIGN;
+        at += (size_t)count * sizeof(T);
+        return reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(p) + here);
+    }
+    template <typename Fn>      // lines(): the carve() lines from offset 0, returns the bytes they take
+    int layout(reloc_ctx *ctx, Fn lines) { if (int rc = reserve(ctx, lines())) return rc; lines(); return RELOC_OK; }
+};
+
 // Teach-time occupancy map of a context (reloc_occ_configure; include/reloc_spec.h "OCCUPANCY"; reloc_occupancy.hip); 0 x 0 = none,
-// the default: a context that never configures a map allocates and launches nothing of it.  One device block of its own,
-// taken by reloc_occ_configure and freed by occ_release.
+// the default: a context that never configures a map allocates and launches nothing of it.  One DevBlock of its own.
 struct OccState {
     int w = 0, h = 0;                    // cells
     int sub = RELOC_OCC_SUBSAMPLE_DEFAULT;
     double ox = 0, oy = 0, res = 0, z_lo = 0, z_hi = 0;
-    uint8_t *block = nullptr;            // the pointers below lie in it
-    int64_t block_cells = 0;             // the cells it was sized for
+    DevBlock block;                      // the pointers below lie in it
     int32_t *acc = nullptr;              // w * h: sums of the cells beyond the on-chip window, zero between frames
     int64_t *counters = nullptr;         // frames_integrated, total_points_integrated, frames_skipped_empty
     int32_t *frame = nullptr;            // the last frame: rays, box of its far rays
@@ -425,17 +443,17 @@ struct OccState {
 };
 
 // Depth-correlation anchor of a context (include/reloc_spec.h "CORRELATION"; reloc_correlation.hip); 0 x 0 = no map, the default: a
-// context that never sets a correlation map allocates and launches nothing of it.  Two device blocks of its own: the map's
-// (reloc_corr_set_map*) and the search's (reloc_corr_configure), both freed by corr_release.
+// context that never sets a correlation map allocates and launches nothing of it.  Two DevBlocks of its own: the map's
+// (reloc_corr_set_map*) and the search's (reloc_corr_configure).
 struct CorrState {
     int w = 0, h = 0, mp = 0;            // the map: cells, words per packed row
     double ox = 0, oy = 0, res = 0;
-    uint8_t *map_block = nullptr;        // two packed planes of map_words words: the dilation goes from one to the other
-    int64_t map_words = 0;
+    DevBlock map_block;                  // two packed planes of h x mp words: the dilation goes from one to the other
+    uint32_t *plane[2] = {};
     uint32_t *map = nullptr;             // the one that holds the dilated map
     int n_side = 0, min_points = 0, half = 0;      // offsets per axis (0: not configured); the window is 2 * half + 1 cells a side
     double z_lo = 0, z_hi = 0, max_range = 0;
-    uint8_t *cfg_block = nullptr;        // the pointers below lie in it, sized for the limits of reloc_spec.h
+    DevBlock cfg_block;                  // the pointers below lie in it, sized for the limits of reloc_spec.h
     uint32_t *list = nullptr;            // the last tick's scan: the non-zero words of the window's bitmap (row << 5 | word, bits)
     int32_t *surface = nullptr;          // n_side x n_side hits of the last tick
     int32_t *table = nullptr;            // n_side cell offsets
@@ -445,20 +463,18 @@ struct CorrState {
 };
 
 // Route clearance of a context (include/reloc_spec.h "ROUTE"; reloc_route.hip); 0 x 0 = no map, the default: a context that never
-// sets a route map or a costmap allocates and launches nothing of it.  Two device blocks of its own: the map's
-// (reloc_route_set_map*) and the costmap's (reloc_route_set_costmap), both freed by route_release.
+// sets a route map or a costmap allocates and launches nothing of it.  Two DevBlocks of its own: the map's
+// (reloc_route_set_map*) and the costmap's (reloc_route_set_costmap).
 struct RouteState {
     int w = 0, h = 0, mp = 0, ws = 0;    // the map: cells, words per packed row, bytes per row of the two byte planes (32 * mp)
     int cap = 0;
-    uint8_t *block = nullptr;            // the pointers below lie in it
-    int64_t block_bytes = 0;
+    DevBlock block;                      // the pointers below lie in it
     uint32_t *bits = nullptr;            // h x mp: the occupied plane with the stamps, one bit per cell
     uint8_t *rowd = nullptr;             // h x ws: capped distance to the nearest occupied cell of the same row
     uint8_t *clear = nullptr;            // h x ws: the clearance plane (d)
     int32_t *row_remap = nullptr, *col_remap = nullptr;      // h and w entries (e)
     int cw = 0, ch = 0;                  // the costmap: cells
-    int8_t *cost = nullptr;              // ch x cw, a block of its own
-    int64_t cost_bytes = 0;
+    DevBlock cost;                       // ch x cw int8, a block of its own
     bool on() const { return w > 0; }
     bool has_cost() const { return cw > 0; }
 };
@@ -709,15 +725,21 @@ int image_gray_plain(reloc_ctx *c, const uint8_t *src, int w, int h, int sstride
 // working frame.  stereo_release: the events of a context that had stereo on.
 int stereo_frame(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img_right_dev, int w, int h, int order, int *ww, int *wh);
 void stereo_release(reloc_ctx *ctx);
-// the occupancy map's block, if the context has one (reloc_occupancy.hip)
+// blocks of a 1-D grid-stride launch of 256 threads over n elements: at least one, at most max_blocks
+static inline unsigned grid_1d(int64_t n, int max_blocks) { const int64_t b = (n + 255) / 256; return (unsigned)(b < 1 ? 1 : b < max_blocks ? b : max_blocks); }
+// an entry point that needs a map the context lacks: RELOC_E_STATE
+static inline int need_map(bool on, const char *who, const char *what, const char *setter)
+{
+    if (!on) reloc_set_error("%s: no %s map on this context (%s)", who, what, setter);
+    return on ? RELOC_OK : RELOC_E_STATE;
+}
+// the blocks of the occupancy map, the correlation anchor and the route clearance (each in its own file); leaves the state a new context's
 void occ_release(reloc_ctx *ctx);
-// the correlation anchor's blocks, if the context has any (reloc_correlation.hip)
 void corr_release(reloc_ctx *ctx);
+void route_release(reloc_ctx *ctx);
 // an occupied plane on the device (h x w uint8, non-zero = occupied; from_units: the occupancy map's int8 units, occupied from
 // RELOC_OCC_UNITS_OCC) as h packed rows of mp = ceil(w / 32) words, the bits beyond column w - 1 clear (reloc_correlation.hip)
 void corr_pack_plane(HostStaging &st, const void *plane, bool from_units, uint32_t *bits, int w, int h, int mp);
-// the route clearance's blocks, if the context has any (reloc_route.hip)
-void route_release(reloc_ctx *ctx);
 // Dense stereo depth: both eyes' frames (ctx->frame_img, right->frame_img, w x h as handed in) through the gray half of their
 // chains, each on its own stream, no ORB; then k_stereo_dense and k_stereo_dense_finish on ctx's stream into ctx->stereo.dense
 // (mm: dense rows of *ww uint16).  Checks stereo on, right != ctx, capacity and the chains' agreement.

@@ -160,7 +160,7 @@ __global__ __launch_bounds__(256) void k_occ_classify(const int8_t *__restrict__
 // ---- host ---------------------------------------------------------------------------------------------------------------
 void occ_release(reloc_ctx *ctx)
 {
-    if (ctx->occ.block) (void)hipFree(ctx->occ.block);
+    ctx->occ.block.release();
     ctx->occ = OccState{};
 }
 
@@ -176,44 +176,36 @@ RELOC_API int reloc_occ_configure(reloc_ctx *ctx, double origin_x, double origin
     }
     OccState &o = ctx->occ;
     const int64_t cells = (int64_t)w_cells * h_cells;
-    const size_t acc_bytes = (size_t)((cells * 4 + 7) & ~(int64_t)7);
-    const size_t bytes = acc_bytes + 3 * 8 + OCC_FRAME_WORDS * 4 + (size_t)cells * 2;
-    if (!o.block || o.block_cells != cells) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        occ_release(ctx);
-        HIP_TRY(hipMalloc((void **)&o.block, bytes));
-        o.block_cells = cells;
-        o.acc = (int32_t *)o.block;
-        o.counters = (int64_t *)(o.block + acc_bytes);
-        o.frame = (int32_t *)(o.block + acc_bytes + 3 * 8);
-        o.units = (int8_t *)(o.block + acc_bytes + 3 * 8 + OCC_FRAME_WORDS * 4);
-        o.pgm = (uint8_t *)o.units + cells;
-    }
+    if (int rc = o.block.layout(ctx, [&] {
+            size_t at = 0;
+            o.acc = o.block.carve<int32_t>(at, cells);
+            o.counters = o.block.carve<int64_t, 8>(at, 3);
+            o.frame = o.block.carve<int32_t>(at, OCC_FRAME_WORDS);
+            o.units = o.block.carve<int8_t>(at, cells);
+            o.pgm = o.block.carve<uint8_t>(at, cells);
+            return at;
+        })) { occ_release(ctx); return rc; }
     o.w = w_cells; o.h = h_cells; o.sub = subsample;
     o.ox = origin_x; o.oy = origin_y; o.res = res; o.z_lo = z_lo; o.z_hi = z_hi;
-    HIP_TRY(hipMemsetAsync(o.block, 0, bytes, ctx->stream));
+    HIP_TRY(hipMemsetAsync(o.block.p, 0, (size_t)(o.pgm + cells - o.block.p), ctx->stream));      // what this geometry takes of the block
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return RELOC_OK;
 }
 
 static int occ_check(reloc_ctx *ctx, const double *T12, const char *who)
 {
-    if (!ctx->occ.on()) { reloc_set_error("%s: no occupancy map on this context (reloc_occ_configure)", who); return RELOC_E_STATE; }
-    for (int k = 0; k < 12; ++k)
-        if (!occ_finite(T12[k])) { reloc_set_error("bad argument: %s: the transform must be finite", who); return RELOC_E_ARG; }
-    return RELOC_OK;
+    if (int rc = occ_need_map(ctx, who)) return rc;
+    return frame_transform_check(T12, who);
 }
 
 // A frame: the two launches on the context's stream, then the frame's rays into *out_rays (may be NULL); !wait: enqueues only.
-static int occ_frame(reloc_ctx *ctx, HostStaging &st, int kind, const OccSrc &src, const double *T12, int32_t *out_rays, bool wait)
+static int occ_frame(reloc_ctx *ctx, HostStaging &st, const FrameSrc &f, const double *T12, int32_t *out_rays, bool wait)
 {
     const OccState &o = ctx->occ;
     OccT T;
     memcpy(T.v, T12, sizeof(T.v));
     const OccGeom g{o.ox, o.oy, o.res, o.z_lo, o.z_hi, o.w, o.h, o.sub};
-    st.launch(kind == OCC_SRC_POINTS ? k_occ_integrate<OCC_SRC_POINTS> : kind == OCC_SRC_DEPTH_F32 ? k_occ_integrate<OCC_SRC_DEPTH_F32>
-                                                                                                 : k_occ_integrate<OCC_SRC_DEPTH_U16>,
-              dim3(1), dim3(1024), src, T, g, o.units, o.acc, o.counters, o.frame);
+    st.launch(FRAME_KERNEL(k_occ_integrate, f.kind), dim3(1), dim3(1024), f.src, T, g, o.units, o.acc, o.counters, o.frame);
     st.launch(k_occ_apply, dim3(64), dim3(256), o.units, o.acc, (const int32_t *)o.frame, o.w, o.h);
     if (!wait) return st.rc;
     const int32_t rays = st.count(o.frame);
@@ -227,8 +219,7 @@ RELOC_API int reloc_occ_integrate_points(reloc_ctx *ctx, const float *pts, int n
     ARG_CHECK_CTX(ctx, n >= 0 && (pts || n == 0) && T12, "reloc_occ_integrate_points");
     if (int rc = occ_check(ctx, T12, "reloc_occ_integrate_points")) return rc;
     HostStaging st{ctx};
-    const OccSrc src{n > 0 ? st.upload_slot(5, pts, (int64_t)n * 3) : nullptr, n, {}};
-    return occ_frame(ctx, st, OCC_SRC_POINTS, src, T12, out_rays, true);
+    return occ_frame(ctx, st, frame_from_cloud(st, pts, n), T12, out_rays, true);
 }
 
 RELOC_API int reloc_occ_integrate_depth(reloc_ctx *ctx, const void *depth, int is_f32, int w, int h, int step, const double K4[4],
@@ -236,11 +227,8 @@ RELOC_API int reloc_occ_integrate_depth(reloc_ctx *ctx, const void *depth, int i
 {
     ARG_CHECK_CTX(ctx, depth && w > 0 && h > 0 && step > 0 && K4 && T12, "reloc_occ_integrate_depth");
     if (int rc = occ_check(ctx, T12, "reloc_occ_integrate_depth")) return rc;
-    if ((int64_t)w * h > (int64_t)ctx->max_w * ctx->max_h) { reloc_set_error("depth image exceeds ctx capacity"); return RELOC_E_CAPACITY; }
     HostStaging st{ctx};
-    const void *ddepth = st.upload_slot(5, (const uint8_t *)depth, (int64_t)w * h * (is_f32 ? 4 : 2));
-    const OccSrc src{nullptr, 0, depth_grid(ddepth, is_f32, w, h, w, step, K4, zmin, zmax)};
-    return occ_frame(ctx, st, is_f32 ? OCC_SRC_DEPTH_F32 : OCC_SRC_DEPTH_U16, src, T12, out_rays, true);
+    return occ_frame(ctx, st, frame_from_depth(st, depth, is_f32, w, h, step, K4, zmin, zmax), T12, out_rays, true);
 }
 
 // The plane of the last dense stereo pass where it lies.  out_rays == NULL: enqueues only, the host never waits.
@@ -248,24 +236,20 @@ RELOC_API int reloc_occ_integrate_stereo_dev(reloc_ctx *ctx, int step, float zmi
 {
     ARG_CHECK_CTX(ctx, step > 0 && T12, "reloc_occ_integrate_stereo_dev");
     if (int rc = occ_check(ctx, T12, "reloc_occ_integrate_stereo_dev")) return rc;
-    const StereoState::Dense &d = ctx->stereo.dense;
-    if (!d.block || d.w == 0) { reloc_set_error("no dense stereo pass on this context yet"); return RELOC_E_STATE; }
     HostStaging st{ctx};
-    const OccSrc src{nullptr, 0, depth_grid(d.mm, 0, d.w, d.h, d.w, step, ctx->cam.K4, zmin, zmax)};
-    return occ_frame(ctx, st, OCC_SRC_DEPTH_U16, src, T12, out_rays, out_rays != nullptr);
+    return occ_frame(ctx, st, frame_from_stereo(st, step, zmin, zmax), T12, out_rays, out_rays != nullptr);
 }
 
 RELOC_API int reloc_occ_read(reloc_ctx *ctx, int8_t *units, uint8_t *pgm, int64_t counters[3])
 {
     ARG_CHECK_CTX(ctx, true, "reloc_occ_read");
+    if (int rc = occ_need_map(ctx, "reloc_occ_read")) return rc;
     const OccState &o = ctx->occ;
-    if (!o.on()) { reloc_set_error("reloc_occ_read: no occupancy map on this context (reloc_occ_configure)"); return RELOC_E_STATE; }
     const int64_t cells = (int64_t)o.w * o.h;
     HostStaging st{ctx};
     if (units) st.download(units, o.units, cells);
     if (pgm) {
-        st.launch(k_occ_classify, dim3((unsigned)((cells + 255) / 256 < 1024 ? (cells + 255) / 256 : 1024)), dim3(256), (const int8_t *)o.units,
-                  o.pgm, o.w, o.h);
+        st.launch(k_occ_classify, dim3(grid_1d(cells, 1024)), dim3(256), (const int8_t *)o.units, o.pgm, o.w, o.h);
         st.download(pgm, o.pgm, cells);
     }
     if (counters) st.download(counters, o.counters, 3 * 8);

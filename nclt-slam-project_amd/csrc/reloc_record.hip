@@ -513,10 +513,8 @@ RELOC_API int reloc_depth_points(reloc_ctx *ctx, const void *depth, int is_f32, 
                                  float zmin, float zmax, float *points, int32_t *n_out)
 {
     ARG_CHECK_CTX(ctx, depth && points && n_out && w > 0 && h > 0 && step > 0 && K4, "reloc_depth_points");
-    if ((int64_t)w * h > (int64_t)ctx->max_w * ctx->max_h) { reloc_set_error("depth image exceeds ctx capacity"); return RELOC_E_CAPACITY; }
     HostStaging st{ctx};
-    const void *ddepth = st.upload_slot(5, (const uint8_t *)depth, (int64_t)w * h * (is_f32 ? 4 : 2));
-    const int32_t n = depth_cloud(st, depth_grid(ddepth, is_f32, w, h, w, step, K4, zmin, zmax), points);
+    const int32_t n = depth_cloud(st, frame_from_depth(st, depth, is_f32, w, h, step, K4, zmin, zmax).src.grid, points);
     if (int rc = st.finish()) return rc;
     *n_out = n;
     return RELOC_OK;
@@ -532,7 +530,7 @@ RELOC_API int reloc_stereo_frame_points(reloc_ctx *ctx, reloc_ctx *right, const 
     StereoPairStaging st(ctx, right);
     st.upload_pair(img, img_right, w, h);
     st.run([&] { return stereo_dense_frame(ctx, right, w, h, order, &w, &h); });      // from here on the working frame
-    const int32_t n = depth_cloud(st, depth_grid(ctx->stereo.dense.mm, 0, w, h, w, step, ctx->cam.K4, zmin, zmax), points);
+    const int32_t n = depth_cloud(st, frame_from_stereo(st, step, zmin, zmax).src.grid, points);      // the pass just enqueued
     if (int rc = st.finish()) return rc;
     *n_out = n;
     return RELOC_OK;

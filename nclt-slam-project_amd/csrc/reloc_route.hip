@@ -150,12 +150,10 @@ __global__ __launch_bounds__(256) void k_route_search(const void *__restrict__ p
 // ---- host ---------------------------------------------------------------------------------------------------------------
 void route_release(reloc_ctx *ctx)
 {
-    if (ctx->route.block) (void)hipFree(ctx->route.block);
-    if (ctx->route.cost) (void)hipFree(ctx->route.cost);
+    ctx->route.block.release();
+    ctx->route.cost.release();
     ctx->route = RouteState{};
 }
-
-static inline unsigned route_grid(int64_t n) { const int64_t b = (n + 255) / 256; return (unsigned)(b < 1 ? 1 : b < 4096 ? b : 4096); }
 
 static int route_capacity(int w, int h, const char *who)
 {
@@ -189,21 +187,16 @@ static int route_map_begin(reloc_ctx *ctx, int w, int h, int cap)
 {
     RouteState &s = ctx->route;
     const int mp = (w + 31) / 32, ws = 32 * mp;
-    const int64_t plane = (int64_t)ws * h;
-    const int64_t bytes = (int64_t)mp * h * 4 + 2 * plane + ((int64_t)h + w) * 4;
     s.w = s.h = 0;
-    if (!s.block || s.block_bytes < bytes) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (s.block) (void)hipFree(s.block);
-        s.block = nullptr; s.block_bytes = 0;
-        HIP_TRY(hipMalloc((void **)&s.block, (size_t)bytes));
-        s.block_bytes = bytes;
-    }
-    s.rowd = s.block;                             // the planes of 32-byte rows first: their uint4 stores stay aligned
-    s.clear = s.rowd + plane;
-    s.bits = (uint32_t *)(s.clear + plane);
-    s.row_remap = (int32_t *)(s.bits + (int64_t)mp * h);
-    s.col_remap = s.row_remap + h;
+    if (int rc = s.block.layout(ctx, [&] {
+            size_t at = 0;
+            s.rowd = s.block.carve<uint8_t, 16>(at, (int64_t)ws * h);      // rows of 32 bytes first: k_route_rows stores uint4
+            s.clear = s.block.carve<uint8_t, 16>(at, (int64_t)ws * h);
+            s.bits = s.block.carve<uint32_t>(at, (int64_t)mp * h);
+            s.row_remap = s.block.carve<int32_t>(at, h);
+            s.col_remap = s.block.carve<int32_t>(at, w);
+            return at;
+        })) return rc;
     s.mp = mp; s.ws = ws; s.cap = cap;
     return RELOC_OK;
 }
@@ -218,8 +211,8 @@ static int route_map_build(reloc_ctx *ctx, HostStaging &st, int w, int h, const 
     corr_pack_plane(st, plane, from_units, s.bits, w, h, s.mp);
     if (n_stamps > 0)
         st.launch(k_route_stamp, dim3(n_stamps), dim3(256), (const int32_t *)st.upload_slot(5, stamps, (int64_t)n_stamps * 4), s.bits, w, h, s.mp);
-    st.launch(k_route_rows, dim3(route_grid(words)), dim3(256), (const uint32_t *)s.bits, s.rowd, h, s.mp, cap);
-    st.launch(k_route_cols, dim3(route_grid((int64_t)S * h)), dim3(256), (const uint32_t *)s.rowd, (uint32_t *)s.clear, h, S, cap);
+    st.launch(k_route_rows, dim3(grid_1d(words, 4096)), dim3(256), (const uint32_t *)s.bits, s.rowd, h, s.mp, cap);
+    st.launch(k_route_cols, dim3(grid_1d((int64_t)S * h, 4096)), dim3(256), (const uint32_t *)s.rowd, (uint32_t *)s.clear, h, S, cap);
     std::vector<int32_t> ident;
     if (!row_remap || !col_remap) {
         ident.resize(w > h ? w : h);
@@ -247,20 +240,15 @@ RELOC_API int reloc_route_set_map_from_occ(reloc_ctx *ctx, const int32_t *stamps
                                            const int32_t *col_remap)
 {
     ARG_CHECK_CTX(ctx, n_stamps >= 0 && (stamps || n_stamps == 0), "reloc_route_set_map_from_occ: n_stamps >= 0 with their rectangles");
+    if (int rc = occ_need_map(ctx, "reloc_route_set_map_from_occ")) return rc;
     const OccState &o = ctx->occ;
-    if (!o.on()) { reloc_set_error("reloc_route_set_map_from_occ: no occupancy map on this context (reloc_occ_configure)"); return RELOC_E_STATE; }
     if (int rc = route_map_check(o.w, o.h, stamps, n_stamps, cap, row_remap, col_remap, "reloc_route_set_map_from_occ")) return rc;
     if (int rc = route_map_begin(ctx, o.w, o.h, cap)) return rc;
     HostStaging st{ctx};
     return route_map_build(ctx, st, o.w, o.h, o.units, true, stamps, n_stamps, row_remap, col_remap);
 }
 
-static int route_need_map(const reloc_ctx *ctx, const char *who)
-{
-    if (ctx->route.on()) return RELOC_OK;
-    reloc_set_error("%s: no route map on this context (reloc_route_set_map)", who);
-    return RELOC_E_STATE;
-}
+static int route_need_map(const reloc_ctx *ctx, const char *who) { return need_map(ctx->route.on(), who, "route", "reloc_route_set_map"); }
 
 RELOC_API int reloc_route_read_clearance(reloc_ctx *ctx, uint8_t *plane, int32_t *w, int32_t *h)
 {
@@ -284,7 +272,7 @@ RELOC_API int reloc_route_clearance_at(reloc_ctx *ctx, const int32_t *cells_rc, 
     HostStaging st{ctx};
     const int32_t *cells = st.upload_slot(5, cells_rc, (int64_t)n * 2);
     uint8_t *d = st.slot<uint8_t>(6, n);
-    st.launch(k_route_gather, dim3(route_grid(n)), dim3(256), (const uint8_t *)s.clear, s.w, s.h, s.ws, cells, n, d);
+    st.launch(k_route_gather, dim3(grid_1d(n, 4096)), dim3(256), (const uint8_t *)s.clear, s.w, s.h, s.ws, cells, n, d);
     st.download(out, d, n);
     return st.finish();
 }
@@ -296,15 +284,9 @@ RELOC_API int reloc_route_set_costmap(reloc_ctx *ctx, const int8_t *cost, int w,
     RouteState &s = ctx->route;
     const int64_t bytes = (int64_t)w * h;
     s.cw = s.ch = 0;
-    if (!s.cost || s.cost_bytes < bytes) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (s.cost) (void)hipFree(s.cost);
-        s.cost = nullptr; s.cost_bytes = 0;
-        HIP_TRY(hipMalloc((void **)&s.cost, (size_t)bytes));
-        s.cost_bytes = bytes;
-    }
+    if (int rc = s.cost.reserve(ctx, (size_t)bytes)) return rc;
     HostStaging st{ctx};
-    st.upload(s.cost, cost, bytes);
+    st.upload(s.cost.p, cost, bytes);
     const int rc = st.finish();
     if (!rc) { s.cw = w; s.ch = h; }
     return rc;
@@ -346,7 +328,7 @@ RELOC_API int reloc_route_search(reloc_ctx *ctx, int predicate, int thresh, cons
         st.launch(k_route_search<RELOC_ROUTE_PRED_CLEARANCE>, grid, block, (const void *)s.clear, s.w, s.h, s.ws, (const int32_t *)s.row_remap,
                   (const int32_t *)s.col_remap, thresh, table, n_offsets, cells, n, d);
     else
-        st.launch(k_route_search<RELOC_ROUTE_PRED_COST>, grid, block, (const void *)s.cost, s.cw, s.ch, s.cw, (const int32_t *)nullptr,
+        st.launch(k_route_search<RELOC_ROUTE_PRED_COST>, grid, block, (const void *)s.cost.p, s.cw, s.ch, s.cw, (const int32_t *)nullptr,
                   (const int32_t *)nullptr, thresh, table, n_offsets, cells, n, d);
     st.download(out_index, d, (int64_t)n * 4);
     return st.finish();

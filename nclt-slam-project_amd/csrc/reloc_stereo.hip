@@ -304,17 +304,15 @@ RELOC_API int reloc_stereo_depth(reloc_ctx *ctx, const uint8_t *left, const uint
     return st.finish();
 }
 
-// What a stereo pass checks of its pair of contexts before it enqueues anything: stereo on, two contexts of one device and one
-// gray conversion, the frame within both capacities, the two chains in agreement as in a batch; *ww x *wh: the working frame.
+// What a stereo pass checks of its pair of contexts before it enqueues anything: what an entry point checks (stereo_pair_entry),
+// then two contexts of one device and one gray conversion, the two chains in agreement as in a batch; *ww x *wh: the working frame.
 static int stereo_pair_check(reloc_ctx *ctx, reloc_ctx *right, int w, int h, int *ww, int *wh)
 {
-    if (!ctx->stereo.on()) { reloc_set_error("stereo is off on this context (reloc_set_stereo)"); return RELOC_E_STATE; }
-    if (right == ctx) { reloc_set_error("bad argument: the right eye needs a context of its own"); return RELOC_E_ARG; }
+    if (int rc = stereo_pair_entry(ctx, right, w, h)) return rc;
     if (right->device != ctx->device || right->prm.gray_coeff_bits != ctx->prm.gray_coeff_bits) {
         reloc_set_error("stereo: the right eye's context is on another device or has another gray_coeff_bits");
         return RELOC_E_STATE;
     }
-    if (w > right->max_w || h > right->max_h || w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
     reloc_ctx *pair[2] = {ctx, right};
     *ww = w; *wh = h;
     if (int rc = image_chain_check(pair, 2, true, ww, wh)) return rc;

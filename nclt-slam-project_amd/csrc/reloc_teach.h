@@ -1,7 +1,7 @@
-// reloc_teach.h -- what the teach-side files (reloc_record.hip, reloc_stereo.hip, reloc_occupancy.hip, reloc_correlation.hip) share
+// reloc_teach.h -- what the teach-side files (reloc_record, _stereo, _occupancy, _correlation, _route .hip) share
 // and no other file includes: the ordered compaction of a 1024-thread workgroup, the depth pixel of the obstacle cloud and of the
-// occupancy map, the frame source and map point of the occupancy map and the correlation scan, and the staging of a stereo pair
-// that comes from the caller's memory.
+// occupancy map, the frame source and map point of the occupancy map and the correlation scan (host side: FrameSrc, frame_from_*,
+// FRAME_KERNEL, frame_transform_check, occ_need_map), the staging of a stereo pair from the caller's memory.
 #pragma once
 #include "reloc_internal.h"
 
@@ -93,6 +93,36 @@ __device__ __forceinline__ bool occ_cell(double x, double origin, double res, in
 }
 
 static inline bool occ_finite(double v) { return v - v == 0.0; }
+
+// Where a frame comes from (host): the source and its OCC_SRC_* kind on an entry point's staging, clouds and depth images through
+// scratch slot 5.  A source that cannot be had leaves its code in st.rc and its text in the error: all behind it is a no-op.
+struct FrameSrc { OccSrc src; int kind; };
+#define FRAME_KERNEL(kern, kind) /* the instantiation of a kernel template <int SRC> for a kind */ \
+    ((kind) == OCC_SRC_POINTS ? kern<OCC_SRC_POINTS> : (kind) == OCC_SRC_DEPTH_F32 ? kern<OCC_SRC_DEPTH_F32> : kern<OCC_SRC_DEPTH_U16>)
+
+static inline FrameSrc frame_from_cloud(HostStaging &st, const float *pts, int n) { return {{n > 0 ? st.upload_slot(5, pts, (int64_t)n * 3) : nullptr, n, {}}, OCC_SRC_POINTS}; }
+static inline FrameSrc frame_from_depth(HostStaging &st, const void *depth, int is_f32, int w, int h, int step, const double K4[4], float zmin, float zmax)
+{
+    if (!st.rc && (int64_t)w * h > (int64_t)st.ctx->max_w * st.ctx->max_h) { reloc_set_error("depth image exceeds ctx capacity"); st.rc = RELOC_E_CAPACITY; }
+    const void *ddepth = st.upload_slot(5, (const uint8_t *)depth, (int64_t)w * h * (is_f32 ? 4 : 2));
+    return {{nullptr, 0, depth_grid(ddepth, is_f32, w, h, w, step, K4, zmin, zmax)}, is_f32 ? OCC_SRC_DEPTH_F32 : OCC_SRC_DEPTH_U16};
+}
+// the millimetre plane of the context's last dense stereo pass where it lies, under the context's camera
+static inline FrameSrc frame_from_stereo(HostStaging &st, int step, float zmin, float zmax)
+{
+    const StereoState::Dense &d = st.ctx->stereo.dense;
+    if (!st.rc && (!d.block || d.w == 0)) { reloc_set_error("no dense stereo pass on this context yet"); st.rc = RELOC_E_STATE; }
+    return {{nullptr, 0, depth_grid(d.mm, 0, d.w, d.h, d.w, step, st.ctx->cam.K4, zmin, zmax)}, OCC_SRC_DEPTH_U16};
+}
+// the 3 x 4 transform of a frame: every value finite
+static inline int frame_transform_check(const double *T12, const char *who)
+{
+    for (int k = 0; k < 12; ++k)
+        if (!occ_finite(T12[k])) { reloc_set_error("bad argument: %s: the transform must be finite", who); return RELOC_E_ARG; }
+    return RELOC_OK;
+}
+// what reads the context's occupancy grid, the *_from_occ calls included (its plane and geometry are ctx->occ's)
+static inline int occ_need_map(const reloc_ctx *ctx, const char *who) { return need_map(ctx->occ.on(), who, "occupancy", "reloc_occ_configure"); }
 
 // What an entry point checks of a stereo pair before it enqueues anything.
 static inline int stereo_pair_entry(const reloc_ctx *ctx, const reloc_ctx *right, int w, int h)

@@ -533,6 +533,10 @@ class Engine:
             raise N.RelocError(f"{what}: a packed 4:2:2 frame must have an even width")
         return img
 
+    def _record_arrays(self):
+        mf = self.max_feat
+        return np.empty((mf, 2), np.float32), np.empty((mf, 32), np.uint8), np.empty((mf, 3), np.float32), np.empty(mf, np.int32)
+
     def record_frame(self, bgr: np.ndarray, depth_mm: np.ndarray, nfeatures: int = 500, order_rgb: bool = False):
         """teach-side record arrays of one frame: dict(xy (n,2), desc (n,32), pts3d (n,3), kp_index (n,), n, n_kp); bgr:
         (H, W, 3), the (H, W) mosaic with the Bayer stage on, or a frame of the pixel format"""
@@ -541,9 +545,7 @@ class Engine:
         h, w = bgr.shape[:2]
         if depth_mm.shape != (h, w):
             raise N.RelocError("record_frame: depth and colour sizes differ")
-        mf = self.max_feat
-        xy = np.empty((mf, 2), np.float32); desc = np.empty((mf, 32), np.uint8); pts = np.empty((mf, 3), np.float32)
-        idx = np.empty(mf, np.int32)
+        xy, desc, pts, idx = self._record_arrays()
         n, nk = N.outs(i32, i32)
         self._api.reloc_record_frame(self._ctx, bgr, depth_mm, w, h, int(order_rgb), int(nfeatures), xy, desc, pts, idx, n, nk)
         k = n.value
@@ -593,9 +595,7 @@ class Engine:
         """record_frame with the right eye's frame in the depth image's place (reloc_record_frame_stereo): right_engine
         carries that eye's image chain.  The dict of record_frame plus n_stereo, the keypoints with a stereo depth."""
         bgr, right_frame, w, h = self._stereo_pair(bgr, right_frame, right_engine, "record_frame_stereo")
-        mf = self.max_feat
-        xy = np.empty((mf, 2), np.float32); desc = np.empty((mf, 32), np.uint8); pts = np.empty((mf, 3), np.float32)
-        idx = np.empty(mf, np.int32)
+        xy, desc, pts, idx = self._record_arrays()
         n, nk, ns = N.outs(i32, i32, i32)
         self._api.reloc_record_frame_stereo(self._ctx, right_engine._ctx, bgr, right_frame, w, h, int(order_rgb), int(nfeatures),
                                             xy, desc, pts, idx, n, nk, ns)
@@ -830,16 +830,43 @@ class Engine:
 
     def depth_points(self, depth, step: int = 4, K4=K4_DEFAULT, zmin: float = 0.3, zmax: float = 10.0):
         """(n, 3) float32 obstacle points (z, -x, -y) of every step-th valid depth pixel, raster order"""
-        depth = np.ascontiguousarray(depth)
-        if depth.dtype not in (np.float32, np.uint16) or depth.ndim != 2:
-            raise N.RelocError("depth_points: expected an (H, W) float32 (metres) or uint16 (millimetres) image")
-        h, w = depth.shape
-        K4 = np.ascontiguousarray(K4, np.float64)
+        depth, is_f32, w, h = self._depth_image(depth, "depth_points")
         pts = np.empty((-(-w // step) * -(-h // step), 3), np.float32)
         n = i32()
-        self._api.reloc_depth_points(self._ctx, depth, int(depth.dtype == np.float32), w, h, int(step), K4, float(zmin),
-                                     float(zmax), pts, n)
+        self._api.reloc_depth_points(self._ctx, depth, is_f32, w, h, int(step), np.ascontiguousarray(K4, np.float64), float(zmin), float(zmax), pts, n)
         return pts[: n.value].copy()
+
+    @staticmethod
+    def _depth_image(depth, what):
+        """(depth, is_f32, w, h) of an (H, W) float32 (metres) or uint16 (millimetres) image, as the depth entry points take them"""
+        depth = np.ascontiguousarray(depth)
+        if depth.dtype not in (np.float32, np.uint16) or depth.ndim != 2:
+            raise N.RelocError(f"{what}: expected an (H, W) float32 (metres) or uint16 (millimetres) image")
+        return depth, int(depth.dtype == np.float32), depth.shape[1], depth.shape[0]
+
+    @staticmethod
+    def _cloud(points, what):
+        """(points, n) of an (n, 3) float32 cloud, as the cloud entry points take them: None for an empty one"""
+        pts = np.ascontiguousarray(points, np.float32)
+        if pts.size and (pts.ndim != 2 or pts.shape[1] != 3):
+            raise N.RelocError(f"{what}: expected an (n, 3) cloud")
+        return (pts if pts.size else None), pts.size // 3
+
+    @staticmethod
+    def _occupied_plane(occupied, what):
+        """a non-empty (H, W) plane of any dtype, non-zero = occupied, as C-contiguous uint8 of 0 / 1"""
+        occ = np.asarray(occupied)
+        if occ.ndim != 2 or occ.size == 0:
+            raise N.RelocError(f"{what}: expected a non-empty (H, W) plane")
+        return np.ascontiguousarray(occ != 0, np.uint8)
+
+    def _read_plane(self, entry_point, dtype=np.uint8):
+        """the (H, W) plane of an entry point (ctx, plane, &w, &h) that answers its size when asked without a plane"""
+        w, h = N.outs(i32, i32)
+        entry_point(self._ctx, None, w, h)
+        plane = np.zeros((h.value, w.value), dtype)
+        entry_point(self._ctx, plane, None, None)
+        return plane
 
     # ------------------------------------------------------------------ teach-time occupancy map (reloc_spec.h "OCCUPANCY")
     def occ_configure(self, origin_x: float, origin_y: float, res: float, w_cells: int, h_cells: int, z_lo: float = 0.2,
@@ -860,23 +887,15 @@ class Engine:
 
     def occ_integrate_points(self, points, T) -> int:
         """one frame from an (n, 3) float32 cloud in the sensor frame; returns the number of rays"""
-        pts = np.ascontiguousarray(points, np.float32)
-        if pts.size and (pts.ndim != 2 or pts.shape[1] != 3):
-            raise N.RelocError("occ_integrate_points: expected an (n, 3) cloud")
         rays = i32()
-        self._api.reloc_occ_integrate_points(self._ctx, pts if pts.size else None, pts.size // 3, self._occ_T(T, "occ_integrate_points"), rays)
+        self._api.reloc_occ_integrate_points(self._ctx, *self._cloud(points, "occ_integrate_points"), self._occ_T(T, "occ_integrate_points"), rays)
         return rays.value
 
     def occ_integrate_depth(self, depth, T, step: int = 4, K4=K4_DEFAULT, zmin: float = 0.3, zmax: float = 10.0) -> int:
         """one frame from a depth image as depth_points takes it; the cloud is never written"""
-        depth = np.ascontiguousarray(depth)
-        if depth.dtype not in (np.float32, np.uint16) or depth.ndim != 2:
-            raise N.RelocError("occ_integrate_depth: expected an (H, W) float32 (metres) or uint16 (millimetres) image")
-        h, w = depth.shape
         rays = i32()
-        self._api.reloc_occ_integrate_depth(self._ctx, depth, int(depth.dtype == np.float32), w, h, int(step),
-                                            np.ascontiguousarray(K4, np.float64), float(zmin), float(zmax),
-                                            self._occ_T(T, "occ_integrate_depth"), rays)
+        self._api.reloc_occ_integrate_depth(self._ctx, *self._depth_image(depth, "occ_integrate_depth"), int(step),
+                                            np.ascontiguousarray(K4, np.float64), float(zmin), float(zmax), self._occ_T(T, "occ_integrate_depth"), rays)
         return rays.value
 
     def occ_integrate_stereo(self, T, step: int = 4, zmin: float = 0.3, zmax: float = 10.0, wait: bool = True):
@@ -899,10 +918,7 @@ class Engine:
     # ------------------------------------------------------------------ depth-correlation anchor (reloc_spec.h "CORRELATION")
     def corr_set_map(self, occupied, origin_x: float, origin_y: float, res: float, dilate: int = 1):
         """the teach map: an (H, W) plane, row 0 at origin_y, non-zero = occupied; dilated `dilate` times on the device"""
-        occ = np.ascontiguousarray(occupied)
-        if occ.ndim != 2 or occ.size == 0:
-            raise N.RelocError("corr_set_map: expected a non-empty (H, W) plane")
-        occ = np.ascontiguousarray(occ != 0, np.uint8)
+        occ = self._occupied_plane(occupied, "corr_set_map")
         h, w = occ.shape
         self._api.reloc_corr_set_map(self._ctx, occ, w, h, float(origin_x), float(origin_y), float(res), int(dilate))
 
@@ -924,23 +940,16 @@ class Engine:
 
     def corr_match_points(self, points, T, vio_x: float, vio_y: float, surface: bool = False):
         """one tick from an (n, 3) float32 cloud in the sensor frame: (record of 8 int32, surface [i][j] or None)"""
-        pts = np.ascontiguousarray(points, np.float32)
-        if pts.size and (pts.ndim != 2 or pts.shape[1] != 3):
-            raise N.RelocError("corr_match_points: expected an (n, 3) cloud")
         rec, surf = self._corr_out(surface)
-        self._api.reloc_corr_match_points(self._ctx, pts if pts.size else None, pts.size // 3, self._occ_T(T, "corr_match_points"),
+        self._api.reloc_corr_match_points(self._ctx, *self._cloud(points, "corr_match_points"), self._occ_T(T, "corr_match_points"),
                                           float(vio_x), float(vio_y), rec, surf)
         return rec, surf
 
     def corr_match_depth(self, depth, T, vio_x: float, vio_y: float, step: int = 4, K4=K4_DEFAULT, zmin: float = 0.3, zmax: float = 10.0,
                          surface: bool = False):
         """one tick from a depth image as depth_points takes it; the cloud is never written"""
-        depth = np.ascontiguousarray(depth)
-        if depth.dtype not in (np.float32, np.uint16) or depth.ndim != 2:
-            raise N.RelocError("corr_match_depth: expected an (H, W) float32 (metres) or uint16 (millimetres) image")
-        h, w = depth.shape
         rec, surf = self._corr_out(surface)
-        self._api.reloc_corr_match_depth(self._ctx, depth, int(depth.dtype == np.float32), w, h, int(step), np.ascontiguousarray(K4, np.float64),
+        self._api.reloc_corr_match_depth(self._ctx, *self._depth_image(depth, "corr_match_depth"), int(step), np.ascontiguousarray(K4, np.float64),
                                          float(zmin), float(zmax), self._occ_T(T, "corr_match_depth"), float(vio_x), float(vio_y), rec, surf)
         return rec, surf
 
@@ -953,11 +962,7 @@ class Engine:
 
     def corr_read_map(self):
         """the dilated teach map: (H, W) bool, row 0 at origin_y"""
-        w, h = i32(), i32()
-        self._api.reloc_corr_read_map(self._ctx, None, w, h)
-        plane = np.zeros((h.value, w.value), np.uint8)
-        self._api.reloc_corr_read_map(self._ctx, plane, None, None)
-        return plane.astype(bool)
+        return self._read_plane(self._api.reloc_corr_read_map).astype(bool)
 
     # ------------------------------------------------------------------ route clearance (reloc_spec.h "ROUTE")
     @staticmethod
@@ -969,10 +974,7 @@ class Engine:
     def route_set_map(self, occupied, stamps=None, cap: int = 19, row_remap=None, col_remap=None):
         """the occupied plane: (H, W), row 0 at origin_y, non-zero = occupied; stamps: (n, 4) cell rectangles r_lo, r_hi, c_lo,
         c_hi OR-ed in on the device; the clearance plane is computed with `cap`; the remap tables of rule (e), None = identity"""
-        occ = np.ascontiguousarray(occupied)
-        if occ.ndim != 2 or occ.size == 0:
-            raise N.RelocError("route_set_map: expected a non-empty (H, W) plane")
-        occ = np.ascontiguousarray(occ != 0, np.uint8)
+        occ = self._occupied_plane(occupied, "route_set_map")
         h, w = occ.shape
         s, n, rr, cr = self._route_map_args(stamps, row_remap, col_remap)
         if (rr is not None and rr.shape != (h,)) or (cr is not None and cr.shape != (w,)):
@@ -989,11 +991,7 @@ class Engine:
 
     def route_read_clearance(self):
         """the clearance plane: (H, W) uint8, row 0 at origin_y, 255 = no occupied cell within cap"""
-        w, h = i32(), i32()
-        self._api.reloc_route_read_clearance(self._ctx, None, w, h)
-        plane = np.zeros((h.value, w.value), np.uint8)
-        self._api.reloc_route_read_clearance(self._ctx, plane, None, None)
-        return plane
+        return self._read_plane(self._api.reloc_route_read_clearance)
 
     @staticmethod
     def _route_cells(cells, what):

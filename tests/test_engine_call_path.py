@@ -96,6 +96,38 @@ def test_image_rows_refuses_with_the_callers_message():
     assert image_rows(np.zeros((8, 8, 4), np.uint8), (4,), "four").shape == (8, 8, 4)
 
 
+# ---- what the map layer's methods take: checked once, refused with the method's name --------------------------------------
+def test_depth_image_helper():
+    for dtype in (np.float32, np.uint16):
+        img = np.arange(12, dtype=dtype).reshape(3, 4)
+        depth, is_f32, w, h = Engine._depth_image(img, "m")
+        assert depth.dtype == dtype and np.array_equal(depth, img) and (is_f32, w, h) == (int(dtype == np.float32), 4, 3)
+        assert Engine._depth_image(np.zeros((6, 8), dtype)[:, ::2], "m")[0].flags.c_contiguous
+    for bad in (np.zeros((3, 4), np.float64), np.zeros((3, 4, 1), np.float32), np.zeros(12, np.uint16), np.zeros((3, 4), np.int16)):
+        with pytest.raises(N.RelocError, match=r"^some_method: expected an \(H, W\) float32 \(metres\) or uint16 \(millimetres\) image$"):
+            Engine._depth_image(bad, "some_method")
+
+
+def test_cloud_helper():
+    for empty in (np.zeros((0, 3), np.float32), [], np.zeros((0, 2))):
+        assert Engine._cloud(empty, "m") == (None, 0)
+    pts, n = Engine._cloud(np.arange(12, dtype=np.float64).reshape(4, 3)[::2], "m")
+    assert n == 2 and pts.dtype == np.float32 and pts.flags.c_contiguous and pts.tolist() == [[0, 1, 2], [6, 7, 8]]
+    for bad in (np.zeros((4, 2)), np.zeros(6), np.zeros((2, 3, 1))):
+        with pytest.raises(N.RelocError, match=r"^some_method: expected an \(n, 3\) cloud$"):
+            Engine._cloud(bad, "some_method")
+
+
+def test_occupied_plane_helper():
+    want = np.array([[0, 1, 1], [1, 0, 1]], np.uint8)
+    for plane in (want.astype(bool), want * 255, want.astype(np.int8) * -3, want * 0.5, (want.astype(np.int32) * 7).T.copy().T, want.tolist()):
+        got = Engine._occupied_plane(plane, "m")
+        assert got.dtype == np.uint8 and got.flags.c_contiguous and np.array_equal(got, want)
+    for bad in (np.zeros((0, 4), np.uint8), np.zeros((4, 0), bool), np.zeros((2, 3, 1), np.uint8), np.zeros(6, np.uint8)):
+        with pytest.raises(N.RelocError, match=r"^some_method: expected a non-empty \(H, W\) plane$"):
+            Engine._occupied_plane(bad, "some_method")
+
+
 # ---- the frame format is the context's --------------------------------------------------------------------------------
 def _records_equal(got, exp):
     assert got.keys() == exp.keys()
