@@ -208,13 +208,6 @@ __global__ __launch_bounds__(1024) void k_corr_pick(const int32_t *__restrict__ 
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
-void corr_release(reloc_ctx *ctx)
-{
-    ctx->corr.map_block.release();
-    ctx->corr.cfg_block.release();
-    ctx->corr = CorrState{};
-}
-
 // half the window's side for a range and a cell size; RELOC_E_CAPACITY beyond RELOC_CORR_MAX_WINDOW
 static int corr_window(double max_range, double res, int *half)
 {
@@ -241,11 +234,7 @@ static int corr_map_begin(reloc_ctx *ctx, int w, int h, double ox, double oy, do
     if (s.configured())
         if (int rc = corr_window(s.max_range, res, &half)) return rc;
     const int mp = (w + 31) / 32;
-    if (int rc = s.map_block.layout(ctx, [&] {
-            size_t at = 0;
-            for (uint32_t *&plane : s.plane) plane = s.map_block.carve<uint32_t>(at, (int64_t)mp * h);
-            return at;
-        })) { s.w = s.h = 0; return rc; }
+    if (int rc = s.map_block.layout(ctx, [&](BlockCarver &c) { for (uint32_t *&plane : s.plane) c(plane, (int64_t)mp * h); })) return rc;
     s.w = w; s.h = h; s.mp = mp; s.ox = ox; s.oy = oy; s.res = res;
     if (s.configured()) s.half = half;
     return RELOC_OK;
@@ -308,14 +297,12 @@ RELOC_API int reloc_corr_configure(reloc_ctx *ctx, const int32_t *cell_offsets, 
     int half = 0;
     if (int rc = corr_window(max_range, s.res, &half)) return rc;
     static_assert(RELOC_CORR_MAX_TABLE <= 256, "the table's room in the search's block");
-    if (int rc = s.cfg_block.layout(ctx, [&] {      // sized for the limits: taken once
-            size_t at = 0;
-            s.list = s.cfg_block.carve<uint32_t, 8>(at, CORR_LIST_WORDS);      // k_corr_correlate reads uint2
-            s.surface = s.cfg_block.carve<int32_t>(at, RELOC_CORR_MAX_TABLE * RELOC_CORR_MAX_TABLE);
-            s.table = s.cfg_block.carve<int32_t>(at, 256);
-            s.record = s.cfg_block.carve<int32_t>(at, CORR_REC_DEV);
-            return at;
-        })) { s.n_side = 0; return rc; }
+    if (int rc = s.cfg_block.layout(ctx, [&](BlockCarver &c) {      // sized for the limits: taken once
+            c.aligned<8>(s.list, CORR_LIST_WORDS);      // k_corr_correlate reads uint2
+            c(s.surface, RELOC_CORR_MAX_TABLE * RELOC_CORR_MAX_TABLE);
+            c(s.table, 256);
+            c(s.record, CORR_REC_DEV);
+        })) return rc;
     HostStaging st{ctx};
     st.upload(s.table, cell_offsets, (int64_t)n_side * 4);
     if (int rc = st.finish()) { s.n_side = 0; return rc; }

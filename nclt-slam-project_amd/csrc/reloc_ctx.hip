@@ -25,12 +25,11 @@ RELOC_API int reloc_device_count(void)
 
 static int ctx_alloc(reloc_ctx *c)
 {
-    int rc = orb_alloc(c);
-    rc |= scan_alloc(c);
-    rc |= tick_alloc(c);
-    rc |= ctx_dev_alloc(c, &c->frame_img, (int64_t)c->max_w * c->max_h * 3);
-    rc |= ctx_dev_alloc(c, &c->accum_res, 1);
-    return rc;
+    if (int rc = orb_alloc(c)) return rc;
+    if (int rc = scan_alloc(c)) return rc;
+    if (int rc = tick_alloc(c)) return rc;
+    if (int rc = frame_img_reserve(c, 3)) return rc;
+    return c->accum_block.layout(c, [&](BlockCarver &b) { b.own(c->accum_res, 1); });
 }
 
 int g_reloc_live_contexts = 0;
@@ -107,13 +106,8 @@ RELOC_API void reloc_destroy(reloc_ctx *c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (DbArena &db : c->db_slot) db_arena_release(db);      // owner or adopter alike: one reference each
-    for (void *p : c->dev_blocks) (void)hipFree(p);
-    for (void *p : c->scratch) if (p) (void)hipFree(p);
     tick_release(c);
     stereo_release(c);
-    occ_release(c);
-    corr_release(c);
-    route_release(c);
     for (int k = 0; k < RELOC_PROF_N; ++k)
         if (c->prof[k].init)
             for (int i = 0; i < RELOC_PROF_RING; ++i) {
@@ -124,7 +118,7 @@ RELOC_API void reloc_destroy(reloc_ctx *c)
     if (c->t1) (void)hipEventDestroy(c->t1);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     __atomic_sub_fetch(&g_reloc_live_contexts, 1, __ATOMIC_RELAXED);
-    delete c;
+    delete c;      // the device blocks go with their owners (DevBlock): the device is current and the stream drained
 }
 
 RELOC_API int reloc_get_params(reloc_ctx *c, reloc_params *out)
@@ -250,28 +244,41 @@ RELOC_API int reloc_timer_end(reloc_ctx *c, float *ms)
 // ---- staging of the host-pointer entry points (HostStaging, reloc_internal.h) -----------------------------------
 void *HostStaging::slot_bytes(int s, int64_t bytes)
 {
-    void *&p = ctx->scratch[s];
-    int64_t &cap = ctx->scratch_bytes[s];
-    if (!rc && cap < bytes) {
-        if (p) hip(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");      // work in flight may still use the slot
-        if (p && !rc) hip(hipFree(p), "hipFree(scratch)");
-        if (!rc) {
-            p = nullptr; cap = 0;
-            hip(hipMalloc(&p, (size_t)(bytes + bytes / 4 + 4096)), "hipMalloc(scratch)");
-            if (!rc) cap = bytes + bytes / 4 + 4096;
-        }
-    }
-    return rc ? nullptr : p;
+    DevBlock &b = ctx->scratch[s];
+    if (!rc && (int64_t)b.bytes < bytes) rc = b.reserve(ctx, (size_t)(bytes + bytes / 4 + 4096));
+    return rc ? nullptr : b.p;
 }
 
-int DevBlock::reserve(reloc_ctx *ctx, size_t need)
+// ---- the one owner of a context's device memory (DevBlock, reloc_internal.h) ---------------------------------------------
+int DevBlock::reserve(reloc_ctx *ctx, size_t need, size_t keep)
 {
     if (p && bytes >= need) return RELOC_OK;
-    if (p) HIP_TRY(hipStreamSynchronize(ctx->stream));      // work in flight may still use the block
-    release();
-    HIP_TRY(hipMalloc((void **)&p, need));
+    uint8_t *grown = nullptr;
+    if (hipError_t e = hipMalloc((void **)&grown, need ? need : 1); e != hipSuccess) {
+        (void)hipGetLastError();      // the context lives on with the old block: no sticky error for its next launch check
+        reloc_set_error("hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
+        return RELOC_E_HIP;
+    }
+    if (p) {
+        hipError_t e = hipStreamSynchronize(ctx->stream);      // work in flight may still use the old block
+        if (e == hipSuccess && keep) e = hipMemcpy(grown, p, keep, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(grown);
+            reloc_set_error("growing a device block failed: %s", hipGetErrorString(e));
+            return RELOC_E_HIP;
+        }
+        (void)hipFree(p);
+    }
+    p = grown;
     bytes = need;
     return RELOC_OK;
+}
+
+void DevBlock::release()
+{
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
 }
 
 void HostStaging::hip(hipError_t e, const char *what)

@@ -1143,7 +1143,7 @@ RELOC_API int reloc_set_bayer(reloc_ctx *ctx, int code)
         return RELOC_E_STATE;
     }
     if (code && !b.plane)       // first enable: the gray plane of the largest mosaic
-        if (int rc = ctx_dev_alloc(ctx, &b.plane, stage_plane_bytes(ctx))) return rc;
+        if (int rc = b.block.layout(ctx, [&](BlockCarver &c) { c.own(b.plane, stage_plane_bytes(ctx)); })) return rc;
     b.code = code;
     return RELOC_OK;
 }
@@ -1156,16 +1156,11 @@ RELOC_API int reloc_get_bayer(reloc_ctx *ctx, int32_t *code)
 }
 
 // ---- pixel format entry points ------------------------------------------------------------------------------
-// the staging plane holds frames of bpp bytes per pixel; grown once, to 4 (frames in flight may still read the old one)
-static int frame_img_reserve(reloc_ctx *ctx, int bpp)
+// the staging plane holds frames of bpp bytes per pixel: 3 from creation, grown once, to 4; nothing of it survives the growth
+int frame_img_reserve(reloc_ctx *ctx, int bpp)
 {
     if (bpp <= ctx->frame_img_bpp) return RELOC_OK;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    uint8_t *old = ctx->frame_img, *grown = nullptr;
-    if (int rc = ctx_dev_alloc(ctx, &grown, (int64_t)ctx->max_w * ctx->max_h * bpp)) return rc;
-    ctx->dev_blocks.erase(std::find(ctx->dev_blocks.begin(), ctx->dev_blocks.end(), (void *)old));
-    (void)hipFree(old);
-    ctx->frame_img = grown;
+    if (int rc = ctx->frame_block.layout(ctx, [&](BlockCarver &c) { c.own(ctx->frame_img, (int64_t)ctx->max_w * ctx->max_h * bpp); })) return rc;
     ctx->frame_img_bpp = bpp;
     return RELOC_OK;
 }
@@ -1215,7 +1210,7 @@ RELOC_API int reloc_set_pixel_format(reloc_ctx *ctx, int fmt)
     }
     if (pixfmt_packed(fmt)) {
         if (!p.plane)           // first enable of a packed format: the gray plane of the largest frame
-            if (int rc = ctx_dev_alloc(ctx, &p.plane, stage_plane_bytes(ctx))) return rc;
+            if (int rc = p.block.layout(ctx, [&](BlockCarver &c) { c.own(p.plane, stage_plane_bytes(ctx)); })) return rc;
         if (int rc = frame_img_reserve(ctx, pixfmt_422(fmt) ? 2 : 4)) return rc;
     }
     p.fmt = fmt;
@@ -1245,11 +1240,11 @@ RELOC_API int reloc_set_clahe(reloc_ctx *ctx, double clip_limit, int tiles_x, in
     }
     ARG_CHECK(clahe_args_ok(clip_limit, tiles_x, tiles_y),
               "reloc_set_clahe: tiles_x and tiles_y must both be 0 (off) or both in 1..64, and clip_limit finite");
-    if (!c.plane) {
-        // first enable, one block: the plane of the largest frame, then the LUTs of the largest grid
-        if (int rc = ctx_dev_alloc(ctx, &c.plane, stage_plane_bytes(ctx) + (size_t)CLAHE_MAX_TILES * CLAHE_MAX_TILES * 256)) return rc;
-        c.lut = c.plane + stage_plane_bytes(ctx);
-    }
+    if (!c.plane)       // first enable, one block: the plane of the largest frame, then the LUTs of the largest grid
+        if (int rc = c.block.layout(ctx, [&](BlockCarver &b) {
+                b.own(c.plane, stage_plane_bytes(ctx));
+                b.aligned<64>(c.lut, (int64_t)CLAHE_MAX_TILES * CLAHE_MAX_TILES * 256);
+            })) return rc;
     c.clip = clip_limit == 0.0 ? 0.0 : clip_limit;     // -0 -> +0: equal settings compare equal
     c.tx = tiles_x; c.ty = tiles_y;
     return RELOC_OK;
@@ -1291,11 +1286,13 @@ RELOC_API int reloc_set_rectify_map(reloc_ctx *ctx, const int16_t *xy, const uin
     if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("rectification map exceeds ctx capacity"); return RELOC_E_CAPACITY; }
     if (!r.plane) {
         // first enable, one block: the plane, then maps and depth of the largest frame
-        const size_t px = (size_t)ctx->max_w * ctx->max_h;
-        if (int rc = ctx_dev_alloc(ctx, &r.plane, stage_plane_bytes(ctx) + px * 4 + px * 2 + px * 2)) return rc;
-        r.xy = (int16_t *)(r.plane + stage_plane_bytes(ctx));
-        r.alpha = (uint16_t *)(r.xy + px * 2);
-        r.depth = r.alpha + px;
+        const int64_t px = (int64_t)ctx->max_w * ctx->max_h;
+        if (int rc = r.block.layout(ctx, [&](BlockCarver &c) {
+                c.own(r.plane, stage_plane_bytes(ctx));
+                c.aligned<64>(r.xy, px * 2);
+                c.aligned<4>(r.alpha, px);
+                c(r.depth, px);
+            })) return rc;
     }
     // frames in flight may still read the previous map
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1423,14 +1420,13 @@ RELOC_API int reloc_set_resize(reloc_ctx *ctx, int sw, int sh, int dw, int dh)
     // and axis for the depth
     const size_t area_words = 6 * ((size_t)ctx->max_w + ctx->max_h), near_words = (size_t)ctx->max_w + ctx->max_h;
     if (area.tab.size() > area_words || nearest.tab.size() > near_words) { reloc_set_error("resize tables exceed ctx capacity"); return RELOC_E_CAPACITY; }
-    if (!r.plane) {
-        // first enable, one block: the plane, then the tables and the depth plane
-        const size_t bytes = stage_plane_bytes(ctx) + (area_words + near_words) * 4 + (size_t)ctx->max_w * ctx->max_h * 2;
-        if (int rc = ctx_dev_alloc(ctx, &r.plane, bytes)) return rc;
-        r.tab = (int32_t *)(r.plane + stage_plane_bytes(ctx));
-        r.ntab = r.tab + area_words;
-        r.depth = (uint16_t *)(r.ntab + near_words);
-    }
+    if (!r.plane)       // first enable, one block: the plane, then the tables and the depth plane
+        if (int rc = r.block.layout(ctx, [&](BlockCarver &c) {
+                c.own(r.plane, stage_plane_bytes(ctx));
+                c.aligned<64>(r.tab, area_words);
+                c(r.ntab, near_words);
+                c.aligned<4>(r.depth, (int64_t)ctx->max_w * ctx->max_h);
+            })) return rc;
     // frames in flight may still read the previous tables
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (!area.tab.empty()) HIP_TRY(hipMemcpy(r.tab, area.tab.data(), area.tab.size() * 4, hipMemcpyHostToDevice));

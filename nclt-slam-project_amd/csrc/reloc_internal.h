@@ -9,6 +9,7 @@
 
 #include "../../include/reloc.h"
 #include "../../include/reloc_spec.h"
+#include "reloc_block_layout.h"
 #include "reloc_orb_plan.h"
 
 #define RELOC_API extern "C" __attribute__((visibility("default")))
@@ -147,13 +148,14 @@ struct PnpOut {
 // quad_perm / mirror steps leave a row's result in all of its 16 lanes, row_bcast15 / row_bcast31 carry it
 // across the four rows, lane 63 ends with the total.  A chain of such reductions costs a few VALU
 // instructions each instead of six dependent ds_bpermute round trips.  All 64 lanes must be active.
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v)
+template <bool MAX>      // the wave's maximum (MAX) or minimum
+__device__ __forceinline__ unsigned wave_minmax_u32(unsigned v)
 {
     int x = (int)v;
 #define RELOC_DPP_STEP(ctrl, rmask)                                                                     \
     {                                                                                                   \
         const unsigned o = (unsigned)__builtin_amdgcn_update_dpp(x, x, ctrl, rmask, 0xF, false);         \
-        x = (int)((unsigned)x > o ? (unsigned)x : o);                                                    \
+        x = (int)((MAX ? (unsigned)x > o : (unsigned)x < o) ? (unsigned)x : o);                          \
     }
     RELOC_DPP_STEP(0xB1, 0xF)    // quad_perm [1,0,3,2]
     RELOC_DPP_STEP(0x4E, 0xF)    // quad_perm [2,3,0,1]
@@ -164,6 +166,8 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v)
 #undef RELOC_DPP_STEP
     return (unsigned)__builtin_amdgcn_readlane(x, 63);
 }
+__device__ __forceinline__ unsigned wave_max_u32(unsigned v) { return wave_minmax_u32<true>(v); }
+__device__ __forceinline__ unsigned wave_min_u32(unsigned v) { return wave_minmax_u32<false>(v); }
 
 // value of lane (l ^ K) for K = 1, 2, 4, 8 through DPP (quad permutes, row shifts with bank masks, row rotate)
 template <int K>
@@ -273,11 +277,43 @@ struct ScanMask {
 };
 
 // ---- context state ("Context state") ------------------------------------------------------------------------
-// Device memory: every fixed block (ctx_alloc's buffers, the one block of a stage's first enable) comes from ctx_dev_alloc
-// and is freed by reloc_destroy from ctx->dev_blocks, the scratch slots of HostStaging in the same place; a DbArena owns its
-// database.  Settings: one struct per image stage and one for the camera, next to the buffers they fill.  on(): the stage
-// runs.  same(): two contexts may share a batched launch; it compares every setting of its struct and no buffer, and nothing
-// else decides that (ctx_batch_check, image_chain_check*): a new setting is compared because it is a member of its stage.
+// Device memory: every block of a context is a DevBlock member of the state that uses it (one per lifetime, laid out by one
+// carve list in the state's file) and goes with the context; a DbArena owns its database.  Settings: one struct per image
+// stage and one for the camera, next to the buffers they fill.  on(): the stage runs.  same(): two contexts may share a
+// batched launch; it compares every setting of its struct and no buffer, and nothing else decides that (ctx_batch_check,
+// image_chain_check*): a new setting is compared because it is a member of its stage.
+
+// A device block that a context owns: grown when too small, never shrunk, freed with its owner (move-only).  Its layout is a
+// list of carve lines in block order (BlockCarver, reloc_block_layout.h) that layout() walks twice: for the size, writing
+// nothing, then behind reserve() for the pointers.  A failed reserve() or layout() leaves the block, its size and every pointer
+// carved from it as they were.
+struct DevBlock {
+    uint8_t *p = nullptr;
+    size_t bytes = 0;
+    DevBlock() = default;
+    DevBlock(DevBlock &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBlock &operator=(DevBlock &&o) noexcept
+    {
+        if (this != &o) { release(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; }
+        return *this;
+    }
+    ~DevBlock() { release(); }
+    // Replaces a missing or smaller block: the new one is allocated first, then, behind a drain of ctx's stream (work in flight
+    // may still use the old one), the first `keep` bytes move over and the old one is freed (reloc_ctx.hip)
+    int reserve(reloc_ctx *ctx, size_t need, size_t keep = 0);
+    template <typename Fn>      // lines(BlockCarver &): the carve lines
+    int layout(reloc_ctx *ctx, Fn lines, size_t keep = 0)
+    {
+        BlockCarver size;
+        lines(size);
+        if (int rc = reserve(ctx, size.at, keep)) return rc;
+        BlockCarver commit{p};
+        lines(commit);
+        return RELOC_OK;
+    }
+private:
+    void release();
+};
 
 // camera (reference M:49-52, M:107-112) and lens (reloc_set_camera, reloc_set_distortion)
 struct CameraModel {
@@ -297,6 +333,7 @@ struct CameraModel {
 // Bayer stage in front of the whole image chain (reloc_set_bayer): every frame of the chain's entry points is a raw 8-bit mosaic
 struct BayerStage {
     int code = 0;                        // RELOC_BAYER_*2BGR; 0 = off, the default
+    DevBlock block;                      // taken on the first enable
     uint8_t *plane = nullptr;            // demosaiced gray plane, row stride (w + 63) & ~63
     bool on() const { return code != 0; }
     bool same(const BayerStage &o) const { return code == o.code; }
@@ -307,6 +344,7 @@ struct BayerStage {
 // the head-of-chain stage k_unpack, in the Bayer stage's place (the two exclude each other)
 struct PixfmtStage {
     int fmt = RELOC_FMT_BGR;
+    DevBlock block;                      // taken on the first enable of a packed format
     uint8_t *plane = nullptr;            // unpacked gray plane of a packed format, row stride (w + 63) & ~63
     bool on() const { return fmt >= RELOC_FMT_BGRA; }                    // the unpack stage runs
     int bpp() const { return fmt == RELOC_FMT_BGR ? 3 : fmt == RELOC_FMT_MONO8 ? 1 : fmt <= RELOC_FMT_RGBA ? 4 : 2; }
@@ -319,6 +357,7 @@ struct ResizeStage {
     int sw = 0, sh = 0;                  // the size every frame must have
     int dw = 0, dh = 0;                  // the working frame: what rectification, CLAHE, ORB, the recorder and the camera see
     int kind = 0, isx = 1, isy = 1;      // kernel kind and integer box of the INTER_AREA resize (reloc_image.hip): derived from the sizes
+    DevBlock block;                      // taken on the first enable; the pointers below lie in it
     int32_t *tab = nullptr;              // INTER_AREA tap lists
     int32_t *ntab = nullptr;             // INTER_NEAREST offsets of the depth image
     uint8_t *plane = nullptr;            // resized gray plane, row stride (dw + 63) & ~63
@@ -330,6 +369,7 @@ struct ResizeStage {
 // rectification in front of ORB and CLAHE on 3-channel frames (reloc_set_rectify_map); 0 x 0 = off, the default
 struct RectifyStage {
     int w = 0, h = 0;                    // map = frame size
+    DevBlock block;                      // taken on the first enable; the pointers below lie in it
     int16_t *xy = nullptr;               // max_h x max_w x 2, dense rows of w
     uint16_t *alpha = nullptr;           // max_h x max_w
     uint8_t *plane = nullptr;            // rectified gray plane, row stride (w + 63) & ~63
@@ -342,6 +382,7 @@ struct RectifyStage {
 struct ClaheStage {
     double clip = 0.0;                   // clipLimit (0 when off; -0 normalised to +0)
     int tx = 0, ty = 0;                  // tileGridSize
+    DevBlock block;                      // taken on the first enable; the pointers below lie in it
     uint8_t *plane = nullptr;            // equalised gray plane, row stride (w + 63) & ~63
     uint8_t *lut = nullptr;              // tiles_y x tiles_x x 256 LUTs (64 x 64 x 256 bytes)
     bool on() const { return tx > 0; }
@@ -351,6 +392,7 @@ struct ClaheStage {
 // ORB's detection mask on the working frame of the image chain (reloc_set_orb_mask); 0 x 0 = off, the default
 struct OrbMaskStage {
     int w = 0, h = 0;                    // the persistent mask = working-frame size
+    DevBlock block;                      // both pyramids, taken on the first use of a mask; grows with the arenas (orb_grow)
     uint8_t *pyr = nullptr;              // its mask pyramid, geometry of orb.buf.pyr; level 0 is the mask as given
     uint8_t *call = nullptr;             // the same for the mask of one reloc_orb_detect_compute_masked call
     bool built = false;                  // levels 1.. of pyr belong to the mask of level 0 (k_mask_level ran since it was set)
@@ -375,7 +417,7 @@ struct MatchPolicy {
 struct StereoState {
     double baseline = 0.0;               // metres
     int min_disp = 0, num_disp = RELOC_STEREO_NUM_DISP_DEFAULT, uniq = RELOC_STEREO_UNIQUENESS_DEFAULT, lr = 1;
-    uint8_t *block = nullptr;            // the one device block of the first enable; the four pointers below lie in it
+    DevBlock block;                      // taken on the first enable; the four pointers below lie in it (stereo_sparse_lines)
     uint8_t *plane = nullptr;            // right eye's gray plane where its chain has no stage on (dense rows)
     uint16_t *mm = nullptr;              // max_feat: depth of the keypoints of the frame's ORB output
     float *disp = nullptr;               // max_feat
@@ -387,7 +429,7 @@ struct StereoState {
     // Dense stereo depth ("STEREO, dense"): one block of max_w x max_h pixels, taken on the first dense call of the context
     // (stereo_dense_alloc); a context that never asks for a dense plane has none of it.
     struct Dense {
-        uint8_t *block = nullptr;        // the pointers below lie in it
+        DevBlock block;                  // the pointers below lie in it (stereo_dense_lines)
         uint32_t *rmap = nullptr;        // the right disparity map as cost << 11 | d' keys, KEY_NONE = no candidate
         uint2 *best = nullptr;           // per pixel d* | C(d*) << 16, C(d* - 1) | C(d* + 1) << 16: k_stereo_dense to k_stereo_dense_finish
         float *disp = nullptr;
@@ -400,35 +442,10 @@ struct StereoState {
     // the default.  It labels in the dense block's best plane, which k_stereo_dense_finish has read by then: no memory of its own.
     int speckle_window = 0, speckle_range = 1;
     bool on() const { return baseline > 0.0; }
-    // the settings, no buffer: reloc_set_stereo returns at once where nothing changes
-    bool same(const StereoState &o) const
-    {
-        return baseline == o.baseline && min_disp == o.min_disp && num_disp == o.num_disp && uniq == o.uniq && lr == o.lr;
-    }
-};
-
-// A device block that a map state owns: grown when too small, never shrunk.  Its layout is a list of carve() lines in block order
-// that layout() walks twice on every configure / set-map call: for the size, then behind reserve() for the pointers (those of the
-// first walk mean nothing; a caller turns its state off when layout() fails).
-struct DevBlock {
-    uint8_t *p = nullptr;
-    size_t bytes = 0;
-    int reserve(reloc_ctx *ctx, size_t need);      // replaces a missing or smaller block, a live one behind a drain of ctx's stream (reloc_ctx.hip)
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-    template <typename T, size_t ALIGN = alignof(T)>      // count elements of T at the next multiple of ALIGN from `at`, which moves behind them
-    T *carve(size_t &at, int64_t count) const
-    {
-        static_assert(ALIGN % alignof(T) == 0 && 256 % ALIGN == 0, "hipMalloc aligns a block to 256 bytes");
-        const size_t here = at = (at + ALIGN - 1) / ALIGN * ALIGN;
-        at += (size_t)count * sizeof(T);
-        return reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(p) + here);
-    }
-    template <typename Fn>      // lines(): the carve() lines from offset 0, returns the bytes they take
-    int layout(reloc_ctx *ctx, Fn lines) { if (int rc = reserve(ctx, lines())) return rc; lines(); return RELOC_OK; }
 };
 
 // Teach-time occupancy map of a context (reloc_occ_configure; include/reloc_spec.h "OCCUPANCY"; reloc_occupancy.hip); 0 x 0 = none,
-// the default: a context that never configures a map allocates and launches nothing of it.  One DevBlock of its own.
+// the default: a context that never configures a map allocates and launches nothing of it.
 struct OccState {
     int w = 0, h = 0;                    // cells
     int sub = RELOC_OCC_SUBSAMPLE_DEFAULT;
@@ -443,8 +460,8 @@ struct OccState {
 };
 
 // Depth-correlation anchor of a context (include/reloc_spec.h "CORRELATION"; reloc_correlation.hip); 0 x 0 = no map, the default: a
-// context that never sets a correlation map allocates and launches nothing of it.  Two DevBlocks of its own: the map's
-// (reloc_corr_set_map*) and the search's (reloc_corr_configure).
+// context that never sets a correlation map allocates and launches nothing of it.  Two blocks: the map's (reloc_corr_set_map*)
+// and the search's (reloc_corr_configure).
 struct CorrState {
     int w = 0, h = 0, mp = 0;            // the map: cells, words per packed row
     double ox = 0, oy = 0, res = 0;
@@ -463,8 +480,8 @@ struct CorrState {
 };
 
 // Route clearance of a context (include/reloc_spec.h "ROUTE"; reloc_route.hip); 0 x 0 = no map, the default: a context that never
-// sets a route map or a costmap allocates and launches nothing of it.  Two DevBlocks of its own: the map's
-// (reloc_route_set_map*) and the costmap's (reloc_route_set_costmap).
+// sets a route map or a costmap allocates and launches nothing of it.  Two blocks: the map's (reloc_route_set_map*) and the
+// costmap's (reloc_route_set_costmap).
 struct RouteState {
     int w = 0, h = 0, mp = 0, ws = 0;    // the map: cells, words per packed row, bytes per row of the two byte planes (32 * mp)
     int cap = 0;
@@ -500,18 +517,20 @@ struct OrbState {
     PyrLds lds = {};               // LDS layout of k_pyramid, its workgroups and its dynamic LDS
     int ntiles = 0, lds_bytes = 0;
     OrbCaps caps = {};             // bytes of each of buf.pyr / nms / blur (and of a mask pyramid), entries of buf.rz and buf.tiles
-    // Device blocks, as the kernels take them; src and mask stay NULL here, a launch sets them in its copy.  tab, tiles, rz:
+    DevBlock fixed, arenas;        // what buf points into: the arenas (pyr, blur, nms) grow with the ORB parameters, the rest is fixed
+    // Device buffers, as the kernels take them; src and mask stay NULL here, a launch sets them in its copy.  tab, tiles, rz:
     // the tables of the geometry above.  pyr, blur, nms: pyramid levels, blurred levels and NMS-kept FAST score maps
     // (stage-1 source, parity tap), one geometry.  hist: NLEV x 256 score histograms.  cand_*: stage-1 lists (NLEV counters,
     // NLEV x STAGE1_CAP keys y << 16 | x and Harris responses).  kp_*: the kept keypoints in raster order per level.  dbg_cut:
     // NLEV stage-1 cut scores of the last frame.  f_*: the frame's features, max_feat rows, and their count.
     OrbFrame buf = {};
-    OrbMaskStage mask;             // detection mask between NMS and the stage-1 cut; both pyramids are one block, taken on first use
+    OrbMaskStage mask;             // detection mask between NMS and the stage-1 cut
 };
 
 // Tick, match and PnP scratch of a context (allocated and released by reloc_tick.hip); every pointer is device memory
 // except res_host / res_ext.
 struct TickState {
+    DevBlock block;                  // every device pointer below lies in it (tick_alloc)
     int32_t *cand_ids = nullptr;     // MAX_CAND candidate records of the current tick
     int32_t *cand_n = nullptr;       // 1
     int32_t *flags = nullptr;        // [0] relocating: the candidates came from the whole-database search
@@ -545,15 +564,13 @@ struct reloc_ctx {
     // the device in the middle (prof_flush synchronises)
     struct ProfSlot { hipEvent_t a[RELOC_PROF_RING], b[RELOC_PROF_RING]; int n = 0; float total = 0.f; int launches = 0; bool init = false; } prof[RELOC_PROF_N];
 
-    std::vector<void *> dev_blocks;      // every block ctx_dev_alloc handed out; reloc_destroy frees them
-    // generic scratch (grown on demand by host-pointer entry points: HostStaging)
-    void *scratch[8] = {};
-    int64_t scratch_bytes[8] = {};
+    DevBlock scratch[8];           // generic scratch, grown on demand by the host-pointer entry points (HostStaging)
 
     OrbState orb;                  // reloc_orb.hip
+    DevBlock frame_block;
     uint8_t *frame_img = nullptr;  // staging plane of the host-pointer entry points (image stages, recording, tick, ORB): the
                                    // caller's frame on the device, max_w * max_h * frame_img_bpp bytes; no ORB state
-    int frame_img_bpp = 3;         // 4 once a 4-byte pixel format was enabled or converted (frame_img_reserve)
+    int frame_img_bpp = 0;         // 3 from creation, 4 once a 4-byte pixel format was enabled or converted (frame_img_reserve)
 
     CameraModel cam;
     // the image chain's stages in its order (reloc_image.hip); a stage's buffers are one block, taken on its first enable
@@ -568,11 +585,13 @@ struct reloc_ctx {
     RouteState route;                // reloc_route.hip
     int scan_gens = 0;               // RELOC_SCAN_GENS (developer switch), read once at creation: n > 0 = single whole-database
                                      // scans in the form of batched ones (n generations of row budgets + sweepers, launch_db_count)
+    DevBlock scan_block;
     uint32_t *scan_ticket = nullptr; // SCAN_TICKET_WORDS counters of the whole-database scans (scan_alloc, reloc_scan.hip)
 
     // ---- database: two arenas; db_sel names the selected one (ctx_db below), reloc_db_select only changes db_sel ----
     DbArena db_slot[2];
     int db_sel = 0;
+    DevBlock accum_block;
     AccumResult *accum_res = nullptr;   // 1
 
     TickState tick;                  // reloc_tick.hip
@@ -580,17 +599,6 @@ struct reloc_ctx {
                                      // -1 (default) = it is while it is the only live context of this process (ctx_alone())
     bool local_two_stage = false;    // developer switch RELOC_LOCAL_TWO_STAGE=1: local candidates by k_topk_part + k_candidates_local
 };
-
-// The one allocation of a context's fixed device blocks: count elements of T (at least one), recorded for reloc_destroy
-template <typename T>
-static inline int ctx_dev_alloc(reloc_ctx *ctx, T **p, int64_t count)
-{
-    void *q = nullptr;
-    HIP_TRY(hipMalloc(&q, (size_t)(count > 0 ? count : 1) * sizeof(T)));
-    ctx->dev_blocks.push_back(q);
-    *p = (T *)q;
-    return 0;
-}
 
 // The one staging path of the host-pointer entry points, on the context's stream: scratch slots, copies in, launches,
 // copies out, finish.  The first error sticks (rc) and turns everything behind it into a no-op, so an entry point reads as
@@ -602,7 +610,7 @@ struct HostStaging {
     int rc = RELOC_OK;
     bool pending = false;       // work enqueued since the last synchronisation
     void hip(hipError_t e, const char *what);       // a HIP call's result: the first failure becomes rc and the error text
-    void *slot_bytes(int s, int64_t bytes);         // scratch slot s, re-allocated when too small (drains the stream first)
+    void *slot_bytes(int s, int64_t bytes);         // scratch slot s, grown with headroom when too small; NULL after an error
     template <typename T>
     T *slot(int s, int64_t count) { return (T *)slot_bytes(s, count * (int64_t)sizeof(T)); }       // NULL after an error
     void copy(void *dst, const void *src, int64_t bytes, hipMemcpyKind kind)
@@ -688,7 +696,9 @@ inline bool db_ready(const reloc_ctx *ctx)
     return db.desc && db.off && db.pose && db.xy_heading && db.counts && db.records > 0;
 }
 // the fixed blocks of a new context, each stage's by its own file: ORB (reloc_orb.hip), scan counters (reloc_scan.hip), tick /
-// match / PnP scratch with the pinned result record (reloc_tick.hip; tick_release lets go of that record)
+// match / PnP scratch with the pinned result record (reloc_tick.hip; tick_release lets go of that record), the staging plane
+// of bpp bytes per pixel (reloc_image.hip; grows once, to 4)
+int frame_img_reserve(reloc_ctx *ctx, int bpp);
 int orb_alloc(reloc_ctx *ctx);
 int scan_alloc(reloc_ctx *ctx);
 int tick_alloc(reloc_ctx *ctx);
@@ -733,10 +743,6 @@ static inline int need_map(bool on, const char *who, const char *what, const cha
     if (!on) reloc_set_error("%s: no %s map on this context (%s)", who, what, setter);
     return on ? RELOC_OK : RELOC_E_STATE;
 }
-// the blocks of the occupancy map, the correlation anchor and the route clearance (each in its own file); leaves the state a new context's
-void occ_release(reloc_ctx *ctx);
-void corr_release(reloc_ctx *ctx);
-void route_release(reloc_ctx *ctx);
 // an occupied plane on the device (h x w uint8, non-zero = occupied; from_units: the occupancy map's int8 units, occupied from
 // RELOC_OCC_UNITS_OCC) as h packed rows of mp = ceil(w / 32) words, the bits beyond column w - 1 clear (reloc_correlation.hip)
 void corr_pack_plane(HostStaging &st, const void *plane, bool from_units, uint32_t *bits, int w, int h, int mp);

@@ -158,12 +158,6 @@ __global__ __launch_bounds__(256) void k_occ_classify(const int8_t *__restrict__
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
-void occ_release(reloc_ctx *ctx)
-{
-    ctx->occ.block.release();
-    ctx->occ = OccState{};
-}
-
 RELOC_API int reloc_occ_configure(reloc_ctx *ctx, double origin_x, double origin_y, double res, int w_cells, int h_cells, double z_lo,
                                   double z_hi, int subsample)
 {
@@ -176,15 +170,13 @@ RELOC_API int reloc_occ_configure(reloc_ctx *ctx, double origin_x, double origin
     }
     OccState &o = ctx->occ;
     const int64_t cells = (int64_t)w_cells * h_cells;
-    if (int rc = o.block.layout(ctx, [&] {
-            size_t at = 0;
-            o.acc = o.block.carve<int32_t>(at, cells);
-            o.counters = o.block.carve<int64_t, 8>(at, 3);
-            o.frame = o.block.carve<int32_t>(at, OCC_FRAME_WORDS);
-            o.units = o.block.carve<int8_t>(at, cells);
-            o.pgm = o.block.carve<uint8_t>(at, cells);
-            return at;
-        })) { occ_release(ctx); return rc; }
+    if (int rc = o.block.layout(ctx, [&](BlockCarver &c) {
+            c(o.acc, cells);
+            c(o.counters, 3);
+            c(o.frame, OCC_FRAME_WORDS);
+            c(o.units, cells);
+            c(o.pgm, cells);
+        })) return rc;
     o.w = w_cells; o.h = h_cells; o.sub = subsample;
     o.ox = origin_x; o.oy = origin_y; o.res = res; o.z_lo = z_lo; o.z_hi = z_hi;
     HIP_TRY(hipMemsetAsync(o.block.p, 0, (size_t)(o.pgm + cells - o.block.p), ctx->stream));      // what this geometry takes of the block

@@ -1071,6 +1071,19 @@ __global__ __launch_bounds__(256) void k_describe_batch(OrbBatch b, int max_feat
 }
 
 // ------------------------------------------------------------------------------------------------
+// The three pyramid arenas, and both mask pyramids (level 0 of the persistent one first: `keep` bytes of it survive a growth),
+// of pyr_bytes each
+static int orb_arenas_layout(reloc_ctx *ctx, int64_t pyr_bytes)
+{
+    OrbFrame &b = ctx->orb.buf;
+    return ctx->orb.arenas.layout(ctx, [&](BlockCarver &c) { for (uint8_t **p : {&b.pyr, &b.blur, &b.nms}) c.own(*p, pyr_bytes); });
+}
+static int orb_mask_layout(reloc_ctx *ctx, int64_t pyr_bytes, size_t keep)
+{
+    OrbMaskStage &m = ctx->orb.mask;
+    return m.block.layout(ctx, [&](BlockCarver &c) { c.own(m.pyr, pyr_bytes); c.own(m.call, pyr_bytes); }, keep);
+}
+
 // The fixed blocks of a context's ORB state, sized for its capacity (orb_caps) and its feature rows
 int orb_alloc(reloc_ctx *ctx)
 {
@@ -1078,52 +1091,39 @@ int orb_alloc(reloc_ctx *ctx)
     OrbFrame &b = o.buf;
     const int64_t mf = ctx->max_feat, s1 = (int64_t)NLEV * RELOC_ORB_STAGE1_CAP;
     o.caps = orb_caps(ctx->max_w, ctx->max_h);
-    int rc = 0;
-    for (uint8_t **p : {&b.pyr, &b.blur, &b.nms}) rc |= ctx_dev_alloc(ctx, p, o.caps.pyr_bytes);
-    rc |= ctx_dev_alloc(ctx, &b.tab, 1);
-    rc |= ctx_dev_alloc(ctx, &b.rz, o.caps.rz_entries);
-    rc |= ctx_dev_alloc(ctx, &b.tiles, o.caps.tiles);
-    rc |= ctx_dev_alloc(ctx, &b.hist, NLEV * 256);
-    for (int32_t **p : {&b.cand_cnt, &b.kp_cnt, &b.dbg_cut}) rc |= ctx_dev_alloc(ctx, p, NLEV);
-    for (uint32_t **p : {&b.cand_key, &b.kp_key}) rc |= ctx_dev_alloc(ctx, p, s1);
-    for (float **p : {&b.cand_resp, &b.kp_resp}) rc |= ctx_dev_alloc(ctx, p, s1);
-    rc |= ctx_dev_alloc(ctx, &b.f_xy, mf * 2);
-    for (float **p : {&b.f_size, &b.f_angle, &b.f_resp}) rc |= ctx_dev_alloc(ctx, p, mf);
-    rc |= ctx_dev_alloc(ctx, &b.f_oct, mf);
-    rc |= ctx_dev_alloc(ctx, &b.f_desc, mf * 32);
-    rc |= ctx_dev_alloc(ctx, &b.f_count, 1);
-    return rc;
+    if (int rc = orb_arenas_layout(ctx, o.caps.pyr_bytes)) return rc;
+    return o.fixed.layout(ctx, [&](BlockCarver &c) {
+        c.own(b.tab, 1);
+        c.own(b.rz, o.caps.rz_entries);
+        c.own(b.tiles, o.caps.tiles);
+        c.own(b.hist, NLEV * 256);
+        for (int32_t **p : {&b.cand_cnt, &b.kp_cnt, &b.dbg_cut}) c.own(*p, NLEV);
+        for (uint32_t **p : {&b.cand_key, &b.kp_key}) c.own(*p, s1);
+        for (float **p : {&b.cand_resp, &b.kp_resp}) c.own(*p, s1);
+        c.own(b.f_xy, mf * 2);
+        for (float **p : {&b.f_size, &b.f_angle, &b.f_resp}) c.own(*p, mf);
+        c.own(b.f_oct, mf);
+        c.own(b.f_desc, mf * 32);
+        c.own(b.f_count, 1);
+    });
 }
 
 // The blocks whose size depends on the ORB parameters (the three pyramid arenas, both mask pyramids) grown for prm when the
-// context holds less; they never shrink, and a context that keeps the defaults keeps what orb_alloc took.  Drains the
-// stream first; the arenas hold nothing that outlives a frame except level 0 of the persistent mask, which moves.
+// context holds less; they never shrink, and a context that keeps the defaults keeps what orb_alloc took.  The arenas hold
+// nothing that outlives a frame except level 0 of the persistent mask, which moves.
 static int orb_grow(reloc_ctx *ctx, const OrbParams &prm)
 {
     OrbState &o = ctx->orb;
     const OrbCaps want = orb_caps(ctx->max_w, ctx->max_h, prm);
     if (want.pyr_bytes <= o.caps.pyr_bytes) return RELOC_OK;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    auto swap_block = [ctx](uint8_t **p, int64_t bytes, int64_t keep) -> int {
-        void *q = nullptr;
-        HIP_TRY(hipMalloc(&q, (size_t)bytes));
-        if (keep > 0) HIP_TRY(hipMemcpy(q, *p, (size_t)keep, hipMemcpyDeviceToDevice));
-        for (void *&b : ctx->dev_blocks)
-            if (b == (void *)*p) b = q;
-        HIP_TRY(hipFree(*p));
-        *p = (uint8_t *)q;
-        return RELOC_OK;
-    };
-    for (uint8_t **p : {&o.buf.pyr, &o.buf.blur, &o.buf.nms})
-        if (int rc = swap_block(p, want.pyr_bytes, 0)) return rc;
     OrbMaskStage &m = o.mask;
-    if (m.pyr) {
-        const int64_t level0 = m.on() ? (int64_t)((m.w + 63) / 64 * 64) * m.h : 0;
-        if (int rc = swap_block(&m.pyr, 2 * want.pyr_bytes, level0)) return rc;
-        m.call = m.pyr + want.pyr_bytes;
+    if (m.pyr) {      // the mask block first: if the arenas fail behind it, it is only larger than it need be
+        const size_t level0 = m.on() ? (size_t)((m.w + 63) / 64 * 64) * m.h : 0;
+        if (int rc = orb_mask_layout(ctx, want.pyr_bytes, level0)) return rc;
         m.built = false;
         m.last = nullptr;
     }
+    if (int rc = orb_arenas_layout(ctx, want.pyr_bytes)) return rc;
     o.caps.pyr_bytes = want.pyr_bytes;
     o.w = o.h = o.nfeat = 0;      // the debug planes of the last frame went with the old arenas
     return RELOC_OK;
@@ -1165,10 +1165,7 @@ int orb_prepare(reloc_ctx *ctx, int w, int h, int nfeatures, const OrbParams &pr
 static int mask_alloc(reloc_ctx *ctx)
 {
     OrbMaskStage &m = ctx->orb.mask;
-    if (m.pyr) return RELOC_OK;
-    if (int rc = ctx_dev_alloc(ctx, &m.pyr, 2 * ctx->orb.caps.pyr_bytes)) return rc;
-    m.call = m.pyr + ctx->orb.caps.pyr_bytes;
-    return RELOC_OK;
+    return m.pyr ? (int)RELOC_OK : orb_mask_layout(ctx, ctx->orb.caps.pyr_bytes, 0);
 }
 
 // levels 1.. of the mask pyramid mp of a prepared context from its level 0, on the context's stream

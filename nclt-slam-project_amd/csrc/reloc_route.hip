@@ -148,13 +148,6 @@ __global__ __launch_bounds__(256) void k_route_search(const void *__restrict__ p
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
-void route_release(reloc_ctx *ctx)
-{
-    ctx->route.block.release();
-    ctx->route.cost.release();
-    ctx->route = RouteState{};
-}
-
 static int route_capacity(int w, int h, const char *who)
 {
     if (w > RELOC_ROUTE_MAX_SIDE || h > RELOC_ROUTE_MAX_SIDE || (int64_t)w * h > RELOC_OCC_MAX_CELLS) {
@@ -182,21 +175,19 @@ static int route_map_check(int w, int h, const int32_t *stamps, int n_stamps, in
     return RELOC_OK;
 }
 
-// the block of a w x h map, grown when too small; the map before is gone from here on
+// the block of a w x h map, grown when too small; a failure leaves the map before as it was, behind the layout it is gone
 static int route_map_begin(reloc_ctx *ctx, int w, int h, int cap)
 {
     RouteState &s = ctx->route;
     const int mp = (w + 31) / 32, ws = 32 * mp;
-    s.w = s.h = 0;
-    if (int rc = s.block.layout(ctx, [&] {
-            size_t at = 0;
-            s.rowd = s.block.carve<uint8_t, 16>(at, (int64_t)ws * h);      // rows of 32 bytes first: k_route_rows stores uint4
-            s.clear = s.block.carve<uint8_t, 16>(at, (int64_t)ws * h);
-            s.bits = s.block.carve<uint32_t>(at, (int64_t)mp * h);
-            s.row_remap = s.block.carve<int32_t>(at, h);
-            s.col_remap = s.block.carve<int32_t>(at, w);
-            return at;
+    if (int rc = s.block.layout(ctx, [&](BlockCarver &c) {
+            c.aligned<16>(s.rowd, (int64_t)ws * h);      // rows of 32 bytes first: k_route_rows stores uint4
+            c.aligned<16>(s.clear, (int64_t)ws * h);
+            c(s.bits, (int64_t)mp * h);
+            c(s.row_remap, h);
+            c(s.col_remap, w);
         })) return rc;
+    s.w = s.h = 0;
     s.mp = mp; s.ws = ws; s.cap = cap;
     return RELOC_OK;
 }
@@ -283,8 +274,8 @@ RELOC_API int reloc_route_set_costmap(reloc_ctx *ctx, const int8_t *cost, int w,
     if (int rc = route_capacity(w, h, "reloc_route_set_costmap")) return rc;
     RouteState &s = ctx->route;
     const int64_t bytes = (int64_t)w * h;
-    s.cw = s.ch = 0;
     if (int rc = s.cost.reserve(ctx, (size_t)bytes)) return rc;
+    s.cw = s.ch = 0;
     HostStaging st{ctx};
     st.upload(s.cost.p, cost, bytes);
     const int rc = st.finish();

@@ -669,7 +669,7 @@ struct CountPlan {
 // leave zeroes them again.
 int scan_alloc(reloc_ctx *ctx)
 {
-    if (int rc = ctx_dev_alloc(ctx, &ctx->scan_ticket, SCAN_TICKET_WORDS)) return rc;
+    if (int rc = ctx->scan_block.layout(ctx, [&](BlockCarver &c) { c.own(ctx->scan_ticket, SCAN_TICKET_WORDS); })) return rc;
     HIP_TRY(hipMemset(ctx->scan_ticket, 0, SCAN_TICKET_WORDS * sizeof(uint32_t)));
     return RELOC_OK;
 }

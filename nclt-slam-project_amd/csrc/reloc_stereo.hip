@@ -30,25 +30,6 @@ struct StereoParams {
     int min_disp, num_disp, uniq, lr;
 };
 
-// wave-wide minimum in the DPP network (wave_max_u32's steps); all 64 lanes active
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v)
-{
-    int x = (int)v;
-#define RELOC_DPP_STEP(ctrl, rmask)                                                                     \
-    {                                                                                                   \
-        const unsigned o = (unsigned)__builtin_amdgcn_update_dpp(x, x, ctrl, rmask, 0xF, false);         \
-        x = (int)((unsigned)x < o ? (unsigned)x : o);                                                    \
-    }
-    RELOC_DPP_STEP(0xB1, 0xF)    // quad_perm [1,0,3,2]
-    RELOC_DPP_STEP(0x4E, 0xF)    // quad_perm [2,3,0,1]
-    RELOC_DPP_STEP(0x141, 0xF)   // row_half_mirror
-    RELOC_DPP_STEP(0x140, 0xF)   // row_mirror
-    RELOC_DPP_STEP(0x142, 0xA)   // row_bcast15 -> rows 1, 3
-    RELOC_DPP_STEP(0x143, 0xC)   // row_bcast31 -> rows 2, 3
-#undef RELOC_DPP_STEP
-    return (unsigned)__builtin_amdgcn_readlane(x, 63);
-}
-
 // rows v - R .. v + R of img, bytes x0 .. x0 + 4 ndw - 1, as dwords dst[row * ndw + k]; a byte outside 0 <= x < w is 0 and is
 // not fetched; patch: the bytes behind the eleventh are 0 as well
 __device__ __forceinline__ void stereo_stage(const uint8_t *__restrict__ img, int stride, int w, int v, int x0, int ndw, bool patch,
@@ -229,26 +210,20 @@ RELOC_API int reloc_set_stereo(reloc_ctx *ctx, double baseline_m, int min_dispar
         return RELOC_OK;
     }
     if (int rc = stereo_args_check(baseline_m, min_disparity, num_disparities, uniqueness, lr_check, true)) return rc;
-    StereoState want = s;
-    want.baseline = baseline_m; want.min_disp = min_disparity; want.num_disp = num_disparities; want.uniq = uniqueness; want.lr = lr_check;
-    if (s.same(want)) return RELOC_OK;
-    if (!s.disp) {
-        // one block: disparities, millimetres, status of max_feat keypoints, then the right eye's plain gray plane.  The block
-        // belongs to the context from ctx_dev_alloc on (reloc_destroy frees it); the state is wired up only when the block is
-        // zeroed and both events exist, so a failure leaves the context as it was: stereo off, nothing of it alive.
-        const int64_t mf = ctx->max_feat, head = (mf * 7 + 255) / 256 * 256;
-        if (!s.block)
-            if (int rc = ctx_dev_alloc(ctx, &s.block, head + (int64_t)ctx->max_w * ctx->max_h)) return rc;
-        HIP_TRY(hipMemsetAsync(s.block, 0, (size_t)head, ctx->stream));
+    if (s.baseline == baseline_m && s.min_disp == min_disparity && s.num_disp == num_disparities && s.uniq == uniqueness && s.lr == lr_check)
+        return RELOC_OK;       // nothing changes
+    if (!s.left_ready) {
+        // first enable: the block, zeroed in front of the plane, and both events; a failure leaves stereo off
+        if (int rc = s.block.layout(ctx, [&](BlockCarver &c) { stereo_sparse_lines(c, s, ctx->max_feat, (int64_t)ctx->max_w * ctx->max_h); })) return rc;
+        HIP_TRY(hipMemsetAsync(s.block.p, 0, (size_t)(s.plane - s.block.p), ctx->stream));
         if ((!s.right_done && hipEventCreateWithFlags(&s.right_done, hipEventDisableTiming) != hipSuccess) ||
             (!s.left_ready && hipEventCreateWithFlags(&s.left_ready, hipEventDisableTiming) != hipSuccess)) {
             stereo_release(ctx);
             reloc_set_error("stereo: event creation failed");
             return RELOC_E_HIP;
         }
-        s.disp = (float *)s.block; s.mm = (uint16_t *)(s.block + mf * 4); s.status = s.block + mf * 6; s.plane = s.block + head;
     }
-    s.baseline = want.baseline; s.min_disp = want.min_disp; s.num_disp = want.num_disp; s.uniq = want.uniq; s.lr = want.lr;
+    s.baseline = baseline_m; s.min_disp = min_disparity; s.num_disp = num_disparities; s.uniq = uniqueness; s.lr = lr_check;
     return RELOC_OK;
 }
 
@@ -580,14 +555,8 @@ __global__ __launch_bounds__(256) void k_stereo_dense_finish(StereoParams p, con
 static int stereo_dense_alloc(reloc_ctx *ctx)
 {
     StereoState::Dense &d = ctx->stereo.dense;
-    if (d.block) return RELOC_OK;
-    const int64_t px = (int64_t)ctx->max_w * ctx->max_h;
-    uint8_t *blk = nullptr;
-    if (int rc = ctx_dev_alloc(ctx, &blk, px * 20)) return rc;
-    d.block = blk;
-    d.best = (uint2 *)blk; d.rmap = (uint32_t *)(blk + px * 8); d.disp = (float *)(blk + px * 12);
-    d.mm = (uint16_t *)(blk + px * 16); d.status = blk + px * 18; d.left = blk + px * 19;
-    return RELOC_OK;
+    if (d.block.p) return RELOC_OK;
+    return d.block.layout(ctx, [&](BlockCarver &c) { stereo_dense_lines(c, d, (int64_t)ctx->max_w * ctx->max_h); });
 }
 
 // both kernels on ctx's stream, into ctx's dense planes (dense rows of p.w); the planes of the eyes are device pointers;
@@ -670,7 +639,7 @@ RELOC_API int reloc_stereo_dense_debug(reloc_ctx *ctx, uint16_t *depth_mm, float
 {
     ARG_CHECK_CTX(ctx, true, "reloc_stereo_dense_debug");
     const StereoState::Dense &d = ctx->stereo.dense;
-    if (!d.block || d.w == 0) { reloc_set_error("no dense stereo pass on this context yet"); return RELOC_E_STATE; }
+    if (!d.block.p || d.w == 0) { reloc_set_error("no dense stereo pass on this context yet"); return RELOC_E_STATE; }
     const int64_t px = (int64_t)d.w * d.h;
     HostStaging st{ctx};
     if (depth_mm) st.download(depth_mm, d.mm, px * 2);

@@ -111,7 +111,7 @@ static inline FrameSrc frame_from_depth(HostStaging &st, const void *depth, int 
 static inline FrameSrc frame_from_stereo(HostStaging &st, int step, float zmin, float zmax)
 {
     const StereoState::Dense &d = st.ctx->stereo.dense;
-    if (!st.rc && (!d.block || d.w == 0)) { reloc_set_error("no dense stereo pass on this context yet"); st.rc = RELOC_E_STATE; }
+    if (!st.rc && (!d.block.p || d.w == 0)) { reloc_set_error("no dense stereo pass on this context yet"); st.rc = RELOC_E_STATE; }
     return {{nullptr, 0, depth_grid(d.mm, 0, d.w, d.h, d.w, step, st.ctx->cam.K4, zmin, zmax)}, OCC_SRC_DEPTH_U16};
 }
 // the 3 x 4 transform of a frame: every value finite

@@ -606,26 +606,29 @@ int tick_alloc(reloc_ctx *ctx)
 {
     TickState &t = ctx->tick;
     const int64_t rows = (int64_t)MAX_CAND * MAX_REC_ROWS, hyps = (int64_t)MAX_CAND * MAX_HYP;
-    int rc = ctx_dev_alloc(ctx, &t.cand_ids, MAX_CAND);
-    rc |= ctx_dev_alloc(ctx, &t.cand_n, 1);
-    rc |= ctx_dev_alloc(ctx, &t.flags, 4);
-    for (int32_t **p : {&t.m_qidx, &t.m_tidx, &t.m_dist, &t.p_inl}) rc |= ctx_dev_alloc(ctx, p, rows);
-    rc |= ctx_dev_alloc(ctx, &t.m_n, 2 * MAX_CAND);        // list lengths, and the lengths PnP takes under RELOC_MATCH_RATIO
-    rc |= ctx_dev_alloc(ctx, &t.p_obj, rows * 3);
-    rc |= ctx_dev_alloc(ctx, &t.p_img, rows * 2);
-    rc |= ctx_dev_alloc(ctx, &t.p_Rt, hyps * 12);
-    rc |= ctx_dev_alloc(ctx, &t.p_cnt, hyps);
-    rc |= ctx_dev_alloc(ctx, &t.p_out, MAX_CAND);
-    rc |= ctx_dev_alloc(ctx, &t.res, 1);
+    if (int rc = t.block.layout(ctx, [&](BlockCarver &c) {
+            c.own(t.cand_ids, MAX_CAND);
+            c.own(t.cand_n, 1);
+            c.own(t.flags, 4);
+            for (int32_t **p : {&t.m_qidx, &t.m_tidx, &t.m_dist, &t.p_inl}) c.own(*p, rows);
+            c.own(t.m_n, 2 * MAX_CAND);        // list lengths, and the lengths PnP takes under RELOC_MATCH_RATIO
+            c.own(t.p_obj, rows * 3);
+            c.own(t.p_img, rows * 2);
+            c.own(t.p_Rt, hyps * 12);
+            c.own(t.p_cnt, hyps);
+            c.own(t.p_out, MAX_CAND);
+            c.own(t.res, 1);
+        })) return rc;
     if (hipHostMalloc((void **)&t.res_host, sizeof(TickResult), hipHostMallocDefault) != hipSuccess) {
         reloc_set_error("hipHostMalloc(result record) failed");
         t.res_host = nullptr;
-        rc |= RELOC_E_HIP;
-    } else memset(t.res_host, 0, sizeof(TickResult));
-    return rc;
+        return RELOC_E_HIP;
+    }
+    memset(t.res_host, 0, sizeof(TickResult));
+    return RELOC_OK;
 }
 
-// reloc_destroy frees the device blocks with the context's others; the pinned record is let go of here
+// the device block goes with the context; the pinned record is let go of here
 void tick_release(reloc_ctx *ctx) { if (ctx->tick.res_host) (void)hipHostFree(ctx->tick.res_host); }
 
 // the stamp of the tick being enqueued: 1, 2, ... (never 0: 0 means "no stamp")
@@ -1188,14 +1191,6 @@ RELOC_API int reloc_debug_local_candidates(reloc_ctx *ctx, const double base_pos
     return RELOC_OK;
 }
 
-namespace {
-// the tap's own device scratch: freed on every way out of the call
-struct RankScratch {
-    int32_t *counts = nullptr, *ids = nullptr, *cnt = nullptr, *n = nullptr, *flags = nullptr;
-    ~RankScratch() { for (int32_t *p : {counts, ids, cnt, n, flags}) if (p) (void)hipFree(p); }
-};
-}
-
 RELOC_API int reloc_debug_rank_counts(reloc_ctx *ctx, const int32_t *counts_host, int n_frames, int64_t L, int k, int64_t id_base,
                                       int min_matches, int max_count, const int32_t *skip_in, int32_t *ids_out, int32_t *counts_out,
                                       int32_t *n_out)
@@ -1205,13 +1200,17 @@ RELOC_API int reloc_debug_rank_counts(reloc_ctx *ctx, const int32_t *counts_host
     ARG_CHECK(k >= 1 && k <= MAX_CAND && L >= 1 && L <= MAX_DB_RECORDS && id_base >= 0 && id_base + L <= 0x7fffffff &&
               min_matches >= RELOC_PNP_SAMPLE && max_count >= 0 && ((size_t)max_count + 2) * sizeof(int) <= TOPK_HIST_LDS_MAX,
               "reloc_debug_rank_counts: 1 <= k <= 32, 1 <= L <= 1048575, id_base + L < 2^31, min_matches >= 4, max_count <= 16254");
-    RankScratch s;
+    // the tap's own device scratch: freed on every way out of the call
+    struct { int32_t *counts = nullptr, *ids = nullptr, *cnt = nullptr, *n = nullptr, *flags = nullptr; } s;
     const size_t slots = (size_t)n_frames * MAX_CAND * sizeof(int32_t), cbytes = (size_t)n_frames * (size_t)L * sizeof(int32_t);
-    HIP_TRY(hipMalloc((void **)&s.counts, cbytes));
-    HIP_TRY(hipMalloc((void **)&s.ids, slots));
-    HIP_TRY(hipMalloc((void **)&s.cnt, slots));
-    HIP_TRY(hipMalloc((void **)&s.n, RELOC_BATCH_MAX * sizeof(int32_t)));
-    HIP_TRY(hipMalloc((void **)&s.flags, RELOC_BATCH_MAX * sizeof(int32_t)));
+    DevBlock block;
+    if (int rc = block.layout(ctx, [&](BlockCarver &c) {
+            c.own(s.counts, (int64_t)n_frames * L);
+            c.own(s.ids, (int64_t)n_frames * MAX_CAND);
+            c.own(s.cnt, (int64_t)n_frames * MAX_CAND);
+            c.own(s.n, RELOC_BATCH_MAX);
+            c.own(s.flags, RELOC_BATCH_MAX);
+        })) return rc;
     HIP_TRY(hipMemcpyAsync(s.counts, counts_host, cbytes, hipMemcpyHostToDevice, ctx->stream));
     // poison: an entry the ranking does not write comes back as 0xA5A5A5A5
     HIP_TRY(hipMemsetAsync(s.ids, 0xA5, slots, ctx->stream));
