@@ -598,6 +598,55 @@ int reloc_route_set_costmap(reloc_ctx *ctx, const int8_t *cost, int w, int h);
 int reloc_route_search(reloc_ctx *ctx, int predicate, int thresh, const int32_t *offsets_rc, int n_offsets, const int32_t *cells_rc,
                        int n, int32_t *out_index);
 
+/* ---- local obstacles (include/reloc_spec.h, "OBSTACLE") ------------------------------------------ */
+/* What the reference's traversability_filter.py, gap_navigator.py (its depth profile) and local_obstacle_grid.py compute of every
+ * depth frame.  A depth image is h x w float32 (metres) or uint16 (millimetres) in host memory, w <= RELOC_OBS_MAX_COLS and
+ * w * h within the context's capacity (RELOC_E_CAPACITY), or the plane the context's last dense stereo pass left on the device
+ * (*_stereo_dev: RELOC_E_STATE before the first pass).  A context that never calls any of this allocates and launches nothing
+ * of it.  A refused call leaves the filter, the grid and its configuration as they were.
+ * reloc_obs_set_filter: the traversability filter of rule (d); bh == 0 && bw == 0 switches it off (the default), otherwise sides
+ * in [RELOC_OBS_MIN_BLOCK, RELOC_OBS_MAX_BLOCK] (RELOC_E_CAPACITY), 0 <= lo < hi, min_count >= 1, coverage > 0, everything
+ * finite (RELOC_E_ARG).  The getter also returns n_cov. */
+int reloc_obs_set_filter(reloc_ctx *ctx, int bh, int bw, float lo, float hi, int min_count, double coverage, double var_thresh,
+                         double min_solid, float fill);
+int reloc_obs_get_filter(reloc_ctx *ctx, int32_t *bh, int32_t *bw, float *lo, float *hi, int32_t *min_count, int32_t *n_cov,
+                         double *var_thresh, double *min_solid, float *fill);
+/* The filter on one host image: filtered (h x w float32 metres, may be NULL) and mask ((h / bh) x (w / bw) bytes, 1 =
+ * traversable, may be NULL).  RELOC_E_STATE while the filter is off.  Synchronous. */
+int reloc_obs_filter_depth(reloc_ctx *ctx, const void *depth, int is_f32, int w, int h, float *filtered, uint8_t *mask);
+/* Rules (a)-(c): profile and counts take ceil(w / step) entries each (either may be NULL).  use_filter != 0: the pixels are
+ * those of the filtered image (RELOC_E_STATE while the filter is off).  step >= 1, 0 <= lo, q in [0, 100], min_valid >= 1,
+ * everything finite (RELOC_E_ARG); a strip of more than RELOC_OBS_MAX_STRIP rows: RELOC_E_CAPACITY.  Synchronous; the
+ * _stereo_dev form with both outputs NULL enqueues only. */
+int reloc_obs_profile_depth(reloc_ctx *ctx, const void *depth, int is_f32, int w, int h, int step, float lo, float hi, int q,
+                            int min_valid, float fill, int use_filter, float *profile, int32_t *counts);
+int reloc_obs_profile_stereo_dev(reloc_ctx *ctx, int step, float lo, float hi, int q, int min_valid, float fill, int use_filter,
+                                 float *profile, int32_t *counts);
+/* The ego grid of rule (e): cells x cells zeros, and what every update projects with: the profile's parameters as above.
+ * cells in [1, RELOC_OBS_MAX_CELLS] (RELOC_E_CAPACITY); res, decay, hit, hit_nb, obstacle_hits positive and finite
+ * (RELOC_E_ARG).  A second call resets the grid.  Everything below returns RELOC_E_STATE before it. */
+int reloc_obs_grid_configure(reloc_ctx *ctx, int cells, double res, float decay, float hit, float hit_nb, float obstacle_hits,
+                             int step, float lo, float hi, int q, int min_valid, int use_filter);
+/* One update: shift by (sx, sy) cells, decay, and with depth != NULL the projection along dirs: ceil(w / step) pairs (c, s) of
+ * float64, n_dirs of them (another count: RELOC_E_ARG; more than RELOC_OBS_MAX_GRID_COLS: RELOC_E_CAPACITY).  depth == NULL:
+ * shift and decay only, the other arguments are ignored.  Synchronous; the _stereo_dev form enqueues only. */
+int reloc_obs_grid_update_depth(reloc_ctx *ctx, int sx, int sy, const void *depth, int is_f32, int w, int h, const double *dirs,
+                                int n_dirs);
+int reloc_obs_grid_update_stereo_dev(reloc_ctx *ctx, int sx, int sy, const double *dirs, int n_dirs);
+/* Rule (f): n sectors along dirs (n pairs (c, s)), out n float64.  max_range finite; n > RELOC_OBS_MAX_SECTORS or
+ * max_range / res > RELOC_OBS_MAX_STEPS: RELOC_E_CAPACITY.  n == 0 launches nothing. */
+int reloc_obs_grid_profile(reloc_ctx *ctx, const double *dirs, int n, double max_range, double *out);
+/* Rule (g): grid cells x cells float32, image the same size uint8, the count of cells >= obstacle_hits and the maximum; any
+ * pointer may be NULL.  *cells: the side (may be NULL). */
+int reloc_obs_grid_read(reloc_ctx *ctx, float *grid, uint8_t *image, int32_t *obstacle_cells, float *max_hits, int32_t *cells);
+
+/* cv2.erode / cv2.dilate of an 8-bit single-channel image (rows `stride` bytes apart) with a kh x kw all-ones rectangle anchored
+ * at (kw / 2, kh / 2), `iterations` times, OpenCV's default border: a pixel outside the image never lowers an erosion and never
+ * raises a dilation.  dst: dense rows of w.  dilate: 0 erode, 1 dilate.  A side beyond RELOC_MORPH_MAX_KERNEL, more than
+ * RELOC_MORPH_MAX_ITERATIONS or an image beyond the context's capacity: RELOC_E_CAPACITY.  Synchronous. */
+int reloc_morph_rect(reloc_ctx *ctx, const uint8_t *src, int w, int h, int stride, int kw, int kh, int dilate, int iterations,
+                     uint8_t *dst);
+
 /* ---- fused tick ----------------------------------------------------------------------------- */
 #define RELOC_TICK_LOCAL   0   /* candidates by VIO distance / heading only                          M:293-302 */
 #define RELOC_TICK_GLOBAL  1   /* whole-database search unconditionally (the benchmarked shape)       G:329-344 */

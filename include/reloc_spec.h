@@ -526,4 +526,53 @@
 #define RELOC_ROUTE_PRED_CLEARANCE  0
 #define RELOC_ROUTE_PRED_COST       1
 
+/* OBSTACLE: local obstacle perception, what the reference's repeat driver asks of every depth frame: traversability_filter.py (F
+ * below), gap_navigator.py's depth_to_obstacle_profile (N below) and local_obstacle_grid.py (G below; the files of experiment
+ * 39 and scripts/_archive).  Restated in tests/obstacle_ref.py, which the library equals bit for bit in everything but the
+ * variance of (d), where the decision is the rule.
+ *   (a) pixel    z in metres is the one depth pixel of the teach path: float32 as it is, uint16 as f32(mm) / 1000.0f.  Valid iff
+ *              z > lo && z < hi and z is finite; lo, hi float32 with 0 <= lo, the bounds themselves invalid (F:36-38, N:69-73,
+ *              G:97-101).
+ *   (b) strip    rows [h / 3, 2 h / 3) in integer division (N:63-64, G:86-88); columns 0, step, 2 step, ... with step >= 1
+ *              (N:67 step 1, G:95 step 4).
+ *   (c) percentile of a column's n valid values, sorted ascending as s, equal to np.percentile(valid_float32, q) (N:75, G:106):
+ *              qf = f32(q) / f32(100), vi = f32(n - 1) * qf, lo_i = floor(vi), hi_i = min(lo_i + 1, n - 1), g = vi - f32(lo_i),
+ *              d = s[hi_i] - s[lo_i]; the result is s[hi_i] - d * (1 - g) if g >= 0.5f, else s[lo_i] + d * g.  float32, every
+ *              operation rounded on its own, no contraction.  q an integer percent in [0, 100].  A column with n < min_valid
+ *              yields the caller's fill (N:74 needs n >= 4, G:103 n >= 3); the count n is returned beside it.  A strip of more
+ *              than RELOC_OBS_MAX_STRIP rows is beyond the capacity.
+ *   (d) traversability (F:21-53) over the (h / bh) x (w / bw) whole blocks; remainder rows and columns are never touched.  Per
+ *              block over the pixels valid under (a) with F's own lo, hi (0.3, 10.0): the count n, the minimum, and the variance
+ *              in float64 in two passes (mean, then mean of squared deviations).  Traversable iff n >= min_count (F:40, 10),
+ *              n <= n_cov with n_cov the largest n for which n / (bh * bw) < coverage in float64 (F:43, 49; the host finds it,
+ *              the device compares integers), variance > var_thresh (F:48) and (double)min > min_solid (F:50).  Every pixel of a
+ *              traversable block reads as fill (F:51, 10.0) for whatever comes behind.  The device sums in a fixed tree, numpy's
+ *              float32 np.var pairwise: the value may differ in its last bits, so a fixture keeps every block's variance more
+ *              than 1e-3 relative away from the threshold.
+ *   (e) grid     cells x cells float32, the robot at centre = cells / 2 (G:22-25).  One update, in G's order (G:42-122):
+ *              shift by (sx, sy) whole cells with zero fill, new[r][c] = old[r + sy][c + sx] or 0 outside (G:57-70: np.roll by
+ *              -sx on axis 1, then by -sy on axis 0; |s| >= cells clears everything); every cell times f32(decay) (G:76); then,
+ *              with a depth source, for the columns of (b) in ascending order whose n >= min_valid: depth = (double)percentile,
+ *              gx = centre + (int)(depth * c / res), gy = centre + (int)(depth * s / res) in float64, truncated toward zero
+ *              (G:108-113), (c, s) that column's entry of a direction table the host computes (G:90-92, 108: cos and sin of
+ *              yaw + linspace(-fov / 2, fov / 2, w)[col]); if (gx, gy) is inside the grid, f32(hit) is added to it and f32(hit_nb)
+ *              to (gx + 1, gy), (gx - 1, gy), (gx, gy + 1), (gx, gy - 1), each only if inside (G:115-122).  The additions to a
+ *              cell are float32 and happen in exactly that order: 0.45f is not exact, so the order is part of the answer.  The
+ *              host computes sx = int((x - prev_x) / res), sy likewise (G:50-55), prev updated on every frame (G:72-73).
+ *   (f) sectors  (G:124-157) one direction-table entry per sector; dist starts at 2 * res and grows by dist += res in float64
+ *              while dist < max_range; the cell is (centre + (int)(dist * c / res), centre + (int)(dist * s / res)); leaving
+ *              the grid ends the ray with max_range, the first cell with value >= obstacle_hits ends it with dist.  float64 out.
+ *   (g) read-out the grid; G's debug image (uint8)(clip(grid / hits, 0, 1) * 255) in float32 (G:159-162); the number of cells
+ *              >= obstacle_hits and the maximum (G:164-168). */
+#define RELOC_OBS_MAX_STRIP      512       /* rows of the strip (b) */
+#define RELOC_OBS_MAX_COLS       4096      /* width of a depth image of these entry points */
+#define RELOC_OBS_MIN_BLOCK      4         /* side of a block of (d) ... */
+#define RELOC_OBS_MAX_BLOCK      64        /* ... */
+#define RELOC_OBS_MAX_CELLS      512       /* cells per side of the grid (e) */
+#define RELOC_OBS_MAX_GRID_COLS  1024      /* columns of (b) that one grid update projects */
+#define RELOC_OBS_MAX_SECTORS    4096      /* sectors of one profile (f) */
+#define RELOC_OBS_MAX_STEPS      (1 << 20) /* max_range / res of (f) */
+#define RELOC_MORPH_MAX_KERNEL    4096      /* side of the rectangle of reloc_morph_rect; a pixel reads min(side, image side) pixels */
+#define RELOC_MORPH_MAX_ITERATIONS 64
+
 #endif /* RELOC_SPEC_H */

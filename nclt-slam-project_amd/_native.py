@@ -155,6 +155,17 @@ SIGNATURES = {
     "reloc_route_clearance_at": (C.c_int, [c_ctx, P, C.c_int, P]),
     "reloc_route_set_costmap": (C.c_int, [c_ctx, P, C.c_int, C.c_int]),
     "reloc_route_search": (C.c_int, [c_ctx, C.c_int, C.c_int, P, C.c_int, P, C.c_int, P]),
+    "reloc_obs_set_filter": (C.c_int, [c_ctx, C.c_int, C.c_int, f32, f32, C.c_int, f64, f64, f64, f32]),
+    "reloc_obs_get_filter": (C.c_int, [c_ctx, P, P, P, P, P, P, P, P, P]),
+    "reloc_obs_filter_depth": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, P, P]),
+    "reloc_obs_profile_depth": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, C.c_int, f32, f32, C.c_int, C.c_int, f32, C.c_int, P, P]),
+    "reloc_obs_profile_stereo_dev": (C.c_int, [c_ctx, C.c_int, f32, f32, C.c_int, C.c_int, f32, C.c_int, P, P]),
+    "reloc_obs_grid_configure": (C.c_int, [c_ctx, C.c_int, f64, f32, f32, f32, f32, C.c_int, f32, f32, C.c_int, C.c_int, C.c_int]),
+    "reloc_obs_grid_update_depth": (C.c_int, [c_ctx, C.c_int, C.c_int, P, C.c_int, C.c_int, C.c_int, P, C.c_int]),
+    "reloc_obs_grid_update_stereo_dev": (C.c_int, [c_ctx, C.c_int, C.c_int, P, C.c_int]),
+    "reloc_obs_grid_profile": (C.c_int, [c_ctx, P, C.c_int, f64, P]),
+    "reloc_obs_grid_read": (C.c_int, [c_ctx, P, P, P, P, P]),
+    "reloc_morph_rect": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P]),
     "reloc_tick_debug": (C.c_int, [c_ctx, P, P, P, P, P, P, P]),
     "reloc_tick_debug_matches": (C.c_int, [c_ctx, C.c_int, P, P, P, P, P, P]),
     "reloc_debug_local_candidates": (C.c_int, [c_ctx, P, C.c_int, P, P]),

@@ -108,6 +108,7 @@ RELOC_API void reloc_destroy(reloc_ctx *c)
     for (DbArena &db : c->db_slot) db_arena_release(db);      // owner or adopter alike: one reference each
     tick_release(c);
     stereo_release(c);
+    obs_release(c);
     for (int k = 0; k < RELOC_PROF_N; ++k)
         if (c->prof[k].init)
             for (int i = 0; i < RELOC_PROF_RING; ++i) {

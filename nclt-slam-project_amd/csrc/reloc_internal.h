@@ -496,6 +496,32 @@ struct RouteState {
     bool has_cost() const { return cw > 0; }
 };
 
+// Local obstacle perception of a context (include/reloc_spec.h "OBSTACLE"; reloc_obstacle.hip); nothing configured and no block
+// taken is the default: a context that never calls reloc_obs_* allocates and launches nothing of it.  Two blocks: what a frame
+// leaves (taken by the first call that reads a depth image) and the grid's (reloc_obs_grid_configure).
+struct ObstacleState {
+    // the traversability filter (d), reloc_obs_set_filter; bh == 0: off
+    int bh = 0, bw = 0, min_count = 0, n_cov = 0;
+    float f_lo = 0, f_hi = 0, f_fill = 0;
+    double var_thresh = 0, min_solid = 0;
+    DevBlock frame_block;                // the pointers below lie in it
+    uint8_t *mask = nullptr;             // the last frame's block mask, max_w * max_h / RELOC_OBS_MIN_BLOCK^2 bytes
+    float *prof = nullptr;               // RELOC_OBS_MAX_COLS: the last profile ...
+    int32_t *cnt = nullptr;              // ... and its counts
+    // the grid (e), reloc_obs_grid_configure; cells == 0: none
+    int cells = 0, step = 0, q = 0, min_valid = 0, use_filter = 0, cur = 0;
+    double res = 0;
+    float decay = 0, hit = 0, hit_nb = 0, obstacle_hits = 0, lo = 0, hi = 0;
+    DevBlock grid_block;                 // the pointers below lie in it
+    float *grid[2] = {};                 // grid[cur] holds the grid, an update writes the other one
+    uint8_t *image = nullptr;            // cells x cells: the debug image of the last reloc_obs_grid_read
+    int32_t *stats = nullptr;            // 2: cells >= obstacle_hits, the maximum's bits
+    double *dirs_host = nullptr;         // pinned, RELOC_OBS_MAX_GRID_COLS pairs: the directions of an enqueue-only update ...
+    hipEvent_t dirs_read = nullptr;      // ... and the copy out of it: the next such update waits for it before it overwrites them
+    bool filter_on() const { return bh > 0; }
+    bool on() const { return cells > 0; }
+};
+
 // What the five ORB kernels read and write of one frame, in the form they take it: a single-frame launch passes the members
 // as arguments, a batched one up to 8 of these in its kernel arguments (OrbBatch, blockIdx.y = frame).
 struct OrbFrame {
@@ -583,6 +609,7 @@ struct reloc_ctx {
     OccState occ;                    // reloc_occupancy.hip
     CorrState corr;                  // reloc_correlation.hip
     RouteState route;                // reloc_route.hip
+    ObstacleState obs;               // reloc_obstacle.hip
     int scan_gens = 0;               // RELOC_SCAN_GENS (developer switch), read once at creation: n > 0 = single whole-database
                                      // scans in the form of batched ones (n generations of row budgets + sweepers, launch_db_count)
     DevBlock scan_block;
@@ -735,6 +762,8 @@ int image_gray_plain(reloc_ctx *c, const uint8_t *src, int w, int h, int sstride
 // working frame.  stereo_release: the events of a context that had stereo on.
 int stereo_frame(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img_right_dev, int w, int h, int order, int *ww, int *wh);
 void stereo_release(reloc_ctx *ctx);
+// the pinned direction table and its event of a context that updated its obstacle grid from the stereo plane (reloc_obstacle.hip)
+void obs_release(reloc_ctx *ctx);
 // blocks of a 1-D grid-stride launch of 256 threads over n elements: at least one, at most max_blocks
 static inline unsigned grid_1d(int64_t n, int max_blocks) { const int64_t b = (n + 255) / 256; return (unsigned)(b < 1 ? 1 : b < max_blocks ? b : max_blocks); }
 // an entry point that needs a map the context lacks: RELOC_E_STATE

@@ -31,6 +31,11 @@ the four of the fisheye model.  Other interpolation or border modes, other dtype
 resize is OpenCV's 8-bit INTER_NEAREST / INTER_LINEAR / INTER_AREA (downscale) resize (include/reloc_spec.h, "RESIZE") on the
 backend, INTER_NEAREST also for single-channel 16-bit images; other interpolations and dtypes and INTER_AREA upscaling raise.
 
+erode / dilate are OpenCV's 8-bit single-channel morphology with a rectangular all-ones kernel (getStructuringElement(MORPH_RECT,
+...) or any all-ones 2-D array), the anchor at the kernel's centre and the default border, which never lowers an erosion and never
+raises a dilation; a 1-D array is the n x 1 image OpenCV makes of it.  Any other structuring element, dtype, channel count, border
+or anchor raises.
+
 `Cv2Shim(backend)` takes any object with the Engine's method names; the module-level functions
 bind to one lazily created HIP Engine.
 """
@@ -98,6 +103,9 @@ INTER_NEAREST = 0
 INTER_LINEAR = 1
 INTER_AREA = 3
 BORDER_CONSTANT = 0
+MORPH_RECT = 0
+MORPH_CROSS = 1
+MORPH_ELLIPSE = 2
 ORB_HARRIS_SCORE = 0
 ORB_FAST_SCORE = 1
 CV_16UC1 = 2
@@ -518,6 +526,21 @@ def _fisheye_init_undistort_rectify_map(K, D, R, P, size, m1type):
     return _maps_out(u, v, m1type)
 
 
+def getStructuringElement(shape, ksize, anchor=None):
+    """cv2.getStructuringElement(MORPH_RECT, (width, height)): a (height, width) array of ones"""
+    if shape != MORPH_RECT:
+        raise error("getStructuringElement: only MORPH_RECT is implemented")
+    if anchor is not None and tuple(anchor) != (-1, -1):
+        raise error("getStructuringElement: only the default anchor is implemented")
+    try:
+        kw, kh = (int(v) for v in ksize)
+    except (TypeError, ValueError) as e:
+        raise error("getStructuringElement: ksize is (width, height)") from e
+    if kw < 1 or kh < 1:
+        raise error("getStructuringElement: ksize must be positive")
+    return np.ones((kh, kw), np.uint8)
+
+
 class _Fisheye:
     """cv2.fisheye: initUndistortRectifyMap builds a rectification map on the host; the fisheye model itself (points, PnP)
     is not implemented, and every other function raises `error`."""
@@ -554,6 +577,9 @@ class Cv2Shim:
     ORB_HARRIS_SCORE = ORB_HARRIS_SCORE
     ORB_FAST_SCORE = ORB_FAST_SCORE
     BORDER_CONSTANT = BORDER_CONSTANT
+    MORPH_RECT = MORPH_RECT
+    MORPH_CROSS = MORPH_CROSS
+    MORPH_ELLIPSE = MORPH_ELLIPSE
     CV_16UC1 = CV_16UC1
     CV_32FC1 = CV_32FC1
     CV_16SC2 = CV_16SC2
@@ -801,6 +827,35 @@ class Cv2Shim:
             raise error(str(e)) from e
         return img, buf
 
+    getStructuringElement = staticmethod(getStructuringElement)
+
+    def _morph(self, what, dilate, src, kernel, dst, anchor, iterations, borderType, borderValue):
+        if dst is not None or borderType is not None or borderValue is not None:
+            raise error(f"{what}: dst, borderType and borderValue are not implemented (the default border only)")
+        if anchor is not None and tuple(anchor) != (-1, -1):
+            raise error(f"{what}: only the default anchor (the kernel's centre) is implemented")
+        img = np.asarray(src)
+        if img.dtype != np.uint8 or img.ndim not in (1, 2) or img.size == 0:
+            raise error(f"{what}: expected a non-empty (H, W) uint8 single-channel image")
+        k = np.ones((3, 3), np.uint8) if kernel is None else np.asarray(kernel)
+        if k.ndim != 2 or k.size == 0 or not (k != 0).all():
+            raise error(f"{what}: only a rectangular all-ones structuring element is implemented (MORPH_RECT)")
+        if int(iterations) != iterations or iterations < 1:
+            raise error(f"{what}: iterations must be an integer >= 1")
+        fn = self._backend("morph_rect", what)
+        try:
+            return fn(img.reshape(-1, 1) if img.ndim == 1 else img, k.shape[1], k.shape[0], dilate, int(iterations))
+        except RelocError as e:
+            raise error(str(e)) from e
+
+    def erode(self, src, kernel, dst=None, anchor=None, iterations=1, borderType=None, borderValue=None):
+        """cv2.erode of an (H, W) uint8 image with a rectangular all-ones kernel"""
+        return self._morph("erode", False, src, kernel, dst, anchor, iterations, borderType, borderValue)
+
+    def dilate(self, src, kernel, dst=None, anchor=None, iterations=1, borderType=None, borderValue=None):
+        """cv2.dilate of an (H, W) uint8 image with a rectangular all-ones kernel"""
+        return self._morph("dilate", True, src, kernel, dst, anchor, iterations, borderType, borderValue)
+
     def ORB_create(self, nfeatures=500, **kwargs):
         """cv2.ORB_create: nlevels (1..8), scaleFactor (1.01..2.0), fastThreshold (1..254) and scoreType (ORB_HARRIS_SCORE,
         ORB_FAST_SCORE) are settings (include/reloc_spec.h "ORB PARAMS") on a backend whose orb_detect_compute takes orb=;
@@ -958,6 +1013,14 @@ def resize(*a, **kw):
 
 def filterSpeckles(*a, **kw):
     return default_shim().filterSpeckles(*a, **kw)
+
+
+def erode(*a, **kw):
+    return default_shim().erode(*a, **kw)
+
+
+def dilate(*a, **kw):
+    return default_shim().dilate(*a, **kw)
 
 
 def ORB_create(nfeatures=500, **kw):

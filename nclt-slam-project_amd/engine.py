@@ -1025,6 +1025,110 @@ class Engine:
                                      out if len(c) else None)
         return out
 
+    # ------------------------------------------------------------------ local obstacles (reloc_spec.h "OBSTACLE")
+    def obs_set_filter(self, block=(40, 40), lo: float = 0.3, hi: float = 10.0, min_count: int = 10, coverage: float = 0.3,
+                       var_thresh: float = 0.5, min_solid: float = 0.8, fill: float = 10.0):
+        """the traversability filter of rule (d); block = (bh, bw), None switches it off"""
+        bh, bw = (0, 0) if block is None else block
+        self._api.reloc_obs_set_filter(self._ctx, int(bh), int(bw), float(lo), float(hi), int(min_count), float(coverage), float(var_thresh),
+                                       float(min_solid), float(fill))
+
+    def obs_get_filter(self):
+        """dict of the filter's settings, block None while it is off; n_cov: the largest count rule (d) still calls sparse"""
+        bh, bw, lo, hi, mc, nc, vt, ms, fill = N.outs(i32, i32, f32, f32, i32, i32, f64, f64, f32)
+        self._api.reloc_obs_get_filter(self._ctx, bh, bw, lo, hi, mc, nc, vt, ms, fill)
+        return dict(block=(bh.value, bw.value) if bh.value else None, lo=lo.value, hi=hi.value, min_count=mc.value, n_cov=nc.value,
+                    var_thresh=vt.value, min_solid=ms.value, fill=fill.value)
+
+    def obs_filter_depth(self, depth):
+        """(filtered (H, W) float32 metres, mask (H // bh, W // bw) bool) of one depth image under the filter"""
+        d, is_f32, w, h = self._depth_image(depth, "obs_filter_depth")
+        blk = self.obs_get_filter()["block"] or (1, 1)
+        out, mask = np.zeros((h, w), np.float32), np.zeros((h // blk[0], w // blk[1]), np.uint8)
+        self._api.reloc_obs_filter_depth(self._ctx, d, is_f32, w, h, out, mask if mask.size else None)
+        return out, mask.astype(bool)
+
+    def obs_profile_depth(self, depth, step: int = 1, lo: float = 0.8, hi: float = 5.0, q: int = 10, min_valid: int = 4, fill: float = 5.0,
+                          use_filter: bool = False):
+        """rules (a)-(c) on one depth image: (profile float32, counts int32), one entry per step-th column"""
+        d, is_f32, w, h = self._depth_image(depth, "obs_profile_depth")
+        n = (w + int(step) - 1) // max(int(step), 1) if int(step) >= 1 else 0
+        prof, cnt = np.zeros(n, np.float32), np.zeros(n, np.int32)
+        self._api.reloc_obs_profile_depth(self._ctx, d, is_f32, w, h, int(step), float(lo), float(hi), int(q), int(min_valid), float(fill),
+                                          int(bool(use_filter)), prof, cnt)
+        return prof, cnt
+
+    def obs_profile_stereo(self, step: int = 1, lo: float = 0.8, hi: float = 5.0, q: int = 10, min_valid: int = 4, fill: float = 5.0,
+                           use_filter: bool = False, wait: bool = True):
+        """the same on the depth plane of this engine's last dense stereo pass, on the device; wait=False enqueues only and
+        returns None"""
+        args = (int(step), float(lo), float(hi), int(q), int(min_valid), float(fill), int(bool(use_filter)))
+        if not wait:
+            self._api.reloc_obs_profile_stereo_dev(self._ctx, *args, None, None)
+            return None
+        w = i32()
+        self._api.reloc_stereo_dense_debug(self._ctx, None, None, None, w, None)
+        n = (w.value + int(step) - 1) // max(int(step), 1)
+        prof, cnt = np.zeros(n, np.float32), np.zeros(n, np.int32)
+        self._api.reloc_obs_profile_stereo_dev(self._ctx, *args, prof, cnt)
+        return prof, cnt
+
+    def obs_grid_configure(self, cells: int = 100, res: float = 0.2, decay: float = 0.997, hit: float = 1.5, hit_nb: float = 0.45,
+                           obstacle_hits: float = 8.0, step: int = 4, lo: float = 0.3, hi: float = 5.0, q: int = 10, min_valid: int = 3,
+                           use_filter: bool = False):
+        """allocates and zeroes the ego grid of rule (e) and fixes what every update projects with; a second call resets it"""
+        self._api.reloc_obs_grid_configure(self._ctx, int(cells), float(res), float(decay), float(hit), float(hit_nb), float(obstacle_hits),
+                                           int(step), float(lo), float(hi), int(q), int(min_valid), int(bool(use_filter)))
+
+    @staticmethod
+    def _obs_dirs(dirs, what):
+        d = np.ascontiguousarray(dirs, np.float64)
+        if d.size and (d.ndim != 2 or d.shape[1] != 2):
+            raise N.RelocError(f"{what}: expected (n, 2) directions (cos, sin)")
+        return d.reshape(-1, 2)
+
+    def obs_grid_update_depth(self, sx: int, sy: int, depth=None, dirs=None):
+        """one update: shift by (sx, sy) cells, decay, and with a depth image the projection along `dirs`, one (cos, sin) per
+        step-th column"""
+        if depth is None:
+            self._api.reloc_obs_grid_update_depth(self._ctx, int(sx), int(sy), None, 0, 0, 0, None, 0)
+            return
+        d, is_f32, w, h = self._depth_image(depth, "obs_grid_update_depth")
+        t = self._obs_dirs(dirs if dirs is not None else [], "obs_grid_update_depth")
+        self._api.reloc_obs_grid_update_depth(self._ctx, int(sx), int(sy), d, is_f32, w, h, t if len(t) else None, len(t))
+
+    def obs_grid_update_stereo(self, sx: int, sy: int, dirs):
+        """one update from the depth plane of this engine's last dense stereo pass, on the device; enqueues only"""
+        t = self._obs_dirs(dirs, "obs_grid_update_stereo")
+        self._api.reloc_obs_grid_update_stereo_dev(self._ctx, int(sx), int(sy), t if len(t) else None, len(t))
+
+    def obs_grid_profile(self, dirs, max_range: float = 8.0):
+        """rule (f): the distance to the first confirmed obstacle along each of the (n, 2) directions, float64"""
+        t = self._obs_dirs(dirs, "obs_grid_profile")
+        out = np.zeros(len(t), np.float64)
+        self._api.reloc_obs_grid_profile(self._ctx, t if len(t) else None, len(t), float(max_range), out if len(t) else None)
+        return out
+
+    def obs_grid_read(self, grid: bool = True, image: bool = True):
+        """dict(grid (cells, cells) float32, image uint8, obstacle_cells, max_hits) of rule (g); grid / image only when asked for"""
+        n = i32()
+        self._api.reloc_obs_grid_read(self._ctx, None, None, None, None, n)
+        g = np.zeros((n.value, n.value), np.float32) if grid else None
+        im = np.zeros((n.value, n.value), np.uint8) if image else None
+        cells, mx = N.outs(i32, f32)
+        self._api.reloc_obs_grid_read(self._ctx, g, im, cells, mx, None)
+        return dict(grid=g, image=im, obstacle_cells=cells.value, max_hits=mx.value)
+
+    def morph_rect(self, img, kw: int, kh: int, dilate: bool = False, iterations: int = 1):
+        """erode (dilate) of an (H, W) uint8 image with a kh x kw all-ones rectangle anchored at its centre, OpenCV's default border"""
+        a = np.asarray(img)
+        if a.dtype != np.uint8 or a.ndim != 2 or a.size == 0:
+            raise N.RelocError("morph_rect: expected a non-empty (H, W) uint8 image")
+        a = np.ascontiguousarray(a)
+        out = np.empty_like(a)
+        self._api.reloc_morph_rect(self._ctx, a, a.shape[1], a.shape[0], a.shape[1], int(kw), int(kh), int(bool(dilate)), int(iterations), out)
+        return out
+
     def hamming_matrix(self, a, b):
         a = self._desc(a, "hamming_matrix"); b = self._desc(b, "hamming_matrix")
         out = np.empty((len(a), len(b)), np.uint16)

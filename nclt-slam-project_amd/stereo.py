@@ -185,6 +185,31 @@ class StereoDepthCore:
             return anchor.tick_stereo(base_pose7, ts)
         return anchor.tick_depth(self.depth(left_frame, right_frame), self.K4, base_pose7, ts)
 
+    def obstacle_profile(self, navigator, left_frame, right_frame):
+        """the obstacle profile of a gap navigator (obstacle.GapNavigatorCore) from the pair: the dense pass, then the column
+        percentiles on the plane where it lies -- the depth never crosses to the host; the navigator must stand on this core's
+        left Engine.  On the cv2-shaped path the depth image goes through the navigator's depth_to_obstacle_profile.  Returns
+        (free mask, profile float64)."""
+        if self.engine is None:
+            return navigator.depth_to_obstacle_profile(self.depth(left_frame, right_frame))
+        if navigator.engine is not self.engine:
+            raise ValueError("StereoDepthCore.obstacle_profile: the navigator must use this core's left engine")
+        self.engine.stereo_frame_depth(left_frame, right_frame, self.right_engine, download=False)
+        prof, _ = self.engine.obs_profile_stereo(1, navigator.MIN_VALID_DEPTH, navigator.MAX_RANGE, 10, 4, navigator.MAX_RANGE, navigator.use_filter)
+        profile = prof.astype(np.float64)
+        return profile > navigator.OBSTACLE_THRESHOLD, profile
+
+    def grid_update(self, grid, left_frame, right_frame, robot_x, robot_y, robot_yaw):
+        """one update of a local obstacle grid (obstacle.LocalObstacleGridCore) from the pair: the dense pass, then the grid's
+        update_stereo on the plane where it lies, enqueued without a wait; the grid must stand on this core's left Engine.  On
+        the cv2-shaped path the depth image goes through the grid's update."""
+        if self.engine is None:
+            return grid.update(robot_x, robot_y, robot_yaw, self.depth(left_frame, right_frame))
+        if grid.engine is not self.engine:
+            raise ValueError("StereoDepthCore.grid_update: the grid must use this core's left engine")
+        _, w = self.engine.stereo_frame_depth(left_frame, right_frame, self.right_engine, download=False)
+        return grid.update_stereo(robot_x, robot_y, robot_yaw, w)
+
     def close(self):
         """closes the right eye's Engine, which this core made; the left Engine stays the caller's"""
         if self.right_engine is not None:
