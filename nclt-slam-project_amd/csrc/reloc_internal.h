@@ -522,8 +522,8 @@ struct ObstacleState {
     bool on() const { return cells > 0; }
 };
 
-// What the five ORB kernels read and write of one frame, in the form they take it: a single-frame launch passes the members
-// as arguments, a batched one up to 8 of these in its kernel arguments (OrbBatch, blockIdx.y = frame).
+// What the five ORB kernels read and write of one frame, in the form they take it: a launch carries a FrameTable of these in
+// its kernel arguments (blockIdx.y = frame).
 struct OrbFrame {
     const OrbTable *tab; const PyrTile *tiles; const int32_t *rz; const uint8_t *src;
     uint8_t *pyr, *nms, *blur; int32_t *hist, *cand_cnt; uint32_t *cand_key; float *cand_resp; int32_t *dbg_cut;
@@ -531,7 +531,7 @@ struct OrbFrame {
     int32_t *f_count;
     const uint8_t *mask;    // mask pyramid of the frame (geometry of pyr), read by the MASKED kernels only
 };
-static_assert(sizeof(OrbFrame) == 184, "OrbFrame travels in the kernel arguments of the batched ORB launches (DESIGN.md)");
+static_assert(sizeof(OrbFrame) == 184, "OrbFrame travels in the kernel arguments of the ORB launches (DESIGN.md)");
 
 // ORB front end of a context (reloc_orb.hip): the blocks orb_alloc sized for the context's capacity and the geometry of the
 // frame size orb_prepare last published.
@@ -687,18 +687,38 @@ static inline bool ctx_alone(const reloc_ctx *c)
 }
 
 // Stage launchers shared between translation units.  Each takes the n <= RELOC_BATCH_MAX contexts of one call (one stream,
-// equal geometry, parameters and database: ctx_batch_check in reloc_tick.hip) and makes ONE launch per kernel of its stage:
-// at n == 1 the pointer-argument kernel with frame 0's buffers, at n > 1 the frame-table kernel (*_batch, blockIdx = frame).
+// equal geometry, parameters and database: ctx_batch_check in reloc_tick.hip) and makes ONE launch per kernel of its stage.
+// The ORB, PnP and tick kernels take a FrameTable of per-frame structs by value and index it with the last grid dimension;
+// everything that differs between frames (buffers, seed, base pose, sequence stamp, masks) is a field of that struct, the
+// other kernel arguments are what the frames share.  Each kernel exists for N = 1 (one frame, a 1-slot table) and for
+// N = RELOC_BATCH_MAX (2..8 frames); a launcher is written once as a template on N and picked by n == 1.  Two kernels keep
+// a pointer-argument form for one frame beside the 8-slot table form, each for a measured reason stated at the kernel:
+// k_pyramid (reloc_orb.hip) and k_topk_counts (reloc_tick.hip).  (The scan family keeps its own single / batch kernels:
+// reloc_hamming.h.)
 // latency: kernels sized for latency instead of for fitting beside another stream's whole-database scan (512-thread
-// pyramid, 8-wave emit pass, unconstrained k_pnp_finish); only a single frame (n == 1) ever gets them.
+// pyramid, 8-wave emit pass, unconstrained k_pnp_finish); only a single frame (N == 1) ever gets them.
 constexpr int RELOC_BATCH_MAX = 8;          // frames per batched launch (reloc_tick_batch_dev, reloc_shard_*_batch_dev)
 
+// N is 1 or RELOC_BATCH_MAX.  The 1-slot table never reads the block index.
+template <typename Frame, int N> struct FrameTable {
+    Frame f[N];
+    __device__ __forceinline__ const Frame &at(unsigned i) const { return f[N == 1 ? 0 : i]; }
+};
+
 // Visits the RELOC_BATCH_MAX slots of a frame table: fn(slot, ctx, frame) with frame = slot for the n frames of the call and
-// frame 0 for the padding slots (never read: the grid holds n frames).
+// frame 0 for the padding slots (never read: the grid holds n frames).  A one-frame launch takes slot 0 of it.
 template <typename Fn>
 static inline void frame_slots(reloc_ctx *const *ctxs, int n, Fn fn)
 {
     for (int f = 0; f < RELOC_BATCH_MAX; ++f) fn(f, ctxs[f < n ? f : 0], f < n ? f : 0);
+}
+// the table a launch<N> passes: the first N slots of the filled one
+template <int N, typename Frame>
+static inline FrameTable<Frame, N> frame_table(const FrameTable<Frame, RELOC_BATCH_MAX> &b)
+{
+    FrameTable<Frame, N> t;
+    for (int f = 0; f < N; ++f) t.f[f] = b.f[f];
+    return t;
 }
 
 // The whole-database scans count the mutual matches of the current descriptors (cur, n_cur_max capacity, count on the

@@ -74,10 +74,9 @@ __device__ __forceinline__ int find_level(const int *base, int id)
 // table slices are worked out by the host once per frame size (orb_plan; PyrTile, PyrLds and the tile size PT_W x PT_H:
 // reloc_orb_plan.h).
 
-// Frame-batched launches (reloc_tick_batch_dev, the sharded halves): the five ORB kernels of up to 8 contexts as FIVE
-// launches, blockIdx.y = frame.  Everything a kernel needs of one context travels in the kernel arguments (OrbFrame,
-// reloc_internal.h).
-struct OrbBatch { OrbFrame f[RELOC_BATCH_MAX]; };
+// The five ORB kernels of the 1..8 contexts of a call are FIVE launches, blockIdx.y = frame.  Everything a kernel needs of
+// one context travels in the kernel arguments (OrbFrame, FrameTable: reloc_internal.h).
+template <int N> using OrbFrames = FrameTable<OrbFrame, N>;
 
 // flat table index i -> positions of the (offset, coefficient) entries in the resize tables; the level is found
 // by selects over uniform values so that no load depends on it
@@ -235,6 +234,10 @@ __device__ __forceinline__ void pyramid_body(const OrbTable *__restrict__ tab, c
         }
     }
 }
+// The one stage that keeps a pointer-argument kernel for one frame beside its frame-table kernel: the body reads its tables
+// (tab, tiles, rz: uniform addresses) between barriers, and only `const __restrict__` kernel arguments let the compiler keep
+// those reads scalar -- from a frame table they become ~100 vector loads and the kernel 1.7 us longer (measured: DESIGN.md
+// section 4).
 template <int CH, bool ALIGNED, int PYR_BS>
 __global__ __launch_bounds__(PYR_BS) void k_pyramid(const OrbTable *__restrict__ tab, const PyrTile *__restrict__ tiles,
                                                  const int32_t *__restrict__ rz, const uint8_t *__restrict__ src, int w, int h,
@@ -245,10 +248,10 @@ __global__ __launch_bounds__(PYR_BS) void k_pyramid(const OrbTable *__restrict__
     pyramid_body<CH, ALIGNED, PYR_BS>(tab, tiles, rz, src, w, h, sstride, order_rgb, pyr, lds, hist, cand_cnt);
 }
 template <int CH, bool ALIGNED, int PYR_BS>
-__global__ __launch_bounds__(PYR_BS) void k_pyramid_batch(OrbBatch b, int w, int h, int sstride, int order_rgb, PyrLds lds)
+__global__ __launch_bounds__(PYR_BS) void k_pyramid_batch(OrbFrames<RELOC_BATCH_MAX> b, int w, int h, int sstride, int order_rgb, PyrLds lds)
 {
     RELOC_SMALL_KERNEL_PRIO();
-    const OrbFrame &F = b.f[blockIdx.y];
+    const OrbFrame &F = b.at(blockIdx.y);
     pyramid_body<CH, ALIGNED, PYR_BS>(F.tab, F.tiles, F.rz, F.src, w, h, sstride, order_rgb, F.pyr, lds, F.hist, F.cand_cnt);
 }
 
@@ -615,22 +618,13 @@ __device__ __forceinline__ void fast_nms_tile(const OrbTable *__restrict__ tab, 
 // feeds Harris and the blur feeds the descriptors, so they need not run one after the other.  (A smaller grid whose workgroups
 // walk the tiles paid beside 112-register scans and pays nothing beside 104-register ones: profiles/README.md "Dropped
 // experiments" #8.)
-// MASKED = true: the same with the detection mask applied behind NMS; `mask` is the last argument and unread otherwise.
+// MASKED = true: the same with the detection mask applied behind NMS; the frame's `mask` is unread otherwise.
 // THR: fast_nms_tile.
-template <bool MASKED, int THR>
-__global__ __launch_bounds__(256) void k_fast_blur(const OrbTable *__restrict__ tab, const uint8_t *__restrict__ pyr,
-                                                   uint8_t *__restrict__ nms, int32_t *__restrict__ hist,
-                                                   uint8_t *__restrict__ blur, int n_fast, const uint8_t *__restrict__ mask)
+template <bool MASKED, int THR, int N>
+__global__ __launch_bounds__(256) void k_fast_blur(OrbFrames<N> b, int n_fast)
 {
     RELOC_SMALL_KERNEL_PRIO();
-    if ((int)blockIdx.x < n_fast) fast_nms_tile<MASKED, THR>(tab, pyr, nms, hist, (int)blockIdx.x, mask);
-    else blur7_tile(tab, pyr, blur, (int)blockIdx.x - n_fast);
-}
-template <bool MASKED, int THR>
-__global__ __launch_bounds__(256) void k_fast_blur_batch(OrbBatch b, int n_fast)
-{
-    RELOC_SMALL_KERNEL_PRIO();
-    const OrbFrame &F = b.f[blockIdx.y];
+    const OrbFrame &F = b.at(blockIdx.y);
     if ((int)blockIdx.x < n_fast) fast_nms_tile<MASKED, THR>(F.tab, F.pyr, F.nms, F.hist, (int)blockIdx.x, F.mask);
     else blur7_tile(F.tab, F.pyr, F.blur, (int)blockIdx.x - n_fast);
 }
@@ -844,20 +838,11 @@ __device__ __forceinline__ void harris_body(const OrbTable *__restrict__ tab, co
         }
     }
 }
-template <int MODE>
-__global__ __launch_bounds__(256) void k_harris(const OrbTable *__restrict__ tab, const uint8_t *__restrict__ pyr,
-                                                const uint8_t *__restrict__ nms, const int32_t *__restrict__ hist,
-                                                int32_t *__restrict__ cand_cnt, u32 *__restrict__ cand_key,
-                                                float *__restrict__ cand_resp, int32_t *__restrict__ dbg_cut)
+template <int MODE, int N>
+__global__ __launch_bounds__(256) void k_harris(OrbFrames<N> b)
 {
     RELOC_SMALL_KERNEL_PRIO();
-    harris_body<MODE>(tab, pyr, nms, hist, cand_cnt, cand_key, cand_resp, dbg_cut);
-}
-template <int MODE>
-__global__ __launch_bounds__(256) void k_harris_batch(OrbBatch b)
-{
-    RELOC_SMALL_KERNEL_PRIO();
-    const OrbFrame &F = b.f[blockIdx.y];
+    const OrbFrame &F = b.at(blockIdx.y);
     harris_body<MODE>(F.tab, F.pyr, F.nms, F.hist, F.cand_cnt, F.cand_key, F.cand_resp, F.dbg_cut);
 }
 
@@ -902,18 +887,11 @@ __device__ __forceinline__ void select_body(const OrbTable *__restrict__ tab, co
     }
     if (tid == 0) kp_cnt[l] = K;
 }
-__global__ __launch_bounds__(1024) void k_select(const OrbTable *__restrict__ tab, const int32_t *__restrict__ cand_cnt,
-                                                 const u32 *__restrict__ cand_key, const float *__restrict__ cand_resp,
-                                                 int32_t *__restrict__ kp_cnt, u32 *__restrict__ kp_key,
-                                                 float *__restrict__ kp_resp)
+template <int N>
+__global__ __launch_bounds__(1024) void k_select(OrbFrames<N> b)
 {
     RELOC_SMALL_KERNEL_PRIO();
-    select_body(tab, cand_cnt, cand_key, cand_resp, kp_cnt, kp_key, kp_resp);
-}
-__global__ __launch_bounds__(1024) void k_select_batch(OrbBatch b)
-{
-    RELOC_SMALL_KERNEL_PRIO();
-    const OrbFrame &F = b.f[blockIdx.y];
+    const OrbFrame &F = b.at(blockIdx.y);
     select_body(F.tab, F.cand_cnt, F.cand_key, F.cand_resp, F.kp_cnt, F.kp_key, F.kp_resp);
 }
 
@@ -1051,21 +1029,11 @@ __device__ __forceinline__ void describe_body(const OrbTable *__restrict__ tab, 
         f_oct[g] = l;
     }
 }
-__global__ __launch_bounds__(256) void k_describe(const OrbTable *__restrict__ tab, const uint8_t *__restrict__ pyr,
-                                                  const uint8_t *__restrict__ blur, const int32_t *__restrict__ kp_cnt,
-                                                  const u32 *__restrict__ kp_key, const float *__restrict__ kp_resp,
-                                                  int max_feat, float *__restrict__ f_xy, float *__restrict__ f_size,
-                                                  float *__restrict__ f_angle, float *__restrict__ f_resp,
-                                                  int32_t *__restrict__ f_oct, uint8_t *__restrict__ f_desc,
-                                                  int32_t *__restrict__ f_count)
+template <int N>
+__global__ __launch_bounds__(256) void k_describe(OrbFrames<N> b, int max_feat)
 {
     RELOC_SMALL_KERNEL_PRIO();
-    describe_body(tab, pyr, blur, kp_cnt, kp_key, kp_resp, max_feat, f_xy, f_size, f_angle, f_resp, f_oct, f_desc, f_count);
-}
-__global__ __launch_bounds__(256) void k_describe_batch(OrbBatch b, int max_feat)
-{
-    RELOC_SMALL_KERNEL_PRIO();
-    const OrbFrame &F = b.f[blockIdx.y];
+    const OrbFrame &F = b.at(blockIdx.y);
     describe_body(F.tab, F.pyr, F.blur, F.kp_cnt, F.kp_key, F.kp_resp, max_feat, F.f_xy, F.f_size, F.f_angle, F.f_resp, F.f_oct, F.f_desc,
                   F.f_count);
 }
@@ -1184,6 +1152,38 @@ static void mask_pyramid_launch(reloc_ctx *c, uint8_t *mp)
 // stage on, w x h is the source size and everything from orb_prepare on sees the working frame.  The pyramid reads the last
 // plane the chain wrote, or the frame itself.  It runs 512-thread workgroups for latency, 256 where it shares the chip with
 // whole-database scans.
+template <int N>
+static void orb_launch(reloc_ctx *c0, int n, const OrbFrames<RELOC_BATCH_MAX> &all, const OrbParams &P, int w, int h, int stride,
+                       int flags, int channels, bool aligned, bool masked, bool latency)
+{
+    const OrbFrames<N> b = frame_table<N>(all);
+    const OrbTable *tab_h = &c0->orb.tab;
+    hipStream_t st = c0->stream;
+    const int n_fast = tab_h->fast_tile_base[NLEV], n_blur = tab_h->blur_tile_base[NLEV];
+    // the default detector runs the kernels built for it; any other threshold or score the ones that read the table
+    const bool thr_def = P.fast_thr == RELOC_FAST_THRESHOLD;
+    const int mode = P.score == RELOC_ORB_FAST_SCORE ? ORB_MODE_FAST : thr_def ? ORB_MODE_DEFAULT : ORB_MODE_HARRIS;
+    if constexpr (N == 1) {         // k_pyramid: pointer arguments for one frame, and only one frame gets the 512-thread shape
+        const OrbFrame &F = b.f[0];
+        auto kern512 = channels == 3 ? (aligned ? k_pyramid<3, true, 512> : k_pyramid<3, false, 512>) : (aligned ? k_pyramid<1, true, 512> : k_pyramid<1, false, 512>);
+        auto kern256 = channels == 3 ? (aligned ? k_pyramid<3, true, 256> : k_pyramid<3, false, 256>) : (aligned ? k_pyramid<1, true, 256> : k_pyramid<1, false, 256>);
+        hipLaunchKernelGGL(latency ? kern512 : kern256, dim3(c0->orb.ntiles), dim3(latency ? 512 : 256), c0->orb.lds_bytes, st, F.tab,
+                           F.tiles, F.rz, F.src, w, h, stride, flags, F.pyr, c0->orb.lds, F.hist, F.cand_cnt);
+    } else {
+        auto kern = channels == 3 ? (aligned ? k_pyramid_batch<3, true, 256> : k_pyramid_batch<3, false, 256>)
+                                  : (aligned ? k_pyramid_batch<1, true, 256> : k_pyramid_batch<1, false, 256>);
+        hipLaunchKernelGGL(kern, dim3(c0->orb.ntiles, n), dim3(256), c0->orb.lds_bytes, st, b, w, h, stride, flags, c0->orb.lds);
+    }
+    auto fast = masked ? (thr_def ? k_fast_blur<true, RELOC_FAST_THRESHOLD, N> : k_fast_blur<true, 0, N>)
+                       : (thr_def ? k_fast_blur<false, RELOC_FAST_THRESHOLD, N> : k_fast_blur<false, 0, N>);
+    auto harris = mode == ORB_MODE_FAST ? k_harris<ORB_MODE_FAST, N>
+                                        : mode == ORB_MODE_HARRIS ? k_harris<ORB_MODE_HARRIS, N> : k_harris<ORB_MODE_DEFAULT, N>;
+    hipLaunchKernelGGL(fast, dim3(n_fast + n_blur, n), dim3(256), 0, st, b, n_fast);
+    hipLaunchKernelGGL(harris, dim3(tab_h->flat_base[NLEV], n), dim3(256), 0, st, b);
+    hipLaunchKernelGGL(k_select<N>, dim3(NLEV, n), dim3(1024), 0, st, b);
+    hipLaunchKernelGGL(k_describe<N>, dim3((c0->max_feat + 3) / 4, n), dim3(256), 0, st, b, c0->max_feat);
+}
+
 int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, int h, int stride, bool chain, int order,
             int nfeatures, bool latency, bool call_mask, const OrbParams *call_prm)
 {
@@ -1223,9 +1223,7 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
             else if (!m.built || !m.built_prm.same(P)) { mask_pyramid_launch(ctxs[f], m.pyr); m.built = true; m.built_prm = P; }
             m.last = call_mask ? m.call : m.pyr; m.last_w = w; m.last_h = h;
         }
-    const OrbTable *tab_h = &c0->orb.tab;
     const int flags = gray_flags(c0, order);
-    hipStream_t st = c0->stream;
     reloc_prof_begin(c0, RELOC_PROF_ORB);
     const uint8_t *planes[RELOC_BATCH_MAX];
     int channels = 1;       // of what the pyramid reads: the last plane the chain wrote, a gray plane, or a 3-channel frame
@@ -1235,42 +1233,10 @@ int orb_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *srcs, int w, in
     }
     bool aligned = w % 4 == 0 && stride % 4 == 0;
     for (int f = 0; f < n; ++f) aligned = aligned && ((uintptr_t)srcs[f]) % 4 == 0;
-    OrbBatch b;
+    OrbFrames<RELOC_BATCH_MAX> b;
     frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int g) { b.f[f] = c->orb.buf; b.f[f].src = srcs[g]; b.f[f].mask = masked ? c->orb.mask.last : nullptr; });
-    const PyrLds lds = c0->orb.lds;
-    const int n_fast = tab_h->fast_tile_base[NLEV], n_blur = tab_h->blur_tile_base[NLEV];
-    // the default detector runs the kernels built for it; any other threshold or score the ones that read the table
-    const bool thr_def = P.fast_thr == RELOC_FAST_THRESHOLD;
-    const int mode = P.score == RELOC_ORB_FAST_SCORE ? ORB_MODE_FAST : thr_def ? ORB_MODE_DEFAULT : ORB_MODE_HARRIS;
-    if (n == 1) {
-        const OrbFrame &F = b.f[0];
-        auto kern512 = channels == 3 ? (aligned ? k_pyramid<3, true, 512> : k_pyramid<3, false, 512>) : (aligned ? k_pyramid<1, true, 512> : k_pyramid<1, false, 512>);
-        auto kern256 = channels == 3 ? (aligned ? k_pyramid<3, true, 256> : k_pyramid<3, false, 256>) : (aligned ? k_pyramid<1, true, 256> : k_pyramid<1, false, 256>);
-        hipLaunchKernelGGL(latency ? kern512 : kern256, dim3(c0->orb.ntiles), dim3(latency ? 512 : 256), c0->orb.lds_bytes, st, F.tab,
-                           F.tiles, F.rz, F.src, w, h, stride, flags, F.pyr, lds, F.hist, F.cand_cnt);
-        auto fast = masked ? (thr_def ? k_fast_blur<true, RELOC_FAST_THRESHOLD> : k_fast_blur<true, 0>)
-                           : (thr_def ? k_fast_blur<false, RELOC_FAST_THRESHOLD> : k_fast_blur<false, 0>);
-        auto harris = mode == ORB_MODE_FAST ? k_harris<ORB_MODE_FAST> : mode == ORB_MODE_HARRIS ? k_harris<ORB_MODE_HARRIS> : k_harris<ORB_MODE_DEFAULT>;
-        hipLaunchKernelGGL(fast, dim3(n_fast + n_blur), dim3(256), 0, st, F.tab, F.pyr, F.nms, F.hist, F.blur, n_fast, F.mask);
-        hipLaunchKernelGGL(harris, dim3(tab_h->flat_base[NLEV]), dim3(256), 0, st, F.tab, F.pyr, F.nms, F.hist, F.cand_cnt, F.cand_key,
-                           F.cand_resp, F.dbg_cut);
-        hipLaunchKernelGGL(k_select, dim3(NLEV), dim3(1024), 0, st, F.tab, F.cand_cnt, F.cand_key, F.cand_resp, F.kp_cnt, F.kp_key,
-                           F.kp_resp);
-        hipLaunchKernelGGL(k_describe, dim3((c0->max_feat + 3) / 4), dim3(256), 0, st, F.tab, F.pyr, F.blur, F.kp_cnt, F.kp_key,
-                           F.kp_resp, c0->max_feat, F.f_xy, F.f_size, F.f_angle, F.f_resp, F.f_oct, F.f_desc, F.f_count);
-    } else {
-        auto kern = channels == 3 ? (aligned ? k_pyramid_batch<3, true, 256> : k_pyramid_batch<3, false, 256>)
-                                  : (aligned ? k_pyramid_batch<1, true, 256> : k_pyramid_batch<1, false, 256>);
-        hipLaunchKernelGGL(kern, dim3(c0->orb.ntiles, n), dim3(256), c0->orb.lds_bytes, st, b, w, h, stride, flags, lds);
-        auto fast = masked ? (thr_def ? k_fast_blur_batch<true, RELOC_FAST_THRESHOLD> : k_fast_blur_batch<true, 0>)
-                           : (thr_def ? k_fast_blur_batch<false, RELOC_FAST_THRESHOLD> : k_fast_blur_batch<false, 0>);
-        auto harris = mode == ORB_MODE_FAST ? k_harris_batch<ORB_MODE_FAST>
-                                            : mode == ORB_MODE_HARRIS ? k_harris_batch<ORB_MODE_HARRIS> : k_harris_batch<ORB_MODE_DEFAULT>;
-        hipLaunchKernelGGL(fast, dim3(n_fast + n_blur, n), dim3(256), 0, st, b, n_fast);
-        hipLaunchKernelGGL(harris, dim3(tab_h->flat_base[NLEV], n), dim3(256), 0, st, b);
-        hipLaunchKernelGGL(k_select_batch, dim3(NLEV, n), dim3(1024), 0, st, b);
-        hipLaunchKernelGGL(k_describe_batch, dim3((c0->max_feat + 3) / 4, n), dim3(256), 0, st, b, c0->max_feat);
-    }
+    n == 1 ? orb_launch<1>(c0, n, b, P, w, h, stride, flags, channels, aligned, masked, latency)
+           : orb_launch<RELOC_BATCH_MAX>(c0, n, b, P, w, h, stride, flags, channels, aligned, masked, latency);
     reloc_prof_end(c0, RELOC_PROF_ORB);
     HIP_TRY(hipGetLastError());
     return RELOC_OK;

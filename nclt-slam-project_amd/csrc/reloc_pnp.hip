@@ -317,7 +317,6 @@ struct PnpParams {
     double K4[4];
     double conf;
     double thr2;
-    uint64_t seed;
     int iters;
     int stride;      // rows per candidate in obj/img/inlier arrays
     int min_m;       // fewer correspondences than this => no model (matcher gate M:330, or 4)
@@ -327,13 +326,14 @@ struct PnpParams {
     int gate_local, gate_global;
 };
 
-// Frame-batched launches (reloc_tick_batch_dev, the sharded halves): the candidates of up to 8 contexts in one launch per
-// kernel; the frame is the last grid dimension.
+// The candidates of the 1..8 contexts of a call in one launch per kernel; the frame is the last grid dimension (FrameTable:
+// reloc_internal.h).  mask: k_pnp_score's per-point inlier flags (reloc_pnp_score), NULL in a tick.  PnpParams is what the
+// frames share.
 struct PnpFrame {
     const float *obj, *img; const int32_t *m_arr, *n_cand_p; double *Rt; int32_t *cnt, *inl; PnpOut *out; uint64_t seed;
-    const int32_t *relocating;
+    const int32_t *relocating; uint8_t *mask;
 };
-struct PnpBatch { PnpFrame f[RELOC_BATCH_MAX]; };
+template <int N> using PnpFrames = FrameTable<PnpFrame, N>;
 
 // grid (ceil(iters/64), n_cand_max), block 256: FOUR lanes per hypothesis.  The sampler, the quartic and its resolvent are
 // per hypothesis (the four lanes of a quad compute them in lockstep, same values); each of the <= 4 real roots is then
@@ -350,8 +350,8 @@ __device__ __forceinline__ int pnp_gate(const PnpParams &prm, const int32_t *rel
 template <bool DIST>
 __device__ __forceinline__ void pnp_hyp_body(const float *__restrict__ obj, const float *__restrict__ img,
                                              const int32_t *__restrict__ m_arr, const int32_t *__restrict__ n_cand_p,
-                                             const PnpParams &prm, double *__restrict__ Rt_out, int32_t *__restrict__ cnt,
-                                             const int32_t *__restrict__ relocating_p, const DistCoef &dc)
+                                             const PnpParams &prm, uint64_t seed, double *__restrict__ Rt_out,
+                                             int32_t *__restrict__ cnt, const int32_t *__restrict__ relocating_p, const DistCoef &dc)
 {
     const int c = blockIdx.y;
     if (n_cand_p && c >= *n_cand_p) return;
@@ -365,7 +365,7 @@ __device__ __forceinline__ void pnp_hyp_body(const float *__restrict__ obj, cons
     int idx[4];
     PNP_T(0);
     // fewer correspondences than the inlier gate: no consensus set of this candidate can be accepted -- no hypotheses at all
-    if (m < prm.min_m || m < pnp_gate(prm, relocating_p) || !pnp_sample(prm.seed, h, m, idx)) { if (sol == 0) *cn = -1; return; }
+    if (m < prm.min_m || m < pnp_gate(prm, relocating_p) || !pnp_sample(seed, h, m, idx)) { if (sol == 0) *cn = -1; return; }
     PNP_T(1);
     double P[9], xn[6], Rt[12];
     for (int k = 0; k < 3; ++k) {
@@ -418,23 +418,13 @@ __device__ __forceinline__ void pnp_hyp_body(const float *__restrict__ obj, cons
     }
     PNP_T(7);
 }
-template <bool DIST>
-__global__ __launch_bounds__(HYP_BLOCK) void k_pnp_hyp(const float *__restrict__ obj, const float *__restrict__ img,
-                                                const int32_t *__restrict__ m_arr, const int32_t *__restrict__ n_cand_p,
-                                                PnpParams prm, double *__restrict__ Rt_out, int32_t *__restrict__ cnt,
-                                                const int32_t *__restrict__ relocating_p, DistCoef dc)
-{
-    RELOC_SMALL_KERNEL_PRIO();
-    pnp_hyp_body<DIST>(obj, img, m_arr, n_cand_p, prm, Rt_out, cnt, relocating_p, dc);
-}
 // grid (ceil(iters/64), n_cand_max, frames)
-template <bool DIST>
-__global__ __launch_bounds__(HYP_BLOCK) void k_pnp_hyp_batch(PnpBatch b, PnpParams prm, DistCoef dc)
+template <bool DIST, int N>
+__global__ __launch_bounds__(HYP_BLOCK) void k_pnp_hyp(PnpFrames<N> b, PnpParams prm, DistCoef dc)
 {
     RELOC_SMALL_KERNEL_PRIO();
-    const PnpFrame &F = b.f[blockIdx.z];
-    prm.seed = F.seed;
-    pnp_hyp_body<DIST>(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, F.relocating, dc);
+    const PnpFrame &F = b.at(blockIdx.z);
+    pnp_hyp_body<DIST>(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.seed, F.Rt, F.cnt, F.relocating, dc);
 }
 
 
@@ -471,23 +461,13 @@ __device__ __forceinline__ void pnp_score_body(const float *__restrict__ obj, co
     }
     if (threadIdx.x == 0) *cn = count;
 }
-template <bool DIST>
-__global__ __launch_bounds__(64) void k_pnp_score(const float *__restrict__ obj, const float *__restrict__ img,
-                                                  const int32_t *__restrict__ m_arr, const int32_t *__restrict__ n_cand_p,
-                                                  PnpParams prm, const double *__restrict__ Rt_in,
-                                                  int32_t *__restrict__ cnt, uint8_t *__restrict__ mask, int hyp_stride,
-                                                  DistCoef dc)
-{
-    RELOC_SMALL_KERNEL_PRIO();
-    pnp_score_body<DIST>(obj, img, m_arr, n_cand_p, prm, Rt_in, cnt, mask, hyp_stride, dc);
-}
 // grid (iters, n_cand_max, frames)
-template <bool DIST>
-__global__ __launch_bounds__(64) void k_pnp_score_batch(PnpBatch b, PnpParams prm, int hyp_stride, DistCoef dc)
+template <bool DIST, int N>
+__global__ __launch_bounds__(64) void k_pnp_score(PnpFrames<N> b, PnpParams prm, int hyp_stride, DistCoef dc)
 {
     RELOC_SMALL_KERNEL_PRIO();
-    const PnpFrame &F = b.f[blockIdx.z];
-    pnp_score_body<DIST>(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, nullptr, hyp_stride, dc);
+    const PnpFrame &F = b.at(blockIdx.z);
+    pnp_score_body<DIST>(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, F.mask, hyp_stride, dc);
 }
 
 
@@ -892,38 +872,24 @@ __device__ __forceinline__ void pnp_finish_body(const float *__restrict__ obj, c
     PNP_T(13);
     PNP_V(14, n);
 }
-template <bool DIST, int WAVES>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) void k_pnp_finish(const float *__restrict__ obj, const float *__restrict__ img,
-                                                   const int32_t *__restrict__ m_arr, const int32_t *__restrict__ n_cand_p,
-                                                   PnpParams prm, const double *__restrict__ Rt_all,
-                                                   const int32_t *__restrict__ cnt, int32_t *__restrict__ inl_out,
-                                                   PnpOut *__restrict__ out, const int32_t *__restrict__ relocating_p,
-                                                   DistCoef dc)
-{
-    RELOC_SMALL_KERNEL_PRIO();
-    pnp_finish_body<DIST>(obj, img, m_arr, n_cand_p, prm, Rt_all, cnt, inl_out, out, relocating_p, dc);
-}
 // grid (n_cand_max, frames)
-template <bool DIST, int WAVES>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) void k_pnp_finish_batch(PnpBatch b, PnpParams prm, DistCoef dc)
+template <bool DIST, int WAVES, int N>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) void k_pnp_finish(PnpFrames<N> b, PnpParams prm, DistCoef dc)
 {
     RELOC_SMALL_KERNEL_PRIO();
-    const PnpFrame &F = b.f[blockIdx.y];
-    prm.seed = F.seed;
+    const PnpFrame &F = b.at(blockIdx.y);
     pnp_finish_body<DIST>(F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, F.inl, F.out, F.relocating, dc);
 }
 // DIST: one instantiation for every shape, budget PNP_DIST_WAVES (see pnp_launch)
 constexpr int PNP_DIST_WAVES = 2;
 
 
-static PnpParams make_params(const double K4[4], int iters, float thr_px, double conf, uint64_t seed, int stride,
-                             int min_m)
+static PnpParams make_params(const double K4[4], int iters, float thr_px, double conf, int stride, int min_m)
 {
     PnpParams p;
     for (int k = 0; k < 4; ++k) p.K4[k] = K4[k];
     p.conf = conf;
     p.thr2 = (double)thr_px * (double)thr_px;
-    p.seed = seed;
     p.iters = iters;
     p.stride = stride;
     p.min_m = min_m < RELOC_PNP_SAMPLE ? RELOC_PNP_SAMPLE : min_m;
@@ -944,46 +910,41 @@ static PnpFrame pnp_frame(const reloc_ctx *c, uint64_t seed)
     PnpFrame F;
     const TickState &t = c->tick;
     F.obj = t.p_obj; F.img = t.p_img; F.m_arr = tick_pnp_lengths(c); F.n_cand_p = t.cand_n; F.Rt = t.p_Rt; F.cnt = t.p_cnt; F.inl = t.p_inl;
-    F.out = t.p_out; F.seed = seed; F.relocating = t.flags;
+    F.out = t.p_out; F.seed = seed; F.relocating = t.flags; F.mask = nullptr;
     return F;
 }
 
-// Three launches for up to n_cand_max candidates of every frame (grid y / z = frame at n > 1); prm.seed is each frame's.
+// Three launches for up to n_cand_max candidates of every frame (the last grid dimension = frame).
 // The DIST kernels run when dist is non-NULL.  Their k_pnp_finish has ONE register budget, PNP_DIST_WAVES = 2 waves per SIMD
 // (256 VGPRs): the forward model and its Jacobian do not fit the pinhole kernel's 128 without scratch.
-static int pnp_launch(reloc_ctx *const *ctxs, int n, const PnpBatch &b, int n_cand_max, PnpParams prm, const double *dist,
-                      bool latency)
+template <int N>
+static void pnp_launch_n(hipStream_t st, int n, const PnpFrames<RELOC_BATCH_MAX> &all, int n_cand_max, const PnpParams &prm,
+                         const double *dist, bool latency)
+{
+    const PnpFrames<N> b = frame_table<N>(all);
+    const DistCoef dc = make_dist(dist);
+    const int iters = prm.iters;
+    auto hyp = dist ? k_pnp_hyp<true, N> : k_pnp_hyp<false, N>;
+    auto score = dist ? k_pnp_score<true, N> : k_pnp_score<false, N>;
+    auto finish = dist ? k_pnp_finish<true, PNP_DIST_WAVES, N> : k_pnp_finish<false, 4, N>;
+    if constexpr (N == 1)
+        if (latency && !dist) finish = k_pnp_finish<false, 1, N>;
+    hipLaunchKernelGGL(hyp, dim3((iters + 63) / 64, n_cand_max, n), dim3(HYP_BLOCK), 0, st, b, prm, dc);
+    hipLaunchKernelGGL(score, dim3(iters, n_cand_max, n), dim3(64), 0, st, b, prm, MAX_HYP, dc);
+    hipLaunchKernelGGL(finish, dim3(n_cand_max, n), dim3(64), 0, st, b, prm, dc);
+}
+static int pnp_launch(reloc_ctx *const *ctxs, int n, const PnpFrames<RELOC_BATCH_MAX> &b, int n_cand_max, const PnpParams &prm,
+                      const double *dist, bool latency)
 {
     reloc_ctx *c0 = ctxs[0];
-    const int iters = prm.iters;
     if (n_cand_max <= 0) return RELOC_OK;
-    if (n < 1 || n > RELOC_BATCH_MAX || n_cand_max > MAX_CAND || iters < 1 || iters > MAX_HYP) {
-        reloc_set_error("pnp: n %d n_cand %d (max %d) iters %d (max %d)", n, n_cand_max, MAX_CAND, iters, MAX_HYP);
+    if (n < 1 || n > RELOC_BATCH_MAX || n_cand_max > MAX_CAND || prm.iters < 1 || prm.iters > MAX_HYP) {
+        reloc_set_error("pnp: n %d n_cand %d (max %d) iters %d (max %d)", n, n_cand_max, MAX_CAND, prm.iters, MAX_HYP);
         return RELOC_E_CAPACITY;
     }
-    const DistCoef dc = make_dist(dist);
-    hipStream_t st = c0->stream;
     reloc_prof_begin(c0, RELOC_PROF_PNP);
-    if (n == 1) {
-        const PnpFrame &F = b.f[0];
-        prm.seed = F.seed;
-        auto hyp = dist ? k_pnp_hyp<true> : k_pnp_hyp<false>;
-        auto score = dist ? k_pnp_score<true> : k_pnp_score<false>;
-        auto finish = dist ? k_pnp_finish<true, PNP_DIST_WAVES> : latency ? k_pnp_finish<false, 1> : k_pnp_finish<false, 4>;
-        hipLaunchKernelGGL(hyp, dim3((iters + 63) / 64, n_cand_max), dim3(HYP_BLOCK), 0, st, F.obj, F.img, F.m_arr, F.n_cand_p, prm,
-                           F.Rt, F.cnt, F.relocating, dc);
-        hipLaunchKernelGGL(score, dim3(iters, n_cand_max), dim3(64), 0, st, F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt,
-                           (uint8_t *)nullptr, MAX_HYP, dc);
-        hipLaunchKernelGGL(finish, dim3(n_cand_max), dim3(64), 0, st, F.obj, F.img, F.m_arr, F.n_cand_p, prm, F.Rt, F.cnt, F.inl,
-                           F.out, F.relocating, dc);
-    } else {
-        auto hyp = dist ? k_pnp_hyp_batch<true> : k_pnp_hyp_batch<false>;
-        auto score = dist ? k_pnp_score_batch<true> : k_pnp_score_batch<false>;
-        auto finish = dist ? k_pnp_finish_batch<true, PNP_DIST_WAVES> : k_pnp_finish_batch<false, 4>;
-        hipLaunchKernelGGL(hyp, dim3((iters + 63) / 64, n_cand_max, n), dim3(HYP_BLOCK), 0, st, b, prm, dc);
-        hipLaunchKernelGGL(score, dim3(iters, n_cand_max, n), dim3(64), 0, st, b, prm, MAX_HYP, dc);
-        hipLaunchKernelGGL(finish, dim3(n_cand_max, n), dim3(64), 0, st, b, prm, dc);
-    }
+    n == 1 ? pnp_launch_n<1>(c0->stream, n, b, n_cand_max, prm, dist, latency)
+           : pnp_launch_n<RELOC_BATCH_MAX>(c0->stream, n, b, n_cand_max, prm, dist, latency);
     reloc_prof_end(c0, RELOC_PROF_PNP);
     HIP_TRY(hipGetLastError());
     return RELOC_OK;
@@ -993,10 +954,10 @@ int pnp_run_candidates(reloc_ctx *const *ctxs, int n, const uint64_t *seeds, boo
 {
     reloc_ctx *c0 = ctxs[0];
     const reloc_params &q = c0->prm;
-    PnpParams prm = make_params(c0->cam.K4, q.ransac_iterations, (float)q.ransac_reproj_px, q.ransac_confidence, 0, MAX_REC_ROWS,
+    PnpParams prm = make_params(c0->cam.K4, q.ransac_iterations, (float)q.ransac_reproj_px, q.ransac_confidence, MAX_REC_ROWS,
                                 q.min_matches);
     prm.gate_local = q.min_inliers; prm.gate_global = q.global_min_inliers;
-    PnpBatch b;
+    PnpFrames<RELOC_BATCH_MAX> b;
     frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int g) { b.f[f] = pnp_frame(c, seeds ? seeds[g] : 0); });
     // the contexts of a call carry equal coefficients (ctx_batch_check)
     return pnp_launch(ctxs, n, b, MAX_CAND, prm, c0->cam.lens(), latency);
@@ -1017,11 +978,13 @@ static int pnp_score_impl(reloc_ctx *ctx, const float *obj, const float *img, in
     if (st.rc) return st.rc;
     int32_t *dm = dcnt + H;
     const float *dobj = st.upload_slot(0, obj, (int64_t)m * 3), *dimg = st.upload_slot(1, img, (int64_t)m * 2);
-    const double *drt = st.upload_slot(2, Rt, (int64_t)H * 12);
+    double *drt = st.upload_slot(2, Rt, (int64_t)H * 12);
     st.upload(dm, &m, 4);
     st.run([&] { HIP_TRY(hipMemsetAsync(dcnt, 0, (size_t)H * 4, ctx->stream)); return RELOC_OK; });
-    st.launch(dist ? k_pnp_score<true> : k_pnp_score<false>, dim3(H, 1), dim3(64), dobj, dimg, dm, (const int32_t *)nullptr,
-              make_params(K4, H, thr_px, 0.99, 0, m, 0), drt, dcnt, dmask, H, make_dist(dist));
+    PnpFrames<1> b = {};                // one candidate of m pairs on the scratch slots: H hypotheses, H counts, H x m flags
+    b.f[0].obj = dobj; b.f[0].img = dimg; b.f[0].m_arr = dm; b.f[0].Rt = drt; b.f[0].cnt = dcnt; b.f[0].mask = dmask;
+    st.launch(dist ? k_pnp_score<true, 1> : k_pnp_score<false, 1>, dim3(H, 1), dim3(64), b, make_params(K4, H, thr_px, 0.99, m, 0), H,
+              make_dist(dist));
     st.download(inlier_count, dcnt, (int64_t)H * 4);
     if (mask) st.download(mask, dmask, (int64_t)H * m);
     return st.finish();
@@ -1061,11 +1024,11 @@ static int pnp_ransac_impl(reloc_ctx *ctx, const float *obj, const float *img, i
     st.upload(ctx->tick.p_img, img, (int64_t)m * 8);
     st.upload(ctx->tick.m_n, &m, 4);
     // the single-call path has no MIN_MATCHES gate (that gate belongs to the matcher, M:330)
-    PnpBatch b;
+    PnpFrames<RELOC_BATCH_MAX> b;
     b.f[0] = pnp_frame(ctx, seed);
     b.f[0].n_cand_p = nullptr; b.f[0].relocating = nullptr;       // one candidate of m pairs, no relocation flag
     b.f[0].m_arr = ctx->tick.m_n;                                 // ... its length uploaded above, whatever the match policy
-    st.run([&] { return pnp_launch(&ctx, 1, b, 1, make_params(K4, iters, thr_px, conf, seed, MAX_REC_ROWS, RELOC_PNP_SAMPLE), dist, true); });
+    st.run([&] { return pnp_launch(&ctx, 1, b, 1, make_params(K4, iters, thr_px, conf, MAX_REC_ROWS, RELOC_PNP_SAMPLE), dist, true); });
     PnpOut po = {};
     st.download(&po, ctx->tick.p_out, sizeof(po));
     if (int rc = st.finish()) return rc;

@@ -14,8 +14,9 @@
 
 #include "reloc_internal.h"
 
+// What the frames of a call share; base_pose is that of a local candidate search (k_candidates_*: one launch per frame).
 struct TickParams {
-    double base_pose[7];
+    double base_pose[7];      // read by k_candidates_* only
     double b2c_t[3];
     double b2c_R[9];
     int mode;                 // RELOC_TICK_LOCAL / GLOBAL / AUTO; which one produced the candidates is the device flag
@@ -24,7 +25,7 @@ struct TickParams {
     // matcher parameters (reloc_params)
     int max_candidates, min_matches, min_inliers, global_min_inliers;
     double radius_m, cos_tol, reproj_max_px, global_reproj_max_px, consistency_m;
-    int seq;                  // sequence stamp of this tick (ctx->tick.seq), stored into the host records after their body
+    int seq;                  // unread: keeps the kernel arguments behind a TickParams where they were
 };
 
 __device__ void rot_to_quat(const double R[9], double q[4])
@@ -330,26 +331,29 @@ __device__ __forceinline__ void topk_counts_body(const int32_t *__restrict__ cou
         }
     }
 }
-__global__ __launch_bounds__(TOPK_HIST_THREADS) void k_topk_counts(const int32_t *__restrict__ counts, int L, int k, int id_base,
-                                                                   int min_matches, int max_count, int32_t *__restrict__ out_ids,
-                                                                   int32_t *__restrict__ out_counts, int32_t *out_n,
-                                                                   const int32_t *skip_if, int32_t *__restrict__ relocating,
-                                                                   const int32_t *__restrict__ f_count = nullptr,
-                                                                   int32_t *__restrict__ out_nfeat = nullptr)
-{
-    RELOC_SMALL_KERNEL_PRIO();
-    topk_counts_body(counts, L, k, id_base, min_matches, max_count, out_ids, out_counts, out_n, skip_if, relocating, f_count, out_nfeat);
-}
-// the rankings of up to 8 frames in one launch: block = frame
+// the rankings of the 1..8 frames of a call in one launch: block = frame
 struct TopkFrame {
     const int32_t *counts; int32_t *out_ids, *out_counts, *out_n; const int32_t *skip_if; int32_t *relocating; const int32_t *f_count;
     int32_t *out_nfeat;
 };
-struct TopkBatch { TopkFrame f[RELOC_BATCH_MAX]; };
-__global__ __launch_bounds__(TOPK_HIST_THREADS) void k_topk_counts_batch(TopkBatch b, int L, int k, int id_base, int min_matches, int max_count)
+template <int N> using TopkFrames = FrameTable<TopkFrame, N>;
+// One frame keeps a pointer-argument kernel beside the frame-table one: the 1024-thread block needs four wave slots on every
+// SIMD of one CU at once, beside four resident scan waves, and fits there by SGPRs at the pointer form's 45 and not at the
+// table form's 58 (ranking 10 -> 56 us, 10 % of the 4-stream frame rate; the arithmetic and the measurements: DESIGN.md, 4).
+__global__ __launch_bounds__(TOPK_HIST_THREADS) void k_topk_counts(const int32_t *__restrict__ counts, int L, int k, int id_base,
+                                                                   int min_matches, int max_count, int32_t *__restrict__ out_ids,
+                                                                   int32_t *__restrict__ out_counts, int32_t *out_n,
+                                                                   const int32_t *skip_if, int32_t *__restrict__ relocating,
+                                                                   const int32_t *__restrict__ f_count, int32_t *__restrict__ out_nfeat)
 {
     RELOC_SMALL_KERNEL_PRIO();
-    const TopkFrame &F = b.f[blockIdx.x];
+    topk_counts_body(counts, L, k, id_base, min_matches, max_count, out_ids, out_counts, out_n, skip_if, relocating, f_count, out_nfeat);
+}
+__global__ __launch_bounds__(TOPK_HIST_THREADS) void k_topk_counts_batch(TopkFrames<RELOC_BATCH_MAX> b, int L, int k, int id_base, int min_matches,
+                                                                         int max_count)
+{
+    RELOC_SMALL_KERNEL_PRIO();
+    const TopkFrame &F = b.at(blockIdx.x);
     topk_counts_body(F.counts, L, k, id_base, min_matches, max_count, F.out_ids, F.out_counts, F.out_n, F.skip_if, F.relocating, F.f_count,
                      F.out_nfeat);
 }
@@ -471,8 +475,9 @@ __device__ __forceinline__ void tick_stamp(TickResult *res_host, TickResult *res
 __device__ __forceinline__ void tick_finalize_body(const int32_t *__restrict__ cand_ids, const int32_t *__restrict__ cand_n,
                                                    const PnpOut *__restrict__ pnp, const double *__restrict__ db_pose,
                                                    const int32_t *__restrict__ f_count, const TickParams &prm,
-                                                   const int32_t *__restrict__ relocating_p, TickResult *__restrict__ res,
-                                                   TickResult *__restrict__ res_host, TickResult *__restrict__ res_ext, int seq){
+                                                   const double (&base_pose)[7], const int32_t *__restrict__ relocating_p,
+                                                   TickResult *__restrict__ res, TickResult *__restrict__ res_host,
+                                                   TickResult *__restrict__ res_ext, int seq){
     // seq: after the record's 96 bytes, its last-but-one word (pad[0]) receives the tick's sequence stamp with a system-scope
     // release store: a host that polls that word (reloc_tick_wait) has the complete record the moment it sees the stamp,
     // without going through the runtime's stream-completion path.
@@ -546,7 +551,7 @@ __device__ __forceinline__ void tick_finalize_body(const int32_t *__restrict__ c
         out.pad[0] = out.pad[1] = 0;
         for (int k = 0; k < 7; ++k) out.anchor_pose[k] = pose[k];
         out.n_inl = inl; out.reproj = err; out.lm_idx = cand_ids[s]; out.relocating = relocating; out.n_features = nfeat; out.n_candidates = nc;
-        const double dx = pose[0] - prm.base_pose[0], dy = pose[1] - prm.base_pose[1];
+        const double dx = pose[0] - base_pose[0], dy = pose[1] - base_pose[1];
         const double shift = sqrt(dx * dx + dy * dy);
         out.outcome = (check && shift > prm.consistency_m) ? RELOC_OUT_CONSISTENCY_FAIL : RELOC_OUT_PUBLISHED;
         *res = out;
@@ -555,28 +560,19 @@ __device__ __forceinline__ void tick_finalize_body(const int32_t *__restrict__ c
         tick_stamp(res_host, res_ext, seq);
     }
 }
-__global__ __launch_bounds__(64) void k_tick_finalize(const int32_t *__restrict__ cand_ids, const int32_t *__restrict__ cand_n,
-                                                      const PnpOut *__restrict__ pnp, const double *__restrict__ db_pose,
-                                                      const int32_t *__restrict__ f_count, TickParams prm,
-                                                      const int32_t *__restrict__ relocating_p, TickResult *__restrict__ res,
-                                                      TickResult *__restrict__ res_host, TickResult *__restrict__ res_ext)
-{
-    RELOC_SMALL_KERNEL_PRIO();
-    tick_finalize_body(cand_ids, cand_n, pnp, db_pose, f_count, prm, relocating_p, res, res_host, res_ext, prm.seq);
-}
-// the finalisation of up to 8 frames in one launch: block = frame; prm carries what the frames share, F.base_pose the rest
+// the finalisation of the 1..8 frames of a call in one launch: block = frame; prm carries what the frames share
 struct FinalFrame {
     const int32_t *cand_ids, *cand_n; const PnpOut *pnp; const int32_t *f_count, *relocating; TickResult *res, *res_host, *res_ext;
     double base_pose[7];
-    int seq;
+    int seq;                  // sequence stamp of this tick (ctx->tick.seq), stored into the host records after their body
 };
-struct FinalBatch { FinalFrame f[RELOC_BATCH_MAX]; };
-__global__ __launch_bounds__(64) void k_tick_finalize_batch(FinalBatch b, const double *__restrict__ db_pose, TickParams prm)
+template <int N> using FinalFrames = FrameTable<FinalFrame, N>;
+template <int N>
+__global__ __launch_bounds__(64) void k_tick_finalize(FinalFrames<N> b, const double *__restrict__ db_pose, TickParams prm)
 {
     RELOC_SMALL_KERNEL_PRIO();
-    const FinalFrame &F = b.f[blockIdx.x];
-    for (int k = 0; k < 7; ++k) prm.base_pose[k] = F.base_pose[k];
-    tick_finalize_body(F.cand_ids, F.cand_n, F.pnp, db_pose, F.f_count, prm, F.relocating, F.res, F.res_host, F.res_ext, F.seq);
+    const FinalFrame &F = b.at(blockIdx.x);
+    tick_finalize_body(F.cand_ids, F.cand_n, F.pnp, db_pose, F.f_count, prm, F.base_pose, F.relocating, F.res, F.res_host, F.res_ext, F.seq);
 }
 
 
@@ -586,7 +582,7 @@ static double heading_cos_tol_host(const reloc_ctx *ctx) { return cos(ctx->prm.h
 static TickParams make_tick_params(reloc_ctx *ctx, const double base_pose[7], int mode, int check_consistency)
 {
     TickParams p;
-    for (int k = 0; k < 7; ++k) p.base_pose[k] = base_pose[k];
+    for (int k = 0; k < 7; ++k) p.base_pose[k] = base_pose ? base_pose[k] : 0.0;      // NULL: the finalisation's, see TickParams
     for (int k = 0; k < 3; ++k) p.b2c_t[k] = ctx->cam.b2c_t[k];
     for (int k = 0; k < 9; ++k) p.b2c_R[k] = ctx->cam.b2c_R[k];
     p.mode = mode;
@@ -654,8 +650,10 @@ __global__ void k_set_candidates_batch(const int32_t *__restrict__ ids, int k, S
 }
 
 // ---- the stages of a tick for the n contexts of one call ------------------------------------------------------------------
-// Each stage is ONE launch per kernel whatever n is: the pointer-argument kernel with frame 0's buffers at n == 1, the
-// frame-table kernel (blockIdx = frame) at n > 1.  The frame builders state which buffers of a context a stage reads and writes.
+// Each stage is ONE launch per kernel whatever n is: the kernel takes a frame table (FrameTable, reloc_internal.h: one slot at
+// n == 1, RELOC_BATCH_MAX otherwise) and its last grid dimension is the frame; the ranking of one frame takes the frame's
+// members as pointer arguments (k_topk_counts).  The frame builders state which buffers of a context a stage reads and
+// writes, and everything else that is the frame's own: seed, base pose, sequence stamp.
 static TopkFrame topk_frame(const reloc_ctx *c, int32_t *out_ids, int32_t *out_counts, int32_t *out_nfeat, bool auto_mode)
 {
     TopkFrame F;
@@ -692,36 +690,32 @@ static TopkShape topk_shape(const reloc_ctx *c0)
     return TopkShape{(int)db.records, max_count, c0->prm.min_matches};
 }
 
-static void launch_topk_shape(hipStream_t stream, int n, const TopkBatch &b, const TopkShape &s, int k, int id_base)
+static void launch_topk_shape(hipStream_t stream, int n, const TopkFrames<RELOC_BATCH_MAX> &b, const TopkShape &s, int k, int id_base)
 {
     const size_t lds = (size_t)(s.max_count + 2) * sizeof(int);
-    if (n == 1) {
+    if (n == 1) {                   // pointer arguments for one frame: see k_topk_counts
         const TopkFrame &F = b.f[0];
         hipLaunchKernelGGL(k_topk_counts, dim3(1), dim3(TOPK_HIST_THREADS), lds, stream, F.counts, s.L, k, id_base, s.min_matches,
                            s.max_count, F.out_ids, F.out_counts, F.out_n, F.skip_if, F.relocating, F.f_count, F.out_nfeat);
     } else {
-        hipLaunchKernelGGL(k_topk_counts_batch, dim3(n), dim3(TOPK_HIST_THREADS), lds, stream, b, s.L, k, id_base, s.min_matches,
-                           s.max_count);
+        hipLaunchKernelGGL(k_topk_counts_batch, dim3(n), dim3(TOPK_HIST_THREADS), lds, stream, b, s.L, k, id_base, s.min_matches, s.max_count);
     }
 }
 
-static void launch_topk_counts(reloc_ctx *const *ctxs, int n, const TopkBatch &b, int k, int id_base)
+static void launch_topk_counts(reloc_ctx *const *ctxs, int n, const TopkFrames<RELOC_BATCH_MAX> &b, int k, int id_base)
 {
     launch_topk_shape(ctxs[0]->stream, n, b, topk_shape(ctxs[0]), k, id_base);
 }
 
-// gates, pose composition and the result records; prm carries what the frames share (frame 0's base pose)
-static int launch_tick_finalize(reloc_ctx *const *ctxs, int n, const FinalBatch &b, TickParams prm)
+// gates, pose composition and the result records; prm carries what the frames share
+template <int N>
+static void launch_finalize_n(reloc_ctx *c0, int n, const FinalFrames<RELOC_BATCH_MAX> &b, const TickParams &prm)
 {
-    reloc_ctx *c0 = ctxs[0];
-    if (n == 1) {
-        const FinalFrame &F = b.f[0];
-        prm.seq = F.seq;
-        hipLaunchKernelGGL(k_tick_finalize, dim3(1), dim3(64), 0, c0->stream, F.cand_ids, F.cand_n, F.pnp, ctx_db(c0).pose, F.f_count, prm,
-                           F.relocating, F.res, F.res_host, F.res_ext);
-    } else {
-        hipLaunchKernelGGL(k_tick_finalize_batch, dim3(n), dim3(64), 0, c0->stream, b, ctx_db(c0).pose, prm);
-    }
+    hipLaunchKernelGGL(k_tick_finalize<N>, dim3(n), dim3(64), 0, c0->stream, frame_table<N>(b), ctx_db(c0).pose, prm);
+}
+static int launch_tick_finalize(reloc_ctx *const *ctxs, int n, const FinalFrames<RELOC_BATCH_MAX> &b, const TickParams &prm)
+{
+    n == 1 ? launch_finalize_n<1>(ctxs[0], n, b, prm) : launch_finalize_n<RELOC_BATCH_MAX>(ctxs[0], n, b, prm);
     HIP_TRY(hipGetLastError());
     return RELOC_OK;
 }
@@ -877,11 +871,11 @@ static int solve_run(reloc_ctx *const *ctxs, int n, const int32_t *cand_dev, int
     }
     if ((rc = launch_tick_emit(ctxs, n, latency))) return rc;
     if ((rc = pnp_run_candidates(ctxs, n, seeds, latency))) return rc;
-    FinalBatch b;
+    FinalFrames<RELOC_BATCH_MAX> b;
     frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int g) {
         b.f[f] = final_frame(c, base_poses + 7 * g, res_ext_base ? res_ext_base + g : c->tick.res_ext, f < n ? tick_next_seq(c) : 0);
     });
-    return launch_tick_finalize(ctxs, n, b, make_tick_params(c0, base_poses, mode, check_consistency));
+    return launch_tick_finalize(ctxs, n, b, make_tick_params(c0, nullptr, mode, check_consistency));
 }
 
 // The tick: ORB, local candidates (LOCAL / AUTO), whole-database scan and ranking (GLOBAL / AUTO), solve half.
@@ -900,7 +894,7 @@ static int tick_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *imgs, i
         }
     if (mode != RELOC_TICK_LOCAL) {
         if ((rc = scan_counts(ctxs, n, base_poses, mode == RELOC_TICK_AUTO))) return rc;
-        TopkBatch b;
+        TopkFrames<RELOC_BATCH_MAX> b;
         frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int) { b.f[f] = topk_frame(c, c->tick.cand_ids, nullptr, nullptr, mode == RELOC_TICK_AUTO); });
         launch_topk_counts(ctxs, n, b, c0->prm.global_max_candidates, 0);
     }
@@ -909,7 +903,7 @@ static int tick_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *imgs, i
 
 // Scan half of the sharded tick: ORB, whole-database scan (heading mask when base_poses != NULL), ranking into out.
 static int scan_run(reloc_ctx *const *ctxs, int n, const uint8_t *const *imgs, int w, int h, int order, const double *base_poses,
-                    const TopkBatch &out, int k, int id_base)
+                    const TopkFrames<RELOC_BATCH_MAX> &out, int k, int id_base)
 {
     int rc;
     if ((rc = orb_run(ctxs, n, imgs, w, h, w * image_chain_frame_bpp(ctxs[0]), true, order, ctxs[0]->prm.nfeatures,
@@ -1032,7 +1026,7 @@ RELOC_API int reloc_tick_scan_dev(reloc_ctx *ctx, const uint8_t *img_dev, int w,
     ARG_CHECK_CTX(ctx, img_dev && topk_ids_dev && topk_counts_dev && k > 0 && k <= MAX_CAND && w >= 64 && h >= 64,
               "reloc_tick_scan_dev");
     if (int rc = ctx_batch_check(&ctx, 1, "reloc_tick_scan_dev")) return rc;
-    TopkBatch out;
+    TopkFrames<RELOC_BATCH_MAX> out;
     frame_slots(&ctx, 1, [&](int f, reloc_ctx *c, int) { out.f[f] = topk_frame(c, topk_ids_dev, topk_counts_dev, nullptr, false); });
     return scan_run(&ctx, 1, &img_dev, w, h, order, base_pose, out, k, 0);
 }
@@ -1062,7 +1056,7 @@ RELOC_API int reloc_shard_scan_batch_dev(reloc_ctx *const *ctxs, int n, const ui
               id_base + ctx_db(ctxs[0]).records <= 0x7fffffff, "reloc_shard_scan_batch_dev");
     for (int f = 0; f < n; ++f) ARG_CHECK(imgs_dev[f], "reloc_shard_scan_batch_dev: NULL frame");
     // frame f's list goes to row f of scan_out_dev: 2k + 2 int32 (k ids + id_base, k counts, feature count, one pad word the call never writes)
-    TopkBatch out;
+    TopkFrames<RELOC_BATCH_MAX> out;
     frame_slots(ctxs, n, [&](int f, reloc_ctx *c, int g) {
         int32_t *row = scan_out_dev + (size_t)g * (2 * k + 2);
         out.f[f] = topk_frame(c, row, row + k, row + 2 * k, false);
@@ -1219,7 +1213,7 @@ RELOC_API int reloc_debug_rank_counts(reloc_ctx *ctx, const int32_t *counts_host
     HIP_TRY(hipMemsetAsync(s.flags, 0xA5, RELOC_BATCH_MAX * sizeof(int32_t), ctx->stream));
     // skip_in given: the AUTO arrangement -- out_n holds what the local search left (0: nothing found) and is the skip_if too
     if (skip_in) HIP_TRY(hipMemcpyAsync(s.n, skip_in, (size_t)n_frames * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    TopkBatch b;
+    TopkFrames<RELOC_BATCH_MAX> b;
     for (int f = 0; f < RELOC_BATCH_MAX; ++f) {
         const int g = f < n_frames ? f : 0;
         TopkFrame &F = b.f[f];

@@ -220,8 +220,8 @@ def test_batch_refuses_contexts_with_different_distortion(eng):
 
 
 def test_batched_tick_with_distortion_equals_single_ticks():
-    """reloc_tick_batch_dev over two contexts with EQUAL distortion (k_pnp_*_batch<true>) gives each frame the record of
-    its own reloc_tick_dev (k_pnp_*<true>)"""
+    """reloc_tick_batch_dev over two contexts with EQUAL distortion (k_pnp_*<true, .., 8>) gives each frame the record of
+    its own reloc_tick_dev (k_pnp_*<true, .., 1>)"""
     from nclt_slam_project_amd import landmarks as LM
     scene = synth.WallScene(dist=D_MODERATE)
     with CH.engines(2) as rig:

@@ -8,7 +8,7 @@ reloc_tick_debug / reloc_tick_debug_matches:
   - obj bit-equal to pts3d[off[r] + qidx], img bit-equal to xy[tidx] (every row and xy encodes its own index),
   - n_matches of the PnP record, the list length and the counting scan of the same features agree,
 for k_db_scan_emit<NJ, 8> / <NJ, 4> (every NJ and column-block count, through max_feat) and k_db_scan_emit_batch; and the
-per-candidate PnP (k_pnp_finish<false, 1>, <false, 4>, the *_batch kernels) against oracle.pnp_ransac on the pairs the tap
+per-candidate PnP (k_pnp_finish<false, 1, 1>, <false, 4, 1>, the 8-slot frame-table kernels) against oracle.pnp_ransac on the pairs the tap
 hands out, with exactly test_gpu_pnp.py's assertions.  Lens distortion stays out (tests/test_gpu_distortion.py)."""
 import numpy as np
 import pytest
@@ -339,8 +339,8 @@ def test_pnp_every_candidate(oracle, variant):
 
 
 def test_pnp_batch_every_frame_every_candidate(oracle):
-    """the three *_batch PnP kernels (grid y = candidate, z = frame): two frames of one database with different image points,
-    candidate rows and seeds"""
+    """the three PnP kernels on the 8-slot frame table (k_pnp_hyp / k_pnp_score / k_pnp_finish<.., 8>; grid y = candidate,
+    z = frame): two frames of one database with different image points, candidate rows and seeds"""
     seeds = [41, 97]
     fr = _pnp_frame(seeds[0])
     # frame 1: the same features seen with every pixel moved by the same 2-D similarity about the principal point --

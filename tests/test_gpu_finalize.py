@@ -1,5 +1,5 @@
-"""GPU parity: the last stage of a tick (tick_finalize_body of csrc/reloc_tick.hip, launched as k_tick_finalize and
-k_tick_finalize_batch), slot by slot and at every heading.
+"""GPU parity: the last stage of a tick (tick_finalize_body of csrc/reloc_tick.hip, launched as k_tick_finalize<1> and
+k_tick_finalize<8>), slot by slot and at every heading.
 
 The solve half is driven directly through the C-ABI (no ORB: chosen descriptors, xy and count are copied into the context's
 feature buffers), every result is read as the raw 96-byte record, and the device and the caller-named record are filled with
@@ -10,7 +10,7 @@ test_finalize_host.py's bounds with the independent one -- the check depends nei
   (b) the inlier and reprojection gates at their boundaries, in the local and the whole-database regime
   (c) the best pick: ties, holes, slot 31 of 32, a record twice, more than 1023 inliers
   (d) the five outcomes and the consistency gate at its boundary; check_consistency = -1 through whole ticks
-  (e) k_tick_finalize_batch: per-frame tables, seeds and base poses
+  (e) k_tick_finalize<8>: per-frame tables, seeds and base poses
   (f) the three copies of the record and the sequence stamp (checked after every solve of this file)"""
 import collections
 import math
@@ -493,7 +493,7 @@ def _close_batch(es):
 
 @pytest.mark.parametrize("n", [2, 3, 8])
 def test_shard_solve_batch_every_frame(n):
-    """k_tick_finalize_batch through reloc_shard_solve_batch_dev: every frame with its own features (PnP pose, count), candidate
+    """k_tick_finalize<8> through reloc_shard_solve_batch_dev: every frame with its own features (PnP pose, count), candidate
     row, seed and base pose; frame f's record in res_out against the reference on engine f's tick_debug (whole-database gates,
     no consistency check -- that call has no local regime; the per-frame base pose is pinned through reloc_tick_batch_dev below)"""
     db = _small_db()
@@ -543,7 +543,7 @@ def test_shard_solve_batch_every_frame(n):
 @pytest.mark.parametrize("mode,layout", [(LOCAL, "near off"), (LOCAL, "off near"), (LOCAL, "off near off"), (AUTO, "far off near"),
                                          (GLOBAL, "off near")])
 def test_tick_batch_per_frame_base_pose(mode, layout):
-    """k_tick_finalize_batch through reloc_tick_batch_dev (ORB path): the frames see the same image from base poses of which
+    """k_tick_finalize<8> through reloc_tick_batch_dev (ORB path): the frames see the same image from base poses of which
     some lie within consistency_m of the anchor and some beyond, so the same anchor publishes for some frames and fails the
     consistency gate for others -- frame 0's decision differs from a later frame's.  Every frame against the reference on
     its engine's tick_debug."""

@@ -1,0 +1,168 @@
+"""GPU: the ORB, PnP and tick kernels take one frame table for any number of frames (FrameTable in csrc/reloc_internal.h: a
+1-slot table for one frame, an 8-slot table for 2..8; k_pyramid and k_topk_counts take pointer arguments for one frame).
+What must hold of that: a batch of one is the single tick, every frame
+of a batch of two or of eight gets the record and the features of its own single tick -- each frame with its own pixels, base
+pose and seed, so a table index stuck at 0 or a per-frame value taken from frame 0 shows -- and the stand-alone entry points
+that build a one-frame table themselves (pnp_score with its mask, debug_rank_counts) still compute the reference's answer.
+
+The frames are the four teach frames of the wall route (tests/golden/tick_scene.json, teach_x), the database their four
+records.  Every comparison between ticks is byte for byte on the 96-byte device record and on the features."""
+import json
+import os
+
+import numpy as np
+import pytest
+
+import candidates_ref as R
+import chain_harness as CH
+import orb_mask_ref as MR
+import pnp_ref as PR
+from nclt_slam_project_amd import landmarks as LM, synth
+from nclt_slam_project_amd.engine import DEBUG_POISON, MAX_CAND, TICK_RESULT, Engine
+
+pytestmark = pytest.mark.gpu
+GOLD = os.path.join(os.path.dirname(__file__), "golden", "tick_scene.json")
+D_MODERATE = (-0.12, 0.03, 5e-4, -3e-4, 0.0)
+W, H = 640, 480
+MODES = (False, True)               # local tick, whole-database tick
+BATCH_MAX = 8
+
+
+class World:
+    """n engines on one stream and one database: the wall route taught under `dist`; frames[i] = teach frame i on the device"""
+
+    def __init__(self, rig, dist):
+        from nclt_slam_project_amd.recorder import LandmarkRecorderCore
+        self.rig, self.es = rig, rig.es
+        self.xs = json.load(open(GOLD))["teach_x"]
+        scene = synth.WallScene(dist=dist)
+        shots = {x: scene.render(synth.base_pose(x, 0.0, 0.0)) for x in self.xs}
+        rec = CH.teach_wall(LandmarkRecorderCore(engine=self.es[0], dist=dist or ()), self.xs, lambda bp: shots[bp[0]])
+        assert len(rec.landmarks) == len(self.xs)
+        self.es[0].db_upload(*LM.pack_landmarks(rec.database()["landmarks"]))
+        rig.share()
+        for e in self.es:
+            e.set_distortion(dist or ())
+        self.frames = [rig.to_device(shots[x][0]) for x in self.xs]
+
+    def slot(self, f):
+        """frame, base pose and seed of slot f: pairwise different poses and seeds, frame f mod 4.  An odd slot's base pose
+        lies more than consistency_m (5 m) beside the route and within the candidate radius (8 m): its local tick fails the
+        consistency check, an even slot's publishes -- unless a slot is finalised with another slot's pose."""
+        i = f % len(self.xs)
+        y = 5.5 + 0.1 * f if f % 2 else 0.02 * f - 0.05
+        return self.frames[i], synth.base_pose(self.xs[i] + 0.05 * f, y, 0.4 * f - 1.0), 11 + 3 * f
+
+    def single(self, f, mode, seed=None):
+        """slot f ticked alone (seed: instead of the slot's): (device record, features)"""
+        e = self.es[0]
+        img, bp, own = self.slot(f)
+        seed = own if seed is None else seed
+        e.tick_dev(img, W, H, bp, global_reloc=mode, seed=seed)
+        return CH.device_record(e), e.orb_features()
+
+    def batch(self, slots, mode):
+        """the slots as one batch over the first len(slots) engines: [(device record, features)]"""
+        es = self.es[:len(slots)]
+        imgs, bps, seeds = zip(*[self.slot(f) for f in slots])
+        Engine.tick_batch_dev(es, imgs, W, H, bps, global_reloc=mode, seeds=list(seeds))
+        return [(CH.device_record(e), e.orb_features()) for e in es]
+
+
+@pytest.fixture(scope="module")
+def pin():
+    with CH.engines(BATCH_MAX) as rig:
+        yield World(rig, None)
+
+
+@pytest.fixture(scope="module")
+def lens():
+    with CH.engines(1) as rig:
+        yield World(rig, D_MODERATE)
+
+
+def _same(got, exp, what):
+    assert got[0].tobytes() == exp[0].tobytes(), what
+    CH.assert_same_features(got[1], exp[1], 100)
+
+
+def _differ(a, b):
+    return a[0].tobytes() != b[0].tobytes() and (a[1]["n"] != b[1]["n"] or not np.array_equal(a[1]["desc"], b[1]["desc"]))
+
+
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("world", ["pin", "lens"])
+def test_batch_of_one_is_the_single_tick(world, masked, request):
+    """Engine.tick_batch_dev([e], ...) against tick_dev on the same frame, pose and seed: local and whole-database ticks,
+    pinhole and distorted camera, with and without a detection mask.  A tick of another frame runs in between, so the batch
+    has something to overwrite.  The whole-database tick also runs under set_exclusive (the kernels sized for latency)."""
+    w = request.getfixturevalue(world)
+    e = w.es[0]
+    try:
+        e.set_orb_mask(MR.half_band(W, H) if masked else None)
+        for mode in MODES:
+            for excl in ((False, True) if mode else (False,)):
+                e.set_exclusive(excl)
+                exp = w.single(1, mode)
+                other = w.single(2, mode)
+                assert _differ(exp, other)
+                got, = w.batch([1], mode)
+                r = exp[0].view(TICK_RESULT)[0]
+                print(f"{world} masked {masked} mode {mode} exclusive {excl}: outcome {r['outcome']} inliers {r['n_inliers']} "
+                      f"candidates {r['n_candidates']} features {r['n_features']}")
+                _same(got, exp, (world, masked, mode, excl))
+                assert r["n_features"] > 100 and r["n_candidates"] >= 1         # the whole chain ran
+    finally:
+        e.set_exclusive(False)
+        e.set_orb_mask(None)
+
+
+@pytest.mark.parametrize("n", [2, BATCH_MAX])
+def test_every_frame_of_a_batch_is_its_own_single_tick(pin, n):
+    """n = 2 and n = 8 frames, pairwise different base poses and seeds, frames of different pixels: slot f's record and
+    features are those of slot f ticked alone.  The batch is run twice, the first time with the slots in reverse order, so
+    that no engine holds its expected answer beforehand; the last slot differs from slot 0."""
+    slots = list(range(n))
+    for mode in MODES:
+        exp = [pin.single(f, mode) for f in slots]
+        assert _differ(exp[0], exp[n - 1])
+        outcomes = [int(x[0].view(TICK_RESULT)[0]["outcome"]) for x in exp]
+        print(f"n {n} mode {mode}: outcomes {outcomes}")
+        if mode:        # the seed reaches the record (frame n - 1 with slot 0's seed: another record) ...
+            assert pin.single(n - 1, mode, seed=pin.slot(0)[2])[0].tobytes() != exp[n - 1][0].tobytes()
+            assert 0 in outcomes                                # ... of a frame that went through PnP and published
+        else:           # ... and so does the base pose: see World.slot
+            assert outcomes == [4 if f % 2 else 0 for f in slots]
+        rev = pin.batch(slots[::-1], mode)
+        for f in slots:
+            _same(rev[n - 1 - f], exp[f], ("reversed", mode, f))
+        got = pin.batch(slots, mode)
+        for f in slots:
+            _same(got[f], exp[f], (mode, f))
+
+
+@pytest.mark.parametrize("m", [4, 100])
+def test_pnp_score_counts_and_mask(pin, m):
+    """pnp_score builds a one-frame table on its scratch slots, the mask slot included: counts and per-point flags against
+    the float64 projection of tests/pnp_ref.py, at one wave's worth of points and at two"""
+    rng = np.random.default_rng(40 + m)
+    obj, img, rvec, tvec, _ = synth.pnp_problem(rng, m=m, outlier_ratio=0.0 if m == 4 else 0.3, noise_px=0.3)
+    Rt = np.array([np.concatenate([synth.rodrigues(rvec + rng.normal(0, 0.004 * (h % 4), 3)).ravel(), tvec + rng.normal(0, 0.004 * (h % 3), 3)])
+                   for h in range(9)])
+    e2 = np.stack([PR.err2(r, obj, img, PR.K4_DEFAULT) for r in Rt])
+    assert np.abs(e2 - 9.0).min() > 1e-6                        # no point decides on the last bits
+    cnt, mask = pin.es[0].pnp_score(obj, img, Rt, want_mask=True)
+    np.testing.assert_array_equal(mask, (e2 <= 9.0).astype(np.uint8))
+    np.testing.assert_array_equal(cnt, (e2 <= 9.0).sum(1))
+    assert cnt[0] >= m // 2 and len(set(cnt.tolist())) > (1 if m > 4 else 0)
+    np.testing.assert_array_equal(pin.es[0].pnp_score(obj, img, Rt), cnt)      # without the mask: the same counts
+
+
+def test_rank_counts_of_one_frame(pin):
+    """debug_rank_counts on a three-record count vector at k = 1: the best (count, id), nothing else written"""
+    for counts in ([12, 40, 40], [9, 3, 0], [10, 11, 4]):
+        exp = R.rank_counts(counts, 10, 1)
+        ids, cnt, n = pin.es[0].debug_rank_counts(np.array(counts, np.int32), 1, id_base=5, min_matches=10, max_count=64)
+        assert n.tolist() == [len(exp)]
+        assert ids[0, 0] == (exp[0][1] + 5 if exp else -1) and cnt[0, 0] == (exp[0][0] if exp else 0)
+        assert (ids[0, 1:] == DEBUG_POISON).all() and (cnt[0, 1:] == DEBUG_POISON).all() and ids.shape == (1, MAX_CAND)
