@@ -137,6 +137,10 @@ const int32_t *reloc_frame_count_dev(reloc_ctx *ctx);     /* 1 x i32: number of 
 /* Debug/parity taps: copy intermediate planes of the last frame to host.  level in [0, 8).
  * what: 0 = pyramid level, 1 = blurred level, 2 = NMS-kept FAST score map. */
 int reloc_frame_debug_plane(reloc_ctx *ctx, int what, int level, uint8_t *out, int32_t *w, int32_t *h);
+/* The stage record of the last frame, 8 x i32 each: the stage-1 cut score of every level (-1 where the level's NMS map is
+ * empty, so that no cut was computed), the length of its stage-1 candidate list and the number of keypoints kept of it.
+ * Read only; synchronises the stream. */
+int reloc_orb_debug_levels(reloc_ctx *ctx, int32_t *cut, int32_t *cand_cnt, int32_t *kp_cnt);
 
 /* ---- ORB detection mask (include/reloc_spec.h, "ORB MASK") ---------------------------------------- */
 /* cv2.ORB.detectAndCompute(image, mask): mask is a host plane of h rows of w bytes, stride bytes apart; a corner is kept

@@ -70,6 +70,7 @@ SIGNATURES = {
     "reloc_frame_xy_dev": (C.c_void_p, [c_ctx]),
     "reloc_frame_count_dev": (C.c_void_p, [c_ctx]),
     "reloc_frame_debug_plane": (C.c_int, [c_ctx, C.c_int, C.c_int, P, P, P]),
+    "reloc_orb_debug_levels": (C.c_int, [c_ctx, P, P, P]),
     "reloc_set_orb_mask": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int]),
     "reloc_get_orb_mask": (C.c_int, [c_ctx, P, P]),
     "reloc_orb_detect_compute_masked": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, P, C.c_int, C.c_int, P, P, P, P, P, P, P]),

@@ -1405,3 +1405,26 @@ RELOC_API int reloc_frame_debug_plane(reloc_ctx *ctx, int what, int level, uint8
     *h = L.h;
     return RELOC_OK;
 }
+
+// The stage record of the last frame, read only: nothing in a frame's launches exists for it.  dbg_cut keeps the cut of an
+// earlier frame where no block of this one reached the cut computation, which is the case exactly when the level's
+// histogram sums to 0 (no NMS survivor in any chunk): those levels report -1.
+RELOC_API int reloc_orb_debug_levels(reloc_ctx *ctx, int32_t *cut, int32_t *cand_cnt, int32_t *kp_cnt)
+{
+    ARG_CHECK_CTX(ctx, cut && cand_cnt && kp_cnt, "reloc_orb_debug_levels");
+    if (!ctx->orb.w) { reloc_set_error("no frame processed yet"); return RELOC_E_STATE; }
+    const OrbFrame &b = ctx->orb.buf;
+    std::vector<int32_t> hist(NLEV * 256);
+    const hipError_t e0 = hipMemcpyAsync(hist.data(), b.hist, sizeof(int32_t) * hist.size(), hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t e1 = hipMemcpyAsync(cut, b.dbg_cut, sizeof(int32_t) * NLEV, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t e2 = hipMemcpyAsync(cand_cnt, b.cand_cnt, sizeof(int32_t) * NLEV, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t e3 = hipMemcpyAsync(kp_cnt, b.kp_cnt, sizeof(int32_t) * NLEV, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t e4 = hipStreamSynchronize(ctx->stream);      // the histogram copy leaves with this function
+    HIP_TRY(e0); HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4);
+    for (int l = 0; l < NLEV; ++l) {
+        int64_t sum = 0;
+        for (int s = 0; s < 256; ++s) sum += hist[l * 256 + s];
+        if (sum == 0) cut[l] = -1;
+    }
+    return RELOC_OK;
+}

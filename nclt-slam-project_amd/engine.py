@@ -721,6 +721,13 @@ class Engine:
         self._api.reloc_frame_debug_plane(self._ctx, what, level, buf, w, h)
         return buf[: w.value * h.value].reshape(h.value, w.value).copy()
 
+    def orb_debug_levels(self):
+        """the stage record of the last frame, (8,) int32 each: `cut` (the stage-1 cut score; -1 where the level's NMS map
+        is empty), `cand_cnt` (stage-1 candidates), `kp_cnt` (keypoints kept).  Read only; synchronises the stream"""
+        cut, cand, kp = (np.zeros(8, np.int32) for _ in range(3))
+        self._api.reloc_orb_debug_levels(self._ctx, cut, cand, kp)
+        return dict(cut=cut, cand_cnt=cand, kp_cnt=kp)
+
     # ------------------------------------------------------------------ matching
     @staticmethod
     def _desc(a, name):

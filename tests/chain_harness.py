@@ -1,18 +1,22 @@
 """What the GPU suites of the image chain share (lens distortion, CLAHE, rectification, resize, Bayer, the detection mask):
-engines and device buffers released in one order, the small readers, the wall-route teach loop, and the five scenarios every
+engines and device buffers released in one order, the small readers, the wall-route teach loop and the World of the batch
+tests (engines on one stream over the taught wall route), and the five scenarios every
 stage owes -- off is off, the two sessions agree, a batch equals single ticks, recording equals the cv2 path, accumulated
 records are equal.  A scenario is parameterised by what varies between stages: how the setting is switched, how it is read
 back, how a frame is made.  Imported like clahe_ref; Engine is imported inside functions, so CPU-only tests can import it."""
 import contextlib
+import json
+import os
 
 import numpy as np
 import pytest
 
-from nclt_slam_project_amd import RelocError, synth
+from nclt_slam_project_amd import RelocError, landmarks as LM, synth
 from nclt_slam_project_amd.engine import TICK_RESULT
 
 RESULT_KEYS = ("outcome", "n_inliers", "lm_idx", "n_candidates", "relocating", "n_features")
 RECORD_KEYS = ("descriptors", "keypoints_2d", "keypoints_3d_cam")
+TICK_SCENE = os.path.join(os.path.dirname(__file__), "golden", "tick_scene.json")
 
 
 # ---- resources ------------------------------------------------------------------------------------------------------
@@ -102,6 +106,58 @@ def teach_wall(recorder, xs, render):
         bgr, dep = render(bp)
         recorder.tick(bgr, dep, bp, rgb_ts=x)
     return recorder
+
+
+class World:
+    """n engines on one stream and one database: the wall route (tests/golden/tick_scene.json, teach_x) taught under `dist`;
+    frames[i] = teach frame i on the device.  The batch harness of tests/test_gpu_frame_table.py and test_gpu_orb_dense.py"""
+    W, H = 640, 480
+
+    def __init__(self, rig, dist):
+        from nclt_slam_project_amd.recorder import LandmarkRecorderCore
+        self.rig, self.es = rig, rig.es
+        self.xs = json.load(open(TICK_SCENE))["teach_x"]
+        scene = synth.WallScene(dist=dist)
+        shots = {x: scene.render(synth.base_pose(x, 0.0, 0.0)) for x in self.xs}
+        rec = teach_wall(LandmarkRecorderCore(engine=self.es[0], dist=dist or ()), self.xs, lambda bp: shots[bp[0]])
+        assert len(rec.landmarks) == len(self.xs)
+        self.es[0].db_upload(*LM.pack_landmarks(rec.database()["landmarks"]))
+        rig.share()
+        for e in self.es:
+            e.set_distortion(dist or ())
+        self.frames = [rig.to_device(shots[x][0]) for x in self.xs]
+
+    def slot(self, f):
+        """frame, base pose and seed of slot f: pairwise different poses and seeds, frame f mod 4.  An odd slot's base pose
+        lies more than consistency_m (5 m) beside the route and within the candidate radius (8 m): its local tick fails the
+        consistency check, an even slot's publishes -- unless a slot is finalised with another slot's pose."""
+        i = f % len(self.xs)
+        y = 5.5 + 0.1 * f if f % 2 else 0.02 * f - 0.05
+        return self.frames[i], synth.base_pose(self.xs[i] + 0.05 * f, y, 0.4 * f - 1.0), 11 + 3 * f
+
+    def tick_alone(self, item, mode, e=None):
+        """(frame on the device, base pose, seed) ticked alone on the first engine (or e): (device record, features)"""
+        e = e or self.es[0]
+        img, bp, seed = item
+        e.tick_dev(img, self.W, self.H, bp, global_reloc=mode, seed=seed)
+        return device_record(e), e.orb_features()
+
+    def tick_batch(self, items, mode):
+        """the items as one batch over the first len(items) engines: [(device record, features)]"""
+        from nclt_slam_project_amd.engine import Engine
+        es = self.es[:len(items)]
+        imgs, bps, seeds = zip(*items)
+        Engine.tick_batch_dev(es, imgs, self.W, self.H, bps, global_reloc=mode, seeds=list(seeds))
+        return [(device_record(e), e.orb_features()) for e in es]
+
+    def single(self, f, mode, seed=None):
+        """slot f ticked alone (seed: instead of the slot's): (device record, features)"""
+        img, bp, own = self.slot(f)
+        return self.tick_alone((img, bp, own if seed is None else seed), mode)
+
+    def batch(self, slots, mode):
+        """the slots as one batch over the first len(slots) engines: [(device record, features)]"""
+        return self.tick_batch([self.slot(f) for f in slots], mode)
 
 
 # ---- scenarios ------------------------------------------------------------------------------------------------------

@@ -7,9 +7,6 @@ that build a one-frame table themselves (pnp_score with its mask, debug_rank_cou
 
 The frames are the four teach frames of the wall route (tests/golden/tick_scene.json, teach_x), the database their four
 records.  Every comparison between ticks is byte for byte on the 96-byte device record and on the features."""
-import json
-import os
-
 import numpy as np
 import pytest
 
@@ -17,68 +14,26 @@ import candidates_ref as R
 import chain_harness as CH
 import orb_mask_ref as MR
 import pnp_ref as PR
-from nclt_slam_project_amd import landmarks as LM, synth
-from nclt_slam_project_amd.engine import DEBUG_POISON, MAX_CAND, TICK_RESULT, Engine
+from nclt_slam_project_amd import synth
+from nclt_slam_project_amd.engine import DEBUG_POISON, MAX_CAND, TICK_RESULT
 
 pytestmark = pytest.mark.gpu
-GOLD = os.path.join(os.path.dirname(__file__), "golden", "tick_scene.json")
 D_MODERATE = (-0.12, 0.03, 5e-4, -3e-4, 0.0)
-W, H = 640, 480
+W, H = CH.World.W, CH.World.H
 MODES = (False, True)               # local tick, whole-database tick
 BATCH_MAX = 8
-
-
-class World:
-    """n engines on one stream and one database: the wall route taught under `dist`; frames[i] = teach frame i on the device"""
-
-    def __init__(self, rig, dist):
-        from nclt_slam_project_amd.recorder import LandmarkRecorderCore
-        self.rig, self.es = rig, rig.es
-        self.xs = json.load(open(GOLD))["teach_x"]
-        scene = synth.WallScene(dist=dist)
-        shots = {x: scene.render(synth.base_pose(x, 0.0, 0.0)) for x in self.xs}
-        rec = CH.teach_wall(LandmarkRecorderCore(engine=self.es[0], dist=dist or ()), self.xs, lambda bp: shots[bp[0]])
-        assert len(rec.landmarks) == len(self.xs)
-        self.es[0].db_upload(*LM.pack_landmarks(rec.database()["landmarks"]))
-        rig.share()
-        for e in self.es:
-            e.set_distortion(dist or ())
-        self.frames = [rig.to_device(shots[x][0]) for x in self.xs]
-
-    def slot(self, f):
-        """frame, base pose and seed of slot f: pairwise different poses and seeds, frame f mod 4.  An odd slot's base pose
-        lies more than consistency_m (5 m) beside the route and within the candidate radius (8 m): its local tick fails the
-        consistency check, an even slot's publishes -- unless a slot is finalised with another slot's pose."""
-        i = f % len(self.xs)
-        y = 5.5 + 0.1 * f if f % 2 else 0.02 * f - 0.05
-        return self.frames[i], synth.base_pose(self.xs[i] + 0.05 * f, y, 0.4 * f - 1.0), 11 + 3 * f
-
-    def single(self, f, mode, seed=None):
-        """slot f ticked alone (seed: instead of the slot's): (device record, features)"""
-        e = self.es[0]
-        img, bp, own = self.slot(f)
-        seed = own if seed is None else seed
-        e.tick_dev(img, W, H, bp, global_reloc=mode, seed=seed)
-        return CH.device_record(e), e.orb_features()
-
-    def batch(self, slots, mode):
-        """the slots as one batch over the first len(slots) engines: [(device record, features)]"""
-        es = self.es[:len(slots)]
-        imgs, bps, seeds = zip(*[self.slot(f) for f in slots])
-        Engine.tick_batch_dev(es, imgs, W, H, bps, global_reloc=mode, seeds=list(seeds))
-        return [(CH.device_record(e), e.orb_features()) for e in es]
 
 
 @pytest.fixture(scope="module")
 def pin():
     with CH.engines(BATCH_MAX) as rig:
-        yield World(rig, None)
+        yield CH.World(rig, None)
 
 
 @pytest.fixture(scope="module")
 def lens():
     with CH.engines(1) as rig:
-        yield World(rig, D_MODERATE)
+        yield CH.World(rig, D_MODERATE)
 
 
 def _same(got, exp, what):
