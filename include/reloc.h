@@ -109,7 +109,9 @@ int  reloc_timer_end(reloc_ctx *ctx, float *ms);
 #define RELOC_PROF_PNP      3
 #define RELOC_PROF_STEREO   4   /* k_stereo_depth (reloc_stereo_depth and the stereo recording / accumulation) */
 #define RELOC_PROF_STEREO_DENSE 5 /* k_stereo_dense + k_stereo_dense_finish with the right map's reset (the dense stereo entry points) */
-#define RELOC_PROF_N        6
+#define RELOC_PROF_N        6   /* the slots above */
+#define RELOC_PROF_STEREO_SGM 6 /* the semi-global dense pass: both resets, volume, paths, selection, finish (and the speckle stage) */
+#define RELOC_PROF_COUNT    7   /* every slot: reloc_profile_get takes 0 <= which < RELOC_PROF_COUNT */
 int  reloc_profile_enable(reloc_ctx *ctx, int on);
 int  reloc_profile_get(reloc_ctx *ctx, int which, float *total_ms, int32_t *launches);
 
@@ -498,6 +500,27 @@ int reloc_stereo_frame_points(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *i
  * max_w x max_h, or of the pass's size; any pointer may be NULL).  RELOC_E_STATE before the first pass.  Synchronises the
  * context's stream. */
 int reloc_stereo_dense_debug(reloc_ctx *ctx, uint16_t *depth_mm, float *disparity, uint8_t *status, int32_t *w, int32_t *h);
+
+/* ---- semi-global aggregation (include/reloc_spec.h, "STEREO, semi-global") ------------------------- */
+/* The dense pass with the SAD costs aggregated along 4 or 8 directions before the selection; this project's own matcher, not
+ * OpenCV's StereoSGBM.  A persistent setting of the LEFT context: paths 0 = off (a new context; p1, p2 are then ignored and
+ * return to their defaults), 4 (mask 0x0F) or 8 (mask 0xFF); 0 <= p1 <= p2 <= RELOC_STEREO_SGM_P2_MAX.  Independent of
+ * reloc_set_stereo and of reloc_set_stereo_speckle.  It applies to every dense pass that runs with the context's settings
+ * (reloc_stereo_frame_depth, reloc_stereo_frame_points, and so to what reloc_occ_integrate_stereo_dev,
+ * reloc_corr_match_stereo_dev, reloc_obs_*_stereo_dev and reloc_stereo_dense_debug read).  Bad values return RELOC_E_ARG and
+ * change nothing.  The volumes (6 bytes per pixel and disparity) are taken at the first semi-global pass and sized from it;
+ * RELOC_E_CAPACITY when the device has no room for them, the context stays usable. */
+int reloc_set_stereo_sgm(reloc_ctx *ctx, int paths, int p1, int p2);
+int reloc_get_stereo_sgm(reloc_ctx *ctx, int32_t *paths, int32_t *p1, int32_t *p2);
+/* The explicit twin of reloc_stereo_depth_image, with the same checks: path_mask in 1..255 (bit b selects direction b of the
+ * specification), the penalties as above.  Never speckle-filtered.  Host pointers; synchronous. */
+int reloc_stereo_sgm_image(reloc_ctx *ctx, const uint8_t *left, const uint8_t *right, int w, int h, int stride, double fx,
+                           double baseline_m, int min_disparity, int num_disparities, int uniqueness, int lr_check,
+                           int path_mask, int p1, int p2, uint16_t *depth_mm, float *disparity, uint8_t *status);
+/* Parity tap: the sum volume S of the context's last semi-global pass as [v][u][k], k = d - min_disparity, *w * *h * *nd
+ * values, 0xFFFFFFFF at undefined entries.  S may be NULL (the sizes only).  RELOC_E_STATE before the first such pass.  With
+ * reloc_stereo_sgm_image and a single-bit mask it is the per-direction tap. */
+int reloc_stereo_sgm_debug(reloc_ctx *ctx, uint32_t *S, int32_t *w, int32_t *h, int32_t *nd);
 
 /* ---- speckle filter (include/reloc_spec.h, "STEREO, speckle") -------------------------------------- */
 /* OpenCV's filterSpeckles on an int16 plane of w x h, rows stride ELEMENTS apart, in place: every pixel of a 4-connected

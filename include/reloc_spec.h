@@ -371,7 +371,31 @@
  *              such q is positive), q = -16 elsewhere -- status 6 included.
  *   stage      the filter with newVal = -16, maxSpeckleSize = speckle_window, maxDiff = 16 * speckle_range.  A pixel of
  *              status 0 that it removes gets status 7, depth_mm 0 and disparity 0; no other pixel changes.
- * tests/speckle_ref.py restates filter and stage. */
+ * tests/speckle_ref.py restates filter and stage.
+ *
+ * STEREO, semi-global: an optional aggregation between the cost volume and the selection of the dense pass.  This is the
+ * recurrence of semi-global matching over this project's SAD costs, not OpenCV's StereoSGBM (no Birchfield-Tomasi cost, no
+ * 5-direction mode, no disparity scaling).
+ *   volume     C(v, u, d) of "STEREO, dense", defined for R <= v < h - R, R <= u < w - R and d in D(u) = { min_disparity <= d <
+ *              min_disparity + num_disparities, u - d - R >= 0 }.  A pixel is in the domain when it lies in those row and
+ *              column bounds and D(u) is not empty.
+ *   settings   path_mask in 1..255, bit b selects direction r_b = (du, dv): 0 (+1, 0), 1 (-1, 0), 2 (0, +1), 3 (0, -1),
+ *              4 (+1, +1), 5 (-1, -1), 6 (+1, -1), 7 (-1, +1); paths = 4 is mask 0x0F, paths = 8 mask 0xFF.
+ *              0 <= P1 <= P2 <= RELOC_STEREO_SGM_P2_MAX; the defaults are 8 and 32 times the 121 pixels of the window.
+ *   path cost  for a selected direction r, a domain pixel p = (u, v), its predecessor q = p - r and d in D(p):
+ *              L_r(p, d) = C(p, d) when q is not in the domain; else, with m = min over k in D(q) of L_r(q, k),
+ *              L_r(p, d) = C(p, d) + min( L_r(q, d), L_r(q, d - 1) + P1, L_r(q, d + 1) + P1, m + P2 ) - m,
+ *              a term whose disparity is not in D(q) left out (m + P2 always exists).  C <= 30855 and L_r <= C + P2 < 2^16.
+ *   sum        S(p, d) = sum of L_r(p, d) over the selected directions, below 2^19.
+ *   selection  steps 2 and 4 to 8 of "STEREO" with S in place of C: d* = argmin S, lowest d on ties; the edge gate; the
+ *              uniqueness gate on S; the left-right gate with dR(v, xr) = argmin over d' of S(v, xr + d', d'), lowest d' on
+ *              ties, over the defined entries of that diagonal; the parabola through S(d* - 1), S(d*), S(d* + 1) (integers
+ *              below 2^22, exact in float32); the depth.  The same eight status codes and three planes; the speckle stage
+ *              behind it is unchanged.
+ *   identity   with P1 = P2 = 0 every L_r equals C, so S = n C for n selected directions: the argmin, both gates (a common
+ *              factor on both sides) and the parabola's quotient (numerator and denominator scaled alike, and the division
+ *              is correctly rounded) are those of C, and every plane equals the dense pass bit for bit, for every mask.
+ * tests/stereo_sgm_ref.py restates it. */
 #define RELOC_STEREO_R                 5
 #define RELOC_STEREO_MIN_DISPARITY_MAX 1024
 #define RELOC_STEREO_NUM_DISP_MIN      8
@@ -388,6 +412,9 @@
 #define RELOC_STEREO_FAR         6
 #define RELOC_STEREO_SPECKLE     7
 #define RELOC_STEREO_SPECKLE_RANGE_MAX 255
+#define RELOC_STEREO_SGM_P1_DEFAULT    968      /* 8 * 121 */
+#define RELOC_STEREO_SGM_P2_DEFAULT    3872     /* 32 * 121 */
+#define RELOC_STEREO_SGM_P2_MAX        8191
 
 /* OCCUPANCY: the teach-time occupancy map of the reference's teach_run_depth_mapper.py (D below): a 2-D log-odds grid that
  * the obstacle cloud of a frame is ray-traced into, written as .pgm + .yaml for the repeat run's static costmap layer.

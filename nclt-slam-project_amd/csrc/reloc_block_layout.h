@@ -52,3 +52,13 @@ void stereo_dense_lines(BlockCarver &c, D &d, int64_t px)
     c(d.status, px);
     c(d.left, px);
 }
+
+// Semi-global stereo (StereoState::Sgm): the cost volume and the sum volume of `entries` = w * h * num_disparities values, the
+// best plane of px pixels
+template <typename G>
+void stereo_sgm_lines(BlockCarver &c, G &g, int64_t entries, int64_t px)
+{
+    c.own(g.sum, entries);
+    c.own(g.vol, entries);
+    c.own(g.best, px);
+}

@@ -109,7 +109,7 @@ RELOC_API void reloc_destroy(reloc_ctx *c)
     tick_release(c);
     stereo_release(c);
     obs_release(c);
-    for (int k = 0; k < RELOC_PROF_N; ++k)
+    for (int k = 0; k < RELOC_PROF_COUNT; ++k)
         if (c->prof[k].init)
             for (int i = 0; i < RELOC_PROF_RING; ++i) {
                 (void)hipEventDestroy(c->prof[k].a[i]);
@@ -326,7 +326,7 @@ void reloc_prof_end(reloc_ctx *c, int which)
 RELOC_API int reloc_profile_enable(reloc_ctx *c, int on)
 {
     ARG_CHECK_CTX(c, true, "ctx is NULL");
-    for (int k = 0; k < RELOC_PROF_N; ++k) {
+    for (int k = 0; k < RELOC_PROF_COUNT; ++k) {
         prof_flush(c, k);
         c->prof[k].total = 0.f;
         c->prof[k].launches = 0;
@@ -337,7 +337,7 @@ RELOC_API int reloc_profile_enable(reloc_ctx *c, int on)
 
 RELOC_API int reloc_profile_get(reloc_ctx *c, int which, float *total_ms, int32_t *launches)
 {
-    ARG_CHECK_CTX(c, which >= 0 && which < RELOC_PROF_N && total_ms && launches, "reloc_profile_get");
+    ARG_CHECK_CTX(c, which >= 0 && which < RELOC_PROF_COUNT && total_ms && launches, "reloc_profile_get");
     prof_flush(c, which);
     *total_ms = c->prof[which].total;
     *launches = c->prof[which].launches;

@@ -441,6 +441,18 @@ struct StereoState {
     // The speckle stage behind the dense pass ("STEREO, speckle"; reloc_set_stereo_speckle, a setting of its own): window 0 = off,
     // the default.  It labels in the dense block's best plane, which k_stereo_dense_finish has read by then: no memory of its own.
     int speckle_window = 0, speckle_range = 1;
+    // Semi-global aggregation in the dense pass ("STEREO, semi-global"; reloc_set_stereo_sgm, a setting of its own): paths 0 = off,
+    // the default, else 4 or 8.  The volumes are taken at the first semi-global pass of the context and sized from that pass
+    // (stereo_sgm_alloc); they grow when a later pass needs more.  A context that never turns it on has none of it.
+    int sgm_paths = 0, sgm_p1 = RELOC_STEREO_SGM_P1_DEFAULT, sgm_p2 = RELOC_STEREO_SGM_P2_DEFAULT;
+    struct Sgm {
+        DevBlock block;                  // the pointers below lie in it (stereo_sgm_lines)
+        uint16_t *vol = nullptr;         // C as [v][u][k], k = d - min_disparity; 0xFFFF outside D(u)
+        uint32_t *sum = nullptr;         // S, the same layout
+        uint4 *best = nullptr;           // per pixel d*, S(d*), S(d* - 1), S(d* + 1): k_sgm_select to k_stereo_dense_finish
+        int64_t cap_entries = 0, cap_px = 0;      // what vol / sum and best hold
+        int w = 0, h = 0, nd = 0, dmin = 0;       // the last semi-global pass (reloc_stereo_sgm_debug); w 0 = none yet
+    } sgm;
     bool on() const { return baseline > 0.0; }
 };
 
@@ -588,7 +600,7 @@ struct reloc_ctx {
     int prof_on = 0;
     // ring of event pairs per stopwatch: large enough that a measurement of a few hundred launches never has to wait for
     // the device in the middle (prof_flush synchronises)
-    struct ProfSlot { hipEvent_t a[RELOC_PROF_RING], b[RELOC_PROF_RING]; int n = 0; float total = 0.f; int launches = 0; bool init = false; } prof[RELOC_PROF_N];
+    struct ProfSlot { hipEvent_t a[RELOC_PROF_RING], b[RELOC_PROF_RING]; int n = 0; float total = 0.f; int launches = 0; bool init = false; } prof[RELOC_PROF_COUNT];
 
     DevBlock scratch[8];           // generic scratch, grown on demand by the host-pointer entry points (HostStaging)
 
@@ -797,7 +809,8 @@ static inline int need_map(bool on, const char *who, const char *what, const cha
 void corr_pack_plane(HostStaging &st, const void *plane, bool from_units, uint32_t *bits, int w, int h, int mp);
 // Dense stereo depth: both eyes' frames (ctx->frame_img, right->frame_img, w x h as handed in) through the gray half of their
 // chains, each on its own stream, no ORB; then k_stereo_dense and k_stereo_dense_finish on ctx's stream into ctx->stereo.dense
-// (mm: dense rows of *ww uint16).  Checks stereo on, right != ctx, capacity and the chains' agreement.
+// (mm: dense rows of *ww uint16); with reloc_set_stereo_sgm on, the semi-global pass in their place, into the same planes.
+// Checks stereo on, right != ctx, capacity and the chains' agreement.
 int stereo_dense_frame(reloc_ctx *ctx, reloc_ctx *right, int w, int h, int order, int *ww, int *wh);
 // the speckle stage on the w x h planes of ctx's dense pass with ctx's speckle setting (window > 0), on ctx's stream
 // (reloc_speckle.hip)

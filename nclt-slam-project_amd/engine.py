@@ -715,6 +715,52 @@ class Engine:
         self._api.reloc_get_stereo_speckle(self._ctx, win, rng)
         return win.value, rng.value
 
+    # ------------------------------------------------------------------ semi-global aggregation (reloc_spec.h "STEREO, semi-global")
+    def set_stereo_sgm(self, paths: int = 0, p1: int = 968, p2: int = 3872):
+        """semi-global aggregation in this (the left eye's) engine's dense stereo passes (reloc_set_stereo_sgm): the SAD
+        costs summed along `paths` = 4 or 8 directions with the penalties 0 <= p1 <= p2 <= 8191 before the selection; paths 0
+        turns it off.  This project's matcher, not OpenCV's StereoSGBM."""
+        for name, v in (("paths", paths), ("p1", p1), ("p2", p2)):
+            if int(v) != v:
+                raise N.RelocError(f"set_stereo_sgm: {name} must be an integer")
+        self._api.reloc_set_stereo_sgm(self._ctx, int(paths), int(p1), int(p2))
+
+    def get_stereo_sgm(self):
+        """(paths, p1, p2); paths 0 = off"""
+        paths, p1, p2 = N.outs(i32, i32, i32)
+        self._api.reloc_get_stereo_sgm(self._ctx, paths, p1, p2)
+        return paths.value, p1.value, p2.value
+
+    def stereo_sgm_image(self, left: np.ndarray, right: np.ndarray, fx: float, baseline_m: float, min_disparity: int = 0,
+                         num_disparities: int = 128, uniqueness: int = 15, lr_check: bool = True, paths: int = 8, p1: int = 968,
+                         p2: int = 3872, path_mask: int | None = None):
+        """stereo_depth_image with the costs aggregated semi-globally (reloc_stereo_sgm_image): (depth_mm uint16, disparity
+        float32, status uint8), each (H, W).  paths: 4 or 8; path_mask (1..255, bit b = direction b of the specification)
+        overrides it.  The sum volume of the pass stays on the device (stereo_sgm_volume)."""
+        left, right = self._stereo_planes(left, right, "stereo_sgm_image")
+        if path_mask is None:
+            if paths not in (4, 8):
+                raise N.RelocError("stereo_sgm_image: paths must be 4 or 8 (or give path_mask)")
+            path_mask = 0x0F if paths == 4 else 0xFF
+        for name, v in (("path_mask", path_mask), ("p1", p1), ("p2", p2)):
+            if int(v) != v:
+                raise N.RelocError(f"stereo_sgm_image: {name} must be an integer")
+        h, w = left.shape
+        mm = np.zeros((h, w), np.uint16); disp = np.zeros((h, w), np.float32); st = np.zeros((h, w), np.uint8)
+        self._api.reloc_stereo_sgm_image(self._ctx, left.ctypes.data, right.ctypes.data, w, h, left.strides[0], float(fx),
+                                         float(baseline_m), int(min_disparity), int(num_disparities), int(uniqueness),
+                                         int(bool(lr_check)), int(path_mask), int(p1), int(p2), mm, disp, st)
+        return mm, disp, st
+
+    def stereo_sgm_volume(self) -> np.ndarray:
+        """the sum volume S of this engine's last semi-global pass (reloc_stereo_sgm_debug): (H, W, num_disparities) uint32,
+        0xFFFFFFFF where (pixel, disparity) is undefined"""
+        w, h, nd = N.outs(i32, i32, i32)
+        self._api.reloc_stereo_sgm_debug(self._ctx, None, w, h, nd)
+        S = np.zeros(w.value * h.value * nd.value, np.uint32)
+        self._api.reloc_stereo_sgm_debug(self._ctx, S, w, h, nd)
+        return S.reshape(h.value, w.value, nd.value)
+
     def frame_debug_plane(self, what: int, level: int) -> np.ndarray:
         buf = np.empty(self.max_w * self.max_h, np.uint8)
         w, h = N.outs(i32, i32)

@@ -10,6 +10,7 @@
                                                         [one flag per threshold: CORRELATION_FLAGS]
     the first two, for a rectified stereo pair without a depth sensor:
                                                         [--stereo-baseline M --stereo-num-disparities N
+                                                         --stereo-sgm-paths {0,4,8} --stereo-sgm-p1 N --stereo-sgm-p2 N
                                                          --stereo-rectify-right FILE.npz --right-topic NAME]
 
 (reference simulation/isaac/scripts/common/visual_landmark_matcher.py:175-231,503-530,
@@ -28,7 +29,7 @@ import numpy as np
 from .front_end import PIXEL_FORMATS, add_front_end_flags, front_end_flags, load_mask, pixel_format_setting  # noqa: F401  (load_mask: part of this module's interface)
 from .matcher import FusedLandmarkMatcher, LandmarkMatcherCore, MatcherConfig
 from .recorder import LandmarkRecorderCore
-from .stereo import StereoRig
+from .stereo import SGM_P1_DEFAULT, SGM_P2_DEFAULT, StereoRig
 
 RIGHT_TOPIC = "/camera/right/image_raw"      # --right-topic: the right eye of a stereo rig (--stereo-baseline)
 TICK_HZ = 2.0
@@ -403,12 +404,17 @@ def _chain_args(args):
 
 
 def add_stereo_flags(ap):
-    """--stereo-baseline, --stereo-num-disparities, --stereo-rectify-right, --right-topic: a StereoRig beside the front end"""
+    """--stereo-baseline, --stereo-num-disparities, --stereo-rectify-right, --stereo-sgm-*, --right-topic: a StereoRig beside the
+    front end"""
     ap.add_argument("--stereo-baseline", type=float, default=None, metavar="M",
                     help="baseline of a rectified stereo pair in metres: the right eye's frames stand in for the depth image")
     ap.add_argument("--stereo-num-disparities", type=int, default=128, metavar="N", help="searched disparities, 8..256 (default 128)")
     ap.add_argument("--stereo-rectify-right", default=None, metavar="FILE.npz",
                     help="the right eye's rectification maps: an .npz file holding map1 and map2 as cv2.remap takes them")
+    ap.add_argument("--stereo-sgm-paths", type=int, default=0, choices=(0, 4, 8), metavar="{0,4,8}",
+                    help="semi-global aggregation of the dense stereo pass along 4 or 8 directions (default 0: off)")
+    ap.add_argument("--stereo-sgm-p1", type=int, default=SGM_P1_DEFAULT, metavar="N", help=f"its penalty of a disparity step of one (default {SGM_P1_DEFAULT})")
+    ap.add_argument("--stereo-sgm-p2", type=int, default=SGM_P2_DEFAULT, metavar="N", help=f"its penalty of a larger step, p1..8191 (default {SGM_P2_DEFAULT})")
     ap.add_argument("--right-topic", default=RIGHT_TOPIC, metavar="NAME", help="topic of the right eye's frames")
 
 
@@ -420,7 +426,8 @@ def _stereo_kwargs(args):
     if args.stereo_rectify_right is not None:
         with np.load(args.stereo_rectify_right, allow_pickle=False) as z:
             maps = (z["map1"], z["map2"])
-    return dict(stereo=StereoRig(args.stereo_baseline, num_disparities=args.stereo_num_disparities, rectify_right=maps),
+    return dict(stereo=StereoRig(args.stereo_baseline, num_disparities=args.stereo_num_disparities, rectify_right=maps,
+                                 sgm_paths=args.stereo_sgm_paths, sgm_p1=args.stereo_sgm_p1, sgm_p2=args.stereo_sgm_p2),
                 right_topic=args.right_topic)
 
 

@@ -19,6 +19,8 @@ UNIQUENESS_MAX = 50                       # RELOC_STEREO_UNIQUENESS_MAX
 STATUS = ("ok", "border", "range", "edge", "uniqueness", "left-right", "far", "speckle")       # RELOC_STEREO_OK ..
 SPECKLE_RANGE_MAX = 255                   # RELOC_STEREO_SPECKLE_RANGE_MAX
 SPECKLE_NONE = -16                        # the quantised disparity of a pixel without one ("STEREO, speckle")
+SGM_PATHS = (0, 4, 8)                     # reloc_set_stereo_sgm: off, mask 0x0F, mask 0xFF
+SGM_P1_DEFAULT, SGM_P2_DEFAULT, SGM_P2_MAX = 968, 3872, 8191      # RELOC_STEREO_SGM_*
 
 
 @dataclass(frozen=True, eq=False)
@@ -31,7 +33,9 @@ class StereoRig:
     already, or use the left eye's maps being None too).  speckle_window, speckle_range: the speckle stage behind the dense
     pass ("STEREO, speckle"), OpenCV's speckleWindowSize and speckleRange -- components of at most speckle_window pixels whose
     neighbours differ by at most speckle_range disparities lose their depth; 0 = off.  The sparse per-keypoint depth has no
-    neighbourhood and is not filtered."""
+    neighbourhood and is not filtered.  sgm_paths, sgm_p1, sgm_p2: semi-global aggregation of the dense pass ("STEREO,
+    semi-global") along 4 or 8 directions with the penalties 0 <= sgm_p1 <= sgm_p2 <= 8191; 0 paths = off.  It is this
+    project's matcher over its SAD costs, not OpenCV's StereoSGBM, and the sparse per-keypoint depth does not use it."""
     baseline_m: float
     min_disparity: int = 0
     num_disparities: int = 128
@@ -40,23 +44,31 @@ class StereoRig:
     rectify_right: tuple | None = None
     speckle_window: int = 0
     speckle_range: int = 1
+    sgm_paths: int = 0
+    sgm_p1: int = SGM_P1_DEFAULT
+    sgm_p2: int = SGM_P2_DEFAULT
 
     def __post_init__(self):
         b = float(self.baseline_m)
         if not (np.isfinite(b) and b > 0.0):
             raise ValueError("stereo: baseline_m must be finite and > 0 (metres)")
         for name, lo, hi in (("min_disparity", 0, MIN_DISPARITY_MAX), ("num_disparities", *NUM_DISPARITIES), ("uniqueness", 0, UNIQUENESS_MAX),
-                             ("speckle_window", 0, 2 ** 31 - 1), ("speckle_range", 0, SPECKLE_RANGE_MAX)):
+                             ("speckle_window", 0, 2 ** 31 - 1), ("speckle_range", 0, SPECKLE_RANGE_MAX), ("sgm_paths", 0, 8),
+                             ("sgm_p1", 0, SGM_P2_MAX), ("sgm_p2", 0, SGM_P2_MAX)):
             v = getattr(self, name)
             if int(v) != v or not lo <= int(v) <= hi:
                 raise ValueError(f"stereo: {name} must be an integer in {lo}..{hi}")
             object.__setattr__(self, name, int(v))
+        if self.sgm_paths not in SGM_PATHS:
+            raise ValueError("stereo: sgm_paths must be 0, 4 or 8")
+        if self.sgm_p1 > self.sgm_p2:
+            raise ValueError("stereo: sgm_p1 must not exceed sgm_p2")
         object.__setattr__(self, "baseline_m", b)
         object.__setattr__(self, "lr_check", bool(self.lr_check))
 
     def settings(self) -> dict:
-        """the keywords of Engine.set_stereo and, behind fx and baseline_m, of Engine.stereo_depth; the speckle pair travels
-        separately (configure, depth_image)"""
+        """the keywords of Engine.set_stereo and, behind fx and baseline_m, of Engine.stereo_depth; the speckle pair and the
+        semi-global setting travel separately (configure, depth_image)"""
         return dict(baseline_m=self.baseline_m, min_disparity=self.min_disparity, num_disparities=self.num_disparities,
                     uniqueness=self.uniqueness, lr_check=self.lr_check)
 
@@ -65,10 +77,13 @@ class StereoRig:
         return replace(front_end, rectify=self.rectify_right)
 
     def configure(self, engine):
-        """the rig's setting on the left eye's Engine; the speckle stage only where the rig has one"""
+        """the rig's setting on the left eye's Engine; the speckle stage and the semi-global aggregation only where the rig
+        has them"""
         engine.set_stereo(**self.settings())
         if self.speckle_window:
             engine.set_stereo_speckle(self.speckle_window, self.speckle_range)
+        if self.sgm_paths:
+            engine.set_stereo_sgm(self.sgm_paths, self.sgm_p1, self.sgm_p2)
 
     def right_engine(self, engine, front_end):
         """an Engine for the right eye, as large as the left one, on the same device, configured with the right eye's front end"""
@@ -85,8 +100,15 @@ class StereoRig:
     def depth_image(self, backend, left_gray, right_gray, fx):
         """the (H, W) uint16 depth image, millimetres, 0 = no depth, of two planes of the chain's output through the backend's
         dense kernel; with a speckle window, then the stage from public pieces: the quantised disparity in NumPy, the
-        backend's filter_speckles, the depth zeroed where the filter removed a pixel"""
-        mm, disp, status = backend.stereo_depth_image(left_gray, right_gray, fx, **self.settings())
+        backend's filter_speckles, the depth zeroed where the filter removed a pixel.  With sgm_paths the backend's
+        semi-global entry takes the dense kernel's place; a backend without one (the CPU oracle) is refused."""
+        if self.sgm_paths:
+            if not hasattr(backend, "stereo_sgm_image"):
+                raise ValueError("stereo: this backend has no semi-global aggregation (sgm_paths must be 0 on it)")
+            mm, disp, status = backend.stereo_sgm_image(left_gray, right_gray, fx, **self.settings(), paths=self.sgm_paths,
+                                                        p1=self.sgm_p1, p2=self.sgm_p2)
+        else:
+            mm, disp, status = backend.stereo_depth_image(left_gray, right_gray, fx, **self.settings())
         if not self.speckle_window:
             return mm
         ok = np.asarray(status) == 0
