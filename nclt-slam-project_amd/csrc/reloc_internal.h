@@ -794,6 +794,22 @@ int image_gray_plain(reloc_ctx *c, const uint8_t *src, int w, int h, int sstride
 // working frame.  stereo_release: the events of a context that had stereo on.
 int stereo_frame(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img_right_dev, int w, int h, int order, int *ww, int *wh);
 void stereo_release(reloc_ctx *ctx);
+// What the sparse and the dense pass (reloc_stereo_dense.hip) share of reloc_stereo.hip.
+// A semi-global setting as a pass takes it: the directions (bit b of mask selects direction b) and the two penalties.
+struct StereoSgm { int mask, p1, p2; };
+// What a stateless stereo call checks after its pointers, in this order: fx finite and positive, the matcher's parameters, the
+// semi-global setting (sgm == NULL: a plain pass), the frame within ctx's capacity.
+int stereo_call_check(const reloc_ctx *ctx, int w, int h, double fx, double baseline_m, int min_disparity, int num_disparities,
+                      int uniqueness, int lr_check, const StereoSgm *sgm);
+// What a stereo pass checks of its pair of contexts before it enqueues anything: what an entry point checks (stereo_pair_entry),
+// then two contexts of one device and one gray conversion, the two chains in agreement as in a batch; *ww x *wh: the working frame.
+int stereo_pair_check(reloc_ctx *ctx, reloc_ctx *right, int w, int h, int *ww, int *wh);
+// The gray planes of a pass, plane[e] with rows of stride[e] bytes, e = 1 the right eye: the right eye's chain on right's stream,
+// the left eye's (lsrc == NULL: none, plane[0] is not written) on ctx's.  The streams are ordered by events in both directions:
+// right's goes on behind what ctx's holds so far -- the copy that brought the right frame (a _dev caller orders its frames on
+// ctx's stream) and the last stereo kernel, which still reads the right chain's planes -- and ctx's behind the right eye's chain.
+int stereo_gray_planes(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *lsrc, const uint8_t *rsrc, int w, int h, int ww, int wh,
+                       int order, const uint8_t *plane[2], int stride[2]);
 // the pinned direction table and its event of a context that updated its obstacle grid from the stereo plane (reloc_obstacle.hip)
 void obs_release(reloc_ctx *ctx);
 // blocks of a 1-D grid-stride launch of 256 threads over n elements: at least one, at most max_blocks
@@ -807,8 +823,8 @@ static inline int need_map(bool on, const char *who, const char *what, const cha
 // an occupied plane on the device (h x w uint8, non-zero = occupied; from_units: the occupancy map's int8 units, occupied from
 // RELOC_OCC_UNITS_OCC) as h packed rows of mp = ceil(w / 32) words, the bits beyond column w - 1 clear (reloc_correlation.hip)
 void corr_pack_plane(HostStaging &st, const void *plane, bool from_units, uint32_t *bits, int w, int h, int mp);
-// Dense stereo depth: both eyes' frames (ctx->frame_img, right->frame_img, w x h as handed in) through the gray half of their
-// chains, each on its own stream, no ORB; then k_stereo_dense and k_stereo_dense_finish on ctx's stream into ctx->stereo.dense
+// Dense stereo depth (reloc_stereo_dense.hip): both eyes' frames (ctx->frame_img, right->frame_img, w x h as handed in)
+// through the gray half of their chains, each on its own stream, no ORB; then k_stereo_dense and k_stereo_dense_finish on ctx's stream into ctx->stereo.dense
 // (mm: dense rows of *ww uint16); with reloc_set_stereo_sgm on, the semi-global pass in their place, into the same planes.
 // Checks stereo on, right != ctx, capacity and the chains' agreement.
 int stereo_dense_frame(reloc_ctx *ctx, reloc_ctx *right, int w, int h, int order, int *ww, int *wh);

@@ -25,13 +25,7 @@ struct ObsSrc { const void *data; int w, h; };
 struct ObsMask { const uint8_t *mask; int bh, bw, nby, nbx; float fill; };
 struct ObsFilterPrm { int bh, bw, min_count, n_cov; float lo, hi; double var_thresh, min_solid; };
 
-// (a) one depth pixel, as reloc_teach.h's depth_grid_point reads it
-template <bool F32>
-__device__ __forceinline__ float obs_z(const ObsSrc &s, int r, int c)
-{
-    const size_t at = (size_t)r * s.w + c;
-    return F32 ? reinterpret_cast<const float *>(s.data)[at] : __fdiv_rn((float)reinterpret_cast<const uint16_t *>(s.data)[at], 1000.0f);
-}
+// (a) a depth pixel is reloc_teach.h's depth_pixel, at r * w + c of the plane
 __device__ __forceinline__ bool obs_valid(float z, float lo, float hi) { return z > lo && z < hi && isfinite(z); }
 // the pixel behind the filter: fill inside a traversable block
 template <bool F32>
@@ -41,7 +35,7 @@ __device__ __forceinline__ float obs_pixel(const ObsSrc &s, const ObsMask &m, in
         const int by = r / m.bh, bx = c / m.bw;
         if (by < m.nby && bx < m.nbx && m.mask[by * m.nbx + bx]) return m.fill;
     }
-    return obs_z<F32>(s, r, c);
+    return depth_pixel(s.data, F32, (size_t)r * s.w + c);
 }
 
 // sums of a 256-thread workgroup in a fixed tree; every thread gets the total.  s: 256 doubles
@@ -68,7 +62,7 @@ __global__ __launch_bounds__(256) void k_obs_blocks(ObsSrc src, ObsFilterPrm p, 
     float mn = INFINITY;
     double sum = 0.0;
     for (int i = t; i < npix; i += 256) {
-        const float z = obs_z<F32>(src, by * p.bh + i / p.bw, bx * p.bw + i % p.bw);
+        const float z = depth_pixel(src.data, F32, (size_t)(by * p.bh + i / p.bw) * src.w + bx * p.bw + i % p.bw);
         if (obs_valid(z, p.lo, p.hi)) { ++n; mn = fminf(mn, z); sum = __dadd_rn(sum, (double)z); }
     }
     s_min[t] = mn;
@@ -82,7 +76,7 @@ __global__ __launch_bounds__(256) void k_obs_blocks(ObsSrc src, ObsFilterPrm p, 
     const double mean = N > 0 ? __ddiv_rn(total, (double)N) : 0.0;
     double ss = 0.0;
     for (int i = t; i < npix; i += 256) {
-        const float z = obs_z<F32>(src, by * p.bh + i / p.bw, bx * p.bw + i % p.bw);
+        const float z = depth_pixel(src.data, F32, (size_t)(by * p.bh + i / p.bw) * src.w + bx * p.bw + i % p.bw);
         if (obs_valid(z, p.lo, p.hi)) { const double d = __dsub_rn((double)z, mean); ss = __dadd_rn(ss, __dmul_rn(d, d)); }
     }
     const double ss_total = obs_tree_sum(ss, s_sum);
@@ -277,8 +271,6 @@ __global__ __launch_bounds__(256) void k_morph_pass(const uint8_t *__restrict__ 
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
-static inline bool obs_finite(double v) { return v - v == 0.0; }
-
 // the frame block, taken by the first call that reads a depth image
 static int obs_frame_alloc(reloc_ctx *ctx)
 {
@@ -297,11 +289,9 @@ struct ObsFrame { ObsSrc src; bool f32; };
 static int obs_source(HostStaging &st, const void *depth, int is_f32, int w, int h, bool stereo, const char *who, ObsFrame &f)
 {
     reloc_ctx *ctx = st.ctx;
-    if (stereo) {
-        const StereoState::Dense &d = ctx->stereo.dense;
-        if (!d.block.p || d.w == 0) { reloc_set_error("%s: no dense stereo pass on this context yet", who); return RELOC_E_STATE; }
-        w = d.w; h = d.h;
-    }
+    const StereoState::Dense *d = stereo ? stereo_last_dense(ctx) : nullptr;
+    if (stereo && !d) { reloc_set_error("%s: no dense stereo pass on this context yet", who); return RELOC_E_STATE; }
+    if (d) { w = d->w; h = d->h; }
     if (w > RELOC_OBS_MAX_COLS || (int64_t)w * h > (int64_t)ctx->max_w * ctx->max_h) {
         reloc_set_error("%s: depth image %d x %d exceeds the capacity (ctx %d x %d, %d columns)", who, w, h, ctx->max_w, ctx->max_h, RELOC_OBS_MAX_COLS);
         return RELOC_E_CAPACITY;
@@ -311,7 +301,7 @@ static int obs_source(HostStaging &st, const void *depth, int is_f32, int w, int
         return RELOC_E_CAPACITY;
     }
     if (int rc = obs_frame_alloc(ctx)) return rc;
-    const void *dev = stereo ? (const void *)ctx->stereo.dense.mm : (const void *)st.upload_slot(5, (const uint8_t *)depth, (int64_t)w * h * (is_f32 ? 4 : 2));
+    const void *dev = d ? (const void *)d->mm : (const void *)st.upload_slot(5, (const uint8_t *)depth, (int64_t)w * h * (is_f32 ? 4 : 2));
     f = ObsFrame{{dev, w, h}, !stereo && is_f32 != 0};
     return st.rc;
 }
@@ -331,7 +321,7 @@ struct ObsProfilePrm { int step; float lo, hi; int q, min_valid; float fill; int
 
 static int obs_profile_check(const reloc_ctx *ctx, const ObsProfilePrm &p, const char *who)
 {
-    if (!(p.step >= 1 && p.q >= 0 && p.q <= 100 && p.min_valid >= 1 && obs_finite(p.lo) && obs_finite(p.hi) && obs_finite(p.fill) && p.lo >= 0.0f)) {
+    if (!(p.step >= 1 && p.q >= 0 && p.q <= 100 && p.min_valid >= 1 && occ_finite(p.lo) && occ_finite(p.hi) && occ_finite(p.fill) && p.lo >= 0.0f)) {
         reloc_set_error("bad argument: %s: step >= 1, 0 <= lo, q in [0, 100], min_valid >= 1, everything finite", who);
         return RELOC_E_ARG;
     }
@@ -362,8 +352,8 @@ RELOC_API int reloc_obs_set_filter(reloc_ctx *ctx, int bh, int bw, float lo, flo
     ARG_CHECK_CTX(ctx, true, "reloc_obs_set_filter");
     ObstacleState &o = ctx->obs;
     if (bh == 0 && bw == 0) { o.bh = o.bw = 0; return RELOC_OK; }
-    ARG_CHECK(bh > 0 && bw > 0 && obs_finite(lo) && obs_finite(hi) && lo >= 0.0f && hi > lo && min_count >= 1 && obs_finite(coverage) && coverage > 0.0 &&
-                  obs_finite(var_thresh) && obs_finite(min_solid) && obs_finite(fill),
+    ARG_CHECK(bh > 0 && bw > 0 && occ_finite(lo) && occ_finite(hi) && lo >= 0.0f && hi > lo && min_count >= 1 && occ_finite(coverage) && coverage > 0.0 &&
+                  occ_finite(var_thresh) && occ_finite(min_solid) && occ_finite(fill),
               "reloc_obs_set_filter: positive block sides, 0 <= lo < hi, min_count >= 1, coverage > 0, everything finite");
     if (bh < RELOC_OBS_MIN_BLOCK || bw < RELOC_OBS_MIN_BLOCK || bh > RELOC_OBS_MAX_BLOCK || bw > RELOC_OBS_MAX_BLOCK) {
         reloc_set_error("reloc_obs_set_filter: block %d x %d outside the capacity (sides %d .. %d)", bh, bw, RELOC_OBS_MIN_BLOCK, RELOC_OBS_MAX_BLOCK);
@@ -441,8 +431,8 @@ RELOC_API int reloc_obs_profile_stereo_dev(reloc_ctx *ctx, int step, float lo, f
 RELOC_API int reloc_obs_grid_configure(reloc_ctx *ctx, int cells, double res, float decay, float hit, float hit_nb, float obstacle_hits,
                                        int step, float lo, float hi, int q, int min_valid, int use_filter)
 {
-    ARG_CHECK_CTX(ctx, cells > 0 && obs_finite(res) && res > 0 && obs_finite(decay) && decay > 0 && obs_finite(hit) && hit > 0 && obs_finite(hit_nb) &&
-                           hit_nb > 0 && obs_finite(obstacle_hits) && obstacle_hits > 0,
+    ARG_CHECK_CTX(ctx, cells > 0 && occ_finite(res) && res > 0 && occ_finite(decay) && decay > 0 && occ_finite(hit) && hit > 0 && occ_finite(hit_nb) &&
+                           hit_nb > 0 && occ_finite(obstacle_hits) && obstacle_hits > 0,
                   "reloc_obs_grid_configure: cells, res, decay, hit, hit_nb and obstacle_hits must be positive and finite");
     if (int rc = obs_profile_check(ctx, ObsProfilePrm{step, lo, hi, q, min_valid, 0.0f, use_filter}, "reloc_obs_grid_configure")) return rc;
     if (cells > RELOC_OBS_MAX_CELLS) {
@@ -521,7 +511,7 @@ static int obs_grid_update(reloc_ctx *ctx, int sx, int sy, bool have_depth, cons
             return RELOC_E_CAPACITY;
         }
         for (int k = 0; k < 2 * ncols; ++k)
-            if (!obs_finite(dirs[k])) { st.finish(); reloc_set_error("bad argument: %s: the directions must be finite", who); return RELOC_E_ARG; }
+            if (!occ_finite(dirs[k])) { st.finish(); reloc_set_error("bad argument: %s: the directions must be finite", who); return RELOC_E_ARG; }
         obs_profile_launch(st, f, p);
         if (wait) ddirs = (const double2 *)st.upload_slot(6, dirs, (int64_t)2 * ncols);
         else st.run([&] { return obs_dirs_enqueue(ctx, dirs, ncols, st.slot<double>(6, (int64_t)2 * ncols), &ddirs); });
@@ -550,11 +540,11 @@ RELOC_API int reloc_obs_grid_update_stereo_dev(reloc_ctx *ctx, int sx, int sy, c
 
 RELOC_API int reloc_obs_grid_profile(reloc_ctx *ctx, const double *dirs, int n, double max_range, double *out)
 {
-    ARG_CHECK_CTX(ctx, n >= 0 && ((dirs && out) || n == 0) && obs_finite(max_range), "reloc_obs_grid_profile: n >= 0 directions and their output, a finite range");
+    ARG_CHECK_CTX(ctx, n >= 0 && ((dirs && out) || n == 0) && occ_finite(max_range), "reloc_obs_grid_profile: n >= 0 directions and their output, a finite range");
     if (int rc = obs_need_grid(ctx, "reloc_obs_grid_profile")) return rc;
     const ObstacleState &o = ctx->obs;
     for (int k = 0; k < 2 * n; ++k)
-        if (!obs_finite(dirs[k])) { reloc_set_error("bad argument: reloc_obs_grid_profile: the directions must be finite"); return RELOC_E_ARG; }
+        if (!occ_finite(dirs[k])) { reloc_set_error("bad argument: reloc_obs_grid_profile: the directions must be finite"); return RELOC_E_ARG; }
     if (n > RELOC_OBS_MAX_SECTORS || max_range / o.res > (double)RELOC_OBS_MAX_STEPS) {
         reloc_set_error("reloc_obs_grid_profile: %d sectors or %g steps exceed the capacity (%d, %d)", n, max_range / o.res, RELOC_OBS_MAX_SECTORS, RELOC_OBS_MAX_STEPS);
         return RELOC_E_CAPACITY;

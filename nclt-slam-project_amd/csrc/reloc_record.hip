@@ -520,7 +520,7 @@ RELOC_API int reloc_depth_points(reloc_ctx *ctx, const void *depth, int is_f32, 
     return RELOC_OK;
 }
 
-// The cloud of a stereo pair: the dense pass of reloc_stereo.hip, then k_depth_points on its plane where it lies.
+// The cloud of a stereo pair: the dense pass of reloc_stereo_dense.hip, then k_depth_points on its plane where it lies.
 RELOC_API int reloc_stereo_frame_points(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img, const uint8_t *img_right, int w, int h,
                                         int order, int step, float zmin, float zmax, float *points, int32_t *n_out)
 {

@@ -1,7 +1,8 @@
-// reloc_teach.h -- what the teach-side files (reloc_record, _stereo, _occupancy, _correlation, _route .hip) share
-// and no other file includes: the ordered compaction of a 1024-thread workgroup, the depth pixel of the obstacle cloud and of the
-// occupancy map, the frame source and map point of the occupancy map and the correlation scan (host side: FrameSrc, frame_from_*,
-// FRAME_KERNEL, frame_transform_check, occ_need_map), the staging of a stereo pair from the caller's memory.
+// reloc_teach.h -- what the teach-side files (reloc_record, _stereo, _stereo_dense through reloc_stereo_match.h, _occupancy,
+// _correlation, _route, _obstacle .hip) share and no other file includes: the ordered compaction of a 1024-thread workgroup, the
+// depth pixel of the obstacle cloud, the occupancy map and the obstacle profile, the frame source and map point of the occupancy
+// map and the correlation scan (host side: FrameSrc, frame_from_*, FRAME_KERNEL, frame_transform_check, occ_need_map), the
+// last dense stereo pass of a context, the staging of a stereo pair from the caller's memory.
 #pragma once
 #include "reloc_internal.h"
 
@@ -41,14 +42,19 @@ static inline DepthGrid depth_grid(const void *data, int is_f32, int w, int h, i
     return DepthGrid{data, is_f32, w, h, stride, step, (float)K4[2], (float)K4[3], (float)K4[0], (float)K4[1], zmin, zmax};
 }
 
+// Pixel `at` of a depth plane in metres, float32: as it lies, or uint16 millimetres divided by 1000.  f32 is the caller's to pass
+// so that a kernel templated on the format folds the branch.
+__device__ __forceinline__ float depth_pixel(const void *data, bool f32, size_t at)
+{
+    return f32 ? reinterpret_cast<const float *>(data)[at] : __fdiv_rn((float)reinterpret_cast<const uint16_t *>(data)[at], 1000.0f);
+}
+
 // Pixel i of the grid in raster order: p = (z, -(u - cx) / fx * z, -(v - cy) / fy * z) in float32, true iff zmin < z < zmax and
-// z is finite.  f32 is the caller's to pass so that a kernel templated on the format folds the branch.
+// z is finite.
 __device__ __forceinline__ bool depth_grid_point(const DepthGrid &g, bool f32, int i, float p[3])
 {
     const int gw = g.cols(), v = (i / gw) * g.step, u = (i % gw) * g.step;
-    const size_t at = (size_t)v * g.stride + u;
-    const float z = f32 ? reinterpret_cast<const float *>(g.data)[at]
-                        : __fdiv_rn((float)reinterpret_cast<const uint16_t *>(g.data)[at], 1000.0f);
+    const float z = depth_pixel(g.data, f32, (size_t)v * g.stride + u);
     p[0] = z;
     p[1] = -__fmul_rn(__fdiv_rn(__fsub_rn((float)u, g.cx), g.fx), z);
     p[2] = -__fmul_rn(__fdiv_rn(__fsub_rn((float)v, g.cy), g.fy), z);
@@ -107,12 +113,21 @@ static inline FrameSrc frame_from_depth(HostStaging &st, const void *depth, int 
     const void *ddepth = st.upload_slot(5, (const uint8_t *)depth, (int64_t)w * h * (is_f32 ? 4 : 2));
     return {{nullptr, 0, depth_grid(ddepth, is_f32, w, h, w, step, K4, zmin, zmax)}, is_f32 ? OCC_SRC_DEPTH_F32 : OCC_SRC_DEPTH_U16};
 }
+// the last dense stereo pass of a context (its planes, w x h), or NULL: none yet
+static inline const StereoState::Dense *stereo_last_dense(const reloc_ctx *ctx)
+{
+    const StereoState::Dense &d = ctx->stereo.dense;
+    return d.block.p && d.w != 0 ? &d : nullptr;
+}
 // the millimetre plane of the context's last dense stereo pass where it lies, under the context's camera
 static inline FrameSrc frame_from_stereo(HostStaging &st, int step, float zmin, float zmax)
 {
-    const StereoState::Dense &d = st.ctx->stereo.dense;
-    if (!st.rc && (!d.block.p || d.w == 0)) { reloc_set_error("no dense stereo pass on this context yet"); st.rc = RELOC_E_STATE; }
-    return {{nullptr, 0, depth_grid(d.mm, 0, d.w, d.h, d.w, step, st.ctx->cam.K4, zmin, zmax)}, OCC_SRC_DEPTH_U16};
+    const StereoState::Dense *d = stereo_last_dense(st.ctx);
+    if (!d) {       // an empty plane, with the caller's step: the host divides by it (cols, rows) before st.rc stops the launches
+        if (!st.rc) { reloc_set_error("no dense stereo pass on this context yet"); st.rc = RELOC_E_STATE; }
+        return {{nullptr, 0, depth_grid(nullptr, 0, 0, 0, 0, step, st.ctx->cam.K4, zmin, zmax)}, OCC_SRC_DEPTH_U16};
+    }
+    return {{nullptr, 0, depth_grid(d->mm, 0, d->w, d->h, d->w, step, st.ctx->cam.K4, zmin, zmax)}, OCC_SRC_DEPTH_U16};
 }
 // the 3 x 4 transform of a frame: every value finite
 static inline int frame_transform_check(const double *T12, const char *who)

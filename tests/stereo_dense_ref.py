@@ -1,5 +1,5 @@
 """NumPy restatement of the "STEREO, dense" paragraph of include/reloc_spec.h -- k_stereo_dense / k_stereo_dense_finish of
-csrc/reloc_stereo.hip: the STEREO steps at every integer pixel, vectorised.  One int32 cost volume C(d, v, u) per disparity
+csrc/reloc_stereo_dense.hip: the STEREO steps at every integer pixel, vectorised.  One int32 cost volume C(d, v, u) per disparity
 from integral-image box sums; the left-right search of step 6 is read off the diagonal of that volume (the right disparity
 map), never computed from a patch of the right eye.  tests/test_stereo_dense_host.py holds it to the per-keypoint loop of
 tests/stereo_ref.py at every pixel, tests/test_gpu_stereo_dense.py holds the HIP kernels to it bit for bit."""

@@ -141,6 +141,35 @@ def test_dense_equals_the_sparse_kernel_at_rounded_keypoints(engine, scene1):
         assert len(set(sst.tolist())) >= 5
 
 
+@pytest.fixture(scope="module")
+def scene3():
+    """300 x 36, two tiles wide: two planted disparities, a periodic and a constant band"""
+    return SR.banded_scene(5, 300, 36, disparities=(3, 17), periodic=(13, 23, 16, 5), constant=(25, 34, 90))[:2]
+
+
+@pytest.mark.parametrize("lr", [True, False], ids=["lr", "nolr"])
+@pytest.mark.parametrize("md", [0, 7])
+@pytest.mark.parametrize("nd", [8, 65, 256])
+def test_the_three_matchers_agree_at_every_pixel(engine, scene3, nd, md, lr):
+    """One decision per pixel: the sparse kernel with every integer pixel as a keypoint, the dense pass and the semi-global
+    pass with both penalties 0 (S = 8 C: the same minima, gates and parabola) against the dense reference, exactly."""
+    left, right = scene3
+    h, w = left.shape
+    kw = dict(num_disparities=nd, min_disparity=md, lr_check=lr)
+    ref = SD.dense(left, right, FX, BASELINE, **kw)
+    counts = np.bincount(ref[2].ravel(), minlength=7)
+    print("statuses 0..6 of the reference:", counts.tolist())
+    assert (counts[:5] > 0).all()                                    # conditions on the inputs
+    if lr and md == 0:
+        assert (counts > 0).all()
+    uu, vv = np.meshgrid(np.arange(w, dtype=np.float32), np.arange(h, dtype=np.float32))
+    xy = np.stack([uu.ravel(), vv.ravel()], axis=1)
+    sparse = engine.stereo_depth(left, right, xy, FX, BASELINE, **kw)
+    _same(tuple(a.reshape(h, w) for a in sparse), ref)
+    _same(engine.stereo_depth_image(left, right, FX, BASELINE, **kw), ref)
+    _same(engine.stereo_sgm_image(left, right, FX, BASELINE, p1=0, p2=0, path_mask=0xFF, **kw), ref)
+
+
 # ---- 6: the frame path ----------------------------------------------------------------------------------------------
 def _shift_maps(w, h, dx):
     x, y = np.meshgrid(np.arange(w, dtype=np.float32), np.arange(h, dtype=np.float32))
