@@ -522,6 +522,30 @@ int reloc_stereo_sgm_image(reloc_ctx *ctx, const uint8_t *left, const uint8_t *r
  * reloc_stereo_sgm_image and a single-bit mask it is the per-direction tap. */
 int reloc_stereo_sgm_debug(reloc_ctx *ctx, uint32_t *S, int32_t *w, int32_t *h, int32_t *nd);
 
+/* ---- census cost (include/reloc_spec.h, "STEREO, census") ------------------------------------------ */
+/* The data term of the three matchers: RELOC_STEREO_COST_SAD (0, a new context) or RELOC_STEREO_COST_CENSUS (1), the Hamming
+ * distance of 8-bit census transforms of both eyes, for pairs that are exposed unequally.  A persistent setting of the LEFT
+ * context, independent of reloc_set_stereo, reloc_set_stereo_speckle and reloc_set_stereo_sgm.  It applies to every pass
+ * that runs with the context's settings (reloc_record_frame_stereo, reloc_tick_accumulate_stereo_dev,
+ * reloc_stereo_frame_depth, reloc_stereo_frame_points, and so to what reloc_occ_integrate_stereo_dev,
+ * reloc_corr_match_stereo_dev, reloc_obs_*_stereo_dev, reloc_stereo_debug and reloc_stereo_dense_debug read).  A value
+ * outside 0..1 returns RELOC_E_ARG and changes nothing.  The two census planes (2 bytes per pixel of the capacity) are taken
+ * on the first census pass; a context that never selects the census allocates and launches nothing of it. */
+int reloc_set_stereo_cost(reloc_ctx *ctx, int cost);
+int reloc_get_stereo_cost(reloc_ctx *ctx, int32_t *cost);
+/* reloc_stereo_depth with the cost as a parameter (reloc_stereo_depth itself means cost 0); the same checks. */
+int reloc_stereo_depth_cost(reloc_ctx *ctx, const uint8_t *left, const uint8_t *right, int w, int h, int stride,
+                            const float *xy, int n, double fx, double baseline_m, int min_disparity, int num_disparities,
+                            int uniqueness, int lr_check, int cost, uint16_t *depth_mm, float *disparity, uint8_t *status);
+/* reloc_stereo_sgm_image with the cost as a parameter; path_mask 0 means no aggregation (reloc_stereo_depth_image with that
+ * cost; p1, p2 are then ignored).  reloc_stereo_depth_image and reloc_stereo_sgm_image themselves mean cost 0. */
+int reloc_stereo_image_cost(reloc_ctx *ctx, const uint8_t *left, const uint8_t *right, int w, int h, int stride, double fx,
+                            double baseline_m, int min_disparity, int num_disparities, int uniqueness, int lr_check, int cost,
+                            int path_mask, int p1, int p2, uint16_t *depth_mm, float *disparity, uint8_t *status);
+/* Parity tap: the census transform alone of a gray plane of w x h (w, h >= 1, within the capacity), rows stride >= w bytes
+ * apart, into out (w x h, dense rows).  No byte of the padding is read.  Host pointers; synchronous. */
+int reloc_census(reloc_ctx *ctx, const uint8_t *gray, int w, int h, int stride, uint8_t *out);
+
 /* ---- speckle filter (include/reloc_spec.h, "STEREO, speckle") -------------------------------------- */
 /* OpenCV's filterSpeckles on an int16 plane of w x h, rows stride ELEMENTS apart, in place: every pixel of a 4-connected
  * component (valid = differs from new_val; joined = |a - b| <= max_diff) of at most max_speckle_size pixels becomes new_val;

@@ -395,7 +395,30 @@
  *   identity   with P1 = P2 = 0 every L_r equals C, so S = n C for n selected directions: the argmin, both gates (a common
  *              factor on both sides) and the parabola's quotient (numerator and denominator scaled alike, and the division
  *              is correctly rounded) are those of C, and every plane equals the dense pass bit for bit, for every mask.
- * tests/stereo_sgm_ref.py restates it. */
+ * tests/stereo_sgm_ref.py restates it.
+ *
+ * STEREO, census: an optional data term for pairs whose eyes are exposed unequally (own auto-exposure and gain per camera,
+ * vignetting per lens).  One setting, cost: RELOC_STEREO_COST_SAD (0, the default: everything above) or
+ * RELOC_STEREO_COST_CENSUS (1).
+ *   transform  T(I) of a w x h 8-bit plane I, w, h >= 1, is a w x h 8-bit plane: bit k of T(I)[v, u] is set when
+ *              I[clamp(v + dj_k, 0, h - 1), clamp(u + di_k, 0, w - 1)] < I[v, u].  The comparison is strict: equal values give
+ *              0.  (di_k, dj_k), k = 0..7, is (-2,-2) (0,-2) (2,-2) (-2,0) (2,0) (-2,2) (0,2) (2,2), di along the row.
+ *              Coordinates are clamped to the image, not to the stride: no byte outside 0 <= x < w, 0 <= y < h is read.
+ *   cost       with the census, step 3 reads C(d) = sum over j, i in -R..R of popcount(T(L)[v + j, u + i] xor
+ *              T(R)[v + j, u - d + i]), and step 6's C' is formed likewise.  0 <= C <= 8 * 121 = 968.
+ *   unchanged  steps 1, 2 and 4 to 8, the statuses, the dense identity C'(d') = C(v, xr + d', d'), the speckle stage and the
+ *              semi-global recurrence, which runs over these costs as it runs over the SADs.  A flat window (every T equal,
+ *              a constant gray value among them) has all costs 0 and fails at step 4 or 5 as before.
+ *   invariance T(a I + b) = T(I) for a > 0 wherever nothing clips and no two compared values round onto each other: the
+ *              transform keeps the order of gray values and nothing else, so an eye that is re-exposed costs what it cost.
+ *   penalties  the semi-global defaults over census costs are one and four bits on each of the window's 121 pixels,
+ *              RELOC_STEREO_SGM_P1_CENSUS_DEFAULT and _P2_CENSUS_DEFAULT; the SAD defaults over costs of at most 968
+ *              over-smooth.  A setting's own defaults (reloc_set_stereo_sgm with paths 0) stay the SAD ones.
+ * tests/stereo_census_ref.py restates it. */
+#define RELOC_STEREO_COST_SAD          0
+#define RELOC_STEREO_COST_CENSUS       1
+#define RELOC_STEREO_SGM_P1_CENSUS_DEFAULT 121  /* 1 * 121 */
+#define RELOC_STEREO_SGM_P2_CENSUS_DEFAULT 484  /* 4 * 121 */
 #define RELOC_STEREO_R                 5
 #define RELOC_STEREO_MIN_DISPARITY_MAX 1024
 #define RELOC_STEREO_NUM_DISP_MIN      8

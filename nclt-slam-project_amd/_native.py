@@ -143,6 +143,13 @@ SIGNATURES = {
     "reloc_stereo_sgm_image": (C.c_int, [c_ctx, P, P, C.c_int, C.c_int, C.c_int, f64, f64, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_int, P, P, P]),
     "reloc_stereo_sgm_debug": (C.c_int, [c_ctx, P, P, P, P]),
+    "reloc_set_stereo_cost": (C.c_int, [c_ctx, C.c_int]),
+    "reloc_get_stereo_cost": (C.c_int, [c_ctx, P]),
+    "reloc_stereo_depth_cost": (C.c_int, [c_ctx, P, P, C.c_int, C.c_int, C.c_int, P, C.c_int, f64, f64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, P, P, P]),
+    "reloc_stereo_image_cost": (C.c_int, [c_ctx, P, P, C.c_int, C.c_int, C.c_int, f64, f64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.c_int, C.c_int, P, P, P]),
+    "reloc_census": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, P]),
     "reloc_occ_configure": (C.c_int, [c_ctx, f64, f64, f64, C.c_int, C.c_int, f64, f64, C.c_int]),
     "reloc_occ_integrate_points": (C.c_int, [c_ctx, P, C.c_int, P, P]),
     "reloc_occ_integrate_depth": (C.c_int, [c_ctx, P, C.c_int, C.c_int, C.c_int, C.c_int, P, f32, f32, P, P]),

@@ -62,3 +62,11 @@ void stereo_sgm_lines(BlockCarver &c, G &g, int64_t entries, int64_t px)
     c.own(g.vol, entries);
     c.own(g.best, px);
 }
+
+// Census stereo (StereoState::Census): the census planes of both eyes, px = max_w * max_h bytes each
+template <typename C>
+void stereo_census_lines(BlockCarver &c, C &s, int64_t px)
+{
+    c.own(s.left, px);
+    c.own(s.right, px);
+}

@@ -453,6 +453,14 @@ struct StereoState {
         int64_t cap_entries = 0, cap_px = 0;      // what vol / sum and best hold
         int w = 0, h = 0, nd = 0, dmin = 0;       // the last semi-global pass (reloc_stereo_sgm_debug); w 0 = none yet
     } sgm;
+    // The data term of the three matchers ("STEREO, census"; reloc_set_stereo_cost, a setting of its own): SAD, the default, or
+    // the census.  The census planes of a pass's two eyes (dense rows of the pass's width) are taken on the first census pass
+    // (stereo_census_alloc); a context that never selects the census has none of it.
+    int cost = RELOC_STEREO_COST_SAD;
+    struct Census {
+        DevBlock block;                  // the pointers below lie in it (stereo_census_lines)
+        uint8_t *left = nullptr, *right = nullptr;
+    } census;
     bool on() const { return baseline > 0.0; }
 };
 
@@ -800,7 +808,7 @@ struct StereoSgm { int mask, p1, p2; };
 // What a stateless stereo call checks after its pointers, in this order: fx finite and positive, the matcher's parameters, the
 // semi-global setting (sgm == NULL: a plain pass), the frame within ctx's capacity.
 int stereo_call_check(const reloc_ctx *ctx, int w, int h, double fx, double baseline_m, int min_disparity, int num_disparities,
-                      int uniqueness, int lr_check, const StereoSgm *sgm);
+                      int uniqueness, int lr_check, int cost, const StereoSgm *sgm);
 // What a stereo pass checks of its pair of contexts before it enqueues anything: what an entry point checks (stereo_pair_entry),
 // then two contexts of one device and one gray conversion, the two chains in agreement as in a batch; *ww x *wh: the working frame.
 int stereo_pair_check(reloc_ctx *ctx, reloc_ctx *right, int w, int h, int *ww, int *wh);
@@ -810,6 +818,11 @@ int stereo_pair_check(reloc_ctx *ctx, reloc_ctx *right, int w, int h, int *ww, i
 // ctx's stream) and the last stereo kernel, which still reads the right chain's planes -- and ctx's behind the right eye's chain.
 int stereo_gray_planes(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *lsrc, const uint8_t *rsrc, int w, int h, int ww, int wh,
                        int order, const uint8_t *plane[2], int stride[2]);
+// The census planes of a pass's eyes (reloc_census.hip; "STEREO, census").  stereo_census_alloc: the context's census block on
+// its first census pass, before the pass's stopwatch bracket.  stereo_census_launch: k_census over both eyes (device pointers,
+// w x h, each with its own stride) on ctx's stream; afterwards the pointers name ctx's census planes and both strides are w.
+int stereo_census_alloc(reloc_ctx *ctx);
+void stereo_census_launch(reloc_ctx *ctx, const uint8_t *&left, int &lstride, const uint8_t *&right, int &rstride, int w, int h);
 // the pinned direction table and its event of a context that updated its obstacle grid from the stereo plane (reloc_obstacle.hip)
 void obs_release(reloc_ctx *ctx);
 // blocks of a 1-D grid-stride launch of 256 threads over n elements: at least one, at most max_blocks

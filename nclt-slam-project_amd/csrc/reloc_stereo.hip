@@ -12,6 +12,8 @@
 //                    so the lowest disparity wins a tie by the reduction itself.  The costs of a wave stay in registers (one
 //                    per pass); the parabola's neighbours are read back from the lanes that hold them.
 //                    Every branch on a status is wave-uniform; a workgroup is one wave, so its barriers cost nothing.
+//                    k_stereo_depth<COST>: with the census ("STEREO, census") the planes are the census planes of
+//                    reloc_census.hip, staged the same way, and a dword's cost is an xor and a popcount (stereo_cost4).
 // Each eye has its own row stride (a pyramid level or a stage's plane: (w + 63) & ~63; a dense gray plane or a caller's mono8
 // frame: w; reloc_stereo_depth: the caller's).  The bytes are staged one by one through the cache: rows start at any
 // alignment, and a byte outside 0 <= x < w, row padding included, is never fetched.
@@ -39,7 +41,16 @@ __device__ __forceinline__ void stereo_stage(const uint8_t *__restrict__ img, in
     }
 }
 
-// SAD of the staged patch and the SP x SP window whose first byte is byte `off` of the staged rows
+// the cost of four bytes against four bytes on top of acc: the SAD of gray bytes, or the Hamming distance of census bytes
+template <int COST>
+__device__ __forceinline__ unsigned stereo_cost4(unsigned a, unsigned b, unsigned acc)
+{
+    if constexpr (COST == RELOC_STEREO_COST_CENSUS) return acc + (unsigned)__builtin_popcount(a ^ b);      // v_xor, v_bcnt with its addend
+    else return __builtin_amdgcn_sad_u8(a, b, acc);
+}
+
+// cost of the staged patch and the SP x SP window whose first byte is byte `off` of the staged rows
+template <int COST>
 __device__ __forceinline__ int stereo_cost(const uint32_t *strip, const uint32_t *patch, int off)
 {
     const int q = off >> 2;
@@ -49,14 +60,16 @@ __device__ __forceinline__ int stereo_cost(const uint32_t *strip, const uint32_t
     for (int j = 0; j < SP; ++j) {
         const uint32_t *s = strip + j * STRIP_DW + q;
         const uint32_t w0 = s[0], w1 = s[1], w2 = s[2], w3 = s[3];
-        c = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w1, w0, sh), patch[PATCH_DW * j], c);
-        c = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w2, w1, sh), patch[PATCH_DW * j + 1], c);
-        c = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w3, w2, sh) & 0x00FFFFFFu, patch[PATCH_DW * j + 2], c);
+        c = stereo_cost4<COST>(__builtin_amdgcn_alignbyte(w1, w0, sh), patch[PATCH_DW * j], c);
+        c = stereo_cost4<COST>(__builtin_amdgcn_alignbyte(w2, w1, sh), patch[PATCH_DW * j + 1], c);
+        c = stereo_cost4<COST>(__builtin_amdgcn_alignbyte(w3, w2, sh) & 0x00FFFFFFu, patch[PATCH_DW * j + 2], c);
     }
     return (int)c;
 }
 
-// keypoint blockIdx.x of xy; count: their number on the device (the frame's own keypoints, at most n_max) or NULL: n_max
+// keypoint blockIdx.x of xy; count: their number on the device (the frame's own keypoints, at most n_max) or NULL: n_max.
+// COST: the planes are gray planes (SAD) or census planes
+template <int COST>
 __global__ __launch_bounds__(64) void k_stereo_depth(const uint8_t *__restrict__ left, int lstride, const uint8_t *__restrict__ right,
                                                      int rstride, const float *__restrict__ xy, const int32_t *__restrict__ count,
                                                      int n_max, StereoParams p, uint16_t *__restrict__ o_mm,
@@ -84,7 +97,7 @@ __global__ __launch_bounds__(64) void k_stereo_depth(const uint8_t *__restrict__
                     if (q) __syncthreads();                       // the previous pass has read the strip
                     stereo_stage(right, rstride, p.w, v, u - dmin - 64 * q - 63 - SR, STRIP_DW, false, s_strip, lane);
                     __syncthreads();
-                    cost[q] = stereo_cost(s_strip, s_patch, 63 - lane);
+                    cost[q] = stereo_cost<COST>(s_strip, s_patch, 63 - lane);
                 }
             }
         }
@@ -104,7 +117,7 @@ __global__ __launch_bounds__(64) void k_stereo_depth(const uint8_t *__restrict__
             if (q) __syncthreads();
             stereo_stage(left, lstride, p.w, v, xr + d0 - SR, STRIP_DW, false, s_strip, lane);
             __syncthreads();
-            const int cq = stereo_cost(s_strip, s_patch, lane);
+            const int cq = stereo_cost<COST>(s_strip, s_patch, lane);
             if (d <= dhi2) key = min(key, stereo_key(cq, d));
         }
         key = wave_min_u32(key);
@@ -119,13 +132,27 @@ __global__ __launch_bounds__(64) void k_stereo_depth(const uint8_t *__restrict__
     }
 }
 
+// cost: RELOC_STEREO_COST_*; with the census both planes go through k_census first, inside the same stopwatch bracket
 static int stereo_launch(reloc_ctx *ctx, const uint8_t *left, int lstride, const uint8_t *right, int rstride, const float *xy,
-                         const int32_t *count, int n_max, const StereoParams &p, uint16_t *mm, float *disp, uint8_t *status)
+                         const int32_t *count, int n_max, const StereoParams &p, int cost, uint16_t *mm, float *disp, uint8_t *status)
 {
+    if (cost)
+        if (int rc = stereo_census_alloc(ctx)) return rc;
     reloc_prof_begin(ctx, RELOC_PROF_STEREO);
-    hipLaunchKernelGGL(k_stereo_depth, dim3(n_max), dim3(64), 0, ctx->stream, left, lstride, right, rstride, xy, count, n_max, p, mm, disp, status);
+    if (cost) stereo_census_launch(ctx, left, lstride, right, rstride, p.w, p.h);
+    hipLaunchKernelGGL(cost ? k_stereo_depth<RELOC_STEREO_COST_CENSUS> : k_stereo_depth<RELOC_STEREO_COST_SAD>, dim3(n_max), dim3(64), 0,
+                       ctx->stream, left, lstride, right, rstride, xy, count, n_max, p, mm, disp, status);
     reloc_prof_end(ctx, RELOC_PROF_STEREO);
     HIP_TRY(hipGetLastError());
+    return RELOC_OK;
+}
+
+static int stereo_cost_check(int cost)
+{
+    if (cost != RELOC_STEREO_COST_SAD && cost != RELOC_STEREO_COST_CENSUS) {
+        reloc_set_error("bad argument: stereo cost %d outside 0..1", cost);
+        return RELOC_E_ARG;
+    }
     return RELOC_OK;
 }
 
@@ -162,10 +189,11 @@ static int stereo_sgm_args_check(const StereoSgm &g)
 }
 
 int stereo_call_check(const reloc_ctx *ctx, int w, int h, double fx, double baseline_m, int min_disparity, int num_disparities,
-                      int uniqueness, int lr_check, const StereoSgm *sgm)
+                      int uniqueness, int lr_check, int cost, const StereoSgm *sgm)
 {
     if (!(fx - fx == 0.0) || fx <= 0.0) { reloc_set_error("bad argument: stereo fx %g is not finite and > 0", fx); return RELOC_E_ARG; }
     if (int rc = stereo_args_check(baseline_m, min_disparity, num_disparities, uniqueness, lr_check, false)) return rc;
+    if (int rc = stereo_cost_check(cost)) return rc;
     if (sgm)
         if (int rc = stereo_sgm_args_check(*sgm)) return rc;
     if (w > ctx->max_w || h > ctx->max_h) { reloc_set_error("frame exceeds ctx capacity"); return RELOC_E_CAPACITY; }
@@ -235,6 +263,21 @@ RELOC_API int reloc_get_stereo_sgm(reloc_ctx *ctx, int32_t *paths, int32_t *p1, 
     return RELOC_OK;
 }
 
+RELOC_API int reloc_set_stereo_cost(reloc_ctx *ctx, int cost)
+{
+    ARG_CHECK_CTX(ctx, true, "reloc_set_stereo_cost");
+    if (int rc = stereo_cost_check(cost)) return rc;
+    ctx->stereo.cost = cost;
+    return RELOC_OK;
+}
+
+RELOC_API int reloc_get_stereo_cost(reloc_ctx *ctx, int32_t *cost)
+{
+    ARG_CHECK(ctx, "reloc_get_stereo_cost");
+    if (cost) *cost = ctx->stereo.cost;
+    return RELOC_OK;
+}
+
 void stereo_release(reloc_ctx *ctx)
 {
     StereoState &s = ctx->stereo;
@@ -244,13 +287,12 @@ void stereo_release(reloc_ctx *ctx)
     s.ran = false;
 }
 
-RELOC_API int reloc_stereo_depth(reloc_ctx *ctx, const uint8_t *left, const uint8_t *right, int w, int h, int stride, const float *xy,
-                                 int n, double fx, double baseline_m, int min_disparity, int num_disparities, int uniqueness,
-                                 int lr_check, uint16_t *depth_mm, float *disparity, uint8_t *status)
+// the stateless per-keypoint call: two gray planes of the caller's with one stride, explicit parameters
+static int stereo_sparse_call(reloc_ctx *ctx, const uint8_t *left, const uint8_t *right, int w, int h, int stride, const float *xy, int n,
+                              double fx, double baseline_m, int min_disparity, int num_disparities, int uniqueness, int lr_check, int cost,
+                              uint16_t *depth_mm, float *disparity, uint8_t *status)
 {
-    ARG_CHECK_CTX(ctx, left && right && w >= SP && h >= SP && stride >= w && n >= 0 && (n == 0 || (xy && depth_mm && disparity && status)),
-                  "reloc_stereo_depth");
-    if (int rc = stereo_call_check(ctx, w, h, fx, baseline_m, min_disparity, num_disparities, uniqueness, lr_check, nullptr)) return rc;
+    if (int rc = stereo_call_check(ctx, w, h, fx, baseline_m, min_disparity, num_disparities, uniqueness, lr_check, cost, nullptr)) return rc;
     if (n == 0) return RELOC_OK;
     // the planes go to the device as they lie at the caller's, padding included, and the kernel walks the caller's stride
     const int64_t bytes = (int64_t)(h - 1) * stride + w;
@@ -265,11 +307,31 @@ RELOC_API int reloc_stereo_depth(reloc_ctx *ctx, const uint8_t *left, const uint
     st.upload(dl, left, bytes);
     st.upload(dr, right, bytes);
     const StereoParams p = {fx, baseline_m, w, h, min_disparity, num_disparities, uniqueness, lr_check};
-    st.run([&] { return stereo_launch(ctx, dl, stride, dr, stride, dxy, nullptr, n, p, o_mm, o_disp, o_st); });
+    st.run([&] { return stereo_launch(ctx, dl, stride, dr, stride, dxy, nullptr, n, p, cost, o_mm, o_disp, o_st); });
     st.download(disparity, o_disp, (int64_t)n * 4);
     st.download(depth_mm, o_mm, (int64_t)n * 2);
     st.download(status, o_st, n);
     return st.finish();
+}
+
+RELOC_API int reloc_stereo_depth(reloc_ctx *ctx, const uint8_t *left, const uint8_t *right, int w, int h, int stride, const float *xy,
+                                 int n, double fx, double baseline_m, int min_disparity, int num_disparities, int uniqueness,
+                                 int lr_check, uint16_t *depth_mm, float *disparity, uint8_t *status)
+{
+    ARG_CHECK_CTX(ctx, left && right && w >= SP && h >= SP && stride >= w && n >= 0 && (n == 0 || (xy && depth_mm && disparity && status)),
+                  "reloc_stereo_depth");
+    return stereo_sparse_call(ctx, left, right, w, h, stride, xy, n, fx, baseline_m, min_disparity, num_disparities, uniqueness, lr_check,
+                              RELOC_STEREO_COST_SAD, depth_mm, disparity, status);
+}
+
+RELOC_API int reloc_stereo_depth_cost(reloc_ctx *ctx, const uint8_t *left, const uint8_t *right, int w, int h, int stride, const float *xy,
+                                      int n, double fx, double baseline_m, int min_disparity, int num_disparities, int uniqueness,
+                                      int lr_check, int cost, uint16_t *depth_mm, float *disparity, uint8_t *status)
+{
+    ARG_CHECK_CTX(ctx, left && right && w >= SP && h >= SP && stride >= w && n >= 0 && (n == 0 || (xy && depth_mm && disparity && status)),
+                  "reloc_stereo_depth_cost");
+    return stereo_sparse_call(ctx, left, right, w, h, stride, xy, n, fx, baseline_m, min_disparity, num_disparities, uniqueness, lr_check,
+                              cost, depth_mm, disparity, status);
 }
 
 int stereo_pair_check(reloc_ctx *ctx, reloc_ctx *right, int w, int h, int *ww, int *wh)
@@ -327,7 +389,7 @@ int stereo_frame(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img_right_dev,
     const OrbLevel &L0 = ctx->orb.tab.lev[0];       // level 0 of the pyramid is the chain's output (the blurred levels live in buf.blur)
     const StereoParams p = {ctx->cam.K4[0], s.baseline, *ww, *wh, s.min_disp, s.num_disp, s.uniq, s.lr};
     if (int rc = stereo_launch(ctx, ctx->orb.buf.pyr + L0.off, L0.stride, plane[1], stride[1], ctx->orb.buf.f_xy, ctx->orb.buf.f_count,
-                               ctx->max_feat, p, s.mm, s.disp, s.status)) return rc;
+                               ctx->max_feat, p, s.cost, s.mm, s.disp, s.status)) return rc;
     s.ran = true;
     return RELOC_OK;
 }

@@ -1,7 +1,9 @@
 // reloc_stereo_dense.hip -- dense stereo depth on gfx950 (include/reloc_spec.h, "STEREO, dense"): the specification of
 // reloc_stereo.hip's sparse matcher at every integer pixel, with the optional semi-global aggregation between costs and
 // selection (second half of this file; "STEREO, semi-global").  The decision per pixel is reloc_stereo_match.h's.
-//   k_stereo_dense<NP>     a workgroup of four waves takes DT_W output columns of one row, a wave 64 of them; lanes over
+//   k_stereo_dense<NP, VOL, COST>  (COST: SAD over gray planes, or the Hamming distance over the census planes of
+//                          reloc_census.hip -- "STEREO, census"; only the column cost differs)
+//                          a workgroup of four waves takes DT_W output columns of one row, a wave 64 of them; lanes over
 //                          disparities, NP = ceil(num_disparities / 64) of them per lane.  The 11 rows that the row's windows
 //                          cover are staged in LDS column by column: the 11 bytes of a column in three dwords (16 bytes per
 //                          column), so that the SAD of one column of the window -- 11 absolute differences -- is three
@@ -25,12 +27,15 @@
 constexpr int DT_W = 256;                                   // output columns of a workgroup
 constexpr int DT_L = DT_W + 2 * SR;                         // staged columns of the left eye
 constexpr int DT_R = DT_L + RELOC_STEREO_NUM_DISP_MAX;      // ... of the right eye, and words of the right map's piece
-constexpr uint16_t SGM_NONE = 0xFFFFu;   // an entry of the semi-global cost volume outside D(u): above every SAD cost (30 855)
+constexpr uint16_t SGM_NONE = 0xFFFFu;   // an entry of the semi-global cost volume outside D(u): above every SAD (30 855) and census cost (968)
 
 // the instantiation of a kernel template <int NP, ...> for np = ceil(num_disparities / 64) in 1 .. STEREO_PASSES
 #define STEREO_NP_KERNEL(np, kern, ...) \
     ((np) == 1 ? kern<1, ##__VA_ARGS__> : (np) == 2 ? kern<2, ##__VA_ARGS__> : (np) == 3 ? kern<3, ##__VA_ARGS__> : kern<4, ##__VA_ARGS__>)
 static_assert(STEREO_PASSES == 4, "STEREO_NP_KERNEL names every NP");
+// ... of k_stereo_dense<NP, vol, COST> for cost = RELOC_STEREO_COST_*
+#define STEREO_DENSE_KERNEL(np, vol, cost) \
+    ((cost) ? STEREO_NP_KERNEL(np, k_stereo_dense, vol, RELOC_STEREO_COST_CENSUS) : STEREO_NP_KERNEL(np, k_stereo_dense, vol, RELOC_STEREO_COST_SAD))
 
 // the bytes of column x, rows v - R .. v + R, in three dwords (row v - R in the low byte of .x)
 __device__ __forceinline__ uint4 stereo_pack_column(const uint8_t *__restrict__ img, int stride, int v, int x)
@@ -127,9 +132,24 @@ struct StereoTile {
     }
 };
 
+// the cost of one column of the window, 11 bytes in three dwords each: three v_sad_u8 over gray bytes, or, over census bytes
+// ("STEREO, census"), three xors and three v_bcnt with their addend
+template <int COST>
+__device__ __forceinline__ unsigned stereo_column_cost(const uint4 &lc, const uint4 &rc)
+{
+    if constexpr (COST == RELOC_STEREO_COST_CENSUS)
+        return (unsigned)__builtin_popcount(lc.x ^ rc.x) + (unsigned)__builtin_popcount(lc.y ^ rc.y) + (unsigned)__builtin_popcount(lc.z ^ rc.z);
+    else {
+        unsigned cs = __builtin_amdgcn_sad_u8(lc.x, rc.x, 0u);
+        cs = __builtin_amdgcn_sad_u8(lc.y, rc.y, cs);
+        return __builtin_amdgcn_sad_u8(lc.z, rc.z, cs);
+    }
+}
+
 // VOL: the volume pass of the semi-global matcher -- the same walk, but a pixel's costs go to vol[(v w + u) nd + k], k = d - dmin,
 // as uint16 (SGM_NONE beyond d_hi(u)) and nothing else is written: selection, right map and statuses follow from the sums.
-template <int NP, bool VOL>
+// COST: the planes are gray planes (SAD) or census planes; everything but the column cost is the same code.
+template <int NP, bool VOL, int COST>
 __global__ __launch_bounds__(256) void k_stereo_dense(const uint8_t *__restrict__ left, int lstride, const uint8_t *__restrict__ right,
                                                       int rstride, StereoParams p, uint32_t *__restrict__ rmap,
                                                       uint2 *__restrict__ o_best, uint8_t *__restrict__ o_status,
@@ -170,9 +190,7 @@ __global__ __launch_bounds__(256) void k_stereo_dense(const uint8_t *__restrict_
 #pragma unroll
                     for (int q = 0; q < NP; ++q) {
                         const uint4 rc = s_r[x + ebase - 64 * q];
-                        unsigned cs = __builtin_amdgcn_sad_u8(lc.x, rc.x, 0u);
-                        cs = __builtin_amdgcn_sad_u8(lc.y, rc.y, cs);
-                        cs = __builtin_amdgcn_sad_u8(lc.z, rc.z, cs);
+                        const unsigned cs = stereo_column_cost<COST>(lc, rc);
                         cost[q] += (int)cs - ring[q][k];
                         ring[q][k] = (int)cs;
                     }
@@ -378,11 +396,15 @@ static int stereo_sgm_alloc(reloc_ctx *ctx, int w, int h, int nd)
 // sgm == NULL: k_stereo_dense and k_stereo_dense_finish; else the semi-global pass: the volume, the paths of sgm->mask, the
 // selection over the sums and the same finish.  speckle: then the speckle stage with ctx's setting ("STEREO, speckle"), inside
 // the same stopwatch bracket.
+// cost: RELOC_STEREO_COST_*; with the census both planes go through k_census first, inside the same bracket, and the tile
+// kernels read the census planes.
 static int stereo_dense_launch(reloc_ctx *ctx, const uint8_t *left, int lstride, const uint8_t *right, int rstride, const StereoParams &p,
-                               bool speckle, const StereoSgm *sgm)
+                               int cost, bool speckle, const StereoSgm *sgm)
 {
     if (sgm)
         if (int rc = stereo_sgm_alloc(ctx, p.w, p.h, p.num_disp)) return rc;
+    if (cost)
+        if (int rc = stereo_census_alloc(ctx)) return rc;
     StereoState::Dense &d = ctx->stereo.dense;
     StereoState::Sgm &g = ctx->stereo.sgm;
     const int64_t px = (int64_t)p.w * p.h;
@@ -391,14 +413,15 @@ static int stereo_dense_launch(reloc_ctx *ctx, const uint8_t *left, int lstride,
     reloc_prof_begin(ctx, slot);
     hipError_t reset = sgm ? hipMemsetAsync(g.sum, 0, (size_t)(px * p.num_disp) * 4, ctx->stream) : hipSuccess;
     if (reset == hipSuccess && p.lr) reset = hipMemsetAsync(d.rmap, 0xFF, (size_t)px * 4, ctx->stream);      // KEY_NONE
+    if (cost) stereo_census_launch(ctx, left, lstride, right, rstride, p.w, p.h);
     if (!sgm) {
-        hipLaunchKernelGGL(STEREO_NP_KERNEL(np, k_stereo_dense, false), tiles, dim3(256), 0, ctx->stream, left, lstride, right, rstride, p,
+        hipLaunchKernelGGL(STEREO_DENSE_KERNEL(np, false, cost), tiles, dim3(256), 0, ctx->stream, left, lstride, right, rstride, p,
                            d.rmap, d.best, d.status, (uint16_t *)nullptr);
         hipLaunchKernelGGL(k_stereo_dense_finish<uint2>, pixels, dim3(256), 0, ctx->stream, p, d.rmap, d.best, d.status, d.mm, d.disp);
     } else {
         const int dw = p.w - 2 * SR - p.min_disp, dh = p.h - 2 * SR;
         const int ndirs = __builtin_popcount((unsigned)sgm->mask), diagonal = sgm->mask & 0xF0, lines = diagonal ? dw + dh - 1 : dw > dh ? dw : dh;
-        hipLaunchKernelGGL(STEREO_NP_KERNEL(np, k_stereo_dense, true), tiles, dim3(256), 0, ctx->stream, left, lstride, right, rstride, p,
+        hipLaunchKernelGGL(STEREO_DENSE_KERNEL(np, true, cost), tiles, dim3(256), 0, ctx->stream, left, lstride, right, rstride, p,
                            (uint32_t *)nullptr, (uint2 *)nullptr, (uint8_t *)nullptr, g.vol);
         if (dw > 0)                                                   // else no pixel has a disparity to search: the domain is empty
             hipLaunchKernelGGL(STEREO_NP_KERNEL(np, k_sgm_paths), dim3(lines, ndirs), dim3(64), 0, ctx->stream, g.vol, g.sum, p, sgm->mask,
@@ -418,10 +441,10 @@ static int stereo_dense_launch(reloc_ctx *ctx, const uint8_t *left, int lstride,
 
 // the stateless image call: two gray planes of the caller's with one stride, explicit parameters, the three planes back
 static int stereo_image(reloc_ctx *ctx, const uint8_t *left, const uint8_t *right, int w, int h, int stride, double fx, double baseline_m,
-                        int min_disparity, int num_disparities, int uniqueness, int lr_check, const StereoSgm *sgm, uint16_t *depth_mm,
-                        float *disparity, uint8_t *status)
+                        int min_disparity, int num_disparities, int uniqueness, int lr_check, int cost, const StereoSgm *sgm,
+                        uint16_t *depth_mm, float *disparity, uint8_t *status)
 {
-    if (int rc = stereo_call_check(ctx, w, h, fx, baseline_m, min_disparity, num_disparities, uniqueness, lr_check, sgm)) return rc;
+    if (int rc = stereo_call_check(ctx, w, h, fx, baseline_m, min_disparity, num_disparities, uniqueness, lr_check, cost, sgm)) return rc;
     if (int rc = stereo_dense_alloc(ctx)) return rc;
     if (sgm)
         if (int rc = stereo_sgm_alloc(ctx, w, h, num_disparities)) return rc;
@@ -433,7 +456,7 @@ static int stereo_image(reloc_ctx *ctx, const uint8_t *left, const uint8_t *righ
     st.upload(dl, left, bytes);
     st.upload(dr, right, bytes);
     const StereoParams p = {fx, baseline_m, w, h, min_disparity, num_disparities, uniqueness, lr_check};
-    st.run([&] { return stereo_dense_launch(ctx, dl, stride, dr, stride, p, false, sgm); });
+    st.run([&] { return stereo_dense_launch(ctx, dl, stride, dr, stride, p, cost, false, sgm); });
     st.download(depth_mm, d.mm, px * 2);
     if (disparity) st.download(disparity, d.disp, px * 4);
     if (status) st.download(status, d.status, px);
@@ -445,8 +468,8 @@ RELOC_API int reloc_stereo_depth_image(reloc_ctx *ctx, const uint8_t *left, cons
                                        uint16_t *depth_mm, float *disparity, uint8_t *status)
 {
     ARG_CHECK_CTX(ctx, left && right && depth_mm && w >= SP && h >= SP && stride >= w, "reloc_stereo_depth_image");
-    return stereo_image(ctx, left, right, w, h, stride, fx, baseline_m, min_disparity, num_disparities, uniqueness, lr_check, nullptr, depth_mm,
-                        disparity, status);
+    return stereo_image(ctx, left, right, w, h, stride, fx, baseline_m, min_disparity, num_disparities, uniqueness, lr_check,
+                        RELOC_STEREO_COST_SAD, nullptr, depth_mm, disparity, status);
 }
 
 RELOC_API int reloc_stereo_sgm_image(reloc_ctx *ctx, const uint8_t *left, const uint8_t *right, int w, int h, int stride, double fx,
@@ -455,8 +478,18 @@ RELOC_API int reloc_stereo_sgm_image(reloc_ctx *ctx, const uint8_t *left, const 
 {
     ARG_CHECK_CTX(ctx, left && right && depth_mm && w >= SP && h >= SP && stride >= w, "reloc_stereo_sgm_image");
     const StereoSgm sgm = {path_mask, p1, p2};
-    return stereo_image(ctx, left, right, w, h, stride, fx, baseline_m, min_disparity, num_disparities, uniqueness, lr_check, &sgm, depth_mm,
-                        disparity, status);
+    return stereo_image(ctx, left, right, w, h, stride, fx, baseline_m, min_disparity, num_disparities, uniqueness, lr_check,
+                        RELOC_STEREO_COST_SAD, &sgm, depth_mm, disparity, status);
+}
+
+RELOC_API int reloc_stereo_image_cost(reloc_ctx *ctx, const uint8_t *left, const uint8_t *right, int w, int h, int stride, double fx,
+                                      double baseline_m, int min_disparity, int num_disparities, int uniqueness, int lr_check, int cost,
+                                      int path_mask, int p1, int p2, uint16_t *depth_mm, float *disparity, uint8_t *status)
+{
+    ARG_CHECK_CTX(ctx, left && right && depth_mm && w >= SP && h >= SP && stride >= w, "reloc_stereo_image_cost");
+    const StereoSgm sgm = {path_mask, p1, p2};
+    return stereo_image(ctx, left, right, w, h, stride, fx, baseline_m, min_disparity, num_disparities, uniqueness, lr_check, cost,
+                        path_mask ? &sgm : nullptr, depth_mm, disparity, status);
 }
 
 RELOC_API int reloc_stereo_sgm_debug(reloc_ctx *ctx, uint32_t *S, int32_t *w, int32_t *h, int32_t *nd)
@@ -489,7 +522,7 @@ int stereo_dense_frame(reloc_ctx *ctx, reloc_ctx *right, int w, int h, int order
     if (int rc = stereo_gray_planes(ctx, right, ctx->frame_img, right->frame_img, w, h, *ww, *wh, order, plane, pstride)) return rc;
     const StereoParams p = {ctx->cam.K4[0], s.baseline, *ww, *wh, s.min_disp, s.num_disp, s.uniq, s.lr};
     const StereoSgm sgm = {s.sgm_paths == 4 ? 0x0F : 0xFF, s.sgm_p1, s.sgm_p2};
-    return stereo_dense_launch(ctx, plane[0], pstride[0], plane[1], pstride[1], p, s.speckle_window > 0, s.sgm_paths ? &sgm : nullptr);
+    return stereo_dense_launch(ctx, plane[0], pstride[0], plane[1], pstride[1], p, s.cost, s.speckle_window > 0, s.sgm_paths ? &sgm : nullptr);
 }
 
 RELOC_API int reloc_stereo_frame_depth(reloc_ctx *ctx, reloc_ctx *right, const uint8_t *img, const uint8_t *img_right, int w, int h,

@@ -41,6 +41,7 @@ def match_policy_setting(policy, ratio):
     return name, r
 
 
+STEREO_COSTS = ("sad", "census")                  # RELOC_STEREO_COST_* of include/reloc_spec.h, by value
 ROUTE_PREDICATES = {"clearance": 0, "cost": 1}      # RELOC_ROUTE_PRED_* of include/reloc_spec.h
 
 MAX_CAND = 32           # candidates of one tick (MAX_CAND of csrc/reloc_internal.h): the longest top-k / candidate list
@@ -576,18 +577,30 @@ class Engine:
             left = np.ascontiguousarray(left); right = np.ascontiguousarray(right)
         return left, right
 
+    @staticmethod
+    def _stereo_cost(cost, what):
+        """RELOC_STEREO_COST_* of a cost keyword"""
+        if cost not in STEREO_COSTS:
+            raise N.RelocError(f"{what}: cost must be one of {', '.join(STEREO_COSTS)}")
+        return STEREO_COSTS.index(cost)
+
     def stereo_depth(self, left: np.ndarray, right: np.ndarray, xy, fx: float, baseline_m: float, min_disparity: int = 0,
-                     num_disparities: int = 128, uniqueness: int = 15, lr_check: bool = True):
+                     num_disparities: int = 128, uniqueness: int = 15, lr_check: bool = True, cost: str = "sad"):
         """(depth_mm (n,) uint16, disparity (n,) float32, status (n,) uint8) of the keypoints xy (n, 2) on two rectified (H, W)
-        uint8 planes with explicit parameters (reloc_stereo_depth); the planes may be row-strided views of one stride"""
+        uint8 planes with explicit parameters (reloc_stereo_depth); the planes may be row-strided views of one stride.
+        cost: "sad" or "census" (reloc_stereo_depth_cost; "STEREO, census")"""
         left, right = self._stereo_planes(left, right, "stereo_depth")
+        c = self._stereo_cost(cost, "stereo_depth")
         h, w = left.shape
         xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
         n = len(xy)
         mm = np.zeros(n, np.uint16); disp = np.zeros(n, np.float32); st = np.zeros(n, np.uint8)
-        self._api.reloc_stereo_depth(self._ctx, left.ctypes.data, right.ctypes.data, w, h, left.strides[0], xy, n, float(fx),
-                                     float(baseline_m), int(min_disparity), int(num_disparities), int(uniqueness),
-                                     int(bool(lr_check)), mm, disp, st)
+        head = (self._ctx, left.ctypes.data, right.ctypes.data, w, h, left.strides[0], xy, n, float(fx), float(baseline_m),
+                int(min_disparity), int(num_disparities), int(uniqueness), int(bool(lr_check)))
+        if c:
+            self._api.reloc_stereo_depth_cost(*head, c, mm, disp, st)
+        else:
+            self._api.reloc_stereo_depth(*head, mm, disp, st)
         return mm, disp, st
 
     def record_frame_stereo(self, bgr: np.ndarray, right_frame: np.ndarray, right_engine: "Engine", nfeatures: int = 500,
@@ -619,17 +632,50 @@ class Engine:
 
     # ------------------------------------------------------------------ dense stereo depth (reloc_spec.h "STEREO, dense")
     def stereo_depth_image(self, left: np.ndarray, right: np.ndarray, fx: float, baseline_m: float, min_disparity: int = 0,
-                           num_disparities: int = 128, uniqueness: int = 15, lr_check: bool = True):
+                           num_disparities: int = 128, uniqueness: int = 15, lr_check: bool = True, cost: str = "sad"):
         """(depth_mm uint16, disparity float32, status uint8), each (H, W): the depth of every pixel of two rectified (H, W)
         uint8 planes with explicit parameters (reloc_stereo_depth_image), what stereo_depth gives for a keypoint there; the
-        planes may be row-strided views of one stride"""
+        planes may be row-strided views of one stride.  cost: "sad" or "census" (reloc_stereo_image_cost; "STEREO, census")"""
         left, right = self._stereo_planes(left, right, "stereo_depth_image")
+        c = self._stereo_cost(cost, "stereo_depth_image")
         h, w = left.shape
         mm = np.zeros((h, w), np.uint16); disp = np.zeros((h, w), np.float32); st = np.zeros((h, w), np.uint8)
-        self._api.reloc_stereo_depth_image(self._ctx, left.ctypes.data, right.ctypes.data, w, h, left.strides[0], float(fx),
-                                           float(baseline_m), int(min_disparity), int(num_disparities), int(uniqueness),
-                                           int(bool(lr_check)), mm, disp, st)
+        head = (self._ctx, left.ctypes.data, right.ctypes.data, w, h, left.strides[0], float(fx), float(baseline_m),
+                int(min_disparity), int(num_disparities), int(uniqueness), int(bool(lr_check)))
+        if c:
+            self._api.reloc_stereo_image_cost(*head, c, 0, 0, 0, mm, disp, st)
+        else:
+            self._api.reloc_stereo_depth_image(*head, mm, disp, st)
         return mm, disp, st
+
+    # ------------------------------------------------------------------ census cost (reloc_spec.h "STEREO, census")
+    def set_stereo_cost(self, cost: str | int = "sad"):
+        """the data term of this (the left eye's) engine's stereo passes (reloc_set_stereo_cost): "sad" (0) or "census" (1),
+        the Hamming distance of 8-bit census transforms, for pairs whose eyes are exposed unequally"""
+        if isinstance(cost, str):
+            cost = self._stereo_cost(cost, "set_stereo_cost")
+        elif int(cost) != cost:
+            raise N.RelocError("set_stereo_cost: cost must be a name or an integer")
+        self._api.reloc_set_stereo_cost(self._ctx, int(cost))
+
+    def get_stereo_cost(self) -> int:
+        """0 = SAD, 1 = census (STEREO_COSTS names them)"""
+        cost = i32()
+        self._api.reloc_get_stereo_cost(self._ctx, cost)
+        return cost.value
+
+    def census(self, gray: np.ndarray) -> np.ndarray:
+        """the census transform of an (H, W) uint8 plane (reloc_census): (H, W) uint8, bit k set where the k-th of the eight
+        samples at radius 2 is darker than the pixel; rows may be strided, the padding is not read"""
+        gray = np.asarray(gray)
+        if gray.dtype != np.uint8 or gray.ndim != 2 or gray.size == 0:
+            raise N.RelocError("census: expected a non-empty (H, W) uint8 plane")
+        h, w = gray.shape
+        if gray.strides[1] != 1 or (h > 1 and gray.strides[0] < w):
+            gray = np.ascontiguousarray(gray)
+        out = np.zeros((h, w), np.uint8)
+        self._api.reloc_census(self._ctx, gray.ctypes.data, w, h, w if h == 1 else gray.strides[0], out)
+        return out
 
     def _stereo_pair(self, frame, right_frame, right_engine, what):
         """both eyes' frames of a host-pointer stereo call, each checked against its own engine's chain, and their size"""
@@ -733,11 +779,13 @@ class Engine:
 
     def stereo_sgm_image(self, left: np.ndarray, right: np.ndarray, fx: float, baseline_m: float, min_disparity: int = 0,
                          num_disparities: int = 128, uniqueness: int = 15, lr_check: bool = True, paths: int = 8, p1: int = 968,
-                         p2: int = 3872, path_mask: int | None = None):
+                         p2: int = 3872, path_mask: int | None = None, cost: str = "sad"):
         """stereo_depth_image with the costs aggregated semi-globally (reloc_stereo_sgm_image): (depth_mm uint16, disparity
         float32, status uint8), each (H, W).  paths: 4 or 8; path_mask (1..255, bit b = direction b of the specification)
-        overrides it.  The sum volume of the pass stays on the device (stereo_sgm_volume)."""
+        overrides it.  The sum volume of the pass stays on the device (stereo_sgm_volume).  cost: "sad" or "census"
+        (reloc_stereo_image_cost; p1, p2 are the caller's either way -- 121 / 484 suit census costs)."""
         left, right = self._stereo_planes(left, right, "stereo_sgm_image")
+        c = self._stereo_cost(cost, "stereo_sgm_image")
         if path_mask is None:
             if paths not in (4, 8):
                 raise N.RelocError("stereo_sgm_image: paths must be 4 or 8 (or give path_mask)")
@@ -747,9 +795,14 @@ class Engine:
                 raise N.RelocError(f"stereo_sgm_image: {name} must be an integer")
         h, w = left.shape
         mm = np.zeros((h, w), np.uint16); disp = np.zeros((h, w), np.float32); st = np.zeros((h, w), np.uint8)
-        self._api.reloc_stereo_sgm_image(self._ctx, left.ctypes.data, right.ctypes.data, w, h, left.strides[0], float(fx),
-                                         float(baseline_m), int(min_disparity), int(num_disparities), int(uniqueness),
-                                         int(bool(lr_check)), int(path_mask), int(p1), int(p2), mm, disp, st)
+        head = (self._ctx, left.ctypes.data, right.ctypes.data, w, h, left.strides[0], float(fx), float(baseline_m),
+                int(min_disparity), int(num_disparities), int(uniqueness), int(bool(lr_check)))
+        if c:
+            if not 1 <= int(path_mask) <= 255:      # the cost twin reads mask 0 as "no aggregation"
+                raise N.RelocError("stereo_sgm_image: path_mask must lie in 1..255")
+            self._api.reloc_stereo_image_cost(*head, c, int(path_mask), int(p1), int(p2), mm, disp, st)
+        else:
+            self._api.reloc_stereo_sgm_image(*head, int(path_mask), int(p1), int(p2), mm, disp, st)
         return mm, disp, st
 
     def stereo_sgm_volume(self) -> np.ndarray:

@@ -11,6 +11,7 @@
     the first two, for a rectified stereo pair without a depth sensor:
                                                         [--stereo-baseline M --stereo-num-disparities N
                                                          --stereo-sgm-paths {0,4,8} --stereo-sgm-p1 N --stereo-sgm-p2 N
+                                                         --stereo-cost {sad,census}
                                                          --stereo-rectify-right FILE.npz --right-topic NAME]
 
 (reference simulation/isaac/scripts/common/visual_landmark_matcher.py:175-231,503-530,
@@ -29,7 +30,7 @@ import numpy as np
 from .front_end import PIXEL_FORMATS, add_front_end_flags, front_end_flags, load_mask, pixel_format_setting  # noqa: F401  (load_mask: part of this module's interface)
 from .matcher import FusedLandmarkMatcher, LandmarkMatcherCore, MatcherConfig
 from .recorder import LandmarkRecorderCore
-from .stereo import SGM_P1_DEFAULT, SGM_P2_DEFAULT, StereoRig
+from .stereo import COSTS, SGM_P1_DEFAULT, SGM_P2_DEFAULT, StereoRig
 
 RIGHT_TOPIC = "/camera/right/image_raw"      # --right-topic: the right eye of a stereo rig (--stereo-baseline)
 TICK_HZ = 2.0
@@ -403,8 +404,13 @@ def _chain_args(args):
     return tuple(tail)
 
 
+class _FollowsCost(int):
+    """the value of --stereo-sgm-p1 / -p2 while the flag is not given: it reads as the SAD default and tells _stereo_kwargs to
+    leave the penalty to the rig, which takes the default of its cost"""
+
+
 def add_stereo_flags(ap):
-    """--stereo-baseline, --stereo-num-disparities, --stereo-rectify-right, --stereo-sgm-*, --right-topic: a StereoRig beside the
+    """--stereo-baseline, --stereo-num-disparities, --stereo-rectify-right, --stereo-sgm-*, --stereo-cost, --right-topic: a StereoRig beside the
     front end"""
     ap.add_argument("--stereo-baseline", type=float, default=None, metavar="M",
                     help="baseline of a rectified stereo pair in metres: the right eye's frames stand in for the depth image")
@@ -413,8 +419,12 @@ def add_stereo_flags(ap):
                     help="the right eye's rectification maps: an .npz file holding map1 and map2 as cv2.remap takes them")
     ap.add_argument("--stereo-sgm-paths", type=int, default=0, choices=(0, 4, 8), metavar="{0,4,8}",
                     help="semi-global aggregation of the dense stereo pass along 4 or 8 directions (default 0: off)")
-    ap.add_argument("--stereo-sgm-p1", type=int, default=SGM_P1_DEFAULT, metavar="N", help=f"its penalty of a disparity step of one (default {SGM_P1_DEFAULT})")
-    ap.add_argument("--stereo-sgm-p2", type=int, default=SGM_P2_DEFAULT, metavar="N", help=f"its penalty of a larger step, p1..8191 (default {SGM_P2_DEFAULT})")
+    ap.add_argument("--stereo-sgm-p1", type=int, default=_FollowsCost(SGM_P1_DEFAULT), metavar="N",
+                    help=f"its penalty of a disparity step of one (default {SGM_P1_DEFAULT}; 121 with --stereo-cost census)")
+    ap.add_argument("--stereo-sgm-p2", type=int, default=_FollowsCost(SGM_P2_DEFAULT), metavar="N",
+                    help=f"its penalty of a larger step, p1..8191 (default {SGM_P2_DEFAULT}; 484 with --stereo-cost census)")
+    ap.add_argument("--stereo-cost", default="sad", choices=COSTS,
+                    help="data term of the stereo matchers: sad, or census for eyes with their own exposure and gain (default sad)")
     ap.add_argument("--right-topic", default=RIGHT_TOPIC, metavar="NAME", help="topic of the right eye's frames")
 
 
@@ -426,8 +436,9 @@ def _stereo_kwargs(args):
     if args.stereo_rectify_right is not None:
         with np.load(args.stereo_rectify_right, allow_pickle=False) as z:
             maps = (z["map1"], z["map2"])
+    p1, p2 = (None if isinstance(v, _FollowsCost) else v for v in (args.stereo_sgm_p1, args.stereo_sgm_p2))
     return dict(stereo=StereoRig(args.stereo_baseline, num_disparities=args.stereo_num_disparities, rectify_right=maps,
-                                 sgm_paths=args.stereo_sgm_paths, sgm_p1=args.stereo_sgm_p1, sgm_p2=args.stereo_sgm_p2),
+                                 sgm_paths=args.stereo_sgm_paths, sgm_p1=p1, sgm_p2=p2, cost=args.stereo_cost),
                 right_topic=args.right_topic)
 
 

@@ -21,6 +21,8 @@ SPECKLE_RANGE_MAX = 255                   # RELOC_STEREO_SPECKLE_RANGE_MAX
 SPECKLE_NONE = -16                        # the quantised disparity of a pixel without one ("STEREO, speckle")
 SGM_PATHS = (0, 4, 8)                     # reloc_set_stereo_sgm: off, mask 0x0F, mask 0xFF
 SGM_P1_DEFAULT, SGM_P2_DEFAULT, SGM_P2_MAX = 968, 3872, 8191      # RELOC_STEREO_SGM_*
+COSTS = ("sad", "census")                 # RELOC_STEREO_COST_SAD, _CENSUS
+SGM_PENALTY_DEFAULTS = {"sad": (SGM_P1_DEFAULT, SGM_P2_DEFAULT), "census": (121, 484)}      # ... and RELOC_STEREO_SGM_P*_CENSUS_DEFAULT
 
 
 @dataclass(frozen=True, eq=False)
@@ -35,7 +37,10 @@ class StereoRig:
     neighbours differ by at most speckle_range disparities lose their depth; 0 = off.  The sparse per-keypoint depth has no
     neighbourhood and is not filtered.  sgm_paths, sgm_p1, sgm_p2: semi-global aggregation of the dense pass ("STEREO,
     semi-global") along 4 or 8 directions with the penalties 0 <= sgm_p1 <= sgm_p2 <= 8191; 0 paths = off.  It is this
-    project's matcher over its SAD costs, not OpenCV's StereoSGBM, and the sparse per-keypoint depth does not use it."""
+    project's matcher over its own costs, not OpenCV's StereoSGBM, and the sparse per-keypoint depth does not use it; a
+    penalty left None takes the default of the rig's cost (968 / 3872 over SAD costs, 121 / 484 over census costs).  cost: the
+    data term of every pass ("STEREO, census") -- "sad", the sum of absolute gray differences, or "census", the Hamming
+    distance of 8-bit census transforms, for eyes with their own exposure, gain or vignetting."""
     baseline_m: float
     min_disparity: int = 0
     num_disparities: int = 128
@@ -45,10 +50,16 @@ class StereoRig:
     speckle_window: int = 0
     speckle_range: int = 1
     sgm_paths: int = 0
-    sgm_p1: int = SGM_P1_DEFAULT
-    sgm_p2: int = SGM_P2_DEFAULT
+    sgm_p1: int | None = None
+    sgm_p2: int | None = None
+    cost: str = "sad"
 
     def __post_init__(self):
+        if self.cost not in COSTS:
+            raise ValueError("stereo: cost must be 'sad' or 'census'")
+        for name, default in zip(("sgm_p1", "sgm_p2"), SGM_PENALTY_DEFAULTS[self.cost]):
+            if getattr(self, name) is None:
+                object.__setattr__(self, name, default)
         b = float(self.baseline_m)
         if not (np.isfinite(b) and b > 0.0):
             raise ValueError("stereo: baseline_m must be finite and > 0 (metres)")
@@ -77,9 +88,11 @@ class StereoRig:
         return replace(front_end, rectify=self.rectify_right)
 
     def configure(self, engine):
-        """the rig's setting on the left eye's Engine; the speckle stage and the semi-global aggregation only where the rig
-        has them"""
+        """the rig's setting on the left eye's Engine; the speckle stage, the semi-global aggregation and the census cost only
+        where the rig has them"""
         engine.set_stereo(**self.settings())
+        if self.cost != "sad":
+            engine.set_stereo_cost(self.cost)
         if self.speckle_window:
             engine.set_stereo_speckle(self.speckle_window, self.speckle_range)
         if self.sgm_paths:
@@ -95,20 +108,33 @@ class StereoRig:
 
     def keypoint_depth_mm(self, backend, left_gray, right_gray, xy, fx):
         """uint16 millimetres per keypoint (0 = no depth) from two planes of the chain's output through the backend's kernel"""
-        return backend.stereo_depth(left_gray, right_gray, xy, fx, **self.settings())[0]
+        return backend.stereo_depth(left_gray, right_gray, xy, fx, **self.settings(), **self._cost_keyword(backend, "stereo_depth"))[0]
+
+    def _cost_keyword(self, backend, call):
+        """{} for a SAD rig (today's call), else the cost keyword of the backend's call; a backend whose call takes none (the
+        CPU oracle) is refused"""
+        if self.cost == "sad":
+            return {}
+        import inspect
+        fn = getattr(backend, call, None)
+        if fn is None or "cost" not in inspect.signature(fn).parameters:
+            raise ValueError(f"stereo: this backend's {call} takes no cost (cost must be 'sad' on it)")
+        return dict(cost=self.cost)
 
     def depth_image(self, backend, left_gray, right_gray, fx):
         """the (H, W) uint16 depth image, millimetres, 0 = no depth, of two planes of the chain's output through the backend's
         dense kernel; with a speckle window, then the stage from public pieces: the quantised disparity in NumPy, the
         backend's filter_speckles, the depth zeroed where the filter removed a pixel.  With sgm_paths the backend's
-        semi-global entry takes the dense kernel's place; a backend without one (the CPU oracle) is refused."""
+        semi-global entry takes the dense kernel's place; a backend without one (the CPU oracle) is refused, and so is one
+        whose calls take no cost under a census rig."""
         if self.sgm_paths:
             if not hasattr(backend, "stereo_sgm_image"):
                 raise ValueError("stereo: this backend has no semi-global aggregation (sgm_paths must be 0 on it)")
             mm, disp, status = backend.stereo_sgm_image(left_gray, right_gray, fx, **self.settings(), paths=self.sgm_paths,
-                                                        p1=self.sgm_p1, p2=self.sgm_p2)
+                                                        p1=self.sgm_p1, p2=self.sgm_p2, **self._cost_keyword(backend, "stereo_sgm_image"))
         else:
-            mm, disp, status = backend.stereo_depth_image(left_gray, right_gray, fx, **self.settings())
+            mm, disp, status = backend.stereo_depth_image(left_gray, right_gray, fx, **self.settings(),
+                                                          **self._cost_keyword(backend, "stereo_depth_image"))
         if not self.speckle_window:
             return mm
         ok = np.asarray(status) == 0
